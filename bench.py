@@ -77,6 +77,9 @@ def parse_args():
                     help="do not measure roofline.traffic in this run (two rocprofv3 --pmc passes of a short child run); use profiles/traffic.json")
     ap.add_argument("--no-extras", action="store_true", help="skip the side measurements (stated-size configs, H2D-inclusive rate)")
     ap.add_argument("--probe-reps", type=int, default=20, help="passes of the bare read probe before and after the timed steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (the merged state: counters and sums) "
+                         "as DIR/<name>.npy in float64, so that two builds can be compared output for output")
     ap.add_argument("--calib-copy", action="store_true",
                     help="(child runs of measure_traffic) one 1 GiB device-to-device copy first: the counter pass calibrates its bytes-per-count on it")
     return ap.parse_args()
@@ -384,6 +387,24 @@ def measure_traffic(a, rows):
     return b, note, raw
 
 
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(d, arrays):
+    """--dump-outputs: each array as <d>/<name>.npy in float64 (int64 counters up to 2^53 stay exact).  An array beyond its share of
+    the 64 MB budget is written as a fixed, seeded sample of its elements, in index order, with the indexes as <name>_index.npy."""
+    os.makedirs(d, exist_ok=True)
+    share = DUMP_BUDGET_BYTES // max(1, len(arrays))
+    for name, x in arrays.items():
+        x = np.asarray(x).reshape(-1).astype(np.float64)
+        if x.nbytes > share:
+            keep = share // 16  # the sample and its int64 indexes
+            idx = np.sort(np.random.default_rng(12345).choice(x.size, keep, replace=False))
+            np.save(os.path.join(d, f"{name}_index.npy"), idx.astype(np.int64))
+            x = x[idx]
+        np.save(os.path.join(d, f"{name}.npy"), x)
+
+
 def time_config(ctx, kind, rows, steps=50, warmup=5):
     """A config at the size BASELINE.json states it (c2 @ 1e7, c3 @ 1e8): (ms per step, kernel ms, roofline fraction)."""
     wl = Workload(ctx, kind, rows, 0, rows)
@@ -452,6 +473,8 @@ def main():
     a = parse_args()
     if a.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if a.steps < 1:
+        raise SystemExit("--steps must be >= 1")
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         self_launch(a)
     rank = int(os.environ.get("RANK", 0))
@@ -624,6 +647,9 @@ def main():
     final = merged.cpu()
     counts = final[:wl.n_i64].numpy()
     sums = final[wl.n_i64:].view(torch.float64).numpy() if wl.n_f64 else None
+
+    if rank == 0 and a.dump_outputs:
+        dump_outputs(a.dump_outputs, {"counts": counts} if sums is None else {"counts": counts, "sums": sums})
 
     if rank == 0:
         ms_per_step = elapsed / a.steps * 1e3

@@ -1,5 +1,6 @@
 """The native collectives fail TOGETHER and never hang: exon_hip_stream_reconcile_keys and
-exon_hip_stream_all_reduce with 2 and 8 ranks that share cuda:0.  RCCL refuses several ranks on one device, so the communicator is the
+exon_hip_stream_all_reduce with 2 and 4 ranks that share cuda:0 (at most four, so that with the test process no more than five
+processes hold the device).  RCCL refuses several ranks on one device, so the communicator is the
 library's callback kind (exon_hip_comm_from_callbacks) over gloo: the vote / reconcile / merge logic under test is the same C++ the
 RCCL kind runs, only the bytes travel through torch.distributed.  EXON_HIP_FAULT=site@rank makes one rank fail at a named site; every
 rank must come back with the same status within seconds.  What AggregateExec(Final) over file groups does in the reference:
@@ -53,7 +54,7 @@ try:
 except exon_amd.ExonHipError as e:
     out.update(ok=False, code=e.code, text=str(e))
 out["seconds"] = time.time() - t0
-with open(os.path.join(sys.argv[5], f"rank{rank}.json"), "w") as fh:  # (stdout of 8 ranks interleaves)
+with open(os.path.join(sys.argv[5], f"rank{rank}.json"), "w") as fh:  # (stdout of several ranks interleaves)
     json.dump(out, fh)
 try:
     dist.barrier()
@@ -93,7 +94,7 @@ def files(tmp_path, world):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("world", [2, 8])
+@pytest.mark.parametrize("world", [2, 4])
 def test_native_reconcile_and_merge_over_n_ranks(tmp_path, oracle, world):
     """no fault: the native path end to end -- every rank ends with the same keys and the same state, equal to the oracle over the
     one concatenated table"""
@@ -110,7 +111,7 @@ def test_native_reconcile_and_merge_over_n_ranks(tmp_path, oracle, world):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("world", [2, 8])
+@pytest.mark.parametrize("world", [2, 4])
 @pytest.mark.parametrize("fault,code", [("reconcile_enter@1", -5), ("reconcile_malloc@1", -2), ("reconcile_rekey@1", -2), ("allreduce_enter@1", -5),
                                         ("allreduce_malloc@1", -2)])
 def test_a_fault_on_one_rank_fails_every_rank_together(tmp_path, world, fault, code):
@@ -125,7 +126,7 @@ def test_a_fault_on_one_rank_fails_every_rank_together(tmp_path, world, fault, c
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("world", [2, 8])
+@pytest.mark.parametrize("world", [2, 4])
 def test_real_refusals_fail_together_too(tmp_path, world):
     """(a) a rank whose stream has finished; (b) nobody reconciled: states keyed by rank-local dictionaries; (c) the union of the
     dictionaries exceeds n_groups -- every rank gets the same status, none hangs"""

@@ -175,8 +175,6 @@ def test_k6_no_bitmaps_boundaries_and_accumulate(ctx, oracle):
 @pytest.mark.parametrize("n", [1, 4097, 1_000_001, 20_000_000])
 @pytest.mark.parametrize("mask,value,qmin", [(1284, 0, 30), (4, 4, 0), (0x10, 0x10, 60), (0, 0, -5), (1, 0, 0)])
 def test_k3_flag_mapq_group_count(ctx, oracle, n, mask, value, qmin):
-    if n > 2_000_000 and (mask, value, qmin) != (1284, 0, 30):
-        pytest.skip("large size only for the config-3 predicate")
     refs = oracle.c3_refs()
     f, mq, mv, ref, rv = ctx.gen_c3(3, 0, n)
     d = ctx.zeros(np.int64, len(refs) + 1)
