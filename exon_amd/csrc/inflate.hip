@@ -8,20 +8,20 @@
 // (<= 64 KiB of text each), so a slab of compressed blocks crosses PCIe as it is (3-5x fewer bytes than text) and
 // is inflated by one wavefront per block.
 //
-// One wavefront per block (k_inflate_w / k_inflate, one wavefront per workgroup, 4928 B of static LDS, 64 VGPRs, <= 79 SGPRs -> 32
-// members per CU):
+// One wavefront per block in the serial kernel k_inflate_w (one wavefront per workgroup, 4928 B of static LDS, 64 VGPRs, <= 79
+// SGPRs -> 32 members per CU):
 //   * Huffman tables live in LDS: a 9-bit (literal/length) and an 8-bit (distance) first-level table whose entries are complete
 //     decode results (literal byte / length or distance base + extra-bit count + code length), built lane-parallel from the code
 //     lengths (ballot ranks give the canonical codes); per-length first-code / count / offset arrays serve the longer codes;
 //   * the last 1 KiB of output stays in an LDS ring: literals and near matches are LDS stores / LDS->LDS copies, farther matches
 //     read the output already drained to HBM; the ring is drained in aligned 256-byte rows, one dword per lane;
-//   * the symbol loop (round 5, default): wide_run -- 64 lanes decode the symbols that would start at 64 consecutive BIT offsets,
+//   * the symbol loop: wide_run -- 64 lanes decode the symbols that would start at 64 consecutive BIT offsets,
 //     the true chain is followed with one v_readlane per symbol and the round's output (<= 64 bytes) is produced in one step;
 //     its ordinary rounds are hand-written (wide_rounds_asm), and so are the common rare ones: literal and distance codes longer than
 //     the tables are decoded inside the walk, a match that overlaps its own output takes its sources whole periods back, a round
-//     ends in front of a symbol that starts beyond its 64 bytes.  Rounds 1-4's loops -- one symbol per step on the scalar unit
-//     (symbol_run), on the vector unit with software pipelining (symbol_run_v) -- stay selectable (EXON_HIP_INFLATE_FLAVOR=0|1|2)
-//     and serve the lane-parallel kernel's hand-backs.  Tuning logs: profiles/r1_tuning.md ... HISTORY.md section 7e.
+//     ends in front of a symbol that starts beyond its 64 bytes.
+// The lane-parallel kernel k_inflate_par decodes a DEFLATE block speculatively from 64 bit offsets at once (par_decode_block)
+// and hands the blocks it cannot finish to a one-symbol-per-step loop on the vector unit with software pipelining (symbol_run_v).
 // Every block reports a status; any failure makes the caller inflate on the host instead.  The CRC-32 of every
 // inflated block is checked by a second kernel (k_crc32: 64 slices per block, combined in GF(2)[x] mod P with powers of x from a table).
 #include <hip/hip_runtime.h>
@@ -47,9 +47,6 @@ constexpr int LIT_BITS = EXON_LIT_BITS, DIST_BITS = EXON_DIST_BITS, CL_BITS = 7;
 constexpr int WAVES_PER_WG = 4;     // k_crc32
 #ifndef EXON_INFLATE_RING
 #define EXON_INFLATE_RING 2048
-#endif
-#ifndef EXON_INFLATE_LIT
-#define EXON_INFLATE_LIT 2  // symbol loop: 0 = the compiler's (readable reference), 1 = literal_run, 2 = symbol_run
 #endif
 constexpr int INFLATE_RING = EXON_INFLATE_RING;  // bytes of recent output kept in LDS per wavefront (k_inflate_par: also its window)
 // The serial kernel's ring is 1 KiB since round 4: 1024 + 3840 bytes of LDS per member are under the 5120-byte tier that lets a
@@ -509,238 +506,15 @@ __device__ __forceinline__ uint32_t lds_addr(const void* p) {
   return (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) void*)p;
 }
 
-// The literal loop, hand-written: refill -> first-level lookup -> store -> next in 22 instructions per literal (the
-// compiler's version of the same loop, EXON_INFLATE_LIT=0: 26, with two more taken branches).  Table index and ring
-// address are computed on the vector ALU, the row check rides on the SCC of s_and.  Worth +2 % (VCF text), +5 % (BAM),
-// +13 % (FASTQ) on the same box; a batched variant (one lookup for all 64 bit offsets, the chain of literals followed
-// with v_readlane) was no faster on literal-heavy data and slower on match-heavy data (profiles/r1_tuning.md).
-// Leaves with   0: `e` is a first-level entry that is not a literal (its code bits are NOT consumed; 0 = long code)
-//               1: a literal was stored and o.pos entered a new 256-byte row
-// `vpos` is the per-lane copy of `pos` (ring addresses), `lane4` = 4 * lane.  Relies on the ring sitting at LDS
-// address 0 (checked by the kernel).
-template <int RING>
-__device__ __forceinline__ uint32_t literal_run(BitReader& br, uint32_t& pos, uint32_t& vpos, uint32_t lane4, uint32_t& e) {
-  uint32_t why, vt, ve;
-  uint64_t buf = br.buf;
-  int cnt = br.cnt;
-  uint32_t widx = br.widx;
-  asm volatile(
-      "L_lit_loop%=:\n"
-      "  s_cmp_gt_i32 s52, 32\n"
-      "  s_cbranch_scc1 L_lit_have%=\n"
-      "  s_waitcnt vmcnt(0)\n"
-      "  v_readlane_b32 s60, %[cur], s53\n"
-      "  s_mov_b32 s61, 0\n"
-      "  s_lshl_b64 s[60:61], s[60:61], s52\n"
-      "  s_or_b64 s[50:51], s[50:51], s[60:61]\n"
-      "  s_add_i32 s52, s52, 32\n"
-      "  s_add_i32 s53, s53, 1\n"
-      "  s_and_b32 s57, s53, 63\n"
-      "  s_cbranch_scc1 L_lit_have%=\n"
-      "  v_lshl_add_u32 %[vt], s53, 2, %[lane4]\n"
-      "  global_load_dword %[cur], %[vt], s[58:59]\n"
-      "L_lit_have%=:\n"
-      "  v_lshlrev_b32 %[vt], 2, s50\n"
-      "  v_and_b32 %[vt], %[lutmask], %[vt]\n"
-      "  ds_read_b32 %[ve], %[vt] offset:%[lutoff]\n"
-      "  s_waitcnt lgkmcnt(0)\n"
-      "  v_readfirstlane_b32 s55, %[ve]\n"
-      "  s_bitcmp1_b32 s55, 8\n"
-      "  s_cbranch_scc0 L_lit_other%=\n"
-      "  s_and_b32 s57, s55, 15\n"
-      "  s_lshr_b64 s[50:51], s[50:51], s57\n"
-      "  s_sub_i32 s52, s52, s57\n"
-      "  v_and_b32 %[vt], %[ringmask], %[vpos]\n"
-      "  ds_write_b8_d16_hi %[vt], %[ve]\n"
-      "  v_add_u32 %[vpos], 1, %[vpos]\n"
-      "  s_add_i32 s54, s54, 1\n"
-      "  s_and_b32 s57, s54, 0xff\n"
-      "  s_cbranch_scc1 L_lit_loop%=\n"
-      "  s_mov_b32 s56, 1\n"
-      "  s_branch L_lit_out%=\n"
-      "L_lit_other%=:\n"
-      "  s_mov_b32 s56, 0\n"
-      "L_lit_out%=:\n"
-      "  s_waitcnt vmcnt(0) lgkmcnt(0)\n"
-      : [buf] "+{s[50:51]}"(buf), [cnt] "+{s52}"(cnt), [widx] "+{s53}"(widx), [pos] "+{s54}"(pos), [e] "={s55}"(e), [why] "={s56}"(why),
-        [cur] "+v"(br.cur), [vpos] "+v"(vpos), [vt] "=&v"(vt), [ve] "=&v"(ve)
-      : [base] "{s[58:59]}"(br.base), [lane4] "v"(lane4), [lutmask] "i"(((1 << LIT_BITS) - 1) << 2), [ringmask] "i"(RING - 1),
-        [lutoff] "i"(RING + (int)__builtin_offsetof(WaveLds, lit_lut))
-      : "s57", "s60", "s61", "scc", "memory");
-  // asm results count as divergent for the compiler even in scalar registers: say otherwise (folds to plain copies)
-  br.buf = ((uint64_t)uniu((uint32_t)(buf >> 32)) << 32) | uniu((uint32_t)buf);
-  br.cnt = uni(cnt);
-  br.widx = uniu(widx);
-  pos = uniu(pos);
-  e = uniu(e);
-  return uniu(why);
-}
-
-// literal_run plus the common match, in one block: a length code and a distance code that both sit in the first-level
-// tables, at most 64 bytes, source either in the ring without overlap or far enough back to be in HBM already --
-// decoded, copied (one masked read + write) and advanced without leaving the loop.  Anything else leaves with what has
-// been decoded so far:
-//   0: `e` is a first-level entry the loop does not handle (long code, end of block, invalid); nothing consumed
-//   1: o.pos entered a new 256-byte row (after a literal or a match)
-//   2: a match is decoded (len, d; all its bits consumed) but not copied: overlapping, longer than 64, or a bad distance
-//   3: a length is decoded (len) and consumed, the buffer refilled; the distance code needs the slow path
-template <int RING>
-__device__ __forceinline__ uint32_t symbol_run(BitReader& br, uint32_t& pos, uint32_t& vpos, uint32_t lane, uint32_t lane4, uint32_t begin,
-                                               const uint8_t* out, uint32_t& e, uint32_t& len, uint32_t& d) {
-  uint32_t why, vt, ve;
-  uint64_t buf = br.buf;
-  int cnt = br.cnt;
-  uint32_t widx = br.widx;
-#define EXON_REFILL(tag)                                \
-  "  s_cmp_gt_i32 s52, 32\n"                            \
-  "  s_cbranch_scc1 L_have_" tag "%=\n"                 \
-  "  s_waitcnt vmcnt(0)\n"                              \
-  "  v_readlane_b32 s60, %[cur], s53\n"                 \
-  "  s_mov_b32 s61, 0\n"                                \
-  "  s_lshl_b64 s[60:61], s[60:61], s52\n"              \
-  "  s_or_b64 s[50:51], s[50:51], s[60:61]\n"           \
-  "  s_add_i32 s52, s52, 32\n"                          \
-  "  s_add_i32 s53, s53, 1\n"                           \
-  "  s_and_b32 s57, s53, 63\n"                          \
-  "  s_cbranch_scc1 L_have_" tag "%=\n"                 \
-  "  v_lshl_add_u32 %[vt], s53, 2, %[lane4]\n"          \
-  "  global_load_dword %[cur], %[vt], s[58:59]\n"       \
-  "L_have_" tag "%=:\n"
-  asm volatile(
-      "L_sym_loop%=:\n" EXON_REFILL("l")
-      "  v_lshlrev_b32 %[vt], 2, s50\n"
-      "  v_and_b32 %[vt], %[lutmask], %[vt]\n"
-      "  ds_read_b32 %[ve], %[vt] offset:%[lutoff]\n"
-      "  s_waitcnt lgkmcnt(0)\n"
-      "  v_readfirstlane_b32 s55, %[ve]\n"
-      "  s_bitcmp1_b32 s55, 8\n"
-      "  s_cbranch_scc0 L_sym_match%=\n"
-      "  s_and_b32 s57, s55, 15\n"
-      "  s_lshr_b64 s[50:51], s[50:51], s57\n"
-      "  s_sub_i32 s52, s52, s57\n"
-      "  v_and_b32 %[vt], %[ringmask], %[vpos]\n"
-      "  ds_write_b8_d16_hi %[vt], %[ve]\n"
-      "  v_add_u32 %[vpos], 1, %[vpos]\n"
-      "  s_add_i32 s54, s54, 1\n"
-      "  s_and_b32 s57, s54, 0xff\n"
-      "  s_cbranch_scc1 L_sym_loop%=\n"
-      "  s_branch L_sym_row%=\n"
-      // ---- not a literal: a length code?
-      "L_sym_match%=:\n"
-      "  s_and_b32 s57, s55, 15\n"            // code length; SCC = (it is in the table)
-      "  s_cbranch_scc0 L_sym_exit0%=\n"
-      "  s_and_b32 s64, s55, 0x600\n"         // end of block / invalid
-      "  s_cbranch_scc1 L_sym_exit0%=\n"
-      "  s_lshr_b64 s[50:51], s[50:51], s57\n"
-      "  s_sub_i32 s52, s52, s57\n"
-      "  s_lshr_b32 s62, s55, 16\n"           // length base
-      "  s_bfe_u32 s57, s55, 0x40004\n"       // extra bits; SCC = (any)
-      "  s_cbranch_scc0 L_sym_len%=\n"
-      "  s_bfm_b32 s64, s57, 0\n"
-      "  s_and_b32 s64, s50, s64\n"
-      "  s_add_i32 s62, s62, s64\n"
-      "  s_lshr_b64 s[50:51], s[50:51], s57\n"
-      "  s_sub_i32 s52, s52, s57\n"
-      "L_sym_len%=:\n" EXON_REFILL("m")
-      // ---- the distance
-      "  v_lshlrev_b32 %[vt], 2, s50\n"
-      "  v_and_b32 %[vt], %[dmask], %[vt]\n"
-      "  ds_read_b32 %[ve], %[vt] offset:%[dlut]\n"
-      "  s_waitcnt lgkmcnt(0)\n"
-      "  v_readfirstlane_b32 s65, %[ve]\n"
-      "  s_and_b32 s57, s65, 15\n"
-      "  s_cbranch_scc0 L_sym_exit3%=\n"      // long or nonexistent code
-      "  s_bitcmp1_b32 s65, 10\n"
-      "  s_cbranch_scc1 L_sym_exit3%=\n"      // invalid symbol (30, 31)
-      "  s_lshr_b64 s[50:51], s[50:51], s57\n"
-      "  s_sub_i32 s52, s52, s57\n"
-      "  s_lshr_b32 s63, s65, 16\n"           // distance base
-      "  s_bfe_u32 s57, s65, 0x40004\n"       // extra bits; SCC = (any)
-      "  s_cbranch_scc0 L_sym_dist%=\n"
-      "  s_bfm_b32 s64, s57, 0\n"
-      "  s_and_b32 s64, s50, s64\n"
-      "  s_add_i32 s63, s63, s64\n"
-      "  s_lshr_b64 s[50:51], s[50:51], s57\n"
-      "  s_sub_i32 s52, s52, s57\n"
-      "L_sym_dist%=:\n"
-      // ---- the copies the loop does itself: d <= history, len <= 64, and either len <= d <= NEAR (ring -> ring) or
-      //      d > NEAR (the source is below `drained`, i.e. in HBM already)
-      "  s_sub_i32 s57, s54, s66\n"
-      "  s_cmp_gt_u32 s63, s57\n"
-      "  s_cbranch_scc1 L_sym_exit2%=\n"
-      "  s_cmp_gt_u32 s62, 64\n"
-      "  s_cbranch_scc1 L_sym_exit2%=\n"
-      "  v_cmp_gt_u32 vcc, s62, %[lane]\n"     // lanes below len
-      "  s_sub_i32 s57, s54, s63\n"            // first source byte
-      "  s_cmp_gt_u32 s63, %[near]\n"
-      "  s_cbranch_scc1 L_sym_far%=\n"
-      "  s_cmp_gt_u32 s62, s63\n"
-      "  s_cbranch_scc1 L_sym_exit2%=\n"       // overlapping run
-      "  s_and_saveexec_b64 s[60:61], vcc\n"
-      "  v_add_u32 %[vt], s57, %[lane]\n"
-      "  v_and_b32 %[vt], %[ringmask], %[vt]\n"
-      "  ds_read_u8 %[ve], %[vt]\n"
-      "  v_add_u32 %[vt], s54, %[lane]\n"
-      "  v_and_b32 %[vt], %[ringmask], %[vt]\n"
-      "  s_waitcnt lgkmcnt(0)\n"
-      "  ds_write_b8 %[vt], %[ve]\n"
-      "  s_mov_b64 exec, s[60:61]\n"
-      "  s_branch L_sym_adv%=\n"
-      "L_sym_far%=:\n"
-      "  s_and_saveexec_b64 s[60:61], vcc\n"
-      "  v_add_u32 %[vt], s57, %[lane]\n"
-      "  global_load_ubyte %[ve], %[vt], s[68:69]\n"
-      "  v_add_u32 %[vt], s54, %[lane]\n"
-      "  v_and_b32 %[vt], %[ringmask], %[vt]\n"
-      "  s_waitcnt vmcnt(0)\n"
-      "  ds_write_b8 %[vt], %[ve]\n"
-      "  s_mov_b64 exec, s[60:61]\n"
-      "L_sym_adv%=:\n"
-      "  s_add_i32 s57, s54, s62\n"
-      "  s_xor_b32 s64, s57, s54\n"
-      "  s_mov_b32 s54, s57\n"
-      "  v_mov_b32 %[vpos], s57\n"
-      "  s_lshr_b32 s64, s64, 8\n"            // SCC = a 256-byte row boundary was crossed
-      "  s_cbranch_scc0 L_sym_loop%=\n"
-      "L_sym_row%=:\n"
-      "  s_mov_b32 s56, 1\n"
-      "  s_branch L_sym_out%=\n"
-      "L_sym_exit0%=:\n"
-      "  s_mov_b32 s56, 0\n"
-      "  s_branch L_sym_out%=\n"
-      "L_sym_exit2%=:\n"
-      "  s_mov_b32 s56, 2\n"
-      "  s_branch L_sym_out%=\n"
-      "L_sym_exit3%=:\n"
-      "  s_mov_b32 s56, 3\n"
-      "L_sym_out%=:\n"
-      "  s_waitcnt vmcnt(0) lgkmcnt(0)\n"
-      : [buf] "+{s[50:51]}"(buf), [cnt] "+{s52}"(cnt), [widx] "+{s53}"(widx), [pos] "+{s54}"(pos), [e] "={s55}"(e), [why] "={s56}"(why),
-        [len] "={s62}"(len), [d] "={s63}"(d), [cur] "+v"(br.cur), [vpos] "+v"(vpos), [vt] "=&v"(vt), [ve] "=&v"(ve)
-      : [base] "{s[58:59]}"(br.base), [begin] "{s66}"(begin), [out] "{s[68:69]}"(out), [lane] "v"(lane), [lane4] "v"(lane4), [lutmask] "i"(((1 << LIT_BITS) - 1) << 2),
-        [dmask] "i"(((1 << DIST_BITS) - 1) << 2), [ringmask] "i"(RING - 1), [near] "i"(RING - 258),
-        [lutoff] "i"(RING + (int)__builtin_offsetof(WaveLds, lit_lut)), [dlut] "i"(RING + (int)__builtin_offsetof(WaveLds, dist_lut))
-      : "s57", "s60", "s61", "s64", "s65", "vcc", "scc", "memory");
-#undef EXON_REFILL
-  br.buf = ((uint64_t)uniu((uint32_t)(buf >> 32)) << 32) | uniu((uint32_t)buf);
-  br.cnt = uni(cnt);
-  br.widx = uniu(widx);
-  pos = uniu(pos);
-  e = uniu(e);
-  len = uniu(len);
-  d = uniu(d);
-  return uniu(why);
-}
-
-// symbol_run on the VECTOR unit, software-pipelined (round 4).
-// (1) Where the instructions issue.  The loop above keeps the bit buffer in scalar registers, so nearly every instruction of a
-// symbol goes through the CU's ONE scalar ALU, which issues one instruction per clock for the whole CU (tools/issue_rate.hip:
+// One symbol per step on the VECTOR unit, software-pipelined: the loop that finishes the blocks k_inflate_par hands back.
+// (1) Where the instructions issue.  A loop that keeps the bit buffer in scalar registers sends nearly every instruction of a
+// symbol through the CU's ONE scalar ALU, which issues one instruction per clock for the whole CU (tools/issue_rate.hip:
 // 1.02 per clock and CU from 16 waves up).  The four SIMD-32 units of a gfx950 CU issue a wave64 vector instruction every two
 // clocks EACH (measured 1.8-1.95 per clock and CU on the same dependent chains; a v_cmp + s_cbranch_vccnz pair costs what
 // s_cmp + s_cbranch_scc costs), and a wave-uniform value can just as well live in a vector register with all 64 lanes
 // computing the same thing.  So here the bit buffer, the bit count, the table entries, length and distance are VGPRs; what
 // stays scalar is what is cheap there: the output position (ring address, row test), the window index of the refill, the
-// exec mask of the copy.  A plain translation of symbol_run (8 vector + 3 scalar instructions per literal instead of 5 + 10)
+// exec mask of the copy.  A plain translation of the scalar loop (8 vector + 3 scalar instructions per literal instead of 5 + 10)
 // measured the SAME throughput as the scalar loop on every format (profiles/r4_inflate_flavor_v1.log), and so did making the
 // far copies free (r4_inflate_far_nowait.log: +6..12 %): 24 waves per CU are bound by each wave's own dependency chain
 // buffer -> table index -> LDS lookup (~100 clocks) -> code length -> shift, not by an issue port.
@@ -749,7 +523,14 @@ __device__ __forceinline__ uint32_t symbol_run(BitReader& br, uint32_t& pos, uin
 // before the literal is stored, the counters move, the buffer is refilled or the match is copied; all of that now runs under
 // the lookup's latency.  Length + extra bits (and distance + extra bits) leave the buffer with ONE 64-bit shift, the extra
 // value comes from a v_bfe with register operands.  The refill is out of line (the common no-refill case falls through).
-// Same contract as symbol_run: same `why` codes, same registers in and out; a lookup in flight at an exit is dropped.
+// Literals and the common match -- a length code and a distance code that both sit in the first-level tables, at most 64 bytes,
+// source either in the ring without overlap or far enough back to be in HBM already -- are decoded, copied and advanced without
+// leaving the loop.  Anything else leaves with what has been decoded so far (a lookup in flight at an exit is dropped):
+//   0: `e` is a first-level entry the loop does not handle (long code, end of block, invalid); nothing consumed
+//   1: o.pos entered a new 256-byte row (after a literal or a match)
+//   2: a match is decoded (len, d; all its bits consumed) but not copied: overlapping, longer than 64, or a bad distance
+//   3: a length is decoded (len) and consumed, the buffer refilled; the distance code needs the slow path
+// `vpos` is the per-lane copy of `pos`, `lane4` = 4 * lane.  Relies on the ring sitting at LDS address 0 (checked by the kernel).
 // Hazards the assembler does not see inside an asm block (gfx940 family): a VALU-written SGPR needs 2 wait states before a
 // VALU reads it (v_readlane -> v_lshlrev_b64 in the refill: two scalar instructions in between), a VALU-written VGPR 1 before
 // v_readfirstlane reads it (the exits start with scalar instructions).  VALU-written VCC / SGPRs read by the scalar unit or by
@@ -886,7 +667,7 @@ __device__ __forceinline__ uint32_t symbol_run_v(BitReader& br, uint32_t& pos, u
       "  v_lshrrev_b32 v54, 16, v52\n"
       "  v_add_u32 v54, v54, v35\n"            // distance
       "  v_sub_u32 v50, v50, v38\n"
-      // ---- the copies the loop does itself (as in symbol_run): d <= history, len <= 64, and either len <= d <= NEAR or d > NEAR
+      // ---- the copies the loop does itself: d <= history, len <= 64, and either len <= d <= NEAR or d > NEAR
       "  s_sub_i32 s57, s54, s66\n"
       "  v_cmp_lt_u32 vcc, s57, v54\n"
       "  s_cbranch_vccnz L_vsym_exit2%=\n"
@@ -923,9 +704,6 @@ __device__ __forceinline__ uint32_t symbol_run_v(BitReader& br, uint32_t& pos, u
       // reads them, when the block is left (row drains, slow paths) -- so the round trip to L2 / HBM runs under the decoding
       // of the symbols behind it.  Nothing reads those ring bytes earlier: literals and copies only write at `pos` and above.
       "L_vsym_far%=:\n"
-#ifdef EXON_INFLATE_FAR_NOWAIT  // timing experiment only (wrong bytes): what the loop would cost if far copies were free
-      "  s_branch L_vsym_adv%=\n"
-#endif
       "  v_cmp_gt_u32_e64 s[60:61], v53, %[lane]\n"
       "  s_and_saveexec_b64 s[64:65], s[60:61]\n"
       "  v_add_u32 %[vt], v39, %[lane]\n"
@@ -1014,7 +792,7 @@ __device__ __forceinline__ uint32_t symbol_run_v(BitReader& br, uint32_t& pos, u
 
 // ================================================================================================================
 // The WIDE symbol loop (round 5): 64 lanes = 64 consecutive BIT OFFSETS of the stream.
-// The loops above decode one symbol per step with one useful lane: every step pays an LDS round trip (table lookup) on the
+// The loop above decodes one symbol per step with one useful lane: every step pays an LDS round trip (table lookup) on the
 // wave's own dependency chain, ~300 clocks per symbol with 8 waves sharing a SIMD.  Here a ROUND takes 64 bits of the stream
 // at once: lane l decodes the complete symbol that WOULD start at bit l (literal, or length + extra bits + distance + extra
 // bits: two table lookups for all 64 offsets together), so after two LDS round trips every possible symbol start of the
@@ -1032,8 +810,8 @@ __device__ __forceinline__ uint32_t symbol_run_v(BitReader& br, uint32_t& pos, u
 //   * a symbol the tables do not resolve ends the chain in front of it (its lane's record is 0, the chain goes to 64 + lane).  A
 //     LITERAL with a code longer than the table is decoded right there (all candidate lengths at once, one per lane) and the walk
 //     goes on; end of block, a long length / distance code or an invalid code leave the loop: the round consumes what precedes
-//     it and the caller's slow path takes the symbol, as for the loops above.
-// Same contract as symbol_run: why 0 / 1 / 2 as there (e / len / d), 4 = a distance reaches before the member's output.
+//     it and the caller's slow path takes the symbol, as for the loop above.
+// Same contract as symbol_run_v: why 0 / 1 / 2 as there (e / len / d), 4 = a distance reaches before the member's output.
 // Window: `cur` = dwords [wb, wb + 64) of the compressed data, one per lane, wb a multiple of 32; a round needs the dwords
 // k .. k + 4 with k = bp >> 5 < 32 + 4; when bp passes 1024 the window moves by 32 dwords (upper half of cur + lower half of
 // nxt, nxt = dwords [wb + 64, wb + 128) loaded long before).
@@ -1103,9 +881,7 @@ __device__ __forceinline__ uint32_t wide_rounds_asm(const __attribute__((address
       // sits on a 64-byte line: the chain walk's loop, 268 bytes further on, then lies inside one line -- the kernel is 1.2 % faster on
       // FASTQ and VCF members than with the loop 4 bytes further along, profiles/r5_inflate_code_alignment.log.  The padding is only
       // run through when the rounds are entered.)
-#ifndef EXON_WIDE_NO_ALIGN
       "  .p2align 6\n"
-#endif
       "L_wr_round%=:\n"
       "  s_waitcnt lgkmcnt(0)\n"
       "  v_alignbit_b32 v38, v36, v35, v33\n"
@@ -1545,7 +1321,7 @@ __device__ __forceinline__ uint32_t wide_run(BitReader& br, Out& o, uint32_t& e_
   static_assert(NEARW >= 64 + 255 + 64, "a far source must lie below the drained rows");
   const uint32_t lane = lane_id();
   uint8_t* ring = wave_ring<RING>();
-  const WaveLds* L = wave_lds<RING>();
+  [[maybe_unused]] const WaveLds* L = wave_lds<RING>();  // (the EXON_WIDE_ASM=0 round reads the tables through it)
   typedef const __attribute__((address_space(1))) uint32_t* gptr32;  // global_load, not flat_load (a flat load also counts as an LDS operation)
   typedef const __attribute__((address_space(1))) uint8_t* gptr8;
   gptr32 base = (gptr32)br.base;
@@ -1718,9 +1494,6 @@ __device__ __forceinline__ uint32_t wide_run(BitReader& br, Out& o, uint32_t& e_
         if (bfar) fnew = gout[src1 - 1u];  // below `drained`: in HBM already
         fdata = fnew;
         faddr = bfar ? ra : FAR_NONE;
-#ifdef EXON_WIDE_SYNC_FAR  // debugging: no deferral
-        complete_far();
-#endif
       }
       __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     }
@@ -1770,48 +1543,22 @@ __device__ __forceinline__ uint32_t wide_run(BitReader& br, Out& o, uint32_t& e_
   return why;
 }
 
-// `vflav` (wave-uniform): the hand-written symbol loop runs on the vector unit (symbol_run_v) instead of the scalar one
+// WIDE: the serial kernel's loop (wide_run); otherwise the parallel kernel's hand-back loop (symbol_run_v)
 template <int RING, bool WIDE>
-__device__ __noinline__ SymResult decode_symbols(BitReader br, Out o, int vflav) {
+__device__ __noinline__ SymResult decode_symbols(BitReader br, Out o) {
   constexpr uint32_t M = RING - 1;
   constexpr uint32_t NEAR = RING - 258;  // largest distance served from the ring (the copy must not overwrite its source)
   static_assert(RING >= 1024, "far matches rely on NEAR >= 258 + 255");
   br.make_uniform();
   o.make_uniform();
-  vflav = uni(vflav);
   uint8_t* ring = wave_ring<RING>();
   const WaveLds* L = wave_lds<RING>();
   const uint32_t lane = lane_id();
-  uint32_t vpos = o.pos;  // per-lane copy of o.pos: ring addresses of literals come from the vector ALU (literal_run)
+  uint32_t vpos = o.pos;  // per-lane copy of o.pos: ring addresses of literals come from the vector ALU (symbol_run_v)
   const uint32_t lane4 = lane * 4u;
-  (void)vpos;
-  (void)lane4;
   int err;  // every way out of the loop goes through ONE exit (several exit blocks cost a state variable on the back edge)
   for (;;) {
-    uint32_t e;
-#if EXON_INFLATE_LIT == 0
-    br.refill();
-    e = uniu(L->lit_lut[br.peek(LIT_BITS)]);
-    if (e & E_LIT) {  // literal with a first-level code (its length field is never 0)
-      br.drop((int)(e & 15u));
-      ring[o.pos & M] = (uint8_t)(e >> 16);  // every lane stores the same byte
-      ++o.pos;
-      if (__builtin_expect((o.pos & 255u) == 0, 0)) {
-        if (o.pos > o.end || br.overrun()) { err = br.overrun() ? INF_INPUT_OVERRUN : INF_OUTPUT_OVERRUN; break; }
-        o.drained = uniu(drain_rows<RING>(o.out, o.drained, o.pos));
-      }
-      continue;
-    }
-#elif EXON_INFLATE_LIT == 1
-    if (literal_run<RING>(br, o.pos, vpos, lane4, e)) {  // a 256-byte row of the ring is complete
-      if (o.pos > o.end || br.overrun()) { err = br.overrun() ? INF_INPUT_OVERRUN : INF_OUTPUT_OVERRUN; break; }
-      o.drained = uniu(drain_rows<RING>(o.out, o.drained, o.pos & ~255u));
-      continue;
-    }
-#endif
-    uint32_t len, d;
-#if EXON_INFLATE_LIT == 2
-    uint32_t why;
+    uint32_t e, len, d, why;
     if (WIDE) {
       why = uniu(wide_run<RING>(br, o, e, len, d));
       br.make_uniform();
@@ -1830,8 +1577,7 @@ __device__ __noinline__ SymResult decode_symbols(BitReader br, Out o, int vflav)
       }
       if (why == 1) continue;
     } else {
-      why = vflav ? symbol_run_v<RING>(br, o.pos, vpos, lane, lane4, o.begin, o.out, e, len, d)
-                  : symbol_run<RING>(br, o.pos, vpos, lane, lane4, o.begin, o.out, e, len, d);
+      why = symbol_run_v<RING>(br, o.pos, vpos, lane, lane4, o.begin, o.out, e, len, d);
     }
     if (why == 1) {  // a 256-byte row of the ring is complete
       if (o.pos > o.end || br.overrun()) { err = br.overrun() ? INF_INPUT_OVERRUN : INF_OUTPUT_OVERRUN; break; }
@@ -1840,10 +1586,6 @@ __device__ __noinline__ SymResult decode_symbols(BitReader br, Out o, int vflav)
     }
     if (why != 2) {
       if (why == 0) {
-#else
-    {
-      {
-#endif
         if (__builtin_expect((e & 15u) == 0, 0)) {  // a code longer than the table, or no such code
           const int r = uni(decode_long<RING>(CODE_LIT, (uint32_t)br.buf));
           // lengths are <= 15: the entry's length field holds it; no such code -> E_INVALID (caught below, no exit from here)
@@ -2485,14 +2227,14 @@ __device__ __noinline__ int par_decode_block(const uint8_t* __restrict__ comp /*
 }
 
 // One BGZF member.  PAR: dynamic / fixed DEFLATE blocks first try par_decode_block (scratch slot `sl`, fallback counters `stats`).
-template <int RING, bool PAR, bool WIDE = false>
+template <int RING, bool PAR>
 __device__ __forceinline__ void inflate_member(const uint8_t* __restrict__ comp, const Block* __restrict__ blocks, int b, uint8_t* out,
-                                               int* __restrict__ status, const ParSlot sl, unsigned* __restrict__ stats, int vflav) {
+                                               int* __restrict__ status, const ParSlot sl, unsigned* __restrict__ stats) {
   constexpr uint32_t M = RING - 1;
   const int lane = (int)lane_id();
   WaveLds* L = wave_lds<RING>();
   uint8_t* ring = wave_ring<RING>();
-  if (lds_addr(wave_ring<RING>()) != 0) {  // literal_run addresses the ring and the table with immediates (folds away when true)
+  if (lds_addr(wave_ring<RING>()) != 0) {  // the symbol loops address the ring and the tables with immediates (folds away when true)
     if (lane == 0) status[b] = INF_BAD_BTYPE;
     return;
   }
@@ -2617,7 +2359,7 @@ __device__ __forceinline__ void inflate_member(const uint8_t* __restrict__ comp,
         continue;
       }
     }
-    const SymResult r = decode_symbols<RING, WIDE>(br, o, vflav);
+    const SymResult r = decode_symbols<RING, !PAR>(br, o);
     br = r.br;
     br.make_uniform();
     o = r.o;
@@ -2631,25 +2373,7 @@ __device__ __forceinline__ void inflate_member(const uint8_t* __restrict__ comp,
   if (lane == 0) status[b] = err;
 }
 
-// Which symbol loop a wave runs: 0 scalar (symbol_run), 1 vector (symbol_run_v), 2 both on every CU -- workgroup b lands on
-// XCD b % 8 and the XCD deals its workgroups over its 32 CUs, so bit 8 of b splits the waves of a CU, not the CUs
-__device__ __forceinline__ int flavor_of(int flavor) { return flavor == 2 ? (int)((blockIdx.x >> 8) & 1u) : flavor; }
-
-#ifdef EXON_INFLATE_WPE  // A/B builds: waves per SIMD the register allocation aims for (8 = 64 VGPRs)
-#define EXON_INFLATE_WPE_ATTR __attribute__((amdgpu_waves_per_eu(EXON_INFLATE_WPE, EXON_INFLATE_WPE)))
-#else
-#define EXON_INFLATE_WPE_ATTR
-#endif
-template <int RING>
-__global__ __launch_bounds__(64 * INF_WAVES, 8) EXON_INFLATE_WPE_ATTR __attribute__((amdgpu_num_sgpr(72))) void k_inflate(const uint8_t* __restrict__ comp, const Block* __restrict__ blocks, int n_blocks,
-                                                uint8_t* out, int* __restrict__ status, int flavor) {
-  const int b = uni((int)(blockIdx.x * INF_WAVES + (threadIdx.x >> 6)));
-  if (b >= n_blocks) return;
-  inflate_member<RING, false>(comp, blocks, b, out, status, ParSlot{}, nullptr, flavor_of(flavor));
-}
-
-
-// The wide symbol loop (wide_run) as its own kernel: its register budget is not the serial loops'
+// The serial kernel: one member per wavefront, the wide symbol loop (wide_run)
 template <int RING>
 __global__ __launch_bounds__(64 * INF_WAVES, 8) __attribute__((amdgpu_num_sgpr(72))) void k_inflate_w(const uint8_t* __restrict__ comp, const Block* __restrict__ blocks, int n_blocks, uint8_t* out,
                                                               int* __restrict__ status) {
@@ -2658,7 +2382,7 @@ __global__ __launch_bounds__(64 * INF_WAVES, 8) __attribute__((amdgpu_num_sgpr(7
 #ifdef EXON_WIDE_STATS
   const unsigned long long ws0 = __builtin_readcyclecounter();
 #endif
-  inflate_member<RING, false, true>(comp, blocks, b, out, status, ParSlot{}, nullptr, 1);
+  inflate_member<RING, false>(comp, blocks, b, out, status, ParSlot{}, nullptr);
 #ifdef EXON_WIDE_STATS
   if (lane_id() == 0) {
     atomicAdd(&g_wide_stats[1], __builtin_readcyclecounter() - ws0);
@@ -2671,15 +2395,14 @@ __global__ __launch_bounds__(64 * INF_WAVES, 8) __attribute__((amdgpu_num_sgpr(7
 template <int RING>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void k_inflate_par(const uint8_t* __restrict__ comp, const Block* __restrict__ blocks, int n_blocks, uint8_t* out,
                                                     int* __restrict__ status, uint8_t* __restrict__ scratch, unsigned* __restrict__ counter,
-                                                    unsigned* __restrict__ stats, int flavor) {
+                                                    unsigned* __restrict__ stats) {
   const ParSlot sl = par_slot(scratch, blockIdx.x);
-  const int vflav = flavor_of(flavor);
   for (;;) {
     unsigned b = 0;
     if (lane_id() == 0) b = atomicAdd(counter, 1u);
     b = uniu(b);
     if (b >= (unsigned)n_blocks) return;
-    inflate_member<RING, true>(comp, blocks, (int)b, out, status, sl, stats, vflav);
+    inflate_member<RING, true>(comp, blocks, (int)b, out, status, sl, stats);
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
   }
 }
@@ -2953,22 +2676,14 @@ namespace {
 //          Round 4 (profiles/r4_inflate_par_crossover.log, one launch of K members through either decoder): VCF text 0.9 ms
 //          against 2.9 ms up to 256 members (one per CU) and 2.97-3.2 against 2.9-3.0 ms from 512 on; BAM and FASTQ members
 //          (mostly handed back to the serial loop inside the parallel kernel) 10 % slower at every size.  The limit was 1536.
-//   0      serial always      1  lane-parallel always      2  both side by side (a share of the members each)
+//   0      serial always      1  lane-parallel always      any other value: auto
 constexpr int PAR_AUTO_MAX = 256;
 int par_mode() {
   static const int m = [] {
     const char* e = getenv("EXON_HIP_INFLATE_PAR");
-    return e && *e ? atoi(e) : -1;
+    return e && (e[0] == '0' || e[0] == '1') && !e[1] ? e[0] - '0' : -1;
   }();
   return m;
-}
-double par_serial_share() {  // hybrid mode: fraction of a launch's members given to the serial kernel
-  static const double r = [] {
-    const char* e = getenv("EXON_HIP_INFLATE_PAR_SERIAL_SHARE");
-    const double v = e ? atof(e) : 0.4;
-    return v < 0 ? 0.0 : v > 0.95 ? 0.95 : v;
-  }();
-  return r;
 }
 int par_slots() {  // resident workgroups of the parallel kernel = scratch slots (16 per CU on 256 CUs)
   static const int n = [] {
@@ -2978,14 +2693,9 @@ int par_slots() {  // resident workgroups of the parallel kernel = scratch slots
   }();
   return n;
 }
-// per device: outcome counters of par_decode_block (64 words, never freed) and, for the hybrid mode, a side stream per
-// caller stream with its fork / join events
+// per device: outcome counters of par_decode_block (64 words, never freed)
 struct ParDev {
   unsigned* stats = nullptr;
-};
-struct ParSide {
-  hipStream_t side = nullptr;
-  hipEvent_t ev_fork = nullptr, ev_join = nullptr;
 };
 // scratch of the parallel kernel: 256 bytes (work counter) + one slot per workgroup, per caller stream (two scans inflating
 // at the same time must not share slots).  Grows to the largest launch seen on the stream, is never freed otherwise.
@@ -2998,7 +2708,6 @@ struct ParPool {
 std::map<std::pair<int, hipStream_t>, ParPool> g_par_pools;
 std::mutex g_par_mu;
 std::map<int, ParDev> g_par_dev;
-std::map<std::pair<int, hipStream_t>, ParSide> g_par_side;
 unsigned* par_stats_buffer(int dev) {
   std::lock_guard<std::mutex> g(g_par_mu);
   ParDev& d = g_par_dev[dev];
@@ -3038,26 +2747,6 @@ uint8_t* par_pool(int dev, hipStream_t s, int want) {
     p.slots = n;
   }
   return p.mem;
-}
-bool par_side(int dev, hipStream_t s, ParSide* out) {
-  std::lock_guard<std::mutex> g(g_par_mu);
-  auto key = std::make_pair(dev, s);
-  if (!g_par_side.count(key)) {
-    int on_dev = 0;
-    for (const auto& kv : g_par_side) on_dev += kv.first.first == dev;
-    if (on_dev >= 8) return false;
-  }
-  ParSide& p = g_par_side[key];
-  if (!p.side) {
-    if (hipStreamCreateWithFlags(&p.side, hipStreamNonBlocking) != hipSuccess || hipEventCreateWithFlags(&p.ev_fork, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&p.ev_join, hipEventDisableTiming) != hipSuccess) {
-      (void)hipGetLastError();
-      g_par_side.erase(key);
-      return false;
-    }
-  }
-  *out = p;
-  return true;
 }
 }  // namespace
 
@@ -3100,35 +2789,12 @@ void exon_bgzf_forget_stream(hipStream_t s) {
       ++it;
     }
   }
-  for (auto sd = g_par_side.begin(); sd != g_par_side.end();) {
-    if (sd->first.second == s) {
-      if (sd->second.side) hipStreamDestroy(sd->second.side);
-      if (sd->second.ev_fork) hipEventDestroy(sd->second.ev_fork);
-      if (sd->second.ev_join) hipEventDestroy(sd->second.ev_join);
-      sd = g_par_side.erase(sd);
-    } else {
-      ++sd;
-    }
-  }
 }
 
 // public form for caller-owned streams handed to exon_hip_bgzf_inflate: releases the scratch kept for `stream` (idle stream)
 extern "C" int exon_hip_bgzf_forget_stream(void* stream) {
   exon_bgzf_forget_stream((hipStream_t)stream);
   return EXON_HIP_OK;
-}
-
-// Which symbol loop a launch runs: 3 the wide loop (wide_run: 64 bit offsets per round, round 5), 1 the software-pipelined
-// vector-unit loop with deferred far copies (symbol_run_v, round 4), 0 round 1's scalar loop (symbol_run), 2 loops 0 and 1 side by
-// side.  EXON_HIP_INFLATE_FLAVOR forces one; otherwise the caller's hint, otherwise 3.  One resident launch, same box
-// (profiles/r5_inflate_wide_v3_32waves.log): VCF text 113 -> 178 GB/s, BAM payloads 102 -> 127, FASTQ 81 -> 82; the file pipelines
-// .vcf.gz 59 -> 41 ms, BAM 59 -> 48-51 ms, .fastq.gz 119 -> 115-120 ms.  (Round 4's history of loops 0 / 1 / 2: HISTORY.md section 7e.)
-static int inflate_flavor(int hint) {
-  static const int forced = [] {
-    const char* e = getenv("EXON_HIP_INFLATE_FLAVOR");
-    return e && e[0] >= '0' && e[0] <= '3' ? e[0] - '0' : -1;
-  }();
-  return forced >= 0 ? forced : hint >= 0 && hint <= 3 ? hint : 3;
 }
 
 // The CRC combine's powers of x: computed once per process, one copy per device (never freed).
@@ -3172,53 +2838,33 @@ const CrcPowers* crc_powers(int dev) {
 }  // namespace
 
 hipError_t exon_bgzf_inflate_launch(hipStream_t s, const uint8_t* d_comp, const exon_hip_bgzf_block* d_blocks, int n_blocks,
-                                    uint8_t* d_out, int* d_status, bool verify_crc, int flavor_hint, bool text_like) {
+                                    uint8_t* d_out, int* d_status, bool verify_crc, bool text_like) {
   if (n_blocks <= 0) return hipSuccess;
-  const int flavor = inflate_flavor(flavor_hint);
   static_assert(sizeof(Block) == sizeof(exon_hip_bgzf_block), "block layouts must agree");
   const Block* blocks = reinterpret_cast<const Block*>(d_blocks);
   const int mode = par_mode();
   // (auto: small launches of TEXT only -- members of BAM / BCF records and FASTQ reads are literal-heavy, the lane-parallel decoder
   //  hands most of them back to a serial loop: 50 k BAM records 3.9 ms through it against 2.1 ms through the wide loop alone,
   //  where 100 k rows of VCF text take 0.93 against 1.32 ms: profiles/r5_inflate_small_launches.log)
-  bool parallel = mode >= 1 || (mode < 0 && n_blocks <= PAR_AUTO_MAX && text_like);
+  bool parallel = mode == 1 || (mode < 0 && n_blocks <= PAR_AUTO_MAX && text_like);
   int dev = 0;
   unsigned* stats = nullptr;
   uint8_t* scratch = nullptr;
-  int n_ser = 0, n_wg = 0;
   if (parallel) {
     // scratch: one slot per workgroup + the work counter; anything that fails here just means "decode serially"
     parallel = hipGetDevice(&dev) == hipSuccess && (stats = par_stats_buffer(dev)) != nullptr;
-    ParSide side;
-    if (parallel && mode == 2 && n_blocks >= 256 && par_side(dev, s, &side)) n_ser = (int)((double)n_blocks * par_serial_share());
-    n_wg = std::min(n_blocks - n_ser, par_slots());
+    const int n_wg = std::min(n_blocks, par_slots());
     if (parallel && !(scratch = par_pool(dev, s, n_wg))) parallel = false;
     if (parallel) {
-      hipError_t e;
-      if ((e = hipMemsetAsync(scratch, 0, 256, s)) != hipSuccess) return e;
-      if (n_ser > 0) {
-        if ((e = hipEventRecord(side.ev_fork, s)) != hipSuccess) return e;
-        if ((e = hipStreamWaitEvent(side.side, side.ev_fork, 0)) != hipSuccess) return e;
-        hipLaunchKernelGGL(k_inflate<INFLATE_RING_SERIAL>, dim3(n_ser), dim3(64), 0, side.side, d_comp, blocks, n_ser, d_out, d_status, flavor);
-        if ((e = hipEventRecord(side.ev_join, side.side)) != hipSuccess) return e;
-      }
-      hipLaunchKernelGGL(k_inflate_par<INFLATE_RING>, dim3(n_wg), dim3(64), 0, s, d_comp, blocks + n_ser, n_blocks - n_ser, d_out, d_status + n_ser,
-                         scratch + 256, reinterpret_cast<unsigned*>(scratch), stats, flavor);
-      if (n_ser > 0 && (e = hipStreamWaitEvent(s, side.ev_join, 0)) != hipSuccess) return e;
+      const hipError_t e = hipMemsetAsync(scratch, 0, 256, s);
+      if (e != hipSuccess) return e;
+      hipLaunchKernelGGL(k_inflate_par<INFLATE_RING>, dim3(n_wg), dim3(64), 0, s, d_comp, blocks, n_blocks, d_out, d_status, scratch + 256,
+                         reinterpret_cast<unsigned*>(scratch), stats);
     }
   }
-  // (experiment knob: EXON_HIP_INFLATE_PAD_LDS=<bytes> of unused dynamic LDS per workgroup = fewer resident waves per CU)
-  static const size_t pad_lds = [] {
-    const char* e = getenv("EXON_HIP_INFLATE_PAD_LDS");
-    const long v = e ? atol(e) : 0;
-    return (size_t)(v > 0 && v <= 32768 ? v : 0);
-  }();
-  if (!parallel && flavor == 3)
-    hipLaunchKernelGGL(k_inflate_w<INFLATE_RING_SERIAL>, dim3((n_blocks + INF_WAVES - 1) / INF_WAVES), dim3(64 * INF_WAVES), pad_lds, s, d_comp, blocks,
+  if (!parallel)
+    hipLaunchKernelGGL(k_inflate_w<INFLATE_RING_SERIAL>, dim3((n_blocks + INF_WAVES - 1) / INF_WAVES), dim3(64 * INF_WAVES), 0, s, d_comp, blocks,
                        n_blocks, d_out, d_status);
-  else if (!parallel)
-    hipLaunchKernelGGL(k_inflate<INFLATE_RING_SERIAL>, dim3((n_blocks + INF_WAVES - 1) / INF_WAVES), dim3(64 * INF_WAVES), pad_lds, s, d_comp, blocks, n_blocks,
-                       d_out, d_status, flavor);
   if (verify_crc) {
     int cdev = 0;
     const CrcPowers* pw = hipGetDevice(&cdev) == hipSuccess ? crc_powers(cdev) : nullptr;  // (nullptr: the kernel computes the powers itself)
@@ -3231,7 +2877,7 @@ hipError_t exon_bgzf_inflate_launch(hipStream_t s, const uint8_t* d_comp, const 
 // resident workgroups per CU of the serial kernel, as the runtime computes it (tools / DESIGN only)
 extern "C" int exon_hip_debug_inflate_occupancy(int dynamic_lds_bytes) {
   int nb = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_inflate<INFLATE_RING_SERIAL>, 64, (size_t)dynamic_lds_bytes) != hipSuccess) return -1;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_inflate_w<INFLATE_RING_SERIAL>, 64 * INF_WAVES, (size_t)dynamic_lds_bytes) != hipSuccess) return -1;
   return nb;
 }
 

@@ -53,11 +53,7 @@ typedef int v4i_t __attribute__((ext_vector_type(4)));
 template <typename T>
 __device__ __forceinline__ T ld16(const void* p) {
   static_assert(sizeof(T) == 16, "16-byte vector expected");
-#ifdef EXON_LD16_PLAIN  // A/B builds only (tools/build_variant.sh): every column load without the streaming hint
-  const v4i_t v = *reinterpret_cast<const v4i_t*>(p);
-#else
   const v4i_t v = __builtin_nontemporal_load(reinterpret_cast<const v4i_t*>(p));
-#endif
   T r;
   __builtin_memcpy(&r, &v, 16);
   return r;
@@ -96,15 +92,9 @@ __device__ __forceinline__ bool valid1(const uint8_t* __restrict__ bm, int64_t r
 
 // Which workgroup takes the rows behind the last whole tile.  Tiles are dealt b, b + grid, ...: the LAST workgroups are the
 // ones with a tile less when the tiles do not divide evenly, so the remainder -- a dependent load behind the tile loop, one
-// HBM latency -- goes to them and stays off the critical path (the first workgroups carried it until round 4; A/B build:
-// -DEXON_REM_FRONT, profiles/r4_small_configs.log).
-__device__ __forceinline__ unsigned rem_block() {
-#ifdef EXON_REM_FRONT
-  return blockIdx.x;
-#else
-  return gridDim.x - 1u - blockIdx.x;
-#endif
-}
+// HBM latency -- goes to them and stays off the critical path (the first workgroups carried it until round 4;
+// profiles/r4_small_configs.log).
+__device__ __forceinline__ unsigned rem_block() { return gridDim.x - 1u - blockIdx.x; }
 
 __device__ __forceinline__ unsigned long long wave_sum(unsigned long long v) {
 #pragma unroll
@@ -197,7 +187,7 @@ __global__ __launch_bounds__(256) void finalize_partials(const unsigned long lon
 //     from the memory side, not from a stale L2 line), folds them block 0, 1, ... (bit-reproducible f64 sums for a
 //     given launch shape), writes the state and resets the ticket for the next launch on this stream.
 // Only records of <= FUSE_MAX_V words take this route: bigger ones (LDS group tables) are a multi-workgroup job and
-// keep the finalize_partials launch.  EXON_HIP_FUSE_FOLD=0 turns it off (A/B runs).
+// keep the finalize_partials launch.
 // ------------------------------------------------------------------------------------------------
 constexpr int FUSE_MAX_V = 256;
 struct FoldArgs {
@@ -276,16 +266,9 @@ __device__ __forceinline__ void fold_if_last(const FoldArgs& fa, const unsigned 
   if (threadIdx.x == 0) __hip_atomic_store(fa.ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-static bool fuse_fold_enabled() {
-  static const bool on = [] {
-    const char* v = getenv("EXON_HIP_FUSE_FOLD");
-    return !(v && v[0] == '0');
-  }();
-  return on;
-}
 static FoldArgs fold_args(const LaunchCfg& cfg, const Workspace& ws, int V, int n_i64, int64_t* st_i64, double* st_f64) {
   FoldArgs fa;
-  fa.ticket = (fuse_fold_enabled() && V <= FUSE_MAX_V) ? reinterpret_cast<unsigned*>(ws.status + 2) : nullptr;
+  fa.ticket = V <= FUSE_MAX_V ? reinterpret_cast<unsigned*>(ws.status + 2) : nullptr;
   fa.st_i64 = st_i64;
   fa.st_f64 = st_f64;
   fa.V = V;
@@ -296,7 +279,7 @@ static FoldArgs fold_args(const LaunchCfg& cfg, const Workspace& ws, int V, int 
 
 static hipError_t run_finalize(hipStream_t s, const LaunchCfg& cfg, const Workspace& ws, int nblocks, int V, int n_i64,
                                int64_t* st_i64, double* st_f64) {
-  if (fuse_fold_enabled() && V <= FUSE_MAX_V) return hipSuccess;  // folded by the main kernel's last workgroup
+  if (V <= FUSE_MAX_V) return hipSuccess;  // folded by the main kernel's last workgroup
   const int grid = (V + 31) / 32;
   hipLaunchKernelGGL(finalize_partials, dim3(grid), dim3(256), 0, s, ws.partials, nblocks, V, n_i64, st_i64, st_f64,
                      cfg.overwrite ? 1 : 0);
@@ -386,17 +369,10 @@ static int resident_blocks(F f, int threads, size_t lds) {
 // 92.0 vs 96.8 us; K3 at 2e7: 31.7 vs 33.4 us), equal within the box-to-box noise from 2.5e8 rows up -- a tie on the critical
 // path is not a tie: the smaller tile also ramps up and drains faster.  K2 / K3 / K6 take J = 2 whenever they take a big
 // shape; K4 keeps J = 4 (its own rule below).
-enum { SHAPE_SMALL = 0, SHAPE_BIG_J2 = 1, SHAPE_BIG_J4 = 2 };
-static int pick_shape(const LaunchCfg& cfg, int64_t n) {
-  static const int forced = [] {
-    const char* v = getenv("EXON_HIP_SHAPE");  // A/B runs: 0 small, 1 big J=2, 2 big J=4
-    return v && v[0] >= '0' && v[0] <= '2' ? v[0] - '0' : -1;
-  }();
-  if (forced >= 0) return forced;
+static bool use_big_shape(const LaunchCfg& cfg, int64_t n) {
   const int64_t cus = std::max(cfg.compute_units, 1);
-  return n / ShapeOf<ShapeBigJ2>::TILE < cus ? SHAPE_SMALL : SHAPE_BIG_J2;
+  return n / ShapeOf<ShapeBigJ2>::TILE >= cus;
 }
-static bool use_big_shape(const LaunchCfg& cfg, int64_t n) { return pick_shape(cfg, n) != SHAPE_SMALL; }
 
 template <typename S>
 static int grid_for(const LaunchCfg& cfg, int64_t n, int resident) {
@@ -550,10 +526,7 @@ hipError_t launch_region_count(hipStream_t s, const LaunchCfg& cfg, const Worksp
   if (n <= 0) return hipSuccess;
   int grid = 1;
   const FoldArgs fa = fold_args(cfg, ws, 1, 1, d_count, nullptr);
-  const int shape = pick_shape(cfg, n);
-  hipError_t e = shape == SHAPE_BIG_J4
-                     ? k2_launch<ShapeBig>(s, cfg, ws, chrom, chrom_valid, pos, pos_valid, n, region_chrom, start, end, &grid, fa)
-                 : shape == SHAPE_BIG_J2
+  hipError_t e = use_big_shape(cfg, n)
                      ? k2_launch<ShapeBigJ2>(s, cfg, ws, chrom, chrom_valid, pos, pos_valid, n, region_chrom, start, end, &grid, fa)
                      : k2_launch<ShapeSmall>(s, cfg, ws, chrom, chrom_valid, pos, pos_valid, n, region_chrom, start, end, &grid, fa);
   if (e != hipSuccess) return e;
@@ -909,11 +882,8 @@ hipError_t launch_flag_mapq_group_count(hipStream_t s, const LaunchCfg& cfg, con
   const bool big = use_big_shape(cfg, n) && (size_t)16 * (n_refs + 1 + 64) * 4 <= 160 * 1024;
   const int V = n_refs + 1;
   const FoldArgs fa = fold_args(cfg, ws, V, V, d_counts, nullptr);
-  hipError_t e = big ? (pick_shape(cfg, n) == SHAPE_BIG_J2
-                            ? k3_launch<ShapeBigJ2>(s, cfg, ws, flag, flag_valid, mapq, mapq_valid, ref_id, ref_valid, n, flag_mask,
-                                                    flag_value, mapq_min, n_refs, &grid, fa)
-                            : k3_launch<ShapeBig>(s, cfg, ws, flag, flag_valid, mapq, mapq_valid, ref_id, ref_valid, n,
-                                                  flag_mask, flag_value, mapq_min, n_refs, &grid, fa))
+  hipError_t e = big ? k3_launch<ShapeBigJ2>(s, cfg, ws, flag, flag_valid, mapq, mapq_valid, ref_id, ref_valid, n, flag_mask,
+                                             flag_value, mapq_min, n_refs, &grid, fa)
                      : k3_launch<ShapeSmall>(s, cfg, ws, flag, flag_valid, mapq, mapq_valid, ref_id, ref_valid, n,
                                              flag_mask, flag_value, mapq_min, n_refs, &grid, fa);
   if (e != hipSuccess) return e;
@@ -972,11 +942,6 @@ constexpr int K4_POS_BITS = 13;       // position field of a cursor: K4_CHUNK + 
 constexpr unsigned K4_POS_MASK = (1u << K4_POS_BITS) - 1u;
 constexpr int K4_DIRECT_MAX_RANGES = 128;
 static inline int k4_stream_copies_log2(int n_ranges) {
-  static const int forced = [] {
-    const char* v = getenv("EXON_HIP_K4_STREAM_COPIES_LOG2");  // A/B
-    return v && v[0] >= '0' && v[0] <= '3' ? v[0] - '0' : -1;
-  }();
-  if (forced >= 0) return forced;
   return n_ranges == 1 ? 2 : 0;  // measured (profiles/r6_groupby_direct.md): the main kernel slows down with the streams a wave store spreads over
 }
 struct K4Tail {                 // tier 3 (unused when NG == NL)
@@ -985,11 +950,10 @@ struct K4Tail {                 // tier 3 (unused when NG == NL)
   // partitioned form (round 3, default): instead of three global atomics per row the main kernel COMPACTS the tier-3 rows
   // into a private region per workgroup -- records {id | y-valid << 31, y bits} -- and counts them per id range of
   // K4_TAIL_RANGE ids; k4_tail_scatter then groups the records by range and k4_tail_aggregate runs the LDS table over
-  // each range.  rec == nullptr: the atomic form (EXON_HIP_K4_TAIL_ATOMICS=1, and the short tail loop of a launch).
+  // each range.  rec == nullptr: the atomic form (no scratch or too many ranges / workgroups, and the short tail loop of a launch).
   uint2* rec;                   // [grid][cap_wg]
   unsigned* wg_count;           // [grid] records each workgroup wrote
   unsigned* wg_hist;            // [grid][n_ranges] records per workgroup and id range
-  int no_uniform_test;          // EXON_HIP_K4_UNIFORM=0 (A/B): tier 2 never tests for a uniform key
   // direct partition (lists != nullptr; rec = the chunk pool)
   uint2* lists;                 // [n_ranges][list_stride] {chunk, records in it}
   unsigned list_stride;
@@ -1083,7 +1047,7 @@ __global__ __launch_bounds__(S::THREADS) void k4_cmp_avg_by_group_main(
   // 2.6 x the step time of the mixed-key case, tools/time_skew.py); then lane 0 adds the group's totals (counts from
   // ballots, the sum from a wave reduction).  The test (4 compares + a vote) is skipped for 15 groups after it found mixed
   // keys, and the mixed-key code is the plain per-row path above: this variant is instruction-bound.
-  int uni_skip = tail.no_uniform_test ? 0x7FFFFFFF : 0;  // wave-uniform
+  int uni_skip = 0;  // wave-uniform
   auto rows4_uniform = [&](int kw, unsigned p0, unsigned p1, unsigned p2, unsigned p3, float4 y4, unsigned yv) {
     if ((unsigned)kw - (unsigned)G >= (unsigned)NO) return;  // the one key lives in another tier
     const unsigned n0 = p0 & (yv >> 0 & 1), n1 = p1 & (yv >> 1 & 1), n2 = p2 & (yv >> 2 & 1), n3 = p3 & (yv >> 3 & 1);
@@ -1423,16 +1387,7 @@ __global__ __launch_bounds__(S::THREADS) void k4_cmp_avg_by_group_main(
 }
 
 constexpr int K4_OVF_REGS = 4;                   // register groups of the > 8-group variant
-// ids handled by registers + the LDS table
-static int k4_lds_groups() {
-  static const int ids = [] {
-    const char* v = getenv("EXON_HIP_K4_LDS_IDS");  // A/B: entries of the tier-2 table
-    const int k = v ? atoi(v) : 0;
-    return k >= 64 && k <= 8192 ? k : 4096;
-  }();
-  return K4_OVF_REGS + ids;
-}
-#define K4_LDS_GROUPS k4_lds_groups()
+constexpr int K4_LDS_GROUPS = K4_OVF_REGS + 4096;  // ids handled by registers + the LDS table
 static int k4_nl(int n_groups) { return n_groups < K4_LDS_GROUPS ? n_groups : K4_LDS_GROUPS; }
 
 size_t k4_partial_words(const LaunchCfg& cfg, int n_groups) { return (size_t)max_grid(cfg) * 3 * (size_t)k4_nl(n_groups); }
@@ -1516,34 +1471,6 @@ bool cmp_to_key_range(double thr, int cmp_op, bool x_is_int, int32_t* klo, int32
     *khi = (int32_t)hi;
   }
   return true;
-}
-
-// Round 2's path for more groups than the LDS table holds: ONE global atomic triple per passing row, whatever its id.
-// Kept behind EXON_HIP_K4_GLOBAL_ONLY=1 as the A/B baseline of the tiered kernel above (profiles/r3_groupby.md).
-__global__ __launch_bounds__(256) void k4_cmp_avg_by_group_global(const float* __restrict__ x, const uint8_t* __restrict__ xvalid,
-                                                                  const float* __restrict__ y, const uint8_t* __restrict__ yvalid,
-                                                                  const int32_t* __restrict__ gid, int64_t n, int32_t klo, int32_t khi,
-                                                                  int32_t negate, int32_t keymask, int32_t yint, int32_t NG,
-                                                                  unsigned long long* __restrict__ counts, double* __restrict__ sums,
-                                                                  int* __restrict__ status) {
-  bool bad = false;
-  for (int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x; r < n; r += (int64_t)gridDim.x * 256) {
-    const unsigned g = (unsigned)gid[r];
-    if (g >= (unsigned)NG) {  // ids are validated over ALL rows, like the LDS paths do
-      bad = true;
-      continue;
-    }
-    const int32_t bx = __float_as_int(x[r]);
-    const int32_t kx = bx ^ ((bx >> 31) & keymask);
-    const unsigned inr = unsigned(kx >= klo) & unsigned(kx <= khi);
-    if (!(valid1(xvalid, r) && (inr ^ (unsigned)negate))) continue;
-    atomicAdd(&counts[NG + g], 1ull);
-    if (valid1(yvalid, r)) {
-      atomicAdd(&counts[g], 1ull);
-      atomicAdd(&sums[g], yint ? (double)__float_as_int(y[r]) : (double)y[r]);
-    }
-  }
-  if (bad) atomicOr(&status[0], 4);
 }
 
 // records [blocks][3 x RG] (kinds cnn, crow, sum over the first RG ids) ADDED into a state of NG > RG groups
@@ -1840,13 +1767,6 @@ size_t k4_tail_records(int64_t n, int n_groups) {
   if (n_groups <= K4_LDS_GROUPS) return 0;
   return (size_t)(std::min<int64_t>(n, K4_TAIL_CHUNK_ROWS) + K4_TAIL_SLACK);
 }
-static bool k4_tail_atomics_forced() {
-  static const bool on = [] {
-    const char* v = getenv("EXON_HIP_K4_TAIL_ATOMICS");  // A/B: tier 3 as global atomics (round 3's first version)
-    return v && v[0] == '1';
-  }();
-  return on;
-}
 
 static hipError_t k4_one_launch(hipStream_t s, const LaunchCfg& cfg, const Workspace& ws, const float* x, const uint8_t* x_valid,
                                 const float* y, const uint8_t* y_valid, const int32_t* gid, int64_t n, int32_t klo, int32_t khi,
@@ -1855,26 +1775,18 @@ static hipError_t k4_one_launch(hipStream_t s, const LaunchCfg& cfg, const Works
   const bool has_tail = n_groups > nl;
   // K4 keeps the 16384-row tile whenever every CU gets one: measured on MI355X at 1e7 rows J = 4 27.8 us, J = 2 31.5 us
   // (its per-tile bookkeeping -- counter spills, 15-value reductions -- outweighs the better tile balance that pays for K2)
-  const bool big = n / ShapeOf<ShapeBig>::TILE >= (int64_t)cfg.compute_units && pick_shape(cfg, n) != SHAPE_SMALL;
+  const bool big = n / ShapeOf<ShapeBig>::TILE >= (int64_t)cfg.compute_units && use_big_shape(cfg, n);
   int grid = 1;
   hipError_t e;
   const FoldArgs fa = has_tail ? FoldArgs{nullptr, nullptr, nullptr, 0, 0, 0}
                                : fold_args(cfg, ws, 3 * n_groups, 2 * n_groups, d_counts, d_sums);
-  static const int no_uni = [] {
-    const char* v = getenv("EXON_HIP_K4_UNIFORM");
-    return v && v[0] == '0' ? 1 : 0;
-  }();
-  K4Tail tail{reinterpret_cast<unsigned long long*>(d_counts), d_sums, nullptr, nullptr, nullptr, no_uni, nullptr, 0, nullptr, nullptr, 0};
+  K4Tail tail{reinterpret_cast<unsigned long long*>(d_counts), d_sums, nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr, 0};
   const int n_ranges = has_tail ? (n_groups - nl + K4_TAIL_RANGE - 1) / K4_TAIL_RANGE : 0;
   // partitioned tier 3 when its scratch is there (capi.cpp sizes it with k4_tail_records) and the launch has whole tiles
-  const bool partition = has_tail && !k4_tail_atomics_forced() && ws.tail_rec_a && ws.tail_rec_b && ws.tail_u32 &&
+  const bool partition = has_tail && ws.tail_rec_a && ws.tail_rec_b && ws.tail_u32 &&
                          ws.tail_capacity >= (size_t)(n + K4_TAIL_SLACK) && n_ranges <= K4_TAIL_MAX_RANGES &&
                          max_grid(cfg) <= K4_TAIL_MAX_GRID;
   // the direct partition (round 6) when the chunk pool + the chunk lists fit the two record buffers (one allocation)
-  static const bool scatter_forced = [] {
-    const char* v = getenv("EXON_HIP_K4_TAIL_SCATTER");  // A/B: round 3's compact -> scatter -> aggregate
-    return v && v[0] == '1';
-  }();
   const int64_t tile_rows = big ? ShapeOf<ShapeBigJ2>::TILE : ShapeOf<ShapeSmall>::TILE;
   const size_t n_streams = (size_t)n_ranges << k4_stream_copies_log2(n_ranges);
   // chunks of all workgroups, at most: their rows (rounded up to tiles per workgroup) + one per stream and workgroup
@@ -1882,7 +1794,7 @@ static hipError_t k4_one_launch(hipStream_t s, const LaunchCfg& cfg, const Works
   const size_t pool_chunks = (size_t)(n + grid_ub * tile_rows) / K4_CHUNK + (size_t)grid_ub * n_streams;
   const int64_t tiles_all = n / tile_rows, grid_min = std::max<int64_t>(1, std::min<int64_t>(tiles_all, cfg.compute_units));
   const size_t cpw_max = (size_t)((tiles_all + grid_min - 1) / grid_min) * tile_rows / K4_CHUNK + n_streams;
-  const bool direct = partition && !scatter_forced && n_ranges <= K4_DIRECT_MAX_RANGES && ws.tail_rec_b == ws.tail_rec_a + ws.tail_capacity &&
+  const bool direct = partition && n_ranges <= K4_DIRECT_MAX_RANGES && ws.tail_rec_b == ws.tail_rec_a + ws.tail_capacity &&
                       pool_chunks * K4_CHUNK + (size_t)n_ranges * pool_chunks <= 2 * ws.tail_capacity &&
                       cpw_max < 65536;  // chunk numbers inside a workgroup are 16-bit
   unsigned *wg_count = nullptr, *totals = nullptr, *offsets = nullptr, *slice_start = nullptr, *wg_hist = nullptr;
@@ -1934,13 +1846,8 @@ static hipError_t k4_one_launch(hipStream_t s, const LaunchCfg& cfg, const Works
   if (has_tail) {
     hipLaunchKernelGGL(k4_finalize_head, dim3((3 * nl + 31) / 32), dim3(1024), 0, s, ws.partials, grid, nl, n_groups,
                        reinterpret_cast<unsigned long long*>(d_counts), d_sums);
-    static const int rounds_d = [] {
-      const char* v = getenv("EXON_HIP_K4_TAIL_ROUNDS");
-      const int k = v ? atoi(v) : 0;
-      return k >= 1 && k <= 16 ? k : 1;
-    }();
     if (direct) {
-      const int target = std::max(1, rounds_d * cfg.compute_units - n_ranges);
+      const int target = std::max(1, cfg.compute_units - n_ranges);
       hipLaunchKernelGGL(k4_tail_offsets, dim3(1), dim3(1024), 0, s, totals, n_ranges, offsets, target, slice_start);
       hipLaunchKernelGGL(k4_tail_aggregate_chunks, dim3(target + n_ranges), dim3(1024), 0, s, ws.tail_rec_a, tail.lists, tail.list_stride, tail.n_list,
                          slice_start, n_ranges, nl, n_groups, yint, reinterpret_cast<unsigned long long*>(d_counts), d_sums);
@@ -1948,16 +1855,10 @@ static hipError_t k4_one_launch(hipStream_t s, const LaunchCfg& cfg, const Works
       const int64_t tile = big ? ShapeOf<ShapeBigJ2>::TILE : ShapeOf<ShapeSmall>::TILE;
       const unsigned cap_wg = (unsigned)(((n / tile + grid - 1) / grid) * tile);  // the main kernel's formula
       hipLaunchKernelGGL(k4_tail_wg_scan, dim3(n_ranges), dim3(1024), 0, s, wg_hist, grid, n_ranges, totals);
-      // k4_tail_aggregate holds one workgroup per CU (128 KiB table): `rounds` workgroups per CU in all, shared out over the
-      // ranges by their records -- whole rounds, because a workgroup more than a multiple of the CUs is a round more.
-      // One round measured best (1e5 zipf keys: 3.90 / 4.07 / 4.32 / 4.54 ms per 1e9 rows for 1 / 2 / 3 / 4: every
-      // workgroup zeroes and flushes a whole table)
-      static const int rounds = [] {
-        const char* v = getenv("EXON_HIP_K4_TAIL_ROUNDS");  // A/B
-        const int k = v ? atoi(v) : 0;
-        return k >= 1 && k <= 16 ? k : 1;
-      }();
-      const int target = std::max(1, rounds * cfg.compute_units - n_ranges);  // + at most one per range from rounding up
+      // k4_tail_aggregate holds one workgroup per CU (128 KiB table): one workgroup per CU in all, shared out over the ranges
+      // by their records.  One round measured best (1e5 zipf keys: 3.90 / 4.07 / 4.32 / 4.54 ms per 1e9 rows for 1 / 2 / 3 / 4
+      // rounds: every workgroup zeroes and flushes a whole table)
+      const int target = std::max(1, cfg.compute_units - n_ranges);  // + at most one per range from rounding up
       hipLaunchKernelGGL(k4_tail_offsets, dim3(1), dim3(1024), 0, s, totals, n_ranges, offsets, target, slice_start);
       hipLaunchKernelGGL(k4_tail_scatter, dim3(grid), dim3(1024), (size_t)n_ranges * 4, s, ws.tail_rec_a, wg_count, cap_wg, nl, n_ranges, offsets,
                          wg_hist, ws.tail_rec_b);
@@ -1980,20 +1881,10 @@ hipError_t launch_cmp_avg_by_group(hipStream_t s, const LaunchCfg& cfg, const Wo
   if (!cmp_to_key_range(thr, cmp_op, cfg.x_is_int, &klo, &khi, &negate)) return hipErrorInvalidValue;
   const int32_t keymask = cfg.x_is_int ? 0 : 0x7FFFFFFF, yint = cfg.y_is_int ? 1 : 0;
   const bool has_tail = n_groups > k4_nl(n_groups);
-  static const bool global_only = [] {
-    const char* v = getenv("EXON_HIP_K4_GLOBAL_ONLY");
-    return v && v[0] == '1';
-  }();
   if (has_tail && cfg.overwrite) {  // tier 3 (and k4_finalize_head) ADD to the caller's arrays
     hipError_t e0 = hipMemsetAsync(d_counts, 0, (size_t)n_groups * 16, s);
     if (e0 == hipSuccess) e0 = hipMemsetAsync(d_sums, 0, (size_t)n_groups * 8, s);
     if (e0 != hipSuccess) return e0;
-  }
-  if (has_tail && global_only) {
-    const int grid = (int)std::min<int64_t>((n + 255) / 256, (int64_t)cfg.compute_units * 32);
-    hipLaunchKernelGGL(k4_cmp_avg_by_group_global, dim3(grid), dim3(256), 0, s, x, x_valid, y, y_valid, gid, n, klo, khi, negate, keymask, yint, n_groups,
-                       reinterpret_cast<unsigned long long*>(d_counts), d_sums, ws.status);
-    return hipGetLastError();
   }
   if (!has_tail || n <= K4_TAIL_CHUNK_ROWS)
     return k4_one_launch(s, cfg, ws, x, x_valid, y, y_valid, gid, n, klo, khi, negate, keymask, yint, n_groups, d_counts, d_sums);

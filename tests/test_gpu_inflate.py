@@ -194,12 +194,6 @@ def test_lane_parallel_block_decoder_in_a_fresh_process():
                         os.path.join(ROOT, "tests", "test_gpu_bam_parse.py"),
                         "-k", "not fresh_process"], env=env, capture_output=True, text=True, timeout=1500)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-2000:]
-    # mode 2: a share of every launch on the serial kernel, the rest on the parallel one, two streams joined by events
-    env2 = dict(os.environ, EXON_HIP_INFLATE_PAR="2", EXON_HIP_INFLATE_PAR_SERIAL_SHARE="0.5")
-    r = subprocess.run([sys.executable, "-m", "pytest", "-x", "-q", "-m", "gpu", "--timeout", "300", "-p", "no:cacheprovider",
-                        os.path.join(ROOT, "tests", "test_gpu_inflate.py"), "-k", "not fresh_process"], env=env2, capture_output=True,
-                       text=True, timeout=900)
-    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-2000:]
     # and the parallel path did decode members (a silent fall-back to the serial loop would prove nothing)
     code = ("import exon_amd, ctypes, numpy as np, sys; sys.path.insert(0, %r); import test_gpu_inflate as t;"
             "ctx = exon_amd.Context(0); raw = t.bgzf_file(t.vcf_like(40000)); got, _ = ctx.bgzf_inflate(raw);"
@@ -212,19 +206,17 @@ def test_lane_parallel_block_decoder_in_a_fresh_process():
 
 @pytest.mark.gpu
 def test_every_symbol_loop_in_a_fresh_process():
-    """EXON_HIP_INFLATE_FLAVOR picks the symbol loop of the serial kernels (read once per process): 3 = the wide loop (64 bit
-    offsets per round; default since round 5), 1 = the software-pipelined vector-unit loop with deferred far copies, 0 = the scalar
-    loop, 2 = loops 0 and 1 side by side.  Small
-    launches take the lane-parallel decoder by default, so the serial kernel is forced (EXON_HIP_INFLATE_PAR=0) and this module's
-    cases -- byte equality with zlib, CRC verification, corruption reports -- rerun under each loop."""
+    """Small launches take the lane-parallel decoder by default, whose hand-backs run symbol_run_v; the serial kernel's wide loop
+    (wide_run, every pipeline's decoder) is forced with EXON_HIP_INFLATE_PAR=0 (read once per process), and this module's cases
+    -- byte equality with zlib, CRC verification, corruption reports -- rerun under it.  (EXON_HIP_INFLATE_PAR=1 reruns them
+    through the lane-parallel decoder: test_lane_parallel_block_decoder_in_a_fresh_process.)"""
     import subprocess
     import sys
-    for flavor in ("0", "1", "2", "3"):
-        env = dict(os.environ, EXON_HIP_INFLATE_PAR="0", EXON_HIP_INFLATE_FLAVOR=flavor)
-        r = subprocess.run([sys.executable, "-m", "pytest", "-x", "-q", "-m", "gpu", "--timeout", "300", "-p", "no:cacheprovider",
-                            os.path.join(ROOT, "tests", "test_gpu_inflate.py"), "-k", "not fresh_process"], env=env, capture_output=True, text=True,
-                           timeout=1500)
-        assert r.returncode == 0, f"flavor {flavor}\n" + r.stdout[-3000:] + r.stderr[-2000:]
+    env = dict(os.environ, EXON_HIP_INFLATE_PAR="0")
+    r = subprocess.run([sys.executable, "-m", "pytest", "-x", "-q", "-m", "gpu", "--timeout", "300", "-p", "no:cacheprovider",
+                        os.path.join(ROOT, "tests", "test_gpu_inflate.py"), "-k", "not fresh_process"], env=env, capture_output=True, text=True,
+                       timeout=1500)
+    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-2000:]
 
 
 @pytest.mark.gpu

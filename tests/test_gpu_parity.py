@@ -649,12 +649,13 @@ def test_k5_ragged_reads(ctx, oracle):
 
 
 @pytest.mark.parametrize("G,dist", [(4105, "uniform"), (20_000, "uniform"), (100_000, "uniform"), (100_000, "early"), (4100 + 64 * 8192, "uniform"),
-                                    (4100 + 64 * 8192 + 1, "uniform")])
+                                    (4100 + 64 * 8192 + 1, "uniform"), (4100 + 130 * 8192 + 5, "uniform")])
 def test_k4_tier3_big_launches_with_many_id_ranges(ctx, G, dist):
-    """Launches big enough for the 1024-thread shape (>= 16384 rows per CU) with id ranges beyond the LDS table: tier 3 =
-    compact -> scatter -> aggregate, with 1, 2, 12, 64 and 65 id ranges of 8192 ids.  Counts bit-exact vs numpy, sums within the
-    budget; a second launch accumulates; the row count is not a multiple of the tile (remainder rows: atomic form).  (Round 4's
-    opt-in partition inside the main kernel, which this test was written for, was removed in round 5: bit-identical, not faster.)"""
+    """Launches big enough for the 1024-thread shape (>= 16384 rows per CU) with id ranges beyond the LDS table: tier 3 with
+    1, 2, 12, 64, 65 and 131 id ranges of 8192 ids -- the direct partition where its chunk pool fits the scratch, compact ->
+    scatter -> aggregate otherwise and always beyond 128 ranges.  Counts bit-exact vs numpy, sums within the budget; a second
+    launch accumulates; the row count is not a multiple of the tile (remainder rows: atomic form).  (Round 4's opt-in partition
+    inside the main kernel, which this test was written for, was removed in round 5: bit-identical, not faster.)"""
     from oracle import Oracle
     orc = Oracle()
     n = 6_000_000 + 4321
@@ -690,8 +691,7 @@ def test_k4_tier3_big_launches_with_many_id_ranges(ctx, G, dist):
 def test_k4_direct_partition_fills_many_chunks_per_stream(ctx, G, n):
     """Tier 3's direct partition (round 6): enough tier-3 records per workgroup and stream that every stream walks through
     several 2048-record chunks (the 6 M-row cases above stay inside their first chunk): counts bit-exact vs numpy, sums within
-    the budget, and the same again through round 3's compact -> scatter path of the library is covered by the A/B switch
-    (EXON_HIP_K4_TAIL_SCATTER=1) in tools/groupby_ab.sh."""
+    the budget.  test_k4_tier3_big_launches_with_many_id_ranges covers the compact -> scatter path (131 id ranges)."""
     rng = np.random.default_rng(G)
     af = rng.random(n, dtype=np.float32)
     q = (rng.random(n, dtype=np.float32) * 100).astype(np.float32)

@@ -36,4 +36,4 @@ for rep in range(runs):
     check = int(sum(int(c) for c in counts))
 warm = times[1:] if len(times) > 1 else times
 print(f"{kind} {rows} rows, sum(counts) {check}: consume best {min(t[0] for t in warm) * 1e3:.1f} ms, median {sorted(t[0] for t in warm)[len(warm) // 2] * 1e3:.1f} ms; "
-      f"open..close best {min(t[1] for t in warm) * 1e3:.1f} ms  [PAR={os.environ.get('EXON_HIP_INFLATE_PAR', 'auto')} share={os.environ.get('EXON_HIP_INFLATE_PAR_SERIAL_SHARE', '-')}]", flush=True)
+      f"open..close best {min(t[1] for t in warm) * 1e3:.1f} ms  [PAR={os.environ.get('EXON_HIP_INFLATE_PAR', 'auto')}]", flush=True)

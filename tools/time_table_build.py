@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Cost of one DEFLATE block header (dynamic tables) in k_inflate: same payload, k sub-blocks per BGZF block."""
+"""Cost of one DEFLATE block header (dynamic tables) in k_inflate_w: same payload, k sub-blocks per BGZF block."""
 import os, struct, sys, zlib
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
