@@ -19,7 +19,7 @@
 
 namespace exon {
 
-class BCFBatchReader {
+class BCFBatchReader : public BatchReader {
  public:
   BCFBatchReader(const std::string& path, VCFConfig cfg) : cfg_(std::move(cfg)) {
     r_.reset(new StreamSource(path, Compression::Gzip, cfg_.threads));
@@ -88,7 +88,7 @@ class BCFBatchReader {
     }
   }
 
-  bool read_batch(struct ArrowArray* out) {
+  bool read_batch(struct ArrowArray* out) override {
     PrimitiveBuilder<int32_t> chrom, filter;
     PrimitiveBuilder<int64_t> pos;
     PrimitiveBuilder<float> qual;
@@ -345,7 +345,7 @@ class BCFBatchReader {
     return true;
   }
 
-  void schema(struct ArrowSchema* out) const {
+  void schema(struct ArrowSchema* out) const override {
     std::vector<struct ArrowSchema*> kids = {new_field("i", "chrom", false, new_field("u", "", false)), new_field("l", "pos", true),
                                              new_field("f", "qual", true), new_field("i", "filter", false, new_field("u", "", false))};
     for (const auto& sp : info_specs) {

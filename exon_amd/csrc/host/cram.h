@@ -916,7 +916,7 @@ class BlockPool {
   size_t held_ = 0;
 };
 
-class CRAMBatchReader {
+class CRAMBatchReader : public BatchReader {
  public:
   CRAMBatchReader(const std::string& path, BAMConfig cfg) : cfg_(std::move(cfg)) {
     fd_ = fdh_.v = ::open(path.c_str(), O_RDONLY);
@@ -982,7 +982,7 @@ class CRAMBatchReader {
   // batches of at most batch_size rows -- a batch never spans two containers -- so this call, the only serial step of the
   // reader, hands out finished arrays.  (The reference's reader fills every batch to batch_size across container borders;
   // batch boundaries carry no meaning for the operators above a scan.)
-  bool read_batch(struct ArrowArray* out) {
+  bool read_batch(struct ArrowArray* out) override {
     while (pending_.empty())
       if (!next_container()) return false;
     *out = pending_.front().a;
@@ -990,7 +990,7 @@ class CRAMBatchReader {
     pending_.pop_front();
     return true;
   }
-  void schema(struct ArrowSchema* out) const {
+  void schema(struct ArrowSchema* out) const override {
     make_schema(out, "+s", "", false,
                 {new_field("i", "flag", false), new_field("C", "mapping_quality", true),
                  new_field("i", "reference", true, new_field("u", "", false)), new_field("l", "start", true),

@@ -33,6 +33,14 @@ namespace exon {
 
 constexpr int64_t DEFAULT_BATCH_SIZE = 8 * 1024;  // exon-common/src/lib.rs:27
 
+// What every format's reader has in common: Arrow batches (false: no rows left) and the schema they follow.
+class BatchReader {
+ public:
+  virtual ~BatchReader() = default;
+  virtual bool read_batch(struct ArrowArray* out) = 0;
+  virtual void schema(struct ArrowSchema* out) const = 0;
+};
+
 struct RegionFilter {  // pushed-down vcf_region_filter / bam_region_filter (per-record interval hit)
   bool active = false;
   Region region;
@@ -550,7 +558,7 @@ inline void parse_vcf_slab(VCFSlab& s, const void* vctx) {
   s.rows = s.b->len();
 }
 
-class VCFBatchReader {
+class VCFBatchReader : public BatchReader {
  public:
   VCFBatchReader(const std::string& path, Compression c, VCFConfig cfg) : cfg_(std::move(cfg)) {
     r_.reset(new StreamSource(path, c, cfg_.threads));
@@ -620,7 +628,7 @@ class VCFBatchReader {
   // AsyncBatchStream::read_batch (exon-vcf/src/async_batch_stream.rs:80-109); with a region filter the
   // per-record test of IndexedAsyncBatchStream::filter applies to EVERY record
   // (exon-vcf/src/indexed_async_batch_stream.rs:99-116; see DESIGN.md on the reference's unfiltered tail).
-  bool read_batch(struct ArrowArray* out) {
+  bool read_batch(struct ArrowArray* out) override {
     if (pipe_) return read_batch_parallel(out);
     if (cfg_.reference_tail_quirk && n_chunks >= 0 && cfg_.filter.active) return read_batch_reference_quirk(out);
     VCFArrayBuilder b(&chrom_dict, &filter_dict, info_specs, &info_dicts, cfg_.projection, &key_types);
@@ -722,7 +730,7 @@ class VCFBatchReader {
     return true;
   }
 
-  void schema(struct ArrowSchema* out) const {
+  void schema(struct ArrowSchema* out) const override {
     std::vector<struct ArrowSchema*> kids = {new_field("i", "chrom", false, new_field("u", "", false)),
                                              new_field("l", "pos", true), new_field("f", "qual", true),
                                              new_field("i", "filter", false, new_field("u", "", false))};
@@ -953,7 +961,7 @@ class BAMArrayBuilder : public ExonArrayBuilder {
   size_t rows_ = 0;
 };
 
-class BAMBatchReader {
+class BAMBatchReader : public BatchReader {
  public:
   BAMBatchReader(const std::string& path, BAMConfig cfg) : cfg_(std::move(cfg)) {
     r_.reset(new StreamSource(path, Compression::Gzip, cfg_.threads));
@@ -990,7 +998,7 @@ class BAMBatchReader {
   // uncompressed offset of the first record (header length), for the GPU-side inflate + record splitting
   int64_t data_offset() const { return n_chunks >= 0 ? -1 : (int64_t)static_cast<StreamSource*>(r_.get())->r.consumed(); }
 
-  bool read_batch(struct ArrowArray* out) {
+  bool read_batch(struct ArrowArray* out) override {
     BAMArrayBuilder b(&ref_names, cfg_.projection);
     std::vector<uint8_t> rec;
     while ((int64_t)b.len() < cfg_.batch_size) {
@@ -1033,7 +1041,7 @@ class BAMBatchReader {
     return true;
   }
 
-  void schema(struct ArrowSchema* out) const {
+  void schema(struct ArrowSchema* out) const override {
     std::vector<struct ArrowSchema*> kids = {new_field("i", "flag", false), new_field("C", "mapping_quality", true),
                                              new_field("i", "reference", true, new_field("u", "", false)), new_field("l", "start", true),
                                              new_field("l", "end", true)};
@@ -1068,7 +1076,7 @@ class BAMBatchReader {
 // SAM (text).  Same schema / device layout as BAM (exon-sam/src/schema_builder.rs:371-402 is shared by
 // SAM, BAM and CRAM; text reader: exon-sam/src/batch_reader.rs, array_builder.rs).
 // ======================================================================================================
-class SAMBatchReader {
+class SAMBatchReader : public BatchReader {
  public:
   SAMBatchReader(const std::string& path, Compression c, BAMConfig cfg) : r_(path, c), cfg_(std::move(cfg)) {
     std::string line;
@@ -1115,7 +1123,7 @@ class SAMBatchReader {
     return r_.release_source();
   }
 
-  bool read_batch(struct ArrowArray* out) {
+  bool read_batch(struct ArrowArray* out) override {
     BAMArrayBuilder b(&ref_names, cfg_.projection);
     std::string line;
     while ((int64_t)b.len() < cfg_.batch_size) {
@@ -1172,7 +1180,7 @@ class SAMBatchReader {
     b.try_into_record_batch(out);
     return true;
   }
-  void schema(struct ArrowSchema* out) const {
+  void schema(struct ArrowSchema* out) const override {
     std::vector<struct ArrowSchema*> kids = {new_field("i", "flag", false), new_field("C", "mapping_quality", true),
                                              new_field("i", "reference", true, new_field("u", "", false)), new_field("l", "start", true),
                                              new_field("l", "end", true)};
@@ -1260,7 +1268,7 @@ inline void parse_fastq_slab(FASTQSlab& s, const void*) {
   s.rows = s.b.len();
 }
 
-class FASTQBatchReader {
+class FASTQBatchReader : public BatchReader {
  public:
   FASTQBatchReader(const std::string& path, Compression c, FASTQConfig cfg) : r_(open_source(path, c, cfg.threads)), cfg_(cfg) {
     const int threads = cfg_.threads > 0 ? cfg_.threads : decode_threads();
@@ -1271,7 +1279,7 @@ class FASTQBatchReader {
       pipe_.reset(new SlabPipeline<FASTQSlab>(r_.release_source(), r_.take_buffered(), 4, threads,
                                               [](FASTQSlab& s, const void* c2) { parse_fastq_slab(s, c2); }, nullptr));
   }
-  bool read_batch(struct ArrowArray* out) {
+  bool read_batch(struct ArrowArray* out) override {
     if (pipe_) {
       // a slab is emitted as ONE batch (its Utf8 columns are already contiguous); slabs are ~4 MiB of text
       for (;;) {
@@ -1303,7 +1311,7 @@ class FASTQBatchReader {
     return r_.release_source();
   }
   const FASTQConfig& config() const { return cfg_; }
-  void schema(struct ArrowSchema* out) const {
+  void schema(struct ArrowSchema* out) const override {
     make_schema(out, "+s", "", false,
                 {new_field("u", "name", false), new_field("u", "description", true), new_field("u", "sequence", false),
                  new_field("u", "quality_scores", false)});
@@ -1342,11 +1350,11 @@ class FASTAArrayBuilder : public ExonArrayBuilder {
   Utf8Builder id_, desc_, seq_;
 };
 
-class FASTABatchReader {
+class FASTABatchReader : public BatchReader {
  public:
   FASTABatchReader(const std::string& path, Compression c, FASTAConfig cfg) : r_(path, c), cfg_(cfg) {}
   // exon-fasta/src/batch_reader.rs:72-99
-  bool read_batch(struct ArrowArray* out) {
+  bool read_batch(struct ArrowArray* out) override {
     FASTAArrayBuilder b;
     std::string line;
     while ((int64_t)b.len() < cfg_.batch_size) {
@@ -1383,7 +1391,7 @@ class FASTABatchReader {
     b.try_into_record_batch(out);
     return true;
   }
-  void schema(struct ArrowSchema* out) const {
+  void schema(struct ArrowSchema* out) const override {
     make_schema(out, "+s", "", false, {new_field("u", "id", false), new_field("u", "description", true), new_field("u", "sequence", false)});
   }
 

@@ -24,7 +24,26 @@
 #include "host/parallel.h"
 #include "internal.h"
 
-struct exon_hip_vcf_parser;  // gpu_parse.hip
+// The device parser of a GPU-decoded scan: whichever handle its format uses, created by the scan's first GPU-parsed consume
+struct DeviceParser {
+  int format = 0;
+  void* h = nullptr;  // exon_hip_{vcf,bcf,bam,sam,fastq}_parser of `format`
+  // the FILTER dictionary (and VCF's String INFO dictionaries) of the scan are the device parser's
+  bool owns_names = false;
+  template <class T>
+  T* as() const { return static_cast<T*>(h); }
+  void destroy() {
+    if (h) switch (format) {
+      case EXON_HIP_FORMAT_VCF: exon_hip_vcf_parser_destroy(as<exon_hip_vcf_parser>()); break;
+      case EXON_HIP_FORMAT_BCF: exon_hip_bcf_parser_destroy(as<exon_hip_bcf_parser>()); break;
+      case EXON_HIP_FORMAT_BAM: exon_hip_bam_parser_destroy(as<exon_hip_bam_parser>()); break;
+      case EXON_HIP_FORMAT_SAM: exon_hip_sam_parser_destroy(as<exon_hip_sam_parser>()); break;
+      case EXON_HIP_FORMAT_FASTQ: exon_hip_fastq_parser_destroy(as<exon_hip_fastq_parser>()); break;
+    }
+    h = nullptr;
+    owns_names = false;
+  }
+};
 
 struct exon_hip_scan {
   int format = 0;
@@ -32,12 +51,7 @@ struct exon_hip_scan {
   std::string path;
   exon_hip_scan_options opt{};
   std::string info_field_s, region_s;
-  exon_hip_vcf_parser* parser = nullptr;  // created by the first GPU-parsed consume; owns the FILTER dictionary
-  exon_hip_ctx* parser_ctx = nullptr;
-  exon_hip_fastq_parser* fq_parser = nullptr;
-  exon_hip_bam_parser* bam_parser = nullptr;
-  exon_hip_bcf_parser* bcf_parser = nullptr;
-  exon_hip_sam_parser* sam_parser = nullptr;
+  DeviceParser parser;
   struct GpuExporter* exporter = nullptr;  // exon_hip_scan_bind_ctx: batches (exon_hip_scan_next) come out of the GPU pipeline
   // opened with gpu_parse but with INFO keys only the host reader builds (String / Character values, list-valued keys): batches
   // (exon_hip_scan_next) come from the host reader, but a consume_scan whose plan reads none of those columns still takes the
@@ -46,13 +60,7 @@ struct exon_hip_scan {
   bool gpu_inflated = false;  // the last GPU-parsed consume also inflated BGZF blocks on the device
   bool gpu_decoded = false;   // the last consume decoded every record on the device (no host fallback)
   exon::Dictionary gpu_filter_dict;       // names fetched from the parser after the consume
-  std::unique_ptr<exon::VCFBatchReader> vcf;
-  std::unique_ptr<exon::BAMBatchReader> bam;
-  std::unique_ptr<exon::SAMBatchReader> sam;
-  std::unique_ptr<exon::CRAMBatchReader> cram;
-  std::unique_ptr<exon::BCFBatchReader> bcf;
-  std::unique_ptr<exon::FASTQBatchReader> fastq;
-  std::unique_ptr<exon::FASTABatchReader> fasta;
+  std::unique_ptr<exon::BatchReader> reader;  // of `format`
   int64_t rows = 0;
   exon::Dictionary bam_dict_view;  // reference names as a dictionary (ids = header order)
   // pushed-down region filter (vcf_region_filter / bam_region_filter) on the GPU decode path
@@ -60,8 +68,22 @@ struct exon_hip_scan {
   uint8_t* d_region_mask = nullptr;         // row mask of the slab being consumed (grown on demand)
   size_t region_mask_cap = 0;
   unsigned long long* d_region_pass = nullptr;  // rows kept so far in this consume
-  exon_hip_ctx* region_ctx = nullptr;
   ExonTextScratch* text_scratch = nullptr;  // device buffers of the projected string / list columns (text_columns.hip)
+
+  // the reader as its format's class (nullptr for any other format)
+  template <class R>
+  R* reader_if(int f) const { return format == f ? static_cast<R*>(reader.get()) : nullptr; }
+  exon::VCFBatchReader* vcf() const { return reader_if<exon::VCFBatchReader>(EXON_HIP_FORMAT_VCF); }
+  exon::BCFBatchReader* bcf() const { return reader_if<exon::BCFBatchReader>(EXON_HIP_FORMAT_BCF); }
+  exon::BAMBatchReader* bam() const { return reader_if<exon::BAMBatchReader>(EXON_HIP_FORMAT_BAM); }
+  exon::SAMBatchReader* sam() const { return reader_if<exon::SAMBatchReader>(EXON_HIP_FORMAT_SAM); }
+  exon::FASTQBatchReader* fastq() const { return reader_if<exon::FASTQBatchReader>(EXON_HIP_FORMAT_FASTQ); }
+  // VCF and BCF: chrom / pos / qual / filter + typed INFO columns (else BAM / SAM / CRAM's flag / mapq / ref / start / end)
+  bool vcf_like() const { return format == EXON_HIP_FORMAT_VCF || format == EXON_HIP_FORMAT_BCF; }
+  const std::vector<exon::InfoSpec>& info_specs() const { return vcf() ? vcf()->info_specs : bcf()->info_specs; }
+  std::vector<exon::Dictionary>& info_dicts() const { return vcf() ? vcf()->info_dicts : bcf()->info_dicts; }
+  exon::Dictionary& chrom_dict() const { return vcf() ? vcf()->chrom_dict : bcf()->chrom_dict; }
+  exon::Dictionary& host_filter_dict() const { return vcf() ? vcf()->filter_dict : bcf()->filter_dict; }
 };
 
 // Batches from the GPU decode pipeline (exon_hip_scan_bind_ctx + exon_hip_scan_next on a scan opened with gpu_parse): a producer
@@ -91,11 +113,7 @@ struct GpuExporter {
   // the host reader that takes over when the device hands the file back.  It lives HERE while the producer thread runs: the
   // scan's own reader (which exon_hip_scan_schema / _dictionary_* read from the consumer's thread) is never touched by the
   // producer; gpu_next moves the fallback into the scan after the thread has been joined.
-  std::unique_ptr<exon::VCFBatchReader> fb_vcf;
-  std::unique_ptr<exon::BAMBatchReader> fb_bam;
-  std::unique_ptr<exon::SAMBatchReader> fb_sam;
-  std::unique_ptr<exon::BCFBatchReader> fb_bcf;
-  std::unique_ptr<exon::FASTQBatchReader> fb_fastq;
+  std::unique_ptr<exon::BatchReader> fallback;
   bool handed_over = false;
   // A slab's columns cross PCIe while the NEXT slab is inflated and parsed: export_slab copies what it needs device to device
   // into a staging slot (the parsers reuse their output buffers), a copy stream takes it to the pinned block, and the slab's
@@ -220,19 +238,98 @@ static const char* unsupported_codec(const char* path) {
 
 // INFO kinds the GPU pipeline of THIS scan decodes: Float / Integer / Flag everywhere; Number=1 String / Character (dictionary ids,
 // the dictionary built on the device) for VCF text
-static bool info_kind_decoded_on_gpu(const exon_hip_scan* s, char kind) { return exon::info_kind_on_device(kind) || (kind == 's' && s->vcf != nullptr); }
+static bool info_kind_decoded_on_gpu(const exon_hip_scan* s, char kind) { return exon::info_kind_on_device(kind) || (kind == 's' && s->format == EXON_HIP_FORMAT_VCF); }
 
 static exon::Dictionary* dict_of(exon_hip_scan* s, int col) {
-  if (s->format == EXON_HIP_FORMAT_BCF && col == 0) return &s->bcf->chrom_dict;
-  if (s->format == EXON_HIP_FORMAT_BCF && col == 3) return s->bcf_parser ? &s->gpu_filter_dict : &s->bcf->filter_dict;
-  if (s->format == EXON_HIP_FORMAT_VCF && col == 0) return &s->vcf->chrom_dict;
-  if (s->format == EXON_HIP_FORMAT_VCF && col == 3) return s->parser ? &s->gpu_filter_dict : &s->vcf->filter_dict;
-  if ((s->format == EXON_HIP_FORMAT_BAM || s->format == EXON_HIP_FORMAT_SAM || s->format == EXON_HIP_FORMAT_CRAM) && col == 2) return &s->bam_dict_view;
+  if (!s->vcf_like()) {
+    const bool refs = s->format == EXON_HIP_FORMAT_BAM || s->format == EXON_HIP_FORMAT_SAM || s->format == EXON_HIP_FORMAT_CRAM;
+    return refs && col == 2 ? &s->bam_dict_view : nullptr;
+  }
+  if (col == 0) return &s->chrom_dict();
+  if (col == 3) return s->parser.owns_names ? &s->gpu_filter_dict : &s->host_filter_dict();
   // string INFO fields (scan columns 4 ..) are dictionary-encoded by the host readers
-  if (s->format == EXON_HIP_FORMAT_VCF && col >= 4 && (size_t)(col - 4) < s->vcf->info_specs.size() && (s->vcf->info_specs[(size_t)(col - 4)].kind == 's' || s->vcf->info_specs[(size_t)(col - 4)].kind == 'S'))
-    return &s->vcf->info_dicts[(size_t)(col - 4)];
-  if (s->format == EXON_HIP_FORMAT_BCF && col >= 4 && (size_t)(col - 4) < s->bcf->info_specs.size() && (s->bcf->info_specs[(size_t)(col - 4)].kind == 's' || s->bcf->info_specs[(size_t)(col - 4)].kind == 'S'))
-    return &s->bcf->info_dicts[(size_t)(col - 4)];
+  const std::vector<exon::InfoSpec>& specs = s->info_specs();
+  if (col >= 4 && (size_t)(col - 4) < specs.size() && (specs[(size_t)(col - 4)].kind == 's' || specs[(size_t)(col - 4)].kind == 'S'))
+    return &s->info_dicts()[(size_t)(col - 4)];
+  return nullptr;
+}
+
+static exon::Compression compression_of(const exon_hip_scan_options& o) {
+  return o.compression == EXON_HIP_COMPRESSION_GZIP ? exon::Compression::Gzip : o.compression == EXON_HIP_COMPRESSION_NONE ? exon::Compression::None : exon::Compression::Auto;
+}
+
+// EXON_HIP_REFERENCE_QUIRKS=1: an indexed VCF scan reproduces the reference's unfiltered tail after a full batch of hits
+// (exon-vcf/src/indexed_async_batch_stream.rs:143-154) -- a property of its per-chunk record loop, so the host reader runs it;
+// default: every record is tested (what vcf_region_filter documents)
+static bool reference_tail_quirk(const exon::RegionFilter& rf) {
+  const char* qv = getenv("EXON_HIP_REFERENCE_QUIRKS");
+  return qv && qv[0] == '1' && rf.active && rf.use_index;
+}
+
+// Who decodes the records of a scan: the device (the host reader reads the header only and does not start its decode pipeline;
+// one thread when the device inflates the file too), or the host reader (every record, its own threads).
+enum class Decode { Device, Host };
+
+// The scan's host reader, opened for `mode`.  A scan that has one already re-opens it from the start with the same config (the
+// caller replaces it); otherwise the config comes from the scan's options.
+static std::unique_ptr<exon::BatchReader> open_reader(const exon_hip_scan& s, Decode mode) {
+  const bool device = mode == Decode::Device;
+  const int threads = device && wants_gpu_inflate(&s.opt, s.path.c_str()) ? 1 : 0;
+  const exon::Compression c = compression_of(s.opt);
+  // the config of the reader being replaced, else `fresh`; the threads of `mode` either way
+  auto config = [&](const auto* r, auto fresh) {
+    auto cfg = r ? r->config() : fresh;
+    cfg.threads = threads;
+    return cfg;
+  };
+  const int64_t bs = s.opt.batch_size > 0 ? s.opt.batch_size : exon::DEFAULT_BATCH_SIZE;
+  exon::RegionFilter rf = s.region;  // index chunks are planned for VCF (tabix) and BAM (BAI)
+  rf.use_index = rf.use_index && (s.format == EXON_HIP_FORMAT_VCF || s.format == EXON_HIP_FORMAT_BAM);
+  exon::VCFConfig vc;
+  vc.batch_size = bs;
+  vc.info_field = s.info_field_s;
+  vc.filter = rf;
+  vc.projection = s.opt.projection;
+  exon::BAMConfig ac;
+  ac.batch_size = bs;
+  ac.filter = rf;
+  ac.projection = s.opt.projection;
+  switch (s.format) {
+    case EXON_HIP_FORMAT_VCF: {
+      vc.reference_tail_quirk = reference_tail_quirk(rf);
+      exon::VCFConfig cfg = config(s.vcf(), vc);
+      cfg.defer_decode = device;
+      return std::unique_ptr<exon::BatchReader>(new exon::VCFBatchReader(s.path, c, cfg));
+    }
+    case EXON_HIP_FORMAT_BCF: return std::unique_ptr<exon::BatchReader>(new exon::BCFBatchReader(s.path, config(s.bcf(), vc)));
+    case EXON_HIP_FORMAT_BAM: return std::unique_ptr<exon::BatchReader>(new exon::BAMBatchReader(s.path, config(s.bam(), ac)));
+    case EXON_HIP_FORMAT_SAM: return std::unique_ptr<exon::BatchReader>(new exon::SAMBatchReader(s.path, c, config(s.sam(), ac)));
+    case EXON_HIP_FORMAT_CRAM: return std::unique_ptr<exon::BatchReader>(new exon::CRAMBatchReader(s.path, ac));  // (host decoder only)
+    case EXON_HIP_FORMAT_FASTQ: {
+      exon::FASTQConfig fresh;
+      fresh.batch_size = bs;
+      exon::FASTQConfig cfg = config(s.fastq(), fresh);
+      cfg.defer_decode = device;
+      return std::unique_ptr<exon::BatchReader>(new exon::FASTQBatchReader(s.path, c, cfg));
+    }
+    case EXON_HIP_FORMAT_FASTA: {
+      exon::FASTAConfig cfg;
+      cfg.batch_size = bs;
+      return std::unique_ptr<exon::BatchReader>(new exon::FASTABatchReader(s.path, c, cfg));
+    }
+  }
+  throw std::runtime_error("unknown format " + std::to_string(s.format));
+}
+
+// the contig / reference names of the file's header (ids = header order)
+static const std::vector<std::string>* contig_names(const exon_hip_scan* s) {
+  switch (s->format) {
+    case EXON_HIP_FORMAT_VCF: return &s->vcf()->header.contigs;
+    case EXON_HIP_FORMAT_BCF: return &s->bcf()->header.contigs;
+    case EXON_HIP_FORMAT_BAM: return &s->bam()->ref_names;
+    case EXON_HIP_FORMAT_SAM: return &s->sam()->ref_names;
+    case EXON_HIP_FORMAT_CRAM: return &s->reader_if<exon::CRAMBatchReader>(EXON_HIP_FORMAT_CRAM)->ref_names;
+  }
   return nullptr;
 }
 
@@ -251,10 +348,6 @@ int exon_hip_scan_open(const char* path, const exon_hip_scan_options* o, exon_hi
     s->opt = *o;
     s->info_field_s = o->info_field ? o->info_field : "";
     s->region_s = o->region ? o->region : "";
-    const exon::Compression c = o->compression == EXON_HIP_COMPRESSION_GZIP   ? exon::Compression::Gzip
-                                : o->compression == EXON_HIP_COMPRESSION_NONE ? exon::Compression::None
-                                                                              : exon::Compression::Auto;
-    const int64_t bs = o->batch_size > 0 ? o->batch_size : exon::DEFAULT_BATCH_SIZE;
     exon::RegionFilter rf;
     if (o->region && o->region[0]) {
       std::string err;
@@ -266,12 +359,7 @@ int exon_hip_scan_open(const char* path, const exon_hip_scan_options* o, exon_hi
     if (o->projection && o->format != EXON_HIP_FORMAT_VCF && o->format != EXON_HIP_FORMAT_BAM && o->format != EXON_HIP_FORMAT_BCF && o->format != EXON_HIP_FORMAT_SAM)
       return fail(nullptr, EXON_HIP_EUNSUPPORTED, "exon_hip_scan_options.projection: the id / ref / alt (/ info / formats) and name / cigar / sequence / quality_score columns are built for VCF, BCF, BAM and SAM scans");
     switch (o->format) {
-      case EXON_HIP_FORMAT_VCF: {
-        exon::VCFConfig cfg;
-        cfg.batch_size = bs;
-        cfg.info_field = o->info_field ? o->info_field : "";
-        cfg.filter = rf;
-        cfg.projection = o->projection;
+      case EXON_HIP_FORMAT_VCF:
         if (o->projection & ~31ull) return fail(nullptr, EXON_HIP_EINVAL, "projection 0x%llx: VCF knows EXON_HIP_PROJECT_VCF_ID / _REF / _ALT / _INFO / _FORMATS", (unsigned long long)o->projection);
         // a pushed-down region filter rides along as a row mask (k_region_mask); with use_index the host plans the
         // tabix chunks and only their BGZF blocks are shipped (indexed scans are BGZF by definition)
@@ -282,105 +370,42 @@ int exon_hip_scan_open(const char* path, const exon_hip_scan_options* o, exon_hi
           s->gpu_candidate = s->gpu_parse;  // (a fused plan never reads them: exon_hip_stream_consume_scan may still decode on the device)
           s->gpu_parse = false;
         }
-        // EXON_HIP_REFERENCE_QUIRKS=1: an indexed VCF scan reproduces the reference's unfiltered tail after a full batch of
-        // hits (exon-vcf/src/indexed_async_batch_stream.rs:143-154) -- a property of its per-chunk record loop, so the host
-        // reader runs it; default: every record is tested (what vcf_region_filter documents)
-        if (const char* qv = getenv("EXON_HIP_REFERENCE_QUIRKS"); qv && qv[0] == '1' && rf.active && rf.use_index) {
-          cfg.reference_tail_quirk = true;
-          s->gpu_parse = false;
-        }
-        cfg.defer_decode = s->gpu_parse;
-        if (s->gpu_parse && wants_gpu_inflate(o, path)) cfg.threads = 1;  // only the header is read on the host
-        s->vcf.reset(new exon::VCFBatchReader(path, c, cfg));
-        if (s->gpu_parse) {
-          bool string_info = false;
-          for (const auto& sp : s->vcf->info_specs) string_info |= !info_kind_decoded_on_gpu(s.get(), sp.kind);
-          if (string_info) {  // string / list INFO columns are built by the host reader only: batches come from there
-            s->gpu_parse = false;
-            s->gpu_candidate = true;
-            cfg.defer_decode = false;
-            cfg.threads = 0;
-            s->vcf.reset(new exon::VCFBatchReader(path, c, cfg));
-          }
-        }
+        if (reference_tail_quirk(rf)) s->gpu_parse = false;
         break;
-      }
-      case EXON_HIP_FORMAT_BAM: {
-        exon::BAMConfig cfg;
-        cfg.batch_size = bs;
-        cfg.filter = rf;
-        cfg.projection = o->projection;
+      case EXON_HIP_FORMAT_BAM:
         if (o->projection & ~15ull) return fail(nullptr, EXON_HIP_EINVAL, "projection 0x%llx: BAM knows EXON_HIP_PROJECT_BAM_NAME / _CIGAR / _SEQUENCE / _QUALITY_SCORES", (unsigned long long)o->projection);
         // BAM is BGZF by definition: the GPU path inflates and splits records on the device or is not taken at all
         s->gpu_parse = wants_gpu_inflate(o, path);  // with a region: row mask on the device, BAI chunks planned on the host
-        if (s->gpu_parse) cfg.threads = 1;  // only the header is read on the host
-        s->bam.reset(new exon::BAMBatchReader(path, cfg));
-        s->bam_dict_view.names = s->bam->ref_names;
         break;
-      }
-      case EXON_HIP_FORMAT_BCF: {
-        exon::VCFConfig cfg;
-        cfg.batch_size = bs;
-        cfg.info_field = o->info_field ? o->info_field : "";
-        cfg.filter = rf;
-        cfg.filter.use_index = false;
-        cfg.projection = o->projection;
+      case EXON_HIP_FORMAT_BCF:
         if (o->projection & ~7ull) return fail(nullptr, EXON_HIP_EINVAL, "projection 0x%llx: BCF knows EXON_HIP_PROJECT_VCF_ID / _REF / _ALT", (unsigned long long)o->projection);
         s->gpu_parse = wants_gpu_inflate(o, path);  // BCF is BGZF by definition; a region becomes a row mask (id / ref / alt come from the device too)
-        if (s->gpu_parse) cfg.threads = 1;  // only the header is read on the host
-        s->bcf.reset(new exon::BCFBatchReader(path, cfg));
-        if (s->gpu_parse) {
-          bool string_info = false;
-          for (const auto& sp : s->bcf->info_specs) string_info |= !exon::info_kind_on_device(sp.kind);
-          if (string_info) {
-            s->gpu_parse = false;
-            s->gpu_candidate = true;
-            cfg.threads = 0;
-            s->bcf.reset(new exon::BCFBatchReader(path, cfg));
-          }
-        }
         break;
-      }
-      case EXON_HIP_FORMAT_SAM: {
-        exon::BAMConfig cfg;
-        cfg.batch_size = bs;
-        cfg.filter = rf;
-        cfg.filter.use_index = false;
-        cfg.projection = o->projection;
+      case EXON_HIP_FORMAT_SAM:
         if (o->projection & ~15ull) return fail(nullptr, EXON_HIP_EINVAL, "projection 0x%llx: SAM knows EXON_HIP_PROJECT_BAM_NAME / _CIGAR / _SEQUENCE / _QUALITY_SCORES", (unsigned long long)o->projection);
         s->gpu_parse = o->gpu_parse != 0;  // (the text columns come from the device too: text_columns.hip, k_sam_measure / k_sam_fill)
-        s->sam.reset(new exon::SAMBatchReader(path, c, cfg));
-        s->bam_dict_view.names = s->sam->ref_names;
         break;
-      }
-      case EXON_HIP_FORMAT_CRAM: {  // host decoder only: the columns go to HBM through the staging path
-        exon::BAMConfig cfg;
-        cfg.batch_size = bs;
-        cfg.filter = rf;
-        cfg.filter.use_index = false;
-        s->gpu_parse = false;
-        s->cram.reset(new exon::CRAMBatchReader(path, cfg));
-        s->bam_dict_view.names = s->cram->ref_names;
-        break;
-      }
-      case EXON_HIP_FORMAT_FASTQ: {
-        exon::FASTQConfig cfg;
-        cfg.batch_size = bs;
+      case EXON_HIP_FORMAT_FASTQ:
         s->gpu_parse = o->gpu_parse != 0;
-        cfg.defer_decode = s->gpu_parse;
-        if (s->gpu_parse && wants_gpu_inflate(o, path)) cfg.threads = 1;
-        s->fastq.reset(new exon::FASTQBatchReader(path, c, cfg));
         break;
-      }
-      case EXON_HIP_FORMAT_FASTA: {
-        exon::FASTAConfig cfg;
-        cfg.batch_size = bs;
-        s->fasta.reset(new exon::FASTABatchReader(path, c, cfg));
+      case EXON_HIP_FORMAT_CRAM:
+      case EXON_HIP_FORMAT_FASTA:
         break;
-      }
       default:
         return fail(nullptr, EXON_HIP_EINVAL, "unknown format %d", o->format);
     }
+    s->reader = open_reader(*s, s->gpu_parse ? Decode::Device : Decode::Host);
+    if (s->gpu_parse && s->vcf_like()) {
+      bool string_info = false;
+      for (const auto& sp : s->info_specs()) string_info |= !info_kind_decoded_on_gpu(s.get(), sp.kind);
+      if (string_info) {  // string / list INFO columns are built by the host reader only: batches come from there
+        s->gpu_parse = false;
+        s->gpu_candidate = true;
+        s->reader = open_reader(*s, Decode::Host);
+      }
+    }
+    if (!s->vcf_like())
+      if (const std::vector<std::string>* refs = contig_names(s.get())) s->bam_dict_view.names = *refs;
     *out = s.release();
     return EXON_HIP_OK;
   } catch (const std::exception& e) {
@@ -391,13 +416,7 @@ int exon_hip_scan_open(const char* path, const exon_hip_scan_options* o, exon_hi
 int exon_hip_scan_schema(exon_hip_scan* s, struct ArrowSchema* out) {
   if (!s || !out) return fail(nullptr, EXON_HIP_EINVAL, "exon_hip_scan_schema: NULL argument");
   try {
-    if (s->vcf) s->vcf->schema(out);
-    else if (s->bam) s->bam->schema(out);
-    else if (s->sam) s->sam->schema(out);
-    else if (s->cram) s->cram->schema(out);
-    else if (s->bcf) s->bcf->schema(out);
-    else if (s->fastq) s->fastq->schema(out);
-    else s->fasta->schema(out);
+    s->reader->schema(out);
     return EXON_HIP_OK;
   } catch (const std::exception& e) {
     return fail(nullptr, EXON_HIP_EINVAL, "%s", e.what());
@@ -411,15 +430,7 @@ int exon_hip_scan_next(exon_hip_scan* s, struct ArrowArray* out) {
     return fail(nullptr, EXON_HIP_ESTATE, "this scan was opened with gpu_parse: use exon_hip_stream_consume_scan, or exon_hip_scan_bind_ctx for batches from the GPU pipeline");
   try {
     memset(out, 0, sizeof *out);
-    bool got;
-    if (s->vcf) got = s->vcf->read_batch(out);
-    else if (s->bam) got = s->bam->read_batch(out);
-    else if (s->sam) got = s->sam->read_batch(out);
-    else if (s->cram) got = s->cram->read_batch(out);
-    else if (s->bcf) got = s->bcf->read_batch(out);
-    else if (s->fastq) got = s->fastq->read_batch(out);
-    else got = s->fasta->read_batch(out);
-    if (!got) return 1;
+    if (!s->reader->read_batch(out)) return 1;
     s->rows += out->length;
     return EXON_HIP_OK;
   } catch (const std::exception& e) {
@@ -463,7 +474,7 @@ int exon_hip_scan_rows(exon_hip_scan* s, int64_t* rows) {
 
 int exon_hip_scan_index_chunks(exon_hip_scan* s, int32_t* n) {
   if (!s || !n) return fail(nullptr, EXON_HIP_EINVAL, "NULL argument");
-  *n = s->vcf ? s->vcf->n_chunks : s->bam ? s->bam->n_chunks : -1;
+  *n = s->vcf() ? s->vcf()->n_chunks : s->bam() ? s->bam()->n_chunks : -1;
   return EXON_HIP_OK;
 }
 
@@ -493,7 +504,7 @@ int exon_hip_index_query(const char* index_path, int32_t is_bai, const char* ref
 int exon_hip_scan_bind_ctx(exon_hip_scan* s, exon_hip_ctx* ctx) {
   if (!s || !ctx) return fail(ctx, EXON_HIP_EINVAL, "exon_hip_scan_bind_ctx: NULL argument");
   if (s->exporter) return fail(ctx, EXON_HIP_ESTATE, "the scan is bound to a context already");
-  if (!(s->vcf || s->bcf || s->bam || s->sam || s->fastq))
+  if (s->format == EXON_HIP_FORMAT_FASTA || s->format == EXON_HIP_FORMAT_CRAM)
     return fail(ctx, EXON_HIP_EUNSUPPORTED, "batches from the GPU pipeline: VCF, BCF, BAM, SAM and FASTQ scans (FASTA / CRAM batches come from the host readers)");
   if (!s->gpu_parse)  // not opened with gpu_parse, or String / list-valued INFO keys were named: the host reader builds those columns
     return fail(ctx, EXON_HIP_EUNSUPPORTED, "this scan's batches come from the host reader (opened without gpu_parse, or it names INFO keys only the host reader builds)");
@@ -505,11 +516,7 @@ int exon_hip_scan_bind_ctx(exon_hip_scan* s, exon_hip_ctx* ctx) {
 
 int exon_hip_scan_close(exon_hip_scan* s) {
   if (s && s->exporter) gpu_export_shutdown(s);
-  if (s && s->parser) exon_hip_vcf_parser_destroy(s->parser);
-  if (s && s->fq_parser) exon_hip_fastq_parser_destroy(s->fq_parser);
-  if (s && s->bam_parser) exon_hip_bam_parser_destroy(s->bam_parser);
-  if (s && s->bcf_parser) exon_hip_bcf_parser_destroy(s->bcf_parser);
-  if (s && s->sam_parser) exon_hip_sam_parser_destroy(s->sam_parser);
+  if (s) s->parser.destroy();
   if (s && s->text_scratch) exon_text_scratch_destroy(s->text_scratch);
   if (s && s->d_region_mask) hipFree(s->d_region_mask);
   if (s && s->d_region_pass) hipFree(s->d_region_pass);
@@ -815,13 +822,20 @@ void exon_hip_release_ctx_caches(exon_hip_ctx* ctx) {
 
 class GpuTextSource {
  public:
-  // trim_last (BGZF only): inflated bytes to drop behind the last block -- an index chunk ends inside its last block
-  // gz: `src` delivers the RAW bytes of a plain-gzip (non-BGZF) file; they cross PCIe as they are and are inflated on the GPU
-  // (gzip_stream.hip) straight into the text buffer -- everything downstream is the plain-text mode
-  GpuTextSource(exon_hip_ctx* ctx, hipStream_t hs, std::unique_ptr<exon::ByteSource> src, bool bgzf, uint64_t skip_first,
-                std::string carry, bool binary = false, bool text_async = false, size_t trim_last = 0, bool gz = false)
-      : ctx_(ctx), hs_(hs), src_(std::move(src)), rd_(src_.get()), bgzf_(bgzf), binary_(binary), text_async_(text_async), gz_(gz), skip_(skip_first),
-        trim_last_(trim_last), carry_(std::move(carry)) {
+  // What `src` delivers.  Text: the records' bytes as they are.  Bgzf: BGZF blocks, inflated on the GPU (inflate.hip).  Gzip: the
+  // RAW bytes of a plain-gzip (non-BGZF) file; they cross PCIe as they are and are inflated on the GPU (gzip_stream.hip) straight
+  // into the text buffer -- everything downstream is the plain-text mode.
+  enum class Kind { Text, Bgzf, Gzip };
+  struct Options {
+    uint64_t skip_first = 0;  // Bgzf / Gzip: inflated bytes in front of the first record (the header, or an index chunk's head)
+    std::string carry;        // Text: what the host header reader had buffered (goes in front of the first slab)
+    bool binary = false;      // binary records (BAM, BCF): no line structure
+    bool text_async = false;  // the consumer's kernels read the slab text after the parser has returned (FASTQ views)
+    size_t trim_last = 0;     // Bgzf: inflated bytes to drop behind the last block -- an index chunk ends inside its last block
+  };
+  GpuTextSource(exon_hip_ctx* ctx, hipStream_t hs, std::unique_ptr<exon::ByteSource> src, Kind kind, Options o)
+      : ctx_(ctx), hs_(hs), src_(std::move(src)), rd_(src_.get()), bgzf_(kind == Kind::Bgzf), binary_(o.binary), text_async_(o.text_async),
+        gz_(kind == Kind::Gzip), skip_(o.skip_first), trim_last_(o.trim_last), carry_(std::move(o.carry)) {
     slab_ = gz_ ? gz_slab_bytes() : slab_bytes(bgzf_ && !text_async_);
     ring_geometry();
     local_cpus_ = gpu_local_cpus(ctx_->device);
@@ -1606,12 +1620,12 @@ class GpuTextSource {
   std::unique_ptr<exon::ByteSource> src_;
   SlabReader rd_;
   bool bgzf_, binary_;
-  bool text_async_;  // the consumer's kernels read the slab text after the parser has returned (FASTQ views)
+  bool text_async_;
   bool gz_ = false;  // plain gzip inflated on the GPU (the text side is the plain mode)
   hipEvent_t ev_carry_ = nullptr;
   uint64_t skip_;
   size_t trim_last_ = 0;
-  std::string carry_;      // plain: what the host header reader had buffered (goes in front of the first slab)
+  std::string carry_;
   size_t carry_dev_ = 0;   // bytes of the carried tail (lives in d_text_[carry_k_] at carry_off_ until the next slab is taken)
   size_t slab_ = 0, comp_cap_ = 0, text_cap_ = 0, gap_ = 0, hcap_ = 0;
   bool complete_ = false;  // all buffers allocated (only complete sets go back to the cache)
@@ -1738,31 +1752,28 @@ static std::vector<ChunkRange> plan_chunk_ranges(const std::string& path, const 
 // the pushed-down region as (dictionary id, [a, b]) for the device row mask; id < 0: no row can match
 static void region_target(const exon_hip_scan* scan, int32_t* id, int64_t* a, int64_t* b, bool* range_form) {
   const exon::Region& rg = scan->region.region;
-  const std::vector<std::string>* names = scan->vcf   ? &scan->vcf->header.contigs
-                                          : scan->bcf ? &scan->bcf->header.contigs
-                                          : scan->bam ? &scan->bam->ref_names
-                                                      : &scan->sam->ref_names;
+  const std::vector<std::string>* names = contig_names(scan);
   *id = -1;
   for (size_t i = 0; i < names->size(); ++i)
     if ((*names)[i] == rg.name) *id = (int32_t)i;
   *a = rg.start;
   *b = rg.end;
-  *range_form = scan->bam != nullptr || scan->sam != nullptr;
+  *range_form = !scan->vcf_like();
 }
 
-// VCF / FASTQ file -> text slabs in HBM (GpuTextSource) -> GPU parser -> fused kernel.  Returns 1 when the device could
-// not decide something: the caller restores the state and re-decodes the file on the host.
 // FILTER dictionary of the device parser, names in id order
 static int gpu_filter_names(exon_hip_scan* scan, std::vector<std::string>* names) {
   names->clear();
   int rc = EXON_HIP_OK;
-  if (scan->bcf && scan->bcf_parser) {
+  if (!scan->parser.owns_names) return rc;
+  if (exon::BCFBatchReader* bcf = scan->bcf()) {
+    exon_hip_bcf_parser* p = scan->parser.as<exon_hip_bcf_parser>();
     int32_t nf = 0;
-    rc = exon_hip_bcf_parser_filters(scan->bcf_parser, nullptr, nullptr, 0, &nf);
+    rc = exon_hip_bcf_parser_filters(p, nullptr, nullptr, 0, &nf);
     std::vector<int32_t> lists((size_t)std::max(nf, 1) * 8), counts((size_t)std::max(nf, 1));
-    if (!rc) rc = exon_hip_bcf_parser_filters(scan->bcf_parser, lists.data(), counts.data(), nf, &nf);
+    if (!rc) rc = exon_hip_bcf_parser_filters(p, lists.data(), counts.data(), nf, &nf);
     if (rc) return rc;
-    const std::vector<std::string>& strs = scan->bcf->strings();
+    const std::vector<std::string>& strs = bcf->strings();
     for (int32_t i = 0; i < nf; ++i) {
       std::string name;
       for (int32_t k = 0; k < counts[(size_t)i]; ++k) {
@@ -1771,10 +1782,10 @@ static int gpu_filter_names(exon_hip_scan* scan, std::vector<std::string>* names
       }
       names->push_back(name);
     }
-  } else if (scan->vcf && scan->parser) {
+  } else {
     int32_t nf = 0;
     std::vector<char> buf(1 << 20);
-    rc = exon_hip_vcf_parser_filters(scan->parser, buf.data(), buf.size(), &nf);
+    rc = exon_hip_vcf_parser_filters(scan->parser.as<exon_hip_vcf_parser>(), buf.data(), buf.size(), &nf);
     if (rc) return rc;
     size_t o = 0;
     for (int32_t i = 0; i < nf; ++i) {
@@ -1788,8 +1799,8 @@ static int gpu_filter_names(exon_hip_scan* scan, std::vector<std::string>* names
 // the value dictionaries of the String INFO keys the device decoded (VCF text): names[k] for scan column 4 + k (empty for other kinds)
 static int gpu_info_names(exon_hip_scan* scan, std::vector<std::vector<std::string>>* names) {
   names->clear();
-  if (!scan->vcf || !scan->parser) return EXON_HIP_OK;
-  const std::vector<exon::InfoSpec>& specs = scan->vcf->info_specs;
+  if (!scan->vcf() || !scan->parser.owns_names) return EXON_HIP_OK;
+  const std::vector<exon::InfoSpec>& specs = scan->vcf()->info_specs;
   names->resize(specs.size());
   int q = 0;
   std::vector<char> buf;
@@ -1798,7 +1809,7 @@ static int gpu_info_names(exon_hip_scan* scan, std::vector<std::vector<std::stri
     if (specs[k].kind == 's') {
       int32_t nv = 0;
       buf.resize(2u << 20);
-      const int rc = exon_hip_vcf_parser_info_values(scan->parser, q, buf.data(), buf.size(), &nv);
+      const int rc = exon_hip_vcf_parser_info_values(scan->parser.as<exon_hip_vcf_parser>(), q, buf.data(), buf.size(), &nv);
       if (rc) return rc;
       size_t o = 0;
       for (int32_t i = 0; i < nv; ++i) {
@@ -1895,8 +1906,16 @@ static thread_local double g_t_text_kernels = 0, g_t_fetch_text = 0, g_t_fetch_c
 // zero offsets for the item-less `alt` lists of a batch: every batch of up to K_ZERO_ROWS rows points at the same static array
 static constexpr int64_t K_ZERO_ROWS = 65000;
 static const int32_t k_zero_offsets[K_ZERO_ROWS + 64] = {0};
-static int fetch_text(exon_hip_ctx* ctx, SlabCopier* cp, size_t also_reserve, int64_t n_rows, uint64_t projection, const ExonVcfText* vt, const ExonBamText* bt, HostText* h,
-                      bool big_batches, const ExonBcfText* ct = nullptr) {
+// the projected text columns of one slab: `build` fills the member of `format` on the device (export_slab calls it once it knows
+// that the slab keeps rows at all)
+struct SlabText {
+  int format = 0;
+  ExonVcfText vcf;
+  ExonBamText bam;  // BAM and SAM
+  ExonBcfText bcf;
+  std::function<int()> build;
+};
+static int fetch_text(exon_hip_ctx* ctx, SlabCopier* cp, size_t also_reserve, int64_t n_rows, uint64_t projection, const SlabText& t, HostText* h, bool big_batches) {
   h->projection = projection;
   struct Want {
     std::function<void(const uint8_t*)> place;  // points the span at its bytes inside the block
@@ -1910,7 +1929,8 @@ static int fetch_text(exon_hip_ctx* ctx, SlabCopier* cp, size_t also_reserve, in
     wants.push_back(Want{[sp, count](const uint8_t* at) { sp->p = reinterpret_cast<const T*>(at); sp->n = count; }, src, count, sizeof(T)});
   };
   const size_t n = (size_t)n_rows, nb = (n + 7) / 8;
-  if (vt) {
+  if (t.format == EXON_HIP_FORMAT_VCF) {
+    const ExonVcfText* vt = &t.vcf;
     h->vcf = true;
     if (projection & EXON_HIP_PROJECT_VCF_ID) {
       get(h->off[0], vt->id_list_offsets, n + 1);
@@ -1927,7 +1947,8 @@ static int fetch_text(exon_hip_ctx* ctx, SlabCopier* cp, size_t also_reserve, in
       if (big_batches) get(h->zeros, nullptr, n + 1);  // (no source: cleared below; batches of up to 65 000 rows share a static array)
     }
   }
-  if (ct) {  // BCF: lists with their items, never NULL (eager_array_builder.rs:112-134)
+  if (t.format == EXON_HIP_FORMAT_BCF) {  // lists with their items, never NULL (eager_array_builder.rs:112-134)
+    const ExonBcfText* ct = &t.bcf;
     h->bcf = true;
     if (projection & EXON_HIP_PROJECT_VCF_ID) {
       get(h->off[0], ct->id_list_offsets, n + 1);
@@ -1944,7 +1965,8 @@ static int fetch_text(exon_hip_ctx* ctx, SlabCopier* cp, size_t also_reserve, in
       get(h->val[1], ct->alt_values, (size_t)ct->n_alt_bytes);
     }
   }
-  if (bt) {
+  if (t.format == EXON_HIP_FORMAT_BAM || t.format == EXON_HIP_FORMAT_SAM) {
+    const ExonBamText* bt = &t.bam;
     h->bam = true;
     if (projection & EXON_HIP_PROJECT_BAM_NAME) {
       get(h->off[0], bt->name_offsets, n + 1);
@@ -2106,8 +2128,36 @@ static void text_batch(const HostText& h, const int64_t* rows, int64_t r0, int64
   }
 }
 
-static int export_slab(exon_hip_scan* scan, const exon_hip_column* sc, int64_t n_rows, const uint8_t* row_mask, hipStream_t hs, const ExonVcfText* vt = nullptr,
-                       const ExonBamText* bt = nullptr, const std::function<int()>* build_text = nullptr, const ExonBcfText* ct = nullptr) {
+// the batches of the slab before this one (export_slab: their copy ran under this slab's inflate and parse); the last slab's (its
+// copy has nothing left to hide behind); those in front of a hand-over to the host reader, which continues behind the rows EMITTED
+static int export_flush(exon_hip_scan* scan) {
+  GpuExporter* ex = scan->exporter;
+  if (!ex || !ex->pending) return EXON_HIP_OK;
+  std::function<int()> emit;
+  emit.swap(ex->pending);
+  return emit();
+}
+
+// a batch of `n` rows onto the exporter's queue (waits while it is full); 2: the consumer has gone away, the batch is dropped
+static int push_batch(GpuExporter* ex, struct ArrowArray* out, int64_t n) {
+  const double te0 = now_s();
+  std::unique_lock<std::mutex> lk(ex->mu);
+  ex->cv_put.wait(lk, [&] { return ex->stop || ex->q.size() < ex->cap; });
+  g_t_enqueue += now_s() - te0;
+  if (ex->stop) {
+    lk.unlock();
+    out->release(out);
+    free(out);
+    return 2;
+  }
+  ex->q.push_back(out);
+  ex->emitted += n;
+  lk.unlock();
+  ex->cv_get.notify_one();
+  return EXON_HIP_OK;
+}
+
+static int export_slab(exon_hip_scan* scan, const exon_hip_column* sc, int64_t n_rows, const uint8_t* row_mask, hipStream_t hs, SlabText* projected) {
   GpuExporter* ex = scan->exporter;
   exon_hip_ctx* ctx = ex->ctx;
   // A pushed-down region: the row mask comes back first.  A slab that keeps nothing sends nothing else; when the kept rows are
@@ -2167,20 +2217,14 @@ static int export_slab(exon_hip_scan* scan, const exon_hip_column* sc, int64_t n
       runs.clear();
     }
   }
-  // the batches of the slab before this one: its copy ran under this slab's inflate and parse
-  if (ex->pending) {
-    std::function<int()> emit;
-    emit.swap(ex->pending);
-    const int rc = emit();
-    if (rc) return rc;
-  }
+  if (const int rc = export_flush(scan)) return rc;  // the slab before this one
   SlabCopier cp(ex, hs);
   ++ex->n_exports;
   auto text_p = std::make_shared<HostText>();
   HostText& text = *text_p;
   const double tc0 = now_s();
-  const bool vcf_like = scan->vcf || scan->bcf;
-  const std::vector<exon::InfoSpec>* specs = scan->vcf ? &scan->vcf->info_specs : scan->bcf ? &scan->bcf->info_specs : nullptr;
+  const bool vcf_like = scan->vcf_like();
+  const std::vector<exon::InfoSpec>* specs = vcf_like ? &scan->info_specs() : nullptr;
   const int n_cols = vcf_like ? 4 + (int)specs->size() : 5;
   // element widths in the scan's column order (0 = no values: a Flag, whose bitmap is its value)
   std::vector<int> elem((size_t)n_cols, 4);
@@ -2205,13 +2249,11 @@ static int export_slab(exon_hip_scan* scan, const exon_hip_column* sc, int64_t n
   const size_t moff = bytes;
   bytes += nb;
   const size_t path_stage = bytes + 512 * (size_t)n_cols;
-  if ((vt || bt || ct) && scan->opt.projection) {
-    if (build_text) {  // the device builds *vt / *bt / *ct now
-      const int rc = (*build_text)();
-      if (rc) return rc;
-    }
+  if (projected) {
+    int rc = projected->build();  // the device builds the text columns now
+    if (rc) return rc;
     const double tf0 = now_s();
-    const int rc = fetch_text(ctx, &cp, path_stage, n_rows, scan->opt.projection, vt, bt, &text, scan->opt.batch_size > K_ZERO_ROWS, ct);
+    rc = fetch_text(ctx, &cp, path_stage, n_rows, scan->opt.projection, *projected, &text, scan->opt.batch_size > K_ZERO_ROWS);
     g_t_fetch_text += now_s() - tf0;
     if (rc) return rc;
   } else if (!cp.reserve(path_stage)) {
@@ -2252,7 +2294,7 @@ static int export_slab(exon_hip_scan* scan, const exon_hip_column* sc, int64_t n
     if (rc) return rc;
   }
   std::vector<std::vector<std::string>> info_names;
-  if (scan->vcf) {
+  if (scan->vcf()) {
     const int rc = gpu_info_names(scan, &info_names);
     if (rc) return rc;
   }
@@ -2261,54 +2303,13 @@ static int export_slab(exon_hip_scan* scan, const exon_hip_column* sc, int64_t n
   auto dicts_p = std::make_shared<std::vector<std::shared_ptr<const exon::SharedUtf8>>>((size_t)n_cols);
   std::vector<std::shared_ptr<const exon::SharedUtf8>>& dicts = *dicts_p;
   for (int c = 0; c < n_cols; ++c) {
-    if (vcf_like && c == 0) dicts[(size_t)c] = std::make_shared<const exon::SharedUtf8>(scan->vcf ? scan->vcf->chrom_dict.names : scan->bcf->chrom_dict.names);
+    if (vcf_like && c == 0) dicts[(size_t)c] = std::make_shared<const exon::SharedUtf8>(scan->chrom_dict().names);
     else if (vcf_like && c == 3) dicts[(size_t)c] = std::make_shared<const exon::SharedUtf8>(filters);
-    else if (scan->vcf && c >= 4 && (size_t)(c - 4) < info_names.size() && (*specs)[(size_t)(c - 4)].kind == 's')
+    else if (scan->vcf() && c >= 4 && (size_t)(c - 4) < info_names.size() && (*specs)[(size_t)(c - 4)].kind == 's')
       dicts[(size_t)c] = std::make_shared<const exon::SharedUtf8>(info_names[(size_t)(c - 4)]);
     else if (!vcf_like && c == 2) dicts[(size_t)c] = std::make_shared<const exon::SharedUtf8>(scan->bam_dict_view.names);
   }
   auto dict_of_col = [&](int c) -> struct ArrowArray* { return dicts[(size_t)c] ? exon::shared_utf8_array(dicts[(size_t)c]) : nullptr; };
-  auto push_batch = [&](struct ArrowArray* out, int64_t n) -> int {
-    const double te0 = now_s();
-    std::unique_lock<std::mutex> lk(ex->mu);
-    ex->cv_put.wait(lk, [&] { return ex->stop || ex->q.size() < ex->cap; });
-    g_t_enqueue += now_s() - te0;
-    if (ex->stop) {
-      lk.unlock();
-      out->release(out);
-      free(out);
-      return 2;
-    }
-    ex->q.push_back(out);
-    ex->emitted += n;
-    lk.unlock();
-    ex->cv_get.notify_one();
-    return EXON_HIP_OK;
-  };
-  auto enqueue_arena = [&](exon::BatchArena* arena, const std::vector<struct ArrowArray*>& kids, int64_t n) -> int {
-    struct ArrowArray* out = static_cast<struct ArrowArray*>(malloc(sizeof *out));
-    exon::make_struct_of_arena(out, n, arena, kids);
-    return push_batch(out, n);
-  };
-  auto enqueue = [&](std::vector<struct ArrowArray*> kids, int64_t n) -> int {
-    struct ArrowArray* out = static_cast<struct ArrowArray*>(malloc(sizeof *out));
-    exon::make_struct(out, n, std::move(kids));
-    const double te0 = now_s();
-    std::unique_lock<std::mutex> lk(ex->mu);
-    ex->cv_put.wait(lk, [&] { return ex->stop || ex->q.size() < ex->cap; });
-    g_t_enqueue += now_s() - te0;
-    if (ex->stop) {
-      lk.unlock();
-      out->release(out);
-      free(out);
-      return 2;
-    }
-    ex->q.push_back(out);
-    ex->emitted += n;
-    lk.unlock();
-    ex->cv_get.notify_one();
-    return EXON_HIP_OK;
-  };
   if (as_views) {
     struct Tm {
       double t0 = now_s();
@@ -2333,8 +2334,9 @@ static int export_slab(exon_hip_scan* scan, const exon_hip_column* sc, int64_t n
       g_t_views += tv1 - tv0;
       if (text.vcf || text.bam || text.bcf) text_batch(text, nullptr, b0, n, &kids, arena);
       g_t_text_batch += now_s() - tv1;
-      const int rc = enqueue_arena(arena, kids, n);
-      if (rc) return rc;
+      struct ArrowArray* out = static_cast<struct ArrowArray*>(malloc(sizeof *out));
+      exon::make_struct_of_arena(out, n, arena, kids);
+      if (const int rc = push_batch(ex, out, n)) return rc;
     }
     return EXON_HIP_OK;
   }
@@ -2374,16 +2376,13 @@ static int export_slab(exon_hip_scan* scan, const exon_hip_column* sc, int64_t n
       }
     }
     if (text.vcf || text.bam || text.bcf) text_batch(text, keep.data() + b0, 0, n, &kids);
-    const int rc = enqueue(std::move(kids), n);
-    if (rc) return rc;
+    struct ArrowArray* out = static_cast<struct ArrowArray*>(malloc(sizeof *out));
+    exon::make_struct(out, n, std::move(kids));
+    if (const int rc = push_batch(ex, out, n)) return rc;
   }
   return EXON_HIP_OK;
   };
-  if (getenv("EXON_HIP_EXPORT_SYNC") && getenv("EXON_HIP_EXPORT_SYNC")[0] == '1') {  // A/B: no overlap with the next slab
-    std::function<int()> emit;
-    emit.swap(ex->pending);
-    return emit();
-  }
+  if (getenv("EXON_HIP_EXPORT_SYNC") && getenv("EXON_HIP_EXPORT_SYNC")[0] == '1') return export_flush(scan);  // A/B: no overlap with the next slab
   return EXON_HIP_OK;
 }
 
@@ -2393,12 +2392,7 @@ static int export_slab(exon_hip_scan* scan, const exon_hip_column* sc, int64_t n
 static int export_fastq_slab(exon_hip_scan* scan, const ExonFastqText& ft, int64_t n_reads, hipStream_t hs) {
   GpuExporter* ex = scan->exporter;
   exon_hip_ctx* ctx = ex->ctx;
-  if (ex->pending) {  // the batches of the slab before this one
-    std::function<int()> emit;
-    emit.swap(ex->pending);
-    const int rc = emit();
-    if (rc) return rc;
-  }
+  if (const int rc = export_flush(scan)) return rc;  // the slab before this one
   if (n_reads == 0) return EXON_HIP_OK;
   const size_t n = (size_t)n_reads;
   auto pad = [](size_t b) { return (b + 63) & ~size_t(63); };
@@ -2443,55 +2437,238 @@ static int export_fastq_slab(exon_hip_scan* scan, const ExonFastqText& ft, int64
         kids.push_back(exon::arena_array(arena, m, b0, k == 1 ? -1 : 0, 3, k == 1 ? (const void*)(blk + at_valid) : nullptr, blk + at_off[(size_t)k], blk + at_val[(size_t)k]));
       struct ArrowArray* out = static_cast<struct ArrowArray*>(malloc(sizeof *out));
       exon::make_struct_of_arena(out, m, arena, kids);
-      std::unique_lock<std::mutex> lk(ex->mu);
-      ex->cv_put.wait(lk, [&] { return ex->stop || ex->q.size() < ex->cap; });
-      if (ex->stop) {
-        lk.unlock();
-        out->release(out);
-        free(out);
-        return 2;
-      }
-      ex->q.push_back(out);
-      ex->emitted += m;
-      lk.unlock();
-      ex->cv_get.notify_one();
+      if (const int rc = push_batch(ex, out, m)) return rc;
     }
     return EXON_HIP_OK;
   };
-  if (getenv("EXON_HIP_EXPORT_SYNC") && getenv("EXON_HIP_EXPORT_SYNC")[0] == '1') {
-    std::function<int()> emit;
-    emit.swap(ex->pending);
-    return emit();
-  }
+  if (getenv("EXON_HIP_EXPORT_SYNC") && getenv("EXON_HIP_EXPORT_SYNC")[0] == '1') return export_flush(scan);
   return EXON_HIP_OK;
 }
 
-// the last slab's batches (its copy has nothing left to hide behind); also in front of a hand-over to the host reader, which
-// continues behind the rows EMITTED
-static int export_flush(exon_hip_scan* scan) {
-  GpuExporter* ex = scan->exporter;
-  if (!ex || !ex->pending) return EXON_HIP_OK;
-  std::function<int()> emit;
-  emit.swap(ex->pending);
-  return emit();
+// ---- the per-format parts of the slab loop -------------------------------------------------------------------------
+
+// where the records start in the (inflated) file: the length of the header the host reader has read (-1: not known)
+static int64_t data_offset(const exon_hip_scan* scan) {
+  switch (scan->format) {
+    case EXON_HIP_FORMAT_VCF: return scan->vcf()->data_offset();
+    case EXON_HIP_FORMAT_BCF: return scan->bcf()->data_offset();
+    case EXON_HIP_FORMAT_BAM: return scan->bam()->data_offset();
+    case EXON_HIP_FORMAT_SAM: return scan->sam()->data_offset();
+  }
+  return 0;  // FASTQ: no header
 }
 
+// the records as the host reader's text stream, behind what it has read of them already (`carry`)
+static std::unique_ptr<exon::ByteSource> take_text_stream(exon_hip_scan* scan, std::string* carry) {
+  switch (scan->format) {
+    case EXON_HIP_FORMAT_VCF: return scan->vcf()->take_stream(carry);
+    case EXON_HIP_FORMAT_SAM: return scan->sam()->take_stream(carry);
+    case EXON_HIP_FORMAT_FASTQ: return scan->fastq()->take_stream(carry);
+  }
+  return nullptr;  // (BAM and BCF are BGZF by definition)
+}
+
+// the device parser of the scan's format, for slabs of up to `max_text_bytes`
+static int create_parser(exon_hip_scan* scan, exon_hip_ctx* ctx, int64_t max_text_bytes) {
+  DeviceParser& p = scan->parser;
+  p.format = scan->format;
+  int rc = EXON_HIP_OK;
+  switch (scan->format) {
+    case EXON_HIP_FORMAT_VCF: {
+      std::vector<const char*> names;
+      for (const auto& c : scan->vcf()->header.contigs) names.push_back(c.c_str());
+      std::string keys;  // "name:kind,..." from the header-typed specs of the host reader; String LISTS are not decoded
+      for (const auto& sp : scan->vcf()->info_specs)
+        if (sp.kind != 'S') keys += (keys.empty() ? "" : ",") + sp.name + ":" + std::string(1, sp.kind);
+      exon_hip_vcf_parser* h = nullptr;
+      rc = exon_hip_vcf_parser_create(ctx, names.data(), (int32_t)names.size(), keys.empty() ? nullptr : keys.c_str(), max_text_bytes, &h);
+      p.h = h;
+      break;
+    }
+    case EXON_HIP_FORMAT_BCF: {
+      exon::BCFBatchReader* bcf = scan->bcf();
+      exon_hip_bcf_parser* h = nullptr;
+      rc = exon_hip_bcf_parser_create(ctx, (int32_t)bcf->header.contigs.size(), (int32_t)bcf->strings().size(), (int32_t)bcf->header.samples.size(),
+                                      (int32_t)bcf->info_key(), max_text_bytes, &h);
+      p.h = h;
+      if (rc || bcf->info_specs.empty()) break;
+      std::vector<int32_t> keys;
+      std::string kinds;
+      for (size_t k = 0; k < bcf->info_specs.size(); ++k) {
+        const char kind = bcf->info_specs[k].kind;
+        if (kind == 's' || kind == 'S') continue;  // String / Character keys are not decoded on the device
+        keys.push_back(bcf->info_keys()[k]);
+        kinds += kind;
+      }
+      if (!keys.empty()) rc = exon_hip_bcf_parser_set_info_keys(h, keys.data(), kinds.c_str(), (int32_t)keys.size());
+      break;
+    }
+    case EXON_HIP_FORMAT_BAM: {
+      exon_hip_bam_parser* h = nullptr;
+      rc = exon_hip_bam_parser_create(ctx, (int32_t)scan->bam()->ref_names.size(), max_text_bytes, &h);
+      p.h = h;
+      break;
+    }
+    case EXON_HIP_FORMAT_SAM: {
+      std::vector<const char*> names;
+      for (const auto& c : scan->sam()->ref_names) names.push_back(c.c_str());
+      exon_hip_sam_parser* h = nullptr;
+      rc = exon_hip_sam_parser_create(ctx, names.data(), (int32_t)names.size(), max_text_bytes, &h);
+      p.h = h;
+      break;
+    }
+    case EXON_HIP_FORMAT_FASTQ: {
+      exon_hip_fastq_parser* h = nullptr;
+      rc = exon_hip_fastq_parser_create(ctx, max_text_bytes, &h);
+      p.h = h;
+      break;
+    }
+  }
+  p.owns_names = p.h && scan->vcf_like();
+  return rc;
+}
+
+// One slab parsed on the device: the scan's columns (VCF / BCF: 0 chrom 1 pos 2 qual 3 filter 4.. info fields; BAM / SAM: 0 flag
+// 1 mapq 2 ref 3 start 4 end) with the operands of the region mask, or (FASTQ) the views of the slab's reads
+struct SlabParse {
+  exon_hip_column sc[4 + EXON_HIP_MAX_INFO_FIELDS] = {};
+  int64_t n_rows = 0, consumed = 0, n_undecided = 0;
+  const int32_t* id_col = nullptr;  // region mask: contig / reference ids ...
+  const uint8_t *id_valid = nullptr, *pos_valid = nullptr;
+  const int64_t *c_start = nullptr, *c_end = nullptr;  // ... and the records' intervals
+  bool has_views = false;
+  exon_hip_fastq_views views;
+};
+static int parse_slab(exon_hip_scan* scan, hipStream_t hs, const uint8_t* d_text, size_t n, bool final, SlabParse* p) {
+  exon_hip_column* sc = p->sc;
+  int rc = EXON_HIP_OK;
+  switch (scan->format) {
+    case EXON_HIP_FORMAT_VCF:
+    case EXON_HIP_FORMAT_BCF: {
+      const bool text = scan->format == EXON_HIP_FORMAT_VCF;
+      exon_hip_vcf_columns cols;
+      if (text) {
+        // a fused plan that groups by a String key: NULL is a group of its own (the empty text's id); batches keep NULL
+        exon_hip_vcf_parser_set_null_key(scan->parser.as<exon_hip_vcf_parser>(), scan->exporter ? 0 : 1);
+        rc = exon_hip_vcf_parser_parse(scan->parser.as<exon_hip_vcf_parser>(), hs, d_text, (int64_t)n, &cols);
+      } else {
+        rc = exon_hip_bcf_parser_parse(scan->parser.as<exon_hip_bcf_parser>(), hs, d_text, (int64_t)n, &cols);
+      }
+      if (rc) return rc;
+      p->n_undecided = cols.n_undecided;
+      p->consumed = cols.consumed_bytes;
+      p->n_rows = cols.n_rows;
+      sc[0].values = cols.chrom_id;
+      sc[1].values = cols.pos;
+      sc[1].validity = cols.pos_valid;
+      sc[2].values = cols.qual;
+      sc[2].validity = cols.qual_valid;
+      sc[3].values = cols.filter_id;
+      // device key q -> scan column 4 + k: String / Character keys were left out, list keys are no plan operands
+      const std::vector<exon::InfoSpec>& specs = scan->info_specs();
+      int q = 0;
+      for (size_t k = 0; k < specs.size() && k < (size_t)EXON_HIP_MAX_INFO_FIELDS; ++k) {
+        const char kind = specs[k].kind;
+        if (kind == 'S' || (kind == 's' && !text)) continue;  // (not given to the device parser)
+        if (q < cols.n_info && !exon::info_kind_is_list(kind)) {
+          sc[4 + k].values = cols.infos[q] ? (const void*)cols.infos[q] : (const void*)cols.infos_valid[q];  // a Flag's values ARE its bitmap
+          sc[4 + k].validity = cols.infos_valid[q];
+          // a String key's dictionary ids: without a NULL in this slab the column goes out as NOT NULL (a fused plan that
+          // groups by it refuses nullable ids: there is no NULL group in its state)
+          if (kind == 's' && cols.info_nulls[q] == 0 && !scan->exporter) sc[4 + k].validity = nullptr;
+        }
+        ++q;
+      }
+      p->id_col = cols.chrom_id;
+      p->c_start = p->c_end = cols.pos;
+      p->pos_valid = cols.pos_valid;
+      return EXON_HIP_OK;
+    }
+    case EXON_HIP_FORMAT_BAM:
+    case EXON_HIP_FORMAT_SAM: {
+      exon_hip_bam_columns cols;
+      rc = scan->format == EXON_HIP_FORMAT_BAM ? exon_hip_bam_parser_parse(scan->parser.as<exon_hip_bam_parser>(), hs, d_text, (int64_t)n, &cols)
+                                               : exon_hip_sam_parser_parse(scan->parser.as<exon_hip_sam_parser>(), hs, d_text, (int64_t)n, &cols);
+      if (getenv("EXON_HIP_PIPE_TRACE"))
+        fprintf(stderr, "[exon-hip pipe] bam slab %zu bytes: rc %d rows %lld undecided %lld consumed %lld\n", n, rc, (long long)cols.n_rows, (long long)cols.n_undecided, (long long)cols.consumed_bytes);
+      if (rc) return rc;
+      p->n_undecided = cols.n_undecided;
+      p->consumed = cols.consumed_bytes;
+      p->n_rows = cols.n_rows;
+      sc[0].values = cols.flag;
+      sc[1].values = cols.mapq;
+      sc[1].validity = cols.mapq_valid;
+      sc[2].values = cols.ref_id;
+      sc[2].validity = cols.ref_valid;
+      sc[3].values = cols.start;
+      sc[3].validity = cols.pos_valid;
+      sc[4].values = cols.end;
+      sc[4].validity = cols.pos_valid;
+      p->id_col = cols.ref_id;
+      p->id_valid = cols.ref_valid;
+      p->c_start = cols.start;
+      p->c_end = cols.end;
+      p->pos_valid = cols.pos_valid;
+      return EXON_HIP_OK;
+    }
+    default: {  // FASTQ
+      rc = exon_hip_fastq_parser_parse(scan->parser.as<exon_hip_fastq_parser>(), hs, d_text, (int64_t)n, final ? 1 : 0, &p->views);
+      if (rc) return rc;
+      p->has_views = true;
+      p->n_undecided = p->views.n_undecided;
+      p->consumed = p->views.consumed_bytes;
+      p->n_rows = p->views.n_reads;
+      return EXON_HIP_OK;
+    }
+  }
+}
+
+// the projected text columns of a slab, built on the device from the index the parser has just made into `t`'s member of the
+// scan's format.  1: the host reader takes over.
+static int build_text(exon_hip_scan* scan, exon_hip_ctx* ctx, hipStream_t hs, const uint8_t* d_text, size_t n, int64_t n_rows, SlabText* t) {
+  const double tk0 = now_s();
+  const uint64_t proj = scan->opt.projection;
+  int64_t undecided = 0;
+  int r = EXON_HIP_OK;
+  switch (scan->format) {
+    case EXON_HIP_FORMAT_VCF:
+      r = exon_text_vcf(ctx, hs, &scan->text_scratch, d_text, (int64_t)n, exon_hip_vcf_parser_newlines(scan->parser.as<exon_hip_vcf_parser>()), n_rows, proj, &t->vcf);
+      break;
+    case EXON_HIP_FORMAT_BCF:  // undecided: an ID / allele that is not a typed string (the host reader reports what it is)
+      r = exon_text_bcf(ctx, hs, &scan->text_scratch, d_text, (int64_t)n, exon_hip_bcf_parser_row_records(scan->parser.as<exon_hip_bcf_parser>()), n_rows, proj, &t->bcf, &undecided);
+      break;
+    case EXON_HIP_FORMAT_BAM:
+      r = exon_text_bam(ctx, hs, &scan->text_scratch, d_text, (int64_t)n, exon_hip_bam_parser_row_records(scan->parser.as<exon_hip_bam_parser>()), n_rows, proj, &t->bam);
+      break;
+    case EXON_HIP_FORMAT_SAM:  // undecided: a CIGAR / QUAL the device would not print the way the reader does
+      r = exon_text_sam(ctx, hs, &scan->text_scratch, d_text, (int64_t)n, exon_hip_sam_parser_newlines(scan->parser.as<exon_hip_sam_parser>()), n_rows, proj, &t->bam, &undecided);
+      break;
+  }
+  if (!r && undecided) r = 1;
+  g_t_text_kernels += now_s() - tk0;
+  return r;
+}
+
+// file -> text slabs in HBM (GpuTextSource) -> GPU parser -> fused kernel (or, bound to an exporter, batches).  Returns 1 when the
+// device could not decide something: the caller restores the state and re-decodes the file on the host.
 static int consume_text_gpu(exon_hip_stream* st, exon_hip_scan* scan, int64_t* rows_out) {
   const bool trace = getenv("EXON_HIP_PIPE_TRACE") != nullptr;  // phase timings on stderr
   const double t_begin = now_s();
   double t_next = 0, t_parse = 0;
   exon_hip_ctx* ctx = exon_hip_stream_ctx(st);
   hipStream_t hs = (hipStream_t)exon_hip_stream_hip_stream(st);
-  const bool is_vcf = scan->vcf != nullptr, is_bam = scan->bam != nullptr, is_bcf = scan->bcf != nullptr, is_sam = scan->sam != nullptr;
-  const bool filtered = scan->region.active && (is_vcf || is_bam || is_bcf || is_sam);
-  const bool indexed = filtered && scan->region.use_index && (is_vcf || is_bam);
-  const bool bgzf = gpu_inflate_enabled() && scan->opt.compression != EXON_HIP_COMPRESSION_NONE &&
-                    exon::BgzfParallelSource::is_bgzf(scan->path) && (!is_vcf || indexed || scan->vcf->data_offset() >= 0);
-  if ((is_bam || is_bcf || indexed) && !bgzf) return 1;
+
+  // ---- where the slabs come from: the index chunks' blocks, the BGZF file, a plain-gzip file, or the reader's text stream ----
+  const bool binary = scan->bam() || scan->bcf();  // BGZF by definition: inflated on the device or decoded on the host
+  const bool filtered = scan->region.active && !scan->fastq();
+  const bool indexed = filtered && scan->region.use_index && (scan->vcf() || scan->bam());
+  const bool device_inflate = gpu_inflate_enabled() && scan->opt.compression != EXON_HIP_COMPRESSION_NONE;
+  const bool bgzf = device_inflate && exon::BgzfParallelSource::is_bgzf(scan->path) && (indexed || data_offset(scan) >= 0);
+  if ((binary || indexed) && !bgzf) return 1;
   // a gzip file that is not BGZF (the `else` arm of the reference's openers, fastq/file_opener.rs:79-92): inflated on the GPU too
   // (gzip_stream.hip) when the host reader can say where the records start in the uncompressed stream; EXON_HIP_GPU_GZIP=0: host zlib
-  const bool gz = !bgzf && !indexed && !is_bam && !is_bcf && gpu_inflate_enabled() && gpu_gzip_enabled() && scan->opt.compression != EXON_HIP_COMPRESSION_NONE &&
-                  is_plain_gzip(scan->path) && (!is_vcf || scan->vcf->data_offset() >= 0) && (!is_sam || scan->sam->data_offset() >= 0);
+  const bool gz = !bgzf && device_inflate && gpu_gzip_enabled() && is_plain_gzip(scan->path) && data_offset(scan) >= 0;
+  const GpuTextSource::Kind kind = bgzf ? GpuTextSource::Kind::Bgzf : gz ? GpuTextSource::Kind::Gzip : GpuTextSource::Kind::Text;
   if (!scan->exporter) {
     scan->gpu_inflated = bgzf || gz;
     scan->gpu_decoded = false;
@@ -2503,10 +2680,7 @@ static int consume_text_gpu(exon_hip_stream* st, exon_hip_scan* scan, int64_t* r
   bool rg_range = false;
   if (filtered) {
     region_target(scan, &rg_id, &rg_a, &rg_b, &rg_range);
-    if (!scan->d_region_pass) {
-      HIP_TRY(ctx, hipMalloc((void**)&scan->d_region_pass, 8));
-      scan->region_ctx = ctx;
-    }
+    if (!scan->d_region_pass) HIP_TRY(ctx, hipMalloc((void**)&scan->d_region_pass, 8));
     HIP_TRY(ctx, hipMemsetAsync(scan->d_region_pass, 0, 8, hs));
   }
 
@@ -2514,7 +2688,7 @@ static int consume_text_gpu(exon_hip_stream* st, exon_hip_scan* scan, int64_t* r
   std::vector<ChunkRange> ranges;
   if (indexed) {
     try {
-      ranges = plan_chunk_ranges(scan->path, is_vcf ? scan->vcf->planned_chunks : scan->bam->planned_chunks);
+      ranges = plan_chunk_ranges(scan->path, scan->vcf() ? scan->vcf()->planned_chunks : scan->bam()->planned_chunks);
     } catch (const std::exception& e) {
       return fail(ctx, EXON_HIP_EINVAL, "%s", e.what());
     }
@@ -2527,77 +2701,30 @@ static int consume_text_gpu(exon_hip_stream* st, exon_hip_scan* scan, int64_t* r
   for (size_t si = 0; si < n_sources && rc == EXON_HIP_OK; ++si) {
     std::unique_ptr<GpuTextSource> src;
     try {
+      GpuTextSource::Options so;
+      so.binary = binary;
+      so.text_async = scan->fastq() != nullptr;
+      std::unique_ptr<exon::ByteSource> in;
       if (indexed) {
-        const ChunkRange& r = ranges[si];
-        std::unique_ptr<exon::ByteSource> raw(new FileRangeSource(scan->path, r.lo, r.hi));
-        src.reset(new GpuTextSource(ctx, hs, std::move(raw), true, r.skip, std::string(), is_bam, false, r.trim));
-      } else if (bgzf) {
-        const uint64_t skip = is_vcf   ? (uint64_t)scan->vcf->data_offset()
-                              : is_bam ? (uint64_t)scan->bam->data_offset()
-                              : is_bcf ? (uint64_t)scan->bcf->data_offset()
-                              : is_sam ? (uint64_t)scan->sam->data_offset()
-                                       : 0;
-        std::unique_ptr<exon::ByteSource> raw(new exon::ByteReader(scan->path, exon::Compression::None));
-        src.reset(new GpuTextSource(ctx, hs, std::move(raw), true, skip, std::string(), is_bam || is_bcf, /*text_async=*/!is_vcf && !is_bam && !is_bcf && !is_sam));
-      } else if (gz) {
-        const uint64_t skip = is_vcf ? (uint64_t)scan->vcf->data_offset() : is_sam ? (uint64_t)scan->sam->data_offset() : 0;
-        std::unique_ptr<exon::ByteSource> raw(new exon::ByteReader(scan->path, exon::Compression::None));
-        src.reset(new GpuTextSource(ctx, hs, std::move(raw), false, skip, std::string(), false, false, 0, /*gz=*/true));
+        so.skip_first = ranges[si].skip;
+        so.trim_last = ranges[si].trim;
+        in.reset(new FileRangeSource(scan->path, ranges[si].lo, ranges[si].hi));
+      } else if (kind == GpuTextSource::Kind::Text) {
+        in = take_text_stream(scan, &so.carry);
+        if (!in) return fail(ctx, EXON_HIP_ESTATE, "scan already consumed");
       } else {
-        std::string carry;
-        std::unique_ptr<exon::ByteSource> text = is_vcf   ? scan->vcf->take_stream(&carry)
-                                                 : is_sam ? scan->sam->take_stream(&carry)
-                                                          : scan->fastq->take_stream(&carry);
-        if (!text) return fail(ctx, EXON_HIP_ESTATE, "scan already consumed");
-        src.reset(new GpuTextSource(ctx, hs, std::move(text), false, 0, std::move(carry)));
+        so.skip_first = (uint64_t)data_offset(scan);
+        in.reset(new exon::ByteReader(scan->path, exon::Compression::None));
       }
+      src.reset(new GpuTextSource(ctx, hs, std::move(in), kind, std::move(so)));
     } catch (const std::exception& e) {
       return fail(ctx, EXON_HIP_EINVAL, "%s", e.what());
     }
     rc = src->init();
     if (rc) break;
     const double t_src = now_s();
-    if (is_vcf && !scan->parser) {
-      std::vector<const char*> names;
-      for (const auto& c : scan->vcf->header.contigs) names.push_back(c.c_str());
-      std::string keys;  // "name:kind,..." from the header-typed specs of the host reader; String LISTS are not decoded
-      for (const auto& sp : scan->vcf->info_specs)
-        if (sp.kind != 'S') keys += (keys.empty() ? "" : ",") + sp.name + ":" + std::string(1, sp.kind);
-      rc = exon_hip_vcf_parser_create(ctx, names.data(), (int32_t)names.size(), keys.empty() ? nullptr : keys.c_str(),
-                                      (int64_t)src->max_text_bytes(), &scan->parser);
-      if (rc) break;
-      scan->parser_ctx = ctx;
-    }
-    if (is_bam && !scan->bam_parser) {
-      rc = exon_hip_bam_parser_create(ctx, (int32_t)scan->bam->ref_names.size(), (int64_t)src->max_text_bytes(), &scan->bam_parser);
-      if (rc) break;
-    }
-    if (is_bcf && !scan->bcf_parser) {
-      rc = exon_hip_bcf_parser_create(ctx, (int32_t)scan->bcf->header.contigs.size(), (int32_t)scan->bcf->strings().size(),
-                                      (int32_t)scan->bcf->header.samples.size(), (int32_t)scan->bcf->info_key(), (int64_t)src->max_text_bytes(),
-                                      &scan->bcf_parser);
-      if (rc) break;
-      if (scan->bcf->info_specs.size() > 0) {
-        std::vector<int32_t> keys;
-        std::string kinds;
-        for (size_t k = 0; k < scan->bcf->info_specs.size(); ++k) {
-          const char kind = scan->bcf->info_specs[k].kind;
-          if (kind == 's' || kind == 'S') continue;  // String / Character keys are not decoded on the device
-          keys.push_back(scan->bcf->info_keys()[k]);
-          kinds += kind;
-        }
-        if (!keys.empty()) rc = exon_hip_bcf_parser_set_info_keys(scan->bcf_parser, keys.data(), kinds.c_str(), (int32_t)keys.size());
-        if (rc) break;
-      }
-    }
-    if (is_sam && !scan->sam_parser) {
-      std::vector<const char*> names;
-      for (const auto& c : scan->sam->ref_names) names.push_back(c.c_str());
-      rc = exon_hip_sam_parser_create(ctx, names.data(), (int32_t)names.size(), (int64_t)src->max_text_bytes(), &scan->sam_parser);
-      if (rc) break;
-    }
-    if (!is_vcf && !is_bam && !is_bcf && !is_sam && !scan->fq_parser) {
-      rc = exon_hip_fastq_parser_create(ctx, (int64_t)src->max_text_bytes(), &scan->fq_parser);
+    if (!scan->parser.h) {
+      rc = create_parser(scan, ctx, (int64_t)src->max_text_bytes());
       if (rc) break;
     }
     if (si == 0) {
@@ -2613,149 +2740,61 @@ static int consume_text_gpu(exon_hip_stream* st, exon_hip_scan* scan, int64_t* r
       const double t1 = now_s();
       t_next += t1 - t0;
       if (rc) break;
-      size_t consumed = 0;
-      if (n > 0 && (is_vcf || is_bcf || is_bam || is_sam)) {
-        // parsed columns in the scan's column order: VCF / BCF 0 chrom 1 pos 2 qual 3 filter 4.. info fields; BAM / SAM 0 flag 1 mapq 2 ref 3 start 4 end
-        exon_hip_column sc[4 + EXON_HIP_MAX_INFO_FIELDS];
-        memset(sc, 0, sizeof sc);
-        int64_t n_rows = 0;
-        const int32_t* id_col = nullptr;
-        const uint8_t *id_valid = nullptr, *pos_valid = nullptr;
-        const int64_t *c_start = nullptr, *c_end = nullptr;
-        if (is_vcf || is_bcf) {
-          exon_hip_vcf_columns cols;
-          // a fused plan that groups by a String key: NULL is a group of its own (the empty text's id); batches keep NULL
-          if (is_vcf) exon_hip_vcf_parser_set_null_key(scan->parser, scan->exporter ? 0 : 1);
-          rc = is_vcf ? exon_hip_vcf_parser_parse(scan->parser, hs, d_text, (int64_t)n, &cols)
-                      : exon_hip_bcf_parser_parse(scan->bcf_parser, hs, d_text, (int64_t)n, &cols);
-          t_parse += now_s() - t1;
-          if (!rc && cols.n_undecided > 0) rc = 1;
-          if (rc) break;
-          consumed = (size_t)cols.consumed_bytes;
-          n_rows = cols.n_rows;
-          sc[0].values = cols.chrom_id;
-          sc[1].values = cols.pos;
-          sc[1].validity = cols.pos_valid;
-          sc[2].values = cols.qual;
-          sc[2].validity = cols.qual_valid;
-          sc[3].values = cols.filter_id;
-          {  // device key q -> scan column 4 + k: String / Character keys were left out, list keys are no plan operands
-            const std::vector<exon::InfoSpec>& specs = is_vcf ? scan->vcf->info_specs : scan->bcf->info_specs;
-            int q = 0;
-            for (size_t k = 0; k < specs.size() && k < (size_t)EXON_HIP_MAX_INFO_FIELDS; ++k) {
-              const char kind = specs[k].kind;
-              if (kind == 'S' || (kind == 's' && !is_vcf)) continue;  // (not given to the device parser)
-              if (q < cols.n_info && !exon::info_kind_is_list(kind)) {
-                sc[4 + k].values = cols.infos[q] ? (const void*)cols.infos[q] : (const void*)cols.infos_valid[q];  // a Flag's values ARE its bitmap
-                sc[4 + k].validity = cols.infos_valid[q];
-                // a String key's dictionary ids: without a NULL in this slab the column goes out as NOT NULL (a fused plan that
-                // groups by it refuses nullable ids: there is no NULL group in its state)
-                if (kind == 's' && cols.info_nulls[q] == 0 && !scan->exporter) sc[4 + k].validity = nullptr;
-              }
-              ++q;
-            }
-          }
-          id_col = cols.chrom_id;
-          c_start = c_end = cols.pos;
-          pos_valid = cols.pos_valid;
-        } else {
-          exon_hip_bam_columns cols;
-          rc = is_bam ? exon_hip_bam_parser_parse(scan->bam_parser, hs, d_text, (int64_t)n, &cols)
-                      : exon_hip_sam_parser_parse(scan->sam_parser, hs, d_text, (int64_t)n, &cols);
-          t_parse += now_s() - t1;
-          if (trace) fprintf(stderr, "[exon-hip pipe] bam slab %zu bytes: rc %d rows %lld undecided %lld consumed %lld\n", n, rc, (long long)cols.n_rows, (long long)cols.n_undecided, (long long)cols.consumed_bytes);
-          if (!rc && cols.n_undecided > 0) rc = 1;
-          if (rc) break;
-          consumed = (size_t)cols.consumed_bytes;
-          n_rows = cols.n_rows;
-          sc[0].values = cols.flag;
-          sc[1].values = cols.mapq;
-          sc[1].validity = cols.mapq_valid;
-          sc[2].values = cols.ref_id;
-          sc[2].validity = cols.ref_valid;
-          sc[3].values = cols.start;
-          sc[3].validity = cols.pos_valid;
-          sc[4].values = cols.end;
-          sc[4].validity = cols.pos_valid;
-          id_col = cols.ref_id;
-          id_valid = cols.ref_valid;
-          c_start = cols.start;
-          c_end = cols.end;
-          pos_valid = cols.pos_valid;
-        }
-        if (n_rows > 0) {
-          for (auto& c : sc) c.length = n_rows;
-          const uint8_t* row_mask = nullptr;
-          if (filtered) {
-            // the per-record interval hit, on the device: mask = (first operand's validity) AND hit
-            const size_t need = (size_t)(n_rows + 7) / 8 + 64;
-            if (scan->region_mask_cap < need) {
-              HIP_TRY(ctx, hipStreamSynchronize(hs));  // the previous slab's kernel may still read the old buffer
-              if (scan->d_region_mask) hipFree(scan->d_region_mask);
-              scan->d_region_mask = nullptr;
-              scan->region_mask_cap = 0;
-              const size_t cap = need + need / 2;
-              if (hipMalloc((void**)&scan->d_region_mask, cap) != hipSuccess) return fail(ctx, EXON_HIP_ENOMEM, "row mask of %zu bytes", cap);
-              scan->region_mask_cap = cap;
-            }
-            const int first = exon_hip_stream_plan_first_column(st);
-            const uint8_t* in_valid = first >= 0 && first < 4 + EXON_HIP_MAX_INFO_FIELDS ? sc[first].validity : nullptr;
-            HIP_TRY(ctx, exon::launch_region_mask(hs, rg_range, id_col, id_valid, c_start, c_end, pos_valid, in_valid, n_rows, rg_id, rg_a, rg_b,
-                                                  scan->d_region_mask, scan->d_region_pass));
-            row_mask = scan->d_region_mask;
-          }
-          if (scan->exporter && scan->opt.projection && (is_vcf || is_bam || is_sam || is_bcf)) {
-            // the reference's string / list columns of this slab, built on the device from the index the parser has just made
-            // (by export_slab, once it knows that the slab keeps rows at all)
-            ExonVcfText vt;
-            ExonBamText bt;
-            ExonBcfText ct;
-            const std::function<int()> build_text = [&]() -> int {
-              const double tk0 = now_s();
-              int r;
-              if (is_bcf) {
-                int64_t undecided = 0;
-                r = exon_text_bcf(ctx, hs, &scan->text_scratch, d_text, (int64_t)n, exon_hip_bcf_parser_row_records(scan->bcf_parser), n_rows, scan->opt.projection, &ct, &undecided);
-                if (!r && undecided) r = 1;  // an ID / allele that is not a typed string: the host reader reports what it is
-              } else if (is_sam) {
-                int64_t undecided = 0;
-                r = exon_text_sam(ctx, hs, &scan->text_scratch, d_text, (int64_t)n, exon_hip_sam_parser_newlines(scan->sam_parser), n_rows, scan->opt.projection, &bt, &undecided);
-                if (!r && undecided) r = 1;  // a CIGAR / QUAL the device would not print the way the reader does: the host reader takes over
-              } else {
-                r = is_vcf ? exon_text_vcf(ctx, hs, &scan->text_scratch, d_text, (int64_t)n, exon_hip_vcf_parser_newlines(scan->parser), n_rows, scan->opt.projection, &vt)
-                           : exon_text_bam(ctx, hs, &scan->text_scratch, d_text, (int64_t)n, exon_hip_bam_parser_row_records(scan->bam_parser), n_rows, scan->opt.projection, &bt);
-              }
-              g_t_text_kernels += now_s() - tk0;
-              return r;
-            };
-            rc = export_slab(scan, sc, n_rows, row_mask, hs, is_vcf ? &vt : nullptr, (is_bam || is_sam) ? &bt : nullptr, &build_text, is_bcf ? &ct : nullptr);
-          } else
-          rc = scan->exporter ? export_slab(scan, sc, n_rows, row_mask, hs)
-                              : exon_hip_stream_launch_scan_columns(st, sc, 4 + EXON_HIP_MAX_INFO_FIELDS, n_rows, row_mask);
-          // the parser's column buffers (and the row mask) are reused by the next slab; the kernel is stream-ordered before that
-          total += n_rows;
-        }
-      } else if (n > 0) {
-        exon_hip_fastq_views v;
-        rc = exon_hip_fastq_parser_parse(scan->fq_parser, hs, d_text, (int64_t)n, final ? 1 : 0, &v);
-        if (!rc && v.n_undecided > 0) rc = 1;
-        if (!rc && !final && v.consumed_bytes == 0) rc = 1;  // not one whole record in a slab
+      SlabParse p;
+      if (n > 0) {
+        rc = parse_slab(scan, hs, d_text, n, final, &p);
+        t_parse += now_s() - t1;
+        if (!rc && p.n_undecided > 0) rc = 1;
+        if (!rc && !final && p.consumed == 0) rc = 1;  // not one whole record in a slab
         if (rc) break;
-        consumed = (size_t)v.consumed_bytes;
-        if (v.n_reads > 0 && scan->exporter) {  // batches: the four Utf8 columns, built on the device
+      }
+      if (p.n_rows > 0 && p.has_views) {
+        if (scan->exporter) {  // batches: the four Utf8 columns, built on the device
           ExonFastqText ft;
-          rc = exon_text_fastq(ctx, hs, &scan->text_scratch, &v, (int64_t)n + 16, &ft);
-          if (!rc) rc = export_fastq_slab(scan, ft, v.n_reads, hs);
-          total += v.n_reads;
-        } else if (v.n_reads > 0) {
-          rc = exon_hip_stream_launch_views(st, d_text, v);  // asynchronous: overlaps with preparing the next slab
-          total += v.n_reads;
+          rc = exon_text_fastq(ctx, hs, &scan->text_scratch, &p.views, (int64_t)n + 16, &ft);
+          if (!rc) rc = export_fastq_slab(scan, ft, p.n_rows, hs);
+        } else {
+          rc = exon_hip_stream_launch_views(st, d_text, p.views);  // asynchronous: overlaps with preparing the next slab
         }
+        total += p.n_rows;
+      } else if (p.n_rows > 0) {
+        const int64_t n_rows = p.n_rows;
+        for (auto& c : p.sc) c.length = n_rows;
+        const uint8_t* row_mask = nullptr;
+        if (filtered) {
+          // the per-record interval hit, on the device: mask = (first operand's validity) AND hit
+          const size_t need = (size_t)(n_rows + 7) / 8 + 64;
+          if (scan->region_mask_cap < need) {
+            HIP_TRY(ctx, hipStreamSynchronize(hs));  // the previous slab's kernel may still read the old buffer
+            if (scan->d_region_mask) hipFree(scan->d_region_mask);
+            scan->d_region_mask = nullptr;
+            scan->region_mask_cap = 0;
+            const size_t cap = need + need / 2;
+            if (hipMalloc((void**)&scan->d_region_mask, cap) != hipSuccess) return fail(ctx, EXON_HIP_ENOMEM, "row mask of %zu bytes", cap);
+            scan->region_mask_cap = cap;
+          }
+          const int first = exon_hip_stream_plan_first_column(st);
+          const uint8_t* in_valid = first >= 0 && first < 4 + EXON_HIP_MAX_INFO_FIELDS ? p.sc[first].validity : nullptr;
+          HIP_TRY(ctx, exon::launch_region_mask(hs, rg_range, p.id_col, p.id_valid, p.c_start, p.c_end, p.pos_valid, in_valid, n_rows, rg_id, rg_a, rg_b,
+                                                scan->d_region_mask, scan->d_region_pass));
+          row_mask = scan->d_region_mask;
+        }
+        if (scan->exporter && scan->opt.projection) {
+          // the reference's string / list columns of this slab (by export_slab, once it knows that the slab keeps rows at all)
+          SlabText text;
+          text.format = scan->format;
+          text.build = [&] { return build_text(scan, ctx, hs, d_text, n, n_rows, &text); };
+          rc = export_slab(scan, p.sc, n_rows, row_mask, hs, &text);
+        } else {
+          rc = scan->exporter ? export_slab(scan, p.sc, n_rows, row_mask, hs, nullptr)
+                              : exon_hip_stream_launch_scan_columns(st, p.sc, 4 + EXON_HIP_MAX_INFO_FIELDS, n_rows, row_mask);
+        }
+        // the parser's column buffers (and the row mask) are reused by the next slab; the kernel is stream-ordered before that
+        total += n_rows;
       }
       if (rc) break;
-      if (!final && n > 0 && consumed == 0) { rc = 1; break; }  // a record larger than a slab
       const double tr0 = now_s();
-      rc = src->release(consumed, final);
+      rc = src->release((size_t)p.consumed, final);
       g_t_release += now_s() - tr0;
       if (rc || final) break;
     }
@@ -2785,7 +2824,7 @@ static int consume_text_gpu(exon_hip_stream* st, exon_hip_scan* scan, int64_t* r
     HIP_TRY(ctx, hipMemcpy(&kept, scan->d_region_pass, 8, hipMemcpyDeviceToHost));
     total = (int64_t)kept;
   }
-  if (rc == EXON_HIP_OK && (is_bcf || (is_vcf && scan->parser))) {  // FILTER dictionary -> scan (names in id order)
+  if (rc == EXON_HIP_OK && scan->parser.owns_names) {  // FILTER dictionary -> scan (names in id order)
     std::vector<std::string> names;
     rc = gpu_filter_names(scan, &names);
     if (!rc) {
@@ -2793,15 +2832,15 @@ static int consume_text_gpu(exon_hip_stream* st, exon_hip_scan* scan, int64_t* r
       else scan->gpu_filter_dict.names.swap(names);
     }
   }
-  if (rc == EXON_HIP_OK && is_vcf && scan->parser) {  // String INFO keys: their dictionaries -> scan
+  if (rc == EXON_HIP_OK && scan->vcf() && scan->parser.owns_names) {  // String INFO keys: their dictionaries -> scan
     std::vector<std::vector<std::string>> info_names;
     rc = gpu_info_names(scan, &info_names);
     if (!rc) {
       if (scan->exporter) {
         scan->exporter->final_info_names.swap(info_names);
       } else {
-        for (size_t k = 0; k < info_names.size() && k < scan->vcf->info_dicts.size(); ++k)
-          if (scan->vcf->info_specs[k].kind == 's') scan->vcf->info_dicts[k].names.swap(info_names[k]);
+        for (size_t k = 0; k < info_names.size() && k < scan->vcf()->info_dicts.size(); ++k)
+          if (scan->vcf()->info_specs[k].kind == 's') scan->vcf()->info_dicts[k].names.swap(info_names[k]);
       }
     }
   }
@@ -2836,36 +2875,6 @@ static int region_dict_column(const exon_hip_scan* s) {
 
 }  // extern "C"
 
-// the host reader from the start (a scan opened for the GPU pipeline has read the header only)
-// (built into the exporter, NOT into the scan: the consumer thread may be inside exon_hip_scan_schema / _dictionary_* on the
-// scan's own reader at this very moment)
-static void open_fallback_reader(exon_hip_scan* scan, GpuExporter* ex) {
-  const exon::Compression c = scan->opt.compression == EXON_HIP_COMPRESSION_GZIP   ? exon::Compression::Gzip
-                              : scan->opt.compression == EXON_HIP_COMPRESSION_NONE ? exon::Compression::None
-                                                                                   : exon::Compression::Auto;
-  if (scan->vcf) {
-    exon::VCFConfig cfg = scan->vcf->config();
-    cfg.defer_decode = false;
-    cfg.threads = 0;
-    ex->fb_vcf.reset(new exon::VCFBatchReader(scan->path, c, cfg));
-  } else if (scan->bam) {
-    exon::BAMConfig cfg = scan->bam->config();
-    cfg.threads = 0;
-    ex->fb_bam.reset(new exon::BAMBatchReader(scan->path, cfg));
-  } else if (scan->bcf) {
-    exon::VCFConfig cfg = scan->bcf->config();
-    cfg.threads = 0;
-    ex->fb_bcf.reset(new exon::BCFBatchReader(scan->path, cfg));
-  } else if (scan->sam) {
-    ex->fb_sam.reset(new exon::SAMBatchReader(scan->path, c, scan->sam->config()));
-  } else if (scan->fastq) {
-    exon::FASTQConfig cfg = scan->fastq->config();
-    cfg.defer_decode = false;
-    cfg.threads = 0;
-    ex->fb_fastq.reset(new exon::FASTQBatchReader(scan->path, c, cfg));
-  }
-}
-
 static void gpu_export_producer(exon_hip_scan* scan) {
   GpuExporter* ex = scan->exporter;
   int rc = EXON_HIP_OK;
@@ -2888,9 +2897,11 @@ static void gpu_export_producer(exon_hip_scan* scan) {
     ex->pending = nullptr;
   }
   if (rc == 1) {
-    // the device could not decide something: the host reader goes over the file again and takes over behind the rows emitted
+    // the device could not decide something: the host reader goes over the file again and takes over behind the rows emitted.
+    // It is built into the exporter, NOT into the scan: the consumer thread may be inside exon_hip_scan_schema / _dictionary_*
+    // on the scan's own reader at this very moment.
     try {
-      open_fallback_reader(scan, ex);
+      ex->fallback = open_reader(*scan, Decode::Host);
       int64_t skip = 0;
       {
         std::lock_guard<std::mutex> g(ex->mu);
@@ -2902,8 +2913,7 @@ static void gpu_export_producer(exon_hip_scan* scan) {
       for (;;) {
         struct ArrowArray* out = static_cast<struct ArrowArray*>(malloc(sizeof *out));
         memset(out, 0, sizeof *out);
-        const bool got = ex->fb_vcf ? ex->fb_vcf->read_batch(out) : ex->fb_bam ? ex->fb_bam->read_batch(out) : ex->fb_bcf ? ex->fb_bcf->read_batch(out) : ex->fb_sam ? ex->fb_sam->read_batch(out) : ex->fb_fastq->read_batch(out);
-        if (!got) {
+        if (!ex->fallback->read_batch(out)) {
           free(out);
           break;
         }
@@ -2922,18 +2932,7 @@ static void gpu_export_producer(exon_hip_scan* scan) {
           out->length -= skip;
           skip = 0;
         }
-        std::unique_lock<std::mutex> lk(ex->mu);
-        ex->cv_put.wait(lk, [&] { return ex->stop || ex->q.size() < ex->cap; });
-        if (ex->stop) {
-          lk.unlock();
-          out->release(out);
-          free(out);
-          break;
-        }
-        ex->q.push_back(out);
-        ex->emitted += out->length;
-        lk.unlock();
-        ex->cv_get.notify_one();
+        if (push_batch(ex, out, out->length)) break;  // (the consumer closed the scan)
       }
     } catch (const std::exception& e) {
       rc = EXON_HIP_EINVAL;
@@ -2980,28 +2979,17 @@ static int gpu_next(exon_hip_scan* s, struct ArrowArray* out) {
   if (ex->handed_over) {
     // the producer thread is gone: the reader that finished the file becomes the scan's (its dictionaries are the ones the
     // last batches were built with; every batch carries its dictionary values itself, so nothing emitted earlier depends on it)
-    if (ex->fb_vcf) {
-      s->gpu_filter_dict.names = ex->fb_vcf->filter_dict.names;
-      s->vcf = std::move(ex->fb_vcf);
-    } else if (ex->fb_bcf) {
-      s->gpu_filter_dict.names = ex->fb_bcf->filter_dict.names;
-      s->bcf = std::move(ex->fb_bcf);
-    } else if (ex->fb_bam) {
-      s->bam = std::move(ex->fb_bam);
-    } else if (ex->fb_sam) {
-      s->sam = std::move(ex->fb_sam);
-    } else if (ex->fb_fastq) {
-      s->fastq = std::move(ex->fb_fastq);
-    }
+    s->reader = std::move(ex->fallback);
+    if (s->vcf_like()) s->gpu_filter_dict.names = s->host_filter_dict().names;
     ex->handed_over = false;
     ex->final_filters.clear();
     ex->final_info_names.clear();
   }
   if (ex->rc) return fail(ex->ctx, ex->rc, "%s", ex->err.c_str());
   if (!ex->final_filters.empty()) s->gpu_filter_dict.names.swap(ex->final_filters);
-  if (s->vcf)
-    for (size_t k = 0; k < ex->final_info_names.size() && k < s->vcf->info_dicts.size(); ++k)
-      if (s->vcf->info_specs[k].kind == 's') s->vcf->info_dicts[k].names.swap(ex->final_info_names[k]);
+  if (exon::VCFBatchReader* vcf = s->vcf())
+    for (size_t k = 0; k < ex->final_info_names.size() && k < vcf->info_dicts.size(); ++k)
+      if (vcf->info_specs[k].kind == 's') vcf->info_dicts[k].names.swap(ex->final_info_names[k]);
   s->gpu_decoded = ex->decoded_on_gpu;
   s->gpu_inflated = ex->inflated_on_gpu;
   return 1;
@@ -3067,15 +3055,15 @@ static int consume_scan_impl(exon_hip_stream* st, exon_hip_scan* scan, int64_t* 
   int64_t n = 0;
   // K4 over a VCF / BCF scan: the compared column and AVG's argument may be typed INFO fields (scan columns 4 ..), whose
   // type the FILE's header decides: Type=Integer -> Int32 values, compared / averaged as integers (schema_builder.rs:197-205)
-  if (exon_hip_stream_plan_kind(st) == EXON_HIP_PLAN_CMP_AVG_BY_GROUP && (scan->vcf || scan->bcf)) {
-    const std::vector<exon::InfoSpec>& specs = scan->vcf ? scan->vcf->info_specs : scan->bcf->info_specs;
+  if (exon_hip_stream_plan_kind(st) == EXON_HIP_PLAN_CMP_AVG_BY_GROUP && scan->vcf_like()) {
+    const std::vector<exon::InfoSpec>& specs = scan->info_specs();
     auto type_of = [&](int col) {
       return col >= 4 && (size_t)(col - 4) < specs.size() && specs[(size_t)(col - 4)].kind == 'i' ? EXON_HIP_X_INT32 : EXON_HIP_X_FLOAT32;
     };
     exon_hip_stream_set_value_types(st, type_of(exon_hip_stream_plan_column(st, 0)), type_of(exon_hip_stream_plan_column(st, 1)));
   }
-  if (!scan->gpu_parse && scan->gpu_candidate && scan->rows == 0 && (scan->vcf || scan->bcf)) {
-    const std::vector<exon::InfoSpec>& specs = scan->vcf ? scan->vcf->info_specs : scan->bcf->info_specs;
+  if (!scan->gpu_parse && scan->gpu_candidate && scan->rows == 0 && scan->vcf_like()) {
+    const std::vector<exon::InfoSpec>& specs = scan->info_specs();
     bool reads_host_only = false;
     for (int a = 0; a < 4; ++a) {
       const int col = exon_hip_stream_plan_column(st, a);
@@ -3083,19 +3071,7 @@ static int consume_scan_impl(exon_hip_stream* st, exon_hip_scan* scan, int64_t* 
     }
     if (!reads_host_only) {
       try {  // the host reader goes back to "header only": the bytes are the device's
-        if (scan->vcf) {
-          const exon::Compression c = scan->opt.compression == EXON_HIP_COMPRESSION_GZIP   ? exon::Compression::Gzip
-                                      : scan->opt.compression == EXON_HIP_COMPRESSION_NONE ? exon::Compression::None
-                                                                                           : exon::Compression::Auto;
-          exon::VCFConfig cfg = scan->vcf->config();
-          cfg.defer_decode = true;
-          if (wants_gpu_inflate(&scan->opt, scan->path.c_str())) cfg.threads = 1;
-          scan->vcf.reset(new exon::VCFBatchReader(scan->path, c, cfg));
-        } else {
-          exon::VCFConfig cfg = scan->bcf->config();
-          cfg.threads = 1;
-          scan->bcf.reset(new exon::BCFBatchReader(scan->path, cfg));
-        }
+        scan->reader = open_reader(*scan, Decode::Device);
         scan->gpu_parse = true;
         scan->gpu_candidate = false;
       } catch (const std::exception& e) {
@@ -3103,7 +3079,7 @@ static int consume_scan_impl(exon_hip_stream* st, exon_hip_scan* scan, int64_t* 
       }
     }
   }
-  if (scan->gpu_parse && (scan->vcf || scan->fastq || scan->bam || scan->bcf || scan->sam)) {
+  if (scan->gpu_parse) {
     // speculative GPU decode; when the device cannot decide something, restore the state and fall back to the host decoder
     exon_hip_ctx* ctx = exon_hip_stream_ctx(st);
     void* snap = nullptr;
@@ -3123,40 +3099,10 @@ static int consume_scan_impl(exon_hip_stream* st, exon_hip_scan* scan, int64_t* 
     if (const char* strict = getenv("EXON_HIP_GPU_PARSE_STRICT"); strict && strict[0] == '1')
       return fail(ctx, EXON_HIP_ESTATE, "%s: the GPU decoders could not decide every record and EXON_HIP_GPU_PARSE_STRICT=1 forbids the host decoders",
                   scan->path.c_str());
-    if (scan->parser) {
-      exon_hip_vcf_parser_destroy(scan->parser);
-      scan->parser = nullptr;
-    }
-    if (scan->bcf_parser) {
-      exon_hip_bcf_parser_destroy(scan->bcf_parser);
-      scan->bcf_parser = nullptr;
-    }
+    scan->parser.destroy();
     scan->gpu_parse = false;
     try {
-      const exon::Compression c = scan->opt.compression == EXON_HIP_COMPRESSION_GZIP   ? exon::Compression::Gzip
-                                  : scan->opt.compression == EXON_HIP_COMPRESSION_NONE ? exon::Compression::None
-                                                                                       : exon::Compression::Auto;
-      if (scan->vcf) {
-        exon::VCFConfig cfg = scan->vcf->config();
-        cfg.defer_decode = false;
-        cfg.threads = 0;
-        scan->vcf.reset(new exon::VCFBatchReader(scan->path, c, cfg));
-      } else if (scan->fastq) {
-        exon::FASTQConfig cfg = scan->fastq->config();
-        cfg.defer_decode = false;
-        cfg.threads = 0;
-        scan->fastq.reset(new exon::FASTQBatchReader(scan->path, c, cfg));
-      } else if (scan->bam) {
-        exon::BAMConfig cfg = scan->bam->config();
-        cfg.threads = 0;
-        scan->bam.reset(new exon::BAMBatchReader(scan->path, cfg));
-      } else if (scan->bcf) {
-        exon::VCFConfig cfg = scan->bcf->config();
-        cfg.threads = 0;
-        scan->bcf.reset(new exon::BCFBatchReader(scan->path, cfg));
-      } else {
-        scan->sam.reset(new exon::SAMBatchReader(scan->path, c, scan->sam->config()));
-      }
+      scan->reader = open_reader(*scan, Decode::Host);
     } catch (const std::exception& e) {
       return fail(nullptr, EXON_HIP_EINVAL, "%s", e.what());
     }
@@ -3169,8 +3115,8 @@ static int consume_scan_impl(exon_hip_stream* st, exon_hip_scan* scan, int64_t* 
     exon_hip_stream* st;
     ~NullGroupGuard() { exon_hip_stream_set_null_group(st, nullptr); }
   } null_group_guard{st};
-  if (exon_hip_stream_plan_kind(st) == EXON_HIP_PLAN_CMP_AVG_BY_GROUP && (scan->vcf || scan->bcf)) {
-    const std::vector<exon::InfoSpec>& specs = scan->vcf ? scan->vcf->info_specs : scan->bcf->info_specs;
+  if (exon_hip_stream_plan_kind(st) == EXON_HIP_PLAN_CMP_AVG_BY_GROUP && scan->vcf_like()) {
+    const std::vector<exon::InfoSpec>& specs = scan->info_specs();
     const int gcol = exon_hip_stream_plan_column(st, 2);
     if (gcol >= 4 && (size_t)(gcol - 4) < specs.size() && specs[(size_t)(gcol - 4)].kind == 's')
       exon_hip_stream_set_null_group(st, [scan, gcol]() -> int32_t {
@@ -3179,11 +3125,11 @@ static int consume_scan_impl(exon_hip_stream* st, exon_hip_scan* scan, int64_t* 
       });
   }
   // fast path: a multi-threaded VCF scan hands its slabs over as raw vectors (no Arrow batch in between)
-  if (scan->vcf) {
+  if (exon::VCFBatchReader* vcf = scan->vcf()) {
     try {
       exon::RawBatch rb;
       bool end = false;
-      while (scan->vcf->read_raw(&rb, &end)) {
+      while (vcf->read_raw(&rb, &end)) {
         const int rc = exon_hip_stream_push_raw(st, rb);
         if (rc < 0) return rc;
         n += rb.rows;
