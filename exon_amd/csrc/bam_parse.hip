@@ -116,15 +116,13 @@ __global__ __launch_bounds__(256) void k_bam_extract(const uint8_t* __restrict__
 }  // namespace
 
 struct exon_hip_bam_parser {
-  exon_hip_ctx* ctx = nullptr;
+  exon_hip_ctx* ctx;
+  PoolBufs bufs;
   int32_t n_ref = 0;
-  int64_t max_bytes = 0, max_rows = 0;
-  uint32_t max_seg = 0;
-  SegInfo* d_seg = nullptr;
-  uint32_t *d_base = nullptr, *d_rec_off = nullptr, *d_scalars = nullptr;
-  void* bufs[9] = {nullptr};
+  int64_t max_bytes = 0;
+  chain::ChainState chain;
   BamOut out{};
-  unsigned* h_scalars = nullptr;
+  explicit exon_hip_bam_parser(exon_hip_ctx* c) : ctx(c), bufs(c) {}
 };
 
 extern "C" {
@@ -133,53 +131,33 @@ int exon_hip_bam_parser_create(exon_hip_ctx* ctx, int32_t n_references, int64_t 
   if (!ctx || !outp || max_bytes < 64 || n_references < 0) return fail(ctx, EXON_HIP_EINVAL, "exon_hip_bam_parser_create: bad argument");
   if (max_bytes > 0xF0000000LL) return fail(ctx, EXON_HIP_EINVAL, "slab size must stay below 4 GiB (32-bit record offsets)");
   *outp = nullptr;
-  exon_hip_bam_parser* p = new (std::nothrow) exon_hip_bam_parser();
+  exon_hip_bam_parser* p = new (std::nothrow) exon_hip_bam_parser(ctx);
   if (!p) return fail(ctx, EXON_HIP_ENOMEM, "out of host memory");
-  p->ctx = ctx;
   p->n_ref = n_references;
   p->max_bytes = max_bytes;
-  p->max_seg = (uint32_t)((max_bytes + SEG - 1) / SEG);
-  p->max_rows = max_bytes / 36 + 1;
   hipSetDevice(ctx->device);
-  hipError_t e = hipSuccess;
-  auto dalloc = [&](void** ptr, size_t bytes) {
-    if (e == hipSuccess && !(*ptr = exon_pool_alloc(ctx, bytes))) e = hipErrorOutOfMemory;
-  };
-  const size_t r = (size_t)p->max_rows, w = (r + 31) / 32 * 4 + 64;
-  dalloc((void**)&p->d_seg, (size_t)p->max_seg * sizeof(SegInfo));
-  dalloc((void**)&p->d_base, (size_t)p->max_seg * 4);
-  dalloc((void**)&p->d_rec_off, (size_t)p->max_seg * SEG_CAP * 4);
-  dalloc((void**)&p->d_scalars, 16);
-  dalloc(&p->bufs[0], r * 4);
-  dalloc(&p->bufs[1], r + 64);
-  dalloc(&p->bufs[2], w);
-  dalloc(&p->bufs[3], r * 4);
-  dalloc(&p->bufs[4], w);
-  dalloc(&p->bufs[5], r * 8);
-  dalloc(&p->bufs[6], r * 8);
-  dalloc(&p->bufs[7], w);
-  dalloc(&p->bufs[8], r * 4);
-  if (e == hipSuccess) e = hipHostMalloc((void**)&p->h_scalars, 16);
-  if (e != hipSuccess) {
-    const std::string msg = hipGetErrorString(e);
-    exon_hip_bam_parser_destroy(p);
+  PoolBufs& b = p->bufs;
+  p->chain.alloc<BamFormat>(b, max_bytes);
+  const size_t r = (size_t)(max_bytes / 36 + 1), w = (r + 31) / 32 * 4 + 64;
+  p->out.flag = b.take<int32_t>(r * 4);
+  p->out.mapq = b.take<uint8_t>(r + 64);
+  p->out.mapq_valid = b.take<uint32_t>(w);
+  p->out.ref_id = b.take<int32_t>(r * 4);
+  p->out.ref_valid = b.take<uint32_t>(w);
+  p->out.start = b.take<int64_t>(r * 8);
+  p->out.end = b.take<int64_t>(r * 8);
+  p->out.pos_valid = b.take<uint32_t>(w);
+  p->out.rec_of_row = b.take<uint32_t>(r * 4);
+  if (b.status() != hipSuccess) {
+    const std::string msg = hipGetErrorString(b.status());
+    delete p;
     return fail(ctx, EXON_HIP_ENOMEM, "bam parser allocation: %s", msg.c_str());
   }
-  p->out = BamOut{(int32_t*)p->bufs[0], (uint8_t*)p->bufs[1], (uint32_t*)p->bufs[2], (int32_t*)p->bufs[3],
-                  (uint32_t*)p->bufs[4], (int64_t*)p->bufs[5], (int64_t*)p->bufs[6], (uint32_t*)p->bufs[7], (uint32_t*)p->bufs[8]};
   *outp = p;
   return EXON_HIP_OK;
 }
 
 int exon_hip_bam_parser_destroy(exon_hip_bam_parser* p) {
-  if (!p) return EXON_HIP_OK;
-  for (void* b : p->bufs)
-    if (b) exon_pool_free(p->ctx, b);
-  if (p->d_seg) exon_pool_free(p->ctx, p->d_seg);
-  if (p->d_base) exon_pool_free(p->ctx, p->d_base);
-  if (p->d_rec_off) exon_pool_free(p->ctx, p->d_rec_off);
-  if (p->d_scalars) exon_pool_free(p->ctx, p->d_scalars);
-  if (p->h_scalars) hipHostFree(p->h_scalars);
   delete p;
   return EXON_HIP_OK;
 }
@@ -191,6 +169,7 @@ int exon_hip_bam_parser_parse(exon_hip_bam_parser* p, void* stream, const uint8_
   memset(cols, 0, sizeof *cols);
   if (n_bytes == 0) return EXON_HIP_OK;
   hipStream_t s = pick_stream(ctx, stream);
+  chain::ChainState& c = p->chain;
   const uint32_t n = (uint32_t)n_bytes, n_seg = (n + SEG - 1) / SEG;
   // rows of this slab <= n / 36: the validity words they can touch are cleared by k_chain_check, the scalars by k_chain_walk
   chain::ZeroList zl{};
@@ -199,17 +178,13 @@ int exon_hip_bam_parser_parse(exon_hip_bam_parser* p, void* stream, const uint8_
   zl.p[2] = p->out.pos_valid;
   zl.n = 3;
   zl.words = (uint32_t)(((size_t)n / 36 + 1 + 31) / 32 + 1);
-  hipLaunchKernelGGL(chain::k_chain_walk<BamFormat>, dim3(n_seg), dim3(64), 0, s, d_data, n, BamFormat{p->n_ref}, p->d_seg, p->d_rec_off,
-                     p->d_scalars);
-  hipLaunchKernelGGL(chain::k_chain_check<0>, dim3(1), dim3(256), 0, s, p->d_seg, n_seg, p->d_base, p->d_scalars, zl);
-  hipLaunchKernelGGL(k_bam_extract, dim3(n_seg), dim3(256), 0, s, d_data, p->d_seg, p->d_base, p->d_rec_off, p->out, p->d_scalars);
-  HIP_TRY(ctx, hipGetLastError());
-  HIP_TRY(ctx, hipMemcpyAsync(p->h_scalars, p->d_scalars, 16, hipMemcpyDeviceToHost, s));
-  HIP_TRY(ctx, hipStreamSynchronize(s));
-  if (getenv("EXON_HIP_CHAIN_TRACE")) fprintf(stderr, "[exon-hip chain] %u segments, %u rows, plain proof %u\n", n_seg, p->h_scalars[0], p->h_scalars[3]);
-  cols->n_rows = p->h_scalars[0];
-  cols->n_undecided = p->h_scalars[1];
-  cols->consumed_bytes = p->h_scalars[2];
+  c.launch(s, d_data, n, BamFormat{p->n_ref}, zl);
+  hipLaunchKernelGGL(k_bam_extract, dim3(n_seg), dim3(256), 0, s, d_data, c.seg, c.base, c.rec_off, p->out, c.d_scalars);
+  if (int rc = c.read_back(ctx, s)) return rc;
+  if (getenv("EXON_HIP_CHAIN_TRACE")) fprintf(stderr, "[exon-hip chain] %u segments, %u rows, plain proof %u\n", n_seg, c.h_scalars[0], c.h_scalars[3]);
+  cols->n_rows = c.h_scalars[0];
+  cols->n_undecided = c.h_scalars[1];
+  cols->consumed_bytes = c.h_scalars[2];
   cols->flag = p->out.flag;
   cols->mapq = p->out.mapq;
   cols->mapq_valid = (uint8_t*)p->out.mapq_valid;

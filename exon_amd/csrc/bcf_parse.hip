@@ -340,24 +340,24 @@ __global__ __launch_bounds__(256) void k_bcf_remap(int32_t* __restrict__ filter_
 }  // namespace
 
 struct exon_hip_bcf_parser {
-  exon_hip_ctx* ctx = nullptr;
+  exon_hip_ctx* ctx;
+  PoolBufs bufs;
   int32_t n_contigs = 0, n_strings = 0, n_samples = 0, info_key = -1;
   BcfInfoKeys ik{};
-  void* ibufs[2 * (EXON_HIP_MAX_INFO_FIELDS - 1)] = {nullptr};  // value / validity buffers of INFO fields 1 .. 15 (field 0 lives in bufs[5] / bufs[6])
-  // list kinds: per key { vector offsets per row, item counts per row, Arrow offsets [rows + 1], item flags, item bitmap, items }
-  void* lbufs[6 * EXON_HIP_MAX_INFO_FIELDS] = {nullptr};
+  InfoBufs info[EXON_HIP_MAX_INFO_FIELDS];  // key 0's value / validity exist from _create on (the single key it takes)
   unsigned* d_list_blocks = nullptr;
-  size_t words = 0;
   int64_t max_bytes = 0, max_rows = 0;
-  uint32_t max_seg = 0;
-  SegInfo* d_seg = nullptr;
-  uint32_t *d_base = nullptr, *d_rec_off = nullptr, *d_scalars = nullptr;
-  void* bufs[8] = {nullptr};
-  void* fbufs[5] = {nullptr};
-  uint32_t* d_rec_of_row = nullptr;
+  chain::ChainState chain;
   BcfOut out{};
   FilterLists filters{};
-  unsigned* h_scalars = nullptr;
+  explicit exon_hip_bcf_parser(exon_hip_ctx* c) : ctx(c), bufs(c) {}
+  // key q's Number=1 value and validity buffers (once)
+  void take_value(int q) {
+    if (info[q].value) return;
+    const size_t r = (size_t)max_rows;
+    info[q].value = bufs.take<float>(r * 4);
+    info[q].valid = bufs.take<uint32_t>((r + 31) / 32 * 4 + 64);
+  }
 };
 
 extern "C" {
@@ -368,67 +368,43 @@ int exon_hip_bcf_parser_create(exon_hip_ctx* ctx, int32_t n_contigs, int32_t n_s
     return fail(ctx, EXON_HIP_EINVAL, "exon_hip_bcf_parser_create: bad argument");
   if (max_bytes > 0xF0000000LL) return fail(ctx, EXON_HIP_EINVAL, "slab size must stay below 4 GiB (32-bit record offsets)");
   *outp = nullptr;
-  exon_hip_bcf_parser* p = new (std::nothrow) exon_hip_bcf_parser();
+  exon_hip_bcf_parser* p = new (std::nothrow) exon_hip_bcf_parser(ctx);
   if (!p) return fail(ctx, EXON_HIP_ENOMEM, "out of host memory");
-  p->ctx = ctx;
   p->n_contigs = n_contigs;
   p->n_strings = n_strings;
   p->n_samples = n_samples;
   p->info_key = info_key;
   p->max_bytes = max_bytes;
-  p->max_seg = (uint32_t)((max_bytes + SEG - 1) / SEG);
   p->max_rows = max_bytes / 32 + 1;
   hipSetDevice(ctx->device);
-  hipError_t e = hipSuccess;
-  auto dalloc = [&](void** ptr, size_t bytes) {
-    if (e == hipSuccess && !(*ptr = exon_pool_alloc(ctx, bytes))) e = hipErrorOutOfMemory;
-  };
+  PoolBufs& b = p->bufs;
+  p->chain.alloc<BcfFormat>(b, max_bytes);
   const size_t r = (size_t)p->max_rows, w = (r + 31) / 32 * 4 + 64;
-  dalloc((void**)&p->d_seg, (size_t)p->max_seg * sizeof(SegInfo));
-  dalloc((void**)&p->d_base, (size_t)p->max_seg * 4);
-  dalloc((void**)&p->d_rec_off, (size_t)p->max_seg * SEG_CAP * 4);
-  dalloc((void**)&p->d_scalars, 16);
-  dalloc(&p->bufs[0], r * 4);
-  dalloc(&p->bufs[1], r * 8);
-  dalloc(&p->bufs[2], r * 4);
-  dalloc(&p->bufs[3], w);
-  dalloc(&p->bufs[4], r * 4);
-  dalloc(&p->bufs[5], r * 4);
-  dalloc(&p->bufs[6], w);
-  dalloc(&p->bufs[7], w);
-  dalloc((void**)&p->d_rec_of_row, r * 4 + 64);
-  dalloc(&p->fbufs[0], (size_t)FSLOTS * 8);
-  dalloc(&p->fbufs[1], (size_t)FSLOTS * 4);
-  dalloc(&p->fbufs[2], (size_t)FSLOTS * FLIST * 4);
-  dalloc(&p->fbufs[3], (size_t)FSLOTS * 4);
-  dalloc(&p->fbufs[4], 16);
-  if (e == hipSuccess) e = hipMemset(p->fbufs[0], 0, (size_t)FSLOTS * 8);
-  if (e == hipSuccess) e = hipMemset(p->fbufs[1], 0xFF, (size_t)FSLOTS * 4);
-  if (e == hipSuccess) e = hipMemset(p->fbufs[4], 0, 16);
-  if (e == hipSuccess) e = hipHostMalloc((void**)&p->h_scalars, 16);
-  if (e != hipSuccess) {
-    const std::string msg = hipGetErrorString(e);
-    exon_hip_bcf_parser_destroy(p);
+  p->out.chrom_id = b.take<int32_t>(r * 4);
+  p->out.pos = b.take<int64_t>(r * 8);
+  p->out.qual = b.take<float>(r * 4);
+  p->out.qual_valid = b.take<uint32_t>(w);
+  p->out.filter_id = b.take<int32_t>(r * 4);
+  p->take_value(0);
+  p->out.pos_valid = b.take<uint32_t>(w);
+  p->out.rec_of_row = b.take<uint32_t>(r * 4 + 64);
+  p->filters.keys = b.take<unsigned long long>((size_t)FSLOTS * 8, 0);
+  p->filters.ids = b.take<int32_t>((size_t)FSLOTS * 4, 0xFF);
+  p->filters.lists = b.take<int32_t>((size_t)FSLOTS * FLIST * 4);
+  p->filters.counts = b.take<int32_t>((size_t)FSLOTS * 4);
+  p->filters.counters = b.take<int32_t>(16, 0);
+  if (b.status() != hipSuccess) {
+    const std::string msg = hipGetErrorString(b.status());
+    delete p;
     return fail(ctx, EXON_HIP_ENOMEM, "bcf parser allocation: %s", msg.c_str());
   }
-  p->out = BcfOut{};
-  p->out.chrom_id = (int32_t*)p->bufs[0];
-  p->out.pos = (int64_t*)p->bufs[1];
-  p->out.qual = (float*)p->bufs[2];
-  p->out.qual_valid = (uint32_t*)p->bufs[3];
-  p->out.filter_id = (int32_t*)p->bufs[4];
-  p->out.info[0] = (float*)p->bufs[5];
-  p->out.info_valid[0] = (uint32_t*)p->bufs[6];
-  p->out.pos_valid = (uint32_t*)p->bufs[7];
-  p->out.rec_of_row = p->d_rec_of_row;
-  p->words = w;
+  p->out.info[0] = p->info[0].value;
+  p->out.info_valid[0] = static_cast<uint32_t*>(p->info[0].valid);
   if (info_key >= 0) {
     p->ik.n = 1;
     p->ik.key[0] = info_key;
     p->ik.kind[0] = 'f';
   }
-  p->filters = FilterLists{(unsigned long long*)p->fbufs[0], (int32_t*)p->fbufs[1], (int32_t*)p->fbufs[2], (int32_t*)p->fbufs[3],
-                           (int32_t*)p->fbufs[4]};
   *outp = p;
   return EXON_HIP_OK;
 }
@@ -445,43 +421,25 @@ int exon_hip_bcf_parser_set_info_keys(exon_hip_bcf_parser* p, const int32_t* key
       return fail(p->ctx, EXON_HIP_EUNSUPPORTED, "INFO kind '%c' is not decoded on the device", kinds[q]);
     p->ik.key[q] = keys[q];
     p->ik.kind[q] = kinds[q];
-    if (kinds[q] == 'F' || kinds[q] == 'I') {  // an item takes at least one byte of the slab
-      const size_t r = (size_t)p->max_rows, items = (size_t)p->max_bytes + 1;
-      const size_t sizes[6] = {r * 4, r * 4, (r + 1) * 4, items, items / 8 + 64, items * 4};
-      for (int k = 0; k < 6; ++k)
-        if (!p->lbufs[6 * q + k] && !(p->lbufs[6 * q + k] = exon_pool_alloc(p->ctx, sizes[k]))) return fail(p->ctx, EXON_HIP_ENOMEM, "INFO list buffers");
-      if (!p->d_list_blocks && !(p->d_list_blocks = (unsigned*)exon_pool_alloc(p->ctx, (r / LIST_TPB + 2) * 4))) return fail(p->ctx, EXON_HIP_ENOMEM, "INFO list buffers");
-      p->out.lv_off[q] = (uint32_t*)p->lbufs[6 * q + 0];
-      p->out.lv_cnt[q] = (uint32_t*)p->lbufs[6 * q + 1];
+    InfoBufs& k = p->info[q];
+    const bool list = kinds[q] == 'F' || kinds[q] == 'I';
+    if (list) {  // an item takes at least one byte of the slab
+      if (!k.lv_off) k.take_list(p->bufs, (size_t)p->max_rows, (size_t)p->max_bytes + 1);
+      if (!p->d_list_blocks) p->d_list_blocks = p->bufs.take<unsigned>(((size_t)p->max_rows / LIST_TPB + 2) * 4);
+      if (p->bufs.status() != hipSuccess) return fail(p->ctx, EXON_HIP_ENOMEM, "INFO list buffers");
+      p->out.lv_off[q] = k.lv_off;
+      p->out.lv_cnt[q] = k.lv_cnt;
     }
-    if (q == 0) {
-      if (kinds[q] == 'F' || kinds[q] == 'I') p->out.info[0] = (float*)p->lbufs[5];
-      continue;
-    }
-    if (!p->ibufs[2 * (q - 1)]) p->ibufs[2 * (q - 1)] = exon_pool_alloc(p->ctx, (size_t)p->max_rows * 4);
-    if (!p->ibufs[2 * (q - 1) + 1]) p->ibufs[2 * (q - 1) + 1] = exon_pool_alloc(p->ctx, p->words);
-    if (!p->ibufs[2 * (q - 1)] || !p->ibufs[2 * (q - 1) + 1]) return fail(p->ctx, EXON_HIP_ENOMEM, "INFO column buffers");
-    p->out.info[q] = (kinds[q] == 'F' || kinds[q] == 'I') ? (float*)p->lbufs[6 * q + 5] : (float*)p->ibufs[2 * (q - 1)];
-    p->out.info_valid[q] = (uint32_t*)p->ibufs[2 * (q - 1) + 1];
+    p->take_value(q);
+    if (p->bufs.status() != hipSuccess) return fail(p->ctx, EXON_HIP_ENOMEM, "INFO column buffers");
+    p->out.info[q] = list ? k.items : k.value;
+    p->out.info_valid[q] = static_cast<uint32_t*>(k.valid);
   }
   p->info_key = n ? keys[0] : -1;
   return EXON_HIP_OK;
 }
 
 int exon_hip_bcf_parser_destroy(exon_hip_bcf_parser* p) {
-  if (!p) return EXON_HIP_OK;
-  for (void* b : p->ibufs) exon_pool_free(p->ctx, b);
-  for (void* b : p->lbufs)
-    if (b) exon_pool_free(p->ctx, b);
-  if (p->d_list_blocks) exon_pool_free(p->ctx, p->d_list_blocks);
-  for (void* b : p->bufs) exon_pool_free(p->ctx, b);
-  for (void* b : p->fbufs) exon_pool_free(p->ctx, b);
-  exon_pool_free(p->ctx, p->d_seg);
-  exon_pool_free(p->ctx, p->d_base);
-  exon_pool_free(p->ctx, p->d_rec_off);
-  if (p->d_rec_of_row) exon_pool_free(p->ctx, p->d_rec_of_row);
-  exon_pool_free(p->ctx, p->d_scalars);
-  if (p->h_scalars) hipHostFree(p->h_scalars);
   delete p;
   return EXON_HIP_OK;
 }
@@ -493,6 +451,7 @@ int exon_hip_bcf_parser_parse(exon_hip_bcf_parser* p, void* stream, const uint8_
   memset(cols, 0, sizeof *cols);
   if (n_bytes == 0) return EXON_HIP_OK;
   hipStream_t s = pick_stream(ctx, stream);
+  chain::ChainState& c = p->chain;
   const uint32_t n = (uint32_t)n_bytes, n_seg = (n + SEG - 1) / SEG;
   // rows of this slab <= n / 32: the validity words they can touch are cleared by k_chain_check, the scalars by k_chain_walk
   chain::ZeroList zl{};
@@ -500,33 +459,27 @@ int exon_hip_bcf_parser_parse(exon_hip_bcf_parser* p, void* stream, const uint8_
   zl.p[zl.n++] = p->out.pos_valid;
   for (int q = 0; q < (p->ik.n ? p->ik.n : 1); ++q) zl.p[zl.n++] = p->out.info_valid[q];
   zl.words = (uint32_t)(((size_t)n / 32 + 1 + 31) / 32 + 1);
-  hipLaunchKernelGGL(chain::k_chain_walk<BcfFormat>, dim3(n_seg), dim3(64), 0, s, d_data, n, BcfFormat{p->n_contigs, p->n_samples}, p->d_seg,
-                     p->d_rec_off, p->d_scalars);
-  hipLaunchKernelGGL(chain::k_chain_check<0>, dim3(1), dim3(256), 0, s, p->d_seg, n_seg, p->d_base, p->d_scalars, zl);
-  hipLaunchKernelGGL(k_bcf_extract, dim3(n_seg), dim3(256), 0, s, d_data, p->d_seg, p->d_base, p->d_rec_off, p->out, p->filters,
-                     p->n_contigs, p->n_strings, p->ik, p->d_scalars);
+  c.launch(s, d_data, n, BcfFormat{p->n_contigs, p->n_samples}, zl);
+  hipLaunchKernelGGL(k_bcf_extract, dim3(n_seg), dim3(256), 0, s, d_data, c.seg, c.base, c.rec_off, p->out, p->filters,
+                     p->n_contigs, p->n_strings, p->ik, c.d_scalars);
   hipLaunchKernelGGL(k_bcf_assign, dim3(1), dim3(256), 0, s, p->filters);
-  hipLaunchKernelGGL(k_bcf_remap, dim3(std::min<uint32_t>(n_seg * 4 + 1, 4096)), dim3(256), 0, s, p->out.filter_id, p->d_scalars, p->filters.ids);
+  hipLaunchKernelGGL(k_bcf_remap, dim3(std::min<uint32_t>(n_seg * 4 + 1, 4096)), dim3(256), 0, s, p->out.filter_id, c.d_scalars, p->filters.ids);
+  const unsigned row_bound = (unsigned)p->max_rows;
+  const int lblocks = (int)((std::min<int64_t>(p->max_rows, n_bytes / 32 + 1) + LIST_TPB - 1) / LIST_TPB);  // a BCF record is >= 32 bytes
+  const unsigned cap_items = (unsigned)std::min<int64_t>(p->max_bytes + 1, 0xFFFFFFFFLL);
   for (int q = 0; q < p->ik.n; ++q) {  // list-valued fields: counts -> offsets -> items -> child validity
     const char kind = p->ik.kind[q];
     if (kind != 'F' && kind != 'I') continue;
-    const unsigned row_bound = (unsigned)p->max_rows;
-    const int lblocks = (int)((std::min<int64_t>(p->max_rows, n_bytes / 32 + 1) + LIST_TPB - 1) / LIST_TPB);  // a BCF record is >= 32 bytes
-    int32_t* offsets = (int32_t*)p->lbufs[6 * q + 2];
-    hipLaunchKernelGGL(k_list_block_sums, dim3(lblocks), dim3(LIST_TPB), 0, s, p->out.lv_cnt[q], p->d_scalars, row_bound, p->d_list_blocks);
-    hipLaunchKernelGGL(k_list_scan_blocks, dim3(1), dim3(256), 0, s, p->d_list_blocks, lblocks, p->d_scalars + 3);
-    hipLaunchKernelGGL(k_bcf_list_fill, dim3(lblocks), dim3(LIST_TPB), 0, s, d_data, p->out.lv_off[q], p->out.lv_cnt[q], p->d_list_blocks, p->d_scalars,
-                       row_bound, (unsigned)std::min<int64_t>(p->max_bytes + 1, 0xFFFFFFFFLL), kind, offsets, p->out.info[q],
-                       (uint8_t*)p->lbufs[6 * q + 3], p->d_scalars + 1);
-    hipLaunchKernelGGL(k_pack_bits, dim3(1024), dim3(256), 0, s, (const uint8_t*)p->lbufs[6 * q + 3], offsets, p->d_scalars, row_bound,
-                       (unsigned)std::min<int64_t>(p->max_bytes + 1, 0xFFFFFFFFLL), (uint8_t*)p->lbufs[6 * q + 4]);
+    const InfoBufs& k = p->info[q];
+    launch_list_scan(s, k.lv_cnt, c.d_scalars, row_bound, lblocks, p->d_list_blocks, c.d_scalars + 3);
+    hipLaunchKernelGGL(k_bcf_list_fill, dim3(lblocks), dim3(LIST_TPB), 0, s, d_data, k.lv_off, k.lv_cnt, p->d_list_blocks, c.d_scalars,
+                       row_bound, cap_items, kind, k.offsets, k.items, k.item_flags, c.d_scalars + 1);
+    k.pack_bits(s, c.d_scalars, row_bound, cap_items);
   }
-  HIP_TRY(ctx, hipGetLastError());
-  HIP_TRY(ctx, hipMemcpyAsync(p->h_scalars, p->d_scalars, 12, hipMemcpyDeviceToHost, s));
-  HIP_TRY(ctx, hipStreamSynchronize(s));
-  cols->n_rows = p->h_scalars[0];
-  cols->n_undecided = p->h_scalars[1];
-  cols->consumed_bytes = p->h_scalars[2];
+  if (int rc = c.read_back(ctx, s)) return rc;
+  cols->n_rows = c.h_scalars[0];
+  cols->n_undecided = c.h_scalars[1];
+  cols->consumed_bytes = c.h_scalars[2];
   cols->chrom_id = p->out.chrom_id;
   cols->pos = p->out.pos;
   cols->pos_valid = (uint8_t*)p->out.pos_valid;  // pos0 = -1 (POS 0) -> NULL
@@ -541,8 +494,8 @@ int exon_hip_bcf_parser_parse(exon_hip_bcf_parser* p, void* stream, const uint8_
     cols->infos_valid[q] = (uint8_t*)p->out.info_valid[q];
     cols->info_kinds[q] = p->ik.kind[q];
     if (p->ik.kind[q] == 'F' || p->ik.kind[q] == 'I') {
-      cols->list_offsets[q] = (int32_t*)p->lbufs[6 * q + 2];
-      cols->list_item_valid[q] = (uint8_t*)p->lbufs[6 * q + 4];
+      cols->list_offsets[q] = p->info[q].offsets;
+      cols->list_item_valid[q] = p->info[q].item_bits;
     }
   }
   return EXON_HIP_OK;

@@ -10,10 +10,12 @@
 //                    ignored).  Any mismatch or a malformed record -> undecided: the caller decodes on the host instead.
 //                    Exclusive scan of the counts -> first row of each segment.
 // A format F provides: MIN_HEADER (bytes a plausibility check needs), MIN_RECORD (smallest record), record_bytes(d, r)
-// (total size of the record at r, 0 = malformed) and plausible(d, n, r).
+// (total size of the record at r, 0 = malformed) and plausible(d, n, r).  ChainState holds a parser's buffers of the walk.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include "internal.h"
 
 namespace chain {
 
@@ -203,5 +205,39 @@ __global__ __launch_bounds__(256) void k_chain_check(SegInfo* __restrict__ seg, 
   __syncthreads();
   if (threadIdx.x == 0 && s_err) atomicAdd(&scalars[1], 1u);
 }
+
+// The chain walk's state in a BAM or BCF parser: segment records, first row of every segment, record offsets, the slab's scalars
+// {rows, undecided, consumed bytes, plain proof} and their pinned mirror.
+struct ChainState {
+  SegInfo* seg = nullptr;
+  uint32_t* base = nullptr;
+  uint32_t* rec_off = nullptr;
+  unsigned* d_scalars = nullptr;
+  unsigned* h_scalars = nullptr;
+
+  template <class F>
+  void alloc(PoolBufs& b, int64_t max_bytes) {
+    const size_t max_seg = (size_t)((max_bytes + SEG - 1) / SEG);
+    seg = b.take<SegInfo>(max_seg * sizeof(SegInfo));
+    base = b.take<uint32_t>(max_seg * 4);
+    rec_off = b.take<uint32_t>(max_seg * seg_cap<F>() * 4);
+    d_scalars = b.take<unsigned>(16);
+    h_scalars = b.pinned<unsigned>(16);
+  }
+  // walk + proof over the slab d[0 .. n): rows, their segments' first rows and record offsets for the format's extract kernel
+  template <class F>
+  void launch(hipStream_t s, const uint8_t* d, uint32_t n, F fmt, const ZeroList& zl) {
+    const uint32_t n_seg = (n + SEG - 1) / SEG;
+    hipLaunchKernelGGL(k_chain_walk<F>, dim3(n_seg), dim3(64), 0, s, d, n, fmt, seg, rec_off, d_scalars);
+    hipLaunchKernelGGL(k_chain_check<0>, dim3(1), dim3(256), 0, s, seg, n_seg, base, d_scalars, zl);
+  }
+  // the scalars, once everything queued on `s` has run
+  int read_back(exon_hip_ctx* ctx, hipStream_t s) {
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipMemcpyAsync(h_scalars, d_scalars, 16, hipMemcpyDeviceToHost, s));
+    HIP_TRY(ctx, hipStreamSynchronize(s));
+    return EXON_HIP_OK;
+  }
+};
 
 }  // namespace chain

@@ -10,8 +10,7 @@
 //
 // Pipeline for one slab of complete lines:
 //   k_index_lines      positions of all newlines, in order (line i = (nl[i-1], nl[i])), in ONE pass: decoupled look-back over
-//                      the tiles' counts (round 5; k_count_newlines / k_scan_blocks / k_fill_newlines, the three-launch form of
-//                      rounds 1-4, stay behind EXON_HIP_LINE_INDEX_PASSES=2)
+//                      the tiles' counts (LineIndex, shared with the FASTQ and SAM parsers below)
 //   k_parse_lines      one thread per line: split on tabs, parse, look names up in hash tables, ballot the validity
 //                      bitmaps; FILTER lists not seen before are inserted with atomicCAS (slot = provisional id)
 //   k_assign_filters   dense ids for newly inserted FILTER lists, their text copied to a persistent pool
@@ -31,8 +30,6 @@
 namespace {
 
 constexpr int TPB = 256;
-constexpr int BYTES_PER_THREAD = 64;  // four 16-byte loads per thread (one cache line): 4 KiB workgroups were launch-bound
-constexpr int BYTES_PER_BLOCK = TPB * BYTES_PER_THREAD;
 constexpr int FILTER_SLOTS = 8192;  // open addressing; at most EXON_HIP_MAX_GROUPS distinct lists are supported
 constexpr int FILTER_POOL = 1 << 20;
 
@@ -70,102 +67,16 @@ __device__ __forceinline__ uint4 load16(const uint8_t* text, int64_t n, int64_t 
   return v;
 }
 
-__global__ __launch_bounds__(TPB) void k_count_newlines(const uint8_t* __restrict__ text, int64_t n, unsigned skip,
-                                                        unsigned* __restrict__ block_counts) {
-  __shared__ unsigned red[TPB / 64];
-  const int64_t off = ((int64_t)blockIdx.x * TPB + threadIdx.x) * BYTES_PER_THREAD;
-  unsigned c = 0;
-#pragma unroll
-  for (int j = 0; j < BYTES_PER_THREAD / 16; ++j)
-    if (off + 16 * j < n) c += (unsigned)count_nl16(load16(text, n, off + 16 * j, skip));
-  for (int o = 32; o > 0; o >>= 1) c += __shfl_down(c, o, 64);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = c;
-  __syncthreads();
-  if (threadIdx.x == 0) block_counts[blockIdx.x] = red[0] + red[1] + red[2] + red[3];
-}
-
-// exclusive scan of `nb` workgroup totals in place; total -> *n_lines.  zero_rest: n_lines is the slab's scalar block
-// {lines, exceptions, consumed, -}: words 1..3 are cleared here (the kernels behind this one add to them), which replaces
-// the 16-byte hipMemsetAsync every slab used to start with -- a tiny kernel of its own, queued behind the inflate
-// (One workgroup of 256 threads, not 1024: a workgroup starts only when ONE CU has wave slots for all of it, and beside the
-//  inflate of the next slab -- 30 of a CU's 32 slots -- sixteen free slots took 0.5-1.3 ms to appear: round 4.)
-__global__ __launch_bounds__(256) void k_scan_blocks(unsigned* __restrict__ counts, int nb, unsigned* __restrict__ n_lines, int zero_rest) {
-  if (zero_rest && threadIdx.x >= 1 && threadIdx.x <= 3) n_lines[threadIdx.x] = 0;
-  __shared__ unsigned part[256];
-  const int per = (nb + 255) / 256;
-  const int b0 = threadIdx.x * per, b1 = min(nb, b0 + per);
-  unsigned s = 0;
-  for (int b = b0; b < b1; ++b) s += counts[b];
-  part[threadIdx.x] = s;
-  __syncthreads();
-  for (int o = 1; o < 256; o <<= 1) {  // inclusive Hillis-Steele scan
-    unsigned v = threadIdx.x >= o ? part[threadIdx.x - o] : 0u;
-    __syncthreads();
-    part[threadIdx.x] += v;
-    __syncthreads();
-  }
-  unsigned run = threadIdx.x ? part[threadIdx.x - 1] : 0u;
-  for (int b = b0; b < b1; ++b) {
-    const unsigned c = counts[b];
-    counts[b] = run;
-    run += c;
-  }
-  if (threadIdx.x == 255) *n_lines = part[255];
-}
-
-__global__ __launch_bounds__(TPB) void k_fill_newlines(const uint8_t* __restrict__ text, int64_t n, unsigned skip,
-                                                       const unsigned* __restrict__ block_offsets,
-                                                       unsigned* __restrict__ nl_pos, unsigned cap) {
-  __shared__ unsigned wave_tot[TPB / 64];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int64_t off = ((int64_t)blockIdx.x * TPB + threadIdx.x) * BYTES_PER_THREAD;
-  constexpr int Q = BYTES_PER_THREAD / 16;
-  uint4 v[Q];
-  unsigned c = 0;
-#pragma unroll
-  for (int j = 0; j < Q; ++j) {
-    v[j] = uint4{0, 0, 0, 0};
-    if (off + 16 * j < n) {
-      v[j] = load16(text, n, off + 16 * j, skip);
-      c += (unsigned)count_nl16(v[j]);
-    }
-  }
-  unsigned incl = c;  // inclusive scan within the wave
-  for (int o = 1; o < 64; o <<= 1) {
-    const unsigned t = __shfl_up(incl, o, 64);
-    if (lane >= o) incl += t;
-  }
-  if (lane == 63) wave_tot[wave] = incl;
-  __syncthreads();
-  unsigned base = block_offsets[blockIdx.x];
-  for (int w = 0; w < wave; ++w) base += wave_tot[w];
-  unsigned k = base + incl - c;
-  if (c) {
-#pragma unroll
-    for (int j = 0; j < Q; ++j) {
-      const unsigned w[4] = {v[j].x, v[j].y, v[j].z, v[j].w};
-      if ((w[0] | w[1] | w[2] | w[3]) == 0) continue;
-#pragma unroll
-      for (int i = 0; i < 16; ++i)
-        if (((w[i >> 2] >> (8 * (i & 3))) & 0xFF) == 0x0A) {
-          if (k < cap) nl_pos[k] = (unsigned)(off + 16 * j + i);  // more lines than VCF records can fill: reported by the caller
-          ++k;
-        }
-    }
-  }
-}
-
 // ---- the line index in ONE pass over the text (round 5) -------------------------------------------------------------------------
-// k_count_newlines + k_scan_blocks + k_fill_newlines read the slab twice and are three launches (each of which queues behind the
-// next slab's inflate).  Here a workgroup takes its tile off a counter (so tile t runs only after tiles 0 .. t-1 have started),
-// counts its newlines, publishes the count, finds the number of newlines in front of its tile by looking BACK over its
-// predecessors' published words -- a word is (generation, value, flag): flag 1 = the tile's own count, flag 2 = the count of
-// everything up to and including the tile; a wave reads 64 predecessors at a time and stops at the first "inclusive" word -- and
-// writes the positions of its newlines.  Decoupled look-back; the words are written and read with agent-scope atomics (the 8
-// XCDs do not share an L2), the generation makes last slab's words read as "not there yet" (no clearing pass), and the counter
-// wraps to 0 by itself (atomicInc).  A look-back that does not see its predecessor within LOOKBACK_SPINS reads gives up, poisons its
-// own word (the tiles behind it give up at once) and marks the slab "one undecided record": the host decoder takes it -- a hang is
-// not possible.
+// A workgroup takes its tile off a counter (so tile t runs only after tiles 0 .. t-1 have started), counts its newlines, publishes
+// the count, finds the number of newlines in front of its tile by looking BACK over its predecessors' published words -- a word is
+// (generation, value, flag): flag 1 = the tile's own count, flag 2 = the count of everything up to and including the tile; a wave
+// reads 64 predecessors at a time and stops at the first "inclusive" word -- and writes the positions of its newlines.  Decoupled
+// look-back; the words are written and read with agent-scope atomics (the 8 XCDs do not share an L2), the generation makes last
+// slab's words read as "not there yet" (no clearing pass), and the counter wraps to 0 by itself (atomicInc).  A look-back that does
+// not see its predecessor within LOOKBACK_SPINS reads gives up, poisons its own word (the tiles behind it give up at once) and marks
+// the slab "one undecided record": the host decoder takes it -- a hang is not possible.  (Rounds 1-4 counted, scanned and filled in
+// three launches that read the slab twice.)
 constexpr unsigned LOOKBACK_SPINS = 1u << 22;
 __device__ __forceinline__ void st_agent_u64(unsigned long long* p, unsigned long long v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ unsigned long long ld_agent_u64(const unsigned long long* p) {
@@ -183,7 +94,7 @@ constexpr int IDX_TPB = EXON_IDX_TPB, IDX_BPT = EXON_IDX_BPT;
 __global__ __launch_bounds__(IDX_TPB) void k_index_lines(const uint8_t* __restrict__ text, int64_t n, unsigned skip, unsigned long long* __restrict__ words,
                                                          unsigned* __restrict__ tile_ctr, unsigned nblocks, unsigned gen, unsigned* __restrict__ nl_pos,
                                                          unsigned cap, unsigned* __restrict__ scalars) {
-  constexpr int TPB = IDX_TPB, BYTES_PER_THREAD = IDX_BPT;  // (this kernel's own tile: shadows the other kernels' constants)
+  constexpr int TPB = IDX_TPB, BYTES_PER_THREAD = IDX_BPT;  // (this kernel's own tile: shadows the other kernels' TPB)
   __shared__ unsigned wave_tot[TPB / 64];
   __shared__ unsigned s_tile, s_prefix, s_bad;
   if (threadIdx.x == 0) {
@@ -280,7 +191,7 @@ __global__ __launch_bounds__(IDX_TPB) void k_index_lines(const uint8_t* __restri
     }
   }
   // the last tile in tile order holds the total; it also clears words 1..3 of the slab's scalar block {lines, exceptions,
-  // consumed, -}, which only the kernels BEHIND this one add to (what k_scan_blocks did; no 16-byte memset per slab)
+  // consumed, -}, which only the kernels BEHIND this one add to (no 16-byte memset per slab)
   if (tile == nblocks - 1u && threadIdx.x < 4) {
     if (threadIdx.x == 0) scalars[0] = s_prefix + T;
     else scalars[threadIdx.x] = 0;
@@ -293,28 +204,52 @@ __global__ void k_index_verdict(const unsigned* __restrict__ tile_ctr, unsigned 
     scalars[1] = 1;
   }
 }
-// one launch instead of count / scan / fill; EXON_HIP_LINE_INDEX_PASSES=2 keeps the three kernels (A/B)
-static void launch_line_index(hipStream_t s, const uint8_t* d_text, int64_t n_bytes, unsigned skip, unsigned* d_block_counts, int64_t max_blocks, int nblocks, unsigned* gen,
-                              unsigned* d_nl, unsigned cap, unsigned* d_scalars) {
-  static const bool two_pass = [] {
-    const char* v = getenv("EXON_HIP_LINE_INDEX_PASSES");
-    return v && v[0] == '2';
-  }();
-  if (two_pass) {
-    hipLaunchKernelGGL(k_count_newlines, dim3(nblocks), dim3(TPB), 0, s, d_text, n_bytes, skip, d_block_counts);
-    hipLaunchKernelGGL(k_scan_blocks, dim3(1), dim3(256), 0, s, d_block_counts, nblocks, d_scalars, 1);
-    hipLaunchKernelGGL(k_fill_newlines, dim3(nblocks), dim3(TPB), 0, s, d_text, n_bytes, skip, d_block_counts, d_nl, cap);
-    return;
+
+// The line index of the VCF, FASTQ and SAM parsers: k_index_lines' look-back words (one per tile, then the tile counter and the
+// sticky verdict word), the newline positions, the slab's scalars {lines, undecided, consumed bytes, -} and their pinned mirror.
+struct LineIndex {
+  static constexpr int64_t TILE_BYTES = (int64_t)IDX_TPB * IDX_BPT;
+  unsigned long long* words = nullptr;
+  unsigned* nl = nullptr;
+  unsigned* d_scalars = nullptr;
+  unsigned* h_scalars = nullptr;
+  int64_t max_bytes = 0;
+  unsigned tiles = 0, cap = 0, gen = 0;  // cap: newlines `nl` holds
+
+  void alloc(PoolBufs& b, int64_t max_bytes_, int64_t max_lines) {
+    max_bytes = max_bytes_;
+    tiles = (unsigned)((max_bytes + TILE_BYTES - 1) / TILE_BYTES);
+    cap = (unsigned)max_lines;
+    words = b.take<unsigned long long>(((size_t)tiles + 1) * 8, 0);  // (zero: no word of any generation, the tile counter at 0)
+    nl = b.take<unsigned>((size_t)max_lines * 4);
+    d_scalars = b.take<unsigned>(16);
+    h_scalars = b.pinned<unsigned>(16);
   }
-  unsigned long long* words = reinterpret_cast<unsigned long long*>(d_block_counts);  // [max blocks] words, then the tile counter
-  *gen = (*gen + 1u) & 0x3FFFFFFFu;
-  if (*gen == 0) *gen = 1;
-  const int64_t tile_bytes = (int64_t)IDX_TPB * IDX_BPT;
-  const unsigned ntiles = (unsigned)std::max<int64_t>(1, (n_bytes + tile_bytes - 1) / tile_bytes);  // (<= nblocks <= max_blocks: the words fit)
-  hipLaunchKernelGGL(k_index_lines, dim3(ntiles), dim3(IDX_TPB), 0, s, d_text, n_bytes, skip, words, reinterpret_cast<unsigned*>(words + max_blocks), ntiles, *gen, d_nl,
-                     cap, d_scalars);
-  hipLaunchKernelGGL(k_index_verdict, dim3(1), dim3(1), 0, s, reinterpret_cast<const unsigned*>(words + max_blocks), *gen, d_scalars);
-}
+  // the kernels read aligned 16-byte groups: start at the aligned address at or below the slab and ignore the `skip` bytes before it
+  int align(exon_hip_ctx* ctx, const uint8_t** text, int64_t* n_bytes, unsigned* skip) const {
+    *skip = (unsigned)(reinterpret_cast<uintptr_t>(*text) & 15);
+    *text -= *skip;
+    *n_bytes += *skip;
+    if (*n_bytes > max_bytes) return fail(ctx, EXON_HIP_EINVAL, "slab of %lld bytes exceeds the parser's %lld", (long long)*n_bytes, (long long)max_bytes);
+    return EXON_HIP_OK;
+  }
+  void launch(hipStream_t s, const uint8_t* text, int64_t n_bytes, unsigned skip) {
+    gen = (gen + 1u) & 0x3FFFFFFFu;
+    if (gen == 0) gen = 1;
+    const unsigned ntiles = (unsigned)std::max<int64_t>(1, (n_bytes + TILE_BYTES - 1) / TILE_BYTES);  // (<= tiles: the words fit)
+    unsigned* tile_ctr = reinterpret_cast<unsigned*>(words + tiles);
+    hipLaunchKernelGGL(k_index_lines, dim3(ntiles), dim3(IDX_TPB), 0, s, text, n_bytes, skip, words, tile_ctr, ntiles, gen, nl, cap, d_scalars);
+    hipLaunchKernelGGL(k_index_verdict, dim3(1), dim3(1), 0, s, tile_ctr, gen, d_scalars);
+  }
+  // the scalars, once everything queued on `s` has run
+  int read_back(exon_hip_ctx* ctx, hipStream_t s) {
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipMemcpyAsync(h_scalars, d_scalars, 16, hipMemcpyDeviceToHost, s));
+    HIP_TRY(ctx, hipStreamSynchronize(s));
+    return EXON_HIP_OK;
+  }
+  int64_t consumed(unsigned skip) const { return h_scalars[2] > skip ? (int64_t)h_scalars[2] - skip : 0; }
+};
 
 // scalars[2] = bytes up to and including the last newline (what a caller may discard after this slab)
 __global__ void k_last_newline(const unsigned* __restrict__ nl_pos, unsigned* __restrict__ scalars, unsigned cap) {
@@ -718,8 +653,8 @@ __global__ __launch_bounds__(TPB) void k_remap_filters(int32_t* __restrict__ fil
 
 }  // namespace
 
-// Upload an open-addressing name table (names[i] -> id i).  bufs[0..5) receive the device allocations.
-static hipError_t build_name_table(exon_hip_ctx* ctx, const char* const* names_in, int32_t n, void** bufs, NameTable* out) {
+// Upload an open-addressing name table (names[i] -> id i) into buffers of `b` (a failure stays in b.status()).
+static void build_name_table(PoolBufs& b, const char* const* names_in, int32_t n, NameTable* out) {
   int cap = 16;
   while (cap < 2 * n + 1) cap <<= 1;
   std::vector<uint64_t> keys((size_t)cap, 0);
@@ -737,23 +672,29 @@ static hipError_t build_name_table(exon_hip_ctx* ctx, const char* const* names_i
     tlen[(size_t)slot] = (uint32_t)nm.size();
     pool += nm;
   }
-  hipError_t e = hipSuccess;
-  auto dalloc = [&](void** ptr, size_t bytes) {
-    if (e == hipSuccess && !(*ptr = exon_pool_alloc(ctx, bytes))) e = hipErrorOutOfMemory;
-  };
-  dalloc(&bufs[0], (size_t)cap * 8);
-  dalloc(&bufs[1], (size_t)cap * 4);
-  dalloc(&bufs[2], (size_t)cap * 4);
-  dalloc(&bufs[3], (size_t)cap * 4);
-  dalloc(&bufs[4], pool.size() + 16);
-  if (e == hipSuccess) e = hipMemcpy(bufs[0], keys.data(), (size_t)cap * 8, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(bufs[1], ids.data(), (size_t)cap * 4, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(bufs[2], toff.data(), (size_t)cap * 4, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(bufs[3], tlen.data(), (size_t)cap * 4, hipMemcpyHostToDevice);
-  if (e == hipSuccess && !pool.empty()) e = hipMemcpy(bufs[4], pool.data(), pool.size(), hipMemcpyHostToDevice);
-  *out = NameTable{(const uint64_t*)bufs[0], (const int32_t*)bufs[1], (const uint32_t*)bufs[2], (const uint32_t*)bufs[3],
-                   (const uint8_t*)bufs[4], cap - 1};
-  return e;
+  uint64_t* d_keys = b.take<uint64_t>((size_t)cap * 8);
+  int32_t* d_ids = b.take<int32_t>((size_t)cap * 4);
+  uint32_t* d_toff = b.take<uint32_t>((size_t)cap * 4);
+  uint32_t* d_tlen = b.take<uint32_t>((size_t)cap * 4);
+  uint8_t* d_pool = b.take<uint8_t>(pool.size() + 16);
+  b.upload(d_keys, keys.data(), (size_t)cap * 8);
+  b.upload(d_ids, ids.data(), (size_t)cap * 4);
+  b.upload(d_toff, toff.data(), (size_t)cap * 4);
+  b.upload(d_tlen, tlen.data(), (size_t)cap * 4);
+  b.upload(d_pool, pool.data(), pool.size());
+  *out = NameTable{d_keys, d_ids, d_toff, d_tlen, d_pool, cap - 1};
+}
+
+// a dictionary the device builds (FILTER lists, the values of a String INFO key): keys 0 (empty), ids -1, counters 0
+static FilterTable take_filter_table(PoolBufs& b) {
+  FilterTable t;
+  t.keys = b.take<unsigned long long>(FILTER_SLOTS * 8, 0);
+  t.ids = b.take<int32_t>(FILTER_SLOTS * 4, 0xFF);
+  t.text_off = b.take<uint32_t>(FILTER_SLOTS * 4);
+  t.text_len = b.take<uint32_t>(FILTER_SLOTS * 4);
+  t.pool = b.take<uint8_t>(FILTER_POOL);
+  t.counters = b.take<int32_t>(16, 0);
+  return t;
 }
 
 // ------------------------------------------------------------------------------------------------------------
@@ -812,28 +753,21 @@ __global__ __launch_bounds__(LIST_TPB) void k_list_fill(const uint8_t* __restric
   if (bad) atomicAdd(exceptions, 1u);
 }
 struct exon_hip_vcf_parser {
-  exon_hip_ctx* ctx = nullptr;
-  int64_t max_bytes = 0, max_rows = 0;
+  exon_hip_ctx* ctx;
+  PoolBufs bufs;
+  int64_t max_rows = 0, cap_items = 0;
   std::string info_field;  // "name[:kind],..." as given; kinds f (default) / b
   InfoKeys ik{};
-  // device state
-  uint8_t* d_info_key = nullptr;
-  unsigned *d_block_counts = nullptr, *d_nl = nullptr, *d_scalars = nullptr;  // scalars: [0] n_lines, [1] exceptions
-  int64_t index_blocks = 0;
-  unsigned index_gen = 0;
+  LineIndex idx;  // scalars: [0] n_lines, [1] exceptions, [2] consumed bytes
   NameTable contigs{};
-  void* contig_bufs[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
   FilterTable filters{};
   ParseOut out{};
-  void* out_bufs[6 + 2 * MAX_INFO] = {nullptr};
-  // list kinds: per key { value offsets per row, item counts per row, Arrow offsets [rows + 1], item flags, item validity bitmap }
-  void* list_bufs[5 * MAX_INFO] = {nullptr};
+  InfoBufs info[MAX_INFO];
   unsigned* d_list_blocks = nullptr;  // per-workgroup sums of the item counts (scanned in place)
-  int64_t cap_items = 0;
-  unsigned* h_scalars = nullptr;  // pinned mirror of d_scalars
-  FilterTable str_tables[MAX_INFO] = {};
+  FilterTable str_tables[MAX_INFO] = {};  // kind 's': the key's value dictionary, built on the device like the FILTER dictionary
   int null_as_value = 0;  // exon_hip_vcf_parser_set_null_key: rows without a value of a String key take the id of the empty text
-  int32_t h_str_stat[MAX_INFO][2] = {{0, 0}};  // per 's' key, last slab: {dictionary overflow, rows without a value}  // kind 's': the key's value dictionary, built on the device like the FILTER dictionary
+  int32_t h_str_stat[MAX_INFO][2] = {{0, 0}};  // per 's' key, last slab: {dictionary overflow, rows without a value}
+  explicit exon_hip_vcf_parser(exon_hip_ctx* c) : ctx(c), bufs(c) {}
 };
 
 extern "C" {
@@ -844,36 +778,15 @@ int exon_hip_vcf_parser_create(exon_hip_ctx* ctx, const char* const* contig_name
     return fail(ctx, EXON_HIP_EINVAL, "exon_hip_vcf_parser_create: bad argument");
   if (max_bytes > 0xF0000000LL) return fail(ctx, EXON_HIP_EINVAL, "slab size must stay below 4 GiB (32-bit line offsets)");
   *outp = nullptr;
-  exon_hip_vcf_parser* p = new (std::nothrow) exon_hip_vcf_parser();
+  exon_hip_vcf_parser* p = new (std::nothrow) exon_hip_vcf_parser(ctx);
   if (!p) return fail(ctx, EXON_HIP_ENOMEM, "out of host memory");
-  p->ctx = ctx;
-  p->max_bytes = max_bytes;
   p->max_rows = max_bytes / 16 + 1;  // a VCF data line has 8 fields: >= 15 bytes + newline
   p->info_field = info_field ? info_field : "";
   hipSetDevice(ctx->device);
-  hipError_t e = hipSuccess;
-  auto dalloc = [&](void** ptr, size_t bytes) {
-    if (e == hipSuccess && !(*ptr = exon_pool_alloc(ctx, bytes))) e = hipErrorOutOfMemory;
-  };
-  // contig table
-  e = build_name_table(ctx, contig_names, n_contigs, p->contig_bufs, &p->contigs);
-  // filter table
-  dalloc((void**)&p->filters.keys, FILTER_SLOTS * 8);
-  dalloc((void**)&p->filters.ids, FILTER_SLOTS * 4);
-  dalloc((void**)&p->filters.text_off, FILTER_SLOTS * 4);
-  dalloc((void**)&p->filters.text_len, FILTER_SLOTS * 4);
-  dalloc((void**)&p->filters.pool, FILTER_POOL);
-  dalloc((void**)&p->filters.counters, 16);
-  if (e == hipSuccess) e = hipMemset(p->filters.keys, 0, FILTER_SLOTS * 8);
-  if (e == hipSuccess) e = hipMemset(p->filters.ids, 0xFF, FILTER_SLOTS * 4);
-  if (e == hipSuccess) e = hipMemset(p->filters.counters, 0, 16);
-  // scratch + outputs
-  const int64_t nblocks = (max_bytes + BYTES_PER_BLOCK - 1) / BYTES_PER_BLOCK;
-  dalloc((void**)&p->d_block_counts, ((size_t)nblocks + 1) * 8);  // the line index's words + its tile counter (zeroed below)
-  p->index_blocks = nblocks;
-  if (e == hipSuccess && p->d_block_counts) e = hipMemset(p->d_block_counts, 0, ((size_t)nblocks + 1) * 8);
-  dalloc((void**)&p->d_nl, (size_t)p->max_rows * 4);
-  dalloc((void**)&p->d_scalars, 16);
+  PoolBufs& b = p->bufs;
+  build_name_table(b, contig_names, n_contigs, &p->contigs);
+  p->filters = take_filter_table(b);
+  p->idx.alloc(b, max_bytes, p->max_rows);
   // INFO keys: "AF,DP:f,DB:b" -> names back to back + (offset, length, kind) per key
   std::string key_text;
   {
@@ -891,7 +804,7 @@ int exon_hip_vcf_parser_create(exon_hip_ctx* ctx, const char* const* contig_name
       }
       if (!item.empty()) {
         if (p->ik.n == MAX_INFO) {
-          exon_hip_vcf_parser_destroy(p);
+          delete p;
           return fail(ctx, EXON_HIP_EUNSUPPORTED, "at most %d INFO fields per parser", MAX_INFO);
         }
         p->ik.off[p->ik.n] = (int)key_text.size();
@@ -903,98 +816,48 @@ int exon_hip_vcf_parser_create(exon_hip_ctx* ctx, const char* const* contig_name
       i = j + 1;
     }
   }
-  dalloc((void**)&p->d_info_key, key_text.size() + 16);
-  if (e == hipSuccess && !key_text.empty()) e = hipMemcpy(p->d_info_key, key_text.data(), key_text.size(), hipMemcpyHostToDevice);
-  p->ik.text = p->d_info_key;
+  uint8_t* d_key_text = b.take<uint8_t>(key_text.size() + 16);
+  b.upload(d_key_text, key_text.data(), key_text.size());
+  p->ik.text = d_key_text;
   const size_t r = (size_t)p->max_rows, rb = r / 8 + 64;
-  dalloc(&p->out_bufs[0], r * 4);
-  dalloc(&p->out_bufs[1], r * 8);
-  dalloc(&p->out_bufs[2], rb);
-  dalloc(&p->out_bufs[3], r * 4);
-  dalloc(&p->out_bufs[4], rb);
-  dalloc(&p->out_bufs[5], r * 4);
+  p->out.chrom_id = b.take<int32_t>(r * 4);
+  p->out.pos = b.take<int64_t>(r * 8);
+  p->out.pos_valid = b.take<uint8_t>(rb);
+  p->out.qual = b.take<float>(r * 4);
+  p->out.qual_valid = b.take<uint8_t>(rb);
+  p->out.filter_id = b.take<int32_t>(r * 4);
   p->cap_items = max_bytes / 2 + 1;  // a non-empty item and its separator take at least two bytes of the slab; a slab of mostly EMPTY
                                      // items (legal: "AF=,,,,") overflows this and is decoded by the host reader (k_list_fill / k_pack_bits clamp)
   for (int q = 0; q < p->ik.n; ++q) {
     const char kind = p->ik.kind[q];
-    if (kind == 'f' || kind == 'i' || kind == 's') dalloc(&p->out_bufs[6 + 2 * q], r * 4);
-    dalloc(&p->out_bufs[7 + 2 * q], rb);
+    InfoBufs& k = p->info[q];
+    if (kind == 'f' || kind == 'i' || kind == 's') k.value = b.take<float>(r * 4);
+    k.valid = b.take<uint8_t>(rb);
     if (kind == 's') {  // Number=1 String / Character: where the value text is (k_parse_lines), then dictionary ids (k_info_string_ids)
-      dalloc(&p->list_bufs[5 * q + 0], r * 4);
-      dalloc(&p->list_bufs[5 * q + 1], r * 4);
-      FilterTable& t = p->str_tables[q];
-      dalloc((void**)&t.keys, FILTER_SLOTS * 8);
-      dalloc((void**)&t.ids, FILTER_SLOTS * 4);
-      dalloc((void**)&t.text_off, FILTER_SLOTS * 4);
-      dalloc((void**)&t.text_len, FILTER_SLOTS * 4);
-      dalloc((void**)&t.pool, FILTER_POOL);
-      dalloc((void**)&t.counters, 16);
-      if (e == hipSuccess) e = hipMemset(t.keys, 0, FILTER_SLOTS * 8);
-      if (e == hipSuccess) e = hipMemset(t.ids, 0xFF, FILTER_SLOTS * 4);
-      if (e == hipSuccess) e = hipMemset(t.counters, 0, 16);
+      k.lv_off = b.take<uint32_t>(r * 4);
+      k.lv_cnt = b.take<uint32_t>(r * 4);
+      p->str_tables[q] = take_filter_table(b);
     }
     if (kind == 'F' || kind == 'I') {
-      dalloc(&p->out_bufs[6 + 2 * q], (size_t)p->cap_items * 4);  // the items
-      dalloc(&p->list_bufs[5 * q + 0], r * 4);
-      dalloc(&p->list_bufs[5 * q + 1], r * 4);
-      dalloc(&p->list_bufs[5 * q + 2], (r + 1) * 4);
-      dalloc(&p->list_bufs[5 * q + 3], (size_t)p->cap_items);
-      dalloc(&p->list_bufs[5 * q + 4], (size_t)p->cap_items / 8 + 64);
-      if (!p->d_list_blocks) dalloc((void**)&p->d_list_blocks, (r / LIST_TPB + 2) * 4);
+      k.take_list(b, r, (size_t)p->cap_items);
+      if (!p->d_list_blocks) p->d_list_blocks = b.take<unsigned>((r / LIST_TPB + 2) * 4);
     }
+    p->out.info[q] = (kind == 'F' || kind == 'I') ? k.items : k.value;
+    p->out.info_valid[q] = static_cast<uint8_t*>(k.valid);
+    p->out.lv_off[q] = k.lv_off;
+    p->out.lv_cnt[q] = k.lv_cnt;
   }
-  if (e == hipSuccess) e = hipHostMalloc((void**)&p->h_scalars, 16);
-  if (e != hipSuccess) {
-    const std::string msg = hipGetErrorString(e);
-    exon_hip_vcf_parser_destroy(p);
+  if (b.status() != hipSuccess) {
+    const std::string msg = hipGetErrorString(b.status());
+    delete p;
     return fail(ctx, EXON_HIP_ENOMEM, "vcf parser allocation: %s", msg.c_str());
   }
-  p->out = ParseOut{};
-  p->out.chrom_id = (int32_t*)p->out_bufs[0];
-  p->out.pos = (int64_t*)p->out_bufs[1];
-  p->out.pos_valid = (uint8_t*)p->out_bufs[2];
-  p->out.qual = (float*)p->out_bufs[3];
-  p->out.qual_valid = (uint8_t*)p->out_bufs[4];
-  p->out.filter_id = (int32_t*)p->out_bufs[5];
-  for (int q = 0; q < p->ik.n; ++q) {
-    p->out.info[q] = (float*)p->out_bufs[6 + 2 * q];
-    p->out.info_valid[q] = (uint8_t*)p->out_bufs[7 + 2 * q];
-    p->out.lv_off[q] = (uint32_t*)p->list_bufs[5 * q + 0];
-    p->out.lv_cnt[q] = (uint32_t*)p->list_bufs[5 * q + 1];
-  }
-  p->out.exceptions = p->d_scalars + 1;
+  p->out.exceptions = p->idx.d_scalars + 1;
   *outp = p;
   return EXON_HIP_OK;
 }
 
 int exon_hip_vcf_parser_destroy(exon_hip_vcf_parser* p) {
-  if (!p) return EXON_HIP_OK;
-  for (void* b : p->contig_bufs)
-    if (b) exon_pool_free(p->ctx, b);
-  for (void* b : p->out_bufs)
-    if (b) exon_pool_free(p->ctx, b);
-  if (p->filters.keys) exon_pool_free(p->ctx, p->filters.keys);
-  if (p->filters.ids) exon_pool_free(p->ctx, p->filters.ids);
-  if (p->filters.text_off) exon_pool_free(p->ctx, p->filters.text_off);
-  if (p->filters.text_len) exon_pool_free(p->ctx, p->filters.text_len);
-  if (p->filters.pool) exon_pool_free(p->ctx, p->filters.pool);
-  if (p->filters.counters) exon_pool_free(p->ctx, p->filters.counters);
-  if (p->d_block_counts) exon_pool_free(p->ctx, p->d_block_counts);
-  if (p->d_nl) exon_pool_free(p->ctx, p->d_nl);
-  if (p->d_scalars) exon_pool_free(p->ctx, p->d_scalars);
-  if (p->d_info_key) exon_pool_free(p->ctx, p->d_info_key);
-  for (FilterTable& t : p->str_tables) {
-    if (t.keys) exon_pool_free(p->ctx, t.keys);
-    if (t.ids) exon_pool_free(p->ctx, t.ids);
-    if (t.text_off) exon_pool_free(p->ctx, t.text_off);
-    if (t.text_len) exon_pool_free(p->ctx, t.text_len);
-    if (t.pool) exon_pool_free(p->ctx, t.pool);
-    if (t.counters) exon_pool_free(p->ctx, t.counters);
-  }
-  for (void* b : p->list_bufs)
-    if (b) exon_pool_free(p->ctx, b);
-  if (p->d_list_blocks) exon_pool_free(p->ctx, p->d_list_blocks);
-  if (p->h_scalars) hipHostFree(p->h_scalars);
   delete p;
   return EXON_HIP_OK;
 }
@@ -1003,56 +866,48 @@ int exon_hip_vcf_parser_parse(exon_hip_vcf_parser* p, void* stream, const uint8_
                               exon_hip_vcf_columns* cols) {
   if (!p || !cols || (n_bytes > 0 && !d_text)) return fail(p ? p->ctx : nullptr, EXON_HIP_EINVAL, "exon_hip_vcf_parser_parse: NULL argument");
   exon_hip_ctx* ctx = p->ctx;
-  if (n_bytes > p->max_bytes) return fail(ctx, EXON_HIP_EINVAL, "slab of %lld bytes exceeds the parser's %lld", (long long)n_bytes, (long long)p->max_bytes);
   memset(cols, 0, sizeof *cols);
   if (n_bytes == 0) return EXON_HIP_OK;
-  // the kernels read aligned 16-byte groups: start at the aligned address at or below d_text and ignore the bytes before it
-  const unsigned skip = (unsigned)(reinterpret_cast<uintptr_t>(d_text) & 15);
-  d_text -= skip;
-  n_bytes += skip;
-  if (n_bytes > p->max_bytes) return fail(ctx, EXON_HIP_EINVAL, "slab of %lld bytes exceeds the parser's %lld", (long long)n_bytes, (long long)p->max_bytes);
+  LineIndex& idx = p->idx;
+  unsigned skip;
+  if (int rc = idx.align(ctx, &d_text, &n_bytes, &skip)) return rc;
   hipStream_t s = pick_stream(ctx, stream);
-  const int nblocks = (int)((n_bytes + BYTES_PER_BLOCK - 1) / BYTES_PER_BLOCK);
-  launch_line_index(s, d_text, n_bytes, skip, p->d_block_counts, p->index_blocks, nblocks, &p->index_gen, p->d_nl, (unsigned)p->max_rows, p->d_scalars);
-  hipLaunchKernelGGL(k_last_newline, dim3(1), dim3(1), 0, s, p->d_nl, p->d_scalars, (unsigned)p->max_rows);
+  idx.launch(s, d_text, n_bytes, skip);
+  hipLaunchKernelGGL(k_last_newline, dim3(1), dim3(1), 0, s, idx.nl, idx.d_scalars, idx.cap);
   // the number of lines is bounded by n_bytes / 16 + 1 for well-formed data lines; launch for that bound
   const int64_t row_bound = std::min<int64_t>(p->max_rows, n_bytes / 16 + 1);
   const int pblocks = (int)((row_bound + TPB - 1) / TPB);
-  hipLaunchKernelGGL(k_parse_lines, dim3(pblocks), dim3(TPB), 0, s, d_text, p->d_nl, p->d_scalars, p->contigs, p->filters,
+  hipLaunchKernelGGL(k_parse_lines, dim3(pblocks), dim3(TPB), 0, s, d_text, idx.nl, idx.d_scalars, p->contigs, p->filters,
                      p->ik, p->out, (unsigned)row_bound, skip, (unsigned)n_bytes);
   hipLaunchKernelGGL(k_assign_filters, dim3(1), dim3(256), 0, s, d_text, p->filters);
-  hipLaunchKernelGGL(k_remap_filters, dim3(std::min(pblocks, 4096)), dim3(TPB), 0, s, p->out.filter_id, p->d_scalars, p->filters.ids, (unsigned)row_bound);
+  hipLaunchKernelGGL(k_remap_filters, dim3(std::min(pblocks, 4096)), dim3(TPB), 0, s, p->out.filter_id, idx.d_scalars, p->filters.ids, (unsigned)row_bound);
+  const int lblocks = (int)((row_bound + LIST_TPB - 1) / LIST_TPB);
+  const unsigned cap_items = (unsigned)std::min<int64_t>(p->cap_items, 0xFFFFFFFFLL);
   for (int q = 0; q < p->ik.n; ++q) {  // list-valued fields: counts -> offsets -> items -> child validity
     const char kind = p->ik.kind[q];
     if (kind != 'F' && kind != 'I') continue;
-    const int lblocks = (int)((row_bound + LIST_TPB - 1) / LIST_TPB);
-    int32_t* offsets = (int32_t*)p->list_bufs[5 * q + 2];
-    hipLaunchKernelGGL(k_list_block_sums, dim3(lblocks), dim3(LIST_TPB), 0, s, p->out.lv_cnt[q], p->d_scalars, (unsigned)row_bound, p->d_list_blocks);
-    hipLaunchKernelGGL(k_list_scan_blocks, dim3(1), dim3(256), 0, s, p->d_list_blocks, lblocks, p->d_scalars + 3);
-    hipLaunchKernelGGL(k_list_fill, dim3(lblocks), dim3(LIST_TPB), 0, s, d_text, (unsigned)n_bytes, p->out.lv_off[q], p->out.lv_cnt[q], p->d_list_blocks,
-                       p->d_scalars, (unsigned)row_bound, (unsigned)std::min<int64_t>(p->cap_items, 0xFFFFFFFFLL), kind, offsets, p->out.info[q],
-                       (uint8_t*)p->list_bufs[5 * q + 3], p->out.exceptions);
-    hipLaunchKernelGGL(k_pack_bits, dim3(1024), dim3(256), 0, s, (const uint8_t*)p->list_bufs[5 * q + 3], offsets, p->d_scalars, (unsigned)row_bound,
-                       (unsigned)std::min<int64_t>(p->cap_items, 0xFFFFFFFFLL), (uint8_t*)p->list_bufs[5 * q + 4]);
+    const InfoBufs& k = p->info[q];
+    launch_list_scan(s, k.lv_cnt, idx.d_scalars, (unsigned)row_bound, lblocks, p->d_list_blocks, idx.d_scalars + 3);
+    hipLaunchKernelGGL(k_list_fill, dim3(lblocks), dim3(LIST_TPB), 0, s, d_text, (unsigned)n_bytes, k.lv_off, k.lv_cnt, p->d_list_blocks,
+                       idx.d_scalars, (unsigned)row_bound, cap_items, kind, k.offsets, k.items, k.item_flags, p->out.exceptions);
+    k.pack_bits(s, idx.d_scalars, (unsigned)row_bound, cap_items);
   }
   for (int q = 0; q < p->ik.n; ++q) {  // String / Character keys: value text -> dictionary ids
     if (p->ik.kind[q] != 's') continue;
     FilterTable& t = p->str_tables[q];
     HIP_TRY(ctx, hipMemsetAsync(t.counters + 3, 0, 4, s));
-    hipLaunchKernelGGL(k_info_string_ids, dim3(pblocks), dim3(TPB), 0, s, d_text, p->out.lv_off[q], p->out.lv_cnt[q], p->out.info_valid[q], p->d_scalars, (unsigned)row_bound, t,
+    hipLaunchKernelGGL(k_info_string_ids, dim3(pblocks), dim3(TPB), 0, s, d_text, p->out.lv_off[q], p->out.lv_cnt[q], p->out.info_valid[q], idx.d_scalars, (unsigned)row_bound, t,
                        (int32_t*)p->out.info[q], p->null_as_value);
     hipLaunchKernelGGL(k_assign_filters, dim3(1), dim3(256), 0, s, d_text, t);
-    hipLaunchKernelGGL(k_remap_filters, dim3(std::min(pblocks, 4096)), dim3(TPB), 0, s, (int32_t*)p->out.info[q], p->d_scalars, t.ids, (unsigned)row_bound);
+    hipLaunchKernelGGL(k_remap_filters, dim3(std::min(pblocks, 4096)), dim3(TPB), 0, s, (int32_t*)p->out.info[q], idx.d_scalars, t.ids, (unsigned)row_bound);
     HIP_TRY(ctx, hipMemcpyAsync(p->h_str_stat[q], t.counters + 2, 8, hipMemcpyDeviceToHost, s));  // {overflow, rows without a value}
   }
-  HIP_TRY(ctx, hipGetLastError());
-  HIP_TRY(ctx, hipMemcpyAsync(p->h_scalars, p->d_scalars, 12, hipMemcpyDeviceToHost, s));
-  HIP_TRY(ctx, hipStreamSynchronize(s));
-  const int64_t n_lines = p->h_scalars[0];
+  if (int rc = idx.read_back(ctx, s)) return rc;
+  const int64_t n_lines = idx.h_scalars[0];
   if (n_lines > row_bound) return fail(ctx, EXON_HIP_EINVAL, "slab has %lld lines, more than its byte size allows for VCF records", (long long)n_lines);
   cols->n_rows = n_lines;
-  cols->n_undecided = p->h_scalars[1];
-  cols->consumed_bytes = p->h_scalars[2] > skip ? (int64_t)p->h_scalars[2] - skip : 0;
+  cols->n_undecided = idx.h_scalars[1];
+  cols->consumed_bytes = idx.consumed(skip);
   cols->chrom_id = p->out.chrom_id;
   cols->pos = p->out.pos;
   cols->pos_valid = p->out.pos_valid;
@@ -1069,15 +924,15 @@ int exon_hip_vcf_parser_parse(exon_hip_vcf_parser* p, void* stream, const uint8_
     cols->info_nulls[q] = p->ik.kind[q] == 's' ? p->h_str_stat[q][1] : -1;
     if (p->ik.kind[q] == 's' && p->h_str_stat[q][0]) ++cols->n_undecided;  // more distinct values than the dictionary holds: the host reader's
     if (p->ik.kind[q] == 'F' || p->ik.kind[q] == 'I') {
-      cols->list_offsets[q] = (int32_t*)p->list_bufs[5 * q + 2];
-      cols->list_item_valid[q] = (uint8_t*)p->list_bufs[5 * q + 4];
+      cols->list_offsets[q] = p->info[q].offsets;
+      cols->list_item_valid[q] = p->info[q].item_bits;
     }
   }
   return EXON_HIP_OK;
 }
 
 }  // extern "C"
-const unsigned* exon_hip_vcf_parser_newlines(exon_hip_vcf_parser* p) { return p ? p->d_nl : nullptr; }
+const unsigned* exon_hip_vcf_parser_newlines(exon_hip_vcf_parser* p) { return p ? p->idx.nl : nullptr; }
 extern "C" {
 
 // a device-built dictionary (FILTER lists, or the values of a String INFO key) in id order: names '\0'-separated into `buf`
@@ -1176,13 +1031,12 @@ __global__ __launch_bounds__(TPB) void k_fastq_views(const uint8_t* __restrict__
 }  // namespace
 
 struct exon_hip_fastq_parser {
-  exon_hip_ctx* ctx = nullptr;
-  int64_t max_bytes = 0, max_lines = 0;
-  unsigned *d_block_counts = nullptr, *d_nl = nullptr, *d_scalars = nullptr;
-  int64_t index_blocks = 0;
-  unsigned index_gen = 0;
+  exon_hip_ctx* ctx;
+  PoolBufs bufs;
+  LineIndex idx;
   int32_t* d_views = nullptr;  // 6 arrays of max_lines / 4 + 1
-  unsigned* h_scalars = nullptr;
+  size_t per = 0;              // ... that long
+  explicit exon_hip_fastq_parser(exon_hip_ctx* c) : ctx(c), bufs(c) {}
 };
 
 extern "C" {
@@ -1191,28 +1045,16 @@ int exon_hip_fastq_parser_create(exon_hip_ctx* ctx, int64_t max_bytes, exon_hip_
   if (!ctx || !outp || max_bytes < 16) return fail(ctx, EXON_HIP_EINVAL, "exon_hip_fastq_parser_create: bad argument");
   if (max_bytes > 0x7FFF0000LL) return fail(ctx, EXON_HIP_EINVAL, "slab size must stay below 2 GiB (32-bit views)");
   *outp = nullptr;
-  exon_hip_fastq_parser* p = new (std::nothrow) exon_hip_fastq_parser();
+  exon_hip_fastq_parser* p = new (std::nothrow) exon_hip_fastq_parser(ctx);
   if (!p) return fail(ctx, EXON_HIP_ENOMEM, "out of host memory");
-  p->ctx = ctx;
-  p->max_bytes = max_bytes;
-  p->max_lines = max_bytes / 4 + 8;  // records of >= 16 bytes; denser text is handed back to the host decoder
+  const int64_t max_lines = max_bytes / 4 + 8;  // records of >= 16 bytes; denser text is handed back to the host decoder
   hipSetDevice(ctx->device);
-  const int64_t nblocks = (max_bytes + BYTES_PER_BLOCK - 1) / BYTES_PER_BLOCK;
-  const size_t per = (size_t)(p->max_lines / 4 + 1);
-  hipError_t e = hipSuccess;
-  auto dalloc = [&](void** ptr, size_t bytes) {
-    if (e == hipSuccess && !(*ptr = exon_pool_alloc(ctx, bytes))) e = hipErrorOutOfMemory;
-  };
-  dalloc((void**)&p->d_block_counts, ((size_t)nblocks + 1) * 8);  // the line index's words + its tile counter (zeroed below)
-  p->index_blocks = nblocks;
-  if (e == hipSuccess && p->d_block_counts) e = hipMemset(p->d_block_counts, 0, ((size_t)nblocks + 1) * 8);
-  dalloc((void**)&p->d_nl, (size_t)p->max_lines * 4);
-  dalloc((void**)&p->d_scalars, 16);
-  dalloc((void**)&p->d_views, per * 6 * 4);
-  if (e == hipSuccess) e = hipHostMalloc((void**)&p->h_scalars, 16);
-  if (e != hipSuccess) {
-    const std::string msg = hipGetErrorString(e);
-    exon_hip_fastq_parser_destroy(p);
+  p->idx.alloc(p->bufs, max_bytes, max_lines);
+  p->per = (size_t)(max_lines / 4 + 1);
+  p->d_views = p->bufs.take<int32_t>(p->per * 6 * 4);
+  if (p->bufs.status() != hipSuccess) {
+    const std::string msg = hipGetErrorString(p->bufs.status());
+    delete p;
     return fail(ctx, EXON_HIP_ENOMEM, "fastq parser allocation: %s", msg.c_str());
   }
   *outp = p;
@@ -1220,12 +1062,6 @@ int exon_hip_fastq_parser_create(exon_hip_ctx* ctx, int64_t max_bytes, exon_hip_
 }
 
 int exon_hip_fastq_parser_destroy(exon_hip_fastq_parser* p) {
-  if (!p) return EXON_HIP_OK;
-  if (p->d_block_counts) exon_pool_free(p->ctx, p->d_block_counts);
-  if (p->d_nl) exon_pool_free(p->ctx, p->d_nl);
-  if (p->d_scalars) exon_pool_free(p->ctx, p->d_scalars);
-  if (p->d_views) exon_pool_free(p->ctx, p->d_views);
-  if (p->h_scalars) hipHostFree(p->h_scalars);
   delete p;
   return EXON_HIP_OK;
 }
@@ -1234,28 +1070,22 @@ int exon_hip_fastq_parser_parse(exon_hip_fastq_parser* p, void* stream, const ui
                                 int32_t final_slab, exon_hip_fastq_views* views) {
   if (!p || !views || (n_bytes > 0 && !d_text)) return fail(p ? p->ctx : nullptr, EXON_HIP_EINVAL, "exon_hip_fastq_parser_parse: NULL argument");
   exon_hip_ctx* ctx = p->ctx;
-  if (n_bytes > p->max_bytes) return fail(ctx, EXON_HIP_EINVAL, "slab of %lld bytes exceeds the parser's %lld", (long long)n_bytes, (long long)p->max_bytes);
   memset(views, 0, sizeof *views);
   if (n_bytes == 0) return EXON_HIP_OK;
-  // the kernels read aligned 16-byte groups: start at the aligned address at or below d_text and ignore the bytes before it
-  const unsigned skip = (unsigned)(reinterpret_cast<uintptr_t>(d_text) & 15);
-  d_text -= skip;
-  n_bytes += skip;
-  if (n_bytes > p->max_bytes) return fail(ctx, EXON_HIP_EINVAL, "slab of %lld bytes exceeds the parser's %lld", (long long)n_bytes, (long long)p->max_bytes);
+  LineIndex& idx = p->idx;
+  unsigned skip;
+  if (int rc = idx.align(ctx, &d_text, &n_bytes, &skip)) return rc;
   hipStream_t s = pick_stream(ctx, stream);
-  const int nblocks = (int)((n_bytes + BYTES_PER_BLOCK - 1) / BYTES_PER_BLOCK);
-  const size_t per = (size_t)(p->max_lines / 4 + 1);
+  const size_t per = p->per;
   int32_t* v = p->d_views;
-  launch_line_index(s, d_text, n_bytes, skip, p->d_block_counts, p->index_blocks, nblocks, &p->index_gen, p->d_nl, (unsigned)p->max_lines, p->d_scalars);
+  idx.launch(s, d_text, n_bytes, skip);
   const int64_t read_bound = std::min<int64_t>((int64_t)per, n_bytes / 4 + 1);  // a record holds 4 newlines
-  hipLaunchKernelGGL(k_fastq_views, dim3((unsigned)((read_bound + TPB - 1) / TPB)), dim3(TPB), 0, s, d_text, p->d_nl, p->d_scalars,
-                     (unsigned)p->max_lines, (int)final_slab, v, v + per, v + 2 * per, v + 3 * per, v + 4 * per, v + 5 * per, skip);
-  HIP_TRY(ctx, hipGetLastError());
-  HIP_TRY(ctx, hipMemcpyAsync(p->h_scalars, p->d_scalars, 16, hipMemcpyDeviceToHost, s));
-  HIP_TRY(ctx, hipStreamSynchronize(s));
-  views->n_undecided = p->h_scalars[1];
-  views->n_reads = p->h_scalars[0] > (unsigned)p->max_lines ? 0 : p->h_scalars[0] / 4;
-  views->consumed_bytes = p->h_scalars[2] > skip ? (int64_t)p->h_scalars[2] - skip : 0;
+  hipLaunchKernelGGL(k_fastq_views, dim3((unsigned)((read_bound + TPB - 1) / TPB)), dim3(TPB), 0, s, d_text, idx.nl, idx.d_scalars,
+                     idx.cap, (int)final_slab, v, v + per, v + 2 * per, v + 3 * per, v + 4 * per, v + 5 * per, skip);
+  if (int rc = idx.read_back(ctx, s)) return rc;
+  views->n_undecided = idx.h_scalars[1];
+  views->n_reads = idx.h_scalars[0] > idx.cap ? 0 : idx.h_scalars[0] / 4;
+  views->consumed_bytes = idx.consumed(skip);
   views->text_base = d_text;
   views->seq_start = v;
   views->seq_end = v + per;
@@ -1378,18 +1208,15 @@ __global__ __launch_bounds__(TPB) void k_parse_sam_lines(const uint8_t* __restri
 }  // namespace
 
 struct exon_hip_sam_parser {
-  exon_hip_ctx* ctx = nullptr;
-  int64_t max_bytes = 0, max_rows = 0;
-  unsigned *d_block_counts = nullptr, *d_nl = nullptr, *d_scalars = nullptr;
-  int64_t index_blocks = 0;
-  unsigned index_gen = 0;
+  exon_hip_ctx* ctx;
+  PoolBufs bufs;
+  int64_t max_rows = 0;
+  LineIndex idx;
   NameTable refs{};
-  void* ref_bufs[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-  void* bufs[8] = {nullptr};
   SamOut out{};
-  unsigned* h_scalars = nullptr;
+  explicit exon_hip_sam_parser(exon_hip_ctx* c) : ctx(c), bufs(c) {}
 };
-const unsigned* exon_hip_sam_parser_newlines(exon_hip_sam_parser* p) { return p ? p->d_nl : nullptr; }
+const unsigned* exon_hip_sam_parser_newlines(exon_hip_sam_parser* p) { return p ? p->idx.nl : nullptr; }
 
 extern "C" {
 
@@ -1398,51 +1225,32 @@ int exon_hip_sam_parser_create(exon_hip_ctx* ctx, const char* const* ref_names, 
   if (!ctx || !outp || (n_refs > 0 && !ref_names) || max_bytes < 16) return fail(ctx, EXON_HIP_EINVAL, "exon_hip_sam_parser_create: bad argument");
   if (max_bytes > 0xF0000000LL) return fail(ctx, EXON_HIP_EINVAL, "slab size must stay below 4 GiB (32-bit line offsets)");
   *outp = nullptr;
-  exon_hip_sam_parser* p = new (std::nothrow) exon_hip_sam_parser();
+  exon_hip_sam_parser* p = new (std::nothrow) exon_hip_sam_parser(ctx);
   if (!p) return fail(ctx, EXON_HIP_ENOMEM, "out of host memory");
-  p->ctx = ctx;
-  p->max_bytes = max_bytes;
   p->max_rows = max_bytes / 12 + 1;  // 11 fields: >= 21 bytes + newline; be generous
   hipSetDevice(ctx->device);
-  hipError_t e = build_name_table(ctx, ref_names, n_refs, p->ref_bufs, &p->refs);
-  auto dalloc = [&](void** ptr, size_t bytes) {
-    if (e == hipSuccess && !(*ptr = exon_pool_alloc(ctx, bytes))) e = hipErrorOutOfMemory;
-  };
-  const int64_t nblocks = (max_bytes + BYTES_PER_BLOCK - 1) / BYTES_PER_BLOCK;
+  PoolBufs& b = p->bufs;
+  build_name_table(b, ref_names, n_refs, &p->refs);
+  p->idx.alloc(b, max_bytes, p->max_rows);
   const size_t r = (size_t)p->max_rows, rb = r / 8 + 64;
-  dalloc((void**)&p->d_block_counts, ((size_t)nblocks + 1) * 8);  // the line index's words + its tile counter (zeroed below)
-  p->index_blocks = nblocks;
-  if (e == hipSuccess && p->d_block_counts) e = hipMemset(p->d_block_counts, 0, ((size_t)nblocks + 1) * 8);
-  dalloc((void**)&p->d_nl, r * 4);
-  dalloc((void**)&p->d_scalars, 16);
-  dalloc(&p->bufs[0], r * 4);
-  dalloc(&p->bufs[1], r + 64);
-  dalloc(&p->bufs[2], rb);
-  dalloc(&p->bufs[3], r * 4);
-  dalloc(&p->bufs[4], rb);
-  dalloc(&p->bufs[5], r * 8);
-  dalloc(&p->bufs[6], r * 8);
-  dalloc(&p->bufs[7], rb);
-  if (e == hipSuccess) e = hipHostMalloc((void**)&p->h_scalars, 16);
-  if (e != hipSuccess) {
-    const std::string msg = hipGetErrorString(e);
-    exon_hip_sam_parser_destroy(p);
+  p->out.flag = b.take<int32_t>(r * 4);
+  p->out.mapq = b.take<uint8_t>(r + 64);
+  p->out.mapq_valid = b.take<uint8_t>(rb);
+  p->out.ref_id = b.take<int32_t>(r * 4);
+  p->out.ref_valid = b.take<uint8_t>(rb);
+  p->out.start = b.take<int64_t>(r * 8);
+  p->out.end = b.take<int64_t>(r * 8);
+  p->out.pos_valid = b.take<uint8_t>(rb);
+  if (b.status() != hipSuccess) {
+    const std::string msg = hipGetErrorString(b.status());
+    delete p;
     return fail(ctx, EXON_HIP_ENOMEM, "sam parser allocation: %s", msg.c_str());
   }
-  p->out = SamOut{(int32_t*)p->bufs[0], (uint8_t*)p->bufs[1], (uint8_t*)p->bufs[2], (int32_t*)p->bufs[3],
-                  (uint8_t*)p->bufs[4], (int64_t*)p->bufs[5], (int64_t*)p->bufs[6], (uint8_t*)p->bufs[7]};
   *outp = p;
   return EXON_HIP_OK;
 }
 
 int exon_hip_sam_parser_destroy(exon_hip_sam_parser* p) {
-  if (!p) return EXON_HIP_OK;
-  for (void* b : p->ref_bufs) exon_pool_free(p->ctx, b);
-  for (void* b : p->bufs) exon_pool_free(p->ctx, b);
-  exon_pool_free(p->ctx, p->d_block_counts);
-  exon_pool_free(p->ctx, p->d_nl);
-  exon_pool_free(p->ctx, p->d_scalars);
-  if (p->h_scalars) hipHostFree(p->h_scalars);
   delete p;
   return EXON_HIP_OK;
 }
@@ -1452,24 +1260,20 @@ int exon_hip_sam_parser_parse(exon_hip_sam_parser* p, void* stream, const uint8_
   exon_hip_ctx* ctx = p->ctx;
   memset(cols, 0, sizeof *cols);
   if (n_bytes == 0) return EXON_HIP_OK;
-  const unsigned skip = (unsigned)(reinterpret_cast<uintptr_t>(d_text) & 15);
-  d_text -= skip;
-  n_bytes += skip;
-  if (n_bytes > p->max_bytes) return fail(ctx, EXON_HIP_EINVAL, "slab of %lld bytes exceeds the parser's %lld", (long long)n_bytes, (long long)p->max_bytes);
+  LineIndex& idx = p->idx;
+  unsigned skip;
+  if (int rc = idx.align(ctx, &d_text, &n_bytes, &skip)) return rc;
   hipStream_t s = pick_stream(ctx, stream);
-  const int nblocks = (int)((n_bytes + BYTES_PER_BLOCK - 1) / BYTES_PER_BLOCK);
-  launch_line_index(s, d_text, n_bytes, skip, p->d_block_counts, p->index_blocks, nblocks, &p->index_gen, p->d_nl, (unsigned)p->max_rows, p->d_scalars);
-  hipLaunchKernelGGL(k_last_newline, dim3(1), dim3(1), 0, s, p->d_nl, p->d_scalars, (unsigned)p->max_rows);
+  idx.launch(s, d_text, n_bytes, skip);
+  hipLaunchKernelGGL(k_last_newline, dim3(1), dim3(1), 0, s, idx.nl, idx.d_scalars, idx.cap);
   const int64_t row_bound = std::min<int64_t>(p->max_rows, n_bytes / 12 + 1);
   const int pblocks = (int)((row_bound + TPB - 1) / TPB);
-  hipLaunchKernelGGL(k_parse_sam_lines, dim3(pblocks), dim3(TPB), 0, s, d_text, p->d_nl, p->d_scalars, p->refs, p->out, (unsigned)row_bound, skip);
-  HIP_TRY(ctx, hipGetLastError());
-  HIP_TRY(ctx, hipMemcpyAsync(p->h_scalars, p->d_scalars, 12, hipMemcpyDeviceToHost, s));
-  HIP_TRY(ctx, hipStreamSynchronize(s));
-  const int64_t n_lines = p->h_scalars[0];
+  hipLaunchKernelGGL(k_parse_sam_lines, dim3(pblocks), dim3(TPB), 0, s, d_text, idx.nl, idx.d_scalars, p->refs, p->out, (unsigned)row_bound, skip);
+  if (int rc = idx.read_back(ctx, s)) return rc;
+  const int64_t n_lines = idx.h_scalars[0];
   cols->n_rows = n_lines;
-  cols->n_undecided = p->h_scalars[1] + (n_lines > row_bound ? 1 : 0);
-  cols->consumed_bytes = p->h_scalars[2] > skip ? (int64_t)p->h_scalars[2] - skip : 0;
+  cols->n_undecided = idx.h_scalars[1] + (n_lines > row_bound ? 1 : 0);
+  cols->consumed_bytes = idx.consumed(skip);
   cols->flag = p->out.flag;
   cols->mapq = p->out.mapq;
   cols->mapq_valid = p->out.mapq_valid;

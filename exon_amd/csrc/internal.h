@@ -5,6 +5,7 @@
 #include <map>
 #include <mutex>
 #include <string>
+#include <vector>
 
 #include "../../include/exon_hip.h"
 #include "kernels.h"
@@ -106,6 +107,52 @@ const uint32_t* exon_hip_bcf_parser_row_records(exon_hip_bcf_parser* p);   // bc
 // capi.cpp: size-keyed recycling of device buffers (released by exon_hip_ctx_destroy)
 void* exon_pool_alloc(exon_hip_ctx* ctx, size_t bytes);
 void exon_pool_free(exon_hip_ctx* ctx, void* p);
+
+// The device buffers of one parser (or scratch) out of the ctx's pool, plus pinned host mirrors: each is freed exactly once, by
+// release() or the destructor.  Failures are sticky: after the first one every take returns nullptr and status() keeps it.
+class PoolBufs {
+ public:
+  explicit PoolBufs(exon_hip_ctx* ctx) : ctx_(ctx) {}
+  ~PoolBufs() { release(); }
+  PoolBufs(const PoolBufs&) = delete;
+  PoolBufs& operator=(const PoolBufs&) = delete;
+  // `bytes` of device memory; fill >= 0: every byte set to it
+  template <class T>
+  T* take(size_t bytes, int fill = -1) {
+    if (err_ != hipSuccess) return nullptr;
+    void* p = exon_pool_alloc(ctx_, bytes);
+    if (!p) {
+      err_ = hipErrorOutOfMemory;
+      return nullptr;
+    }
+    dev_.push_back(p);
+    if (fill >= 0 && (err_ = hipMemset(p, fill, bytes)) != hipSuccess) return nullptr;
+    return static_cast<T*>(p);
+  }
+  template <class T>
+  T* pinned(size_t bytes) {
+    void* p = nullptr;
+    if (err_ != hipSuccess || (err_ = hipHostMalloc(&p, bytes)) != hipSuccess) return nullptr;
+    host_.push_back(p);
+    return static_cast<T*>(p);
+  }
+  void upload(void* dst, const void* src, size_t bytes) {
+    if (err_ == hipSuccess && bytes) err_ = hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice);
+  }
+  hipError_t status() const { return err_; }
+  void release() {
+    for (void* p : dev_) exon_pool_free(ctx_, p);
+    for (void* p : host_) hipHostFree(p);
+    dev_.clear();
+    host_.clear();
+    err_ = hipSuccess;
+  }
+
+ private:
+  exon_hip_ctx* ctx_;
+  std::vector<void*> dev_, host_;
+  hipError_t err_ = hipSuccess;
+};
 
 // internal launch flags next to the public EXON_HIP_LAUNCH_* bits: K4's compared column / AVG argument is Int32
 // (exon_hip_plan_desc.x_type / y_type)

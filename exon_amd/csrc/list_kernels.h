@@ -1,19 +1,24 @@
-// list_kernels.h -- shared by the VCF text parser (gpu_parse.hip) and the BCF parser (bcf_parse.hip): the bookkeeping of
-// list-valued INFO fields in the Arrow List layout.  A format's extract kernel leaves, per row, the number of items (0 for a
-// NULL list) and where they are; here the counts become int32 offsets (block sums -> scan -> the format's fill kernel adds
-// the in-block prefix) and the per-item flags become the child validity bitmap.
+// list_kernels.h -- the exclusive scan of per-row counts into Arrow int32 offsets, shared by the VCF text parser (gpu_parse.hip),
+// the BCF parser (bcf_parse.hip) and the string columns (text_columns.hip): per-workgroup sums (k_list_block_sums) -> one
+// workgroup scans them in place (k_list_scan_blocks) -> the consumer's own kernel adds the in-block prefix (list_first_item).
+// For list-valued INFO fields the extract kernel leaves, per row, the number of items (0 for a NULL list) and where they are,
+// the format's fill kernel parses the items, and k_pack_bits turns the per-item flags into the child validity bitmap; InfoBufs
+// holds one INFO key's device buffers in both parsers.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "internal.h"
+
 namespace {  // one copy per translation unit
 
 constexpr int LIST_TPB = 256;
-// per-workgroup sums of cnt[0 .. n_rows) (n_rows read from the device: the line count of this slab)
+// per-workgroup sums of cnt[0 .. n_rows): n_rows = min(*n_rows_p, cap) read from the device (the row count of this slab), or
+// n_rows = cap when n_rows_p is null (the count is known on the host)
 __global__ __launch_bounds__(LIST_TPB) void k_list_block_sums(const uint32_t* __restrict__ cnt, const unsigned* __restrict__ n_rows_p,
                                                               unsigned cap, unsigned* __restrict__ block_sums) {
   __shared__ unsigned red[LIST_TPB / 64];
-  const unsigned n_rows = min(*n_rows_p, cap);
+  const unsigned n_rows = n_rows_p ? min(*n_rows_p, cap) : cap;
   const unsigned row = blockIdx.x * LIST_TPB + threadIdx.x;
   unsigned c = row < n_rows ? cnt[row] : 0u;
   for (int o = 32; o > 0; o >>= 1) c += __shfl_down(c, o, 64);
@@ -74,5 +79,36 @@ __global__ __launch_bounds__(256) void k_pack_bits(const uint8_t* __restrict__ f
     bitmap[b] = (uint8_t)v;
   }
 }
+
+// counts -> scanned block sums (`nb` workgroups of LIST_TPB rows; the total -> *total): the first two launches of every offsets scan
+inline void launch_list_scan(hipStream_t s, const uint32_t* cnt, const unsigned* n_rows_p, unsigned cap, int nb, unsigned* block_sums,
+                             unsigned* total) {
+  hipLaunchKernelGGL(k_list_block_sums, dim3(nb), dim3(LIST_TPB), 0, s, cnt, n_rows_p, cap, block_sums);
+  hipLaunchKernelGGL(k_list_scan_blocks, dim3(1), dim3(256), 0, s, block_sums, nb, total);
+}
+
+// One INFO key's device buffers.  Number=1 kinds: the 4-byte column `value` and its validity bitmap `valid` (VCF: bytes, BCF: 32-bit
+// words).  List kinds ('F' / 'I'): per row where the value is and how many items it has (VCF 's' keys: the value text), the Arrow
+// offsets [rows + 1], the per-item flags, the child validity bitmap and the items.
+struct InfoBufs {
+  float* value = nullptr;
+  void* valid = nullptr;
+  uint32_t *lv_off = nullptr, *lv_cnt = nullptr;
+  int32_t* offsets = nullptr;
+  uint8_t *item_flags = nullptr, *item_bits = nullptr;
+  float* items = nullptr;
+  void take_list(PoolBufs& b, size_t rows, size_t cap_items) {
+    lv_off = b.take<uint32_t>(rows * 4);
+    lv_cnt = b.take<uint32_t>(rows * 4);
+    offsets = b.take<int32_t>((rows + 1) * 4);
+    item_flags = b.take<uint8_t>(cap_items);
+    item_bits = b.take<uint8_t>(cap_items / 8 + 64);
+    items = b.take<float>(cap_items * 4);
+  }
+  // the per-item flags -> the child validity bitmap, behind the format's fill kernel
+  void pack_bits(hipStream_t s, const unsigned* n_rows_p, unsigned cap, unsigned cap_items) const {
+    hipLaunchKernelGGL(k_pack_bits, dim3(1024), dim3(256), 0, s, item_flags, offsets, n_rows_p, cap, cap_items, item_bits);
+  }
+};
 
 }  // namespace

@@ -21,59 +21,20 @@
 #include <new>
 
 #include "internal.h"
+#include "list_kernels.h"
 
 namespace {
 
 constexpr int TPB = 256;
 
-// ---- exclusive scan of n u32 lengths into n + 1 int32 offsets (three launches; n is known on the host) ------------------------------
-__global__ __launch_bounds__(TPB) void k_block_sums(const uint32_t* __restrict__ len, unsigned n, unsigned* __restrict__ sums) {
-  __shared__ unsigned red[TPB / 64];
-  const unsigned i = blockIdx.x * TPB + threadIdx.x;
-  unsigned c = i < n ? len[i] : 0u;
-  for (int o = 32; o > 0; o >>= 1) c += __shfl_down(c, o, 64);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = c;
-  __syncthreads();
-  if (threadIdx.x == 0) sums[blockIdx.x] = red[0] + red[1] + red[2] + red[3];
-}
-__global__ __launch_bounds__(256) void k_scan_sums(unsigned* __restrict__ sums, int nb, unsigned* __restrict__ total) {
-  __shared__ unsigned part[256];
-  const int per = (nb + 255) / 256;
-  const int b0 = threadIdx.x * per, b1 = min(nb, b0 + per);
-  unsigned s = 0;
-  for (int b = b0; b < b1; ++b) s += sums[b];
-  part[threadIdx.x] = s;
-  __syncthreads();
-  for (int o = 1; o < 256; o <<= 1) {
-    const unsigned v = threadIdx.x >= (unsigned)o ? part[threadIdx.x - o] : 0u;
-    __syncthreads();
-    part[threadIdx.x] += v;
-    __syncthreads();
-  }
-  unsigned run = threadIdx.x ? part[threadIdx.x - 1] : 0u;
-  for (int b = b0; b < b1; ++b) {
-    const unsigned c = sums[b];
-    sums[b] = run;
-    run += c;
-  }
-  if (threadIdx.x == 255) *total = part[255];
-}
-__global__ __launch_bounds__(TPB) void k_write_offsets(const uint32_t* __restrict__ len, unsigned n, const unsigned* __restrict__ sums, int32_t* __restrict__ offsets) {
-  __shared__ unsigned wave_tot[TPB / 64];
-  const unsigned i = blockIdx.x * TPB + threadIdx.x;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+// ---- exclusive scan of n u32 lengths into n + 1 int32 offsets: list_kernels.h's block sums and scan (n is known on the host), then
+// the in-block prefix
+__global__ __launch_bounds__(LIST_TPB) void k_write_offsets(const uint32_t* __restrict__ len, unsigned n, const unsigned* __restrict__ sums, int32_t* __restrict__ offsets) {
+  const unsigned i = blockIdx.x * LIST_TPB + threadIdx.x;
   const unsigned c = i < n ? len[i] : 0u;
-  unsigned incl = c;
-  for (int o = 1; o < 64; o <<= 1) {
-    const unsigned t = __shfl_up(incl, o, 64);
-    if (lane >= o) incl += t;
-  }
-  if (lane == 63) wave_tot[wave] = incl;
-  __syncthreads();
-  unsigned base = sums[blockIdx.x];
-  for (int w = 0; w < wave; ++w) base += wave_tot[w];
-  if (i < n) offsets[i] = (int32_t)(base + incl - c);
-  if (i == n - 1) offsets[n] = (int32_t)(base + incl);
+  const unsigned first = list_first_item(c, sums);
+  if (i < n) offsets[i] = (int32_t)first;
+  if (i == n - 1) offsets[n] = (int32_t)(first + c);
 }
 
 // ---- VCF ---------------------------------------------------------------------------------------------------------------------------
@@ -493,7 +454,7 @@ __global__ __launch_bounds__(TPB) void k_bcf_fill(const uint8_t* __restrict__ d,
 }
 
 struct ExonTextScratch {
-  exon_hip_ctx* ctx = nullptr;
+  PoolBufs bufs, qual_bufs;  // qual_bufs: the quality_scores values, grown on demand
   int64_t max_rows = 0, max_bytes = 0;
   int n_cols = 3;
   uint32_t* len[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
@@ -511,72 +472,73 @@ struct ExonTextScratch {
   uint8_t* values[4] = {nullptr, nullptr, nullptr, nullptr};
   int64_t* qual = nullptr;
   size_t qual_cap = 0;
+  explicit ExonTextScratch(exon_hip_ctx* ctx) : bufs(ctx), qual_bufs(ctx) {}
 };
 
-void exon_text_scratch_destroy(ExonTextScratch* s) {
-  if (!s) return;
-  auto f = [&](void* p) { if (p) exon_pool_free(s->ctx, p); };
-  for (int k = 0; k < 4; ++k) f(s->values[k]);
-  for (int k = 0; k < 5; ++k) f(s->len[k]), f(s->off[k]);
-  f(s->item_off2), f(s->totals5);
-  if (s->h_totals5) hipHostFree(s->h_totals5);
-  f(s->valid[0]), f(s->valid[1]), f(s->field_off), f(s->field_len), f(s->sam_field_off), f(s->sums), f(s->totals), f(s->item_off), f(s->qual);
-  if (s->h_totals) hipHostFree(s->h_totals);
-  delete s;
-}
+void exon_text_scratch_destroy(ExonTextScratch* s) { delete s; }
 
 static int scratch_for(exon_hip_ctx* ctx, ExonTextScratch** sp, int64_t max_rows, int64_t max_bytes, bool vcf, int n_cols = 3) {
   ExonTextScratch* s = *sp;
   if (s && s->max_rows >= max_rows && s->max_bytes >= max_bytes && s->n_cols >= n_cols) return EXON_HIP_OK;
-  if (s) exon_text_scratch_destroy(s);
+  delete s;
   *sp = nullptr;
-  s = new (std::nothrow) ExonTextScratch();
+  s = new (std::nothrow) ExonTextScratch(ctx);
   if (!s) return fail(ctx, EXON_HIP_ENOMEM, "out of host memory");
-  s->ctx = ctx;
   s->max_rows = max_rows;
   s->max_bytes = max_bytes;
   s->n_cols = n_cols;
   hipSetDevice(ctx->device);
-  bool ok = true;
-  auto a = [&](void** p, size_t bytes) {
-    if (ok && !(*p = exon_pool_alloc(ctx, bytes))) ok = false;
-  };
+  PoolBufs& b = s->bufs;
   const size_t r = (size_t)max_rows + 64;
   for (int k = 0; k < n_cols; ++k) {
-    a((void**)&s->len[k], r * 4);
-    a((void**)&s->off[k], (r + 1) * 4);
-    if (k < 4) a((void**)&s->values[k], (size_t)max_bytes + 64);
+    s->len[k] = b.take<uint32_t>(r * 4);
+    s->off[k] = b.take<int32_t>((r + 1) * 4);
+    if (k < 4) s->values[k] = b.take<uint8_t>((size_t)max_bytes + 64);
   }
   if (n_cols >= 5) {  // BCF: alt items
-    a((void**)&s->item_off2, ((size_t)max_bytes / 2 + r + 2) * 4);
-    a((void**)&s->totals5, 32);
-    if (ok && hipHostMalloc((void**)&s->h_totals5, 32) != hipSuccess) ok = false;
+    s->item_off2 = b.take<int32_t>(((size_t)max_bytes / 2 + r + 2) * 4);
+    s->totals5 = b.take<unsigned>(32);
+    s->h_totals5 = b.pinned<unsigned>(32);
   }
-  a((void**)&s->valid[0], r / 8 + 64);
-  a((void**)&s->valid[1], r / 8 + 64);
+  s->valid[0] = b.take<uint32_t>(r / 8 + 64);
+  s->valid[1] = b.take<uint32_t>(r / 8 + 64);
   if (vcf) {
-    a((void**)&s->field_off, 3 * r * 4);
-    a((void**)&s->field_len, 3 * r * 4);
-    a((void**)&s->item_off, ((size_t)max_bytes / 2 + r + 2) * 4);
+    s->field_off = b.take<uint32_t>(3 * r * 4);
+    s->field_len = b.take<uint32_t>(3 * r * 4);
+    s->item_off = b.take<int32_t>(((size_t)max_bytes / 2 + r + 2) * 4);
   }
-  if (n_cols >= 4) a((void**)&s->sam_field_off, 4 * r * 4);
-  a((void**)&s->sums, (r / TPB + 4) * 4);
-  a((void**)&s->totals, 16);
-  if (ok && hipHostMalloc((void**)&s->h_totals, 16) != hipSuccess) ok = false;  // (4 totals: the FASTQ columns use them all)
-  if (!ok) {
+  if (n_cols >= 4) s->sam_field_off = b.take<uint32_t>(4 * r * 4);
+  s->sums = b.take<unsigned>((r / TPB + 4) * 4);
+  s->totals = b.take<unsigned>(16);
+  s->h_totals = b.pinned<unsigned>(16);  // (4 totals: the FASTQ columns use them all)
+  if (b.status() != hipSuccess) {
     (void)hipGetLastError();
-    exon_text_scratch_destroy(s);
+    delete s;
     return fail(ctx, EXON_HIP_ENOMEM, "buffers for the string columns of a slab (%lld rows, %lld bytes)", (long long)max_rows, (long long)max_bytes);
   }
   *sp = s;
   return EXON_HIP_OK;
 }
 
-static void scan_lengths(hipStream_t hs, ExonTextScratch* s, const uint32_t* len, unsigned n, int32_t* offsets, int total_slot) {
-  const int nb = (int)((n + TPB - 1) / TPB);
-  hipLaunchKernelGGL(k_block_sums, dim3(nb), dim3(TPB), 0, hs, len, n, s->sums);
-  hipLaunchKernelGGL(k_scan_sums, dim3(1), dim3(256), 0, hs, s->sums, nb, s->totals + total_slot);
-  hipLaunchKernelGGL(k_write_offsets, dim3(nb), dim3(TPB), 0, hs, len, n, s->sums, offsets);
+// room for `items` quality scores (kept between slabs, grown to at least 1 Mi items)
+static int qual_for(exon_hip_ctx* ctx, ExonTextScratch* s, unsigned items) {
+  if (s->qual_cap >= (size_t)items) return EXON_HIP_OK;
+  s->qual_bufs.release();
+  s->qual_cap = std::max<size_t>((size_t)items, (size_t)1 << 20);
+  s->qual = s->qual_bufs.take<int64_t>(s->qual_cap * 8);
+  if (!s->qual) {
+    s->qual_cap = 0;
+    s->qual_bufs.release();
+    return fail(ctx, EXON_HIP_ENOMEM, "quality_scores of a slab (%u items)", items);
+  }
+  return EXON_HIP_OK;
+}
+
+// lengths -> offsets (n + 1 of them); the total -> *total
+static void scan_lengths(hipStream_t hs, ExonTextScratch* s, const uint32_t* len, unsigned n, int32_t* offsets, unsigned* total) {
+  const int nb = (int)((n + LIST_TPB - 1) / LIST_TPB);
+  launch_list_scan(hs, len, nullptr, n, nb, s->sums, total);
+  hipLaunchKernelGGL(k_write_offsets, dim3(nb), dim3(LIST_TPB), 0, hs, len, n, s->sums, offsets);
 }
 
 int exon_text_vcf(exon_hip_ctx* ctx, void* stream, ExonTextScratch** sp, const uint8_t* d_text, int64_t n_bytes, const unsigned* d_nl, int64_t n_rows, uint64_t projection,
@@ -594,9 +556,9 @@ int exon_text_vcf(exon_hip_ctx* ctx, void* stream, ExonTextScratch** sp, const u
   const int nb = (int)((n + TPB - 1) / TPB);
   VcfLens L{s->len[0], s->len[1], s->len[2], s->field_off, s->field_len};
   hipLaunchKernelGGL(k_vcf_measure, dim3(nb), dim3(TPB), 0, hs, d_text, d_nl, n, skip, L, s->valid[0], s->valid[1]);
-  scan_lengths(hs, s, s->len[0], n, s->off[0], 0);  // ID: list offsets
-  scan_lengths(hs, s, s->len[1], n, s->off[1], 1);  // ID: byte offsets of every row's items
-  scan_lengths(hs, s, s->len[2], n, s->off[2], 2);  // REF
+  scan_lengths(hs, s, s->len[0], n, s->off[0], s->totals + 0);  // ID: list offsets
+  scan_lengths(hs, s, s->len[1], n, s->off[1], s->totals + 1);  // ID: byte offsets of every row's items
+  scan_lengths(hs, s, s->len[2], n, s->off[2], s->totals + 2);  // REF
   HIP_TRY(ctx, hipMemcpyAsync(s->h_totals, s->totals, 16, hipMemcpyDeviceToHost, hs));
   HIP_TRY(ctx, hipStreamSynchronize(hs));
   const unsigned id_items = s->h_totals[0], id_bytes = s->h_totals[1], ref_bytes = s->h_totals[2];
@@ -629,19 +591,12 @@ int exon_text_bam(exon_hip_ctx* ctx, void* stream, ExonTextScratch** sp, const u
   const int nb = (int)((n + TPB - 1) / TPB);
   BamLens L{s->len[0], s->len[1], s->len[2]};
   hipLaunchKernelGGL(k_bam_measure, dim3(nb), dim3(TPB), 0, hs, d_data, d_rec_of_row, n, L, s->valid[0]);
-  for (int k = 0; k < 3; ++k) scan_lengths(hs, s, s->len[k], n, s->off[k], k);
+  for (int k = 0; k < 3; ++k) scan_lengths(hs, s, s->len[k], n, s->off[k], s->totals + k);
   HIP_TRY(ctx, hipMemcpyAsync(s->h_totals, s->totals, 16, hipMemcpyDeviceToHost, hs));
   HIP_TRY(ctx, hipStreamSynchronize(hs));
   const unsigned name_bytes = s->h_totals[0], cigar_bytes = s->h_totals[1], seq_bytes = s->h_totals[2];
-  if ((projection & EXON_HIP_PROJECT_BAM_QUALITY_SCORES) && s->qual_cap < (size_t)seq_bytes) {
-    if (s->qual) exon_pool_free(ctx, s->qual);
-    s->qual_cap = std::max<size_t>((size_t)seq_bytes, (size_t)1 << 20);
-    s->qual = static_cast<int64_t*>(exon_pool_alloc(ctx, s->qual_cap * 8));
-    if (!s->qual) {
-      s->qual_cap = 0;
-      return fail(ctx, EXON_HIP_ENOMEM, "quality_scores of a slab (%u items)", seq_bytes);
-    }
-  }
+  if (projection & EXON_HIP_PROJECT_BAM_QUALITY_SCORES)
+    if (int rc = qual_for(ctx, s, seq_bytes)) return rc;
   hipLaunchKernelGGL(k_bam_fill, dim3(nb), dim3(TPB), 0, hs, d_data, d_rec_of_row, n, projection, s->off[0], s->off[1], s->off[2], s->values[0], s->values[1], s->values[2], s->qual);
   HIP_TRY(ctx, hipGetLastError());
   out->name_offsets = s->off[0];
@@ -673,7 +628,7 @@ int exon_text_fastq(exon_hip_ctx* ctx, void* stream, ExonTextScratch** sp, const
   FastqLens L{s->len[0], s->len[1], s->len[2], s->len[3]};
   hipLaunchKernelGGL(k_fastq_measure, dim3(nb), dim3(TPB), 0, hs, v->text_base, n, v->head_start, v->head_end, v->seq_start, v->seq_end, v->qual_start, v->qual_end, L,
                      s->valid[0]);
-  for (int k = 0; k < 4; ++k) scan_lengths(hs, s, s->len[k], n, s->off[k], k);
+  for (int k = 0; k < 4; ++k) scan_lengths(hs, s, s->len[k], n, s->off[k], s->totals + k);
   hipLaunchKernelGGL(k_fastq_fill, dim3(nb), dim3(TPB), 0, hs, v->text_base, n, v->head_start, v->seq_start, v->qual_start, s->off[0], s->off[1], s->off[2], s->off[3],
                      s->values[0], s->values[1], s->values[2], s->values[3]);
   HIP_TRY(ctx, hipGetLastError());
@@ -709,7 +664,7 @@ int exon_text_sam(exon_hip_ctx* ctx, void* stream, ExonTextScratch** sp, const u
   unsigned* d_und = s->sums + (s->max_rows + 64) / TPB + 2;  // a word of the block-sum buffer behind what scan_lengths uses (nb <= r / TPB + 1)
   HIP_TRY(ctx, hipMemsetAsync(d_und, 0, 4, hs));
   hipLaunchKernelGGL(k_sam_measure, dim3(nb), dim3(TPB), 0, hs, d_text, d_nl, n, skip, L, s->valid[0], d_und);
-  for (int k = 0; k < 4; ++k) scan_lengths(hs, s, s->len[k], n, s->off[k], k);
+  for (int k = 0; k < 4; ++k) scan_lengths(hs, s, s->len[k], n, s->off[k], s->totals + k);
   HIP_TRY(ctx, hipMemcpyAsync(s->h_totals, s->totals, 16, hipMemcpyDeviceToHost, hs));
   unsigned h_und = 0;
   HIP_TRY(ctx, hipMemcpyAsync(&h_und, d_und, 4, hipMemcpyDeviceToHost, hs));
@@ -717,15 +672,8 @@ int exon_text_sam(exon_hip_ctx* ctx, void* stream, ExonTextScratch** sp, const u
   *n_undecided = h_und;
   if (h_und) return EXON_HIP_OK;
   const unsigned qual_items = s->h_totals[3];
-  if ((projection & EXON_HIP_PROJECT_BAM_QUALITY_SCORES) && s->qual_cap < (size_t)qual_items) {
-    if (s->qual) exon_pool_free(ctx, s->qual);
-    s->qual_cap = std::max<size_t>((size_t)qual_items, (size_t)1 << 20);
-    s->qual = static_cast<int64_t*>(exon_pool_alloc(ctx, s->qual_cap * 8));
-    if (!s->qual) {
-      s->qual_cap = 0;
-      return fail(ctx, EXON_HIP_ENOMEM, "quality_scores of a slab (%u items)", qual_items);
-    }
-  }
+  if (projection & EXON_HIP_PROJECT_BAM_QUALITY_SCORES)
+    if (int rc = qual_for(ctx, s, qual_items)) return rc;
   hipLaunchKernelGGL(k_sam_fill, dim3(nb), dim3(TPB), 0, hs, d_text, n, L, projection, s->off[0], s->off[1], s->off[2], s->off[3], s->values[0], s->values[1], s->values[2],
                      s->qual);
   HIP_TRY(ctx, hipGetLastError());
@@ -760,12 +708,7 @@ int exon_text_bcf(exon_hip_ctx* ctx, void* stream, ExonTextScratch** sp, const u
   unsigned* d_und = s->totals5 + 7;
   HIP_TRY(ctx, hipMemsetAsync(s->totals5, 0, 32, hs));
   hipLaunchKernelGGL(k_bcf_measure, dim3(nb), dim3(TPB), 0, hs, d_data, d_rec_of_row, n, L, d_und);
-  for (int k = 0; k < 5; ++k) {  // (scan_lengths' three launches with the totals in this call's own eight words)
-    const int nbk = (int)((n + TPB - 1) / TPB);
-    hipLaunchKernelGGL(k_block_sums, dim3(nbk), dim3(TPB), 0, hs, s->len[k], n, s->sums);
-    hipLaunchKernelGGL(k_scan_sums, dim3(1), dim3(256), 0, hs, s->sums, nbk, s->totals5 + k);
-    hipLaunchKernelGGL(k_write_offsets, dim3(nbk), dim3(TPB), 0, hs, s->len[k], n, s->sums, s->off[k]);
-  }
+  for (int k = 0; k < 5; ++k) scan_lengths(hs, s, s->len[k], n, s->off[k], s->totals5 + k);  // (the totals in this call's own eight words)
   HIP_TRY(ctx, hipMemcpyAsync(s->h_totals5, s->totals5, 32, hipMemcpyDeviceToHost, hs));
   HIP_TRY(ctx, hipStreamSynchronize(hs));
   *n_undecided = s->h_totals5[7];
