@@ -333,7 +333,8 @@ __global__ __launch_bounds__(256) void k_bcf_remap(int32_t* __restrict__ filter_
   const int64_t n = scalars[0];
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
     const unsigned slot = (unsigned)filter_id[i];
-    filter_id[i] = slot < (unsigned)FSLOTS ? ids[slot] : 0;
+    const int id = slot < (unsigned)FSLOTS ? ids[slot] : 0;
+    filter_id[i] = id < EXON_HIP_MAX_GROUPS ? id : 0;  // (beyond the dictionary the slab is undecided: the host reader's)
   }
 }
 
@@ -350,6 +351,7 @@ struct exon_hip_bcf_parser {
   chain::ChainState chain;
   BcfOut out{};
   FilterLists filters{};
+  int32_t h_filter_stat[2] = {0, 0};  // the FILTER dictionary's counters after the last slab: {ids assigned, table overflow}
   explicit exon_hip_bcf_parser(exon_hip_ctx* c) : ctx(c), bufs(c) {}
   // key q's Number=1 value and validity buffers (once)
   void take_value(int q) {
@@ -464,6 +466,7 @@ int exon_hip_bcf_parser_parse(exon_hip_bcf_parser* p, void* stream, const uint8_
                      p->n_contigs, p->n_strings, p->ik, c.d_scalars);
   hipLaunchKernelGGL(k_bcf_assign, dim3(1), dim3(256), 0, s, p->filters);
   hipLaunchKernelGGL(k_bcf_remap, dim3(std::min<uint32_t>(n_seg * 4 + 1, 4096)), dim3(256), 0, s, p->out.filter_id, c.d_scalars, p->filters.ids);
+  HIP_TRY(ctx, hipMemcpyAsync(p->h_filter_stat, p->filters.counters, 8, hipMemcpyDeviceToHost, s));
   const unsigned row_bound = (unsigned)p->max_rows;
   const int lblocks = (int)((std::min<int64_t>(p->max_rows, n_bytes / 32 + 1) + LIST_TPB - 1) / LIST_TPB);  // a BCF record is >= 32 bytes
   const unsigned cap_items = (unsigned)std::min<int64_t>(p->max_bytes + 1, 0xFFFFFFFFLL);
@@ -478,7 +481,8 @@ int exon_hip_bcf_parser_parse(exon_hip_bcf_parser* p, void* stream, const uint8_
   }
   if (int rc = c.read_back(ctx, s)) return rc;
   cols->n_rows = c.h_scalars[0];
-  cols->n_undecided = c.h_scalars[1];
+  // more distinct FILTER lists than the dictionary holds (or a full table): the host reader's
+  cols->n_undecided = c.h_scalars[1] + ((p->h_filter_stat[1] || p->h_filter_stat[0] > EXON_HIP_MAX_GROUPS) ? 1 : 0);
   cols->consumed_bytes = c.h_scalars[2];
   cols->chrom_id = p->out.chrom_id;
   cols->pos = p->out.pos;
@@ -501,13 +505,17 @@ int exon_hip_bcf_parser_parse(exon_hip_bcf_parser* p, void* stream, const uint8_
   return EXON_HIP_OK;
 }
 
-// FILTER lists discovered so far, in id order: lists[i * 8 .. i * 8 + counts[i]) are dictionary (header string) indexes
-int exon_hip_bcf_parser_filters(exon_hip_bcf_parser* p, int32_t* lists, int32_t* counts, int32_t cap, int32_t* n_filters) {
+}  // extern "C"
+
+// so_far: after an overflow, the lists with the first EXON_HIP_MAX_GROUPS ids (those of every slab parsed before it)
+static int bcf_filters(exon_hip_bcf_parser* p, int32_t* lists, int32_t* counts, int32_t cap, int32_t* n_filters, bool so_far) {
   if (!p || !n_filters) return fail(p ? p->ctx : nullptr, EXON_HIP_EINVAL, "exon_hip_bcf_parser_filters: NULL argument");
   exon_hip_ctx* ctx = p->ctx;
   int32_t counters[4];
   HIP_TRY(ctx, hipMemcpy(counters, p->filters.counters, 16, hipMemcpyDeviceToHost));
-  if (counters[1] || counters[0] > EXON_HIP_MAX_GROUPS) return fail(ctx, EXON_HIP_EUNSUPPORTED, "more than %d distinct FILTER lists", EXON_HIP_MAX_GROUPS);
+  if ((counters[1] || counters[0] > EXON_HIP_MAX_GROUPS) && !so_far)
+    return fail(ctx, EXON_HIP_EUNSUPPORTED, "more than %d distinct FILTER lists", EXON_HIP_MAX_GROUPS);
+  counters[0] = std::min(counters[0], EXON_HIP_MAX_GROUPS);
   *n_filters = counters[0];
   if (!lists || !counts) return EXON_HIP_OK;
   if (counters[0] > cap) return fail(ctx, EXON_HIP_EINVAL, "filter list buffer too small (%d needed)", counters[0]);
@@ -525,7 +533,15 @@ int exon_hip_bcf_parser_filters(exon_hip_bcf_parser* p, int32_t* lists, int32_t*
     }
   return EXON_HIP_OK;
 }
+int exon_hip_bcf_parser_filters_so_far(exon_hip_bcf_parser* p, int32_t* lists, int32_t* counts, int32_t cap, int32_t* n_filters) {
+  return bcf_filters(p, lists, counts, cap, n_filters, true);
+}
 
+extern "C" {
+// FILTER lists discovered so far, in id order: lists[i * 8 .. i * 8 + counts[i]) are dictionary (header string) indexes
+int exon_hip_bcf_parser_filters(exon_hip_bcf_parser* p, int32_t* lists, int32_t* counts, int32_t cap, int32_t* n_filters) {
+  return bcf_filters(p, lists, counts, cap, n_filters, false);
+}
 }  // extern "C"
 
 const uint32_t* exon_hip_bcf_parser_row_records(exon_hip_bcf_parser* p) { return p ? p->out.rec_of_row : nullptr; }

@@ -14,7 +14,8 @@
 //   k_parse_lines      one thread per line: split on tabs, parse, look names up in hash tables, ballot the validity
 //                      bitmaps; FILTER lists not seen before are inserted with atomicCAS (slot = provisional id)
 //   k_assign_filters   dense ids for newly inserted FILTER lists, their text copied to a persistent pool
-//   k_remap_filters    provisional slot -> dense id
+//   k_remap_filters    provisional slot -> dense id; every row's text is compared with its key's text in the pool (a 64-bit
+//                      hash match of two different texts sets the table's overflow flag: the slab goes to the host reader)
 // Rows the device cannot decide (a float with > 19 significant digits, a contig missing from the header, a malformed
 // line) are counted; the caller then re-decodes that slab on the host, so results never differ from the CPU path.
 #include <hip/hip_runtime.h>
@@ -31,7 +32,7 @@ namespace {
 
 constexpr int TPB = 256;
 constexpr int FILTER_SLOTS = 8192;  // open addressing; at most EXON_HIP_MAX_GROUPS distinct lists are supported
-constexpr int FILTER_POOL = 1 << 20;
+constexpr int FILTER_POOL = EXON_DICT_POOL;
 
 __host__ __device__ inline uint64_t fnv1a(const uint8_t* p, int n) {
   uint64_t h = 0xCBF29CE484222325ULL;
@@ -272,7 +273,7 @@ struct FilterTable {
   uint32_t* text_off;        // provisional: offset into the CURRENT slab; after assignment: offset into pool
   uint32_t* text_len;
   uint8_t* pool;
-  int32_t* counters;  // [0] = number of dense ids, [1] = pool bytes used, [2] = overflow flag
+  int32_t* counters;  // [0] = ids claimed, [1] = pool bytes claimed, [2] = overflow (or hash collision) flag, [3] = rows without a value
 };
 
 constexpr int MAX_INFO = EXON_HIP_MAX_INFO_FIELDS;  // 16: the by-value key table below is 16 x 9 bytes of kernel arguments
@@ -296,6 +297,8 @@ struct ParseOut {
   float* qual;
   uint8_t* qual_valid;
   int32_t* filter_id;
+  uint32_t* filter_off;  // where the row's FILTER text is in the slab, and its length ('.' -> 0): k_remap_filters verifies it
+  uint32_t* filter_len;
   float* info[MAX_INFO];
   uint8_t* info_valid[MAX_INFO];
   uint32_t* lv_off[MAX_INFO];  // list kinds: offset of the value text in the slab / number of items, per row
@@ -379,7 +382,7 @@ __global__ __launch_bounds__(TPB) void k_parse_lines(const uint8_t* __restrict__
       out.chrom_id[row] = 0;
       out.pos[row] = 0;
       out.qual[row] = 0.f;
-      out.filter_id[row] = 0;
+      out.filter_id[row] = -1;  // no slot: k_remap_filters writes id 0 and compares nothing
       for (int q = 0; q < ik.n; ++q)
         if (ik.kind[q] == 'F' || ik.kind[q] == 'I') out.lv_cnt[q][row] = 0;  // summed by the offsets scan
     } else {
@@ -474,11 +477,10 @@ __global__ __launch_bounds__(TPB) void k_parse_lines(const uint8_t* __restrict__
           }
           slot = (slot + 1) & (FILTER_SLOTS - 1);
         }
-        if (found < 0) {
-          atomicExch(&filters.counters[2], 1);
-          found = 0;
-        }
+        if (found < 0) atomicExch(&filters.counters[2], 1);  // table full (found -1: no slot)
         out.filter_id[row] = found;  // provisional: slot index
+        out.filter_off[row] = fbeg(6);
+        out.filter_len[row] = (uint32_t)len;
       }
       // INFO: `key=value` (or a bare Flag key) among ';'-separated entries; the first occurrence of a key wins
       if (ik.n > 0 && !(EXON_PARSE_SKIP & 16)) {
@@ -584,7 +586,7 @@ __global__ __launch_bounds__(TPB) void k_info_string_ids(const uint8_t* __restri
   bool has = false;
   if (row < n) {
     has = (valid[row >> 3] >> (row & 7)) & 1;
-    int found = 0;
+    int found = -1;  // -1: no slot (no value, or the table is full): k_remap_filters writes id 0 and compares nothing
     // null_as_value (a fused plan groups by this key): a row without a value takes the id of the EMPTY text -- a value no row can
     // carry ("key=" is a missing value) -- so that NULL is a group of its own, as in DataFusion's GROUP BY
     if (has || null_as_value) {
@@ -610,10 +612,7 @@ __global__ __launch_bounds__(TPB) void k_info_string_ids(const uint8_t* __restri
         }
         slot = (slot + 1) & (FILTER_SLOTS - 1);
       }
-      if (found < 0) {
-        atomicExch(&t.counters[2], 1);
-        found = 0;
-      }
+      if (found < 0) atomicExch(&t.counters[2], 1);
     }
     ids[row] = found;
   }
@@ -624,16 +623,17 @@ __global__ __launch_bounds__(TPB) void k_info_string_ids(const uint8_t* __restri
 
 // dense ids for FILTER lists inserted during the last parse, text copied into the persistent pool.  New lists are
 // rare, so every thread scans its share of the slots and claims ids / pool space with atomics (ids are arbitrary
-// but stable; names are recovered through exon_hip_vcf_parser_filters).
+// but stable; names are recovered through exon_hip_vcf_parser_filters).  A slot that finds no room is marked -2: it
+// keeps no id, and its text stays in the slab (an id it claimed is a hole that table_names stops at).
 __global__ __launch_bounds__(256) void k_assign_filters(const uint8_t* __restrict__ text, FilterTable f) {
   for (int s = threadIdx.x; s < FILTER_SLOTS; s += 256)
-    if (f.keys[s] != 0 && f.ids[s] < 0) {
+    if (f.keys[s] != 0 && f.ids[s] == -1) {
       const uint32_t len = f.text_len[s], src = f.text_off[s];
       const int id = atomicAdd(&f.counters[0], 1);
       const int po = atomicAdd(&f.counters[1], (int)len);
-      if (id >= EXON_HIP_MAX_GROUPS || po + (int)len > FILTER_POOL) {
+      if (id >= EXON_HIP_MAX_GROUPS || po < 0 || po + (int64_t)len > FILTER_POOL) {
         f.counters[2] = 1;
-        f.ids[s] = 0;
+        f.ids[s] = -2;
         continue;
       }
       for (uint32_t i = 0; i < len; ++i) f.pool[po + i] = text[src + i];
@@ -642,13 +642,42 @@ __global__ __launch_bounds__(256) void k_assign_filters(const uint8_t* __restric
     }
 }
 
-__global__ __launch_bounds__(TPB) void k_remap_filters(int32_t* __restrict__ filter_id, const unsigned* __restrict__ n_lines_p,
-                                                       const int32_t* __restrict__ ids, unsigned cap) {
+// provisional slot -> dense id, and the text check: a key matched by its 64-bit hash alone may be another text (FNV-1a is no
+// cryptographic hash and the values are free file text), so each row compares its own bytes [off, off + len) with its key's
+// text in the pool.  A mismatch sets the overflow flag: the slab, like one that overflows the table, goes to the host reader.
+// valid: NULL (FILTER: every row with a slot has its text) or the String key's bitmap (a row without a value that took a slot
+// under null_as_value has the EMPTY text).  Rows without a slot (-1) get id 0.  An overflowed table compares nothing: its
+// slab is undecided already, and a slot without an id has no text in the pool.
+__global__ __launch_bounds__(TPB) void k_remap_filters(int32_t* __restrict__ ids_io, const unsigned* __restrict__ n_lines_p, unsigned cap,
+                                                       FilterTable t, const uint8_t* __restrict__ text, const uint32_t* __restrict__ off,
+                                                       const uint32_t* __restrict__ len, const uint8_t* __restrict__ valid) {
   const int64_t n = min(*n_lines_p, cap);
+  const bool check = t.counters[2] == 0;
+  bool differs = false;
   for (int64_t i = (int64_t)blockIdx.x * TPB + threadIdx.x; i < n; i += (int64_t)gridDim.x * TPB) {
-    const unsigned slot = (unsigned)filter_id[i];
-    filter_id[i] = slot < (unsigned)FILTER_SLOTS ? ids[slot] : 0;
+    const unsigned slot = (unsigned)ids_io[i];
+    if (slot >= (unsigned)FILTER_SLOTS) {
+      ids_io[i] = 0;
+      continue;
+    }
+    const int id = t.ids[slot];
+    ids_io[i] = id < 0 ? 0 : id;
+    if (!check) continue;
+    const bool has = !valid || ((valid[i >> 3] >> (i & 7)) & 1);
+    const uint32_t l = has ? len[i] : 0u, to = t.text_off[slot];
+    if (t.text_len[slot] != l || (uint64_t)to + l > (uint64_t)FILTER_POOL) {
+      differs = true;
+      continue;
+    }
+    const uint8_t* a = text + (has ? off[i] : 0u);
+    const uint8_t* b = t.pool + to;
+    for (uint32_t k = 0; k < l; ++k)
+      if (a[k] != b[k]) {
+        differs = true;
+        break;
+      }
   }
+  if (differs) atomicExch(&t.counters[2], 1);
 }
 
 }  // namespace
@@ -767,6 +796,7 @@ struct exon_hip_vcf_parser {
   FilterTable str_tables[MAX_INFO] = {};  // kind 's': the key's value dictionary, built on the device like the FILTER dictionary
   int null_as_value = 0;  // exon_hip_vcf_parser_set_null_key: rows without a value of a String key take the id of the empty text
   int32_t h_str_stat[MAX_INFO][2] = {{0, 0}};  // per 's' key, last slab: {dictionary overflow, rows without a value}
+  int32_t h_filter_stat = 0;                   // the FILTER dictionary's overflow flag after the last slab
   explicit exon_hip_vcf_parser(exon_hip_ctx* c) : ctx(c), bufs(c) {}
 };
 
@@ -826,6 +856,8 @@ int exon_hip_vcf_parser_create(exon_hip_ctx* ctx, const char* const* contig_name
   p->out.qual = b.take<float>(r * 4);
   p->out.qual_valid = b.take<uint8_t>(rb);
   p->out.filter_id = b.take<int32_t>(r * 4);
+  p->out.filter_off = b.take<uint32_t>(r * 4);
+  p->out.filter_len = b.take<uint32_t>(r * 4);
   p->cap_items = max_bytes / 2 + 1;  // a non-empty item and its separator take at least two bytes of the slab; a slab of mostly EMPTY
                                      // items (legal: "AF=,,,,") overflows this and is decoded by the host reader (k_list_fill / k_pack_bits clamp)
   for (int q = 0; q < p->ik.n; ++q) {
@@ -880,7 +912,9 @@ int exon_hip_vcf_parser_parse(exon_hip_vcf_parser* p, void* stream, const uint8_
   hipLaunchKernelGGL(k_parse_lines, dim3(pblocks), dim3(TPB), 0, s, d_text, idx.nl, idx.d_scalars, p->contigs, p->filters,
                      p->ik, p->out, (unsigned)row_bound, skip, (unsigned)n_bytes);
   hipLaunchKernelGGL(k_assign_filters, dim3(1), dim3(256), 0, s, d_text, p->filters);
-  hipLaunchKernelGGL(k_remap_filters, dim3(std::min(pblocks, 4096)), dim3(TPB), 0, s, p->out.filter_id, idx.d_scalars, p->filters.ids, (unsigned)row_bound);
+  hipLaunchKernelGGL(k_remap_filters, dim3(std::min(pblocks, 4096)), dim3(TPB), 0, s, p->out.filter_id, idx.d_scalars, (unsigned)row_bound, p->filters,
+                     d_text, p->out.filter_off, p->out.filter_len, (const uint8_t*)nullptr);
+  HIP_TRY(ctx, hipMemcpyAsync(&p->h_filter_stat, p->filters.counters + 2, 4, hipMemcpyDeviceToHost, s));  // overflow or collision
   const int lblocks = (int)((row_bound + LIST_TPB - 1) / LIST_TPB);
   const unsigned cap_items = (unsigned)std::min<int64_t>(p->cap_items, 0xFFFFFFFFLL);
   for (int q = 0; q < p->ik.n; ++q) {  // list-valued fields: counts -> offsets -> items -> child validity
@@ -899,14 +933,15 @@ int exon_hip_vcf_parser_parse(exon_hip_vcf_parser* p, void* stream, const uint8_
     hipLaunchKernelGGL(k_info_string_ids, dim3(pblocks), dim3(TPB), 0, s, d_text, p->out.lv_off[q], p->out.lv_cnt[q], p->out.info_valid[q], idx.d_scalars, (unsigned)row_bound, t,
                        (int32_t*)p->out.info[q], p->null_as_value);
     hipLaunchKernelGGL(k_assign_filters, dim3(1), dim3(256), 0, s, d_text, t);
-    hipLaunchKernelGGL(k_remap_filters, dim3(std::min(pblocks, 4096)), dim3(TPB), 0, s, (int32_t*)p->out.info[q], idx.d_scalars, t.ids, (unsigned)row_bound);
+    hipLaunchKernelGGL(k_remap_filters, dim3(std::min(pblocks, 4096)), dim3(TPB), 0, s, (int32_t*)p->out.info[q], idx.d_scalars, (unsigned)row_bound, t,
+                       d_text, p->out.lv_off[q], p->out.lv_cnt[q], (const uint8_t*)p->out.info_valid[q]);
     HIP_TRY(ctx, hipMemcpyAsync(p->h_str_stat[q], t.counters + 2, 8, hipMemcpyDeviceToHost, s));  // {overflow, rows without a value}
   }
   if (int rc = idx.read_back(ctx, s)) return rc;
   const int64_t n_lines = idx.h_scalars[0];
   if (n_lines > row_bound) return fail(ctx, EXON_HIP_EINVAL, "slab has %lld lines, more than its byte size allows for VCF records", (long long)n_lines);
   cols->n_rows = n_lines;
-  cols->n_undecided = idx.h_scalars[1];
+  cols->n_undecided = idx.h_scalars[1] + (p->h_filter_stat ? 1 : 0);  // FILTER lists beyond the dictionary: the host reader's
   cols->consumed_bytes = idx.consumed(skip);
   cols->chrom_id = p->out.chrom_id;
   cols->pos = p->out.pos;
@@ -935,11 +970,16 @@ int exon_hip_vcf_parser_parse(exon_hip_vcf_parser* p, void* stream, const uint8_
 const unsigned* exon_hip_vcf_parser_newlines(exon_hip_vcf_parser* p) { return p ? p->idx.nl : nullptr; }
 extern "C" {
 
-// a device-built dictionary (FILTER lists, or the values of a String INFO key) in id order: names '\0'-separated into `buf`
-static int table_names(exon_hip_ctx* ctx, const FilterTable& t, const char* what, char* buf, size_t cap, int32_t* n_names) {
+// a device-built dictionary (FILTER lists, or the values of a String INFO key) in id order: names '\0'-separated into `buf`.
+// so_far: an overflowed (or colliding) table still yields the names it assigned, up to the first id that got no name -- those of
+// every slab parsed before the overflow (the exporter names a slab's batches after the NEXT slab has been parsed)
+static int table_names(exon_hip_ctx* ctx, const FilterTable& t, const char* what, char* buf, size_t cap, int32_t* n_names, bool so_far) {
   int32_t counters[4];
   HIP_TRY(ctx, hipMemcpy(counters, t.counters, 16, hipMemcpyDeviceToHost));
-  if (counters[2]) return fail(ctx, EXON_HIP_EUNSUPPORTED, "more than %d distinct %s (or their text pool exhausted)", EXON_HIP_MAX_GROUPS, what);
+  if (counters[2] && !so_far)
+    return fail(ctx, EXON_HIP_EUNSUPPORTED, "more than %d distinct %s (or their text pool exhausted, or two of them hash alike)", EXON_HIP_MAX_GROUPS, what);
+  counters[0] = std::min(counters[0], EXON_HIP_MAX_GROUPS);
+  counters[1] = std::min(counters[1], FILTER_POOL);
   std::vector<unsigned long long> keys(FILTER_SLOTS);
   std::vector<int32_t> ids(FILTER_SLOTS);
   std::vector<uint32_t> toff(FILTER_SLOTS), tlen(FILTER_SLOTS);
@@ -950,12 +990,19 @@ static int table_names(exon_hip_ctx* ctx, const FilterTable& t, const char* what
   HIP_TRY(ctx, hipMemcpy(tlen.data(), t.text_len, FILTER_SLOTS * 4, hipMemcpyDeviceToHost));
   if (counters[1] > 0) HIP_TRY(ctx, hipMemcpy(pool.data(), t.pool, (size_t)counters[1], hipMemcpyDeviceToHost));
   std::vector<std::string> names((size_t)counters[0]);
+  std::vector<char> named((size_t)counters[0], 0);
   for (int s = 0; s < FILTER_SLOTS; ++s)
-    if (keys[(size_t)s] != 0 && ids[(size_t)s] >= 0 && ids[(size_t)s] < counters[0])
+    if (keys[(size_t)s] != 0 && ids[(size_t)s] >= 0 && ids[(size_t)s] < counters[0] && (size_t)toff[(size_t)s] + tlen[(size_t)s] <= pool.size()) {
       names[(size_t)ids[(size_t)s]] = std::string(reinterpret_cast<const char*>(pool.data()) + toff[(size_t)s], tlen[(size_t)s]);
+      named[(size_t)ids[(size_t)s]] = 1;
+    }
+  size_t n = 0;
+  while (n < names.size() && named[n]) ++n;
+  if (n < names.size() && !counters[2]) return fail(ctx, EXON_HIP_EDEVICE, "%s: id %zu has no name", what, n);
+  names.resize(n);
   size_t need = 0;
   for (const auto& nm : names) need += nm.size() + 1;
-  *n_names = counters[0];
+  *n_names = (int32_t)n;
   if (buf) {
     if (need > cap) return fail(ctx, EXON_HIP_EINVAL, "name buffer too small (%zu needed)", need);
     size_t o = 0;
@@ -969,7 +1016,7 @@ static int table_names(exon_hip_ctx* ctx, const FilterTable& t, const char* what
 // FILTER dictionary discovered so far: names are written '\0'-separated into `buf` (id order); returns the count
 int exon_hip_vcf_parser_filters(exon_hip_vcf_parser* p, char* buf, size_t cap, int32_t* n_filters) {
   if (!p || !n_filters) return fail(p ? p->ctx : nullptr, EXON_HIP_EINVAL, "exon_hip_vcf_parser_filters: NULL argument");
-  return table_names(p->ctx, p->filters, "FILTER lists", buf, cap, n_filters);
+  return table_names(p->ctx, p->filters, "FILTER lists", buf, cap, n_filters, false);
 }
 // on != 0: a row without a value of a String / Character key gets the dictionary id of the EMPTY text (no row can carry it) and
 // counts as valid: NULL becomes a group key of its own for a plan that groups by the key.  Off (default): NULL stays NULL.
@@ -982,10 +1029,20 @@ int exon_hip_vcf_parser_set_null_key(exon_hip_vcf_parser* p, int32_t on) {
 int exon_hip_vcf_parser_info_values(exon_hip_vcf_parser* p, int32_t key, char* buf, size_t cap, int32_t* n_values) {
   if (!p || !n_values) return fail(p ? p->ctx : nullptr, EXON_HIP_EINVAL, "exon_hip_vcf_parser_info_values: NULL argument");
   if (key < 0 || key >= p->ik.n || p->ik.kind[key] != 's') return fail(p->ctx, EXON_HIP_EINVAL, "exon_hip_vcf_parser_info_values: key %d is not a String / Character key of this parser", key);
-  return table_names(p->ctx, p->str_tables[key], "values of a String INFO key", buf, cap, n_values);
+  return table_names(p->ctx, p->str_tables[key], "values of a String INFO key", buf, cap, n_values, false);
 }
 
 }  // extern "C"
+
+int exon_hip_vcf_parser_filters_so_far(exon_hip_vcf_parser* p, char* buf, size_t cap, int32_t* n_filters) {
+  if (!p || !n_filters) return fail(p ? p->ctx : nullptr, EXON_HIP_EINVAL, "exon_hip_vcf_parser_filters_so_far: NULL argument");
+  return table_names(p->ctx, p->filters, "FILTER lists", buf, cap, n_filters, true);
+}
+int exon_hip_vcf_parser_info_values_so_far(exon_hip_vcf_parser* p, int32_t key, char* buf, size_t cap, int32_t* n_values) {
+  if (!p || !n_values || key < 0 || key >= p->ik.n || p->ik.kind[key] != 's')
+    return fail(p ? p->ctx : nullptr, EXON_HIP_EINVAL, "exon_hip_vcf_parser_info_values_so_far: bad argument");
+  return table_names(p->ctx, p->str_tables[key], "values of a String INFO key", buf, cap, n_values, true);
+}
 
 // ------------------------------------------------------------------------------------------------------------
 // FASTQ: the newline index above is all the "parsing" a histogram over quality (or sequence) lines needs.  Read r

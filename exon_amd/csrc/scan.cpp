@@ -1761,17 +1761,19 @@ static void region_target(const exon_hip_scan* scan, int32_t* id, int64_t* a, in
   *range_form = !scan->vcf_like();
 }
 
-// FILTER dictionary of the device parser, names in id order
-static int gpu_filter_names(exon_hip_scan* scan, std::vector<std::string>* names) {
+// FILTER dictionary of the device parser, names in id order.  so_far: also after the table overflowed, the names assigned
+// before (the exporter's names of a slab whose successor overflowed: that hand-over is not an error)
+static int gpu_filter_names(exon_hip_scan* scan, std::vector<std::string>* names, bool so_far = false) {
   names->clear();
   int rc = EXON_HIP_OK;
   if (!scan->parser.owns_names) return rc;
   if (exon::BCFBatchReader* bcf = scan->bcf()) {
     exon_hip_bcf_parser* p = scan->parser.as<exon_hip_bcf_parser>();
     int32_t nf = 0;
-    rc = exon_hip_bcf_parser_filters(p, nullptr, nullptr, 0, &nf);
+    auto fetch = so_far ? exon_hip_bcf_parser_filters_so_far : exon_hip_bcf_parser_filters;
+    rc = fetch(p, nullptr, nullptr, 0, &nf);
     std::vector<int32_t> lists((size_t)std::max(nf, 1) * 8), counts((size_t)std::max(nf, 1));
-    if (!rc) rc = exon_hip_bcf_parser_filters(p, lists.data(), counts.data(), nf, &nf);
+    if (!rc) rc = fetch(p, lists.data(), counts.data(), nf, &nf);
     if (rc) return rc;
     const std::vector<std::string>& strs = bcf->strings();
     for (int32_t i = 0; i < nf; ++i) {
@@ -1784,8 +1786,8 @@ static int gpu_filter_names(exon_hip_scan* scan, std::vector<std::string>* names
     }
   } else {
     int32_t nf = 0;
-    std::vector<char> buf(1 << 20);
-    rc = exon_hip_vcf_parser_filters(scan->parser.as<exon_hip_vcf_parser>(), buf.data(), buf.size(), &nf);
+    std::vector<char> buf(EXON_DICT_NAMES_CAP);
+    rc = (so_far ? exon_hip_vcf_parser_filters_so_far : exon_hip_vcf_parser_filters)(scan->parser.as<exon_hip_vcf_parser>(), buf.data(), buf.size(), &nf);
     if (rc) return rc;
     size_t o = 0;
     for (int32_t i = 0; i < nf; ++i) {
@@ -1797,7 +1799,7 @@ static int gpu_filter_names(exon_hip_scan* scan, std::vector<std::string>* names
 }
 
 // the value dictionaries of the String INFO keys the device decoded (VCF text): names[k] for scan column 4 + k (empty for other kinds)
-static int gpu_info_names(exon_hip_scan* scan, std::vector<std::vector<std::string>>* names) {
+static int gpu_info_names(exon_hip_scan* scan, std::vector<std::vector<std::string>>* names, bool so_far = false) {
   names->clear();
   if (!scan->vcf() || !scan->parser.owns_names) return EXON_HIP_OK;
   const std::vector<exon::InfoSpec>& specs = scan->vcf()->info_specs;
@@ -1808,8 +1810,8 @@ static int gpu_info_names(exon_hip_scan* scan, std::vector<std::vector<std::stri
     if (specs[k].kind == 'S') continue;
     if (specs[k].kind == 's') {
       int32_t nv = 0;
-      buf.resize(2u << 20);
-      const int rc = exon_hip_vcf_parser_info_values(scan->parser.as<exon_hip_vcf_parser>(), q, buf.data(), buf.size(), &nv);
+      buf.resize(EXON_DICT_NAMES_CAP);
+      const int rc = (so_far ? exon_hip_vcf_parser_info_values_so_far : exon_hip_vcf_parser_info_values)(scan->parser.as<exon_hip_vcf_parser>(), q, buf.data(), buf.size(), &nv);
       if (rc) return rc;
       size_t o = 0;
       for (int32_t i = 0; i < nv; ++i) {
@@ -2289,13 +2291,14 @@ static int export_slab(exon_hip_scan* scan, const exon_hip_column* sc, int64_t n
   const HostText& text = *text_p;
   const double tn0 = now_s();
   std::vector<std::string> filters;
+  // (so far: the next slab, parsed by now, may have overflowed a table and handed the scan over; this slab's ids come first)
   if (vcf_like) {
-    const int rc = gpu_filter_names(scan, &filters);
+    const int rc = gpu_filter_names(scan, &filters, true);
     if (rc) return rc;
   }
   std::vector<std::vector<std::string>> info_names;
   if (scan->vcf()) {
-    const int rc = gpu_info_names(scan, &info_names);
+    const int rc = gpu_info_names(scan, &info_names, true);
     if (rc) return rc;
   }
   g_t_names += now_s() - tn0;

@@ -535,7 +535,7 @@ class VCFParser:
 
     def filters(self):
         n = C.c_int32()
-        buf = C.create_string_buffer(1 << 20)
+        buf = C.create_string_buffer((1 << 20) + 4096)  # the dictionary's text pool plus one NUL per name (EXON_HIP_MAX_GROUPS)
         self.ctx._check(self.ctx.lib.exon_hip_vcf_parser_filters(self.h, buf, len(buf), C.byref(n)))
         names, o = [], 0
         raw = buf.raw

@@ -12,11 +12,12 @@ INFO_HEADER = [("AF", "1", "Float"), ("DP", "1", "Integer"), ("DB", "0", "Flag")
 FILTERS = ["q10", "s50"]
 
 
-def header_text(bcf):
+def header_text(bcf, filters=FILTERS):
+    """filters: the FILTER IDs the header declares besides PASS (IDX 1 .. in BCF)"""
     idx = 0
     lines = ["##fileformat=VCFv4.3", '##FILTER=<ID=PASS,Description="All filters passed"' + (",IDX=0>" if bcf else ">"),
              "##contig=<ID=1" + (",IDX=0>" if bcf else ">"), "##contig=<ID=2" + (",IDX=1>" if bcf else ">")]
-    for f in FILTERS:
+    for f in filters:
         idx += 1
         lines.append(f'##FILTER=<ID={f},Description="x"' + (f",IDX={idx}>" if bcf else ">"))
     for name, number, typ in INFO_HEADER:
@@ -26,8 +27,8 @@ def header_text(bcf):
     return "\n".join(lines) + "\n"
 
 
-def string_index():
-    names = ["PASS"] + FILTERS + [n for n, _, _ in INFO_HEADER]
+def string_index(filters=FILTERS):
+    names = ["PASS"] + list(filters) + [n for n, _, _ in INFO_HEADER]
     return {n: i for i, n in enumerate(names)}
 
 
@@ -86,9 +87,9 @@ def _info_text(info):
     return ";".join(parts)
 
 
-def write_vcf(path, rows):
+def write_vcf(path, rows, filters=FILTERS):
     with open(path, "w") as f:
-        f.write(header_text(False))
+        f.write(header_text(False, filters))
         for r in rows:
             q = "." if r["qual"] is None else np.format_float_positional(np.float32(r["qual"]), unique=True, trim="0")
             f.write(f"{r['chrom']}\t{r['pos']}\t.\tA\tC\t{q}\t{';'.join(r['filter']) or '.'}\t{_info_text(r['info'])}\n")
@@ -122,11 +123,11 @@ def _typed_str(s):
     return _desc(len(b), 7) + b
 
 
-def write_bcf(path, rows, bgzip):
-    """uncompressed BCF stream -> `bgzip` (tools/bin/bgzip) -> path"""
-    sidx = string_index()
+def write_bcf(path, rows, bgzip, filters=FILTERS):
+    """uncompressed BCF stream -> `bgzip` (tools/bin/bgzip) -> path; a row's FILTER IDs are PASS or among `filters`"""
+    sidx = string_index(filters)
     types = {n: (num, typ) for n, num, typ in INFO_HEADER}
-    text = header_text(True).encode() + b"\0"
+    text = header_text(True, filters).encode() + b"\0"
     out = [b"BCF\x02\x02", struct.pack("<I", len(text)), text]
     for r in rows:
         info = r["info"] or {}
