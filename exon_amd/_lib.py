@@ -99,6 +99,13 @@ class VCFColumns(C.Structure):
                 ("info_nulls", C.c_int32 * 16)]
 
 
+class GFFColumns(C.Structure):
+    _fields_ = [("n_rows", C.c_int64), ("n_undecided", C.c_int64), ("consumed_bytes", C.c_int64),
+                ("seqname_id", C.c_void_p), ("source_id", C.c_void_p), ("type_id", C.c_void_p), ("start", C.c_void_p),
+                ("end", C.c_void_p), ("score", C.c_void_p), ("score_valid", C.c_void_p), ("strand_id", C.c_void_p),
+                ("strand_valid", C.c_void_p), ("phase_id", C.c_void_p), ("phase_valid", C.c_void_p)]
+
+
 class ScanOptions(C.Structure):
     _fields_ = [("format", C.c_int32), ("compression", C.c_int32), ("batch_size", C.c_int64),
                 ("info_field", C.c_char_p), ("region", C.c_char_p), ("use_index", C.c_int32), ("gpu_parse", C.c_int32),
@@ -109,7 +116,7 @@ class GzipStats(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in ("calls", "chunks", "repairs", "overflow_retries", "members", "comp_bytes", "out_bytes")]
 
 
-FORMATS = {"vcf": 1, "bam": 2, "fastq": 3, "fasta": 4, "sam": 5, "bcf": 6, "cram": 7}
+FORMATS = {"vcf": 1, "bam": 2, "fastq": 3, "fasta": 4, "sam": 5, "bcf": 6, "cram": 7, "gff": 8}
 COMPRESSION = {"auto": 0, None: 0, "none": 1, "gzip": 2}
 
 PLAN_REGION_COUNT = 2
@@ -218,6 +225,10 @@ SIGNATURES = {
     "exon_hip_sam_parser_create": (C.c_int, [_vp, C.POINTER(C.c_char_p), _i32, _i64, C.POINTER(_vp)]),
     "exon_hip_sam_parser_parse": (C.c_int, [_vp, _vp, _vp, _i64, C.POINTER(BAMColumns)]),
     "exon_hip_sam_parser_destroy": (C.c_int, [_vp]),
+    "exon_hip_gff_parser_create": (C.c_int, [_vp, C.POINTER(C.c_char_p), _i32, _i64, C.POINTER(_vp)]),
+    "exon_hip_gff_parser_parse": (C.c_int, [_vp, _vp, _vp, _i64, C.POINTER(GFFColumns)]),
+    "exon_hip_gff_parser_names": (C.c_int, [_vp, _i32, C.c_char_p, C.c_size_t, C.POINTER(_i32)]),
+    "exon_hip_gff_parser_destroy": (C.c_int, [_vp]),
     "exon_hip_bcf_parser_create": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i64, C.POINTER(_vp)]),
     "exon_hip_bcf_parser_set_info_keys": (C.c_int, [_vp, C.POINTER(_i32), C.c_char_p, _i32]),
     "exon_hip_bcf_parser_parse": (C.c_int, [_vp, _vp, _vp, _i64, C.POINTER(VCFColumns)]),

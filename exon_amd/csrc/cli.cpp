@@ -6,12 +6,13 @@
 // GPU, like config 1); predicates / GROUP BY run through exon_hip_plan_* / exon_hip_stream_* on the GPU.
 //
 //   SET exon.vcf_parse_info = true;
-//   CREATE EXTERNAL TABLE t STORED AS FASTA|FASTQ|VCF|BAM|INDEXED_VCF|INDEXED_BAM [OPTIONS (compression gzip)] LOCATION '<path|dir>';
+//   CREATE EXTERNAL TABLE t STORED AS FASTA|FASTQ|VCF|BAM|GFF|INDEXED_VCF|INDEXED_BAM|INDEXED_GFF [OPTIONS (compression gzip)] LOCATION '<path|dir>';
 //   SELECT COUNT(*) FROM t | fasta_scan('<p>'[, 'gzip']) | fastq_scan(..) | vcf_scan(..) | bam_scan(..)
-//                         | vcf_indexed_scan('<p>', '<region>') | bam_indexed_scan('<p>', '<region>')
+//                         | vcf_indexed_scan('<p>', '<region>') | bam_indexed_scan('<p>', '<region>') | gff_scan(..) | gff_indexed_scan(..)
 //   SELECT COUNT(*) FROM v WHERE chrom = '7' AND pos >= 50000000 AND pos <= 100000000            -- K2
 //   SELECT COUNT(*) FROM v WHERE vcf_region_filter('7:50000000-100000000', chrom[, pos]) [= true] -- pushed down
 //   SELECT COUNT(*) FROM b WHERE bam_region_filter('chr1:1-100', reference, start, end) [= true]  -- pushed down
+//   SELECT COUNT(*) FROM g WHERE gff_region_filter('chr1[:a-b]', seqname[, start]) [= true]       -- K2 over (seqname, start)
 //   SELECT reference, COUNT(*) FROM b WHERE flag & 1284 = 0 AND CAST(mapping_quality AS INT) >= 30 GROUP BY reference  -- K3
 //   SELECT filter, AVG(qual), COUNT(*) FROM v WHERE info."AF" > 0.01 GROUP BY filter            -- K4
 //   SELECT * FROM fastq_quality_histogram('<p>'[, 'gzip'])                                        -- K5
@@ -188,6 +189,7 @@ std::vector<std::string> format_exts(int format, const std::string& custom) {
     case EXON_HIP_FORMAT_SAM: return {".sam"};
     case EXON_HIP_FORMAT_BCF: return {".bcf"};
     case EXON_HIP_FORMAT_CRAM: return {".cram"};
+    case EXON_HIP_FORMAT_GFF: return {".gff", ".gff3"};
     default: return {".bam"};
   }
 }
@@ -203,6 +205,7 @@ int format_of(const std::string& name, bool* indexed) {
   if (f == "sam") return EXON_HIP_FORMAT_SAM;
   if (f == "bcf") return EXON_HIP_FORMAT_BCF;
   if (f == "cram") return EXON_HIP_FORMAT_CRAM;
+  if (f == "gff") return EXON_HIP_FORMAT_GFF;
   throw Err("unsupported file type " + name);
 }
 
@@ -273,7 +276,7 @@ void open_scan(const Source& src, const std::string& file, const char* info_fiel
   // INDEXED_* tables / *_indexed_scan: plan BGZF chunks from <file>.tbi / <file>.bai
   // (exon-core/src/datasources/indexed_file/indexed_bgzf_file.rs:129-155)
   o.use_index = (src.indexed && !region.empty()) ? 1 : 0;
-  o.gpu_parse = (for_gpu_query && (src.format == EXON_HIP_FORMAT_VCF || src.format == EXON_HIP_FORMAT_FASTQ || src.format == EXON_HIP_FORMAT_BAM || src.format == EXON_HIP_FORMAT_BCF || src.format == EXON_HIP_FORMAT_SAM) &&
+  o.gpu_parse = (for_gpu_query && (src.format == EXON_HIP_FORMAT_VCF || src.format == EXON_HIP_FORMAT_FASTQ || src.format == EXON_HIP_FORMAT_BAM || src.format == EXON_HIP_FORMAT_BCF || src.format == EXON_HIP_FORMAT_SAM || src.format == EXON_HIP_FORMAT_GFF) &&
                  region.empty() && gpu_parse_enabled()) ? 1 : 0;
   ck(nullptr, exon_hip_scan_open(file.c_str(), &o, &g->s));
 }
@@ -316,8 +319,8 @@ int cmp_code(const std::string& s) {
 
 Predicate parse_where(Parser& ps, int format) {
   Predicate pr;
-  // pushed-down marker UDFs (exon-core/src/udfs/vcf/vcf_region_filter.rs:23-75, udfs/sam/bam_region_filter.rs:23-86)
-  if (ps.is_kw("vcf_region_filter") || ps.is_kw("bam_region_filter")) {
+  // pushed-down marker UDFs (exon-core/src/udfs/vcf/vcf_region_filter.rs:23-75, udfs/sam/bam_region_filter.rs:23-86, udfs/gff/gff_region_filter.rs)
+  if (ps.is_kw("vcf_region_filter") || ps.is_kw("bam_region_filter") || ps.is_kw("gff_region_filter")) {
     ps.ident();
     ps.expect_sym("(");
     pr.kind = Predicate::PushedRegion;
@@ -474,6 +477,32 @@ void exec_select(Session& se, Parser& ps) {
       exon_hip_plan_desc d; memset(&d, 0, sizeof d);
       d.kind = EXON_HIP_PLAN_OVERLAP_COUNT; d.region_chrom_id = rid; d.region_start = a; d.region_end = b;
       d.columns[0] = 2; d.columns[1] = 3; d.columns[2] = 4;
+      ck(ctx, exon_hip_plan_create(ctx, &d, &sg.p));
+      ck(ctx, exon_hip_stream_open(sg.p, 0, &sg.s));
+      ck(ctx, exon_hip_stream_consume_scan(sg.s, g.s, nullptr));
+      int64_t c = 0;
+      ck(ctx, exon_hip_stream_finish(sg.s, &c, nullptr));
+      total += c;
+    }
+    print_table({"count(*)"}, {{std::to_string(total)}}, se.quiet);
+    return;
+  }
+  if (count_only && pr.kind == Predicate::PushedRegion && !src.indexed && gpu_parse_enabled() && src.format == EXON_HIP_FORMAT_GFF) {
+    // gff_region_filter is the reference reader's own test (exon-gff/src/batch_reader.rs:76-97: seqname = name AND start inside
+    // the interval): K2 over scan columns (0, 3), the text parsed on the device
+    exon_hip_ctx* ctx = se.gpu();
+    char name[512];
+    int64_t a = 1, b = INT64_MAX;
+    ck(nullptr, exon_hip_parse_region(pr.region.c_str(), name, sizeof name, &a, &b));
+    int64_t total = 0;
+    for (const auto& f : src.files) {
+      ScanGuard g; open_scan(src, f, nullptr, "", &g, true);
+      int32_t sid = -1;
+      ck(nullptr, exon_hip_scan_dictionary_intern(g.s, 0, name, &sid));  // (GFF has no header: the name seeds the scan's dictionary)
+      StreamGuard sg;
+      exon_hip_plan_desc d; memset(&d, 0, sizeof d);
+      d.kind = EXON_HIP_PLAN_REGION_COUNT; d.region_chrom_id = sid; d.region_start = a; d.region_end = b;
+      d.columns[0] = 0; d.columns[1] = 3;
       ck(ctx, exon_hip_plan_create(ctx, &d, &sg.p));
       ck(ctx, exon_hip_stream_open(sg.p, 0, &sg.s));
       ck(ctx, exon_hip_stream_consume_scan(sg.s, g.s, nullptr));
@@ -657,10 +686,11 @@ int main(int argc, char** argv) {
     else if (a == "-q" || a == "--quiet") se.quiet = true;
     else if (a == "-h" || a == "--help") {
       printf("exon-hip-cli [-q] -c '<sql>'... | -f <file>...\n"
-             "  tables:    CREATE EXTERNAL TABLE t STORED AS FASTA|FASTQ|VCF|BAM|INDEXED_VCF|INDEXED_BAM [OPTIONS (compression gzip)] LOCATION '<path>'\n"
-             "  functions: fasta_scan fastq_scan vcf_scan bam_scan ('<path>'[, 'gzip']); vcf_indexed_scan bam_indexed_scan ('<path>', '<region>');\n"
+             "  tables:    CREATE EXTERNAL TABLE t STORED AS FASTA|FASTQ|VCF|BAM|GFF|INDEXED_VCF|INDEXED_BAM|INDEXED_GFF [OPTIONS (compression gzip)] LOCATION '<path>'\n"
+             "  functions: fasta_scan fastq_scan vcf_scan bam_scan gff_scan ('<path>'[, 'gzip']); vcf_indexed_scan bam_indexed_scan gff_indexed_scan ('<path>', '<region>');\n"
              "             fastq_quality_histogram('<path>')\n"
-             "  queries:   SELECT COUNT(*) FROM <src> [WHERE chrom = 'c' AND pos >= a AND pos <= b | vcf_region_filter('r', chrom) | bam_region_filter('r', reference, start, end)]\n"
+             "  queries:   SELECT COUNT(*) FROM <src> [WHERE chrom = 'c' AND pos >= a AND pos <= b | vcf_region_filter('r', chrom) | bam_region_filter('r', reference, start, end)\n"
+             "             | gff_region_filter('r', seqname[, start])]\n"
              "             SELECT reference, COUNT(*) FROM <bam> WHERE flag & M = V AND CAST(mapping_quality AS INT) >= q GROUP BY reference\n"
              "             SET exon.vcf_parse_info = true; SELECT filter, AVG(qual), COUNT(*) FROM <vcf> WHERE info.\"AF\" > 0.01 GROUP BY filter\n");
       return 0;

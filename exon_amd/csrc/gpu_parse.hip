@@ -1343,3 +1343,355 @@ int exon_hip_sam_parser_parse(exon_hip_sam_parser* p, void* stream, const uint8_
 }
 
 }  // extern "C"
+
+// ------------------------------------------------------------------------------------------------------------
+// GFF3 text: the first eight tab-separated fields of every record line -> the GFF device layout (host/gff.h states the line
+// rules once; exon-gff/src/array_builder.rs is the schema).  GFF has no header: seqname, source and type are free text whose
+// dictionaries are built on the device, each in a FilterTable of its own (claim in the line kernel, k_assign_filters,
+// k_remap_filters with the text compare, exactly as the FILTER dictionary).  Lines that start with '#' are no rows, so a row's
+// number is its RANK among the lines that are: k_gff_classify marks them, the offsets scan (list_kernels.h) ranks them, and a
+// slab without any '#' line -- every slab but a file's first, usually -- takes the identity (row = line, validity by ballot).
+// Rows the device cannot decide (a malformed field, more than 18 digits, a float the Eisel-Lemire path leaves open, an empty
+// line, a "##FASTA" line, a dictionary past its limits) are counted: the caller decodes the file on the host, which reports.
+namespace {
+
+struct GffOut {
+  int32_t* id[3];    // seqname, source, type: provisional slot, then the dense id (k_remap_filters)
+  uint32_t* off[3];  // where the field's text is in the slab, and its length: k_remap_filters verifies it
+  uint32_t* len[3];
+  int64_t* start;
+  int64_t* end;
+  float* score;
+  int32_t* strand;
+  int32_t* phase;
+  uint8_t *score_valid, *strand_valid, *phase_valid;
+  uint8_t* vflags;  // ranked slabs: bit 0 score, 1 strand, 2 phase of every row (k_gff_pack_valid makes the bitmaps of them)
+};
+
+// scalars: [0] lines (in), [1] undecided (+=), [2] consumed bytes, [3] rows (the offsets scan's total)
+__global__ __launch_bounds__(TPB) void k_gff_classify(const uint8_t* __restrict__ text, const unsigned* __restrict__ nl_pos, unsigned* __restrict__ scalars,
+                                                      unsigned cap, unsigned skip, uint32_t* __restrict__ is_row) {
+  const unsigned n_lines = min(scalars[0], cap);
+  const unsigned line = blockIdx.x * TPB + threadIdx.x;
+  if (line >= n_lines) return;
+  const unsigned begin = line ? nl_pos[line - 1] + 1 : skip, end = nl_pos[line];
+  const bool row = text[begin] != '#';  // (an empty line reads its own '\n': a row, and an undecided one)
+  is_row[line] = row ? 1u : 0u;
+  if (!row && end - begin >= 7u) {
+    const uint8_t* p = text + begin;
+    if (p[1] == '#' && p[2] == 'F' && p[3] == 'A' && p[4] == 'S' && p[5] == 'T' && p[6] == 'A') atomicAdd(&scalars[1], 1u);
+  }
+}
+
+// the slot of text [off, off + len) in `t`, claimed if it is new (k_parse_lines' FILTER lookup); -1: the table is full
+__device__ __forceinline__ int table_claim(const FilterTable& t, const uint8_t* __restrict__ text, unsigned off, int len) {
+  const unsigned long long h = fnv1a(text + off, len);
+  int slot = (int)(h & (FILTER_SLOTS - 1));
+  for (int probe = 0; probe < FILTER_SLOTS; ++probe) {
+    unsigned long long k = t.keys[slot];
+    if (k == 0) {
+      k = atomicCAS(&t.keys[slot], 0ull, h);
+      if (k == 0) {
+        t.text_off[slot] = off;
+        t.text_len[slot] = (uint32_t)len;
+        return slot;
+      }
+    }
+    if (k == h) return slot;
+    slot = (slot + 1) & (FILTER_SLOTS - 1);
+  }
+  atomicExch(&t.counters[2], 1);
+  return -1;
+}
+
+// start / end: Rust's usize::from_str (one '+', digits) and >= 1; up to 18 digits here, longer ones are the host's
+__device__ __forceinline__ bool gff_position(const uint8_t* __restrict__ text, unsigned pb, unsigned pe, unsigned n_total, int64_t* out) {
+  unsigned pn = pe - pb;
+  if (pn && text[pb] == '+') ++pb, --pn;
+  bool ok = pn > 0 && pn <= 18;
+  uint64_t v = 0;  // (unsigned: a spoiled value wraps, it is then not used)
+  if (pn <= 16 && pb + 16u <= n_total) {  // the digits from two (unaligned) 8-byte loads, no branch per digit
+    uint64_t w[2];
+    __builtin_memcpy(w, text + pb, 16);
+    for (unsigned k = 0; k < pn; ++k) {
+      const unsigned d = ((unsigned)(w[k >> 3] >> (8 * (k & 7))) & 0xFFu) - (unsigned)'0';
+      ok &= d <= 9u;
+      v = v * 10 + d;
+    }
+  } else {
+    for (unsigned i = pb; i < pb + pn && ok; ++i) {
+      const unsigned d = (unsigned)text[i] - (unsigned)'0';
+      ok = d <= 9u;
+      v = v * 10 + d;
+    }
+  }
+  ok = ok && v >= 1;
+  *out = ok ? (int64_t)v : 0;
+  return ok;
+}
+
+__global__ __launch_bounds__(TPB) void k_parse_gff_lines(const uint8_t* __restrict__ text, const unsigned* __restrict__ nl_pos, unsigned* __restrict__ scalars,
+                                                         const uint32_t* __restrict__ is_row, const unsigned* __restrict__ block_offsets, FilterTable t0,
+                                                         FilterTable t1, FilterTable t2, GffOut out, unsigned cap, unsigned skip, unsigned n_total) {
+  static_assert(TPB == LIST_TPB, "list_first_item ranks a workgroup of LIST_TPB lines");
+  const unsigned n_lines = min(scalars[0], cap), n_rows = scalars[3];
+  const bool identity = n_rows == n_lines;  // no '#' line in the slab (the same for every thread of the launch)
+  const unsigned line = blockIdx.x * TPB + threadIdx.x;
+  const int lane = threadIdx.x & 63;
+  const unsigned c = line < n_lines ? is_row[line] : 0u;
+  const unsigned row = identity ? line : list_first_item(c, block_offsets);
+  auto group16 = [&](unsigned a) {  // an aligned 16-byte group of the slab; the last one byte by byte
+    uint4 v = {0, 0, 0, 0};
+    if (a + 16u <= n_total) {
+      v = *reinterpret_cast<const uint4*>(text + a);
+    } else {
+      unsigned* w = &v.x;
+      for (unsigned i = 0; a + i < n_total; ++i) w[i >> 2] |= (unsigned)text[a + i] << (8 * (i & 3));
+    }
+    return v;
+  };
+  bool score_ok = false, strand_ok = false, phase_ok = false, bad = false;
+  if (c) {
+    const unsigned begin = line ? nl_pos[line - 1] + 1 : skip;
+    unsigned end = nl_pos[line];
+    if (end > begin && text[end - 1] == '\r') --end;
+    unsigned fs[9];  // field f spans [fs[f], fs[f + 1] - 1); the ninth is whatever follows the eighth tab
+    int nf = 0;
+    fs[0] = begin;
+    for (unsigned a = begin & ~15u; a < end && nf < 8; a += 16) {
+      unsigned m = clip_mask16(eq_mask16(group16(a), 0x09090909u), a, begin, end);
+      while (m && nf < 8) {
+        fs[++nf] = a + (unsigned)__ffs((int)m);
+        m &= m - 1;
+      }
+    }
+    int64_t start = 0, stop = 0;
+    float score = 0.f;
+    int32_t strand = 0, phase = 0, slot[3] = {-1, -1, -1};
+    if (nf < 8) {
+      bad = true;  // an empty line, or fewer than nine fields
+      for (int k = 0; k < 9; ++k) fs[k] = begin;  // (the row's slots below get defined values)
+    } else {
+      slot[0] = table_claim(t0, text, fs[0], (int)(fs[1] - 1 - fs[0]));
+      slot[1] = table_claim(t1, text, fs[1], (int)(fs[2] - 1 - fs[1]));
+      slot[2] = table_claim(t2, text, fs[2], (int)(fs[3] - 1 - fs[2]));
+      bad |= !gff_position(text, fs[3], fs[4] - 1, n_total, &start);
+      bad |= !gff_position(text, fs[4], fs[5] - 1, n_total, &stop);
+      const int sl = (int)(fs[6] - 1 - fs[5]);
+      if (!(sl == 1 && text[fs[5]] == '.')) {
+        uint32_t bits;
+        if (exon::dec::parse_f32(reinterpret_cast<const char*>(text + fs[5]), sl, &bits)) {
+          score = __uint_as_float(bits);
+          score_ok = true;
+        } else {
+          bad = true;  // not a number, or one the host decides (more than 19 digits, inf / nan)
+        }
+      }
+      const unsigned sc = fs[7] - 1 - fs[6] == 1u ? text[fs[6]] : 0u;
+      strand_ok = sc == '+' || sc == '-';
+      strand = sc == '-' ? 1 : 0;
+      bad |= !(strand_ok || sc == '.' || sc == '?');
+      const unsigned pc = fs[8] - 1 - fs[7] == 1u ? text[fs[7]] : 0u;
+      phase_ok = pc - (unsigned)'0' <= 2u;
+      phase = phase_ok ? (int32_t)(pc - '0') : 0;
+      bad |= !(phase_ok || pc == '.');
+    }
+    for (int k = 0; k < 3; ++k) {
+      out.id[k][row] = slot[k];  // -1: no slot, k_remap_filters writes id 0 and compares nothing
+      out.off[k][row] = fs[k];
+      out.len[k][row] = nf < 8 ? 0u : fs[k + 1] - 1 - fs[k];
+    }
+    out.start[row] = start;
+    out.end[row] = stop;
+    out.score[row] = score;
+    out.strand[row] = strand;
+    out.phase[row] = phase;
+    if (!identity) out.vflags[row] = (uint8_t)((score_ok ? 1 : 0) | (strand_ok ? 2 : 0) | (phase_ok ? 4 : 0));
+  }
+  if (identity) {
+    const int64_t row0 = (int64_t)line - lane;
+    store_valid(out.score_valid, row0, n_rows, score_ok, lane);
+    store_valid(out.strand_valid, row0, n_rows, strand_ok, lane);
+    store_valid(out.phase_valid, row0, n_rows, phase_ok, lane);
+  }
+  const unsigned long long nb = __ballot(bad);
+  if (lane == 0 && nb) atomicAdd(&scalars[1], (unsigned)__popcll(nb));
+}
+
+// a ranked slab's validity bitmaps from the rows' flag bytes (nothing to do when the line kernel took the identity)
+__global__ __launch_bounds__(256) void k_gff_pack_valid(const unsigned* __restrict__ scalars, unsigned cap, const uint8_t* __restrict__ vflags,
+                                                        uint8_t* __restrict__ score_valid, uint8_t* __restrict__ strand_valid, uint8_t* __restrict__ phase_valid) {
+  const unsigned n = scalars[3];
+  if (n == min(scalars[0], cap)) return;
+  for (unsigned b = blockIdx.x * 256 + threadIdx.x; b * 8 < n; b += gridDim.x * 256) {
+    unsigned s = 0, t = 0, p = 0;
+    for (unsigned k = 0; k < 8 && b * 8 + k < n; ++k) {
+      const unsigned f = vflags[b * 8 + k];
+      s |= (f & 1u) << k;
+      t |= ((f >> 1) & 1u) << k;
+      p |= ((f >> 2) & 1u) << k;
+    }
+    score_valid[b] = (uint8_t)s;
+    strand_valid[b] = (uint8_t)t;
+    phase_valid[b] = (uint8_t)p;
+  }
+}
+
+}  // namespace
+
+struct exon_hip_gff_parser {
+  exon_hip_ctx* ctx;
+  PoolBufs bufs;
+  int64_t max_rows = 0;
+  LineIndex idx;  // scalars: [0] lines, [1] undecided, [2] consumed bytes, [3] rows
+  FilterTable tables[3] = {};
+  GffOut out{};
+  uint32_t* d_is_row = nullptr;
+  unsigned* d_blocks = nullptr;   // per-workgroup sums of is_row (scanned in place)
+  int32_t h_stat[3] = {0, 0, 0};  // the dictionaries' overflow flags after the last slab
+  explicit exon_hip_gff_parser(exon_hip_ctx* c) : ctx(c), bufs(c) {}
+};
+
+// names[i] -> id i of a device-built dictionary before the first slab: keys, ids, the text pool and the two claim counters
+static int seed_filter_table(exon_hip_ctx* ctx, PoolBufs& b, const FilterTable& t, const char* const* names, int32_t n) {
+  if (n <= 0) return EXON_HIP_OK;
+  if (n > EXON_HIP_MAX_GROUPS) return fail(ctx, EXON_HIP_EINVAL, "%d seed names: a device-built dictionary holds %d", n, EXON_HIP_MAX_GROUPS);
+  std::vector<unsigned long long> keys(FILTER_SLOTS, 0);
+  std::vector<int32_t> ids(FILTER_SLOTS, -1);
+  std::vector<uint32_t> toff(FILTER_SLOTS, 0), tlen(FILTER_SLOTS, 0);
+  std::string pool;
+  for (int32_t i = 0; i < n; ++i) {
+    const std::string nm = names[i] ? names[i] : "";
+    if (pool.size() + nm.size() > (size_t)FILTER_POOL) return fail(ctx, EXON_HIP_EINVAL, "seed names exceed the dictionary's %d-byte text pool", FILTER_POOL);
+    const unsigned long long h = fnv1a(reinterpret_cast<const uint8_t*>(nm.data()), (int)nm.size());
+    int slot = (int)(h & (FILTER_SLOTS - 1));
+    while (keys[(size_t)slot] != 0) {
+      if (keys[(size_t)slot] == h) return fail(ctx, EXON_HIP_EINVAL, "seed name '%s' is given twice (or hashes like another)", nm.c_str());
+      slot = (slot + 1) & (FILTER_SLOTS - 1);
+    }
+    keys[(size_t)slot] = h;
+    ids[(size_t)slot] = i;
+    toff[(size_t)slot] = (uint32_t)pool.size();
+    tlen[(size_t)slot] = (uint32_t)nm.size();
+    pool += nm;
+  }
+  const int32_t counters[4] = {n, (int32_t)pool.size(), 0, 0};
+  b.upload(t.keys, keys.data(), FILTER_SLOTS * 8);
+  b.upload(t.ids, ids.data(), FILTER_SLOTS * 4);
+  b.upload(t.text_off, toff.data(), FILTER_SLOTS * 4);
+  b.upload(t.text_len, tlen.data(), FILTER_SLOTS * 4);
+  b.upload(t.pool, pool.data(), pool.size());
+  b.upload(t.counters, counters, sizeof counters);
+  return EXON_HIP_OK;
+}
+
+extern "C" {
+
+int exon_hip_gff_parser_create(exon_hip_ctx* ctx, const char* const* seed_seqnames, int32_t n_seed, int64_t max_bytes, exon_hip_gff_parser** outp) {
+  if (!ctx || !outp || n_seed < 0 || (n_seed > 0 && !seed_seqnames) || max_bytes < 16) return fail(ctx, EXON_HIP_EINVAL, "exon_hip_gff_parser_create: bad argument");
+  if (max_bytes > 0xF0000000LL) return fail(ctx, EXON_HIP_EINVAL, "slab size must stay below 4 GiB (32-bit line offsets)");
+  *outp = nullptr;
+  exon_hip_gff_parser* p = new (std::nothrow) exon_hip_gff_parser(ctx);
+  if (!p) return fail(ctx, EXON_HIP_ENOMEM, "out of host memory");
+  p->max_rows = max_bytes / 16 + 1;  // a record has eight tabs and eight fields of a byte or more in front of its newline; a slab of
+                                     // shorter lines ('#' comments, empty lines) than that on average is handed to the host reader
+  hipSetDevice(ctx->device);
+  PoolBufs& b = p->bufs;
+  for (auto& t : p->tables) t = take_filter_table(b);
+  p->idx.alloc(b, max_bytes, p->max_rows);
+  const size_t r = (size_t)p->max_rows, rb = r / 8 + 64;
+  for (int k = 0; k < 3; ++k) {
+    p->out.id[k] = b.take<int32_t>(r * 4);
+    p->out.off[k] = b.take<uint32_t>(r * 4);
+    p->out.len[k] = b.take<uint32_t>(r * 4);
+  }
+  p->out.start = b.take<int64_t>(r * 8);
+  p->out.end = b.take<int64_t>(r * 8);
+  p->out.score = b.take<float>(r * 4);
+  p->out.strand = b.take<int32_t>(r * 4);
+  p->out.phase = b.take<int32_t>(r * 4);
+  p->out.score_valid = b.take<uint8_t>(rb);
+  p->out.strand_valid = b.take<uint8_t>(rb);
+  p->out.phase_valid = b.take<uint8_t>(rb);
+  p->out.vflags = b.take<uint8_t>(r + 64);
+  p->d_is_row = b.take<uint32_t>(r * 4);
+  p->d_blocks = b.take<unsigned>((r / LIST_TPB + 2) * 4);
+  int rc = EXON_HIP_OK;
+  if (b.status() == hipSuccess) rc = seed_filter_table(ctx, b, p->tables[0], seed_seqnames, n_seed);
+  if (rc) {
+    delete p;
+    return rc;
+  }
+  if (b.status() != hipSuccess) {
+    const std::string msg = hipGetErrorString(b.status());
+    delete p;
+    return fail(ctx, EXON_HIP_ENOMEM, "gff parser allocation: %s", msg.c_str());
+  }
+  *outp = p;
+  return EXON_HIP_OK;
+}
+
+int exon_hip_gff_parser_destroy(exon_hip_gff_parser* p) {
+  delete p;
+  return EXON_HIP_OK;
+}
+
+int exon_hip_gff_parser_parse(exon_hip_gff_parser* p, void* stream, const uint8_t* d_text, int64_t n_bytes, exon_hip_gff_columns* cols) {
+  if (!p || !cols || (n_bytes > 0 && !d_text)) return fail(p ? p->ctx : nullptr, EXON_HIP_EINVAL, "exon_hip_gff_parser_parse: NULL argument");
+  exon_hip_ctx* ctx = p->ctx;
+  memset(cols, 0, sizeof *cols);
+  if (n_bytes == 0) return EXON_HIP_OK;
+  LineIndex& idx = p->idx;
+  unsigned skip;
+  if (int rc = idx.align(ctx, &d_text, &n_bytes, &skip)) return rc;
+  hipStream_t s = pick_stream(ctx, stream);
+  idx.launch(s, d_text, n_bytes, skip);
+  hipLaunchKernelGGL(k_last_newline, dim3(1), dim3(1), 0, s, idx.nl, idx.d_scalars, idx.cap);
+  const int64_t row_bound = std::min<int64_t>(p->max_rows, n_bytes / 16 + 1);
+  const int pblocks = (int)((row_bound + TPB - 1) / TPB);
+  const GffOut& o = p->out;
+  hipLaunchKernelGGL(k_gff_classify, dim3(pblocks), dim3(TPB), 0, s, d_text, idx.nl, idx.d_scalars, (unsigned)row_bound, skip, p->d_is_row);
+  launch_list_scan(s, p->d_is_row, idx.d_scalars, (unsigned)row_bound, pblocks, p->d_blocks, idx.d_scalars + 3);
+  hipLaunchKernelGGL(k_parse_gff_lines, dim3(pblocks), dim3(TPB), 0, s, d_text, idx.nl, idx.d_scalars, p->d_is_row, p->d_blocks, p->tables[0], p->tables[1],
+                     p->tables[2], o, (unsigned)row_bound, skip, (unsigned)n_bytes);
+  hipLaunchKernelGGL(k_gff_pack_valid, dim3(std::min(pblocks, 1024)), dim3(256), 0, s, idx.d_scalars, (unsigned)row_bound, o.vflags, o.score_valid,
+                     o.strand_valid, o.phase_valid);
+  for (int k = 0; k < 3; ++k) {
+    hipLaunchKernelGGL(k_assign_filters, dim3(1), dim3(256), 0, s, d_text, p->tables[k]);
+    hipLaunchKernelGGL(k_remap_filters, dim3(std::min(pblocks, 4096)), dim3(TPB), 0, s, o.id[k], idx.d_scalars + 3, (unsigned)row_bound, p->tables[k], d_text,
+                       o.off[k], o.len[k], (const uint8_t*)nullptr);
+    HIP_TRY(ctx, hipMemcpyAsync(&p->h_stat[k], p->tables[k].counters + 2, 4, hipMemcpyDeviceToHost, s));  // overflow or collision
+  }
+  if (int rc = idx.read_back(ctx, s)) return rc;
+  const int64_t n_lines = idx.h_scalars[0];
+  cols->n_rows = idx.h_scalars[3];
+  cols->n_undecided = idx.h_scalars[1] + (n_lines > row_bound ? 1 : 0);  // more lines than the slab's bytes allow for records: the host reader's
+  for (int k = 0; k < 3; ++k) cols->n_undecided += p->h_stat[k] ? 1 : 0;  // a dictionary past its limits (or two texts that hash alike)
+  cols->consumed_bytes = idx.consumed(skip);
+  cols->seqname_id = o.id[0];
+  cols->source_id = o.id[1];
+  cols->type_id = o.id[2];
+  cols->start = o.start;
+  cols->end = o.end;
+  cols->score = o.score;
+  cols->score_valid = o.score_valid;
+  cols->strand_id = o.strand;
+  cols->strand_valid = o.strand_valid;
+  cols->phase_id = o.phase;
+  cols->phase_valid = o.phase_valid;
+  return EXON_HIP_OK;
+}
+
+// the dictionary of column 0 (seqname), 1 (source) or 2 (type) discovered so far, '\0'-separated in id order
+int exon_hip_gff_parser_names(exon_hip_gff_parser* p, int32_t column, char* buf, size_t cap, int32_t* n_names) {
+  if (!p || !n_names || column < 0 || column > 2) return fail(p ? p->ctx : nullptr, EXON_HIP_EINVAL, "exon_hip_gff_parser_names: bad argument");
+  static const char* const what[3] = {"seqnames", "sources", "feature types"};
+  return table_names(p->ctx, p->tables[column], what[column], buf, cap, n_names, false);
+}
+
+}  // extern "C"
+
+int exon_hip_gff_parser_names_so_far(exon_hip_gff_parser* p, int32_t column, char* buf, size_t cap, int32_t* n_names) {
+  if (!p || !n_names || column < 0 || column > 2) return fail(p ? p->ctx : nullptr, EXON_HIP_EINVAL, "exon_hip_gff_parser_names_so_far: bad argument");
+  return table_names(p->ctx, p->tables[column], "GFF names", buf, cap, n_names, true);
+}

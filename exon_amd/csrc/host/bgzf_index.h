@@ -39,6 +39,9 @@ struct BinningIndex {
   std::vector<std::string> names;  // tabix only (BAI names come from the BAM header)
   std::vector<RefIndex> refs;
   int min_shift = 14, depth = 5;
+  // tabix only: the preset the index was built with (TBI header: format, the 1-based sequence / begin / end columns, the
+  // comment character, lines skipped)
+  int32_t format = 0, col_seq = 0, col_beg = 0, col_end = 0, meta = 0, skip = 0;
 };
 
 namespace detail {
@@ -94,7 +97,12 @@ inline BinningIndex read_tabix(const std::string& path) {
   c.p = 4;
   BinningIndex idx;
   const int32_t n_ref = c.get<int32_t>();
-  for (int i = 0; i < 6; ++i) c.get<int32_t>();  // format, col_seq, col_beg, col_end, meta, skip
+  idx.format = c.get<int32_t>();
+  idx.col_seq = c.get<int32_t>();
+  idx.col_beg = c.get<int32_t>();
+  idx.col_end = c.get<int32_t>();
+  idx.meta = c.get<int32_t>();
+  idx.skip = c.get<int32_t>();
   const int32_t l_nm = c.get<int32_t>();
   if (c.p + (size_t)l_nm > raw.size()) throw std::runtime_error("truncated tabix names");
   size_t s = c.p;
@@ -192,11 +200,13 @@ class BgzfReader {
   }
   bool read_line(std::string* line) {
     line->clear();
+    terminated_ = false;
     for (;;) {
       if (pos_ == block_.size() && !next_block()) return !line->empty();
       const uint8_t* p = block_.data() + pos_;
       const uint8_t* nl = static_cast<const uint8_t*>(memchr(p, '\n', block_.size() - pos_));
       if (nl) {
+        terminated_ = true;
         line->append(reinterpret_cast<const char*>(p), nl - p);
         pos_ += (nl - p) + 1;
         if (!line->empty() && line->back() == '\r') line->pop_back();
@@ -206,6 +216,8 @@ class BgzfReader {
       pos_ = block_.size();
     }
   }
+  // did the line read_line returned last end in '\n' (false: the data ended first)?
+  bool last_line_terminated() const { return terminated_; }
   bool read_exact(uint8_t* dst, size_t n) {
     size_t got = 0;
     while (got < n) {
@@ -257,7 +269,7 @@ class BgzfReader {
   bool z_init_ = false;
   size_t pos_ = 0;
   int64_t block_off_ = 0, block_csize_ = 0;
-  bool eof_ = false;
+  bool eof_ = false, terminated_ = false;
 };
 
 }  // namespace exon

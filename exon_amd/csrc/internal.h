@@ -107,6 +107,7 @@ constexpr int EXON_DICT_POOL = 1 << 20;
 constexpr size_t EXON_DICT_NAMES_CAP = (size_t)EXON_DICT_POOL + EXON_HIP_MAX_GROUPS;
 int exon_hip_vcf_parser_filters_so_far(exon_hip_vcf_parser* p, char* buf, size_t cap, int32_t* n_filters);
 int exon_hip_vcf_parser_info_values_so_far(exon_hip_vcf_parser* p, int32_t key, char* buf, size_t cap, int32_t* n_values);
+int exon_hip_gff_parser_names_so_far(exon_hip_gff_parser* p, int32_t column, char* buf, size_t cap, int32_t* n_names);
 int exon_hip_bcf_parser_filters_so_far(exon_hip_bcf_parser* p, int32_t* lists, int32_t* counts, int32_t cap, int32_t* n_filters);
 const unsigned* exon_hip_sam_parser_newlines(exon_hip_sam_parser* p);      // gpu_parse.hip: the same for SAM lines      // gpu_parse.hip: byte offset of every line's '\n' in the aligned slab
 const uint32_t* exon_hip_bam_parser_row_records(exon_hip_bam_parser* p);

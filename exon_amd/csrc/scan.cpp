@@ -21,14 +21,15 @@
 #include "host/bcf.h"
 #include "host/cram.h"
 #include "host/formats.h"
+#include "host/gff.h"
 #include "host/parallel.h"
 #include "internal.h"
 
 // The device parser of a GPU-decoded scan: whichever handle its format uses, created by the scan's first GPU-parsed consume
 struct DeviceParser {
   int format = 0;
-  void* h = nullptr;  // exon_hip_{vcf,bcf,bam,sam,fastq}_parser of `format`
-  // the FILTER dictionary (and VCF's String INFO dictionaries) of the scan are the device parser's
+  void* h = nullptr;  // exon_hip_{vcf,bcf,bam,sam,fastq,gff}_parser of `format`
+  // the FILTER dictionary (and VCF's String INFO dictionaries; GFF: seqname / source / type) of the scan are the device parser's
   bool owns_names = false;
   template <class T>
   T* as() const { return static_cast<T*>(h); }
@@ -39,6 +40,7 @@ struct DeviceParser {
       case EXON_HIP_FORMAT_BAM: exon_hip_bam_parser_destroy(as<exon_hip_bam_parser>()); break;
       case EXON_HIP_FORMAT_SAM: exon_hip_sam_parser_destroy(as<exon_hip_sam_parser>()); break;
       case EXON_HIP_FORMAT_FASTQ: exon_hip_fastq_parser_destroy(as<exon_hip_fastq_parser>()); break;
+      case EXON_HIP_FORMAT_GFF: exon_hip_gff_parser_destroy(as<exon_hip_gff_parser>()); break;
     }
     h = nullptr;
     owns_names = false;
@@ -60,6 +62,7 @@ struct exon_hip_scan {
   bool gpu_inflated = false;  // the last GPU-parsed consume also inflated BGZF blocks on the device
   bool gpu_decoded = false;   // the last consume decoded every record on the device (no host fallback)
   exon::Dictionary gpu_filter_dict;       // names fetched from the parser after the consume
+  exon::Dictionary gpu_gff_dicts[3];      // GFF: seqname / source / type, likewise
   std::unique_ptr<exon::BatchReader> reader;  // of `format`
   int64_t rows = 0;
   exon::Dictionary bam_dict_view;  // reference names as a dictionary (ids = header order)
@@ -78,6 +81,7 @@ struct exon_hip_scan {
   exon::BAMBatchReader* bam() const { return reader_if<exon::BAMBatchReader>(EXON_HIP_FORMAT_BAM); }
   exon::SAMBatchReader* sam() const { return reader_if<exon::SAMBatchReader>(EXON_HIP_FORMAT_SAM); }
   exon::FASTQBatchReader* fastq() const { return reader_if<exon::FASTQBatchReader>(EXON_HIP_FORMAT_FASTQ); }
+  exon::GFFBatchReader* gff() const { return reader_if<exon::GFFBatchReader>(EXON_HIP_FORMAT_GFF); }
   // VCF and BCF: chrom / pos / qual / filter + typed INFO columns (else BAM / SAM / CRAM's flag / mapq / ref / start / end)
   bool vcf_like() const { return format == EXON_HIP_FORMAT_VCF || format == EXON_HIP_FORMAT_BCF; }
   const std::vector<exon::InfoSpec>& info_specs() const { return vcf() ? vcf()->info_specs : bcf()->info_specs; }
@@ -109,6 +113,8 @@ struct GpuExporter {
   int64_t emitted = 0;                       // rows handed to the queue so far
   std::vector<std::string> final_filters;    // the FILTER dictionary when the producer has finished
   std::vector<std::vector<std::string>> final_info_names;  // ... and the String INFO keys' dictionaries
+  std::vector<std::string> final_gff_names[3];              // GFF: the seqname / source / type dictionaries
+  bool has_gff_names = false;
   bool decoded_on_gpu = false, inflated_on_gpu = false;
   // the host reader that takes over when the device hands the file back.  It lives HERE while the producer thread runs: the
   // scan's own reader (which exon_hip_scan_schema / _dictionary_* read from the consumer's thread) is never touched by the
@@ -241,6 +247,10 @@ static const char* unsupported_codec(const char* path) {
 static bool info_kind_decoded_on_gpu(const exon_hip_scan* s, char kind) { return exon::info_kind_on_device(kind) || (kind == 's' && s->format == EXON_HIP_FORMAT_VCF); }
 
 static exon::Dictionary* dict_of(exon_hip_scan* s, int col) {
+  if (exon::GFFBatchReader* g = s->gff()) {
+    if (col >= 0 && col < 3) return s->parser.owns_names ? &s->gpu_gff_dicts[col] : &g->dicts[col];
+    return col == 6 ? &g->strand_dict : col == 7 ? &g->phase_dict : nullptr;
+  }
   if (!s->vcf_like()) {
     const bool refs = s->format == EXON_HIP_FORMAT_BAM || s->format == EXON_HIP_FORMAT_SAM || s->format == EXON_HIP_FORMAT_CRAM;
     return refs && col == 2 ? &s->bam_dict_view : nullptr;
@@ -283,8 +293,8 @@ static std::unique_ptr<exon::BatchReader> open_reader(const exon_hip_scan& s, De
     return cfg;
   };
   const int64_t bs = s.opt.batch_size > 0 ? s.opt.batch_size : exon::DEFAULT_BATCH_SIZE;
-  exon::RegionFilter rf = s.region;  // index chunks are planned for VCF (tabix) and BAM (BAI)
-  rf.use_index = rf.use_index && (s.format == EXON_HIP_FORMAT_VCF || s.format == EXON_HIP_FORMAT_BAM);
+  exon::RegionFilter rf = s.region;  // index chunks are planned for VCF and GFF (tabix) and BAM (BAI)
+  rf.use_index = rf.use_index && (s.format == EXON_HIP_FORMAT_VCF || s.format == EXON_HIP_FORMAT_BAM || s.format == EXON_HIP_FORMAT_GFF);
   exon::VCFConfig vc;
   vc.batch_size = bs;
   vc.info_field = s.info_field_s;
@@ -316,6 +326,19 @@ static std::unique_ptr<exon::BatchReader> open_reader(const exon_hip_scan& s, De
       exon::FASTAConfig cfg;
       cfg.batch_size = bs;
       return std::unique_ptr<exon::BatchReader>(new exon::FASTABatchReader(s.path, c, cfg));
+    }
+    case EXON_HIP_FORMAT_GFF: {
+      exon::GFFConfig fresh;
+      fresh.batch_size = bs;
+      fresh.filter = rf;
+      fresh.reference_block_quirk = reference_tail_quirk(rf);
+      exon::GFFConfig cfg = config(s.gff(), fresh);
+      cfg.defer_decode = device;
+      std::unique_ptr<exon::GFFBatchReader> r(new exon::GFFBatchReader(s.path, c, cfg));
+      // names interned into the reader being replaced (a region plan's contig) keep their ids: a plan may hold one already
+      if (const exon::GFFBatchReader* old = s.gff())
+        for (int k = 0; k < 3; ++k) r->dicts[k].names = old->dicts[k].names;
+      return r;
     }
   }
   throw std::runtime_error("unknown format " + std::to_string(s.format));
@@ -356,6 +379,8 @@ int exon_hip_scan_open(const char* path, const exon_hip_scan_options* o, exon_hi
       rf.use_index = o->use_index != 0;
     }
     s->region = rf;
+    if (o->projection && o->format == EXON_HIP_FORMAT_GFF)
+      return fail(nullptr, EXON_HIP_EUNSUPPORTED, "exon_hip_scan_options.projection: the GFF `attributes` column (Map<Utf8, List<Utf8>>) is not built");
     if (o->projection && o->format != EXON_HIP_FORMAT_VCF && o->format != EXON_HIP_FORMAT_BAM && o->format != EXON_HIP_FORMAT_BCF && o->format != EXON_HIP_FORMAT_SAM)
       return fail(nullptr, EXON_HIP_EUNSUPPORTED, "exon_hip_scan_options.projection: the id / ref / alt (/ info / formats) and name / cigar / sequence / quality_score columns are built for VCF, BCF, BAM and SAM scans");
     switch (o->format) {
@@ -388,6 +413,11 @@ int exon_hip_scan_open(const char* path, const exon_hip_scan_options* o, exon_hi
       case EXON_HIP_FORMAT_FASTQ:
         s->gpu_parse = o->gpu_parse != 0;
         break;
+      case EXON_HIP_FORMAT_GFF:
+        // as VCF text: a region rides along as a row mask; with use_index only the tabix chunks' BGZF blocks are shipped.  The
+        // reference's block-range quirk is a property of its opener's byte range: the host reader reproduces it
+        s->gpu_parse = o->gpu_parse != 0 && (!rf.use_index || (rf.active && wants_gpu_inflate(o, path))) && !reference_tail_quirk(rf);
+        break;
       case EXON_HIP_FORMAT_CRAM:
       case EXON_HIP_FORMAT_FASTA:
         break;
@@ -395,6 +425,8 @@ int exon_hip_scan_open(const char* path, const exon_hip_scan_options* o, exon_hi
         return fail(nullptr, EXON_HIP_EINVAL, "unknown format %d", o->format);
     }
     s->reader = open_reader(*s, s->gpu_parse ? Decode::Device : Decode::Host);
+    // GFF has no header to number its seqnames: the device parser is seeded with the region's, so that the row mask knows its id
+    if (s->gpu_parse && s->gff() && rf.active) s->gff()->dicts[0].lookup_or_insert(rf.region.name.data(), rf.region.name.size());
     if (s->gpu_parse && s->vcf_like()) {
       bool string_info = false;
       for (const auto& sp : s->info_specs()) string_info |= !info_kind_decoded_on_gpu(s.get(), sp.kind);
@@ -408,6 +440,8 @@ int exon_hip_scan_open(const char* path, const exon_hip_scan_options* o, exon_hi
       if (const std::vector<std::string>* refs = contig_names(s.get())) s->bam_dict_view.names = *refs;
     *out = s.release();
     return EXON_HIP_OK;
+  } catch (const exon::UnsupportedError& e) {
+    return fail(nullptr, EXON_HIP_EUNSUPPORTED, "%s", e.what());
   } catch (const std::exception& e) {
     return fail(nullptr, EXON_HIP_EINVAL, "%s", e.what());
   }
@@ -433,6 +467,8 @@ int exon_hip_scan_next(exon_hip_scan* s, struct ArrowArray* out) {
     if (!s->reader->read_batch(out)) return 1;
     s->rows += out->length;
     return EXON_HIP_OK;
+  } catch (const exon::UnsupportedError& e) {
+    return fail(nullptr, EXON_HIP_EUNSUPPORTED, "%s", e.what());
   } catch (const std::exception& e) {
     return fail(nullptr, EXON_HIP_EINVAL, "%s", e.what());
   }
@@ -450,7 +486,7 @@ int exon_hip_scan_dictionary_intern(exon_hip_scan* s, int32_t column, const char
   if (!s || !name || !id) return fail(nullptr, EXON_HIP_EINVAL, "NULL argument");
   exon::Dictionary* d = dict_of(s, column);
   if (!d) return fail(nullptr, EXON_HIP_EINVAL, "column %d is not dictionary-encoded", column);
-  if (s->format == EXON_HIP_FORMAT_BAM || s->format == EXON_HIP_FORMAT_SAM || s->format == EXON_HIP_FORMAT_CRAM) {  // reference ids are fixed by the header
+  if (s->format == EXON_HIP_FORMAT_BAM || s->format == EXON_HIP_FORMAT_SAM || s->format == EXON_HIP_FORMAT_CRAM || (s->gff() && column >= 6)) {  // ids fixed by the header (GFF strand / phase: by the format)
     *id = d->find(name);
     return EXON_HIP_OK;
   }
@@ -474,7 +510,7 @@ int exon_hip_scan_rows(exon_hip_scan* s, int64_t* rows) {
 
 int exon_hip_scan_index_chunks(exon_hip_scan* s, int32_t* n) {
   if (!s || !n) return fail(nullptr, EXON_HIP_EINVAL, "NULL argument");
-  *n = s->vcf() ? s->vcf()->n_chunks : s->bam() ? s->bam()->n_chunks : -1;
+  *n = s->vcf() ? s->vcf()->n_chunks : s->bam() ? s->bam()->n_chunks : s->gff() ? s->gff()->n_chunks : -1;
   return EXON_HIP_OK;
 }
 
@@ -505,7 +541,7 @@ int exon_hip_scan_bind_ctx(exon_hip_scan* s, exon_hip_ctx* ctx) {
   if (!s || !ctx) return fail(ctx, EXON_HIP_EINVAL, "exon_hip_scan_bind_ctx: NULL argument");
   if (s->exporter) return fail(ctx, EXON_HIP_ESTATE, "the scan is bound to a context already");
   if (s->format == EXON_HIP_FORMAT_FASTA || s->format == EXON_HIP_FORMAT_CRAM)
-    return fail(ctx, EXON_HIP_EUNSUPPORTED, "batches from the GPU pipeline: VCF, BCF, BAM, SAM and FASTQ scans (FASTA / CRAM batches come from the host readers)");
+    return fail(ctx, EXON_HIP_EUNSUPPORTED, "batches from the GPU pipeline: VCF, BCF, BAM, SAM, FASTQ and GFF scans (FASTA / CRAM batches come from the host readers)");
   if (!s->gpu_parse)  // not opened with gpu_parse, or String / list-valued INFO keys were named: the host reader builds those columns
     return fail(ctx, EXON_HIP_EUNSUPPORTED, "this scan's batches come from the host reader (opened without gpu_parse, or it names INFO keys only the host reader builds)");
   if (s->rows != 0) return fail(ctx, EXON_HIP_ESTATE, "the scan has been read from already");
@@ -1752,12 +1788,17 @@ static std::vector<ChunkRange> plan_chunk_ranges(const std::string& path, const 
 // the pushed-down region as (dictionary id, [a, b]) for the device row mask; id < 0: no row can match
 static void region_target(const exon_hip_scan* scan, int32_t* id, int64_t* a, int64_t* b, bool* range_form) {
   const exon::Region& rg = scan->region.region;
+  *a = rg.start;
+  *b = rg.end;
+  if (exon::GFFBatchReader* g = scan->gff()) {  // the reader's filter tests the start alone (batch_reader.rs:76-97); ids: the parser's seeds
+    *id = g->dicts[0].find(rg.name);
+    *range_form = false;
+    return;
+  }
   const std::vector<std::string>* names = contig_names(scan);
   *id = -1;
   for (size_t i = 0; i < names->size(); ++i)
     if ((*names)[i] == rg.name) *id = (int32_t)i;
-  *a = rg.start;
-  *b = rg.end;
   *range_form = !scan->vcf_like();
 }
 
@@ -1794,6 +1835,21 @@ static int gpu_filter_names(exon_hip_scan* scan, std::vector<std::string>* names
       names->emplace_back(buf.data() + o);
       o += names->back().size() + 1;
     }
+  }
+  return rc;
+}
+
+// GFF: the device parser's dictionary of column 0 (seqname), 1 (source) or 2 (type), names in id order
+static int gpu_gff_names(exon_hip_scan* scan, int column, std::vector<std::string>* names, bool so_far) {
+  names->clear();
+  int32_t nn = 0;
+  std::vector<char> buf(EXON_DICT_NAMES_CAP);
+  const int rc = (so_far ? exon_hip_gff_parser_names_so_far : exon_hip_gff_parser_names)(scan->parser.as<exon_hip_gff_parser>(), column, buf.data(), buf.size(), &nn);
+  if (rc) return rc;
+  size_t o = 0;
+  for (int32_t i = 0; i < nn; ++i) {
+    names->emplace_back(buf.data() + o);
+    o += names->back().size() + 1;
   }
   return rc;
 }
@@ -2227,12 +2283,15 @@ static int export_slab(exon_hip_scan* scan, const exon_hip_column* sc, int64_t n
   const double tc0 = now_s();
   const bool vcf_like = scan->vcf_like();
   const std::vector<exon::InfoSpec>* specs = vcf_like ? &scan->info_specs() : nullptr;
-  const int n_cols = vcf_like ? 4 + (int)specs->size() : 5;
+  const bool gff = scan->gff() != nullptr;
+  const int n_cols = vcf_like ? 4 + (int)specs->size() : gff ? 8 : 5;
   // element widths in the scan's column order (0 = no values: a Flag, whose bitmap is its value)
   std::vector<int> elem((size_t)n_cols, 4);
   if (vcf_like) {
     elem[1] = 8;
     for (size_t k = 0; k < specs->size(); ++k) elem[4 + k] = (*specs)[k].kind == 'b' ? 0 : 4;
+  } else if (gff) {
+    elem[3] = elem[4] = 8;
   } else {
     elem[1] = 1;
     elem[3] = elem[4] = 8;
@@ -2301,6 +2360,9 @@ static int export_slab(exon_hip_scan* scan, const exon_hip_column* sc, int64_t n
     const int rc = gpu_info_names(scan, &info_names, true);
     if (rc) return rc;
   }
+  std::vector<std::string> gff_names[3];
+  for (int k = 0; gff && k < 3; ++k)
+    if (const int rc = gpu_gff_names(scan, k, &gff_names[k], true)) return rc;
   g_t_names += now_s() - tn0;
   // the dictionaries of this slab's batches: built once, shared by every batch's column
   auto dicts_p = std::make_shared<std::vector<std::shared_ptr<const exon::SharedUtf8>>>((size_t)n_cols);
@@ -2310,7 +2372,9 @@ static int export_slab(exon_hip_scan* scan, const exon_hip_column* sc, int64_t n
     else if (vcf_like && c == 3) dicts[(size_t)c] = std::make_shared<const exon::SharedUtf8>(filters);
     else if (scan->vcf() && c >= 4 && (size_t)(c - 4) < info_names.size() && (*specs)[(size_t)(c - 4)].kind == 's')
       dicts[(size_t)c] = std::make_shared<const exon::SharedUtf8>(info_names[(size_t)(c - 4)]);
-    else if (!vcf_like && c == 2) dicts[(size_t)c] = std::make_shared<const exon::SharedUtf8>(scan->bam_dict_view.names);
+    else if (gff && c < 3) dicts[(size_t)c] = std::make_shared<const exon::SharedUtf8>(gff_names[c]);
+    else if (gff && (c == 6 || c == 7)) dicts[(size_t)c] = std::make_shared<const exon::SharedUtf8>(c == 6 ? exon::gff_strand_names() : exon::gff_phase_names());
+    else if (!vcf_like && !gff && c == 2) dicts[(size_t)c] = std::make_shared<const exon::SharedUtf8>(scan->bam_dict_view.names);
   }
   auto dict_of_col = [&](int c) -> struct ArrowArray* { return dicts[(size_t)c] ? exon::shared_utf8_array(dicts[(size_t)c]) : nullptr; };
   if (as_views) {
@@ -2368,7 +2432,7 @@ static int export_slab(exon_hip_scan* scan, const exon_hip_column* sc, int64_t n
     for (int c = 0; c < n_cols; ++c) {
       if (elem[(size_t)c] == 8) prim(c, int64_t());
       else if (elem[(size_t)c] == 1) prim(c, uint8_t());
-      else if (elem[(size_t)c] == 4 && vcf_like && (c == 2 || (c >= 4 && (*specs)[(size_t)(c - 4)].kind == 'f'))) prim(c, float());
+      else if (elem[(size_t)c] == 4 && ((gff && c == 5) || (vcf_like && (c == 2 || (c >= 4 && (*specs)[(size_t)(c - 4)].kind == 'f'))))) prim(c, float());
       else if (elem[(size_t)c] == 4) prim(c, int32_t());
       else {  // Flag -> Boolean: true where present, NULL elsewhere
         std::vector<uint8_t> v((size_t)n);
@@ -2457,6 +2521,7 @@ static int64_t data_offset(const exon_hip_scan* scan) {
     case EXON_HIP_FORMAT_BCF: return scan->bcf()->data_offset();
     case EXON_HIP_FORMAT_BAM: return scan->bam()->data_offset();
     case EXON_HIP_FORMAT_SAM: return scan->sam()->data_offset();
+    case EXON_HIP_FORMAT_GFF: return scan->gff()->data_offset();  // (no header: '#' lines are the device parser's to skip)
   }
   return 0;  // FASTQ: no header
 }
@@ -2467,6 +2532,7 @@ static std::unique_ptr<exon::ByteSource> take_text_stream(exon_hip_scan* scan, s
     case EXON_HIP_FORMAT_VCF: return scan->vcf()->take_stream(carry);
     case EXON_HIP_FORMAT_SAM: return scan->sam()->take_stream(carry);
     case EXON_HIP_FORMAT_FASTQ: return scan->fastq()->take_stream(carry);
+    case EXON_HIP_FORMAT_GFF: return scan->gff()->take_stream(carry);
   }
   return nullptr;  // (BAM and BCF are BGZF by definition)
 }
@@ -2526,8 +2592,16 @@ static int create_parser(exon_hip_scan* scan, exon_hip_ctx* ctx, int64_t max_tex
       p.h = h;
       break;
     }
+    case EXON_HIP_FORMAT_GFF: {  // seeded with the names interned so far (a region's contig): their ids stay
+      std::vector<const char*> names;
+      for (const auto& c : scan->gff()->dicts[0].names) names.push_back(c.c_str());
+      exon_hip_gff_parser* h = nullptr;
+      rc = exon_hip_gff_parser_create(ctx, names.data(), (int32_t)names.size(), max_text_bytes, &h);
+      p.h = h;
+      break;
+    }
   }
-  p.owns_names = p.h && scan->vcf_like();
+  p.owns_names = p.h && (scan->vcf_like() || scan->gff());
   return rc;
 }
 
@@ -2614,6 +2688,28 @@ static int parse_slab(exon_hip_scan* scan, hipStream_t hs, const uint8_t* d_text
       p->pos_valid = cols.pos_valid;
       return EXON_HIP_OK;
     }
+    case EXON_HIP_FORMAT_GFF: {
+      exon_hip_gff_columns cols;
+      rc = exon_hip_gff_parser_parse(scan->parser.as<exon_hip_gff_parser>(), hs, d_text, (int64_t)n, &cols);
+      if (rc) return rc;
+      p->n_undecided = cols.n_undecided;
+      p->consumed = cols.consumed_bytes;
+      p->n_rows = cols.n_rows;
+      sc[0].values = cols.seqname_id;
+      sc[1].values = cols.source_id;
+      sc[2].values = cols.type_id;
+      sc[3].values = cols.start;
+      sc[4].values = cols.end;
+      sc[5].values = cols.score;
+      sc[5].validity = cols.score_valid;
+      sc[6].values = cols.strand_id;
+      sc[6].validity = cols.strand_valid;
+      sc[7].values = cols.phase_id;
+      sc[7].validity = cols.phase_valid;
+      p->id_col = cols.seqname_id;
+      p->c_start = p->c_end = cols.start;
+      return EXON_HIP_OK;
+    }
     default: {  // FASTQ
       rc = exon_hip_fastq_parser_parse(scan->parser.as<exon_hip_fastq_parser>(), hs, d_text, (int64_t)n, final ? 1 : 0, &p->views);
       if (rc) return rc;
@@ -2664,7 +2760,7 @@ static int consume_text_gpu(exon_hip_stream* st, exon_hip_scan* scan, int64_t* r
   // ---- where the slabs come from: the index chunks' blocks, the BGZF file, a plain-gzip file, or the reader's text stream ----
   const bool binary = scan->bam() || scan->bcf();  // BGZF by definition: inflated on the device or decoded on the host
   const bool filtered = scan->region.active && !scan->fastq();
-  const bool indexed = filtered && scan->region.use_index && (scan->vcf() || scan->bam());
+  const bool indexed = filtered && scan->region.use_index && (scan->vcf() || scan->bam() || scan->gff());
   const bool device_inflate = gpu_inflate_enabled() && scan->opt.compression != EXON_HIP_COMPRESSION_NONE;
   const bool bgzf = device_inflate && exon::BgzfParallelSource::is_bgzf(scan->path) && (indexed || data_offset(scan) >= 0);
   if ((binary || indexed) && !bgzf) return 1;
@@ -2691,7 +2787,7 @@ static int consume_text_gpu(exon_hip_stream* st, exon_hip_scan* scan, int64_t* r
   std::vector<ChunkRange> ranges;
   if (indexed) {
     try {
-      ranges = plan_chunk_ranges(scan->path, scan->vcf() ? scan->vcf()->planned_chunks : scan->bam()->planned_chunks);
+      ranges = plan_chunk_ranges(scan->path, scan->vcf() ? scan->vcf()->planned_chunks : scan->bam() ? scan->bam()->planned_chunks : scan->gff()->planned_chunks);
     } catch (const std::exception& e) {
       return fail(ctx, EXON_HIP_EINVAL, "%s", e.what());
     }
@@ -2827,7 +2923,7 @@ static int consume_text_gpu(exon_hip_stream* st, exon_hip_scan* scan, int64_t* r
     HIP_TRY(ctx, hipMemcpy(&kept, scan->d_region_pass, 8, hipMemcpyDeviceToHost));
     total = (int64_t)kept;
   }
-  if (rc == EXON_HIP_OK && scan->parser.owns_names) {  // FILTER dictionary -> scan (names in id order)
+  if (rc == EXON_HIP_OK && scan->vcf_like() && scan->parser.owns_names) {  // FILTER dictionary -> scan (names in id order)
     std::vector<std::string> names;
     rc = gpu_filter_names(scan, &names);
     if (!rc) {
@@ -2846,6 +2942,15 @@ static int consume_text_gpu(exon_hip_stream* st, exon_hip_scan* scan, int64_t* r
           if (scan->vcf()->info_specs[k].kind == 's') scan->vcf()->info_dicts[k].names.swap(info_names[k]);
       }
     }
+  }
+  if (rc == EXON_HIP_OK && scan->gff() && scan->parser.owns_names) {  // GFF: the three dictionaries the device built -> scan
+    std::vector<std::string> names[3];
+    for (int k = 0; k < 3 && !rc; ++k) rc = gpu_gff_names(scan, k, &names[k], false);
+    for (int k = 0; k < 3 && !rc; ++k) {
+      if (scan->exporter) scan->exporter->final_gff_names[k].swap(names[k]);
+      else scan->gpu_gff_dicts[k].names.swap(names[k]);
+    }
+    if (!rc && scan->exporter) scan->exporter->has_gff_names = true;
   }
   if (rc == EXON_HIP_OK) {
     if (scan->exporter) {
@@ -2873,7 +2978,7 @@ static int consume_scan_impl(exon_hip_stream* st, exon_hip_scan* scan, int64_t* 
 
 // column of the scan that holds the contig / reference dictionary a region is named in
 static int region_dict_column(const exon_hip_scan* s) {
-  return (s->format == EXON_HIP_FORMAT_VCF || s->format == EXON_HIP_FORMAT_BCF) ? 0 : 2;
+  return (s->format == EXON_HIP_FORMAT_VCF || s->format == EXON_HIP_FORMAT_BCF || s->format == EXON_HIP_FORMAT_GFF) ? 0 : 2;
 }
 
 }  // extern "C"
@@ -2937,6 +3042,9 @@ static void gpu_export_producer(exon_hip_scan* scan) {
         }
         if (push_batch(ex, out, out->length)) break;  // (the consumer closed the scan)
       }
+    } catch (const exon::UnsupportedError& e) {
+      rc = EXON_HIP_EUNSUPPORTED;
+      err = e.what();
     } catch (const std::exception& e) {
       rc = EXON_HIP_EINVAL;
       err = e.what();
@@ -2984,15 +3092,21 @@ static int gpu_next(exon_hip_scan* s, struct ArrowArray* out) {
     // last batches were built with; every batch carries its dictionary values itself, so nothing emitted earlier depends on it)
     s->reader = std::move(ex->fallback);
     if (s->vcf_like()) s->gpu_filter_dict.names = s->host_filter_dict().names;
+    if (exon::GFFBatchReader* g = s->gff())
+      for (int k = 0; k < 3; ++k) s->gpu_gff_dicts[k].names = g->dicts[k].names;
     ex->handed_over = false;
     ex->final_filters.clear();
     ex->final_info_names.clear();
+    ex->has_gff_names = false;
   }
   if (ex->rc) return fail(ex->ctx, ex->rc, "%s", ex->err.c_str());
   if (!ex->final_filters.empty()) s->gpu_filter_dict.names.swap(ex->final_filters);
   if (exon::VCFBatchReader* vcf = s->vcf())
     for (size_t k = 0; k < ex->final_info_names.size() && k < vcf->info_dicts.size(); ++k)
       if (vcf->info_specs[k].kind == 's') vcf->info_dicts[k].names.swap(ex->final_info_names[k]);
+  if (ex->has_gff_names)
+    for (int k = 0; k < 3; ++k) s->gpu_gff_dicts[k].names.swap(ex->final_gff_names[k]);
+  ex->has_gff_names = false;
   s->gpu_decoded = ex->decoded_on_gpu;
   s->gpu_inflated = ex->inflated_on_gpu;
   return 1;

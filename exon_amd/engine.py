@@ -551,6 +551,67 @@ class VCFParser:
             self.h = None
 
 
+class GFFParser:
+    """GFF3 record parsing on the GPU (exon_hip_gff_parser_*): text slab in HBM -> the GFF device layout in HBM.  The seqname, source
+    and type dictionaries grow across slabs; `seed_seqnames` take the ids 0 .. len - 1 before the first slab."""
+
+    def __init__(self, ctx, seed_seqnames=(), max_slab_bytes=64 << 20):
+        self.ctx = ctx
+        names = (C.c_char_p * max(len(seed_seqnames), 1))(*[c.encode() for c in seed_seqnames])
+        h = C.c_void_p()
+        ctx._check(ctx.lib.exon_hip_gff_parser_create(ctx.h, names, len(seed_seqnames), max_slab_bytes, C.byref(h)))
+        self.h = h
+
+    def parse_device(self, d_text, n_bytes, stream=None):
+        cols = L.GFFColumns()
+        ptr = d_text.ptr if isinstance(d_text, DeviceBuffer) else int(d_text)
+        self.ctx._check(self.ctx.lib.exon_hip_gff_parser_parse(self.h, stream, ptr, n_bytes, C.byref(cols)))
+        return cols
+
+    def parse_host(self, text, misalign=0):
+        """Test helper: copy `text` to HBM (`misalign` bytes past a 16-byte boundary), parse, bring the columns back as numpy arrays
+        (none of them when the device left a row undecided)."""
+        buf = np.frombuffer(text, np.uint8)
+        d = self.ctx.to_device(np.concatenate([np.full(misalign, 10, np.uint8), buf, np.zeros(64, np.uint8)]))
+        cols = self.parse_device(d.ptr + misalign, len(buf))
+        n = cols.n_rows if cols.n_undecided == 0 else 0
+        nb = (n + 7) // 8
+
+        def get(ptr, dtype, count):
+            out = np.empty(count, dtype)
+            if count:
+                self.ctx._check(self.ctx.lib.exon_hip_memcpy_d2h(self.ctx.h, _np_ptr(out), ptr, out.nbytes, None))
+            return out
+
+        res = {"n_rows": cols.n_rows, "n_undecided": cols.n_undecided, "consumed_bytes": cols.consumed_bytes}
+        for name in ("seqname_id", "source_id", "type_id", "strand_id", "phase_id"):
+            res[name] = get(getattr(cols, name), np.int32, n)
+        for name in ("start", "end"):
+            res[name] = get(getattr(cols, name), np.int64, n)
+        res["score"] = get(cols.score, np.float32, n)
+        for name in ("score_valid", "strand_valid", "phase_valid"):
+            res[name] = get(getattr(cols, name), np.uint8, nb)
+        return res
+
+    def names(self, column):
+        """The dictionary of column 0 (seqname), 1 (source) or 2 (type) discovered so far, in id order."""
+        n = C.c_int32()
+        buf = C.create_string_buffer((1 << 20) + 4096)
+        self.ctx._check(self.ctx.lib.exon_hip_gff_parser_names(self.h, column, buf, len(buf), C.byref(n)))
+        names, o = [], 0
+        raw = buf.raw
+        for _ in range(n.value):
+            e = raw.index(b"\0", o)
+            names.append(raw[o:e].decode(errors="replace"))
+            o = e + 1
+        return names
+
+    def close(self):
+        if self.h:
+            self.ctx.lib.exon_hip_gff_parser_destroy(self.h)
+            self.h = None
+
+
 class BAMParser:
     """BAM record splitting + field extraction on the GPU (exon_hip_bam_parser_*): inflated bytes in HBM -> columns."""
 

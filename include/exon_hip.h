@@ -429,6 +429,12 @@ int exon_hip_stream_close(exon_hip_stream* s);
  *   VCF   0 chrom(dict) 1 pos:i64? 2 qual:f32? 3 filter(dict of ';'-joined lists, "" = []) [4.. info.<F>: f32? | bool? | dict?]
  *   BAM   0 flag:i32 1 mapping_quality:u8? 2 reference(dict)? 3 start:i64? 4 end:i64?
  *   FASTQ 0 name 1 description? 2 sequence 3 quality_scores      FASTA 0 id 1 description? 2 sequence
+ *   GFF   0 seqname(dict) 1 source(dict) 2 type(dict) 3 start:i64 4 end:i64 5 score:f32? 6 strand(dict ["+","-"])? 7 phase(dict
+ *         ["0","1","2"])?  -- the reference's schema order (exon-gff/src/array_builder.rs); the three leading dictionaries are
+ *         built from the file (GFF has no header).  `attributes` is not built: any projection is EXON_HIP_EUNSUPPORTED.  A region
+ *         is the reference reader's own filter (exon-gff/src/batch_reader.rs:76-97): seqname = name AND start inside the
+ *         interval; with use_index the chunks come from <path>.tbi (GFF preset, read from the index header).  A ##FASTA
+ *         section is EXON_HIP_EUNSUPPORTED.  Plans address the columns by index: K2 (0, 3); K6 / K7 (0, 3, 4).
  * CPU-only: no ctx needed; errors are reported through exon_hip_last_error(NULL). */
 #define EXON_HIP_FORMAT_VCF 1
 #define EXON_HIP_FORMAT_BAM 2
@@ -437,6 +443,7 @@ int exon_hip_stream_close(exon_hip_stream* s);
 #define EXON_HIP_FORMAT_SAM 5 /* text SAM: same columns as BAM */
 #define EXON_HIP_FORMAT_BCF 6 /* BCF2: same columns as VCF */
 #define EXON_HIP_FORMAT_CRAM 7 /* CRAM 3.0 (raw / gzip / bzip2 / lzma / rANS 4x8 blocks), host decoder: same columns as BAM */
+#define EXON_HIP_FORMAT_GFF 8 /* GFF3 text (additive; the ABI stays 5): columns above; GTF and BED are not read */
 #define EXON_HIP_COMPRESSION_AUTO 0 /* sniff the gzip/BGZF magic */
 #define EXON_HIP_COMPRESSION_NONE 1
 #define EXON_HIP_COMPRESSION_GZIP 2
@@ -455,8 +462,8 @@ typedef struct exon_hip_scan_options {
                              any other Number -> List<f32 | i32 | dictionary>? (items '.' are NULL items; host decoders);
                              INFO '.' makes all of them NULL (the struct itself is NULL in the reference) */
   const char* region;     /* pushed-down vcf_region_filter / bam_region_filter ("chr1:1-100"), NULL = none */
-  int32_t use_index;      /* with `region`: plan BGZF chunks from <path>.tbi / <path>.bai (INDEXED_VCF / INDEXED_BAM) */
-  int32_t gpu_parse;      /* VCF, BCF, FASTQ, BAM, SAM: exon_hip_stream_consume_scan ships the file's bytes to HBM and decodes
+  int32_t use_index;      /* with `region`: plan BGZF chunks from <path>.tbi / <path>.bai (INDEXED_VCF / INDEXED_BAM / INDEXED_GFF) */
+  int32_t gpu_parse;      /* VCF, BCF, FASTQ, BAM, SAM, GFF: exon_hip_stream_consume_scan ships the file's bytes to HBM and decodes
                              them on the GPU (exon_hip_bgzf_inflate, exon_hip_vcf_parser_* / exon_hip_fastq_parser_* /
                              exon_hip_bam_parser_* ...).  exon_hip_scan_next on such a scan needs exon_hip_scan_bind_ctx first
                              (batches then come out of the same GPU pipeline); without a bound ctx it returns ESTATE */
@@ -488,7 +495,7 @@ int exon_hip_scan_open(const char* path, const exon_hip_scan_options* options, e
 int exon_hip_scan_schema(exon_hip_scan* scan, struct ArrowSchema* out);
 /* 0 = a batch was written to *out (caller releases or moves it); 1 = end of stream; <0 = error */
 int exon_hip_scan_next(exon_hip_scan* scan, struct ArrowArray* out);
-/* dictionary of a dict-encoded column (VCF 0/3, BAM 2): current size, and id of `name` (interned if new) */
+/* dictionary of a dict-encoded column (VCF 0/3, BAM 2, GFF 0/1/2/6/7): current size, and id of `name` (interned if new) */
 int exon_hip_scan_dictionary_size(exon_hip_scan* scan, int32_t column, int32_t* size);
 int exon_hip_scan_dictionary_intern(exon_hip_scan* scan, int32_t column, const char* name, int32_t* id);
 int exon_hip_scan_dictionary_value(exon_hip_scan* scan, int32_t column, int32_t id, const char** name);
@@ -694,6 +701,33 @@ int exon_hip_sam_parser_create(exon_hip_ctx* ctx, const char* const* reference_n
 int exon_hip_sam_parser_parse(exon_hip_sam_parser* parser, void* stream, const uint8_t* d_text, int64_t n_bytes,
                               exon_hip_bam_columns* cols);
 int exon_hip_sam_parser_destroy(exon_hip_sam_parser* parser);
+
+/* ---- GFF3 text parsing on the GPU (lines in HBM -> the GFF device layout) ----
+ * Line rules of exon_amd/csrc/host/gff.h.  Lines that start with '#' are no rows.  seqname / source / type become ids into
+ * dictionaries the parser builds across slabs (at most EXON_HIP_MAX_GROUPS values and 1 MiB of text each); `seed_seqnames`
+ * are inserted before the first slab with ids 0 .. n_seed - 1, so that a region plan knows its contig's id up front.
+ * n_undecided != 0 (a malformed field, more than 18 digits, a score the device leaves open, an empty line, a ##FASTA line, a
+ * dictionary past its limits): decode the file on the host instead -- errors are the host reader's to report. */
+typedef struct exon_hip_gff_parser exon_hip_gff_parser;
+typedef struct exon_hip_gff_columns {
+  int64_t n_rows, n_undecided, consumed_bytes; /* consumed: up to and including the last newline */
+  const int32_t *seqname_id, *source_id, *type_id; /* device pointers owned by the parser, overwritten by the next parse call */
+  const int64_t *start, *end;
+  const float* score;
+  const uint8_t* score_valid;
+  const int32_t* strand_id; /* 0 "+", 1 "-" */
+  const uint8_t* strand_valid;
+  const int32_t* phase_id;  /* 0, 1, 2 */
+  const uint8_t* phase_valid;
+} exon_hip_gff_columns;
+int exon_hip_gff_parser_create(exon_hip_ctx* ctx, const char* const* seed_seqnames, int32_t n_seed, int64_t max_slab_bytes,
+                               exon_hip_gff_parser** out);
+/* d_text: '\n'-terminated lines, any alignment; a trailing partial line is left to the caller.  Synchronises `stream`. */
+int exon_hip_gff_parser_parse(exon_hip_gff_parser* parser, void* stream, const uint8_t* d_text, int64_t n_bytes,
+                              exon_hip_gff_columns* cols);
+/* the dictionary of column 0 (seqname), 1 (source) or 2 (type) discovered so far, '\0'-separated in id order */
+int exon_hip_gff_parser_names(exon_hip_gff_parser* parser, int32_t column, char* buf, size_t cap, int32_t* n_names);
+int exon_hip_gff_parser_destroy(exon_hip_gff_parser* parser);
 
 /* ---- BCF2 record splitting + field extraction on the GPU (inflated BCF bytes in HBM -> the VCF device layout) ----
  * Same Arrow schema as VCF (exon-core/src/datasources/bcf/, exon-bcf); records are found like BAM's (parallel chain

@@ -2,6 +2,7 @@
 // kernels.hip / oracle) so the decode -> HBM -> kernel pipeline can be timed end to end on real files.
 // `gen_text fastq <reads> <out> [read_len=150] [ragged=0]` writes 4-line FASTQ records (config 5 end to end);
 // `gen_text bam <reads> <out> [read_len=100]` an uncompressed BAM stream (bgzip it to get a .bam; config 3 end to end).
+// `gen_text gff <rows> <out>` a GFF3 table sorted by (seqname, start), so that bgzip + a tabix index (GFF preset) serve it.
 // build: g++ -O2 -std=c++17 tools/gen_text.cpp -o tools/bin/gen_text      run: gen_text vcf <rows> <out.vcf>
 #include <cstdint>
 #include <cstdio>
@@ -12,7 +13,7 @@ static inline uint64_t mix64(uint64_t z) { z = (z ^ (z >> 30)) * 0xBF58476D1CE4E
 static inline uint64_t rnd(uint64_t seed, uint64_t col, uint64_t i) { return mix64(seed + col * 0xD1B54A32D192ED03ULL + (i + 1) * 0x9E3779B97F4A7C15ULL); }
 static inline uint32_t pct_thr(int p) { return (uint32_t)((((uint64_t)p) << 32) / 100); }
 int main(int argc, char** argv) {
-  if (argc < 4) { fprintf(stderr, "usage: gen_text vcf|bcf|fastq|bam|sam <rows> <out> [read_len] [ragged]\n"); return 2; }
+  if (argc < 4) { fprintf(stderr, "usage: gen_text vcf|bcf|fastq|bam|sam|gff <rows> <out> [read_len] [ragged]\n"); return 2; }
   const int64_t n = (int64_t)atof(argv[2]);
   FILE* f = fopen(argv[3], "wb");
   if (!f) return 1;
@@ -48,6 +49,33 @@ int main(int argc, char** argv) {
       fputc('\t', f);
       fwrite(qual.data(), 1, (size_t)len, f);
       fputs(i % 3 ? "\tNM:i:1\n" : "\n", f);
+    }
+    fclose(f);
+    return 0;
+  }
+  if (!strcmp(argv[1], "gff")) {
+    // 24 seqnames in contiguous runs, starts ascending inside a run (step 100 + jitter < 100), 10 types, 3 sources, scores present
+    // and '.', all four strand and phase spellings, "###" every 1000 rows, a '#' comment every 7777 rows
+    static const char* TYPES[10] = {"gene", "mRNA", "exon", "CDS", "five_prime_UTR", "three_prime_UTR", "ncRNA_gene", "lnc_RNA", "pseudogene", "biological_region"};
+    static const char* SOURCES[3] = {"ensembl", "havana", "ensembl_havana"};
+    static const char STRAND[4] = {'+', '-', '.', '?'}, PHASE[4] = {'.', '0', '1', '2'};
+    const int NSEQ = 24;
+    fputs("##gff-version 3\n", f);
+    for (int64_t i = 0; i < n; ++i) {
+      const uint64_t a = rnd(8, 0, (uint64_t)i), b = rnd(8, 1, (uint64_t)i);
+      const int seq = (int)((i * NSEQ) / n);
+      const int64_t first = ((int64_t)seq * n + NSEQ - 1) / NSEQ;  // the first row of this seqname's run
+      const int64_t start = 1 + (i - first) * 100 + (int64_t)(a % 100), end = start + (int64_t)((a >> 8) % 5000);
+      char name[16], score[16];
+      if (seq < 22) snprintf(name, sizeof name, "chr%d", seq + 1);
+      else strcpy(name, seq == 22 ? "chrX" : "chrY");
+      const uint32_t k = (uint32_t)((a >> 24) % 10000u);
+      if ((b & 3) == 0) strcpy(score, ".");
+      else snprintf(score, sizeof score, "%u.%u", k / 10, k % 10);
+      if (i && i % 1000 == 0) fputs("###\n", f);
+      if (i % 7777 == 5) fprintf(f, "# rows from %lld on\n", (long long)i);
+      fprintf(f, "%s\t%s\t%s\t%lld\t%lld\t%s\t%c\t%c\tID=f%lld;Name=n%u\n", name, SOURCES[(b >> 2) % 3], TYPES[(b >> 8) % 10], (long long)start, (long long)end,
+              score, STRAND[(b >> 16) & 3], PHASE[(b >> 18) & 3], (long long)i, (unsigned)(b >> 40) & 0xFFFFu);
     }
     fclose(f);
     return 0;
