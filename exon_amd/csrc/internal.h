@@ -81,10 +81,12 @@ struct ExonBamText {
   const int32_t* qual_offsets;  // quality_scores' list offsets (BAM: = seq_offsets; SAM: its own, QUAL may be '*' next to a SEQ)
   int64_t n_qual_items;
 };
+// n_undecided != 0 (every exon_text_* that has it): nothing was built, the slab is the host reader's -- a total beyond what the
+// scratch buffers hold (IDs of many empty items, CIGARs of long ops; see scratch_for), or what the format's own note names
 int exon_text_vcf(exon_hip_ctx* ctx, void* stream, ExonTextScratch** scratch, const uint8_t* d_text, int64_t n_bytes, const unsigned* d_nl, int64_t n_rows, uint64_t projection,
-                  ExonVcfText* out);
+                  ExonVcfText* out, int64_t* n_undecided);
 int exon_text_bam(exon_hip_ctx* ctx, void* stream, ExonTextScratch** scratch, const uint8_t* d_data, int64_t n_bytes, const uint32_t* d_rec_of_row, int64_t n_rows, uint64_t projection,
-                  ExonBamText* out);
+                  ExonBamText* out, int64_t* n_undecided);
 struct ExonFastqText {  // name, description, sequence, quality_scores (exon-fastq/src/config.rs:79-88), in that order
   const int32_t* offsets[4];  // [n_reads + 1] each
   const uint8_t* values[4];

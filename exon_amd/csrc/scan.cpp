@@ -2263,10 +2263,8 @@ static int export_slab(exon_hip_scan* scan, const exon_hip_column* sc, int64_t n
     } else if (kept == 0) {
       return EXON_HIP_OK;
     }
-    static const bool gather_forced = [] {
-      const char* v = getenv("EXON_HIP_EXPORT_GATHER");  // A/B: 1 = every filtered slab through the row-by-row gather
-      return v && v[0] == '1';
-    }();
+    const char* gv = getenv("EXON_HIP_EXPORT_GATHER");  // A/B, read for every slab: 1 = every filtered slab through the row-by-row gather
+    const bool gather_forced = gv && gv[0] == '1';
     if (!too_many && !gather_forced) {
       as_views = true;
       run_lo = runs.front().first;
@@ -2730,20 +2728,24 @@ static int build_text(exon_hip_scan* scan, exon_hip_ctx* ctx, hipStream_t hs, co
   int64_t undecided = 0;
   int r = EXON_HIP_OK;
   switch (scan->format) {
-    case EXON_HIP_FORMAT_VCF:
-      r = exon_text_vcf(ctx, hs, &scan->text_scratch, d_text, (int64_t)n, exon_hip_vcf_parser_newlines(scan->parser.as<exon_hip_vcf_parser>()), n_rows, proj, &t->vcf);
+    case EXON_HIP_FORMAT_VCF:  // undecided (here and for BAM, as for the other two): totals beyond what the scratch buffers hold
+      r = exon_text_vcf(ctx, hs, &scan->text_scratch, d_text, (int64_t)n, exon_hip_vcf_parser_newlines(scan->parser.as<exon_hip_vcf_parser>()), n_rows, proj, &t->vcf, &undecided);
       break;
     case EXON_HIP_FORMAT_BCF:  // undecided: an ID / allele that is not a typed string (the host reader reports what it is)
       r = exon_text_bcf(ctx, hs, &scan->text_scratch, d_text, (int64_t)n, exon_hip_bcf_parser_row_records(scan->parser.as<exon_hip_bcf_parser>()), n_rows, proj, &t->bcf, &undecided);
       break;
     case EXON_HIP_FORMAT_BAM:
-      r = exon_text_bam(ctx, hs, &scan->text_scratch, d_text, (int64_t)n, exon_hip_bam_parser_row_records(scan->parser.as<exon_hip_bam_parser>()), n_rows, proj, &t->bam);
+      r = exon_text_bam(ctx, hs, &scan->text_scratch, d_text, (int64_t)n, exon_hip_bam_parser_row_records(scan->parser.as<exon_hip_bam_parser>()), n_rows, proj, &t->bam, &undecided);
       break;
     case EXON_HIP_FORMAT_SAM:  // undecided: a CIGAR / QUAL the device would not print the way the reader does
       r = exon_text_sam(ctx, hs, &scan->text_scratch, d_text, (int64_t)n, exon_hip_sam_parser_newlines(scan->parser.as<exon_hip_sam_parser>()), n_rows, proj, &t->bam, &undecided);
       break;
   }
   if (!r && undecided) r = 1;
+  // the fill kernels read the slab's text: the source takes a slab's buffer for free once its parser has returned and inflates the
+  // slab after the next into it, so the text must have been read before this slab is released (a CIGAR fill of long records used to
+  // lose that race: records of the slab after the next showed up in its text)
+  if (!r && hipStreamSynchronize(hs) != hipSuccess) r = fail(ctx, EXON_HIP_EDEVICE, "string columns of a slab: the kernels failed");
   g_t_text_kernels += now_s() - tk0;
   return r;
 }

@@ -18,6 +18,7 @@
 
 #include <algorithm>
 #include <cstring>
+#include <initializer_list>
 #include <new>
 
 #include "internal.h"
@@ -369,7 +370,7 @@ __device__ __forceinline__ bool bcf_typed_string(const uint8_t* d, uint32_t* p, 
     *p += w;
   }
   if (!(t == 7 || (t == 0 && n == 0))) return false;
-  if (*p + n > end) return false;
+  if (n > end - *p) return false;  // (*p <= end here; `*p + n` would wrap for a count near 2^32)
   *at = *p;
   *len = t == 7 ? n : 0u;
   *p += *len;
@@ -472,11 +473,31 @@ struct ExonTextScratch {
   uint8_t* values[4] = {nullptr, nullptr, nullptr, nullptr};
   int64_t* qual = nullptr;
   size_t qual_cap = 0;
+  size_t value_cap = 0;  // bytes every values[k] holds
+  size_t item_cap = 0;   // entries item_off / item_off2 hold
   explicit ExonTextScratch(exon_hip_ctx* ctx) : bufs(ctx), qual_bufs(ctx) {}
 };
 
 void exon_text_scratch_destroy(ExonTextScratch* s) { delete s; }
 
+// The largest totals a slab of n_bytes bytes and n_rows rows can produce, buffer by buffer, against the sizes below (the callers
+// pass max_rows >= n_rows and max_bytes as named).  "fits": the size always holds it; "checked": it may not, fits() compares the
+// total on the host before the fill kernel is launched and hands a slab that does not fit to the host reader.
+//   every format  len / off / valid / sums: n_rows lengths, n_rows + 1 offsets, a bit a row, a sum per 256 rows; sized for max_rows + 64: fits
+//   VCF    values[0] (max_bytes = n_bytes): the ID fields without their ';', parts of the text: <= n_bytes: fits
+//   VCF    values[2]: the REF fields, parts of the text: <= n_bytes: fits
+//   VCF    item_off: an ID field of k bytes is up to k + 1 items (k ';') and a line has a byte more than its ID (the LF): up to n_bytes
+//                    items + 1 entry, against max_bytes / 2 + max_rows + 66: checked
+//   BCF    values[0], [1], [2] (max_bytes = n_bytes): id / ref / alt, characters of typed strings inside the records: <= n_bytes each: fits
+//   BCF    item_off: a typed ID of k characters is up to k + 1 items behind a descriptor byte: up to n_bytes items + 1 entry: checked
+//   BCF    item_off2: an empty allele is its descriptor byte alone: up to n_bytes items + 1 entry: checked
+//   BAM    values[0] (max_bytes = 2 n_bytes): names, l_read_name - 1 bytes of the record: <= n_bytes: fits
+//   BAM    values[1]: a CIGAR op of 4 bytes prints as up to 9 digits and a letter: up to 2.5 n_bytes: checked
+//   BAM    values[2]: two bases a byte, 2 n_bytes when every l_seq lies inside its record; l_seq is the record's own word: checked
+//   BAM    qual: l_seq items a row; qual_for grows it to the total before the fill: fits
+//   SAM    values[0], [1], [2] (max_bytes = n_bytes): QNAME / CIGAR / SEQ fields, copied as they are: <= n_bytes each: fits
+//   SAM    qual: an item per QUAL byte; qual_for grows it to the total before the fill: fits
+//   FASTQ  values[0 .. 3] (max_bytes = n_bytes + 16): name / description / sequence / quality, disjoint parts of the text: <= n_bytes: fits
 static int scratch_for(exon_hip_ctx* ctx, ExonTextScratch** sp, int64_t max_rows, int64_t max_bytes, bool vcf, int n_cols = 3) {
   ExonTextScratch* s = *sp;
   if (s && s->max_rows >= max_rows && s->max_bytes >= max_bytes && s->n_cols >= n_cols) return EXON_HIP_OK;
@@ -490,13 +511,15 @@ static int scratch_for(exon_hip_ctx* ctx, ExonTextScratch** sp, int64_t max_rows
   hipSetDevice(ctx->device);
   PoolBufs& b = s->bufs;
   const size_t r = (size_t)max_rows + 64;
+  s->value_cap = (size_t)max_bytes;
+  s->item_cap = (size_t)max_bytes / 2 + r + 2;
   for (int k = 0; k < n_cols; ++k) {
     s->len[k] = b.take<uint32_t>(r * 4);
     s->off[k] = b.take<int32_t>((r + 1) * 4);
     if (k < 4) s->values[k] = b.take<uint8_t>((size_t)max_bytes + 64);
   }
   if (n_cols >= 5) {  // BCF: alt items
-    s->item_off2 = b.take<int32_t>(((size_t)max_bytes / 2 + r + 2) * 4);
+    s->item_off2 = b.take<int32_t>(s->item_cap * 4);
     s->totals5 = b.take<unsigned>(32);
     s->h_totals5 = b.pinned<unsigned>(32);
   }
@@ -505,7 +528,7 @@ static int scratch_for(exon_hip_ctx* ctx, ExonTextScratch** sp, int64_t max_rows
   if (vcf) {
     s->field_off = b.take<uint32_t>(3 * r * 4);
     s->field_len = b.take<uint32_t>(3 * r * 4);
-    s->item_off = b.take<int32_t>(((size_t)max_bytes / 2 + r + 2) * 4);
+    s->item_off = b.take<int32_t>(s->item_cap * 4);
   }
   if (n_cols >= 4) s->sam_field_off = b.take<uint32_t>(4 * r * 4);
   s->sums = b.take<unsigned>((r / TPB + 4) * 4);
@@ -534,6 +557,16 @@ static int qual_for(exon_hip_ctx* ctx, ExonTextScratch* s, unsigned items) {
   return EXON_HIP_OK;
 }
 
+// the totals the measure kernels have brought back against what the fill kernel's buffers hold: `bytes` into a values buffer,
+// `items` (+ the closing entry) into an item-offsets buffer.  false: the fill is not launched, the slab is the host reader's
+static bool fits(const ExonTextScratch* s, std::initializer_list<unsigned> bytes, std::initializer_list<unsigned> items = {}) {
+  for (unsigned b : bytes)
+    if ((size_t)b > s->value_cap) return false;
+  for (unsigned i : items)
+    if ((size_t)i + 1 > s->item_cap) return false;
+  return true;
+}
+
 // lengths -> offsets (n + 1 of them); the total -> *total
 static void scan_lengths(hipStream_t hs, ExonTextScratch* s, const uint32_t* len, unsigned n, int32_t* offsets, unsigned* total) {
   const int nb = (int)((n + LIST_TPB - 1) / LIST_TPB);
@@ -542,8 +575,9 @@ static void scan_lengths(hipStream_t hs, ExonTextScratch* s, const uint32_t* len
 }
 
 int exon_text_vcf(exon_hip_ctx* ctx, void* stream, ExonTextScratch** sp, const uint8_t* d_text, int64_t n_bytes, const unsigned* d_nl, int64_t n_rows, uint64_t projection,
-                  ExonVcfText* out) {
+                  ExonVcfText* out, int64_t* n_undecided) {
   memset(out, 0, sizeof *out);
+  *n_undecided = 0;
   if (n_rows == 0 || !(projection & (EXON_HIP_PROJECT_VCF_ID | EXON_HIP_PROJECT_VCF_REF | EXON_HIP_PROJECT_VCF_ALT))) return EXON_HIP_OK;
   const unsigned skip = (unsigned)(reinterpret_cast<uintptr_t>(d_text) & 15);
   d_text -= skip;
@@ -562,6 +596,10 @@ int exon_text_vcf(exon_hip_ctx* ctx, void* stream, ExonTextScratch** sp, const u
   HIP_TRY(ctx, hipMemcpyAsync(s->h_totals, s->totals, 16, hipMemcpyDeviceToHost, hs));
   HIP_TRY(ctx, hipStreamSynchronize(hs));
   const unsigned id_items = s->h_totals[0], id_bytes = s->h_totals[1], ref_bytes = s->h_totals[2];
+  if (!fits(s, {id_bytes, ref_bytes}, {id_items})) {  // (IDs of many empty items)
+    *n_undecided = n_rows;
+    return EXON_HIP_OK;
+  }
   hipLaunchKernelGGL(k_vcf_fill, dim3(nb), dim3(TPB), 0, hs, d_text, n, L, s->off[0], s->off[1], s->off[2], s->item_off, s->values[0], s->values[2], id_items, id_bytes);
   if (id_items == 0) HIP_TRY(ctx, hipMemsetAsync(s->item_off, 0, 4, hs));
   HIP_TRY(ctx, hipGetLastError());
@@ -579,8 +617,9 @@ int exon_text_vcf(exon_hip_ctx* ctx, void* stream, ExonTextScratch** sp, const u
 }
 
 int exon_text_bam(exon_hip_ctx* ctx, void* stream, ExonTextScratch** sp, const uint8_t* d_data, int64_t n_bytes, const uint32_t* d_rec_of_row, int64_t n_rows, uint64_t projection,
-                  ExonBamText* out) {
+                  ExonBamText* out, int64_t* n_undecided) {
   memset(out, 0, sizeof *out);
+  *n_undecided = 0;
   const uint64_t all = EXON_HIP_PROJECT_BAM_NAME | EXON_HIP_PROJECT_BAM_CIGAR | EXON_HIP_PROJECT_BAM_SEQUENCE | EXON_HIP_PROJECT_BAM_QUALITY_SCORES;
   if (n_rows == 0 || !(projection & all)) return EXON_HIP_OK;
   int rc = scratch_for(ctx, sp, std::max<int64_t>(n_rows, 1 << 16), std::max<int64_t>(2 * n_bytes, 1 << 20), false);  // (a sequence doubles its 4-bit codes)
@@ -595,6 +634,10 @@ int exon_text_bam(exon_hip_ctx* ctx, void* stream, ExonTextScratch** sp, const u
   HIP_TRY(ctx, hipMemcpyAsync(s->h_totals, s->totals, 16, hipMemcpyDeviceToHost, hs));
   HIP_TRY(ctx, hipStreamSynchronize(hs));
   const unsigned name_bytes = s->h_totals[0], cigar_bytes = s->h_totals[1], seq_bytes = s->h_totals[2];
+  if (!fits(s, {name_bytes, cigar_bytes, seq_bytes})) {  // (CIGARs of long ops: up to ten characters out of four bytes)
+    *n_undecided = n_rows;
+    return EXON_HIP_OK;
+  }
   if (projection & EXON_HIP_PROJECT_BAM_QUALITY_SCORES)
     if (int rc = qual_for(ctx, s, seq_bytes)) return rc;
   hipLaunchKernelGGL(k_bam_fill, dim3(nb), dim3(TPB), 0, hs, d_data, d_rec_of_row, n, projection, s->off[0], s->off[1], s->off[2], s->values[0], s->values[1], s->values[2], s->qual);
@@ -714,6 +757,10 @@ int exon_text_bcf(exon_hip_ctx* ctx, void* stream, ExonTextScratch** sp, const u
   *n_undecided = s->h_totals5[7];
   if (*n_undecided) return EXON_HIP_OK;
   const unsigned id_items = s->h_totals5[0], id_bytes = s->h_totals5[1], ref_bytes = s->h_totals5[2], alt_items = s->h_totals5[3], alt_bytes = s->h_totals5[4];
+  if (!fits(s, {id_bytes, ref_bytes, alt_bytes}, {id_items, alt_items})) {  // (IDs of many empty items, empty alleles)
+    *n_undecided = n_rows;
+    return EXON_HIP_OK;
+  }
   hipLaunchKernelGGL(k_bcf_fill, dim3(nb), dim3(TPB), 0, hs, d_data, d_rec_of_row, n, projection, s->off[0], s->off[1], s->off[2], s->off[3], s->off[4], s->item_off, s->item_off2,
                      s->values[0], s->values[1], s->values[2], id_items, id_bytes, alt_items, alt_bytes);
   if (id_items == 0) HIP_TRY(ctx, hipMemsetAsync(s->item_off, 0, 4, hs));

@@ -295,7 +295,8 @@ def decode_bam(path):
             name=name, flag=flag, ref_id=ref_id if ref_id >= 0 else None, start=start,
             end=(start + ref_len - 1) if start is not None else None,
             mapq=None if mapq == 255 else mapq,
-            cigar="".join(f"{c >> 4}{CIGAR_OPS[c & 0xF]}" for c in cigar),
+            # (op codes 9-15 are not defined: noodles refuses such a record; both readers of this project print '?')
+            cigar="".join(f"{c >> 4}{CIGAR_OPS[c & 0xF] if (c & 0xF) < 9 else '?'}" for c in cigar),
             mate_ref_id=next_ref if next_ref >= 0 else None,
             sequence="".join("=ACMGRSVTWYHKDBN"[(seq[i >> 1] >> (4 if i % 2 == 0 else 0)) & 0xF] for i in range(l_seq)),
             quality_score=qual))
@@ -319,6 +320,7 @@ def decode_sam(path):
     None, MAPQ 255 -> None, end from the CIGAR."""
     refs, recs = [], []
     for line in read_bytes(path).decode().split("\n"):
+        line = line[:-1] if line.endswith("\r") else line  # (the line reader drops a CR in front of the LF, as for VCF)
         if not line:
             continue
         if line.startswith("@"):

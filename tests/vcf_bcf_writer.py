@@ -2,6 +2,7 @@
 (exon-core/src/datasources/vcf/schema_builder.rs:197-249): Float / Integer scalars, a Flag, a String scalar, and lists
 (Number=A Integer, Number=. Float, Number=. String).  Independent of the product's decoders and of the oracle: rows are
 python dicts, the BCF side encodes typed values the way htslib does (smallest integer type that holds every item)."""
+import functools
 import struct
 import subprocess
 
@@ -34,7 +35,9 @@ def string_index(filters=FILTERS):
 
 def make_rows(n, seed=7):
     """rows: dict(chrom, pos, qual (float | None), filter (list[str]), info (dict | None)).  info values: float, int, True,
-    str, or lists with None items; a key mapped to None means `key=.`"""
+    str, or lists with None items; a key mapped to None means `key=.`.  Optional keys (row_id_ref_alt): id (the ID field's text,
+    "" = an empty field), ref (text), alt (list of alleles; None or [] = none: '.' in VCF, REF alone in BCF; BCF alleles may be
+    empty strings), alleles (BCF only: every allele, REF first; [] = n_allele 0)"""
     rng = np.random.default_rng(seed)
     edge_dp = [16777215, 16777216, 16777217, 16777218, 16777219, 2**31 - 1, -(2**31) + 8, -5, 0, 127, 128, -120, 32767, 32768, 100000]
     rows = []
@@ -87,12 +90,20 @@ def _info_text(info):
     return ";".join(parts)
 
 
-def write_vcf(path, rows, filters=FILTERS):
-    with open(path, "w") as f:
+def row_id_ref_alt(r):
+    """(id text, ref, alt alleles) of a row: today's '.', 'A', ['C'] unless the row says otherwise"""
+    alt = r.get("alt", ["C"])
+    return r.get("id", "."), r.get("ref", "A"), [] if alt is None else list(alt)
+
+
+def write_vcf(path, rows, filters=FILTERS, eol=lambda i: "\n"):
+    """eol(i): the line end of row i ("\r\n"; "" for a last line without LF)"""
+    with open(path, "w", newline="") as f:
         f.write(header_text(False, filters))
-        for r in rows:
+        for i, r in enumerate(rows):
             q = "." if r["qual"] is None else np.format_float_positional(np.float32(r["qual"]), unique=True, trim="0")
-            f.write(f"{r['chrom']}\t{r['pos']}\t.\tA\tC\t{q}\t{';'.join(r['filter']) or '.'}\t{_info_text(r['info'])}\n")
+            rid, ref, alt = row_id_ref_alt(r)
+            f.write(f"{r['chrom']}\t{r['pos']}\t{rid}\t{ref}\t{','.join(alt) or '.'}\t{q}\t{';'.join(r['filter']) or '.'}\t{_info_text(r['info'])}{eol(i)}")
 
 
 def _typed_ints(vals):
@@ -118,6 +129,7 @@ def _typed_floats(vals):
     return _desc(len(vals), 5) + b"".join(struct.pack("<I", 0x7F800001) if v is None else struct.pack("<f", np.float32(v)) for v in vals)
 
 
+@functools.lru_cache(maxsize=4096)
 def _typed_str(s):
     b = s.encode()
     return _desc(len(b), 7) + b
@@ -131,10 +143,12 @@ def write_bcf(path, rows, bgzip, filters=FILTERS):
     out = [b"BCF\x02\x02", struct.pack("<I", len(text)), text]
     for r in rows:
         info = r["info"] or {}
+        rid, ref, alt = row_id_ref_alt(r)
+        alleles = r["alleles"] if "alleles" in r else [ref] + alt
         shared = struct.pack("<iiiIII", int(r["chrom"]) - 1, r["pos"] - 1, 1,
                              0x7F800001 if r["qual"] is None else struct.unpack("<I", struct.pack("<f", np.float32(r["qual"])))[0],
-                             len(info) | (2 << 16), 0)
-        shared += b"\x07" + _typed_str("A") + _typed_str("C")
+                             len(info) | (len(alleles) << 16), 0)
+        shared += (_typed_str(r["id"]) if "id" in r else b"\x07") + b"".join(_typed_str(a) for a in alleles)
         shared += _typed_ints([sidx[f] for f in r["filter"]]) if r["filter"] else b"\x00"
         for k, v in info.items():
             shared += _typed_ints([sidx[k]])
