@@ -106,6 +106,12 @@ class GFFColumns(C.Structure):
                 ("strand_valid", C.c_void_p), ("phase_id", C.c_void_p), ("phase_valid", C.c_void_p)]
 
 
+class GFFAttributes(C.Structure):
+    _fields_ = [("n_entries", C.c_int64), ("n_items", C.c_int64), ("n_key_bytes", C.c_int64), ("n_item_bytes", C.c_int64),
+                ("n_undecided", C.c_int64), ("map_offsets", C.c_void_p), ("key_offsets", C.c_void_p), ("key_values", C.c_void_p),
+                ("list_offsets", C.c_void_p), ("item_offsets", C.c_void_p), ("item_values", C.c_void_p)]
+
+
 class ScanOptions(C.Structure):
     _fields_ = [("format", C.c_int32), ("compression", C.c_int32), ("batch_size", C.c_int64),
                 ("info_field", C.c_char_p), ("region", C.c_char_p), ("use_index", C.c_int32), ("gpu_parse", C.c_int32),
@@ -227,6 +233,8 @@ SIGNATURES = {
     "exon_hip_sam_parser_destroy": (C.c_int, [_vp]),
     "exon_hip_gff_parser_create": (C.c_int, [_vp, C.POINTER(C.c_char_p), _i32, _i64, C.POINTER(_vp)]),
     "exon_hip_gff_parser_parse": (C.c_int, [_vp, _vp, _vp, _i64, C.POINTER(GFFColumns)]),
+    "exon_hip_gff_parser_want_attributes": (C.c_int, [_vp, _i32]),
+    "exon_hip_gff_parser_attributes": (C.c_int, [_vp, _vp, C.POINTER(GFFAttributes)]),
     "exon_hip_gff_parser_names": (C.c_int, [_vp, _i32, C.c_char_p, C.c_size_t, C.POINTER(_i32)]),
     "exon_hip_gff_parser_destroy": (C.c_int, [_vp]),
     "exon_hip_bcf_parser_create": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i64, C.POINTER(_vp)]),

@@ -1430,9 +1430,14 @@ __device__ __forceinline__ bool gff_position(const uint8_t* __restrict__ text, u
   return ok;
 }
 
+// ATTR (the scan projects `attributes`): where every row's ninth field lies, for text_columns.hip's k_gff_attr_measure / _fill.
+// The two pointers trail the arguments and the ATTR = false instantiation never reads them: its code is the kernel's as it
+// was before the column existed.
+template <bool ATTR>
 __global__ __launch_bounds__(TPB) void k_parse_gff_lines(const uint8_t* __restrict__ text, const unsigned* __restrict__ nl_pos, unsigned* __restrict__ scalars,
                                                          const uint32_t* __restrict__ is_row, const unsigned* __restrict__ block_offsets, FilterTable t0,
-                                                         FilterTable t1, FilterTable t2, GffOut out, unsigned cap, unsigned skip, unsigned n_total) {
+                                                         FilterTable t1, FilterTable t2, GffOut out, unsigned cap, unsigned skip, unsigned n_total,
+                                                         uint32_t* __restrict__ attr_off, uint32_t* __restrict__ attr_len) {
   static_assert(TPB == LIST_TPB, "list_first_item ranks a workgroup of LIST_TPB lines");
   const unsigned n_lines = min(scalars[0], cap), n_rows = scalars[3];
   const bool identity = n_rows == n_lines;  // no '#' line in the slab (the same for every thread of the launch)
@@ -1506,6 +1511,10 @@ __global__ __launch_bounds__(TPB) void k_parse_gff_lines(const uint8_t* __restri
     out.score[row] = score;
     out.strand[row] = strand;
     out.phase[row] = phase;
+    if (ATTR) {  // (a short record: an empty field, the row is undecided anyway)
+      attr_off[row] = fs[8];
+      attr_len[row] = nf < 8 ? 0u : end - fs[8];
+    }
     if (!identity) out.vflags[row] = (uint8_t)((score_ok ? 1 : 0) | (strand_ok ? 2 : 0) | (phase_ok ? 4 : 0));
   }
   if (identity) {
@@ -1549,7 +1558,16 @@ struct exon_hip_gff_parser {
   uint32_t* d_is_row = nullptr;
   unsigned* d_blocks = nullptr;   // per-workgroup sums of is_row (scanned in place)
   int32_t h_stat[3] = {0, 0, 0};  // the dictionaries' overflow flags after the last slab
-  explicit exon_hip_gff_parser(exon_hip_ctx* c) : ctx(c), bufs(c) {}
+  // the `attributes` column (exon_hip_gff_parser_want_attributes): every row's ninth field, recorded by the line kernel, and the
+  // slab of the last parse call (aligned) for exon_hip_gff_parser_attributes
+  bool want_attr = false;
+  PoolBufs attr_bufs;  // (of their own: a failed allocation is released and does not stick to the parser's)
+  uint32_t *d_attr_off = nullptr, *d_attr_len = nullptr;
+  ExonTextScratch* attr_scratch = nullptr;
+  const uint8_t* last_text = nullptr;
+  int64_t last_bytes = 0, last_rows = -1;
+  explicit exon_hip_gff_parser(exon_hip_ctx* c) : ctx(c), bufs(c), attr_bufs(c) {}
+  ~exon_hip_gff_parser() { exon_text_scratch_destroy(attr_scratch); }
 };
 
 // names[i] -> id i of a device-built dictionary before the first slab: keys, ids, the text pool and the two claim counters
@@ -1652,8 +1670,12 @@ int exon_hip_gff_parser_parse(exon_hip_gff_parser* p, void* stream, const uint8_
   const GffOut& o = p->out;
   hipLaunchKernelGGL(k_gff_classify, dim3(pblocks), dim3(TPB), 0, s, d_text, idx.nl, idx.d_scalars, (unsigned)row_bound, skip, p->d_is_row);
   launch_list_scan(s, p->d_is_row, idx.d_scalars, (unsigned)row_bound, pblocks, p->d_blocks, idx.d_scalars + 3);
-  hipLaunchKernelGGL(k_parse_gff_lines, dim3(pblocks), dim3(TPB), 0, s, d_text, idx.nl, idx.d_scalars, p->d_is_row, p->d_blocks, p->tables[0], p->tables[1],
-                     p->tables[2], o, (unsigned)row_bound, skip, (unsigned)n_bytes);
+  if (p->want_attr)
+    hipLaunchKernelGGL(k_parse_gff_lines<true>, dim3(pblocks), dim3(TPB), 0, s, d_text, idx.nl, idx.d_scalars, p->d_is_row, p->d_blocks, p->tables[0], p->tables[1],
+                       p->tables[2], o, (unsigned)row_bound, skip, (unsigned)n_bytes, p->d_attr_off, p->d_attr_len);
+  else
+    hipLaunchKernelGGL(k_parse_gff_lines<false>, dim3(pblocks), dim3(TPB), 0, s, d_text, idx.nl, idx.d_scalars, p->d_is_row, p->d_blocks, p->tables[0], p->tables[1],
+                       p->tables[2], o, (unsigned)row_bound, skip, (unsigned)n_bytes, (uint32_t*)nullptr, (uint32_t*)nullptr);
   hipLaunchKernelGGL(k_gff_pack_valid, dim3(std::min(pblocks, 1024)), dim3(256), 0, s, idx.d_scalars, (unsigned)row_bound, o.vflags, o.score_valid,
                      o.strand_valid, o.phase_valid);
   for (int k = 0; k < 3; ++k) {
@@ -1668,6 +1690,9 @@ int exon_hip_gff_parser_parse(exon_hip_gff_parser* p, void* stream, const uint8_
   cols->n_undecided = idx.h_scalars[1] + (n_lines > row_bound ? 1 : 0);  // more lines than the slab's bytes allow for records: the host reader's
   for (int k = 0; k < 3; ++k) cols->n_undecided += p->h_stat[k] ? 1 : 0;  // a dictionary past its limits (or two texts that hash alike)
   cols->consumed_bytes = idx.consumed(skip);
+  p->last_text = d_text;
+  p->last_bytes = n_bytes;
+  p->last_rows = p->want_attr && cols->n_undecided == 0 ? cols->n_rows : -1;
   cols->seqname_id = o.id[0];
   cols->source_id = o.id[1];
   cols->type_id = o.id[2];
@@ -1682,6 +1707,48 @@ int exon_hip_gff_parser_parse(exon_hip_gff_parser* p, void* stream, const uint8_
   return EXON_HIP_OK;
 }
 
+int exon_hip_gff_parser_want_attributes(exon_hip_gff_parser* p, int32_t on) {
+  if (!p) return fail(nullptr, EXON_HIP_EINVAL, "exon_hip_gff_parser_want_attributes: NULL argument");
+  if (on && !p->d_attr_off) {
+    hipSetDevice(p->ctx->device);
+    p->d_attr_off = p->attr_bufs.take<uint32_t>((size_t)p->max_rows * 4);
+    p->d_attr_len = p->attr_bufs.take<uint32_t>((size_t)p->max_rows * 4);
+    if (p->attr_bufs.status() != hipSuccess) {
+      (void)hipGetLastError();
+      p->attr_bufs.release();
+      p->d_attr_off = p->d_attr_len = nullptr;
+      return fail(p->ctx, EXON_HIP_ENOMEM, "gff parser: the rows' attribute fields (%lld rows)", (long long)p->max_rows);
+    }
+  }
+  p->want_attr = on != 0;
+  p->last_rows = -1;
+  return EXON_HIP_OK;
+}
+
+int exon_hip_gff_parser_attributes(exon_hip_gff_parser* p, void* stream, exon_hip_gff_attributes* out) {
+  if (!p || !out) return fail(p ? p->ctx : nullptr, EXON_HIP_EINVAL, "exon_hip_gff_parser_attributes: NULL argument");
+  memset(out, 0, sizeof *out);
+  if (p->last_rows < 0)
+    return fail(p->ctx, EXON_HIP_ESTATE, "exon_hip_gff_parser_attributes: no slab to build from (call exon_hip_gff_parser_want_attributes, then parse; a slab with undecided rows has none)");
+  ExonGffText t;
+  int64_t und = 0;
+  if (int rc = exon_text_gff(p->ctx, stream, &p->attr_scratch, p->last_text, p->last_bytes, p->d_attr_off, p->d_attr_len, p->last_rows, &t, &und)) return rc;
+  HIP_TRY(p->ctx, hipStreamSynchronize(pick_stream(p->ctx, stream)));
+  out->n_undecided = und;
+  if (und) return EXON_HIP_OK;
+  out->n_entries = t.n_entries;
+  out->n_items = t.n_items;
+  out->n_key_bytes = t.n_key_bytes;
+  out->n_item_bytes = t.n_item_bytes;
+  out->map_offsets = t.map_offsets;
+  out->key_offsets = t.key_offsets;
+  out->key_values = t.key_values;
+  out->list_offsets = t.list_offsets;
+  out->item_offsets = t.item_offsets;
+  out->item_values = t.item_values;
+  return EXON_HIP_OK;
+}
+
 // the dictionary of column 0 (seqname), 1 (source) or 2 (type) discovered so far, '\0'-separated in id order
 int exon_hip_gff_parser_names(exon_hip_gff_parser* p, int32_t column, char* buf, size_t cap, int32_t* n_names) {
   if (!p || !n_names || column < 0 || column > 2) return fail(p ? p->ctx : nullptr, EXON_HIP_EINVAL, "exon_hip_gff_parser_names: bad argument");
@@ -1690,6 +1757,13 @@ int exon_hip_gff_parser_names(exon_hip_gff_parser* p, int32_t column, char* buf,
 }
 
 }  // extern "C"
+
+void exon_hip_gff_parser_attr_fields(exon_hip_gff_parser* p, const uint8_t** text, int64_t* n_bytes, const uint32_t** off, const uint32_t** len) {
+  *text = p->last_text;
+  *n_bytes = p->last_bytes;
+  *off = p->d_attr_off;
+  *len = p->d_attr_len;
+}
 
 int exon_hip_gff_parser_names_so_far(exon_hip_gff_parser* p, int32_t column, char* buf, size_t cap, int32_t* n_names) {
   if (!p || !n_names || column < 0 || column > 2) return fail(p ? p->ctx : nullptr, EXON_HIP_EINVAL, "exon_hip_gff_parser_names_so_far: bad argument");

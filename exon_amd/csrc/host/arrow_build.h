@@ -255,7 +255,7 @@ struct BatchArena;
 struct ArenaNode {
   struct ArrowArray arr;
   const void* bufs[3];
-  struct ArrowArray* kid;
+  struct ArrowArray* kids[2];  // one child (a list's items), or the two of a map's entries
   BatchArena* arena;
 };
 struct BatchArena {
@@ -303,7 +303,8 @@ inline struct ArrowArray* arena_array(BatchArena* a, int64_t length, int64_t off
   nd->bufs[0] = b0;
   nd->bufs[1] = b1;
   nd->bufs[2] = b2;
-  nd->kid = kid;
+  nd->kids[0] = kid;
+  nd->kids[1] = nullptr;
   memset(&nd->arr, 0, sizeof nd->arr);
   nd->arr.length = length;
   nd->arr.offset = offset;
@@ -311,11 +312,20 @@ inline struct ArrowArray* arena_array(BatchArena* a, int64_t length, int64_t off
   nd->arr.n_buffers = n_buffers;
   nd->arr.buffers = nd->bufs;
   nd->arr.n_children = kid ? 1 : 0;
-  nd->arr.children = kid ? &nd->kid : nullptr;
+  nd->arr.children = kid ? nd->kids : nullptr;
   nd->arr.dictionary = dict;
   nd->arr.release = release_arena_array;
   nd->arr.private_data = nd;
   return &nd->arr;
+}
+// a struct of two children (a map's `entries`: keys and values), not NULL
+inline struct ArrowArray* arena_struct2(BatchArena* a, int64_t length, struct ArrowArray* k0, struct ArrowArray* k1) {
+  struct ArrowArray* s = arena_array(a, length, 0, 0, 1, nullptr, nullptr, nullptr, k0);
+  if (!s) return nullptr;
+  ArenaNode* nd = static_cast<ArenaNode*>(s->private_data);
+  nd->kids[1] = k1;
+  s->n_children = 2;
+  return s;
 }
 // the values of dictionary `d` (slab-wide) as an array of the arena
 inline struct ArrowArray* arena_dictionary(BatchArena* a, const SharedUtf8& d) {
@@ -330,7 +340,7 @@ inline void make_struct_of_arena(struct ArrowArray* out, int64_t n, BatchArena* 
   nd->bufs[0] = nullptr;
   struct ArrowArray** kp = reinterpret_cast<struct ArrowArray**>(a->nodes() + a->cap);  // behind the nodes: room for n_columns pointers
   for (size_t i = 0; i < kids.size(); ++i) kp[i] = kids[i];
-  nd->kid = nullptr;
+  nd->kids[0] = nd->kids[1] = nullptr;
   out->length = n;
   out->n_buffers = 1;
   out->buffers = nd->bufs;

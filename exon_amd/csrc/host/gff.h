@@ -5,7 +5,7 @@
 //   0 seqname  1 source  2 type : i32 ids into dictionaries built from the file (GFF has no header), never NULL
 //   3 start  4 end : i64, never NULL          5 score : f32? ('.' -> NULL)
 //   6 strand : i32 id into ["+", "-"]? ('.' and '?' -> NULL)      7 phase : i32 id into ["0", "1", "2"]? ('.' -> NULL)
-// `attributes` (Map<Utf8, List<Utf8>>) is not built.
+//   8 attributes : Map<Utf8, List<Utf8>>, only with EXON_HIP_PROJECT_GFF_ATTRIBUTES (config.rs:81-108, array_builder.rs:141-165)
 //
 // THE LINE RULES (the device parser, gpu_parse.hip's k_parse_gff_lines, agrees with them or hands the file over):
 //   * a line ends at '\n'; one '\r' in front of it is dropped
@@ -23,6 +23,22 @@
 // Four corners could not be checked against the reference's parser (noodles-gff 0.41.0) and are DECISIONS of this library:
 // an empty line and a record with fewer than eight TABs are errors; end < start is accepted as it is; percent-escapes in the
 // first three fields are kept raw.
+//
+// THE ATTRIBUTE RULES (field 9 with the column projected; text_columns.hip's k_gff_attr_measure / k_gff_attr_fill agree with them
+// or hand the file over).  array_builder.rs:141-165 fixes the shape: one entry per attribute in file order, a String value is a
+// list of one item, an Array value one item per element; the map, its value lists and the items are never NULL (:149,159,164).
+// How noodles-gff splits and decodes the text cannot be read here, so every rule marked DECISION is this library's own:
+//   * field 9 is everything behind the eighth TAB up to the line end (CR dropped); TABs inside it are kept
+//   * "" and "." give a map of 0 entries
+//   * DECISION: entries are split at every ';'.  Exactly one empty piece at the very end (a trailing ';': all 7 rows of the
+//     reference's ecoli.gff end so, and its slt reads them) is ignored; any other empty piece (a leading ';', ";;", "a=b;;") is
+//     an error that quotes the line
+//   * DECISION: a piece is split at its first '='; no '=' is an error; an empty key is accepted; an empty value is one empty item
+//   * DECISION: a value that contains ',' is one item per ','-separated piece (empty pieces are empty items), else one item
+//   * DECISION: percent-decoding applies to the key and to every item AFTER the splitting: '%' and two hex digits (either case)
+//     become that byte, a '%' without them stays; every decoded key and item must be valid UTF-8, else it is an error
+//   * DECISION: nothing is trimmed or unquoted; duplicate keys stay separate entries, in file order
+//   * with the column projected, field 9 of EVERY record is validated, whether a pushed-down filter keeps it or not
 #pragma once
 #include "formats.h"
 
@@ -37,6 +53,7 @@ struct GFFConfig {
   int64_t batch_size = DEFAULT_BATCH_SIZE;
   int threads = 0;            // decode threads: 0 = all host cores, 1 = sequential reader
   bool defer_decode = false;  // the caller will take the byte stream (GPU-side parsing): start no parse pipeline
+  uint64_t projection = 0;    // EXON_HIP_PROJECT_GFF_ATTRIBUTES: column 8
   RegionFilter filter;        // batch_reader.rs:76-97: seqname == region name AND start inside the interval (start only)
   // EXON_HIP_REFERENCE_QUIRKS=1 on an indexed scan: IndexedGffOpener (indexed_file_opener.rs:77-82) reads the COMPRESSED
   // range [chunk.start.compressed, chunk.end.compressed) -- the block that holds the chunk's end is never read, and the line
@@ -60,6 +77,8 @@ struct GFFRecord {
   float score = 0.f;
   bool has_score = false;
   int32_t strand = -1, phase = -1;  // -1: NULL
+  const char* attr = nullptr;       // field 9 (TABs included)
+  size_t attr_len = 0;
 };
 
 [[noreturn]] inline void gff_fail(const char* line, size_t len, const std::string& what) {
@@ -93,6 +112,8 @@ inline void parse_gff_record(const char* line, size_t len, GFFRecord* r) {
     r->f[k] = f[k];
     r->fl[k] = fl[k];
   }
+  r->attr = line + at;
+  r->attr_len = len - at;
   if (!VCFArrayBuilder::parse_pos(f[3], fl[3], &r->start) || r->start < 1) gff_fail(line, len, "invalid start '" + std::string(f[3], fl[3]) + "'");
   if (!VCFArrayBuilder::parse_pos(f[4], fl[4], &r->end) || r->end < 1) gff_fail(line, len, "invalid end '" + std::string(f[4], fl[4]) + "'");
   r->has_score = !(fl[5] == 1 && f[5][0] == '.');
@@ -115,13 +136,126 @@ inline void parse_gff_record(const char* line, size_t len, GFFRecord* r) {
   else gff_fail(line, len, "invalid phase '" + std::string(f[7], fl[7]) + "'");
 }
 
+// Rust's str::from_utf8: no overlong forms, no surrogates, nothing above U+10FFFF
+inline bool gff_utf8_valid(const std::string& s) {
+  const size_t n = s.size();
+  for (size_t i = 0; i < n;) {
+    const unsigned c = (unsigned char)s[i];
+    if (c < 0x80) {
+      ++i;
+      continue;
+    }
+    size_t more;
+    unsigned lo = 0x80, hi = 0xBF;  // the range of the first continuation byte
+    if (c >= 0xC2 && c <= 0xDF) more = 1;
+    else if (c >= 0xE0 && c <= 0xEF) more = 2, lo = c == 0xE0 ? 0xA0 : 0x80, hi = c == 0xED ? 0x9F : 0xBF;
+    else if (c >= 0xF0 && c <= 0xF4) more = 3, lo = c == 0xF0 ? 0x90 : 0x80, hi = c == 0xF4 ? 0x8F : 0xBF;
+    else return false;
+    if (i + more >= n) return false;
+    for (size_t k = 1; k <= more; ++k) {
+      const unsigned d = (unsigned char)s[i + k];
+      if (d < (k == 1 ? lo : 0x80u) || d > (k == 1 ? hi : 0xBFu)) return false;
+    }
+    i += more + 1;
+  }
+  return true;
+}
+
+// the attributes column of a run of rows: the four offset levels and the two byte pools of Map<Utf8, List<Utf8>>
+struct GFFAttrColumn {
+  std::vector<int32_t> map_off{0}, key_off{0}, list_off{0}, item_off{0};  // rows -> entries -> (key bytes | items -> item bytes)
+  std::string keys, items;
+  size_t rows() const { return map_off.size() - 1; }
+  void clear() {
+    map_off.assign(1, 0);
+    key_off.assign(1, 0);
+    list_off.assign(1, 0);
+    item_off.assign(1, 0);
+    keys.clear();
+    items.clear();
+  }
+  // rows [o, o + n) as an array of their own (offsets rebased, bytes copied); the whole column with o = 0, n = rows()
+  struct ArrowArray* slice(size_t o, size_t n) const {
+    const int32_t e0 = map_off[o], e1 = map_off[o + n], i0 = list_off[(size_t)e0], i1 = list_off[(size_t)e1];
+    const int32_t k0 = key_off[(size_t)e0], k1 = key_off[(size_t)e1], b0 = item_off[(size_t)i0], b1 = item_off[(size_t)i1];
+    auto rebased = [](const std::vector<int32_t>& v, int32_t from, int32_t to, int32_t base) {
+      std::vector<int32_t> r((size_t)(to - from) + 1);
+      for (size_t k = 0; k < r.size(); ++k) r[k] = v[(size_t)from + k] - base;
+      return r;
+    };
+    auto arr = [] { return static_cast<struct ArrowArray*>(malloc(sizeof(struct ArrowArray))); };
+    struct ArrowArray *ka = arr(), *ia = arr(), *la = arr(), *ea = arr(), *ma = arr();
+    make_utf8(ka, rebased(key_off, e0, e1, k0), keys.substr((size_t)k0, (size_t)(k1 - k0)), {});
+    make_utf8(ia, rebased(item_off, i0, i1, b0), items.substr((size_t)b0, (size_t)(b1 - b0)), {});
+    make_list(la, rebased(list_off, e0, e1, i0), {}, ia);
+    make_struct(ea, e1 - e0, {ka, la});
+    make_list(ma, rebased(map_off, (int32_t)o, (int32_t)(o + n), e0), {}, ea);  // (a map's buffers are a list's: offsets over one child)
+    return ma;
+  }
+};
+
+// [p, p + n) percent-decoded onto `out`: '%' and two hex digits become that byte, any other '%' stays
+inline void gff_percent_decode(const char* p, size_t n, std::string* out) {
+  auto hex = [](char c) { return c >= '0' && c <= '9' ? c - '0' : c >= 'a' && c <= 'f' ? c - 'a' + 10 : c >= 'A' && c <= 'F' ? c - 'A' + 10 : -1; };
+  for (size_t i = 0; i < n; ++i) {
+    if (p[i] == '%' && i + 2 < n && hex(p[i + 1]) >= 0 && hex(p[i + 2]) >= 0) {
+      out->push_back((char)(hex(p[i + 1]) * 16 + hex(p[i + 2])));
+      i += 2;
+    } else {
+      out->push_back(p[i]);
+    }
+  }
+}
+
+// field 9 of record `r` by THE ATTRIBUTE RULES: validated, and appended to `col` as one row when there is one
+inline void parse_gff_attributes(const char* line, size_t len, const GFFRecord& r, GFFAttrColumn* col) {
+  const char* a = r.attr;
+  const size_t n = r.attr_len;
+  std::string tmp;
+  auto text = [&](const char* p, size_t m, std::string* pool, std::vector<int32_t>* off, const char* what) {
+    tmp.clear();
+    gff_percent_decode(p, m, &tmp);
+    if (!gff_utf8_valid(tmp)) gff_fail(line, len, std::string("attribute ") + what + " is not valid UTF-8");
+    if (col) {
+      pool->append(tmp);
+      off->push_back((int32_t)pool->size());
+    }
+  };
+  if (!(n == 0 || (n == 1 && a[0] == '.'))) {
+    size_t at = 0;
+    while (at <= n) {
+      const char* semi = static_cast<const char*>(memchr(a + at, ';', n - at));
+      const size_t end = semi ? (size_t)(semi - a) : n;
+      if (end == at) {
+        if (!semi && at > 0) break;  // the one empty piece behind a trailing ';'
+        gff_fail(line, len, "empty attribute (a ';' with nothing in front of it)");
+      }
+      const char* eq = static_cast<const char*>(memchr(a + at, '=', end - at));
+      if (!eq) gff_fail(line, len, "attribute '" + std::string(a + at, std::min<size_t>(end - at, 60)) + "' has no '='");
+      text(a + at, (size_t)(eq - (a + at)), col ? &col->keys : nullptr, col ? &col->key_off : nullptr, "key");
+      size_t v = (size_t)(eq - a) + 1;
+      for (;;) {
+        const char* comma = static_cast<const char*>(memchr(a + v, ',', end - v));
+        const size_t ve = comma ? (size_t)(comma - a) : end;
+        text(a + v, ve - v, col ? &col->items : nullptr, col ? &col->item_off : nullptr, "value");
+        if (!comma) break;
+        v = ve + 1;
+      }
+      if (col) col->list_off.push_back((int32_t)col->item_off.size() - 1);
+      at = end + 1;
+    }
+  }
+  if (col) col->map_off.push_back((int32_t)col->key_off.size() - 1);
+}
+
 inline bool gff_region_hit(const GFFRecord& r, const Region& rg) {
   return r.fl[0] == rg.name.size() && memcmp(r.f[0], rg.name.data(), r.fl[0]) == 0 && r.start >= rg.start && r.start <= rg.end;
 }
 
 class GFFArrayBuilder : public ExonArrayBuilder {
  public:
-  GFFArrayBuilder(Dictionary* seqnames, Dictionary* sources, Dictionary* types) : dicts_{seqnames, sources, types} {}
+  GFFArrayBuilder(Dictionary* seqnames, Dictionary* sources, Dictionary* types, bool attributes = false)
+      : dicts_{seqnames, sources, types}, with_attrs_(attributes) {}
 
   void append(const GFFRecord& r) {
     for (int k = 0; k < 3; ++k) ids_[k].append_value(dicts_[k]->lookup_or_insert(r.f[k], r.fl[k]));
@@ -144,6 +278,10 @@ class GFFArrayBuilder : public ExonArrayBuilder {
     out.push_back(score_.finish());
     out.push_back(strand_.finish(utf8_array(gff_strand_names())));
     out.push_back(phase_.finish(utf8_array(gff_phase_names())));
+    if (with_attrs_) {
+      out.push_back(attrs_.slice(0, attrs_.rows()));
+      attrs_.clear();
+    }
     rows_ = 0;
     return out;
   }
@@ -159,24 +297,33 @@ class GFFArrayBuilder : public ExonArrayBuilder {
   PrimitiveBuilder<float>& scores() { return score_; }
   PrimitiveBuilder<int32_t>& strands() { return strand_; }
   PrimitiveBuilder<int32_t>& phases() { return phase_; }
+  bool with_attributes() const { return with_attrs_; }
+  GFFAttrColumn& attributes() { return attrs_; }  // (the caller appends the row's map: parse_gff_attributes)
 
  private:
   Dictionary* dicts_[3];
   PrimitiveBuilder<int32_t> ids_[3], strand_, phase_;
   PrimitiveBuilder<int64_t> start_, end_;
   PrimitiveBuilder<float> score_;
+  bool with_attrs_;
+  GFFAttrColumn attrs_;
   size_t rows_ = 0;
 };
 
 // one slab of GFF text parsed with slab-local dictionaries (re-keyed by the reader in file order)
+struct GFFSlabConfig {
+  RegionFilter filter;
+  bool attributes = false;
+};
 struct GFFSlab : TextSlab {
   Dictionary dicts[3];
   std::unique_ptr<GFFArrayBuilder> b;
   size_t rows = 0;
 };
-inline void parse_gff_slab(GFFSlab& s, const void* vfilter) {
-  const RegionFilter& filter = *static_cast<const RegionFilter*>(vfilter);
-  s.b.reset(new GFFArrayBuilder(&s.dicts[0], &s.dicts[1], &s.dicts[2]));
+inline void parse_gff_slab(GFFSlab& s, const void* vcfg) {
+  const GFFSlabConfig& sc = *static_cast<const GFFSlabConfig*>(vcfg);
+  const RegionFilter& filter = sc.filter;
+  s.b.reset(new GFFArrayBuilder(&s.dicts[0], &s.dicts[1], &s.dicts[2], sc.attributes));
   const char* p = s.data();
   const char* end = p + s.len;
   s.b->reserve(s.len / 64 + 16);
@@ -188,7 +335,9 @@ inline void parse_gff_slab(GFFSlab& s, const void* vfilter) {
     if (nl && len && p[len - 1] == '\r') --len;
     if (gff_is_record(p, len)) {
       parse_gff_record(p, len, &rec);
-      if (!filter.active || gff_region_hit(rec, filter.region)) s.b->append(rec);
+      const bool keep = !filter.active || gff_region_hit(rec, filter.region);
+      if (sc.attributes) parse_gff_attributes(p, len, rec, keep ? &s.b->attributes() : nullptr);
+      if (keep) s.b->append(rec);
     }
     p = next;
   }
@@ -198,6 +347,8 @@ inline void parse_gff_slab(GFFSlab& s, const void* vfilter) {
 class GFFBatchReader : public BatchReader {
  public:
   GFFBatchReader(const std::string& path, Compression c, GFFConfig cfg) : cfg_(std::move(cfg)) {
+    slab_cfg_.filter = cfg_.filter;
+    slab_cfg_.attributes = attributes();
     if (cfg_.filter.active && cfg_.filter.use_index) {
       // get_byte_range_for_file (indexed_bgzf_file.rs:52-112) with the index's own column preset
       const BinningIndex idx = read_tabix(path + ".tbi");
@@ -218,10 +369,11 @@ class GFFBatchReader : public BatchReader {
     const int threads = cfg_.threads > 0 ? cfg_.threads : decode_threads();
     if (threads > 1 && file_size(path) >= (8 << 20) && !cfg_.defer_decode)
       pipe_.reset(new SlabPipeline<GFFSlab>(r_->release_source(), std::string(), 1, threads, [](GFFSlab& s, const void* c2) { parse_gff_slab(s, c2); },
-                                            &cfg_.filter));
+                                            &slab_cfg_));
   }
 
   const GFFConfig& config() const { return cfg_; }
+  bool attributes() const { return (cfg_.projection & EXON_HIP_PROJECT_GFF_ATTRIBUTES) != 0; }
   // the whole file as a raw byte stream (GPU-side parsing; GFF has no header to read first); only valid before the first read_batch
   std::unique_ptr<ByteSource> take_stream(std::string* carry) {
     if (pipe_ || n_chunks >= 0 || !r_) return nullptr;
@@ -232,14 +384,15 @@ class GFFBatchReader : public BatchReader {
 
   bool read_batch(struct ArrowArray* out) override {
     if (pipe_) return read_batch_parallel(out);
-    GFFArrayBuilder b(&dicts[0], &dicts[1], &dicts[2]);
+    GFFArrayBuilder b(&dicts[0], &dicts[1], &dicts[2], attributes());
     std::string line;
     GFFRecord rec;
     while ((int64_t)b.len() < cfg_.batch_size && next_line(&line)) {
       if (!gff_is_record(line.data(), line.size())) continue;
       parse_gff_record(line.data(), line.size(), &rec);
-      if (cfg_.filter.active && !gff_region_hit(rec, cfg_.filter.region)) continue;
-      b.append(rec);
+      const bool keep = !cfg_.filter.active || gff_region_hit(rec, cfg_.filter.region);
+      if (attributes()) parse_gff_attributes(line.data(), line.size(), rec, keep ? &b.attributes() : nullptr);
+      if (keep) b.append(rec);
     }
     if (b.is_empty()) return false;
     b.try_into_record_batch(out);
@@ -255,6 +408,16 @@ class GFFBatchReader : public BatchReader {
                                              new_field("f", "score", true),
                                              new_field("i", "strand", true, new_field("u", "", false)),
                                              new_field("i", "phase", true, new_field("u", "", false))};
+    if (attributes()) {  // Field::new_map("attributes", "entries", keys, values, sorted = false) of config.rs:81-104
+      auto field = [](const char* fmt, const char* name, bool nullable, std::vector<struct ArrowSchema*> k) {
+        struct ArrowSchema* f = static_cast<struct ArrowSchema*>(malloc(sizeof *f));
+        make_schema(f, fmt, name, nullable, std::move(k));
+        return f;
+      };
+      struct ArrowSchema* values = field("+l", "values", true, {new_field("u", "item", true)});
+      struct ArrowSchema* entries = field("+s", "entries", false, {new_field("u", "keys", false), values});
+      kids.push_back(field("+m", "attributes", false, {entries}));
+    }
     make_schema(out, "+s", "", false, kids);
   }
 
@@ -321,12 +484,14 @@ class GFFBatchReader : public BatchReader {
     kids.push_back(slice(b.scores(), 4, nullptr));
     kids.push_back(slice(b.strands(), 4, utf8_array(gff_strand_names())));
     kids.push_back(slice(b.phases(), 4, utf8_array(gff_phase_names())));
+    if (b.with_attributes()) kids.push_back(b.attributes().slice(o, n));
     make_struct(out, (int64_t)n, std::move(kids));
     cur_pos_ += n;
     return true;
   }
 
   GFFConfig cfg_;
+  GFFSlabConfig slab_cfg_;  // what the slab workers read (outlives the pipeline: declared in front of it)
   std::unique_ptr<BufReader> r_;
   std::unique_ptr<ChunkSource> chunks_;
   std::unique_ptr<BgzfReader> bgzf_;  // reference_block_quirk: the chunks' block ranges

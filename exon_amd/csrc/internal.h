@@ -99,6 +99,17 @@ int exon_text_sam(exon_hip_ctx* ctx, void* stream, ExonTextScratch** scratch, co
 int exon_text_fastq(exon_hip_ctx* ctx, void* stream, ExonTextScratch** scratch, const exon_hip_fastq_views* views, int64_t n_bytes, ExonFastqText* out);
 int exon_text_bcf(exon_hip_ctx* ctx, void* stream, ExonTextScratch** scratch, const uint8_t* d_data, int64_t n_bytes, const uint32_t* d_rec_of_row, int64_t n_rows, uint64_t projection,
                   ExonBcfText* out, int64_t* n_undecided);
+// GFF `attributes` (Map<Utf8, List<Utf8>>, host/gff.h's ATTRIBUTE RULES): rows -> entries -> (key bytes | items -> item bytes),
+// bytes after percent-decoding.  d_text is the ALIGNED slab the parser indexed; d_attr_off / d_attr_len every row's ninth field
+// in it (k_parse_gff_lines<true>).  n_undecided != 0: a field with a byte >= 0x80 (raw or decoded: UTF-8 is the host's to
+// validate), a piece without '=', an empty piece other than the one behind a trailing ';', or more items than item_offsets holds
+struct ExonGffText {
+  const int32_t *map_offsets, *key_offsets, *list_offsets, *item_offsets;  // [n_rows + 1], [n_entries + 1] twice, [n_items + 1]
+  const uint8_t *key_values, *item_values;
+  int64_t n_entries, n_items, n_key_bytes, n_item_bytes;
+};
+int exon_text_gff(exon_hip_ctx* ctx, void* stream, ExonTextScratch** scratch, const uint8_t* d_text, int64_t n_bytes, const uint32_t* d_attr_off, const uint32_t* d_attr_len,
+                  int64_t n_rows, ExonGffText* out, int64_t* n_undecided);
 void exon_text_scratch_destroy(ExonTextScratch* s);
 // the parsers' own indexes the text columns are built from (valid until the next parse call)
 const unsigned* exon_hip_vcf_parser_newlines(exon_hip_vcf_parser* p);
@@ -110,6 +121,8 @@ constexpr size_t EXON_DICT_NAMES_CAP = (size_t)EXON_DICT_POOL + EXON_HIP_MAX_GRO
 int exon_hip_vcf_parser_filters_so_far(exon_hip_vcf_parser* p, char* buf, size_t cap, int32_t* n_filters);
 int exon_hip_vcf_parser_info_values_so_far(exon_hip_vcf_parser* p, int32_t key, char* buf, size_t cap, int32_t* n_values);
 int exon_hip_gff_parser_names_so_far(exon_hip_gff_parser* p, int32_t column, char* buf, size_t cap, int32_t* n_names);
+// gpu_parse.hip: the aligned slab of the last parse call and every row's ninth field in it (after exon_hip_gff_parser_want_attributes)
+void exon_hip_gff_parser_attr_fields(exon_hip_gff_parser* p, const uint8_t** text, int64_t* n_bytes, const uint32_t** off, const uint32_t** len);
 int exon_hip_bcf_parser_filters_so_far(exon_hip_bcf_parser* p, int32_t* lists, int32_t* counts, int32_t cap, int32_t* n_filters);
 const unsigned* exon_hip_sam_parser_newlines(exon_hip_sam_parser* p);      // gpu_parse.hip: the same for SAM lines      // gpu_parse.hip: byte offset of every line's '\n' in the aligned slab
 const uint32_t* exon_hip_bam_parser_row_records(exon_hip_bam_parser* p);

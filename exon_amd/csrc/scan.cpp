@@ -331,6 +331,7 @@ static std::unique_ptr<exon::BatchReader> open_reader(const exon_hip_scan& s, De
       exon::GFFConfig fresh;
       fresh.batch_size = bs;
       fresh.filter = rf;
+      fresh.projection = s.opt.projection;
       fresh.reference_block_quirk = reference_tail_quirk(rf);
       exon::GFFConfig cfg = config(s.gff(), fresh);
       cfg.defer_decode = device;
@@ -379,9 +380,9 @@ int exon_hip_scan_open(const char* path, const exon_hip_scan_options* o, exon_hi
       rf.use_index = o->use_index != 0;
     }
     s->region = rf;
-    if (o->projection && o->format == EXON_HIP_FORMAT_GFF)
-      return fail(nullptr, EXON_HIP_EUNSUPPORTED, "exon_hip_scan_options.projection: the GFF `attributes` column (Map<Utf8, List<Utf8>>) is not built");
-    if (o->projection && o->format != EXON_HIP_FORMAT_VCF && o->format != EXON_HIP_FORMAT_BAM && o->format != EXON_HIP_FORMAT_BCF && o->format != EXON_HIP_FORMAT_SAM)
+    if (o->format == EXON_HIP_FORMAT_GFF && (o->projection & ~EXON_HIP_PROJECT_GFF_ATTRIBUTES))
+      return fail(nullptr, EXON_HIP_EUNSUPPORTED, "exon_hip_scan_options.projection 0x%llx: GFF knows one projected column, `attributes` (Map<Utf8, List<Utf8>>), by EXON_HIP_PROJECT_GFF_ATTRIBUTES (256: the column's index in the reference's schema)", (unsigned long long)o->projection);
+    if (o->projection && o->format != EXON_HIP_FORMAT_VCF && o->format != EXON_HIP_FORMAT_BAM && o->format != EXON_HIP_FORMAT_BCF && o->format != EXON_HIP_FORMAT_SAM && o->format != EXON_HIP_FORMAT_GFF)
       return fail(nullptr, EXON_HIP_EUNSUPPORTED, "exon_hip_scan_options.projection: the id / ref / alt (/ info / formats) and name / cigar / sequence / quality_score columns are built for VCF, BCF, BAM and SAM scans");
     switch (o->format) {
       case EXON_HIP_FORMAT_VCF:
@@ -1945,8 +1946,10 @@ struct Span {
   const T* begin() const { return p; }
 };
 struct HostText {
-  bool vcf = false, bam = false, bcf = false;
+  bool vcf = false, bam = false, bcf = false, gff = false;
   uint64_t projection = 0;
+  // GFF attributes: off[0] = the map's offsets, key_off / val[0] the keys, list_off the value lists, gff_item_off / val[1] their items
+  Span<int32_t> key_off, list_off, gff_item_off;
   Span<int32_t> alt_item_off;  // BCF: off[1] = alt's list offsets, alt_item_off / val[1] its items
   Span<int32_t> off[3], item_off, qual_off;  // qual_off: quality_scores' own list offsets (SAM), else off[2]
   Span<uint8_t> val[3], valid[2];
@@ -1965,12 +1968,13 @@ static thread_local double g_t_text_kernels = 0, g_t_fetch_text = 0, g_t_fetch_c
 static constexpr int64_t K_ZERO_ROWS = 65000;
 static const int32_t k_zero_offsets[K_ZERO_ROWS + 64] = {0};
 // the projected text columns of one slab: `build` fills the member of `format` on the device (export_slab calls it once it knows
-// that the slab keeps rows at all)
+// that the slab keeps rows at all; for GFF `attributes` also when it keeps none: the build is the validation of every ninth field)
 struct SlabText {
   int format = 0;
   ExonVcfText vcf;
   ExonBamText bam;  // BAM and SAM
   ExonBcfText bcf;
+  ExonGffText gff;
   std::function<int()> build;
 };
 static int fetch_text(exon_hip_ctx* ctx, SlabCopier* cp, size_t also_reserve, int64_t n_rows, uint64_t projection, const SlabText& t, HostText* h, bool big_batches) {
@@ -2042,6 +2046,16 @@ static int fetch_text(exon_hip_ctx* ctx, SlabCopier* cp, size_t also_reserve, in
       if (bt->qual_offsets != bt->seq_offsets) get(h->qual_off, bt->qual_offsets, n + 1);  // SAM: QUAL may be '*' next to a SEQ
     }
   }
+  if (t.format == EXON_HIP_FORMAT_GFF && (projection & EXON_HIP_PROJECT_GFF_ATTRIBUTES)) {
+    const ExonGffText* gt = &t.gff;
+    h->gff = true;
+    get(h->off[0], gt->map_offsets, n + 1);
+    get(h->key_off, gt->key_offsets, (size_t)gt->n_entries + 1);
+    get(h->val[0], gt->key_values, (size_t)gt->n_key_bytes);
+    get(h->list_off, gt->list_offsets, (size_t)gt->n_entries + 1);
+    get(h->gff_item_off, gt->item_offsets, (size_t)gt->n_items + 1);
+    get(h->val[1], gt->item_values, (size_t)gt->n_item_bytes);
+  }
   size_t total = 64;
   for (const Want& w : wants) total += (w.count * w.elem + 63) & ~(size_t)63;
   if (!cp->reserve(total + 256 * wants.size() + also_reserve)) return fail(ctx, EXON_HIP_ENOMEM, "no device staging buffer of %zu bytes for a slab's string columns", total);
@@ -2100,6 +2114,13 @@ static void text_batch(const HostText& h, const int64_t* rows, int64_t r0, int64
         struct ArrowArray* items = utf8_view(h.alt_item_off, h.val[1], nullptr, 0, (int64_t)h.alt_item_off.n - 1);
         kids->push_back(exon::arena_array(arena, n, r0, 0, 2, nullptr, h.off[1].data(), nullptr, items));
       }
+    }
+    if (h.gff) {  // the slab's entries, keys, value lists and items shared by every batch; the map cut by its offset
+      struct ArrowArray* keys = utf8_view(h.key_off, h.val[0], nullptr, 0, (int64_t)h.key_off.n - 1);
+      struct ArrowArray* items = utf8_view(h.gff_item_off, h.val[1], nullptr, 0, (int64_t)h.gff_item_off.n - 1);
+      struct ArrowArray* values = exon::arena_array(arena, (int64_t)h.list_off.n - 1, 0, 0, 2, nullptr, h.list_off.data(), nullptr, items);
+      struct ArrowArray* entries = exon::arena_struct2(arena, (int64_t)h.key_off.n - 1, keys, values);
+      kids->push_back(exon::arena_array(arena, n, r0, 0, 2, nullptr, h.off[0].data(), nullptr, entries));
     }
     if (h.bam) {
       if (h.projection & EXON_HIP_PROJECT_BAM_NAME) kids->push_back(utf8_view(h.off[0], h.val[0], &h.valid[0], r0, n));
@@ -2167,6 +2188,23 @@ static void text_batch(const HostText& h, const int64_t* rows, int64_t r0, int64
     if (h.projection & EXON_HIP_PROJECT_VCF_ID) kids->push_back(list_of(h.off[0], h.item_off, h.val[0]));
     if (h.projection & EXON_HIP_PROJECT_VCF_REF) kids->push_back(utf8(h.off[2], h.val[2], nullptr));
     if (h.projection & EXON_HIP_PROJECT_VCF_ALT) kids->push_back(list_of(h.off[1], h.alt_item_off, h.val[1]));
+  }
+  if (h.gff) {  // the map gather: every kept row's entries, keys, lists and items, copied
+    exon::GFFAttrColumn col;
+    for (int64_t i = 0; i < n; ++i) {
+      const int64_t r = row_at(i);
+      for (int32_t e = h.off[0][(size_t)r]; e < h.off[0][(size_t)r + 1]; ++e) {
+        col.keys.append(reinterpret_cast<const char*>(h.val[0].data()) + h.key_off[(size_t)e], (size_t)(h.key_off[(size_t)e + 1] - h.key_off[(size_t)e]));
+        col.key_off.push_back((int32_t)col.keys.size());
+        for (int32_t k = h.list_off[(size_t)e]; k < h.list_off[(size_t)e + 1]; ++k) {
+          col.items.append(reinterpret_cast<const char*>(h.val[1].data()) + h.gff_item_off[(size_t)k], (size_t)(h.gff_item_off[(size_t)k + 1] - h.gff_item_off[(size_t)k]));
+          col.item_off.push_back((int32_t)col.items.size());
+        }
+        col.list_off.push_back((int32_t)col.item_off.size() - 1);
+      }
+      col.map_off.push_back((int32_t)col.key_off.size() - 1);
+    }
+    kids->push_back(col.slice(0, (size_t)n));
   }
   if (h.bam) {
     if (h.projection & EXON_HIP_PROJECT_BAM_NAME) kids->push_back(utf8(h.off[0], h.val[0], &h.valid[0]));
@@ -2261,6 +2299,10 @@ static int export_slab(exon_hip_scan* scan, const exon_hip_column* sc, int64_t n
     if (too_many) {  // (kept is not complete then: the gather below counts for itself)
       runs.clear();
     } else if (kept == 0) {
+      // GFF `attributes`: field 9 of every record is validated, kept or not (host/gff.h) -- the measure pass runs over a slab that
+      // sends nothing too, and hands the file over when it meets a row the host reader must judge
+      if (projected && projected->format == EXON_HIP_FORMAT_GFF)
+        if (const int rc = projected->build()) return rc;
       return EXON_HIP_OK;
     }
     const char* gv = getenv("EXON_HIP_EXPORT_GATHER");  // A/B, read for every slab: 1 = every filtered slab through the row-by-row gather
@@ -2397,7 +2439,7 @@ static int export_slab(exon_hip_scan* scan, const exon_hip_column* sc, int64_t n
       }
       const double tv1 = now_s();
       g_t_views += tv1 - tv0;
-      if (text.vcf || text.bam || text.bcf) text_batch(text, nullptr, b0, n, &kids, arena);
+      if (text.vcf || text.bam || text.bcf || text.gff) text_batch(text, nullptr, b0, n, &kids, arena);
       g_t_text_batch += now_s() - tv1;
       struct ArrowArray* out = static_cast<struct ArrowArray*>(malloc(sizeof *out));
       exon::make_struct_of_arena(out, n, arena, kids);
@@ -2440,7 +2482,7 @@ static int export_slab(exon_hip_scan* scan, const exon_hip_column* sc, int64_t n
         kids.push_back(a);
       }
     }
-    if (text.vcf || text.bam || text.bcf) text_batch(text, keep.data() + b0, 0, n, &kids);
+    if (text.vcf || text.bam || text.bcf || text.gff) text_batch(text, keep.data() + b0, 0, n, &kids);
     struct ArrowArray* out = static_cast<struct ArrowArray*>(malloc(sizeof *out));
     exon::make_struct(out, n, std::move(kids));
     if (const int rc = push_batch(ex, out, n)) return rc;
@@ -2740,6 +2782,15 @@ static int build_text(exon_hip_scan* scan, exon_hip_ctx* ctx, hipStream_t hs, co
     case EXON_HIP_FORMAT_SAM:  // undecided: a CIGAR / QUAL the device would not print the way the reader does
       r = exon_text_sam(ctx, hs, &scan->text_scratch, d_text, (int64_t)n, exon_hip_sam_parser_newlines(scan->parser.as<exon_hip_sam_parser>()), n_rows, proj, &t->bam, &undecided);
       break;
+    case EXON_HIP_FORMAT_GFF: {  // undecided: a field the ATTRIBUTE RULES refuse or whose UTF-8 the host must check; more items than the scratch holds
+      const uint8_t* text = nullptr;
+      int64_t text_bytes = 0;
+      const uint32_t *off = nullptr, *len = nullptr;
+      exon_hip_gff_parser_attr_fields(scan->parser.as<exon_hip_gff_parser>(), &text, &text_bytes, &off, &len);
+      if (!off || !len || !text) return fail(ctx, EXON_HIP_ESTATE, "GFF attributes: the slab was parsed without its ninth fields recorded");
+      r = exon_text_gff(ctx, hs, &scan->text_scratch, text, text_bytes, off, len, n_rows, &t->gff, &undecided);
+      break;
+    }
   }
   if (!r && undecided) r = 1;
   // the fill kernels read the slab's text: the source takes a slab's buffer for free once its parser has returned and inflates the
@@ -2828,6 +2879,12 @@ static int consume_text_gpu(exon_hip_stream* st, exon_hip_scan* scan, int64_t* r
       rc = create_parser(scan, ctx, (int64_t)src->max_text_bytes());
       if (rc) break;
     }
+    // batches with GFF `attributes`: the line kernel records every row's ninth field (asked for here, not where the parser is made:
+    // a parser may outlive the pass it was made for; a fused plan reads columns 0, 3, 4 and nothing new runs)
+    if (scan->gff()) {
+      rc = exon_hip_gff_parser_want_attributes(scan->parser.as<exon_hip_gff_parser>(), scan->exporter && (scan->opt.projection & EXON_HIP_PROJECT_GFF_ATTRIBUTES) ? 1 : 0);
+      if (rc) break;
+    }
     if (si == 0) {
       t_init = now_s();
       if (trace) fprintf(stderr, "[exon-hip pipe] source init %.1f ms, parser create %.1f ms\n", (t_src - t_begin) * 1e3, (t_init - t_src) * 1e3);
@@ -2881,7 +2938,8 @@ static int consume_text_gpu(exon_hip_stream* st, exon_hip_scan* scan, int64_t* r
           row_mask = scan->d_region_mask;
         }
         if (scan->exporter && scan->opt.projection) {
-          // the reference's string / list columns of this slab (by export_slab, once it knows that the slab keeps rows at all)
+          // the reference's string / list columns of this slab (by export_slab, once it knows that the slab keeps rows at all -- or,
+          // GFF `attributes`, that it keeps none: every record's ninth field is validated)
           SlabText text;
           text.format = scan->format;
           text.build = [&] { return build_text(scan, ctx, hs, d_text, n, n_rows, &text); };

@@ -11,6 +11,7 @@
 //        cigar      Utf8, "<len><op>..." with ops MIDNSHP=X           :144-167
 //        sequence   Utf8, 4-bit codes through "=ACMGRSVTWYHKDBN"      :178-183
 //        quality_scores  List<Int64>, the raw bytes as i8 -> i64      :184-201
+//   GFF  attributes Map<Utf8, List<Utf8>>, never NULL                 exon-gff/src/array_builder.rs:141-165 (host/gff.h: THE ATTRIBUTE RULES)
 // One thread per row measures, an exclusive scan turns lengths into offsets, one thread per row fills (rows are short; the bytes
 // of a slab are read twice, L2-resident the second time).  Nothing here is on the fused kernels' path: a scan that projects none of
 // these columns launches none of this.
@@ -454,6 +455,123 @@ __global__ __launch_bounds__(TPB) void k_bcf_fill(const uint8_t* __restrict__ d,
   }
 }
 
+// ---- GFF ---------------------------------------------------------------------------------------------------------------------------
+// `attributes`, Map<Utf8, List<Utf8>>, by THE ATTRIBUTE RULES of host/gff.h: the ninth field of row r is text[off[r], off[r] +
+// len[r]) (k_parse_gff_lines<true> recorded it under the row's RANK, so ranked slabs and row = line slabs look the same here).
+// Both kernels walk the field once, byte by byte, through the same states: pieces end at ';', the key at the piece's first '=',
+// items at ',' behind it; "%XX" is one byte of the key or item it stands in (hex digits are no separators, so an escape never
+// straddles one).  A byte >= 0x80, raw or decoded, makes the row undecided: whether it is UTF-8 is the host reader's to say.
+__device__ __forceinline__ int gff_hex(unsigned c) {
+  const unsigned d = c - (unsigned)'0', l = (c | 0x20u) - (unsigned)'a';
+  return d <= 9u ? (int)d : l <= 5u ? (int)l + 10 : -1;
+}
+// the byte at text[i] of a field that ends at `end`, decoded: *step = 3 for an escape, else 1
+__device__ __forceinline__ unsigned gff_attr_byte(const uint8_t* __restrict__ text, unsigned i, unsigned end, unsigned* step) {
+  const unsigned c = text[i];
+  *step = 1;
+  if (c == '%' && i + 2 < end) {
+    const int h = gff_hex(text[i + 1]), l = gff_hex(text[i + 2]);
+    if ((h | l) >= 0) {
+      *step = 3;
+      return (unsigned)(h * 16 + l) | 0x100u;  // (bit 8: decoded, never a separator)
+    }
+  }
+  return c;
+}
+struct GffLens {
+  uint32_t *entries, *items, *key_bytes, *item_bytes;  // per row
+};
+__global__ __launch_bounds__(TPB) void k_gff_attr_measure(const uint8_t* __restrict__ text, const uint32_t* __restrict__ attr_off, const uint32_t* __restrict__ attr_len,
+                                                          unsigned n_rows, GffLens o, unsigned* __restrict__ undecided) {
+  const unsigned row = blockIdx.x * TPB + threadIdx.x;
+  bool bad = false;
+  if (row < n_rows) {
+    const unsigned begin = attr_off[row], end = begin + attr_len[row];
+    unsigned entries = 0, items = 0, kb = 0, ib = 0;
+    if (!(end == begin || (end == begin + 1 && text[begin] == '.'))) {
+      unsigned piece = 0;   // bytes of the piece so far (raw)
+      bool in_key = true;   // in front of the piece's first '='
+      for (unsigned i = begin, step; i < end; i += step) {
+        const unsigned c = gff_attr_byte(text, i, end, &step);
+        bad |= (c & 0x80u) != 0;
+        if (c == ';') {
+          bad |= piece == 0 || in_key;  // an empty piece, or one without '='
+          piece = 0;
+          in_key = true;
+          continue;
+        }
+        piece += step;
+        if (in_key) {
+          if (c == '=') {
+            in_key = false;
+            ++entries;
+            ++items;
+          } else {
+            ++kb;
+          }
+        } else if (c == ',') {
+          ++items;
+        } else {
+          ++ib;
+        }
+      }
+      bad |= piece != 0 && in_key;  // (piece == 0 here: the one empty piece behind a trailing ';')
+    }
+    o.entries[row] = bad ? 0u : entries;
+    o.items[row] = bad ? 0u : items;
+    o.key_bytes[row] = bad ? 0u : kb;
+    o.item_bytes[row] = bad ? 0u : ib;
+  }
+  const unsigned long long bb = __ballot(bad);
+  if ((threadIdx.x & 63) == 0 && bb) atomicAdd(undecided, (unsigned)__popcll(bb));
+}
+// row_* : the scans of the four lengths (the row's first entry, item, key byte, item byte); row_entry is the map's offsets buffer
+__global__ __launch_bounds__(TPB) void k_gff_attr_fill(const uint8_t* __restrict__ text, const uint32_t* __restrict__ attr_off, const uint32_t* __restrict__ attr_len,
+                                                       unsigned n_rows, const int32_t* __restrict__ row_entry, const int32_t* __restrict__ row_item,
+                                                       const int32_t* __restrict__ row_kb, const int32_t* __restrict__ row_ib, int32_t* __restrict__ key_off,
+                                                       int32_t* __restrict__ list_off, int32_t* __restrict__ item_off, uint8_t* __restrict__ key_values,
+                                                       uint8_t* __restrict__ item_values, unsigned entries_total, unsigned items_total, unsigned kb_total,
+                                                       unsigned ib_total) {
+  const unsigned row = blockIdx.x * TPB + threadIdx.x;
+  if (row >= n_rows) return;
+  const unsigned begin = attr_off[row], end = begin + attr_len[row];
+  if (row_entry[row + 1] > row_entry[row]) {  // (a row of no entries writes nothing: "", ".")
+    unsigned e = (unsigned)row_entry[row], it = (unsigned)row_item[row], kw = (unsigned)row_kb[row], iw = (unsigned)row_ib[row];
+    bool in_key = true, fresh = true;  // fresh: the next byte opens a piece
+    for (unsigned i = begin, step; i < end; i += step) {
+      const unsigned c = gff_attr_byte(text, i, end, &step);
+      if (c == ';') {
+        in_key = true;
+        fresh = true;
+        continue;
+      }
+      if (fresh) {
+        key_off[e] = (int32_t)kw;
+        list_off[e] = (int32_t)it;
+        ++e;
+        fresh = false;
+      }
+      if (in_key) {
+        if (c == '=') {
+          in_key = false;
+          item_off[it++] = (int32_t)iw;
+        } else {
+          key_values[kw++] = (uint8_t)c;
+        }
+      } else if (c == ',') {
+        item_off[it++] = (int32_t)iw;
+      } else {
+        item_values[iw++] = (uint8_t)c;
+      }
+    }
+  }
+  if (row == n_rows - 1) {  // the closing offsets (entry 0 of each level when the slab has no entry at all)
+    key_off[entries_total] = (int32_t)kb_total;
+    list_off[entries_total] = (int32_t)items_total;
+    item_off[items_total] = (int32_t)ib_total;
+  }
+}
+
 struct ExonTextScratch {
   PoolBufs bufs, qual_bufs;  // qual_bufs: the quality_scores values, grown on demand
   int64_t max_rows = 0, max_bytes = 0;
@@ -467,7 +585,8 @@ struct ExonTextScratch {
   unsigned* totals = nullptr;    // device [4]
   unsigned* h_totals = nullptr;  // pinned
   int32_t* item_off = nullptr;   // VCF / BCF id items
-  int32_t* item_off2 = nullptr;  // BCF alt items
+  int32_t* item_off2 = nullptr;  // BCF alt items; GFF: the entries' list offsets (item_off: their key offsets)
+  int32_t* item_off3 = nullptr;  // GFF: the items' byte offsets
   unsigned* totals5 = nullptr;   // device [8]: the five totals of the BCF columns
   unsigned* h_totals5 = nullptr; // pinned
   uint8_t* values[4] = {nullptr, nullptr, nullptr, nullptr};
@@ -498,7 +617,14 @@ void exon_text_scratch_destroy(ExonTextScratch* s) { delete s; }
 //   SAM    values[0], [1], [2] (max_bytes = n_bytes): QNAME / CIGAR / SEQ fields, copied as they are: <= n_bytes each: fits
 //   SAM    qual: an item per QUAL byte; qual_for grows it to the total before the fill: fits
 //   FASTQ  values[0 .. 3] (max_bytes = n_bytes + 16): name / description / sequence / quality, disjoint parts of the text: <= n_bytes: fits
-static int scratch_for(exon_hip_ctx* ctx, ExonTextScratch** sp, int64_t max_rows, int64_t max_bytes, bool vcf, int n_cols = 3) {
+//   GFF    (max_bytes = n_bytes; F = the bytes of the slab's ninth fields; a record has at least 16 bytes in front of its ninth field
+//          -- eight fields, eight TABs -- and its LF behind it: F <= n_bytes - 17 n_rows)
+//   GFF    values[0]: decoded key bytes, values[1]: decoded item bytes; a byte of either comes from a byte of the field or from three: <= F each: fits
+//   GFF    item_off, item_off2 (an entry's key offset and list offset): an entry is a piece of at least a byte ("=") and all but a
+//                    row's last are followed by a ';': a field of k bytes holds up to (k + 1) / 2, a slab up to (F + n_rows) / 2 <=
+//                    n_bytes / 2 entries + 1 closing, against max_bytes / 2 + max_rows + 66: fits
+//   GFF    item_off3 (an item's byte offset): "=,,,," is an item a byte: up to F items + 1 entry, against the same size: checked
+static int scratch_for(exon_hip_ctx* ctx, ExonTextScratch** sp, int64_t max_rows, int64_t max_bytes, bool vcf, int n_cols = 3, bool gff = false) {
   ExonTextScratch* s = *sp;
   if (s && s->max_rows >= max_rows && s->max_bytes >= max_bytes && s->n_cols >= n_cols) return EXON_HIP_OK;
   delete s;
@@ -516,7 +642,14 @@ static int scratch_for(exon_hip_ctx* ctx, ExonTextScratch** sp, int64_t max_rows
   for (int k = 0; k < n_cols; ++k) {
     s->len[k] = b.take<uint32_t>(r * 4);
     s->off[k] = b.take<int32_t>((r + 1) * 4);
-    if (k < 4) s->values[k] = b.take<uint8_t>((size_t)max_bytes + 64);
+    if (k < (gff ? 2 : 4)) s->values[k] = b.take<uint8_t>((size_t)max_bytes + 64);
+  }
+  if (gff) {
+    s->item_off = b.take<int32_t>(s->item_cap * 4);
+    s->item_off2 = b.take<int32_t>(s->item_cap * 4);
+    s->item_off3 = b.take<int32_t>(s->item_cap * 4);
+    s->totals5 = b.take<unsigned>(32);
+    s->h_totals5 = b.pinned<unsigned>(32);
   }
   if (n_cols >= 5) {  // BCF: alt items
     s->item_off2 = b.take<int32_t>(s->item_cap * 4);
@@ -530,7 +663,7 @@ static int scratch_for(exon_hip_ctx* ctx, ExonTextScratch** sp, int64_t max_rows
     s->field_len = b.take<uint32_t>(3 * r * 4);
     s->item_off = b.take<int32_t>(s->item_cap * 4);
   }
-  if (n_cols >= 4) s->sam_field_off = b.take<uint32_t>(4 * r * 4);
+  if (n_cols >= 4 && !gff) s->sam_field_off = b.take<uint32_t>(4 * r * 4);
   s->sums = b.take<unsigned>((r / TPB + 4) * 4);
   s->totals = b.take<unsigned>(16);
   s->h_totals = b.pinned<unsigned>(16);  // (4 totals: the FASTQ columns use them all)
@@ -779,5 +912,46 @@ int exon_text_bcf(exon_hip_ctx* ctx, void* stream, ExonTextScratch** sp, const u
   out->alt_values = s->values[2];
   out->n_alt_items = alt_items;
   out->n_alt_bytes = alt_bytes;
+  return EXON_HIP_OK;
+}
+
+int exon_text_gff(exon_hip_ctx* ctx, void* stream, ExonTextScratch** sp, const uint8_t* d_text, int64_t n_bytes, const uint32_t* d_attr_off, const uint32_t* d_attr_len,
+                  int64_t n_rows, ExonGffText* out, int64_t* n_undecided) {
+  memset(out, 0, sizeof *out);
+  *n_undecided = 0;
+  if (n_rows == 0) return EXON_HIP_OK;
+  int rc = scratch_for(ctx, sp, std::max<int64_t>(n_rows, 1 << 16), std::max<int64_t>(n_bytes, 1 << 20), false, 4, true);
+  if (rc) return rc;
+  ExonTextScratch* s = *sp;
+  hipStream_t hs = pick_stream(ctx, stream);
+  const unsigned n = (unsigned)n_rows;
+  const int nb = (int)((n + TPB - 1) / TPB);
+  GffLens L{s->len[0], s->len[1], s->len[2], s->len[3]};
+  unsigned* d_und = s->totals5 + 7;
+  HIP_TRY(ctx, hipMemsetAsync(s->totals5, 0, 32, hs));
+  hipLaunchKernelGGL(k_gff_attr_measure, dim3(nb), dim3(TPB), 0, hs, d_text, d_attr_off, d_attr_len, n, L, d_und);
+  for (int k = 0; k < 4; ++k) scan_lengths(hs, s, s->len[k], n, s->off[k], s->totals5 + k);  // entries (the map's offsets), items, key bytes, item bytes
+  HIP_TRY(ctx, hipMemcpyAsync(s->h_totals5, s->totals5, 32, hipMemcpyDeviceToHost, hs));
+  HIP_TRY(ctx, hipStreamSynchronize(hs));
+  *n_undecided = s->h_totals5[7];
+  if (*n_undecided) return EXON_HIP_OK;
+  const unsigned entries = s->h_totals5[0], items = s->h_totals5[1], key_bytes = s->h_totals5[2], item_bytes = s->h_totals5[3];
+  if (!fits(s, {key_bytes, item_bytes}, {entries, items})) {  // (values that are mostly ',': an item a byte)
+    *n_undecided = n_rows;
+    return EXON_HIP_OK;
+  }
+  hipLaunchKernelGGL(k_gff_attr_fill, dim3(nb), dim3(TPB), 0, hs, d_text, d_attr_off, d_attr_len, n, s->off[0], s->off[1], s->off[2], s->off[3], s->item_off, s->item_off2,
+                     s->item_off3, s->values[0], s->values[1], entries, items, key_bytes, item_bytes);
+  HIP_TRY(ctx, hipGetLastError());
+  out->map_offsets = s->off[0];
+  out->key_offsets = s->item_off;
+  out->list_offsets = s->item_off2;
+  out->item_offsets = s->item_off3;
+  out->key_values = s->values[0];
+  out->item_values = s->values[1];
+  out->n_entries = entries;
+  out->n_items = items;
+  out->n_key_bytes = key_bytes;
+  out->n_item_bytes = item_bytes;
   return EXON_HIP_OK;
 }

@@ -396,13 +396,15 @@ class Scan:
     CPU-only: usable without a GPU."""
 
     PROJECT = {"vcf": {"id": 1, "ref": 2, "alt": 4, "info": 8, "formats": 16}, "bam": {"name": 1, "cigar": 2, "sequence": 4, "quality_score": 8},
-               "bcf": {"id": 1, "ref": 2, "alt": 4}, "sam": {"name": 1, "cigar": 2, "sequence": 4, "quality_score": 8}}
+               "bcf": {"id": 1, "ref": 2, "alt": 4}, "sam": {"name": 1, "cigar": 2, "sequence": 4, "quality_score": 8},
+               "gff": {"attributes": 256}}
 
     def __init__(self, path, fmt, compression=None, batch_size=0, info_field=None, region=None, use_index=False,
                  gpu_parse=False, project=()):
         """project: names of the reference's columns beyond the fused kernels' operands (EXON_HIP_PROJECT_*): VCF "id", "ref", "alt",
         "info", "formats" (the last two as the reference's unparsed Utf8 columns; host reader only);
-        BAM "name", "cigar", "sequence", "quality_score" -- appended behind the default columns in that order."""
+        BAM "name", "cigar", "sequence", "quality_score" -- appended behind the default columns in that order; GFF "attributes"
+        (the reference's Map<Utf8, List<Utf8>>, column 8)."""
         self.lib = L.load()
         self.fmt = fmt
         mask = 0
@@ -568,11 +570,13 @@ class GFFParser:
         self.ctx._check(self.ctx.lib.exon_hip_gff_parser_parse(self.h, stream, ptr, n_bytes, C.byref(cols)))
         return cols
 
-    def parse_host(self, text, misalign=0):
+    def parse_host(self, text, misalign=0, attributes=False):
         """Test helper: copy `text` to HBM (`misalign` bytes past a 16-byte boundary), parse, bring the columns back as numpy arrays
-        (none of them when the device left a row undecided)."""
+        (none of them when the device left a row undecided).  attributes: the `attributes` column too, built on the device
+        (exon_hip_gff_parser_attributes): res["attributes"] = its six buffers, four totals and n_undecided (buffers only when 0)."""
         buf = np.frombuffer(text, np.uint8)
         d = self.ctx.to_device(np.concatenate([np.full(misalign, 10, np.uint8), buf, np.zeros(64, np.uint8)]))
+        self.ctx._check(self.ctx.lib.exon_hip_gff_parser_want_attributes(self.h, 1 if attributes else 0))
         cols = self.parse_device(d.ptr + misalign, len(buf))
         n = cols.n_rows if cols.n_undecided == 0 else 0
         nb = (n + 7) // 8
@@ -591,6 +595,18 @@ class GFFParser:
         res["score"] = get(cols.score, np.float32, n)
         for name in ("score_valid", "strand_valid", "phase_valid"):
             res[name] = get(getattr(cols, name), np.uint8, nb)
+        if attributes and cols.n_undecided == 0:
+            a = L.GFFAttributes()
+            self.ctx._check(self.ctx.lib.exon_hip_gff_parser_attributes(self.h, None, C.byref(a)))
+            at = {k: getattr(a, k) for k in ("n_entries", "n_items", "n_key_bytes", "n_item_bytes", "n_undecided")}
+            if a.n_undecided == 0 and n:
+                at["map_offsets"] = get(a.map_offsets, np.int32, n + 1)
+                at["key_offsets"] = get(a.key_offsets, np.int32, a.n_entries + 1)
+                at["key_values"] = get(a.key_values, np.uint8, a.n_key_bytes)
+                at["list_offsets"] = get(a.list_offsets, np.int32, a.n_entries + 1)
+                at["item_offsets"] = get(a.item_offsets, np.int32, a.n_items + 1)
+                at["item_values"] = get(a.item_values, np.uint8, a.n_item_bytes)
+            res["attributes"] = at
         return res
 
     def names(self, column):

@@ -431,7 +431,11 @@ int exon_hip_stream_close(exon_hip_stream* s);
  *   FASTQ 0 name 1 description? 2 sequence 3 quality_scores      FASTA 0 id 1 description? 2 sequence
  *   GFF   0 seqname(dict) 1 source(dict) 2 type(dict) 3 start:i64 4 end:i64 5 score:f32? 6 strand(dict ["+","-"])? 7 phase(dict
  *         ["0","1","2"])?  -- the reference's schema order (exon-gff/src/array_builder.rs); the three leading dictionaries are
- *         built from the file (GFF has no header).  `attributes` is not built: any projection is EXON_HIP_EUNSUPPORTED.  A region
+ *         built from the file (GFF has no header).  With EXON_HIP_PROJECT_GFF_ATTRIBUTES column 8 is `attributes`, the
+ *         reference's Map<Utf8, List<Utf8>> (Arrow "+m", not NULL, keys unsorted; entries{keys: Utf8, values: List<item:
+ *         Utf8>?}; exon-gff/src/config.rs:81-108), by the ATTRIBUTE RULES of exon_amd/csrc/host/gff.h: split at ';' then the
+ *         first '=' then ',', percent-decoded, validated on every record.  Built by the host reader and by the GPU pipeline
+ *         (text_columns.hip); any other GFF projection bit is EXON_HIP_EUNSUPPORTED.  A region
  *         is the reference reader's own filter (exon-gff/src/batch_reader.rs:76-97): seqname = name AND start inside the
  *         interval; with use_index the chunks come from <path>.tbi (GFF preset, read from the index header).  A ##FASTA
  *         section is EXON_HIP_EUNSUPPORTED.  Plans address the columns by index: K2 (0, 3); K6 / K7 (0, 3, 4).
@@ -479,7 +483,9 @@ typedef struct exon_hip_scan_options {
                              These two are built by the host reader only: a gpu_parse scan that asks for them decodes on the host.
                              BCF: id List<Utf8>, ref Utf8, alt List<Utf8> through the reference's EAGER builder (lists with their
                              items, never NULL: eager_array_builder.rs:112-134); SAM: the BAM columns from the line's fields
-                             (exon-sam/src/array_builder.rs:101-185); both from the host readers and from the GPU pipeline */
+                             (exon-sam/src/array_builder.rs:101-185); both from the host readers and from the GPU pipeline.
+                             GFF: attributes Map<Utf8, List<Utf8>> (exon-gff/src/array_builder.rs:141-165), bit 8 = the column's
+                             index in the reference's schema; from the host reader and from the GPU pipeline */
 } exon_hip_scan_options;
 #define EXON_HIP_PROJECT_VCF_ID 1ull
 #define EXON_HIP_PROJECT_VCF_REF 2ull
@@ -490,6 +496,7 @@ typedef struct exon_hip_scan_options {
 #define EXON_HIP_PROJECT_BAM_CIGAR 2ull
 #define EXON_HIP_PROJECT_BAM_SEQUENCE 4ull
 #define EXON_HIP_PROJECT_BAM_QUALITY_SCORES 8ull
+#define EXON_HIP_PROJECT_GFF_ATTRIBUTES 256ull /* (additive; the ABI stays 5) bit 8: `attributes` is column 8 of the reference's schema */
 
 int exon_hip_scan_open(const char* path, const exon_hip_scan_options* options, exon_hip_scan** out);
 int exon_hip_scan_schema(exon_hip_scan* scan, struct ArrowSchema* out);
@@ -727,6 +734,24 @@ int exon_hip_gff_parser_parse(exon_hip_gff_parser* parser, void* stream, const u
                               exon_hip_gff_columns* cols);
 /* the dictionary of column 0 (seqname), 1 (source) or 2 (type) discovered so far, '\0'-separated in id order */
 int exon_hip_gff_parser_names(exon_hip_gff_parser* parser, int32_t column, char* buf, size_t cap, int32_t* n_names);
+/* The `attributes` column of the slab of the last parse call (additive; the ABI stays 5), built on the device: the buffers of
+ * Map<Utf8, List<Utf8>> -- rows -> entries (map_offsets), entries -> key bytes (key_offsets) and -> items (list_offsets),
+ * items -> item bytes (item_offsets); bytes after percent-decoding.  Call exon_hip_gff_parser_want_attributes(parser, 1)
+ * BEFORE the parse call (the line kernel then records where every row's ninth field lies; without it nothing new runs), and
+ * exon_hip_gff_parser_attributes after it and before the next one.  n_undecided != 0 (a byte >= 0x80, raw or decoded; a piece
+ * without '='; an empty piece other than the one behind a trailing ';'; more items than the scratch holds): nothing was
+ * built, the host reader decides.  Device pointers owned by the parser, overwritten by the next call.  Synchronises `stream`. */
+typedef struct exon_hip_gff_attributes {
+  int64_t n_entries, n_items, n_key_bytes, n_item_bytes, n_undecided;
+  const int32_t* map_offsets;  /* [n_rows + 1] */
+  const int32_t* key_offsets;  /* [n_entries + 1] */
+  const uint8_t* key_values;   /* [n_key_bytes] */
+  const int32_t* list_offsets; /* [n_entries + 1] */
+  const int32_t* item_offsets; /* [n_items + 1] */
+  const uint8_t* item_values;  /* [n_item_bytes] */
+} exon_hip_gff_attributes;
+int exon_hip_gff_parser_want_attributes(exon_hip_gff_parser* parser, int32_t on);
+int exon_hip_gff_parser_attributes(exon_hip_gff_parser* parser, void* stream, exon_hip_gff_attributes* out);
 int exon_hip_gff_parser_destroy(exon_hip_gff_parser* parser);
 
 /* ---- BCF2 record splitting + field extraction on the GPU (inflated BCF bytes in HBM -> the VCF device layout) ----

@@ -2,7 +2,8 @@
 // kernels.hip / oracle) so the decode -> HBM -> kernel pipeline can be timed end to end on real files.
 // `gen_text fastq <reads> <out> [read_len=150] [ragged=0]` writes 4-line FASTQ records (config 5 end to end);
 // `gen_text bam <reads> <out> [read_len=100]` an uncompressed BAM stream (bgzip it to get a .bam; config 3 end to end).
-// `gen_text gff <rows> <out>` a GFF3 table sorted by (seqname, start), so that bgzip + a tabix index (GFF preset) serve it.
+// `gen_text gff <rows> <out>` a GFF3 table sorted by (seqname, start), so that bgzip + a tabix index (GFF preset) serve it;
+// `gen_text gff <rows> <out> attrs` the same rows with rich ninth fields (every shape of the attribute rules, ASCII only).
 // build: g++ -O2 -std=c++17 tools/gen_text.cpp -o tools/bin/gen_text      run: gen_text vcf <rows> <out.vcf>
 #include <cstdint>
 #include <cstdio>
@@ -13,7 +14,7 @@ static inline uint64_t mix64(uint64_t z) { z = (z ^ (z >> 30)) * 0xBF58476D1CE4E
 static inline uint64_t rnd(uint64_t seed, uint64_t col, uint64_t i) { return mix64(seed + col * 0xD1B54A32D192ED03ULL + (i + 1) * 0x9E3779B97F4A7C15ULL); }
 static inline uint32_t pct_thr(int p) { return (uint32_t)((((uint64_t)p) << 32) / 100); }
 int main(int argc, char** argv) {
-  if (argc < 4) { fprintf(stderr, "usage: gen_text vcf|bcf|fastq|bam|sam|gff <rows> <out> [read_len] [ragged]\n"); return 2; }
+  if (argc < 4) { fprintf(stderr, "usage: gen_text vcf|bcf|fastq|bam|sam|gff <rows> <out> [read_len | attrs] [ragged]\n"); return 2; }
   const int64_t n = (int64_t)atof(argv[2]);
   FILE* f = fopen(argv[3], "wb");
   if (!f) return 1;
@@ -60,6 +61,38 @@ int main(int argc, char** argv) {
     static const char* SOURCES[3] = {"ensembl", "havana", "ensembl_havana"};
     static const char STRAND[4] = {'+', '-', '.', '?'}, PHASE[4] = {'.', '0', '1', '2'};
     const int NSEQ = 24;
+    const bool attrs = argc > 4 && !strcmp(argv[4], "attrs");
+    // attrs: 0-12 entries a row; '.' and empty fields; a trailing ';' on every other row; keys that repeat inside a row, an escaped
+    // key, now and then an empty one; values of 0, 1, 7, 8, 9 bytes, comma lists with empty pieces, %3B / %2c / %25 and a lone '%',
+    // and (7 in 16) up to 300 bytes
+    static const char* KEYS[8] = {"ID", "Parent", "Name", "gene_id", "Dbxref", "Note", "tag%20x", "Alias"};
+    static const char* LISTS[4] = {"a,b", ",x,,y,", "GO:0001,GO:0002,GO:0003", ","};
+    static const char* ESCAPES[4] = {"a%3Bb%2cc%25d", "100%", "%zz%3", "x%3Dy%2C%09z"};
+    auto attributes = [&](int64_t i, std::string* out) {
+      out->clear();
+      const uint64_t r = rnd(9, 0, (uint64_t)i);
+      const int n_entries = (int)((r >> 4) % 13);
+      if ((r & 15) == 0 || n_entries == 0) {
+        if (r & 16) *out = ".";
+        return;
+      }
+      for (int j = 0; j < n_entries; ++j) {
+        const uint64_t q = rnd(9, 1, (uint64_t)(i * 16 + j));
+        if (j) out->push_back(';');
+        if ((q >> 40) % 64 != 0) *out += KEYS[(q >> 4) & 7];
+        out->push_back('=');
+        const int kind = (int)(q & 15);
+        const int fixed[5] = {0, 1, 7, 8, 9};
+        int len = -1;
+        if (kind < 5) len = fixed[kind];
+        else if (kind < 7) *out += LISTS[(q >> 8) & 3];
+        else if (kind < 9) *out += ESCAPES[(q >> 8) & 3];
+        else len = (int)((q >> 8) % 301);
+        for (int k = 0; k < len; ++k) out->push_back("abcdefghijklmnopqrstuvwxyz0123456789 _-.:|"[((q >> 20) + (uint64_t)k * 7) % 42]);
+      }
+      if (r & 32) out->push_back(';');
+    };
+    std::string field9;
     fputs("##gff-version 3\n", f);
     for (int64_t i = 0; i < n; ++i) {
       const uint64_t a = rnd(8, 0, (uint64_t)i), b = rnd(8, 1, (uint64_t)i);
@@ -74,6 +107,14 @@ int main(int argc, char** argv) {
       else snprintf(score, sizeof score, "%u.%u", k / 10, k % 10);
       if (i && i % 1000 == 0) fputs("###\n", f);
       if (i % 7777 == 5) fprintf(f, "# rows from %lld on\n", (long long)i);
+      if (attrs) {
+        attributes(i, &field9);
+        fprintf(f, "%s\t%s\t%s\t%lld\t%lld\t%s\t%c\t%c\t", name, SOURCES[(b >> 2) % 3], TYPES[(b >> 8) % 10], (long long)start, (long long)end, score,
+                STRAND[(b >> 16) & 3], PHASE[(b >> 18) & 3]);
+        fwrite(field9.data(), 1, field9.size(), f);
+        fputc('\n', f);
+        continue;
+      }
       fprintf(f, "%s\t%s\t%s\t%lld\t%lld\t%s\t%c\t%c\tID=f%lld;Name=n%u\n", name, SOURCES[(b >> 2) % 3], TYPES[(b >> 8) % 10], (long long)start, (long long)end,
               score, STRAND[(b >> 16) & 3], PHASE[(b >> 18) & 3], (long long)i, (unsigned)(b >> 40) & 0xFFFFu);
     }
