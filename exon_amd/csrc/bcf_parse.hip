@@ -71,7 +71,8 @@ struct BcfOut {
   int32_t* filter_id;
   float* info[EXON_HIP_MAX_INFO_FIELDS];  // typed INFO fields (4-byte values), in the order of exon_hip_bcf_parser_set_info_keys
   uint32_t* info_valid[EXON_HIP_MAX_INFO_FIELDS];
-  uint32_t* lv_off[EXON_HIP_MAX_INFO_FIELDS];  // list kinds ('F' / 'I'): where the row's typed vector starts (| value type << 29)
+  uint32_t* lv_off[EXON_HIP_MAX_INFO_FIELDS];  // list kinds ('F' / 'I'): where the row's typed vector starts -- its descriptor byte: the
+                                               // value type is read again from there (all 32 bits are the offset: slabs reach 0xF0000000 bytes)
   uint32_t* lv_cnt[EXON_HIP_MAX_INFO_FIELDS];  // ... and how many items it holds (0: NULL list)
   uint32_t* pos_valid;  // POS 0 (BCF pos0 = -1, the telomere) is NULL like in the VCF path
   uint32_t* rec_of_row;  // byte offset of every row's record (id / ref / alt are built from it: text_columns.hip)
@@ -169,6 +170,7 @@ __global__ __launch_bounds__(256) void k_bcf_extract(const uint8_t* __restrict__
       c.typed_header(&kt, &kc);
       const int64_t key = kc ? c.read_int(kt) : -1;
       int vt, vc;
+      const uint32_t vh = c.o;  // the value's descriptor
       c.typed_header(&vt, &vc);
       if (c.bad) break;
       for (int w = 0; w < ik.n; ++w) {
@@ -177,7 +179,8 @@ __global__ __launch_bounds__(256) void k_bcf_extract(const uint8_t* __restrict__
           have |= 1u << w;  // a Flag is true by being there
         } else if (ik.kind[w] == 'F' || ik.kind[w] == 'I') {
           // a typed vector -> List<item>: count the items up to the type's end-of-vector value; ONE item that is the type's
-          // 'missing' value is `key=.` (NULL list).  The items are parsed by k_bcf_list_fill behind the offsets scan.
+          // 'missing' value (whatever padding follows it) is `key=.` (NULL list).  The items are parsed by k_bcf_list_fill
+          // behind the offsets scan.
           const bool ints = vt >= 1 && vt <= 3, flts = vt == 5 && ik.kind[w] == 'F';
           if (vc >= 1 && (ints || flts)) {
             const uint32_t sz = (uint32_t)type_size(vt);
@@ -199,20 +202,21 @@ __global__ __launch_bounds__(256) void k_bcf_extract(const uint8_t* __restrict__
               }
               ++items;
             }
-            if (items > 0 && !(vc == 1 && first_missing)) {
-              out.lv_off[w][row] = c.o | ((uint32_t)vt << 29);
+            if (items > 0 && !(items == 1 && first_missing)) {
+              out.lv_off[w][row] = vh;
               out.lv_cnt[w][row] = items;
               have |= 1u << w;
             }
           }
         } else if (ik.kind[w] == 'i') {
-          // Type=Integer: int8 / int16 / int32 widened to Int32 exactly (bit pattern in the 4-byte column)
+          // Type=Integer: int8 / int16 / int32 widened to Int32 exactly (bit pattern in the 4-byte column); an end-of-vector
+          // value in front is a vector without items: NULL, like the float 0x7F800002 below
           if (vc >= 1 && vt >= 1 && vt <= 3) {
             Cursor t = c;
             const int64_t v = t.read_int(vt);
             if (t.bad) { c.bad = true; break; }
             const int64_t missing = vt == 1 ? -128 : vt == 2 ? -32768 : (int64_t)INT32_MIN;
-            if (v != missing) {
+            if (v != missing && v != missing + 1) {
               out.info[w][row] = __int_as_float((int32_t)v);
               have |= 1u << w;
             }
@@ -230,7 +234,7 @@ __global__ __launch_bounds__(256) void k_bcf_extract(const uint8_t* __restrict__
             const int64_t v = t.read_int(vt);
             if (t.bad) { c.bad = true; break; }
             const int64_t missing = vt == 1 ? -128 : vt == 2 ? -32768 : (int64_t)INT32_MIN;
-            if (v != missing) {
+            if (v != missing && v != missing + 1) {
               out.info[w][row] = (float)v;
               have |= 1u << w;
             }
@@ -290,18 +294,24 @@ __global__ __launch_bounds__(LIST_TPB) void k_bcf_list_fill(const uint8_t* __res
                                                             uint8_t* __restrict__ item_flags, unsigned* __restrict__ exceptions) {
   const unsigned n_rows = min(*n_rows_p, cap);
   const unsigned row = blockIdx.x * LIST_TPB + threadIdx.x;
+  // a slab with an undecided record goes to the host reader as a whole, and k_bcf_extract leaves that record's count and offset as
+  // they were (last slab's, or never written): no row of such a slab reads its items
+  const bool undecided = *exceptions != 0;
   const unsigned c = row < n_rows ? cnt[row] : 0u;
   const unsigned first = list_first_item(c, block_offsets);
   if (row < n_rows) offsets[row] = (int32_t)first;
   if (row + 1 == n_rows) offsets[n_rows] = (int32_t)(first + c);
   if (row == 0 && n_rows == 0) offsets[0] = 0;
-  if (row >= n_rows || c == 0) return;
+  if (row >= n_rows || c == 0 || undecided) return;
   if ((uint64_t)first + c > cap_items) {
     atomicAdd(exceptions, 1u);
     return;
   }
-  const uint32_t o = lv_off[row] & 0x1FFFFFFFu;
-  const int vt = (int)(lv_off[row] >> 29);
+  // the descriptor k_bcf_extract walked over (and bounds-checked with its items against the record's end): type, count, items
+  Cursor h{d, lv_off[row], 0xFFFFFFFFu, false};
+  int vt, vc;
+  h.typed_header(&vt, &vc);
+  const uint32_t o = h.o;
   const int64_t missing = vt == 1 ? -128 : vt == 2 ? -32768 : (int64_t)INT32_MIN;
   for (unsigned i = 0; i < c; ++i) {
     uint32_t bits = 0;

@@ -193,12 +193,13 @@ class BCFBatchReader : public BatchReader {
           if (kind == 'b') {
             have[q] = true;  // a Flag is true by being there (typed value: missing type, or an int8 1)
           } else if (kind == 'i' && vc >= 1) {
-            // Type=Integer: int8 / int16 / int32 typed value, widened to Int32 exactly; the type's minimum is 'missing'
+            // Type=Integer: int8 / int16 / int32 typed value, widened to Int32 exactly; the type's minimum is 'missing', the
+            // value above it 'end of vector' (in front: a vector without items, NULL like the float 0x7F800002 below)
             if (vt >= 1 && vt <= 3) {
               size_t oo = o;
               const int64_t v = read_int(rec, &oo, end, vt);
               const int64_t missing = vt == 1 ? -128 : vt == 2 ? -32768 : (int64_t)INT32_MIN;
-              if (v != missing) {
+              if (v != missing && v != missing + 1) {
                 sv[q] = (int32_t)v;
                 have[q] = true;
               }
@@ -215,7 +216,7 @@ class BCFBatchReader : public BatchReader {
               size_t oo = o;
               const int64_t v = read_int(rec, &oo, end, vt);
               const int64_t missing = vt == 1 ? -128 : vt == 2 ? -32768 : (int64_t)INT32_MIN;
-              if (v != missing) {
+              if (v != missing && v != missing + 1) {
                 fv[q] = (float)v;
                 have[q] = true;
               }
@@ -240,10 +241,11 @@ class BCFBatchReader : public BatchReader {
               }
             } else if (kind == 'F' && vt == 5) {
               int items = 0;
-              if (vc == 1) {  // a single 'missing' item is `key=.`: the whole value is missing
-                uint32_t b0;
+              {  // a single 'missing' item (whatever end-of-vector padding follows it) is `key=.`: the whole value is missing
+                uint32_t b0, b1 = 0x7F800002u;
                 memcpy(&b0, &rec[o], 4);
-                if (b0 == 0x7F800001u) continue;
+                if (vc > 1) memcpy(&b1, &rec[o + 4], 4);
+                if (b0 == 0x7F800001u && b1 == 0x7F800002u) continue;
               }
               for (int e = 0; e < vc; ++e) {
                 uint32_t b;
@@ -263,9 +265,10 @@ class BCFBatchReader : public BatchReader {
               size_t oo = o;
               const int64_t missing = vt == 1 ? -128 : vt == 2 ? -32768 : (int64_t)INT32_MIN;
               int items = 0;
-              if (vc == 1) {  // a single 'missing' item is `key=.`: the whole value is missing
+              {  // a single 'missing' item (whatever end-of-vector padding follows it) is `key=.`: the whole value is missing
                 size_t o1 = o;
-                if (read_int(rec, &o1, end, vt) == missing) continue;
+                const int64_t v0 = read_int(rec, &o1, end, vt), v1 = vc > 1 ? read_int(rec, &o1, end, vt) : missing + 1;
+                if (v0 == missing && v1 == missing + 1) continue;
               }
               for (int e = 0; e < vc; ++e) {
                 const int64_t v = read_int(rec, &oo, end, vt);

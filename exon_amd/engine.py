@@ -504,6 +504,7 @@ class VCFParser:
                                                       max_slab_bytes, C.byref(h)))
         self.h = h
         self.has_info = bool(info_field)
+        self.cap_items = max_slab_bytes // 2 + 1  # items a list key's buffers hold (exon_hip_vcf_parser_create)
 
     def parse_device(self, d_text, n_bytes, stream=None):
         cols = L.VCFColumns()
@@ -533,6 +534,20 @@ class VCFParser:
         if self.has_info:
             res["info"] = get(cols.info, np.float32, n)
             res["info_valid"] = get(cols.info_valid, np.uint8, nb)
+            # every key: {"kind", "valid"} + "values" (scalar kinds: one 4-byte slot per row) or, for the list kinds 'F' / 'I',
+            # "offsets" (n + 1), "values" (the items) and "item_valid" (their bitmap); nothing but the validity for a Flag
+            res["infos"] = []
+            for q in range(cols.n_info):
+                kind = cols.info_kinds[q:q + 1].decode()
+                k = {"kind": kind, "valid": get(cols.infos_valid[q], np.uint8, nb)}
+                if kind in "FI":
+                    k["offsets"] = get(cols.list_offsets[q], np.int32, n + 1 if n else 0)
+                    items = min(int(k["offsets"][-1]) if n else 0, self.cap_items)  # (more items than the buffers hold: an undecided slab)
+                    k["values"] = get(cols.infos[q], np.float32, items)
+                    k["item_valid"] = get(cols.list_item_valid[q], np.uint8, (items + 7) // 8)
+                elif kind != "b":
+                    k["values"] = get(cols.infos[q], np.float32, n)
+                res["infos"].append(k)
         return res
 
     def filters(self):
@@ -570,15 +585,16 @@ class GFFParser:
         self.ctx._check(self.ctx.lib.exon_hip_gff_parser_parse(self.h, stream, ptr, n_bytes, C.byref(cols)))
         return cols
 
-    def parse_host(self, text, misalign=0, attributes=False):
+    def parse_host(self, text, misalign=0, attributes=False, all_rows=False):
         """Test helper: copy `text` to HBM (`misalign` bytes past a 16-byte boundary), parse, bring the columns back as numpy arrays
         (none of them when the device left a row undecided).  attributes: the `attributes` column too, built on the device
-        (exon_hip_gff_parser_attributes): res["attributes"] = its six buffers, four totals and n_undecided (buffers only when 0)."""
+        (exon_hip_gff_parser_attributes): res["attributes"] = its six buffers, four totals and n_undecided (buffers only when 0).
+        all_rows: the columns of an undecided slab too (its decided rows hold their values; dictionary ids are provisional)."""
         buf = np.frombuffer(text, np.uint8)
         d = self.ctx.to_device(np.concatenate([np.full(misalign, 10, np.uint8), buf, np.zeros(64, np.uint8)]))
         self.ctx._check(self.ctx.lib.exon_hip_gff_parser_want_attributes(self.h, 1 if attributes else 0))
         cols = self.parse_device(d.ptr + misalign, len(buf))
-        n = cols.n_rows if cols.n_undecided == 0 else 0
+        n = cols.n_rows if cols.n_undecided == 0 or all_rows else 0
         nb = (n + 7) // 8
 
         def get(ptr, dtype, count):
@@ -625,6 +641,50 @@ class GFFParser:
     def close(self):
         if self.h:
             self.ctx.lib.exon_hip_gff_parser_destroy(self.h)
+            self.h = None
+
+
+class SAMParser:
+    """SAM text parsing on the GPU (exon_hip_sam_parser_*): alignment lines in HBM -> the BAM device layout (flag, mapq, reference id,
+    start, end) in HBM.  `references`: the header's @SQ names in order (their ids)."""
+
+    def __init__(self, ctx, references, max_slab_bytes=64 << 20):
+        self.ctx = ctx
+        names = (C.c_char_p * max(len(references), 1))(*[r.encode() for r in references])
+        h = C.c_void_p()
+        ctx._check(ctx.lib.exon_hip_sam_parser_create(ctx.h, names, len(references), max_slab_bytes, C.byref(h)))
+        self.h = h
+
+    def parse_device(self, d_text, n_bytes, stream=None):
+        cols = L.BAMColumns()
+        ptr = d_text.ptr if isinstance(d_text, DeviceBuffer) else int(d_text)
+        self.ctx._check(self.ctx.lib.exon_hip_sam_parser_parse(self.h, stream, ptr, n_bytes, C.byref(cols)))
+        return cols
+
+    def parse_host(self, text, misalign=0):
+        """Test helper: copy `text` (complete alignment lines) to HBM (`misalign` bytes past a 16-byte boundary), parse, bring the
+        columns back as numpy arrays -- of every row, undecided ones included (their slots hold whatever was there)."""
+        buf = np.frombuffer(text, np.uint8)
+        d = self.ctx.to_device(np.concatenate([np.full(misalign, 10, np.uint8), buf, np.zeros(64, np.uint8)]))
+        cols = self.parse_device(d.ptr + misalign, len(buf))
+        n = cols.n_rows
+        nb = (n + 7) // 8
+
+        def get(ptr, dtype, count):
+            out = np.empty(count, dtype)
+            if count:
+                self.ctx._check(self.ctx.lib.exon_hip_memcpy_d2h(self.ctx.h, _np_ptr(out), ptr, out.nbytes, None))
+            return out
+
+        return {"n_rows": n, "n_undecided": cols.n_undecided, "consumed_bytes": cols.consumed_bytes,
+                "flag": get(cols.flag, np.int32, n), "mapq": get(cols.mapq, np.uint8, n),
+                "mapq_valid": get(cols.mapq_valid, np.uint8, nb), "ref_id": get(cols.ref_id, np.int32, n),
+                "ref_valid": get(cols.ref_valid, np.uint8, nb), "start": get(cols.start, np.int64, n),
+                "end": get(cols.end, np.int64, n), "pos_valid": get(cols.pos_valid, np.uint8, nb)}
+
+    def close(self):
+        if self.h:
+            self.ctx.lib.exon_hip_sam_parser_destroy(self.h)
             self.h = None
 
 

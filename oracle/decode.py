@@ -19,6 +19,14 @@ import struct
 
 import numpy as np
 
+from . import decimal_exact
+
+
+def f32_value(x):
+    """a Float field's text -> np.float32 the way Rust's `str::parse::<f32>` rounds it: to the NEAREST binary32.  np.float32(text)
+    rounds to a double first, which is one unit off next to a binary32 tie (oracle/decimal_exact.py)."""
+    return np.float32(decimal_exact.f32(x)) if isinstance(x, str) else np.float32(x)
+
 
 def read_bytes(path):
     raw = open(path, "rb").read()
@@ -65,7 +73,7 @@ def decode_vcf(path):
         if not digits.isascii() or not digits.isdigit():
             raise ValueError(f"invalid POS {c[1]!r}")
         rows["pos"].append(int(digits) or None)
-        rows["qual"].append(None if c[5] == "." else np.float32(c[5]))
+        rows["qual"].append(None if c[5] == "." else f32_value(c[5]))
         rows["filter"].append([] if c[6] == "." else c[6].split(";"))
         rows["id"].append(None if c[2] in (".", "") else c[2].split(";"))
         rows["ref"].append(c[3])
@@ -97,7 +105,7 @@ _RESERVED_FORMAT.update(dict.fromkeys("GL GP CNQ CNL CNP".split(), "Float"))
 
 def rust_f32_display(x):
     """Rust's `{}` of an f32 (`v.to_string()`, lazy_array_builder.rs:233): shortest digits that round-trip, never an exponent."""
-    v = np.float32(x)
+    v = f32_value(x)
     if np.isnan(v):
         return "NaN"
     if np.isinf(v):
@@ -120,7 +128,7 @@ def _print_value(typ, text):
                 raise ValueError(f"integer out of the int32 range {item!r}")
             out.append(str(int(item)))
         elif typ == "Float":
-            out.append(rust_f32_display(np.float32(item)))
+            out.append(rust_f32_display(f32_value(item)))
         else:
             out.append(item)
     return ",".join(out)
@@ -210,7 +218,7 @@ def typed_info(v, key):
                 raise ValueError(f"INFO integer out of the int32 range: {x!r}")
             return int(x)
         if typ == "Float":
-            return float(np.float32(x))
+            return float(f32_value(x))
         return str(x)
 
     col = []

@@ -19,7 +19,7 @@ def vcf_columns(path, fmt="vcf", info_field=None):
         vals = []
         for i in v["info"]:
             x = None if i is None else i.get(info_field)
-            vals.append(None if x is None or x is True or x == "." else float(np.float32(x)))
+            vals.append(None if x is None or x is True or x == "." else float(decode.f32_value(x)))
         out["info"] = vals
     return out
 

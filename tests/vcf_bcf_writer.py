@@ -106,23 +106,55 @@ def write_vcf(path, rows, filters=FILTERS, eol=lambda i: "\n"):
             f.write(f"{r['chrom']}\t{r['pos']}\t{rid}\t{ref}\t{','.join(alt) or '.'}\t{q}\t{';'.join(r['filter']) or '.'}\t{_info_text(r['info'])}{eol(i)}")
 
 
-def _typed_ints(vals):
-    """typed integer vector (None = missing) in the smallest type that holds every item (reserving the 8 lowest values)"""
+INT_TYPES = {1: ("b", -128), 2: ("h", -32768), 3: ("i", -2147483648)}  # BCF type code -> (struct format, 'missing'; + 1 = end of vector)
+FLOAT_MISSING, FLOAT_EOV = 0x7F800001, 0x7F800002
+
+
+class Ints:
+    """Opt-in control over how an INFO value is written to BCF (write_bcf only): an integer vector -- under an Integer key or, as
+    htslib never does but the format allows, a Float key -- in a forced width (1 / 2 / 3 = int8 / int16 / int32; None: the
+    narrowest), followed by `pad` end-of-vector values (they count in the vector's length), its length written as an extended
+    count in the integer width `count_width` (None: inline below 15 items).  vals: int, or None = the width's missing value."""
+
+    def __init__(self, vals, width=None, pad=0, count_width=None):
+        self.vals, self.width, self.pad, self.count_width = list(vals), width, pad, count_width
+
+    def encode(self):
+        return _typed_ints(self.vals, self.width, self.pad, self.count_width)
+
+
+class Floats:
+    """... a float vector given as raw bit patterns (None = missing, 0x7F800001), `pad` end-of-vector values behind it"""
+
+    def __init__(self, bits, pad=0, count_width=None):
+        self.bits, self.pad, self.count_width = list(bits), pad, count_width
+
+    def encode(self):
+        words = [FLOAT_MISSING if b is None else b for b in self.bits] + [FLOAT_EOV] * self.pad
+        return _desc(len(words), 5, self.count_width) + b"".join(struct.pack("<I", w) for w in words)
+
+
+def _typed_ints(vals, width=None, pad=0, count_width=None):
+    """typed integer vector (None = missing) in the smallest type that holds every item (reserving the 8 lowest values), or in
+    the forced `width`; `pad` end-of-vector values behind the items"""
     present = [v for v in vals if v is not None]
     lo, hi = (min(present), max(present)) if present else (0, 0)
-    if -120 <= lo and hi <= 127:
-        t, fmt, miss = 1, "b", -128
+    if width is not None:
+        t = width
+    elif -120 <= lo and hi <= 127:
+        t = 1
     elif -32760 <= lo and hi <= 32767:
-        t, fmt, miss = 2, "h", -32768
+        t = 2
     else:
-        t, fmt, miss = 3, "i", -2147483648
-    return _desc(len(vals), t) + b"".join(struct.pack("<" + fmt, miss if v is None else v) for v in vals)
+        t = 3
+    fmt, miss = INT_TYPES[t]
+    return _desc(len(vals) + pad, t, count_width) + b"".join(struct.pack("<" + fmt, miss if v is None else v) for v in vals) + struct.pack("<" + fmt, miss + 1) * pad
 
 
-def _desc(n, t):
-    if n < 15:
+def _desc(n, t, count_width=None):
+    if n < 15 and count_width is None:
         return bytes([(n << 4) | t])
-    return bytes([0xF0 | t]) + _typed_ints([n])
+    return bytes([0xF0 | t]) + _typed_ints([n], count_width)
 
 
 def _typed_floats(vals):
@@ -136,7 +168,9 @@ def _typed_str(s):
 
 
 def write_bcf(path, rows, bgzip, filters=FILTERS):
-    """uncompressed BCF stream -> `bgzip` (tools/bin/bgzip) -> path; a row's FILTER IDs are PASS or among `filters`"""
+    """uncompressed BCF stream -> `bgzip` (tools/bin/bgzip) -> path; a row's FILTER IDs are PASS or among `filters`.
+    Opt-in row keys: "qual_bits" (QUAL as a raw bit pattern), "pos0" (the 0-based POS field as it is), "key_width" (the integer
+    width of every INFO key index of the row); an INFO value may be an `Ints` or a `Floats`."""
     sidx = string_index(filters)
     types = {n: (num, typ) for n, num, typ in INFO_HEADER}
     text = header_text(True, filters).encode() + b"\0"
@@ -145,15 +179,16 @@ def write_bcf(path, rows, bgzip, filters=FILTERS):
         info = r["info"] or {}
         rid, ref, alt = row_id_ref_alt(r)
         alleles = r["alleles"] if "alleles" in r else [ref] + alt
-        shared = struct.pack("<iiiIII", int(r["chrom"]) - 1, r["pos"] - 1, 1,
-                             0x7F800001 if r["qual"] is None else struct.unpack("<I", struct.pack("<f", np.float32(r["qual"])))[0],
-                             len(info) | (len(alleles) << 16), 0)
+        qbits = r["qual_bits"] if "qual_bits" in r else (0x7F800001 if r["qual"] is None else struct.unpack("<I", struct.pack("<f", np.float32(r["qual"])))[0])
+        shared = struct.pack("<iiiIII", int(r["chrom"]) - 1, r["pos0"] if "pos0" in r else r["pos"] - 1, 1, qbits, len(info) | (len(alleles) << 16), 0)
         shared += (_typed_str(r["id"]) if "id" in r else b"\x07") + b"".join(_typed_str(a) for a in alleles)
         shared += _typed_ints([sidx[f] for f in r["filter"]]) if r["filter"] else b"\x00"
         for k, v in info.items():
-            shared += _typed_ints([sidx[k]])
+            shared += _typed_ints([sidx[k]], r.get("key_width"))
             num, typ = types[k]
-            if typ == "Flag":
+            if isinstance(v, (Ints, Floats)):
+                shared += v.encode()
+            elif typ == "Flag":
                 shared += b"\x00"
             elif v is None:
                 shared += (_typed_floats([None]) if typ == "Float" else _typed_ints([None]) if typ == "Integer" else _typed_str("."))
