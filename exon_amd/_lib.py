@@ -112,6 +112,12 @@ class GFFAttributes(C.Structure):
                 ("list_offsets", C.c_void_p), ("item_offsets", C.c_void_p), ("item_values", C.c_void_p)]
 
 
+class GTFAttributes(C.Structure):
+    _fields_ = [("n_entries", C.c_int64), ("n_key_bytes", C.c_int64), ("n_value_bytes", C.c_int64), ("n_undecided", C.c_int64),
+                ("map_offsets", C.c_void_p), ("key_offsets", C.c_void_p), ("key_values", C.c_void_p),
+                ("value_offsets", C.c_void_p), ("value_values", C.c_void_p)]
+
+
 class ScanOptions(C.Structure):
     _fields_ = [("format", C.c_int32), ("compression", C.c_int32), ("batch_size", C.c_int64),
                 ("info_field", C.c_char_p), ("region", C.c_char_p), ("use_index", C.c_int32), ("gpu_parse", C.c_int32),
@@ -122,7 +128,7 @@ class GzipStats(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in ("calls", "chunks", "repairs", "overflow_retries", "members", "comp_bytes", "out_bytes")]
 
 
-FORMATS = {"vcf": 1, "bam": 2, "fastq": 3, "fasta": 4, "sam": 5, "bcf": 6, "cram": 7, "gff": 8}
+FORMATS = {"vcf": 1, "bam": 2, "fastq": 3, "fasta": 4, "sam": 5, "bcf": 6, "cram": 7, "gff": 8, "gtf": 9}
 COMPRESSION = {"auto": 0, None: 0, "none": 1, "gzip": 2}
 
 PLAN_REGION_COUNT = 2
@@ -235,6 +241,8 @@ SIGNATURES = {
     "exon_hip_gff_parser_parse": (C.c_int, [_vp, _vp, _vp, _i64, C.POINTER(GFFColumns)]),
     "exon_hip_gff_parser_want_attributes": (C.c_int, [_vp, _i32]),
     "exon_hip_gff_parser_attributes": (C.c_int, [_vp, _vp, C.POINTER(GFFAttributes)]),
+    "exon_hip_gff_parser_set_dialect": (C.c_int, [_vp, _i32]),
+    "exon_hip_gff_parser_gtf_attributes": (C.c_int, [_vp, _vp, C.POINTER(GTFAttributes)]),
     "exon_hip_gff_parser_names": (C.c_int, [_vp, _i32, C.c_char_p, C.c_size_t, C.POINTER(_i32)]),
     "exon_hip_gff_parser_destroy": (C.c_int, [_vp]),
     "exon_hip_bcf_parser_create": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i64, C.POINTER(_vp)]),

@@ -6,13 +6,13 @@
 // GPU, like config 1); predicates / GROUP BY run through exon_hip_plan_* / exon_hip_stream_* on the GPU.
 //
 //   SET exon.vcf_parse_info = true;
-//   CREATE EXTERNAL TABLE t STORED AS FASTA|FASTQ|VCF|BAM|GFF|INDEXED_VCF|INDEXED_BAM|INDEXED_GFF [OPTIONS (compression gzip)] LOCATION '<path|dir>';
+//   CREATE EXTERNAL TABLE t STORED AS FASTA|FASTQ|VCF|BAM|GFF|GTF|INDEXED_VCF|INDEXED_BAM|INDEXED_GFF [OPTIONS (compression gzip)] LOCATION '<path|dir>';
 //   SELECT COUNT(*) FROM t | fasta_scan('<p>'[, 'gzip']) | fastq_scan(..) | vcf_scan(..) | bam_scan(..)
-//                         | vcf_indexed_scan('<p>', '<region>') | bam_indexed_scan('<p>', '<region>') | gff_scan(..) | gff_indexed_scan(..)
+//                         | vcf_indexed_scan('<p>', '<region>') | bam_indexed_scan('<p>', '<region>') | gff_scan(..) | gtf_scan(..) | gff_indexed_scan(..)
 //   SELECT COUNT(*) FROM v WHERE chrom = '7' AND pos >= 50000000 AND pos <= 100000000            -- K2
 //   SELECT COUNT(*) FROM v WHERE vcf_region_filter('7:50000000-100000000', chrom[, pos]) [= true] -- pushed down
 //   SELECT COUNT(*) FROM b WHERE bam_region_filter('chr1:1-100', reference, start, end) [= true]  -- pushed down
-//   SELECT COUNT(*) FROM g WHERE gff_region_filter('chr1[:a-b]', seqname[, start]) [= true]       -- K2 over (seqname, start)
+//   SELECT COUNT(*) FROM g WHERE gff_region_filter('chr1[:a-b]', seqname[, start]) [= true]       -- K2 over (seqname, start); GFF and GTF sources
 //   SELECT reference, COUNT(*) FROM b WHERE flag & 1284 = 0 AND CAST(mapping_quality AS INT) >= 30 GROUP BY reference  -- K3
 //   SELECT filter, AVG(qual), COUNT(*) FROM v WHERE info."AF" > 0.01 GROUP BY filter            -- K4
 //   SELECT * FROM fastq_quality_histogram('<p>'[, 'gzip'])                                        -- K5
@@ -190,6 +190,7 @@ std::vector<std::string> format_exts(int format, const std::string& custom) {
     case EXON_HIP_FORMAT_BCF: return {".bcf"};
     case EXON_HIP_FORMAT_CRAM: return {".cram"};
     case EXON_HIP_FORMAT_GFF: return {".gff", ".gff3"};
+    case EXON_HIP_FORMAT_GTF: return {".gtf"};
     default: return {".bam"};
   }
 }
@@ -206,6 +207,10 @@ int format_of(const std::string& name, bool* indexed) {
   if (f == "bcf") return EXON_HIP_FORMAT_BCF;
   if (f == "cram") return EXON_HIP_FORMAT_CRAM;
   if (f == "gff") return EXON_HIP_FORMAT_GFF;
+  if (f == "gtf") {
+    if (*indexed) throw Err("unsupported file type " + name + " (there is no indexed GTF table)");
+    return EXON_HIP_FORMAT_GTF;
+  }
   throw Err("unsupported file type " + name);
 }
 
@@ -276,7 +281,7 @@ void open_scan(const Source& src, const std::string& file, const char* info_fiel
   // INDEXED_* tables / *_indexed_scan: plan BGZF chunks from <file>.tbi / <file>.bai
   // (exon-core/src/datasources/indexed_file/indexed_bgzf_file.rs:129-155)
   o.use_index = (src.indexed && !region.empty()) ? 1 : 0;
-  o.gpu_parse = (for_gpu_query && (src.format == EXON_HIP_FORMAT_VCF || src.format == EXON_HIP_FORMAT_FASTQ || src.format == EXON_HIP_FORMAT_BAM || src.format == EXON_HIP_FORMAT_BCF || src.format == EXON_HIP_FORMAT_SAM || src.format == EXON_HIP_FORMAT_GFF) &&
+  o.gpu_parse = (for_gpu_query && (src.format == EXON_HIP_FORMAT_VCF || src.format == EXON_HIP_FORMAT_FASTQ || src.format == EXON_HIP_FORMAT_BAM || src.format == EXON_HIP_FORMAT_BCF || src.format == EXON_HIP_FORMAT_SAM || src.format == EXON_HIP_FORMAT_GFF || src.format == EXON_HIP_FORMAT_GTF) &&
                  region.empty() && gpu_parse_enabled()) ? 1 : 0;
   ck(nullptr, exon_hip_scan_open(file.c_str(), &o, &g->s));
 }
@@ -407,6 +412,63 @@ Source resolve_from(Session& se, Parser& ps) {
   return src;
 }
 
+// SELECT <columns | *> FROM <GFF or GTF source> [LIMIT n]: rows of the eight leading columns through the host reader (the
+// attributes map is not printed); values rendered like datafusion's CLI: NULL for a null, a float in its shortest form
+void select_annotation_rows(const Source& src, bool star, const std::vector<std::string>& proj, int64_t limit, bool quiet) {
+  const std::vector<std::string> names = {"seqname", "source", "type", "start", "end", "score", "strand", src.format == EXON_HIP_FORMAT_GTF ? "frame" : "phase"};
+  std::vector<int> cols;
+  if (star) for (int c = 0; c < 8; ++c) cols.push_back(c);
+  for (const auto& p : proj) {
+    const auto it = std::find(names.begin(), names.end(), p);
+    if (it == names.end()) throw Err("column '" + p + "' is not one this build prints (" + names[0] + " .. " + names[7] + ")");
+    cols.push_back((int)(it - names.begin()));
+  }
+  std::vector<std::string> head;
+  for (int c : cols) head.push_back(names[(size_t)c]);
+  std::vector<std::vector<std::string>> rows;
+  auto valid = [](const struct ArrowArray* a, int64_t i) {
+    const uint8_t* bm = static_cast<const uint8_t*>(a->buffers[0]);
+    return !bm || ((bm[(i + a->offset) >> 3] >> ((i + a->offset) & 7)) & 1);
+  };
+  for (const auto& f : src.files) {
+    ScanGuard g;
+    open_scan(src, f, nullptr, "", &g);
+    for (;;) {
+      if (limit >= 0 && (int64_t)rows.size() >= limit) break;
+      struct ArrowArray b;
+      const int rc = exon_hip_scan_next(g.s, &b);
+      if (rc == 1) break;
+      ck(nullptr, rc);
+      for (int64_t i = 0; i < b.length && (limit < 0 || (int64_t)rows.size() < limit); ++i) {
+        std::vector<std::string> row;
+        for (int c : cols) {
+          const struct ArrowArray* a = b.children[c];
+          if (!valid(a, i)) { row.push_back("NULL"); continue; }
+          const int64_t at = i + a->offset;
+          if (c == 3 || c == 4) {
+            row.push_back(std::to_string(static_cast<const int64_t*>(a->buffers[1])[at]));
+          } else if (c == 5) {
+            const float v = static_cast<const float*>(a->buffers[1])[at];
+            char t[64];
+            for (int p = 1; p <= 9; ++p) { snprintf(t, sizeof t, "%.*g", p, (double)v); if (strtof(t, nullptr) == v) break; }
+            std::string sv = t;
+            if (sv.find_first_of(".eEn") == std::string::npos) sv += ".0";
+            row.push_back(sv);
+          } else {  // a dictionary: the id's name
+            const int32_t id = static_cast<const int32_t*>(a->buffers[1])[at];
+            const struct ArrowArray* d = a->dictionary;
+            const int32_t* off = static_cast<const int32_t*>(d->buffers[1]) + d->offset;
+            row.push_back(std::string(static_cast<const char*>(d->buffers[2]) + off[id], (size_t)(off[id + 1] - off[id])));
+          }
+        }
+        rows.push_back(std::move(row));
+      }
+      if (b.release) b.release(&b);
+    }
+  }
+  print_table(head, rows, quiet);
+}
+
 void exec_select(Session& se, Parser& ps) {
   // projection
   std::vector<std::string> proj;
@@ -429,7 +491,9 @@ void exec_select(Session& se, Parser& ps) {
   if (ps.accept_kw("where")) pr = parse_where(ps, src.format);
   std::string group_by;
   if (ps.accept_kw("group")) { ps.expect_kw("by"); group_by = lower(ps.ident()); while (ps.accept_sym(",")) ps.ident(); }
-  if (ps.accept_kw("order")) { ps.expect_kw("by"); while (!ps.at_end() && !ps.is_sym(";")) ps.p++; }
+  if (ps.accept_kw("order")) { ps.expect_kw("by"); while (!ps.at_end() && !ps.is_sym(";") && !ps.is_kw("limit")) ps.p++; }
+  int64_t limit = -1;
+  if (ps.accept_kw("limit")) limit = atoll(ps.number().c_str());
   if (!ps.at_end()) throw Err("unexpected '" + ps.peek().text + "'");
 
   if (src.indexed && src.region.empty() && pr.kind != Predicate::PushedRegion)
@@ -461,6 +525,10 @@ void exec_select(Session& se, Parser& ps) {
   }
 
   const bool count_only = proj.size() == 1 && proj[0] == "count(*)" && group_by.empty() && !star;
+  if (!count_only && group_by.empty() && pr.kind == Predicate::None && (src.format == EXON_HIP_FORMAT_GFF || src.format == EXON_HIP_FORMAT_GTF)) {
+    select_annotation_rows(src, star, proj, limit, se.quiet);
+    return;
+  }
   if (count_only && pr.kind == Predicate::PushedRegion && !src.indexed && gpu_parse_enabled() &&
       (src.format == EXON_HIP_FORMAT_BAM || src.format == EXON_HIP_FORMAT_SAM || src.format == EXON_HIP_FORMAT_CRAM)) {  // K6: interval overlap on the GPU
     exon_hip_ctx* ctx = se.gpu();
@@ -487,7 +555,7 @@ void exec_select(Session& se, Parser& ps) {
     print_table({"count(*)"}, {{std::to_string(total)}}, se.quiet);
     return;
   }
-  if (count_only && pr.kind == Predicate::PushedRegion && !src.indexed && gpu_parse_enabled() && src.format == EXON_HIP_FORMAT_GFF) {
+  if (count_only && pr.kind == Predicate::PushedRegion && !src.indexed && gpu_parse_enabled() && (src.format == EXON_HIP_FORMAT_GFF || src.format == EXON_HIP_FORMAT_GTF)) {
     // gff_region_filter is the reference reader's own test (exon-gff/src/batch_reader.rs:76-97: seqname = name AND start inside
     // the interval): K2 over scan columns (0, 3), the text parsed on the device
     exon_hip_ctx* ctx = se.gpu();
@@ -686,8 +754,8 @@ int main(int argc, char** argv) {
     else if (a == "-q" || a == "--quiet") se.quiet = true;
     else if (a == "-h" || a == "--help") {
       printf("exon-hip-cli [-q] -c '<sql>'... | -f <file>...\n"
-             "  tables:    CREATE EXTERNAL TABLE t STORED AS FASTA|FASTQ|VCF|BAM|GFF|INDEXED_VCF|INDEXED_BAM|INDEXED_GFF [OPTIONS (compression gzip)] LOCATION '<path>'\n"
-             "  functions: fasta_scan fastq_scan vcf_scan bam_scan gff_scan ('<path>'[, 'gzip']); vcf_indexed_scan bam_indexed_scan gff_indexed_scan ('<path>', '<region>');\n"
+             "  tables:    CREATE EXTERNAL TABLE t STORED AS FASTA|FASTQ|VCF|BAM|GFF|GTF|INDEXED_VCF|INDEXED_BAM|INDEXED_GFF [OPTIONS (compression gzip)] LOCATION '<path>'\n"
+             "  functions: fasta_scan fastq_scan vcf_scan bam_scan gff_scan gtf_scan ('<path>'[, 'gzip']); vcf_indexed_scan bam_indexed_scan gff_indexed_scan ('<path>', '<region>');\n"
              "             fastq_quality_histogram('<path>')\n"
              "  queries:   SELECT COUNT(*) FROM <src> [WHERE chrom = 'c' AND pos >= a AND pos <= b | vcf_region_filter('r', chrom) | bam_region_filter('r', reference, start, end)\n"
              "             | gff_region_filter('r', seqname[, start])]\n"

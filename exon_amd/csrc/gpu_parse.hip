@@ -1433,7 +1433,9 @@ __device__ __forceinline__ bool gff_position(const uint8_t* __restrict__ text, u
 // ATTR (the scan projects `attributes`): where every row's ninth field lies, for text_columns.hip's k_gff_attr_measure / _fill.
 // The two pointers trail the arguments and the ATTR = false instantiation never reads them: its code is the kernel's as it
 // was before the column existed.
-template <bool ATTR>
+// GTF (host/gtf.h: the same eight fields by the same rules but one): a '?' strand makes the row undecided.  A compile-time
+// dialect, so the GFF instantiations are the code they were.
+template <bool ATTR, bool GTF = false>
 __global__ __launch_bounds__(TPB) void k_parse_gff_lines(const uint8_t* __restrict__ text, const unsigned* __restrict__ nl_pos, unsigned* __restrict__ scalars,
                                                          const uint32_t* __restrict__ is_row, const unsigned* __restrict__ block_offsets, FilterTable t0,
                                                          FilterTable t1, FilterTable t2, GffOut out, unsigned cap, unsigned skip, unsigned n_total,
@@ -1495,7 +1497,7 @@ __global__ __launch_bounds__(TPB) void k_parse_gff_lines(const uint8_t* __restri
       const unsigned sc = fs[7] - 1 - fs[6] == 1u ? text[fs[6]] : 0u;
       strand_ok = sc == '+' || sc == '-';
       strand = sc == '-' ? 1 : 0;
-      bad |= !(strand_ok || sc == '.' || sc == '?');
+      bad |= !(strand_ok || sc == '.' || (!GTF && sc == '?'));
       const unsigned pc = fs[8] - 1 - fs[7] == 1u ? text[fs[7]] : 0u;
       phase_ok = pc - (unsigned)'0' <= 2u;
       phase = phase_ok ? (int32_t)(pc - '0') : 0;
@@ -1561,6 +1563,7 @@ struct exon_hip_gff_parser {
   // the `attributes` column (exon_hip_gff_parser_want_attributes): every row's ninth field, recorded by the line kernel, and the
   // slab of the last parse call (aligned) for exon_hip_gff_parser_attributes
   bool want_attr = false;
+  bool gtf = false;  // exon_hip_gff_parser_set_dialect: the GTF line rules and its attributes column
   PoolBufs attr_bufs;  // (of their own: a failed allocation is released and does not stick to the parser's)
   uint32_t *d_attr_off = nullptr, *d_attr_len = nullptr;
   ExonTextScratch* attr_scratch = nullptr;
@@ -1670,12 +1673,10 @@ int exon_hip_gff_parser_parse(exon_hip_gff_parser* p, void* stream, const uint8_
   const GffOut& o = p->out;
   hipLaunchKernelGGL(k_gff_classify, dim3(pblocks), dim3(TPB), 0, s, d_text, idx.nl, idx.d_scalars, (unsigned)row_bound, skip, p->d_is_row);
   launch_list_scan(s, p->d_is_row, idx.d_scalars, (unsigned)row_bound, pblocks, p->d_blocks, idx.d_scalars + 3);
-  if (p->want_attr)
-    hipLaunchKernelGGL(k_parse_gff_lines<true>, dim3(pblocks), dim3(TPB), 0, s, d_text, idx.nl, idx.d_scalars, p->d_is_row, p->d_blocks, p->tables[0], p->tables[1],
-                       p->tables[2], o, (unsigned)row_bound, skip, (unsigned)n_bytes, p->d_attr_off, p->d_attr_len);
-  else
-    hipLaunchKernelGGL(k_parse_gff_lines<false>, dim3(pblocks), dim3(TPB), 0, s, d_text, idx.nl, idx.d_scalars, p->d_is_row, p->d_blocks, p->tables[0], p->tables[1],
-                       p->tables[2], o, (unsigned)row_bound, skip, (unsigned)n_bytes, (uint32_t*)nullptr, (uint32_t*)nullptr);
+  auto* const line_kernel = p->gtf ? (p->want_attr ? k_parse_gff_lines<true, true> : k_parse_gff_lines<false, true>)
+                                   : (p->want_attr ? k_parse_gff_lines<true, false> : k_parse_gff_lines<false, false>);
+  hipLaunchKernelGGL(line_kernel, dim3(pblocks), dim3(TPB), 0, s, d_text, idx.nl, idx.d_scalars, p->d_is_row, p->d_blocks, p->tables[0], p->tables[1], p->tables[2], o,
+                     (unsigned)row_bound, skip, (unsigned)n_bytes, p->want_attr ? p->d_attr_off : (uint32_t*)nullptr, p->want_attr ? p->d_attr_len : (uint32_t*)nullptr);
   hipLaunchKernelGGL(k_gff_pack_valid, dim3(std::min(pblocks, 1024)), dim3(256), 0, s, idx.d_scalars, (unsigned)row_bound, o.vflags, o.score_valid,
                      o.strand_valid, o.phase_valid);
   for (int k = 0; k < 3; ++k) {
@@ -1728,6 +1729,7 @@ int exon_hip_gff_parser_want_attributes(exon_hip_gff_parser* p, int32_t on) {
 int exon_hip_gff_parser_attributes(exon_hip_gff_parser* p, void* stream, exon_hip_gff_attributes* out) {
   if (!p || !out) return fail(p ? p->ctx : nullptr, EXON_HIP_EINVAL, "exon_hip_gff_parser_attributes: NULL argument");
   memset(out, 0, sizeof *out);
+  if (p->gtf) return fail(p->ctx, EXON_HIP_ESTATE, "exon_hip_gff_parser_attributes: the parser reads GTF (exon_hip_gff_parser_gtf_attributes builds its Map<Utf8, Utf8>)");
   if (p->last_rows < 0)
     return fail(p->ctx, EXON_HIP_ESTATE, "exon_hip_gff_parser_attributes: no slab to build from (call exon_hip_gff_parser_want_attributes, then parse; a slab with undecided rows has none)");
   ExonGffText t;
@@ -1746,6 +1748,37 @@ int exon_hip_gff_parser_attributes(exon_hip_gff_parser* p, void* stream, exon_hi
   out->list_offsets = t.list_offsets;
   out->item_offsets = t.item_offsets;
   out->item_values = t.item_values;
+  return EXON_HIP_OK;
+}
+
+int exon_hip_gff_parser_set_dialect(exon_hip_gff_parser* p, int32_t format) {
+  if (!p || (format != EXON_HIP_FORMAT_GFF && format != EXON_HIP_FORMAT_GTF))
+    return fail(p ? p->ctx : nullptr, EXON_HIP_EINVAL, "exon_hip_gff_parser_set_dialect: EXON_HIP_FORMAT_GFF or EXON_HIP_FORMAT_GTF");
+  p->gtf = format == EXON_HIP_FORMAT_GTF;
+  p->last_rows = -1;
+  return EXON_HIP_OK;
+}
+
+int exon_hip_gff_parser_gtf_attributes(exon_hip_gff_parser* p, void* stream, exon_hip_gtf_attributes* out) {
+  if (!p || !out) return fail(p ? p->ctx : nullptr, EXON_HIP_EINVAL, "exon_hip_gff_parser_gtf_attributes: NULL argument");
+  memset(out, 0, sizeof *out);
+  if (!p->gtf) return fail(p->ctx, EXON_HIP_ESTATE, "exon_hip_gff_parser_gtf_attributes: the parser reads GFF3 (exon_hip_gff_parser_set_dialect)");
+  if (p->last_rows < 0)
+    return fail(p->ctx, EXON_HIP_ESTATE, "exon_hip_gff_parser_gtf_attributes: no slab to build from (call exon_hip_gff_parser_want_attributes, then parse; a slab with undecided rows has none)");
+  ExonGtfText t;
+  int64_t und = 0;
+  if (int rc = exon_text_gtf(p->ctx, stream, &p->attr_scratch, p->last_text, p->last_bytes, p->d_attr_off, p->d_attr_len, p->last_rows, &t, &und)) return rc;
+  HIP_TRY(p->ctx, hipStreamSynchronize(pick_stream(p->ctx, stream)));
+  out->n_undecided = und;
+  if (und) return EXON_HIP_OK;
+  out->n_entries = t.n_entries;
+  out->n_key_bytes = t.n_key_bytes;
+  out->n_value_bytes = t.n_value_bytes;
+  out->map_offsets = t.map_offsets;
+  out->key_offsets = t.key_offsets;
+  out->key_values = t.key_values;
+  out->value_offsets = t.value_offsets;
+  out->value_values = t.value_values;
   return EXON_HIP_OK;
 }
 

@@ -81,8 +81,8 @@ struct GFFRecord {
   size_t attr_len = 0;
 };
 
-[[noreturn]] inline void gff_fail(const char* line, size_t len, const std::string& what) {
-  throw std::runtime_error("GFF line '" + std::string(line, std::min<size_t>(len, 120)) + (len > 120 ? "...'" : "'") + ": " + what);
+[[noreturn]] inline void gff_fail(const char* line, size_t len, const std::string& what, const char* format = "GFF") {
+  throw std::runtime_error(std::string(format) + " line '" + std::string(line, std::min<size_t>(len, 120)) + (len > 120 ? "...'" : "'") + ": " + what);
 }
 
 // is the line (terminator and CR dropped) a row at all?  Throws for an empty line and for a ##FASTA section.
@@ -94,8 +94,10 @@ inline bool gff_is_record(const char* line, size_t len) {
   return false;
 }
 
-// one record line -> its eight columns; any violation of the line rules throws
-inline void parse_gff_record(const char* line, size_t len, GFFRecord* r) {
+// one record line -> its eight columns; any violation of the line rules throws.  GTF (gtf.h states its rules): the same eight
+// fields, but a '?' strand is an error and the eighth column is called the frame
+inline void parse_gff_columns(const char* line, size_t len, GFFRecord* r, bool gtf) {
+  const char* const fmt = gtf ? "GTF" : "GFF";
   const char* f[8];
   size_t fl[8];
   int nf = 0;
@@ -107,34 +109,35 @@ inline void parse_gff_record(const char* line, size_t len, GFFRecord* r) {
       ++nf;
       at = i + 1;
     }
-  if (nf < 8) gff_fail(line, len, "fewer than nine TAB-separated fields");
+  if (nf < 8) gff_fail(line, len, "fewer than nine TAB-separated fields", fmt);
   for (int k = 0; k < 3; ++k) {
     r->f[k] = f[k];
     r->fl[k] = fl[k];
   }
   r->attr = line + at;
   r->attr_len = len - at;
-  if (!VCFArrayBuilder::parse_pos(f[3], fl[3], &r->start) || r->start < 1) gff_fail(line, len, "invalid start '" + std::string(f[3], fl[3]) + "'");
-  if (!VCFArrayBuilder::parse_pos(f[4], fl[4], &r->end) || r->end < 1) gff_fail(line, len, "invalid end '" + std::string(f[4], fl[4]) + "'");
+  if (!VCFArrayBuilder::parse_pos(f[3], fl[3], &r->start) || r->start < 1) gff_fail(line, len, "invalid start '" + std::string(f[3], fl[3]) + "'", fmt);
+  if (!VCFArrayBuilder::parse_pos(f[4], fl[4], &r->end) || r->end < 1) gff_fail(line, len, "invalid end '" + std::string(f[4], fl[4]) + "'", fmt);
   r->has_score = !(fl[5] == 1 && f[5][0] == '.');
   r->score = 0.f;
   if (r->has_score) {
     try {
       r->score = VCFArrayBuilder::parse_f32(f[5], fl[5]);
     } catch (const std::exception&) {
-      gff_fail(line, len, "invalid score '" + std::string(f[5], fl[5]) + "'");
+      gff_fail(line, len, "invalid score '" + std::string(f[5], fl[5]) + "'", fmt);
     }
   }
   const char sc = fl[6] == 1 ? f[6][0] : '\0';
   if (sc == '+') r->strand = 0;
   else if (sc == '-') r->strand = 1;
-  else if (sc == '.' || sc == '?') r->strand = -1;
-  else gff_fail(line, len, "invalid strand '" + std::string(f[6], fl[6]) + "'");
+  else if (sc == '.' || (sc == '?' && !gtf)) r->strand = -1;
+  else gff_fail(line, len, "invalid strand '" + std::string(f[6], fl[6]) + "'", fmt);
   const char pc = fl[7] == 1 ? f[7][0] : '\0';
   if (pc == '.') r->phase = -1;
   else if (pc >= '0' && pc <= '2') r->phase = pc - '0';
-  else gff_fail(line, len, "invalid phase '" + std::string(f[7], fl[7]) + "'");
+  else gff_fail(line, len, std::string(gtf ? "invalid frame '" : "invalid phase '") + std::string(f[7], fl[7]) + "'", fmt);
 }
+inline void parse_gff_record(const char* line, size_t len, GFFRecord* r) { parse_gff_columns(line, len, r, false); }
 
 // Rust's str::from_utf8: no overlong forms, no surrogates, nothing above U+10FFFF
 inline bool gff_utf8_valid(const std::string& s) {
@@ -161,12 +164,20 @@ inline bool gff_utf8_valid(const std::string& s) {
   return true;
 }
 
+// the ninth column of a run of rows as the reader's builders and slab machinery hold it, whatever its Arrow type
+struct AttrColumn {
+  virtual ~AttrColumn() {}
+  virtual size_t rows() const = 0;
+  virtual void clear() = 0;
+  virtual struct ArrowArray* slice(size_t o, size_t n) const = 0;  // rows [o, o + n) as an array of their own
+};
+
 // the attributes column of a run of rows: the four offset levels and the two byte pools of Map<Utf8, List<Utf8>>
-struct GFFAttrColumn {
+struct GFFAttrColumn : AttrColumn {
   std::vector<int32_t> map_off{0}, key_off{0}, list_off{0}, item_off{0};  // rows -> entries -> (key bytes | items -> item bytes)
   std::string keys, items;
-  size_t rows() const { return map_off.size() - 1; }
-  void clear() {
+  size_t rows() const override { return map_off.size() - 1; }
+  void clear() override {
     map_off.assign(1, 0);
     key_off.assign(1, 0);
     list_off.assign(1, 0);
@@ -175,7 +186,7 @@ struct GFFAttrColumn {
     items.clear();
   }
   // rows [o, o + n) as an array of their own (offsets rebased, bytes copied); the whole column with o = 0, n = rows()
-  struct ArrowArray* slice(size_t o, size_t n) const {
+  struct ArrowArray* slice(size_t o, size_t n) const override {
     const int32_t e0 = map_off[o], e1 = map_off[o + n], i0 = list_off[(size_t)e0], i1 = list_off[(size_t)e1];
     const int32_t k0 = key_off[(size_t)e0], k1 = key_off[(size_t)e1], b0 = item_off[(size_t)i0], b1 = item_off[(size_t)i1];
     auto rebased = [](const std::vector<int32_t>& v, int32_t from, int32_t to, int32_t base) {
@@ -208,7 +219,8 @@ inline void gff_percent_decode(const char* p, size_t n, std::string* out) {
 }
 
 // field 9 of record `r` by THE ATTRIBUTE RULES: validated, and appended to `col` as one row when there is one
-inline void parse_gff_attributes(const char* line, size_t len, const GFFRecord& r, GFFAttrColumn* col) {
+inline void parse_gff_attributes(const char* line, size_t len, const GFFRecord& r, AttrColumn* sink) {
+  GFFAttrColumn* col = static_cast<GFFAttrColumn*>(sink);
   const char* a = r.attr;
   const size_t n = r.attr_len;
   std::string tmp;
@@ -252,10 +264,38 @@ inline bool gff_region_hit(const GFFRecord& r, const Region& rg) {
   return r.fl[0] == rg.name.size() && memcmp(r.f[0], rg.name.data(), r.fl[0]) == 0 && r.start >= rg.start && r.start <= rg.end;
 }
 
+// a field of a schema with children
+inline struct ArrowSchema* new_nested_field(const char* fmt, const char* name, bool nullable, std::vector<struct ArrowSchema*> kids) {
+  struct ArrowSchema* f = static_cast<struct ArrowSchema*>(malloc(sizeof *f));
+  make_schema(f, fmt, name, nullable, std::move(kids));
+  return f;
+}
+
+// What differs between the two formats GFFBatchReader reads -- GFF3 (here) and GTF (gtf.h): the line rules, the ninth column and
+// the eighth column's name.  Everything else (slabs, dictionaries and their re-keying, the filter, the batches) is shared.
+struct GFFDialect {
+  bool (*is_record)(const char* line, size_t len);                                                  // a row at all?  (throws: no line of the format)
+  void (*parse_record)(const char* line, size_t len, GFFRecord* r);                                 // the eight columns
+  void (*parse_attributes)(const char* line, size_t len, const GFFRecord& r, AttrColumn* sink);     // field 9: validated, appended when sink != nullptr
+  AttrColumn* (*new_attributes)();
+  struct ArrowSchema* (*attributes_field)();
+  const char* column7;
+};
+inline const GFFDialect* gff3_dialect() {
+  static const GFFDialect d = {gff_is_record, parse_gff_record, parse_gff_attributes, [] { return static_cast<AttrColumn*>(new GFFAttrColumn()); },
+                               [] {  // Field::new_map("attributes", "entries", keys, values, sorted = false) of config.rs:81-104
+                                 struct ArrowSchema* values = new_nested_field("+l", "values", true, {new_field("u", "item", true)});
+                                 struct ArrowSchema* entries = new_nested_field("+s", "entries", false, {new_field("u", "keys", false), values});
+                                 return new_nested_field("+m", "attributes", false, {entries});
+                               },
+                               "phase"};
+  return &d;
+}
+
 class GFFArrayBuilder : public ExonArrayBuilder {
  public:
-  GFFArrayBuilder(Dictionary* seqnames, Dictionary* sources, Dictionary* types, bool attributes = false)
-      : dicts_{seqnames, sources, types}, with_attrs_(attributes) {}
+  GFFArrayBuilder(Dictionary* seqnames, Dictionary* sources, Dictionary* types, const GFFDialect* dialect, bool attributes = false)
+      : dicts_{seqnames, sources, types}, with_attrs_(attributes), attrs_(dialect->new_attributes()) {}
 
   void append(const GFFRecord& r) {
     for (int k = 0; k < 3; ++k) ids_[k].append_value(dicts_[k]->lookup_or_insert(r.f[k], r.fl[k]));
@@ -279,8 +319,8 @@ class GFFArrayBuilder : public ExonArrayBuilder {
     out.push_back(strand_.finish(utf8_array(gff_strand_names())));
     out.push_back(phase_.finish(utf8_array(gff_phase_names())));
     if (with_attrs_) {
-      out.push_back(attrs_.slice(0, attrs_.rows()));
-      attrs_.clear();
+      out.push_back(attrs_->slice(0, attrs_->rows()));
+      attrs_->clear();
     }
     rows_ = 0;
     return out;
@@ -298,7 +338,7 @@ class GFFArrayBuilder : public ExonArrayBuilder {
   PrimitiveBuilder<int32_t>& strands() { return strand_; }
   PrimitiveBuilder<int32_t>& phases() { return phase_; }
   bool with_attributes() const { return with_attrs_; }
-  GFFAttrColumn& attributes() { return attrs_; }  // (the caller appends the row's map: parse_gff_attributes)
+  AttrColumn& attributes() { return *attrs_; }  // (the caller appends the row's map: the dialect's parse_attributes)
 
  private:
   Dictionary* dicts_[3];
@@ -306,7 +346,7 @@ class GFFArrayBuilder : public ExonArrayBuilder {
   PrimitiveBuilder<int64_t> start_, end_;
   PrimitiveBuilder<float> score_;
   bool with_attrs_;
-  GFFAttrColumn attrs_;
+  std::unique_ptr<AttrColumn> attrs_;
   size_t rows_ = 0;
 };
 
@@ -314,6 +354,7 @@ class GFFArrayBuilder : public ExonArrayBuilder {
 struct GFFSlabConfig {
   RegionFilter filter;
   bool attributes = false;
+  const GFFDialect* dialect = gff3_dialect();
 };
 struct GFFSlab : TextSlab {
   Dictionary dicts[3];
@@ -323,7 +364,8 @@ struct GFFSlab : TextSlab {
 inline void parse_gff_slab(GFFSlab& s, const void* vcfg) {
   const GFFSlabConfig& sc = *static_cast<const GFFSlabConfig*>(vcfg);
   const RegionFilter& filter = sc.filter;
-  s.b.reset(new GFFArrayBuilder(&s.dicts[0], &s.dicts[1], &s.dicts[2], sc.attributes));
+  const GFFDialect& d = *sc.dialect;
+  s.b.reset(new GFFArrayBuilder(&s.dicts[0], &s.dicts[1], &s.dicts[2], &d, sc.attributes));
   const char* p = s.data();
   const char* end = p + s.len;
   s.b->reserve(s.len / 64 + 16);
@@ -333,10 +375,10 @@ inline void parse_gff_slab(GFFSlab& s, const void* vcfg) {
     size_t len = nl ? (size_t)(nl - p) : (size_t)(end - p);
     const char* next = nl ? nl + 1 : end;
     if (nl && len && p[len - 1] == '\r') --len;
-    if (gff_is_record(p, len)) {
-      parse_gff_record(p, len, &rec);
+    if (d.is_record(p, len)) {
+      d.parse_record(p, len, &rec);
       const bool keep = !filter.active || gff_region_hit(rec, filter.region);
-      if (sc.attributes) parse_gff_attributes(p, len, rec, keep ? &s.b->attributes() : nullptr);
+      if (sc.attributes) d.parse_attributes(p, len, rec, keep ? &s.b->attributes() : nullptr);
       if (keep) s.b->append(rec);
     }
     p = next;
@@ -346,9 +388,10 @@ inline void parse_gff_slab(GFFSlab& s, const void* vcfg) {
 
 class GFFBatchReader : public BatchReader {
  public:
-  GFFBatchReader(const std::string& path, Compression c, GFFConfig cfg) : cfg_(std::move(cfg)) {
+  GFFBatchReader(const std::string& path, Compression c, GFFConfig cfg, const GFFDialect* dialect = gff3_dialect()) : cfg_(std::move(cfg)), d_(dialect) {
     slab_cfg_.filter = cfg_.filter;
     slab_cfg_.attributes = attributes();
+    slab_cfg_.dialect = d_;
     if (cfg_.filter.active && cfg_.filter.use_index) {
       // get_byte_range_for_file (indexed_bgzf_file.rs:52-112) with the index's own column preset
       const BinningIndex idx = read_tabix(path + ".tbi");
@@ -384,14 +427,14 @@ class GFFBatchReader : public BatchReader {
 
   bool read_batch(struct ArrowArray* out) override {
     if (pipe_) return read_batch_parallel(out);
-    GFFArrayBuilder b(&dicts[0], &dicts[1], &dicts[2], attributes());
+    GFFArrayBuilder b(&dicts[0], &dicts[1], &dicts[2], d_, attributes());
     std::string line;
     GFFRecord rec;
     while ((int64_t)b.len() < cfg_.batch_size && next_line(&line)) {
-      if (!gff_is_record(line.data(), line.size())) continue;
-      parse_gff_record(line.data(), line.size(), &rec);
+      if (!d_->is_record(line.data(), line.size())) continue;
+      d_->parse_record(line.data(), line.size(), &rec);
       const bool keep = !cfg_.filter.active || gff_region_hit(rec, cfg_.filter.region);
-      if (attributes()) parse_gff_attributes(line.data(), line.size(), rec, keep ? &b.attributes() : nullptr);
+      if (attributes()) d_->parse_attributes(line.data(), line.size(), rec, keep ? &b.attributes() : nullptr);
       if (keep) b.append(rec);
     }
     if (b.is_empty()) return false;
@@ -407,17 +450,8 @@ class GFFBatchReader : public BatchReader {
                                              new_field("l", "end", false),
                                              new_field("f", "score", true),
                                              new_field("i", "strand", true, new_field("u", "", false)),
-                                             new_field("i", "phase", true, new_field("u", "", false))};
-    if (attributes()) {  // Field::new_map("attributes", "entries", keys, values, sorted = false) of config.rs:81-104
-      auto field = [](const char* fmt, const char* name, bool nullable, std::vector<struct ArrowSchema*> k) {
-        struct ArrowSchema* f = static_cast<struct ArrowSchema*>(malloc(sizeof *f));
-        make_schema(f, fmt, name, nullable, std::move(k));
-        return f;
-      };
-      struct ArrowSchema* values = field("+l", "values", true, {new_field("u", "item", true)});
-      struct ArrowSchema* entries = field("+s", "entries", false, {new_field("u", "keys", false), values});
-      kids.push_back(field("+m", "attributes", false, {entries}));
-    }
+                                             new_field("i", d_->column7, true, new_field("u", "", false))};
+    if (attributes()) kids.push_back(d_->attributes_field());
     make_schema(out, "+s", "", false, kids);
   }
 
@@ -491,6 +525,7 @@ class GFFBatchReader : public BatchReader {
   }
 
   GFFConfig cfg_;
+  const GFFDialect* d_;
   GFFSlabConfig slab_cfg_;  // what the slab workers read (outlives the pipeline: declared in front of it)
   std::unique_ptr<BufReader> r_;
   std::unique_ptr<ChunkSource> chunks_;

@@ -110,6 +110,17 @@ struct ExonGffText {
 };
 int exon_text_gff(exon_hip_ctx* ctx, void* stream, ExonTextScratch** scratch, const uint8_t* d_text, int64_t n_bytes, const uint32_t* d_attr_off, const uint32_t* d_attr_len,
                   int64_t n_rows, ExonGffText* out, int64_t* n_undecided);
+// GTF `attributes` (Map<Utf8, Utf8>, host/gtf.h's ATTRIBUTE RULES): rows -> entries -> (key bytes | value bytes), keys and values
+// spans of the text as they stand (quotes dropped).  d_text / d_attr_off / d_attr_len as for exon_text_gff (the line kernel of the
+// GTF dialect recorded them).  n_undecided != 0: a field with a byte >= 0x80, a missing closing quote, a key without a value, an
+// empty piece, or bytes other than spaces behind a closing quote
+struct ExonGtfText {
+  const int32_t *map_offsets, *key_offsets, *value_offsets;  // [n_rows + 1], [n_entries + 1] twice
+  const uint8_t *key_values, *value_values;
+  int64_t n_entries, n_key_bytes, n_value_bytes;
+};
+int exon_text_gtf(exon_hip_ctx* ctx, void* stream, ExonTextScratch** scratch, const uint8_t* d_text, int64_t n_bytes, const uint32_t* d_attr_off, const uint32_t* d_attr_len,
+                  int64_t n_rows, ExonGtfText* out, int64_t* n_undecided);
 void exon_text_scratch_destroy(ExonTextScratch* s);
 // the parsers' own indexes the text columns are built from (valid until the next parse call)
 const unsigned* exon_hip_vcf_parser_newlines(exon_hip_vcf_parser* p);

@@ -22,6 +22,7 @@
 #include "host/cram.h"
 #include "host/formats.h"
 #include "host/gff.h"
+#include "host/gtf.h"
 #include "host/parallel.h"
 #include "internal.h"
 
@@ -40,7 +41,8 @@ struct DeviceParser {
       case EXON_HIP_FORMAT_BAM: exon_hip_bam_parser_destroy(as<exon_hip_bam_parser>()); break;
       case EXON_HIP_FORMAT_SAM: exon_hip_sam_parser_destroy(as<exon_hip_sam_parser>()); break;
       case EXON_HIP_FORMAT_FASTQ: exon_hip_fastq_parser_destroy(as<exon_hip_fastq_parser>()); break;
-      case EXON_HIP_FORMAT_GFF: exon_hip_gff_parser_destroy(as<exon_hip_gff_parser>()); break;
+      case EXON_HIP_FORMAT_GFF:
+      case EXON_HIP_FORMAT_GTF: exon_hip_gff_parser_destroy(as<exon_hip_gff_parser>()); break;  // (GTF: the same parser, its dialect set)
     }
     h = nullptr;
     owns_names = false;
@@ -81,7 +83,9 @@ struct exon_hip_scan {
   exon::BAMBatchReader* bam() const { return reader_if<exon::BAMBatchReader>(EXON_HIP_FORMAT_BAM); }
   exon::SAMBatchReader* sam() const { return reader_if<exon::SAMBatchReader>(EXON_HIP_FORMAT_SAM); }
   exon::FASTQBatchReader* fastq() const { return reader_if<exon::FASTQBatchReader>(EXON_HIP_FORMAT_FASTQ); }
-  exon::GFFBatchReader* gff() const { return reader_if<exon::GFFBatchReader>(EXON_HIP_FORMAT_GFF); }
+  // GFF and GTF: one reader class (GTFBatchReader is its GTF dialect), one device parser, one column layout
+  exon::GFFBatchReader* gff() const { return reader_if<exon::GFFBatchReader>(gtf() ? EXON_HIP_FORMAT_GTF : EXON_HIP_FORMAT_GFF); }
+  bool gtf() const { return format == EXON_HIP_FORMAT_GTF; }
   // VCF and BCF: chrom / pos / qual / filter + typed INFO columns (else BAM / SAM / CRAM's flag / mapq / ref / start / end)
   bool vcf_like() const { return format == EXON_HIP_FORMAT_VCF || format == EXON_HIP_FORMAT_BCF; }
   const std::vector<exon::InfoSpec>& info_specs() const { return vcf() ? vcf()->info_specs : bcf()->info_specs; }
@@ -327,7 +331,8 @@ static std::unique_ptr<exon::BatchReader> open_reader(const exon_hip_scan& s, De
       cfg.batch_size = bs;
       return std::unique_ptr<exon::BatchReader>(new exon::FASTABatchReader(s.path, c, cfg));
     }
-    case EXON_HIP_FORMAT_GFF: {
+    case EXON_HIP_FORMAT_GFF:
+    case EXON_HIP_FORMAT_GTF: {
       exon::GFFConfig fresh;
       fresh.batch_size = bs;
       fresh.filter = rf;
@@ -335,7 +340,7 @@ static std::unique_ptr<exon::BatchReader> open_reader(const exon_hip_scan& s, De
       fresh.reference_block_quirk = reference_tail_quirk(rf);
       exon::GFFConfig cfg = config(s.gff(), fresh);
       cfg.defer_decode = device;
-      std::unique_ptr<exon::GFFBatchReader> r(new exon::GFFBatchReader(s.path, c, cfg));
+      std::unique_ptr<exon::GFFBatchReader> r(s.gtf() ? new exon::GTFBatchReader(s.path, c, cfg) : new exon::GFFBatchReader(s.path, c, cfg));
       // names interned into the reader being replaced (a region plan's contig) keep their ids: a plan may hold one already
       if (const exon::GFFBatchReader* old = s.gff())
         for (int k = 0; k < 3; ++k) r->dicts[k].names = old->dicts[k].names;
@@ -380,9 +385,13 @@ int exon_hip_scan_open(const char* path, const exon_hip_scan_options* o, exon_hi
       rf.use_index = o->use_index != 0;
     }
     s->region = rf;
+    if (o->format == EXON_HIP_FORMAT_GTF && (o->projection & ~EXON_HIP_PROJECT_GTF_ATTRIBUTES))
+      return fail(nullptr, EXON_HIP_EUNSUPPORTED, "exon_hip_scan_options.projection 0x%llx: GTF knows one projected column, `attributes` (Map<Utf8, Utf8>), by EXON_HIP_PROJECT_GTF_ATTRIBUTES (256: the column's index in the reference's schema)", (unsigned long long)o->projection);
+    if (o->format == EXON_HIP_FORMAT_GTF && rf.use_index)
+      return fail(nullptr, EXON_HIP_EUNSUPPORTED, "exon_hip_scan_options.use_index: there is no indexed GTF table (the reference has none); a region without use_index filters the whole file");
     if (o->format == EXON_HIP_FORMAT_GFF && (o->projection & ~EXON_HIP_PROJECT_GFF_ATTRIBUTES))
       return fail(nullptr, EXON_HIP_EUNSUPPORTED, "exon_hip_scan_options.projection 0x%llx: GFF knows one projected column, `attributes` (Map<Utf8, List<Utf8>>), by EXON_HIP_PROJECT_GFF_ATTRIBUTES (256: the column's index in the reference's schema)", (unsigned long long)o->projection);
-    if (o->projection && o->format != EXON_HIP_FORMAT_VCF && o->format != EXON_HIP_FORMAT_BAM && o->format != EXON_HIP_FORMAT_BCF && o->format != EXON_HIP_FORMAT_SAM && o->format != EXON_HIP_FORMAT_GFF)
+    if (o->projection && o->format != EXON_HIP_FORMAT_VCF && o->format != EXON_HIP_FORMAT_BAM && o->format != EXON_HIP_FORMAT_BCF && o->format != EXON_HIP_FORMAT_SAM && o->format != EXON_HIP_FORMAT_GFF && o->format != EXON_HIP_FORMAT_GTF)
       return fail(nullptr, EXON_HIP_EUNSUPPORTED, "exon_hip_scan_options.projection: the id / ref / alt (/ info / formats) and name / cigar / sequence / quality_score columns are built for VCF, BCF, BAM and SAM scans");
     switch (o->format) {
       case EXON_HIP_FORMAT_VCF:
@@ -418,6 +427,9 @@ int exon_hip_scan_open(const char* path, const exon_hip_scan_options* o, exon_hi
         // as VCF text: a region rides along as a row mask; with use_index only the tabix chunks' BGZF blocks are shipped.  The
         // reference's block-range quirk is a property of its opener's byte range: the host reader reproduces it
         s->gpu_parse = o->gpu_parse != 0 && (!rf.use_index || (rf.active && wants_gpu_inflate(o, path))) && !reference_tail_quirk(rf);
+        break;
+      case EXON_HIP_FORMAT_GTF:  // a region rides along as a row mask (use_index was refused above)
+        s->gpu_parse = o->gpu_parse != 0;
         break;
       case EXON_HIP_FORMAT_CRAM:
       case EXON_HIP_FORMAT_FASTA:
@@ -542,7 +554,7 @@ int exon_hip_scan_bind_ctx(exon_hip_scan* s, exon_hip_ctx* ctx) {
   if (!s || !ctx) return fail(ctx, EXON_HIP_EINVAL, "exon_hip_scan_bind_ctx: NULL argument");
   if (s->exporter) return fail(ctx, EXON_HIP_ESTATE, "the scan is bound to a context already");
   if (s->format == EXON_HIP_FORMAT_FASTA || s->format == EXON_HIP_FORMAT_CRAM)
-    return fail(ctx, EXON_HIP_EUNSUPPORTED, "batches from the GPU pipeline: VCF, BCF, BAM, SAM, FASTQ and GFF scans (FASTA / CRAM batches come from the host readers)");
+    return fail(ctx, EXON_HIP_EUNSUPPORTED, "batches from the GPU pipeline: VCF, BCF, BAM, SAM, FASTQ, GFF and GTF scans (FASTA / CRAM batches come from the host readers)");
   if (!s->gpu_parse)  // not opened with gpu_parse, or String / list-valued INFO keys were named: the host reader builds those columns
     return fail(ctx, EXON_HIP_EUNSUPPORTED, "this scan's batches come from the host reader (opened without gpu_parse, or it names INFO keys only the host reader builds)");
   if (s->rows != 0) return fail(ctx, EXON_HIP_ESTATE, "the scan has been read from already");
@@ -1946,7 +1958,8 @@ struct Span {
   const T* begin() const { return p; }
 };
 struct HostText {
-  bool vcf = false, bam = false, bcf = false, gff = false;
+  bool vcf = false, bam = false, bcf = false, gff = false, gtf = false;
+  Span<int32_t> gtf_val_off;  // GTF attributes: off[0] = the map's offsets, key_off / val[0] the keys, gtf_val_off / val[1] the values
   uint64_t projection = 0;
   // GFF attributes: off[0] = the map's offsets, key_off / val[0] the keys, list_off the value lists, gff_item_off / val[1] their items
   Span<int32_t> key_off, list_off, gff_item_off;
@@ -1975,6 +1988,7 @@ struct SlabText {
   ExonBamText bam;  // BAM and SAM
   ExonBcfText bcf;
   ExonGffText gff;
+  ExonGtfText gtf;
   std::function<int()> build;
 };
 static int fetch_text(exon_hip_ctx* ctx, SlabCopier* cp, size_t also_reserve, int64_t n_rows, uint64_t projection, const SlabText& t, HostText* h, bool big_batches) {
@@ -2056,6 +2070,15 @@ static int fetch_text(exon_hip_ctx* ctx, SlabCopier* cp, size_t also_reserve, in
     get(h->gff_item_off, gt->item_offsets, (size_t)gt->n_items + 1);
     get(h->val[1], gt->item_values, (size_t)gt->n_item_bytes);
   }
+  if (t.format == EXON_HIP_FORMAT_GTF && (projection & EXON_HIP_PROJECT_GTF_ATTRIBUTES)) {
+    const ExonGtfText* gt = &t.gtf;
+    h->gtf = true;
+    get(h->off[0], gt->map_offsets, n + 1);
+    get(h->key_off, gt->key_offsets, (size_t)gt->n_entries + 1);
+    get(h->val[0], gt->key_values, (size_t)gt->n_key_bytes);
+    get(h->gtf_val_off, gt->value_offsets, (size_t)gt->n_entries + 1);
+    get(h->val[1], gt->value_values, (size_t)gt->n_value_bytes);
+  }
   size_t total = 64;
   for (const Want& w : wants) total += (w.count * w.elem + 63) & ~(size_t)63;
   if (!cp->reserve(total + 256 * wants.size() + also_reserve)) return fail(ctx, EXON_HIP_ENOMEM, "no device staging buffer of %zu bytes for a slab's string columns", total);
@@ -2119,6 +2142,12 @@ static void text_batch(const HostText& h, const int64_t* rows, int64_t r0, int64
       struct ArrowArray* keys = utf8_view(h.key_off, h.val[0], nullptr, 0, (int64_t)h.key_off.n - 1);
       struct ArrowArray* items = utf8_view(h.gff_item_off, h.val[1], nullptr, 0, (int64_t)h.gff_item_off.n - 1);
       struct ArrowArray* values = exon::arena_array(arena, (int64_t)h.list_off.n - 1, 0, 0, 2, nullptr, h.list_off.data(), nullptr, items);
+      struct ArrowArray* entries = exon::arena_struct2(arena, (int64_t)h.key_off.n - 1, keys, values);
+      kids->push_back(exon::arena_array(arena, n, r0, 0, 2, nullptr, h.off[0].data(), nullptr, entries));
+    }
+    if (h.gtf) {  // the slab's entries, keys and values shared by every batch; the map cut by its offset
+      struct ArrowArray* keys = utf8_view(h.key_off, h.val[0], nullptr, 0, (int64_t)h.key_off.n - 1);
+      struct ArrowArray* values = utf8_view(h.gtf_val_off, h.val[1], nullptr, 0, (int64_t)h.gtf_val_off.n - 1);
       struct ArrowArray* entries = exon::arena_struct2(arena, (int64_t)h.key_off.n - 1, keys, values);
       kids->push_back(exon::arena_array(arena, n, r0, 0, 2, nullptr, h.off[0].data(), nullptr, entries));
     }
@@ -2203,6 +2232,19 @@ static void text_batch(const HostText& h, const int64_t* rows, int64_t r0, int64
         col.list_off.push_back((int32_t)col.item_off.size() - 1);
       }
       col.map_off.push_back((int32_t)col.key_off.size() - 1);
+    }
+    kids->push_back(col.slice(0, (size_t)n));
+  }
+  if (h.gtf) {  // the map gather, two levels: every kept row's entries, their keys and values, copied
+    exon::GTFAttrColumn col;
+    const char* kv = reinterpret_cast<const char*>(h.val[0].data());
+    const char* vv = reinterpret_cast<const char*>(h.val[1].data());
+    for (int64_t i = 0; i < n; ++i) {
+      const int64_t r = row_at(i);
+      for (int32_t e = h.off[0][(size_t)r]; e < h.off[0][(size_t)r + 1]; ++e)
+        col.append(kv + h.key_off[(size_t)e], (size_t)(h.key_off[(size_t)e + 1] - h.key_off[(size_t)e]), vv + h.gtf_val_off[(size_t)e],
+                   (size_t)(h.gtf_val_off[(size_t)e + 1] - h.gtf_val_off[(size_t)e]));
+      col.close_row();
     }
     kids->push_back(col.slice(0, (size_t)n));
   }
@@ -2301,7 +2343,7 @@ static int export_slab(exon_hip_scan* scan, const exon_hip_column* sc, int64_t n
     } else if (kept == 0) {
       // GFF `attributes`: field 9 of every record is validated, kept or not (host/gff.h) -- the measure pass runs over a slab that
       // sends nothing too, and hands the file over when it meets a row the host reader must judge
-      if (projected && projected->format == EXON_HIP_FORMAT_GFF)
+      if (projected && (projected->format == EXON_HIP_FORMAT_GFF || projected->format == EXON_HIP_FORMAT_GTF))
         if (const int rc = projected->build()) return rc;
       return EXON_HIP_OK;
     }
@@ -2439,7 +2481,7 @@ static int export_slab(exon_hip_scan* scan, const exon_hip_column* sc, int64_t n
       }
       const double tv1 = now_s();
       g_t_views += tv1 - tv0;
-      if (text.vcf || text.bam || text.bcf || text.gff) text_batch(text, nullptr, b0, n, &kids, arena);
+      if (text.vcf || text.bam || text.bcf || text.gff || text.gtf) text_batch(text, nullptr, b0, n, &kids, arena);
       g_t_text_batch += now_s() - tv1;
       struct ArrowArray* out = static_cast<struct ArrowArray*>(malloc(sizeof *out));
       exon::make_struct_of_arena(out, n, arena, kids);
@@ -2482,7 +2524,7 @@ static int export_slab(exon_hip_scan* scan, const exon_hip_column* sc, int64_t n
         kids.push_back(a);
       }
     }
-    if (text.vcf || text.bam || text.bcf || text.gff) text_batch(text, keep.data() + b0, 0, n, &kids);
+    if (text.vcf || text.bam || text.bcf || text.gff || text.gtf) text_batch(text, keep.data() + b0, 0, n, &kids);
     struct ArrowArray* out = static_cast<struct ArrowArray*>(malloc(sizeof *out));
     exon::make_struct(out, n, std::move(kids));
     if (const int rc = push_batch(ex, out, n)) return rc;
@@ -2561,7 +2603,8 @@ static int64_t data_offset(const exon_hip_scan* scan) {
     case EXON_HIP_FORMAT_BCF: return scan->bcf()->data_offset();
     case EXON_HIP_FORMAT_BAM: return scan->bam()->data_offset();
     case EXON_HIP_FORMAT_SAM: return scan->sam()->data_offset();
-    case EXON_HIP_FORMAT_GFF: return scan->gff()->data_offset();  // (no header: '#' lines are the device parser's to skip)
+    case EXON_HIP_FORMAT_GFF:
+    case EXON_HIP_FORMAT_GTF: return scan->gff()->data_offset();  // (no header: '#' lines are the device parser's to skip)
   }
   return 0;  // FASTQ: no header
 }
@@ -2572,7 +2615,8 @@ static std::unique_ptr<exon::ByteSource> take_text_stream(exon_hip_scan* scan, s
     case EXON_HIP_FORMAT_VCF: return scan->vcf()->take_stream(carry);
     case EXON_HIP_FORMAT_SAM: return scan->sam()->take_stream(carry);
     case EXON_HIP_FORMAT_FASTQ: return scan->fastq()->take_stream(carry);
-    case EXON_HIP_FORMAT_GFF: return scan->gff()->take_stream(carry);
+    case EXON_HIP_FORMAT_GFF:
+    case EXON_HIP_FORMAT_GTF: return scan->gff()->take_stream(carry);
   }
   return nullptr;  // (BAM and BCF are BGZF by definition)
 }
@@ -2632,12 +2676,14 @@ static int create_parser(exon_hip_scan* scan, exon_hip_ctx* ctx, int64_t max_tex
       p.h = h;
       break;
     }
-    case EXON_HIP_FORMAT_GFF: {  // seeded with the names interned so far (a region's contig): their ids stay
+    case EXON_HIP_FORMAT_GFF:
+    case EXON_HIP_FORMAT_GTF: {  // seeded with the names interned so far (a region's contig): their ids stay
       std::vector<const char*> names;
       for (const auto& c : scan->gff()->dicts[0].names) names.push_back(c.c_str());
       exon_hip_gff_parser* h = nullptr;
       rc = exon_hip_gff_parser_create(ctx, names.data(), (int32_t)names.size(), max_text_bytes, &h);
       p.h = h;
+      if (!rc && scan->gtf()) rc = exon_hip_gff_parser_set_dialect(h, EXON_HIP_FORMAT_GTF);
       break;
     }
   }
@@ -2728,7 +2774,8 @@ static int parse_slab(exon_hip_scan* scan, hipStream_t hs, const uint8_t* d_text
       p->pos_valid = cols.pos_valid;
       return EXON_HIP_OK;
     }
-    case EXON_HIP_FORMAT_GFF: {
+    case EXON_HIP_FORMAT_GFF:
+    case EXON_HIP_FORMAT_GTF: {
       exon_hip_gff_columns cols;
       rc = exon_hip_gff_parser_parse(scan->parser.as<exon_hip_gff_parser>(), hs, d_text, (int64_t)n, &cols);
       if (rc) return rc;
@@ -2782,13 +2829,15 @@ static int build_text(exon_hip_scan* scan, exon_hip_ctx* ctx, hipStream_t hs, co
     case EXON_HIP_FORMAT_SAM:  // undecided: a CIGAR / QUAL the device would not print the way the reader does
       r = exon_text_sam(ctx, hs, &scan->text_scratch, d_text, (int64_t)n, exon_hip_sam_parser_newlines(scan->parser.as<exon_hip_sam_parser>()), n_rows, proj, &t->bam, &undecided);
       break;
-    case EXON_HIP_FORMAT_GFF: {  // undecided: a field the ATTRIBUTE RULES refuse or whose UTF-8 the host must check; more items than the scratch holds
+    case EXON_HIP_FORMAT_GFF:
+    case EXON_HIP_FORMAT_GTF: {  // undecided: a field the ATTRIBUTE RULES refuse or whose UTF-8 the host must check; GFF: more items than the scratch holds
       const uint8_t* text = nullptr;
       int64_t text_bytes = 0;
       const uint32_t *off = nullptr, *len = nullptr;
       exon_hip_gff_parser_attr_fields(scan->parser.as<exon_hip_gff_parser>(), &text, &text_bytes, &off, &len);
       if (!off || !len || !text) return fail(ctx, EXON_HIP_ESTATE, "GFF attributes: the slab was parsed without its ninth fields recorded");
-      r = exon_text_gff(ctx, hs, &scan->text_scratch, text, text_bytes, off, len, n_rows, &t->gff, &undecided);
+      if (scan->gtf()) r = exon_text_gtf(ctx, hs, &scan->text_scratch, text, text_bytes, off, len, n_rows, &t->gtf, &undecided);
+      else r = exon_text_gff(ctx, hs, &scan->text_scratch, text, text_bytes, off, len, n_rows, &t->gff, &undecided);
       break;
     }
   }
@@ -3038,7 +3087,7 @@ static int consume_scan_impl(exon_hip_stream* st, exon_hip_scan* scan, int64_t* 
 
 // column of the scan that holds the contig / reference dictionary a region is named in
 static int region_dict_column(const exon_hip_scan* s) {
-  return (s->format == EXON_HIP_FORMAT_VCF || s->format == EXON_HIP_FORMAT_BCF || s->format == EXON_HIP_FORMAT_GFF) ? 0 : 2;
+  return (s->format == EXON_HIP_FORMAT_VCF || s->format == EXON_HIP_FORMAT_BCF || s->gff()) ? 0 : 2;
 }
 
 }  // extern "C"

@@ -12,6 +12,7 @@
 //        sequence   Utf8, 4-bit codes through "=ACMGRSVTWYHKDBN"      :178-183
 //        quality_scores  List<Int64>, the raw bytes as i8 -> i64      :184-201
 //   GFF  attributes Map<Utf8, List<Utf8>>, never NULL                 exon-gff/src/array_builder.rs:141-165 (host/gff.h: THE ATTRIBUTE RULES)
+//   GTF  attributes Map<Utf8, Utf8>, never NULL                       exon-gtf/src/array_builder.rs:82-87 (host/gtf.h: THE ATTRIBUTE RULES)
 // One thread per row measures, an exclusive scan turns lengths into offsets, one thread per row fills (rows are short; the bytes
 // of a slab are read twice, L2-resident the second time).  Nothing here is on the fused kernels' path: a scan that projects none of
 // these columns launches none of this.
@@ -572,6 +573,123 @@ __global__ __launch_bounds__(TPB) void k_gff_attr_fill(const uint8_t* __restrict
   }
 }
 
+// ---- GTF ---------------------------------------------------------------------------------------------------------------------------
+// `attributes`, Map<Utf8, Utf8>, by THE ATTRIBUTE RULES of host/gtf.h: the ninth field of row r is text[off[r], off[r] + len[r])
+// (k_parse_gff_lines<true, true> recorded it under the row's rank).  Both kernels walk the field once through the same five
+// states -- key, gap, quoted value, bare value, after-value -- in gtf_attr_walk, which calls `emit` with the spans of every
+// entry's key and value: they are parts of the text as they stand (quotes and trailing spaces lie outside the spans, nothing is
+// decoded), so the measure kernel adds up their lengths and the fill kernel copies them eight bytes at a time.  A byte >= 0x80
+// anywhere in the field makes the row undecided: whether it is UTF-8 is the host reader's to say.
+enum : unsigned { GTF_KEY, GTF_GAP, GTF_QUOTED, GTF_BARE, GTF_AFTER };
+// true: the field breaks a rule (entries emitted in front of the break do not count: the row is the host reader's)
+template <class Emit>
+__device__ __forceinline__ bool gtf_attr_walk(const uint8_t* __restrict__ text, unsigned begin, unsigned end, Emit&& emit) {
+  unsigned st = GTF_KEY;
+  unsigned kb = begin, ke = begin, vb = begin, ve = begin;  // the key [kb, ke); a bare value up to its last non-space byte [vb, ve)
+  bool bad = false;
+  for (unsigned i = begin; i < end; ++i) {
+    const unsigned c = text[i];
+    bad |= c >= 0x80u;
+    if (st == GTF_KEY) {
+      if (c == ' ') {
+        if (i == kb) kb = i + 1;  // spaces in front of a key
+        else ke = i, st = GTF_GAP;
+      } else if (c == ';') {  // an empty piece, or a key without a value
+        bad = true;
+        kb = i + 1;
+      }
+    } else if (st == GTF_GAP) {
+      if (c == ';') {  // a key without a value
+        bad = true;
+        kb = i + 1;
+        st = GTF_KEY;
+      } else if (c == '"') {
+        vb = i + 1;
+        st = GTF_QUOTED;
+      } else if (c != ' ') {
+        vb = i;
+        ve = i + 1;
+        st = GTF_BARE;
+      }
+    } else if (st == GTF_QUOTED) {
+      if (c == '"') {
+        emit(kb, ke, vb, i);
+        st = GTF_AFTER;
+      }
+    } else if (st == GTF_BARE) {
+      if (c == ';') {
+        emit(kb, ke, vb, ve);
+        kb = i + 1;
+        st = GTF_KEY;
+      } else if (c != ' ') {
+        ve = i + 1;
+      }
+    } else {  // GTF_AFTER: spaces, then ';' or the end
+      if (c == ';') {
+        kb = i + 1;
+        st = GTF_KEY;
+      } else if (c != ' ') {
+        bad = true;
+      }
+    }
+  }
+  if (st == GTF_BARE) emit(kb, ke, vb, ve);
+  // the field may end behind an entry or in front of a key; not inside a key, behind one, or inside quotes
+  return bad || (st == GTF_KEY && kb < end) || st == GTF_GAP || st == GTF_QUOTED;
+}
+struct GtfLens {
+  uint32_t *entries, *key_bytes, *value_bytes;  // per row
+};
+__global__ __launch_bounds__(TPB) void k_gtf_attr_measure(const uint8_t* __restrict__ text, const uint32_t* __restrict__ attr_off, const uint32_t* __restrict__ attr_len,
+                                                          unsigned n_rows, GtfLens o, unsigned* __restrict__ undecided) {
+  const unsigned row = blockIdx.x * TPB + threadIdx.x;
+  bool bad = false;
+  if (row < n_rows) {
+    const unsigned begin = attr_off[row], end = begin + attr_len[row];
+    unsigned entries = 0, kbytes = 0, vbytes = 0;
+    bad = gtf_attr_walk(text, begin, end, [&](unsigned kb, unsigned ke, unsigned vb, unsigned ve) {
+      ++entries;
+      kbytes += ke - kb;
+      vbytes += ve - vb;
+    });
+    o.entries[row] = bad ? 0u : entries;
+    o.key_bytes[row] = bad ? 0u : kbytes;
+    o.value_bytes[row] = bad ? 0u : vbytes;
+  }
+  const unsigned long long bb = __ballot(bad);
+  if ((threadIdx.x & 63) == 0 && bb) atomicAdd(undecided, (unsigned)__popcll(bb));
+}
+// row_* : the scans of the three lengths (the row's first entry, key byte, value byte); row_entry is the map's offsets buffer.
+// Every write is bounded by what its buffer holds (offset_cap entries in key_off / value_off, byte_cap bytes in the two pools).
+__global__ __launch_bounds__(TPB) void k_gtf_attr_fill(const uint8_t* __restrict__ text, const uint32_t* __restrict__ attr_off, const uint32_t* __restrict__ attr_len,
+                                                       unsigned n_rows, const int32_t* __restrict__ row_entry, const int32_t* __restrict__ row_kb,
+                                                       const int32_t* __restrict__ row_vb, int32_t* __restrict__ key_off, int32_t* __restrict__ value_off,
+                                                       uint8_t* __restrict__ key_values, uint8_t* __restrict__ value_values, unsigned entries_total,
+                                                       unsigned kb_total, unsigned vb_total, unsigned offset_cap, unsigned byte_cap) {
+  const unsigned row = blockIdx.x * TPB + threadIdx.x;
+  if (row >= n_rows) return;
+  if (row_entry[row + 1] > row_entry[row]) {  // (a row of no entries writes nothing)
+    const unsigned begin = attr_off[row], end = begin + attr_len[row];
+    unsigned e = (unsigned)row_entry[row], kw = (unsigned)row_kb[row], vw = (unsigned)row_vb[row];
+    gtf_attr_walk(text, begin, end, [&](unsigned kb, unsigned ke, unsigned vb, unsigned ve) {
+      const unsigned kn = ke - kb, vn = ve - vb;
+      if (e < offset_cap) {
+        key_off[e] = (int32_t)kw;
+        value_off[e] = (int32_t)vw;
+      }
+      if (kw + kn <= byte_cap) copy_run(key_values + kw, text + kb, kn);
+      if (vw + vn <= byte_cap) copy_run(value_values + vw, text + vb, vn);
+      ++e;
+      kw += kn;
+      vw += vn;
+    });
+  }
+  if (row == n_rows - 1 && entries_total < offset_cap) {  // the closing offsets (entry 0 of both levels when the slab has no entry at all)
+    key_off[entries_total] = (int32_t)kb_total;
+    value_off[entries_total] = (int32_t)vb_total;
+  }
+}
+
 struct ExonTextScratch {
   PoolBufs bufs, qual_bufs;  // qual_bufs: the quality_scores values, grown on demand
   int64_t max_rows = 0, max_bytes = 0;
@@ -585,7 +703,7 @@ struct ExonTextScratch {
   unsigned* totals = nullptr;    // device [4]
   unsigned* h_totals = nullptr;  // pinned
   int32_t* item_off = nullptr;   // VCF / BCF id items
-  int32_t* item_off2 = nullptr;  // BCF alt items; GFF: the entries' list offsets (item_off: their key offsets)
+  int32_t* item_off2 = nullptr;  // BCF alt items; GFF: the entries' list offsets (item_off: their key offsets); GTF: their value offsets
   int32_t* item_off3 = nullptr;  // GFF: the items' byte offsets
   unsigned* totals5 = nullptr;   // device [8]: the five totals of the BCF columns
   unsigned* h_totals5 = nullptr; // pinned
@@ -624,7 +742,19 @@ void exon_text_scratch_destroy(ExonTextScratch* s) { delete s; }
 //                    row's last are followed by a ';': a field of k bytes holds up to (k + 1) / 2, a slab up to (F + n_rows) / 2 <=
 //                    n_bytes / 2 entries + 1 closing, against max_bytes / 2 + max_rows + 66: fits
 //   GFF    item_off3 (an item's byte offset): "=,,,," is an item a byte: up to F items + 1 entry, against the same size: checked
-static int scratch_for(exon_hip_ctx* ctx, ExonTextScratch** sp, int64_t max_rows, int64_t max_bytes, bool vcf, int n_cols = 3, bool gff = false) {
+//   GTF    (max_bytes = n_bytes; F as for GFF: the eight columns in front of the ninth field are the same)
+//   GTF    values[0]: key bytes, values[1]: value bytes; both are parts of the field as they stand, and a key and its value never
+//                    share a byte: <= F together: fits
+//   GTF    item_off, item_off2 (an entry's key offset and value offset): the shortest entry is three bytes ("k v": a key byte, a
+//                    space, a value byte; a quoted one has four) and all but a row's last are followed by a ';': a field of k
+//                    bytes holds up to (k + 1) / 4, a slab up to (F + n_rows) / 4 <= n_bytes / 4 entries + 1 closing, against
+//                    max_bytes / 2 + max_rows + 66: fits
+//          No GTF buffer is "checked".  exon_text_gtf still passes its totals through fits() and k_gtf_attr_fill bounds its writes:
+//          the derivation above is then not the only thing between a slab and the end of a buffer.
+// attr: 0, ATTR_GFF or ATTR_GTF -- the offset buffers of the map column
+enum { ATTR_NONE = 0, ATTR_GFF = 1, ATTR_GTF = 2 };
+static int scratch_for(exon_hip_ctx* ctx, ExonTextScratch** sp, int64_t max_rows, int64_t max_bytes, bool vcf, int n_cols = 3, int attr = ATTR_NONE) {
+  const bool gff = attr != ATTR_NONE;  // (either map column: two byte pools, no SAM field index)
   ExonTextScratch* s = *sp;
   if (s && s->max_rows >= max_rows && s->max_bytes >= max_bytes && s->n_cols >= n_cols) return EXON_HIP_OK;
   delete s;
@@ -647,7 +777,7 @@ static int scratch_for(exon_hip_ctx* ctx, ExonTextScratch** sp, int64_t max_rows
   if (gff) {
     s->item_off = b.take<int32_t>(s->item_cap * 4);
     s->item_off2 = b.take<int32_t>(s->item_cap * 4);
-    s->item_off3 = b.take<int32_t>(s->item_cap * 4);
+    if (attr == ATTR_GFF) s->item_off3 = b.take<int32_t>(s->item_cap * 4);
     s->totals5 = b.take<unsigned>(32);
     s->h_totals5 = b.pinned<unsigned>(32);
   }
@@ -920,7 +1050,7 @@ int exon_text_gff(exon_hip_ctx* ctx, void* stream, ExonTextScratch** sp, const u
   memset(out, 0, sizeof *out);
   *n_undecided = 0;
   if (n_rows == 0) return EXON_HIP_OK;
-  int rc = scratch_for(ctx, sp, std::max<int64_t>(n_rows, 1 << 16), std::max<int64_t>(n_bytes, 1 << 20), false, 4, true);
+  int rc = scratch_for(ctx, sp, std::max<int64_t>(n_rows, 1 << 16), std::max<int64_t>(n_bytes, 1 << 20), false, 4, ATTR_GFF);
   if (rc) return rc;
   ExonTextScratch* s = *sp;
   hipStream_t hs = pick_stream(ctx, stream);
@@ -953,5 +1083,44 @@ int exon_text_gff(exon_hip_ctx* ctx, void* stream, ExonTextScratch** sp, const u
   out->n_items = items;
   out->n_key_bytes = key_bytes;
   out->n_item_bytes = item_bytes;
+  return EXON_HIP_OK;
+}
+
+int exon_text_gtf(exon_hip_ctx* ctx, void* stream, ExonTextScratch** sp, const uint8_t* d_text, int64_t n_bytes, const uint32_t* d_attr_off, const uint32_t* d_attr_len,
+                  int64_t n_rows, ExonGtfText* out, int64_t* n_undecided) {
+  memset(out, 0, sizeof *out);
+  *n_undecided = 0;
+  if (n_rows == 0) return EXON_HIP_OK;
+  int rc = scratch_for(ctx, sp, std::max<int64_t>(n_rows, 1 << 16), std::max<int64_t>(n_bytes, 1 << 20), false, 3, ATTR_GTF);
+  if (rc) return rc;
+  ExonTextScratch* s = *sp;
+  hipStream_t hs = pick_stream(ctx, stream);
+  const unsigned n = (unsigned)n_rows;
+  const int nb = (int)((n + TPB - 1) / TPB);
+  GtfLens L{s->len[0], s->len[1], s->len[2]};
+  unsigned* d_und = s->totals5 + 7;
+  HIP_TRY(ctx, hipMemsetAsync(s->totals5, 0, 32, hs));
+  hipLaunchKernelGGL(k_gtf_attr_measure, dim3(nb), dim3(TPB), 0, hs, d_text, d_attr_off, d_attr_len, n, L, d_und);
+  for (int k = 0; k < 3; ++k) scan_lengths(hs, s, s->len[k], n, s->off[k], s->totals5 + k);  // entries (the map's offsets), key bytes, value bytes
+  HIP_TRY(ctx, hipMemcpyAsync(s->h_totals5, s->totals5, 32, hipMemcpyDeviceToHost, hs));
+  HIP_TRY(ctx, hipStreamSynchronize(hs));
+  *n_undecided = s->h_totals5[7];
+  if (*n_undecided) return EXON_HIP_OK;
+  const unsigned entries = s->h_totals5[0], key_bytes = s->h_totals5[1], value_bytes = s->h_totals5[2];
+  if (!fits(s, {key_bytes, value_bytes}, {entries})) {  // (never, by the capacity table above scratch_for)
+    *n_undecided = n_rows;
+    return EXON_HIP_OK;
+  }
+  hipLaunchKernelGGL(k_gtf_attr_fill, dim3(nb), dim3(TPB), 0, hs, d_text, d_attr_off, d_attr_len, n, s->off[0], s->off[1], s->off[2], s->item_off, s->item_off2, s->values[0],
+                     s->values[1], entries, key_bytes, value_bytes, (unsigned)std::min<size_t>(s->item_cap, 0xFFFFFFFFu), (unsigned)std::min<size_t>(s->value_cap, 0xFFFFFFFFu));
+  HIP_TRY(ctx, hipGetLastError());
+  out->map_offsets = s->off[0];
+  out->key_offsets = s->item_off;
+  out->value_offsets = s->item_off2;
+  out->key_values = s->values[0];
+  out->value_values = s->values[1];
+  out->n_entries = entries;
+  out->n_key_bytes = key_bytes;
+  out->n_value_bytes = value_bytes;
   return EXON_HIP_OK;
 }

@@ -397,14 +397,14 @@ class Scan:
 
     PROJECT = {"vcf": {"id": 1, "ref": 2, "alt": 4, "info": 8, "formats": 16}, "bam": {"name": 1, "cigar": 2, "sequence": 4, "quality_score": 8},
                "bcf": {"id": 1, "ref": 2, "alt": 4}, "sam": {"name": 1, "cigar": 2, "sequence": 4, "quality_score": 8},
-               "gff": {"attributes": 256}}
+               "gff": {"attributes": 256}, "gtf": {"attributes": 256}}
 
     def __init__(self, path, fmt, compression=None, batch_size=0, info_field=None, region=None, use_index=False,
                  gpu_parse=False, project=()):
         """project: names of the reference's columns beyond the fused kernels' operands (EXON_HIP_PROJECT_*): VCF "id", "ref", "alt",
         "info", "formats" (the last two as the reference's unparsed Utf8 columns; host reader only);
         BAM "name", "cigar", "sequence", "quality_score" -- appended behind the default columns in that order; GFF "attributes"
-        (the reference's Map<Utf8, List<Utf8>>, column 8)."""
+        (the reference's Map<Utf8, List<Utf8>>, column 8); GTF "attributes" (the reference's Map<Utf8, Utf8>, column 8)."""
         self.lib = L.load()
         self.fmt = fmt
         mask = 0
@@ -570,14 +570,19 @@ class VCFParser:
 
 class GFFParser:
     """GFF3 record parsing on the GPU (exon_hip_gff_parser_*): text slab in HBM -> the GFF device layout in HBM.  The seqname, source
-    and type dictionaries grow across slabs; `seed_seqnames` take the ids 0 .. len - 1 before the first slab."""
+    and type dictionaries grow across slabs; `seed_seqnames` take the ids 0 .. len - 1 before the first slab.
+    dialect="gtf": the same parser under the GTF rules (exon_hip_gff_parser_set_dialect) -- a '?' strand is undecided, and the
+    attributes column is Map<Utf8, Utf8> (exon_hip_gff_parser_gtf_attributes)."""
 
-    def __init__(self, ctx, seed_seqnames=(), max_slab_bytes=64 << 20):
+    def __init__(self, ctx, seed_seqnames=(), max_slab_bytes=64 << 20, dialect="gff"):
         self.ctx = ctx
+        self.dialect = dialect
         names = (C.c_char_p * max(len(seed_seqnames), 1))(*[c.encode() for c in seed_seqnames])
         h = C.c_void_p()
         ctx._check(ctx.lib.exon_hip_gff_parser_create(ctx.h, names, len(seed_seqnames), max_slab_bytes, C.byref(h)))
         self.h = h
+        if dialect != "gff":
+            ctx._check(ctx.lib.exon_hip_gff_parser_set_dialect(h, L.FORMATS[dialect]))
 
     def parse_device(self, d_text, n_bytes, stream=None):
         cols = L.GFFColumns()
@@ -588,7 +593,8 @@ class GFFParser:
     def parse_host(self, text, misalign=0, attributes=False, all_rows=False):
         """Test helper: copy `text` to HBM (`misalign` bytes past a 16-byte boundary), parse, bring the columns back as numpy arrays
         (none of them when the device left a row undecided).  attributes: the `attributes` column too, built on the device
-        (exon_hip_gff_parser_attributes): res["attributes"] = its six buffers, four totals and n_undecided (buffers only when 0).
+        (exon_hip_gff_parser_attributes): res["attributes"] = its six buffers, four totals and n_undecided (buffers only when 0);
+        for the GTF dialect (exon_hip_gff_parser_gtf_attributes) its five buffers, three totals and n_undecided.
         all_rows: the columns of an undecided slab too (its decided rows hold their values; dictionary ids are provisional)."""
         buf = np.frombuffer(text, np.uint8)
         d = self.ctx.to_device(np.concatenate([np.full(misalign, 10, np.uint8), buf, np.zeros(64, np.uint8)]))
@@ -611,7 +617,18 @@ class GFFParser:
         res["score"] = get(cols.score, np.float32, n)
         for name in ("score_valid", "strand_valid", "phase_valid"):
             res[name] = get(getattr(cols, name), np.uint8, nb)
-        if attributes and cols.n_undecided == 0:
+        if attributes and cols.n_undecided == 0 and self.dialect == "gtf":
+            a = L.GTFAttributes()
+            self.ctx._check(self.ctx.lib.exon_hip_gff_parser_gtf_attributes(self.h, None, C.byref(a)))
+            at = {k: getattr(a, k) for k in ("n_entries", "n_key_bytes", "n_value_bytes", "n_undecided")}
+            if a.n_undecided == 0 and n:
+                at["map_offsets"] = get(a.map_offsets, np.int32, n + 1)
+                at["key_offsets"] = get(a.key_offsets, np.int32, a.n_entries + 1)
+                at["key_values"] = get(a.key_values, np.uint8, a.n_key_bytes)
+                at["value_offsets"] = get(a.value_offsets, np.int32, a.n_entries + 1)
+                at["value_values"] = get(a.value_values, np.uint8, a.n_value_bytes)
+            res["attributes"] = at
+        elif attributes and cols.n_undecided == 0:
             a = L.GFFAttributes()
             self.ctx._check(self.ctx.lib.exon_hip_gff_parser_attributes(self.h, None, C.byref(a)))
             at = {k: getattr(a, k) for k in ("n_entries", "n_items", "n_key_bytes", "n_item_bytes", "n_undecided")}

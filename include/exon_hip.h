@@ -439,6 +439,15 @@ int exon_hip_stream_close(exon_hip_stream* s);
  *         is the reference reader's own filter (exon-gff/src/batch_reader.rs:76-97): seqname = name AND start inside the
  *         interval; with use_index the chunks come from <path>.tbi (GFF preset, read from the index header).  A ##FASTA
  *         section is EXON_HIP_EUNSUPPORTED.  Plans address the columns by index: K2 (0, 3); K6 / K7 (0, 3, 4).
+ *   GTF   0 seqname(dict) 1 source(dict) 2 type(dict) 3 start:i64 4 end:i64 5 score:f32? 6 strand(dict ["+","-"])? 7 frame(dict
+ *         ["0","1","2"])?  -- the reference's schema order (exon-gtf/src/config.rs); dictionaries as for GFF.  With
+ *         EXON_HIP_PROJECT_GTF_ATTRIBUTES column 8 is `attributes`, the reference's Map<Utf8, Utf8> (Arrow "+m", not NULL, keys
+ *         unsorted; entries{keys: Utf8, values: Utf8?}, no value is ever NULL; exon-gtf/src/config.rs:28-41), by the ATTRIBUTE
+ *         RULES of exon_amd/csrc/host/gtf.h: `key "value"; key value;`, a ';' inside quotes belongs to the value, quotes
+ *         dropped, nothing decoded, validated on every record.  Built by the host reader and by the GPU pipeline; any other
+ *         GTF projection bit is EXON_HIP_EUNSUPPORTED.  A region is the GFF reader's filter (seqname = name AND start inside
+ *         the interval); use_index is EXON_HIP_EUNSUPPORTED (the reference has no indexed GTF table).  A '?' strand is an
+ *         error (GFF3 reads it as NULL).  Plans address the columns as for GFF.
  * CPU-only: no ctx needed; errors are reported through exon_hip_last_error(NULL). */
 #define EXON_HIP_FORMAT_VCF 1
 #define EXON_HIP_FORMAT_BAM 2
@@ -447,7 +456,8 @@ int exon_hip_stream_close(exon_hip_stream* s);
 #define EXON_HIP_FORMAT_SAM 5 /* text SAM: same columns as BAM */
 #define EXON_HIP_FORMAT_BCF 6 /* BCF2: same columns as VCF */
 #define EXON_HIP_FORMAT_CRAM 7 /* CRAM 3.0 (raw / gzip / bzip2 / lzma / rANS 4x8 blocks), host decoder: same columns as BAM */
-#define EXON_HIP_FORMAT_GFF 8 /* GFF3 text (additive; the ABI stays 5): columns above; GTF and BED are not read */
+#define EXON_HIP_FORMAT_GFF 8 /* GFF3 text (additive; the ABI stays 5): columns above; GTF is a format of its own, BED is not read */
+#define EXON_HIP_FORMAT_GTF 9 /* GTF text (additive; the ABI stays 5): columns above */
 #define EXON_HIP_COMPRESSION_AUTO 0 /* sniff the gzip/BGZF magic */
 #define EXON_HIP_COMPRESSION_NONE 1
 #define EXON_HIP_COMPRESSION_GZIP 2
@@ -467,7 +477,7 @@ typedef struct exon_hip_scan_options {
                              INFO '.' makes all of them NULL (the struct itself is NULL in the reference) */
   const char* region;     /* pushed-down vcf_region_filter / bam_region_filter ("chr1:1-100"), NULL = none */
   int32_t use_index;      /* with `region`: plan BGZF chunks from <path>.tbi / <path>.bai (INDEXED_VCF / INDEXED_BAM / INDEXED_GFF) */
-  int32_t gpu_parse;      /* VCF, BCF, FASTQ, BAM, SAM, GFF: exon_hip_stream_consume_scan ships the file's bytes to HBM and decodes
+  int32_t gpu_parse;      /* VCF, BCF, FASTQ, BAM, SAM, GFF, GTF: exon_hip_stream_consume_scan ships the file's bytes to HBM and decodes
                              them on the GPU (exon_hip_bgzf_inflate, exon_hip_vcf_parser_* / exon_hip_fastq_parser_* /
                              exon_hip_bam_parser_* ...).  exon_hip_scan_next on such a scan needs exon_hip_scan_bind_ctx first
                              (batches then come out of the same GPU pipeline); without a bound ctx it returns ESTATE */
@@ -485,7 +495,8 @@ typedef struct exon_hip_scan_options {
                              items, never NULL: eager_array_builder.rs:112-134); SAM: the BAM columns from the line's fields
                              (exon-sam/src/array_builder.rs:101-185); both from the host readers and from the GPU pipeline.
                              GFF: attributes Map<Utf8, List<Utf8>> (exon-gff/src/array_builder.rs:141-165), bit 8 = the column's
-                             index in the reference's schema; from the host reader and from the GPU pipeline */
+                             index in the reference's schema; from the host reader and from the GPU pipeline.
+                             GTF: attributes Map<Utf8, Utf8> (exon-gtf/src/array_builder.rs:82-87), the same bit */
 } exon_hip_scan_options;
 #define EXON_HIP_PROJECT_VCF_ID 1ull
 #define EXON_HIP_PROJECT_VCF_REF 2ull
@@ -497,12 +508,13 @@ typedef struct exon_hip_scan_options {
 #define EXON_HIP_PROJECT_BAM_SEQUENCE 4ull
 #define EXON_HIP_PROJECT_BAM_QUALITY_SCORES 8ull
 #define EXON_HIP_PROJECT_GFF_ATTRIBUTES 256ull /* (additive; the ABI stays 5) bit 8: `attributes` is column 8 of the reference's schema */
+#define EXON_HIP_PROJECT_GTF_ATTRIBUTES 256ull /* (additive) GTF's `attributes` is column 8 of the reference's schema too */
 
 int exon_hip_scan_open(const char* path, const exon_hip_scan_options* options, exon_hip_scan** out);
 int exon_hip_scan_schema(exon_hip_scan* scan, struct ArrowSchema* out);
 /* 0 = a batch was written to *out (caller releases or moves it); 1 = end of stream; <0 = error */
 int exon_hip_scan_next(exon_hip_scan* scan, struct ArrowArray* out);
-/* dictionary of a dict-encoded column (VCF 0/3, BAM 2, GFF 0/1/2/6/7): current size, and id of `name` (interned if new) */
+/* dictionary of a dict-encoded column (VCF 0/3, BAM 2, GFF and GTF 0/1/2/6/7): current size, and id of `name` (interned if new) */
 int exon_hip_scan_dictionary_size(exon_hip_scan* scan, int32_t column, int32_t* size);
 int exon_hip_scan_dictionary_intern(exon_hip_scan* scan, int32_t column, const char* name, int32_t* id);
 int exon_hip_scan_dictionary_value(exon_hip_scan* scan, int32_t column, int32_t id, const char** name);
@@ -752,6 +764,25 @@ typedef struct exon_hip_gff_attributes {
 } exon_hip_gff_attributes;
 int exon_hip_gff_parser_want_attributes(exon_hip_gff_parser* parser, int32_t on);
 int exon_hip_gff_parser_attributes(exon_hip_gff_parser* parser, void* stream, exon_hip_gff_attributes* out);
+/* GTF on the same parser (additive; the ABI stays 5).  exon_hip_gff_parser_set_dialect(parser, EXON_HIP_FORMAT_GTF) before a
+ * parse call: the line rules of exon_amd/csrc/host/gtf.h (a '?' strand makes the row undecided; the eighth column is the frame)
+ * hold from then on; EXON_HIP_FORMAT_GFF switches back, any other value is EXON_HIP_EINVAL.
+ * exon_hip_gff_parser_gtf_attributes builds the slab's `attributes` column, Map<Utf8, Utf8>, by gtf.h's ATTRIBUTE RULES -- rows ->
+ * entries (map_offsets), entries -> key bytes (key_offsets) and -> value bytes (value_offsets); keys and values are spans of the
+ * text, quotes dropped.  Same protocol as exon_hip_gff_parser_attributes (want_attributes, parse, then this); on a parser of
+ * the GFF dialect it is EXON_HIP_ESTATE, as exon_hip_gff_parser_attributes is on one of the GTF dialect.  n_undecided != 0 (a
+ * byte >= 0x80; a missing closing quote; a key without a value; an empty piece; bytes other than spaces behind a closing
+ * quote): nothing was built, the host reader decides. */
+typedef struct exon_hip_gtf_attributes {
+  int64_t n_entries, n_key_bytes, n_value_bytes, n_undecided;
+  const int32_t* map_offsets;   /* [n_rows + 1] */
+  const int32_t* key_offsets;   /* [n_entries + 1] */
+  const uint8_t* key_values;    /* [n_key_bytes] */
+  const int32_t* value_offsets; /* [n_entries + 1] */
+  const uint8_t* value_values;  /* [n_value_bytes] */
+} exon_hip_gtf_attributes;
+int exon_hip_gff_parser_set_dialect(exon_hip_gff_parser* parser, int32_t format);
+int exon_hip_gff_parser_gtf_attributes(exon_hip_gff_parser* parser, void* stream, exon_hip_gtf_attributes* out);
 int exon_hip_gff_parser_destroy(exon_hip_gff_parser* parser);
 
 /* ---- BCF2 record splitting + field extraction on the GPU (inflated BCF bytes in HBM -> the VCF device layout) ----

@@ -35,6 +35,8 @@ pub const EXON_HIP_FORMAT_SAM: i32 = 5;
 pub const EXON_HIP_FORMAT_BCF: i32 = 6;
 pub const EXON_HIP_FORMAT_CRAM: i32 = 7;
 pub const EXON_HIP_FORMAT_GFF: i32 = 8;
+pub const EXON_HIP_FORMAT_GTF: i32 = 9;
+pub const EXON_HIP_PROJECT_GTF_ATTRIBUTES: u64 = 256; // exon_hip_scan_options.projection: GTF column 8, Map<Utf8, Utf8>
 pub const EXON_HIP_PROJECT_GFF_ATTRIBUTES: u64 = 256; // exon_hip_scan_options.projection: GFF column 8, Map<Utf8, List<Utf8>>
 pub const EXON_HIP_COMPRESSION_AUTO: i32 = 0;
 pub const EXON_HIP_MAX_GROUPS: i32 = 4096;

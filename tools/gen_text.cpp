@@ -4,6 +4,7 @@
 // `gen_text bam <reads> <out> [read_len=100]` an uncompressed BAM stream (bgzip it to get a .bam; config 3 end to end).
 // `gen_text gff <rows> <out>` a GFF3 table sorted by (seqname, start), so that bgzip + a tabix index (GFF preset) serve it;
 // `gen_text gff <rows> <out> attrs` the same rows with rich ninth fields (every shape of the attribute rules, ASCII only).
+// `gen_text gtf <rows> <out> [attrs]` an Ensembl-like GTF table with the same (seqname, start) layout; attrs: rich ninth fields.
 // build: g++ -O2 -std=c++17 tools/gen_text.cpp -o tools/bin/gen_text      run: gen_text vcf <rows> <out.vcf>
 #include <cstdint>
 #include <cstdio>
@@ -14,7 +15,7 @@ static inline uint64_t mix64(uint64_t z) { z = (z ^ (z >> 30)) * 0xBF58476D1CE4E
 static inline uint64_t rnd(uint64_t seed, uint64_t col, uint64_t i) { return mix64(seed + col * 0xD1B54A32D192ED03ULL + (i + 1) * 0x9E3779B97F4A7C15ULL); }
 static inline uint32_t pct_thr(int p) { return (uint32_t)((((uint64_t)p) << 32) / 100); }
 int main(int argc, char** argv) {
-  if (argc < 4) { fprintf(stderr, "usage: gen_text vcf|bcf|fastq|bam|sam|gff <rows> <out> [read_len | attrs] [ragged]\n"); return 2; }
+  if (argc < 4) { fprintf(stderr, "usage: gen_text vcf|bcf|fastq|bam|sam|gff|gtf <rows> <out> [read_len | attrs] [ragged]\n"); return 2; }
   const int64_t n = (int64_t)atof(argv[2]);
   FILE* f = fopen(argv[3], "wb");
   if (!f) return 1;
@@ -117,6 +118,77 @@ int main(int argc, char** argv) {
       }
       fprintf(f, "%s\t%s\t%s\t%lld\t%lld\t%s\t%c\t%c\tID=f%lld;Name=n%u\n", name, SOURCES[(b >> 2) % 3], TYPES[(b >> 8) % 10], (long long)start, (long long)end,
               score, STRAND[(b >> 16) & 3], PHASE[(b >> 18) & 3], (long long)i, (unsigned)(b >> 40) & 0xFFFFu);
+    }
+    fclose(f);
+    return 0;
+  }
+  if (!strcmp(argv[1], "gtf")) {
+    // the GFF mode's rows as GTF: 24 seqnames in contiguous runs, starts ascending inside a run, Ensembl's sources and feature types,
+    // scores present and '.', strands + - . (never '?'), every frame spelling; "#!" header lines, and a '#' comment every 1000 rows so
+    // that most slabs are ranked.  The default ninth field is Ensembl's (gene_id, transcript_id, exon_number, gene_name, ..).
+    static const char* TYPES[8] = {"gene", "transcript", "exon", "CDS", "start_codon", "stop_codon", "five_prime_utr", "three_prime_utr"};
+    static const char* SOURCES[3] = {"ensembl", "havana", "ensembl_havana"};
+    static const char* BIOTYPES[4] = {"protein_coding", "lncRNA", "processed_pseudogene", "miRNA"};
+    static const char STRAND[4] = {'+', '-', '.', '+'}, FRAME[4] = {'.', '0', '1', '2'};
+    const int NSEQ = 24;
+    const bool attrs = argc > 4 && !strcmp(argv[4], "attrs");
+    // attrs: 0-12 entries a row; empty fields; the last entry with or without its ';' and spaces behind it; quoted values with ';'
+    // and spaces inside, empty ones, of 1, 7, 8, 9 and (now and then) up to 300 bytes; bare numeric values, with spaces in front of
+    // the ';'; several spaces between key and value and behind a ';'; `tag` repeated inside a row
+    static const char* KEYS[8] = {"gene_id", "transcript_id", "gene_name", "gene_biotype", "exon_id", "transcript_support_level", "ccdsid", "note"};
+    static const char* QUOTED[4] = {"a;b", "basic; CCDS ;x", "", "Ensembl canonical"};
+    auto attributes = [&](int64_t i, std::string* out) {
+      out->clear();
+      const uint64_t r = rnd(11, 0, (uint64_t)i);
+      const int n_entries = (int)((r >> 4) % 13);
+      if ((r & 15) == 0) return;
+      for (int j = 0; j < n_entries; ++j) {
+        const uint64_t q = rnd(11, 1, (uint64_t)(i * 16 + j));
+        const int kind = (int)(q & 15);
+        if (j) *out += (q >> 50) % 5 == 0 ? ";  " : "; ";
+        *out += kind >= 13 ? "tag" : KEYS[(q >> 4) & 7];
+        *out += (q >> 44) % 9 == 0 ? "   " : " ";
+        if (kind < 3) {  // bare numbers
+          *out += std::to_string((q >> 8) % 100000);
+          if (kind == 2) *out += " ";
+        } else {
+          out->push_back('"');
+          const int fixed[4] = {1, 7, 8, 9};
+          int len = 0;
+          if (kind < 7) len = fixed[kind - 3];
+          else if (kind < 10) *out += QUOTED[(q >> 8) & 3];
+          else if (kind == 10) len = (int)((q >> 8) % 301);
+          else len = 4 + (int)((q >> 8) % 12);
+          for (int k = 0; k < len; ++k) out->push_back("abcdefghijklmnopqrstuvwxyz0123456789 _-.:;|"[((q >> 20) + (uint64_t)k * 7) % 43]);
+          out->push_back('"');
+        }
+      }
+      if (n_entries && (r & 32)) *out += (r & 64) ? "; " : ";";
+    };
+    std::string field9;
+    fputs("#!genome-build GRCh38.p14\n#!genome-version GRCh38\n", f);
+    for (int64_t i = 0; i < n; ++i) {
+      const uint64_t a = rnd(10, 0, (uint64_t)i), b = rnd(10, 1, (uint64_t)i);
+      const int seq = (int)((i * NSEQ) / n);
+      const int64_t first = ((int64_t)seq * n + NSEQ - 1) / NSEQ;  // the first row of this seqname's run
+      const int64_t start = 1 + (i - first) * 100 + (int64_t)(a % 100), end = start + (int64_t)((a >> 8) % 5000);
+      char name[16], score[16];
+      if (seq < 22) snprintf(name, sizeof name, "chr%d", seq + 1);
+      else strcpy(name, seq == 22 ? "chrX" : "chrY");
+      const uint32_t k = (uint32_t)((a >> 24) % 10000u);
+      if ((b & 3) != 0) strcpy(score, ".");
+      else snprintf(score, sizeof score, "%u.%u", k / 10, k % 10);
+      if (i % 1000 == 500) fprintf(f, "# rows from %lld on\n", (long long)i);
+      fprintf(f, "%s\t%s\t%s\t%lld\t%lld\t%s\t%c\t%c\t", name, SOURCES[(b >> 2) % 3], TYPES[(b >> 8) % 8], (long long)start, (long long)end, score,
+              STRAND[(b >> 16) & 3], FRAME[(b >> 18) & 3]);
+      if (attrs) {
+        attributes(i, &field9);
+        fwrite(field9.data(), 1, field9.size(), f);
+        fputc('\n', f);
+        continue;
+      }
+      fprintf(f, "gene_id \"ENSG%011lld\"; transcript_id \"ENST%011lld\"; exon_number %u; gene_name \"G%u\"; gene_biotype \"%s\"; tag \"basic\"; tag \"CCDS\";\n",
+              (long long)(i / 40), (long long)(i / 8), (unsigned)(i % 8) + 1, (unsigned)(b >> 40) & 0xFFFFu, BIOTYPES[(b >> 20) & 3]);
     }
     fclose(f);
     return 0;
