@@ -4,7 +4,8 @@
 // Reference semantics: BAMArrayBuilder::append (exon-bam/src/array_builder.rs:102-218) restricted to the columns of
 // the device layout -- flag = raw u16 bits as Int32 (:114-117), reference = refID (NULL if -1, :118-127), start =
 // pos + 1 (NULL if pos < 0), end = start + (sum of M/D/N/=/X lengths) - 1, mapping_quality NULL when 255 (:136-143);
-// record layout: SAM specification section 4.2.
+// record layout: SAM specification section 4.2.  Undecided (the host reader reports what is wrong): a CIGAR that does not fit in
+// block_size, a reference id beyond the header's (the reference indexes its name table with it, :118-122).
 //
 // Records are found by the parallel chain walk of chain_walk.h (64 KiB segments, guessed starts proven by induction);
 //   k_bam_extract  one thread per record: fixed fields, CIGAR walk for the reference length, columns + validity bits.
@@ -66,7 +67,7 @@ struct BamOut {
 
 __global__ __launch_bounds__(256) void k_bam_extract(const uint8_t* __restrict__ d, const SegInfo* __restrict__ seg,
                                                      const uint32_t* __restrict__ base, const uint32_t* __restrict__ rec_off, BamOut o,
-                                                     unsigned* __restrict__ scalars) {
+                                                     int32_t n_ref, unsigned* __restrict__ scalars) {
   const uint32_t s = blockIdx.x;
   if (scalars[1] != 0) return;  // the segmentation was not proven: nothing here can be trusted
   const uint32_t cnt = seg[s].count, row0 = base[s];
@@ -89,7 +90,7 @@ __global__ __launch_bounds__(256) void k_bam_extract(const uint8_t* __restrict__
     const int32_t ref = (int32_t)ld32(d + r + 4), pos = (int32_t)ld32(d + r + 8);
     const uint32_t l_name = d[r + 12], mapq = d[r + 13], n_cigar = ld16(d + r + 16), flag = ld16(d + r + 18);
     const uint32_t co = 32 + l_name;
-    const bool ok = co + 4 * n_cigar <= bs;  // else "corrupt BAM cigar" on the host
+    const bool ok = co + 4 * n_cigar <= bs && ref < n_ref;  // else "corrupt BAM cigar" / "BAM reference id out of range" on the host
     if (!ok) atomicAdd(&scalars[1], 1u);
     int64_t ref_len = 0;
     for (uint32_t c = 0; ok && c < n_cigar; ++c) {
@@ -179,7 +180,7 @@ int exon_hip_bam_parser_parse(exon_hip_bam_parser* p, void* stream, const uint8_
   zl.n = 3;
   zl.words = (uint32_t)(((size_t)n / 36 + 1 + 31) / 32 + 1);
   c.launch(s, d_data, n, BamFormat{p->n_ref}, zl);
-  hipLaunchKernelGGL(k_bam_extract, dim3(n_seg), dim3(256), 0, s, d_data, c.seg, c.base, c.rec_off, p->out, c.d_scalars);
+  hipLaunchKernelGGL(k_bam_extract, dim3(n_seg), dim3(256), 0, s, d_data, c.seg, c.base, c.rec_off, p->out, p->n_ref, c.d_scalars);
   if (int rc = c.read_back(ctx, s)) return rc;
   if (getenv("EXON_HIP_CHAIN_TRACE")) fprintf(stderr, "[exon-hip chain] %u segments, %u rows, plain proof %u\n", n_seg, c.h_scalars[0], c.h_scalars[3]);
   cols->n_rows = c.h_scalars[0];

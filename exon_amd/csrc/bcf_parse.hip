@@ -112,11 +112,18 @@ struct Cursor {
       if (*count < 0) bad = true;
     }
   }
+  // step over `count` items of `type`: the count is any typed int32 (0 .. 2^31 - 1), so the byte count is taken in 64 bits and
+  // compared with what the record has left (o <= end always) -- `o += count * size` in 32 bits wraps to 0 for 2^30 four-byte items
+  __device__ void advance(int type, int count) {
+    if (bad) return;
+    const uint64_t bytes = (uint64_t)(uint32_t)count * (uint64_t)type_size(type);
+    if (count < 0 || bytes > (uint64_t)(end - o)) { bad = true; return; }
+    o += (uint32_t)bytes;
+  }
   __device__ void skip_typed() {
     int t, c;
     typed_header(&t, &c);
-    o += (uint32_t)c * (uint32_t)type_size(t);
-    if (o > end) bad = true;
+    advance(t, c);
   }
 };
 
@@ -242,8 +249,7 @@ __global__ __launch_bounds__(256) void k_bcf_extract(const uint8_t* __restrict__
         }
       }
       if (c.bad) break;
-      c.o += (uint32_t)vc * (uint32_t)type_size(vt);
-      if (c.o > c.end) c.bad = true;
+      c.advance(vt, vc);
     }
     if (c.bad || undecided) {
       atomicAdd(&scalars[1], 1u);

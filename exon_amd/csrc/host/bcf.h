@@ -404,10 +404,13 @@ class BCFBatchReader : public BatchReader {
     const uint8_t d = b[(*o)++];
     *type = d & 0xF;
     *count = d >> 4;
-    if (*count == 15) {  // the real count follows as a typed integer
-      int ct, cc;
-      typed_header(b, o, end, &ct, &cc);
+    if (*count == 15) {  // the real count follows as a typed integer: its descriptor's type says how wide (as in bcf_parse.hip)
+      if (*o >= end) throw std::runtime_error("corrupt BCF typed value");
+      const int ct = b[(*o)++] & 0xF;
       *count = (int)read_int(b, o, end, ct);
+      // a length cannot be negative (VCF 4.x specification 6.3.3: the count is "the number of elements"); taken as it is, it would
+      // step the offset backwards below and pass every bound
+      if (*count < 0) throw std::runtime_error("corrupt BCF typed value: negative count");
     }
   }
   static void skip_typed(const std::vector<uint8_t>& b, size_t* o, size_t end) {

@@ -1016,6 +1016,9 @@ class BAMBatchReader : public BatchReader {
       const uint8_t l_read_name = rec[8], mapq = rec[9];
       memcpy(&n_cigar, &rec[12], 2);
       memcpy(&flag, &rec[14], 2);
+      // a reference beyond the header's has no name: the reference indexes its name table with it and fails
+      // (exon-bam/src/array_builder.rs:118-122); as a row it would be a dictionary index outside the dictionary
+      if (ref_id >= (int32_t)ref_names.size()) throw std::runtime_error("BAM reference id out of range");
       // reference length = sum of M/D/N/=/X op lengths (ops 0,2,3,7,8)
       int64_t ref_len = 0;
       const size_t co = 32 + l_read_name;

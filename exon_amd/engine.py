@@ -742,6 +742,71 @@ class BAMParser:
             self.h = None
 
 
+class BCFParser:
+    """BCF record splitting + typed-value walk on the GPU (exon_hip_bcf_parser_*): inflated bytes in HBM -> the VCF device layout.
+    info_keys: header-string indexes of the INFO fields to extract, info_kinds: one letter each ('f', 'i', 'b', 'F', 'I')."""
+
+    def __init__(self, ctx, n_contigs, n_strings, n_samples=0, info_keys=(), info_kinds="", max_slab_bytes=64 << 20):
+        self.ctx = ctx
+        h = C.c_void_p()
+        ctx._check(ctx.lib.exon_hip_bcf_parser_create(ctx.h, n_contigs, n_strings, n_samples, -1, max_slab_bytes, C.byref(h)))
+        self.h = h
+        if info_keys:
+            ctx._check(ctx.lib.exon_hip_bcf_parser_set_info_keys(self.h, (C.c_int32 * len(info_keys))(*info_keys),
+                                                                 info_kinds.encode(), len(info_keys)))
+        self.cap_items = max_slab_bytes + 1  # items a list key's buffers hold (exon_hip_bcf_parser_set_info_keys)
+
+    def parse_host(self, data):
+        """Test helper: copy `data` (record bytes, starting at a record boundary) to HBM, split + extract, bring the columns back
+        as numpy arrays (no rows of an undecided slab).  "filters": the FILTER index list behind every filter id; "infos": as
+        VCFParser.parse_host gives them."""
+        buf = np.frombuffer(data, np.uint8)
+        d = self.ctx.to_device(np.concatenate([buf, np.zeros(64, np.uint8)]))
+        cols = L.VCFColumns()
+        self.ctx._check(self.ctx.lib.exon_hip_bcf_parser_parse(self.h, None, d.ptr, len(buf), C.byref(cols)))
+        n = cols.n_rows if cols.n_undecided == 0 else 0
+        nb = (n + 7) // 8
+
+        def get(ptr, dtype, count):
+            out = np.empty(count, dtype)
+            if count:
+                self.ctx._check(self.ctx.lib.exon_hip_memcpy_d2h(self.ctx.h, _np_ptr(out), ptr, out.nbytes, None))
+            return out
+
+        res = {"n_rows": cols.n_rows, "n_undecided": cols.n_undecided, "consumed_bytes": cols.consumed_bytes,
+               "chrom_id": get(cols.chrom_id, np.int32, n), "pos": get(cols.pos, np.int64, n),
+               "pos_valid": get(cols.pos_valid, np.uint8, nb), "qual": get(cols.qual, np.float32, n),
+               "qual_valid": get(cols.qual_valid, np.uint8, nb), "filter_id": get(cols.filter_id, np.int32, n),
+               "filters": [], "infos": []}
+        if cols.n_undecided == 0:
+            res["filters"] = self.filters()
+        for q in range(cols.n_info):
+            kind = cols.info_kinds[q:q + 1].decode()
+            k = {"kind": kind, "valid": get(cols.infos_valid[q], np.uint8, nb)}
+            if kind in "FI":
+                k["offsets"] = get(cols.list_offsets[q], np.int32, n + 1 if n else 0)
+                items = min(int(k["offsets"][-1]) if n else 0, self.cap_items)
+                k["values"] = get(cols.infos[q], np.float32, items)
+                k["item_valid"] = get(cols.list_item_valid[q], np.uint8, (items + 7) // 8)
+            elif kind != "b":
+                k["values"] = get(cols.infos[q], np.float32, n)
+            res["infos"].append(k)
+        return res
+
+    def filters(self):
+        """the FILTER lists seen so far, in id order: tuples of header-string indexes"""
+        n = C.c_int32()
+        self.ctx._check(self.ctx.lib.exon_hip_bcf_parser_filters(self.h, None, None, 0, C.byref(n)))
+        lists, counts = (C.c_int32 * (8 * max(n.value, 1)))(), (C.c_int32 * max(n.value, 1))()
+        self.ctx._check(self.ctx.lib.exon_hip_bcf_parser_filters(self.h, lists, counts, n.value, C.byref(n)))
+        return [tuple(lists[8 * i:8 * i + counts[i]]) for i in range(n.value)]
+
+    def close(self):
+        if self.h:
+            self.ctx.lib.exon_hip_bcf_parser_destroy(self.h)
+            self.h = None
+
+
 class FASTQParser:
     """FASTQ record splitting on the GPU (exon_hip_fastq_parser_*): text slab in HBM -> per-read views into it."""
 

@@ -127,3 +127,61 @@ def test_oracle_sam_decoder_on_the_reference_fixture():
     # and the product's host SAM reader agrees
     b = rows_of(os.path.join(FX, "sam", "test.sam"), "sam")[0]
     assert [b.field(i).to_pylist()[0] for i in range(5)] == [99, 0, "ref1", 1, 10]
+
+
+def _bcf_scan(path, **kw):
+    import bcf_typed_walk_cases as T
+    return [r for b in rows_of(str(path), "bcf", info_field=T.INFO_FIELD, **kw) for r in b.to_pylist()]
+
+
+def test_bcf_host_reader_walks_typed_values_like_the_plain_statement(tmp_path):
+    """The typed-walk table (bcf_typed_walk_cases.py) through the host BCF reader, each case between two good records: rows the
+    plain statement of the format (record_expect.py, unbounded integers) decodes are equal, field by field; what it refuses is
+    an error -- a negative extended count (VCF specification 6.3.3: a length) among them, which used to step the reader's
+    offset backwards in silence.  More than 8 FILTER entries are the device layout's limit, not the reader's."""
+    import bcf_typed_walk_cases as T
+    import record_expect as X
+    import vcf_bcf_writer as W
+    contigs, strings = ["1", "2"], sorted(W.string_index([]), key=W.string_index([]).get)
+    names = T.INFO_FIELD.split(",")
+    assert len(strings) == T.N_STRINGS
+
+    def want(rec):
+        row = X.bcf_row(rec, T.N_CONTIGS, T.N_STRINGS, T.KEYS, max_filters=None)
+        return row if isinstance(row, X.Reject) else X.bcf_scan_row(row, contigs, strings, T.KEYS, names)
+
+    wrong = []
+    for n, (name, rec, label) in enumerate(T.cases()):
+        recs = [T.good(n + 1), rec, T.good(n + 2)]
+        expect = [want(r) for r in recs]
+        assert isinstance(expect[1], X.Reject) == (label == T.REJECT), name  # the label, written down with the case, and the statement agree
+        path = tmp_path / "c.bcf"
+        path.write_bytes(X.bcf_file(b"".join(recs)))
+        try:
+            got = _bcf_scan(path)
+        except exon_amd.ExonHipError as e:
+            got = e
+        if label == T.REJECT:
+            if not isinstance(got, exon_amd.ExonHipError):
+                wrong.append((name, "no error", got[1] if len(got) > 1 else got))
+        elif got != expect:
+            wrong.append((name, got, expect))
+    assert not wrong, wrong
+
+
+def test_bam_reference_id_beyond_the_header_is_an_error(tmp_path):
+    """A record whose reference id has no @SQ line behind it: the reference indexes its name table with the id and fails
+    (exon-bam/src/array_builder.rs:118-122); the host reader used to hand out a dictionary index outside the dictionary.  The last
+    reference of the header, -1 and (NULL like -1, as before) -7 are rows."""
+    import record_expect as X
+    recs = [X.bam_record(ref=r, cigar=[(7 << 4) | 0], seq=b"\x11" * 4, qual=b"\x20" * 7) for r in (2, -1, -7, 0)]
+    p = tmp_path / "ok.bam"
+    p.write_bytes(X.bam_file(b"".join(recs), 3))
+    rows = [r for b in rows_of(str(p), "bam") for r in b.to_pylist()]
+    assert [r["reference"] for r in rows] == ["c2", None, None, "c0"]
+    assert [X.bam_row(r, 3)["ref"] for r in recs] == [2, None, None, 0]
+    p = tmp_path / "bad.bam"
+    p.write_bytes(X.bam_file(b"".join(recs + [X.bam_record(ref=3)]), 3))
+    assert isinstance(X.bam_row(X.bam_record(ref=3), 3), X.Reject)
+    with pytest.raises(exon_amd.ExonHipError, match="reference id"):
+        rows_of(str(p), "bam")

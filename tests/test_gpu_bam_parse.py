@@ -11,6 +11,7 @@ import pytest
 
 import exon_amd
 from oracle_expect import bam_columns, k3_expected, k6_expected
+from record_expect import bam_record
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -195,9 +196,7 @@ def _raw_bam_records(lengths, rng, n_ref=25):
     for i, ln in enumerate(lengths):
         name = b"r%d\0" % i
         ref, pos = int(rng.integers(0, n_ref)), int(rng.integers(0, 1 << 28))
-        body = struct.pack("<iiBBHHHiiii", ref, pos, len(name), int(rng.integers(0, 61)), 4680, 1, 0, ln, -1, -1, 0)
-        body += name + struct.pack("<I", (ln << 4) | 0) + bytes((ln + 1) // 2) + bytes(ln)
-        out.append(struct.pack("<i", len(body)) + body)
+        out.append(bam_record(ref=ref, pos=pos, name=name, mapq=int(rng.integers(0, 61)), cigar=[(ln << 4) | 0], seq=bytes((ln + 1) // 2), qual=bytes(ln)))
     return out
 
 

@@ -151,8 +151,13 @@ def _typed_ints(vals, width=None, pad=0, count_width=None):
     return _desc(len(vals) + pad, t, count_width) + b"".join(struct.pack("<" + fmt, miss if v is None else v) for v in vals) + struct.pack("<" + fmt, miss + 1) * pad
 
 
-def _desc(n, t, count_width=None):
-    if n < 15 and count_width is None:
+def _desc(n, t, count_width=None, count_bytes=None):
+    """descriptor byte(s) of a typed vector of n items of type t.  Opt-in: `count_width` forces the extended form with the count
+    in that integer width (n may then be anything the width holds, negative included); `count_bytes` are written behind the
+    0xF? byte as they are, in place of the typed count (a count whose own descriptor is no integer's, a cut-off count)."""
+    if count_bytes is not None:
+        return bytes([0xF0 | t]) + count_bytes
+    if 0 <= n < 15 and count_width is None:
         return bytes([(n << 4) | t])
     return bytes([0xF0 | t]) + _typed_ints([n], count_width)
 
