@@ -70,6 +70,7 @@ enum : uint32_t {
   GZ_BAD_HEADER = 8,     // member header: magic / method / reserved flags
   GZ_MEMBER_OVERFLOW = 9,
   GZ_TRUNCATED = 10,
+  GZ_FAR_DISTANCE = 11,  // a match that reaches in front of its member's first byte (zlib: "invalid distance too far back")
 };
 enum : uint32_t { START_SEARCH = 0, START_BLOCK = 1, START_MEMBER = 2 };
 enum : uint32_t { F_EXHAUSTED = 1, F_STREAM_END = 2, F_AT_MEMBER = 4 /* end_bit is a member header (the input ended inside it) */ };
@@ -80,12 +81,16 @@ struct GzTask {        // one wavefront's work
   uint32_t kind;
   uint32_t region;     // which region of the symbol scratch / which result record
 };
-struct GzChunk {         // 40 bytes
+struct GzChunk {         // 48 bytes
   uint64_t start_bit;    // where the accepted decode began
   uint64_t end_bit;      // the block boundary it stopped at
   uint32_t n_out;        // symbols
   uint32_t status, flags, n_members;
   uint32_t ticks, slot;  // diagnostics (EXON_HIP_GZ_TRACE): 100 MHz ticks this wavefront spent on the task, when it started
+  // how far in front of the chunk's first symbol the matches of the member it began INSIDE reach (0: not at all).  A member that
+  // begins inside the chunk is judged by the wavefront itself (GZ_FAR_DISTANCE); for this one only the host knows how many of the
+  // member's bytes lie in front of the chunk.
+  uint32_t reach, pad;
 };
 struct GzMember {        // a member trailer crossed by a chunk: `out_off` symbols of the chunk belong to the member that ends
   uint32_t out_off, crc, isize, pad;
@@ -369,7 +374,7 @@ __device__ __forceinline__ void copy_match(Out& o, uint32_t len, uint32_t dist) 
 
 struct ChainResult {
   uint64_t end_bit;
-  uint32_t n_out, status, flags, n_members;
+  uint32_t n_out, status, flags, n_members, reach;
 };
 
 // gzip member header at a byte boundary (RFC 1952 section 2.3).  0 ok, 1 not a gzip header, 2 ran out of input
@@ -429,9 +434,15 @@ __device__ __noinline__ ChainResult decode_chain(const uint32_t* comp, uint64_t 
   r.status = GZ_OK;
   r.flags = 0;
   r.n_members = 0;
+  r.reach = 0;
   Bits br;
   br.init(comp, start_bit);
   Out o{sym, cap, 0, 0};
+  // A member's window is its own output (zlib: "invalid distance too far back"): what lies in front of its first byte -- the member
+  // in front, or nothing at all at the head of the file -- is not a source.  member_lo = the chunk's symbol the member began at, when
+  // it began inside this chain; a chain that starts inside a member reports how far in front of itself it reached instead.
+  bool member_known = start_kind == START_MEMBER;
+  uint32_t member_lo = 0, reach = 0;
   if (start_kind == START_MEMBER) {
     const int h = uni(member_header(br, n_bits));
     if (h == 1) {
@@ -445,7 +456,7 @@ __device__ __noinline__ ChainResult decode_chain(const uint32_t* comp, uint64_t 
   }
   for (;;) {
     const uint64_t block_bit = br.pos();
-    const uint32_t block_pos = o.pos, block_members = r.n_members;
+    const uint32_t block_pos = o.pos, block_members = r.n_members, block_reach = reach;
     auto exhausted = [&]() {  // roll back to this block's start
       r.end_bit = block_bit;
       r.n_out = block_pos;
@@ -453,6 +464,7 @@ __device__ __noinline__ ChainResult decode_chain(const uint32_t* comp, uint64_t 
       r.flags |= F_EXHAUSTED;
       r.status = GZ_OK;
       o.pos = block_pos;
+      reach = block_reach;  // (what the padding behind the input decoded to has reached nowhere)
     };
     if (block_bit >= stop_bit) {
       r.end_bit = block_bit;
@@ -652,6 +664,13 @@ __device__ __noinline__ ChainResult decode_chain(const uint32_t* comp, uint64_t 
               break;
             }
             const uint32_t dist = (de >> 16) + br.take((int)((de >> 4) & 15u));
+            if (__builtin_expect(dist > o.pos - member_lo, 0)) {  // in front of the member (known), or of the chunk
+              if (member_known) {
+                r.status = GZ_FAR_DISTANCE;
+                break;
+              }
+              reach = max(reach, dist - o.pos);
+            }
             copy_match(o, len, dist);  // (a special case for short matches whose sources all lie in the ring measured SLOWER on VCF text: profiles/r6_gz_loop_ab.log)
           }
         }
@@ -715,9 +734,12 @@ __device__ __noinline__ ChainResult decode_chain(const uint32_t* comp, uint64_t 
         exhausted();
         break;
       }
+      member_known = true;
+      member_lo = o.pos;
     }
   }
 chain_done:
+  r.reach = reach;
   if (r.status == GZ_OK) {
     o.pos = r.n_out;
     if (!drain_rest(o)) r.status = GZ_SYM_OVERFLOW;
@@ -744,6 +766,7 @@ __global__ __launch_bounds__(64) void k_gz_decode(const uint32_t* __restrict__ c
     r.n_out = 0;
     r.flags = 0;
     r.n_members = 0;
+    r.reach = 0;
     const uint64_t lo = uni64(st.bit);
     const uint64_t hi = min(stop_bit, n_bits);
     bool done = false;
@@ -798,6 +821,8 @@ __global__ __launch_bounds__(64) void k_gz_decode(const uint32_t* __restrict__ c
     out.status = r.status;
     out.flags = r.flags;
     out.n_members = r.n_members;
+    out.reach = r.reach;
+    out.pad = 0;
     out.ticks = (uint32_t)(wall_clock64() - t_begin);
     out.slot = (uint32_t)t_begin;
     res[c] = out;
@@ -1008,6 +1033,7 @@ const char* gz_status_name(uint32_t s) {
     case GZ_BAD_HEADER: return "not a gzip member header";
     case GZ_MEMBER_OVERFLOW: return "too many members in one chunk";
     case GZ_TRUNCATED: return "truncated gzip stream";
+    case GZ_FAR_DISTANCE: return "invalid distance too far back";
   }
   return "?";
 }
@@ -1047,6 +1073,7 @@ struct exon_hip_gzip_stream {
   bool ended = false;           // the last member's trailer was the end of the input
   uint32_t member_raw = 0;      // running CRC register of the member being decoded (zero initial value, no xors)
   uint64_t member_len = 0;
+  uint64_t member_out = 0;      // bytes of the member being decoded that earlier chunks and calls produced: all a match may reach into
   bool verify_crc = true;
   // statistics
   exon_hip_gzip_stats stats{};
@@ -1343,6 +1370,18 @@ int exon_hip_gzip_stream_decode(exon_hip_gzip_stream* s, void* stream, const uin
       off += r.n_out;
       total_members += (int)r.n_members;
     }
+    // A chunk that began inside a member could not tell how much of the member lies in front of it: the chain can.  (A member's
+    // window is its own output; the one in front -- or the zeros in front of the file -- would be copied without this.)
+    if (total_members) {
+      HIP_TRY(ctx, hipMemcpyAsync(s->h_members, s->d_members, (size_t)n_records * MAX_MEMBER_ENDS * sizeof(GzMember), hipMemcpyDeviceToHost, hs));
+      HIP_TRY(ctx, hipStreamSynchronize(hs));
+    }
+    uint64_t member_out = s->member_out;
+    for (size_t a = 0; a < n_acc; ++a) {
+      const GzChunk& r = s->h_res[chain[a]];
+      if ((uint64_t)r.reach > member_out) return fail(ctx, EXON_HIP_EINVAL, "gzip stream: %s", gz_status_name(GZ_FAR_DISTANCE));
+      member_out = r.n_members ? (uint64_t)r.n_out - s->h_members[(size_t)chain[a] * MAX_MEMBER_ENDS + r.n_members - 1].out_off : member_out + r.n_out;
+    }
     HIP_TRY(ctx, hipMemcpyAsync(s->d_acc, s->h_acc, n_acc * sizeof(Accepted), hipMemcpyHostToDevice, hs));
     const int n_groups = (int)((n_acc + GROUP - 1) / GROUP);
     uint8_t* win_in = s->d_win[s->win_k];
@@ -1360,9 +1399,7 @@ int exon_hip_gzip_stream_decode(exon_hip_gzip_stream* s, void* stream, const uin
     size_t n_pieces = 0;
     std::vector<std::pair<uint64_t, const GzMember*>> ends;  // (absolute output offset of a member end, its trailer)
     if (s->verify_crc) {
-      if (total_members) {
-        HIP_TRY(ctx, hipMemcpyAsync(s->h_members, s->d_members, (size_t)n_records * MAX_MEMBER_ENDS * sizeof(GzMember), hipMemcpyDeviceToHost, hs));
-        HIP_TRY(ctx, hipStreamSynchronize(hs));
+      if (total_members) {  // (the trailers were fetched for the distance check above)
         for (size_t a = 0; a < n_acc; ++a) {
           const GzChunk& r = s->h_res[chain[a]];
           for (uint32_t m = 0; m < r.n_members; ++m) {
@@ -1418,6 +1455,7 @@ int exon_hip_gzip_stream_decode(exon_hip_gzip_stream* s, void* stream, const uin
     *produced = (int64_t)off;
     s->start_bit = (uint32_t)(end_bit & 7);
     s->start_kind = (last.flags & F_AT_MEMBER) ? START_MEMBER : START_BLOCK;
+    s->member_out = member_out;
     s->stats.out_bytes += off;
     s->stats.comp_bytes += (uint64_t)*consumed;
     ++s->stats.calls;

@@ -89,14 +89,15 @@ inline void bgzf_block_info(const uint8_t* p, size_t avail, BgzfBlockInfo* info,
 // Inflates one block into out[0, isize) with a raw-deflate z_stream the caller keeps (inflateInit2(z, -15)); checks
 // that the stream ends exactly at ISIZE and that the CRC-32 matches.
 inline void inflate_bgzf_block(z_stream* z, const uint8_t* blk, const BgzfBlockInfo& info, uint8_t* out, const std::string& what) {
-  if (info.isize) {
-    if (inflateReset(z) != Z_OK) throw std::runtime_error("inflateReset failed: " + what);
-    z->next_in = const_cast<uint8_t*>(blk + info.data);
-    z->avail_in = (uInt)info.data_len;
-    z->next_out = out;
-    z->avail_out = info.isize;
-    if (inflate(z, Z_FINISH) != Z_STREAM_END || z->avail_out != 0) throw std::runtime_error("BGZF inflate error: " + what);
-  }
+  // (a member that claims no output is inflated too: its DEFLATE data must be a stream that ends without a byte, as the device
+  //  inflate demands -- the end-of-file marker is one; zlib wants an output pointer even for nothing)
+  uint8_t none = 0;
+  if (inflateReset(z) != Z_OK) throw std::runtime_error("inflateReset failed: " + what);
+  z->next_in = const_cast<uint8_t*>(blk + info.data);
+  z->avail_in = (uInt)info.data_len;
+  z->next_out = info.isize ? out : &none;
+  z->avail_out = info.isize;
+  if (inflate(z, Z_FINISH) != Z_STREAM_END || z->avail_out != 0) throw std::runtime_error("BGZF inflate error: " + what);
   if ((uint32_t)crc32(crc32(0L, Z_NULL, 0), out, info.isize) != info.crc32) throw std::runtime_error("BGZF CRC-32 mismatch: " + what);
 }
 

@@ -333,7 +333,11 @@ __device__ __noinline__ int build_code_impl(int which, int lens_off, int n) {
       total += rq;
     }
   }
-  if (left > 0 && total > 1) return 0;  // incomplete (RFC 1951 allows it only for a single distance code)
+  // incomplete: zlib's rule (inflate_table: left > 0 && (type == CODES || max != 1)), which the host readers that take over apply.
+  // A literal/length or distance code may be incomplete only as ONE code of length 1 -- the one case that leaves 2^14 of the 2^15
+  // code points -- and a code-length code never; a code without any symbol is legal for distances alone (any match is then an
+  // invalid code).  (No "longest length" is kept for this: the function's registers stay where they were.)
+  if (total == 0 ? which != CODE_DIST : left > 0 && (which == CODE_CL || total != 1 || left != (1 << 14))) return 0;
   if (lane < 16) {
     c.count[lane] = (uint16_t)run_l;
     c.first[lane] = (uint16_t)first_l;
@@ -2367,6 +2371,9 @@ __device__ __forceinline__ void inflate_member(const uint8_t* __restrict__ comp,
     err = uni(r.err);
   }
   if (err == INF_OK && (o.pos > o.end || br.overrun())) err = br.overrun() ? INF_INPUT_OVERRUN : INF_OUTPUT_OVERRUN;
+  // overrun() allows the reader's two dwords of look-ahead; at the member's end the reader is exact: a stream whose last bits lie in
+  // the trailer (or in the member behind it) has not ended inside its member -- zlib, given the member's bytes alone, wants more
+  if (err == INF_OK && br.byte_pos() > comp_end) err = INF_INPUT_OVERRUN;
   if (err != INF_OK) o.pos = min(o.pos, o.end);
   drain_to<RING>(o, o.pos);
   if (err == INF_OK && o.pos != o.end) err = INF_SIZE_MISMATCH;
