@@ -118,6 +118,13 @@ class GTFAttributes(C.Structure):
                 ("value_offsets", C.c_void_p), ("value_values", C.c_void_p)]
 
 
+class BEDColumns(C.Structure):
+    _fields_ = [("n_rows", C.c_int64), ("n_undecided", C.c_int64), ("consumed_bytes", C.c_int64),
+                ("chrom_id", C.c_void_p), ("start", C.c_void_p), ("end", C.c_void_p), ("score", C.c_void_p), ("score_valid", C.c_void_p),
+                ("strand_id", C.c_void_p), ("strand_valid", C.c_void_p), ("name_off", C.c_void_p), ("name_len", C.c_void_p),
+                ("name_valid", C.c_void_p), ("text", C.c_void_p)]
+
+
 class ScanOptions(C.Structure):
     _fields_ = [("format", C.c_int32), ("compression", C.c_int32), ("batch_size", C.c_int64),
                 ("info_field", C.c_char_p), ("region", C.c_char_p), ("use_index", C.c_int32), ("gpu_parse", C.c_int32),
@@ -128,8 +135,11 @@ class GzipStats(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in ("calls", "chunks", "repairs", "overflow_retries", "members", "comp_bytes", "out_bytes")]
 
 
-FORMATS = {"vcf": 1, "bam": 2, "fastq": 3, "fasta": 4, "sam": 5, "bcf": 6, "cram": 7, "gff": 8, "gtf": 9}
+FORMATS = {"vcf": 1, "bam": 2, "fastq": 3, "fasta": 4, "sam": 5, "bcf": 6, "cram": 7, "gff": 8, "gtf": 9, "bed": 10}
 COMPRESSION = {"auto": 0, None: 0, "none": 1, "gzip": 2}
+# EXON_HIP_PROJECT_BED_*: bit k = column k of the reference's BED schema; n_fields = k is the mask of bits 3 .. k - 1
+PROJECT_BED = {"name": 1 << 3, "score": 1 << 4, "strand": 1 << 5, "thick_start": 1 << 6, "thick_end": 1 << 7, "color": 1 << 8,
+               "block_count": 1 << 9, "block_sizes": 1 << 10, "block_starts": 1 << 11}
 
 PLAN_REGION_COUNT = 2
 PLAN_FLAG_MAPQ_GROUP_COUNT = 3
@@ -245,6 +255,11 @@ SIGNATURES = {
     "exon_hip_gff_parser_gtf_attributes": (C.c_int, [_vp, _vp, C.POINTER(GTFAttributes)]),
     "exon_hip_gff_parser_names": (C.c_int, [_vp, _i32, C.c_char_p, C.c_size_t, C.POINTER(_i32)]),
     "exon_hip_gff_parser_destroy": (C.c_int, [_vp]),
+    "exon_hip_bed_parser_create": (C.c_int, [_vp, C.POINTER(C.c_char_p), _i32, _i64, C.POINTER(_vp)]),
+    "exon_hip_bed_parser_want": (C.c_int, [_vp, C.c_uint64]),
+    "exon_hip_bed_parser_parse": (C.c_int, [_vp, _vp, _vp, _i64, C.POINTER(BEDColumns)]),
+    "exon_hip_bed_parser_names": (C.c_int, [_vp, C.c_char_p, C.c_size_t, C.POINTER(_i32)]),
+    "exon_hip_bed_parser_destroy": (C.c_int, [_vp]),
     "exon_hip_bcf_parser_create": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i64, C.POINTER(_vp)]),
     "exon_hip_bcf_parser_set_info_keys": (C.c_int, [_vp, C.POINTER(_i32), C.c_char_p, _i32]),
     "exon_hip_bcf_parser_parse": (C.c_int, [_vp, _vp, _vp, _i64, C.POINTER(VCFColumns)]),

@@ -6,13 +6,14 @@
 // GPU, like config 1); predicates / GROUP BY run through exon_hip_plan_* / exon_hip_stream_* on the GPU.
 //
 //   SET exon.vcf_parse_info = true;
-//   CREATE EXTERNAL TABLE t STORED AS FASTA|FASTQ|VCF|BAM|GFF|GTF|INDEXED_VCF|INDEXED_BAM|INDEXED_GFF [OPTIONS (compression gzip)] LOCATION '<path|dir>';
+//   CREATE EXTERNAL TABLE t STORED AS FASTA|FASTQ|VCF|BAM|GFF|GTF|BED|INDEXED_VCF|INDEXED_BAM|INDEXED_GFF [OPTIONS (compression gzip, n_fields 6)] LOCATION '<path|dir>';
 //   SELECT COUNT(*) FROM t | fasta_scan('<p>'[, 'gzip']) | fastq_scan(..) | vcf_scan(..) | bam_scan(..)
-//                         | vcf_indexed_scan('<p>', '<region>') | bam_indexed_scan('<p>', '<region>') | gff_scan(..) | gtf_scan(..) | gff_indexed_scan(..)
+//                         | vcf_indexed_scan('<p>', '<region>') | bam_indexed_scan('<p>', '<region>') | gff_scan(..) | gtf_scan(..) | bed_scan(..) | gff_indexed_scan(..)
 //   SELECT COUNT(*) FROM v WHERE chrom = '7' AND pos >= 50000000 AND pos <= 100000000            -- K2
 //   SELECT COUNT(*) FROM v WHERE vcf_region_filter('7:50000000-100000000', chrom[, pos]) [= true] -- pushed down
 //   SELECT COUNT(*) FROM b WHERE bam_region_filter('chr1:1-100', reference, start, end) [= true]  -- pushed down
 //   SELECT COUNT(*) FROM g WHERE gff_region_filter('chr1[:a-b]', seqname[, start]) [= true]       -- K2 over (seqname, start); GFF and GTF sources
+//   SELECT COUNT(*) FROM b WHERE gff_region_filter('chr1[:a-b]', reference_sequence_name[, start]) [= true] -- the same over a BED source: K2 over (0, 1)
 //   SELECT reference, COUNT(*) FROM b WHERE flag & 1284 = 0 AND CAST(mapping_quality AS INT) >= 30 GROUP BY reference  -- K3
 //   SELECT filter, AVG(qual), COUNT(*) FROM v WHERE info."AF" > 0.01 GROUP BY filter            -- K4
 //   SELECT * FROM fastq_quality_histogram('<p>'[, 'gzip'])                                        -- K5
@@ -126,6 +127,7 @@ struct Table {
   int format = 0;
   bool indexed = false;
   int compression = EXON_HIP_COMPRESSION_AUTO;
+  int n_fields = 12;  // BED: the schema's leading columns (exon-core/src/datasources/bed/table_options.rs:34-45)
   std::string location, extension;
 };
 
@@ -135,6 +137,7 @@ struct Source {  // resolved FROM clause
   std::vector<std::string> files;
   std::string region;  // from *_indexed_scan
   bool indexed = false;
+  int n_fields = 12;  // BED
 };
 
 struct Session {
@@ -191,6 +194,7 @@ std::vector<std::string> format_exts(int format, const std::string& custom) {
     case EXON_HIP_FORMAT_CRAM: return {".cram"};
     case EXON_HIP_FORMAT_GFF: return {".gff", ".gff3"};
     case EXON_HIP_FORMAT_GTF: return {".gtf"};
+    case EXON_HIP_FORMAT_BED: return {".bed"};
     default: return {".bam"};
   }
 }
@@ -210,6 +214,10 @@ int format_of(const std::string& name, bool* indexed) {
   if (f == "gtf") {
     if (*indexed) throw Err("unsupported file type " + name + " (there is no indexed GTF table)");
     return EXON_HIP_FORMAT_GTF;
+  }
+  if (f == "bed") {
+    if (*indexed) throw Err("unsupported file type " + name + " (there is no indexed BED table)");
+    return EXON_HIP_FORMAT_BED;
   }
   throw Err("unsupported file type " + name);
 }
@@ -271,17 +279,18 @@ bool gpu_parse_enabled() {
 }
 
 void open_scan(const Source& src, const std::string& file, const char* info_field, const std::string& region, ScanGuard* g,
-               bool for_gpu_query = false) {
+               bool for_gpu_query = false, uint64_t projection = 0) {
   exon_hip_scan_options o;
   memset(&o, 0, sizeof o);
   o.format = src.format;
   o.compression = src.compression;
   o.info_field = info_field;
   o.region = region.empty() ? nullptr : region.c_str();
+  o.projection = projection;
   // INDEXED_* tables / *_indexed_scan: plan BGZF chunks from <file>.tbi / <file>.bai
   // (exon-core/src/datasources/indexed_file/indexed_bgzf_file.rs:129-155)
   o.use_index = (src.indexed && !region.empty()) ? 1 : 0;
-  o.gpu_parse = (for_gpu_query && (src.format == EXON_HIP_FORMAT_VCF || src.format == EXON_HIP_FORMAT_FASTQ || src.format == EXON_HIP_FORMAT_BAM || src.format == EXON_HIP_FORMAT_BCF || src.format == EXON_HIP_FORMAT_SAM || src.format == EXON_HIP_FORMAT_GFF || src.format == EXON_HIP_FORMAT_GTF) &&
+  o.gpu_parse = (for_gpu_query && (src.format == EXON_HIP_FORMAT_VCF || src.format == EXON_HIP_FORMAT_FASTQ || src.format == EXON_HIP_FORMAT_BAM || src.format == EXON_HIP_FORMAT_BCF || src.format == EXON_HIP_FORMAT_SAM || src.format == EXON_HIP_FORMAT_GFF || src.format == EXON_HIP_FORMAT_GTF || src.format == EXON_HIP_FORMAT_BED) &&
                  region.empty() && gpu_parse_enabled()) ? 1 : 0;
   ck(nullptr, exon_hip_scan_open(file.c_str(), &o, &g->s));
 }
@@ -406,6 +415,7 @@ Source resolve_from(Session& se, Parser& ps) {
   auto it = se.tables.find(lname);
   if (it == se.tables.end()) throw Err("table '" + name + "' not found");
   src.format = it->second.format;
+  src.n_fields = it->second.n_fields;
   src.compression = it->second.compression;
   src.indexed = it->second.indexed;
   list_files(it->second.location, format_exts(src.format, it->second.extension), &src.files);
@@ -460,6 +470,60 @@ void select_annotation_rows(const Source& src, bool star, const std::vector<std:
             const int32_t* off = static_cast<const int32_t*>(d->buffers[1]) + d->offset;
             row.push_back(std::string(static_cast<const char*>(d->buffers[2]) + off[id], (size_t)(off[id + 1] - off[id])));
           }
+        }
+        rows.push_back(std::move(row));
+      }
+      if (b.release) b.release(&b);
+    }
+  }
+  print_table(head, rows, quiet);
+}
+
+// SELECT <columns | *> FROM <BED source> [LIMIT n]: rows of the table's n_fields leading columns (schema.rs:27-48) through the host
+// reader, NULLs printed as datafusion's CLI prints them
+void select_bed_rows(const Source& src, bool star, const std::vector<std::string>& proj, int64_t limit, bool quiet) {
+  static const char* const NAMES[12] = {"reference_sequence_name", "start", "end", "name", "score", "strand", "thick_start", "thick_end", "color", "block_count",
+                                        "block_sizes", "block_starts"};
+  static const bool UTF8[12] = {false, false, false, true, false, false, false, false, true, false, true, true};
+  uint64_t mask = 0;
+  for (int c = 3; c < src.n_fields; ++c) mask |= 1ull << c;
+  std::vector<int> cols;
+  if (star) for (int c = 0; c < src.n_fields; ++c) cols.push_back(c);
+  for (const auto& p : proj) {
+    int at = -1;
+    for (int c = 0; c < src.n_fields; ++c) if (p == NAMES[c] || p == std::string("\"") + NAMES[c] + "\"") at = c;
+    if (at < 0) throw Err("column '" + p + "' is not one of this BED table's " + std::to_string(src.n_fields) + " (n_fields)");
+    cols.push_back(at);
+  }
+  std::vector<std::string> head;
+  for (int c : cols) head.push_back(NAMES[c]);
+  std::vector<std::vector<std::string>> rows;
+  auto valid = [](const struct ArrowArray* a, int64_t i) {
+    const uint8_t* bm = static_cast<const uint8_t*>(a->buffers[0]);
+    return !bm || ((bm[(i + a->offset) >> 3] >> ((i + a->offset) & 7)) & 1);
+  };
+  auto utf8 = [](const struct ArrowArray* a, int64_t at) {
+    const int32_t* off = static_cast<const int32_t*>(a->buffers[1]);
+    return std::string(static_cast<const char*>(a->buffers[2]) + off[at], (size_t)(off[at + 1] - off[at]));
+  };
+  for (const auto& f : src.files) {
+    ScanGuard g;
+    open_scan(src, f, nullptr, "", &g, false, mask);
+    for (;;) {
+      if (limit >= 0 && (int64_t)rows.size() >= limit) break;
+      struct ArrowArray b;
+      const int rc = exon_hip_scan_next(g.s, &b);
+      if (rc == 1) break;
+      ck(nullptr, rc);
+      for (int64_t i = 0; i < b.length && (limit < 0 || (int64_t)rows.size() < limit); ++i) {
+        std::vector<std::string> row;
+        for (int c : cols) {
+          const struct ArrowArray* a = b.children[c];  // (the mask is a prefix of the schema: scan column = schema column)
+          if (!valid(a, i)) { row.push_back("NULL"); continue; }
+          const int64_t at = i + a->offset;
+          if (c == 0 || c == 5) row.push_back(utf8(a->dictionary, static_cast<const int32_t*>(a->buffers[1])[at] + a->dictionary->offset));
+          else if (UTF8[c]) row.push_back(utf8(a, at));
+          else row.push_back(std::to_string(static_cast<const int64_t*>(a->buffers[1])[at]));
         }
         rows.push_back(std::move(row));
       }
@@ -527,6 +591,37 @@ void exec_select(Session& se, Parser& ps) {
   const bool count_only = proj.size() == 1 && proj[0] == "count(*)" && group_by.empty() && !star;
   if (!count_only && group_by.empty() && pr.kind == Predicate::None && (src.format == EXON_HIP_FORMAT_GFF || src.format == EXON_HIP_FORMAT_GTF)) {
     select_annotation_rows(src, star, proj, limit, se.quiet);
+    return;
+  }
+  if (!count_only && group_by.empty() && pr.kind == Predicate::None && src.format == EXON_HIP_FORMAT_BED) {
+    select_bed_rows(src, star, proj, limit, se.quiet);
+    return;
+  }
+  if (count_only && pr.kind == Predicate::PushedRegion && src.format == EXON_HIP_FORMAT_BED) {
+    // the region test the CLI knows for GFF sources, over a BED source: reference_sequence_name = name AND start inside the interval,
+    // K2 over scan columns (0, 1).  The reference has no region filter for BED, so nothing is pushed into the reader: the text is
+    // parsed on the device (EXON_HIP_GPU_PARSE=0: by the host reader) and the plan filters
+    exon_hip_ctx* ctx = se.gpu();
+    char name[512];
+    int64_t a = 1, b = INT64_MAX;
+    ck(nullptr, exon_hip_parse_region(pr.region.c_str(), name, sizeof name, &a, &b));
+    int64_t total = 0;
+    for (const auto& f : src.files) {
+      ScanGuard g; open_scan(src, f, nullptr, "", &g, true);
+      int32_t sid = -1;
+      ck(nullptr, exon_hip_scan_dictionary_intern(g.s, 0, name, &sid));  // (BED has no header: the name seeds the scan's dictionary)
+      StreamGuard sg;
+      exon_hip_plan_desc d; memset(&d, 0, sizeof d);
+      d.kind = EXON_HIP_PLAN_REGION_COUNT; d.region_chrom_id = sid; d.region_start = a; d.region_end = b;
+      d.columns[0] = 0; d.columns[1] = 1;
+      ck(ctx, exon_hip_plan_create(ctx, &d, &sg.p));
+      ck(ctx, exon_hip_stream_open(sg.p, 0, &sg.s));
+      ck(ctx, exon_hip_stream_consume_scan(sg.s, g.s, nullptr));
+      int64_t c = 0;
+      ck(ctx, exon_hip_stream_finish(sg.s, &c, nullptr));
+      total += c;
+    }
+    print_table({"count(*)"}, {{std::to_string(total)}}, se.quiet);
     return;
   }
   if (count_only && pr.kind == Predicate::PushedRegion && !src.indexed && gpu_parse_enabled() &&
@@ -713,8 +808,12 @@ void exec_statement(Session& se, const std::string& sql) {
         ps.expect_sym("(");
         while (!ps.accept_sym(")")) {
           std::string k = ps.peek().kind == Tok::Str ? ps.str() : ps.ident();
-          std::string v = ps.peek().kind == Tok::Str ? ps.str() : ps.ident();
+          std::string v = ps.peek().kind == Tok::Str ? ps.str() : ps.peek().kind == Tok::Num ? ps.number() : ps.ident();
           k = lower(k);
+          if (k == "n_fields" || ends_with(k, ".n_fields")) {
+            t.n_fields = atoi(v.c_str());
+            if (t.n_fields < 3 || t.n_fields > 12) throw Err("n_fields " + v + ": a BED table has 3 to 12 fields");
+          }
           if (k == "compression" || ends_with(k, ".compression")) t.compression = compression_of(v);
           if (k == "file_extension" || ends_with(k, ".file_extension")) t.extension = v;
           if (k == "indexed" && lower(v) == "true") t.indexed = true;
@@ -754,8 +853,8 @@ int main(int argc, char** argv) {
     else if (a == "-q" || a == "--quiet") se.quiet = true;
     else if (a == "-h" || a == "--help") {
       printf("exon-hip-cli [-q] -c '<sql>'... | -f <file>...\n"
-             "  tables:    CREATE EXTERNAL TABLE t STORED AS FASTA|FASTQ|VCF|BAM|GFF|GTF|INDEXED_VCF|INDEXED_BAM|INDEXED_GFF [OPTIONS (compression gzip)] LOCATION '<path>'\n"
-             "  functions: fasta_scan fastq_scan vcf_scan bam_scan gff_scan gtf_scan ('<path>'[, 'gzip']); vcf_indexed_scan bam_indexed_scan gff_indexed_scan ('<path>', '<region>');\n"
+             "  tables:    CREATE EXTERNAL TABLE t STORED AS FASTA|FASTQ|VCF|BAM|GFF|GTF|BED|INDEXED_VCF|INDEXED_BAM|INDEXED_GFF [OPTIONS (compression gzip, n_fields 6)] LOCATION '<path>'\n"
+             "  functions: fasta_scan fastq_scan vcf_scan bam_scan gff_scan gtf_scan bed_scan ('<path>'[, 'gzip']); vcf_indexed_scan bam_indexed_scan gff_indexed_scan ('<path>', '<region>');\n"
              "             fastq_quality_histogram('<path>')\n"
              "  queries:   SELECT COUNT(*) FROM <src> [WHERE chrom = 'c' AND pos >= a AND pos <= b | vcf_region_filter('r', chrom) | bam_region_filter('r', reference, start, end)\n"
              "             | gff_region_filter('r', seqname[, start])]\n"

@@ -1404,8 +1404,9 @@ __device__ __forceinline__ int table_claim(const FilterTable& t, const uint8_t* 
   return -1;
 }
 
-// start / end: Rust's usize::from_str (one '+', digits) and >= 1; up to 18 digits here, longer ones are the host's
-__device__ __forceinline__ bool gff_position(const uint8_t* __restrict__ text, unsigned pb, unsigned pe, unsigned n_total, int64_t* out) {
+// start / end: Rust's usize::from_str (one '+', digits) and >= vmin (GFF / GTF: 1; BED is 0-based: 0); up to 18 digits here,
+// longer ones are the host's
+__device__ __forceinline__ bool gff_position(const uint8_t* __restrict__ text, unsigned pb, unsigned pe, unsigned n_total, uint64_t vmin, int64_t* out) {
   unsigned pn = pe - pb;
   if (pn && text[pb] == '+') ++pb, --pn;
   bool ok = pn > 0 && pn <= 18;
@@ -1425,7 +1426,7 @@ __device__ __forceinline__ bool gff_position(const uint8_t* __restrict__ text, u
       v = v * 10 + d;
     }
   }
-  ok = ok && v >= 1;
+  ok = ok && v >= vmin;
   *out = ok ? (int64_t)v : 0;
   return ok;
 }
@@ -1482,8 +1483,8 @@ __global__ __launch_bounds__(TPB) void k_parse_gff_lines(const uint8_t* __restri
       slot[0] = table_claim(t0, text, fs[0], (int)(fs[1] - 1 - fs[0]));
       slot[1] = table_claim(t1, text, fs[1], (int)(fs[2] - 1 - fs[1]));
       slot[2] = table_claim(t2, text, fs[2], (int)(fs[3] - 1 - fs[2]));
-      bad |= !gff_position(text, fs[3], fs[4] - 1, n_total, &start);
-      bad |= !gff_position(text, fs[4], fs[5] - 1, n_total, &stop);
+      bad |= !gff_position(text, fs[3], fs[4] - 1, n_total, 1, &start);
+      bad |= !gff_position(text, fs[4], fs[5] - 1, n_total, 1, &stop);
       const int sl = (int)(fs[6] - 1 - fs[5]);
       if (!(sl == 1 && text[fs[5]] == '.')) {
         uint32_t bits;
@@ -1801,4 +1802,302 @@ void exon_hip_gff_parser_attr_fields(exon_hip_gff_parser* p, const uint8_t** tex
 int exon_hip_gff_parser_names_so_far(exon_hip_gff_parser* p, int32_t column, char* buf, size_t cap, int32_t* n_names) {
   if (!p || !n_names || column < 0 || column > 2) return fail(p ? p->ctx : nullptr, EXON_HIP_EINVAL, "exon_hip_gff_parser_names_so_far: bad argument");
   return table_names(p->ctx, p->tables[column], "GFF names", buf, cap, n_names, true);
+}
+
+// ------------------------------------------------------------------------------------------------------------
+// BED text: every line decoded by its own field count -> the BED device layout (host/bed.h states the line rules once;
+// exon-bed/src/schema.rs is the schema, batch_reader.rs:92-231 the decode by field count).  The shape is k_parse_gff_lines': one
+// line per lane, '#' lines ranked away (k_gff_classify, the offsets scan; the identity when the slab has none), column 0 a
+// dictionary built on the device (table_claim, k_assign_filters, k_remap_filters).  What differs: the WHOLE line is scanned --
+// the field count must be exact up to the 13th TAB, and any byte >= 0x80 makes the row undecided (the line must be valid UTF-8,
+// ignored fields included: the host's to check) -- and the same 16-byte groups give both masks.  Everything the rules call an
+// error, and a position of more than 18 digits, is an undecided row: the host reader raises the error with the line quoted.
+namespace {
+
+struct BedOut {
+  int32_t* id;    // reference_sequence_name: provisional slot, then the dense id (k_remap_filters)
+  uint32_t* off;  // where the field's text is in the slab, and its length: k_remap_filters verifies it
+  uint32_t* len;
+  int64_t* start;
+  int64_t* end;
+  // PROJ only (exon_hip_bed_parser_want):
+  int64_t* score;
+  int32_t* strand;
+  uint32_t* name_off;
+  uint32_t* name_len;
+  uint8_t *score_valid, *strand_valid, *name_valid;
+  uint8_t* vflags;  // ranked slabs: bit 0 score, 1 strand, 2 name of every row (k_gff_pack_valid makes the bitmaps of them)
+};
+
+// bit b = byte b of the 16-byte group is >= 0x80
+__device__ __forceinline__ unsigned high_mask16(const uint4& v) {
+  const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+  unsigned mask = 0;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const uint32_t t = (w[k] & 0x80808080u) >> 7;  // bits 0, 8, 16, 24
+    mask |= ((t | (t >> 7) | (t >> 14) | (t >> 21)) & 0xFu) << (4 * k);
+  }
+  return mask;
+}
+
+// PROJ = false (a fused plan: K2 / K6 / K7 read columns 0, 1, 2): the three operand columns and nothing else; the line is
+// validated in full all the same.
+template <bool PROJ>
+__global__ __launch_bounds__(TPB) void k_parse_bed_lines(const uint8_t* __restrict__ text, const unsigned* __restrict__ nl_pos, unsigned* __restrict__ scalars,
+                                                         const uint32_t* __restrict__ is_row, const unsigned* __restrict__ block_offsets, FilterTable t0, BedOut out,
+                                                         unsigned cap, unsigned skip, unsigned n_total) {
+  static_assert(TPB == LIST_TPB, "list_first_item ranks a workgroup of LIST_TPB lines");
+  const unsigned n_lines = min(scalars[0], cap), n_rows = scalars[3];
+  const bool identity = n_rows == n_lines;  // no '#' line in the slab (the same for every thread of the launch)
+  const unsigned line = blockIdx.x * TPB + threadIdx.x;
+  const int lane = threadIdx.x & 63;
+  const unsigned c = line < n_lines ? is_row[line] : 0u;
+  const unsigned row = identity ? line : list_first_item(c, block_offsets);
+  auto group16 = [&](unsigned a) {  // an aligned 16-byte group of the slab; the last one byte by byte
+    uint4 v = {0, 0, 0, 0};
+    if (a + 16u <= n_total) {
+      v = *reinterpret_cast<const uint4*>(text + a);
+    } else {
+      unsigned* w = &v.x;
+      for (unsigned i = 0; a + i < n_total; ++i) w[i >> 2] |= (unsigned)text[a + i] << (8 * (i & 3));
+    }
+    return v;
+  };
+  bool score_ok = false, strand_ok = false, name_ok = false, bad = false;
+  if (c) {
+    const unsigned begin = line ? nl_pos[line - 1] + 1 : skip;
+    unsigned end = nl_pos[line];
+    if (end > begin && text[end - 1] == '\r') --end;
+    unsigned fs[7];  // field f (0..5) spans [fs[f], fs[f + 1] - 1)
+    int nt = 0;      // TABs seen, up to 13: the field count is nt + 1
+    unsigned high = 0;
+    fs[0] = begin;
+    for (unsigned a = begin & ~15u; a < end && nt < 13; a += 16) {
+      const uint4 v = group16(a);
+      unsigned m = clip_mask16(eq_mask16(v, 0x09090909u), a, begin, end);
+      high |= clip_mask16(high_mask16(v), a, begin, end);
+      while (m) {
+        if (nt < 6) fs[nt + 1] = a + (unsigned)__ffs((int)m);
+        ++nt;
+        m &= m - 1;
+      }
+    }
+    const int nf = nt + 1;
+    const bool counted = nf == 3 || nf == 4 || nf == 5 || nf == 6 || nf == 12;
+    bad = !counted || high != 0;  // (13 TABs end the scan early: the row is undecided whatever lies behind them)
+    int64_t start = 0, stop = 0, score = 0;
+    int32_t strand = 0, slot = -1;
+    unsigned name_off = begin, name_len = 0;
+    if (!counted) {
+      for (int k = 0; k < 7; ++k) fs[k] = begin;  // (the row's slots below get defined values)
+    } else {
+      if (nt < 6) fs[nt + 1] = end + 1;  // the last field ends at the line's end
+      slot = table_claim(t0, text, fs[0], (int)(fs[1] - 1 - fs[0]));
+      bad |= !gff_position(text, fs[1], fs[2] - 1, n_total, 0, &start);
+      bad |= !gff_position(text, fs[2], fs[3] - 1, n_total, 0, &stop);
+      if (nf >= 5) {
+        name_ok = true;
+        name_off = fs[3];
+        name_len = fs[4] - 1 - fs[3];
+        unsigned sb = fs[4], sn = fs[5] - 1 - fs[4];  // u16::from_str: one '+', digits; more than 5 digits (leading zeros) are the host's
+        if (sn && text[sb] == '+') ++sb, --sn;
+        score_ok = sn >= 1 && sn <= 5;
+        unsigned v = 0;
+        for (unsigned i = 0; i < sn && score_ok; ++i) {
+          const unsigned d = (unsigned)text[sb + i] - (unsigned)'0';
+          score_ok = d <= 9u;
+          v = v * 10 + d;
+        }
+        score_ok = score_ok && v <= 65535u;
+        score = score_ok ? (int64_t)v : 0;
+        bad |= !score_ok;
+      }
+      if (nf >= 6) {
+        const unsigned sc = fs[6] - 1 - fs[5] == 1u ? text[fs[5]] : 0u;
+        strand_ok = sc == '+' || sc == '-';
+        strand = sc == '-' ? 1 : 0;
+        bad |= !(strand_ok || sc == '.');
+      }
+    }
+    out.id[row] = slot;  // -1: no slot, k_remap_filters writes id 0 and compares nothing
+    out.off[row] = fs[0];
+    out.len[row] = counted ? fs[1] - 1 - fs[0] : 0u;
+    out.start[row] = start;
+    out.end[row] = stop;
+    if (PROJ) {
+      out.score[row] = score;
+      out.strand[row] = strand;
+      out.name_off[row] = name_off;
+      out.name_len[row] = name_len;
+      if (!identity) out.vflags[row] = (uint8_t)((score_ok ? 1 : 0) | (strand_ok ? 2 : 0) | (name_ok ? 4 : 0));
+    }
+  }
+  if (PROJ && identity) {
+    const int64_t row0 = (int64_t)line - lane;
+    store_valid(out.score_valid, row0, n_rows, score_ok, lane);
+    store_valid(out.strand_valid, row0, n_rows, strand_ok, lane);
+    store_valid(out.name_valid, row0, n_rows, name_ok, lane);
+  }
+  const unsigned long long nb = __ballot(bad);
+  if (lane == 0 && nb) atomicAdd(&scalars[1], (unsigned)__popcll(nb));
+}
+
+}  // namespace
+
+struct exon_hip_bed_parser {
+  exon_hip_ctx* ctx;
+  PoolBufs bufs;
+  int64_t max_rows = 0;
+  LineIndex idx;  // scalars: [0] lines, [1] undecided, [2] consumed bytes, [3] rows
+  FilterTable table = {};
+  BedOut out{};
+  uint32_t* d_is_row = nullptr;
+  unsigned* d_blocks = nullptr;  // per-workgroup sums of is_row (scanned in place)
+  int32_t h_stat = 0;            // the dictionary's overflow flag after the last slab
+  bool proj = false;             // exon_hip_bed_parser_want: score, strand and the names' places
+  const uint8_t* last_text = nullptr;  // the slab of the last parse call (aligned), for the scan's `name` column
+  int64_t last_bytes = 0;
+  PoolBufs proj_bufs;            // (of their own: a failed allocation is released and does not stick to the parser's)
+  explicit exon_hip_bed_parser(exon_hip_ctx* c) : ctx(c), bufs(c), proj_bufs(c) {}
+};
+
+extern "C" {
+
+int exon_hip_bed_parser_create(exon_hip_ctx* ctx, const char* const* seed_names, int32_t n_seed, int64_t max_bytes, exon_hip_bed_parser** outp) {
+  if (!ctx || !outp || n_seed < 0 || (n_seed > 0 && !seed_names) || max_bytes < 16) return fail(ctx, EXON_HIP_EINVAL, "exon_hip_bed_parser_create: bad argument");
+  if (max_bytes > 0xF0000000LL) return fail(ctx, EXON_HIP_EINVAL, "slab size must stay below 4 GiB (32-bit line offsets)");
+  *outp = nullptr;
+  exon_hip_bed_parser* p = new (std::nothrow) exon_hip_bed_parser(ctx);
+  if (!p) return fail(ctx, EXON_HIP_ENOMEM, "out of host memory");
+  p->max_rows = max_bytes / 8 + 1;  // "chr1", two positions, two tabs and the newline are nine bytes; a slab of shorter lines than
+                                    // eight bytes on average ('#' alone, empty lines, one-letter names) is handed to the host reader
+  hipSetDevice(ctx->device);
+  PoolBufs& b = p->bufs;
+  p->table = take_filter_table(b);
+  p->idx.alloc(b, max_bytes, p->max_rows);
+  const size_t r = (size_t)p->max_rows;
+  p->out.id = b.take<int32_t>(r * 4);
+  p->out.off = b.take<uint32_t>(r * 4);
+  p->out.len = b.take<uint32_t>(r * 4);
+  p->out.start = b.take<int64_t>(r * 8);
+  p->out.end = b.take<int64_t>(r * 8);
+  p->d_is_row = b.take<uint32_t>(r * 4);
+  p->d_blocks = b.take<unsigned>((r / LIST_TPB + 2) * 4);
+  int rc = EXON_HIP_OK;
+  if (b.status() == hipSuccess) rc = seed_filter_table(ctx, b, p->table, seed_names, n_seed);
+  if (rc) {
+    delete p;
+    return rc;
+  }
+  if (b.status() != hipSuccess) {
+    const std::string msg = hipGetErrorString(b.status());
+    delete p;
+    return fail(ctx, EXON_HIP_ENOMEM, "bed parser allocation: %s", msg.c_str());
+  }
+  *outp = p;
+  return EXON_HIP_OK;
+}
+
+int exon_hip_bed_parser_destroy(exon_hip_bed_parser* p) {
+  delete p;
+  return EXON_HIP_OK;
+}
+
+int exon_hip_bed_parser_want(exon_hip_bed_parser* p, uint64_t projection) {
+  if (!p) return fail(nullptr, EXON_HIP_EINVAL, "exon_hip_bed_parser_want: NULL argument");
+  if (projection & ~0xFF8ull) return fail(p->ctx, EXON_HIP_EUNSUPPORTED, "exon_hip_bed_parser_want: projection 0x%llx (EXON_HIP_PROJECT_BED_*: bits 3 .. 11)", (unsigned long long)projection);
+  const bool on = (projection & (EXON_HIP_PROJECT_BED_NAME | EXON_HIP_PROJECT_BED_SCORE | EXON_HIP_PROJECT_BED_STRAND)) != 0;  // (columns 6 .. 11 are NULL: nothing to parse)
+  if (on && !p->out.score) {
+    hipSetDevice(p->ctx->device);
+    PoolBufs& b = p->proj_bufs;
+    const size_t r = (size_t)p->max_rows, rb = r / 8 + 64;
+    BedOut& o = p->out;
+    o.score = b.take<int64_t>(r * 8);
+    o.strand = b.take<int32_t>(r * 4);
+    o.name_off = b.take<uint32_t>(r * 4);
+    o.name_len = b.take<uint32_t>(r * 4);
+    o.score_valid = b.take<uint8_t>(rb);
+    o.strand_valid = b.take<uint8_t>(rb);
+    o.name_valid = b.take<uint8_t>(rb);
+    o.vflags = b.take<uint8_t>(r + 64);
+    if (b.status() != hipSuccess) {
+      (void)hipGetLastError();
+      b.release();
+      o.score = nullptr;
+      return fail(p->ctx, EXON_HIP_ENOMEM, "bed parser: the projected columns (%lld rows)", (long long)p->max_rows);
+    }
+  }
+  p->proj = on;
+  return EXON_HIP_OK;
+}
+
+int exon_hip_bed_parser_parse(exon_hip_bed_parser* p, void* stream, const uint8_t* d_text, int64_t n_bytes, exon_hip_bed_columns* cols) {
+  if (!p || !cols || (n_bytes > 0 && !d_text)) return fail(p ? p->ctx : nullptr, EXON_HIP_EINVAL, "exon_hip_bed_parser_parse: NULL argument");
+  exon_hip_ctx* ctx = p->ctx;
+  memset(cols, 0, sizeof *cols);
+  if (n_bytes == 0) return EXON_HIP_OK;
+  LineIndex& idx = p->idx;
+  unsigned skip;
+  if (int rc = idx.align(ctx, &d_text, &n_bytes, &skip)) return rc;
+  hipStream_t s = pick_stream(ctx, stream);
+  idx.launch(s, d_text, n_bytes, skip);
+  hipLaunchKernelGGL(k_last_newline, dim3(1), dim3(1), 0, s, idx.nl, idx.d_scalars, idx.cap);
+  const int64_t row_bound = std::min<int64_t>(p->max_rows, n_bytes / 8 + 1);
+  const int pblocks = (int)((row_bound + TPB - 1) / TPB);
+  const BedOut& o = p->out;
+  hipLaunchKernelGGL(k_gff_classify, dim3(pblocks), dim3(TPB), 0, s, d_text, idx.nl, idx.d_scalars, (unsigned)row_bound, skip, p->d_is_row);
+  launch_list_scan(s, p->d_is_row, idx.d_scalars, (unsigned)row_bound, pblocks, p->d_blocks, idx.d_scalars + 3);
+  hipLaunchKernelGGL(p->proj ? k_parse_bed_lines<true> : k_parse_bed_lines<false>, dim3(pblocks), dim3(TPB), 0, s, d_text, idx.nl, idx.d_scalars, p->d_is_row, p->d_blocks,
+                     p->table, o, (unsigned)row_bound, skip, (unsigned)n_bytes);
+  if (p->proj)
+    hipLaunchKernelGGL(k_gff_pack_valid, dim3(std::min(pblocks, 1024)), dim3(256), 0, s, idx.d_scalars, (unsigned)row_bound, o.vflags, o.score_valid, o.strand_valid,
+                       o.name_valid);
+  hipLaunchKernelGGL(k_assign_filters, dim3(1), dim3(256), 0, s, d_text, p->table);
+  hipLaunchKernelGGL(k_remap_filters, dim3(std::min(pblocks, 4096)), dim3(TPB), 0, s, o.id, idx.d_scalars + 3, (unsigned)row_bound, p->table, d_text, o.off, o.len,
+                     (const uint8_t*)nullptr);
+  HIP_TRY(ctx, hipMemcpyAsync(&p->h_stat, p->table.counters + 2, 4, hipMemcpyDeviceToHost, s));  // overflow or collision
+  if (int rc = idx.read_back(ctx, s)) return rc;
+  const int64_t n_lines = idx.h_scalars[0];
+  cols->n_rows = idx.h_scalars[3];
+  cols->n_undecided = idx.h_scalars[1] + (n_lines > row_bound ? 1 : 0);  // more lines than the slab's bytes allow for records: the host reader's
+  cols->n_undecided += p->h_stat ? 1 : 0;                                // the dictionary past its limits (or two texts that hash alike)
+  cols->consumed_bytes = idx.consumed(skip);
+  p->last_text = d_text;
+  p->last_bytes = n_bytes;
+  cols->chrom_id = o.id;
+  cols->start = o.start;
+  cols->end = o.end;
+  if (p->proj) {
+    cols->score = o.score;
+    cols->score_valid = o.score_valid;
+    cols->strand_id = o.strand;
+    cols->strand_valid = o.strand_valid;
+    cols->name_off = o.name_off;
+    cols->name_len = o.name_len;
+    cols->name_valid = o.name_valid;
+    cols->text = d_text;
+  }
+  return EXON_HIP_OK;
+}
+
+// the reference_sequence_name dictionary discovered so far, '\0'-separated in id order
+int exon_hip_bed_parser_names(exon_hip_bed_parser* p, char* buf, size_t cap, int32_t* n_names) {
+  if (!p || !n_names) return fail(p ? p->ctx : nullptr, EXON_HIP_EINVAL, "exon_hip_bed_parser_names: bad argument");
+  return table_names(p->ctx, p->table, "reference sequence names", buf, cap, n_names, false);
+}
+
+}  // extern "C"
+
+void exon_hip_bed_parser_name_fields(exon_hip_bed_parser* p, const uint8_t** text, int64_t* n_bytes, const uint32_t** off, const uint32_t** len, const uint8_t** valid) {
+  *text = p->last_text;
+  *n_bytes = p->last_bytes;
+  *off = p->proj ? p->out.name_off : nullptr;
+  *len = p->proj ? p->out.name_len : nullptr;
+  *valid = p->proj ? p->out.name_valid : nullptr;
+}
+
+int exon_hip_bed_parser_names_so_far(exon_hip_bed_parser* p, char* buf, size_t cap, int32_t* n_names) {
+  if (!p || !n_names) return fail(p ? p->ctx : nullptr, EXON_HIP_EINVAL, "exon_hip_bed_parser_names_so_far: bad argument");
+  return table_names(p->ctx, p->table, "BED names", buf, cap, n_names, true);
 }

@@ -121,6 +121,16 @@ struct ExonGtfText {
 };
 int exon_text_gtf(exon_hip_ctx* ctx, void* stream, ExonTextScratch** scratch, const uint8_t* d_text, int64_t n_bytes, const uint32_t* d_attr_off, const uint32_t* d_attr_len,
                   int64_t n_rows, ExonGtfText* out, int64_t* n_undecided);
+// BED `name` (Utf8?, host/bed.h: the field's bytes as they stand, NULL on 3- and 4-field lines): d_text is the ALIGNED slab the
+// parser indexed; d_name_off / d_name_len every row's name in it (k_parse_bed_lines<true>; length 0 where NULL) and d_name_valid its
+// bitmap, which the column takes as it is.  Nothing here is undecided: the line kernel has judged every byte of the line
+struct ExonBedText {
+  const int32_t* name_offsets;  // [n_rows + 1]
+  const uint8_t *name_values, *name_valid;
+  int64_t n_name_bytes;
+};
+int exon_text_bed(exon_hip_ctx* ctx, void* stream, ExonTextScratch** scratch, const uint8_t* d_text, int64_t n_bytes, const uint32_t* d_name_off, const uint32_t* d_name_len,
+                  const uint8_t* d_name_valid, int64_t n_rows, ExonBedText* out);
 void exon_text_scratch_destroy(ExonTextScratch* s);
 // the parsers' own indexes the text columns are built from (valid until the next parse call)
 const unsigned* exon_hip_vcf_parser_newlines(exon_hip_vcf_parser* p);
@@ -134,6 +144,10 @@ int exon_hip_vcf_parser_info_values_so_far(exon_hip_vcf_parser* p, int32_t key, 
 int exon_hip_gff_parser_names_so_far(exon_hip_gff_parser* p, int32_t column, char* buf, size_t cap, int32_t* n_names);
 // gpu_parse.hip: the aligned slab of the last parse call and every row's ninth field in it (after exon_hip_gff_parser_want_attributes)
 void exon_hip_gff_parser_attr_fields(exon_hip_gff_parser* p, const uint8_t** text, int64_t* n_bytes, const uint32_t** off, const uint32_t** len);
+struct exon_hip_bed_parser;
+int exon_hip_bed_parser_names_so_far(exon_hip_bed_parser* p, char* buf, size_t cap, int32_t* n_names);
+// gpu_parse.hip: the aligned slab of the last parse call and every row's name in it (after exon_hip_bed_parser_want with a projection)
+void exon_hip_bed_parser_name_fields(exon_hip_bed_parser* p, const uint8_t** text, int64_t* n_bytes, const uint32_t** off, const uint32_t** len, const uint8_t** valid);
 int exon_hip_bcf_parser_filters_so_far(exon_hip_bcf_parser* p, int32_t* lists, int32_t* counts, int32_t cap, int32_t* n_filters);
 const unsigned* exon_hip_sam_parser_newlines(exon_hip_sam_parser* p);      // gpu_parse.hip: the same for SAM lines      // gpu_parse.hip: byte offset of every line's '\n' in the aligned slab
 const uint32_t* exon_hip_bam_parser_row_records(exon_hip_bam_parser* p);

@@ -23,6 +23,7 @@
 #include "host/formats.h"
 #include "host/gff.h"
 #include "host/gtf.h"
+#include "host/bed.h"
 #include "host/parallel.h"
 #include "internal.h"
 
@@ -43,6 +44,7 @@ struct DeviceParser {
       case EXON_HIP_FORMAT_FASTQ: exon_hip_fastq_parser_destroy(as<exon_hip_fastq_parser>()); break;
       case EXON_HIP_FORMAT_GFF:
       case EXON_HIP_FORMAT_GTF: exon_hip_gff_parser_destroy(as<exon_hip_gff_parser>()); break;  // (GTF: the same parser, its dialect set)
+      case EXON_HIP_FORMAT_BED: exon_hip_bed_parser_destroy(as<exon_hip_bed_parser>()); break;
     }
     h = nullptr;
     owns_names = false;
@@ -64,7 +66,7 @@ struct exon_hip_scan {
   bool gpu_inflated = false;  // the last GPU-parsed consume also inflated BGZF blocks on the device
   bool gpu_decoded = false;   // the last consume decoded every record on the device (no host fallback)
   exon::Dictionary gpu_filter_dict;       // names fetched from the parser after the consume
-  exon::Dictionary gpu_gff_dicts[3];      // GFF: seqname / source / type, likewise
+  exon::Dictionary gpu_gff_dicts[3];      // GFF: seqname / source / type, likewise (BED: [0] is reference_sequence_name)
   std::unique_ptr<exon::BatchReader> reader;  // of `format`
   int64_t rows = 0;
   exon::Dictionary bam_dict_view;  // reference names as a dictionary (ids = header order)
@@ -86,6 +88,7 @@ struct exon_hip_scan {
   // GFF and GTF: one reader class (GTFBatchReader is its GTF dialect), one device parser, one column layout
   exon::GFFBatchReader* gff() const { return reader_if<exon::GFFBatchReader>(gtf() ? EXON_HIP_FORMAT_GTF : EXON_HIP_FORMAT_GFF); }
   bool gtf() const { return format == EXON_HIP_FORMAT_GTF; }
+  exon::BEDBatchReader* bed() const { return reader_if<exon::BEDBatchReader>(EXON_HIP_FORMAT_BED); }
   // VCF and BCF: chrom / pos / qual / filter + typed INFO columns (else BAM / SAM / CRAM's flag / mapq / ref / start / end)
   bool vcf_like() const { return format == EXON_HIP_FORMAT_VCF || format == EXON_HIP_FORMAT_BCF; }
   const std::vector<exon::InfoSpec>& info_specs() const { return vcf() ? vcf()->info_specs : bcf()->info_specs; }
@@ -255,6 +258,10 @@ static exon::Dictionary* dict_of(exon_hip_scan* s, int col) {
     if (col >= 0 && col < 3) return s->parser.owns_names ? &s->gpu_gff_dicts[col] : &g->dicts[col];
     return col == 6 ? &g->strand_dict : col == 7 ? &g->phase_dict : nullptr;
   }
+  if (exon::BEDBatchReader* b = s->bed()) {  // column 0, and strand's column when it is projected
+    if (col == 0) return s->parser.owns_names ? &s->gpu_gff_dicts[0] : &b->dict;
+    return col >= 3 && col == exon::BEDBatchReader::scan_column(s->opt.projection, 5) ? &b->strand_dict : nullptr;
+  }
   if (!s->vcf_like()) {
     const bool refs = s->format == EXON_HIP_FORMAT_BAM || s->format == EXON_HIP_FORMAT_SAM || s->format == EXON_HIP_FORMAT_CRAM;
     return refs && col == 2 ? &s->bam_dict_view : nullptr;
@@ -346,6 +353,16 @@ static std::unique_ptr<exon::BatchReader> open_reader(const exon_hip_scan& s, De
         for (int k = 0; k < 3; ++k) r->dicts[k].names = old->dicts[k].names;
       return r;
     }
+    case EXON_HIP_FORMAT_BED: {
+      exon::BEDConfig fresh;
+      fresh.batch_size = bs;
+      fresh.projection = s.opt.projection;
+      exon::BEDConfig cfg = config(s.bed(), fresh);
+      cfg.defer_decode = device;
+      std::unique_ptr<exon::BEDBatchReader> r(new exon::BEDBatchReader(s.path, c, cfg));
+      if (const exon::BEDBatchReader* old = s.bed()) r->dict.names = old->dict.names;  // (a region plan's contig keeps its id)
+      return r;
+    }
   }
   throw std::runtime_error("unknown format " + std::to_string(s.format));
 }
@@ -389,9 +406,16 @@ int exon_hip_scan_open(const char* path, const exon_hip_scan_options* o, exon_hi
       return fail(nullptr, EXON_HIP_EUNSUPPORTED, "exon_hip_scan_options.projection 0x%llx: GTF knows one projected column, `attributes` (Map<Utf8, Utf8>), by EXON_HIP_PROJECT_GTF_ATTRIBUTES (256: the column's index in the reference's schema)", (unsigned long long)o->projection);
     if (o->format == EXON_HIP_FORMAT_GTF && rf.use_index)
       return fail(nullptr, EXON_HIP_EUNSUPPORTED, "exon_hip_scan_options.use_index: there is no indexed GTF table (the reference has none); a region without use_index filters the whole file");
+    if (o->format == EXON_HIP_FORMAT_BED) {
+      if (o->projection & ~exon::BED_PROJECTION_BITS)
+        return fail(nullptr, EXON_HIP_EUNSUPPORTED, "exon_hip_scan_options.projection 0x%llx: BED knows EXON_HIP_PROJECT_BED_NAME .. _BLOCK_STARTS (bits 3 .. 11: the columns' indexes in the reference's schema)", (unsigned long long)o->projection);
+      if (rf.active || o->use_index)
+        return fail(nullptr, EXON_HIP_EUNSUPPORTED, "exon_hip_scan_options.%s: a BED scan takes neither a region nor an index (the reference has neither a region filter nor an indexed table for BED); filter with a K2 / K6 / K7 plan over columns (0, 1, 2)", rf.active ? "region" : "use_index");
+      if (o->info_field) return fail(nullptr, EXON_HIP_EINVAL, "exon_hip_scan_options.info_field must be NULL for a BED scan");
+    }
     if (o->format == EXON_HIP_FORMAT_GFF && (o->projection & ~EXON_HIP_PROJECT_GFF_ATTRIBUTES))
       return fail(nullptr, EXON_HIP_EUNSUPPORTED, "exon_hip_scan_options.projection 0x%llx: GFF knows one projected column, `attributes` (Map<Utf8, List<Utf8>>), by EXON_HIP_PROJECT_GFF_ATTRIBUTES (256: the column's index in the reference's schema)", (unsigned long long)o->projection);
-    if (o->projection && o->format != EXON_HIP_FORMAT_VCF && o->format != EXON_HIP_FORMAT_BAM && o->format != EXON_HIP_FORMAT_BCF && o->format != EXON_HIP_FORMAT_SAM && o->format != EXON_HIP_FORMAT_GFF && o->format != EXON_HIP_FORMAT_GTF)
+    if (o->projection && o->format != EXON_HIP_FORMAT_VCF && o->format != EXON_HIP_FORMAT_BAM && o->format != EXON_HIP_FORMAT_BCF && o->format != EXON_HIP_FORMAT_SAM && o->format != EXON_HIP_FORMAT_GFF && o->format != EXON_HIP_FORMAT_GTF && o->format != EXON_HIP_FORMAT_BED)
       return fail(nullptr, EXON_HIP_EUNSUPPORTED, "exon_hip_scan_options.projection: the id / ref / alt (/ info / formats) and name / cigar / sequence / quality_score columns are built for VCF, BCF, BAM and SAM scans");
     switch (o->format) {
       case EXON_HIP_FORMAT_VCF:
@@ -429,6 +453,9 @@ int exon_hip_scan_open(const char* path, const exon_hip_scan_options* o, exon_hi
         s->gpu_parse = o->gpu_parse != 0 && (!rf.use_index || (rf.active && wants_gpu_inflate(o, path))) && !reference_tail_quirk(rf);
         break;
       case EXON_HIP_FORMAT_GTF:  // a region rides along as a row mask (use_index was refused above)
+        s->gpu_parse = o->gpu_parse != 0;
+        break;
+      case EXON_HIP_FORMAT_BED:  // (no region, no index: refused above)
         s->gpu_parse = o->gpu_parse != 0;
         break;
       case EXON_HIP_FORMAT_CRAM:
@@ -499,7 +526,7 @@ int exon_hip_scan_dictionary_intern(exon_hip_scan* s, int32_t column, const char
   if (!s || !name || !id) return fail(nullptr, EXON_HIP_EINVAL, "NULL argument");
   exon::Dictionary* d = dict_of(s, column);
   if (!d) return fail(nullptr, EXON_HIP_EINVAL, "column %d is not dictionary-encoded", column);
-  if (s->format == EXON_HIP_FORMAT_BAM || s->format == EXON_HIP_FORMAT_SAM || s->format == EXON_HIP_FORMAT_CRAM || (s->gff() && column >= 6)) {  // ids fixed by the header (GFF strand / phase: by the format)
+  if (s->format == EXON_HIP_FORMAT_BAM || s->format == EXON_HIP_FORMAT_SAM || s->format == EXON_HIP_FORMAT_CRAM || (s->gff() && column >= 6) || (s->bed() && column >= 3)) {  // ids fixed by the header (GFF strand / phase: by the format)
     *id = d->find(name);
     return EXON_HIP_OK;
   }
@@ -554,7 +581,7 @@ int exon_hip_scan_bind_ctx(exon_hip_scan* s, exon_hip_ctx* ctx) {
   if (!s || !ctx) return fail(ctx, EXON_HIP_EINVAL, "exon_hip_scan_bind_ctx: NULL argument");
   if (s->exporter) return fail(ctx, EXON_HIP_ESTATE, "the scan is bound to a context already");
   if (s->format == EXON_HIP_FORMAT_FASTA || s->format == EXON_HIP_FORMAT_CRAM)
-    return fail(ctx, EXON_HIP_EUNSUPPORTED, "batches from the GPU pipeline: VCF, BCF, BAM, SAM, FASTQ, GFF and GTF scans (FASTA / CRAM batches come from the host readers)");
+    return fail(ctx, EXON_HIP_EUNSUPPORTED, "batches from the GPU pipeline: VCF, BCF, BAM, SAM, FASTQ, GFF, GTF and BED scans (FASTA / CRAM batches come from the host readers)");
   if (!s->gpu_parse)  // not opened with gpu_parse, or String / list-valued INFO keys were named: the host reader builds those columns
     return fail(ctx, EXON_HIP_EUNSUPPORTED, "this scan's batches come from the host reader (opened without gpu_parse, or it names INFO keys only the host reader builds)");
   if (s->rows != 0) return fail(ctx, EXON_HIP_ESTATE, "the scan has been read from already");
@@ -1867,6 +1894,21 @@ static int gpu_gff_names(exon_hip_scan* scan, int column, std::vector<std::strin
   return rc;
 }
 
+// BED: the device parser's reference_sequence_name dictionary, names in id order
+static int gpu_bed_names(exon_hip_scan* scan, std::vector<std::string>* names, bool so_far) {
+  names->clear();
+  int32_t nn = 0;
+  std::vector<char> buf(EXON_DICT_NAMES_CAP);
+  const int rc = (so_far ? exon_hip_bed_parser_names_so_far : exon_hip_bed_parser_names)(scan->parser.as<exon_hip_bed_parser>(), buf.data(), buf.size(), &nn);
+  if (rc) return rc;
+  size_t o = 0;
+  for (int32_t i = 0; i < nn; ++i) {
+    names->emplace_back(buf.data() + o);
+    o += names->back().size() + 1;
+  }
+  return rc;
+}
+
 // the value dictionaries of the String INFO keys the device decoded (VCF text): names[k] for scan column 4 + k (empty for other kinds)
 static int gpu_info_names(exon_hip_scan* scan, std::vector<std::vector<std::string>>* names, bool so_far = false) {
   names->clear();
@@ -1958,7 +2000,7 @@ struct Span {
   const T* begin() const { return p; }
 };
 struct HostText {
-  bool vcf = false, bam = false, bcf = false, gff = false, gtf = false;
+  bool vcf = false, bam = false, bcf = false, gff = false, gtf = false, bed = false;  // bed: off[0] / val[0] / valid[0] the names
   Span<int32_t> gtf_val_off;  // GTF attributes: off[0] = the map's offsets, key_off / val[0] the keys, gtf_val_off / val[1] the values
   uint64_t projection = 0;
   // GFF attributes: off[0] = the map's offsets, key_off / val[0] the keys, list_off the value lists, gff_item_off / val[1] their items
@@ -1989,6 +2031,7 @@ struct SlabText {
   ExonBcfText bcf;
   ExonGffText gff;
   ExonGtfText gtf;
+  ExonBedText bed;
   std::function<int()> build;
 };
 static int fetch_text(exon_hip_ctx* ctx, SlabCopier* cp, size_t also_reserve, int64_t n_rows, uint64_t projection, const SlabText& t, HostText* h, bool big_batches) {
@@ -2079,6 +2122,12 @@ static int fetch_text(exon_hip_ctx* ctx, SlabCopier* cp, size_t also_reserve, in
     get(h->gtf_val_off, gt->value_offsets, (size_t)gt->n_entries + 1);
     get(h->val[1], gt->value_values, (size_t)gt->n_value_bytes);
   }
+  if (t.format == EXON_HIP_FORMAT_BED && (projection & EXON_HIP_PROJECT_BED_NAME)) {
+    h->bed = true;
+    get(h->off[0], t.bed.name_offsets, n + 1);
+    get(h->val[0], t.bed.name_values, (size_t)t.bed.n_name_bytes);
+    get(h->valid[0], t.bed.name_valid, nb);
+  }
   size_t total = 64;
   for (const Want& w : wants) total += (w.count * w.elem + 63) & ~(size_t)63;
   if (!cp->reserve(total + 256 * wants.size() + also_reserve)) return fail(ctx, EXON_HIP_ENOMEM, "no device staging buffer of %zu bytes for a slab's string columns", total);
@@ -2151,6 +2200,7 @@ static void text_batch(const HostText& h, const int64_t* rows, int64_t r0, int64
       struct ArrowArray* entries = exon::arena_struct2(arena, (int64_t)h.key_off.n - 1, keys, values);
       kids->push_back(exon::arena_array(arena, n, r0, 0, 2, nullptr, h.off[0].data(), nullptr, entries));
     }
+    if (h.bed) kids->push_back(utf8_view(h.off[0], h.val[0], &h.valid[0], r0, n));
     if (h.bam) {
       if (h.projection & EXON_HIP_PROJECT_BAM_NAME) kids->push_back(utf8_view(h.off[0], h.val[0], &h.valid[0], r0, n));
       if (h.projection & EXON_HIP_PROJECT_BAM_CIGAR) kids->push_back(utf8_view(h.off[1], h.val[1], nullptr, r0, n));
@@ -2248,6 +2298,7 @@ static void text_batch(const HostText& h, const int64_t* rows, int64_t r0, int64
     }
     kids->push_back(col.slice(0, (size_t)n));
   }
+  if (h.bed) kids->push_back(utf8(h.off[0], h.val[0], &h.valid[0]));
   if (h.bam) {
     if (h.projection & EXON_HIP_PROJECT_BAM_NAME) kids->push_back(utf8(h.off[0], h.val[0], &h.valid[0]));
     if (h.projection & EXON_HIP_PROJECT_BAM_CIGAR) kids->push_back(utf8(h.off[1], h.val[1], nullptr));
@@ -2366,7 +2417,13 @@ static int export_slab(exon_hip_scan* scan, const exon_hip_column* sc, int64_t n
   const bool vcf_like = scan->vcf_like();
   const std::vector<exon::InfoSpec>* specs = vcf_like ? &scan->info_specs() : nullptr;
   const bool gff = scan->gff() != nullptr;
-  const int n_cols = vcf_like ? 4 + (int)specs->size() : gff ? 8 : 5;
+  // BED: the fixed-width columns are 0 reference_sequence_name, 1 start, 2 end, then score and strand when projected (parse_slab);
+  // `name` is the text column, columns 6 .. 11 are NULL on every row; bed_order() puts a batch's arrays into the schema's order
+  const bool bed = scan->bed() != nullptr;
+  const uint64_t bed_proj = bed ? scan->opt.projection : 0;
+  const int bed_score = (bed_proj & EXON_HIP_PROJECT_BED_SCORE) ? 3 : -1, bed_strand = (bed_proj & EXON_HIP_PROJECT_BED_STRAND) ? (bed_score < 0 ? 3 : 4) : -1;
+  const bool bed_nulls = (bed_proj >> 6) != 0;
+  const int n_cols = vcf_like ? 4 + (int)specs->size() : gff ? 8 : bed ? 3 + (bed_score >= 0) + (bed_strand >= 0) : 5;
   // element widths in the scan's column order (0 = no values: a Flag, whose bitmap is its value)
   std::vector<int> elem((size_t)n_cols, 4);
   if (vcf_like) {
@@ -2374,6 +2431,9 @@ static int export_slab(exon_hip_scan* scan, const exon_hip_column* sc, int64_t n
     for (size_t k = 0; k < specs->size(); ++k) elem[4 + k] = (*specs)[k].kind == 'b' ? 0 : 4;
   } else if (gff) {
     elem[3] = elem[4] = 8;
+  } else if (bed) {
+    elem[1] = elem[2] = 8;
+    if (bed_score >= 0) elem[(size_t)bed_score] = 8;
   } else {
     elem[1] = 1;
     elem[3] = elem[4] = 8;
@@ -2391,6 +2451,9 @@ static int export_slab(exon_hip_scan* scan, const exon_hip_column* sc, int64_t n
   }
   const size_t moff = bytes;
   bytes += nb;
+  // BED columns 6 .. 11: one run of zeros serves them all as validity bitmap (every row NULL), offsets and values
+  const size_t zoff = bytes, zbytes = bed_nulls ? (((size_t)c_n + 1) * 8 + 63) & ~size_t(63) : 0;
+  bytes += zbytes;
   const size_t path_stage = bytes + 512 * (size_t)n_cols;
   if (projected) {
     int rc = projected->build();  // the device builds the text columns now
@@ -2420,6 +2483,7 @@ static int export_slab(exon_hip_scan* scan, const exon_hip_column* sc, int64_t n
     }
   }
   if (row_mask && !as_views) memcpy(blk + moff, hmask.data(), hmask.size());
+  if (zbytes) memset(blk + zoff, 0, zbytes);
   const hipError_t e = cp.launch();
   if (e != hipSuccess) return fail(ctx, EXON_HIP_EDEVICE, "columns of a slab towards the host: %s", hipGetErrorString(e));
   g_t_fetch_cols += now_s() - tc0;
@@ -2445,6 +2509,9 @@ static int export_slab(exon_hip_scan* scan, const exon_hip_column* sc, int64_t n
   std::vector<std::string> gff_names[3];
   for (int k = 0; gff && k < 3; ++k)
     if (const int rc = gpu_gff_names(scan, k, &gff_names[k], true)) return rc;
+  std::vector<std::string> bed_names;
+  if (bed)
+    if (const int rc = gpu_bed_names(scan, &bed_names, true)) return rc;
   g_t_names += now_s() - tn0;
   // the dictionaries of this slab's batches: built once, shared by every batch's column
   auto dicts_p = std::make_shared<std::vector<std::shared_ptr<const exon::SharedUtf8>>>((size_t)n_cols);
@@ -2456,8 +2523,21 @@ static int export_slab(exon_hip_scan* scan, const exon_hip_column* sc, int64_t n
       dicts[(size_t)c] = std::make_shared<const exon::SharedUtf8>(info_names[(size_t)(c - 4)]);
     else if (gff && c < 3) dicts[(size_t)c] = std::make_shared<const exon::SharedUtf8>(gff_names[c]);
     else if (gff && (c == 6 || c == 7)) dicts[(size_t)c] = std::make_shared<const exon::SharedUtf8>(c == 6 ? exon::gff_strand_names() : exon::gff_phase_names());
-    else if (!vcf_like && !gff && c == 2) dicts[(size_t)c] = std::make_shared<const exon::SharedUtf8>(scan->bam_dict_view.names);
+    else if (bed && c == 0) dicts[(size_t)c] = std::make_shared<const exon::SharedUtf8>(bed_names);
+    else if (bed && c == bed_strand) dicts[(size_t)c] = std::make_shared<const exon::SharedUtf8>(exon::gff_strand_names());
+    else if (!vcf_like && !gff && !bed && c == 2) dicts[(size_t)c] = std::make_shared<const exon::SharedUtf8>(scan->bam_dict_view.names);
   }
+  // BED: `kids` holds the fixed-width columns and then the name; the schema wants name in front of score and strand, and the NULL columns
+  // behind them.  null_of(c, n): n NULL rows of schema column c
+  auto bed_order = [&](std::vector<struct ArrowArray*>* kids, int64_t n, const std::function<struct ArrowArray*(int, int64_t)>& null_of) {
+    std::vector<struct ArrowArray*> out(kids->begin(), kids->begin() + 3);
+    if (bed_proj & EXON_HIP_PROJECT_BED_NAME) out.push_back(kids->back());
+    if (bed_score >= 0) out.push_back((*kids)[(size_t)bed_score]);
+    if (bed_strand >= 0) out.push_back((*kids)[(size_t)bed_strand]);
+    for (int c = 6; c < 12; ++c)
+      if (bed_proj & (1ull << c)) out.push_back(null_of(c, n));
+    kids->swap(out);
+  };
   auto dict_of_col = [&](int c) -> struct ArrowArray* { return dicts[(size_t)c] ? exon::shared_utf8_array(dicts[(size_t)c]) : nullptr; };
   if (as_views) {
     struct Tm {
@@ -2472,7 +2552,7 @@ static int export_slab(exon_hip_scan* scan, const exon_hip_column* sc, int64_t n
       const double tv0 = now_s();
       // every array of the batch out of one allocation (exon::BatchArena): per column its array + its dictionary, the text
       // columns' lists + items, the struct itself
-      exon::BatchArena* arena = exon::new_batch_arena(2 * n_cols + 8 + 1, n_cols + 4, sb, text.sb, dicts_p);
+      exon::BatchArena* arena = exon::new_batch_arena(2 * n_cols + 8 + 1, n_cols + 12, sb, text.sb, dicts_p);
       for (int c = 0; c < n_cols; ++c) {
         const void* bits = has_bits[(size_t)c] ? blk + boff[(size_t)c] : nullptr;
         const void* vals = elem[(size_t)c] ? (const void*)(blk + voff[(size_t)c]) : bits;  // a Flag: true where present
@@ -2481,7 +2561,12 @@ static int export_slab(exon_hip_scan* scan, const exon_hip_column* sc, int64_t n
       }
       const double tv1 = now_s();
       g_t_views += tv1 - tv0;
-      if (text.vcf || text.bam || text.bcf || text.gff || text.gtf) text_batch(text, nullptr, b0, n, &kids, arena);
+      if (text.vcf || text.bam || text.bcf || text.gff || text.gtf || text.bed) text_batch(text, nullptr, b0, n, &kids, arena);
+      if (bed)  // (a NULL column: every buffer the same zeros; Utf8 has three of them)
+        bed_order(&kids, n, [&](int c, int64_t m) {
+          const bool utf8 = exon::bed_fields()[c].fmt[0] == 'u';
+          return exon::arena_array(arena, m, 0, m, utf8 ? 3 : 2, blk + zoff, blk + zoff, utf8 ? blk + zoff : nullptr);
+        });
       g_t_text_batch += now_s() - tv1;
       struct ArrowArray* out = static_cast<struct ArrowArray*>(malloc(sizeof *out));
       exon::make_struct_of_arena(out, n, arena, kids);
@@ -2524,7 +2609,8 @@ static int export_slab(exon_hip_scan* scan, const exon_hip_column* sc, int64_t n
         kids.push_back(a);
       }
     }
-    if (text.vcf || text.bam || text.bcf || text.gff || text.gtf) text_batch(text, keep.data() + b0, 0, n, &kids);
+    if (text.vcf || text.bam || text.bcf || text.gff || text.gtf || text.bed) text_batch(text, keep.data() + b0, 0, n, &kids);
+    if (bed) bed_order(&kids, n, [](int c, int64_t m) { return exon::bed_null_column(c, (size_t)m); });
     struct ArrowArray* out = static_cast<struct ArrowArray*>(malloc(sizeof *out));
     exon::make_struct(out, n, std::move(kids));
     if (const int rc = push_batch(ex, out, n)) return rc;
@@ -2605,6 +2691,7 @@ static int64_t data_offset(const exon_hip_scan* scan) {
     case EXON_HIP_FORMAT_SAM: return scan->sam()->data_offset();
     case EXON_HIP_FORMAT_GFF:
     case EXON_HIP_FORMAT_GTF: return scan->gff()->data_offset();  // (no header: '#' lines are the device parser's to skip)
+    case EXON_HIP_FORMAT_BED: return scan->bed()->data_offset();
   }
   return 0;  // FASTQ: no header
 }
@@ -2617,6 +2704,7 @@ static std::unique_ptr<exon::ByteSource> take_text_stream(exon_hip_scan* scan, s
     case EXON_HIP_FORMAT_FASTQ: return scan->fastq()->take_stream(carry);
     case EXON_HIP_FORMAT_GFF:
     case EXON_HIP_FORMAT_GTF: return scan->gff()->take_stream(carry);
+    case EXON_HIP_FORMAT_BED: return scan->bed()->take_stream(carry);
   }
   return nullptr;  // (BAM and BCF are BGZF by definition)
 }
@@ -2686,8 +2774,16 @@ static int create_parser(exon_hip_scan* scan, exon_hip_ctx* ctx, int64_t max_tex
       if (!rc && scan->gtf()) rc = exon_hip_gff_parser_set_dialect(h, EXON_HIP_FORMAT_GTF);
       break;
     }
+    case EXON_HIP_FORMAT_BED: {  // seeded with the names interned so far (a region plan's contig): their ids stay
+      std::vector<const char*> names;
+      for (const auto& c : scan->bed()->dict.names) names.push_back(c.c_str());
+      exon_hip_bed_parser* h = nullptr;
+      rc = exon_hip_bed_parser_create(ctx, names.data(), (int32_t)names.size(), max_text_bytes, &h);
+      p.h = h;
+      break;
+    }
   }
-  p.owns_names = p.h && (scan->vcf_like() || scan->gff());
+  p.owns_names = p.h && (scan->vcf_like() || scan->gff() || scan->bed());
   return rc;
 }
 
@@ -2797,6 +2893,27 @@ static int parse_slab(exon_hip_scan* scan, hipStream_t hs, const uint8_t* d_text
       p->c_start = p->c_end = cols.start;
       return EXON_HIP_OK;
     }
+    case EXON_HIP_FORMAT_BED: {  // (a fused plan reads the three operand columns: the line kernel then builds nothing else)
+      exon_hip_bed_columns cols;
+      rc = exon_hip_bed_parser_parse(scan->parser.as<exon_hip_bed_parser>(), hs, d_text, (int64_t)n, &cols);
+      if (rc) return rc;
+      p->n_undecided = cols.n_undecided;
+      p->consumed = cols.consumed_bytes;
+      p->n_rows = cols.n_rows;
+      sc[0].values = cols.chrom_id;
+      sc[1].values = cols.start;
+      sc[2].values = cols.end;
+      int k = 3;  // batches: score and strand behind them, when projected (export_slab knows the order)
+      if (scan->exporter && (scan->opt.projection & EXON_HIP_PROJECT_BED_SCORE)) {
+        sc[k].values = cols.score;
+        sc[k++].validity = cols.score_valid;
+      }
+      if (scan->exporter && (scan->opt.projection & EXON_HIP_PROJECT_BED_STRAND)) {
+        sc[k].values = cols.strand_id;
+        sc[k++].validity = cols.strand_valid;
+      }
+      return EXON_HIP_OK;
+    }
     default: {  // FASTQ
       rc = exon_hip_fastq_parser_parse(scan->parser.as<exon_hip_fastq_parser>(), hs, d_text, (int64_t)n, final ? 1 : 0, &p->views);
       if (rc) return rc;
@@ -2838,6 +2955,15 @@ static int build_text(exon_hip_scan* scan, exon_hip_ctx* ctx, hipStream_t hs, co
       if (!off || !len || !text) return fail(ctx, EXON_HIP_ESTATE, "GFF attributes: the slab was parsed without its ninth fields recorded");
       if (scan->gtf()) r = exon_text_gtf(ctx, hs, &scan->text_scratch, text, text_bytes, off, len, n_rows, &t->gtf, &undecided);
       else r = exon_text_gff(ctx, hs, &scan->text_scratch, text, text_bytes, off, len, n_rows, &t->gff, &undecided);
+      break;
+    }
+    case EXON_HIP_FORMAT_BED: {
+      const uint8_t *text = nullptr, *valid = nullptr;
+      int64_t text_bytes = 0;
+      const uint32_t *off = nullptr, *len = nullptr;
+      exon_hip_bed_parser_name_fields(scan->parser.as<exon_hip_bed_parser>(), &text, &text_bytes, &off, &len, &valid);
+      if (!off || !len || !valid || !text) return fail(ctx, EXON_HIP_ESTATE, "BED names: the slab was parsed without its names recorded");
+      r = exon_text_bed(ctx, hs, &scan->text_scratch, text, text_bytes, off, len, valid, n_rows, &t->bed);
       break;
     }
   }
@@ -2934,6 +3060,10 @@ static int consume_text_gpu(exon_hip_stream* st, exon_hip_scan* scan, int64_t* r
       rc = exon_hip_gff_parser_want_attributes(scan->parser.as<exon_hip_gff_parser>(), scan->exporter && (scan->opt.projection & EXON_HIP_PROJECT_GFF_ATTRIBUTES) ? 1 : 0);
       if (rc) break;
     }
+    if (scan->bed()) {  // batches: score, strand and the names' places as projected; a fused plan: nothing but the operands
+      rc = exon_hip_bed_parser_want(scan->parser.as<exon_hip_bed_parser>(), scan->exporter ? scan->opt.projection : 0);
+      if (rc) break;
+    }
     if (si == 0) {
       t_init = now_s();
       if (trace) fprintf(stderr, "[exon-hip pipe] source init %.1f ms, parser create %.1f ms\n", (t_src - t_begin) * 1e3, (t_init - t_src) * 1e3);
@@ -2986,7 +3116,8 @@ static int consume_text_gpu(exon_hip_stream* st, exon_hip_scan* scan, int64_t* r
                                                 scan->d_region_mask, scan->d_region_pass));
           row_mask = scan->d_region_mask;
         }
-        if (scan->exporter && scan->opt.projection) {
+        // (BED: of its projection bits only `name` is a text column; the others are fixed-width or NULL)
+        if (scan->exporter && (scan->bed() ? (scan->opt.projection & EXON_HIP_PROJECT_BED_NAME) : scan->opt.projection)) {
           // the reference's string / list columns of this slab (by export_slab, once it knows that the slab keeps rows at all -- or,
           // GFF `attributes`, that it keeps none: every record's ninth field is validated)
           SlabText text;
@@ -3061,6 +3192,18 @@ static int consume_text_gpu(exon_hip_stream* st, exon_hip_scan* scan, int64_t* r
     }
     if (!rc && scan->exporter) scan->exporter->has_gff_names = true;
   }
+  if (rc == EXON_HIP_OK && scan->bed() && scan->parser.owns_names) {  // BED: the dictionary the device built -> scan
+    std::vector<std::string> names;
+    rc = gpu_bed_names(scan, &names, false);
+    if (!rc) {
+      if (scan->exporter) {
+        scan->exporter->final_gff_names[0].swap(names);
+        scan->exporter->has_gff_names = true;
+      } else {
+        scan->gpu_gff_dicts[0].names.swap(names);
+      }
+    }
+  }
   if (rc == EXON_HIP_OK) {
     if (scan->exporter) {
       scan->exporter->decoded_on_gpu = true;
@@ -3087,7 +3230,7 @@ static int consume_scan_impl(exon_hip_stream* st, exon_hip_scan* scan, int64_t* 
 
 // column of the scan that holds the contig / reference dictionary a region is named in
 static int region_dict_column(const exon_hip_scan* s) {
-  return (s->format == EXON_HIP_FORMAT_VCF || s->format == EXON_HIP_FORMAT_BCF || s->gff()) ? 0 : 2;
+  return (s->format == EXON_HIP_FORMAT_VCF || s->format == EXON_HIP_FORMAT_BCF || s->gff() || s->bed()) ? 0 : 2;
 }
 
 }  // extern "C"
@@ -3203,6 +3346,7 @@ static int gpu_next(exon_hip_scan* s, struct ArrowArray* out) {
     if (s->vcf_like()) s->gpu_filter_dict.names = s->host_filter_dict().names;
     if (exon::GFFBatchReader* g = s->gff())
       for (int k = 0; k < 3; ++k) s->gpu_gff_dicts[k].names = g->dicts[k].names;
+    if (exon::BEDBatchReader* b = s->bed()) s->gpu_gff_dicts[0].names = b->dict.names;
     ex->handed_over = false;
     ex->final_filters.clear();
     ex->final_info_names.clear();

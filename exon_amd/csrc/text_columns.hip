@@ -690,6 +690,20 @@ __global__ __launch_bounds__(TPB) void k_gtf_attr_fill(const uint8_t* __restrict
   }
 }
 
+// ---- BED `name` --------------------------------------------------------------------------------------------------------------------
+// The name column of a BED slab (host/bed.h: the field's bytes as they stand; NULL on 3- and 4-field lines).  The line kernel
+// (gpu_parse.hip, k_parse_bed_lines<true>) has recorded where every row's name lies, how long it is (0 where NULL) and the validity
+// bitmap, so there is nothing left to measure: the lengths are scanned into offsets and the fill copies the spans with
+// k_fastq_fill's 8-byte copier.  Every write is bounded by the buffer's size, whatever the capacity table says.
+__global__ __launch_bounds__(TPB) void k_bed_name_fill(const uint8_t* __restrict__ text, unsigned n_total, unsigned n_rows, const uint32_t* __restrict__ name_off,
+                                                       const int32_t* __restrict__ off, uint8_t* __restrict__ values, unsigned cap) {
+  const unsigned r = blockIdx.x * TPB + threadIdx.x;
+  if (r >= n_rows) return;
+  const unsigned at = (unsigned)off[r], n = (unsigned)(off[r + 1] - off[r]), src = name_off[r];
+  if (n == 0 || (uint64_t)at + n > cap || (uint64_t)src + n > n_total) return;  // (the last two: never, by the capacity table)
+  copy_run(values + at, text + src, n);
+}
+
 struct ExonTextScratch {
   PoolBufs bufs, qual_bufs;  // qual_bufs: the quality_scores values, grown on demand
   int64_t max_rows = 0, max_bytes = 0;
@@ -751,6 +765,8 @@ void exon_text_scratch_destroy(ExonTextScratch* s) { delete s; }
 //                    max_bytes / 2 + max_rows + 66: fits
 //          No GTF buffer is "checked".  exon_text_gtf still passes its totals through fits() and k_gtf_attr_fill bounds its writes:
 //          the derivation above is then not the only thing between a slab and the end of a buffer.
+//   BED    values[0] (max_bytes = n_bytes): the name fields, disjoint parts of the text: <= n_bytes: fits.  No BED buffer is "checked":
+//          the name bytes of a slab cannot exceed the slab.  k_bed_name_fill bounds its reads and writes all the same.
 // attr: 0, ATTR_GFF or ATTR_GTF -- the offset buffers of the map column
 enum { ATTR_NONE = 0, ATTR_GFF = 1, ATTR_GTF = 2 };
 static int scratch_for(exon_hip_ctx* ctx, ExonTextScratch** sp, int64_t max_rows, int64_t max_bytes, bool vcf, int n_cols = 3, int attr = ATTR_NONE) {
@@ -946,6 +962,29 @@ int exon_text_fastq(exon_hip_ctx* ctx, void* stream, ExonTextScratch** sp, const
     out->n_bytes[k] = s->h_totals[k];
   }
   out->desc_valid = reinterpret_cast<const uint8_t*>(s->valid[0]);
+  return EXON_HIP_OK;
+}
+
+int exon_text_bed(exon_hip_ctx* ctx, void* stream, ExonTextScratch** sp, const uint8_t* d_text, int64_t n_bytes, const uint32_t* d_name_off, const uint32_t* d_name_len,
+                  const uint8_t* d_name_valid, int64_t n_rows, ExonBedText* out) {
+  memset(out, 0, sizeof *out);
+  if (n_rows == 0) return EXON_HIP_OK;
+  int rc = scratch_for(ctx, sp, std::max<int64_t>(n_rows, 1 << 16), std::max<int64_t>(n_bytes, 1 << 20), false, 1);
+  if (rc) return rc;
+  ExonTextScratch* s = *sp;
+  hipStream_t hs = pick_stream(ctx, stream);
+  const unsigned n = (unsigned)n_rows;
+  const int nb = (int)((n + TPB - 1) / TPB);
+  scan_lengths(hs, s, d_name_len, n, s->off[0], s->totals);
+  hipLaunchKernelGGL(k_bed_name_fill, dim3(nb), dim3(TPB), 0, hs, d_text, (unsigned)n_bytes, n, d_name_off, s->off[0], s->values[0], (unsigned)std::min<size_t>(s->value_cap, 0xFFFFFFFFu));
+  HIP_TRY(ctx, hipGetLastError());
+  HIP_TRY(ctx, hipMemcpyAsync(s->h_totals, s->totals, 4, hipMemcpyDeviceToHost, hs));
+  HIP_TRY(ctx, hipStreamSynchronize(hs));
+  if (!fits(s, {s->h_totals[0]})) return fail(ctx, EXON_HIP_ESTATE, "BED names of %u bytes in a slab of %lld", s->h_totals[0], (long long)n_bytes);  // (never: the table above scratch_for)
+  out->name_offsets = s->off[0];
+  out->name_values = s->values[0];
+  out->name_valid = d_name_valid;
+  out->n_name_bytes = s->h_totals[0];
   return EXON_HIP_OK;
 }
 

@@ -397,14 +397,16 @@ class Scan:
 
     PROJECT = {"vcf": {"id": 1, "ref": 2, "alt": 4, "info": 8, "formats": 16}, "bam": {"name": 1, "cigar": 2, "sequence": 4, "quality_score": 8},
                "bcf": {"id": 1, "ref": 2, "alt": 4}, "sam": {"name": 1, "cigar": 2, "sequence": 4, "quality_score": 8},
-               "gff": {"attributes": 256}, "gtf": {"attributes": 256}}
+               "gff": {"attributes": 256}, "gtf": {"attributes": 256}, "bed": L.PROJECT_BED}
 
     def __init__(self, path, fmt, compression=None, batch_size=0, info_field=None, region=None, use_index=False,
                  gpu_parse=False, project=()):
         """project: names of the reference's columns beyond the fused kernels' operands (EXON_HIP_PROJECT_*): VCF "id", "ref", "alt",
         "info", "formats" (the last two as the reference's unparsed Utf8 columns; host reader only);
         BAM "name", "cigar", "sequence", "quality_score" -- appended behind the default columns in that order; GFF "attributes"
-        (the reference's Map<Utf8, List<Utf8>>, column 8); GTF "attributes" (the reference's Map<Utf8, Utf8>, column 8)."""
+        (the reference's Map<Utf8, List<Utf8>>, column 8); GTF "attributes" (the reference's Map<Utf8, Utf8>, column 8); BED "name",
+        "score", "strand", "thick_start", "thick_end", "color", "block_count", "block_sizes", "block_starts" (bits 3 .. 11: the
+        reference's n_fields = k is the first k - 3 of them), appended behind reference_sequence_name / start / end in that order."""
         self.lib = L.load()
         self.fmt = fmt
         mask = 0
@@ -658,6 +660,78 @@ class GFFParser:
     def close(self):
         if self.h:
             self.ctx.lib.exon_hip_gff_parser_destroy(self.h)
+            self.h = None
+
+
+class BEDParser:
+    """BED record parsing on the GPU (exon_hip_bed_parser_*): text slab in HBM -> the BED device layout in HBM.  The
+    reference_sequence_name dictionary grows across slabs; `seed_names` take the ids 0 .. len - 1 before the first slab."""
+
+    def __init__(self, ctx, seed_names=(), max_slab_bytes=64 << 20):
+        self.ctx = ctx
+        names = (C.c_char_p * max(len(seed_names), 1))(*[c.encode() for c in seed_names])
+        h = C.c_void_p()
+        ctx._check(ctx.lib.exon_hip_bed_parser_create(ctx.h, names, len(seed_names), max_slab_bytes, C.byref(h)))
+        self.h = h
+
+    def parse_device(self, d_text, n_bytes, stream=None):
+        cols = L.BEDColumns()
+        ptr = d_text.ptr if isinstance(d_text, DeviceBuffer) else int(d_text)
+        self.ctx._check(self.ctx.lib.exon_hip_bed_parser_parse(self.h, stream, ptr, n_bytes, C.byref(cols)))
+        return cols
+
+    def parse_host(self, text, misalign=0, projection=0, all_rows=False):
+        """Test helper: copy `text` to HBM (`misalign` bytes past a 16-byte boundary), parse, bring the columns back as numpy arrays
+        (none of them when the device left a row undecided).  projection: EXON_HIP_PROJECT_BED_* bits (exon_hip_bed_parser_want);
+        with name, score or strand among them also score / strand / their validity and res["names"], the rows' names (None where
+        NULL) cut from the slab by the device's (offset, length, validity).  0: the three operand columns alone.
+        all_rows: the columns of an undecided slab too (its decided rows hold their values; dictionary ids are provisional)."""
+        buf = np.frombuffer(text, np.uint8)
+        d = self.ctx.to_device(np.concatenate([np.full(misalign, 10, np.uint8), buf, np.zeros(64, np.uint8)]))
+        self.ctx._check(self.ctx.lib.exon_hip_bed_parser_want(self.h, projection))
+        cols = self.parse_device(d.ptr + misalign, len(buf))
+        n = cols.n_rows if cols.n_undecided == 0 or all_rows else 0
+        nb = (n + 7) // 8
+
+        def get(ptr, dtype, count):
+            out = np.empty(count, dtype)
+            if count:
+                self.ctx._check(self.ctx.lib.exon_hip_memcpy_d2h(self.ctx.h, _np_ptr(out), ptr, out.nbytes, None))
+            return out
+
+        res = {"n_rows": cols.n_rows, "n_undecided": cols.n_undecided, "consumed_bytes": cols.consumed_bytes, "projected": bool(cols.score)}
+        res["chrom_id"] = get(cols.chrom_id, np.int32, n)
+        for name in ("start", "end"):
+            res[name] = get(getattr(cols, name), np.int64, n)
+        if cols.score:
+            res["score"] = get(cols.score, np.int64, n)
+            res["strand_id"] = get(cols.strand_id, np.int32, n)
+            for name in ("score_valid", "strand_valid", "name_valid"):
+                res[name] = get(getattr(cols, name), np.uint8, nb)
+            off, ln = get(cols.name_off, np.uint32, n), get(cols.name_len, np.uint32, n)
+            skip = misalign % 16  # the offsets count from the aligned address at or below the slab
+            valid = np.unpackbits(res["name_valid"], bitorder="little")[:n].astype(bool)
+            raw = buf.tobytes()
+            res["name_len"] = ln
+            res["names"] = [raw[int(o) - skip:int(o) - skip + int(k)] if v else None for o, k, v in zip(off, ln, valid)]
+        return res
+
+    def names(self):
+        """The reference_sequence_name dictionary discovered so far, in id order."""
+        n = C.c_int32()
+        buf = C.create_string_buffer((1 << 20) + 4096)
+        self.ctx._check(self.ctx.lib.exon_hip_bed_parser_names(self.h, buf, len(buf), C.byref(n)))
+        names, o = [], 0
+        raw = buf.raw
+        for _ in range(n.value):
+            e = raw.index(b"\0", o)
+            names.append(raw[o:e].decode(errors="replace"))
+            o = e + 1
+        return names
+
+    def close(self):
+        if self.h:
+            self.ctx.lib.exon_hip_bed_parser_destroy(self.h)
             self.h = None
 
 

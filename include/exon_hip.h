@@ -448,6 +448,17 @@ int exon_hip_stream_close(exon_hip_stream* s);
  *         GTF projection bit is EXON_HIP_EUNSUPPORTED.  A region is the GFF reader's filter (seqname = name AND start inside
  *         the interval); use_index is EXON_HIP_EUNSUPPORTED (the reference has no indexed GTF table).  A '?' strand is an
  *         error (GFF3 reads it as NULL).  Plans address the columns as for GFF.
+ *   BED   0 reference_sequence_name(dict, built from the file, never NULL) 1 start:i64 2 end:i64 -- the interval kernels'
+ *         operands and nothing else: K2 (0, 1); K6 / K7 (0, 1, 2); a region's contig travels by name
+ *         (exon_hip_stream_set_region_contig) and is resolved in each file's dictionary, as for GFF.  The other columns of the
+ *         reference's schema (exon-bed/src/schema.rs:27-48) are EXON_HIP_PROJECT_BED_* bits, each bit the column's index there,
+ *         appended in bit order: 3 name Utf8?, 4 score i64?, 5 strand(dict ["+","-"])?, 6 thick_start i64?, 7 thick_end i64?,
+ *         8 color Utf8?, 9 block_count i64?, 10 block_sizes Utf8?, 11 block_starts Utf8? -- 6..11 are NULL on every row, as in
+ *         the reference, whose n_fields = k (table_options.rs:34-45) is the mask of bits 3 .. k - 1.  Any other bit is
+ *         EXON_HIP_EUNSUPPORTED.  A line is decoded by its own field count (3, 4, 5, 6 or 12; anything else is an error) and
+ *         validated in full whatever is projected; start and end are 0-based as they stand.  Rules and DECISIONs:
+ *         exon_amd/csrc/host/bed.h.  `region` and `use_index` are EXON_HIP_EUNSUPPORTED (the reference has neither for BED);
+ *         info_field must be NULL.
  * CPU-only: no ctx needed; errors are reported through exon_hip_last_error(NULL). */
 #define EXON_HIP_FORMAT_VCF 1
 #define EXON_HIP_FORMAT_BAM 2
@@ -456,8 +467,9 @@ int exon_hip_stream_close(exon_hip_stream* s);
 #define EXON_HIP_FORMAT_SAM 5 /* text SAM: same columns as BAM */
 #define EXON_HIP_FORMAT_BCF 6 /* BCF2: same columns as VCF */
 #define EXON_HIP_FORMAT_CRAM 7 /* CRAM 3.0 (raw / gzip / bzip2 / lzma / rANS 4x8 blocks), host decoder: same columns as BAM */
-#define EXON_HIP_FORMAT_GFF 8 /* GFF3 text (additive; the ABI stays 5): columns above; GTF is a format of its own, BED is not read */
+#define EXON_HIP_FORMAT_GFF 8 /* GFF3 text (additive; the ABI stays 5): columns above; GTF and BED are formats of their own */
 #define EXON_HIP_FORMAT_GTF 9 /* GTF text (additive; the ABI stays 5): columns above */
+#define EXON_HIP_FORMAT_BED 10 /* BED text (additive; the ABI stays 5): columns above */
 #define EXON_HIP_COMPRESSION_AUTO 0 /* sniff the gzip/BGZF magic */
 #define EXON_HIP_COMPRESSION_NONE 1
 #define EXON_HIP_COMPRESSION_GZIP 2
@@ -477,7 +489,7 @@ typedef struct exon_hip_scan_options {
                              INFO '.' makes all of them NULL (the struct itself is NULL in the reference) */
   const char* region;     /* pushed-down vcf_region_filter / bam_region_filter ("chr1:1-100"), NULL = none */
   int32_t use_index;      /* with `region`: plan BGZF chunks from <path>.tbi / <path>.bai (INDEXED_VCF / INDEXED_BAM / INDEXED_GFF) */
-  int32_t gpu_parse;      /* VCF, BCF, FASTQ, BAM, SAM, GFF, GTF: exon_hip_stream_consume_scan ships the file's bytes to HBM and decodes
+  int32_t gpu_parse;      /* VCF, BCF, FASTQ, BAM, SAM, GFF, GTF, BED: exon_hip_stream_consume_scan ships the file's bytes to HBM and decodes
                              them on the GPU (exon_hip_bgzf_inflate, exon_hip_vcf_parser_* / exon_hip_fastq_parser_* /
                              exon_hip_bam_parser_* ...).  exon_hip_scan_next on such a scan needs exon_hip_scan_bind_ctx first
                              (batches then come out of the same GPU pipeline); without a bound ctx it returns ESTATE */
@@ -496,7 +508,8 @@ typedef struct exon_hip_scan_options {
                              (exon-sam/src/array_builder.rs:101-185); both from the host readers and from the GPU pipeline.
                              GFF: attributes Map<Utf8, List<Utf8>> (exon-gff/src/array_builder.rs:141-165), bit 8 = the column's
                              index in the reference's schema; from the host reader and from the GPU pipeline.
-                             GTF: attributes Map<Utf8, Utf8> (exon-gtf/src/array_builder.rs:82-87), the same bit */
+                             GTF: attributes Map<Utf8, Utf8> (exon-gtf/src/array_builder.rs:82-87), the same bit.
+                             BED: bits 3 .. 11 = columns 3 .. 11 of the reference's schema (name .. block_starts) */
 } exon_hip_scan_options;
 #define EXON_HIP_PROJECT_VCF_ID 1ull
 #define EXON_HIP_PROJECT_VCF_REF 2ull
@@ -509,12 +522,22 @@ typedef struct exon_hip_scan_options {
 #define EXON_HIP_PROJECT_BAM_QUALITY_SCORES 8ull
 #define EXON_HIP_PROJECT_GFF_ATTRIBUTES 256ull /* (additive; the ABI stays 5) bit 8: `attributes` is column 8 of the reference's schema */
 #define EXON_HIP_PROJECT_GTF_ATTRIBUTES 256ull /* (additive) GTF's `attributes` is column 8 of the reference's schema too */
+/* (additive; the ABI stays 5) BED: bit k = column k of the reference's schema; n_fields = k is the mask of bits 3 .. k - 1 */
+#define EXON_HIP_PROJECT_BED_NAME (1ull << 3)
+#define EXON_HIP_PROJECT_BED_SCORE (1ull << 4)
+#define EXON_HIP_PROJECT_BED_STRAND (1ull << 5)
+#define EXON_HIP_PROJECT_BED_THICK_START (1ull << 6)
+#define EXON_HIP_PROJECT_BED_THICK_END (1ull << 7)
+#define EXON_HIP_PROJECT_BED_COLOR (1ull << 8)
+#define EXON_HIP_PROJECT_BED_BLOCK_COUNT (1ull << 9)
+#define EXON_HIP_PROJECT_BED_BLOCK_SIZES (1ull << 10)
+#define EXON_HIP_PROJECT_BED_BLOCK_STARTS (1ull << 11)
 
 int exon_hip_scan_open(const char* path, const exon_hip_scan_options* options, exon_hip_scan** out);
 int exon_hip_scan_schema(exon_hip_scan* scan, struct ArrowSchema* out);
 /* 0 = a batch was written to *out (caller releases or moves it); 1 = end of stream; <0 = error */
 int exon_hip_scan_next(exon_hip_scan* scan, struct ArrowArray* out);
-/* dictionary of a dict-encoded column (VCF 0/3, BAM 2, GFF and GTF 0/1/2/6/7): current size, and id of `name` (interned if new) */
+/* dictionary of a dict-encoded column (VCF 0/3, BAM 2, GFF and GTF 0/1/2/6/7, BED 0 and strand's column when projected): current size, and id of `name` (interned if new) */
 int exon_hip_scan_dictionary_size(exon_hip_scan* scan, int32_t column, int32_t* size);
 int exon_hip_scan_dictionary_intern(exon_hip_scan* scan, int32_t column, const char* name, int32_t* id);
 int exon_hip_scan_dictionary_value(exon_hip_scan* scan, int32_t column, int32_t id, const char** name);
@@ -784,6 +807,38 @@ typedef struct exon_hip_gtf_attributes {
 int exon_hip_gff_parser_set_dialect(exon_hip_gff_parser* parser, int32_t format);
 int exon_hip_gff_parser_gtf_attributes(exon_hip_gff_parser* parser, void* stream, exon_hip_gtf_attributes* out);
 int exon_hip_gff_parser_destroy(exon_hip_gff_parser* parser);
+
+/* ---- BED text parsing on the GPU (lines in HBM -> the BED device layout; additive, the ABI stays 5) ----
+ * Line rules of exon_amd/csrc/host/bed.h.  Lines that start with '#' are no rows.  reference_sequence_name becomes an id into a
+ * dictionary the parser builds across slabs (limits and `seed_names` as for the GFF parser).  Every line is validated in full.
+ * exon_hip_bed_parser_want(parser, projection) BEFORE a parse call: with any of EXON_HIP_PROJECT_BED_NAME / _SCORE / _STRAND the
+ * line kernel also writes score, strand and where every row's name lies; with 0 (the default: a fused plan) it writes the three
+ * operand columns and nothing else, and the other pointers of exon_hip_bed_columns are NULL.
+ * n_undecided != 0 (anything the rules call an error, a byte >= 0x80 anywhere in a line -- UTF-8 is the host's to validate --, a
+ * position of more than 18 digits, a ##FASTA line, a dictionary past its limits): decode the file on the host instead --
+ * errors are the host reader's to report. */
+typedef struct exon_hip_bed_parser exon_hip_bed_parser;
+typedef struct exon_hip_bed_columns {
+  int64_t n_rows, n_undecided, consumed_bytes; /* consumed: up to and including the last newline */
+  const int32_t* chrom_id;                     /* device pointers owned by the parser, overwritten by the next parse call */
+  const int64_t *start, *end;
+  const int64_t* score;
+  const uint8_t* score_valid;
+  const int32_t* strand_id; /* 0 "+", 1 "-" */
+  const uint8_t* strand_valid;
+  const uint32_t *name_off, *name_len; /* the name's bytes in the (16-byte aligned) slab `text`; length 0 where NULL */
+  const uint8_t* name_valid;
+  const uint8_t* text;
+} exon_hip_bed_columns;
+int exon_hip_bed_parser_create(exon_hip_ctx* ctx, const char* const* seed_names, int32_t n_seed, int64_t max_slab_bytes,
+                               exon_hip_bed_parser** out);
+int exon_hip_bed_parser_want(exon_hip_bed_parser* parser, uint64_t projection);
+/* d_text: '\n'-terminated lines, any alignment; a trailing partial line is left to the caller.  Synchronises `stream`. */
+int exon_hip_bed_parser_parse(exon_hip_bed_parser* parser, void* stream, const uint8_t* d_text, int64_t n_bytes,
+                              exon_hip_bed_columns* cols);
+/* the reference_sequence_name dictionary discovered so far, '\0'-separated in id order */
+int exon_hip_bed_parser_names(exon_hip_bed_parser* parser, char* buf, size_t cap, int32_t* n_names);
+int exon_hip_bed_parser_destroy(exon_hip_bed_parser* parser);
 
 /* ---- BCF2 record splitting + field extraction on the GPU (inflated BCF bytes in HBM -> the VCF device layout) ----
  * Same Arrow schema as VCF (exon-core/src/datasources/bcf/, exon-bcf); records are found like BAM's (parallel chain

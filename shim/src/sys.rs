@@ -36,6 +36,17 @@ pub const EXON_HIP_FORMAT_BCF: i32 = 6;
 pub const EXON_HIP_FORMAT_CRAM: i32 = 7;
 pub const EXON_HIP_FORMAT_GFF: i32 = 8;
 pub const EXON_HIP_FORMAT_GTF: i32 = 9;
+pub const EXON_HIP_FORMAT_BED: i32 = 10;
+// exon_hip_scan_options.projection of a BED scan: bit k = column k of the reference's schema (n_fields = k: bits 3 .. k - 1)
+pub const EXON_HIP_PROJECT_BED_NAME: u64 = 1 << 3;
+pub const EXON_HIP_PROJECT_BED_SCORE: u64 = 1 << 4;
+pub const EXON_HIP_PROJECT_BED_STRAND: u64 = 1 << 5;
+pub const EXON_HIP_PROJECT_BED_THICK_START: u64 = 1 << 6;
+pub const EXON_HIP_PROJECT_BED_THICK_END: u64 = 1 << 7;
+pub const EXON_HIP_PROJECT_BED_COLOR: u64 = 1 << 8;
+pub const EXON_HIP_PROJECT_BED_BLOCK_COUNT: u64 = 1 << 9;
+pub const EXON_HIP_PROJECT_BED_BLOCK_SIZES: u64 = 1 << 10;
+pub const EXON_HIP_PROJECT_BED_BLOCK_STARTS: u64 = 1 << 11;
 pub const EXON_HIP_PROJECT_GTF_ATTRIBUTES: u64 = 256; // exon_hip_scan_options.projection: GTF column 8, Map<Utf8, Utf8>
 pub const EXON_HIP_PROJECT_GFF_ATTRIBUTES: u64 = 256; // exon_hip_scan_options.projection: GFF column 8, Map<Utf8, List<Utf8>>
 pub const EXON_HIP_COMPRESSION_AUTO: i32 = 0;

@@ -5,6 +5,8 @@
 // `gen_text gff <rows> <out>` a GFF3 table sorted by (seqname, start), so that bgzip + a tabix index (GFF preset) serve it;
 // `gen_text gff <rows> <out> attrs` the same rows with rich ninth fields (every shape of the attribute rules, ASCII only).
 // `gen_text gtf <rows> <out> [attrs]` an Ensembl-like GTF table with the same (seqname, start) layout; attrs: rich ninth fields.
+// `gen_text bed <rows> <out> [n=6]` a BED table of n-field lines (3, 4, 5, 6 or 12; `mix`: all five, changing from row to row),
+// sorted by (reference_sequence_name, start); 0-based starts, scores 0 .. 65535, strands + - .
 // build: g++ -O2 -std=c++17 tools/gen_text.cpp -o tools/bin/gen_text      run: gen_text vcf <rows> <out.vcf>
 #include <cstdint>
 #include <cstdio>
@@ -15,7 +17,7 @@ static inline uint64_t mix64(uint64_t z) { z = (z ^ (z >> 30)) * 0xBF58476D1CE4E
 static inline uint64_t rnd(uint64_t seed, uint64_t col, uint64_t i) { return mix64(seed + col * 0xD1B54A32D192ED03ULL + (i + 1) * 0x9E3779B97F4A7C15ULL); }
 static inline uint32_t pct_thr(int p) { return (uint32_t)((((uint64_t)p) << 32) / 100); }
 int main(int argc, char** argv) {
-  if (argc < 4) { fprintf(stderr, "usage: gen_text vcf|bcf|fastq|bam|sam|gff|gtf <rows> <out> [read_len | attrs] [ragged]\n"); return 2; }
+  if (argc < 4) { fprintf(stderr, "usage: gen_text vcf|bcf|fastq|bam|sam|gff|gtf|bed <rows> <out> [read_len | attrs | n] [ragged]\n"); return 2; }
   const int64_t n = (int64_t)atof(argv[2]);
   FILE* f = fopen(argv[3], "wb");
   if (!f) return 1;
@@ -189,6 +191,51 @@ int main(int argc, char** argv) {
       }
       fprintf(f, "gene_id \"ENSG%011lld\"; transcript_id \"ENST%011lld\"; exon_number %u; gene_name \"G%u\"; gene_biotype \"%s\"; tag \"basic\"; tag \"CCDS\";\n",
               (long long)(i / 40), (long long)(i / 8), (unsigned)(i % 8) + 1, (unsigned)(b >> 40) & 0xFFFFu, BIOTYPES[(b >> 20) & 3]);
+    }
+    fclose(f);
+    return 0;
+  }
+  if (!strcmp(argv[1], "bed")) {
+    // the GFF mode's layout: 24 names in contiguous runs, starts ascending inside a run (the first of a run may be 0), names of 0 to
+    // 40 bytes ("." now and then), scores 0 .. 1000 and the two ends of u16, a '#' comment first and every 1000 rows so that most
+    // slabs are ranked; 12-field lines carry thick / colour / block fields as UCSC writes them (they are never read)
+    static const int COUNTS[5] = {3, 4, 5, 6, 12};
+    static const char STRAND[3] = {'+', '-', '.'};
+    const int NSEQ = 24;
+    const bool mix = argc > 4 && !strcmp(argv[4], "mix");
+    const int fixed = argc > 4 && !mix ? atoi(argv[4]) : 6;
+    if (!mix && fixed != 3 && fixed != 4 && fixed != 5 && fixed != 6 && fixed != 12) { fprintf(stderr, "gen_text bed: n is 3, 4, 5, 6, 12 or mix\n"); return 2; }
+    fputs("#chrom\tchromStart\tchromEnd\n", f);
+    for (int64_t i = 0; i < n; ++i) {
+      const uint64_t a = rnd(11, 0, (uint64_t)i), b = rnd(11, 1, (uint64_t)i);
+      const int seq = (int)((i * NSEQ) / n);
+      const int64_t first = ((int64_t)seq * n + NSEQ - 1) / NSEQ;  // the first row of this name's run
+      const int64_t start = (i - first) * 100 + (int64_t)(a % 100) - (i == first ? (int64_t)(a % 100) : 0), end = start + (int64_t)((a >> 8) % 5000);
+      const int nf = mix ? COUNTS[(b >> 50) % 5] : fixed;
+      char chrom[16];
+      if (seq < 22) snprintf(chrom, sizeof chrom, "chr%d", seq + 1);
+      else strcpy(chrom, seq == 22 ? "chrX" : "chrY");
+      if (i && i % 1000 == 0) fprintf(f, "# rows from %lld on\n", (long long)i);
+      fprintf(f, "%s\t%lld\t%lld", chrom, (long long)start, (long long)end);
+      if (nf >= 4) {
+        char name[64];
+        const int kind = (int)(b & 15);
+        if (kind == 0) strcpy(name, ".");
+        else if (kind == 1) name[0] = 0;
+        else {
+          const int len = snprintf(name, sizeof name, "NR_%06u_exon_%u_0_%s_%lld_%c", (unsigned)((b >> 8) % 1000000u), (unsigned)((b >> 28) % 40u), chrom, (long long)start + 1, (b & 16) ? 'f' : 'r');
+          if (kind == 2) name[len / 3] = 0;
+        }
+        fprintf(f, "\t%s", name);
+      }
+      if (nf >= 5) {
+        const unsigned k = (unsigned)((a >> 24) % 1003u);
+        fprintf(f, "\t%u", k == 1001 ? 65535u : k == 1002 ? 0u : k);
+      }
+      if (nf >= 6) fprintf(f, "\t%c", STRAND[(b >> 20) % 3]);
+      if (nf == 12) fprintf(f, "\t%lld\t%lld\t%u,%u,%u\t2\t%u,%u\t0,%u", (long long)start, (long long)end, (unsigned)(b >> 30) & 255u, (unsigned)(b >> 38) & 255u, (unsigned)(b >> 46) & 255u,
+                            (unsigned)(a >> 40) % 500u + 1, (unsigned)(a >> 50) % 500u + 1, (unsigned)(a >> 44) % 4000u + 600u);
+      fputc('\n', f);
     }
     fclose(f);
     return 0;
