@@ -112,6 +112,10 @@ class GFFAttributes(C.Structure):
                 ("list_offsets", C.c_void_p), ("item_offsets", C.c_void_p), ("item_values", C.c_void_p)]
 
 
+class VCFInfoText(C.Structure):
+    _fields_ = [("n_bytes", C.c_int64), ("n_undecided", C.c_int64), ("offsets", C.c_void_p), ("values", C.c_void_p)]
+
+
 class GTFAttributes(C.Structure):
     _fields_ = [("n_entries", C.c_int64), ("n_key_bytes", C.c_int64), ("n_value_bytes", C.c_int64), ("n_undecided", C.c_int64),
                 ("map_offsets", C.c_void_p), ("key_offsets", C.c_void_p), ("key_values", C.c_void_p),
@@ -235,6 +239,8 @@ SIGNATURES = {
     "exon_hip_vcf_parser_filters": (C.c_int, [_vp, C.c_char_p, C.c_size_t, C.POINTER(_i32)]),
     "exon_hip_vcf_parser_info_values": (C.c_int, [_vp, _i32, C.c_char_p, C.c_size_t, C.POINTER(_i32)]),
     "exon_hip_vcf_parser_set_null_key": (C.c_int, [_vp, _i32]),
+    "exon_hip_vcf_parser_set_key_types": (C.c_int, [_vp, C.c_char_p, C.c_char_p, _i32]),
+    "exon_hip_vcf_parser_info_text": (C.c_int, [_vp, _vp, C.POINTER(VCFInfoText)]),
     "exon_hip_vcf_parser_destroy": (C.c_int, [_vp]),
     "exon_hip_qual_pos_hist_chunks": (C.c_int, [_vp, _vp, _colp, _i32, _vp, _i32, _vp]),
     "exon_hip_qual_pos_hist_views": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp]),

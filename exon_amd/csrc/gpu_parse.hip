@@ -797,7 +797,15 @@ struct exon_hip_vcf_parser {
   int null_as_value = 0;  // exon_hip_vcf_parser_set_null_key: rows without a value of a String key take the id of the empty text
   int32_t h_str_stat[MAX_INFO][2] = {{0, 0}};  // per 's' key, last slab: {dictionary overflow, rows without a value}
   int32_t h_filter_stat = 0;                   // the FILTER dictionary's overflow flag after the last slab
-  explicit exon_hip_vcf_parser(exon_hip_ctx* c) : ctx(c), bufs(c) {}
+  // the `info` text column (exon_hip_vcf_parser_set_key_types / _info_text): the header's key types on the device, the slab of
+  // the last parse call as the caller passed it (last_rows < 0: none, or one with undecided rows) and the column's buffers
+  PoolBufs key_bufs;
+  ExonVcfKeyTable key_table{};
+  const uint8_t* last_text = nullptr;
+  int64_t last_bytes = 0, last_rows = -1;
+  ExonTextScratch* info_scratch = nullptr;
+  explicit exon_hip_vcf_parser(exon_hip_ctx* c) : ctx(c), bufs(c), key_bufs(c) {}
+  ~exon_hip_vcf_parser() { exon_text_scratch_destroy(info_scratch); }
 };
 
 extern "C" {
@@ -899,8 +907,11 @@ int exon_hip_vcf_parser_parse(exon_hip_vcf_parser* p, void* stream, const uint8_
   if (!p || !cols || (n_bytes > 0 && !d_text)) return fail(p ? p->ctx : nullptr, EXON_HIP_EINVAL, "exon_hip_vcf_parser_parse: NULL argument");
   exon_hip_ctx* ctx = p->ctx;
   memset(cols, 0, sizeof *cols);
+  p->last_rows = -1;
   if (n_bytes == 0) return EXON_HIP_OK;
   LineIndex& idx = p->idx;
+  const uint8_t* const text_given = d_text;
+  const int64_t bytes_given = n_bytes;
   unsigned skip;
   if (int rc = idx.align(ctx, &d_text, &n_bytes, &skip)) return rc;
   hipStream_t s = pick_stream(ctx, stream);
@@ -963,11 +974,41 @@ int exon_hip_vcf_parser_parse(exon_hip_vcf_parser* p, void* stream, const uint8_
       cols->list_item_valid[q] = p->info[q].item_bits;
     }
   }
+  if (cols->n_undecided == 0) {
+    p->last_text = text_given;
+    p->last_bytes = bytes_given;
+    p->last_rows = n_lines;
+  }
+  return EXON_HIP_OK;
+}
+
+int exon_hip_vcf_parser_set_key_types(exon_hip_vcf_parser* p, const char* packed_keys, const char* kinds, int32_t n) {
+  if (!p || n < 0 || (n > 0 && (!packed_keys || !kinds))) return fail(p ? p->ctx : nullptr, EXON_HIP_EINVAL, "exon_hip_vcf_parser_set_key_types: bad argument");
+  for (int32_t k = 0; k < n; ++k)
+    if (!strchr("ifbcs", kinds[k]) || !kinds[k]) return fail(p->ctx, EXON_HIP_EINVAL, "exon_hip_vcf_parser_set_key_types: kind '%c' of key %d (i f b c s)", kinds[k], k);
+  return exon_vcf_key_table_build(p->ctx, &p->key_bufs, packed_keys, kinds, n, &p->key_table);
+}
+
+int exon_hip_vcf_parser_info_text(exon_hip_vcf_parser* p, void* stream, exon_hip_vcf_info_text* out) {
+  if (!p || !out) return fail(p ? p->ctx : nullptr, EXON_HIP_EINVAL, "exon_hip_vcf_parser_info_text: NULL argument");
+  memset(out, 0, sizeof *out);
+  if (!p->key_table.hash) return fail(p->ctx, EXON_HIP_ESTATE, "exon_hip_vcf_parser_info_text: no key types (call exon_hip_vcf_parser_set_key_types first)");
+  if (p->last_rows < 0) return fail(p->ctx, EXON_HIP_ESTATE, "exon_hip_vcf_parser_info_text: no slab to build from (parse first; a slab with undecided rows has none)");
+  ExonVcfText t;
+  int64_t und = 0;
+  if (int rc = exon_text_vcf(p->ctx, stream, &p->info_scratch, p->last_text, p->last_bytes, p->idx.nl, p->last_rows, EXON_HIP_PROJECT_VCF_INFO, &p->key_table, &t, &und)) return rc;
+  HIP_TRY(p->ctx, hipStreamSynchronize(pick_stream(p->ctx, stream)));
+  out->n_undecided = und;
+  if (und) return EXON_HIP_OK;
+  out->n_bytes = t.n_info_bytes;
+  out->offsets = t.info_offsets;
+  out->values = t.info_values;
   return EXON_HIP_OK;
 }
 
 }  // extern "C"
 const unsigned* exon_hip_vcf_parser_newlines(exon_hip_vcf_parser* p) { return p ? p->idx.nl : nullptr; }
+const ExonVcfKeyTable* exon_hip_vcf_parser_key_table(exon_hip_vcf_parser* p) { return p ? &p->key_table : nullptr; }
 extern "C" {
 
 // a device-built dictionary (FILTER lists, or the values of a String INFO key) in id order: names '\0'-separated into `buf`.

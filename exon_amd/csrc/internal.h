@@ -65,7 +65,22 @@ struct ExonVcfText {
   const uint8_t* ref_values;
   int64_t n_ref_bytes;
   const uint8_t* alt_valid;        // bitmap: the ALT field is not '.' (the list itself has no items: see text_columns.hip)
+  const int32_t* info_offsets;     // [n_rows + 1]: `info`, the entries printed again (never NULL; "" for INFO '.')
+  const uint8_t* info_values;
+  int64_t n_info_bytes;
 };
+// the INFO key types of a VCF header on the device (text_columns.hip: exon_vcf_key_table_build, vcf_key_type): open addressing
+// by the key's 64-bit hash (0: an empty slot), the key's text verified; type: i f b c s
+struct ExonVcfKeyTable {
+  const unsigned long long* hash;
+  const uint32_t *off, *len;  // the key's text in `text`
+  const uint8_t *type, *text;
+  unsigned mask;              // slots - 1
+};
+class PoolBufs;
+int exon_vcf_key_table_build(exon_hip_ctx* ctx, PoolBufs* bufs, const char* keys, const char* kinds, int32_t n, ExonVcfKeyTable* out);
+// gpu_parse.hip: the table exon_hip_vcf_parser_set_key_types has made (hash == nullptr: none yet)
+const ExonVcfKeyTable* exon_hip_vcf_parser_key_table(exon_hip_vcf_parser* p);
 // BCF id / ref / alt through the reference's EAGER builder (eager_array_builder.rs:112-134): both lists carry their items, neither is
 // ever NULL (an empty list when the record has no id / no alternate bases)
 struct ExonBcfText {
@@ -83,8 +98,9 @@ struct ExonBamText {
 };
 // n_undecided != 0 (every exon_text_* that has it): nothing was built, the slab is the host reader's -- a total beyond what the
 // scratch buffers hold (IDs of many empty items, CIGARs of long ops; see scratch_for), or what the format's own note names
+// (VCF `info`, with EXON_HIP_PROJECT_VCF_INFO and info_keys: the rows text_columns.hip lists next to k_vcf_info_measure)
 int exon_text_vcf(exon_hip_ctx* ctx, void* stream, ExonTextScratch** scratch, const uint8_t* d_text, int64_t n_bytes, const unsigned* d_nl, int64_t n_rows, uint64_t projection,
-                  ExonVcfText* out, int64_t* n_undecided);
+                  const ExonVcfKeyTable* info_keys, ExonVcfText* out, int64_t* n_undecided);
 int exon_text_bam(exon_hip_ctx* ctx, void* stream, ExonTextScratch** scratch, const uint8_t* d_data, int64_t n_bytes, const uint32_t* d_rec_of_row, int64_t n_rows, uint64_t projection,
                   ExonBamText* out, int64_t* n_undecided);
 struct ExonFastqText {  // name, description, sequence, quality_scores (exon-fastq/src/config.rs:79-88), in that order

@@ -423,11 +423,12 @@ int exon_hip_scan_open(const char* path, const exon_hip_scan_options* o, exon_hi
         // a pushed-down region filter rides along as a row mask (k_region_mask); with use_index the host plans the
         // tabix chunks and only their BGZF blocks are shipped (indexed scans are BGZF by definition)
         s->gpu_parse = o->gpu_parse != 0 && (!rf.use_index || (rf.active && wants_gpu_inflate(o, path)));
-        // info / formats as text are the reference's re-printed entries (host/vcf_text.h: number formatting per header type):
-        // the host reader builds them, so such a scan decodes there
+        // info / formats as text are the reference's re-printed entries (host/vcf_text.h: number formatting per header type).
+        // info is printed on the device too (text_columns.hip: k_vcf_info_measure / k_vcf_info_fill); formats -- genotypes,
+        // per-sample walks -- is the host reader's, so a scan that asks for it decodes there
         if (o->projection & (EXON_HIP_PROJECT_VCF_INFO | EXON_HIP_PROJECT_VCF_FORMATS)) {
           s->gpu_candidate = s->gpu_parse;  // (a fused plan never reads them: exon_hip_stream_consume_scan may still decode on the device)
-          s->gpu_parse = false;
+          if (o->projection & EXON_HIP_PROJECT_VCF_FORMATS) s->gpu_parse = false;
         }
         if (reference_tail_quirk(rf)) s->gpu_parse = false;
         break;
@@ -2000,7 +2001,7 @@ struct Span {
   const T* begin() const { return p; }
 };
 struct HostText {
-  bool vcf = false, bam = false, bcf = false, gff = false, gtf = false, bed = false;  // bed: off[0] / val[0] / valid[0] the names
+  bool vcf = false, bam = false, bcf = false, gff = false, gtf = false, bed = false;  // bed: off[0] / val[0] / valid[0] the names; vcf: off[1] / val[1] `info`
   Span<int32_t> gtf_val_off;  // GTF attributes: off[0] = the map's offsets, key_off / val[0] the keys, gtf_val_off / val[1] the values
   uint64_t projection = 0;
   // GFF attributes: off[0] = the map's offsets, key_off / val[0] the keys, list_off the value lists, gff_item_off / val[1] their items
@@ -2064,6 +2065,10 @@ static int fetch_text(exon_hip_ctx* ctx, SlabCopier* cp, size_t also_reserve, in
     if (projection & EXON_HIP_PROJECT_VCF_ALT) {
       get(h->valid[1], vt->alt_valid, nb);
       if (big_batches) get(h->zeros, nullptr, n + 1);  // (no source: cleared below; batches of up to 65 000 rows share a static array)
+    }
+    if (projection & EXON_HIP_PROJECT_VCF_INFO) {  // off[1] / val[1]: free in a VCF slab (alt has no items)
+      get(h->off[1], vt->info_offsets, n + 1);
+      get(h->val[1], vt->info_values, (size_t)vt->n_info_bytes);
     }
   }
   if (t.format == EXON_HIP_FORMAT_BCF) {  // lists with their items, never NULL (eager_array_builder.rs:112-134)
@@ -2175,6 +2180,7 @@ static void text_batch(const HostText& h, const int64_t* rows, int64_t r0, int64
           kids->push_back(exon::arena_array(arena, n, r0 & 7, -1, 2, h.valid[1].data() + (r0 >> 3), k_zero_offsets, nullptr, items));
         }
       }
+      if (h.projection & EXON_HIP_PROJECT_VCF_INFO) kids->push_back(utf8_view(h.off[1], h.val[1], nullptr, r0, n));
     }
     if (h.bcf) {
       if (h.projection & EXON_HIP_PROJECT_VCF_ID) {
@@ -2250,6 +2256,7 @@ static void text_batch(const HostText& h, const int64_t* rows, int64_t r0, int64
       b.items.valid.clear();
       kids->push_back(b.finish());
     }
+    if (h.projection & EXON_HIP_PROJECT_VCF_INFO) kids->push_back(utf8(h.off[1], h.val[1], nullptr));
   }
   if (h.bcf) {
     auto list_of = [&](const Span<int32_t>& list_off, const Span<int32_t>& item_off, const Span<uint8_t>& val) {
@@ -2724,6 +2731,14 @@ static int create_parser(exon_hip_scan* scan, exon_hip_ctx* ctx, int64_t max_tex
       exon_hip_vcf_parser* h = nullptr;
       rc = exon_hip_vcf_parser_create(ctx, names.data(), (int32_t)names.size(), keys.empty() ? nullptr : keys.c_str(), max_text_bytes, &h);
       p.h = h;
+      if (!rc && (scan->opt.projection & EXON_HIP_PROJECT_VCF_INFO)) {  // the `info` text column: the header's value types for the device printer
+        std::string packed, kinds;
+        for (const auto& kv : scan->vcf()->key_types.info) {
+          packed.append(kv.first.c_str(), kv.first.size() + 1);
+          kinds += kv.second;
+        }
+        rc = exon_hip_vcf_parser_set_key_types(h, packed.data(), kinds.data(), (int32_t)kinds.size());
+      }
       break;
     }
     case EXON_HIP_FORMAT_BCF: {
@@ -2934,8 +2949,9 @@ static int build_text(exon_hip_scan* scan, exon_hip_ctx* ctx, hipStream_t hs, co
   int64_t undecided = 0;
   int r = EXON_HIP_OK;
   switch (scan->format) {
-    case EXON_HIP_FORMAT_VCF:  // undecided (here and for BAM, as for the other two): totals beyond what the scratch buffers hold
-      r = exon_text_vcf(ctx, hs, &scan->text_scratch, d_text, (int64_t)n, exon_hip_vcf_parser_newlines(scan->parser.as<exon_hip_vcf_parser>()), n_rows, proj, &t->vcf, &undecided);
+    case EXON_HIP_FORMAT_VCF:  // undecided (here and for BAM, as for the other two): totals beyond what the scratch buffers hold; `info`: a row the host reader must print or refuse
+      r = exon_text_vcf(ctx, hs, &scan->text_scratch, d_text, (int64_t)n, exon_hip_vcf_parser_newlines(scan->parser.as<exon_hip_vcf_parser>()), n_rows, proj,
+                        exon_hip_vcf_parser_key_table(scan->parser.as<exon_hip_vcf_parser>()), &t->vcf, &undecided);
       break;
     case EXON_HIP_FORMAT_BCF:  // undecided: an ID / allele that is not a typed string (the host reader reports what it is)
       r = exon_text_bcf(ctx, hs, &scan->text_scratch, d_text, (int64_t)n, exon_hip_bcf_parser_row_records(scan->parser.as<exon_hip_bcf_parser>()), n_rows, proj, &t->bcf, &undecided);

@@ -7,6 +7,7 @@
 //        alt        List<Utf8>: NULL when ALT is '.', otherwise a list with NO items -- the reference concatenates the alternate
 //                   bases into a local string and then calls `alternates.append(true)` without ever appending a value (:191-205);
 //                   reproduced as it is (results identical to the reference's), the quirk is written down in DESIGN.md
+//        info       Utf8: the parsed entries printed again, not the field's bytes ("AF=0.50" -> "AF=0.5")      :216-297
 //   BAM  name       Utf8, NULL for '*'                                exon-bam/src/array_builder.rs:105-113
 //        cigar      Utf8, "<len><op>..." with ops MIDNSHP=X           :144-167
 //        sequence   Utf8, 4-bit codes through "=ACMGRSVTWYHKDBN"      :178-183
@@ -23,6 +24,9 @@
 #include <initializer_list>
 #include <new>
 
+#include "host/decimal_f32.h"
+#include "host/f32_print.h"
+#include "host/vcf_text.h"
 #include "internal.h"
 #include "list_kernels.h"
 
@@ -704,8 +708,225 @@ __global__ __launch_bounds__(TPB) void k_bed_name_fill(const uint8_t* __restrict
   copy_run(values + at, text + src, n);
 }
 
+// ---- VCF `info` --------------------------------------------------------------------------------------------------------------------
+// The `info` Utf8 column (host/vcf_text.h: vcf_info_string / print_value / print_i32, restated): field 8 of the line, its entries
+// printed again.  "" for an empty field or "."; pieces split at ';' (empty ones skipped), a piece at its first '='; the type
+// comes from the key (ExonVcfKeyTable: the header's ##INFO lines over the reserved keys, a miss is String); a Flag prints
+// "key=true" whatever follows it; String values, and Character values without a comma, are copied; otherwise the items between
+// ',' are printed one by one -- "." as ".", except in a Character list, which drops it; an Integer through the i32 rules (sign,
+// digits, |v| <= 2^31 and v <= 2^31 - 1, printed without '+', leading zeros or "-0"); a Float through dec::parse_f32 and
+// f32p::print (host/decimal_f32.h, host/f32_print.h).
+// UNDECIDED (the row is counted, the file goes to the host reader, which prints it or raises with its own message): fewer than
+// eight fields; a key without a value ("key", "key=", "key=."); an integer print_i32 refuses; a float dec::parse_f32 leaves
+// open -- more than 19 significant digits, anything that is no plain decimal (the inf / infinity / nan spellings are NOT handed
+// over: vcf_f32_word takes them, they print "inf" / "-inf" / "NaN"); a byte >= 0x80 anywhere in the field: the host builder copies such bytes as they stand, and
+// whether they are UTF-8 is the host reader's to say, as for the GFF and GTF attributes.
+// Both kernels are instantiations of vcf_info_walk, which calls its emitter with what the row prints: the measure kernel's adds
+// lengths up, the fill kernel's writes into [offsets[r], offsets[r + 1]) and never outside it.  The measure kernel finds field 8
+// by the line's tabs (as k_vcf_measure finds fields 3 - 5; k_parse_lines is not touched) and leaves its place for the fill.
+__host__ __device__ __forceinline__ uint64_t vcf_key_hash(const uint8_t* p, unsigned n) {  // FNV-1a; never 0 (0 marks an empty slot)
+  uint64_t h = 0xcbf29ce484222325ull;
+  for (unsigned i = 0; i < n; ++i) h = (h ^ p[i]) * 0x100000001b3ull;
+  return h | (1ull << 63);
+}
+// the type of the key text[kb, kb + kn): by hash, then by the text (a key of the file may collide with one of the header)
+__device__ __forceinline__ unsigned vcf_key_type(const ExonVcfKeyTable& t, const uint8_t* __restrict__ text, unsigned kb, unsigned kn) {
+  const uint64_t h = vcf_key_hash(text + kb, kn);
+  for (unsigned slot = (unsigned)h & t.mask;; slot = (slot + 1) & t.mask) {  // (at most half of the slots are taken)
+    const uint64_t e = t.hash[slot];
+    if (e == 0) return 's';
+    if (e != h || t.len[slot] != kn) continue;
+    const uint8_t* k = t.text + t.off[slot];
+    unsigned i = 0;
+    while (i < kn && k[i] == text[kb + i]) ++i;
+    if (i == kn) return t.type[slot];
+  }
+}
+// [sign] (inf | infinity | nan) in any letter case, the spellings Rust's f32::from_str takes next to the decimals (the host
+// reader: VCFArrayBuilder::parse_f32); the sign of a NaN is kept and never printed
+__device__ __forceinline__ bool vcf_f32_word(const uint8_t* __restrict__ text, unsigned a, unsigned e, uint32_t* bits) {
+  uint32_t sign = 0;
+  if (a < e && (text[a] == '-' || text[a] == '+')) sign = text[a++] == '-' ? 0x80000000u : 0u;
+  const unsigned n = e - a;
+  if (n != 3 && n != 8) return false;
+  uint64_t w = 0;  // the letters, lower case, first one in the top byte
+  for (unsigned i = 0; i < n; ++i) w = w << 8 | (text[a + i] | 0x20u);
+  if (w == 0x696e66ull || w == 0x696e66696e697479ull) *bits = sign | 0x7F800000u;  // "inf", "infinity"
+  else if (w == 0x6e616eull) *bits = sign | 0x7FC00000u;                           // "nan"
+  else return false;
+  return true;
+}
+// true: the row is undecided (what has been emitted by then does not count)
+template <class Emit>
+__device__ __forceinline__ bool vcf_info_walk(const uint8_t* __restrict__ text, unsigned begin, unsigned end, const ExonVcfKeyTable& kt, Emit& em) {
+  if (end == begin || (end == begin + 1 && text[begin] == '.')) return false;
+  bool bad = false, first_entry = true;
+  for (unsigned i = begin; i < end && !bad;) {
+    unsigned j = i, eq = end;  // the piece [i, j), its first '=' (end: none)
+    for (; j < end; ++j) {
+      const unsigned c = text[j];
+      bad |= c >= 0x80u;
+      if (c == ';') break;
+      if (c == '=' && eq == end) eq = j;
+    }
+    if (j > i) {
+      const bool has_eq = eq != end;
+      if (!has_eq) eq = j;
+      const unsigned ty = vcf_key_type(kt, text, i, eq - i);
+      if (!first_entry) em.byte(';');
+      first_entry = false;
+      em.span(i, eq - i);
+      em.byte('=');
+      const unsigned vb = eq + 1, vl = has_eq ? j - vb : 0u, ve = vb + vl;
+      if (ty == 'b') {
+        em.word_true();
+      } else if (vl == 0 || (vl == 1 && text[vb] == '.')) {
+        bad = true;  // a missing value
+      } else {
+        bool comma = false;
+        if (ty == 'c')
+          for (unsigned k = vb; k < ve; ++k) comma |= text[k] == ',';
+        if (ty == 's' || (ty == 'c' && !comma)) {
+          em.span(vb, vl);
+        } else {
+          bool first_item = true;
+          for (unsigned a = vb; a <= ve && !bad;) {
+            unsigned e = a;
+            while (e < ve && text[e] != ',') ++e;
+            const bool dot = e - a == 1 && text[a] == '.';
+            if (!(dot && ty == 'c')) {
+              if (!first_item) em.byte(',');
+              first_item = false;
+              if (dot) {
+                em.byte('.');
+              } else if (ty == 'i') {
+                unsigned k = a;
+                bool neg = false;
+                if (k < e && (text[k] == '-' || text[k] == '+')) neg = text[k++] == '-';
+                bad |= k == e;
+                uint64_t v = 0;
+                for (; k < e; ++k) {
+                  const unsigned d = (unsigned)text[k] - (unsigned)'0';
+                  bad |= d > 9u;
+                  v = v * 10 + d;
+                  if (v > 0x80000000ull) v = 0x80000001ull;  // (out of range for good: print_i32 stops here)
+                }
+                bad |= v > 0x80000000ull || (!neg && v > 0x7FFFFFFFull);
+                if (!bad) em.i32(neg && v != 0, (uint32_t)v);
+              } else if (ty == 'f') {
+                uint32_t bits = 0;
+                if (exon::dec::parse_f32(reinterpret_cast<const char*>(text + a), (int)(e - a), &bits) || vcf_f32_word(text, a, e, &bits)) em.f32(bits);
+                else bad = true;
+              } else {
+                em.span(a, e - a);
+              }
+            }
+            a = e + 1;
+          }
+        }
+      }
+    }
+    i = j + 1;
+  }
+  return bad;
+}
+struct VcfInfoMeasure {
+  unsigned n = 0;
+  __device__ __forceinline__ void byte(unsigned) { ++n; }
+  __device__ __forceinline__ void span(unsigned, unsigned len) { n += len; }
+  __device__ __forceinline__ void word_true() { n += 4; }
+  __device__ __forceinline__ void i32(bool minus, uint32_t v) { n += (minus ? 1u : 0u) + dec_digits(v); }
+  __device__ __forceinline__ void f32(uint32_t bits) { n += (unsigned)exon::f32p::length(bits); }
+};
+// writes at dst[w ..); `lim` = the row's bytes by the offsets: nothing is written at or behind dst[lim]
+struct VcfInfoFill {
+  const uint8_t* __restrict__ text;
+  uint8_t* __restrict__ dst;
+  unsigned lim, w = 0;
+  __device__ __forceinline__ void byte(unsigned c) {
+    if (w < lim) dst[w] = (uint8_t)c;
+    ++w;
+  }
+  __device__ __forceinline__ void span(unsigned off, unsigned len) {
+    if (len <= lim && w <= lim - len) copy_run(dst + w, text + off, len);
+    w += len;
+  }
+  __device__ __forceinline__ void word_true() {
+    if (w + 4 <= lim) dst[w] = 't', dst[w + 1] = 'r', dst[w + 2] = 'u', dst[w + 3] = 'e';
+    w += 4;
+  }
+  __device__ __forceinline__ void i32(bool minus, uint32_t v) {
+    const unsigned nd = dec_digits(v), len = nd + (minus ? 1u : 0u);
+    if (len <= lim && w <= lim - len) {
+      if (minus) dst[w] = '-';
+      uint8_t* p = dst + w + (minus ? 1u : 0u);
+      for (unsigned i = nd; i > 0; --i) {
+        p[i - 1] = (uint8_t)('0' + v % 10);
+        v /= 10;
+      }
+    }
+    w += len;
+  }
+  __device__ __forceinline__ void f32(uint32_t bits) {
+    const unsigned len = (unsigned)exon::f32p::length(bits);
+    if (len <= lim && w <= lim - len) exon::f32p::print(bits, dst + w);
+    w += len;
+  }
+};
+// scal: [0, 1] the slab's printed bytes as one 64-bit sum (the u32 scan of the lengths may wrap), [2] undecided rows
+__global__ __launch_bounds__(TPB) void k_vcf_info_measure(const uint8_t* __restrict__ text, const unsigned* __restrict__ nl, unsigned n_rows, unsigned skip,
+                                                          ExonVcfKeyTable kt, uint32_t* __restrict__ field_off, uint32_t* __restrict__ field_len,
+                                                          uint32_t* __restrict__ out_len, unsigned* __restrict__ scal) {
+  const unsigned row = blockIdx.x * TPB + threadIdx.x;
+  bool bad = false;
+  unsigned printed = 0;
+  if (row < n_rows) {
+    const unsigned begin = row ? nl[row - 1] + 1 : skip;
+    unsigned end = nl[row];
+    if (end > begin && text[end - 1] == '\r') --end;
+    unsigned fb = begin, tabs = 0;  // field 8 starts behind the seventh tab ...
+    for (; fb < end && tabs < 7; ++fb) tabs += text[fb] == '\t';
+    unsigned fe = fb;  // ... and ends at the eighth or with the line
+    while (fe < end && text[fe] != '\t') ++fe;
+    bad = tabs < 7;  // fewer than eight fields: no data line
+    VcfInfoMeasure m;
+    if (!bad) bad = vcf_info_walk(text, fb, fe, kt, m);
+    printed = bad ? 0u : m.n;
+    field_off[row] = fb;
+    field_len[row] = bad ? 0u : fe - fb;
+    out_len[row] = printed;
+  }
+  unsigned long long sum = printed;
+  for (int d = 32; d > 0; d >>= 1) sum += __shfl_down(sum, d);
+  const unsigned long long bb = __ballot(bad);
+  if ((threadIdx.x & 63) == 0) {
+    if (sum) atomicAdd(reinterpret_cast<unsigned long long*>(scal), sum);
+    if (bb) atomicAdd(scal + 2, (unsigned)__popcll(bb));
+  }
+}
+// cap: the bytes `values` holds (the host has compared the total with it; a row that would reach past it writes nothing)
+__global__ __launch_bounds__(TPB) void k_vcf_info_fill(const uint8_t* __restrict__ text, unsigned n_rows, ExonVcfKeyTable kt, const uint32_t* __restrict__ field_off,
+                                                       const uint32_t* __restrict__ field_len, const int32_t* __restrict__ off, uint8_t* __restrict__ values,
+                                                       unsigned cap) {
+  const unsigned row = blockIdx.x * TPB + threadIdx.x;
+  if (row >= n_rows) return;
+  const unsigned at = (unsigned)off[row], n = (unsigned)(off[row + 1] - off[row]);
+  if (n == 0 || (uint64_t)at + n > cap) return;
+  VcfInfoFill f{text, values + at, n};
+  const unsigned fb = field_off[row];
+  vcf_info_walk(text, fb, fb + field_len[row], kt, f);
+}
+
 struct ExonTextScratch {
   PoolBufs bufs, qual_bufs;  // qual_bufs: the quality_scores values, grown on demand
+  // VCF `info`: per-row buffers (field place, printed length, offsets) for info_rows rows, the printed bytes (info_cap), both grown on demand
+  PoolBufs info_row_bufs, info_value_bufs;
+  size_t info_rows = 0, info_cap = 0;
+  uint32_t *info_field_off = nullptr, *info_field_len = nullptr, *info_len = nullptr;
+  int32_t* info_off = nullptr;
+  uint8_t* info_values = nullptr;
+  unsigned* info_scal = nullptr;    // device [4]: k_vcf_info_measure's scalars
+  unsigned* h_info_scal = nullptr;  // pinned
   int64_t max_rows = 0, max_bytes = 0;
   int n_cols = 3;
   uint32_t* len[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
@@ -726,7 +947,7 @@ struct ExonTextScratch {
   size_t qual_cap = 0;
   size_t value_cap = 0;  // bytes every values[k] holds
   size_t item_cap = 0;   // entries item_off / item_off2 hold
-  explicit ExonTextScratch(exon_hip_ctx* ctx) : bufs(ctx), qual_bufs(ctx) {}
+  explicit ExonTextScratch(exon_hip_ctx* ctx) : bufs(ctx), qual_bufs(ctx), info_row_bufs(ctx), info_value_bufs(ctx) {}
 };
 
 void exon_text_scratch_destroy(ExonTextScratch* s) { delete s; }
@@ -739,6 +960,10 @@ void exon_text_scratch_destroy(ExonTextScratch* s) { delete s; }
 //   VCF    values[2]: the REF fields, parts of the text: <= n_bytes: fits
 //   VCF    item_off: an ID field of k bytes is up to k + 1 items (k ';') and a line has a byte more than its ID (the LF): up to n_bytes
 //                    items + 1 entry, against max_bytes / 2 + max_rows + 66: checked
+//   VCF    info_values: the printed `info` entries, NOT bounded by the slab ("DB" prints "DB=true", "1e38" 39 digits: up to eight times
+//                    the field).  k_vcf_info_measure yields every row's exact length and their 64-bit sum; info_for grows the buffer to
+//                    the sum before the fill; a sum beyond INT32_MAX (int32 offsets), or a buffer that cannot be had, hands the slab
+//                    over; k_vcf_info_fill writes inside [offsets[r], offsets[r + 1]) and below the buffer's size only: checked
 //   BCF    values[0], [1], [2] (max_bytes = n_bytes): id / ref / alt, characters of typed strings inside the records: <= n_bytes each: fits
 //   BCF    item_off: a typed ID of k characters is up to k + 1 items behind a descriptor byte: up to n_bytes items + 1 entry: checked
 //   BCF    item_off2: an empty allele is its descriptor byte alone: up to n_bytes items + 1 entry: checked
@@ -853,11 +1078,110 @@ static void scan_lengths(hipStream_t hs, ExonTextScratch* s, const uint32_t* len
   hipLaunchKernelGGL(k_write_offsets, dim3(nb), dim3(LIST_TPB), 0, hs, len, n, s->sums, offsets);
 }
 
+// room for the `info` column of a slab of `rows` rows (bytes == 0) or for its `bytes` printed bytes: kept between slabs, the values
+// at least 1 MiB.  false: no memory (the caller hands the slab over)
+static bool info_for(ExonTextScratch* s, size_t rows, size_t bytes) {
+  if (bytes == 0 && s->info_rows < rows) {
+    s->info_row_bufs.release();
+    s->info_rows = 0;
+    const size_t r = rows + 64;
+    PoolBufs& b = s->info_row_bufs;
+    s->info_field_off = b.take<uint32_t>(r * 4);
+    s->info_field_len = b.take<uint32_t>(r * 4);
+    s->info_len = b.take<uint32_t>(r * 4);
+    s->info_off = b.take<int32_t>((r + 1) * 4);
+    s->info_scal = b.take<unsigned>(16);
+    s->h_info_scal = b.pinned<unsigned>(16);
+    if (b.status() != hipSuccess) {
+      (void)hipGetLastError();
+      b.release();
+      return false;
+    }
+    s->info_rows = rows;
+  }
+  if (bytes > s->info_cap) {
+    s->info_value_bufs.release();
+    s->info_cap = 0;
+    const size_t cap = std::max<size_t>(bytes + bytes / 4, (size_t)1 << 20);
+    s->info_values = s->info_value_bufs.take<uint8_t>(cap + 64);
+    if (!s->info_values) {
+      (void)hipGetLastError();
+      s->info_value_bufs.release();
+      return false;
+    }
+    s->info_cap = cap;
+  }
+  return true;
+}
+
+// the key types of a VCF header, flattened for the device: open addressing over a power of two of slots, at most half of them taken.
+// keys: n names, each with its NUL, back to back; kinds: their n type characters (i f b c s).  The first line of a key wins, as
+// in the host reader; the reserved keys of the specification follow with the types noodles falls back to (VcfKeyTypes::
+// reserved_info), unless the header has typed them.
+int exon_vcf_key_table_build(exon_hip_ctx* ctx, PoolBufs* bufs, const char* keys, const char* kinds, int32_t n, ExonVcfKeyTable* out) {
+  // (the names of VcfKeyTypes::reserved_info's three lists: that function is the authority on their types)
+  static const char* const reserved[] = {"AC", "AD", "ADF", "ADR", "AN", "DP", "END", "MQ0", "NS", "SB", "SVLEN", "CIPOS", "CIEND", "HOMLEN", "CILEN", "DPADJ",
+                                         "CN", "CNADJ", "CICN", "CICNADJ", "AF", "BQ", "MQ", "DB", "H2", "H3", "SOMATIC", "VALIDATED", "1000G", "IMPRECISE", "NOVEL"};
+  std::vector<std::pair<std::string, char>> entries;
+  const char* p = keys;
+  for (int32_t k = 0; k < n; ++k) {
+    entries.emplace_back(std::string(p), kinds[k]);
+    p += entries.back().first.size() + 1;
+  }
+  for (const char* r : reserved) entries.emplace_back(r, exon::VcfKeyTypes::reserved_info(r));
+  size_t slots = 64;
+  while (slots < 2 * entries.size()) slots *= 2;
+  std::vector<uint64_t> hash(slots, 0);
+  std::vector<uint32_t> off(slots, 0), len(slots, 0);
+  std::vector<uint8_t> type(slots, 0);
+  std::string text;
+  for (const auto& e : entries) {
+    const uint64_t h = vcf_key_hash(reinterpret_cast<const uint8_t*>(e.first.data()), (unsigned)e.first.size());
+    size_t slot = (size_t)h & (slots - 1);
+    bool known = false;
+    for (; hash[slot]; slot = (slot + 1) & (slots - 1))
+      if (hash[slot] == h && len[slot] == e.first.size() && text.compare(off[slot], len[slot], e.first) == 0) {
+        known = true;  // (an earlier line of the key, or the header's type of a reserved key)
+        break;
+      }
+    if (known) continue;
+    hash[slot] = h;
+    off[slot] = (uint32_t)text.size();
+    len[slot] = (uint32_t)e.first.size();
+    type[slot] = (uint8_t)e.second;
+    text += e.first;
+  }
+  hipSetDevice(ctx->device);
+  bufs->release();
+  unsigned long long* d_hash = bufs->take<unsigned long long>(slots * 8);
+  uint32_t* d_off = bufs->take<uint32_t>(slots * 4);
+  uint32_t* d_len = bufs->take<uint32_t>(slots * 4);
+  uint8_t* d_type = bufs->take<uint8_t>(slots);
+  uint8_t* d_text = bufs->take<uint8_t>(text.size() + 16);
+  bufs->upload(d_hash, hash.data(), slots * 8);
+  bufs->upload(d_off, off.data(), slots * 4);
+  bufs->upload(d_len, len.data(), slots * 4);
+  bufs->upload(d_type, type.data(), slots);
+  bufs->upload(d_text, text.data(), text.size());
+  if (bufs->status() != hipSuccess) {
+    const std::string msg = hipGetErrorString(bufs->status());
+    (void)hipGetLastError();
+    bufs->release();
+    memset(out, 0, sizeof *out);
+    return fail(ctx, EXON_HIP_ENOMEM, "the INFO key types of a VCF header (%zu keys): %s", entries.size(), msg.c_str());
+  }
+  *out = ExonVcfKeyTable{d_hash, d_off, d_len, d_type, d_text, (unsigned)(slots - 1)};
+  return EXON_HIP_OK;
+}
+
 int exon_text_vcf(exon_hip_ctx* ctx, void* stream, ExonTextScratch** sp, const uint8_t* d_text, int64_t n_bytes, const unsigned* d_nl, int64_t n_rows, uint64_t projection,
-                  ExonVcfText* out, int64_t* n_undecided) {
+                  const ExonVcfKeyTable* info_keys, ExonVcfText* out, int64_t* n_undecided) {
   memset(out, 0, sizeof *out);
   *n_undecided = 0;
-  if (n_rows == 0 || !(projection & (EXON_HIP_PROJECT_VCF_ID | EXON_HIP_PROJECT_VCF_REF | EXON_HIP_PROJECT_VCF_ALT))) return EXON_HIP_OK;
+  const bool path3 = (projection & (EXON_HIP_PROJECT_VCF_ID | EXON_HIP_PROJECT_VCF_REF | EXON_HIP_PROJECT_VCF_ALT)) != 0;
+  const bool info = (projection & EXON_HIP_PROJECT_VCF_INFO) != 0;
+  if (n_rows == 0 || !(path3 || info)) return EXON_HIP_OK;
+  if (info && (!info_keys || !info_keys->hash)) return fail(ctx, EXON_HIP_ESTATE, "the VCF info column needs the header's key types (exon_hip_vcf_parser_set_key_types)");
   const unsigned skip = (unsigned)(reinterpret_cast<uintptr_t>(d_text) & 15);
   d_text -= skip;
   n_bytes += skip;
@@ -868,30 +1192,63 @@ int exon_text_vcf(exon_hip_ctx* ctx, void* stream, ExonTextScratch** sp, const u
   const unsigned n = (unsigned)n_rows;
   const int nb = (int)((n + TPB - 1) / TPB);
   VcfLens L{s->len[0], s->len[1], s->len[2], s->field_off, s->field_len};
-  hipLaunchKernelGGL(k_vcf_measure, dim3(nb), dim3(TPB), 0, hs, d_text, d_nl, n, skip, L, s->valid[0], s->valid[1]);
-  scan_lengths(hs, s, s->len[0], n, s->off[0], s->totals + 0);  // ID: list offsets
-  scan_lengths(hs, s, s->len[1], n, s->off[1], s->totals + 1);  // ID: byte offsets of every row's items
-  scan_lengths(hs, s, s->len[2], n, s->off[2], s->totals + 2);  // REF
-  HIP_TRY(ctx, hipMemcpyAsync(s->h_totals, s->totals, 16, hipMemcpyDeviceToHost, hs));
+  if (info) {
+    if (!info_for(s, (size_t)std::max<int64_t>(n_rows, 1 << 16), 0)) return fail(ctx, EXON_HIP_ENOMEM, "buffers for the info column of a slab (%lld rows)", (long long)n_rows);
+    HIP_TRY(ctx, hipMemsetAsync(s->info_scal, 0, 16, hs));
+    hipLaunchKernelGGL(k_vcf_info_measure, dim3(nb), dim3(TPB), 0, hs, d_text, d_nl, n, skip, *info_keys, s->info_field_off, s->info_field_len, s->info_len, s->info_scal);
+    scan_lengths(hs, s, s->info_len, n, s->info_off, s->totals + 3);
+    HIP_TRY(ctx, hipMemcpyAsync(s->h_info_scal, s->info_scal, 16, hipMemcpyDeviceToHost, hs));
+  }
+  if (path3) {
+    hipLaunchKernelGGL(k_vcf_measure, dim3(nb), dim3(TPB), 0, hs, d_text, d_nl, n, skip, L, s->valid[0], s->valid[1]);
+    scan_lengths(hs, s, s->len[0], n, s->off[0], s->totals + 0);  // ID: list offsets
+    scan_lengths(hs, s, s->len[1], n, s->off[1], s->totals + 1);  // ID: byte offsets of every row's items
+    scan_lengths(hs, s, s->len[2], n, s->off[2], s->totals + 2);  // REF
+    HIP_TRY(ctx, hipMemcpyAsync(s->h_totals, s->totals, 16, hipMemcpyDeviceToHost, hs));
+  }
   HIP_TRY(ctx, hipStreamSynchronize(hs));
-  const unsigned id_items = s->h_totals[0], id_bytes = s->h_totals[1], ref_bytes = s->h_totals[2];
-  if (!fits(s, {id_bytes, ref_bytes}, {id_items})) {  // (IDs of many empty items)
+  uint64_t info_bytes = 0;
+  if (info) {
+    if (s->h_info_scal[2]) {  // rows the host reader must print, or refuse
+      *n_undecided = s->h_info_scal[2];
+      return EXON_HIP_OK;
+    }
+    info_bytes = (uint64_t)s->h_info_scal[0] | (uint64_t)s->h_info_scal[1] << 32;
+    if (info_bytes > (uint64_t)INT32_MAX || !info_for(s, 0, (size_t)std::max<uint64_t>(info_bytes, 1))) {  // int32 offsets; no buffer of that size
+      *n_undecided = n_rows;
+      return EXON_HIP_OK;
+    }
+  }
+  const unsigned id_items = path3 ? s->h_totals[0] : 0u, id_bytes = path3 ? s->h_totals[1] : 0u, ref_bytes = path3 ? s->h_totals[2] : 0u;
+  if (path3 && !fits(s, {id_bytes, ref_bytes}, {id_items})) {  // (IDs of many empty items)
     *n_undecided = n_rows;
     return EXON_HIP_OK;
   }
-  hipLaunchKernelGGL(k_vcf_fill, dim3(nb), dim3(TPB), 0, hs, d_text, n, L, s->off[0], s->off[1], s->off[2], s->item_off, s->values[0], s->values[2], id_items, id_bytes);
-  if (id_items == 0) HIP_TRY(ctx, hipMemsetAsync(s->item_off, 0, 4, hs));
+  if (path3) {
+    hipLaunchKernelGGL(k_vcf_fill, dim3(nb), dim3(TPB), 0, hs, d_text, n, L, s->off[0], s->off[1], s->off[2], s->item_off, s->values[0], s->values[2], id_items, id_bytes);
+    if (id_items == 0) HIP_TRY(ctx, hipMemsetAsync(s->item_off, 0, 4, hs));
+  }
+  if (info)
+    hipLaunchKernelGGL(k_vcf_info_fill, dim3(nb), dim3(TPB), 0, hs, d_text, n, *info_keys, s->info_field_off, s->info_field_len, s->info_off, s->info_values,
+                       (unsigned)std::min<size_t>(s->info_cap, 0xFFFFFFFFu));
   HIP_TRY(ctx, hipGetLastError());
-  out->id_list_offsets = s->off[0];
-  out->id_valid = reinterpret_cast<const uint8_t*>(s->valid[0]);
-  out->id_item_offsets = s->item_off;
-  out->id_values = s->values[0];
-  out->n_id_items = id_items;
-  out->n_id_bytes = id_bytes;
-  out->ref_offsets = s->off[2];
-  out->ref_values = s->values[2];
-  out->n_ref_bytes = ref_bytes;
-  out->alt_valid = reinterpret_cast<const uint8_t*>(s->valid[1]);
+  if (path3) {
+    out->id_list_offsets = s->off[0];
+    out->id_valid = reinterpret_cast<const uint8_t*>(s->valid[0]);
+    out->id_item_offsets = s->item_off;
+    out->id_values = s->values[0];
+    out->n_id_items = id_items;
+    out->n_id_bytes = id_bytes;
+    out->ref_offsets = s->off[2];
+    out->ref_values = s->values[2];
+    out->n_ref_bytes = ref_bytes;
+    out->alt_valid = reinterpret_cast<const uint8_t*>(s->valid[1]);
+  }
+  if (info) {
+    out->info_offsets = s->info_off;
+    out->info_values = s->info_values;
+    out->n_info_bytes = (int64_t)info_bytes;
+  }
   return EXON_HIP_OK;
 }
 

@@ -402,7 +402,7 @@ class Scan:
     def __init__(self, path, fmt, compression=None, batch_size=0, info_field=None, region=None, use_index=False,
                  gpu_parse=False, project=()):
         """project: names of the reference's columns beyond the fused kernels' operands (EXON_HIP_PROJECT_*): VCF "id", "ref", "alt",
-        "info", "formats" (the last two as the reference's unparsed Utf8 columns; host reader only);
+        "info", "formats" (the last two as the reference's unparsed Utf8 columns; info from the GPU pipeline too, formats host reader only);
         BAM "name", "cigar", "sequence", "quality_score" -- appended behind the default columns in that order; GFF "attributes"
         (the reference's Map<Utf8, List<Utf8>>, column 8); GTF "attributes" (the reference's Map<Utf8, Utf8>, column 8); BED "name",
         "score", "strand", "thick_start", "thick_end", "color", "block_count", "block_sizes", "block_starts" (bits 3 .. 11: the
@@ -498,13 +498,17 @@ class Scan:
 class VCFParser:
     """VCF record parsing on the GPU (exon_hip_vcf_parser_*): text slab in HBM -> device-layout columns in HBM."""
 
-    def __init__(self, ctx, contigs, info_field=None, max_slab_bytes=64 << 20):
+    def __init__(self, ctx, contigs, info_field=None, max_slab_bytes=64 << 20, key_types=None):
+        """key_types: {INFO key: "i" | "f" | "b" | "c" | "s"} as the header's ##INFO lines type them, for the `info` text column
+        (parse_host(..., info_text=True)); {} = the reserved keys of the specification alone."""
         self.ctx = ctx
         names = (C.c_char_p * max(len(contigs), 1))(*[c.encode() for c in contigs])
         h = C.c_void_p()
         ctx._check(ctx.lib.exon_hip_vcf_parser_create(ctx.h, names, len(contigs), info_field.encode() if info_field else None,
                                                       max_slab_bytes, C.byref(h)))
         self.h = h
+        if key_types is not None:
+            self.set_key_types(key_types)
         self.has_info = bool(info_field)
         self.cap_items = max_slab_bytes // 2 + 1  # items a list key's buffers hold (exon_hip_vcf_parser_create)
 
@@ -514,9 +518,17 @@ class VCFParser:
         self.ctx._check(self.ctx.lib.exon_hip_vcf_parser_parse(self.h, stream, ptr, n_bytes, C.byref(cols)))
         return cols
 
-    def parse_host(self, text, misalign=0):
+    def set_key_types(self, key_types):
+        """The value types of the header's INFO keys (exon_hip_vcf_parser_set_key_types)."""
+        packed = b"".join(k.encode() + b"\0" for k in key_types)
+        kinds = "".join(key_types.values()).encode()
+        self.ctx._check(self.ctx.lib.exon_hip_vcf_parser_set_key_types(self.h, packed, kinds, len(key_types)))
+
+    def parse_host(self, text, misalign=0, info_text=False):
         """Test helper: copy `text` (bytes of complete lines) to HBM (`misalign` bytes past a 16-byte boundary), parse,
-        bring the columns back as numpy arrays."""
+        bring the columns back as numpy arrays.  info_text: the `info` Utf8 column too, printed on the device
+        (exon_hip_vcf_parser_info_text): res["info_text"] = {"n_bytes", "n_undecided"} + "offsets" / "values" when 0 rows are
+        undecided (nothing when the parse itself left rows undecided)."""
         buf = np.frombuffer(text, np.uint8)
         d = self.ctx.to_device(np.concatenate([np.full(misalign, 10, np.uint8), buf, np.zeros(64, np.uint8)]))
         cols = self.parse_device(d.ptr + misalign, len(buf))
@@ -550,6 +562,14 @@ class VCFParser:
                 elif kind != "b":
                     k["values"] = get(cols.infos[q], np.float32, n)
                 res["infos"].append(k)
+        if info_text and cols.n_undecided == 0 and n:
+            t = L.VCFInfoText()
+            self.ctx._check(self.ctx.lib.exon_hip_vcf_parser_info_text(self.h, None, C.byref(t)))
+            it = {"n_bytes": t.n_bytes, "n_undecided": t.n_undecided}
+            if t.n_undecided == 0:
+                it["offsets"] = get(t.offsets, np.int32, n + 1)
+                it["values"] = get(t.values, np.uint8, t.n_bytes)
+            res["info_text"] = it
         return res
 
     def filters(self):

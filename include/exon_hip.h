@@ -502,7 +502,11 @@ typedef struct exon_hip_scan_options {
                              VCF text also: info Utf8, formats Utf8 -- the unparsed forms of the reference's default schema, which
                              are the parsed entries PRINTED AGAIN, not the fields' bytes ("AF=0.50" -> "AF=0.5", a Flag ->
                              "DB=true", formats = keys TAB samples; lazy_array_builder.rs:216-297, :310-423; host/vcf_text.h).
-                             These two are built by the host reader only: a gpu_parse scan that asks for them decodes on the host.
+                             info comes from the host reader and from the GPU pipeline (text_columns.hip: k_vcf_info_measure /
+                             k_vcf_info_fill print the entries on the device; a row the device does not decide -- a missing
+                             value, an integer outside i32, a float of more than 19 significant digits, a byte >= 0x80
+                             -- hands the file to the host reader).  formats is built by the host reader only: a gpu_parse scan
+                             that asks for it decodes on the host.
                              BCF: id List<Utf8>, ref Utf8, alt List<Utf8> through the reference's EAGER builder (lists with their
                              items, never NULL: eager_array_builder.rs:112-134); SAM: the BAM columns from the line's fields
                              (exon-sam/src/array_builder.rs:101-185); both from the host readers and from the GPU pipeline.
@@ -514,8 +518,8 @@ typedef struct exon_hip_scan_options {
 #define EXON_HIP_PROJECT_VCF_ID 1ull
 #define EXON_HIP_PROJECT_VCF_REF 2ull
 #define EXON_HIP_PROJECT_VCF_ALT 4ull
-#define EXON_HIP_PROJECT_VCF_INFO 8ull
-#define EXON_HIP_PROJECT_VCF_FORMATS 16ull
+#define EXON_HIP_PROJECT_VCF_INFO 8ull     /* host reader and GPU pipeline (the entries are printed again on the device) */
+#define EXON_HIP_PROJECT_VCF_FORMATS 16ull /* host reader only: a gpu_parse scan that asks for it decodes on the host */
 #define EXON_HIP_PROJECT_BAM_NAME 1ull
 #define EXON_HIP_PROJECT_BAM_CIGAR 2ull
 #define EXON_HIP_PROJECT_BAM_SEQUENCE 4ull
@@ -647,6 +651,22 @@ int exon_hip_vcf_parser_info_values(exon_hip_vcf_parser* parser, int32_t key, ch
  * does with a nullable key.  exon_hip_stream_consume_scan switches it on (a fused plan cannot skip rows by a key's bitmap);
  * batches (exon_hip_scan_next) keep NULL as NULL.  In a keyed stream's dictionary the NULL group is the key "". */
 int exon_hip_vcf_parser_set_null_key(exon_hip_vcf_parser* parser, int32_t on);
+/* (additive; the ABI stays 5) The `info` Utf8 column of the reference's default schema, built on the device: every record's INFO
+ * entries printed again (see exon_hip_scan_options.projection).  set_key_types gives the parser the value types of the header's
+ * ##INFO lines: packed_keys = n key names, each with its NUL, back to back; kinds[k] = i (Integer), f (Float), b (Flag),
+ * c (Character) or s (String).  The first line of a key wins; the reserved keys of the specification keep their types unless the
+ * header names them; any other key is a String.  n = 0: the reserved keys alone.
+ * info_text, after a parse call without undecided rows and before the next one: offsets [n_rows + 1] and values [n_bytes] in
+ * HBM, owned by the parser and valid until its next call.  n_undecided != 0: rows the host reader must print or refuse (no
+ * buffers then).  Synchronises `stream`. */
+typedef struct exon_hip_vcf_info_text {
+  int64_t n_bytes;
+  int64_t n_undecided;
+  const int32_t* offsets;
+  const uint8_t* values;
+} exon_hip_vcf_info_text;
+int exon_hip_vcf_parser_set_key_types(exon_hip_vcf_parser* parser, const char* packed_keys, const char* kinds, int32_t n);
+int exon_hip_vcf_parser_info_text(exon_hip_vcf_parser* parser, void* stream, exon_hip_vcf_info_text* out);
 int exon_hip_vcf_parser_destroy(exon_hip_vcf_parser* parser);
 
 /* ---- BGZF inflate on the GPU (compressed blocks in HBM -> inflated bytes in HBM) ------------------------------------

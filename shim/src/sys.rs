@@ -49,6 +49,9 @@ pub const EXON_HIP_PROJECT_BED_BLOCK_SIZES: u64 = 1 << 10;
 pub const EXON_HIP_PROJECT_BED_BLOCK_STARTS: u64 = 1 << 11;
 pub const EXON_HIP_PROJECT_GTF_ATTRIBUTES: u64 = 256; // exon_hip_scan_options.projection: GTF column 8, Map<Utf8, Utf8>
 pub const EXON_HIP_PROJECT_GFF_ATTRIBUTES: u64 = 256; // exon_hip_scan_options.projection: GFF column 8, Map<Utf8, List<Utf8>>
+// exon_hip_scan_options.projection of a VCF scan: the reference's unparsed Utf8 columns (the parsed entries printed again)
+pub const EXON_HIP_PROJECT_VCF_INFO: u64 = 8; // from the host reader and, printed on the device, from the GPU pipeline
+pub const EXON_HIP_PROJECT_VCF_FORMATS: u64 = 16; // host reader only: a gpu_parse scan that asks for it decodes on the host
 pub const EXON_HIP_COMPRESSION_AUTO: i32 = 0;
 pub const EXON_HIP_MAX_GROUPS: i32 = 4096;
 pub const EXON_HIP_REGION_OPEN_END: i64 = i64::MAX;
