@@ -994,15 +994,16 @@ int exon_hip_vcf_parser_info_text(exon_hip_vcf_parser* p, void* stream, exon_hip
   memset(out, 0, sizeof *out);
   if (!p->key_table.hash) return fail(p->ctx, EXON_HIP_ESTATE, "exon_hip_vcf_parser_info_text: no key types (call exon_hip_vcf_parser_set_key_types first)");
   if (p->last_rows < 0) return fail(p->ctx, EXON_HIP_ESTATE, "exon_hip_vcf_parser_info_text: no slab to build from (parse first; a slab with undecided rows has none)");
-  ExonVcfText t;
+  ExonTextColumns t;
   int64_t und = 0;
   if (int rc = exon_text_vcf(p->ctx, stream, &p->info_scratch, p->last_text, p->last_bytes, p->idx.nl, p->last_rows, EXON_HIP_PROJECT_VCF_INFO, &p->key_table, &t, &und)) return rc;
   HIP_TRY(p->ctx, hipStreamSynchronize(pick_stream(p->ctx, stream)));
   out->n_undecided = und;
-  if (und) return EXON_HIP_OK;
-  out->n_bytes = t.n_info_bytes;
-  out->offsets = t.info_offsets;
-  out->values = t.info_values;
+  if (und || !t.n_roots) return EXON_HIP_OK;  // (a slab of no rows has no column)
+  const ExonTextNode& info = t.nodes[t.roots[0]];
+  out->n_bytes = info.n_values;
+  out->offsets = info.offsets;
+  out->values = static_cast<const uint8_t*>(info.values);
   return EXON_HIP_OK;
 }
 
@@ -1774,22 +1775,23 @@ int exon_hip_gff_parser_attributes(exon_hip_gff_parser* p, void* stream, exon_hi
   if (p->gtf) return fail(p->ctx, EXON_HIP_ESTATE, "exon_hip_gff_parser_attributes: the parser reads GTF (exon_hip_gff_parser_gtf_attributes builds its Map<Utf8, Utf8>)");
   if (p->last_rows < 0)
     return fail(p->ctx, EXON_HIP_ESTATE, "exon_hip_gff_parser_attributes: no slab to build from (call exon_hip_gff_parser_want_attributes, then parse; a slab with undecided rows has none)");
-  ExonGffText t;
+  ExonTextColumns t;
   int64_t und = 0;
   if (int rc = exon_text_gff(p->ctx, stream, &p->attr_scratch, p->last_text, p->last_bytes, p->d_attr_off, p->d_attr_len, p->last_rows, &t, &und)) return rc;
   HIP_TRY(p->ctx, hipStreamSynchronize(pick_stream(p->ctx, stream)));
   out->n_undecided = und;
-  if (und) return EXON_HIP_OK;
-  out->n_entries = t.n_entries;
-  out->n_items = t.n_items;
-  out->n_key_bytes = t.n_key_bytes;
-  out->n_item_bytes = t.n_item_bytes;
-  out->map_offsets = t.map_offsets;
-  out->key_offsets = t.key_offsets;
-  out->key_values = t.key_values;
-  out->list_offsets = t.list_offsets;
-  out->item_offsets = t.item_offsets;
-  out->item_values = t.item_values;
+  if (und || !t.n_roots) return EXON_HIP_OK;  // (a slab of no rows has no column)
+  const ExonTextNode &map = t.nodes[t.roots[0]], &entries = t.nodes[map.kid[0]], &keys = t.nodes[entries.kid[0]], &lists = t.nodes[entries.kid[1]], &items = t.nodes[lists.kid[0]];
+  out->n_entries = entries.length;
+  out->n_items = items.length;
+  out->n_key_bytes = keys.n_values;
+  out->n_item_bytes = items.n_values;
+  out->map_offsets = map.offsets;
+  out->key_offsets = keys.offsets;
+  out->key_values = static_cast<const uint8_t*>(keys.values);
+  out->list_offsets = lists.offsets;
+  out->item_offsets = items.offsets;
+  out->item_values = static_cast<const uint8_t*>(items.values);
   return EXON_HIP_OK;
 }
 
@@ -1807,20 +1809,21 @@ int exon_hip_gff_parser_gtf_attributes(exon_hip_gff_parser* p, void* stream, exo
   if (!p->gtf) return fail(p->ctx, EXON_HIP_ESTATE, "exon_hip_gff_parser_gtf_attributes: the parser reads GFF3 (exon_hip_gff_parser_set_dialect)");
   if (p->last_rows < 0)
     return fail(p->ctx, EXON_HIP_ESTATE, "exon_hip_gff_parser_gtf_attributes: no slab to build from (call exon_hip_gff_parser_want_attributes, then parse; a slab with undecided rows has none)");
-  ExonGtfText t;
+  ExonTextColumns t;
   int64_t und = 0;
   if (int rc = exon_text_gtf(p->ctx, stream, &p->attr_scratch, p->last_text, p->last_bytes, p->d_attr_off, p->d_attr_len, p->last_rows, &t, &und)) return rc;
   HIP_TRY(p->ctx, hipStreamSynchronize(pick_stream(p->ctx, stream)));
   out->n_undecided = und;
-  if (und) return EXON_HIP_OK;
-  out->n_entries = t.n_entries;
-  out->n_key_bytes = t.n_key_bytes;
-  out->n_value_bytes = t.n_value_bytes;
-  out->map_offsets = t.map_offsets;
-  out->key_offsets = t.key_offsets;
-  out->key_values = t.key_values;
-  out->value_offsets = t.value_offsets;
-  out->value_values = t.value_values;
+  if (und || !t.n_roots) return EXON_HIP_OK;  // (a slab of no rows has no column)
+  const ExonTextNode &map = t.nodes[t.roots[0]], &entries = t.nodes[map.kid[0]], &keys = t.nodes[entries.kid[0]], &values = t.nodes[entries.kid[1]];
+  out->n_entries = entries.length;
+  out->n_key_bytes = keys.n_values;
+  out->n_value_bytes = values.n_values;
+  out->map_offsets = map.offsets;
+  out->key_offsets = keys.offsets;
+  out->key_values = static_cast<const uint8_t*>(keys.values);
+  out->value_offsets = values.offsets;
+  out->value_values = static_cast<const uint8_t*>(values.values);
   return EXON_HIP_OK;
 }
 

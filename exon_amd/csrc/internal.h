@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "../../include/exon_hip.h"
+#include "host/text_nodes.h"
 #include "kernels.h"
 
 struct exon_hip_ctx {
@@ -53,22 +54,9 @@ const void* exon_hip_gpu_local_cpus(int device);  // scan.cpp: a cpu_set_t of th
 void exon_hip_run_on(const void* cpus);            // ... the calling thread's affinity set to it (host threads that feed the DMA engine)
 void exon_hip_prewarm_ctx(exon_hip_ctx* ctx);  // scan.cpp: the file pipelines' side streams and events, made with the context
 
-// text_columns.hip: the reference's string / list columns of a slab as Arrow buffers on the device (exon_hip_scan_options.projection)
+// text_columns.hip: the reference's string / list columns of a slab as Arrow buffers on the device (exon_hip_scan_options.projection).
+// Every exon_text_* describes what it built as ExonTextColumns (host/text_nodes.h): one root per projected column, in schema order.
 struct ExonTextScratch;
-struct ExonVcfText {
-  const int32_t* id_list_offsets;  // [n_rows + 1] -> items
-  const uint8_t* id_valid;         // bitmap: the ID field is not '.'
-  const int32_t* id_item_offsets;  // [n_id_items + 1] -> id_values
-  const uint8_t* id_values;
-  int64_t n_id_items, n_id_bytes;
-  const int32_t* ref_offsets;      // [n_rows + 1]
-  const uint8_t* ref_values;
-  int64_t n_ref_bytes;
-  const uint8_t* alt_valid;        // bitmap: the ALT field is not '.' (the list itself has no items: see text_columns.hip)
-  const int32_t* info_offsets;     // [n_rows + 1]: `info`, the entries printed again (never NULL; "" for INFO '.')
-  const uint8_t* info_values;
-  int64_t n_info_bytes;
-};
 // the INFO key types of a VCF header on the device (text_columns.hip: exon_vcf_key_table_build, vcf_key_type): open addressing
 // by the key's 64-bit hash (0: an empty slot), the key's text verified; type: i f b c s
 struct ExonVcfKeyTable {
@@ -81,72 +69,45 @@ class PoolBufs;
 int exon_vcf_key_table_build(exon_hip_ctx* ctx, PoolBufs* bufs, const char* keys, const char* kinds, int32_t n, ExonVcfKeyTable* out);
 // gpu_parse.hip: the table exon_hip_vcf_parser_set_key_types has made (hash == nullptr: none yet)
 const ExonVcfKeyTable* exon_hip_vcf_parser_key_table(exon_hip_vcf_parser* p);
-// BCF id / ref / alt through the reference's EAGER builder (eager_array_builder.rs:112-134): both lists carry their items, neither is
-// ever NULL (an empty list when the record has no id / no alternate bases)
-struct ExonBcfText {
-  const int32_t *id_list_offsets, *id_item_offsets, *ref_offsets, *alt_list_offsets, *alt_item_offsets;
-  const uint8_t *id_values, *ref_values, *alt_values;
-  int64_t n_id_items, n_id_bytes, n_ref_bytes, n_alt_items, n_alt_bytes;
-};
-struct ExonBamText {
-  const int32_t *name_offsets, *cigar_offsets, *seq_offsets;  // [n_rows + 1] each; seq_offsets are quality_scores' list offsets too
-  const uint8_t *name_values, *cigar_values, *seq_values, *name_valid;
-  const int64_t* qual_values;
-  int64_t n_name_bytes, n_cigar_bytes, n_seq_bytes;
-  const int32_t* qual_offsets;  // quality_scores' list offsets (BAM: = seq_offsets; SAM: its own, QUAL may be '*' next to a SEQ)
-  int64_t n_qual_items;
-};
 // n_undecided != 0 (every exon_text_* that has it): nothing was built, the slab is the host reader's -- a total beyond what the
 // scratch buffers hold (IDs of many empty items, CIGARs of long ops; see scratch_for), or what the format's own note names
 // (VCF `info`, with EXON_HIP_PROJECT_VCF_INFO and info_keys: the rows text_columns.hip lists next to k_vcf_info_measure)
+// VCF: id List<Utf8>? (validity: the ID field is not '.'), ref Utf8, alt List<Utf8>? (validity: ALT is not '.'; no offsets, no items:
+// see text_columns.hip), info Utf8 (the entries printed again; never NULL, "" for INFO '.')
 int exon_text_vcf(exon_hip_ctx* ctx, void* stream, ExonTextScratch** scratch, const uint8_t* d_text, int64_t n_bytes, const unsigned* d_nl, int64_t n_rows, uint64_t projection,
-                  const ExonVcfKeyTable* info_keys, ExonVcfText* out, int64_t* n_undecided);
+                  const ExonVcfKeyTable* info_keys, ExonTextColumns* out, int64_t* n_undecided);
+// BAM: name Utf8?, cigar Utf8, sequence Utf8, quality_scores List<Int64> over sequence's offsets (a record's qualities are as many as its bases)
 int exon_text_bam(exon_hip_ctx* ctx, void* stream, ExonTextScratch** scratch, const uint8_t* d_data, int64_t n_bytes, const uint32_t* d_rec_of_row, int64_t n_rows, uint64_t projection,
-                  ExonBamText* out, int64_t* n_undecided);
-struct ExonFastqText {  // name, description, sequence, quality_scores (exon-fastq/src/config.rs:79-88), in that order
-  const int32_t* offsets[4];  // [n_reads + 1] each
-  const uint8_t* values[4];
-  int64_t n_bytes[4];
-  const uint8_t* desc_valid;  // bitmap: the header has something behind its first space
-};
-// SAM lines (the parser's newline index) -> the same columns; n_undecided != 0: a line the device does not print the way the reader would
+                  ExonTextColumns* out, int64_t* n_undecided);
+// SAM lines (the parser's newline index) -> the same columns, quality_scores over offsets of its own (QUAL may be '*' next to a SEQ);
+// n_undecided != 0: a line the device does not print the way the reader would
 int exon_text_sam(exon_hip_ctx* ctx, void* stream, ExonTextScratch** scratch, const uint8_t* d_text, int64_t n_bytes, const unsigned* d_nl, int64_t n_rows, uint64_t projection,
-                  ExonBamText* out, int64_t* n_undecided);
-int exon_text_fastq(exon_hip_ctx* ctx, void* stream, ExonTextScratch** scratch, const exon_hip_fastq_views* views, int64_t n_bytes, ExonFastqText* out);
+                  ExonTextColumns* out, int64_t* n_undecided);
+// FASTQ: name, description? (validity: the header has something behind its first space), sequence, quality_scores, all Utf8
+// (exon-fastq/src/config.rs:79-88), in that order
+int exon_text_fastq(exon_hip_ctx* ctx, void* stream, ExonTextScratch** scratch, const exon_hip_fastq_views* views, int64_t n_bytes, ExonTextColumns* out);
+// BCF id / ref / alt through the reference's EAGER builder (eager_array_builder.rs:112-134): both lists carry their items, neither is
+// ever NULL (an empty list when the record has no id / no alternate bases)
 int exon_text_bcf(exon_hip_ctx* ctx, void* stream, ExonTextScratch** scratch, const uint8_t* d_data, int64_t n_bytes, const uint32_t* d_rec_of_row, int64_t n_rows, uint64_t projection,
-                  ExonBcfText* out, int64_t* n_undecided);
+                  ExonTextColumns* out, int64_t* n_undecided);
 // GFF `attributes` (Map<Utf8, List<Utf8>>, host/gff.h's ATTRIBUTE RULES): rows -> entries -> (key bytes | items -> item bytes),
-// bytes after percent-decoding.  d_text is the ALIGNED slab the parser indexed; d_attr_off / d_attr_len every row's ninth field
-// in it (k_parse_gff_lines<true>).  n_undecided != 0: a field with a byte >= 0x80 (raw or decoded: UTF-8 is the host's to
-// validate), a piece without '=', an empty piece other than the one behind a trailing ';', or more items than item_offsets holds
-struct ExonGffText {
-  const int32_t *map_offsets, *key_offsets, *list_offsets, *item_offsets;  // [n_rows + 1], [n_entries + 1] twice, [n_items + 1]
-  const uint8_t *key_values, *item_values;
-  int64_t n_entries, n_items, n_key_bytes, n_item_bytes;
-};
+// bytes after percent-decoding.  d_text is the ALIGNED slab the
+// parser indexed; d_attr_off / d_attr_len every row's ninth field in it (k_parse_gff_lines<true>).  n_undecided != 0: a field with a
+// byte >= 0x80 (raw or decoded: UTF-8 is the host's to validate), a piece without '=', an empty piece other than the one behind a
+// trailing ';', or more items than the items' offsets hold
 int exon_text_gff(exon_hip_ctx* ctx, void* stream, ExonTextScratch** scratch, const uint8_t* d_text, int64_t n_bytes, const uint32_t* d_attr_off, const uint32_t* d_attr_len,
-                  int64_t n_rows, ExonGffText* out, int64_t* n_undecided);
+                  int64_t n_rows, ExonTextColumns* out, int64_t* n_undecided);
 // GTF `attributes` (Map<Utf8, Utf8>, host/gtf.h's ATTRIBUTE RULES): rows -> entries -> (key bytes | value bytes), keys and values
-// spans of the text as they stand (quotes dropped).  d_text / d_attr_off / d_attr_len as for exon_text_gff (the line kernel of the
-// GTF dialect recorded them).  n_undecided != 0: a field with a byte >= 0x80, a missing closing quote, a key without a value, an
-// empty piece, or bytes other than spaces behind a closing quote
-struct ExonGtfText {
-  const int32_t *map_offsets, *key_offsets, *value_offsets;  // [n_rows + 1], [n_entries + 1] twice
-  const uint8_t *key_values, *value_values;
-  int64_t n_entries, n_key_bytes, n_value_bytes;
-};
+// spans of the text as they stand (quotes dropped).  d_text / d_attr_off / d_attr_len
+// as for exon_text_gff (the line kernel of the GTF dialect recorded them).  n_undecided != 0: a field with a byte >= 0x80, a missing
+// closing quote, a key without a value, an empty piece, or bytes other than spaces behind a closing quote
 int exon_text_gtf(exon_hip_ctx* ctx, void* stream, ExonTextScratch** scratch, const uint8_t* d_text, int64_t n_bytes, const uint32_t* d_attr_off, const uint32_t* d_attr_len,
-                  int64_t n_rows, ExonGtfText* out, int64_t* n_undecided);
+                  int64_t n_rows, ExonTextColumns* out, int64_t* n_undecided);
 // BED `name` (Utf8?, host/bed.h: the field's bytes as they stand, NULL on 3- and 4-field lines): d_text is the ALIGNED slab the
 // parser indexed; d_name_off / d_name_len every row's name in it (k_parse_bed_lines<true>; length 0 where NULL) and d_name_valid its
 // bitmap, which the column takes as it is.  Nothing here is undecided: the line kernel has judged every byte of the line
-struct ExonBedText {
-  const int32_t* name_offsets;  // [n_rows + 1]
-  const uint8_t *name_values, *name_valid;
-  int64_t n_name_bytes;
-};
 int exon_text_bed(exon_hip_ctx* ctx, void* stream, ExonTextScratch** scratch, const uint8_t* d_text, int64_t n_bytes, const uint32_t* d_name_off, const uint32_t* d_name_len,
-                  const uint8_t* d_name_valid, int64_t n_rows, ExonBedText* out);
+                  const uint8_t* d_name_valid, int64_t n_rows, ExonTextColumns* out);
 void exon_text_scratch_destroy(ExonTextScratch* s);
 // the parsers' own indexes the text columns are built from (valid until the next parse call)
 const unsigned* exon_hip_vcf_parser_newlines(exon_hip_vcf_parser* p);

@@ -25,6 +25,7 @@
 #include "host/gtf.h"
 #include "host/bed.h"
 #include "host/parallel.h"
+#include "host/text_export.h"
 #include "internal.h"
 
 // The device parser of a GPU-decoded scan: whichever handle its format uses, created by the scan's first GPU-parsed consume
@@ -1992,25 +1993,8 @@ void export_block_put(void* p, size_t bytes) {
 // consumer); with one the kept rows are gathered.  Returns 2 when the consumer has gone away (scan closed with batches left).
 // the projected string / list columns of a slab, copied back into ONE pinned block of the export pool (pageable destinations are
 // staged by the runtime at a tenth of the link's rate): per-batch arrays are cut out of these
-template <class T>
-struct Span {
-  const T* p = nullptr;
-  size_t n = 0;
-  const T& operator[](size_t i) const { return p[i]; }
-  const T* data() const { return p; }
-  const T* begin() const { return p; }
-};
 struct HostText {
-  bool vcf = false, bam = false, bcf = false, gff = false, gtf = false, bed = false;  // bed: off[0] / val[0] / valid[0] the names; vcf: off[1] / val[1] `info`
-  Span<int32_t> gtf_val_off;  // GTF attributes: off[0] = the map's offsets, key_off / val[0] the keys, gtf_val_off / val[1] the values
-  uint64_t projection = 0;
-  // GFF attributes: off[0] = the map's offsets, key_off / val[0] the keys, list_off the value lists, gff_item_off / val[1] their items
-  Span<int32_t> key_off, list_off, gff_item_off;
-  Span<int32_t> alt_item_off;  // BCF: off[1] = alt's list offsets, alt_item_off / val[1] its items
-  Span<int32_t> off[3], item_off, qual_off;  // qual_off: quality_scores' own list offsets (SAM), else off[2]
-  Span<uint8_t> val[3], valid[2];
-  Span<int64_t> qual;
-  Span<int32_t> zeros;  // n_rows + 1 zero offsets: the item-less `alt` lists
+  ExonTextColumns cols;  // the device-built columns with their buffers where they lie in the block (host/text_export.h: text_place)
   void* blk = nullptr;
   size_t blk_bytes = 0;
   exon::SharedBlock* sb = nullptr;  // the block, shared with the batches that are views into it
@@ -2019,123 +2003,17 @@ struct HostText {
 // EXON_HIP_PIPE_TRACE: where a slab's export spends its time (seconds; per producer thread: every scan's pipeline runs in its own)
 static thread_local double g_t_batches = 0, g_t_release = 0, g_t_text_batch = 0, g_t_views = 0;
 static thread_local double g_t_text_kernels = 0, g_t_fetch_text = 0, g_t_fetch_cols = 0, g_t_block_get = 0, g_t_enqueue = 0, g_t_names = 0;
-// (the copies go through `cp`: they have arrived when the slab's copy event has fired)
-// zero offsets for the item-less `alt` lists of a batch: every batch of up to K_ZERO_ROWS rows points at the same static array
-static constexpr int64_t K_ZERO_ROWS = 65000;
-static const int32_t k_zero_offsets[K_ZERO_ROWS + 64] = {0};
-// the projected text columns of one slab: `build` fills the member of `format` on the device (export_slab calls it once it knows
-// that the slab keeps rows at all; for GFF `attributes` also when it keeps none: the build is the validation of every ninth field)
+// the projected text columns of one slab: `build` describes them in `cols` once the device has built them (export_slab calls it once
+// it knows that the slab keeps rows at all; for GFF `attributes` also when it keeps none: the build is the validation of every ninth field)
 struct SlabText {
-  int format = 0;
-  ExonVcfText vcf;
-  ExonBamText bam;  // BAM and SAM
-  ExonBcfText bcf;
-  ExonGffText gff;
-  ExonGtfText gtf;
-  ExonBedText bed;
+  ExonTextColumns cols;
   std::function<int()> build;
 };
-static int fetch_text(exon_hip_ctx* ctx, SlabCopier* cp, size_t also_reserve, int64_t n_rows, uint64_t projection, const SlabText& t, HostText* h, bool big_batches) {
-  h->projection = projection;
-  struct Want {
-    std::function<void(const uint8_t*)> place;  // points the span at its bytes inside the block
-    const void* src;
-    size_t count, elem;
-  };
-  std::vector<Want> wants;
-  auto get = [&](auto& span, const void* src, size_t count) {
-    typedef typename std::remove_reference<decltype(*span.p)>::type T;
-    auto* sp = &span;
-    wants.push_back(Want{[sp, count](const uint8_t* at) { sp->p = reinterpret_cast<const T*>(at); sp->n = count; }, src, count, sizeof(T)});
-  };
-  const size_t n = (size_t)n_rows, nb = (n + 7) / 8;
-  if (t.format == EXON_HIP_FORMAT_VCF) {
-    const ExonVcfText* vt = &t.vcf;
-    h->vcf = true;
-    if (projection & EXON_HIP_PROJECT_VCF_ID) {
-      get(h->off[0], vt->id_list_offsets, n + 1);
-      get(h->valid[0], vt->id_valid, nb);
-      get(h->item_off, vt->id_item_offsets, (size_t)vt->n_id_items + 1);
-      get(h->val[0], vt->id_values, (size_t)vt->n_id_bytes);
-    }
-    if (projection & EXON_HIP_PROJECT_VCF_REF) {
-      get(h->off[2], vt->ref_offsets, n + 1);
-      get(h->val[2], vt->ref_values, (size_t)vt->n_ref_bytes);
-    }
-    if (projection & EXON_HIP_PROJECT_VCF_ALT) {
-      get(h->valid[1], vt->alt_valid, nb);
-      if (big_batches) get(h->zeros, nullptr, n + 1);  // (no source: cleared below; batches of up to 65 000 rows share a static array)
-    }
-    if (projection & EXON_HIP_PROJECT_VCF_INFO) {  // off[1] / val[1]: free in a VCF slab (alt has no items)
-      get(h->off[1], vt->info_offsets, n + 1);
-      get(h->val[1], vt->info_values, (size_t)vt->n_info_bytes);
-    }
-  }
-  if (t.format == EXON_HIP_FORMAT_BCF) {  // lists with their items, never NULL (eager_array_builder.rs:112-134)
-    const ExonBcfText* ct = &t.bcf;
-    h->bcf = true;
-    if (projection & EXON_HIP_PROJECT_VCF_ID) {
-      get(h->off[0], ct->id_list_offsets, n + 1);
-      get(h->item_off, ct->id_item_offsets, (size_t)ct->n_id_items + 1);
-      get(h->val[0], ct->id_values, (size_t)ct->n_id_bytes);
-    }
-    if (projection & EXON_HIP_PROJECT_VCF_REF) {
-      get(h->off[2], ct->ref_offsets, n + 1);
-      get(h->val[2], ct->ref_values, (size_t)ct->n_ref_bytes);
-    }
-    if (projection & EXON_HIP_PROJECT_VCF_ALT) {
-      get(h->off[1], ct->alt_list_offsets, n + 1);
-      get(h->alt_item_off, ct->alt_item_offsets, (size_t)ct->n_alt_items + 1);
-      get(h->val[1], ct->alt_values, (size_t)ct->n_alt_bytes);
-    }
-  }
-  if (t.format == EXON_HIP_FORMAT_BAM || t.format == EXON_HIP_FORMAT_SAM) {
-    const ExonBamText* bt = &t.bam;
-    h->bam = true;
-    if (projection & EXON_HIP_PROJECT_BAM_NAME) {
-      get(h->off[0], bt->name_offsets, n + 1);
-      get(h->val[0], bt->name_values, (size_t)bt->n_name_bytes);
-      get(h->valid[0], bt->name_valid, nb);
-    }
-    if (projection & EXON_HIP_PROJECT_BAM_CIGAR) {
-      get(h->off[1], bt->cigar_offsets, n + 1);
-      get(h->val[1], bt->cigar_values, (size_t)bt->n_cigar_bytes);
-    }
-    if (projection & (EXON_HIP_PROJECT_BAM_SEQUENCE | EXON_HIP_PROJECT_BAM_QUALITY_SCORES)) get(h->off[2], bt->seq_offsets, n + 1);
-    if (projection & EXON_HIP_PROJECT_BAM_SEQUENCE) get(h->val[2], bt->seq_values, (size_t)bt->n_seq_bytes);
-    if (projection & EXON_HIP_PROJECT_BAM_QUALITY_SCORES) {
-      get(h->qual, bt->qual_values, (size_t)bt->n_qual_items);
-      if (bt->qual_offsets != bt->seq_offsets) get(h->qual_off, bt->qual_offsets, n + 1);  // SAM: QUAL may be '*' next to a SEQ
-    }
-  }
-  if (t.format == EXON_HIP_FORMAT_GFF && (projection & EXON_HIP_PROJECT_GFF_ATTRIBUTES)) {
-    const ExonGffText* gt = &t.gff;
-    h->gff = true;
-    get(h->off[0], gt->map_offsets, n + 1);
-    get(h->key_off, gt->key_offsets, (size_t)gt->n_entries + 1);
-    get(h->val[0], gt->key_values, (size_t)gt->n_key_bytes);
-    get(h->list_off, gt->list_offsets, (size_t)gt->n_entries + 1);
-    get(h->gff_item_off, gt->item_offsets, (size_t)gt->n_items + 1);
-    get(h->val[1], gt->item_values, (size_t)gt->n_item_bytes);
-  }
-  if (t.format == EXON_HIP_FORMAT_GTF && (projection & EXON_HIP_PROJECT_GTF_ATTRIBUTES)) {
-    const ExonGtfText* gt = &t.gtf;
-    h->gtf = true;
-    get(h->off[0], gt->map_offsets, n + 1);
-    get(h->key_off, gt->key_offsets, (size_t)gt->n_entries + 1);
-    get(h->val[0], gt->key_values, (size_t)gt->n_key_bytes);
-    get(h->gtf_val_off, gt->value_offsets, (size_t)gt->n_entries + 1);
-    get(h->val[1], gt->value_values, (size_t)gt->n_value_bytes);
-  }
-  if (t.format == EXON_HIP_FORMAT_BED && (projection & EXON_HIP_PROJECT_BED_NAME)) {
-    h->bed = true;
-    get(h->off[0], t.bed.name_offsets, n + 1);
-    get(h->val[0], t.bed.name_values, (size_t)t.bed.n_name_bytes);
-    get(h->valid[0], t.bed.name_valid, nb);
-  }
-  size_t total = 64;
-  for (const Want& w : wants) total += (w.count * w.elem + 63) & ~(size_t)63;
-  if (!cp->reserve(total + 256 * wants.size() + also_reserve)) return fail(ctx, EXON_HIP_ENOMEM, "no device staging buffer of %zu bytes for a slab's string columns", total);
+// (the copies go through `cp`: they have arrived when the slab's copy event has fired)
+static int fetch_text(exon_hip_ctx* ctx, SlabCopier* cp, size_t also_reserve, const ExonTextColumns& dev, HostText* h, bool big_batches) {
+  const exon::TextPlan plan = exon::text_plan(dev, big_batches);
+  const size_t total = plan.total;
+  if (!cp->reserve(total + 256 * plan.copies.size() + also_reserve)) return fail(ctx, EXON_HIP_ENOMEM, "no device staging buffer of %zu bytes for a slab's string columns", total);
   h->blk_bytes = total;
   const double tb0 = now_s();
   h->blk = export_block_get(&h->blk_bytes);
@@ -2145,183 +2023,22 @@ static int fetch_text(exon_hip_ctx* ctx, SlabCopier* cp, size_t also_reserve, in
   h->sb->block = h->blk;
   h->sb->bytes = h->blk_bytes;
   h->sb->put = export_block_put;
-  size_t at = 0;
-  for (const Want& w : wants) {
-    uint8_t* dst = static_cast<uint8_t*>(h->blk) + at;
-    w.place(dst);
-    if (!w.src) memset(dst, 0, w.count * w.elem);
-    if (w.count && w.src) cp->add(dst, w.src, w.count * w.elem);
-    at += (w.count * w.elem + 63) & ~(size_t)63;
+  uint8_t* blk = static_cast<uint8_t*>(h->blk);
+  for (const exon::TextCopy& c : plan.copies) {
+    if (c.src) cp->add(blk + c.at, c.src, c.bytes);
+    else memset(blk + c.at, 0, c.bytes);
   }
+  h->cols = exon::text_place(dev, plan, blk);
   if (cp->err != hipSuccess) return fail(ctx, EXON_HIP_EDEVICE, "string columns of a slab towards the host: %s", hipGetErrorString(cp->err));
   return EXON_HIP_OK;
 }
-// the projected columns of the rows `rows[0 .. n)` of the slab (in the order of the projection bits), appended to `kids`
+// the projected columns of the rows `rows[0 .. n)` of the slab (in the order of the schema), appended to `kids`
 // Without a row list (no pushed-down region) the batch's columns are VIEWS into the slab's pinned block: the slab-wide validity /
 // offsets / data buffers with ArrowArray::offset = the batch's first row, the item arrays of the lists shared by reference -- no
 // per-row work on the host (profiles/r6_scan_next_native.log).
 static void text_batch(const HostText& h, const int64_t* rows, int64_t r0, int64_t n, std::vector<struct ArrowArray*>* kids, exon::BatchArena* arena = nullptr) {
-  if (!rows) {
-    auto utf8_view = [&](const Span<int32_t>& off, const Span<uint8_t>& val, const Span<uint8_t>* valid, int64_t first, int64_t len) {
-      return exon::arena_array(arena, len, first, valid ? -1 : 0, 3, valid ? (const void*)valid->data() : nullptr, off.data(), val.data());
-    };
-    if (h.vcf) {
-      if (h.projection & EXON_HIP_PROJECT_VCF_ID) {
-        struct ArrowArray* items = utf8_view(h.item_off, h.val[0], nullptr, 0, (int64_t)h.item_off.n - 1);
-        kids->push_back(exon::arena_array(arena, n, r0, -1, 2, h.valid[0].data(), h.off[0].data(), nullptr, items));
-      }
-      if (h.projection & EXON_HIP_PROJECT_VCF_REF) kids->push_back(utf8_view(h.off[2], h.val[2], nullptr, r0, n));
-      if (h.projection & EXON_HIP_PROJECT_VCF_ALT) {
-        if (h.zeros.p) {  // (batches larger than the static zero array: slab-wide zeros)
-          struct ArrowArray* items = exon::arena_array(arena, 0, 0, 0, 3, nullptr, h.zeros.data(), h.zeros.data());
-          kids->push_back(exon::arena_array(arena, n, r0, -1, 2, h.valid[1].data(), h.zeros.data(), nullptr, items));
-        } else {  // the bitmap from the byte the batch starts in, the offsets from the shared zeros
-          struct ArrowArray* items = exon::arena_array(arena, 0, 0, 0, 3, nullptr, k_zero_offsets, k_zero_offsets);
-          kids->push_back(exon::arena_array(arena, n, r0 & 7, -1, 2, h.valid[1].data() + (r0 >> 3), k_zero_offsets, nullptr, items));
-        }
-      }
-      if (h.projection & EXON_HIP_PROJECT_VCF_INFO) kids->push_back(utf8_view(h.off[1], h.val[1], nullptr, r0, n));
-    }
-    if (h.bcf) {
-      if (h.projection & EXON_HIP_PROJECT_VCF_ID) {
-        struct ArrowArray* items = utf8_view(h.item_off, h.val[0], nullptr, 0, (int64_t)h.item_off.n - 1);
-        kids->push_back(exon::arena_array(arena, n, r0, 0, 2, nullptr, h.off[0].data(), nullptr, items));
-      }
-      if (h.projection & EXON_HIP_PROJECT_VCF_REF) kids->push_back(utf8_view(h.off[2], h.val[2], nullptr, r0, n));
-      if (h.projection & EXON_HIP_PROJECT_VCF_ALT) {
-        struct ArrowArray* items = utf8_view(h.alt_item_off, h.val[1], nullptr, 0, (int64_t)h.alt_item_off.n - 1);
-        kids->push_back(exon::arena_array(arena, n, r0, 0, 2, nullptr, h.off[1].data(), nullptr, items));
-      }
-    }
-    if (h.gff) {  // the slab's entries, keys, value lists and items shared by every batch; the map cut by its offset
-      struct ArrowArray* keys = utf8_view(h.key_off, h.val[0], nullptr, 0, (int64_t)h.key_off.n - 1);
-      struct ArrowArray* items = utf8_view(h.gff_item_off, h.val[1], nullptr, 0, (int64_t)h.gff_item_off.n - 1);
-      struct ArrowArray* values = exon::arena_array(arena, (int64_t)h.list_off.n - 1, 0, 0, 2, nullptr, h.list_off.data(), nullptr, items);
-      struct ArrowArray* entries = exon::arena_struct2(arena, (int64_t)h.key_off.n - 1, keys, values);
-      kids->push_back(exon::arena_array(arena, n, r0, 0, 2, nullptr, h.off[0].data(), nullptr, entries));
-    }
-    if (h.gtf) {  // the slab's entries, keys and values shared by every batch; the map cut by its offset
-      struct ArrowArray* keys = utf8_view(h.key_off, h.val[0], nullptr, 0, (int64_t)h.key_off.n - 1);
-      struct ArrowArray* values = utf8_view(h.gtf_val_off, h.val[1], nullptr, 0, (int64_t)h.gtf_val_off.n - 1);
-      struct ArrowArray* entries = exon::arena_struct2(arena, (int64_t)h.key_off.n - 1, keys, values);
-      kids->push_back(exon::arena_array(arena, n, r0, 0, 2, nullptr, h.off[0].data(), nullptr, entries));
-    }
-    if (h.bed) kids->push_back(utf8_view(h.off[0], h.val[0], &h.valid[0], r0, n));
-    if (h.bam) {
-      if (h.projection & EXON_HIP_PROJECT_BAM_NAME) kids->push_back(utf8_view(h.off[0], h.val[0], &h.valid[0], r0, n));
-      if (h.projection & EXON_HIP_PROJECT_BAM_CIGAR) kids->push_back(utf8_view(h.off[1], h.val[1], nullptr, r0, n));
-      if (h.projection & EXON_HIP_PROJECT_BAM_SEQUENCE) kids->push_back(utf8_view(h.off[2], h.val[2], nullptr, r0, n));
-      if (h.projection & EXON_HIP_PROJECT_BAM_QUALITY_SCORES) {
-        struct ArrowArray* items = exon::arena_array(arena, (int64_t)h.qual.n, 0, 0, 2, nullptr, h.qual.data(), nullptr);
-        kids->push_back(exon::arena_array(arena, n, r0, 0, 2, nullptr, (h.qual_off.p ? h.qual_off : h.off[2]).data(), nullptr, items));
-      }
-    }
-    return;
-  }
-  auto row_at = [&](int64_t i) { return rows ? rows[i] : r0 + i; };
-  auto bit = [&](const Span<uint8_t>& bm, int64_t r) { return (uint8_t)((bm[(size_t)(r >> 3)] >> (r & 7)) & 1); };
-  auto utf8 = [&](const Span<int32_t>& off, const Span<uint8_t>& val, const Span<uint8_t>* valid) {
-    exon::Utf8Builder b;
-    for (int64_t i = 0; i < n; ++i) {
-      const int64_t r = row_at(i);
-      if (valid && !bit(*valid, r)) b.append_null();
-      else b.append_value(reinterpret_cast<const char*>(val.data()) + off[(size_t)r], (size_t)(off[(size_t)r + 1] - off[(size_t)r]));
-    }
-    if (!valid) b.valid.clear();
-    return b.finish();
-  };
-  if (h.vcf) {
-    if (h.projection & EXON_HIP_PROJECT_VCF_ID) {
-      exon::ListUtf8Builder b;
-      for (int64_t i = 0; i < n; ++i) {
-        const int64_t r = row_at(i);
-        if (!bit(h.valid[0], r)) {
-          b.append_null();
-          continue;
-        }
-        for (int32_t k = h.off[0][(size_t)r]; k < h.off[0][(size_t)r + 1]; ++k)
-          b.items.append_value(reinterpret_cast<const char*>(h.val[0].data()) + h.item_off[(size_t)k], (size_t)(h.item_off[(size_t)k + 1] - h.item_off[(size_t)k]));
-        b.close_row();
-      }
-      b.items.valid.clear();
-      kids->push_back(b.finish());
-    }
-    if (h.projection & EXON_HIP_PROJECT_VCF_REF) kids->push_back(utf8(h.off[2], h.val[2], nullptr));
-    if (h.projection & EXON_HIP_PROJECT_VCF_ALT) {
-      exon::ListUtf8Builder b;
-      for (int64_t i = 0; i < n; ++i) {
-        if (bit(h.valid[1], row_at(i))) b.close_row();
-        else b.append_null();
-      }
-      b.items.valid.clear();
-      kids->push_back(b.finish());
-    }
-    if (h.projection & EXON_HIP_PROJECT_VCF_INFO) kids->push_back(utf8(h.off[1], h.val[1], nullptr));
-  }
-  if (h.bcf) {
-    auto list_of = [&](const Span<int32_t>& list_off, const Span<int32_t>& item_off, const Span<uint8_t>& val) {
-      exon::ListUtf8Builder b;
-      for (int64_t i = 0; i < n; ++i) {
-        const int64_t r = row_at(i);
-        for (int32_t k = list_off[(size_t)r]; k < list_off[(size_t)r + 1]; ++k)
-          b.items.append_value(reinterpret_cast<const char*>(val.data()) + item_off[(size_t)k], (size_t)(item_off[(size_t)k + 1] - item_off[(size_t)k]));
-        b.close_row();
-      }
-      b.items.valid.clear();
-      b.valid.clear();
-      return b.finish();
-    };
-    if (h.projection & EXON_HIP_PROJECT_VCF_ID) kids->push_back(list_of(h.off[0], h.item_off, h.val[0]));
-    if (h.projection & EXON_HIP_PROJECT_VCF_REF) kids->push_back(utf8(h.off[2], h.val[2], nullptr));
-    if (h.projection & EXON_HIP_PROJECT_VCF_ALT) kids->push_back(list_of(h.off[1], h.alt_item_off, h.val[1]));
-  }
-  if (h.gff) {  // the map gather: every kept row's entries, keys, lists and items, copied
-    exon::GFFAttrColumn col;
-    for (int64_t i = 0; i < n; ++i) {
-      const int64_t r = row_at(i);
-      for (int32_t e = h.off[0][(size_t)r]; e < h.off[0][(size_t)r + 1]; ++e) {
-        col.keys.append(reinterpret_cast<const char*>(h.val[0].data()) + h.key_off[(size_t)e], (size_t)(h.key_off[(size_t)e + 1] - h.key_off[(size_t)e]));
-        col.key_off.push_back((int32_t)col.keys.size());
-        for (int32_t k = h.list_off[(size_t)e]; k < h.list_off[(size_t)e + 1]; ++k) {
-          col.items.append(reinterpret_cast<const char*>(h.val[1].data()) + h.gff_item_off[(size_t)k], (size_t)(h.gff_item_off[(size_t)k + 1] - h.gff_item_off[(size_t)k]));
-          col.item_off.push_back((int32_t)col.items.size());
-        }
-        col.list_off.push_back((int32_t)col.item_off.size() - 1);
-      }
-      col.map_off.push_back((int32_t)col.key_off.size() - 1);
-    }
-    kids->push_back(col.slice(0, (size_t)n));
-  }
-  if (h.gtf) {  // the map gather, two levels: every kept row's entries, their keys and values, copied
-    exon::GTFAttrColumn col;
-    const char* kv = reinterpret_cast<const char*>(h.val[0].data());
-    const char* vv = reinterpret_cast<const char*>(h.val[1].data());
-    for (int64_t i = 0; i < n; ++i) {
-      const int64_t r = row_at(i);
-      for (int32_t e = h.off[0][(size_t)r]; e < h.off[0][(size_t)r + 1]; ++e)
-        col.append(kv + h.key_off[(size_t)e], (size_t)(h.key_off[(size_t)e + 1] - h.key_off[(size_t)e]), vv + h.gtf_val_off[(size_t)e],
-                   (size_t)(h.gtf_val_off[(size_t)e + 1] - h.gtf_val_off[(size_t)e]));
-      col.close_row();
-    }
-    kids->push_back(col.slice(0, (size_t)n));
-  }
-  if (h.bed) kids->push_back(utf8(h.off[0], h.val[0], &h.valid[0]));
-  if (h.bam) {
-    if (h.projection & EXON_HIP_PROJECT_BAM_NAME) kids->push_back(utf8(h.off[0], h.val[0], &h.valid[0]));
-    if (h.projection & EXON_HIP_PROJECT_BAM_CIGAR) kids->push_back(utf8(h.off[1], h.val[1], nullptr));
-    if (h.projection & EXON_HIP_PROJECT_BAM_SEQUENCE) kids->push_back(utf8(h.off[2], h.val[2], nullptr));
-    if (h.projection & EXON_HIP_PROJECT_BAM_QUALITY_SCORES) {
-      exon::ListBuilder<int64_t> b;
-      for (int64_t i = 0; i < n; ++i) {
-        const int64_t r = row_at(i);
-        const Span<int32_t>& qo = h.qual_off.p ? h.qual_off : h.off[2];
-        const int32_t a = qo[(size_t)r], z = qo[(size_t)r + 1];
-        b.items.values.insert(b.items.values.end(), h.qual.begin() + a, h.qual.begin() + z);
-        b.close_row();
-      }
-      kids->push_back(b.finish());
-    }
-  }
+  for (int k = 0; k < h.cols.n_roots; ++k)
+    kids->push_back(rows ? exon::text_gather_rows(h.cols, h.cols.roots[k], rows, n) : exon::text_view(arena, h.cols, h.cols.roots[k], r0, n));
 }
 
 // the batches of the slab before this one (export_slab: their copy ran under this slab's inflate and parse); the last slab's (its
@@ -2401,7 +2118,7 @@ static int export_slab(exon_hip_scan* scan, const exon_hip_column* sc, int64_t n
     } else if (kept == 0) {
       // GFF `attributes`: field 9 of every record is validated, kept or not (host/gff.h) -- the measure pass runs over a slab that
       // sends nothing too, and hands the file over when it meets a row the host reader must judge
-      if (projected && (projected->format == EXON_HIP_FORMAT_GFF || projected->format == EXON_HIP_FORMAT_GTF))
+      if (projected && scan->gff())
         if (const int rc = projected->build()) return rc;
       return EXON_HIP_OK;
     }
@@ -2466,7 +2183,7 @@ static int export_slab(exon_hip_scan* scan, const exon_hip_column* sc, int64_t n
     int rc = projected->build();  // the device builds the text columns now
     if (rc) return rc;
     const double tf0 = now_s();
-    rc = fetch_text(ctx, &cp, path_stage, n_rows, scan->opt.projection, *projected, &text, scan->opt.batch_size > K_ZERO_ROWS);
+    rc = fetch_text(ctx, &cp, path_stage, projected->cols, &text, scan->opt.batch_size > exon::K_ZERO_ROWS);
     g_t_fetch_text += now_s() - tf0;
     if (rc) return rc;
   } else if (!cp.reserve(path_stage)) {
@@ -2558,8 +2275,8 @@ static int export_slab(exon_hip_scan* scan, const exon_hip_column* sc, int64_t n
       std::vector<struct ArrowArray*> kids;
       const double tv0 = now_s();
       // every array of the batch out of one allocation (exon::BatchArena): per column its array + its dictionary, the text
-      // columns' lists + items, the struct itself
-      exon::BatchArena* arena = exon::new_batch_arena(2 * n_cols + 8 + 1, n_cols + 12, sb, text.sb, dicts_p);
+      // columns' nodes, BED's NULL columns, the struct itself
+      exon::BatchArena* arena = exon::new_batch_arena(2 * n_cols + text.cols.n_nodes + __builtin_popcountll(bed_proj >> 6) + 1, n_cols + 12, sb, text.sb, dicts_p);
       for (int c = 0; c < n_cols; ++c) {
         const void* bits = has_bits[(size_t)c] ? blk + boff[(size_t)c] : nullptr;
         const void* vals = elem[(size_t)c] ? (const void*)(blk + voff[(size_t)c]) : bits;  // a Flag: true where present
@@ -2568,7 +2285,7 @@ static int export_slab(exon_hip_scan* scan, const exon_hip_column* sc, int64_t n
       }
       const double tv1 = now_s();
       g_t_views += tv1 - tv0;
-      if (text.vcf || text.bam || text.bcf || text.gff || text.gtf || text.bed) text_batch(text, nullptr, b0, n, &kids, arena);
+      text_batch(text, nullptr, b0, n, &kids, arena);
       if (bed)  // (a NULL column: every buffer the same zeros; Utf8 has three of them)
         bed_order(&kids, n, [&](int c, int64_t m) {
           const bool utf8 = exon::bed_fields()[c].fmt[0] == 'u';
@@ -2616,7 +2333,7 @@ static int export_slab(exon_hip_scan* scan, const exon_hip_column* sc, int64_t n
         kids.push_back(a);
       }
     }
-    if (text.vcf || text.bam || text.bcf || text.gff || text.gtf || text.bed) text_batch(text, keep.data() + b0, 0, n, &kids);
+    text_batch(text, keep.data() + b0, 0, n, &kids);
     if (bed) bed_order(&kids, n, [](int c, int64_t m) { return exon::bed_null_column(c, (size_t)m); });
     struct ArrowArray* out = static_cast<struct ArrowArray*>(malloc(sizeof *out));
     exon::make_struct(out, n, std::move(kids));
@@ -2631,52 +2348,27 @@ static int export_slab(exon_hip_scan* scan, const exon_hip_column* sc, int64_t n
 // FASTQ batches from the GPU pipeline: the slab's four Utf8 columns (text_columns.hip: name, description?, sequence,
 // quality_scores -- exon-fastq/src/config.rs:79-88) come back into ONE pinned block and go out as batch_size-row views into it
 // (slab-wide offsets / data buffers, ArrowArray::offset = the batch's first read).
-static int export_fastq_slab(exon_hip_scan* scan, const ExonFastqText& ft, int64_t n_reads, hipStream_t hs) {
+static int export_fastq_slab(exon_hip_scan* scan, const ExonTextColumns& ft, int64_t n_reads, hipStream_t hs) {
   GpuExporter* ex = scan->exporter;
   exon_hip_ctx* ctx = ex->ctx;
   if (const int rc = export_flush(scan)) return rc;  // the slab before this one
   if (n_reads == 0) return EXON_HIP_OK;
-  const size_t n = (size_t)n_reads;
-  auto pad = [](size_t b) { return (b + 63) & ~size_t(63); };
-  size_t total = 64;
-  std::array<size_t, 4> at_off, at_val;
-  for (int k = 0; k < 4; ++k) {
-    at_off[(size_t)k] = total;
-    total += pad((n + 1) * 4);
-    at_val[(size_t)k] = total;
-    total += pad((size_t)ft.n_bytes[k] + 8);
-  }
-  const size_t at_valid = total;
-  total += pad((n + 7) / 8 + 8);
   SlabCopier cp(ex, hs);
   ++ex->n_exports;
-  if (!cp.reserve(total + 4096)) return fail(ctx, EXON_HIP_ENOMEM, "no device staging buffer of %zu bytes for a slab of reads", total);
-  size_t blk_bytes = total;
-  uint8_t* blk = static_cast<uint8_t*>(export_block_get(&blk_bytes));
-  if (!blk) return fail(ctx, EXON_HIP_ENOMEM, "no pinned block of %zu bytes for a slab of reads", total);
-  exon::SharedBlock* sb = new exon::SharedBlock();
-  sb->block = blk;
-  sb->bytes = blk_bytes;
-  sb->put = export_block_put;
-  std::shared_ptr<exon::SharedBlock> sb_ref(sb, [](exon::SharedBlock* b) { exon::block_unref(b); });
-  for (int k = 0; k < 4; ++k) {
-    cp.add(blk + at_off[(size_t)k], ft.offsets[k], (n + 1) * 4);
-    cp.add(blk + at_val[(size_t)k], ft.values[k], (size_t)ft.n_bytes[k]);
-  }
-  cp.add(blk + at_valid, ft.desc_valid, (n + 7) / 8);
+  auto text_p = std::make_shared<HostText>();  // (its reference to the block lives as long as the closure below)
+  if (const int rc = fetch_text(ctx, &cp, 4096, ft, text_p.get(), false)) return rc;
   const hipError_t e = cp.launch();
   if (e != hipSuccess) return fail(ctx, EXON_HIP_EDEVICE, "reads of a slab towards the host: %s", hipGetErrorString(e));
   const int slot = cp.slot;
   const int64_t bs = scan->opt.batch_size > 0 ? scan->opt.batch_size : 8192;
   ex->pending = [=]() -> int {
-    (void)sb_ref;
     if (hipEventSynchronize(ex->ev_done[slot]) != hipSuccess) return fail(ctx, EXON_HIP_EDEVICE, "reads of a slab back to the host: the copy failed");
+    const HostText& text = *text_p;
     for (int64_t b0 = 0; b0 < n_reads; b0 += bs) {
       const int64_t m = std::min(n_reads, b0 + bs) - b0;
       std::vector<struct ArrowArray*> kids;
-      exon::BatchArena* arena = exon::new_batch_arena(5, 4, sb, nullptr, nullptr);
-      for (int k = 0; k < 4; ++k)
-        kids.push_back(exon::arena_array(arena, m, b0, k == 1 ? -1 : 0, 3, k == 1 ? (const void*)(blk + at_valid) : nullptr, blk + at_off[(size_t)k], blk + at_val[(size_t)k]));
+      exon::BatchArena* arena = exon::new_batch_arena(text.cols.n_nodes + 1, text.cols.n_roots, text.sb, nullptr, nullptr);
+      text_batch(text, nullptr, b0, m, &kids, arena);
       struct ArrowArray* out = static_cast<struct ArrowArray*>(malloc(sizeof *out));
       exon::make_struct_of_arena(out, m, arena, kids);
       if (const int rc = push_batch(ex, out, m)) return rc;
@@ -2941,8 +2633,8 @@ static int parse_slab(exon_hip_scan* scan, hipStream_t hs, const uint8_t* d_text
   }
 }
 
-// the projected text columns of a slab, built on the device from the index the parser has just made into `t`'s member of the
-// scan's format.  1: the host reader takes over.
+// the projected text columns of a slab, built on the device from the index the parser has just made and described in t->cols.
+// 1: the host reader takes over.
 static int build_text(exon_hip_scan* scan, exon_hip_ctx* ctx, hipStream_t hs, const uint8_t* d_text, size_t n, int64_t n_rows, SlabText* t) {
   const double tk0 = now_s();
   const uint64_t proj = scan->opt.projection;
@@ -2951,16 +2643,16 @@ static int build_text(exon_hip_scan* scan, exon_hip_ctx* ctx, hipStream_t hs, co
   switch (scan->format) {
     case EXON_HIP_FORMAT_VCF:  // undecided (here and for BAM, as for the other two): totals beyond what the scratch buffers hold; `info`: a row the host reader must print or refuse
       r = exon_text_vcf(ctx, hs, &scan->text_scratch, d_text, (int64_t)n, exon_hip_vcf_parser_newlines(scan->parser.as<exon_hip_vcf_parser>()), n_rows, proj,
-                        exon_hip_vcf_parser_key_table(scan->parser.as<exon_hip_vcf_parser>()), &t->vcf, &undecided);
+                        exon_hip_vcf_parser_key_table(scan->parser.as<exon_hip_vcf_parser>()), &t->cols, &undecided);
       break;
     case EXON_HIP_FORMAT_BCF:  // undecided: an ID / allele that is not a typed string (the host reader reports what it is)
-      r = exon_text_bcf(ctx, hs, &scan->text_scratch, d_text, (int64_t)n, exon_hip_bcf_parser_row_records(scan->parser.as<exon_hip_bcf_parser>()), n_rows, proj, &t->bcf, &undecided);
+      r = exon_text_bcf(ctx, hs, &scan->text_scratch, d_text, (int64_t)n, exon_hip_bcf_parser_row_records(scan->parser.as<exon_hip_bcf_parser>()), n_rows, proj, &t->cols, &undecided);
       break;
     case EXON_HIP_FORMAT_BAM:
-      r = exon_text_bam(ctx, hs, &scan->text_scratch, d_text, (int64_t)n, exon_hip_bam_parser_row_records(scan->parser.as<exon_hip_bam_parser>()), n_rows, proj, &t->bam, &undecided);
+      r = exon_text_bam(ctx, hs, &scan->text_scratch, d_text, (int64_t)n, exon_hip_bam_parser_row_records(scan->parser.as<exon_hip_bam_parser>()), n_rows, proj, &t->cols, &undecided);
       break;
     case EXON_HIP_FORMAT_SAM:  // undecided: a CIGAR / QUAL the device would not print the way the reader does
-      r = exon_text_sam(ctx, hs, &scan->text_scratch, d_text, (int64_t)n, exon_hip_sam_parser_newlines(scan->parser.as<exon_hip_sam_parser>()), n_rows, proj, &t->bam, &undecided);
+      r = exon_text_sam(ctx, hs, &scan->text_scratch, d_text, (int64_t)n, exon_hip_sam_parser_newlines(scan->parser.as<exon_hip_sam_parser>()), n_rows, proj, &t->cols, &undecided);
       break;
     case EXON_HIP_FORMAT_GFF:
     case EXON_HIP_FORMAT_GTF: {  // undecided: a field the ATTRIBUTE RULES refuse or whose UTF-8 the host must check; GFF: more items than the scratch holds
@@ -2969,8 +2661,8 @@ static int build_text(exon_hip_scan* scan, exon_hip_ctx* ctx, hipStream_t hs, co
       const uint32_t *off = nullptr, *len = nullptr;
       exon_hip_gff_parser_attr_fields(scan->parser.as<exon_hip_gff_parser>(), &text, &text_bytes, &off, &len);
       if (!off || !len || !text) return fail(ctx, EXON_HIP_ESTATE, "GFF attributes: the slab was parsed without its ninth fields recorded");
-      if (scan->gtf()) r = exon_text_gtf(ctx, hs, &scan->text_scratch, text, text_bytes, off, len, n_rows, &t->gtf, &undecided);
-      else r = exon_text_gff(ctx, hs, &scan->text_scratch, text, text_bytes, off, len, n_rows, &t->gff, &undecided);
+      if (scan->gtf()) r = exon_text_gtf(ctx, hs, &scan->text_scratch, text, text_bytes, off, len, n_rows, &t->cols, &undecided);
+      else r = exon_text_gff(ctx, hs, &scan->text_scratch, text, text_bytes, off, len, n_rows, &t->cols, &undecided);
       break;
     }
     case EXON_HIP_FORMAT_BED: {
@@ -2979,7 +2671,7 @@ static int build_text(exon_hip_scan* scan, exon_hip_ctx* ctx, hipStream_t hs, co
       const uint32_t *off = nullptr, *len = nullptr;
       exon_hip_bed_parser_name_fields(scan->parser.as<exon_hip_bed_parser>(), &text, &text_bytes, &off, &len, &valid);
       if (!off || !len || !valid || !text) return fail(ctx, EXON_HIP_ESTATE, "BED names: the slab was parsed without its names recorded");
-      r = exon_text_bed(ctx, hs, &scan->text_scratch, text, text_bytes, off, len, valid, n_rows, &t->bed);
+      r = exon_text_bed(ctx, hs, &scan->text_scratch, text, text_bytes, off, len, valid, n_rows, &t->cols);
       break;
     }
   }
@@ -3103,7 +2795,7 @@ static int consume_text_gpu(exon_hip_stream* st, exon_hip_scan* scan, int64_t* r
       }
       if (p.n_rows > 0 && p.has_views) {
         if (scan->exporter) {  // batches: the four Utf8 columns, built on the device
-          ExonFastqText ft;
+          ExonTextColumns ft;
           rc = exon_text_fastq(ctx, hs, &scan->text_scratch, &p.views, (int64_t)n + 16, &ft);
           if (!rc) rc = export_fastq_slab(scan, ft, p.n_rows, hs);
         } else {
@@ -3137,7 +2829,6 @@ static int consume_text_gpu(exon_hip_stream* st, exon_hip_scan* scan, int64_t* r
           // the reference's string / list columns of this slab (by export_slab, once it knows that the slab keeps rows at all -- or,
           // GFF `attributes`, that it keeps none: every record's ninth field is validated)
           SlabText text;
-          text.format = scan->format;
           text.build = [&] { return build_text(scan, ctx, hs, d_text, n, n_rows, &text); };
           rc = export_slab(scan, p.sc, n_rows, row_mask, hs, &text);
         } else {

@@ -127,6 +127,7 @@ __global__ __launch_bounds__(TPB) void k_vcf_fill(const uint8_t* __restrict__ te
   }
   if (row == n_rows - 1) id_item_off[id_items_total] = (int32_t)id_bytes_total;
 }
+enum { VCF_ID_ITEMS };  // ExonTextScratch::item_off
 
 // ---- BAM ---------------------------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ uint32_t ld32u(const uint8_t* p) { return (uint32_t)p[0] | (uint32_t)p[1] << 8 | (uint32_t)p[2] << 16 | (uint32_t)p[3] << 24; }
@@ -459,6 +460,7 @@ __global__ __launch_bounds__(TPB) void k_bcf_fill(const uint8_t* __restrict__ d,
     alt_item_off[alt_items_total] = (int32_t)alt_bytes_total;
   }
 }
+enum { BCF_ID_ITEMS, BCF_ALT_ITEMS };  // ExonTextScratch::item_off
 
 // ---- GFF ---------------------------------------------------------------------------------------------------------------------------
 // `attributes`, Map<Utf8, List<Utf8>>, by THE ATTRIBUTE RULES of host/gff.h: the ninth field of row r is text[off[r], off[r] +
@@ -576,6 +578,7 @@ __global__ __launch_bounds__(TPB) void k_gff_attr_fill(const uint8_t* __restrict
     item_off[items_total] = (int32_t)ib_total;
   }
 }
+enum { GFF_KEY_OFF, GFF_LIST_OFF, GFF_ITEM_OFF };  // ExonTextScratch::item_off: the entries' keys, their value lists, the items' bytes
 
 // ---- GTF ---------------------------------------------------------------------------------------------------------------------------
 // `attributes`, Map<Utf8, Utf8>, by THE ATTRIBUTE RULES of host/gtf.h: the ninth field of row r is text[off[r], off[r] + len[r])
@@ -693,6 +696,7 @@ __global__ __launch_bounds__(TPB) void k_gtf_attr_fill(const uint8_t* __restrict
     value_off[entries_total] = (int32_t)vb_total;
   }
 }
+enum { GTF_KEY_OFF, GTF_VALUE_OFF };  // ExonTextScratch::item_off: the entries' keys and values
 
 // ---- BED `name` --------------------------------------------------------------------------------------------------------------------
 // The name column of a BED slab (host/bed.h: the field's bytes as they stand; NULL on 3- and 4-field lines).  The line kernel
@@ -917,6 +921,19 @@ __global__ __launch_bounds__(TPB) void k_vcf_info_fill(const uint8_t* __restrict
   vcf_info_walk(text, fb, fb + field_len[row], kt, f);
 }
 
+// What a format's kernels need of the scratch.  A scratch serves the layout it was made for and no other (scratch_for).
+struct TextLayout {
+  int8_t cols;         // length arrays and the offsets scanned out of them (len[k], off[k])
+  int8_t pools;        // byte pools (values[k])
+  int8_t item_offs;    // item-offset arrays (item_off[k]: every format names its own with an enum next to its kernels)
+  int8_t field_words;  // words a row in `field`: where the measure kernel found the row's fields, for the fill
+  int8_t valids;       // validity bitmaps (valid[k])
+  bool operator==(const TextLayout& o) const { return cols == o.cols && pools == o.pools && item_offs == o.item_offs && field_words == o.field_words && valids == o.valids; }
+};
+constexpr TextLayout LAYOUT_VCF{3, 3, 1, 6, 2}, LAYOUT_BCF{5, 3, 2, 0, 0}, LAYOUT_BAM{3, 3, 0, 0, 1}, LAYOUT_SAM{4, 3, 0, 4, 1}, LAYOUT_FASTQ{4, 4, 0, 0, 1},
+    LAYOUT_GFF{4, 2, 3, 0, 0}, LAYOUT_GTF{3, 2, 2, 0, 0}, LAYOUT_BED{1, 1, 0, 0, 0};
+constexpr int RES_WORDS = 8, RES_UNDECIDED = 7;
+
 struct ExonTextScratch {
   PoolBufs bufs, qual_bufs;  // qual_bufs: the quality_scores values, grown on demand
   // VCF `info`: per-row buffers (field place, printed length, offsets) for info_rows rows, the printed bytes (info_cap), both grown on demand
@@ -928,25 +945,20 @@ struct ExonTextScratch {
   unsigned* info_scal = nullptr;    // device [4]: k_vcf_info_measure's scalars
   unsigned* h_info_scal = nullptr;  // pinned
   int64_t max_rows = 0, max_bytes = 0;
-  int n_cols = 3;
+  TextLayout layout{};
   uint32_t* len[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
   int32_t* off[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
   uint32_t* valid[2] = {nullptr, nullptr};
-  uint32_t *field_off = nullptr, *field_len = nullptr;
-  uint32_t* sam_field_off = nullptr;  // [4 r] (SAM)
+  uint32_t* field = nullptr;  // [layout.field_words * (max_rows + 64)]: SAM [4 r]; VCF [3 r] starts and, behind them, [3 r] lengths
   unsigned* sums = nullptr;
-  unsigned* totals = nullptr;    // device [4]
-  unsigned* h_totals = nullptr;  // pinned
-  int32_t* item_off = nullptr;   // VCF / BCF id items
-  int32_t* item_off2 = nullptr;  // BCF alt items; GFF: the entries' list offsets (item_off: their key offsets); GTF: their value offsets
-  int32_t* item_off3 = nullptr;  // GFF: the items' byte offsets
-  unsigned* totals5 = nullptr;   // device [8]: the five totals of the BCF columns
-  unsigned* h_totals5 = nullptr; // pinned
+  unsigned* res = nullptr;    // device [RES_WORDS]: the totals of the scans in the low words, the undecided rows in word RES_UNDECIDED
+  unsigned* h_res = nullptr;  // pinned
+  int32_t* item_off[3] = {nullptr, nullptr, nullptr};
   uint8_t* values[4] = {nullptr, nullptr, nullptr, nullptr};
   int64_t* qual = nullptr;
   size_t qual_cap = 0;
   size_t value_cap = 0;  // bytes every values[k] holds
-  size_t item_cap = 0;   // entries item_off / item_off2 hold
+  size_t item_cap = 0;   // entries every item_off[k] holds
   explicit ExonTextScratch(exon_hip_ctx* ctx) : bufs(ctx), qual_bufs(ctx), info_row_bufs(ctx), info_value_bufs(ctx) {}
 };
 
@@ -955,18 +967,19 @@ void exon_text_scratch_destroy(ExonTextScratch* s) { delete s; }
 // The largest totals a slab of n_bytes bytes and n_rows rows can produce, buffer by buffer, against the sizes below (the callers
 // pass max_rows >= n_rows and max_bytes as named).  "fits": the size always holds it; "checked": it may not, fits() compares the
 // total on the host before the fill kernel is launched and hands a slab that does not fit to the host reader.
-//   every format  len / off / valid / sums: n_rows lengths, n_rows + 1 offsets, a bit a row, a sum per 256 rows; sized for max_rows + 64: fits
+//   every format  len / off / valid / field / sums: n_rows lengths, n_rows + 1 offsets, a bit a row, the layout's field words a row, a sum per
+//                    256 rows; sized for max_rows + 64: fits
 //   VCF    values[0] (max_bytes = n_bytes): the ID fields without their ';', parts of the text: <= n_bytes: fits
 //   VCF    values[2]: the REF fields, parts of the text: <= n_bytes: fits
-//   VCF    item_off: an ID field of k bytes is up to k + 1 items (k ';') and a line has a byte more than its ID (the LF): up to n_bytes
+//   VCF    item_off[VCF_ID_ITEMS]: an ID field of k bytes is up to k + 1 items (k ';') and a line has a byte more than its ID (the LF): up to n_bytes
 //                    items + 1 entry, against max_bytes / 2 + max_rows + 66: checked
 //   VCF    info_values: the printed `info` entries, NOT bounded by the slab ("DB" prints "DB=true", "1e38" 39 digits: up to eight times
 //                    the field).  k_vcf_info_measure yields every row's exact length and their 64-bit sum; info_for grows the buffer to
 //                    the sum before the fill; a sum beyond INT32_MAX (int32 offsets), or a buffer that cannot be had, hands the slab
 //                    over; k_vcf_info_fill writes inside [offsets[r], offsets[r + 1]) and below the buffer's size only: checked
 //   BCF    values[0], [1], [2] (max_bytes = n_bytes): id / ref / alt, characters of typed strings inside the records: <= n_bytes each: fits
-//   BCF    item_off: a typed ID of k characters is up to k + 1 items behind a descriptor byte: up to n_bytes items + 1 entry: checked
-//   BCF    item_off2: an empty allele is its descriptor byte alone: up to n_bytes items + 1 entry: checked
+//   BCF    item_off[BCF_ID_ITEMS]: a typed ID of k characters is up to k + 1 items behind a descriptor byte: up to n_bytes items + 1 entry: checked
+//   BCF    item_off[BCF_ALT_ITEMS]: an empty allele is its descriptor byte alone: up to n_bytes items + 1 entry: checked
 //   BAM    values[0] (max_bytes = 2 n_bytes): names, l_read_name - 1 bytes of the record: <= n_bytes: fits
 //   BAM    values[1]: a CIGAR op of 4 bytes prints as up to 9 digits and a letter: up to 2.5 n_bytes: checked
 //   BAM    values[2]: two bases a byte, 2 n_bytes when every l_seq lies inside its record; l_seq is the record's own word: checked
@@ -977,14 +990,14 @@ void exon_text_scratch_destroy(ExonTextScratch* s) { delete s; }
 //   GFF    (max_bytes = n_bytes; F = the bytes of the slab's ninth fields; a record has at least 16 bytes in front of its ninth field
 //          -- eight fields, eight TABs -- and its LF behind it: F <= n_bytes - 17 n_rows)
 //   GFF    values[0]: decoded key bytes, values[1]: decoded item bytes; a byte of either comes from a byte of the field or from three: <= F each: fits
-//   GFF    item_off, item_off2 (an entry's key offset and list offset): an entry is a piece of at least a byte ("=") and all but a
+//   GFF    item_off[GFF_KEY_OFF], [GFF_LIST_OFF] (an entry's key offset and list offset): an entry is a piece of at least a byte ("=") and all but a
 //                    row's last are followed by a ';': a field of k bytes holds up to (k + 1) / 2, a slab up to (F + n_rows) / 2 <=
 //                    n_bytes / 2 entries + 1 closing, against max_bytes / 2 + max_rows + 66: fits
-//   GFF    item_off3 (an item's byte offset): "=,,,," is an item a byte: up to F items + 1 entry, against the same size: checked
+//   GFF    item_off[GFF_ITEM_OFF] (an item's byte offset): "=,,,," is an item a byte: up to F items + 1 entry, against the same size: checked
 //   GTF    (max_bytes = n_bytes; F as for GFF: the eight columns in front of the ninth field are the same)
 //   GTF    values[0]: key bytes, values[1]: value bytes; both are parts of the field as they stand, and a key and its value never
 //                    share a byte: <= F together: fits
-//   GTF    item_off, item_off2 (an entry's key offset and value offset): the shortest entry is three bytes ("k v": a key byte, a
+//   GTF    item_off[GTF_KEY_OFF], [GTF_VALUE_OFF] (an entry's key offset and value offset): the shortest entry is three bytes ("k v": a key byte, a
 //                    space, a value byte; a quoted one has four) and all but a row's last are followed by a ';': a field of k
 //                    bytes holds up to (k + 1) / 4, a slab up to (F + n_rows) / 4 <= n_bytes / 4 entries + 1 closing, against
 //                    max_bytes / 2 + max_rows + 66: fits
@@ -992,52 +1005,32 @@ void exon_text_scratch_destroy(ExonTextScratch* s) { delete s; }
 //          the derivation above is then not the only thing between a slab and the end of a buffer.
 //   BED    values[0] (max_bytes = n_bytes): the name fields, disjoint parts of the text: <= n_bytes: fits.  No BED buffer is "checked":
 //          the name bytes of a slab cannot exceed the slab.  k_bed_name_fill bounds its reads and writes all the same.
-// attr: 0, ATTR_GFF or ATTR_GTF -- the offset buffers of the map column
-enum { ATTR_NONE = 0, ATTR_GFF = 1, ATTR_GTF = 2 };
-static int scratch_for(exon_hip_ctx* ctx, ExonTextScratch** sp, int64_t max_rows, int64_t max_bytes, bool vcf, int n_cols = 3, int attr = ATTR_NONE) {
-  const bool gff = attr != ATTR_NONE;  // (either map column: two byte pools, no SAM field index)
+static int scratch_for(exon_hip_ctx* ctx, ExonTextScratch** sp, int64_t max_rows, int64_t max_bytes, TextLayout lay) {
   ExonTextScratch* s = *sp;
-  if (s && s->max_rows >= max_rows && s->max_bytes >= max_bytes && s->n_cols >= n_cols) return EXON_HIP_OK;
+  if (s && s->layout == lay && s->max_rows >= max_rows && s->max_bytes >= max_bytes) return EXON_HIP_OK;
   delete s;
   *sp = nullptr;
   s = new (std::nothrow) ExonTextScratch(ctx);
   if (!s) return fail(ctx, EXON_HIP_ENOMEM, "out of host memory");
   s->max_rows = max_rows;
   s->max_bytes = max_bytes;
-  s->n_cols = n_cols;
+  s->layout = lay;
   hipSetDevice(ctx->device);
   PoolBufs& b = s->bufs;
   const size_t r = (size_t)max_rows + 64;
   s->value_cap = (size_t)max_bytes;
   s->item_cap = (size_t)max_bytes / 2 + r + 2;
-  for (int k = 0; k < n_cols; ++k) {
+  for (int k = 0; k < lay.cols; ++k) {
     s->len[k] = b.take<uint32_t>(r * 4);
     s->off[k] = b.take<int32_t>((r + 1) * 4);
-    if (k < (gff ? 2 : 4)) s->values[k] = b.take<uint8_t>((size_t)max_bytes + 64);
   }
-  if (gff) {
-    s->item_off = b.take<int32_t>(s->item_cap * 4);
-    s->item_off2 = b.take<int32_t>(s->item_cap * 4);
-    if (attr == ATTR_GFF) s->item_off3 = b.take<int32_t>(s->item_cap * 4);
-    s->totals5 = b.take<unsigned>(32);
-    s->h_totals5 = b.pinned<unsigned>(32);
-  }
-  if (n_cols >= 5) {  // BCF: alt items
-    s->item_off2 = b.take<int32_t>(s->item_cap * 4);
-    s->totals5 = b.take<unsigned>(32);
-    s->h_totals5 = b.pinned<unsigned>(32);
-  }
-  s->valid[0] = b.take<uint32_t>(r / 8 + 64);
-  s->valid[1] = b.take<uint32_t>(r / 8 + 64);
-  if (vcf) {
-    s->field_off = b.take<uint32_t>(3 * r * 4);
-    s->field_len = b.take<uint32_t>(3 * r * 4);
-    s->item_off = b.take<int32_t>(s->item_cap * 4);
-  }
-  if (n_cols >= 4 && !gff) s->sam_field_off = b.take<uint32_t>(4 * r * 4);
+  for (int k = 0; k < lay.pools; ++k) s->values[k] = b.take<uint8_t>((size_t)max_bytes + 64);
+  for (int k = 0; k < lay.item_offs; ++k) s->item_off[k] = b.take<int32_t>(s->item_cap * 4);
+  for (int k = 0; k < lay.valids; ++k) s->valid[k] = b.take<uint32_t>(r / 8 + 64);
+  if (lay.field_words) s->field = b.take<uint32_t>((size_t)lay.field_words * r * 4);
   s->sums = b.take<unsigned>((r / TPB + 4) * 4);
-  s->totals = b.take<unsigned>(16);
-  s->h_totals = b.pinned<unsigned>(16);  // (4 totals: the FASTQ columns use them all)
+  s->res = b.take<unsigned>(RES_WORDS * 4);
+  s->h_res = b.pinned<unsigned>(RES_WORDS * 4);
   if (b.status() != hipSuccess) {
     (void)hipGetLastError();
     delete s;
@@ -1076,6 +1069,38 @@ static void scan_lengths(hipStream_t hs, ExonTextScratch* s, const uint32_t* len
   const int nb = (int)((n + LIST_TPB - 1) / LIST_TPB);
   launch_list_scan(hs, len, nullptr, n, nb, s->sums, total);
   hipLaunchKernelGGL(k_write_offsets, dim3(nb), dim3(LIST_TPB), 0, hs, len, n, s->sums, offsets);
+}
+
+// One builder's run.  text_begin is every builder's prologue: a scratch of the format's layout for the slab, the stream, the launch
+// shape, the result block cleared (the measure kernels count undecided rows into it)
+struct TextRun {
+  ExonTextScratch* s;
+  hipStream_t hs;
+  unsigned n;  // rows
+  int nb;      // blocks of TPB rows
+};
+static int text_begin(exon_hip_ctx* ctx, void* stream, ExonTextScratch** sp, int64_t n_rows, int64_t max_bytes, TextLayout lay, TextRun* t) {
+  if (int rc = scratch_for(ctx, sp, std::max<int64_t>(n_rows, 1 << 16), std::max<int64_t>(max_bytes, 1 << 20), lay)) return rc;
+  *t = TextRun{*sp, pick_stream(ctx, stream), (unsigned)n_rows, (int)(((unsigned)n_rows + TPB - 1) / TPB)};
+  HIP_TRY(ctx, hipMemsetAsync(t->s->res, 0, RES_WORDS * 4, t->hs));
+  return EXON_HIP_OK;
+}
+// len[0 .. k) -> off[0 .. k), their totals -> res[0 .. k)
+static void scan_cols(const TextRun& t, int k) {
+  for (int i = 0; i < k; ++i) scan_lengths(t.hs, t.s, t.s->len[i], t.n, t.s->off[i], t.s->res + i);
+}
+// every builder's middle: the k scans, the result block back in its pinned mirror h_res, the stream drained; the rows the measure
+// kernel has counted undecided -> *undecided
+static int text_totals(exon_hip_ctx* ctx, const TextRun& t, int k, int64_t* undecided = nullptr) {
+  scan_cols(t, k);
+  HIP_TRY(ctx, hipMemcpyAsync(t.s->h_res, t.s->res, RES_WORDS * 4, hipMemcpyDeviceToHost, t.hs));
+  HIP_TRY(ctx, hipStreamSynchronize(t.hs));
+  if (undecided) *undecided = t.s->h_res[RES_UNDECIDED];
+  return EXON_HIP_OK;
+}
+// every builder's last line: a column that found no room in `out` is an error, never a column less
+static int text_done(exon_hip_ctx* ctx, const ExonTextColumns* out) {
+  return out->overflow ? fail(ctx, EXON_HIP_ESTATE, "more device-built text columns than ExonTextColumns holds") : EXON_HIP_OK;
 }
 
 // room for the `info` column of a slab of `rows` rows (bytes == 0) or for its `bytes` printed bytes: kept between slabs, the values
@@ -1175,8 +1200,8 @@ int exon_vcf_key_table_build(exon_hip_ctx* ctx, PoolBufs* bufs, const char* keys
 }
 
 int exon_text_vcf(exon_hip_ctx* ctx, void* stream, ExonTextScratch** sp, const uint8_t* d_text, int64_t n_bytes, const unsigned* d_nl, int64_t n_rows, uint64_t projection,
-                  const ExonVcfKeyTable* info_keys, ExonVcfText* out, int64_t* n_undecided) {
-  memset(out, 0, sizeof *out);
+                  const ExonVcfKeyTable* info_keys, ExonTextColumns* out, int64_t* n_undecided) {
+  *out = ExonTextColumns();
   *n_undecided = 0;
   const bool path3 = (projection & (EXON_HIP_PROJECT_VCF_ID | EXON_HIP_PROJECT_VCF_REF | EXON_HIP_PROJECT_VCF_ALT)) != 0;
   const bool info = (projection & EXON_HIP_PROJECT_VCF_INFO) != 0;
@@ -1185,28 +1210,19 @@ int exon_text_vcf(exon_hip_ctx* ctx, void* stream, ExonTextScratch** sp, const u
   const unsigned skip = (unsigned)(reinterpret_cast<uintptr_t>(d_text) & 15);
   d_text -= skip;
   n_bytes += skip;
-  int rc = scratch_for(ctx, sp, std::max<int64_t>(n_rows, 1 << 16), std::max<int64_t>(n_bytes, 1 << 20), true);
-  if (rc) return rc;
-  ExonTextScratch* s = *sp;
-  hipStream_t hs = pick_stream(ctx, stream);
-  const unsigned n = (unsigned)n_rows;
-  const int nb = (int)((n + TPB - 1) / TPB);
-  VcfLens L{s->len[0], s->len[1], s->len[2], s->field_off, s->field_len};
+  TextRun t;
+  if (int rc = text_begin(ctx, stream, sp, n_rows, n_bytes, LAYOUT_VCF, &t)) return rc;
+  ExonTextScratch* s = t.s;
+  VcfLens L{s->len[0], s->len[1], s->len[2], s->field, s->field + 3 * ((size_t)s->max_rows + 64)};
   if (info) {
     if (!info_for(s, (size_t)std::max<int64_t>(n_rows, 1 << 16), 0)) return fail(ctx, EXON_HIP_ENOMEM, "buffers for the info column of a slab (%lld rows)", (long long)n_rows);
-    HIP_TRY(ctx, hipMemsetAsync(s->info_scal, 0, 16, hs));
-    hipLaunchKernelGGL(k_vcf_info_measure, dim3(nb), dim3(TPB), 0, hs, d_text, d_nl, n, skip, *info_keys, s->info_field_off, s->info_field_len, s->info_len, s->info_scal);
-    scan_lengths(hs, s, s->info_len, n, s->info_off, s->totals + 3);
-    HIP_TRY(ctx, hipMemcpyAsync(s->h_info_scal, s->info_scal, 16, hipMemcpyDeviceToHost, hs));
+    HIP_TRY(ctx, hipMemsetAsync(s->info_scal, 0, 16, t.hs));
+    hipLaunchKernelGGL(k_vcf_info_measure, dim3(t.nb), dim3(TPB), 0, t.hs, d_text, d_nl, t.n, skip, *info_keys, s->info_field_off, s->info_field_len, s->info_len, s->info_scal);
+    scan_lengths(t.hs, s, s->info_len, t.n, s->info_off, s->res + 3);
+    HIP_TRY(ctx, hipMemcpyAsync(s->h_info_scal, s->info_scal, 16, hipMemcpyDeviceToHost, t.hs));
   }
-  if (path3) {
-    hipLaunchKernelGGL(k_vcf_measure, dim3(nb), dim3(TPB), 0, hs, d_text, d_nl, n, skip, L, s->valid[0], s->valid[1]);
-    scan_lengths(hs, s, s->len[0], n, s->off[0], s->totals + 0);  // ID: list offsets
-    scan_lengths(hs, s, s->len[1], n, s->off[1], s->totals + 1);  // ID: byte offsets of every row's items
-    scan_lengths(hs, s, s->len[2], n, s->off[2], s->totals + 2);  // REF
-    HIP_TRY(ctx, hipMemcpyAsync(s->h_totals, s->totals, 16, hipMemcpyDeviceToHost, hs));
-  }
-  HIP_TRY(ctx, hipStreamSynchronize(hs));
+  if (path3) hipLaunchKernelGGL(k_vcf_measure, dim3(t.nb), dim3(TPB), 0, t.hs, d_text, d_nl, t.n, skip, L, s->valid[0], s->valid[1]);
+  if (int rc = text_totals(ctx, t, path3 ? 3 : 0)) return rc;  // ID: list offsets, ID: byte offsets of every row's items, REF
   uint64_t info_bytes = 0;
   if (info) {
     if (s->h_info_scal[2]) {  // rows the host reader must print, or refuse
@@ -1219,304 +1235,200 @@ int exon_text_vcf(exon_hip_ctx* ctx, void* stream, ExonTextScratch** sp, const u
       return EXON_HIP_OK;
     }
   }
-  const unsigned id_items = path3 ? s->h_totals[0] : 0u, id_bytes = path3 ? s->h_totals[1] : 0u, ref_bytes = path3 ? s->h_totals[2] : 0u;
+  const unsigned id_items = path3 ? s->h_res[0] : 0u, id_bytes = path3 ? s->h_res[1] : 0u, ref_bytes = path3 ? s->h_res[2] : 0u;
   if (path3 && !fits(s, {id_bytes, ref_bytes}, {id_items})) {  // (IDs of many empty items)
     *n_undecided = n_rows;
     return EXON_HIP_OK;
   }
   if (path3) {
-    hipLaunchKernelGGL(k_vcf_fill, dim3(nb), dim3(TPB), 0, hs, d_text, n, L, s->off[0], s->off[1], s->off[2], s->item_off, s->values[0], s->values[2], id_items, id_bytes);
-    if (id_items == 0) HIP_TRY(ctx, hipMemsetAsync(s->item_off, 0, 4, hs));
+    hipLaunchKernelGGL(k_vcf_fill, dim3(t.nb), dim3(TPB), 0, t.hs, d_text, t.n, L, s->off[0], s->off[1], s->off[2], s->item_off[VCF_ID_ITEMS], s->values[0], s->values[2], id_items,
+                       id_bytes);
+    if (id_items == 0) HIP_TRY(ctx, hipMemsetAsync(s->item_off[VCF_ID_ITEMS], 0, 4, t.hs));
   }
   if (info)
-    hipLaunchKernelGGL(k_vcf_info_fill, dim3(nb), dim3(TPB), 0, hs, d_text, n, *info_keys, s->info_field_off, s->info_field_len, s->info_off, s->info_values,
+    hipLaunchKernelGGL(k_vcf_info_fill, dim3(t.nb), dim3(TPB), 0, t.hs, d_text, t.n, *info_keys, s->info_field_off, s->info_field_len, s->info_off, s->info_values,
                        (unsigned)std::min<size_t>(s->info_cap, 0xFFFFFFFFu));
   HIP_TRY(ctx, hipGetLastError());
-  if (path3) {
-    out->id_list_offsets = s->off[0];
-    out->id_valid = reinterpret_cast<const uint8_t*>(s->valid[0]);
-    out->id_item_offsets = s->item_off;
-    out->id_values = s->values[0];
-    out->n_id_items = id_items;
-    out->n_id_bytes = id_bytes;
-    out->ref_offsets = s->off[2];
-    out->ref_values = s->values[2];
-    out->n_ref_bytes = ref_bytes;
-    out->alt_valid = reinterpret_cast<const uint8_t*>(s->valid[1]);
-  }
-  if (info) {
-    out->info_offsets = s->info_off;
-    out->info_values = s->info_values;
-    out->n_info_bytes = (int64_t)info_bytes;
-  }
-  return EXON_HIP_OK;
+  if (projection & EXON_HIP_PROJECT_VCF_ID) out->root(out->list_utf8(t.n, s->off[0], s->valid[0], id_items, s->item_off[VCF_ID_ITEMS], s->values[0], id_bytes));
+  if (projection & EXON_HIP_PROJECT_VCF_REF) out->root(out->utf8(t.n, s->off[2], nullptr, s->values[2], ref_bytes));
+  if (projection & EXON_HIP_PROJECT_VCF_ALT) out->root(out->list_utf8(t.n, nullptr, s->valid[1], 0, nullptr, nullptr, 0));  // (no items: the note at the top)
+  if (info) out->root(out->utf8(t.n, s->info_off, nullptr, s->info_values, (int64_t)info_bytes));
+  return text_done(ctx, out);
 }
 
+// name, cigar, sequence, quality_scores of BAM records or SAM lines, as projected; qual_off: the list offsets of quality_scores
+static void bam_columns(ExonTextColumns* out, const TextRun& t, uint64_t projection, const int32_t* qual_off, unsigned qual_items) {
+  const ExonTextScratch* s = t.s;
+  if (projection & EXON_HIP_PROJECT_BAM_NAME) out->root(out->utf8(t.n, s->off[0], s->valid[0], s->values[0], s->h_res[0]));
+  if (projection & EXON_HIP_PROJECT_BAM_CIGAR) out->root(out->utf8(t.n, s->off[1], nullptr, s->values[1], s->h_res[1]));
+  if (projection & EXON_HIP_PROJECT_BAM_SEQUENCE) out->root(out->utf8(t.n, s->off[2], nullptr, s->values[2], s->h_res[2]));
+  if (projection & EXON_HIP_PROJECT_BAM_QUALITY_SCORES) out->root(out->list(t.n, qual_off, nullptr, out->int64s(s->qual, qual_items)));
+}
+constexpr uint64_t BAM_TEXT = EXON_HIP_PROJECT_BAM_NAME | EXON_HIP_PROJECT_BAM_CIGAR | EXON_HIP_PROJECT_BAM_SEQUENCE | EXON_HIP_PROJECT_BAM_QUALITY_SCORES;
+
 int exon_text_bam(exon_hip_ctx* ctx, void* stream, ExonTextScratch** sp, const uint8_t* d_data, int64_t n_bytes, const uint32_t* d_rec_of_row, int64_t n_rows, uint64_t projection,
-                  ExonBamText* out, int64_t* n_undecided) {
-  memset(out, 0, sizeof *out);
+                  ExonTextColumns* out, int64_t* n_undecided) {
+  *out = ExonTextColumns();
   *n_undecided = 0;
-  const uint64_t all = EXON_HIP_PROJECT_BAM_NAME | EXON_HIP_PROJECT_BAM_CIGAR | EXON_HIP_PROJECT_BAM_SEQUENCE | EXON_HIP_PROJECT_BAM_QUALITY_SCORES;
-  if (n_rows == 0 || !(projection & all)) return EXON_HIP_OK;
-  int rc = scratch_for(ctx, sp, std::max<int64_t>(n_rows, 1 << 16), std::max<int64_t>(2 * n_bytes, 1 << 20), false);  // (a sequence doubles its 4-bit codes)
-  if (rc) return rc;
-  ExonTextScratch* s = *sp;
-  hipStream_t hs = pick_stream(ctx, stream);
-  const unsigned n = (unsigned)n_rows;
-  const int nb = (int)((n + TPB - 1) / TPB);
+  if (n_rows == 0 || !(projection & BAM_TEXT)) return EXON_HIP_OK;
+  TextRun t;
+  if (int rc = text_begin(ctx, stream, sp, n_rows, 2 * n_bytes, LAYOUT_BAM, &t)) return rc;  // (a sequence doubles its 4-bit codes)
+  ExonTextScratch* s = t.s;
   BamLens L{s->len[0], s->len[1], s->len[2]};
-  hipLaunchKernelGGL(k_bam_measure, dim3(nb), dim3(TPB), 0, hs, d_data, d_rec_of_row, n, L, s->valid[0]);
-  for (int k = 0; k < 3; ++k) scan_lengths(hs, s, s->len[k], n, s->off[k], s->totals + k);
-  HIP_TRY(ctx, hipMemcpyAsync(s->h_totals, s->totals, 16, hipMemcpyDeviceToHost, hs));
-  HIP_TRY(ctx, hipStreamSynchronize(hs));
-  const unsigned name_bytes = s->h_totals[0], cigar_bytes = s->h_totals[1], seq_bytes = s->h_totals[2];
+  hipLaunchKernelGGL(k_bam_measure, dim3(t.nb), dim3(TPB), 0, t.hs, d_data, d_rec_of_row, t.n, L, s->valid[0]);
+  if (int rc = text_totals(ctx, t, 3)) return rc;
+  const unsigned name_bytes = s->h_res[0], cigar_bytes = s->h_res[1], seq_bytes = s->h_res[2];
   if (!fits(s, {name_bytes, cigar_bytes, seq_bytes})) {  // (CIGARs of long ops: up to ten characters out of four bytes)
     *n_undecided = n_rows;
     return EXON_HIP_OK;
   }
   if (projection & EXON_HIP_PROJECT_BAM_QUALITY_SCORES)
     if (int rc = qual_for(ctx, s, seq_bytes)) return rc;
-  hipLaunchKernelGGL(k_bam_fill, dim3(nb), dim3(TPB), 0, hs, d_data, d_rec_of_row, n, projection, s->off[0], s->off[1], s->off[2], s->values[0], s->values[1], s->values[2], s->qual);
+  hipLaunchKernelGGL(k_bam_fill, dim3(t.nb), dim3(TPB), 0, t.hs, d_data, d_rec_of_row, t.n, projection, s->off[0], s->off[1], s->off[2], s->values[0], s->values[1], s->values[2],
+                     s->qual);
   HIP_TRY(ctx, hipGetLastError());
-  out->name_offsets = s->off[0];
-  out->name_values = s->values[0];
-  out->name_valid = reinterpret_cast<const uint8_t*>(s->valid[0]);
-  out->n_name_bytes = name_bytes;
-  out->cigar_offsets = s->off[1];
-  out->cigar_values = s->values[1];
-  out->n_cigar_bytes = cigar_bytes;
-  out->seq_offsets = s->off[2];
-  out->seq_values = s->values[2];
-  out->n_seq_bytes = seq_bytes;
-  out->qual_values = s->qual;
-  out->qual_offsets = s->off[2];  // (a BAM record's qualities are as many as its bases)
-  out->n_qual_items = seq_bytes;
-  return EXON_HIP_OK;
+  bam_columns(out, t, projection, s->off[2], seq_bytes);  // (a BAM record's qualities are as many as its bases)
+  return text_done(ctx, out);
 }
 
-int exon_text_fastq(exon_hip_ctx* ctx, void* stream, ExonTextScratch** sp, const exon_hip_fastq_views* v, int64_t n_bytes, ExonFastqText* out) {
-  memset(out, 0, sizeof *out);
-  const int64_t n_reads = v->n_reads;
-  if (n_reads == 0) return EXON_HIP_OK;
-  int rc = scratch_for(ctx, sp, std::max<int64_t>(n_reads, 1 << 16), std::max<int64_t>(n_bytes, 1 << 20), false, 4);
-  if (rc) return rc;
-  ExonTextScratch* s = *sp;
-  hipStream_t hs = pick_stream(ctx, stream);
-  const unsigned n = (unsigned)n_reads;
-  const int nb = (int)((n + TPB - 1) / TPB);
+int exon_text_fastq(exon_hip_ctx* ctx, void* stream, ExonTextScratch** sp, const exon_hip_fastq_views* v, int64_t n_bytes, ExonTextColumns* out) {
+  *out = ExonTextColumns();
+  if (v->n_reads == 0) return EXON_HIP_OK;
+  TextRun t;
+  if (int rc = text_begin(ctx, stream, sp, v->n_reads, n_bytes, LAYOUT_FASTQ, &t)) return rc;
+  ExonTextScratch* s = t.s;
   FastqLens L{s->len[0], s->len[1], s->len[2], s->len[3]};
-  hipLaunchKernelGGL(k_fastq_measure, dim3(nb), dim3(TPB), 0, hs, v->text_base, n, v->head_start, v->head_end, v->seq_start, v->seq_end, v->qual_start, v->qual_end, L,
+  hipLaunchKernelGGL(k_fastq_measure, dim3(t.nb), dim3(TPB), 0, t.hs, v->text_base, t.n, v->head_start, v->head_end, v->seq_start, v->seq_end, v->qual_start, v->qual_end, L,
                      s->valid[0]);
-  for (int k = 0; k < 4; ++k) scan_lengths(hs, s, s->len[k], n, s->off[k], s->totals + k);
-  hipLaunchKernelGGL(k_fastq_fill, dim3(nb), dim3(TPB), 0, hs, v->text_base, n, v->head_start, v->seq_start, v->qual_start, s->off[0], s->off[1], s->off[2], s->off[3],
+  scan_cols(t, 4);  // (nothing to check: the fill goes in front of the totals' way back, the text is read when this returns)
+  hipLaunchKernelGGL(k_fastq_fill, dim3(t.nb), dim3(TPB), 0, t.hs, v->text_base, t.n, v->head_start, v->seq_start, v->qual_start, s->off[0], s->off[1], s->off[2], s->off[3],
                      s->values[0], s->values[1], s->values[2], s->values[3]);
   HIP_TRY(ctx, hipGetLastError());
-  HIP_TRY(ctx, hipMemcpyAsync(s->h_totals, s->totals, 16, hipMemcpyDeviceToHost, hs));
-  HIP_TRY(ctx, hipStreamSynchronize(hs));
-  for (int k = 0; k < 4; ++k) {
-    out->offsets[k] = s->off[k];
-    out->values[k] = s->values[k];
-    out->n_bytes[k] = s->h_totals[k];
-  }
-  out->desc_valid = reinterpret_cast<const uint8_t*>(s->valid[0]);
-  return EXON_HIP_OK;
+  if (int rc = text_totals(ctx, t, 0)) return rc;
+  for (int k = 0; k < 4; ++k) out->root(out->utf8(t.n, s->off[k], k == 1 ? s->valid[0] : nullptr, s->values[k], s->h_res[k]));
+  return text_done(ctx, out);
 }
 
 int exon_text_bed(exon_hip_ctx* ctx, void* stream, ExonTextScratch** sp, const uint8_t* d_text, int64_t n_bytes, const uint32_t* d_name_off, const uint32_t* d_name_len,
-                  const uint8_t* d_name_valid, int64_t n_rows, ExonBedText* out) {
-  memset(out, 0, sizeof *out);
+                  const uint8_t* d_name_valid, int64_t n_rows, ExonTextColumns* out) {
+  *out = ExonTextColumns();
   if (n_rows == 0) return EXON_HIP_OK;
-  int rc = scratch_for(ctx, sp, std::max<int64_t>(n_rows, 1 << 16), std::max<int64_t>(n_bytes, 1 << 20), false, 1);
-  if (rc) return rc;
-  ExonTextScratch* s = *sp;
-  hipStream_t hs = pick_stream(ctx, stream);
-  const unsigned n = (unsigned)n_rows;
-  const int nb = (int)((n + TPB - 1) / TPB);
-  scan_lengths(hs, s, d_name_len, n, s->off[0], s->totals);
-  hipLaunchKernelGGL(k_bed_name_fill, dim3(nb), dim3(TPB), 0, hs, d_text, (unsigned)n_bytes, n, d_name_off, s->off[0], s->values[0], (unsigned)std::min<size_t>(s->value_cap, 0xFFFFFFFFu));
+  TextRun t;
+  if (int rc = text_begin(ctx, stream, sp, n_rows, n_bytes, LAYOUT_BED, &t)) return rc;
+  ExonTextScratch* s = t.s;
+  scan_lengths(t.hs, s, d_name_len, t.n, s->off[0], s->res);
+  hipLaunchKernelGGL(k_bed_name_fill, dim3(t.nb), dim3(TPB), 0, t.hs, d_text, (unsigned)n_bytes, t.n, d_name_off, s->off[0], s->values[0], (unsigned)std::min<size_t>(s->value_cap, 0xFFFFFFFFu));
   HIP_TRY(ctx, hipGetLastError());
-  HIP_TRY(ctx, hipMemcpyAsync(s->h_totals, s->totals, 4, hipMemcpyDeviceToHost, hs));
-  HIP_TRY(ctx, hipStreamSynchronize(hs));
-  if (!fits(s, {s->h_totals[0]})) return fail(ctx, EXON_HIP_ESTATE, "BED names of %u bytes in a slab of %lld", s->h_totals[0], (long long)n_bytes);  // (never: the table above scratch_for)
-  out->name_offsets = s->off[0];
-  out->name_values = s->values[0];
-  out->name_valid = d_name_valid;
-  out->n_name_bytes = s->h_totals[0];
-  return EXON_HIP_OK;
+  if (int rc = text_totals(ctx, t, 0)) return rc;
+  if (!fits(s, {s->h_res[0]})) return fail(ctx, EXON_HIP_ESTATE, "BED names of %u bytes in a slab of %lld", s->h_res[0], (long long)n_bytes);  // (never: the table above scratch_for)
+  out->root(out->utf8(t.n, s->off[0], d_name_valid, s->values[0], s->h_res[0]));
+  return text_done(ctx, out);
 }
 
-// SAM lines -> the BAM text columns (ExonBamText; quality_scores has list offsets of its own here: QUAL may be '*' next to a SEQ)
+// SAM lines -> the BAM text columns (quality_scores has list offsets of its own here: QUAL may be '*' next to a SEQ)
 int exon_text_sam(exon_hip_ctx* ctx, void* stream, ExonTextScratch** sp, const uint8_t* d_text, int64_t n_bytes, const unsigned* d_nl, int64_t n_rows, uint64_t projection,
-                  ExonBamText* out, int64_t* n_undecided) {
-  memset(out, 0, sizeof *out);
+                  ExonTextColumns* out, int64_t* n_undecided) {
+  *out = ExonTextColumns();
   *n_undecided = 0;
-  const uint64_t all = EXON_HIP_PROJECT_BAM_NAME | EXON_HIP_PROJECT_BAM_CIGAR | EXON_HIP_PROJECT_BAM_SEQUENCE | EXON_HIP_PROJECT_BAM_QUALITY_SCORES;
-  if (n_rows == 0 || !(projection & all)) return EXON_HIP_OK;
+  if (n_rows == 0 || !(projection & BAM_TEXT)) return EXON_HIP_OK;
   const unsigned skip = (unsigned)(reinterpret_cast<uintptr_t>(d_text) & 15);
   d_text -= skip;
   n_bytes += skip;
-  int rc = scratch_for(ctx, sp, std::max<int64_t>(n_rows, 1 << 16), std::max<int64_t>(n_bytes, 1 << 20), false, 4);
-  if (rc) return rc;
-  ExonTextScratch* s = *sp;
-  hipStream_t hs = pick_stream(ctx, stream);
-  const unsigned n = (unsigned)n_rows;
-  const int nb = (int)((n + TPB - 1) / TPB);
-  SamLens L{s->len[0], s->len[1], s->len[2], s->len[3], s->sam_field_off};
-  HIP_TRY(ctx, hipMemsetAsync(s->totals, 0, 16, hs));
-  unsigned* d_und = s->sums + (s->max_rows + 64) / TPB + 2;  // a word of the block-sum buffer behind what scan_lengths uses (nb <= r / TPB + 1)
-  HIP_TRY(ctx, hipMemsetAsync(d_und, 0, 4, hs));
-  hipLaunchKernelGGL(k_sam_measure, dim3(nb), dim3(TPB), 0, hs, d_text, d_nl, n, skip, L, s->valid[0], d_und);
-  for (int k = 0; k < 4; ++k) scan_lengths(hs, s, s->len[k], n, s->off[k], s->totals + k);
-  HIP_TRY(ctx, hipMemcpyAsync(s->h_totals, s->totals, 16, hipMemcpyDeviceToHost, hs));
-  unsigned h_und = 0;
-  HIP_TRY(ctx, hipMemcpyAsync(&h_und, d_und, 4, hipMemcpyDeviceToHost, hs));
-  HIP_TRY(ctx, hipStreamSynchronize(hs));
-  *n_undecided = h_und;
-  if (h_und) return EXON_HIP_OK;
-  const unsigned qual_items = s->h_totals[3];
+  TextRun t;
+  if (int rc = text_begin(ctx, stream, sp, n_rows, n_bytes, LAYOUT_SAM, &t)) return rc;
+  ExonTextScratch* s = t.s;
+  SamLens L{s->len[0], s->len[1], s->len[2], s->len[3], s->field};
+  hipLaunchKernelGGL(k_sam_measure, dim3(t.nb), dim3(TPB), 0, t.hs, d_text, d_nl, t.n, skip, L, s->valid[0], s->res + RES_UNDECIDED);
+  if (int rc = text_totals(ctx, t, 4, n_undecided)) return rc;
+  if (*n_undecided) return EXON_HIP_OK;
+  const unsigned qual_items = s->h_res[3];
   if (projection & EXON_HIP_PROJECT_BAM_QUALITY_SCORES)
     if (int rc = qual_for(ctx, s, qual_items)) return rc;
-  hipLaunchKernelGGL(k_sam_fill, dim3(nb), dim3(TPB), 0, hs, d_text, n, L, projection, s->off[0], s->off[1], s->off[2], s->off[3], s->values[0], s->values[1], s->values[2],
+  hipLaunchKernelGGL(k_sam_fill, dim3(t.nb), dim3(TPB), 0, t.hs, d_text, t.n, L, projection, s->off[0], s->off[1], s->off[2], s->off[3], s->values[0], s->values[1], s->values[2],
                      s->qual);
   HIP_TRY(ctx, hipGetLastError());
-  out->name_offsets = s->off[0];
-  out->name_values = s->values[0];
-  out->name_valid = reinterpret_cast<const uint8_t*>(s->valid[0]);
-  out->n_name_bytes = s->h_totals[0];
-  out->cigar_offsets = s->off[1];
-  out->cigar_values = s->values[1];
-  out->n_cigar_bytes = s->h_totals[1];
-  out->seq_offsets = s->off[2];
-  out->seq_values = s->values[2];
-  out->n_seq_bytes = s->h_totals[2];
-  out->qual_values = s->qual;
-  out->qual_offsets = s->off[3];
-  out->n_qual_items = qual_items;
-  return EXON_HIP_OK;
+  bam_columns(out, t, projection, s->off[3], qual_items);
+  return text_done(ctx, out);
 }
 
 int exon_text_bcf(exon_hip_ctx* ctx, void* stream, ExonTextScratch** sp, const uint8_t* d_data, int64_t n_bytes, const uint32_t* d_rec_of_row, int64_t n_rows, uint64_t projection,
-                  ExonBcfText* out, int64_t* n_undecided) {
-  memset(out, 0, sizeof *out);
+                  ExonTextColumns* out, int64_t* n_undecided) {
+  *out = ExonTextColumns();
   *n_undecided = 0;
   if (n_rows == 0 || !(projection & (EXON_HIP_PROJECT_VCF_ID | EXON_HIP_PROJECT_VCF_REF | EXON_HIP_PROJECT_VCF_ALT))) return EXON_HIP_OK;
-  int rc = scratch_for(ctx, sp, std::max<int64_t>(n_rows, 1 << 16), std::max<int64_t>(n_bytes, 1 << 20), true, 5);
-  if (rc) return rc;
-  ExonTextScratch* s = *sp;
-  hipStream_t hs = pick_stream(ctx, stream);
-  const unsigned n = (unsigned)n_rows;
-  const int nb = (int)((n + TPB - 1) / TPB);
+  TextRun t;
+  if (int rc = text_begin(ctx, stream, sp, n_rows, n_bytes, LAYOUT_BCF, &t)) return rc;
+  ExonTextScratch* s = t.s;
   BcfLens L{s->len[0], s->len[1], s->len[2], s->len[3], s->len[4]};
-  unsigned* d_und = s->totals5 + 7;
-  HIP_TRY(ctx, hipMemsetAsync(s->totals5, 0, 32, hs));
-  hipLaunchKernelGGL(k_bcf_measure, dim3(nb), dim3(TPB), 0, hs, d_data, d_rec_of_row, n, L, d_und);
-  for (int k = 0; k < 5; ++k) scan_lengths(hs, s, s->len[k], n, s->off[k], s->totals5 + k);  // (the totals in this call's own eight words)
-  HIP_TRY(ctx, hipMemcpyAsync(s->h_totals5, s->totals5, 32, hipMemcpyDeviceToHost, hs));
-  HIP_TRY(ctx, hipStreamSynchronize(hs));
-  *n_undecided = s->h_totals5[7];
+  hipLaunchKernelGGL(k_bcf_measure, dim3(t.nb), dim3(TPB), 0, t.hs, d_data, d_rec_of_row, t.n, L, s->res + RES_UNDECIDED);
+  if (int rc = text_totals(ctx, t, 5, n_undecided)) return rc;
   if (*n_undecided) return EXON_HIP_OK;
-  const unsigned id_items = s->h_totals5[0], id_bytes = s->h_totals5[1], ref_bytes = s->h_totals5[2], alt_items = s->h_totals5[3], alt_bytes = s->h_totals5[4];
+  const unsigned id_items = s->h_res[0], id_bytes = s->h_res[1], ref_bytes = s->h_res[2], alt_items = s->h_res[3], alt_bytes = s->h_res[4];
   if (!fits(s, {id_bytes, ref_bytes, alt_bytes}, {id_items, alt_items})) {  // (IDs of many empty items, empty alleles)
     *n_undecided = n_rows;
     return EXON_HIP_OK;
   }
-  hipLaunchKernelGGL(k_bcf_fill, dim3(nb), dim3(TPB), 0, hs, d_data, d_rec_of_row, n, projection, s->off[0], s->off[1], s->off[2], s->off[3], s->off[4], s->item_off, s->item_off2,
+  int32_t *id_item_off = s->item_off[BCF_ID_ITEMS], *alt_item_off = s->item_off[BCF_ALT_ITEMS];
+  hipLaunchKernelGGL(k_bcf_fill, dim3(t.nb), dim3(TPB), 0, t.hs, d_data, d_rec_of_row, t.n, projection, s->off[0], s->off[1], s->off[2], s->off[3], s->off[4], id_item_off, alt_item_off,
                      s->values[0], s->values[1], s->values[2], id_items, id_bytes, alt_items, alt_bytes);
-  if (id_items == 0) HIP_TRY(ctx, hipMemsetAsync(s->item_off, 0, 4, hs));
-  if (alt_items == 0) HIP_TRY(ctx, hipMemsetAsync(s->item_off2, 0, 4, hs));
+  if (id_items == 0) HIP_TRY(ctx, hipMemsetAsync(id_item_off, 0, 4, t.hs));
+  if (alt_items == 0) HIP_TRY(ctx, hipMemsetAsync(alt_item_off, 0, 4, t.hs));
   HIP_TRY(ctx, hipGetLastError());
-  out->id_list_offsets = s->off[0];
-  out->id_item_offsets = s->item_off;
-  out->id_values = s->values[0];
-  out->n_id_items = id_items;
-  out->n_id_bytes = id_bytes;
-  out->ref_offsets = s->off[2];
-  out->ref_values = s->values[1];
-  out->n_ref_bytes = ref_bytes;
-  out->alt_list_offsets = s->off[3];
-  out->alt_item_offsets = s->item_off2;
-  out->alt_values = s->values[2];
-  out->n_alt_items = alt_items;
-  out->n_alt_bytes = alt_bytes;
-  return EXON_HIP_OK;
+  if (projection & EXON_HIP_PROJECT_VCF_ID) out->root(out->list_utf8(t.n, s->off[0], nullptr, id_items, id_item_off, s->values[0], id_bytes));
+  if (projection & EXON_HIP_PROJECT_VCF_REF) out->root(out->utf8(t.n, s->off[2], nullptr, s->values[1], ref_bytes));
+  if (projection & EXON_HIP_PROJECT_VCF_ALT) out->root(out->list_utf8(t.n, s->off[3], nullptr, alt_items, alt_item_off, s->values[2], alt_bytes));
+  return text_done(ctx, out);
 }
 
 int exon_text_gff(exon_hip_ctx* ctx, void* stream, ExonTextScratch** sp, const uint8_t* d_text, int64_t n_bytes, const uint32_t* d_attr_off, const uint32_t* d_attr_len,
-                  int64_t n_rows, ExonGffText* out, int64_t* n_undecided) {
-  memset(out, 0, sizeof *out);
+                  int64_t n_rows, ExonTextColumns* out, int64_t* n_undecided) {
+  *out = ExonTextColumns();
   *n_undecided = 0;
   if (n_rows == 0) return EXON_HIP_OK;
-  int rc = scratch_for(ctx, sp, std::max<int64_t>(n_rows, 1 << 16), std::max<int64_t>(n_bytes, 1 << 20), false, 4, ATTR_GFF);
-  if (rc) return rc;
-  ExonTextScratch* s = *sp;
-  hipStream_t hs = pick_stream(ctx, stream);
-  const unsigned n = (unsigned)n_rows;
-  const int nb = (int)((n + TPB - 1) / TPB);
+  TextRun t;
+  if (int rc = text_begin(ctx, stream, sp, n_rows, n_bytes, LAYOUT_GFF, &t)) return rc;
+  ExonTextScratch* s = t.s;
   GffLens L{s->len[0], s->len[1], s->len[2], s->len[3]};
-  unsigned* d_und = s->totals5 + 7;
-  HIP_TRY(ctx, hipMemsetAsync(s->totals5, 0, 32, hs));
-  hipLaunchKernelGGL(k_gff_attr_measure, dim3(nb), dim3(TPB), 0, hs, d_text, d_attr_off, d_attr_len, n, L, d_und);
-  for (int k = 0; k < 4; ++k) scan_lengths(hs, s, s->len[k], n, s->off[k], s->totals5 + k);  // entries (the map's offsets), items, key bytes, item bytes
-  HIP_TRY(ctx, hipMemcpyAsync(s->h_totals5, s->totals5, 32, hipMemcpyDeviceToHost, hs));
-  HIP_TRY(ctx, hipStreamSynchronize(hs));
-  *n_undecided = s->h_totals5[7];
+  hipLaunchKernelGGL(k_gff_attr_measure, dim3(t.nb), dim3(TPB), 0, t.hs, d_text, d_attr_off, d_attr_len, t.n, L, s->res + RES_UNDECIDED);
+  if (int rc = text_totals(ctx, t, 4, n_undecided)) return rc;  // entries (the map's offsets), items, key bytes, item bytes
   if (*n_undecided) return EXON_HIP_OK;
-  const unsigned entries = s->h_totals5[0], items = s->h_totals5[1], key_bytes = s->h_totals5[2], item_bytes = s->h_totals5[3];
+  const unsigned entries = s->h_res[0], items = s->h_res[1], key_bytes = s->h_res[2], item_bytes = s->h_res[3];
   if (!fits(s, {key_bytes, item_bytes}, {entries, items})) {  // (values that are mostly ',': an item a byte)
     *n_undecided = n_rows;
     return EXON_HIP_OK;
   }
-  hipLaunchKernelGGL(k_gff_attr_fill, dim3(nb), dim3(TPB), 0, hs, d_text, d_attr_off, d_attr_len, n, s->off[0], s->off[1], s->off[2], s->off[3], s->item_off, s->item_off2,
-                     s->item_off3, s->values[0], s->values[1], entries, items, key_bytes, item_bytes);
+  hipLaunchKernelGGL(k_gff_attr_fill, dim3(t.nb), dim3(TPB), 0, t.hs, d_text, d_attr_off, d_attr_len, t.n, s->off[0], s->off[1], s->off[2], s->off[3], s->item_off[GFF_KEY_OFF],
+                     s->item_off[GFF_LIST_OFF], s->item_off[GFF_ITEM_OFF], s->values[0], s->values[1], entries, items, key_bytes, item_bytes);
   HIP_TRY(ctx, hipGetLastError());
-  out->map_offsets = s->off[0];
-  out->key_offsets = s->item_off;
-  out->list_offsets = s->item_off2;
-  out->item_offsets = s->item_off3;
-  out->key_values = s->values[0];
-  out->item_values = s->values[1];
-  out->n_entries = entries;
-  out->n_items = items;
-  out->n_key_bytes = key_bytes;
-  out->n_item_bytes = item_bytes;
-  return EXON_HIP_OK;
+  const int keys = out->utf8(entries, s->item_off[GFF_KEY_OFF], nullptr, s->values[0], key_bytes);
+  const int lists = out->list_utf8(entries, s->item_off[GFF_LIST_OFF], nullptr, items, s->item_off[GFF_ITEM_OFF], s->values[1], item_bytes);
+  out->root(out->list(t.n, s->off[0], nullptr, out->struct2(entries, keys, lists)));
+  return text_done(ctx, out);
 }
 
 int exon_text_gtf(exon_hip_ctx* ctx, void* stream, ExonTextScratch** sp, const uint8_t* d_text, int64_t n_bytes, const uint32_t* d_attr_off, const uint32_t* d_attr_len,
-                  int64_t n_rows, ExonGtfText* out, int64_t* n_undecided) {
-  memset(out, 0, sizeof *out);
+                  int64_t n_rows, ExonTextColumns* out, int64_t* n_undecided) {
+  *out = ExonTextColumns();
   *n_undecided = 0;
   if (n_rows == 0) return EXON_HIP_OK;
-  int rc = scratch_for(ctx, sp, std::max<int64_t>(n_rows, 1 << 16), std::max<int64_t>(n_bytes, 1 << 20), false, 3, ATTR_GTF);
-  if (rc) return rc;
-  ExonTextScratch* s = *sp;
-  hipStream_t hs = pick_stream(ctx, stream);
-  const unsigned n = (unsigned)n_rows;
-  const int nb = (int)((n + TPB - 1) / TPB);
+  TextRun t;
+  if (int rc = text_begin(ctx, stream, sp, n_rows, n_bytes, LAYOUT_GTF, &t)) return rc;
+  ExonTextScratch* s = t.s;
   GtfLens L{s->len[0], s->len[1], s->len[2]};
-  unsigned* d_und = s->totals5 + 7;
-  HIP_TRY(ctx, hipMemsetAsync(s->totals5, 0, 32, hs));
-  hipLaunchKernelGGL(k_gtf_attr_measure, dim3(nb), dim3(TPB), 0, hs, d_text, d_attr_off, d_attr_len, n, L, d_und);
-  for (int k = 0; k < 3; ++k) scan_lengths(hs, s, s->len[k], n, s->off[k], s->totals5 + k);  // entries (the map's offsets), key bytes, value bytes
-  HIP_TRY(ctx, hipMemcpyAsync(s->h_totals5, s->totals5, 32, hipMemcpyDeviceToHost, hs));
-  HIP_TRY(ctx, hipStreamSynchronize(hs));
-  *n_undecided = s->h_totals5[7];
+  hipLaunchKernelGGL(k_gtf_attr_measure, dim3(t.nb), dim3(TPB), 0, t.hs, d_text, d_attr_off, d_attr_len, t.n, L, s->res + RES_UNDECIDED);
+  if (int rc = text_totals(ctx, t, 3, n_undecided)) return rc;  // entries (the map's offsets), key bytes, value bytes
   if (*n_undecided) return EXON_HIP_OK;
-  const unsigned entries = s->h_totals5[0], key_bytes = s->h_totals5[1], value_bytes = s->h_totals5[2];
+  const unsigned entries = s->h_res[0], key_bytes = s->h_res[1], value_bytes = s->h_res[2];
   if (!fits(s, {key_bytes, value_bytes}, {entries})) {  // (never, by the capacity table above scratch_for)
     *n_undecided = n_rows;
     return EXON_HIP_OK;
   }
-  hipLaunchKernelGGL(k_gtf_attr_fill, dim3(nb), dim3(TPB), 0, hs, d_text, d_attr_off, d_attr_len, n, s->off[0], s->off[1], s->off[2], s->item_off, s->item_off2, s->values[0],
-                     s->values[1], entries, key_bytes, value_bytes, (unsigned)std::min<size_t>(s->item_cap, 0xFFFFFFFFu), (unsigned)std::min<size_t>(s->value_cap, 0xFFFFFFFFu));
+  hipLaunchKernelGGL(k_gtf_attr_fill, dim3(t.nb), dim3(TPB), 0, t.hs, d_text, d_attr_off, d_attr_len, t.n, s->off[0], s->off[1], s->off[2], s->item_off[GTF_KEY_OFF],
+                     s->item_off[GTF_VALUE_OFF], s->values[0], s->values[1], entries, key_bytes, value_bytes, (unsigned)std::min<size_t>(s->item_cap, 0xFFFFFFFFu),
+                     (unsigned)std::min<size_t>(s->value_cap, 0xFFFFFFFFu));
   HIP_TRY(ctx, hipGetLastError());
-  out->map_offsets = s->off[0];
-  out->key_offsets = s->item_off;
-  out->value_offsets = s->item_off2;
-  out->key_values = s->values[0];
-  out->value_values = s->values[1];
-  out->n_entries = entries;
-  out->n_key_bytes = key_bytes;
-  out->n_value_bytes = value_bytes;
-  return EXON_HIP_OK;
+  const int keys = out->utf8(entries, s->item_off[GTF_KEY_OFF], nullptr, s->values[0], key_bytes);
+  const int values = out->utf8(entries, s->item_off[GTF_VALUE_OFF], nullptr, s->values[1], value_bytes);
+  out->root(out->list(t.n, s->off[0], nullptr, out->struct2(entries, keys, values)));
+  return text_done(ctx, out);
 }
