@@ -524,7 +524,7 @@ int exon_hip_bcf_parser_parse(exon_hip_bcf_parser* p, void* stream, const uint8_
 }  // extern "C"
 
 // so_far: after an overflow, the lists with the first EXON_HIP_MAX_GROUPS ids (those of every slab parsed before it)
-static int bcf_filters(exon_hip_bcf_parser* p, int32_t* lists, int32_t* counts, int32_t cap, int32_t* n_filters, bool so_far) {
+int exon_bcf_parser_filter_lists(exon_hip_bcf_parser* p, int32_t* lists, int32_t* counts, int32_t cap, int32_t* n_filters, bool so_far) {
   if (!p || !n_filters) return fail(p ? p->ctx : nullptr, EXON_HIP_EINVAL, "exon_hip_bcf_parser_filters: NULL argument");
   exon_hip_ctx* ctx = p->ctx;
   int32_t counters[4];
@@ -549,14 +549,11 @@ static int bcf_filters(exon_hip_bcf_parser* p, int32_t* lists, int32_t* counts, 
     }
   return EXON_HIP_OK;
 }
-int exon_hip_bcf_parser_filters_so_far(exon_hip_bcf_parser* p, int32_t* lists, int32_t* counts, int32_t cap, int32_t* n_filters) {
-  return bcf_filters(p, lists, counts, cap, n_filters, true);
-}
 
 extern "C" {
 // FILTER lists discovered so far, in id order: lists[i * 8 .. i * 8 + counts[i]) are dictionary (header string) indexes
 int exon_hip_bcf_parser_filters(exon_hip_bcf_parser* p, int32_t* lists, int32_t* counts, int32_t cap, int32_t* n_filters) {
-  return bcf_filters(p, lists, counts, cap, n_filters, false);
+  return exon_bcf_parser_filter_lists(p, lists, counts, cap, n_filters, false);
 }
 }  // extern "C"
 

@@ -1056,10 +1056,7 @@ static int table_names(exon_hip_ctx* ctx, const FilterTable& t, const char* what
   return EXON_HIP_OK;
 }
 // FILTER dictionary discovered so far: names are written '\0'-separated into `buf` (id order); returns the count
-int exon_hip_vcf_parser_filters(exon_hip_vcf_parser* p, char* buf, size_t cap, int32_t* n_filters) {
-  if (!p || !n_filters) return fail(p ? p->ctx : nullptr, EXON_HIP_EINVAL, "exon_hip_vcf_parser_filters: NULL argument");
-  return table_names(p->ctx, p->filters, "FILTER lists", buf, cap, n_filters, false);
-}
+int exon_hip_vcf_parser_filters(exon_hip_vcf_parser* p, char* buf, size_t cap, int32_t* n_filters) { return exon_vcf_parser_filter_names(p, buf, cap, n_filters, false); }
 // on != 0: a row without a value of a String / Character key gets the dictionary id of the EMPTY text (no row can carry it) and
 // counts as valid: NULL becomes a group key of its own for a plan that groups by the key.  Off (default): NULL stays NULL.
 int exon_hip_vcf_parser_set_null_key(exon_hip_vcf_parser* p, int32_t on) {
@@ -1068,22 +1065,18 @@ int exon_hip_vcf_parser_set_null_key(exon_hip_vcf_parser* p, int32_t on) {
   return EXON_HIP_OK;
 }
 // the value dictionary of INFO key `key` (its index in the parser's key list; kind 's') in id order
-int exon_hip_vcf_parser_info_values(exon_hip_vcf_parser* p, int32_t key, char* buf, size_t cap, int32_t* n_values) {
-  if (!p || !n_values) return fail(p ? p->ctx : nullptr, EXON_HIP_EINVAL, "exon_hip_vcf_parser_info_values: NULL argument");
-  if (key < 0 || key >= p->ik.n || p->ik.kind[key] != 's') return fail(p->ctx, EXON_HIP_EINVAL, "exon_hip_vcf_parser_info_values: key %d is not a String / Character key of this parser", key);
-  return table_names(p->ctx, p->str_tables[key], "values of a String INFO key", buf, cap, n_values, false);
-}
+int exon_hip_vcf_parser_info_values(exon_hip_vcf_parser* p, int32_t key, char* buf, size_t cap, int32_t* n_values) { return exon_vcf_parser_info_value_names(p, key, buf, cap, n_values, false); }
 
 }  // extern "C"
 
-int exon_hip_vcf_parser_filters_so_far(exon_hip_vcf_parser* p, char* buf, size_t cap, int32_t* n_filters) {
-  if (!p || !n_filters) return fail(p ? p->ctx : nullptr, EXON_HIP_EINVAL, "exon_hip_vcf_parser_filters_so_far: NULL argument");
-  return table_names(p->ctx, p->filters, "FILTER lists", buf, cap, n_filters, true);
+int exon_vcf_parser_filter_names(exon_hip_vcf_parser* p, char* buf, size_t cap, int32_t* n_filters, bool so_far) {
+  if (!p || !n_filters) return fail(p ? p->ctx : nullptr, EXON_HIP_EINVAL, "exon_hip_vcf_parser_filters: NULL argument");
+  return table_names(p->ctx, p->filters, "FILTER lists", buf, cap, n_filters, so_far);
 }
-int exon_hip_vcf_parser_info_values_so_far(exon_hip_vcf_parser* p, int32_t key, char* buf, size_t cap, int32_t* n_values) {
-  if (!p || !n_values || key < 0 || key >= p->ik.n || p->ik.kind[key] != 's')
-    return fail(p ? p->ctx : nullptr, EXON_HIP_EINVAL, "exon_hip_vcf_parser_info_values_so_far: bad argument");
-  return table_names(p->ctx, p->str_tables[key], "values of a String INFO key", buf, cap, n_values, true);
+int exon_vcf_parser_info_value_names(exon_hip_vcf_parser* p, int32_t key, char* buf, size_t cap, int32_t* n_values, bool so_far) {
+  if (!p || !n_values) return fail(p ? p->ctx : nullptr, EXON_HIP_EINVAL, "exon_hip_vcf_parser_info_values: NULL argument");
+  if (key < 0 || key >= p->ik.n || p->ik.kind[key] != 's') return fail(p->ctx, EXON_HIP_EINVAL, "exon_hip_vcf_parser_info_values: key %d is not a String / Character key of this parser", key);
+  return table_names(p->ctx, p->str_tables[key], "values of a String INFO key", buf, cap, n_values, so_far);
 }
 
 // ------------------------------------------------------------------------------------------------------------
@@ -1828,11 +1821,7 @@ int exon_hip_gff_parser_gtf_attributes(exon_hip_gff_parser* p, void* stream, exo
 }
 
 // the dictionary of column 0 (seqname), 1 (source) or 2 (type) discovered so far, '\0'-separated in id order
-int exon_hip_gff_parser_names(exon_hip_gff_parser* p, int32_t column, char* buf, size_t cap, int32_t* n_names) {
-  if (!p || !n_names || column < 0 || column > 2) return fail(p ? p->ctx : nullptr, EXON_HIP_EINVAL, "exon_hip_gff_parser_names: bad argument");
-  static const char* const what[3] = {"seqnames", "sources", "feature types"};
-  return table_names(p->ctx, p->tables[column], what[column], buf, cap, n_names, false);
-}
+int exon_hip_gff_parser_names(exon_hip_gff_parser* p, int32_t column, char* buf, size_t cap, int32_t* n_names) { return exon_gff_parser_column_names(p, column, buf, cap, n_names, false); }
 
 }  // extern "C"
 
@@ -1843,9 +1832,10 @@ void exon_hip_gff_parser_attr_fields(exon_hip_gff_parser* p, const uint8_t** tex
   *len = p->d_attr_len;
 }
 
-int exon_hip_gff_parser_names_so_far(exon_hip_gff_parser* p, int32_t column, char* buf, size_t cap, int32_t* n_names) {
-  if (!p || !n_names || column < 0 || column > 2) return fail(p ? p->ctx : nullptr, EXON_HIP_EINVAL, "exon_hip_gff_parser_names_so_far: bad argument");
-  return table_names(p->ctx, p->tables[column], "GFF names", buf, cap, n_names, true);
+int exon_gff_parser_column_names(exon_hip_gff_parser* p, int32_t column, char* buf, size_t cap, int32_t* n_names, bool so_far) {
+  if (!p || !n_names || column < 0 || column > 2) return fail(p ? p->ctx : nullptr, EXON_HIP_EINVAL, "exon_hip_gff_parser_names: bad argument");
+  static const char* const what[3] = {"seqnames", "sources", "feature types"};
+  return table_names(p->ctx, p->tables[column], what[column], buf, cap, n_names, so_far);
 }
 
 // ------------------------------------------------------------------------------------------------------------
@@ -2126,10 +2116,7 @@ int exon_hip_bed_parser_parse(exon_hip_bed_parser* p, void* stream, const uint8_
 }
 
 // the reference_sequence_name dictionary discovered so far, '\0'-separated in id order
-int exon_hip_bed_parser_names(exon_hip_bed_parser* p, char* buf, size_t cap, int32_t* n_names) {
-  if (!p || !n_names) return fail(p ? p->ctx : nullptr, EXON_HIP_EINVAL, "exon_hip_bed_parser_names: bad argument");
-  return table_names(p->ctx, p->table, "reference sequence names", buf, cap, n_names, false);
-}
+int exon_hip_bed_parser_names(exon_hip_bed_parser* p, char* buf, size_t cap, int32_t* n_names) { return exon_bed_parser_reference_names(p, buf, cap, n_names, false); }
 
 }  // extern "C"
 
@@ -2141,7 +2128,7 @@ void exon_hip_bed_parser_name_fields(exon_hip_bed_parser* p, const uint8_t** tex
   *valid = p->proj ? p->out.name_valid : nullptr;
 }
 
-int exon_hip_bed_parser_names_so_far(exon_hip_bed_parser* p, char* buf, size_t cap, int32_t* n_names) {
-  if (!p || !n_names) return fail(p ? p->ctx : nullptr, EXON_HIP_EINVAL, "exon_hip_bed_parser_names_so_far: bad argument");
-  return table_names(p->ctx, p->table, "BED names", buf, cap, n_names, true);
+int exon_bed_parser_reference_names(exon_hip_bed_parser* p, char* buf, size_t cap, int32_t* n_names, bool so_far) {
+  if (!p || !n_names) return fail(p ? p->ctx : nullptr, EXON_HIP_EINVAL, "exon_hip_bed_parser_names: bad argument");
+  return table_names(p->ctx, p->table, "reference sequence names", buf, cap, n_names, so_far);
 }

@@ -38,6 +38,7 @@
 // (ref) The reference has no region filter and no indexed table for BED: exon_hip_scan_open refuses `region` and `use_index`.
 #pragma once
 #include "gff.h"
+#include "slab_export.h"
 
 namespace exon {
 
@@ -128,17 +129,7 @@ inline const BEDField* bed_fields() {
 constexpr uint64_t BED_PROJECTION_BITS = 0xFF8ull;  // bits 3..11
 
 // n all-NULL rows of a column of bed_fields()[c] (c >= 6)
-inline struct ArrowArray* bed_null_column(int c, size_t n) {
-  struct ArrowArray* a = static_cast<struct ArrowArray*>(malloc(sizeof *a));
-  const std::vector<uint8_t> valid(n, 0);
-  if (bed_fields()[c].fmt[0] == 'u') {
-    make_utf8(a, std::vector<int32_t>(n + 1, 0), std::string(), valid);
-  } else {
-    const std::vector<int64_t> zeros(n, 0);
-    make_primitive(a, zeros.data(), (int64_t)n, 8, valid);
-  }
-  return a;
-}
+inline struct ArrowArray* bed_null_column(int c, size_t n) { return slab_null_column(bed_fields()[c].fmt[0] == 'u', (int64_t)n); }
 
 class BEDArrayBuilder : public ExonArrayBuilder {
  public:

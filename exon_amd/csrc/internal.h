@@ -112,20 +112,21 @@ void exon_text_scratch_destroy(ExonTextScratch* s);
 // the parsers' own indexes the text columns are built from (valid until the next parse call)
 const unsigned* exon_hip_vcf_parser_newlines(exon_hip_vcf_parser* p);
 // a device-built dictionary holds up to EXON_HIP_MAX_GROUPS names in a text pool of EXON_DICT_POOL bytes: its names, '\0'-separated,
-// fit EXON_DICT_NAMES_CAP bytes.  The *_so_far fetches also answer after the table overflowed: the names assigned before it
-// (the exporter names a slab's batches after the next slab was parsed, which may have overflowed the table)
+// fit EXON_DICT_NAMES_CAP bytes.  The fetches behind the public exon_hip_*_parser_filters / _names / _info_values; so_far: they also
+// answer after the table overflowed, with the names assigned before it (the exporter names a slab's batches after the next slab was
+// parsed, which may have overflowed the table)
 constexpr int EXON_DICT_POOL = 1 << 20;
 constexpr size_t EXON_DICT_NAMES_CAP = (size_t)EXON_DICT_POOL + EXON_HIP_MAX_GROUPS;
-int exon_hip_vcf_parser_filters_so_far(exon_hip_vcf_parser* p, char* buf, size_t cap, int32_t* n_filters);
-int exon_hip_vcf_parser_info_values_so_far(exon_hip_vcf_parser* p, int32_t key, char* buf, size_t cap, int32_t* n_values);
-int exon_hip_gff_parser_names_so_far(exon_hip_gff_parser* p, int32_t column, char* buf, size_t cap, int32_t* n_names);
+int exon_vcf_parser_filter_names(exon_hip_vcf_parser* p, char* buf, size_t cap, int32_t* n_filters, bool so_far);
+int exon_vcf_parser_info_value_names(exon_hip_vcf_parser* p, int32_t key, char* buf, size_t cap, int32_t* n_values, bool so_far);
+int exon_gff_parser_column_names(exon_hip_gff_parser* p, int32_t column, char* buf, size_t cap, int32_t* n_names, bool so_far);
 // gpu_parse.hip: the aligned slab of the last parse call and every row's ninth field in it (after exon_hip_gff_parser_want_attributes)
 void exon_hip_gff_parser_attr_fields(exon_hip_gff_parser* p, const uint8_t** text, int64_t* n_bytes, const uint32_t** off, const uint32_t** len);
 struct exon_hip_bed_parser;
-int exon_hip_bed_parser_names_so_far(exon_hip_bed_parser* p, char* buf, size_t cap, int32_t* n_names);
+int exon_bed_parser_reference_names(exon_hip_bed_parser* p, char* buf, size_t cap, int32_t* n_names, bool so_far);
 // gpu_parse.hip: the aligned slab of the last parse call and every row's name in it (after exon_hip_bed_parser_want with a projection)
 void exon_hip_bed_parser_name_fields(exon_hip_bed_parser* p, const uint8_t** text, int64_t* n_bytes, const uint32_t** off, const uint32_t** len, const uint8_t** valid);
-int exon_hip_bcf_parser_filters_so_far(exon_hip_bcf_parser* p, int32_t* lists, int32_t* counts, int32_t cap, int32_t* n_filters);
+int exon_bcf_parser_filter_lists(exon_hip_bcf_parser* p, int32_t* lists, int32_t* counts, int32_t cap, int32_t* n_filters, bool so_far);
 const unsigned* exon_hip_sam_parser_newlines(exon_hip_sam_parser* p);      // gpu_parse.hip: the same for SAM lines      // gpu_parse.hip: byte offset of every line's '\n' in the aligned slab
 const uint32_t* exon_hip_bam_parser_row_records(exon_hip_bam_parser* p);
 const uint32_t* exon_hip_bcf_parser_row_records(exon_hip_bcf_parser* p);   // bcf_parse.hip: the same for BCF records   // bam_parse.hip: byte offset of every row's record

@@ -25,6 +25,7 @@
 #include "host/gtf.h"
 #include "host/bed.h"
 #include "host/parallel.h"
+#include "host/slab_export.h"
 #include "host/text_export.h"
 #include "internal.h"
 
@@ -32,7 +33,7 @@
 struct DeviceParser {
   int format = 0;
   void* h = nullptr;  // exon_hip_{vcf,bcf,bam,sam,fastq,gff}_parser of `format`
-  // the FILTER dictionary (and VCF's String INFO dictionaries; GFF: seqname / source / type) of the scan are the device parser's
+  // the dictionaries of the layout's device_names columns (FILTER, VCF's String INFO keys, GFF / BED names) are the device parser's
   bool owns_names = false;
   template <class T>
   T* as() const { return static_cast<T*>(h); }
@@ -66,8 +67,8 @@ struct exon_hip_scan {
   bool gpu_candidate = false;
   bool gpu_inflated = false;  // the last GPU-parsed consume also inflated BGZF blocks on the device
   bool gpu_decoded = false;   // the last consume decoded every record on the device (no host fallback)
-  exon::Dictionary gpu_filter_dict;       // names fetched from the parser after the consume
-  exon::Dictionary gpu_gff_dicts[3];      // GFF: seqname / source / type, likewise (BED: [0] is reference_sequence_name)
+  exon::SlabLayout layout;                // the fixed-width columns and the children of a batch (slab_layout, at open)
+  std::vector<exon::Dictionary> names;    // by scan column: the dictionaries the device parser built, adopted after the consume (adopt_names)
   std::unique_ptr<exon::BatchReader> reader;  // of `format`
   int64_t rows = 0;
   exon::Dictionary bam_dict_view;  // reference names as a dictionary (ids = header order)
@@ -119,10 +120,7 @@ struct GpuExporter {
   int rc = 0;
   std::string err;
   int64_t emitted = 0;                       // rows handed to the queue so far
-  std::vector<std::string> final_filters;    // the FILTER dictionary when the producer has finished
-  std::vector<std::vector<std::string>> final_info_names;  // ... and the String INFO keys' dictionaries
-  std::vector<std::string> final_gff_names[3];              // GFF: the seqname / source / type dictionaries
-  bool has_gff_names = false;
+  std::vector<std::vector<std::string>> final_names;  // by scan column: the device-built dictionaries when the producer has finished
   bool decoded_on_gpu = false, inflated_on_gpu = false;
   // the host reader that takes over when the device hands the file back.  It lives HERE while the producer thread runs: the
   // scan's own reader (which exon_hip_scan_schema / _dictionary_* read from the consumer's thread) is never touched by the
@@ -254,13 +252,14 @@ static const char* unsupported_codec(const char* path) {
 // the dictionary built on the device) for VCF text
 static bool info_kind_decoded_on_gpu(const exon_hip_scan* s, char kind) { return exon::info_kind_on_device(kind) || (kind == 's' && s->format == EXON_HIP_FORMAT_VCF); }
 
-static exon::Dictionary* dict_of(exon_hip_scan* s, int col) {
+// the host reader's dictionary of child `col` of the scan's batches
+static exon::Dictionary* host_dict_of(exon_hip_scan* s, int col) {
   if (exon::GFFBatchReader* g = s->gff()) {
-    if (col >= 0 && col < 3) return s->parser.owns_names ? &s->gpu_gff_dicts[col] : &g->dicts[col];
+    if (col >= 0 && col < 3) return &g->dicts[col];
     return col == 6 ? &g->strand_dict : col == 7 ? &g->phase_dict : nullptr;
   }
   if (exon::BEDBatchReader* b = s->bed()) {  // column 0, and strand's column when it is projected
-    if (col == 0) return s->parser.owns_names ? &s->gpu_gff_dicts[0] : &b->dict;
+    if (col == 0) return &b->dict;
     return col >= 3 && col == exon::BEDBatchReader::scan_column(s->opt.projection, 5) ? &b->strand_dict : nullptr;
   }
   if (!s->vcf_like()) {
@@ -268,12 +267,74 @@ static exon::Dictionary* dict_of(exon_hip_scan* s, int col) {
     return refs && col == 2 ? &s->bam_dict_view : nullptr;
   }
   if (col == 0) return &s->chrom_dict();
-  if (col == 3) return s->parser.owns_names ? &s->gpu_filter_dict : &s->host_filter_dict();
+  if (col == 3) return &s->host_filter_dict();
   // string INFO fields (scan columns 4 ..) are dictionary-encoded by the host readers
   const std::vector<exon::InfoSpec>& specs = s->info_specs();
   if (col >= 4 && (size_t)(col - 4) < specs.size() && (specs[(size_t)(col - 4)].kind == 's' || specs[(size_t)(col - 4)].kind == 'S'))
     return &s->info_dicts()[(size_t)(col - 4)];
   return nullptr;
+}
+// child `col` of the scan's batches: where the device parser builds the dictionary, the names the scan has adopted from it
+static exon::Dictionary* dict_of(exon_hip_scan* s, int col) {
+  const exon::SlabLayout& L = s->layout;
+  if (s->parser.owns_names && col >= 0 && col < L.n_children && L.children[col].kind == exon::SlabChild::FIXED && L.cols[L.children[col].index].device_names)
+    return &s->names[(size_t)L.children[col].index];
+  return host_dict_of(s, col);
+}
+// the host reader's names of fixed column c (one of the layout's dictionary columns)
+static const std::vector<std::string>& host_names_of(exon_hip_scan* s, int c) { return host_dict_of(s, s->layout.cols[c].child)->names; }
+// the device-built dictionaries of a finished consume become the scan's
+static void adopt_names(exon_hip_scan* s, std::vector<std::vector<std::string>>* by_column) {
+  for (size_t c = 0; c < by_column->size() && c < s->names.size(); ++c)
+    if (s->layout.cols[c].device_names) s->names[c].names.swap((*by_column)[c]);
+  by_column->clear();
+}
+
+// What the scan's batches look like (host/slab_export.h): the fixed-width columns the device parser fills (parse_slab), their
+// dictionaries, and the children of a batch in the schema's order.  The one place that knows this per format.
+static exon::SlabLayout slab_layout(const exon_hip_scan& s) {
+  exon::SlabLayout L;
+  L.region_col = 0;
+  switch (s.format) {
+    case EXON_HIP_FORMAT_VCF:
+    case EXON_HIP_FORMAT_BCF:
+      L.add("HlfD");  // 0 chrom 1 pos 2 qual 3 filter 4.. the typed INFO fields
+      for (size_t k = 0, key = 0; k < s.info_specs().size() && k < (size_t)EXON_HIP_MAX_INFO_FIELDS; ++k) {
+        const char kind = s.info_specs()[k].kind;
+        // a String key of VCF text: ids, the dictionary built on the device; `field` its place in the parser's key list (no String lists there)
+        const bool ids = kind == 's' && s.format == EXON_HIP_FORMAT_VCF;
+        L.add(kind == 'b' ? exon::SlabColumn::FLAG : kind == 'f' ? exon::SlabColumn::F32 : exon::SlabColumn::I32, ids, ids, (int)key);
+        key += kind != 'S';
+      }
+      break;
+    case EXON_HIP_FORMAT_BAM:
+    case EXON_HIP_FORMAT_SAM:
+    case EXON_HIP_FORMAT_CRAM:
+      L.add("iCHll");  // 0 flag 1 mapq 2 reference 3 start 4 end
+      L.region_col = 2;
+      break;
+    case EXON_HIP_FORMAT_GFF:
+    case EXON_HIP_FORMAT_GTF:
+      L.add("DDDllfHH");     // 0 seqname 1 source 2 type 3 start 4 end 5 score 6 strand 7 phase
+      L.text_unkept = true;  // `attributes`: field 9 of every record is validated, kept or not (host/gff.h)
+      break;
+    case EXON_HIP_FORMAT_BED: {
+      // 0 reference_sequence_name 1 start 2 end, then score and strand when projected; the schema wants `name` (the text column) in
+      // front of those two and columns 6 .. 11 (NULL on every row) behind them
+      const uint64_t proj = s.opt.projection;
+      L.add("Dll");
+      for (int c = 0; c < 3; ++c) L.child(exon::SlabChild::FIXED, c);
+      if (proj & EXON_HIP_PROJECT_BED_NAME) L.child(exon::SlabChild::TEXT, 0);
+      if (proj & EXON_HIP_PROJECT_BED_SCORE) L.child(exon::SlabChild::FIXED, L.add(exon::SlabColumn::I64, false, false, 4));
+      if (proj & EXON_HIP_PROJECT_BED_STRAND) L.child(exon::SlabChild::FIXED, L.add(exon::SlabColumn::I32, true, false, 5));
+      for (int c = 6; c < 12; ++c)
+        if (proj & (1ull << c)) L.child(exon::bed_fields()[c].fmt[0] == 'u' ? exon::SlabChild::NULL_UTF8 : exon::SlabChild::NULL_I64, c);
+      return L;
+    }
+    default: L.region_col = -1;  // FASTQ / FASTA: text columns alone (export_fastq_slab)
+  }
+  L.plain_children();
+  return L;
 }
 
 static exon::Compression compression_of(const exon_hip_scan_options& o) {
@@ -480,6 +541,8 @@ int exon_hip_scan_open(const char* path, const exon_hip_scan_options* o, exon_hi
     }
     if (!s->vcf_like())
       if (const std::vector<std::string>* refs = contig_names(s.get())) s->bam_dict_view.names = *refs;
+    s->layout = slab_layout(*s);
+    s->names.resize((size_t)s->layout.n_cols);
     *out = s.release();
     return EXON_HIP_OK;
   } catch (const exon::UnsupportedError& e) {
@@ -1844,95 +1907,54 @@ static void region_target(const exon_hip_scan* scan, int32_t* id, int64_t* a, in
   *range_form = !scan->vcf_like();
 }
 
-// FILTER dictionary of the device parser, names in id order.  so_far: also after the table overflowed, the names assigned
-// before (the exporter's names of a slab whose successor overflowed: that hand-over is not an error)
-static int gpu_filter_names(exon_hip_scan* scan, std::vector<std::string>* names, bool so_far = false) {
-  names->clear();
-  int rc = EXON_HIP_OK;
-  if (!scan->parser.owns_names) return rc;
-  if (exon::BCFBatchReader* bcf = scan->bcf()) {
-    exon_hip_bcf_parser* p = scan->parser.as<exon_hip_bcf_parser>();
-    int32_t nf = 0;
-    auto fetch = so_far ? exon_hip_bcf_parser_filters_so_far : exon_hip_bcf_parser_filters;
-    rc = fetch(p, nullptr, nullptr, 0, &nf);
-    std::vector<int32_t> lists((size_t)std::max(nf, 1) * 8), counts((size_t)std::max(nf, 1));
-    if (!rc) rc = fetch(p, lists.data(), counts.data(), nf, &nf);
-    if (rc) return rc;
-    const std::vector<std::string>& strs = bcf->strings();
-    for (int32_t i = 0; i < nf; ++i) {
-      std::string name;
-      for (int32_t k = 0; k < counts[(size_t)i]; ++k) {
-        if (k) name += ';';
-        name += strs[(size_t)lists[(size_t)i * 8 + (size_t)k]];
-      }
-      names->push_back(name);
+// BCF: the device parser's FILTER lists are lists of header string ids; a list's name joins its strings with ';'
+static int bcf_filter_names(exon_hip_scan* scan, bool so_far, std::vector<std::string>* names) {
+  exon_hip_bcf_parser* p = scan->parser.as<exon_hip_bcf_parser>();
+  int32_t nf = 0;
+  int rc = exon_bcf_parser_filter_lists(p, nullptr, nullptr, 0, &nf, so_far);
+  std::vector<int32_t> lists((size_t)std::max(nf, 1) * 8), counts((size_t)std::max(nf, 1));
+  if (!rc) rc = exon_bcf_parser_filter_lists(p, lists.data(), counts.data(), nf, &nf, so_far);
+  if (rc) return rc;
+  const std::vector<std::string>& strs = scan->bcf()->strings();
+  for (int32_t i = 0; i < nf; ++i) {
+    std::string name;
+    for (int32_t k = 0; k < counts[(size_t)i]; ++k) {
+      if (k) name += ';';
+      name += strs[(size_t)lists[(size_t)i * 8 + (size_t)k]];
     }
-  } else {
-    int32_t nf = 0;
-    std::vector<char> buf(EXON_DICT_NAMES_CAP);
-    rc = (so_far ? exon_hip_vcf_parser_filters_so_far : exon_hip_vcf_parser_filters)(scan->parser.as<exon_hip_vcf_parser>(), buf.data(), buf.size(), &nf);
+    names->push_back(name);
+  }
+  return EXON_HIP_OK;
+}
+// The dictionaries the device parser has built, by scan column (the layout's device_names columns; names in id order).  so_far: also
+// after a table overflowed, the names assigned before (the exporter's names of a slab whose successor overflowed: that hand-over is
+// not an error)
+static int device_names(exon_hip_scan* scan, bool so_far, std::vector<std::vector<std::string>>* by_column) {
+  const exon::SlabLayout& L = scan->layout;
+  by_column->assign((size_t)L.n_cols, {});
+  if (!scan->parser.owns_names) return EXON_HIP_OK;
+  std::vector<char> buf(EXON_DICT_NAMES_CAP);  // a table's names, NUL-separated
+  for (int c = 0; c < L.n_cols; ++c) {
+    if (!L.cols[c].device_names) continue;
+    std::vector<std::string>& names = (*by_column)[(size_t)c];
+    int32_t n = 0;
+    int rc = EXON_HIP_OK;
+    switch (scan->format) {
+      case EXON_HIP_FORMAT_VCF:
+        if (c == 3) rc = exon_vcf_parser_filter_names(scan->parser.as<exon_hip_vcf_parser>(), buf.data(), buf.size(), &n, so_far);
+        else rc = exon_vcf_parser_info_value_names(scan->parser.as<exon_hip_vcf_parser>(), L.cols[c].field, buf.data(), buf.size(), &n, so_far);
+        break;
+      case EXON_HIP_FORMAT_BCF: rc = bcf_filter_names(scan, so_far, &names); break;
+      case EXON_HIP_FORMAT_GFF:
+      case EXON_HIP_FORMAT_GTF: rc = exon_gff_parser_column_names(scan->parser.as<exon_hip_gff_parser>(), c, buf.data(), buf.size(), &n, so_far); break;
+      case EXON_HIP_FORMAT_BED: rc = exon_bed_parser_reference_names(scan->parser.as<exon_hip_bed_parser>(), buf.data(), buf.size(), &n, so_far); break;
+    }
     if (rc) return rc;
     size_t o = 0;
-    for (int32_t i = 0; i < nf; ++i) {
-      names->emplace_back(buf.data() + o);
-      o += names->back().size() + 1;
+    for (int32_t i = 0; i < n; ++i) {
+      names.emplace_back(buf.data() + o);
+      o += names.back().size() + 1;
     }
-  }
-  return rc;
-}
-
-// GFF: the device parser's dictionary of column 0 (seqname), 1 (source) or 2 (type), names in id order
-static int gpu_gff_names(exon_hip_scan* scan, int column, std::vector<std::string>* names, bool so_far) {
-  names->clear();
-  int32_t nn = 0;
-  std::vector<char> buf(EXON_DICT_NAMES_CAP);
-  const int rc = (so_far ? exon_hip_gff_parser_names_so_far : exon_hip_gff_parser_names)(scan->parser.as<exon_hip_gff_parser>(), column, buf.data(), buf.size(), &nn);
-  if (rc) return rc;
-  size_t o = 0;
-  for (int32_t i = 0; i < nn; ++i) {
-    names->emplace_back(buf.data() + o);
-    o += names->back().size() + 1;
-  }
-  return rc;
-}
-
-// BED: the device parser's reference_sequence_name dictionary, names in id order
-static int gpu_bed_names(exon_hip_scan* scan, std::vector<std::string>* names, bool so_far) {
-  names->clear();
-  int32_t nn = 0;
-  std::vector<char> buf(EXON_DICT_NAMES_CAP);
-  const int rc = (so_far ? exon_hip_bed_parser_names_so_far : exon_hip_bed_parser_names)(scan->parser.as<exon_hip_bed_parser>(), buf.data(), buf.size(), &nn);
-  if (rc) return rc;
-  size_t o = 0;
-  for (int32_t i = 0; i < nn; ++i) {
-    names->emplace_back(buf.data() + o);
-    o += names->back().size() + 1;
-  }
-  return rc;
-}
-
-// the value dictionaries of the String INFO keys the device decoded (VCF text): names[k] for scan column 4 + k (empty for other kinds)
-static int gpu_info_names(exon_hip_scan* scan, std::vector<std::vector<std::string>>* names, bool so_far = false) {
-  names->clear();
-  if (!scan->vcf() || !scan->parser.owns_names) return EXON_HIP_OK;
-  const std::vector<exon::InfoSpec>& specs = scan->vcf()->info_specs;
-  names->resize(specs.size());
-  int q = 0;
-  std::vector<char> buf;
-  for (size_t k = 0; k < specs.size(); ++k) {
-    if (specs[k].kind == 'S') continue;
-    if (specs[k].kind == 's') {
-      int32_t nv = 0;
-      buf.resize(EXON_DICT_NAMES_CAP);
-      const int rc = (so_far ? exon_hip_vcf_parser_info_values_so_far : exon_hip_vcf_parser_info_values)(scan->parser.as<exon_hip_vcf_parser>(), q, buf.data(), buf.size(), &nv);
-      if (rc) return rc;
-      size_t o = 0;
-      for (int32_t i = 0; i < nv; ++i) {
-        (*names)[k].emplace_back(buf.data() + o);
-        o += (*names)[k].back().size() + 1;
-      }
-    }
-    ++q;
   }
   return EXON_HIP_OK;
 }
@@ -1986,6 +2008,16 @@ void export_block_put(void* p, size_t bytes) {
   }
   hipHostFree(drop);
 }
+// a pinned block of at least `bytes` with one reference, the caller's (nullptr: none to be had)
+exon::SharedBlock* new_export_block(size_t bytes) {
+  void* p = export_block_get(&bytes);
+  if (!p) return nullptr;
+  exon::SharedBlock* sb = new exon::SharedBlock();
+  sb->block = p;
+  sb->bytes = bytes;
+  sb->put = export_block_put;
+  return sb;
+}
 }  // namespace
 
 // One slab's device columns -> one pinned host block -> batch_size-row Arrow batches on the exporter's queue.  Without a region
@@ -1995,9 +2027,7 @@ void export_block_put(void* p, size_t bytes) {
 // staged by the runtime at a tenth of the link's rate): per-batch arrays are cut out of these
 struct HostText {
   ExonTextColumns cols;  // the device-built columns with their buffers where they lie in the block (host/text_export.h: text_place)
-  void* blk = nullptr;
-  size_t blk_bytes = 0;
-  exon::SharedBlock* sb = nullptr;  // the block, shared with the batches that are views into it
+  exon::SharedBlock* sb = nullptr;  // the pinned block, shared with the batches that are views into it
   ~HostText() { exon::block_unref(sb); }
 };
 // EXON_HIP_PIPE_TRACE: where a slab's export spends its time (seconds; per producer thread: every scan's pipeline runs in its own)
@@ -2014,16 +2044,11 @@ static int fetch_text(exon_hip_ctx* ctx, SlabCopier* cp, size_t also_reserve, co
   const exon::TextPlan plan = exon::text_plan(dev, big_batches);
   const size_t total = plan.total;
   if (!cp->reserve(total + 256 * plan.copies.size() + also_reserve)) return fail(ctx, EXON_HIP_ENOMEM, "no device staging buffer of %zu bytes for a slab's string columns", total);
-  h->blk_bytes = total;
   const double tb0 = now_s();
-  h->blk = export_block_get(&h->blk_bytes);
+  h->sb = new_export_block(total);
   g_t_block_get += now_s() - tb0;
-  if (!h->blk) return fail(ctx, EXON_HIP_ENOMEM, "no pinned block of %zu bytes for a slab's string columns", total);
-  h->sb = new exon::SharedBlock();
-  h->sb->block = h->blk;
-  h->sb->bytes = h->blk_bytes;
-  h->sb->put = export_block_put;
-  uint8_t* blk = static_cast<uint8_t*>(h->blk);
+  if (!h->sb) return fail(ctx, EXON_HIP_ENOMEM, "no pinned block of %zu bytes for a slab's string columns", total);
+  uint8_t* blk = static_cast<uint8_t*>(h->sb->block);
   for (const exon::TextCopy& c : plan.copies) {
     if (c.src) cp->add(blk + c.at, c.src, c.bytes);
     else memset(blk + c.at, 0, c.bytes);
@@ -2073,141 +2098,62 @@ static int push_batch(GpuExporter* ex, struct ArrowArray* out, int64_t n) {
 static int export_slab(exon_hip_scan* scan, const exon_hip_column* sc, int64_t n_rows, const uint8_t* row_mask, hipStream_t hs, SlabText* projected) {
   GpuExporter* ex = scan->exporter;
   exon_hip_ctx* ctx = ex->ctx;
+  const exon::SlabLayout& L = scan->layout;
   // A pushed-down region: the row mask comes back first.  A slab that keeps nothing sends nothing else; when the kept rows are
   // ONE run of consecutive rows (sorted files: every indexed file, and the reference's own benchmark query,
   // exon-benchmarks/src/main.rs:143-157) only that run's part of every column crosses PCIe and goes out as views like an
   // unfiltered slab; rows kept here and there are gathered from the whole slab.
   std::vector<uint8_t> hmask;
-  int64_t run_lo = 0, run_hi = n_rows;  // the span of rows that go out as views ...
-  std::vector<std::pair<int64_t, int64_t>> runs;  // ... and the runs inside it (one run = the whole span without a mask)
-  bool as_views = !row_mask;
+  std::vector<std::pair<int64_t, int64_t>> runs;  // the runs of rows that go out as views (without a mask: the whole slab); empty: gathered
   if (row_mask) {
     hmask.resize((size_t)(n_rows + 7) / 8);
     if (hipMemcpyAsync(hmask.data(), row_mask, hmask.size(), hipMemcpyDeviceToHost, hs) != hipSuccess || hipStreamSynchronize(hs) != hipSuccess)
       return fail(ctx, EXON_HIP_EDEVICE, "row mask of a slab back to the host");
     if (n_rows & 7) hmask.back() &= (uint8_t)((1u << (n_rows & 7)) - 1u);
-    // the runs of consecutive kept rows: one for a point region over a sorted file, a handful when reads that reach into the
-    // region from the left are interleaved with reads that do not (SemiLazyRecord::intersects is an overlap test)
-    int64_t kept = 0;
-    bool too_many = false;
-    constexpr size_t MAX_RUNS = 256;
-    int64_t open_lo = -1;
-    for (size_t byte = 0; byte < hmask.size() && !too_many; ++byte) {
-      const uint8_t m = hmask[byte];
-      if (m == 0xFF) {
-        if (open_lo < 0) open_lo = (int64_t)byte * 8;
-        kept += 8;
-        continue;
-      }
-      if (m == 0 && open_lo < 0) continue;
-      for (int b = 0; b < 8; ++b) {
-        const int64_t r = (int64_t)byte * 8 + b;
-        if ((m >> b) & 1) {
-          if (open_lo < 0) open_lo = r;
-          ++kept;
-        } else if (open_lo >= 0) {
-          runs.emplace_back(open_lo, r);
-          open_lo = -1;
-          if (runs.size() > MAX_RUNS) too_many = true;
-        }
-      }
-    }
-    if (open_lo >= 0) runs.emplace_back(open_lo, n_rows);
-    if (too_many) {  // (kept is not complete then: the gather below counts for itself)
-      runs.clear();
-    } else if (kept == 0) {
-      // GFF `attributes`: field 9 of every record is validated, kept or not (host/gff.h) -- the measure pass runs over a slab that
-      // sends nothing too, and hands the file over when it meets a row the host reader must judge
-      if (projected && scan->gff())
+    exon::SlabRuns kept = exon::slab_runs(hmask.data(), n_rows);
+    if (!kept.too_many && kept.kept == 0) {  // (the text columns that validate every record are built all the same)
+      if (projected && L.text_unkept)
         if (const int rc = projected->build()) return rc;
       return EXON_HIP_OK;
     }
     const char* gv = getenv("EXON_HIP_EXPORT_GATHER");  // A/B, read for every slab: 1 = every filtered slab through the row-by-row gather
-    const bool gather_forced = gv && gv[0] == '1';
-    if (!too_many && !gather_forced) {
-      as_views = true;
-      run_lo = runs.front().first;
-      run_hi = runs.back().second;
-    } else {
-      runs.clear();
-    }
+    if (!kept.too_many && !(gv && gv[0] == '1')) runs.swap(kept.runs);
+  } else {
+    runs.emplace_back(0, n_rows);
   }
+  const bool as_views = !runs.empty();
   if (const int rc = export_flush(scan)) return rc;  // the slab before this one
   SlabCopier cp(ex, hs);
   ++ex->n_exports;
   auto text_p = std::make_shared<HostText>();
-  HostText& text = *text_p;
   const double tc0 = now_s();
-  const bool vcf_like = scan->vcf_like();
-  const std::vector<exon::InfoSpec>* specs = vcf_like ? &scan->info_specs() : nullptr;
-  const bool gff = scan->gff() != nullptr;
-  // BED: the fixed-width columns are 0 reference_sequence_name, 1 start, 2 end, then score and strand when projected (parse_slab);
-  // `name` is the text column, columns 6 .. 11 are NULL on every row; bed_order() puts a batch's arrays into the schema's order
-  const bool bed = scan->bed() != nullptr;
-  const uint64_t bed_proj = bed ? scan->opt.projection : 0;
-  const int bed_score = (bed_proj & EXON_HIP_PROJECT_BED_SCORE) ? 3 : -1, bed_strand = (bed_proj & EXON_HIP_PROJECT_BED_STRAND) ? (bed_score < 0 ? 3 : 4) : -1;
-  const bool bed_nulls = (bed_proj >> 6) != 0;
-  const int n_cols = vcf_like ? 4 + (int)specs->size() : gff ? 8 : bed ? 3 + (bed_score >= 0) + (bed_strand >= 0) : 5;
-  // element widths in the scan's column order (0 = no values: a Flag, whose bitmap is its value)
-  std::vector<int> elem((size_t)n_cols, 4);
-  if (vcf_like) {
-    elem[1] = 8;
-    for (size_t k = 0; k < specs->size(); ++k) elem[4 + k] = (*specs)[k].kind == 'b' ? 0 : 4;
-  } else if (gff) {
-    elem[3] = elem[4] = 8;
-  } else if (bed) {
-    elem[1] = elem[2] = 8;
-    if (bed_score >= 0) elem[(size_t)bed_score] = 8;
-  } else {
-    elem[1] = 1;
-    elem[3] = elem[4] = 8;
-  }
-  // rows [c_lo, c_hi) of every column come back (c_lo a multiple of 8: bitmaps are cut at a byte)
-  const int64_t c_lo = as_views ? (run_lo & ~int64_t(7)) : 0, c_hi = as_views ? run_hi : n_rows, c_n = c_hi - c_lo;
-  const size_t nb = ((size_t)(c_n + 7) / 8 + 63) & ~size_t(63);
-  std::vector<size_t> voff((size_t)n_cols, 0), boff((size_t)n_cols, 0);
-  size_t bytes = 0;
-  for (int c = 0; c < n_cols; ++c) {
-    voff[(size_t)c] = bytes;
-    bytes += (((size_t)c_n * (size_t)elem[(size_t)c]) + 63) & ~size_t(63);
-    boff[(size_t)c] = bytes;
-    bytes += nb;
-  }
-  const size_t moff = bytes;
-  bytes += nb;
-  // BED columns 6 .. 11: one run of zeros serves them all as validity bitmap (every row NULL), offsets and values
-  const size_t zoff = bytes, zbytes = bed_nulls ? (((size_t)c_n + 1) * 8 + 63) & ~size_t(63) : 0;
-  bytes += zbytes;
-  const size_t path_stage = bytes + 512 * (size_t)n_cols;
+  // rows [c_lo, c_hi) of every column come back: the span of the runs, or the whole slab for the gather
+  exon::SlabPlan plan = as_views ? exon::slab_plan(L, runs.front().first, runs.back().second) : exon::slab_plan(L, 0, n_rows);
+  const size_t path_stage = plan.bytes + 512 * (size_t)L.n_cols;
   if (projected) {
     int rc = projected->build();  // the device builds the text columns now
     if (rc) return rc;
     const double tf0 = now_s();
-    rc = fetch_text(ctx, &cp, path_stage, projected->cols, &text, scan->opt.batch_size > exon::K_ZERO_ROWS);
+    rc = fetch_text(ctx, &cp, path_stage, projected->cols, text_p.get(), scan->opt.batch_size > exon::K_ZERO_ROWS);
     g_t_fetch_text += now_s() - tf0;
     if (rc) return rc;
   } else if (!cp.reserve(path_stage)) {
     return fail(ctx, EXON_HIP_ENOMEM, "no device staging buffer of %zu bytes for a slab's columns", path_stage);
   }
-  size_t blk_bytes = bytes;
-  uint8_t* blk = static_cast<uint8_t*>(export_block_get(&blk_bytes));
-  if (!blk) return fail(ctx, EXON_HIP_ENOMEM, "no pinned block of %zu bytes for a slab's columns", bytes);
-  exon::SharedBlock* sb = new exon::SharedBlock();
-  sb->block = blk;
-  sb->bytes = blk_bytes;
-  sb->put = export_block_put;
+  exon::SharedBlock* sb = new_export_block(plan.bytes);
+  if (!sb) return fail(ctx, EXON_HIP_ENOMEM, "no pinned block of %zu bytes for a slab's columns", plan.bytes);
+  uint8_t* blk = static_cast<uint8_t*>(sb->block);
   std::shared_ptr<exon::SharedBlock> sb_ref(sb, [](exon::SharedBlock* b) { exon::block_unref(b); });  // this slab's own reference
-  std::vector<bool> has_bits((size_t)n_cols, false);
-  for (int c = 0; c < n_cols; ++c) {
-    if (elem[(size_t)c] && sc[c].values)
-      cp.add(blk + voff[(size_t)c], static_cast<const uint8_t*>(sc[c].values) + (size_t)c_lo * (size_t)elem[(size_t)c], (size_t)c_n * (size_t)elem[(size_t)c]);
+  for (int c = 0; c < L.n_cols; ++c) {
+    const size_t w = (size_t)L.cols[c].width();
+    if (w && sc[c].values) cp.add(blk + plan.voff[c], static_cast<const uint8_t*>(sc[c].values) + (size_t)plan.c_lo * w, (size_t)plan.c_n * w);
     if (sc[c].validity) {
-      cp.add(blk + boff[(size_t)c], sc[c].validity + (c_lo >> 3), (size_t)(c_n + 7) / 8);
-      has_bits[(size_t)c] = true;
+      cp.add(blk + plan.boff[c], sc[c].validity + (plan.c_lo >> 3), plan.bits_bytes());
+      plan.has_bits |= 1u << c;
     }
   }
-  if (row_mask && !as_views) memcpy(blk + moff, hmask.data(), hmask.size());
-  if (zbytes) memset(blk + zoff, 0, zbytes);
+  if (!as_views) memcpy(blk + plan.moff, hmask.data(), hmask.size());
+  if (plan.zbytes) memset(blk + plan.zoff, 0, plan.zbytes);
   const hipError_t e = cp.launch();
   if (e != hipSuccess) return fail(ctx, EXON_HIP_EDEVICE, "columns of a slab towards the host: %s", hipGetErrorString(e));
   g_t_fetch_cols += now_s() - tc0;
@@ -2215,131 +2161,46 @@ static int export_slab(exon_hip_scan* scan, const exon_hip_column* sc, int64_t n
   const int64_t bs = scan->opt.batch_size > 0 ? scan->opt.batch_size : 8192;
   // ---- everything below runs when the NEXT slab arrives (or the scan ends): by then the copies have landed -----------------------
   ex->pending = [=]() mutable -> int {
-  (void)sb_ref;  // (the slab's own reference to its block lives as long as this closure)
-  if (hipEventSynchronize(ex->ev_done[slot]) != hipSuccess) return fail(ctx, EXON_HIP_EDEVICE, "columns of a slab back to the host: the copy failed");
-  const HostText& text = *text_p;
-  const double tn0 = now_s();
-  std::vector<std::string> filters;
-  // (so far: the next slab, parsed by now, may have overflowed a table and handed the scan over; this slab's ids come first)
-  if (vcf_like) {
-    const int rc = gpu_filter_names(scan, &filters, true);
-    if (rc) return rc;
-  }
-  std::vector<std::vector<std::string>> info_names;
-  if (scan->vcf()) {
-    const int rc = gpu_info_names(scan, &info_names, true);
-    if (rc) return rc;
-  }
-  std::vector<std::string> gff_names[3];
-  for (int k = 0; gff && k < 3; ++k)
-    if (const int rc = gpu_gff_names(scan, k, &gff_names[k], true)) return rc;
-  std::vector<std::string> bed_names;
-  if (bed)
-    if (const int rc = gpu_bed_names(scan, &bed_names, true)) return rc;
-  g_t_names += now_s() - tn0;
-  // the dictionaries of this slab's batches: built once, shared by every batch's column
-  auto dicts_p = std::make_shared<std::vector<std::shared_ptr<const exon::SharedUtf8>>>((size_t)n_cols);
-  std::vector<std::shared_ptr<const exon::SharedUtf8>>& dicts = *dicts_p;
-  for (int c = 0; c < n_cols; ++c) {
-    if (vcf_like && c == 0) dicts[(size_t)c] = std::make_shared<const exon::SharedUtf8>(scan->chrom_dict().names);
-    else if (vcf_like && c == 3) dicts[(size_t)c] = std::make_shared<const exon::SharedUtf8>(filters);
-    else if (scan->vcf() && c >= 4 && (size_t)(c - 4) < info_names.size() && (*specs)[(size_t)(c - 4)].kind == 's')
-      dicts[(size_t)c] = std::make_shared<const exon::SharedUtf8>(info_names[(size_t)(c - 4)]);
-    else if (gff && c < 3) dicts[(size_t)c] = std::make_shared<const exon::SharedUtf8>(gff_names[c]);
-    else if (gff && (c == 6 || c == 7)) dicts[(size_t)c] = std::make_shared<const exon::SharedUtf8>(c == 6 ? exon::gff_strand_names() : exon::gff_phase_names());
-    else if (bed && c == 0) dicts[(size_t)c] = std::make_shared<const exon::SharedUtf8>(bed_names);
-    else if (bed && c == bed_strand) dicts[(size_t)c] = std::make_shared<const exon::SharedUtf8>(exon::gff_strand_names());
-    else if (!vcf_like && !gff && !bed && c == 2) dicts[(size_t)c] = std::make_shared<const exon::SharedUtf8>(scan->bam_dict_view.names);
-  }
-  // BED: `kids` holds the fixed-width columns and then the name; the schema wants name in front of score and strand, and the NULL columns
-  // behind them.  null_of(c, n): n NULL rows of schema column c
-  auto bed_order = [&](std::vector<struct ArrowArray*>* kids, int64_t n, const std::function<struct ArrowArray*(int, int64_t)>& null_of) {
-    std::vector<struct ArrowArray*> out(kids->begin(), kids->begin() + 3);
-    if (bed_proj & EXON_HIP_PROJECT_BED_NAME) out.push_back(kids->back());
-    if (bed_score >= 0) out.push_back((*kids)[(size_t)bed_score]);
-    if (bed_strand >= 0) out.push_back((*kids)[(size_t)bed_strand]);
-    for (int c = 6; c < 12; ++c)
-      if (bed_proj & (1ull << c)) out.push_back(null_of(c, n));
-    kids->swap(out);
-  };
-  auto dict_of_col = [&](int c) -> struct ArrowArray* { return dicts[(size_t)c] ? exon::shared_utf8_array(dicts[(size_t)c]) : nullptr; };
-  if (as_views) {
+    (void)sb_ref;  // (the slab's own reference to its block lives as long as this closure)
+    if (hipEventSynchronize(ex->ev_done[slot]) != hipSuccess) return fail(ctx, EXON_HIP_EDEVICE, "columns of a slab back to the host: the copy failed");
+    const HostText& text = *text_p;
+    const double tn0 = now_s();
+    // (so far: the next slab, parsed by now, may have overflowed a table and handed the scan over; this slab's ids come first)
+    std::vector<std::vector<std::string>> names;
+    if (const int rc = device_names(scan, true, &names)) return rc;
+    g_t_names += now_s() - tn0;
+    // the dictionaries of this slab's batches: built once, shared by every batch's column
+    auto dicts_p = std::make_shared<exon::SlabDicts>((size_t)L.n_dicts);
+    for (int c = 0; c < L.n_cols; ++c)
+      if (L.cols[c].dict >= 0) (*dicts_p)[(size_t)L.cols[c].dict] = std::make_shared<const exon::SharedUtf8>(L.cols[c].device_names ? names[(size_t)c] : host_names_of(scan, c));
     struct Tm {
       double t0 = now_s();
       ~Tm() { g_t_batches += now_s() - t0; }
     } tm;
-    if (runs.empty()) runs.emplace_back(run_lo, run_hi);
+    // views of the runs' rows -- or the rows the pushed-down region keeps here and there, gathered: one "run" over their list
+    const std::vector<int64_t> keep = as_views ? std::vector<int64_t>() : exon::slab_kept_rows(blk + plan.moff, n_rows);
+    if (!as_views) runs.emplace_back(0, (int64_t)keep.size());
+    std::vector<struct ArrowArray*> kids, text_kids;
     for (const auto& run : runs)
-    for (int64_t b0 = run.first; b0 < run.second; b0 += bs) {
-      const int64_t n = std::min(run.second, b0 + bs) - b0;
-      std::vector<struct ArrowArray*> kids;
-      const double tv0 = now_s();
-      // every array of the batch out of one allocation (exon::BatchArena): per column its array + its dictionary, the text
-      // columns' nodes, BED's NULL columns, the struct itself
-      exon::BatchArena* arena = exon::new_batch_arena(2 * n_cols + text.cols.n_nodes + __builtin_popcountll(bed_proj >> 6) + 1, n_cols + 12, sb, text.sb, dicts_p);
-      for (int c = 0; c < n_cols; ++c) {
-        const void* bits = has_bits[(size_t)c] ? blk + boff[(size_t)c] : nullptr;
-        const void* vals = elem[(size_t)c] ? (const void*)(blk + voff[(size_t)c]) : bits;  // a Flag: true where present
-        struct ArrowArray* dict = dicts[(size_t)c] ? exon::arena_dictionary(arena, *dicts[(size_t)c]) : nullptr;
-        kids.push_back(exon::arena_array(arena, n, b0 - c_lo, bits ? -1 : 0, 2, bits, vals, nullptr, nullptr, dict));
+      for (int64_t b0 = run.first; b0 < run.second; b0 += bs) {
+        const int64_t n = std::min(run.second, b0 + bs) - b0;
+        const int64_t* rows = as_views ? nullptr : keep.data() + b0;
+        const double tv0 = now_s();
+        // the views of a batch come out of one allocation (exon::BatchArena)
+        exon::BatchArena* arena = as_views ? exon::new_batch_arena(L.view_nodes() + text.cols.n_nodes, L.n_children, sb, text.sb, dicts_p) : nullptr;
+        text_kids.clear();
+        text_batch(text, rows, b0, n, &text_kids, arena);
+        const double tv1 = now_s();
+        g_t_text_batch += tv1 - tv0;
+        kids.clear();
+        exon::slab_batch(arena, L, plan, blk, *dicts_p, rows, b0, n, text_kids, &kids);
+        g_t_views += now_s() - tv1;
+        struct ArrowArray* out = static_cast<struct ArrowArray*>(malloc(sizeof *out));
+        if (arena) exon::make_struct_of_arena(out, n, arena, kids);
+        else exon::make_struct(out, n, kids);
+        if (const int rc = push_batch(ex, out, n)) return rc;
       }
-      const double tv1 = now_s();
-      g_t_views += tv1 - tv0;
-      text_batch(text, nullptr, b0, n, &kids, arena);
-      if (bed)  // (a NULL column: every buffer the same zeros; Utf8 has three of them)
-        bed_order(&kids, n, [&](int c, int64_t m) {
-          const bool utf8 = exon::bed_fields()[c].fmt[0] == 'u';
-          return exon::arena_array(arena, m, 0, m, utf8 ? 3 : 2, blk + zoff, blk + zoff, utf8 ? blk + zoff : nullptr);
-        });
-      g_t_text_batch += now_s() - tv1;
-      struct ArrowArray* out = static_cast<struct ArrowArray*>(malloc(sizeof *out));
-      exon::make_struct_of_arena(out, n, arena, kids);
-      if (const int rc = push_batch(ex, out, n)) return rc;
-    }
     return EXON_HIP_OK;
-  }
-  // rows kept by the pushed-down region filter, gathered
-  std::vector<int64_t> keep;
-  const uint8_t* mask = blk + moff;
-  for (int64_t r = 0; r < n_rows; ++r)
-    if ((mask[(size_t)(r >> 3)] >> (r & 7)) & 1) keep.push_back(r);
-  auto bit = [&](int c, int64_t r) { return !has_bits[(size_t)c] ? (uint8_t)1 : (uint8_t)((blk[boff[(size_t)c] + (size_t)(r >> 3)] >> (r & 7)) & 1); };
-  for (int64_t b0 = 0; b0 < (int64_t)keep.size(); b0 += bs) {
-    const int64_t n = std::min((int64_t)keep.size(), b0 + bs) - b0;
-    std::vector<struct ArrowArray*> kids;
-    auto prim = [&](int c, auto tag) {
-      typedef decltype(tag) T;
-      exon::PrimitiveBuilder<T> pb;
-      pb.values.resize((size_t)n);
-      pb.valid.resize((size_t)n);
-      const T* src = reinterpret_cast<const T*>(blk + voff[(size_t)c]);
-      for (int64_t i = 0; i < n; ++i) {
-        const int64_t r = keep[(size_t)(b0 + i)];
-        pb.values[(size_t)i] = src[r];
-        pb.valid[(size_t)i] = bit(c, r);
-      }
-      kids.push_back(pb.finish(dict_of_col(c)));
-    };
-    for (int c = 0; c < n_cols; ++c) {
-      if (elem[(size_t)c] == 8) prim(c, int64_t());
-      else if (elem[(size_t)c] == 1) prim(c, uint8_t());
-      else if (elem[(size_t)c] == 4 && ((gff && c == 5) || (vcf_like && (c == 2 || (c >= 4 && (*specs)[(size_t)(c - 4)].kind == 'f'))))) prim(c, float());
-      else if (elem[(size_t)c] == 4) prim(c, int32_t());
-      else {  // Flag -> Boolean: true where present, NULL elsewhere
-        std::vector<uint8_t> v((size_t)n);
-        for (int64_t i = 0; i < n; ++i) v[(size_t)i] = bit(c, keep[(size_t)(b0 + i)]);
-        struct ArrowArray* a = static_cast<struct ArrowArray*>(malloc(sizeof *a));
-        exon::make_boolean(a, v, v);
-        kids.push_back(a);
-      }
-    }
-    text_batch(text, keep.data() + b0, 0, n, &kids);
-    if (bed) bed_order(&kids, n, [](int c, int64_t m) { return exon::bed_null_column(c, (size_t)m); });
-    struct ArrowArray* out = static_cast<struct ArrowArray*>(malloc(sizeof *out));
-    exon::make_struct(out, n, std::move(kids));
-    if (const int rc = push_batch(ex, out, n)) return rc;
-  }
-  return EXON_HIP_OK;
   };
   if (getenv("EXON_HIP_EXPORT_SYNC") && getenv("EXON_HIP_EXPORT_SYNC")[0] == '1') return export_flush(scan);  // A/B: no overlap with the next slab
   return EXON_HIP_OK;
@@ -2494,8 +2355,8 @@ static int create_parser(exon_hip_scan* scan, exon_hip_ctx* ctx, int64_t max_tex
   return rc;
 }
 
-// One slab parsed on the device: the scan's columns (VCF / BCF: 0 chrom 1 pos 2 qual 3 filter 4.. info fields; BAM / SAM: 0 flag
-// 1 mapq 2 ref 3 start 4 end) with the operands of the region mask, or (FASTQ) the views of the slab's reads
+// One slab parsed on the device: the scan's fixed-width columns in the order of scan->layout (slab_layout names them per format) with
+// the operands of the region mask, or (FASTQ) the views of the slab's reads
 struct SlabParse {
   exon_hip_column sc[4 + EXON_HIP_MAX_INFO_FIELDS] = {};
   int64_t n_rows = 0, consumed = 0, n_undecided = 0;
@@ -2610,14 +2471,10 @@ static int parse_slab(exon_hip_scan* scan, hipStream_t hs, const uint8_t* d_text
       sc[0].values = cols.chrom_id;
       sc[1].values = cols.start;
       sc[2].values = cols.end;
-      int k = 3;  // batches: score and strand behind them, when projected (export_slab knows the order)
-      if (scan->exporter && (scan->opt.projection & EXON_HIP_PROJECT_BED_SCORE)) {
-        sc[k].values = cols.score;
-        sc[k++].validity = cols.score_valid;
-      }
-      if (scan->exporter && (scan->opt.projection & EXON_HIP_PROJECT_BED_STRAND)) {
-        sc[k].values = cols.strand_id;
-        sc[k++].validity = cols.strand_valid;
+      for (int c = 3; scan->exporter && c < scan->layout.n_cols; ++c) {  // batches: score and strand where the layout has them
+        const bool score = scan->layout.cols[c].field == 4;  // (slab_layout: the schema's field, 4 score, 5 strand)
+        sc[c].values = score ? (const void*)cols.score : (const void*)cols.strand_id;
+        sc[c].validity = score ? cols.score_valid : cols.strand_valid;
       }
       return EXON_HIP_OK;
     }
@@ -2870,46 +2727,11 @@ static int consume_text_gpu(exon_hip_stream* st, exon_hip_scan* scan, int64_t* r
     HIP_TRY(ctx, hipMemcpy(&kept, scan->d_region_pass, 8, hipMemcpyDeviceToHost));
     total = (int64_t)kept;
   }
-  if (rc == EXON_HIP_OK && scan->vcf_like() && scan->parser.owns_names) {  // FILTER dictionary -> scan (names in id order)
-    std::vector<std::string> names;
-    rc = gpu_filter_names(scan, &names);
-    if (!rc) {
-      if (scan->exporter) scan->exporter->final_filters.swap(names);  // (adopted by the consumer's thread at the end of the batches)
-      else scan->gpu_filter_dict.names.swap(names);
-    }
-  }
-  if (rc == EXON_HIP_OK && scan->vcf() && scan->parser.owns_names) {  // String INFO keys: their dictionaries -> scan
-    std::vector<std::vector<std::string>> info_names;
-    rc = gpu_info_names(scan, &info_names);
-    if (!rc) {
-      if (scan->exporter) {
-        scan->exporter->final_info_names.swap(info_names);
-      } else {
-        for (size_t k = 0; k < info_names.size() && k < scan->vcf()->info_dicts.size(); ++k)
-          if (scan->vcf()->info_specs[k].kind == 's') scan->vcf()->info_dicts[k].names.swap(info_names[k]);
-      }
-    }
-  }
-  if (rc == EXON_HIP_OK && scan->gff() && scan->parser.owns_names) {  // GFF: the three dictionaries the device built -> scan
-    std::vector<std::string> names[3];
-    for (int k = 0; k < 3 && !rc; ++k) rc = gpu_gff_names(scan, k, &names[k], false);
-    for (int k = 0; k < 3 && !rc; ++k) {
-      if (scan->exporter) scan->exporter->final_gff_names[k].swap(names[k]);
-      else scan->gpu_gff_dicts[k].names.swap(names[k]);
-    }
-    if (!rc && scan->exporter) scan->exporter->has_gff_names = true;
-  }
-  if (rc == EXON_HIP_OK && scan->bed() && scan->parser.owns_names) {  // BED: the dictionary the device built -> scan
-    std::vector<std::string> names;
-    rc = gpu_bed_names(scan, &names, false);
-    if (!rc) {
-      if (scan->exporter) {
-        scan->exporter->final_gff_names[0].swap(names);
-        scan->exporter->has_gff_names = true;
-      } else {
-        scan->gpu_gff_dicts[0].names.swap(names);
-      }
-    }
+  if (rc == EXON_HIP_OK && scan->parser.owns_names) {  // the dictionaries the device built -> scan
+    std::vector<std::vector<std::string>> names;
+    rc = device_names(scan, false, &names);
+    if (!rc && scan->exporter) scan->exporter->final_names.swap(names);  // (adopted by the consumer's thread at the end of the batches)
+    else if (!rc) adopt_names(scan, &names);
   }
   if (rc == EXON_HIP_OK) {
     if (scan->exporter) {
@@ -2936,9 +2758,7 @@ int exon_hip_scan_decoded_on_gpu(exon_hip_scan* scan, int32_t* decoded, int32_t*
 static int consume_scan_impl(exon_hip_stream* st, exon_hip_scan* scan, int64_t* rows);
 
 // column of the scan that holds the contig / reference dictionary a region is named in
-static int region_dict_column(const exon_hip_scan* s) {
-  return (s->format == EXON_HIP_FORMAT_VCF || s->format == EXON_HIP_FORMAT_BCF || s->gff() || s->bed()) ? 0 : 2;
-}
+static int region_dict_column(const exon_hip_scan* s) { return s->layout.region_col; }
 
 }  // extern "C"
 
@@ -3050,23 +2870,13 @@ static int gpu_next(exon_hip_scan* s, struct ArrowArray* out) {
     // the producer thread is gone: the reader that finished the file becomes the scan's (its dictionaries are the ones the
     // last batches were built with; every batch carries its dictionary values itself, so nothing emitted earlier depends on it)
     s->reader = std::move(ex->fallback);
-    if (s->vcf_like()) s->gpu_filter_dict.names = s->host_filter_dict().names;
-    if (exon::GFFBatchReader* g = s->gff())
-      for (int k = 0; k < 3; ++k) s->gpu_gff_dicts[k].names = g->dicts[k].names;
-    if (exon::BEDBatchReader* b = s->bed()) s->gpu_gff_dicts[0].names = b->dict.names;
+    for (int c = 0; c < s->layout.n_cols; ++c)  // (the parser still owns the names: they are the reader's from here on)
+      if (s->layout.cols[c].device_names) s->names[(size_t)c].names = host_names_of(s, c);
+    ex->final_names.clear();
     ex->handed_over = false;
-    ex->final_filters.clear();
-    ex->final_info_names.clear();
-    ex->has_gff_names = false;
   }
   if (ex->rc) return fail(ex->ctx, ex->rc, "%s", ex->err.c_str());
-  if (!ex->final_filters.empty()) s->gpu_filter_dict.names.swap(ex->final_filters);
-  if (exon::VCFBatchReader* vcf = s->vcf())
-    for (size_t k = 0; k < ex->final_info_names.size() && k < vcf->info_dicts.size(); ++k)
-      if (vcf->info_specs[k].kind == 's') vcf->info_dicts[k].names.swap(ex->final_info_names[k]);
-  if (ex->has_gff_names)
-    for (int k = 0; k < 3; ++k) s->gpu_gff_dicts[k].names.swap(ex->final_gff_names[k]);
-  ex->has_gff_names = false;
+  adopt_names(s, &ex->final_names);
   s->gpu_decoded = ex->decoded_on_gpu;
   s->gpu_inflated = ex->inflated_on_gpu;
   return 1;
