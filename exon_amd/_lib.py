@@ -151,6 +151,7 @@ PLAN_CMP_AVG_BY_GROUP = 4
 PLAN_QUAL_POS_HIST = 5
 PLAN_OVERLAP_COUNT = 6
 PLAN_WITHIN_COUNT = 7
+PLAN_CMP_MINMAX_BY_GROUP = 8
 LAUNCH_ACCUMULATE = 0
 LAUNCH_OVERWRITE = 1
 CMP = {">": 0, ">=": 1, "<": 2, "<=": 3, "=": 4, "==": 4, "!=": 5, "<>": 5}
@@ -183,6 +184,8 @@ SIGNATURES = {
     "exon_hip_within_count": (C.c_int, [_vp, _vp, _colp, _colp, _colp, _i64, _i32, _i64, _i64, _vp]),
     "exon_hip_flag_mapq_group_count": (C.c_int, [_vp, _vp, _colp, _colp, _colp, _i64, _i32, _i32, _i32, _i32, _vp]),
     "exon_hip_cmp_avg_by_group": (C.c_int, [_vp, _vp, _colp, _colp, _colp, _i64, _dbl, _i32, _i32, _vp, _vp]),
+    "exon_hip_cmp_minmax_by_group": (C.c_int, [_vp, _vp, _colp, _colp, _colp, _i64, _dbl, _i32, _i32, _vp]),
+    "exon_hip_minmax_decode": (C.c_int, [_vp, _i64, _i32, _i32, _vp, _vp]),
     "exon_hip_qual_pos_hist": (C.c_int, [_vp, _vp, _colp, _i64, _i32, _vp]),
     "exon_hip_gen_c6": (C.c_int, [_vp, _vp, _u64, _i64, _i64, _vp, _vp, _vp, _vp, _vp]),
     "exon_hip_gen_c2": (C.c_int, [_vp, _vp, _u64, _i64, _i64, _i64, _vp, _vp]),
@@ -198,6 +201,7 @@ SIGNATURES = {
     "exon_hip_plan_launch_chunks": (C.c_int, [_vp, _vp, _colp, _i32, _i32, _vp, _i32, _vp]),
     "exon_hip_fold_states": (C.c_int, [_vp, _vp, _vp, _i32, _i64, _i64, _vp]),
     "exon_hip_merge_states": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp]),
+    "exon_hip_plan_fold_states": (C.c_int, [_vp, _vp, _vp, _i32, _vp]),
     "exon_hip_rccl_unique_id": (C.c_int, [_vp]),
     "exon_hip_rccl_comm_init": (C.c_int, [_vp, _vp, _i32, _i32, C.POINTER(_vp)]),
     "exon_hip_rccl_comm_destroy": (C.c_int, [_vp]),

@@ -450,6 +450,31 @@ int exon_op_cmp_avg_by_group(exon_hip_ctx* ctx, void* stream, const exon_hip_col
   return EXON_HIP_OK;
 }
 
+int exon_op_cmp_minmax_by_group(exon_hip_ctx* ctx, void* stream, const exon_hip_column* x, const exon_hip_column* y,
+                                const exon_hip_column* group_id, int64_t n, double threshold, int32_t cmp_op,
+                                int32_t n_groups, int64_t* d_state, int flags) {
+  if (!ctx || !d_state) return fail(ctx, EXON_HIP_EINVAL, "exon_hip_cmp_minmax_by_group: NULL argument");
+  if (n < 0) return fail(ctx, EXON_HIP_EINVAL, "n < 0");
+  if (cmp_op < EXON_HIP_GT || cmp_op > EXON_HIP_NE) return fail(ctx, EXON_HIP_EINVAL, "bad cmp_op %d", cmp_op);
+  if (n_groups < 1) return fail(ctx, EXON_HIP_EINVAL, "n_groups must be >= 1");
+  if (n_groups > EXON_HIP_MAX_GROUPS)
+    return fail(ctx, EXON_HIP_EUNSUPPORTED, "n_groups %d > %d (MIN / MAX by group keeps its groups in the LDS table)", n_groups, EXON_HIP_MAX_GROUPS);
+  if (group_id && group_id->validity)
+    return fail(ctx, EXON_HIP_EUNSUPPORTED, "nullable group ids: encode NULL as its own dictionary id");
+  int rc;
+  if ((rc = check_col(ctx, "x", x, n, false)) || (rc = check_col(ctx, "y", y, n, false)) ||
+      (rc = check_col(ctx, "group_id", group_id, n, false)))
+    return rc;
+  hipStream_t s = pick_stream(ctx, stream);
+  if (n == 0) return empty_input(ctx, s, flags, d_state, (size_t)n_groups * 32);
+  Workspace ws;
+  if ((rc = get_workspace(ctx, s, exon::k8_partial_words(ctx->cfg, n_groups), &ws))) return fail(ctx, rc, "workspace allocation failed");
+  HIP_TRY(ctx, exon::launch_cmp_minmax_by_group(s, cfg_for(ctx, flags), ws, (const float*)x->values, x->validity,
+                                                (const float*)y->values, y->validity, (const int32_t*)group_id->values,
+                                                n, threshold, cmp_op, n_groups, d_state));
+  return EXON_HIP_OK;
+}
+
 int exon_op_qual_pos_hist(exon_hip_ctx* ctx, void* stream, const exon_hip_column* q, int64_t n_reads, int32_t lmax,
                           int64_t* d_hist, int flags) {
   if (!q) return fail(ctx, EXON_HIP_EINVAL, "quality_scores column is NULL");
@@ -535,6 +560,31 @@ int exon_hip_cmp_avg_by_group(exon_hip_ctx* ctx, void* stream, const exon_hip_co
                               int32_t n_groups, int64_t* d_counts, double* d_sums) {
   return exon_op_cmp_avg_by_group(ctx, stream, x, y, group_id, n, threshold, cmp_op, n_groups, d_counts, d_sums,
                                   EXON_HIP_LAUNCH_ACCUMULATE);
+}
+int exon_hip_cmp_minmax_by_group(exon_hip_ctx* ctx, void* stream, const exon_hip_column* x, const exon_hip_column* y,
+                                 const exon_hip_column* group_id, int64_t n, double threshold, int32_t cmp_op,
+                                 int32_t n_groups, int64_t* d_state) {
+  return exon_op_cmp_minmax_by_group(ctx, stream, x, y, group_id, n, threshold, cmp_op, n_groups, d_state,
+                                     EXON_HIP_LAUNCH_ACCUMULATE);
+}
+// state word of K8's min / max plane -> value: 0 = no value; otherwise undo the + 1, the complement of the min plane and the
+// unsigned-ordered key (include/exon_hip.h, K8)
+int exon_hip_minmax_decode(const int64_t* words, int64_t n, int32_t is_min, int32_t y_type, void* out_values, uint8_t* out_valid) {
+  if (n < 0 || (n > 0 && (!words || !out_values || !out_valid))) return fail(nullptr, EXON_HIP_EINVAL, "exon_hip_minmax_decode: bad argument");
+  if (y_type != EXON_HIP_X_FLOAT32 && y_type != EXON_HIP_X_INT32) return fail(nullptr, EXON_HIP_EINVAL, "exon_hip_minmax_decode: y_type %d", y_type);
+  uint32_t* out = static_cast<uint32_t*>(out_values);
+  for (int64_t i = 0; i < n; ++i) {
+    const int64_t w = words[i];
+    if (w < 0 || w > (int64_t)1 << 32) return fail(nullptr, EXON_HIP_EINVAL, "exon_hip_minmax_decode: word %lld is not a min / max state word", (long long)w);
+    out_valid[i] = w != 0;
+    if (!w) {
+      out[i] = 0;
+      continue;
+    }
+    const uint32_t k = (uint32_t)(w - 1), u = is_min ? ~k : k;
+    out[i] = (y_type == EXON_HIP_X_INT32 || (u & 0x80000000u)) ? u ^ 0x80000000u : ~u;
+  }
+  return EXON_HIP_OK;
 }
 int exon_hip_qual_pos_hist(exon_hip_ctx* ctx, void* stream, const exon_hip_column* q, int64_t n_reads, int32_t lmax,
                            int64_t* d_hist) {

@@ -16,6 +16,7 @@
 //   SELECT COUNT(*) FROM b WHERE gff_region_filter('chr1[:a-b]', reference_sequence_name[, start]) [= true] -- the same over a BED source: K2 over (0, 1)
 //   SELECT reference, COUNT(*) FROM b WHERE flag & 1284 = 0 AND CAST(mapping_quality AS INT) >= 30 GROUP BY reference  -- K3
 //   SELECT filter, AVG(qual), COUNT(*) FROM v WHERE info."AF" > 0.01 GROUP BY filter            -- K4
+//   SELECT filter, MIN(qual), MAX(qual), COUNT(*) FROM v WHERE info."AF" > 0.01 GROUP BY filter -- K8 (also MIN / MAX(info."DP"))
 //   SELECT * FROM fastq_quality_histogram('<p>'[, 'gzip'])                                        -- K5
 //   SELECT COUNT(*) FROM <bam table> WHERE bam_region_filter('<r>', reference, start, end)          -- K6 (plain table; INDEXED_BAM plans chunks on the host)
 //   DROP TABLE t;
@@ -541,7 +542,12 @@ void exec_select(Session& se, Parser& ps) {
     if (ps.accept_sym("*")) { star = true; continue; }
     std::string item = lower(ps.ident());
     if (ps.accept_sym("(")) {
-      if (ps.accept_sym("*")) item += "(*)"; else item += "(" + lower(ps.ident()) + ")";
+      if (ps.accept_sym("*")) item += "(*)";
+      else {  // a column, or info."DP" (a quoted key keeps its case; info.dp arrives as one folded identifier)
+        std::string arg = lower(ps.ident());
+        if (arg == "info.") arg += ps.ident();  // (the tokenizer leaves the dot with the identifier in front of a quoted key)
+        item += "(" + arg + ")";
+      }
       ps.expect_sym(")");
     }
     if (ps.accept_kw("as")) ps.ident();
@@ -738,6 +744,77 @@ void exec_select(Session& se, Parser& ps) {
   if (pr.kind == Predicate::InfoCmp && (src.format == EXON_HIP_FORMAT_VCF || src.format == EXON_HIP_FORMAT_BCF) && group_by == "filter") {  // K4
     if (!se.vcf_parse_info) throw Err("info." + pr.info_field + " needs `SET exon.vcf_parse_info = true` (info is a Utf8 column otherwise)");
     exon_hip_ctx* ctx = se.gpu();
+    bool minmax = false;
+    for (const auto& it : proj) minmax = minmax || it.rfind("min(", 0) == 0 || it.rfind("max(", 0) == 0;
+    if (minmax) {  // K8: ONE stream over all files (their FILTER dictionaries are merged by value inside it)
+      std::string arg;  // the one argument of MIN / MAX: qual or info.<key>
+      for (const auto& it : proj) {
+        if (it == "filter" || it == "count(*)") continue;
+        const bool mm = it.rfind("min(", 0) == 0 || it.rfind("max(", 0) == 0;
+        const std::string a = mm ? it.substr(4, it.size() - 5) : "";
+        if (!mm || (!arg.empty() && a != arg) || (a != "qual" && a.rfind("info.", 0) != 0))
+          throw Err("unsupported select item '" + it + "' next to MIN / MAX (supported: filter, MIN(c), MAX(c), COUNT(*) with c = qual or info.\"KEY\")");
+        arg = a;
+      }
+      std::string fields = pr.info_field;
+      int ycol = 2;
+      if (arg != "qual") {
+        const std::string key = arg.substr(5);
+        ycol = key == pr.info_field ? 4 : 5;
+        if (ycol == 5) fields += "," + key;
+      }
+      const int G = EXON_HIP_MAX_GROUPS;  // distinct FILTER lists over all files: what the plan kind takes (a 128 KiB state)
+      StreamGuard sg;
+      exon_hip_plan_desc d; memset(&d, 0, sizeof d);
+      d.kind = EXON_HIP_PLAN_CMP_MINMAX_BY_GROUP; d.n_groups = G; d.cmp_op = pr.cmp_op; d.threshold = pr.literal;
+      d.columns[0] = 4; d.columns[1] = ycol; d.columns[2] = 3;
+      ck(ctx, exon_hip_plan_create(ctx, &d, &sg.p));
+      ck(ctx, exon_hip_stream_open(sg.p, 0, &sg.s));
+      for (const auto& f : src.files) {
+        ScanGuard g; open_scan(src, f, fields.c_str(), "", &g, true);
+        ck(ctx, exon_hip_stream_consume_scan(sg.s, g.s, nullptr));
+      }
+      int32_t nk = 0; size_t kb = 0;
+      ck(ctx, exon_hip_stream_keys(sg.s, nullptr, 0, &nk, &kb, nullptr));
+      std::vector<char> packed(kb + 1);
+      ck(ctx, exon_hip_stream_keys(sg.s, packed.data(), kb, &nk, &kb, nullptr));
+      std::vector<std::string> keys;
+      for (size_t o = 0; (int32_t)keys.size() < nk; o += keys.back().size() + 1) keys.emplace_back(packed.data() + o);
+      struct ArrowArray st; struct ArrowSchema sch;  // group, min[min], max[max], count[count], count(*)[count]
+      ck(ctx, exon_hip_stream_finish_arrow(sg.s, &st, &sch));
+      const bool is_int = sch.children[1]->format[0] == 'i';
+      auto cell = [&](int c, int64_t i) -> std::string {
+        const struct ArrowArray* a = st.children[c];
+        const uint8_t* bm = static_cast<const uint8_t*>(a->buffers[0]);  // (the state batch has no offset)
+        if (bm && !((bm[i >> 3] >> (i & 7)) & 1)) return "NULL";
+        if (is_int) return std::to_string(static_cast<const int32_t*>(a->buffers[1])[i]);
+        return fmt_f64((double)static_cast<const float*>(a->buffers[1])[i]);
+      };
+      std::vector<std::string> head;
+      for (const auto& it : proj) head.push_back(it);
+      std::vector<std::vector<std::string>> rows;
+      for (int64_t i = 0; i < st.length; ++i) {
+        const int32_t gk = static_cast<const int32_t*>(st.children[0]->buffers[1])[i];
+        const std::string k = gk < (int32_t)keys.size() ? keys[(size_t)gk] : "";
+        std::string list = "[";  // List<Utf8> rendered like datafusion: [a, b]
+        for (size_t p0 = 0; !k.empty() && p0 <= k.size();) {
+          const size_t sc = k.find(';', p0);
+          list += (p0 ? ", " : "") + k.substr(p0, sc == std::string::npos ? std::string::npos : sc - p0);
+          if (sc == std::string::npos) break;
+          p0 = sc + 1;
+        }
+        list += "]";
+        std::vector<std::string> row;
+        for (const auto& it : proj)
+          row.push_back(it == "filter" ? list : it == "count(*)" ? std::to_string(static_cast<const int64_t*>(st.children[4]->buffers[1])[i])
+                        : cell(it[1] == 'i' ? 1 : 2, i));
+        rows.push_back(std::move(row));
+      }
+      if (st.release) st.release(&st);
+      if (sch.release) sch.release(&sch);
+      print_table(head, rows, se.quiet);
+      return;
+    }
     struct Acc { double sum = 0; int64_t cnt = 0, rows = 0; };
     std::map<std::string, Acc> merged;
     std::vector<std::string> order;
@@ -859,7 +936,9 @@ int main(int argc, char** argv) {
              "  queries:   SELECT COUNT(*) FROM <src> [WHERE chrom = 'c' AND pos >= a AND pos <= b | vcf_region_filter('r', chrom) | bam_region_filter('r', reference, start, end)\n"
              "             | gff_region_filter('r', seqname[, start])]\n"
              "             SELECT reference, COUNT(*) FROM <bam> WHERE flag & M = V AND CAST(mapping_quality AS INT) >= q GROUP BY reference\n"
-             "             SET exon.vcf_parse_info = true; SELECT filter, AVG(qual), COUNT(*) FROM <vcf> WHERE info.\"AF\" > 0.01 GROUP BY filter\n");
+             "             SET exon.vcf_parse_info = true; SELECT filter, AVG(qual), COUNT(*) FROM <vcf> WHERE info.\"AF\" > 0.01 GROUP BY filter\n"
+             "             SELECT filter, MIN(qual), MAX(qual), COUNT(*) FROM <vcf> WHERE info.\"AF\" > 0.01 GROUP BY filter   (also MIN / MAX(info.\"DP\");\n"
+             "               at most 4096 distinct FILTER lists over the table's files, one type of the argument in all of them)\n");
       return 0;
     } else { fprintf(stderr, "unknown argument %s\n", a.c_str()); return 2; }
   }

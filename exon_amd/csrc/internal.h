@@ -199,6 +199,9 @@ int exon_op_flag_mapq_group_count(exon_hip_ctx* ctx, void* stream, const exon_hi
 int exon_op_cmp_avg_by_group(exon_hip_ctx* ctx, void* stream, const exon_hip_column* x, const exon_hip_column* y,
                              const exon_hip_column* group_id, int64_t n, double threshold, int32_t cmp_op,
                              int32_t n_groups, int64_t* d_counts, double* d_sums, int flags);
+int exon_op_cmp_minmax_by_group(exon_hip_ctx* ctx, void* stream, const exon_hip_column* x, const exon_hip_column* y,
+                                const exon_hip_column* group_id, int64_t n, double threshold, int32_t cmp_op,
+                                int32_t n_groups, int64_t* d_state, int flags);
 int exon_op_qual_pos_hist(exon_hip_ctx* ctx, void* stream, const exon_hip_column* q, int64_t n_reads, int32_t lmax,
                           int64_t* d_hist, int flags);
 // chunk c is q[c * stride]

@@ -34,6 +34,7 @@ size_t k4_partial_words(const LaunchCfg&, int n_groups);
 size_t k4_tail_records(int64_t n, int n_groups);
 constexpr size_t K4_TAIL_U32_WORDS = 2048 + 3 * 2048 + 2 + (size_t)2048 * 2048;  // workgroup counts, range totals, offsets, slice starts, [workgroup][range] histogram
 size_t k5_partial_words(const LaunchCfg&, int lmax);
+size_t k8_partial_words(const LaunchCfg&, int n_groups);
 
 hipError_t launch_region_count(hipStream_t s, const LaunchCfg& cfg, const Workspace& ws, const int32_t* chrom,
                                const uint8_t* chrom_valid, const int64_t* pos, const uint8_t* pos_valid, int64_t n,
@@ -54,6 +55,12 @@ hipError_t launch_flag_mapq_group_count(hipStream_t s, const LaunchCfg& cfg, con
 hipError_t launch_cmp_avg_by_group(hipStream_t s, const LaunchCfg& cfg, const Workspace& ws, const float* x,
                                    const uint8_t* x_valid, const float* y, const uint8_t* y_valid, const int32_t* gid,
                                    int64_t n, double thr, int cmp_op, int n_groups, int64_t* d_counts, double* d_sums);
+
+// K8: K4's predicate, MIN / MAX / COUNT(y) / COUNT(*) per group into the packed state [cnn[G]] [crow[G]] [minw[G]] [maxw[G]]
+// (1 <= n_groups <= 4096; cfg.x_is_int / y_is_int as for K4)
+hipError_t launch_cmp_minmax_by_group(hipStream_t s, const LaunchCfg& cfg, const Workspace& ws, const float* x,
+                                      const uint8_t* x_valid, const float* y, const uint8_t* y_valid, const int32_t* gid,
+                                      int64_t n, double thr, int cmp_op, int n_groups, int64_t* d_state);
 
 hipError_t launch_qual_pos_hist(hipStream_t s, const LaunchCfg& cfg, const Workspace& ws, const int32_t* offsets,
                                 const uint8_t* bytes, int64_t n_reads, int lmax, int64_t* d_hist);
@@ -82,15 +89,17 @@ hipError_t launch_region_mask(hipStream_t s, bool range_form, const int32_t* id_
                               const int64_t* end, const uint8_t* pos_valid, const uint8_t* in_valid, int64_t n, int32_t id,
                               int64_t a, int64_t b, uint8_t* out_valid, unsigned long long* n_pass);
 
-// out[v] = sum over ranks (rank order) of gathered[rank][v]; words [0, n_i64) int64, then n_f64 float64
-hipError_t launch_fold_states(hipStream_t s, const void* gathered, int world, int64_t n_i64, int64_t n_f64, void* out);
+// out[v] = sum over ranks (rank order) of gathered[rank][v]; words [0, n_i64) int64, then n_f64 float64; the last n_max of the
+// int64 words fold by unsigned max instead (K8's extreme planes)
+hipError_t launch_fold_states(hipStream_t s, const void* gathered, int world, int64_t n_i64, int64_t n_f64, void* out, int64_t n_max = 0);
 
 // Re-keying of a packed partial state: dst[plane][map[g]] += src[plane][g] for every keyed plane (`planes_i64` int64 planes of G
 // words, then `tail_i64` unkeyed int64 words that are added in place -- K3's NULL-reference group --, then `planes_f64` float64
-// planes of G words); map[g] < 0: key g carries nothing and is skipped.  Used when the dictionary ids of one scan / one rank
+// planes of G words; the last `planes_max` of the int64 planes are combined by unsigned max instead of add); map[g] < 0: key g
+// carries nothing and is skipped.  Used when the dictionary ids of one scan / one rank
 // are brought into the order of a shared key dictionary (merge by key VALUE, not by id).
 hipError_t launch_permute_add_state(hipStream_t s, const void* src, void* dst, const int32_t* map, int n_map, int G, int planes_i64,
-                                    int tail_i64, int planes_f64);
+                                    int tail_i64, int planes_f64, int planes_max);
 
 // bare streaming read of up to 4 buffers in lock-step, the access pattern and grid of K2-K6 (bench.py's per-box ceiling)
 hipError_t launch_read_probe(hipStream_t s, const LaunchCfg& cfg, const void* const* buffers, int n_buffers, int64_t bytes_each,

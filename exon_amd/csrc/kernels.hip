@@ -203,8 +203,9 @@ __device__ __forceinline__ unsigned long long ld_agent(const unsigned long long*
   return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 // Call with ALL threads of the workgroup after the record `partials[blockIdx.x * V ...]` was written with st_agent().
-template <int THREADS>
-__device__ __forceinline__ void fold_if_last(const FoldArgs& fa, const unsigned long long* __restrict__ partials) {
+// MAXTAIL (K8): an all-integer record whose words [n_add, V) fold by unsigned max instead of add (0 is the identity of both).
+template <int THREADS, bool MAXTAIL = false>
+__device__ __forceinline__ void fold_if_last(const FoldArgs& fa, const unsigned long long* __restrict__ partials, int n_add = 0) {
   __shared__ unsigned long long fold_red[THREADS];
   __shared__ int fold_last;
   __builtin_amdgcn_s_waitcnt(0);  // vmcnt(0): this wave's record stores have been acknowledged
@@ -226,6 +227,7 @@ __device__ __forceinline__ void fold_if_last(const FoldArgs& fa, const unsigned 
   for (int v0 = 0; v0 < V; v0 += VP) {
     const int v = v0 + vi;
     const bool is_int = v < n_i64;
+    const bool is_max = MAXTAIL && v >= n_add;
     unsigned long long acc_i = 0;
     double acc_f = 0.0;
     if (v < V) {
@@ -234,7 +236,10 @@ __device__ __forceinline__ void fold_if_last(const FoldArgs& fa, const unsigned 
         unsigned long long a[8];
 #pragma unroll
         for (int i = 0; i < 8; ++i) a[i] = (b + i < b1) ? ld_agent(p + (size_t)(b + i) * V) : 0ull;  // 0 bits = +0.0
-        if (is_int) {
+        if (MAXTAIL && is_max) {
+#pragma unroll
+          for (int i = 0; i < 8; ++i) acc_i = max(acc_i, a[i]);
+        } else if (is_int) {
 #pragma unroll
           for (int i = 0; i < 8; ++i) acc_i += a[i];
         } else {
@@ -249,13 +254,16 @@ __device__ __forceinline__ void fold_if_last(const FoldArgs& fa, const unsigned 
       if (seg < st) {
         const unsigned long long x = fold_red[threadIdx.x], y = fold_red[threadIdx.x + (st << lg)];
         fold_red[threadIdx.x] =
-            is_int ? x + y
-                   : (unsigned long long)__double_as_longlong(__longlong_as_double((long long)x) + __longlong_as_double((long long)y));
+            (MAXTAIL && is_max) ? max(x, y)
+            : is_int            ? x + y
+                                : (unsigned long long)__double_as_longlong(__longlong_as_double((long long)x) + __longlong_as_double((long long)y));
       }
       __syncthreads();
     }
     if (seg == 0 && v < V) {
-      if (is_int) {
+      if (MAXTAIL && is_max) {
+        fa.st_i64[v] = (int64_t)max(fa.overwrite ? 0ull : (unsigned long long)fa.st_i64[v], fold_red[threadIdx.x]);
+      } else if (is_int) {
         fa.st_i64[v] = (fa.overwrite ? 0 : fa.st_i64[v]) + (int64_t)fold_red[threadIdx.x];
       } else {
         fa.st_f64[v - n_i64] = (fa.overwrite ? 0.0 : fa.st_f64[v - n_i64]) + __longlong_as_double((long long)fold_red[threadIdx.x]);
@@ -290,12 +298,17 @@ static hipError_t run_finalize(hipStream_t s, const LaunchCfg& cfg, const Worksp
 // fold_states: AggregateExec(Final) across GPUs after ONE all-gather of the packed partial states.
 // gathered = [world][V] words (rank-major; words [0, n_i64) int64, the rest float64); out[v] = sum over ranks in
 // rank order 0, 1, ..., world-1: every rank computes the same bits whatever algorithm the collective used.
+// The last n_max of the int64 words (K8's two extreme planes) fold by unsigned max instead.
 // ------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void fold_states(const unsigned long long* __restrict__ gathered, int world, int V,
-                                                   int n_i64, unsigned long long* __restrict__ out) {
+                                                   int n_i64, int n_max, unsigned long long* __restrict__ out) {
   const int v = blockIdx.x * 256 + threadIdx.x;
   if (v >= V) return;
-  if (v < n_i64) {
+  if (v < n_i64 && v >= n_i64 - n_max) {
+    unsigned long long t = 0;
+    for (int r = 0; r < world; ++r) t = max(t, gathered[(size_t)r * V + v]);
+    out[v] = t;
+  } else if (v < n_i64) {
     unsigned long long t = 0;
     for (int r = 0; r < world; ++r) t += gathered[(size_t)r * V + v];
     out[v] = t;
@@ -306,11 +319,11 @@ __global__ __launch_bounds__(256) void fold_states(const unsigned long long* __r
   }
 }
 
-hipError_t launch_fold_states(hipStream_t s, const void* gathered, int world, int64_t n_i64, int64_t n_f64, void* out) {
+hipError_t launch_fold_states(hipStream_t s, const void* gathered, int world, int64_t n_i64, int64_t n_f64, void* out, int64_t n_max) {
   const int64_t V = n_i64 + n_f64;
-  if (V <= 0 || world < 1) return hipErrorInvalidValue;
+  if (V <= 0 || world < 1 || n_max < 0 || n_max > n_i64) return hipErrorInvalidValue;
   hipLaunchKernelGGL(fold_states, dim3((unsigned)((V + 255) / 256)), dim3(256), 0, s,
-                     static_cast<const unsigned long long*>(gathered), world, (int)V, (int)n_i64,
+                     static_cast<const unsigned long long*>(gathered), world, (int)V, (int)n_i64, (int)n_max,
                      static_cast<unsigned long long*>(out));
   return hipGetLastError();
 }
@@ -318,11 +331,12 @@ hipError_t launch_fold_states(hipStream_t s, const void* gathered, int world, in
 // ------------------------------------------------------------------------------------------------
 // permute_add_state: bring a packed partial state keyed by one dictionary's ids into the id order of another.
 // One thread per source key; targets are distinct unless a dictionary repeats a name (then the adds to the shared target
-// are atomic: counts stay exact).  Layout: [planes_i64 x G int64][tail_i64 int64][planes_f64 x G float64].
+// are atomic: counts stay exact).  Layout: [planes_i64 x G int64][tail_i64 int64][planes_f64 x G float64]; the last planes_max
+// of the int64 planes (K8's extremes) are brought in by unsigned max instead of add.
 // ------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void permute_add_state(const unsigned long long* __restrict__ src, unsigned long long* __restrict__ dst,
                                                          const int32_t* __restrict__ map, int n_map, int G, int planes_i64, int tail_i64,
-                                                         int planes_f64) {
+                                                         int planes_f64, int planes_max) {
   const int g = blockIdx.x * 256 + threadIdx.x;
   if (g < tail_i64) {
     const size_t w = (size_t)planes_i64 * G + g;
@@ -333,7 +347,9 @@ __global__ __launch_bounds__(256) void permute_add_state(const unsigned long lon
   if (t < 0 || t >= G) return;
   for (int p = 0; p < planes_i64; ++p) {
     const unsigned long long v = src[(size_t)p * G + g];
-    if (v) atomicAdd(&dst[(size_t)p * G + t], v);
+    if (!v) continue;
+    if (p >= planes_i64 - planes_max) atomicMax(&dst[(size_t)p * G + t], v);
+    else atomicAdd(&dst[(size_t)p * G + t], v);
   }
   const size_t fbase = (size_t)planes_i64 * G + tail_i64;
   for (int p = 0; p < planes_f64; ++p) {
@@ -343,12 +359,12 @@ __global__ __launch_bounds__(256) void permute_add_state(const unsigned long lon
 }
 
 hipError_t launch_permute_add_state(hipStream_t s, const void* src, void* dst, const int32_t* map, int n_map, int G, int planes_i64,
-                                    int tail_i64, int planes_f64) {
-  if (G < 0 || n_map < 0 || planes_i64 < 0 || planes_f64 < 0 || tail_i64 < 0) return hipErrorInvalidValue;
+                                    int tail_i64, int planes_f64, int planes_max) {
+  if (G < 0 || n_map < 0 || planes_i64 < 0 || planes_f64 < 0 || tail_i64 < 0 || planes_max < 0 || planes_max > planes_i64) return hipErrorInvalidValue;
   const int threads = std::max(std::min(n_map, G), tail_i64);
   if (threads == 0) return hipSuccess;
   hipLaunchKernelGGL(permute_add_state, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s, static_cast<const unsigned long long*>(src),
-                     static_cast<unsigned long long*>(dst), map, n_map, G, planes_i64, tail_i64, planes_f64);
+                     static_cast<unsigned long long*>(dst), map, n_map, G, planes_i64, tail_i64, planes_f64, planes_max);
   return hipGetLastError();
 }
 
@@ -919,6 +935,14 @@ hipError_t launch_flag_mapq_group_count(hipStream_t s, const LaunchCfg& cfg, con
 //   for 64 and 4096 keys, uniform and skewed): a CU issues one wave64 vector instruction per clock, so every instruction
 //   per row is 0.025 ms per 1e9 rows.  Hence 4 register groups instead of 8 (4 instead of 8 conditional f64 adds, 32-bit
 //   packed counters), the predicate evaluated once per row for all tiers, one LDS address per row.
+// The row predicate of K4 and K8: x valid AND key(x) in [klo, khi] (complemented for !=), the range the host folded (<op>, thr)
+// into (cmp_to_key_range below).
+__device__ __forceinline__ unsigned cmp_key_passes(float xf, unsigned xv, int32_t klo, int32_t khi, int32_t negate, int32_t keymask) {
+  const int32_t bx = __float_as_int(xf);
+  const int32_t kx = bx ^ ((bx >> 31) & keymask);
+  const unsigned inr = unsigned(kx >= klo) & unsigned(kx <= khi);
+  return xv & (inr ^ (unsigned)negate);
+}
 constexpr int K4_TAIL_MAX_RANGES = 2048;  // (2^24 - 4100) / 8192 ids
 constexpr int K4_TAIL_MAX_GRID = 2048;    // workgroups of the main kernel the partitioned tier 3 has histogram rows for
 constexpr int K4_TAIL_RANGE = 8192;  // ids per range of the partitioned tier 3 = entries of k4_tail_aggregate's LDS table (128 KiB)
@@ -1003,12 +1027,7 @@ __global__ __launch_bounds__(S::THREADS) void k4_cmp_avg_by_group_main(
 
   // keymask = 0x7FFFFFFF: x is Float32, compared through its totalOrder key; keymask = 0: x is Int32 (INFO Type=Integer,
   // schema_builder.rs:197-205), the bit pattern IS the key -- integer predicates never pass through f32
-  auto passes = [&](float xf, unsigned xv) -> unsigned {
-    const int32_t bx = __float_as_int(xf);
-    const int32_t kx = bx ^ ((bx >> 31) & keymask);
-    const unsigned inr = unsigned(kx >= klo) & unsigned(kx <= khi);
-    return xv & (inr ^ (unsigned)negate);
-  };
+  auto passes = [&](float xf, unsigned xv) -> unsigned { return cmp_key_passes(xf, xv, klo, khi, negate, keymask); };
   // AVG's argument widened to f64 (DataFusion casts Float32 AND Int32 arguments of avg to Float64): yint != 0 when the
   // column holds Int32 values (an INFO field of Type=Integer)
   // (the instruction-bound > 8-group variant gets the choice at compile time -- YI -- instead of two conversions and a
@@ -1899,6 +1918,337 @@ hipError_t launch_cmp_avg_by_group(hipStream_t s, const LaunchCfg& cfg, const Wo
     if (e != hipSuccess) return e;
   }
   return hipSuccess;
+}
+
+// ------------------------------------------------------------------------------------------------
+// K8 cmp_minmax_by_group
+//   WHERE CAST(x AS DOUBLE) <op> thr   SELECT g, MIN(y), MAX(y), COUNT(y), COUNT(*) GROUP BY g     (x, y Float32 or Int32)
+//   The predicate is K4's (the same folded key range, evaluated once per row).  MIN / MAX follow DataFusion's
+//   min_max.rs accumulators: NULLs are skipped, floats are ordered by total_cmp -- IEEE totalOrder, the rule K4's predicate
+//   already uses.  u(y) = the unsigned-ordered 32-bit key of y (f32: bits ^ (sign ? 0xFFFFFFFF : 0x80000000); i32: bits ^
+//   0x80000000), so MAX(y) is the unsigned max of u and MIN(y) the unsigned max of ~u: ONE operator for both planes.
+//   Inside the kernel the keys are raw u32 with identity 0 and "no value yet" is count(y) == 0 (u can be 0 and 0xFFFFFFFF:
+//   the NaNs with an all-ones payload); the + 1 that makes 0 mean "empty" is added when a key is widened to the 64-bit
+//   state word:  state = [count(y)[G]] [count(*)[G]] [minw[G]] [maxw[G]],  minw = 1 + ~u(min), maxw = 1 + u(max), 0 = no value.
+//   The same 12.25 B/row stream as K4.  Two tiers:
+//     G <= 8      per-lane registers: G max-of-u + G max-of-~u (m = max(m, g == k ? key : 0): no branch), counts in K4's
+//                 packed 8-bit fields; wave reduction, then the waves through LDS;
+//     9 .. 4096   a per-workgroup LDS table of 16-byte entries {u32 count(y), u32 count(*), u32 max ~u, u32 max u}: two
+//                 ds_add_u32 + two ds_max_u32 on one address register, entered only when some lane of the wave has a passing
+//                 row and branch-free inside (a row that does not count goes to its lane's dummy entry: K4's findings above);
+//                 256 consecutive rows with ONE key (sorted input, a hot key) are reduced in the wave -- ballots for the
+//                 counts, a wave max for the keys -- and lane 0 touches the table once.
+//   Per-workgroup records are already 64-bit state words; they fold by add (counts) / unsigned max (extremes), in the fixed
+//   order of the other kernels (all integers: the result does not depend on it).  OVERWRITE needs no zeroing pass.
+// ------------------------------------------------------------------------------------------------
+struct K8Entry {  // LDS table entry
+  unsigned cnn, crow, nmin, nmax;
+};
+__device__ __forceinline__ unsigned wave_max(unsigned v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = max(v, (unsigned)__shfl_down(v, o, 64));
+  return v;
+}
+template <int G, typename S, bool OVF>
+__global__ __launch_bounds__(S::THREADS) void k8_cmp_minmax_by_group_main(
+    const float* __restrict__ x, const uint8_t* __restrict__ xvalid, const float* __restrict__ y,
+    const uint8_t* __restrict__ yvalid, const int32_t* __restrict__ gid, int64_t n, int32_t klo, int32_t khi,
+    int32_t negate, int32_t keymask, int32_t ysign, int32_t NG, unsigned long long* __restrict__ partials,
+    int* __restrict__ status, const uint8_t* __restrict__ ones, const FoldArgs fa) {
+  constexpr int J = S::J, THREADS = S::THREADS, WAVES = ShapeOf<S>::WAVES, WT = ShapeOf<S>::WAVE_TILE,
+                TILE = ShapeOf<S>::TILE;
+  constexpr int GA = G > 0 ? G : 1;  // (the table variant keeps no register groups)
+  constexpr bool NARROW = G <= 4;
+  using Packed = typename std::conditional<NARROW, unsigned, unsigned long long>::type;
+  constexpr unsigned FMASK = NARROW ? 3u : 7u;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  unsigned mx[GA], mn[GA], cnn[GA], crow[GA];
+#pragma unroll
+  for (int k = 0; k < GA; ++k) mx[k] = mn[k] = cnn[k] = crow[k] = 0;
+  Packed prow = 0, pnn = 0;
+  unsigned gmax = 0;
+  // table (OVF only): NG entries + 64 per-lane dummy entries
+  extern __shared__ K8Entry k8_tab[];
+  if (OVF) {
+    for (int i = threadIdx.x; i < NG + 64; i += THREADS) k8_tab[i] = K8Entry{0u, 0u, 0u, 0u};
+    __syncthreads();
+  }
+  const unsigned dummy = (unsigned)(NG + lane);
+
+  auto passes = [&](float xf, unsigned xv) -> unsigned { return cmp_key_passes(xf, xv, klo, khi, negate, keymask); };  // K4's predicate
+  // ysign = 0x7FFFFFFF: y is Float32 (a negative value has all its bits flipped); 0: Int32 (only the sign bit)
+  auto ukey = [&](float yf) -> unsigned {
+    const int32_t b = __float_as_int(yf);
+    return (unsigned)(b ^ (((b >> 31) & ysign) | INT32_MIN));
+  };
+  auto row = [&](unsigned pass, float yf, int32_t g, unsigned yv) {  // register groups
+    const unsigned yq = pass & yv;
+    gmax = max(gmax, (unsigned)g);  // ids are validated over ALL rows, as in K4
+    const unsigned sh = ((unsigned)g & FMASK) * 8u;
+    prow += (Packed)pass << sh;
+    pnn += (Packed)yq << sh;
+    const int32_t gq = yq ? g : -1;
+    const unsigned u = ukey(yf), nu = ~u;
+#pragma unroll
+    for (int k = 0; k < G; ++k) {
+      mx[k] = max(mx[k], gq == k ? u : 0u);
+      mn[k] = max(mn[k], gq == k ? nu : 0u);
+    }
+  };
+  auto row_lds = [&](unsigned pass, float yf, int32_t g, unsigned yv) {  // all 64 lanes, branch-free
+    const unsigned in = pass & unsigned((unsigned)g < (unsigned)NG);
+    const unsigned yq = in & yv;
+    K8Entry* e = &k8_tab[in ? (unsigned)g : dummy];
+    const unsigned u = ukey(yf);
+    atomicAdd(&e->crow, 1u);
+    atomicAdd(&e->cnn, yq);
+    atomicMax(&e->nmin, yq ? ~u : 0u);
+    atomicMax(&e->nmax, yq ? u : 0u);
+  };
+  int uni_skip = 0;  // wave-uniform: the one-key test is skipped for 15 groups of rows after it found mixed keys (K4's rule)
+  auto rows4_uniform = [&](int kw, unsigned p0, unsigned p1, unsigned p2, unsigned p3, float4 y4, unsigned yv) {
+    if ((unsigned)kw >= (unsigned)NG) return;  // reported through gmax
+    const unsigned n0 = p0 & (yv >> 0 & 1), n1 = p1 & (yv >> 1 & 1), n2 = p2 & (yv >> 2 & 1), n3 = p3 & (yv >> 3 & 1);
+    const unsigned rows = (unsigned)(__popcll(__ballot(p0 != 0)) + __popcll(__ballot(p1 != 0)) + __popcll(__ballot(p2 != 0)) + __popcll(__ballot(p3 != 0)));
+    const unsigned nn = (unsigned)(__popcll(__ballot(n0 != 0)) + __popcll(__ballot(n1 != 0)) + __popcll(__ballot(n2 != 0)) + __popcll(__ballot(n3 != 0)));
+    const unsigned u0 = ukey(y4.x), u1 = ukey(y4.y), u2 = ukey(y4.z), u3 = ukey(y4.w);
+    const unsigned hi = wave_max(max(max(n0 ? u0 : 0u, n1 ? u1 : 0u), max(n2 ? u2 : 0u, n3 ? u3 : 0u)));
+    const unsigned lo = wave_max(max(max(n0 ? ~u0 : 0u, n1 ? ~u1 : 0u), max(n2 ? ~u2 : 0u, n3 ? ~u3 : 0u)));
+    if (lane == 0 && rows != 0) {
+      K8Entry* e = &k8_tab[kw];
+      atomicAdd(&e->crow, rows);
+      atomicAdd(&e->cnn, nn);
+      atomicMax(&e->nmin, lo);
+      atomicMax(&e->nmax, hi);
+    }
+  };
+  auto spill = [&]() {
+#pragma unroll
+    for (int k = 0; k < G; ++k) {
+      crow[k] += (unsigned)(prow >> (8 * k)) & 0xFFu;
+      cnn[k] += (unsigned)(pnn >> (8 * k)) & 0xFFu;
+    }
+    prow = 0;
+    pnn = 0;
+  };
+
+  const int64_t ntiles = n / TILE;
+  int since = 0;  // rows added to the packed counters since the last spill
+  for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    const int64_t wbase = tile * TILE + (int64_t)wave * WT;
+    float4 xs[J], ys[J];
+    int4 gs[J];
+    unsigned xm[J], ym[J];
+#pragma unroll
+    for (int j = 0; j < J; ++j) {
+      const int64_t r = wbase + j * 256 + lane * 4;
+      xs[j] = ld16<float4>(x + r);
+      ys[j] = ld16<float4>(y + r);
+      gs[j] = ld16<int4>(gid + r);
+      xm[j] = valid4_ones(xvalid, ones, wbase, j, lane);
+      ym[j] = valid4_ones(yvalid, ones, wbase, j, lane);
+    }
+#pragma unroll
+    for (int j = 0; j < J; ++j) {
+      const unsigned p0 = passes(xs[j].x, xm[j] >> 0 & 1), p1 = passes(xs[j].y, xm[j] >> 1 & 1),
+                     p2 = passes(xs[j].z, xm[j] >> 2 & 1), p3 = passes(xs[j].w, xm[j] >> 3 & 1);
+      if (!OVF) {
+        row(p0, ys[j].x, gs[j].x, ym[j] >> 0 & 1);
+        row(p1, ys[j].y, gs[j].y, ym[j] >> 1 & 1);
+        row(p2, ys[j].z, gs[j].z, ym[j] >> 2 & 1);
+        row(p3, ys[j].w, gs[j].w, ym[j] >> 3 & 1);
+      } else {
+        // largest id among this lane's 4 rows (unsigned: a negative id is "huge")
+        gmax = max(gmax, max(max((unsigned)gs[j].x, (unsigned)gs[j].y), max((unsigned)gs[j].z, (unsigned)gs[j].w)));
+        if (__any((p0 | p1 | p2 | p3) != 0)) {
+          bool uni = false;
+          const int kw = __builtin_amdgcn_readfirstlane(gs[j].x);
+          if (uni_skip > 0) {
+            --uni_skip;
+          } else {
+            uni = __all((gs[j].x == kw) & (gs[j].y == kw) & (gs[j].z == kw) & (gs[j].w == kw));
+            uni_skip = uni ? 0 : 15;
+          }
+          if (uni) {
+            rows4_uniform(kw, p0, p1, p2, p3, ys[j], ym[j]);
+          } else {
+            row_lds(p0, ys[j].x, gs[j].x, ym[j] >> 0 & 1);
+            row_lds(p1, ys[j].y, gs[j].y, ym[j] >> 1 & 1);
+            row_lds(p2, ys[j].z, gs[j].z, ym[j] >> 2 & 1);
+            row_lds(p3, ys[j].w, gs[j].w, ym[j] >> 3 & 1);
+          }
+        }
+      }
+    }
+    since += 4 * J;
+    if (!OVF && since > 255 - 4 * J) {
+      spill();
+      since = 0;
+    }
+  }
+  spill();
+  since = 0;
+  for (int64_t r = ntiles * TILE + (int64_t)rem_block() * THREADS + threadIdx.x; r < n;
+       r += (int64_t)gridDim.x * THREADS) {
+    const float yf = y[r];
+    const int32_t g = gid[r];
+    const unsigned yv = valid1(yvalid, r), pass = passes(x[r], valid1(xvalid, r));
+    if (!OVF) {
+      row(pass, yf, g, yv);
+      if (++since == 255) {
+        spill();
+        since = 0;
+      }
+    } else {  // the tail loop is short: plain divergent code
+      gmax = max(gmax, (unsigned)g);
+      if (pass && (unsigned)g < (unsigned)NG) {
+        K8Entry* e = &k8_tab[g];
+        atomicAdd(&e->crow, 1u);
+        if (yv) {
+          const unsigned u = ukey(yf);
+          atomicAdd(&e->cnn, 1u);
+          atomicMax(&e->nmin, ~u);
+          atomicMax(&e->nmax, u);
+        }
+      }
+    }
+  }
+  spill();
+  if (gmax >= (unsigned)NG) atomicOr(status, 4);
+
+  // per-workgroup record = state words: [cnn[NG]] [crow[NG]] [minw[NG]] [maxw[NG]]
+  unsigned long long* const rec = partials + (size_t)blockIdx.x * (4 * (size_t)NG);
+  if constexpr (!OVF) {
+    __shared__ unsigned red[WAVES][4 * GA];
+#pragma unroll
+    for (int k = 0; k < G; ++k) {
+      const unsigned a = (unsigned)wave_sum((unsigned long long)cnn[k]), b = (unsigned)wave_sum((unsigned long long)crow[k]);
+      const unsigned c = wave_max(mn[k]), d = wave_max(mx[k]);
+      if (lane == 0) {
+        red[wave][k] = a;
+        red[wave][G + k] = b;
+        red[wave][2 * G + k] = c;
+        red[wave][3 * G + k] = d;
+      }
+    }
+    __syncthreads();
+    if (threadIdx.x < 4 * G) {
+      const int v = threadIdx.x, kind = v / GA, g = v - kind * GA;  // 0: cnn, 1: crow, 2: min, 3: max
+      unsigned long long out = 0, has = 0;
+#pragma unroll
+      for (int w = 0; w < WAVES; ++w) {
+        has += red[w][g];
+        out = kind < 2 ? out + red[w][v] : max(out, (unsigned long long)red[w][v]);
+      }
+      if (kind >= 2) out = has ? out + 1ull : 0ull;
+      st_agent(&rec[v], out);
+    }
+  } else {
+    __syncthreads();
+    for (int i = threadIdx.x; i < NG; i += THREADS) {
+      const K8Entry e = k8_tab[i];
+      st_agent(&rec[i], e.cnn);
+      st_agent(&rec[NG + i], e.crow);
+      st_agent(&rec[2 * NG + i], e.cnn ? 1ull + e.nmin : 0ull);
+      st_agent(&rec[3 * NG + i], e.cnn ? 1ull + e.nmax : 0ull);
+    }
+  }
+  if (fa.ticket) fold_if_last<THREADS, true>(fa, partials, 2 * NG);
+}
+
+// the fold of records too long for the last workgroup (4 G > FUSE_MAX_V words): finalize_partials' shape over integer words,
+// words [n_add, V) by unsigned max
+__global__ __launch_bounds__(256) void k8_finalize(const unsigned long long* __restrict__ partials, int nblocks, int V, int n_add,
+                                                   unsigned long long* __restrict__ state, int overwrite) {
+  __shared__ unsigned long long red[8][32];
+  const int vi = threadIdx.x & 31, seg = threadIdx.x >> 5;
+  const int v = blockIdx.x * 32 + vi;
+  const int per = (nblocks + 7) / 8;
+  const int b0 = seg * per, b1 = min(nblocks, b0 + per);
+  const bool is_max = v >= n_add;
+  unsigned long long acc = 0;
+  if (v < V) {
+    const unsigned long long* p = partials + v;
+    int b = b0;
+    for (; b + 4 <= b1; b += 4) {
+      const unsigned long long a0 = p[(size_t)b * V], a1 = p[(size_t)(b + 1) * V], a2 = p[(size_t)(b + 2) * V], a3 = p[(size_t)(b + 3) * V];
+      acc = is_max ? max(max(acc, a0), max(max(a1, a2), a3)) : acc + a0 + a1 + a2 + a3;
+    }
+    for (; b < b1; ++b) acc = is_max ? max(acc, p[(size_t)b * V]) : acc + p[(size_t)b * V];
+  }
+  red[seg][vi] = acc;
+  __syncthreads();
+  if (seg == 0 && v < V) {
+    unsigned long long t = overwrite ? 0ull : state[v];
+#pragma unroll
+    for (int s = 0; s < 8; ++s) t = is_max ? max(t, red[s][vi]) : t + red[s][vi];
+    state[v] = t;
+  }
+}
+
+constexpr int K8_MAX_GROUPS = 4096;  // = EXON_HIP_MAX_GROUPS: what the LDS table holds (64 KiB + the dummy entries)
+size_t k8_partial_words(const LaunchCfg& cfg, int n_groups) { return (size_t)max_grid(cfg) * 4 * (size_t)n_groups; }
+
+template <int G, typename S, bool OVF>
+static hipError_t k8_launch(hipStream_t s, const LaunchCfg& cfg, int* grid_out, const Workspace& ws, const float* x,
+                            const uint8_t* xv, const float* y, const uint8_t* yv, const int32_t* gid, int64_t n,
+                            int32_t klo, int32_t khi, int32_t negate, int32_t keymask, int32_t ysign, int32_t n_groups,
+                            const FoldArgs& fa) {
+  const size_t lds = OVF ? (size_t)(n_groups + 64) * sizeof(K8Entry) : 0;
+  if (lds > 48 * 1024) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k8_cmp_minmax_by_group_main<G, S, OVF>),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
+  }
+  const int grid = grid_for<S>(cfg, n, resident_blocks(k8_cmp_minmax_by_group_main<G, S, OVF>, S::THREADS, lds));
+  *grid_out = grid;
+  hipLaunchKernelGGL((k8_cmp_minmax_by_group_main<G, S, OVF>), dim3(grid), dim3(S::THREADS), lds, s, x, xv, y, yv, gid, n,
+                     klo, khi, negate, keymask, ysign, n_groups, ws.partials, ws.status, reinterpret_cast<const uint8_t*>(ws.status + 8), fa);
+  return hipGetLastError();
+}
+
+hipError_t launch_cmp_minmax_by_group(hipStream_t s, const LaunchCfg& cfg, const Workspace& ws, const float* x,
+                                      const uint8_t* x_valid, const float* y, const uint8_t* y_valid, const int32_t* gid,
+                                      int64_t n, double thr, int cmp_op, int n_groups, int64_t* d_state) {
+  if (n <= 0) return hipSuccess;
+  if (n_groups < 1 || n_groups > K8_MAX_GROUPS) return hipErrorInvalidValue;
+  int32_t klo, khi, negate;
+  if (!cmp_to_key_range(thr, cmp_op, cfg.x_is_int, &klo, &khi, &negate)) return hipErrorInvalidValue;
+  const int32_t keymask = cfg.x_is_int ? 0 : 0x7FFFFFFF, ysign = cfg.y_is_int ? 0 : 0x7FFFFFFF;
+  const int V = 4 * n_groups, n_add = 2 * n_groups;
+  const FoldArgs fa = fold_args(cfg, ws, V, V, d_state, nullptr);
+  // the big shapes as soon as every CU gets a tile (use_big_shape); the register variant takes K4's 16384-row tile once
+  // every CU gets one of those, the table variant stays at J = 2 (K4's choice for its table variant)
+  const bool big = use_big_shape(cfg, n), big4 = big && n / ShapeOf<ShapeBig>::TILE >= (int64_t)cfg.compute_units;
+  int grid = 1;
+  hipError_t e;
+#define EXON_K8_ARGS s, cfg, &grid, ws, x, x_valid, y, y_valid, gid, n, klo, khi, negate, keymask, ysign, n_groups, fa
+  switch (n_groups) {
+#define EXON_K8_CASE(GG)                                                                                            \
+  case GG:                                                                                                          \
+    e = big4 ? k8_launch<GG, ShapeBig, false>(EXON_K8_ARGS)                                                          \
+        : big ? k8_launch<GG, ShapeBigJ2, false>(EXON_K8_ARGS)                                                       \
+              : k8_launch<GG, ShapeSmall, false>(EXON_K8_ARGS);                                                      \
+    break;
+    EXON_K8_CASE(1)
+    EXON_K8_CASE(2)
+    EXON_K8_CASE(3)
+    EXON_K8_CASE(4)
+    EXON_K8_CASE(5)
+    EXON_K8_CASE(6)
+    EXON_K8_CASE(7)
+    EXON_K8_CASE(8)
+#undef EXON_K8_CASE
+    default:
+      e = big ? k8_launch<0, ShapeBigJ2, true>(EXON_K8_ARGS) : k8_launch<0, ShapeSmall, true>(EXON_K8_ARGS);
+      break;
+  }
+#undef EXON_K8_ARGS
+  if (e != hipSuccess) return e;
+  if (V <= FUSE_MAX_V) return hipSuccess;  // folded by the main kernel's last workgroup
+  hipLaunchKernelGGL(k8_finalize, dim3((V + 31) / 32), dim3(256), 0, s, ws.partials, grid, V, n_add,
+                     reinterpret_cast<unsigned long long*>(d_state), cfg.overwrite ? 1 : 0);
+  return hipGetLastError();
 }
 
 // ------------------------------------------------------------------------------------------------

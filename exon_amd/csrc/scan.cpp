@@ -198,7 +198,7 @@ int exon_hip_stream_launch_scan_columns(exon_hip_stream* st, const exon_hip_colu
 int exon_hip_stream_plan_first_column(exon_hip_stream* st);
 int exon_hip_stream_plan_kind(exon_hip_stream* st);
 int exon_hip_stream_plan_column(exon_hip_stream* st, int arg);
-void exon_hip_stream_set_value_types(exon_hip_stream* st, int x_type, int y_type);
+int exon_hip_stream_set_value_types(exon_hip_stream* st, int x_type, int y_type);
 int exon_hip_stream_set_null_group(exon_hip_stream* st, std::function<int32_t()> id_of_null);
 int exon_hip_stream_launch_views(exon_hip_stream* st, const uint8_t* d_text, const exon_hip_fastq_views& v);
 void* exon_hip_stream_hip_stream(exon_hip_stream* st);
@@ -2938,16 +2938,22 @@ int exon_hip_stream_consume_scan(exon_hip_stream* st, exon_hip_scan* scan, int64
 
 }  // extern "C"
 
+// K4 and K8 share their columns (x, y, group id) and everything a scan has to tell the stream about them
+static bool plan_cmp_by_group(exon_hip_stream* st) {
+  const int kind = exon_hip_stream_plan_kind(st);
+  return kind == EXON_HIP_PLAN_CMP_AVG_BY_GROUP || kind == EXON_HIP_PLAN_CMP_MINMAX_BY_GROUP;
+}
 static int consume_scan_impl(exon_hip_stream* st, exon_hip_scan* scan, int64_t* rows) {
   int64_t n = 0;
-  // K4 over a VCF / BCF scan: the compared column and AVG's argument may be typed INFO fields (scan columns 4 ..), whose
+  // K4 / K8 over a VCF / BCF scan: the compared column and the aggregate's argument may be typed INFO fields (scan columns 4 ..), whose
   // type the FILE's header decides: Type=Integer -> Int32 values, compared / averaged as integers (schema_builder.rs:197-205)
-  if (exon_hip_stream_plan_kind(st) == EXON_HIP_PLAN_CMP_AVG_BY_GROUP && scan->vcf_like()) {
+  if (plan_cmp_by_group(st) && scan->vcf_like()) {
     const std::vector<exon::InfoSpec>& specs = scan->info_specs();
     auto type_of = [&](int col) {
       return col >= 4 && (size_t)(col - 4) < specs.size() && specs[(size_t)(col - 4)].kind == 'i' ? EXON_HIP_X_INT32 : EXON_HIP_X_FLOAT32;
     };
-    exon_hip_stream_set_value_types(st, type_of(exon_hip_stream_plan_column(st, 0)), type_of(exon_hip_stream_plan_column(st, 1)));
+    const int rc = exon_hip_stream_set_value_types(st, type_of(exon_hip_stream_plan_column(st, 0)), type_of(exon_hip_stream_plan_column(st, 1)));
+    if (rc) return rc;
   }
   if (!scan->gpu_parse && scan->gpu_candidate && scan->rows == 0 && scan->vcf_like()) {
     const std::vector<exon::InfoSpec>& specs = scan->info_specs();
@@ -2995,14 +3001,14 @@ static int consume_scan_impl(exon_hip_stream* st, exon_hip_scan* scan, int64_t* 
     }
     // fall through to the host paths below
   }
-  // K4 grouped by a String / Character INFO key (a dictionary column WITH NULLs from the host readers): the stream turns a NULL
+  // K4 / K8 grouped by a String / Character INFO key (a dictionary column WITH NULLs from the host readers): the stream turns a NULL
   // key into the id of the empty text in this scan's dictionary -- interned when the first NULL shows up -- so that NULL is a
   // group of its own (DataFusion's GROUP BY); the device parser does the same (exon_hip_vcf_parser_set_null_key)
   struct NullGroupGuard {
     exon_hip_stream* st;
     ~NullGroupGuard() { exon_hip_stream_set_null_group(st, nullptr); }
   } null_group_guard{st};
-  if (exon_hip_stream_plan_kind(st) == EXON_HIP_PLAN_CMP_AVG_BY_GROUP && scan->vcf_like()) {
+  if (plan_cmp_by_group(st) && scan->vcf_like()) {
     const std::vector<exon::InfoSpec>& specs = scan->info_specs();
     const int gcol = exon_hip_stream_plan_column(st, 2);
     if (gcol >= 4 && (size_t)(gcol - 4) < specs.size() && specs[(size_t)(gcol - 4)].kind == 's')

@@ -87,6 +87,7 @@ struct exon_hip_plan {
   exon_hip_ctx* ctx;
   exon_hip_plan_desc d;
   int64_t n_i64, n_f64;
+  int64_t n_max = 0;  // the last n_max of the n_i64 words fold by unsigned max, not add (CMP_MINMAX_BY_GROUP: its two extreme planes)
   int n_cols;
   ColSpec cols[4];
 };
@@ -130,14 +131,19 @@ enum { KEYS_NONE = 0, KEYS_LOCAL = 1, KEYS_AGREED = 2 };
 constexpr size_t COLL_SCRATCH = 8192;  // device words for the collectives' votes (up to 511 ranks x 16 bytes), allocated with the state
 constexpr int64_t HOLD_MAX_ROWS = 1 << 17;  // batches up to this many rows are held until their slot is flushed
 
-// keyed layout of a plan's packed state: [planes_i x G int64][tail int64][planes_f x G float64]
-static bool key_layout(const exon_hip_plan* p, int* G, int* planes_i, int* tail, int* planes_f) {
+// keyed layout of a plan's packed state: [planes_i x G int64][tail int64][planes_f x G float64]; the last planes_max of the
+// int64 planes fold by unsigned max where the others add
+static bool key_layout(const exon_hip_plan* p, int* G, int* planes_i, int* tail, int* planes_f, int* planes_max) {
+  *planes_max = 0;
   switch (p->d.kind) {
     case EXON_HIP_PLAN_FLAG_MAPQ_GROUP_COUNT:  // count[R] + the NULL-reference group
       *G = p->d.n_groups, *planes_i = 1, *tail = 1, *planes_f = 0;
       return true;
     case EXON_HIP_PLAN_CMP_AVG_BY_GROUP:  // count(y)[G], count(*)[G], sum(y)[G]
       *G = p->d.n_groups, *planes_i = 2, *tail = 0, *planes_f = 1;
+      return true;
+    case EXON_HIP_PLAN_CMP_MINMAX_BY_GROUP:  // count(y)[G], count(*)[G], minw[G], maxw[G]
+      *G = p->d.n_groups, *planes_i = 4, *tail = 0, *planes_f = 0, *planes_max = 2;
       return true;
   }
   return false;
@@ -386,6 +392,9 @@ static int run_plan(const exon_hip_plan* p, void* stream, const exon_hip_column*
     case EXON_HIP_PLAN_CMP_AVG_BY_GROUP:
       return exon_op_cmp_avg_by_group(ctx, stream, &cols[0], &cols[1], &cols[2], n, d.threshold, d.cmp_op, d.n_groups, counts,
                                       sums, flags);
+    case EXON_HIP_PLAN_CMP_MINMAX_BY_GROUP:
+      return exon_op_cmp_minmax_by_group(ctx, stream, &cols[0], &cols[1], &cols[2], n, d.threshold, d.cmp_op, d.n_groups, counts,
+                                         flags);
     case EXON_HIP_PLAN_QUAL_POS_HIST:
       return exon_op_qual_pos_hist(ctx, stream, &cols[0], n, d.lmax, counts, flags);
     case EXON_HIP_PLAN_OVERLAP_COUNT:
@@ -467,7 +476,7 @@ static int flush_slot(exon_hip_stream* st) {
     ColStage& cs = s.cols[(size_t)c];
     const size_t vbytes = p->cols[c].utf8 ? (size_t)s.bytes : (size_t)s.rows * (size_t)p->cols[c].elem;
     bool null_key_rewritten = false;
-    if (cs.any_null_bitmap && c == 2 && p->d.kind == EXON_HIP_PLAN_CMP_AVG_BY_GROUP && st->null_group) {
+    if (cs.any_null_bitmap && c == 2 && (p->d.kind == EXON_HIP_PLAN_CMP_AVG_BY_GROUP || p->d.kind == EXON_HIP_PLAN_CMP_MINMAX_BY_GROUP) && st->null_group) {
       // a NULL group key becomes the scan's id of the NULL group (in the staging copy, before it goes to HBM): no bitmap
       const int32_t id = st->null_group();
       if (id < 0) return fail(st->ctx, EXON_HIP_ESTATE, "the scan has no dictionary for its nullable group key");
@@ -579,6 +588,20 @@ int exon_hip_plan_create(exon_hip_ctx* ctx, const exon_hip_plan_desc* desc, exon
       }
       p->n_i64 = 2 * desc->n_groups;
       p->n_f64 = desc->n_groups;
+      break;
+    case EXON_HIP_PLAN_CMP_MINMAX_BY_GROUP:
+      p->n_cols = 3;
+      p->cols[0].elem = p->cols[1].elem = p->cols[2].elem = 4;
+      if (desc->n_groups < 1 || desc->n_groups > EXON_HIP_MAX_GROUPS) {
+        delete p;
+        return fail(ctx, EXON_HIP_EUNSUPPORTED, "n_groups %d outside [1, %d]", desc->n_groups, EXON_HIP_MAX_GROUPS);
+      }
+      if (desc->cmp_op < EXON_HIP_GT || desc->cmp_op > EXON_HIP_NE) {
+        delete p;
+        return fail(ctx, EXON_HIP_EINVAL, "bad cmp_op %d", desc->cmp_op);
+      }
+      p->n_i64 = 4 * desc->n_groups;
+      p->n_max = 2 * desc->n_groups;
       break;
     case EXON_HIP_PLAN_OVERLAP_COUNT:
       p->n_cols = 3;
@@ -792,9 +815,20 @@ int exon_hip_stream_launch_scan_columns(exon_hip_stream* st, const exon_hip_colu
 int exon_hip_stream_plan_first_column(exon_hip_stream* st) { return st->plan->d.columns[0]; }
 int exon_hip_stream_plan_kind(exon_hip_stream* st) { return st->plan->d.kind; }
 int exon_hip_stream_plan_column(exon_hip_stream* st, int arg) { return arg >= 0 && arg < st->plan->n_cols ? st->plan->d.columns[arg] : -1; }
-void exon_hip_stream_set_value_types(exon_hip_stream* st, int x_type, int y_type) {
+// The words of a MIN / MAX state are keys of y's TYPE (Int32 and Float32 order their bit patterns differently), so the type is
+// part of such a stream's state: once it holds rows, a scan whose header types the argument otherwise is refused -- its words
+// would be folded into planes of the other encoding and decoded as the wrong type.  (K4's f64 sums do not depend on the type.)
+int exon_hip_stream_set_value_types(exon_hip_stream* st, int x_type, int y_type) {
+  if (st->plan->d.kind == EXON_HIP_PLAN_CMP_MINMAX_BY_GROUP && st->rows_pushed > 0) {
+    const int held = st->y_type >= 0 ? st->y_type : st->plan->d.y_type;
+    if (held != y_type)
+      return fail(st->ctx, EXON_HIP_ESTATE,
+                  "the stream's MIN / MAX state holds %s values and this file's header types the argument %s: one stream takes one type "
+                  "(finish it and open another for this file)", held == EXON_HIP_X_INT32 ? "Int32" : "Float32", y_type == EXON_HIP_X_INT32 ? "Int32" : "Float32");
+  }
   st->x_type = x_type;
   st->y_type = y_type;
+  return EXON_HIP_OK;
 }
 // (taking the provider away flushes what is staged first: those rows' NULL keys still need it)
 int exon_hip_stream_set_null_group(exon_hip_stream* st, std::function<int32_t()> id_of_null) {
@@ -954,12 +988,12 @@ static int ensure_rekey_buffers(exon_hip_stream* st, size_t map_entries) {
 
 // dst += src with src's index g landing on map[g]; synchronises the stream (the map is staged from pageable memory)
 static int permute_add(exon_hip_stream* st, const uint8_t* src, uint8_t* dst, const std::vector<int32_t>& map) {
-  int G = 0, pi = 0, tail = 0, pf = 0;
-  if (!key_layout(st->plan, &G, &pi, &tail, &pf)) return fail(st->ctx, EXON_HIP_EINVAL, "this plan has no group keys");
+  int G = 0, pi = 0, tail = 0, pf = 0, pm = 0;
+  if (!key_layout(st->plan, &G, &pi, &tail, &pf, &pm)) return fail(st->ctx, EXON_HIP_EINVAL, "this plan has no group keys");
   int rc = ensure_rekey_buffers(st, map.size());
   if (rc) return rc;
   if (!map.empty()) HIP_TRY(st->ctx, hipMemcpyAsync(st->d_map, map.data(), map.size() * 4, hipMemcpyHostToDevice, st->stream));
-  HIP_TRY(st->ctx, exon::launch_permute_add_state(st->stream, src, dst, st->d_map, (int)map.size(), G, pi, tail, pf));
+  HIP_TRY(st->ctx, exon::launch_permute_add_state(st->stream, src, dst, st->d_map, (int)map.size(), G, pi, tail, pf, pm));
   HIP_TRY(st->ctx, hipStreamSynchronize(st->stream));
   return EXON_HIP_OK;
 }
@@ -968,8 +1002,8 @@ static int permute_add(exon_hip_stream* st, const uint8_t* src, uint8_t* dst, co
 // agreed dictionary), the scan's kernels write into a scratch state under the SCAN's ids; end: the scan's dictionary is
 // interned into the stream's, and the scratch state is added into the real one under the stream's ids.
 bool exon_hip_stream_is_keyed(exon_hip_stream* st) {
-  int G, a, b, c;
-  return key_layout(st->plan, &G, &a, &b, &c);
+  int G, a, b, c, m;
+  return key_layout(st->plan, &G, &a, &b, &c, &m);
 }
 int exon_hip_stream_begin_scan(exon_hip_stream* st, bool* tracked, bool* redirected) {
   *tracked = *redirected = false;
@@ -1002,8 +1036,8 @@ int exon_hip_stream_end_scan(exon_hip_stream* st, const std::vector<std::string>
     st->saved_state = nullptr;
   }
   if (rc || !ok || !tracked) return rc;
-  int G = 0, pi, tail, pf;
-  key_layout(st->plan, &G, &pi, &tail, &pf);
+  int G = 0, pi, tail, pf, pm;
+  key_layout(st->plan, &G, &pi, &tail, &pf, &pm);
   if (!scan_keys) {  // the key column of this scan is not dictionary-encoded: nothing to re-key by
     if (redirected) return fail(st->ctx, EXON_HIP_EUNSUPPORTED, "the stream is keyed by value but this scan's group column has no dictionary");
     return EXON_HIP_OK;
@@ -1316,8 +1350,9 @@ int exon_hip_rccl_comm_count(void* comm, int32_t* world, int32_t* rank) {
 // bit-identical on every rank and for every collective algorithm RCCL may pick.  States above 1 MiB are integer counters
 // only (K3 with millions of references) or too large to gather 8x: those are all-reduced in place (integer sums are exact).
 // No vote here (the caller owns the buffers: nothing in this call can fail on one rank alone but the collective itself).
-int exon_hip_merge_states(exon_hip_ctx* ctx, void* stream, void* comm, void* d_state, int64_t n_i64, int64_t n_f64,
-                          void* d_gather, void* d_out) {
+// n_max: the last n_max int64 words fold by unsigned max (a plan's extreme planes; 0 through the public entry point)
+static int merge_states(exon_hip_ctx* ctx, void* stream, void* comm, void* d_state, int64_t n_i64, int64_t n_f64,
+                        void* d_gather, void* d_out, int64_t n_max) {
   if (!ctx || !comm || !d_state || !d_out) return fail(ctx, EXON_HIP_EINVAL, "exon_hip_merge_states: NULL argument");
   ExonComm* c = comm_of(comm);
   if (!c) return fail(ctx, EXON_HIP_EINVAL, "exon_hip_merge_states: not a communicator of this library (exon_hip_rccl_comm_init / exon_hip_comm_from_callbacks)");
@@ -1329,6 +1364,7 @@ int exon_hip_merge_states(exon_hip_ctx* ctx, void* stream, void* comm, void* d_s
     return fail(ctx, EXON_HIP_EINVAL, "state of %lld words is too large for the gather + fold form", (long long)(n_i64 + n_f64));
   if (d_gather == nullptr) {  // in-place all-reduce form (large integer states)
     if (n_f64) return fail(ctx, EXON_HIP_EINVAL, "a state with float64 sums is merged by gather + fold: pass d_gather");
+    if (n_max) return fail(ctx, EXON_HIP_EINVAL, "a state with max planes is merged by gather + fold (the all-reduce form is sum-only)");
     if (d_out != d_state) return fail(ctx, EXON_HIP_EINVAL, "the all-reduce form is in place");
     if (c->aborted) return fail(ctx, EXON_HIP_ESTATE, "the communicator was aborted by an earlier time-out");
     if (c->kind == 0) {
@@ -1355,7 +1391,19 @@ int exon_hip_merge_states(exon_hip_ctx* ctx, void* stream, void* comm, void* d_s
   }
   const int rc = comm_all_gather_dev(ctx, c, s, d_state, d_gather, words * 8);  // 8-byte words; no arithmetic in flight
   if (rc) return rc;
-  HIP_TRY(ctx, exon::launch_fold_states(s, d_gather, world, n_i64, n_f64, d_out));
+  HIP_TRY(ctx, exon::launch_fold_states(s, d_gather, world, n_i64, n_f64, d_out, n_max));
+  return EXON_HIP_OK;
+}
+int exon_hip_merge_states(exon_hip_ctx* ctx, void* stream, void* comm, void* d_state, int64_t n_i64, int64_t n_f64,
+                          void* d_gather, void* d_out) {
+  return merge_states(ctx, stream, comm, d_state, n_i64, n_f64, d_gather, d_out, 0);
+}
+// the fold by the plan's own layout: add for count / sum words, unsigned max for the extreme planes
+int exon_hip_plan_fold_states(const exon_hip_plan* plan, void* stream, const void* d_gathered, int32_t world, void* d_out) {
+  if (!plan || !d_gathered || !d_out) return fail(plan ? plan->ctx : nullptr, EXON_HIP_EINVAL, "exon_hip_plan_fold_states: NULL argument");
+  if (world < 1 || plan->n_i64 + plan->n_f64 < 1 || plan->n_i64 + plan->n_f64 > INT32_MAX)
+    return fail(plan->ctx, EXON_HIP_EINVAL, "exon_hip_plan_fold_states: bad sizes (world %d, %lld + %lld words)", world, (long long)plan->n_i64, (long long)plan->n_f64);
+  HIP_TRY(plan->ctx, exon::launch_fold_states(pick_stream(plan->ctx, stream), d_gathered, world, plan->n_i64, plan->n_f64, d_out, plan->n_max));
   return EXON_HIP_OK;
 }
 
@@ -1392,7 +1440,7 @@ int exon_hip_stream_all_reduce(exon_hip_stream* st, void* comm) {
     if (!rc) rc = settle_reset(st);
     if (rc) local(rc, exon_hip_last_error(st->ctx));
   }
-  const bool big = sbytes > GATHER_MERGE_MAX_STATE && p->n_f64 == 0;
+  const bool big = sbytes > GATHER_MERGE_MAX_STATE && p->n_f64 == 0 && p->n_max == 0;  // (the in-place all-reduce is sum-only)
   const int world = c->world;
   if (code == EXON_HIP_OK && !big && st->gather_bytes < sbytes * (size_t)world) {
     if (st->d_gather) {
@@ -1411,8 +1459,8 @@ int exon_hip_stream_all_reduce(exon_hip_stream* st, void* comm) {
   }
   const int v = comm_vote(st->ctx, c, st->stream, d_scratch, code, why.c_str(), "exon_hip_stream_all_reduce");
   if (v) return v;
-  if (big) return exon_hip_merge_states(st->ctx, st->stream, comm, st->d_state, p->n_i64, 0, nullptr, st->d_state);
-  return exon_hip_merge_states(st->ctx, st->stream, comm, st->d_state, p->n_i64, p->n_f64, st->d_gather, st->d_state);
+  if (big) return merge_states(st->ctx, st->stream, comm, st->d_state, p->n_i64, 0, nullptr, st->d_state, 0);
+  return merge_states(st->ctx, st->stream, comm, st->d_state, p->n_i64, p->n_f64, st->d_gather, st->d_state, p->n_max);
 }
 
 // ---- group keys by value: the C ABI (include/exon_hip.h "group keys") ---------------------------------------------------------
@@ -1495,8 +1543,8 @@ int exon_hip_stream_keys(exon_hip_stream* st, char* buf, size_t cap, int32_t* n_
 // names as a declaration of what its ids mean; a keyed stream must find every key it holds in `names` and has its state
 // permuted into the new order.
 static int adopt_keys(exon_hip_stream* st, const std::vector<std::string>& names) {
-  int G = 0, pi, tail, pf;
-  if (!key_layout(st->plan, &G, &pi, &tail, &pf)) return fail(st->ctx, EXON_HIP_EINVAL, "this plan does not group by a key");
+  int G = 0, pi, tail, pf, pm;
+  if (!key_layout(st->plan, &G, &pi, &tail, &pf, &pm)) return fail(st->ctx, EXON_HIP_EINVAL, "this plan does not group by a key");
   if ((int64_t)names.size() > G)
     return fail(st->ctx, EXON_HIP_ECAPACITY, "%zu group keys do not fit the plan's n_groups = %d (create the plan for the union's size)", names.size(), G);
   {
@@ -1665,6 +1713,7 @@ int exon_hip_stream_reset(exon_hip_stream* st) {
   st->overwrite_next = true;
   st->closed = false;
   st->rows_pushed = 0;
+  if (st->plan->d.kind == EXON_HIP_PLAN_CMP_MINMAX_BY_GROUP) st->x_type = st->y_type = -1;  // the new query's own types (the plan's, until a scan says otherwise)
   st->keys.clear();  // a new query: its scans define the key dictionary afresh
   st->keys_state = KEYS_NONE;
   return EXON_HIP_OK;
@@ -1788,6 +1837,34 @@ int exon_hip_stream_finish_arrow(exon_hip_stream* st, struct ArrowArray* out, st
       make_struct(out, (int64_t)key.size(), {prim(key), prim(acnt), prim(asum), prim(rows)});
       make_schema(out_schema, "+s", "", false,
                   {field("i", "group", false), field("L", "avg[count]", false), field("g", "avg[sum]", false),
+                   field("l", "count(*)[count]", false)});
+      break;
+    }
+    case EXON_HIP_PLAN_CMP_MINMAX_BY_GROUP: {
+      const int G = d.n_groups;
+      const int y_type = st->y_type >= 0 ? st->y_type : d.y_type;
+      std::vector<uint8_t> vmin((size_t)G), vmax((size_t)G);
+      std::vector<uint32_t> dmin((size_t)G), dmax((size_t)G);
+      if ((rc = exon_hip_minmax_decode(counts.data() + 2 * (size_t)G, G, 1, y_type, dmin.data(), vmin.data())) ||
+          (rc = exon_hip_minmax_decode(counts.data() + 3 * (size_t)G, G, 0, y_type, dmax.data(), vmax.data())))
+        return fail(st->ctx, rc, "%s", exon_hip_last_error(nullptr));
+      std::vector<int32_t> key;
+      std::vector<uint32_t> lo, hi;
+      std::vector<uint8_t> valid;
+      std::vector<int64_t> cnt, rows;
+      for (int g = 0; g < G; ++g)
+        if (counts[(size_t)(G + g)]) {
+          key.push_back(g);
+          lo.push_back(dmin[(size_t)g]);
+          hi.push_back(dmax[(size_t)g]);
+          valid.push_back(vmin[(size_t)g]);
+          cnt.push_back(counts[(size_t)g]);
+          rows.push_back(counts[(size_t)(G + g)]);
+        }
+      const char* fmt = y_type == EXON_HIP_X_INT32 ? "i" : "f";
+      make_struct(out, (int64_t)key.size(), {prim(key), prim(lo, &valid), prim(hi, &valid), prim(cnt), prim(rows)});
+      make_schema(out_schema, "+s", "", false,
+                  {field("i", "group", false), field(fmt, "min[min]", true), field(fmt, "max[max]", true), field("l", "count[count]", false),
                    field("l", "count(*)[count]", false)});
       break;
     }

@@ -15,7 +15,7 @@ library may pick (an all-reduce's association order is the library's business). 
 import ctypes as C
 import os
 
-from ._lib import PLAN_CMP_AVG_BY_GROUP as L_PLAN_K4, PLAN_FLAG_MAPQ_GROUP_COUNT as L_PLAN_K3
+from ._lib import PLAN_CMP_AVG_BY_GROUP as L_PLAN_K4, PLAN_CMP_MINMAX_BY_GROUP as L_PLAN_K8, PLAN_FLAG_MAPQ_GROUP_COUNT as L_PLAN_K3
 
 
 def env_world():
@@ -44,19 +44,30 @@ def _initialised(group=None):
     return dist.is_available() and dist.is_initialized() and dist.get_world_size(group) > 1
 
 
-def fold_states(gathered, world, n_i64, out, ctx=None, stream=None):
+def fold_states(gathered, world, n_i64, out, ctx=None, stream=None, plan=None):
     """out[v] = sum over ranks r = 0..world-1 (in that order) of gathered[r][v]; words [0, n_i64) are int64 counters,
-    the rest float64 sums bit-cast into the int64 tensor.  Device tensors go through the HIP kernel of the C ABI."""
+    the rest float64 sums bit-cast into the int64 tensor.  Device tensors go through the HIP kernel of the C ABI.
+    `plan`: fold by that plan's own layout (exon_hip_plan_fold_states) -- needed for a MIN / MAX plan, whose two extreme
+    planes (the last half of its int64 words) fold by max."""
     import torch
     V = out.numel()
+    n_max = 0
+    if plan is not None and plan.desc.kind in (L_PLAN_K3, L_PLAN_K4, L_PLAN_K8):
+        G, _, _, _, planes_max = state_layout_ex(plan.desc.kind, plan.desc.n_groups)
+        n_max = planes_max * G  # the last planes_max int64 planes
     if gathered.is_cuda:
         if ctx is None:
             raise RuntimeError("fold_states on device tensors needs the exon_amd Context (no torch fallback on the GPU)")
         s = torch.cuda.current_stream().cuda_stream if stream is None else stream
+        if plan is not None:
+            plan.fold_states(gathered.data_ptr(), world, out.data_ptr(), stream=s)
+            return out
         ctx._check(ctx.lib.exon_hip_fold_states(ctx.h, s, gathered.data_ptr(), world, n_i64, V - n_i64, out.data_ptr()))
         return out
     g = gathered.view(world, V)
     out[:n_i64] = g[:, :n_i64].sum(0)
+    if n_max:  # (words are non-negative: the signed max is the unsigned one)
+        out[n_i64 - n_max:n_i64] = g[:, n_i64 - n_max:n_i64].max(0).values
     if V > n_i64:
         acc = torch.zeros(V - n_i64, dtype=torch.float64)
         for r in range(world):  # fixed order, like the kernel
@@ -65,7 +76,7 @@ def fold_states(gathered, world, n_i64, out, ctx=None, stream=None):
     return out
 
 
-def merge_state(state, n_i64, gathered=None, out=None, group=None, ctx=None):
+def merge_state(state, n_i64, gathered=None, out=None, group=None, ctx=None, plan=None):
     """ONE all-gather of the packed int64-typed `state` (float64 sums bit-cast) + the fixed-order fold.  Returns the
     merged state (`out`, or a new tensor); without an initialised process group of more than one rank: `state`."""
     import torch
@@ -88,7 +99,7 @@ def merge_state(state, n_i64, gathered=None, out=None, group=None, ctx=None):
         gathered.copy_(h)
     else:
         dist.all_gather_into_tensor(gathered, state, group=group)
-    return fold_states(gathered, world, n_i64, out, ctx=ctx)
+    return fold_states(gathered, world, n_i64, out, ctx=ctx, plan=plan)
 
 
 # ---- group keys by VALUE across ranks ("dictionaries identical across shards, else union") -----------------
@@ -98,13 +109,26 @@ def merge_state(state, n_i64, gathered=None, out=None, group=None, ctx=None):
 # AggregateExec(Final), which merges the partitions' partial states by key value.
 
 def state_layout(kind, n_groups):
-    """(G, planes_i64, tail_i64, planes_f64) of a plan's packed state, as exon_hip_stream_set_keys lays it out:
-    [planes_i64 x G int64][tail_i64 int64 (K3: the NULL-reference group)][planes_f64 x G float64]."""
-    from ._lib import PLAN_CMP_AVG_BY_GROUP, PLAN_FLAG_MAPQ_GROUP_COUNT
+    """(G, planes_i64, tail_i64, planes_f64) of a K3 / K4 plan's packed state, as exon_hip_stream_set_keys lays it out:
+    [planes_i64 x G int64][tail_i64 int64 (K3: the NULL-reference group)][planes_f64 x G float64].  Every word adds; a plan
+    with planes that fold by max (MIN / MAX by group) has no four-element layout: state_layout_ex."""
+    layout = state_layout_ex(kind, n_groups)
+    if layout[4]:
+        raise ValueError(f"plan kind {kind} folds {layout[4]} planes by max: use state_layout_ex")
+    return layout[:4]
+
+
+def state_layout_ex(kind, n_groups):
+    """(G, planes_i64, tail_i64, planes_f64, planes_max): state_layout plus how many of the int64 planes -- the LAST
+    planes_max of them -- fold by unsigned max instead of add (0 for K3 / K4, 2 for MIN / MAX by group, whose state is
+    [count(y)[G]] [count(*)[G]] [minw[G]] [maxw[G]])."""
+    from ._lib import PLAN_CMP_AVG_BY_GROUP, PLAN_CMP_MINMAX_BY_GROUP, PLAN_FLAG_MAPQ_GROUP_COUNT
     if kind == PLAN_FLAG_MAPQ_GROUP_COUNT:
-        return n_groups, 1, 1, 0
+        return n_groups, 1, 1, 0, 0
     if kind == PLAN_CMP_AVG_BY_GROUP:
-        return n_groups, 2, 0, 1
+        return n_groups, 2, 0, 1, 0
+    if kind == PLAN_CMP_MINMAX_BY_GROUP:
+        return n_groups, 4, 0, 0, 2
     raise ValueError(f"plan kind {kind} has no group keys")
 
 
@@ -112,15 +136,20 @@ def permute_state(state, layout, mapping):
     """CPU statement of the device re-keying (launch_permute_add_state): a packed int64-typed host tensor keyed by local
     ids -> the same state under the ids `mapping[local]`.  Host tensors only -- tests and gloo launchers hold those; a
     device-resident state is permuted by exon_hip_stream_set_keys."""
+    import numpy as np
     import torch
     if state.is_cuda:
         raise RuntimeError("permute_state is the host form; a device state is re-keyed by Stream.set_keys (no torch fallback on the GPU)")
-    G, pi, tail, pf = layout
+    G, pi, tail, pf = layout[:4]
+    pm = layout[4] if len(layout) > 4 else 0  # (a state_layout_ex layout: the last pm int64 planes fold by max)
     out = torch.zeros_like(state)
     idx = torch.as_tensor(list(mapping), dtype=torch.int64)
     src = torch.arange(len(idx))
     for p in range(pi):
-        out[p * G:(p + 1) * G].index_add_(0, idx, state[p * G + src])
+        if p >= pi - pm:  # words are 0 ("no value") or 1 + a 32-bit key: non-negative, so the signed max is the unsigned one
+            np.maximum.at(out.numpy()[p * G:(p + 1) * G], idx.numpy(), state[p * G + src].numpy())  # (shares `out`'s memory)
+        else:
+            out[p * G:(p + 1) * G].index_add_(0, idx, state[p * G + src])
     out[pi * G:pi * G + tail] = state[pi * G:pi * G + tail]
     fb = pi * G + tail
     for p in range(pf):
@@ -183,7 +212,7 @@ def scan_files(ctx, paths, fmt, make_plan, rank=None, world=None, group=None, co
                 rows += stream.consume(scan)
             finally:
                 scan.close()
-        keyed = plan.desc.kind in (L_PLAN_K3, L_PLAN_K4)
+        keyed = plan.desc.kind in (L_PLAN_K3, L_PLAN_K4, L_PLAN_K8)
         if world > 1 and comm is not None:
             if keyed:
                 stream.reconcile_keys(comm.h.value)
@@ -195,7 +224,7 @@ def scan_files(ctx, paths, fmt, make_plan, rank=None, world=None, group=None, co
             counts, sums = stream.snapshot()
             if world > 1:
                 state = torch.from_numpy(np.concatenate([counts, sums.view(np.int64)]))
-                merged = merge_state(state, len(counts), group=group).numpy()
+                merged = merge_state(state, len(counts), group=group, plan=plan).numpy()
                 counts, sums = merged[:len(counts)].copy(), merged[len(counts):].view(np.float64).copy()
         keys = stream.keys()[0] if keyed else []
         total_rows = rows

@@ -179,6 +179,13 @@ class Context:
         self._check(self.lib.exon_hip_cmp_avg_by_group(self.h, stream, C.byref(c0), C.byref(c1), C.byref(c2), n,
                                                        float(threshold), CMP[op], n_groups, d_counts.ptr, d_sums.ptr))
 
+    def cmp_minmax_by_group(self, x, x_valid, y, y_valid, group_id, n, threshold, op, n_groups, d_state, stream=None):
+        """K8 (Float32 x, y): K4's predicate, then MIN / MAX / COUNT(y) / COUNT(*) per group accumulated into `d_state` =
+        [count_y[G]] [count_rows[G]] [minw[G]] [maxw[G]] int64 words (minmax_decode turns the last two planes into values)."""
+        c0, c1, c2 = _col(x, x_valid, None, n), _col(y, y_valid, None, n), _col(group_id, None, None, n)
+        self._check(self.lib.exon_hip_cmp_minmax_by_group(self.h, stream, C.byref(c0), C.byref(c1), C.byref(c2), n,
+                                                          float(threshold), CMP[op], n_groups, d_state.ptr))
+
     def overlap_count(self, ref_id, ref_valid, start, start_valid, end, end_valid, n, region_ref_id, region_start, region_end,
                       d_count, stream=None):
         """K6: rows whose [start, end] on reference `region_ref_id` overlaps [region_start, region_end] (all three valid)."""
@@ -294,9 +301,30 @@ class Context:
                        x_type=1 if x_type == "i32" else 0, y_type=1 if y_type == "i32" else 0)
         return Plan(self, d, columns)
 
+    def plan_cmp_minmax_by_group(self, op, threshold, n_groups, columns=(0, 1, 2), x_type="f32", y_type="f32"):
+        """MIN(y), MAX(y), COUNT(y), COUNT(*) GROUP BY g behind K4's predicate; the arguments are plan_cmp_avg_by_group's.
+        State: 4 * n_groups int64 words, n_groups <= 4096."""
+        d = L.PlanDesc(kind=L.PLAN_CMP_MINMAX_BY_GROUP, n_groups=n_groups, cmp_op=CMP[op], threshold=threshold,
+                       x_type=1 if x_type == "i32" else 0, y_type=1 if y_type == "i32" else 0)
+        return Plan(self, d, columns)
+
     def plan_qual_pos_hist(self, lmax, columns=(0,)):
         d = L.PlanDesc(kind=L.PLAN_QUAL_POS_HIST, lmax=lmax)
         return Plan(self, d, columns)
+
+
+def minmax_decode(words, is_min, y_type="f32"):
+    """exon_hip_minmax_decode (host-only): state words of a MIN / MAX plan's min plane (is_min) or max plane ->
+    (values float32 / int32 array, valid bool array); a word of 0 is "no value"."""
+    lib = L.load()
+    w = np.ascontiguousarray(words, np.int64)
+    vals = np.zeros(len(w), np.int32 if y_type == "i32" else np.float32)
+    valid = np.zeros(len(w), np.uint8)
+    rc = lib.exon_hip_minmax_decode(w.ctypes.data if len(w) else None, len(w), 1 if is_min else 0, 1 if y_type == "i32" else 0,
+                                    vals.ctypes.data if len(w) else None, valid.ctypes.data if len(w) else None)
+    if rc:
+        raise ExonHipError(rc, lib.exon_hip_last_error(None).decode(errors="replace"))
+    return vals, valid.astype(bool)
 
 
 def bgzf_scan(data, out_base=0):
@@ -996,6 +1024,12 @@ class Plan:
         ptr = d_state.ptr if isinstance(d_state, DeviceBuffer) else int(d_state)
         self.ctx._check(self.ctx.lib.exon_hip_plan_launch_chunks(self.h, stream, arr, ncol, len(chunks), ns,
                                                                  L.LAUNCH_OVERWRITE if overwrite else L.LAUNCH_ACCUMULATE, ptr))
+
+    def fold_states(self, d_gathered, world, d_out, stream=None):
+        """exon_hip_plan_fold_states: `world` packed states of this plan (rank-major device memory) folded in rank order by
+        the plan's own layout -- add for counts and sums, unsigned max for the extreme planes of a MIN / MAX plan."""
+        ptr = lambda x: x.ptr if isinstance(x, DeviceBuffer) else int(x)  # noqa: E731
+        self.ctx._check(self.ctx.lib.exon_hip_plan_fold_states(self.h, stream, ptr(d_gathered), world, ptr(d_out)))
 
     def close(self):
         if self.h:

@@ -24,6 +24,8 @@
  *   exon_hip_cmp_avg_by_group             info."AF" > lit, AVG(qual), COUNT(*) GROUP BY filter over
  *        LazyVCFArrayBuilder columns (exon-vcf/src/array_builder/lazy_array_builder.rs:205-216,
  *        info_builder.rs:152-309)
+ *   exon_hip_cmp_minmax_by_group          the same filter, MIN(qual), MAX(qual), COUNT(*) GROUP BY filter: DataFusion 44's
+ *        MinAccumulator / MaxAccumulator (datafusion-functions-aggregate min_max.rs, not vendored) behind the same FilterExec
  *   exon_hip_qual_pos_hist                QualityScoreStringToList::invoke
  *        (exon-core/src/udfs/sequence/quality_score_string_to_list.rs:56-117) + unnest + GROUP BY
  *   exon_hip_regroup_files_by_size        regroup_files_by_size
@@ -213,6 +215,29 @@ int exon_hip_cmp_avg_by_group(exon_hip_ctx* ctx, void* stream, const exon_hip_co
                               int64_t n, double threshold, int32_t cmp_op, int32_t n_groups,
                               int64_t* d_counts /*[2*n_groups]*/, double* d_sums /*[n_groups]*/);
 
+/* K8.  K4's predicate (x valid AND x <cmp_op> threshold: f32 through its totalOrder key, Int32 exactly), then per dictionary id
+ *      g = group_id[i] in [0, n_groups), with d_state = [count_y[G]] [count_rows[G]] [minw[G]] [maxw[G]] (4 * n_groups int64):
+ *        count_y[g]    += (y valid)                                      -- COUNT(y)
+ *        count_rows[g] += 1                                              -- COUNT(*)
+ *        minw[g] = max(minw[g], 1 + (0xFFFFFFFF - u(y)))  if y valid     -- MIN(y)
+ *        maxw[g] = max(maxw[g], 1 + u(y))                 if y valid     -- MAX(y)
+ *      u(y) is the unsigned-ordered 32-bit key of y: Float32 with bits b: b ^ (b < 0 ? 0xFFFFFFFF : 0x80000000) -- IEEE totalOrder,
+ *      -NaN < -inf < ... < -0 < +0 < ... < +inf < +NaN, the order K4's predicate uses and arrow-rs' / DataFusion's ungrouped
+ *      MinAccumulator (min_max.rs, total_cmp) --; Int32: b ^ 0x80000000.  A word of 0 means "no value yet" and BOTH extreme planes
+ *      fold by unsigned max, so a zeroed state is the empty state and two states merge by add (counts) / max (extremes):
+ *      exon_hip_plan_fold_states.  exon_hip_minmax_decode turns the words back into values.
+ *      1 <= n_groups <= EXON_HIP_MAX_GROUPS; more is EXON_HIP_EUNSUPPORTED (K4's tier beyond the LDS table is not extended to this
+ *      operator).  Nullable group ids are refused and an id outside [0, n_groups) is reported as for K4.  Accumulates.  The bare
+ *      operator takes Float32 x and y, like K4's; Int32 columns go through a plan (exon_hip_plan_desc.x_type / y_type). */
+int exon_hip_cmp_minmax_by_group(exon_hip_ctx* ctx, void* stream, const exon_hip_column* x /*f32*/,
+                                 const exon_hip_column* y /*f32*/, const exon_hip_column* group_id /*i32*/,
+                                 int64_t n, double threshold, int32_t cmp_op, int32_t n_groups,
+                                 int64_t* d_state /*[4*n_groups]*/);
+/* Host-only: n state words of K8's min plane (is_min != 0) or max plane -> values.  y_type: EXON_HIP_X_FLOAT32 / EXON_HIP_X_INT32.
+ * out_values receives n 4-byte values (float or int32 bit patterns), out_valid n bytes: 0 where the word is 0 (no value). */
+int exon_hip_minmax_decode(const int64_t* words, int64_t n, int32_t is_min, int32_t y_type, void* out_values /*n x 4 bytes*/,
+                           uint8_t* out_valid /*n bytes*/);
+
 /* K5.  d_hist[p*256 + b] += |{ reads r, p < len(r) : bytes[offsets[r] + p] == b }| for p < lmax;
  *      positions >= lmax are an error (status word, reported by exon_hip_stream_finish / sync). */
 int exon_hip_qual_pos_hist(exon_hip_ctx* ctx, void* stream, const exon_hip_column* quality_scores /*utf8*/,
@@ -261,12 +286,17 @@ int exon_hip_regroup_files_by_size(const int64_t* sizes, int32_t n_files, int32_
 #define EXON_HIP_PLAN_QUAL_POS_HIST 5
 #define EXON_HIP_PLAN_OVERLAP_COUNT 6 /* region_chrom_id / region_start / region_end; columns: ref_id, start, end */
 #define EXON_HIP_PLAN_WITHIN_COUNT 7  /* same fields, strict form: start > region_start AND end < region_end */
+/* K4's fields (cmp_op, threshold, x_type, y_type, n_groups <= EXON_HIP_MAX_GROUPS, columns x, y, group_id); state: 4 * n_groups int64.
+ * The min / max words are keys of y's TYPE, so the type belongs to a stream's state: exon_hip_stream_consume_scan takes it from
+ * the first file's header and refuses (EXON_HIP_ESTATE, the stream unchanged) a later file that types the argument otherwise;
+ * exon_hip_stream_reset starts over.  Ranks that merge such states must have agreed on the type (the plan's, or the same files' headers). */
+#define EXON_HIP_PLAN_CMP_MINMAX_BY_GROUP 8
 
 #define EXON_HIP_X_FLOAT32 0
 #define EXON_HIP_X_INT32 1
 typedef struct exon_hip_plan_desc {
   int32_t kind;          /* EXON_HIP_PLAN_* */
-  int32_t n_groups;      /* K3: n_refs; K4: dictionary size; else 0 */
+  int32_t n_groups;      /* K3: n_refs; K4 / K8: dictionary size; else 0 */
   /* K2 */
   int32_t region_chrom_id;
   /* K4: type of the compared column x.  EXON_HIP_X_FLOAT32 (0): Float32, widened to Float64 and compared in IEEE totalOrder.
@@ -322,6 +352,12 @@ int exon_hip_fold_states(exon_hip_ctx* ctx, void* stream, const void* d_gathered
  * in-place ncclAllReduce of an integer-only state (n_f64 == 0, d_out == d_state) -- for states too large to gather. */
 int exon_hip_merge_states(exon_hip_ctx* ctx, void* stream, void* rccl_comm, void* d_state, int64_t n_i64, int64_t n_f64,
                           void* d_gather, void* d_out);
+/* The fold by the PLAN's own layout: `world` packed states of this plan, rank-major, folded in rank order -- add for count and
+ * sum words, unsigned max for the two extreme planes of a CMP_MINMAX_BY_GROUP plan.  Works for every plan kind; for the kinds
+ * whose words all add it is bit-identical to exon_hip_fold_states.  exon_hip_stream_all_reduce applies the same fold; the in-place
+ * ncclAllReduce form of exon_hip_merge_states is sum-only and is never taken for a plan with max planes.  `stream`: hipStream_t,
+ * NULL = the ctx's own.  d_out may not alias d_gathered. */
+int exon_hip_plan_fold_states(const exon_hip_plan* plan, void* stream, const void* d_gathered, int32_t world, void* d_out);
 /* ncclGetUniqueId / ncclCommInitRank / ncclCommDestroy for hosts without an RCCL binding: rank 0 makes the 128-byte id and
  * ships it to the other ranks by any means; every rank then calls comm_init (collective) on its own ctx / GPU. */
 /* ---- communicators (ABI 5: the handle is OPAQUE -- made by one of the two calls below, never a bare ncclComm_t) --------------------
