@@ -917,7 +917,9 @@ hipError_t launch_flag_mapq_group_count(hipStream_t s, const LaunchCfg& cfg, con
 //   AVG state = f64 sum + count of non-null y (Float32 widened to Float64 before the add).
 //   12.25 B/row: f32 x + f32 y + i32 group id + 2 validity bits.  Group ids < G <= 8 live in registers:
 //   COUNT(*) / COUNT(y) in two u64 registers of 8 x 8-bit fields (a row adds 1 << 8g), spilled to
-//   per-group u32 registers before a field can overflow; sums in G f64 registers.
+//   per-group u32 registers before a field can overflow; sums in G f64 registers for G <= 4, in lane-private LDS
+//   slots (one ds_add_f64 per row, K4_SLOTS_MIN_G below) for G = 5 .. 8 -- the default benchmark's 5 groups: 1.86 - 1.91 ms
+//   per 1e9 rows against 1.99 - 2.00 ms with register groups on the same box (profiles/k4_lane_slots.md).
 // ------------------------------------------------------------------------------------------------
 //   More than 8 groups (OVF), three tiers by dictionary id -- ids are handed out in order of first appearance, so the
 //   frequent keys of a skewed column are the early ones:
@@ -989,6 +991,19 @@ struct K4Entry {  // tier-2 table entry
   double sum;
   unsigned cnn, crow;
 };
+// Lane-private LDS slots (G >= K4_SLOTS_MIN_G register groups, not the > 8-group variant): instead of G conditional f64 adds per
+// row (cmp + 64-bit select + add: 4 G vector instructions, although the row belongs to ONE group) a row adds its y to the slot of
+// its own group with one ds_add_f64.  sum[wave][g][lane], struct of arrays: the 64 lanes of an add sit 8 bytes apart whatever
+// their g, so an access never has a bank conflict; the row g == G of a wave is its dummy: a row that fails the predicate, has a
+// NULL y or carries an id >= G adds THERE (an ADDRESS select, not a value select: a NaN / Inf in such a row never meets a real
+// slot, and an id out of range or negative never leaves the wave's block; gmax reports it as before).  The packed 8-bit counters
+// stay in registers (their LDS form -- two ds_add_u32 per row -- was measured and is not faster: profiles/k4_lane_slots.md).
+// A lane's adds to one slot execute in program order (the LDS queue of a wave is a FIFO) starting from +0.0, and
+// x + (+0.0) == x bit for bit for every x a slot can hold (a slot that starts at +0.0 never becomes -0.0), so the per-lane sums
+// -- and with them the shuffle tree, the record and the fold -- are the bits the register form gives.
+// Tile loop of <5, .>: 30.0 vector instructions + 1 LDS add per row against 45.9 with register groups; 5 and more groups take
+// the slots (and J = 2 with them, see k4_one_launch), 1 .. 4 groups keep the registers: there the slot form is not faster.
+constexpr int K4_SLOTS_MIN_G = 5;
 template <int G, typename S, bool OVF, bool YI = false>
 __global__ __launch_bounds__(S::THREADS) void k4_cmp_avg_by_group_main(
     const float* __restrict__ x, const uint8_t* __restrict__ xvalid, const float* __restrict__ y,
@@ -1012,6 +1027,14 @@ __global__ __launch_bounds__(S::THREADS) void k4_cmp_avg_by_group_main(
   }
   Packed prow = 0, pnn = 0;  // field g
   unsigned gmax = 0;
+  // lane-private LDS slots (above): [wave][g <= G][lane], the row g == G is the wave's dummy
+  constexpr bool SLOTS = !OVF && G >= K4_SLOTS_MIN_G;
+  __shared__ double slot_sum[SLOTS ? WAVES * (G + 1) * 64 : 1];
+  double* const my_sum = slot_sum + (SLOTS ? wave * (G + 1) * 64 + lane : 0);
+  if (SLOTS) {  // every lane clears (and later reads) its own slots only: no barrier
+#pragma unroll
+    for (int k = 0; k <= G; ++k) my_sum[k * 64] = 0.0;
+  }
   // tier-2 table (OVF only): NO entries + 64 per-lane dummy entries
   extern __shared__ K4Entry k4_ovf[];
   const int NO = OVF ? NL - G : 0, NOD = NO + 64;
@@ -1040,6 +1063,14 @@ __global__ __launch_bounds__(S::THREADS) void k4_cmp_avg_by_group_main(
   auto row = [&](unsigned pass, float yf, int32_t g, unsigned yv) {
     unsigned yq = pass & yv;
     gmax = max(gmax, (unsigned)g);  // ids are validated over ALL rows (cheaper than a per-row flag)
+    if (SLOTS) {
+      const unsigned gi = min((unsigned)g, (unsigned)G);  // an id out of range (negative: huge) -> the dummy row
+      atomicAdd(&my_sum[(yq ? gi : (unsigned)G) * 64u], ydbl(yf));
+      const unsigned sh = ((unsigned)g & FMASK) * 8u;
+      prow += (Packed)pass << sh;
+      pnn += (Packed)yq << sh;
+      return;
+    }
     if (OVF) {
       const unsigned in_regs = unsigned((unsigned)g < (unsigned)G);
       pass &= in_regs;
@@ -1327,6 +1358,10 @@ __global__ __launch_bounds__(S::THREADS) void k4_cmp_avg_by_group_main(
     }
   }
   spill();
+  if (SLOTS) {  // the lane's own slots back into its registers: the reductions below are the register form's
+#pragma unroll
+    for (int k = 0; k < G; ++k) sum[k] = my_sum[k * 64];
+  }
 
   if (gmax >= (unsigned)(OVF ? NG : G)) atomicOr(status, 4);
   if (direct) {  // this workgroup's chunks -> the per-range chunk lists
@@ -1787,13 +1822,19 @@ size_t k4_tail_records(int64_t n, int n_groups) {
   return (size_t)(std::min<int64_t>(n, K4_TAIL_CHUNK_ROWS) + K4_TAIL_SLACK);
 }
 
+template <int G>
+using K4Big = typename std::conditional<(G >= K4_SLOTS_MIN_G), ShapeBigJ2, ShapeBig>::type;  // the 1024-thread shape of G register groups
+
 static hipError_t k4_one_launch(hipStream_t s, const LaunchCfg& cfg, const Workspace& ws, const float* x, const uint8_t* x_valid,
                                 const float* y, const uint8_t* y_valid, const int32_t* gid, int64_t n, int32_t klo, int32_t khi,
                                 int32_t negate, int32_t keymask, int32_t yint, int n_groups, int64_t* d_counts, double* d_sums) {
   const int nl = k4_nl(n_groups);
   const bool has_tail = n_groups > nl;
-  // K4 keeps the 16384-row tile whenever every CU gets one: measured on MI355X at 1e7 rows J = 4 27.8 us, J = 2 31.5 us
-  // (its per-tile bookkeeping -- counter spills, 15-value reductions -- outweighs the better tile balance that pays for K2)
+  // With register groups (1 .. 4 groups) K4 keeps the 16384-row tile whenever every CU gets one: measured on MI355X at 1e7 rows
+  // J = 4 27.8 us, J = 2 31.5 us (its per-tile bookkeeping -- counter spills, 15-value reductions -- outweighs the better tile
+  // balance that pays for K2).  With the sums in lane-private LDS slots (5 .. 8 groups) the choice was run again and J = 2 wins:
+  // 5 groups, 1e9 rows 1.86 - 1.91 ms against 1.92 - 1.96 at J = 4, 125e6 rows 0.238 - 0.252 against 0.257, 1e7 rows
+  // 29.5 - 30.5 us against 31.1 (profiles/k4_lane_slots.md); the threshold -- a 16384-row tile per CU -- stays.
   const bool big = n / ShapeOf<ShapeBig>::TILE >= (int64_t)cfg.compute_units && use_big_shape(cfg, n);
   int grid = 1;
   hipError_t e;
@@ -1842,7 +1883,7 @@ static hipError_t k4_one_launch(hipStream_t s, const LaunchCfg& cfg, const Works
   switch (n_groups) {
 #define EXON_K4_CASE(GG)                                                                                                        \
   case GG:                                                                                                                      \
-    e = big ? k4_launch<GG, ShapeBig, false>(s, cfg, &grid, ws, x, x_valid, y, y_valid, gid, n, klo, khi, negate, keymask, yint, GG, fa, tail)   \
+    e = big ? k4_launch<GG, K4Big<GG>, false>(s, cfg, &grid, ws, x, x_valid, y, y_valid, gid, n, klo, khi, negate, keymask, yint, GG, fa, tail)   \
             : k4_launch<GG, ShapeSmall, false>(s, cfg, &grid, ws, x, x_valid, y, y_valid, gid, n, klo, khi, negate, keymask, yint, GG, fa, tail); \
     break;
     EXON_K4_CASE(1)
