@@ -22,6 +22,7 @@
 
 #include "arrow_build.h"
 #include "bgzf_index.h"
+#include "cmp_key.h"
 #include "decimal_f32.h"
 #include "io.h"
 #include "parallel.h"
@@ -97,12 +98,32 @@ struct VCFHeader {
   std::vector<std::string> samples;
 };
 
+// One pushed-down comparison on a numeric column (exon_hip_scan_set_predicate): `qual` (field 6) or a Number=1 Float / Integer INFO key,
+// folded into K4's key range (cmp_key.h) so that the host reader and the device mask share one rule bit for bit.
+struct ValuePredicate {
+  bool active = false;
+  bool qual = false;    // field 6; else INFO key `key`
+  bool is_int = false;  // Type=Integer: Int32 compared exactly
+  std::string key;
+  int32_t klo = 0, khi = 0, negate = 0;
+  // scan column 2 (qual) or an INFO spec; the caller has checked the column's type
+  static ValuePredicate make(bool qual, const std::string& key, bool is_int, int cmp_op, double literal) {
+    ValuePredicate v;
+    v.active = cmp_to_key_range(literal, cmp_op, is_int, &v.klo, &v.khi, &v.negate);
+    v.qual = qual;
+    v.is_int = is_int;
+    v.key = key;
+    return v;
+  }
+};
+
 struct VCFConfig {
   int64_t batch_size = DEFAULT_BATCH_SIZE;
   int threads = 0;  // decode threads: 0 = all host cores (EXON_HIP_DECODE_THREADS), 1 = sequential reader
   bool defer_decode = false;  // the caller will take the byte stream (GPU-side parsing): start no parse pipeline
   std::string info_field;  // exon.vcf_parse_info=true + SELECT info."<F>": Number=1 Float/Integer field -> f32 column
   RegionFilter filter;
+  ValuePredicate value;  // ANDed with `filter`
   // EXON_HIP_REFERENCE_QUIRKS=1: reproduce IndexedAsyncBatchStream::read_batch as written
   // (exon-vcf/src/indexed_async_batch_stream.rs:118-166) on indexed scans: one stream per index chunk; a batch takes records
   // until `batch_size` of them hit the region, then appends up to `batch_size` FURTHER records of the chunk UNFILTERED
@@ -527,11 +548,63 @@ inline bool vcf_region_hit(const char* line, size_t len, const Region& rg) {
   return pos >= 1 && pos >= rg.start && pos <= rg.end;
 }
 
+// The pushed-down value predicate on a raw data line: true iff the predicate's column is valid AND value <op> literal.
+//   qual      field 6: '.' is NULL; else VCFArrayBuilder::parse_f32
+//   INFO key  field 8: INFO '.' is NULL; the FIRST piece whose key matches decides (Info::get); an absent key, a bare key and a
+//             value of '.' (or none) are NULL; Float through parse_f32, Integer through parse_i32 (the builder's Int32 rule)
+// NULL never passes, `!=` included (FilterExec drops a NULL predicate).  A field the builder would raise on -- a malformed number,
+// fewer than eight fields -- lets the record THROUGH: the builder then raises its own error with its own text; nothing is thrown
+// here.
+// DECISION: like the region filter this is the READER'S filter.  Dropped rows are not built (no dictionary entry, no validation of
+// their other fields), and exon_hip_scan_rows counts the rows emitted.
+inline bool vcf_value_hit(const char* line, size_t len, const ValuePredicate& vp) {
+  const int want = vp.qual ? 5 : 7;
+  size_t a = 0;
+  for (int f = 0; f < want; ++f) {
+    const char* t = static_cast<const char*>(memchr(line + a, '\t', len - a));
+    if (!t) return true;  // fewer than eight fields: the builder's error
+    a = (size_t)(t - line) + 1;
+  }
+  const char* t = static_cast<const char*>(memchr(line + a, '\t', len - a));
+  if (!t && vp.qual) return true;  // (QUAL is never the last of eight fields)
+  const char* p = line + a;
+  size_t n = t ? (size_t)(t - p) : len - a;
+  if (n == 1 && p[0] == '.') return false;
+  if (!vp.qual) {  // the first piece of the key
+    size_t i = 0;
+    bool found = false;
+    while (i < n && !found) {
+      size_t j = i;
+      while (j < n && p[j] != ';') ++j;
+      size_t eq = i;
+      while (eq < j && p[eq] != '=') ++eq;
+      if (eq - i == vp.key.size() && memcmp(p + i, vp.key.data(), vp.key.size()) == 0) {
+        if (eq == j) return false;  // a bare key: present but missing
+        const size_t vl = j - eq - 1;
+        p += eq + 1;
+        n = vl;
+        found = true;
+      } else {
+        i = j + 1;
+      }
+    }
+    if (!found || n == 0 || (n == 1 && p[0] == '.')) return false;
+  }
+  int32_t key;
+  try {
+    key = vp.is_int ? VCFArrayBuilder::parse_i32(p, n) : h_f32_key(VCFArrayBuilder::parse_f32(p, n));
+  } catch (const std::exception&) {
+    return true;  // the builder raises it
+  }
+  return cmp_key_hit(key, vp.klo, vp.khi, vp.negate);
+}
+
 // one slab of VCF text parsed with slab-local dictionaries (header contigs pre-seeded, so their ids are global)
 struct VCFParseCtx {
   std::vector<std::string> contigs;
   std::vector<InfoSpec> info_specs;  // numeric / Flag kinds only: string INFO fields keep the reader sequential
   RegionFilter filter;
+  ValuePredicate value;
 };
 struct VCFSlab : TextSlab {
   Dictionary chrom_dict, filter_dict;
@@ -552,7 +625,7 @@ inline void parse_vcf_slab(VCFSlab& s, const void* vctx) {
     size_t len = nl ? (size_t)(nl - p) : (size_t)(end - p);
     const char* next = nl ? nl + 1 : end;
     if (len && p[len - 1] == '\r') --len;
-    if (len && p[0] != '#' && (!ctx.filter.active || vcf_region_hit(p, len, ctx.filter.region))) s.b->append(p, len);
+    if (len && p[0] != '#' && (!ctx.filter.active || vcf_region_hit(p, len, ctx.filter.region)) && (!ctx.value.active || vcf_value_hit(p, len, ctx.value))) s.b->append(p, len);
     p = next;
   }
   s.rows = s.b->len();
@@ -619,6 +692,7 @@ class VCFBatchReader : public BatchReader {
         pctx_.contigs = header.contigs;
         pctx_.info_specs = info_specs;
         pctx_.filter = cfg_.filter;
+        pctx_.value = cfg_.value;
         pipe_.reset(new SlabPipeline<VCFSlab>(ss->r.release_source(), std::move(carry), 1, threads,
                                               [](VCFSlab& s, const void* c) { parse_vcf_slab(s, c); }, &pctx_));
       }
@@ -642,6 +716,7 @@ class VCFBatchReader : public BatchReader {
       }
       if (line.empty() || line[0] == '#') continue;
       if (cfg_.filter.active && !vcf_region_hit(line.data(), line.size(), cfg_.filter.region)) continue;
+      if (cfg_.value.active && !vcf_value_hit(line.data(), line.size(), cfg_.value)) continue;
       b.append(line);
     }
     if (b.is_empty()) return false;

@@ -89,6 +89,12 @@ hipError_t launch_region_mask(hipStream_t s, bool range_form, const int32_t* id_
                               const int64_t* end, const uint8_t* pos_valid, const uint8_t* in_valid, int64_t n, int32_t id,
                               int64_t a, int64_t b, uint8_t* out_valid, unsigned long long* n_pass);
 
+// pushed-down value predicate as a row mask: out_valid = in_valid AND region_mask AND (x valid AND x <cmp_op> literal, K4's rule;
+// x_is_int: Int32 values compared exactly, else Float32 widened to Float64 in totalOrder); *n_pass += rows that pass the predicate
+// and the region.  region_mask / in_valid may be null (all ones); region_mask may be out_valid.  hipErrorInvalidValue: cmp_op.
+hipError_t launch_value_mask(hipStream_t s, const void* x, const uint8_t* x_valid, bool x_is_int, double literal, int cmp_op, const uint8_t* region_mask,
+                             const uint8_t* in_valid, int64_t n, uint8_t* out_valid, unsigned long long* n_pass);
+
 // out[v] = sum over ranks (rank order) of gathered[rank][v]; words [0, n_i64) int64, then n_f64 float64; the last n_max of the
 // int64 words fold by unsigned max instead (K8's extreme planes)
 hipError_t launch_fold_states(hipStream_t s, const void* gathered, int world, int64_t n_i64, int64_t n_f64, void* out, int64_t n_max = 0);

@@ -18,6 +18,7 @@
 //     order, so f64 sums are bit-reproducible for a given launch shape.
 // Reference semantics restated by each kernel are cited at the kernel.
 #include "kernels.h"
+#include "host/cmp_key.h"
 
 #include <algorithm>
 #include <cstdlib>
@@ -1473,58 +1474,56 @@ static hipError_t k4_launch(hipStream_t s, const LaunchCfg& cfg, int* grid_out, 
   return hipGetLastError();
 }
 
-// ---- host: fold (<op>, thr) into an inclusive f32 totalOrder key range --------------------------
-static inline float h_key_f32(int32_t k) {
-  int32_t b = k ^ ((k >> 31) & 0x7FFFFFFF);
-  float f;
-  memcpy(&f, &b, 4);
-  return f;
-}
-static inline int64_t h_f64_key(double d) {
-  int64_t b;
-  memcpy(&b, &d, 8);
-  return b ^ ((b >> 63) & 0x7FFFFFFFFFFFFFFFLL);
-}
-// smallest key k in [INT32_MIN, INT32_MAX + 1] whose column value compares >= t (or > t) with the literal.
-//   Float32 column: the value of key k is the f32 with that totalOrder key, widened to f64, compared in totalOrder;
-//   Int32 column (x_is_int): the value IS k.  DataFusion compares Int32 with an Int64 literal as integers and with a
-//   Float64 literal after casting the column to Float64; every int32 is exact in f64, so one f64 comparison covers both
-//   (an integer literal beyond 2^53 is beyond int32 anyway: the range saturates the same way).  A NaN or -0.0 literal
-//   behaves as in arrow-rs' totalOrder float compare: NaN above every number, (f64)0 = +0.0 above -0.0.
-static int64_t first_key_not_less(int64_t t, bool strict_greater, bool x_is_int) {
-  int64_t lo = INT32_MIN, hi = (int64_t)INT32_MAX + 1;
-  while (lo < hi) {
-    const int64_t mid = lo + (hi - lo) / 2;
-    const int64_t km = h_f64_key(x_is_int ? (double)(int32_t)mid : (double)h_key_f32((int32_t)mid));
-    const bool ok = strict_greater ? (km > t) : (km >= t);
-    if (ok) hi = mid;
-    else lo = mid + 1;
+// ---- host: (<op>, thr) folded into an inclusive f32 totalOrder key range: cmp_to_key_range (host/cmp_key.h), shared with the
+// host reader's pushed-down value predicate
+
+// ------------------------------------------------------------------------------------------------
+// Pushed-down value predicate as a row mask (exon_hip_scan_set_predicate), the sibling of k_region_mask above: one row per lane in
+// whole waves, pass = K4's row predicate on column x (cmp_key_passes: valid AND key in [klo, khi], complemented for !=; an Int32
+// column's bits are its key, keymask = 0), ANDed with the region's mask bit when the scan has a region too.  A ballot gives 8 bytes
+// of bitmap per wave, one atomic per workgroup adds the rows kept to *n_pass.  out_valid is the plan-operand form
+// exon_hip_stream_launch_scan_columns consumes, (first operand's validity) AND pass; without a plan operand (in_valid == nullptr:
+// batches) it is the mask of the rows the scan emits.  region_mask may be out_valid itself: a wave reads the 8 bytes it then writes.
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_value_mask(const float* __restrict__ x, const uint8_t* __restrict__ x_valid, const uint8_t* region_mask,
+                                                    const uint8_t* __restrict__ in_valid, int64_t n, int32_t klo, int32_t khi, int32_t negate,
+                                                    int32_t keymask, uint8_t* out_valid, unsigned long long* __restrict__ n_pass) {
+  const int lane = threadIdx.x & 63;
+  unsigned long long kept = 0;
+  const int64_t n64 = (n + 63) & ~(int64_t)63;  // whole waves: the ballot needs every lane
+  for (int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x; r < n64; r += (int64_t)gridDim.x * 256) {
+    bool pass = false, operand = false;
+    if (r < n) {
+      pass = cmp_key_passes(x[r], valid1(x_valid, r) ? 1u : 0u, klo, khi, negate, keymask) != 0 && valid1(region_mask, r);
+      operand = valid1(in_valid, r);
+    }
+    const unsigned long long hits = __ballot(pass);         // rows the scan emits
+    const unsigned long long m = __ballot(pass && operand);  // ... of which the plan's operand is valid
+    if (lane < 8) {
+      const int64_t r0 = r - lane + lane * 8;
+      if (r0 < n) out_valid[r0 >> 3] = (uint8_t)(m >> (lane * 8));
+    }
+    if (lane == 0) kept += (unsigned long long)__popcll(hits);
   }
-  return lo;
+  // one atomic per workgroup
+  __shared__ unsigned long long red[4];
+  if (lane == 0) red[threadIdx.x >> 6] = kept;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const unsigned long long t = red[0] + red[1] + red[2] + red[3];
+    if (t) atomicAdd(n_pass, t);
+  }
 }
-bool cmp_to_key_range(double thr, int cmp_op, bool x_is_int, int32_t* klo, int32_t* khi, int32_t* negate) {
-  const int64_t t = h_f64_key(thr);
-  const int64_t ge = first_key_not_less(t, false, x_is_int);  // first key with value >= thr
-  const int64_t gt = first_key_not_less(t, true, x_is_int);   // first key with value >  thr
-  int64_t lo, hi;
-  *negate = 0;
-  switch (cmp_op) {
-    case 0: lo = gt; hi = INT32_MAX; break;            // >
-    case 1: lo = ge; hi = INT32_MAX; break;            // >=
-    case 2: lo = INT32_MIN; hi = ge - 1; break;        // <
-    case 3: lo = INT32_MIN; hi = gt - 1; break;        // <=
-    case 4: lo = ge; hi = gt - 1; break;               // =
-    case 5: lo = ge; hi = gt - 1; *negate = 1; break;  // !=
-    default: return false;
-  }
-  if (lo > hi) {  // empty range: encode as an impossible interval
-    *klo = INT32_MAX;
-    *khi = INT32_MIN;
-  } else {
-    *klo = (int32_t)lo;
-    *khi = (int32_t)hi;
-  }
-  return true;
+
+hipError_t launch_value_mask(hipStream_t s, const void* x, const uint8_t* x_valid, bool x_is_int, double literal, int cmp_op, const uint8_t* region_mask,
+                             const uint8_t* in_valid, int64_t n, uint8_t* out_valid, unsigned long long* n_pass) {
+  if (n <= 0) return hipSuccess;
+  int32_t klo, khi, negate;
+  if (!cmp_to_key_range(literal, cmp_op, x_is_int, &klo, &khi, &negate)) return hipErrorInvalidValue;
+  const unsigned grid = (unsigned)std::min<int64_t>((n + 255) / 256, 2048);
+  hipLaunchKernelGGL(k_value_mask, dim3(grid), dim3(256), 0, s, static_cast<const float*>(x), x_valid, region_mask, in_valid, n, klo, khi, negate,
+                     x_is_int ? 0 : 0x7FFFFFFF, out_valid, n_pass);
+  return hipGetLastError();
 }
 
 // records [blocks][3 x RG] (kinds cnn, crow, sum over the first RG ids) ADDED into a state of NG > RG groups

@@ -66,6 +66,17 @@ __device__ __forceinline__ unsigned list_first_item(unsigned c, const unsigned* 
   for (int w = 0; w < wave; ++w) base += wave_tot[w];
   return base + incl - c;
 }
+// bytes [src, src + n) to dst: 8 at a time (unaligned on both sides: the hardware takes it), the rest one by one.  The span copier of
+// the text columns' fill kernels (text_columns.hip) and of the take-rows step (take_rows.hip)
+__device__ __forceinline__ void copy_run(uint8_t* __restrict__ dst, const uint8_t* __restrict__ src, unsigned n) {
+  unsigned i = 0;
+  for (; i + 8 <= n; i += 8) {
+    const uint32_t a = *reinterpret_cast<const uint32_t*>(src + i), b = *reinterpret_cast<const uint32_t*>(src + i + 4);
+    *reinterpret_cast<uint32_t*>(dst + i) = a;
+    *reinterpret_cast<uint32_t*>(dst + i + 4) = b;
+  }
+  for (; i < n; ++i) dst[i] = src[i];
+}
 // byte-per-item flags -> Arrow validity bitmap (8 items per thread); n = offsets[n_rows], never more than the `cap_items`
 // the flag / bitmap buffers were sized for (a slab whose items do not fit is handed back to the host decoder by the fill
 // kernel's exception count: nothing past the buffers may be touched on the way there)

@@ -10,6 +10,7 @@
 #include <map>
 #include <deque>
 #include <array>
+#include <atomic>
 #include <functional>
 #include <memory>
 #include <mutex>
@@ -78,6 +79,14 @@ struct exon_hip_scan {
   size_t region_mask_cap = 0;
   unsigned long long* d_region_pass = nullptr;  // rows kept so far in this consume
   ExonTextScratch* text_scratch = nullptr;  // device buffers of the projected string / list columns (text_columns.hip)
+  // pushed-down value predicate (exon_hip_scan_set_predicate): the host reader's filter (VCFConfig::value) and, on the GPU decode
+  // path, a row mask (k_value_mask) ANDed with the region's; batches take the kept rows on the device (take_rows.hip)
+  exon::ValuePredicate value;
+  int value_column = -1, value_op = 0;
+  double value_literal = 0;
+  ExonTakeScratch* take_scratch = nullptr;
+  // exon_hip_scan_export_stats: written by the exporter's producer thread, read when the scan has ended
+  std::atomic<int64_t> stat_slabs{0}, stat_compacted{0}, stat_d2h{0};
 
   // the reader as its format's class (nullptr for any other format)
   template <class R>
@@ -179,6 +188,11 @@ struct SlabCopier {
     used = off + bytes;
   }
   // the staged bytes start for the host; ev_done[slot] fires when they have arrived
+  size_t bytes() const {
+    size_t b = 0;
+    for (const Item& it : items) b += it.bytes;
+    return b;
+  }
   hipError_t launch() {
     if (err != hipSuccess) return err;
     hipError_t e = hipEventRecord(ex->ev_ready, hs);
@@ -372,6 +386,7 @@ static std::unique_ptr<exon::BatchReader> open_reader(const exon_hip_scan& s, De
   vc.batch_size = bs;
   vc.info_field = s.info_field_s;
   vc.filter = rf;
+  vc.value = s.value;
   vc.projection = s.opt.projection;
   exon::BAMConfig ac;
   ac.batch_size = bs;
@@ -382,6 +397,7 @@ static std::unique_ptr<exon::BatchReader> open_reader(const exon_hip_scan& s, De
       vc.reference_tail_quirk = reference_tail_quirk(rf);
       exon::VCFConfig cfg = config(s.vcf(), vc);
       cfg.defer_decode = device;
+      cfg.value = s.value;  // (set after the scan was opened: exon_hip_scan_set_predicate re-opens the reader)
       return std::unique_ptr<exon::BatchReader>(new exon::VCFBatchReader(s.path, c, cfg));
     }
     case EXON_HIP_FORMAT_BCF: return std::unique_ptr<exon::BatchReader>(new exon::BCFBatchReader(s.path, config(s.bcf(), vc)));
@@ -655,10 +671,50 @@ int exon_hip_scan_bind_ctx(exon_hip_scan* s, exon_hip_ctx* ctx) {
   return EXON_HIP_OK;
 }
 
+int exon_hip_scan_set_predicate(exon_hip_scan* s, int32_t column, int32_t cmp_op, double literal) {
+  if (!s) return fail(nullptr, EXON_HIP_EINVAL, "exon_hip_scan_set_predicate: NULL argument");
+  if (s->format != EXON_HIP_FORMAT_VCF)
+    return fail(nullptr, EXON_HIP_EUNSUPPORTED, "exon_hip_scan_set_predicate: a value predicate is pushed into VCF text scans (plain, gzip, BGZF); filter this format's batches above the scan");
+  if (s->exporter || s->rows != 0)
+    return fail(nullptr, EXON_HIP_ESTATE, "exon_hip_scan_set_predicate: the scan %s already; set the predicate right after exon_hip_scan_open", s->exporter ? "is bound to a context" : "has been read from");
+  const std::vector<exon::InfoSpec>& specs = s->info_specs();
+  if (column < 0 || (size_t)column >= 4 + specs.size()) return fail(nullptr, EXON_HIP_EINVAL, "exon_hip_scan_set_predicate: column %d is outside the scan's %zu columns", column, 4 + specs.size());
+  if (cmp_op < EXON_HIP_GT || cmp_op > EXON_HIP_NE) return fail(nullptr, EXON_HIP_EINVAL, "exon_hip_scan_set_predicate: cmp_op %d (EXON_HIP_GT .. EXON_HIP_NE)", cmp_op);
+  const char kind = column >= 4 ? specs[(size_t)(column - 4)].kind : column == 2 ? 'f' : column == 1 ? 'l' : 's';
+  if (kind != 'f' && kind != 'i') {
+    const char* ty = kind == 'l' ? "Int64" : kind == 'b' ? "a Flag (Boolean)" : kind == 's' ? "dictionary-encoded (Dictionary<Int32, Utf8>)" : "a list (List<..>)";
+    return fail(nullptr, EXON_HIP_EUNSUPPORTED, "exon_hip_scan_set_predicate: column %d is %s; a pushed-down comparison takes a Float32 column or an Int32 column of values (qual, Number=1 Float / Integer INFO keys)", column, ty);
+  }
+  const char* qv = getenv("EXON_HIP_REFERENCE_QUIRKS");
+  if (qv && qv[0] == '1' && s->region.active)
+    return fail(nullptr, EXON_HIP_EUNSUPPORTED, "exon_hip_scan_set_predicate: with EXON_HIP_REFERENCE_QUIRKS=1 a region scan reproduces the reference's unfiltered tail, which has no meaning for a second conjunct");
+  const exon::ValuePredicate before = s->value;
+  s->value = exon::ValuePredicate::make(column == 2, column >= 4 ? specs[(size_t)(column - 4)].name : std::string(), kind == 'i', cmp_op, literal);
+  try {  // the reader starts over with the predicate in its config (nothing has been read: the header again, that is all)
+    s->reader = open_reader(*s, s->gpu_parse ? Decode::Device : Decode::Host);
+  } catch (const std::exception& e) {
+    s->value = before;
+    return fail(nullptr, EXON_HIP_EINVAL, "%s", e.what());
+  }
+  s->value_column = column;
+  s->value_op = cmp_op;
+  s->value_literal = literal;
+  return EXON_HIP_OK;
+}
+
+int exon_hip_scan_export_stats(exon_hip_scan* s, int64_t* slabs, int64_t* compacted_slabs, int64_t* d2h_bytes) {
+  if (!s) return fail(nullptr, EXON_HIP_EINVAL, "exon_hip_scan_export_stats: NULL argument");
+  if (slabs) *slabs = s->stat_slabs.load();
+  if (compacted_slabs) *compacted_slabs = s->stat_compacted.load();
+  if (d2h_bytes) *d2h_bytes = s->stat_d2h.load();
+  return EXON_HIP_OK;
+}
+
 int exon_hip_scan_close(exon_hip_scan* s) {
   if (s && s->exporter) gpu_export_shutdown(s);
   if (s) s->parser.destroy();
   if (s && s->text_scratch) exon_text_scratch_destroy(s->text_scratch);
+  if (s && s->take_scratch) exon_take_scratch_destroy(s->take_scratch);
   if (s && s->d_region_mask) hipFree(s->d_region_mask);
   if (s && s->d_region_pass) hipFree(s->d_region_pass);
   delete s;
@@ -2032,6 +2088,7 @@ struct HostText {
 };
 // EXON_HIP_PIPE_TRACE: where a slab's export spends its time (seconds; per producer thread: every scan's pipeline runs in its own)
 static thread_local double g_t_batches = 0, g_t_release = 0, g_t_text_batch = 0, g_t_views = 0;
+static thread_local double g_t_take = 0;  // the device take-rows step of a scan with a value predicate (its index apart: that is the mask's readback)
 static thread_local double g_t_text_kernels = 0, g_t_fetch_text = 0, g_t_fetch_cols = 0, g_t_block_get = 0, g_t_enqueue = 0, g_t_names = 0;
 // the projected text columns of one slab: `build` describes them in `cols` once the device has built them (export_slab calls it once
 // it knows that the slab keeps rows at all; for GFF `attributes` also when it keeps none: the build is the validation of every ninth field)
@@ -2105,8 +2162,27 @@ static int export_slab(exon_hip_scan* scan, const exon_hip_column* sc, int64_t n
   // unfiltered slab; rows kept here and there are gathered from the whole slab.
   std::vector<uint8_t> hmask;
   std::vector<std::pair<int64_t, int64_t>> runs;  // the runs of rows that go out as views (without a mask: the whole slab); empty: gathered
-  if (row_mask) {
+  // A pushed-down value predicate keeps rows here and there: they are taken out of every column ON THE DEVICE (take_rows.hip) and go
+  // out as one run of views, (0, K) of the taken columns -- no mask comes back, nothing is gathered on the host.  (A region alone
+  // keeps today's paths below, scattered survivors included.)
+  const bool compact = row_mask && scan->value.active;
+  const uint32_t* d_rows = nullptr;
+  const unsigned* d_K = nullptr;
+  scan->stat_slabs += 1;
+  if (compact) {
+    int64_t K = 0;
+    if (const int rc = exon_take_index(ctx, hs, &scan->take_scratch, row_mask, n_rows, &d_rows, &d_K, &K)) return rc;
+    scan->stat_d2h += 4;
+    if (K == 0) {  // as a slab that keeps nothing below
+      if (projected && L.text_unkept)
+        if (const int rc = projected->build()) return rc;
+      return EXON_HIP_OK;
+    }
+    scan->stat_compacted += 1;
+    runs.emplace_back(0, K);
+  } else if (row_mask) {
     hmask.resize((size_t)(n_rows + 7) / 8);
+    scan->stat_d2h += (int64_t)hmask.size();
     if (hipMemcpyAsync(hmask.data(), row_mask, hmask.size(), hipMemcpyDeviceToHost, hs) != hipSuccess || hipStreamSynchronize(hs) != hipSuccess)
       return fail(ctx, EXON_HIP_EDEVICE, "row mask of a slab back to the host");
     if (n_rows & 7) hmask.back() &= (uint8_t)((1u << (n_rows & 7)) - 1u);
@@ -2131,10 +2207,18 @@ static int export_slab(exon_hip_scan* scan, const exon_hip_column* sc, int64_t n
   exon::SlabPlan plan = as_views ? exon::slab_plan(L, runs.front().first, runs.back().second) : exon::slab_plan(L, 0, n_rows);
   const size_t path_stage = plan.bytes + 512 * (size_t)L.n_cols;
   if (projected) {
-    int rc = projected->build();  // the device builds the text columns now
+    int rc = projected->build();  // the device builds the text columns now (of every row: the build validates the records)
     if (rc) return rc;
+    ExonTextColumns taken;
+    if (compact) {  // the kept rows of every text column, as columns of their own
+      const double tt0 = now_s();
+      rc = exon_text_take(ctx, hs, scan->take_scratch, projected->cols, d_rows, d_K, &taken);
+      g_t_take += now_s() - tt0;
+      if (rc) return rc;
+      scan->stat_d2h += 4 * (2 * ExonTextColumns::MAX_NODES + 2);  // (its one readback: the rows kept and every level's total)
+    }
     const double tf0 = now_s();
-    rc = fetch_text(ctx, &cp, path_stage, projected->cols, text_p.get(), scan->opt.batch_size > exon::K_ZERO_ROWS);
+    rc = fetch_text(ctx, &cp, path_stage, compact ? taken : projected->cols, text_p.get(), scan->opt.batch_size > exon::K_ZERO_ROWS);
     g_t_fetch_text += now_s() - tf0;
     if (rc) return rc;
   } else if (!cp.reserve(path_stage)) {
@@ -2144,6 +2228,19 @@ static int export_slab(exon_hip_scan* scan, const exon_hip_column* sc, int64_t n
   if (!sb) return fail(ctx, EXON_HIP_ENOMEM, "no pinned block of %zu bytes for a slab's columns", plan.bytes);
   uint8_t* blk = static_cast<uint8_t*>(sb->block);
   std::shared_ptr<exon::SharedBlock> sb_ref(sb, [](exon::SharedBlock* b) { exon::block_unref(b); });  // this slab's own reference
+  exon_hip_column taken_sc[exon::SLAB_MAX_COLS] = {};
+  if (compact) {  // the kept rows of every fixed-width column: rows [0, K) of the taken columns are what the plan covers
+    const double tt0 = now_s();
+    ExonTakeColumn tc[exon::SLAB_MAX_COLS];
+    for (int c = 0; c < L.n_cols; ++c) tc[c] = ExonTakeColumn{L.cols[c].width() ? sc[c].values : nullptr, sc[c].validity, L.cols[c].width(), nullptr, nullptr};
+    if (const int rc = exon_take_fixed(ctx, hs, scan->take_scratch, tc, L.n_cols)) return rc;
+    for (int c = 0; c < L.n_cols; ++c) {
+      taken_sc[c].values = tc[c].out_values;
+      taken_sc[c].validity = tc[c].out_validity;
+    }
+    sc = taken_sc;
+    g_t_take += now_s() - tt0;
+  }
   for (int c = 0; c < L.n_cols; ++c) {
     const size_t w = (size_t)L.cols[c].width();
     if (w && sc[c].values) cp.add(blk + plan.voff[c], static_cast<const uint8_t*>(sc[c].values) + (size_t)plan.c_lo * w, (size_t)plan.c_n * w);
@@ -2154,6 +2251,7 @@ static int export_slab(exon_hip_scan* scan, const exon_hip_column* sc, int64_t n
   }
   if (!as_views) memcpy(blk + plan.moff, hmask.data(), hmask.size());
   if (plan.zbytes) memset(blk + plan.zoff, 0, plan.zbytes);
+  scan->stat_d2h += (int64_t)cp.bytes();
   const hipError_t e = cp.launch();
   if (e != hipSuccess) return fail(ctx, EXON_HIP_EDEVICE, "columns of a slab towards the host: %s", hipGetErrorString(e));
   g_t_fetch_cols += now_s() - tc0;
@@ -2218,6 +2316,8 @@ static int export_fastq_slab(exon_hip_scan* scan, const ExonTextColumns& ft, int
   ++ex->n_exports;
   auto text_p = std::make_shared<HostText>();  // (its reference to the block lives as long as the closure below)
   if (const int rc = fetch_text(ctx, &cp, 4096, ft, text_p.get(), false)) return rc;
+  scan->stat_slabs += 1;
+  scan->stat_d2h += (int64_t)cp.bytes();
   const hipError_t e = cp.launch();
   if (e != hipSuccess) return fail(ctx, EXON_HIP_EDEVICE, "reads of a slab towards the host: %s", hipGetErrorString(e));
   const int slot = cp.slot;
@@ -2570,10 +2670,13 @@ static int consume_text_gpu(exon_hip_stream* st, exon_hip_scan* scan, int64_t* r
   int32_t rg_id = -1;
   int64_t rg_a = 0, rg_b = 0;
   bool rg_range = false;
-  if (filtered) {
-    region_target(scan, &rg_id, &rg_a, &rg_b, &rg_range);
-    if (!scan->d_region_pass) HIP_TRY(ctx, hipMalloc((void**)&scan->d_region_pass, 8));
-    HIP_TRY(ctx, hipMemsetAsync(scan->d_region_pass, 0, 8, hs));
+  // ---- the pushed-down value predicate (VCF text): a second mask kernel, ANDed with the region's; the count of rows kept is ITS count
+  // then (word 0; the region's own count goes to word 1 and is not read)
+  const bool valued = scan->value.active && scan->vcf();
+  if (filtered) region_target(scan, &rg_id, &rg_a, &rg_b, &rg_range);
+  if (filtered || valued) {
+    if (!scan->d_region_pass) HIP_TRY(ctx, hipMalloc((void**)&scan->d_region_pass, 16));
+    HIP_TRY(ctx, hipMemsetAsync(scan->d_region_pass, 0, 16, hs));
   }
 
   // ---- the byte sources: the whole stream, or one per index chunk ------------------------------------------------
@@ -2663,8 +2766,8 @@ static int consume_text_gpu(exon_hip_stream* st, exon_hip_scan* scan, int64_t* r
         const int64_t n_rows = p.n_rows;
         for (auto& c : p.sc) c.length = n_rows;
         const uint8_t* row_mask = nullptr;
-        if (filtered) {
-          // the per-record interval hit, on the device: mask = (first operand's validity) AND hit
+        if (filtered || valued) {
+          // the per-record interval hit and / or value comparison, on the device: mask = (first operand's validity) AND hit
           const size_t need = (size_t)(n_rows + 7) / 8 + 64;
           if (scan->region_mask_cap < need) {
             HIP_TRY(ctx, hipStreamSynchronize(hs));  // the previous slab's kernel may still read the old buffer
@@ -2677,8 +2780,15 @@ static int consume_text_gpu(exon_hip_stream* st, exon_hip_scan* scan, int64_t* r
           }
           const int first = exon_hip_stream_plan_first_column(st);
           const uint8_t* in_valid = first >= 0 && first < 4 + EXON_HIP_MAX_INFO_FIELDS ? p.sc[first].validity : nullptr;
-          HIP_TRY(ctx, exon::launch_region_mask(hs, rg_range, p.id_col, p.id_valid, p.c_start, p.c_end, p.pos_valid, in_valid, n_rows, rg_id, rg_a, rg_b,
-                                                scan->d_region_mask, scan->d_region_pass));
+          if (filtered)  // (with a value predicate behind it: the bare hits, the plan's operand joins in the second kernel)
+            HIP_TRY(ctx, exon::launch_region_mask(hs, rg_range, p.id_col, p.id_valid, p.c_start, p.c_end, p.pos_valid, valued ? nullptr : in_valid, n_rows, rg_id, rg_a,
+                                                  rg_b, scan->d_region_mask, scan->d_region_pass + (valued ? 1 : 0)));
+          if (valued) {
+            const exon_hip_column& x = p.sc[scan->value_column];
+            if (!x.values) return fail(ctx, EXON_HIP_ESTATE, "value predicate: the device parser did not build column %d", scan->value_column);
+            HIP_TRY(ctx, exon::launch_value_mask(hs, x.values, x.validity, scan->value.is_int, scan->value_literal, scan->value_op, filtered ? scan->d_region_mask : nullptr,
+                                                 in_valid, n_rows, scan->d_region_mask, scan->d_region_pass));
+          }
           row_mask = scan->d_region_mask;
         }
         // (BED: of its projection bits only `name` is a text column; the others are fixed-width or NULL)
@@ -2717,12 +2827,12 @@ static int consume_text_gpu(exon_hip_stream* st, exon_hip_scan* scan, int64_t* r
   const double t_loop = now_s();
   if (trace) {
     if (scan->exporter)
-      fprintf(stderr, "[exon-hip pipe] export (cumulative over this thread): text kernels %.1f ms, text columns D2H %.1f (pinned block %.1f), path columns D2H %.1f, names %.1f, batches %.1f (path views %.1f, text views %.1f, waiting for the consumer %.1f), slab release %.1f\n",
-              g_t_text_kernels * 1e3, g_t_fetch_text * 1e3, g_t_block_get * 1e3, g_t_fetch_cols * 1e3, g_t_names * 1e3, g_t_batches * 1e3, g_t_views * 1e3, g_t_text_batch * 1e3, g_t_enqueue * 1e3, g_t_release * 1e3);
+      fprintf(stderr, "[exon-hip pipe] export (cumulative over this thread): text kernels %.1f ms, take-rows %.1f ms, text columns D2H %.1f (pinned block %.1f), path columns D2H %.1f, names %.1f, batches %.1f (path views %.1f, text views %.1f, waiting for the consumer %.1f), slab release %.1f\n",
+              g_t_text_kernels * 1e3, g_t_take * 1e3, g_t_fetch_text * 1e3, g_t_block_get * 1e3, g_t_fetch_cols * 1e3, g_t_names * 1e3, g_t_batches * 1e3, g_t_views * 1e3, g_t_text_batch * 1e3, g_t_enqueue * 1e3, g_t_release * 1e3);
     fprintf(stderr, "[exon-hip pipe] setup %.1f ms, loop %.1f ms (%zu source(s); slabs: wait+H2D+inflate %.1f, parse %.1f, other %.1f; file reader busy %.1f)\n",
             (t_init - t_begin) * 1e3, (t_loop - t_init) * 1e3, n_sources, t_next * 1e3, t_parse * 1e3, (t_loop - t_init - t_next - t_parse) * 1e3, t_reader * 1e3);
   }
-  if (rc == EXON_HIP_OK && filtered) {  // the scan emitted the rows that hit the region
+  if (rc == EXON_HIP_OK && (filtered || valued)) {  // the scan emitted the rows that hit the region and pass the predicate
     unsigned long long kept = 0;
     HIP_TRY(ctx, hipMemcpy(&kept, scan->d_region_pass, 8, hipMemcpyDeviceToHost));
     total = (int64_t)kept;

@@ -237,16 +237,7 @@ __global__ __launch_bounds__(TPB) void k_fastq_measure(const uint8_t* __restrict
     desc_valid[(r >> 5) + 1] = (uint32_t)(m >> 32);
   }
 }
-// bytes [src, src + n) of the text to dst: 8 at a time (unaligned on both sides: the hardware takes it), the rest one by one
-__device__ __forceinline__ void copy_run(uint8_t* __restrict__ dst, const uint8_t* __restrict__ src, unsigned n) {
-  unsigned i = 0;
-  for (; i + 8 <= n; i += 8) {
-    const uint32_t a = *reinterpret_cast<const uint32_t*>(src + i), b = *reinterpret_cast<const uint32_t*>(src + i + 4);
-    *reinterpret_cast<uint32_t*>(dst + i) = a;
-    *reinterpret_cast<uint32_t*>(dst + i + 4) = b;
-  }
-  for (; i < n; ++i) dst[i] = src[i];
-}
+// (copy_run, the 8-byte span copier of every fill kernel here: list_kernels.h, shared with take_rows.hip)
 __global__ __launch_bounds__(TPB) void k_fastq_fill(const uint8_t* __restrict__ text, unsigned n_reads, const int32_t* __restrict__ head_s,
                                                     const int32_t* __restrict__ seq_s, const int32_t* __restrict__ qual_s, const int32_t* __restrict__ name_off,
                                                     const int32_t* __restrict__ desc_off, const int32_t* __restrict__ seq_off, const int32_t* __restrict__ qual_off,
@@ -1005,6 +996,17 @@ void exon_text_scratch_destroy(ExonTextScratch* s) { delete s; }
 //          the derivation above is then not the only thing between a slab and the end of a buffer.
 //   BED    values[0] (max_bytes = n_bytes): the name fields, disjoint parts of the text: <= n_bytes: fits.  No BED buffer is "checked":
 //          the name bytes of a slab cannot exceed the slab.  k_bed_name_fill bounds its reads and writes all the same.
+//   take-rows (take_rows.hip: the kept rows of the columns above as columns of their own, in a scratch of ITS own that every call
+//          sizes from the inputs it is given; K kept rows of n_rows, a node of `length` elements and `n_values` bytes)
+//   take   rows[K], K <= n_rows indices, against n_rows + 64: fits.  A fixed column's K values / K bits against n_rows values + 64 bytes /
+//                    n_rows / 8 + 64 bytes: fits
+//   take   a node's lengths [k], offsets [k + 1], validity bits [k] for the k <= length elements its rows list names (the rows list of a
+//                    LIST's child is the kept rows' items: no more than the items there are), against length + 64, length + 65 entries,
+//                    length / 8 + 64 bytes: fits
+//   take   a UTF8 node's bytes: spans of the kept elements, disjoint parts of the input's n_values bytes, against n_values + 64: fits
+//   take   a LIST's item-index list: the kept rows' item ranges, disjoint ranges of the child's `length` items, against length + 64: fits
+//          No take buffer is "checked": a compacted buffer is never larger than its input.  The kernels bound every index and every
+//          write all the same.
 static int scratch_for(exon_hip_ctx* ctx, ExonTextScratch** sp, int64_t max_rows, int64_t max_bytes, TextLayout lay) {
   ExonTextScratch* s = *sp;
   if (s && s->layout == lay && s->max_rows >= max_rows && s->max_bytes >= max_bytes) return EXON_HIP_OK;

@@ -428,8 +428,11 @@ class Scan:
                "gff": {"attributes": 256}, "gtf": {"attributes": 256}, "bed": L.PROJECT_BED}
 
     def __init__(self, path, fmt, compression=None, batch_size=0, info_field=None, region=None, use_index=False,
-                 gpu_parse=False, project=()):
-        """project: names of the reference's columns beyond the fused kernels' operands (EXON_HIP_PROJECT_*): VCF "id", "ref", "alt",
+                 gpu_parse=False, project=(), where=None):
+        """where: (column, op, literal), one comparison the scan evaluates itself (exon_hip_scan_set_predicate): `column` a scan column
+        (VCF: 2 = qual, 4 + k = typed INFO field k of info_field; Float32, or Int32 values), `op` one of ">" ">=" "<" "<=" "=" "!=";
+        rows whose column is NULL or fails are not emitted (ANDed with `region`).
+        project: names of the reference's columns beyond the fused kernels' operands (EXON_HIP_PROJECT_*): VCF "id", "ref", "alt",
         "info", "formats" (the last two as the reference's unparsed Utf8 columns; info from the GPU pipeline too, formats host reader only);
         BAM "name", "cigar", "sequence", "quality_score" -- appended behind the default columns in that order; GFF "attributes"
         (the reference's Map<Utf8, List<Utf8>>, column 8); GTF "attributes" (the reference's Map<Utf8, Utf8>, column 8); BED "name",
@@ -448,6 +451,26 @@ class Scan:
         if rc:
             raise ExonHipError(rc, self.lib.exon_hip_last_error(None).decode(errors="replace"))
         self.h = h
+        if where is not None:
+            try:
+                self.set_predicate(*where)
+            except Exception:
+                self.close()
+                raise
+
+    WHERE_OPS = {">": 0, ">=": 1, "<": 2, "<=": 3, "=": 4, "!=": 5}
+
+    def set_predicate(self, column, op, literal):
+        """exon_hip_scan_set_predicate: before bind_ctx / the first batch / Stream.consume; a second call replaces the first.  `op` may
+        be the C ABI's integer too."""
+        self._check(self.lib.exon_hip_scan_set_predicate(self.h, column, self.WHERE_OPS[op] if isinstance(op, str) else op, float(literal)))
+        return self
+
+    def export_stats(self):
+        """After the scan has ended: {"slabs", "compacted_slabs", "d2h_bytes"} of the GPU pipeline's batch export (exon_hip_scan_export_stats)."""
+        a, b, c = C.c_int64(), C.c_int64(), C.c_int64()
+        self._check(self.lib.exon_hip_scan_export_stats(self.h, C.byref(a), C.byref(b), C.byref(c)))
+        return {"slabs": a.value, "compacted_slabs": b.value, "d2h_bytes": c.value}
 
     def _check(self, rc):
         if rc < 0:

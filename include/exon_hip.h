@@ -592,8 +592,27 @@ int exon_hip_scan_rows(exon_hip_scan* scan, int64_t* rows_emitted);
  * sequence, quality_scores as Utf8 columns built on the device (exon-fastq/src/array_builder.rs:68-102), plain, gzip or BGZF;
  * EXON_HIP_EUNSUPPORTED for other formats and for scans whose batches the host reader must build (list-valued INFO keys, the
  * info / formats text columns).  Call before the first
- * exon_hip_scan_next; `ctx` must outlive the scan. */
+ * exon_hip_scan_next; `ctx` must outlive the scan.  A scan with a pushed-down value predicate (exon_hip_scan_set_predicate) masks
+ * every slab on the device, takes the surviving rows of every column there and copies only those back. */
 int exon_hip_scan_bind_ctx(exon_hip_scan* scan, exon_hip_ctx* ctx);
+/* (additive; the ABI stays 5)
+ * One pushed-down comparison, evaluated by the scan itself: a row is emitted iff column `column` is valid AND value <cmp_op> literal
+ * (EXON_HIP_GT .. EXON_HIP_NE), by K4's rule (Float32 widened to Float64 and compared in totalOrder; Int32 compared exactly).
+ * ANDed with `region` when the scan has one.  Call after exon_hip_scan_open and before exon_hip_scan_bind_ctx / the first
+ * exon_hip_scan_next / exon_hip_stream_consume_scan (later: EXON_HIP_ESTATE); a second call replaces the first.
+ * `column` is a scan column as the plans use them; VCF: 2 = qual, 4 + k = typed INFO field k of `info_field`.  Float32 columns and
+ * Int32 columns that are not dictionary ids (Number=1 Float / Integer keys) are accepted; pos (Int64), dictionary, Flag and list
+ * columns are EXON_HIP_EUNSUPPORTED, a column outside the schema or a cmp_op outside 0 .. 5 EXON_HIP_EINVAL, any format but
+ * EXON_HIP_FORMAT_VCF (plain, gzip or BGZF; with or without region / use_index) EXON_HIP_EUNSUPPORTED, and so is a region scan under
+ * EXON_HIP_REFERENCE_QUIRKS=1 (that opener's unfiltered tail has no meaning for a second conjunct).
+ * This is the reader's own filter, like `region`: dropped rows are not built and exon_hip_scan_rows counts the rows emitted.  A
+ * fused plan over such a scan (exon_hip_stream_consume_scan) sees the kept rows only: K2 / K6 / K7 count them, K4 / K8 get a
+ * second conjunct.  As with a region, a FILTER dictionary built on the device may hold values that only dropped rows carried:
+ * they show up as groups with zero counts. */
+int exon_hip_scan_set_predicate(exon_hip_scan* scan, int32_t column, int32_t cmp_op, double literal);
+/* after the scan has ended: slabs exported by the GPU pipeline, how many of them went through the device take-rows step,
+ * bytes copied device -> host for batches (mask / count words included). Any pointer may be NULL. */
+int exon_hip_scan_export_stats(exon_hip_scan* scan, int64_t* slabs, int64_t* compacted_slabs, int64_t* d2h_bytes);
 /* number of index chunks an indexed scan planned (-1 when the scan is not index-driven) */
 int exon_hip_scan_index_chunks(exon_hip_scan* scan, int32_t* n_chunks);
 /* Region -> BGZF chunks from a tabix (.tbi, is_bai = 0; `ref_name` resolved through the index' names) or BAI

@@ -159,6 +159,11 @@ extern "C" {
     pub fn exon_hip_scan_decoded_on_gpu(scan: *mut exon_hip_scan, decoded: *mut i32, inflated: *mut i32) -> c_int;
     pub fn exon_hip_scan_rows(scan: *mut exon_hip_scan, rows_emitted: *mut i64) -> c_int;
     pub fn exon_hip_scan_bind_ctx(scan: *mut exon_hip_scan, ctx: *mut exon_hip_ctx) -> c_int;
+    /// one pushed-down comparison on a Float32 / Int32 value column of a VCF scan (EXON_HIP_GT .. EXON_HIP_NE), evaluated by the scan
+    /// itself and ANDed with its region; call right after exon_hip_scan_open
+    pub fn exon_hip_scan_set_predicate(scan: *mut exon_hip_scan, column: i32, cmp_op: i32, literal: f64) -> c_int;
+    /// after the scan has ended: slabs the GPU pipeline exported, how many went through the device take-rows step, bytes copied back
+    pub fn exon_hip_scan_export_stats(scan: *mut exon_hip_scan, slabs: *mut i64, compacted_slabs: *mut i64, d2h_bytes: *mut i64) -> c_int;
     pub fn exon_hip_scan_close(scan: *mut exon_hip_scan) -> c_int;
     /// GpuFilterAggExec::execute for one file in one call
     pub fn exon_hip_stream_consume_scan(s: *mut exon_hip_stream, scan: *mut exon_hip_scan, rows: *mut i64) -> c_int;
