@@ -152,6 +152,7 @@ PLAN_QUAL_POS_HIST = 5
 PLAN_OVERLAP_COUNT = 6
 PLAN_WITHIN_COUNT = 7
 PLAN_CMP_MINMAX_BY_GROUP = 8
+PLAN_READ_STATS_HIST = 9
 LAUNCH_ACCUMULATE = 0
 LAUNCH_OVERWRITE = 1
 CMP = {">": 0, ">=": 1, "<": 2, "<=": 3, "=": 4, "==": 4, "!=": 5, "<>": 5}
@@ -250,6 +251,9 @@ SIGNATURES = {
     "exon_hip_vcf_parser_destroy": (C.c_int, [_vp]),
     "exon_hip_qual_pos_hist_chunks": (C.c_int, [_vp, _vp, _colp, _i32, _vp, _i32, _vp]),
     "exon_hip_qual_pos_hist_views": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp]),
+    "exon_hip_read_stats_hist": (C.c_int, [_vp, _vp, _colp, _colp, _i64, _i32, _vp]),
+    "exon_hip_read_stats_hist_views": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp]),
+    "exon_hip_read_stats_layout": (C.c_int, [_i32, C.POINTER(_i64)]),
     "exon_hip_fastq_parser_create": (C.c_int, [_vp, _i64, C.POINTER(_vp)]),
     "exon_hip_fastq_parser_parse": (C.c_int, [_vp, _vp, _vp, _i64, _i32, C.POINTER(FASTQViews)]),
     "exon_hip_fastq_parser_destroy": (C.c_int, [_vp]),

@@ -530,6 +530,35 @@ int exon_op_qual_pos_hist_chunks(exon_hip_ctx* ctx, void* stream, const exon_hip
   return EXON_HIP_OK;
 }
 
+// K9 over two sets of line views (a Utf8 column is the views (offsets, offsets + 1) into its data buffer)
+static int read_stats_views(exon_hip_ctx* ctx, void* stream, const char* who, const uint8_t* sbytes, const int32_t* ss, const int32_t* se,
+                            const uint8_t* qbytes, const int32_t* qs, const int32_t* qe, int64_t n_reads, int32_t lmax, int64_t* d_state,
+                            int flags) {
+  if (!ctx || !d_state) return fail(ctx, EXON_HIP_EINVAL, "%s: NULL argument", who);
+  if (n_reads < 0) return fail(ctx, EXON_HIP_EINVAL, "n_reads < 0");
+  if (lmax < 1 || lmax > 65536) return fail(ctx, EXON_HIP_EINVAL, "lmax %d out of range", lmax);
+  if (reinterpret_cast<uintptr_t>(d_state) & 7) return fail(ctx, EXON_HIP_EINVAL, "%s: d_state must be 8-byte aligned", who);
+  hipStream_t s = pick_stream(ctx, stream);
+  if (n_reads == 0) return empty_input(ctx, s, flags, d_state, (size_t)exon::read_stats_words(lmax) * 8);
+  if (!sbytes || !ss || !se || !qbytes || !qs || !qe) return fail(ctx, EXON_HIP_EINVAL, "%s: bytes / starts / ends NULL", who);
+  Workspace ws;
+  int rc;
+  if ((rc = get_workspace(ctx, s, 0, &ws))) return fail(ctx, rc, "workspace allocation failed");
+  HIP_TRY(ctx, exon::launch_read_stats_hist(s, cfg_for(ctx, flags), ws, sbytes, ss, se, qbytes, qs, qe, n_reads, lmax, d_state));
+  return EXON_HIP_OK;
+}
+
+int exon_op_read_stats_hist(exon_hip_ctx* ctx, void* stream, const exon_hip_column* seq, const exon_hip_column* qual, int64_t n_reads,
+                            int32_t lmax, int64_t* d_state, int flags) {
+  static const char* who = "exon_hip_read_stats_hist";
+  if (!seq || !qual) return fail(ctx, EXON_HIP_EINVAL, "%s: sequence / quality_scores column is NULL", who);
+  if (seq->validity || qual->validity) return fail(ctx, EXON_HIP_EUNSUPPORTED, "nullable sequence / quality_scores (the reference columns are non-null)");
+  if (n_reads > 0 && (seq->length < n_reads || qual->length < n_reads)) return fail(ctx, EXON_HIP_EINVAL, "%s: length < n_reads", who);
+  if (n_reads > 0 && (!seq->offsets || !qual->offsets)) return fail(ctx, EXON_HIP_EINVAL, "%s: offsets NULL", who);
+  return read_stats_views(ctx, stream, who, (const uint8_t*)seq->values, seq->offsets, seq->offsets ? seq->offsets + 1 : nullptr,
+                          (const uint8_t*)qual->values, qual->offsets, qual->offsets ? qual->offsets + 1 : nullptr, n_reads, lmax, d_state, flags);
+}
+
 extern "C" {
 
 int exon_hip_region_count(exon_hip_ctx* ctx, void* stream, const exon_hip_column* chrom_id, const exon_hip_column* pos,
@@ -618,6 +647,29 @@ int exon_hip_qual_pos_hist_views(exon_hip_ctx* ctx, void* stream, const uint8_t*
   int rc;
   if ((rc = get_workspace(ctx, s, exon::k5_partial_words(ctx->cfg, lmax), &ws))) return fail(ctx, rc, "workspace allocation failed");
   HIP_TRY(ctx, exon::launch_qual_pos_hist_views(s, ctx->cfg, ws, d_starts, d_ends, d_bytes, n_reads, lmax, d_hist));
+  return EXON_HIP_OK;
+}
+
+int exon_hip_read_stats_hist(exon_hip_ctx* ctx, void* stream, const exon_hip_column* sequence, const exon_hip_column* quality,
+                             int64_t n_reads, int32_t lmax, int64_t* d_state) {
+  return exon_op_read_stats_hist(ctx, stream, sequence, quality, n_reads, lmax, d_state, EXON_HIP_LAUNCH_ACCUMULATE);
+}
+
+int exon_hip_read_stats_hist_views(exon_hip_ctx* ctx, void* stream, const uint8_t* d_bytes, const int32_t* seq_s, const int32_t* seq_e,
+                                   const int32_t* qual_s, const int32_t* qual_e, int64_t n_reads, int32_t lmax, int64_t* d_state) {
+  return read_stats_views(ctx, stream, "exon_hip_read_stats_hist_views", d_bytes, seq_s, seq_e, d_bytes, qual_s, qual_e, n_reads, lmax, d_state,
+                          EXON_HIP_LAUNCH_ACCUMULATE);
+}
+
+// word offsets of the four sections of K9's state, and its size; host only
+int exon_hip_read_stats_layout(int32_t lmax, int64_t* out /*[5]*/) {
+  if (!out) return fail(nullptr, EXON_HIP_EINVAL, "exon_hip_read_stats_layout: out is NULL");
+  if (lmax < 1 || lmax > 65536) return fail(nullptr, EXON_HIP_EINVAL, "lmax %d out of range", lmax);
+  out[0] = 0;
+  out[1] = 4;
+  out[2] = out[1] + lmax + 1;
+  out[3] = out[2] + 102;
+  out[4] = out[3] + 257;
   return EXON_HIP_OK;
 }
 

@@ -18,6 +18,7 @@
 //   SELECT filter, AVG(qual), COUNT(*) FROM v WHERE info."AF" > 0.01 GROUP BY filter            -- K4
 //   SELECT filter, MIN(qual), MAX(qual), COUNT(*) FROM v WHERE info."AF" > 0.01 GROUP BY filter -- K8 (also MIN / MAX(info."DP"))
 //   SELECT * FROM fastq_quality_histogram('<p>'[, 'gzip'])                                        -- K5
+//   SELECT * FROM fastq_read_stats('<p>'[, 'gzip'])                                               -- K9
 //   SELECT COUNT(*) FROM <bam table> WHERE bam_region_filter('<r>', reference, start, end)          -- K6 (plain table; INDEXED_BAM plans chunks on the host)
 //   DROP TABLE t;
 #include <dirent.h>
@@ -399,7 +400,7 @@ Source resolve_from(Session& se, Parser& ps) {
   Source src;
   const std::string name = ps.ident();
   const std::string lname = lower(name);
-  if (ps.accept_sym("(")) {  // table function: <fmt>_scan / <fmt>_indexed_scan / fastq_quality_histogram
+  if (ps.accept_sym("(")) {  // table function: <fmt>_scan / <fmt>_indexed_scan / fastq_quality_histogram / fastq_read_stats
     const std::string path = ps.str();
     std::string arg2;
     if (ps.accept_sym(",")) arg2 = ps.str();
@@ -555,7 +556,7 @@ void exec_select(Session& se, Parser& ps) {
     proj.push_back(item);
   } while (ps.accept_sym(","));
   ps.expect_kw("from");
-  const bool hist = ps.is_kw("fastq_quality_histogram");
+  const bool hist = ps.is_kw("fastq_quality_histogram"), read_stats = ps.is_kw("fastq_read_stats");
   Source src = resolve_from(se, ps);
   Predicate pr;
   if (ps.accept_kw("where")) pr = parse_where(ps, src.format);
@@ -591,6 +592,34 @@ void exec_select(Session& se, Parser& ps) {
       for (int b = 0; b < 256; ++b)
         if (total[(size_t)p * 256 + b]) rows.push_back({std::to_string(p + 1), std::to_string(b - 33), std::to_string(total[(size_t)p * 256 + b])});
     print_table({"position", "quality_score", "count(*)"}, rows, se.quiet);
+    return;
+  }
+
+  if (read_stats) {  // K9: the per-read tables; every word of the state adds, so the files' states do
+    exon_hip_ctx* ctx = se.gpu();
+    const int lmax = 65536;
+    int64_t at[5];
+    ck(nullptr, exon_hip_read_stats_layout(lmax, at));
+    std::vector<int64_t> total((size_t)at[4], 0);
+    for (const auto& f : src.files) {
+      ScanGuard g; open_scan(src, f, nullptr, "", &g, true);
+      StreamGuard sg;
+      exon_hip_plan_desc d; memset(&d, 0, sizeof d);
+      d.kind = EXON_HIP_PLAN_READ_STATS_HIST; d.lmax = lmax; d.columns[0] = 2; d.columns[1] = 3;
+      ck(ctx, exon_hip_plan_create(ctx, &d, &sg.p));
+      ck(ctx, exon_hip_stream_open(sg.p, 0, &sg.s));
+      ck(ctx, exon_hip_stream_consume_scan(sg.s, g.s, nullptr));
+      std::vector<int64_t> h((size_t)at[4]);
+      ck(ctx, exon_hip_stream_finish(sg.s, h.data(), nullptr));
+      for (size_t i = 0; i < h.size(); ++i) total[i] += h[i];
+    }
+    static const char* const stat_names[4] = {"total", "length", "gc_percent", "mean_quality"};
+    static const char* const total_names[4] = {"reads", "bases", "gc", "quality_sum"};
+    std::vector<std::vector<std::string>> rows;
+    for (int st = 0; st < 4; ++st)
+      for (int64_t w = at[st]; w < at[st + 1]; ++w)
+        if (st == 0 || total[(size_t)w]) rows.push_back({stat_names[st], st == 0 ? std::string(total_names[w]) : std::to_string(w - at[st]), std::to_string(total[(size_t)w])});
+    print_table({"stat", "bin", "count"}, rows, se.quiet);
     return;
   }
 
@@ -933,6 +962,7 @@ int main(int argc, char** argv) {
              "  tables:    CREATE EXTERNAL TABLE t STORED AS FASTA|FASTQ|VCF|BAM|GFF|GTF|BED|INDEXED_VCF|INDEXED_BAM|INDEXED_GFF [OPTIONS (compression gzip, n_fields 6)] LOCATION '<path>'\n"
              "  functions: fasta_scan fastq_scan vcf_scan bam_scan gff_scan gtf_scan bed_scan ('<path>'[, 'gzip']); vcf_indexed_scan bam_indexed_scan gff_indexed_scan ('<path>', '<region>');\n"
              "             fastq_quality_histogram('<path>')\n"
+             "             fastq_read_stats('<path>')\n"
              "  queries:   SELECT COUNT(*) FROM <src> [WHERE chrom = 'c' AND pos >= a AND pos <= b | vcf_region_filter('r', chrom) | bam_region_filter('r', reference, start, end)\n"
              "             | gff_region_filter('r', seqname[, start])]\n"
              "             SELECT reference, COUNT(*) FROM <bam> WHERE flag & M = V AND CAST(mapping_quality AS INT) >= q GROUP BY reference\n"

@@ -83,6 +83,15 @@ struct K5Chunks {
 hipError_t launch_qual_pos_hist_chunks(hipStream_t s, const LaunchCfg& cfg, const Workspace& ws, const K5Chunks& ch, int lmax,
                                        int64_t* d_hist);
 
+// K9: per-read length / GC percent / mean quality histograms + four totals over two sets of line views (an Arrow Utf8 column
+// passes (offsets, offsets + 1)); state layout in include/exon_hip.h.  Length bins below K9_LEN_LDS are counted in LDS, the
+// others by global atomics.  1 <= lmax <= 65536.  cfg.overwrite: state := this launch.  ws.status must be allocated.
+constexpr int K9_LEN_LDS = 8192;
+constexpr int64_t read_stats_words(int lmax) { return 4 + ((int64_t)lmax + 1) + 102 + 257; }
+hipError_t launch_read_stats_hist(hipStream_t s, const LaunchCfg& cfg, const Workspace& ws, const uint8_t* sbytes, const int32_t* ss,
+                                  const int32_t* se, const uint8_t* qbytes, const int32_t* qs, const int32_t* qe, int64_t n_reads, int lmax,
+                                  int64_t* d_state);
+
 // pushed-down region filter as a row mask: out_valid = in_valid AND (row hits the region); *n_pass += rows kept.
 // point form (VCF): id_col = chrom id, start = pos; range form (BAM): id_col = reference id, [start, end].
 hipError_t launch_region_mask(hipStream_t s, bool range_form, const int32_t* id_col, const uint8_t* id_valid, const int64_t* start,

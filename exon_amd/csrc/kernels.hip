@@ -2867,6 +2867,188 @@ hipError_t launch_qual_pos_hist_chunks(hipStream_t s, const LaunchCfg& cfg, cons
 }
 
 // ------------------------------------------------------------------------------------------------
+// K9 read_stats_hist
+//   the three per-read QC tables of a FASTQ file in one pass over both lines: read length, GC percent
+//   (gc_content(sequence), exon-core/src/udfs/sequence/gc_content.rs:52-71, as the exact integer floor(100 gc / len))
+//   and mean quality (floor(sum of the raw bytes / len); Phred = bin - 33), plus four totals.  Integers only.
+//   State: [n_reads, sum len(s), sum gc, sum q bytes] [length: lmax + 1] [gc_percent: 102] [mean_quality: 257]
+//   (include/exon_hip.h).  Every line is measured by its OWN length.
+//
+//   A quarter-row of the wave -- 16 lanes, one DPP row -- owns a read; lane l loads the (unaligned) 16 bytes l of each line,
+//   so one step covers 256 bytes of both lines and K9_J reads are in flight per group.  NO load reaches outside a line: a
+//   partial last chunk is fetched as the 16 bytes that END at the line's end and its leading bytes (the previous lane's) are
+//   masked off -- sums and counts do not care where in the chunk a byte sits --, a line shorter than 16 bytes is read a byte
+//   per lane, and a lane with nothing to load reads the 16 bytes of the workspace's pad.  So neither the slab's nor an Arrow
+//   buffer's slack is relied on.
+//   Per dword: quality bytes are summed by v_sad_u8 against 0; G / C are counted by ONE exact SWAR zero-byte test --
+//   'C' = 0x43 and 'G' = 0x47 differ in bit 2 only, so (x & 0xFB) ^ 0x43 is zero for exactly these two bytes; the test adds
+//   0x7F to the low seven bits of every byte (no carry leaves a byte) and ORs the byte's own high bit in, so neither a byte
+//   >= 0x80 nor a neighbour can fake a hit.  The group's lanes are summed by four DPP row rotations.
+//   One lane then issues three ds_add_u32 per read into the workgroup's table (K5's head comment: equal addresses inside a
+//   32-lane half serialise -- here 2 leaders per half, and a file's reads do pile into few bins; at one LDS instruction per
+//   ~200 bytes that is far from what limits the kernel).  Length bins beyond K9_LEN_LDS go to a global atomic.  The totals
+//   stay in registers and are added once per wave; the table reaches the state by one global atomic per nonzero word.
+// ------------------------------------------------------------------------------------------------
+constexpr int K9_THREADS = 1024, K9_W = 16, K9_B = 16, K9_J = 4;
+constexpr int K9_GROUPS = K9_THREADS / K9_W;  // reads a workgroup has in hand per j
+constexpr int K9_STEP = K9_W * K9_B;          // bytes of a line one step covers
+struct K9Args {
+  const uint8_t* sbytes;
+  const uint8_t* qbytes;
+  const int32_t *ss, *se, *qs, *qe;  // start / end byte of every sequence and quality line
+  int64_t n;
+  int lmax, nlen;                    // nlen = length bins kept in LDS = min(lmax + 1, K9_LEN_LDS)
+  unsigned long long* state;
+  int* status;
+  const uint8_t* pad;                // 16 readable bytes
+};
+
+// bytes [q, q + 16) of the line [o0, o0 + len), bytes outside the line zeroed; lines shorter than a chunk give zeros
+__device__ __forceinline__ uint4 k9_fetch(const uint8_t* __restrict__ bytes, int64_t o0, int len, int q, const uint8_t* pad) {
+  const int rem = len - q;
+  const bool active = rem > 0 && len >= K9_B, tail = rem < K9_B;
+  const uint8_t* p = active ? bytes + o0 + (tail ? len - K9_B : q) : pad;
+  uint4 v;
+  __builtin_memcpy(&v, p, 16);  // unaligned 16-byte load
+  const int z = active ? (tail ? K9_B - rem : 0) : K9_B;  // the chunk's first z bytes are not this lane's
+  auto keep = [z](int k) {
+    const int s = z - 4 * k;
+    return s <= 0 ? ~0u : s >= 4 ? 0u : ~0u << (8 * s);
+  };
+  v.x &= keep(0);
+  v.y &= keep(1);
+  v.z &= keep(2);
+  v.w &= keep(3);
+  return v;
+}
+// number of bytes of x equal to 'C' or 'G' + acc
+__device__ __forceinline__ unsigned k9_gc(unsigned x, unsigned acc) {
+  const unsigned y = (x & 0xFBFBFBFBu) ^ 0x43434343u;          // a zero byte <=> 'C' or 'G'
+  const unsigned t = ((y & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | y;    // bit 7 of a byte is clear <=> the byte of y is zero
+  return __builtin_popcount(~t & 0x80808080u) + acc;
+}
+__device__ __forceinline__ unsigned k9_gc4(uint4 v, unsigned acc) { return k9_gc(v.w, k9_gc(v.z, k9_gc(v.y, k9_gc(v.x, acc)))); }
+__device__ __forceinline__ unsigned k9_sum4(uint4 v, unsigned acc) {
+  return __builtin_amdgcn_sad_u8(v.w, 0u, __builtin_amdgcn_sad_u8(v.z, 0u, __builtin_amdgcn_sad_u8(v.y, 0u, __builtin_amdgcn_sad_u8(v.x, 0u, acc))));
+}
+// sum over the 16 lanes of a DPP row, in every lane of it (all lanes of the wave must be active)
+__device__ __forceinline__ unsigned k9_row_sum(unsigned v) {
+  v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x128, 0xF, 0xF, false);  // row_ror:8
+  v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x124, 0xF, 0xF, false);  // row_ror:4
+  v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x122, 0xF, 0xF, false);  // row_ror:2
+  v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x121, 0xF, 0xF, false);  // row_ror:1
+  return v;
+}
+
+__global__ __launch_bounds__(K9_THREADS) void k9_read_stats_main(const K9Args a) {
+  __shared__ unsigned h[K9_LEN_LDS + 102 + 257];  // [length: nlen] [gc_percent: 102] [mean_quality: 257]
+  const int nlen = a.nlen, ntab = nlen + 102 + 257;
+  for (int i = threadIdx.x; i < ntab; i += K9_THREADS) h[i] = 0;
+  __syncthreads();
+  unsigned* const hg = h + nlen;
+  unsigned* const hq = hg + 102;
+  constexpr int J = K9_J;
+  const int gl = threadIdx.x & (K9_W - 1), q0 = gl * K9_B;
+  const int64_t G = (int64_t)gridDim.x * K9_GROUPS, gid = (int64_t)blockIdx.x * K9_GROUPS + (threadIdx.x / K9_W);
+  unsigned long long t_reads = 0, t_len = 0, t_gc = 0, t_q = 0;  // the group leader's share of the totals
+  bool bad = false;
+  // the trip count is the same for every lane of the grid: the DPP sums below see whole waves
+  for (int64_t r0 = 0; r0 < a.n; r0 += G * J) {
+    int so[J], qo[J], sl[J], ql[J];  // the views are int32 byte offsets
+    bool live[J];
+    uint4 xs[J], xq[J];
+#pragma unroll
+    for (int j = 0; j < J; ++j) {  // the views: unconditional loads (index clamped)
+      const int64_t rr = r0 + (int64_t)j * G + gid, rc = rr < a.n ? rr : a.n - 1;
+      const int32_t s0 = a.ss[rc], s1 = a.se[rc], b0 = a.qs[rc], b1 = a.qe[rc];
+      so[j] = s0;
+      qo[j] = b0;
+      sl[j] = max(s1 - s0, 0);
+      ql[j] = max(b1 - b0, 0);
+      live[j] = rr < a.n;
+      if (live[j] && (sl[j] > a.lmax || ql[j] > 65536)) {  // refused: status, and the read adds nothing anywhere
+        bad = true;
+        live[j] = false;
+      }
+      if (!live[j]) sl[j] = ql[j] = 0;
+    }
+#pragma unroll
+    for (int j = 0; j < J; ++j) {  // all data loads of the iteration are issued before any use
+      xs[j] = k9_fetch(a.sbytes, so[j], sl[j], q0, a.pad);
+      xq[j] = k9_fetch(a.qbytes, qo[j], ql[j], q0, a.pad);
+    }
+#pragma unroll
+    for (int j = 0; j < J; ++j) {
+      unsigned gc = k9_gc4(xs[j], 0), qsum = k9_sum4(xq[j], 0);
+      for (int q = q0 + K9_STEP; q < sl[j]; q += K9_STEP) gc = k9_gc4(k9_fetch(a.sbytes, so[j], sl[j], q, a.pad), gc);  // lines longer than a step
+      for (int q = q0 + K9_STEP; q < ql[j]; q += K9_STEP) qsum = k9_sum4(k9_fetch(a.qbytes, qo[j], ql[j], q, a.pad), qsum);
+      if (sl[j] < K9_B && gl < sl[j]) gc = k9_gc(a.sbytes[so[j] + gl], gc);  // lines shorter than a chunk: a byte per lane
+      if (ql[j] < K9_B && gl < ql[j]) qsum += a.qbytes[qo[j] + gl];
+      gc = k9_row_sum(gc);
+      qsum = k9_row_sum(qsum);
+      if (gl == 0 && live[j]) {
+        const unsigned ls = (unsigned)sl[j], lq = (unsigned)ql[j];
+        if ((int)ls < nlen) atomicAdd(&h[ls], 1u);
+        else atomicAdd(&a.state[4 + ls], 1ull);
+        atomicAdd(&hg[ls ? 100u * gc / ls : 101u], 1u);
+        atomicAdd(&hq[lq ? qsum / lq : 256u], 1u);
+        t_reads += 1;
+        t_len += ls;
+        t_gc += gc;
+        t_q += qsum;
+      }
+    }
+  }
+  // totals: once per wave
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) {
+    t_reads += __shfl_down(t_reads, d);
+    t_len += __shfl_down(t_len, d);
+    t_gc += __shfl_down(t_gc, d);
+    t_q += __shfl_down(t_q, d);
+  }
+  const bool any_bad = __any(bad);
+  if ((threadIdx.x & 63) == 0) {
+    if (t_reads) {
+      atomicAdd(&a.state[0], t_reads);
+      atomicAdd(&a.state[1], t_len);
+      atomicAdd(&a.state[2], t_gc);
+      atomicAdd(&a.state[3], t_q);
+    }
+    if (any_bad) atomicOr(a.status, 8);
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i < ntab; i += K9_THREADS) {
+    const unsigned v = h[i];
+    if (v) atomicAdd(&a.state[i < nlen ? 4 + i : 4 + a.lmax + 1 + (i - nlen)], (unsigned long long)v);
+  }
+}
+
+hipError_t launch_read_stats_hist(hipStream_t s, const LaunchCfg& cfg, const Workspace& ws, const uint8_t* sbytes, const int32_t* ss,
+                                  const int32_t* se, const uint8_t* qbytes, const int32_t* qs, const int32_t* qe, int64_t n_reads, int lmax,
+                                  int64_t* d_state) {
+  if (lmax < 1 || lmax > 65536 || !ws.status) return hipErrorInvalidValue;
+  hipError_t e;
+  if (cfg.overwrite && (e = hipMemsetAsync(d_state, 0, (size_t)read_stats_words(lmax) * 8, s)) != hipSuccess) return e;  // the kernel adds
+  // a workgroup's u32 bins count at most the reads of one launch
+  for (int64_t r = 0; r < n_reads; r += (int64_t)1 << 31) {
+    K9Args a;
+    a.sbytes = sbytes, a.qbytes = qbytes;
+    a.ss = ss + r, a.se = se + r, a.qs = qs + r, a.qe = qe + r;
+    a.n = std::min<int64_t>(n_reads - r, (int64_t)1 << 31);
+    a.lmax = lmax;
+    a.nlen = std::min(lmax + 1, K9_LEN_LDS);
+    a.state = reinterpret_cast<unsigned long long*>(d_state);
+    a.status = ws.status;
+    a.pad = reinterpret_cast<const uint8_t*>(ws.status + 8);  // the workspace's 64 bytes of 0xFF
+    const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(cfg.compute_units, (a.n + K9_GROUPS - 1) / K9_GROUPS));
+    hipLaunchKernelGGL(k9_read_stats_main, dim3(grid), dim3(K9_THREADS), 0, s, a);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+  }
+  return hipSuccess;
+}
+
+// ------------------------------------------------------------------------------------------------
 // ------------------------------------------------------------------------------------------------
 // Synthetic inputs (DESIGN.md "Synthetic inputs"): counter-based, bit-identical to oracle/exon_oracle.c
 // ------------------------------------------------------------------------------------------------

@@ -49,6 +49,7 @@ struct ColStage {
   uint8_t* d_valid = nullptr;
   int32_t* d_offsets = nullptr;
   bool any_null_bitmap = false;  // at least one appended batch carried a validity bitmap
+  int64_t bytes = 0;             // utf8 payload bytes appended (each Utf8 column of a plan has its own: K9's two differ)
 };
 
 // A small pushed batch (the reference's 8192 rows = ~100 KB) is not copied when it arrives: it is HELD -- the stream owns it,
@@ -69,7 +70,6 @@ struct HeldBatch {
 struct Slot {
   std::vector<ColStage> cols;
   int64_t rows = 0;
-  int64_t bytes = 0;  // utf8 payload bytes appended
   hipEvent_t done = nullptr;
   bool in_flight = false;
   std::vector<HeldBatch> held;
@@ -364,7 +364,6 @@ static int alloc_slot(exon_hip_stream* st, Slot& s) {
   }
   if (!s.done && hipEventCreateWithFlags(&s.done, hipEventDisableTiming) != hipSuccess) return EXON_HIP_EDEVICE;
   s.rows = 0;
-  s.bytes = 0;
   s.in_flight = false;
   return EXON_HIP_OK;
 }
@@ -397,6 +396,8 @@ static int run_plan(const exon_hip_plan* p, void* stream, const exon_hip_column*
                                          flags);
     case EXON_HIP_PLAN_QUAL_POS_HIST:
       return exon_op_qual_pos_hist(ctx, stream, &cols[0], n, d.lmax, counts, flags);
+    case EXON_HIP_PLAN_READ_STATS_HIST:
+      return exon_op_read_stats_hist(ctx, stream, &cols[0], &cols[1], n, d.lmax, counts, flags);
     case EXON_HIP_PLAN_OVERLAP_COUNT:
     case EXON_HIP_PLAN_WITHIN_COUNT:
       return exon_op_overlap_count(ctx, stream, &cols[0], &cols[1], &cols[2], n, d.region_chrom_id, d.region_start,
@@ -474,7 +475,7 @@ static int flush_slot(exon_hip_stream* st) {
   exon_hip_column cols[4];
   for (int c = 0; c < p->n_cols; ++c) {
     ColStage& cs = s.cols[(size_t)c];
-    const size_t vbytes = p->cols[c].utf8 ? (size_t)s.bytes : (size_t)s.rows * (size_t)p->cols[c].elem;
+    const size_t vbytes = p->cols[c].utf8 ? (size_t)cs.bytes : (size_t)s.rows * (size_t)p->cols[c].elem;
     bool null_key_rewritten = false;
     if (cs.any_null_bitmap && c == 2 && (p->d.kind == EXON_HIP_PLAN_CMP_AVG_BY_GROUP || p->d.kind == EXON_HIP_PLAN_CMP_MINMAX_BY_GROUP) && st->null_group) {
       // a NULL group key becomes the scan's id of the NULL group (in the staging copy, before it goes to HBM): no bitmap
@@ -514,8 +515,8 @@ static int flush_slot(exon_hip_stream* st) {
   }
   st->t_wait += now_s() - t_f1;
   n.rows = 0;
-  n.bytes = 0;
   for (auto& cs : n.cols) {
+    cs.bytes = 0;
     if (cs.any_null_bitmap) memset(cs.h_valid, 0, (size_t)(st->cap_rows + 7) / 8 + 64);
     cs.any_null_bitmap = false;
     if (cs.h_offsets) cs.h_offsets[0] = 0;
@@ -629,6 +630,16 @@ int exon_hip_plan_create(exon_hip_ctx* ctx, const exon_hip_plan_desc* desc, exon
       }
       p->n_i64 = (int64_t)desc->lmax * 256;
       break;
+    case EXON_HIP_PLAN_READ_STATS_HIST:  // sequence, quality_scores
+      p->n_cols = 2;
+      p->cols[0].elem = p->cols[1].elem = 1;
+      p->cols[0].utf8 = p->cols[1].utf8 = true;
+      if (desc->lmax < 1 || desc->lmax > 65536) {
+        delete p;
+        return fail(ctx, EXON_HIP_EINVAL, "lmax %d out of range", desc->lmax);
+      }
+      p->n_i64 = 4 + ((int64_t)desc->lmax + 1) + 102 + 257;  // exon_hip_read_stats_layout
+      break;
     default:
       delete p;
       return fail(ctx, EXON_HIP_EINVAL, "unknown plan kind %d", desc->kind);
@@ -713,18 +724,23 @@ int exon_hip_stream_push(exon_hip_stream* st, struct ArrowArray* batch) {
   int rc = EXON_HIP_OK;
   const struct ArrowArray* ch[4];
   int64_t off[4];
-  int64_t need_bytes = 0;
+  int64_t need_bytes = 0, col_bytes[4] = {0, 0, 0, 0};  // Utf8 payload of this batch: per column, and the largest
   for (int c = 0; c < p->n_cols && !rc; ++c) {
     rc = column_child(st, batch, c, &ch[c], &off[c]);
     if (!rc && p->cols[c].utf8 && rows > 0) {
       const int32_t* o = (const int32_t*)ch[c]->buffers[1];
-      need_bytes = std::max<int64_t>(need_bytes, (int64_t)o[off[c] + rows] - o[off[c]]);
+      col_bytes[c] = (int64_t)o[off[c] + rows] - o[off[c]];
+      need_bytes = std::max<int64_t>(need_bytes, col_bytes[c]);
     }
   }
   if (!rc && rows > 0) {
     rc = ensure_capacity(st, rows, need_bytes);
-    if (!rc && (st->slots[st->cur].rows + rows > st->cap_rows || st->slots[st->cur].bytes + need_bytes > st->cap_bytes))
-      rc = flush_slot(st);
+    if (!rc) {
+      const Slot& cur = st->slots[st->cur];
+      bool full = cur.rows + rows > st->cap_rows;
+      for (int c = 0; c < p->n_cols; ++c) full = full || cur.cols[(size_t)c].bytes + col_bytes[c] > st->cap_bytes;  // every Utf8 column against its own count
+      if (full) rc = flush_slot(st);
+    }
     bool fixed = true;
     for (int c = 0; c < p->n_cols; ++c) fixed = fixed && !p->cols[c].utf8;
     static const bool hold_on = [] {
@@ -771,16 +787,16 @@ int exon_hip_stream_push(exon_hip_stream* st, struct ArrowArray* batch) {
           const int32_t* o = (const int32_t*)ch[c]->buffers[1] + off[c];
           const uint8_t* data = (const uint8_t*)ch[c]->buffers[2];
           const int32_t base = o[0], len = o[rows] - base;
-          if (len) CopyPool::get().copy(cs.h_values + s.bytes, data + base, (size_t)len);
-          const int32_t shift = (int32_t)s.bytes - base;
+          if (len) CopyPool::get().copy(cs.h_values + cs.bytes, data + base, (size_t)len);
+          const int32_t shift = (int32_t)cs.bytes - base;
           for (int64_t i = 1; i <= rows; ++i) cs.h_offsets[s.rows + i] = o[i] + shift;
+          cs.bytes += len;
         } else {
           const int e = p->cols[c].elem;
           CopyPool::get().copy(cs.h_values + (size_t)s.rows * e, (const uint8_t*)ch[c]->buffers[1] + (size_t)off[c] * e, (size_t)rows * e);
         }
       }
       s.rows += rows;
-      s.bytes += need_bytes;
       st->rows_pushed += rows;
       st->t_copy += now_s() - t_c0;
     }
@@ -837,17 +853,27 @@ int exon_hip_stream_set_null_group(exon_hip_stream* st, std::function<int32_t()>
   st->null_group = std::move(id_of_null);
   return rc;
 }
-// K5 over views into text resident in HBM (FASTQ slabs): scan column 2 = sequence lines, 3 = quality lines
+// K5 / K9 over views into text resident in HBM (FASTQ slabs): scan column 2 = sequence lines, 3 = quality lines
 int exon_hip_stream_launch_views(exon_hip_stream* st, const uint8_t* d_text, const exon_hip_fastq_views& v) {
   exon_hip_plan* p = st->plan;
   if (st->closed) return fail(st->ctx, EXON_HIP_ESTATE, "push after finish/close");
-  if (p->d.kind != EXON_HIP_PLAN_QUAL_POS_HIST) return fail(st->ctx, EXON_HIP_EUNSUPPORTED, "GPU-side FASTQ splitting serves the per-position histogram plan only");
+  const bool k9 = p->d.kind == EXON_HIP_PLAN_READ_STATS_HIST;
+  if (p->d.kind != EXON_HIP_PLAN_QUAL_POS_HIST && !k9)
+    return fail(st->ctx, EXON_HIP_EUNSUPPORTED, "GPU-side FASTQ splitting serves the per-position histogram and the per-read statistics plans only");
   const int idx = p->d.columns[0];
+  if (k9 && (idx != 2 || p->d.columns[1] != 3))
+    return fail(st->ctx, EXON_HIP_EINVAL, "the per-read statistics plan needs scan columns (%d, %d); over a FASTQ scan its operands are (2, 3) = (sequence, quality_scores)", idx, p->d.columns[1]);
   if (idx != 2 && idx != 3) return fail(st->ctx, EXON_HIP_EINVAL, "plan needs scan column %d; FASTQ views exist for 2 (sequence) and 3 (quality_scores)", idx);
   int rc = flush_slot(st);
   if (!rc) rc = settle_reset(st);
   if (rc) return rc;
   (void)d_text;  // the views index v.text_base (the aligned address at or below the slab)
+  if (k9) {
+    rc = exon_hip_read_stats_hist_views(st->ctx, st->stream, v.text_base, v.seq_start, v.seq_end, v.qual_start, v.qual_end, v.n_reads, p->d.lmax,
+                                        reinterpret_cast<int64_t*>(st->d_state));
+    if (!rc) st->rows_pushed += v.n_reads;
+    return rc;
+  }
   rc = exon_hip_qual_pos_hist_views(st->ctx, st->stream, v.text_base, idx == 2 ? v.seq_start : v.qual_start,
                                     idx == 2 ? v.seq_end : v.qual_end, v.n_reads, p->d.lmax,
                                     reinterpret_cast<int64_t*>(st->d_state));
@@ -1703,8 +1729,8 @@ int exon_hip_stream_reset(exon_hip_stream* st) {
   release_held(s);  // (batches held for the old query: dropped with it, released uncopied)
   if (!s.cols.empty()) {
     s.rows = 0;
-    s.bytes = 0;
     for (auto& cs : s.cols) {
+      cs.bytes = 0;
       if (cs.any_null_bitmap) memset(cs.h_valid, 0, (size_t)(st->cap_rows + 7) / 8 + 64);
       cs.any_null_bitmap = false;
       if (cs.h_offsets) cs.h_offsets[0] = 0;
@@ -1881,6 +1907,21 @@ int exon_hip_stream_finish_arrow(exon_hip_stream* st, struct ArrowArray* out, st
       make_struct(out, (int64_t)pos.size(), {prim(pos), prim(score), prim(cnt)});
       make_schema(out_schema, "+s", "", false,
                   {field("i", "position", false), field("i", "quality_score", false), field("l", "count(*)[count]", false)});
+      break;
+    }
+    case EXON_HIP_PLAN_READ_STATS_HIST: {  // stat: 0 totals (always its four rows), 1 length, 2 gc_percent, 3 mean_quality (nonzero bins)
+      const int64_t at[5] = {0, 4, 4 + (int64_t)d.lmax + 1, 4 + (int64_t)d.lmax + 1 + 102, p->n_i64};
+      std::vector<int32_t> stat, bin;
+      std::vector<int64_t> cnt;
+      for (int s = 0; s < 4; ++s)
+        for (int64_t w = at[s]; w < at[s + 1]; ++w)
+          if (s == 0 || counts[(size_t)w]) {
+            stat.push_back(s);
+            bin.push_back((int32_t)(w - at[s]));
+            cnt.push_back(counts[(size_t)w]);
+          }
+      make_struct(out, (int64_t)stat.size(), {prim(stat), prim(bin), prim(cnt)});
+      make_schema(out_schema, "+s", "", false, {field("i", "stat", false), field("i", "bin", false), field("l", "count", false)});
       break;
     }
     default:

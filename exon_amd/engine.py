@@ -217,6 +217,19 @@ class Context:
         self._check(self.lib.exon_hip_qual_pos_hist_views(self.h, stream, ptr(d_text), ptr(starts), ptr(ends), n_reads, lmax,
                                                           d_hist.ptr))
 
+    def read_stats_hist(self, seq_offsets, seq_data, qual_offsets, qual_data, n_reads, lmax, d_state, stream=None):
+        """K9 over two Utf8 columns (sequence, quality_scores): per-read length / GC percent / mean quality histograms and
+        four totals accumulated into `d_state` (read_stats_layout(lmax) int64 words)."""
+        c0, c1 = _col(seq_data, None, seq_offsets, n_reads), _col(qual_data, None, qual_offsets, n_reads)
+        self._check(self.lib.exon_hip_read_stats_hist(self.h, stream, C.byref(c0), C.byref(c1), n_reads, lmax,
+                                                      d_state.ptr if isinstance(d_state, DeviceBuffer) else d_state))
+
+    def read_stats_hist_views(self, d_text, seq_start, seq_end, qual_start, qual_end, n_reads, lmax, d_state, stream=None):
+        """K9 over [start[r], end[r]) views of both lines into `d_text` (device pointers / DeviceBuffers)."""
+        ptr = lambda x: x.ptr if isinstance(x, DeviceBuffer) else x  # noqa: E731
+        self._check(self.lib.exon_hip_read_stats_hist_views(self.h, stream, ptr(d_text), ptr(seq_start), ptr(seq_end), ptr(qual_start),
+                                                            ptr(qual_end), n_reads, lmax, ptr(d_state)))
+
     def bgzf_inflate(self, data, verify_crc=True, stream=None):
         """Test / tool helper: BGZF bytes -> inflated bytes through the GPU (exon_hip_bgzf_inflate).  Returns
         (inflated uint8 array, seconds spent in the device call)."""
@@ -311,6 +324,23 @@ class Context:
     def plan_qual_pos_hist(self, lmax, columns=(0,)):
         d = L.PlanDesc(kind=L.PLAN_QUAL_POS_HIST, lmax=lmax)
         return Plan(self, d, columns)
+
+    def plan_read_stats_hist(self, lmax, columns=(0, 1)):
+        """Per-read length / GC percent / mean quality histograms over (sequence, quality_scores): columns (2, 3) of a FASTQ
+        scan.  State: read_stats_layout(lmax)[4] int64 words, all of which add."""
+        d = L.PlanDesc(kind=L.PLAN_READ_STATS_HIST, lmax=lmax)
+        return Plan(self, d, columns)
+
+
+def read_stats_layout(lmax):
+    """exon_hip_read_stats_layout (host-only): word offsets of the totals / length / gc_percent / mean_quality sections of a
+    per-read statistics state, and its size in words."""
+    lib = L.load()
+    out = (C.c_int64 * 5)()
+    rc = lib.exon_hip_read_stats_layout(lmax, out)
+    if rc:
+        raise ExonHipError(rc, lib.exon_hip_last_error(None).decode(errors="replace"))
+    return tuple(out)
 
 
 def minmax_decode(words, is_min, y_type="f32"):

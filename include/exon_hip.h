@@ -28,6 +28,8 @@
  *        MinAccumulator / MaxAccumulator (datafusion-functions-aggregate min_max.rs, not vendored) behind the same FilterExec
  *   exon_hip_qual_pos_hist                QualityScoreStringToList::invoke
  *        (exon-core/src/udfs/sequence/quality_score_string_to_list.rs:56-117) + unnest + GROUP BY
+ *   exon_hip_read_stats_hist              GCContent::invoke (exon-core/src/udfs/sequence/gc_content.rs:52-71), the read length
+ *        and the per-row mean of quality_scores_to_list, each binned (integers) and counted: GROUP BY bin, COUNT(*)
  *   exon_hip_regroup_files_by_size        regroup_files_by_size
  *        (exon-core/src/datasources/exon_file_scan_config.rs:79-110) -- the multi-GPU shard rule
  */
@@ -257,6 +259,26 @@ int exon_hip_qual_pos_hist_chunks(exon_hip_ctx* ctx, void* stream, const exon_hi
 int exon_hip_qual_pos_hist_views(exon_hip_ctx* ctx, void* stream, const uint8_t* d_bytes, const int32_t* d_starts,
                                  const int32_t* d_ends, int64_t n_reads, int32_t lmax, int64_t* d_hist /*[lmax*256]*/);
 
+/* K9.  Per-READ statistics of FASTQ reads (s = sequence bytes, q = quality bytes; each line measured by its OWN length), integers
+ *      only.  d_state holds 4 + (lmax + 1) + 102 + 257 int64 words (exon_hip_read_stats_layout), and every word adds:
+ *        totals       [4]         n_reads, sum len(s), sum gc(s), sum over all q bytes of the raw byte
+ *        length       [lmax + 1]  bin L = reads with len(s) == L
+ *        gc_percent   [102]       bin floor(100 gc(s) / len(s)) (0 .. 100); bin 101 = reads with an empty sequence (gc_content's 0/0).
+ *                                 gc(s) = bytes equal to 'G' or 'C', upper case only (exon-core/src/udfs/sequence/gc_content.rs:52-71).
+ *                                 The bin is the exact integer floor, not floor(gc_content(s) * 100) in Float32
+ *        mean_quality [257]       bin floor(sum of q's bytes / len(q)) on the RAW byte (Phred = bin - 33); bin 256 = empty quality line
+ *      1 <= lmax <= 65536.  A read with len(s) > lmax, or len(q) > 65536, is an error (status word, reported by
+ *      exon_hip_stream_finish / sync, as K5's position >= lmax); such a read adds nothing.  Accumulates. */
+int exon_hip_read_stats_hist(exon_hip_ctx* ctx, void* stream, const exon_hip_column* sequence /*utf8*/,
+                             const exon_hip_column* quality /*utf8*/, int64_t n_reads, int32_t lmax, int64_t* d_state);
+/* K9 over independent views into `d_bytes` (raw FASTQ text resident in HBM, exon_hip_fastq_parser_parse): read r has the sequence
+ * bytes [seq_s[r], seq_e[r]) and the quality bytes [qual_s[r], qual_e[r]).  No byte outside a line is loaded. */
+int exon_hip_read_stats_hist_views(exon_hip_ctx* ctx, void* stream, const uint8_t* d_bytes, const int32_t* seq_s, const int32_t* seq_e,
+                                   const int32_t* qual_s, const int32_t* qual_e, int64_t n_reads, int32_t lmax, int64_t* d_state);
+/* Host-only: out[0..3] = word offset of K9's totals / length / gc_percent / mean_quality sections, out[4] = the state's words.
+ * EXON_HIP_EINVAL outside 1 <= lmax <= 65536.  Needs no device. */
+int exon_hip_read_stats_layout(int32_t lmax, int64_t* out /*[5]*/);
+
 /* ---- synthetic inputs generated in HBM (DESIGN.md "Synthetic inputs"; bit-identical to the
  *      oracle's generators, which the parity tests check) ------------------------------------- */
 int exon_hip_gen_c2(exon_hip_ctx* ctx, void* stream, uint64_t seed, int64_t n_total, int64_t lo, int64_t hi,
@@ -291,6 +313,8 @@ int exon_hip_regroup_files_by_size(const int64_t* sizes, int32_t n_files, int32_
  * the first file's header and refuses (EXON_HIP_ESTATE, the stream unchanged) a later file that types the argument otherwise;
  * exon_hip_stream_reset starts over.  Ranks that merge such states must have agreed on the type (the plan's, or the same files' headers). */
 #define EXON_HIP_PLAN_CMP_MINMAX_BY_GROUP 8
+/* K9: lmax, columns: sequence, quality_scores (both Utf8; (2, 3) of a FASTQ scan); state: exon_hip_read_stats_layout words, all add */
+#define EXON_HIP_PLAN_READ_STATS_HIST 9
 
 #define EXON_HIP_X_FLOAT32 0
 #define EXON_HIP_X_INT32 1
@@ -315,7 +339,7 @@ typedef struct exon_hip_plan_desc {
   /* K4: type of AVG's argument y, EXON_HIP_X_FLOAT32 / EXON_HIP_X_INT32 (DataFusion's avg casts either to Float64) */
   int32_t y_type;
   /* input column indexes into the batch's children, in operator argument order
-   * (K2: chrom_id,pos  K3: flag,mapq,ref_id  K4: x,y,group_id  K5: quality_scores  K6: ref_id,start,end) */
+   * (K2: chrom_id,pos  K3: flag,mapq,ref_id  K4: x,y,group_id  K5: quality_scores  K6: ref_id,start,end  K9: sequence,quality_scores) */
   int32_t columns[4];
 } exon_hip_plan_desc;
 

@@ -22,6 +22,7 @@ pub const EXON_HIP_PLAN_QUAL_POS_HIST: i32 = 5;
 pub const EXON_HIP_PLAN_OVERLAP_COUNT: i32 = 6;
 pub const EXON_HIP_PLAN_WITHIN_COUNT: i32 = 7;
 pub const EXON_HIP_PLAN_CMP_MINMAX_BY_GROUP: i32 = 8; // K4's fields; state = 4 * n_groups int64 words (counts, then min / max words)
+pub const EXON_HIP_PLAN_READ_STATS_HIST: i32 = 9; // lmax, columns (sequence, quality_scores); state = exon_hip_read_stats_layout words, all add
 pub const EXON_HIP_GT: i32 = 0;
 pub const EXON_HIP_GE: i32 = 1;
 pub const EXON_HIP_LT: i32 = 2;
@@ -123,6 +124,12 @@ extern "C" {
     pub fn exon_hip_cmp_minmax_by_group(ctx: *mut exon_hip_ctx, stream: *mut c_void, x: *const exon_hip_column, y: *const exon_hip_column, group_id: *const exon_hip_column, n: i64, threshold: f64, cmp_op: i32, n_groups: i32, d_state: *mut i64) -> c_int;
     /// host-only: words of K8's min (is_min != 0) or max plane -> 4-byte values + validity bytes (a word of 0 = no value)
     pub fn exon_hip_minmax_decode(words: *const i64, n: i64, is_min: i32, y_type: i32, out_values: *mut c_void, out_valid: *mut u8) -> c_int;
+    /// K9 (bare operator): per-read length / GC percent / mean quality histograms + four totals over two Utf8 columns; accumulates
+    pub fn exon_hip_read_stats_hist(ctx: *mut exon_hip_ctx, stream: *mut c_void, sequence: *const exon_hip_column, quality: *const exon_hip_column, n_reads: i64, lmax: i32, d_state: *mut i64) -> c_int;
+    /// K9 over views of both lines into text resident in HBM
+    pub fn exon_hip_read_stats_hist_views(ctx: *mut exon_hip_ctx, stream: *mut c_void, d_bytes: *const u8, seq_s: *const i32, seq_e: *const i32, qual_s: *const i32, qual_e: *const i32, n_reads: i64, lmax: i32, d_state: *mut i64) -> c_int;
+    /// host-only: word offsets of K9's totals / length / gc_percent / mean_quality sections and the state's size
+    pub fn exon_hip_read_stats_layout(lmax: i32, out: *mut i64) -> c_int;
     /// fold of `world` packed states by the plan's own layout (add; unsigned max for K8's extreme planes)
     pub fn exon_hip_plan_fold_states(plan: *const exon_hip_plan, stream: *mut c_void, d_gathered: *const c_void, world: i32, d_out: *mut c_void) -> c_int;
     pub fn exon_hip_stream_open(plan: *mut exon_hip_plan, partition: i32, out: *mut *mut exon_hip_stream) -> c_int;
