@@ -90,6 +90,13 @@ class FASTQViews(C.Structure):
                 ("text_base", C.c_void_p), ("head_start", C.c_void_p), ("head_end", C.c_void_p)]
 
 
+class FASTAViews(C.Structure):
+    _fields_ = [("n_records", C.c_int64), ("n_undecided", C.c_int64), ("consumed_bytes", C.c_int64), ("n_lines", C.c_int64),
+                ("seq_bytes", C.c_int64), ("text_base", C.c_void_p), ("text_bytes", C.c_int64), ("first_line_start", C.c_int64),
+                ("head_start", C.c_void_p), ("head_end", C.c_void_p), ("seq_offsets", C.c_void_p), ("line_end", C.c_void_p),
+                ("line_dst", C.c_void_p)]
+
+
 class VCFColumns(C.Structure):
     _fields_ = [("n_rows", C.c_int64), ("n_undecided", C.c_int64), ("chrom_id", C.c_void_p), ("pos", C.c_void_p),
                 ("pos_valid", C.c_void_p), ("qual", C.c_void_p), ("qual_valid", C.c_void_p), ("filter_id", C.c_void_p),
@@ -257,6 +264,9 @@ SIGNATURES = {
     "exon_hip_fastq_parser_create": (C.c_int, [_vp, _i64, C.POINTER(_vp)]),
     "exon_hip_fastq_parser_parse": (C.c_int, [_vp, _vp, _vp, _i64, _i32, C.POINTER(FASTQViews)]),
     "exon_hip_fastq_parser_destroy": (C.c_int, [_vp]),
+    "exon_hip_fasta_parser_create": (C.c_int, [_vp, _i64, C.POINTER(_vp)]),
+    "exon_hip_fasta_parser_parse": (C.c_int, [_vp, _vp, _vp, _i64, _i32, C.POINTER(FASTAViews)]),
+    "exon_hip_fasta_parser_destroy": (C.c_int, [_vp]),
     "exon_hip_bam_parser_create": (C.c_int, [_vp, _i32, _i64, C.POINTER(_vp)]),
     "exon_hip_bam_parser_parse": (C.c_int, [_vp, _vp, _vp, _i64, C.POINTER(BAMColumns)]),
     "exon_hip_bam_parser_destroy": (C.c_int, [_vp]),

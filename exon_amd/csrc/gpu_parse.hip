@@ -1191,6 +1191,192 @@ int exon_hip_fastq_parser_parse(exon_hip_fastq_parser* p, void* stream, const ui
 }  // extern "C"
 
 // ------------------------------------------------------------------------------------------------------------
+// FASTA.  THE RULES -- what the host reader returns (host/formats.h: FASTABatchReader + FASTAArrayBuilder; exon-fasta/src/
+// batch_reader.rs:72-99, array_builder.rs:114-132), byte for byte; text_columns.hip (exon_text_fasta) builds the columns by them:
+//   * Lines end at '\n'.  One '\r' in front of it is dropped -- on definition lines and on sequence lines alike.
+//   * A line whose first byte is '>' starts a record; the definition is the rest of that line.
+//   * id = the definition up to its first ' ' or '\t' (it may be empty); description = what follows the run of ' ' / '\t' behind
+//     the id, NULL when nothing follows.
+//   * sequence = every following line up to the next '>' line or the end of the input, concatenated as it stands: inner blanks
+//     are kept, empty lines add nothing, a record without sequence lines has "".  A '>' anywhere but at a line's start is a byte
+//     of that line like any other.
+//   * The host reader skips text in front of the first '>' line; the device never sees such text: exon_hip_scan_bind_ctx refuses
+//     an input whose first byte is not '>', and a slab that does not start with '>' is undecided here.
+// A record is a variable number of lines and one record may be most of a slab, so nothing here walks a record.  Over the line
+// index (LineIndex, as for FASTQ):
+//   k_fasta_classify   one thread per line: is_def[line] (first byte '>'), seq_len[line] (0 for a definition line, else the
+//                      line's length without its CR)
+//   two exclusive scans (list_kernels.h: block sums, one workgroup over them; the in-block prefixes are taken by the kernel
+//                      below): the rank of the definition lines is the record number, the prefix of seq_len every line's
+//                      destination in the compacted sequence bytes
+//   k_fasta_records    one thread per line again: line_dst[line] (written over seq_len, with the total behind the last line);
+//                      a definition line writes its record's head_start / head_end and the Arrow offset seq_offsets[record] =
+//                      its own scanned value; the closing offset comes from the last definition line (the record it starts is not
+//                      emitted) or, in the final slab, from the total
+// Slab rules: final_slab == 0 -- the last record is never known to be complete: n_records = definition lines - 1, consumed_bytes
+// ends directly in front of the last definition line; fewer than two definition lines consume nothing (scan.cpp hands the file
+// over when that slab cannot grow: GpuTextSource carries at most its gap, a quarter of a slab and at least 1 MiB, so a record
+// beyond roughly a quarter slab -- 20 MB at the default 80 MB -- is the host reader's: whole chromosomes stay a host format,
+// protein sets, transcriptomes, contigs and reads are the device's).  final_slab != 0 -- every record is complete, consumed_bytes
+// is the whole text.  Undecided: a first line without '>', or more lines than the index holds.
+// LINE CAPACITY: max_slab_bytes / 8 + 8 lines.  FASTA lines are 60 - 80 bytes wide and a one-line-per-record read set has a
+// definition of ten bytes or more next to every read, so real files stay below one line per 30 bytes; 8 bytes a line leaves a
+// factor of four for short records and costs 20 bytes of index per line = 2.5 bytes per slab byte (the newline position, is_def,
+// seq_len / line_dst, and head_start / head_end / seq_offsets sized for a record per line).  Denser text (runs of empty lines,
+// sequence wrapped below seven columns) is undecided and goes to the host reader.
+namespace {
+
+// scalars: [0] n_lines (in), [1] undecided (+=)
+__global__ __launch_bounds__(TPB) void k_fasta_classify(const uint8_t* __restrict__ text, const unsigned* __restrict__ nl, unsigned* __restrict__ scalars,
+                                                        unsigned cap_lines, unsigned skip, uint32_t* __restrict__ is_def, uint32_t* __restrict__ seq_len) {
+  const unsigned n_lines = scalars[0];
+  const unsigned line = blockIdx.x * TPB + threadIdx.x;
+  if (n_lines > cap_lines) {  // the index was truncated: nothing can be trusted
+    if (line == 0) atomicAdd(&scalars[1], 1u);
+    return;
+  }
+  if (line >= n_lines) return;
+  const unsigned begin = line ? nl[line - 1] + 1u : skip, end = nl[line];  // (begin <= end: text[begin] is the line's first byte or its '\n')
+  const bool def = text[begin] == '>';
+  unsigned len = end - begin;
+  if (len && text[end - 1] == '\r') --len;
+  is_def[line] = def ? 1u : 0u;
+  seq_len[line] = def ? 0u : len;
+  if (line == 0 && !def) atomicAdd(&scalars[1], 1u);
+}
+
+// tot: [0] definition lines, [1] sequence bytes of the slab (both from the scans), [2] (out) sequence bytes of the records emitted;
+// scalars[2] (out): consumed bytes.  seq_len becomes line_dst in place: a thread reads its own entry and then writes it.
+__global__ __launch_bounds__(LIST_TPB) void k_fasta_records(const uint8_t* __restrict__ text, const unsigned* __restrict__ nl, unsigned* __restrict__ scalars,
+                                                            unsigned cap_lines, unsigned skip, int final_slab, const uint32_t* __restrict__ is_def,
+                                                            uint32_t* __restrict__ seq_len, const unsigned* __restrict__ def_sums,
+                                                            const unsigned* __restrict__ len_sums, unsigned* __restrict__ tot, int32_t* __restrict__ head_s,
+                                                            int32_t* __restrict__ head_e, int32_t* __restrict__ seq_off) {
+  const unsigned n_lines = scalars[0];
+  if (n_lines > cap_lines) return;  // (uniform: k_fasta_classify has counted the slab undecided)
+  const unsigned line = blockIdx.x * LIST_TPB + threadIdx.x;
+  const bool in = line < n_lines;
+  const unsigned d = in ? is_def[line] : 0u, c = in ? seq_len[line] : 0u;
+  const unsigned rank = list_first_item(d, def_sums);
+  __syncthreads();  // (list_first_item's wave totals are one LDS array: the first call's readers before the second call's writers)
+  const unsigned dst = list_first_item(c, len_sums);
+  if (!in) return;
+  const unsigned n_defs = tot[0];
+  const unsigned n_records = final_slab ? n_defs : (n_defs ? n_defs - 1u : 0u);
+  const unsigned begin = line ? nl[line - 1] + 1u : skip;
+  seq_len[line] = dst;
+  if (line == n_lines - 1u) {
+    seq_len[n_lines] = dst + c;
+    if (final_slab) {
+      seq_off[n_records] = (int32_t)(dst + c);
+      tot[2] = dst + c;
+      scalars[2] = nl[line] + 1u;
+    }
+  }
+  if (!d) return;
+  if (rank < n_records) {
+    unsigned he = nl[line];
+    if (he > begin + 1u && text[he - 1] == '\r') --he;
+    head_s[rank] = (int32_t)(begin + 1u);
+    head_e[rank] = (int32_t)he;
+    seq_off[rank] = (int32_t)dst;
+  } else {  // the last definition line of a slab that is not the input's last: the record it starts stays behind
+    seq_off[rank] = (int32_t)dst;
+    tot[2] = dst;
+    scalars[2] = begin;
+  }
+}
+
+}  // namespace
+
+struct exon_hip_fasta_parser {
+  exon_hip_ctx* ctx;
+  PoolBufs bufs;
+  LineIndex idx;
+  uint32_t *is_def = nullptr, *seq_len = nullptr;  // [cap] and [cap + 1] (seq_len turns into line_dst)
+  unsigned *def_sums = nullptr, *len_sums = nullptr;
+  unsigned *d_tot = nullptr, *h_tot = nullptr;  // device / pinned [4]
+  int32_t *head_s = nullptr, *head_e = nullptr, *seq_off = nullptr;  // [cap], [cap], [cap + 1]: a record is a line at least
+  explicit exon_hip_fasta_parser(exon_hip_ctx* c) : ctx(c), bufs(c) {}
+};
+
+extern "C" {
+
+int exon_hip_fasta_parser_create(exon_hip_ctx* ctx, int64_t max_bytes, exon_hip_fasta_parser** outp) {
+  if (!ctx || !outp || max_bytes < 16) return fail(ctx, EXON_HIP_EINVAL, "exon_hip_fasta_parser_create: bad argument");
+  if (max_bytes > 0x7FFF0000LL) return fail(ctx, EXON_HIP_EINVAL, "slab size must stay below 2 GiB (32-bit views)");
+  *outp = nullptr;
+  exon_hip_fasta_parser* p = new (std::nothrow) exon_hip_fasta_parser(ctx);
+  if (!p) return fail(ctx, EXON_HIP_ENOMEM, "out of host memory");
+  const int64_t max_lines = max_bytes / 8 + 8;  // LINE CAPACITY above; denser text is handed back to the host decoder
+  hipSetDevice(ctx->device);
+  p->idx.alloc(p->bufs, max_bytes, max_lines);
+  const size_t cap = (size_t)max_lines, nb = (cap + LIST_TPB - 1) / LIST_TPB;
+  p->is_def = p->bufs.take<uint32_t>(cap * 4);
+  p->seq_len = p->bufs.take<uint32_t>((cap + 1) * 4);
+  p->def_sums = p->bufs.take<unsigned>((nb + 1) * 4);
+  p->len_sums = p->bufs.take<unsigned>((nb + 1) * 4);
+  p->d_tot = p->bufs.take<unsigned>(16, 0);
+  p->h_tot = p->bufs.pinned<unsigned>(16);
+  p->head_s = p->bufs.take<int32_t>(cap * 4);
+  p->head_e = p->bufs.take<int32_t>(cap * 4);
+  p->seq_off = p->bufs.take<int32_t>((cap + 1) * 4);
+  if (p->bufs.status() != hipSuccess) {
+    const std::string msg = hipGetErrorString(p->bufs.status());
+    delete p;
+    return fail(ctx, EXON_HIP_ENOMEM, "fasta parser allocation: %s", msg.c_str());
+  }
+  *outp = p;
+  return EXON_HIP_OK;
+}
+
+int exon_hip_fasta_parser_destroy(exon_hip_fasta_parser* p) {
+  delete p;
+  return EXON_HIP_OK;
+}
+
+int exon_hip_fasta_parser_parse(exon_hip_fasta_parser* p, void* stream, const uint8_t* d_text, int64_t n_bytes, int32_t final_slab,
+                                exon_hip_fasta_views* views) {
+  if (!p || !views || (n_bytes > 0 && !d_text)) return fail(p ? p->ctx : nullptr, EXON_HIP_EINVAL, "exon_hip_fasta_parser_parse: NULL argument");
+  exon_hip_ctx* ctx = p->ctx;
+  memset(views, 0, sizeof *views);
+  if (n_bytes == 0) return EXON_HIP_OK;
+  LineIndex& idx = p->idx;
+  unsigned skip;
+  if (int rc = idx.align(ctx, &d_text, &n_bytes, &skip)) return rc;
+  hipStream_t s = pick_stream(ctx, stream);
+  idx.launch(s, d_text, n_bytes, skip);
+  // a line is a byte at least (its '\n'): the launches cover the lines the slab can hold, the kernels read the count on the device
+  const unsigned bound = (unsigned)std::min<int64_t>((int64_t)idx.cap, n_bytes);
+  const int nb = (int)((bound + LIST_TPB - 1) / LIST_TPB);
+  hipLaunchKernelGGL(k_fasta_classify, dim3((bound + TPB - 1) / TPB), dim3(TPB), 0, s, d_text, idx.nl, idx.d_scalars, idx.cap, skip, p->is_def, p->seq_len);
+  launch_list_scan(s, p->is_def, idx.d_scalars, idx.cap, nb, p->def_sums, p->d_tot);
+  launch_list_scan(s, p->seq_len, idx.d_scalars, idx.cap, nb, p->len_sums, p->d_tot + 1);
+  hipLaunchKernelGGL(k_fasta_records, dim3(nb), dim3(LIST_TPB), 0, s, d_text, idx.nl, idx.d_scalars, idx.cap, skip, (int)final_slab, p->is_def, p->seq_len, p->def_sums,
+                     p->len_sums, p->d_tot, p->head_s, p->head_e, p->seq_off);
+  HIP_TRY(ctx, hipMemcpyAsync(p->h_tot, p->d_tot, 16, hipMemcpyDeviceToHost, s));
+  if (int rc = idx.read_back(ctx, s)) return rc;
+  views->n_undecided = idx.h_scalars[1];
+  views->text_base = d_text;
+  views->text_bytes = n_bytes;
+  views->first_line_start = skip;
+  const unsigned n_lines = idx.h_scalars[0], n_defs = p->h_tot[0];
+  if (n_lines == 0 || n_lines > idx.cap || views->n_undecided) return EXON_HIP_OK;  // nothing else was written, or nothing of it counts
+  views->n_lines = n_lines;
+  views->n_records = final_slab ? n_defs : (n_defs ? n_defs - 1 : 0);
+  views->consumed_bytes = idx.consumed(skip);
+  views->seq_bytes = p->h_tot[2];
+  views->head_start = p->head_s;
+  views->head_end = p->head_e;
+  views->seq_offsets = p->seq_off;
+  views->line_end = idx.nl;
+  views->line_dst = p->seq_len;
+  return EXON_HIP_OK;
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------------------------------------------
 // SAM text: the first six tab-separated fields of every alignment line -> the BAM device layout (flag, mapq, reference
 // id, start, end).  Field rules of host/formats.h's SAM reader (schema of exon-sam/src/schema_builder.rs:371-402, same
 // columns as BAM): RNAME through the header's @SQ order ('*' or unknown -> NULL), POS 0 -> NULL, MAPQ 255 -> NULL,

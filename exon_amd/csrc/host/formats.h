@@ -1469,6 +1469,14 @@ class FASTABatchReader : public BatchReader {
     b.try_into_record_batch(out);
     return true;
   }
+  // the first byte of the decompressed text (-1: the input is empty); nothing is lost, the byte stays in front of the stream
+  int first_byte() { return r_.peek(); }
+  // the whole input as a raw byte stream (GPU-side record splitting); only valid before the first read_batch
+  std::unique_ptr<ByteSource> take_stream(std::string* carry) {
+    *carry = r_.take_buffered();
+    return r_.release_source();
+  }
+  int64_t data_offset() const { return 0; }  // no header: the records start with the text
   void schema(struct ArrowSchema* out) const override {
     make_schema(out, "+s", "", false, {new_field("u", "id", false), new_field("u", "description", true), new_field("u", "sequence", false)});
   }

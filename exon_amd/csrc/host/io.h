@@ -153,6 +153,8 @@ class BufReader {
     return true;
   }
   bool at_end() { return pos_ == end_ && !fill(); }
+  // the next byte without taking it (-1 at end of data): it stays buffered for read_line / take_buffered
+  int peek() { return at_end() ? -1 : (int)buf_[pos_]; }
 
  private:
   bool fill() {

@@ -86,6 +86,10 @@ int exon_text_sam(exon_hip_ctx* ctx, void* stream, ExonTextScratch** scratch, co
 // FASTQ: name, description? (validity: the header has something behind its first space), sequence, quality_scores, all Utf8
 // (exon-fastq/src/config.rs:79-88), in that order
 int exon_text_fastq(exon_hip_ctx* ctx, void* stream, ExonTextScratch** scratch, const exon_hip_fastq_views* views, int64_t n_bytes, ExonTextColumns* out);
+// FASTA: id, description? (validity: something follows the blanks behind the id), sequence, all Utf8 (host/formats.h FASTABatchReader::schema),
+// in that order; sequence's offsets are the parser's seq_offsets, its bytes every sequence line copied to its line_dst (one small
+// group of lanes per LINE: k_fasta_seq_fill)
+int exon_text_fasta(exon_hip_ctx* ctx, void* stream, ExonTextScratch** scratch, const exon_hip_fasta_views* views, ExonTextColumns* out);
 // BCF id / ref / alt through the reference's EAGER builder (eager_array_builder.rs:112-134): both lists carry their items, neither is
 // ever NULL (an empty list when the record has no id / no alternate bases)
 int exon_text_bcf(exon_hip_ctx* ctx, void* stream, ExonTextScratch** scratch, const uint8_t* d_data, int64_t n_bytes, const uint32_t* d_rec_of_row, int64_t n_rows, uint64_t projection,

@@ -33,7 +33,7 @@
 // The device parser of a GPU-decoded scan: whichever handle its format uses, created by the scan's first GPU-parsed consume
 struct DeviceParser {
   int format = 0;
-  void* h = nullptr;  // exon_hip_{vcf,bcf,bam,sam,fastq,gff}_parser of `format`
+  void* h = nullptr;  // exon_hip_{vcf,bcf,bam,sam,fastq,fasta,gff,bed}_parser of `format`
   // the dictionaries of the layout's device_names columns (FILTER, VCF's String INFO keys, GFF / BED names) are the device parser's
   bool owns_names = false;
   template <class T>
@@ -45,6 +45,7 @@ struct DeviceParser {
       case EXON_HIP_FORMAT_BAM: exon_hip_bam_parser_destroy(as<exon_hip_bam_parser>()); break;
       case EXON_HIP_FORMAT_SAM: exon_hip_sam_parser_destroy(as<exon_hip_sam_parser>()); break;
       case EXON_HIP_FORMAT_FASTQ: exon_hip_fastq_parser_destroy(as<exon_hip_fastq_parser>()); break;
+      case EXON_HIP_FORMAT_FASTA: exon_hip_fasta_parser_destroy(as<exon_hip_fasta_parser>()); break;
       case EXON_HIP_FORMAT_GFF:
       case EXON_HIP_FORMAT_GTF: exon_hip_gff_parser_destroy(as<exon_hip_gff_parser>()); break;  // (GTF: the same parser, its dialect set)
       case EXON_HIP_FORMAT_BED: exon_hip_bed_parser_destroy(as<exon_hip_bed_parser>()); break;
@@ -66,6 +67,9 @@ struct exon_hip_scan {
   // (exon_hip_scan_next) come from the host reader, but a consume_scan whose plan reads none of those columns still takes the
   // GPU pipeline -- the device parser decodes and validates the list keys and does not look at the string keys at all
   bool gpu_candidate = false;
+  // FASTA opened with gpu_parse: remembered for exon_hip_scan_bind_ctx alone, which turns gpu_parse on.  Unbound, the scan is the host
+  // reader's -- exon_hip_scan_next and exon_hip_stream_consume_scan as without the option (there is no fused FASTA plan)
+  bool fasta_gpu_request = false;
   bool gpu_inflated = false;  // the last GPU-parsed consume also inflated BGZF blocks on the device
   bool gpu_decoded = false;   // the last consume decoded every record on the device (no host fallback)
   exon::SlabLayout layout;                // the fixed-width columns and the children of a batch (slab_layout, at open)
@@ -96,6 +100,7 @@ struct exon_hip_scan {
   exon::BAMBatchReader* bam() const { return reader_if<exon::BAMBatchReader>(EXON_HIP_FORMAT_BAM); }
   exon::SAMBatchReader* sam() const { return reader_if<exon::SAMBatchReader>(EXON_HIP_FORMAT_SAM); }
   exon::FASTQBatchReader* fastq() const { return reader_if<exon::FASTQBatchReader>(EXON_HIP_FORMAT_FASTQ); }
+  exon::FASTABatchReader* fasta() const { return reader_if<exon::FASTABatchReader>(EXON_HIP_FORMAT_FASTA); }
   // GFF and GTF: one reader class (GTFBatchReader is its GTF dialect), one device parser, one column layout
   exon::GFFBatchReader* gff() const { return reader_if<exon::GFFBatchReader>(gtf() ? EXON_HIP_FORMAT_GTF : EXON_HIP_FORMAT_GFF); }
   bool gtf() const { return format == EXON_HIP_FORMAT_GTF; }
@@ -345,7 +350,7 @@ static exon::SlabLayout slab_layout(const exon_hip_scan& s) {
         if (proj & (1ull << c)) L.child(exon::bed_fields()[c].fmt[0] == 'u' ? exon::SlabChild::NULL_UTF8 : exon::SlabChild::NULL_I64, c);
       return L;
     }
-    default: L.region_col = -1;  // FASTQ / FASTA: text columns alone (export_fastq_slab)
+    default: L.region_col = -1;  // FASTQ / FASTA: text columns alone (export_text_slab)
   }
   L.plain_children();
   return L;
@@ -537,8 +542,10 @@ int exon_hip_scan_open(const char* path, const exon_hip_scan_options* o, exon_hi
       case EXON_HIP_FORMAT_BED:  // (no region, no index: refused above)
         s->gpu_parse = o->gpu_parse != 0;
         break;
+      case EXON_HIP_FORMAT_FASTA:  // batches from the GPU pipeline once a context is bound; until then the host reader's, which defers nothing
+        s->fasta_gpu_request = o->gpu_parse != 0;
+        break;
       case EXON_HIP_FORMAT_CRAM:
-      case EXON_HIP_FORMAT_FASTA:
         break;
       default:
         return fail(nullptr, EXON_HIP_EINVAL, "unknown format %d", o->format);
@@ -661,11 +668,25 @@ int exon_hip_index_query(const char* index_path, int32_t is_bai, const char* ref
 int exon_hip_scan_bind_ctx(exon_hip_scan* s, exon_hip_ctx* ctx) {
   if (!s || !ctx) return fail(ctx, EXON_HIP_EINVAL, "exon_hip_scan_bind_ctx: NULL argument");
   if (s->exporter) return fail(ctx, EXON_HIP_ESTATE, "the scan is bound to a context already");
-  if (s->format == EXON_HIP_FORMAT_FASTA || s->format == EXON_HIP_FORMAT_CRAM)
-    return fail(ctx, EXON_HIP_EUNSUPPORTED, "batches from the GPU pipeline: VCF, BCF, BAM, SAM, FASTQ, GFF, GTF and BED scans (FASTA / CRAM batches come from the host readers)");
-  if (!s->gpu_parse)  // not opened with gpu_parse, or String / list-valued INFO keys were named: the host reader builds those columns
+  if (s->format == EXON_HIP_FORMAT_CRAM)
+    return fail(ctx, EXON_HIP_EUNSUPPORTED, "batches from the GPU pipeline: VCF, BCF, BAM, SAM, FASTQ, FASTA, GFF, GTF and BED scans (CRAM batches come from the host reader)");
+  if (!s->gpu_parse && !s->fasta_gpu_request)  // not opened with gpu_parse, or String / list-valued INFO keys were named: the host reader builds those columns
     return fail(ctx, EXON_HIP_EUNSUPPORTED, "this scan's batches come from the host reader (opened without gpu_parse, or it names INFO keys only the host reader builds)");
   if (s->rows != 0) return fail(ctx, EXON_HIP_ESTATE, "the scan has been read from already");
+  if (s->fasta()) {
+    // the device parser wants a definition line first: text in front of it is the host reader's to skip (and the reference's to
+    // refuse), an empty input has no batches to build
+    int first = -1;
+    try {
+      first = s->fasta()->first_byte();
+    } catch (const std::exception& e) {
+      return fail(ctx, EXON_HIP_EINVAL, "%s", e.what());
+    }
+    if (first < 0) return fail(ctx, EXON_HIP_EUNSUPPORTED, "%s: an empty FASTA input has no batches for the GPU pipeline (the host reader returns none either)", s->path.c_str());
+    if (first != '>')
+      return fail(ctx, EXON_HIP_EUNSUPPORTED, "%s: the text does not start with a '>' definition line (first byte 0x%02x): text in front of the first record is the host reader's to skip", s->path.c_str(), (unsigned)first);
+    s->gpu_parse = true;
+  }
   s->exporter = new GpuExporter();
   s->exporter->ctx = ctx;
   return EXON_HIP_OK;
@@ -2304,10 +2325,10 @@ static int export_slab(exon_hip_scan* scan, const exon_hip_column* sc, int64_t n
   return EXON_HIP_OK;
 }
 
-// FASTQ batches from the GPU pipeline: the slab's four Utf8 columns (text_columns.hip: name, description?, sequence,
-// quality_scores -- exon-fastq/src/config.rs:79-88) come back into ONE pinned block and go out as batch_size-row views into it
-// (slab-wide offsets / data buffers, ArrowArray::offset = the batch's first read).
-static int export_fastq_slab(exon_hip_scan* scan, const ExonTextColumns& ft, int64_t n_reads, hipStream_t hs) {
+// FASTQ and FASTA batches from the GPU pipeline: the slab's Utf8 columns (text_columns.hip: name, description?, sequence,
+// quality_scores -- exon-fastq/src/config.rs:79-88; id, description?, sequence) come back into ONE pinned block and go out as
+// batch_size-row views into it (slab-wide offsets / data buffers, ArrowArray::offset = the batch's first record).
+static int export_text_slab(exon_hip_scan* scan, const ExonTextColumns& ft, int64_t n_reads, hipStream_t hs) {
   GpuExporter* ex = scan->exporter;
   exon_hip_ctx* ctx = ex->ctx;
   if (const int rc = export_flush(scan)) return rc;  // the slab before this one
@@ -2352,6 +2373,7 @@ static int64_t data_offset(const exon_hip_scan* scan) {
     case EXON_HIP_FORMAT_GFF:
     case EXON_HIP_FORMAT_GTF: return scan->gff()->data_offset();  // (no header: '#' lines are the device parser's to skip)
     case EXON_HIP_FORMAT_BED: return scan->bed()->data_offset();
+    case EXON_HIP_FORMAT_FASTA: return scan->fasta()->data_offset();
   }
   return 0;  // FASTQ: no header
 }
@@ -2362,6 +2384,7 @@ static std::unique_ptr<exon::ByteSource> take_text_stream(exon_hip_scan* scan, s
     case EXON_HIP_FORMAT_VCF: return scan->vcf()->take_stream(carry);
     case EXON_HIP_FORMAT_SAM: return scan->sam()->take_stream(carry);
     case EXON_HIP_FORMAT_FASTQ: return scan->fastq()->take_stream(carry);
+    case EXON_HIP_FORMAT_FASTA: return scan->fasta()->take_stream(carry);
     case EXON_HIP_FORMAT_GFF:
     case EXON_HIP_FORMAT_GTF: return scan->gff()->take_stream(carry);
     case EXON_HIP_FORMAT_BED: return scan->bed()->take_stream(carry);
@@ -2432,6 +2455,12 @@ static int create_parser(exon_hip_scan* scan, exon_hip_ctx* ctx, int64_t max_tex
       p.h = h;
       break;
     }
+    case EXON_HIP_FORMAT_FASTA: {
+      exon_hip_fasta_parser* h = nullptr;
+      rc = exon_hip_fasta_parser_create(ctx, max_text_bytes, &h);
+      p.h = h;
+      break;
+    }
     case EXON_HIP_FORMAT_GFF:
     case EXON_HIP_FORMAT_GTF: {  // seeded with the names interned so far (a region's contig): their ids stay
       std::vector<const char*> names;
@@ -2456,7 +2485,7 @@ static int create_parser(exon_hip_scan* scan, exon_hip_ctx* ctx, int64_t max_tex
 }
 
 // One slab parsed on the device: the scan's fixed-width columns in the order of scan->layout (slab_layout names them per format) with
-// the operands of the region mask, or (FASTQ) the views of the slab's reads
+// the operands of the region mask, or (FASTQ, FASTA) the views of the slab's records
 struct SlabParse {
   exon_hip_column sc[4 + EXON_HIP_MAX_INFO_FIELDS] = {};
   int64_t n_rows = 0, consumed = 0, n_undecided = 0;
@@ -2464,7 +2493,8 @@ struct SlabParse {
   const uint8_t *id_valid = nullptr, *pos_valid = nullptr;
   const int64_t *c_start = nullptr, *c_end = nullptr;  // ... and the records' intervals
   bool has_views = false;
-  exon_hip_fastq_views views;
+  exon_hip_fastq_views views;        // FASTQ
+  exon_hip_fasta_views fasta_views;  // FASTA
 };
 static int parse_slab(exon_hip_scan* scan, hipStream_t hs, const uint8_t* d_text, size_t n, bool final, SlabParse* p) {
   exon_hip_column* sc = p->sc;
@@ -2578,6 +2608,15 @@ static int parse_slab(exon_hip_scan* scan, hipStream_t hs, const uint8_t* d_text
       }
       return EXON_HIP_OK;
     }
+    case EXON_HIP_FORMAT_FASTA: {
+      rc = exon_hip_fasta_parser_parse(scan->parser.as<exon_hip_fasta_parser>(), hs, d_text, (int64_t)n, final ? 1 : 0, &p->fasta_views);
+      if (rc) return rc;
+      p->has_views = true;
+      p->n_undecided = p->fasta_views.n_undecided;
+      p->consumed = p->fasta_views.consumed_bytes;
+      p->n_rows = p->fasta_views.n_records;
+      return EXON_HIP_OK;
+    }
     default: {  // FASTQ
       rc = exon_hip_fastq_parser_parse(scan->parser.as<exon_hip_fastq_parser>(), hs, d_text, (int64_t)n, final ? 1 : 0, &p->views);
       if (rc) return rc;
@@ -2652,7 +2691,7 @@ static int consume_text_gpu(exon_hip_stream* st, exon_hip_scan* scan, int64_t* r
 
   // ---- where the slabs come from: the index chunks' blocks, the BGZF file, a plain-gzip file, or the reader's text stream ----
   const bool binary = scan->bam() || scan->bcf();  // BGZF by definition: inflated on the device or decoded on the host
-  const bool filtered = scan->region.active && !scan->fastq();
+  const bool filtered = scan->region.active && !scan->fastq() && !scan->fasta();
   const bool indexed = filtered && scan->region.use_index && (scan->vcf() || scan->bam() || scan->gff());
   const bool device_inflate = gpu_inflate_enabled() && scan->opt.compression != EXON_HIP_COMPRESSION_NONE;
   const bool bgzf = device_inflate && exon::BgzfParallelSource::is_bgzf(scan->path) && (indexed || data_offset(scan) >= 0);
@@ -2698,7 +2737,7 @@ static int consume_text_gpu(exon_hip_stream* st, exon_hip_scan* scan, int64_t* r
     try {
       GpuTextSource::Options so;
       so.binary = binary;
-      so.text_async = scan->fastq() != nullptr;
+      so.text_async = scan->fastq() || scan->fasta();
       std::unique_ptr<exon::ByteSource> in;
       if (indexed) {
         so.skip_first = ranges[si].skip;
@@ -2754,10 +2793,12 @@ static int consume_text_gpu(exon_hip_stream* st, exon_hip_scan* scan, int64_t* r
         if (rc) break;
       }
       if (p.n_rows > 0 && p.has_views) {
-        if (scan->exporter) {  // batches: the four Utf8 columns, built on the device
+        if (scan->exporter) {  // batches: the Utf8 columns, built on the device
           ExonTextColumns ft;
-          rc = exon_text_fastq(ctx, hs, &scan->text_scratch, &p.views, (int64_t)n + 16, &ft);
-          if (!rc) rc = export_fastq_slab(scan, ft, p.n_rows, hs);
+          rc = scan->fasta() ? exon_text_fasta(ctx, hs, &scan->text_scratch, &p.fasta_views, &ft) : exon_text_fastq(ctx, hs, &scan->text_scratch, &p.views, (int64_t)n + 16, &ft);
+          if (!rc) rc = export_text_slab(scan, ft, p.n_rows, hs);
+        } else if (scan->fasta()) {  // (never: gpu_parse is set on a FASTA scan by exon_hip_scan_bind_ctx alone)
+          rc = fail(ctx, EXON_HIP_EUNSUPPORTED, "there is no fused plan over FASTA text: a stream reads a FASTA scan through the host reader");
         } else {
           rc = exon_hip_stream_launch_views(st, d_text, p.views);  // asynchronous: overlaps with preparing the next slab
         }

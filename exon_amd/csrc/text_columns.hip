@@ -252,6 +252,80 @@ __global__ __launch_bounds__(TPB) void k_fastq_fill(const uint8_t* __restrict__ 
   copy_run(qual_v + qual_off[r], text + qual_s[r], (unsigned)(qual_off[r + 1] - qual_off[r]));
 }
 
+// ---- FASTA -------------------------------------------------------------------------------------------------------------------------
+// id, description, sequence (THE RULES: gpu_parse.hip, next to the FASTA parser; host/formats.h FASTAArrayBuilder::append).  The
+// definition [head_s[r], head_e[r]) is ONE line, so id and description are measured and filled by a thread per record: the id
+// runs up to the first ' ' or '\t' (FASTQ's rule knows the space alone and keeps what follows it as it stands: not reusable), the
+// description starts behind the whole run of blanks and is NULL when nothing is left.  It ends where the definition ends, so
+// the fill finds it again from its length.
+__global__ __launch_bounds__(TPB) void k_fasta_measure(const uint8_t* __restrict__ text, unsigned n_records, const int32_t* __restrict__ head_s,
+                                                       const int32_t* __restrict__ head_e, uint32_t* __restrict__ id_len, uint32_t* __restrict__ desc_len,
+                                                       uint32_t* __restrict__ desc_valid) {
+  const unsigned r = blockIdx.x * TPB + threadIdx.x;
+  bool has_desc = false;
+  if (r < n_records) {
+    const unsigned b = (unsigned)head_s[r], e = (unsigned)head_e[r];
+    unsigned ws = b;
+    while (ws < e && text[ws] != ' ' && text[ws] != '\t') ++ws;
+    unsigned d = ws;
+    while (d < e && (text[d] == ' ' || text[d] == '\t')) ++d;
+    has_desc = d < e;
+    id_len[r] = ws - b;
+    desc_len[r] = e - d;
+  }
+  const unsigned long long m = __ballot(has_desc);
+  if ((threadIdx.x & 63) == 0 && r < n_records + 63) {
+    desc_valid[r >> 5] = (uint32_t)m;
+    desc_valid[(r >> 5) + 1] = (uint32_t)(m >> 32);
+  }
+}
+// cap: the bytes either pool holds; n_total: the bytes readable at `text`.  A record that would reach past either writes nothing
+// (never, by the capacity table: both columns are parts of the text)
+__global__ __launch_bounds__(TPB) void k_fasta_head_fill(const uint8_t* __restrict__ text, unsigned n_total, unsigned n_records, const int32_t* __restrict__ head_s,
+                                                         const int32_t* __restrict__ head_e, const int32_t* __restrict__ id_off, const int32_t* __restrict__ desc_off,
+                                                         uint8_t* __restrict__ id_v, uint8_t* __restrict__ desc_v, unsigned cap) {
+  const unsigned r = blockIdx.x * TPB + threadIdx.x;
+  if (r >= n_records) return;
+  const unsigned b = (unsigned)head_s[r], e = (unsigned)head_e[r];
+  const unsigned ia = (unsigned)id_off[r], in = (unsigned)(id_off[r + 1] - id_off[r]);
+  const unsigned da = (unsigned)desc_off[r], dn = (unsigned)(desc_off[r + 1] - desc_off[r]);
+  if (e > n_total || b > e || in > e - b || dn > e - b) return;
+  if (in && (uint64_t)ia + in <= cap) copy_run(id_v + ia, text + b, in);
+  if (dn && (uint64_t)da + dn <= cap) copy_run(desc_v + da, text + (e - dn), dn);
+}
+// The hot kernel: the sequence column.  The work is cut by LINE, not by record -- a slab that is one 10 MB contig and a slab of
+// 100 000 short records are the same few hundred thousand lines of 60 - 80 bytes, and nothing a lane does grows with a record.
+// FASTA_LPL = 8 lanes take a line, 8 bytes each per step (64 bytes a step: one step for a 60-column line, two for 80); line l's
+// bytes [begin, begin + n) go to [line_dst[l], line_dst[l] + n) with n = line_dst[l + 1] - line_dst[l] (0 for definition and empty
+// lines: those lanes leave at once).  Both sides are unaligned (any line length, any offset): the 8-byte moves are two dword
+// loads and two dword stores, as in copy_run -- the hardware takes unaligned dwords, and the eight lanes of a line and the lines
+// of a wave are contiguous in the text and, definition lines apart, in the column.  The last 1 - 7 bytes of a line go one by one.
+// BOUNDS: a load stays inside the line ([begin, begin + n), begin + n <= line_end[l] < n_total -- checked, not assumed); a store
+// stays inside [line_dst[l], line_dst[l] + n) and below seq_bytes = seq_offsets[n_records] <= cap: lines of the record a
+// non-final slab leaves behind start at or beyond seq_bytes and write nothing.
+constexpr unsigned FASTA_LPL = 8;  // lanes per line
+__global__ __launch_bounds__(TPB) void k_fasta_seq_fill(const uint8_t* __restrict__ text, unsigned n_total, unsigned skip, const unsigned* __restrict__ line_end,
+                                                        const uint32_t* __restrict__ line_dst, unsigned n_lines, uint8_t* __restrict__ seq_v, unsigned seq_bytes,
+                                                        unsigned cap) {
+  const unsigned t = blockIdx.x * TPB + threadIdx.x;
+  const unsigned line = t / FASTA_LPL, sub = t % FASTA_LPL;
+  if (line >= n_lines) return;
+  const unsigned at = line_dst[line], n = line_dst[line + 1] - at;
+  if (n == 0) return;
+  const unsigned begin = line ? line_end[line - 1] + 1u : skip, end = line_end[line];
+  if (end > n_total || begin > end || n > end - begin) return;                          // loads: inside the line, inside the slab
+  if ((uint64_t)at + n > seq_bytes || (uint64_t)at + n > cap) return;  // stores: inside the emitted records' bytes, inside the pool
+  const uint8_t* __restrict__ src = text + begin;
+  uint8_t* __restrict__ dst = seq_v + at;
+  unsigned i = sub * 8u;
+  for (; i + 8u <= n; i += FASTA_LPL * 8u) {
+    const uint32_t a = *reinterpret_cast<const uint32_t*>(src + i), b = *reinterpret_cast<const uint32_t*>(src + i + 4);
+    *reinterpret_cast<uint32_t*>(dst + i) = a;
+    *reinterpret_cast<uint32_t*>(dst + i + 4) = b;
+  }
+  for (; i < n; ++i) dst[i] = src[i];  // (the one lane whose 8-byte group the line's end cuts: i + 8 > n here)
+}
+
 // ---- SAM ---------------------------------------------------------------------------------------------------------------------------
 // The BAM columns from an alignment LINE (exon-sam/src/array_builder.rs:101-185 over noodles' RecordBuf): QNAME '*' -> NULL; the
 // CIGAR printed op by op ('*' -> ""; a text the printer would change -- an op count with a leading zero -- or would refuse makes
@@ -922,7 +996,7 @@ struct TextLayout {
   bool operator==(const TextLayout& o) const { return cols == o.cols && pools == o.pools && item_offs == o.item_offs && field_words == o.field_words && valids == o.valids; }
 };
 constexpr TextLayout LAYOUT_VCF{3, 3, 1, 6, 2}, LAYOUT_BCF{5, 3, 2, 0, 0}, LAYOUT_BAM{3, 3, 0, 0, 1}, LAYOUT_SAM{4, 3, 0, 4, 1}, LAYOUT_FASTQ{4, 4, 0, 0, 1},
-    LAYOUT_GFF{4, 2, 3, 0, 0}, LAYOUT_GTF{3, 2, 2, 0, 0}, LAYOUT_BED{1, 1, 0, 0, 0};
+    LAYOUT_GFF{4, 2, 3, 0, 0}, LAYOUT_GTF{3, 2, 2, 0, 0}, LAYOUT_BED{1, 1, 0, 0, 0}, LAYOUT_FASTA{2, 3, 0, 0, 1};
 constexpr int RES_WORDS = 8, RES_UNDECIDED = 7;
 
 struct ExonTextScratch {
@@ -978,6 +1052,10 @@ void exon_text_scratch_destroy(ExonTextScratch* s) { delete s; }
 //   SAM    values[0], [1], [2] (max_bytes = n_bytes): QNAME / CIGAR / SEQ fields, copied as they are: <= n_bytes each: fits
 //   SAM    qual: an item per QUAL byte; qual_for grows it to the total before the fill: fits
 //   FASTQ  values[0 .. 3] (max_bytes = n_bytes + 16): name / description / sequence / quality, disjoint parts of the text: <= n_bytes: fits
+//   FASTA  values[0 .. 2] (max_bytes = n_bytes + 16): id / description / sequence, disjoint parts of the text (an id and a description share
+//                    a definition line, a sequence byte lies on no definition line): <= n_bytes each: fits.  The sequence offsets are the
+//                    parser's (one per record, sized for a record a line).  k_fasta_head_fill and k_fasta_seq_fill bound their reads
+//                    and writes all the same.
 //   GFF    (max_bytes = n_bytes; F = the bytes of the slab's ninth fields; a record has at least 16 bytes in front of its ninth field
 //          -- eight fields, eight TABs -- and its LF behind it: F <= n_bytes - 17 n_rows)
 //   GFF    values[0]: decoded key bytes, values[1]: decoded item bytes; a byte of either comes from a byte of the field or from three: <= F each: fits
@@ -1308,6 +1386,28 @@ int exon_text_fastq(exon_hip_ctx* ctx, void* stream, ExonTextScratch** sp, const
   HIP_TRY(ctx, hipGetLastError());
   if (int rc = text_totals(ctx, t, 0)) return rc;
   for (int k = 0; k < 4; ++k) out->root(out->utf8(t.n, s->off[k], k == 1 ? s->valid[0] : nullptr, s->values[k], s->h_res[k]));
+  return text_done(ctx, out);
+}
+
+int exon_text_fasta(exon_hip_ctx* ctx, void* stream, ExonTextScratch** sp, const exon_hip_fasta_views* v, ExonTextColumns* out) {
+  *out = ExonTextColumns();
+  if (v->n_records == 0) return EXON_HIP_OK;
+  TextRun t;
+  if (int rc = text_begin(ctx, stream, sp, v->n_records, v->text_bytes + 16, LAYOUT_FASTA, &t)) return rc;
+  ExonTextScratch* s = t.s;
+  const unsigned cap = (unsigned)std::min<size_t>(s->value_cap, 0xFFFFFFFFu), n_total = (unsigned)v->text_bytes;
+  hipLaunchKernelGGL(k_fasta_measure, dim3(t.nb), dim3(TPB), 0, t.hs, v->text_base, t.n, v->head_start, v->head_end, s->len[0], s->len[1], s->valid[0]);
+  scan_cols(t, 2);  // (as for FASTQ: the fills go in front of the totals' way back, the text is read when this returns)
+  hipLaunchKernelGGL(k_fasta_head_fill, dim3(t.nb), dim3(TPB), 0, t.hs, v->text_base, n_total, t.n, v->head_start, v->head_end, s->off[0], s->off[1], s->values[0], s->values[1], cap);
+  const uint64_t fill_threads = (uint64_t)v->n_lines * FASTA_LPL;
+  hipLaunchKernelGGL(k_fasta_seq_fill, dim3((unsigned)((fill_threads + TPB - 1) / TPB)), dim3(TPB), 0, t.hs, v->text_base, n_total, (unsigned)v->first_line_start, v->line_end,
+                     v->line_dst, (unsigned)v->n_lines, s->values[2], (unsigned)v->seq_bytes, cap);
+  HIP_TRY(ctx, hipGetLastError());
+  if (int rc = text_totals(ctx, t, 0)) return rc;
+  if (!fits(s, {s->h_res[0], s->h_res[1], (unsigned)v->seq_bytes})) return fail(ctx, EXON_HIP_ESTATE, "FASTA columns of %u + %u + %lld bytes in a slab of %lld", s->h_res[0], s->h_res[1], (long long)v->seq_bytes, (long long)v->text_bytes);  // (never: the table above scratch_for)
+  out->root(out->utf8(t.n, s->off[0], nullptr, s->values[0], s->h_res[0]));
+  out->root(out->utf8(t.n, s->off[1], s->valid[0], s->values[1], s->h_res[1]));
+  out->root(out->utf8(t.n, v->seq_offsets, nullptr, s->values[2], v->seq_bytes));
   return text_done(ctx, out);
 }
 

@@ -1023,6 +1023,58 @@ class FASTQParser:
             self.h = None
 
 
+class FASTAParser:
+    """FASTA record splitting on the GPU (exon_hip_fasta_parser_*): text slab in HBM -> per record the definition and the
+    Arrow offsets of the sequence column, per line where its bytes go in that column."""
+
+    def __init__(self, ctx, max_slab_bytes=64 << 20):
+        self.ctx = ctx
+        h = C.c_void_p()
+        ctx._check(ctx.lib.exon_hip_fasta_parser_create(ctx.h, max_slab_bytes, C.byref(h)))
+        self.h = h
+
+    def parse_device(self, d_text, n_bytes, final=True, stream=None):
+        v = L.FASTAViews()
+        ptr = d_text.ptr if isinstance(d_text, DeviceBuffer) else int(d_text)
+        self.ctx._check(self.ctx.lib.exon_hip_fasta_parser_parse(self.h, stream, ptr, n_bytes, 1 if final else 0, C.byref(v)))
+        return v
+
+    def parse_host(self, text, final=True, misalign=0):
+        """Test helper: copy `text` to HBM (`misalign` bytes past a 16-byte boundary), split it and bring back, per record, the
+        definition bytes (behind '>', CR dropped) and the sequence length, plus n_records, n_undecided and consumed; line_dst
+        (where every line's bytes go in the sequence column, n_lines + 1 entries) and line_end relative to the start of the
+        text come along."""
+        buf = np.frombuffer(text, np.uint8)
+        d = self.ctx.to_device(np.concatenate([np.full(misalign, 10, np.uint8), buf, np.zeros(64, np.uint8)]))
+        v = self.parse_device(d.ptr + misalign, len(buf), final)
+        n = v.n_records
+
+        def get(ptr, count, dtype=np.int32):
+            out = np.empty(count, dtype)
+            if count:
+                self.ctx._check(self.ctx.lib.exon_hip_memcpy_d2h(self.ctx.h, _np_ptr(out), ptr, out.nbytes, None))
+            return out
+
+        out = {"n_records": n, "n_undecided": v.n_undecided, "consumed": v.consumed_bytes, "n_lines": v.n_lines,
+               "seq_bytes": v.seq_bytes, "views": v, "keepalive": d, "definitions": [], "seq_len": []}
+        if n:
+            shift = v.first_line_start
+            hs, he = get(v.head_start, n) - shift, get(v.head_end, n) - shift
+            off = get(v.seq_offsets, n + 1)
+            out["definitions"] = [bytes(buf[a:b]) for a, b in zip(hs.tolist(), he.tolist())]
+            out["seq_len"] = np.diff(off).tolist()
+            out["seq_offsets"] = off
+        if v.n_lines:
+            out["line_dst"] = get(v.line_dst, v.n_lines + 1, np.uint32)
+            out["line_end"] = get(v.line_end, v.n_lines, np.uint32) - np.uint32(v.first_line_start)
+        return out
+
+    def close(self):
+        if self.h:
+            self.ctx.lib.exon_hip_fasta_parser_destroy(self.h)
+            self.h = None
+
+
 class Plan:
     def __init__(self, ctx, desc, columns):
         self.ctx = ctx

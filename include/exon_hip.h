@@ -552,7 +552,11 @@ typedef struct exon_hip_scan_options {
   int32_t gpu_parse;      /* VCF, BCF, FASTQ, BAM, SAM, GFF, GTF, BED: exon_hip_stream_consume_scan ships the file's bytes to HBM and decodes
                              them on the GPU (exon_hip_bgzf_inflate, exon_hip_vcf_parser_* / exon_hip_fastq_parser_* /
                              exon_hip_bam_parser_* ...).  exon_hip_scan_next on such a scan needs exon_hip_scan_bind_ctx first
-                             (batches then come out of the same GPU pipeline); without a bound ctx it returns ESTATE */
+                             (batches then come out of the same GPU pipeline); without a bound ctx it returns ESTATE.
+                             FASTA: the request is remembered for exon_hip_scan_bind_ctx alone (batches from the GPU pipeline,
+                             exon_hip_fasta_parser_*).  There is no fused FASTA plan: exon_hip_stream_consume_scan reads such a
+                             scan through the host reader, and exon_hip_scan_next without a bound ctx returns the host reader's
+                             batches (that reader defers nothing) */
   uint64_t projection;    /* (ABI 5) EXON_HIP_PROJECT_* bits: columns of the reference's schema beyond the fused kernels' operands,
                              appended BEHIND the default ones in bit order (0 = none: the hot path ships only what a plan reads).
                              VCF text: id List<Utf8>?, ref Utf8, alt List<Utf8>? (lazy_array_builder.rs:169-205; the alt list has no
@@ -614,8 +618,12 @@ int exon_hip_scan_rows(exon_hip_scan* scan, int64_t* rows_emitted);
  * fills a bounded queue; if the device cannot decide a record the host reader takes over behind the last row emitted.
  * VCF / BCF (chrom, pos, qual, filter, Float / Integer / Flag INFO keys), BAM, SAM, and (round 6) FASTQ -- name, description,
  * sequence, quality_scores as Utf8 columns built on the device (exon-fastq/src/array_builder.rs:68-102), plain, gzip or BGZF;
- * EXON_HIP_EUNSUPPORTED for other formats and for scans whose batches the host reader must build (list-valued INFO keys, the
- * info / formats text columns).  Call before the first
+ * GFF, GTF, BED; FASTA -- id, description, sequence as Utf8 columns built on the device (the rules next to
+ * exon_hip_fasta_parser_create), plain, gzip or BGZF: EXON_HIP_EUNSUPPORTED when the input is empty or its first decompressed byte
+ * is not '>' (text in front of the first definition line is the host reader's to skip), and a record larger than the carried tail
+ * of a slab may be (a quarter of a slab, 20 MB at the default size) hands the file to the host reader: whole chromosomes stay a
+ * host format.  EXON_HIP_EUNSUPPORTED for CRAM and for scans whose batches the host reader must build (opened without gpu_parse,
+ * list-valued INFO keys, the formats text column).  Call before the first
  * exon_hip_scan_next; `ctx` must outlive the scan.  A scan with a pushed-down value predicate (exon_hip_scan_set_predicate) masks
  * every slab on the device, takes the surviving rows of every column there and copies only those back. */
 int exon_hip_scan_bind_ctx(exon_hip_scan* scan, exon_hip_ctx* ctx);
@@ -805,6 +813,42 @@ int exon_hip_fastq_parser_create(exon_hip_ctx* ctx, int64_t max_slab_bytes, exon
 int exon_hip_fastq_parser_parse(exon_hip_fastq_parser* parser, void* stream, const uint8_t* d_text, int64_t n_bytes,
                                 int32_t final_slab, exon_hip_fastq_views* views);
 int exon_hip_fastq_parser_destroy(exon_hip_fastq_parser* parser);
+
+/* ---- (additive; the ABI stays 5) FASTA record splitting on the GPU (raw text in HBM -> definitions + compacted sequence layout) ----
+ * The rules are the host reader's (FASTABatchReader + FASTAArrayBuilder, exon_amd/csrc/host/formats.h; exon-fasta/src/
+ * batch_reader.rs:72-99, array_builder.rs:114-132), restated in gpu_parse.hip: lines end at '\n', one '\r' in front of it is dropped;
+ * a line whose first byte is '>' starts a record and the rest of it is the definition; the sequence is every following line up to
+ * the next '>' line, concatenated as it stands.  A record is a variable number of lines, so the parser describes the slab by LINE:
+ * line l ends at line_end[l] (its '\n', an index into text_base), and the bytes it adds to the compacted sequence column lie at
+ * [line_dst[l], line_dst[l + 1]) of that column (nothing for a definition line or an empty line).  Record r has the definition
+ * [head_start[r], head_end[r]) -- behind '>', CR dropped -- and the sequence bytes [seq_offsets[r], seq_offsets[r + 1]): seq_offsets
+ * is the Arrow int32 offsets buffer of the `sequence` column as it stands.
+ * final_slab == 0: the slab's last record is never known to be complete: n_records = definition lines - 1 and consumed_bytes ends
+ * directly in front of the last definition line (0 with fewer than two of them: the caller carries everything, or gives up).
+ * final_slab != 0: every record is complete, consumed_bytes is the whole text (which must end with '\n').
+ * n_undecided != 0 (the first line does not start with '>', more lines than the parser was sized for -- max_slab_bytes / 8 + 8, see
+ * gpu_parse.hip): decode that input on the host instead.  The buffers are the parser's, overwritten by the next parse call. */
+typedef struct exon_hip_fasta_parser exon_hip_fasta_parser;
+typedef struct exon_hip_fasta_views {
+  int64_t n_records;
+  int64_t n_undecided;
+  int64_t consumed_bytes;
+  int64_t n_lines;               /* lines of the slab, the ones behind consumed_bytes included */
+  int64_t seq_bytes;             /* = seq_offsets[n_records] */
+  const uint8_t* text_base;      /* what the views index: the 16-byte aligned address at or below d_text */
+  int64_t text_bytes;            /* bytes readable at text_base: n_bytes + first_line_start */
+  int64_t first_line_start;      /* d_text - text_base (< 16): where line 0 starts */
+  const int32_t* head_start;     /* [n_records] */
+  const int32_t* head_end;       /* [n_records] */
+  const int32_t* seq_offsets;    /* [n_records + 1] */
+  const uint32_t* line_end;      /* [n_lines] */
+  const uint32_t* line_dst;      /* [n_lines + 1] */
+} exon_hip_fasta_views;
+int exon_hip_fasta_parser_create(exon_hip_ctx* ctx, int64_t max_slab_bytes, exon_hip_fasta_parser** out);
+/* d_text: any alignment, < 2 GiB.  Synchronises `stream`. */
+int exon_hip_fasta_parser_parse(exon_hip_fasta_parser* parser, void* stream, const uint8_t* d_text, int64_t n_bytes,
+                                int32_t final_slab, exon_hip_fasta_views* views);
+int exon_hip_fasta_parser_destroy(exon_hip_fasta_parser* parser);
 
 /* ---- BAM record splitting + field extraction on the GPU (inflated BAM bytes in HBM -> device-layout columns) ----
  * Column rules of BAMArrayBuilder::append (exon-bam/src/array_builder.rs:102-218) for flag, mapping_quality (NULL when
