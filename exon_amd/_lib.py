@@ -241,6 +241,7 @@ SIGNATURES = {
     "exon_hip_scan_rows": (C.c_int, [_vp, C.POINTER(_i64)]),
     "exon_hip_scan_bind_ctx": (C.c_int, [_vp, _vp]),
     "exon_hip_scan_set_predicate": (C.c_int, [_vp, _i32, _i32, C.c_double]),
+    "exon_hip_scan_set_flag_predicate": (C.c_int, [_vp, _i32, _i32, _i32]),
     "exon_hip_scan_export_stats": (C.c_int, [_vp, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64)]),
     "exon_hip_scan_decoded_on_gpu": (C.c_int, [_vp, C.POINTER(_i32), C.POINTER(_i32)]),
     "exon_hip_scan_close": (C.c_int, [_vp]),

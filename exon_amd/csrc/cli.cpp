@@ -14,6 +14,7 @@
 //   SELECT COUNT(*) FROM b WHERE bam_region_filter('chr1:1-100', reference, start, end) [= true]  -- pushed down
 //   SELECT COUNT(*) FROM g WHERE gff_region_filter('chr1[:a-b]', seqname[, start]) [= true]       -- K2 over (seqname, start); GFF and GTF sources
 //   SELECT COUNT(*) FROM b WHERE gff_region_filter('chr1[:a-b]', reference_sequence_name[, start]) [= true] -- the same over a BED source: K2 over (0, 1)
+//   SELECT COUNT(*) FROM b WHERE [bam_region_filter(..) AND] flag & 1284 = 0 [AND CAST(mapping_quality AS INT) >= 30]  -- pushed into the BAM / SAM scan (exon_hip_scan_set_flag_predicate)
 //   SELECT reference, COUNT(*) FROM b WHERE flag & 1284 = 0 AND CAST(mapping_quality AS INT) >= 30 GROUP BY reference  -- K3
 //   SELECT filter, AVG(qual), COUNT(*) FROM v WHERE info."AF" > 0.01 GROUP BY filter            -- K4
 //   SELECT filter, MIN(qual), MAX(qual), COUNT(*) FROM v WHERE info."AF" > 0.01 GROUP BY filter -- K8 (also MIN / MAX(info."DP"))
@@ -298,11 +299,14 @@ void open_scan(const Source& src, const std::string& file, const char* info_fiel
 }
 
 // CPU plumbing: decode and count rows (optionally with a pushed-down region filter)
-int64_t count_rows(const Source& src, const std::string& region) {
+struct Predicate;
+void push_flags(exon_hip_scan* s, const Predicate* pr);
+int64_t count_rows(const Source& src, const std::string& region, const Predicate* flags = nullptr) {
   int64_t total = 0;
   for (const auto& f : src.files) {
     ScanGuard g;
     open_scan(src, f, nullptr, region, &g);
+    push_flags(g.s, flags);
     for (;;) {
       struct ArrowArray b;
       const int rc = exon_hip_scan_next(g.s, &b);
@@ -320,8 +324,16 @@ struct Predicate {  // what the WHERE clause turned into
   std::string chrom; int64_t start = 1, end = INT64_MAX;      // Region
   std::string region;                                          // PushedRegion
   int32_t flag_mask = 0, flag_value = 0, mapq_min = INT32_MIN; // FlagMapq
+  bool flags = false;  // a flag / mapping_quality conjunct was given (FlagMapq, or ANDed with a pushed bam_region_filter)
+  // the scan's own form of it (exon_hip_scan_set_flag_predicate): an unset mapq conjunct is -1; a negative bound still drops NULLs
+  int32_t scan_mapq_min() const { return mapq_min == INT32_MIN ? -1 : std::max(mapq_min, 0); }
   std::string info_field; int cmp_op = 0; double literal = 0;  // InfoCmp
 };
+
+// the WHERE clause's flag / mapping_quality conjuncts into the scan itself (BAM, SAM; any other source: the scan's own refusal)
+void push_flags(exon_hip_scan* s, const Predicate* pr) {
+  if (pr && pr->flags) ck(nullptr, exon_hip_scan_set_flag_predicate(s, pr->flag_mask, pr->flag_value, pr->scan_mapq_min()));
+}
 
 int cmp_code(const std::string& s) {
   if (s == ">") return EXON_HIP_GT;
@@ -344,7 +356,7 @@ Predicate parse_where(Parser& ps, int format) {
     while (ps.accept_sym(",")) ps.ident();
     ps.expect_sym(")");
     if (ps.accept_sym("=")) ps.expect_kw("true");
-    return pr;
+    if (!ps.is_kw("and")) return pr;  // (else: bam_region_filter(..) AND flag & M = V [AND CAST(mapping_quality AS INT) >= q])
   }
   if (ps.is_kw("region_match")) {  // region_match(chrom, pos, 'r')
     ps.ident(); ps.expect_sym("("); ps.ident(); ps.expect_sym(","); ps.ident(); ps.expect_sym(",");
@@ -355,15 +367,25 @@ Predicate parse_where(Parser& ps, int format) {
     ps.expect_sym(")");
     return pr;
   }
-  bool first = true;
+  bool first = pr.kind == Predicate::None;
   while (first || ps.accept_kw("and")) {
     first = false;
+    if (ps.is_kw("bam_region_filter")) {  // ... AND bam_region_filter(..): pushed down beside the flag conjuncts
+      ps.ident();
+      ps.expect_sym("(");
+      pr.region = ps.str();
+      while (ps.accept_sym(",")) ps.ident();
+      ps.expect_sym(")");
+      if (ps.accept_sym("=")) ps.expect_kw("true");
+      continue;
+    }
     if (ps.is_kw("cast")) {  // CAST(mapping_quality AS INT) >= q
       ps.ident(); ps.expect_sym("("); ps.ident(); ps.expect_kw("as"); ps.ident(); ps.expect_sym(")");
       const std::string op = ps.peek().text; ps.p++;
       const int q = atoi(ps.number().c_str());
       if (op == ">=") pr.mapq_min = q; else if (op == ">") pr.mapq_min = q + 1; else throw Err("only >= / > on CAST(mapping_quality AS INT)");
       pr.kind = Predicate::FlagMapq;
+      pr.flags = true;
       continue;
     }
     const std::string col = lower(ps.ident());
@@ -382,6 +404,7 @@ Predicate parse_where(Parser& ps, int format) {
     } else if (col == "flag") {  // flag & M = V
       ps.expect_sym("&"); pr.flag_mask = atoi(ps.number().c_str()); ps.expect_sym("="); pr.flag_value = atoi(ps.number().c_str());
       pr.kind = Predicate::FlagMapq;
+      pr.flags = true;
     } else if (col == "info" || col.rfind("info.", 0) == 0) {  // info."AF" <op> lit
       if (col.size() > 5) pr.info_field = col.substr(5);  // unquoted identifiers fold to lower case, as in DataFusion
       else { ps.accept_sym("."); pr.info_field = ps.ident(); }
@@ -391,6 +414,10 @@ Predicate parse_where(Parser& ps, int format) {
     } else {
       throw Err("unsupported predicate column '" + col + "' for this build (the fused shapes are listed in --help)");
     }
+  }
+  if (!pr.region.empty()) {  // a pushed region with further conjuncts: only the flag / mapping_quality ones go into the scan with it
+    if (pr.kind != Predicate::FlagMapq && pr.kind != Predicate::PushedRegion) throw Err("a region filter is ANDed with flag & M = V and CAST(mapping_quality AS INT) >= q only");
+    pr.kind = Predicate::PushedRegion;
   }
   (void)format;
   return pr;
@@ -671,6 +698,7 @@ void exec_select(Session& se, Parser& ps) {
       int32_t rid = -1;
       ck(nullptr, exon_hip_scan_dictionary_intern(g.s, 2, name, &rid));
       if (rid < 0) continue;  // the reference is not in this file's header
+      push_flags(g.s, &pr);  // (K6 then counts the rows the scan keeps)
       StreamGuard sg;
       exon_hip_plan_desc d; memset(&d, 0, sizeof d);
       d.kind = EXON_HIP_PLAN_OVERLAP_COUNT; d.region_chrom_id = rid; d.region_start = a; d.region_end = b;
@@ -713,7 +741,11 @@ void exec_select(Session& se, Parser& ps) {
   }
   if (count_only && (pr.kind == Predicate::None || pr.kind == Predicate::PushedRegion)) {
     // config-1 plumbing / pushed-down region: the decoder's per-record filter is the only filter
-    print_table({"count(*)"}, {{std::to_string(count_rows(src, pr.region))}}, se.quiet);
+    print_table({"count(*)"}, {{std::to_string(count_rows(src, pr.region, &pr))}}, se.quiet);
+    return;
+  }
+  if (count_only && pr.kind == Predicate::FlagMapq) {  // WHERE flag & M = V [AND CAST(mapping_quality AS INT) >= q] without GROUP BY: the scan's own filter
+    print_table({"count(*)"}, {{std::to_string(count_rows(src, "", &pr))}}, se.quiet);
     return;
   }
   if (count_only && pr.kind == Predicate::Region && (src.format == EXON_HIP_FORMAT_VCF || src.format == EXON_HIP_FORMAT_BCF)) {  // K2
@@ -965,6 +997,7 @@ int main(int argc, char** argv) {
              "             fastq_read_stats('<path>')\n"
              "  queries:   SELECT COUNT(*) FROM <src> [WHERE chrom = 'c' AND pos >= a AND pos <= b | vcf_region_filter('r', chrom) | bam_region_filter('r', reference, start, end)\n"
              "             | gff_region_filter('r', seqname[, start])]\n"
+             "             SELECT COUNT(*) FROM <bam|sam> WHERE [bam_region_filter('r', reference, start, end) AND] flag & M = V [AND CAST(mapping_quality AS INT) >= q]\n"
              "             SELECT reference, COUNT(*) FROM <bam> WHERE flag & M = V AND CAST(mapping_quality AS INT) >= q GROUP BY reference\n"
              "             SET exon.vcf_parse_info = true; SELECT filter, AVG(qual), COUNT(*) FROM <vcf> WHERE info.\"AF\" > 0.01 GROUP BY filter\n"
              "             SELECT filter, MIN(qual), MAX(qual), COUNT(*) FROM <vcf> WHERE info.\"AF\" > 0.01 GROUP BY filter   (also MIN / MAX(info.\"DP\");\n"

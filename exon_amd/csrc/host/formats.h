@@ -906,10 +906,45 @@ class VCFBatchReader : public BatchReader {
 // ======================================================================================================
 // BAM
 // ======================================================================================================
+// The pushed-down flag / mapping-quality predicate of BAM and SAM scans (exon_hip_scan_set_flag_predicate): K3's row predicate
+// (udfs/sam/samflags.rs:26-47 over the flag bits), as the host readers and the device mask (k_flag_mapq_mask) both evaluate it.
+// DECISION: mapq_min < 0 is "no conjunct on mapping_quality" (`WHERE flag & 4 = 0` has none); a NULL mapping_quality (255) never
+// passes a mapq_min >= 0, the FilterExec rule.  A value with bits outside the mask, or a mapq_min above 255, keeps no row.
+struct FlagPredicate {
+  bool active = false;
+  int32_t mask = 0, value = 0, mapq_min = -1;
+  bool hit(int32_t flag, int mapq) const { return (flag & mask) == value && (mapq_min < 0 || (mapq != 255 && mapq >= mapq_min)); }
+};
+// a BAM record's fixed fields (the bytes behind block_size, at least 32 of them): mapq is byte 9, flag bytes 14-15
+inline bool bam_flag_hit(const uint8_t* rec, const FlagPredicate& fp) {
+  uint16_t flag;
+  memcpy(&flag, rec + 14, 2);
+  return fp.hit((int32_t)flag, rec[9]);
+}
+// a SAM line's FLAG (field 2) and MAPQ (field 5).  A field the device parser would not take for a number -- empty, a byte that is no
+// digit, a FLAG above 0xFFFF, a MAPQ above 255 -- lets the record THROUGH: the builder then does with it what it does without a
+// predicate (nothing is decided and nothing thrown here).
+inline bool sam_flag_hit(const char* flag, size_t nflag, const char* mapq, size_t nmapq, const FlagPredicate& fp) {
+  auto number = [](const char* p, size_t n, int64_t max, int64_t* out) {
+    if (n == 0 || n > 9) return false;
+    int64_t v = 0;
+    for (size_t i = 0; i < n; ++i) {
+      if (p[i] < '0' || p[i] > '9') return false;
+      v = v * 10 + (p[i] - '0');
+    }
+    *out = v;
+    return v <= max;
+  };
+  int64_t f = 0, q = 0;
+  if (!number(flag, nflag, 0xFFFF, &f) || !number(mapq, nmapq, 255, &q)) return true;
+  return fp.hit((int32_t)f, (int)q);
+}
+
 struct BAMConfig {
   int64_t batch_size = DEFAULT_BATCH_SIZE;
   int threads = 0;  // BGZF inflate threads (0 = all host cores)
   RegionFilter filter;  // bam_region_filter: SemiLazyRecord::intersects
+  FlagPredicate flags;  // ANDed with `filter`; like it the READER'S filter: dropped rows are not built
   uint64_t projection = 0;  // EXON_HIP_PROJECT_BAM_*: name / cigar / sequence / quality_scores behind the default columns
 };
 
@@ -1111,6 +1146,7 @@ class BAMBatchReader : public BatchReader {
         const Region& rg = cfg_.filter.region;
         if (!(ref_id == region_ref_id_ && s <= rg.end && rg.start <= e)) continue;
       }
+      if (cfg_.flags.active && !bam_flag_hit(rec.data(), cfg_.flags)) continue;
       b.append((int32_t)flag, ref_id, pos, mapq, ref_len);
       b.append_text(rec.data(), rec.size());
     }
@@ -1248,6 +1284,7 @@ class SAMBatchReader : public BatchReader {
         const Region& rg = cfg_.filter.region;
         if (!(ref_id == region_ref_id_ && pos1 <= rg.end && rg.start <= e)) continue;
       }
+      if (cfg_.flags.active && !sam_flag_hit(f[1], fl[1], f[4], fl[4], cfg_.flags)) continue;
       if (cfg_.projection) {
         if (nf < 11) throw std::runtime_error("SAM record has fewer than 11 fields");
         b.append_sam_text(f[0], fl[0], f[5], fl[5], f[9], fl[9], f[10], fl[10]);

@@ -113,7 +113,7 @@ int exon_text_gtf(exon_hip_ctx* ctx, void* stream, ExonTextScratch** scratch, co
 int exon_text_bed(exon_hip_ctx* ctx, void* stream, ExonTextScratch** scratch, const uint8_t* d_text, int64_t n_bytes, const uint32_t* d_name_off, const uint32_t* d_name_len,
                   const uint8_t* d_name_valid, int64_t n_rows, ExonTextColumns* out);
 void exon_text_scratch_destroy(ExonTextScratch* s);
-// take_rows.hip: the rows a pushed-down value predicate keeps, taken out of a slab's columns on the device (format-free: a fixed
+// take_rows.hip: the rows a pushed-down predicate (VCF value, BAM / SAM flag / mapping quality) keeps, taken out of a slab's columns on the device (format-free: a fixed
 // column is a width, a text column a tree of ExonTextNode kinds).  The scratch is made by the first exon_take_index and sized from
 // the inputs of every call; what a call returns lives until the same call on the next slab.
 struct ExonTakeScratch;
@@ -131,7 +131,7 @@ struct ExonTakeColumn {
   uint8_t* out_validity;
 };
 int exon_take_fixed(exon_hip_ctx* ctx, void* stream, ExonTakeScratch* scratch, ExonTakeColumn* cols, int n_cols);
-// the kept rows of every root of `in` (UTF8 and LIST nodes; STRUCT2 / INT64: EXON_HIP_EUNSUPPORTED) as columns of their own in `out`,
+// the kept rows of every root of `in` (UTF8 and LIST nodes, a LIST's INT64 item leaf; STRUCT2: EXON_HIP_EUNSUPPORTED) as columns of their own in `out`,
 // lengths and totals filled in from one readback
 int exon_text_take(exon_hip_ctx* ctx, void* stream, ExonTakeScratch* scratch, const ExonTextColumns& in, const uint32_t* d_rows, const unsigned* d_K, ExonTextColumns* out);
 // the parsers' own indexes the text columns are built from (valid until the next parse call)

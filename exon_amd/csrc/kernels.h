@@ -104,6 +104,12 @@ hipError_t launch_region_mask(hipStream_t s, bool range_form, const int32_t* id_
 hipError_t launch_value_mask(hipStream_t s, const void* x, const uint8_t* x_valid, bool x_is_int, double literal, int cmp_op, const uint8_t* region_mask,
                              const uint8_t* in_valid, int64_t n, uint8_t* out_valid, unsigned long long* n_pass);
 
+// pushed-down flag / mapping-quality predicate (BAM, SAM) as a row mask, launch_value_mask's contract: out_valid = in_valid AND
+// region_mask AND (flag & flag_mask) == flag_value AND (mapq_min < 0 OR (mapq valid AND mapq >= mapq_min)); *n_pass += rows that pass
+// the predicate and the region.  region_mask / in_valid / mapq_valid may be null (all ones); region_mask may be out_valid.
+hipError_t launch_flag_mapq_mask(hipStream_t s, const int32_t* flag, const uint8_t* mapq, const uint8_t* mapq_valid, int32_t flag_mask, int32_t flag_value,
+                                 int32_t mapq_min, const uint8_t* region_mask, const uint8_t* in_valid, int64_t n, uint8_t* out_valid, unsigned long long* n_pass);
+
 // out[v] = sum over ranks (rank order) of gathered[rank][v]; words [0, n_i64) int64, then n_f64 float64; the last n_max of the
 // int64 words fold by unsigned max instead (K8's extreme planes)
 hipError_t launch_fold_states(hipStream_t s, const void* gathered, int world, int64_t n_i64, int64_t n_f64, void* out, int64_t n_max = 0);

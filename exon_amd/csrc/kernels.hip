@@ -1526,6 +1526,54 @@ hipError_t launch_value_mask(hipStream_t s, const void* x, const uint8_t* x_vali
   return hipGetLastError();
 }
 
+// ------------------------------------------------------------------------------------------------
+// Pushed-down flag / mapping-quality predicate of BAM and SAM scans as a row mask (exon_hip_scan_set_flag_predicate), k_value_mask's
+// sibling with the same contract: one row per lane in whole waves, pass = K3's row predicate (udfs/sam/samflags.rs:26-47 over the
+// flag bits; a NULL mapping_quality never passes a conjunct on it) -- (flag & mask) == value AND (mapq_min < 0 OR (mapq valid AND
+// mapq >= mapq_min)) -- ANDed with the region's mask bit when the scan has a region too.  A ballot gives 8 bytes of bitmap per wave,
+// one atomic per workgroup adds the rows kept to *n_pass; out_valid = (first operand's validity) AND pass; region_mask may be
+// out_valid itself.  mapq_min < 0: no conjunct on mapping_quality (the column is not read).
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_flag_mapq_mask(const int32_t* __restrict__ flag, const uint8_t* __restrict__ mapq, const uint8_t* __restrict__ mapq_valid,
+                                                        const uint8_t* region_mask, const uint8_t* __restrict__ in_valid, int64_t n, int32_t flag_mask,
+                                                        int32_t flag_value, int32_t mapq_min, uint8_t* out_valid, unsigned long long* __restrict__ n_pass) {
+  const int lane = threadIdx.x & 63;
+  unsigned long long kept = 0;
+  const int64_t n64 = (n + 63) & ~(int64_t)63;  // whole waves: the ballot needs every lane
+  for (int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x; r < n64; r += (int64_t)gridDim.x * 256) {
+    bool pass = false, operand = false;
+    if (r < n) {
+      pass = (flag[r] & flag_mask) == flag_value && valid1(region_mask, r);
+      if (pass && mapq_min >= 0) pass = valid1(mapq_valid, r) && (int32_t)mapq[r] >= mapq_min;
+      operand = valid1(in_valid, r);
+    }
+    const unsigned long long hits = __ballot(pass);         // rows the scan emits
+    const unsigned long long m = __ballot(pass && operand);  // ... of which the plan's operand is valid
+    if (lane < 8) {
+      const int64_t r0 = r - lane + lane * 8;
+      if (r0 < n) out_valid[r0 >> 3] = (uint8_t)(m >> (lane * 8));
+    }
+    if (lane == 0) kept += (unsigned long long)__popcll(hits);
+  }
+  // one atomic per workgroup
+  __shared__ unsigned long long red[4];
+  if (lane == 0) red[threadIdx.x >> 6] = kept;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const unsigned long long t = red[0] + red[1] + red[2] + red[3];
+    if (t) atomicAdd(n_pass, t);
+  }
+}
+
+hipError_t launch_flag_mapq_mask(hipStream_t s, const int32_t* flag, const uint8_t* mapq, const uint8_t* mapq_valid, int32_t flag_mask, int32_t flag_value,
+                                 int32_t mapq_min, const uint8_t* region_mask, const uint8_t* in_valid, int64_t n, uint8_t* out_valid, unsigned long long* n_pass) {
+  if (n <= 0) return hipSuccess;
+  if (!flag || (mapq_min >= 0 && !mapq)) return hipErrorInvalidValue;
+  const unsigned grid = (unsigned)std::min<int64_t>((n + 255) / 256, 2048);
+  hipLaunchKernelGGL(k_flag_mapq_mask, dim3(grid), dim3(256), 0, s, flag, mapq, mapq_valid, region_mask, in_valid, n, flag_mask, flag_value, mapq_min, out_valid, n_pass);
+  return hipGetLastError();
+}
+
 // records [blocks][3 x RG] (kinds cnn, crow, sum over the first RG ids) ADDED into a state of NG > RG groups
 // ([cnn[NG]] [crow[NG]] | [sum[NG]]): the fold of the tiered kernel when tier 3 exists.  One thread per (kind, id),
 // blocks summed in order.  The state was zeroed (overwrite) or holds earlier launches; tier 3 has added to it already.

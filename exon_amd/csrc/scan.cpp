@@ -89,6 +89,9 @@ struct exon_hip_scan {
   int value_column = -1, value_op = 0;
   double value_literal = 0;
   ExonTakeScratch* take_scratch = nullptr;
+  // pushed-down flag / mapping-quality predicate (exon_hip_scan_set_flag_predicate; BAM, SAM): the host reader's filter
+  // (BAMConfig::flags) and, on the GPU decode path, k_flag_mapq_mask in k_value_mask's place
+  exon::FlagPredicate flags;
   // exon_hip_scan_export_stats: written by the exporter's producer thread, read when the scan has ended
   std::atomic<int64_t> stat_slabs{0}, stat_compacted{0}, stat_d2h{0};
 
@@ -396,7 +399,13 @@ static std::unique_ptr<exon::BatchReader> open_reader(const exon_hip_scan& s, De
   exon::BAMConfig ac;
   ac.batch_size = bs;
   ac.filter = rf;
+  ac.flags = s.flags;
   ac.projection = s.opt.projection;
+  // (set after the scan was opened: exon_hip_scan_set_flag_predicate re-opens the reader)
+  auto flagged = [&](exon::BAMConfig cfg) {
+    cfg.flags = s.flags;
+    return cfg;
+  };
   switch (s.format) {
     case EXON_HIP_FORMAT_VCF: {
       vc.reference_tail_quirk = reference_tail_quirk(rf);
@@ -406,8 +415,8 @@ static std::unique_ptr<exon::BatchReader> open_reader(const exon_hip_scan& s, De
       return std::unique_ptr<exon::BatchReader>(new exon::VCFBatchReader(s.path, c, cfg));
     }
     case EXON_HIP_FORMAT_BCF: return std::unique_ptr<exon::BatchReader>(new exon::BCFBatchReader(s.path, config(s.bcf(), vc)));
-    case EXON_HIP_FORMAT_BAM: return std::unique_ptr<exon::BatchReader>(new exon::BAMBatchReader(s.path, config(s.bam(), ac)));
-    case EXON_HIP_FORMAT_SAM: return std::unique_ptr<exon::BatchReader>(new exon::SAMBatchReader(s.path, c, config(s.sam(), ac)));
+    case EXON_HIP_FORMAT_BAM: return std::unique_ptr<exon::BatchReader>(new exon::BAMBatchReader(s.path, flagged(config(s.bam(), ac))));
+    case EXON_HIP_FORMAT_SAM: return std::unique_ptr<exon::BatchReader>(new exon::SAMBatchReader(s.path, c, flagged(config(s.sam(), ac))));
     case EXON_HIP_FORMAT_CRAM: return std::unique_ptr<exon::BatchReader>(new exon::CRAMBatchReader(s.path, ac));  // (host decoder only)
     case EXON_HIP_FORMAT_FASTQ: {
       exon::FASTQConfig fresh;
@@ -720,6 +729,26 @@ int exon_hip_scan_set_predicate(exon_hip_scan* s, int32_t column, int32_t cmp_op
   s->value_column = column;
   s->value_op = cmp_op;
   s->value_literal = literal;
+  return EXON_HIP_OK;
+}
+
+int exon_hip_scan_set_flag_predicate(exon_hip_scan* s, int32_t flag_mask, int32_t flag_value, int32_t mapq_min) {
+  if (!s) return fail(nullptr, EXON_HIP_EINVAL, "exon_hip_scan_set_flag_predicate: NULL argument");
+  if (s->format != EXON_HIP_FORMAT_BAM && s->format != EXON_HIP_FORMAT_SAM)
+    return fail(nullptr, EXON_HIP_EUNSUPPORTED, "exon_hip_scan_set_flag_predicate: a flag / mapping_quality predicate is pushed into BAM and SAM scans; filter this format's batches above the scan");
+  if (s->exporter || s->rows != 0)
+    return fail(nullptr, EXON_HIP_ESTATE, "exon_hip_scan_set_flag_predicate: the scan %s already; set the predicate right after exon_hip_scan_open", s->exporter ? "is bound to a context" : "has been read from");
+  const exon::FlagPredicate before = s->flags;
+  s->flags.active = true;
+  s->flags.mask = flag_mask;
+  s->flags.value = flag_value;
+  s->flags.mapq_min = mapq_min < 0 ? -1 : mapq_min;
+  try {  // the reader starts over with the predicate in its config (nothing has been read: the header again, that is all)
+    s->reader = open_reader(*s, s->gpu_parse ? Decode::Device : Decode::Host);
+  } catch (const std::exception& e) {
+    s->flags = before;
+    return fail(nullptr, EXON_HIP_EINVAL, "%s", e.what());
+  }
   return EXON_HIP_OK;
 }
 
@@ -2183,10 +2212,10 @@ static int export_slab(exon_hip_scan* scan, const exon_hip_column* sc, int64_t n
   // unfiltered slab; rows kept here and there are gathered from the whole slab.
   std::vector<uint8_t> hmask;
   std::vector<std::pair<int64_t, int64_t>> runs;  // the runs of rows that go out as views (without a mask: the whole slab); empty: gathered
-  // A pushed-down value predicate keeps rows here and there: they are taken out of every column ON THE DEVICE (take_rows.hip) and go
+  // A pushed-down value predicate (VCF) or flag / mapping-quality predicate (BAM, SAM) keeps rows here and there: they are taken out of every column ON THE DEVICE (take_rows.hip) and go
   // out as one run of views, (0, K) of the taken columns -- no mask comes back, nothing is gathered on the host.  (A region alone
   // keeps today's paths below, scattered survivors included.)
-  const bool compact = row_mask && scan->value.active;
+  const bool compact = row_mask && (scan->value.active || scan->flags.active);
   const uint32_t* d_rows = nullptr;
   const unsigned* d_K = nullptr;
   scan->stat_slabs += 1;
@@ -2712,8 +2741,10 @@ static int consume_text_gpu(exon_hip_stream* st, exon_hip_scan* scan, int64_t* r
   // ---- the pushed-down value predicate (VCF text): a second mask kernel, ANDed with the region's; the count of rows kept is ITS count
   // then (word 0; the region's own count goes to word 1 and is not read)
   const bool valued = scan->value.active && scan->vcf();
+  // ---- the pushed-down flag / mapping-quality predicate (BAM, SAM): k_flag_mapq_mask in the value mask's place, the same two words
+  const bool flagged = scan->flags.active && (scan->bam() || scan->sam());
   if (filtered) region_target(scan, &rg_id, &rg_a, &rg_b, &rg_range);
-  if (filtered || valued) {
+  if (filtered || valued || flagged) {
     if (!scan->d_region_pass) HIP_TRY(ctx, hipMalloc((void**)&scan->d_region_pass, 16));
     HIP_TRY(ctx, hipMemsetAsync(scan->d_region_pass, 0, 16, hs));
   }
@@ -2807,7 +2838,7 @@ static int consume_text_gpu(exon_hip_stream* st, exon_hip_scan* scan, int64_t* r
         const int64_t n_rows = p.n_rows;
         for (auto& c : p.sc) c.length = n_rows;
         const uint8_t* row_mask = nullptr;
-        if (filtered || valued) {
+        if (filtered || valued || flagged) {
           // the per-record interval hit and / or value comparison, on the device: mask = (first operand's validity) AND hit
           const size_t need = (size_t)(n_rows + 7) / 8 + 64;
           if (scan->region_mask_cap < need) {
@@ -2822,14 +2853,18 @@ static int consume_text_gpu(exon_hip_stream* st, exon_hip_scan* scan, int64_t* r
           const int first = exon_hip_stream_plan_first_column(st);
           const uint8_t* in_valid = first >= 0 && first < 4 + EXON_HIP_MAX_INFO_FIELDS ? p.sc[first].validity : nullptr;
           if (filtered)  // (with a value predicate behind it: the bare hits, the plan's operand joins in the second kernel)
-            HIP_TRY(ctx, exon::launch_region_mask(hs, rg_range, p.id_col, p.id_valid, p.c_start, p.c_end, p.pos_valid, valued ? nullptr : in_valid, n_rows, rg_id, rg_a,
-                                                  rg_b, scan->d_region_mask, scan->d_region_pass + (valued ? 1 : 0)));
+            HIP_TRY(ctx, exon::launch_region_mask(hs, rg_range, p.id_col, p.id_valid, p.c_start, p.c_end, p.pos_valid, valued || flagged ? nullptr : in_valid, n_rows, rg_id, rg_a,
+                                                  rg_b, scan->d_region_mask, scan->d_region_pass + (valued || flagged ? 1 : 0)));
           if (valued) {
             const exon_hip_column& x = p.sc[scan->value_column];
             if (!x.values) return fail(ctx, EXON_HIP_ESTATE, "value predicate: the device parser did not build column %d", scan->value_column);
             HIP_TRY(ctx, exon::launch_value_mask(hs, x.values, x.validity, scan->value.is_int, scan->value_literal, scan->value_op, filtered ? scan->d_region_mask : nullptr,
                                                  in_valid, n_rows, scan->d_region_mask, scan->d_region_pass));
           }
+          if (flagged)  // (BAM / SAM: column 0 flag:i32, column 1 mapq:u8 and its validity, as the device parsers write them)
+            HIP_TRY(ctx, exon::launch_flag_mapq_mask(hs, static_cast<const int32_t*>(p.sc[0].values), static_cast<const uint8_t*>(p.sc[1].values), p.sc[1].validity, scan->flags.mask,
+                                                     scan->flags.value, scan->flags.mapq_min, filtered ? scan->d_region_mask : nullptr, in_valid, n_rows, scan->d_region_mask,
+                                                     scan->d_region_pass));
           row_mask = scan->d_region_mask;
         }
         // (BED: of its projection bits only `name` is a text column; the others are fixed-width or NULL)
@@ -2873,7 +2908,7 @@ static int consume_text_gpu(exon_hip_stream* st, exon_hip_scan* scan, int64_t* r
     fprintf(stderr, "[exon-hip pipe] setup %.1f ms, loop %.1f ms (%zu source(s); slabs: wait+H2D+inflate %.1f, parse %.1f, other %.1f; file reader busy %.1f)\n",
             (t_init - t_begin) * 1e3, (t_loop - t_init) * 1e3, n_sources, t_next * 1e3, t_parse * 1e3, (t_loop - t_init - t_next - t_parse) * 1e3, t_reader * 1e3);
   }
-  if (rc == EXON_HIP_OK && (filtered || valued)) {  // the scan emitted the rows that hit the region and pass the predicate
+  if (rc == EXON_HIP_OK && (filtered || valued || flagged)) {  // the scan emitted the rows that hit the region and pass the predicate
     unsigned long long kept = 0;
     HIP_TRY(ctx, hipMemcpy(&kept, scan->d_region_pass, 8, hipMemcpyDeviceToHost));
     total = (int64_t)kept;

@@ -1,12 +1,14 @@
-// take_rows.hip -- the rows a pushed-down value predicate keeps, taken out of a slab's columns ON THE DEVICE, so that only they cross
+// take_rows.hip -- the rows a pushed-down predicate (a VCF value comparison, a BAM / SAM flag / mapping-quality test) keeps, taken out of a slab's columns ON THE DEVICE, so that only they cross
 // PCIe and the batches still go out as views (scan.cpp: export_slab).  Free of formats: a fixed-width column is a width (SlabLayout),
 // a text column a tree of ExonTextNode kinds (host/text_nodes.h); the host's row-by-row counterpart is slab_gather / text_gather.
 //   exon_take_index   row mask -> rows[K], the kept row indices in ascending order (k_mask_block_counts, the shared block scan of
 //                     list_kernels.h, k_mask_rows_fill); K stays on the device for everything behind it and comes back once
 //   exon_take_fixed   out[i] = in[rows[i]] for widths 1, 4, 8 (k_take_fixed); validity and Flag bitmaps bit by bit (k_take_bits)
 //   exon_text_take    one recursion over the node tree, the mirror of text_gather: UTF8 = lengths of the kept rows, scanned into new
-//                     offsets, spans copied by copy_run; LIST = item counts scanned into new offsets and the kept rows' item ranges
-//                     expanded into an ascending item-index list, which is the child's `rows`.  Every count of a level below the
+//                     offsets, spans copied by copy_run (a thread to a row, or 16 lanes to a row where rows are long); LIST = item counts scanned into new offsets and the kept rows' item ranges
+//                     expanded into an ascending item-index list, which is the child's `rows`.  A LIST over an INT64 leaf (BAM / SAM
+//                     quality_score, List<Int64>) builds no such list: its items are whole spans of 8-byte values, which
+//                     k_take_item_spans copies span by span, 16 lanes to a row (128 bytes a step).  Every count of a level below the
 //                     rows is known on the device only: the kernels are launched over the INPUT's capacity and read their count
 //                     from the device (as launch_list_scan takes n_rows_p); the totals come back in one small copy at the end.
 // Every write is bounded by the destination's capacity and every index is checked against its source's length before use -- never
@@ -24,6 +26,7 @@ namespace {
 
 constexpr int TAKE_TPB = LIST_TPB;  // 256: four waves, the block the shared scan's in-block prefix (list_first_item) is written for
 constexpr int TAKE_RES_WORDS = 2 * ExonTextColumns::MAX_NODES + 2;
+constexpr int64_t TAKE_WIDE_MEAN_BYTES = 32;  // a UTF8 column whose rows are this long on average is copied 16 lanes to a row (k_take_spans_wide)
 
 // bit r of a bitmap
 __device__ __forceinline__ bool bit_of(const uint8_t* __restrict__ bm, unsigned r) { return (bm[r >> 3] >> (r & 7)) & 1; }
@@ -120,6 +123,23 @@ __global__ __launch_bounds__(TAKE_TPB) void k_take_spans(const uint8_t* __restri
     if ((uint64_t)a + c <= in_bytes && (uint64_t)o + c <= out_cap) copy_run(out + o, in + a, c);
   }
 }
+// the same for a column of LONG rows (BAM / SAM `sequence`: a read's 100-250 bases), k_take_item_spans' shape over bytes: 16 lanes to
+// a kept row, lane l moves bytes [8 l, 8 l + 8) of every 128.  exon_text_take picks it by the input's mean row length
+// (TAKE_WIDE_MEAN_BYTES); short rows -- every VCF column, names, CIGARs -- keep k_take_spans, where a row is one or two 8-byte steps
+__global__ __launch_bounds__(TAKE_TPB) void k_take_spans_wide(const uint8_t* __restrict__ in, unsigned in_bytes, const int32_t* __restrict__ off,
+                                                              const uint32_t* __restrict__ rows, const unsigned* __restrict__ n_p, unsigned cap, unsigned n_in,
+                                                              const int32_t* __restrict__ new_off, uint8_t* __restrict__ out, unsigned out_cap) {
+  constexpr unsigned GROUP = 16, GROUPS = TAKE_TPB / GROUP;
+  const unsigned n = min(*n_p, cap);
+  const unsigned l = threadIdx.x & (GROUP - 1);
+  for (unsigned i = blockIdx.x * GROUPS + threadIdx.x / GROUP; i < n; i += gridDim.x * GROUPS) {
+    const unsigned r = rows[i];
+    if (r >= n_in) continue;
+    const unsigned a = (unsigned)off[r], o = (unsigned)new_off[i], c = (unsigned)(new_off[i + 1] - new_off[i]);
+    if ((uint64_t)a + c > in_bytes || (uint64_t)o + c > out_cap) continue;
+    for (unsigned j = l * 8; j < c; j += GROUP * 8) copy_run(out + o + j, in + a + j, min(8u, c - j));
+  }
+}
 // the kept rows' item ranges as an ascending list of item indices: the child's `rows`
 __global__ __launch_bounds__(TAKE_TPB) void k_take_items(const int32_t* __restrict__ off, const uint32_t* __restrict__ rows, const unsigned* __restrict__ n_p, unsigned cap,
                                                          unsigned n_in, const int32_t* __restrict__ new_off, unsigned n_items_in, uint32_t* __restrict__ item_rows) {
@@ -130,6 +150,24 @@ __global__ __launch_bounds__(TAKE_TPB) void k_take_items(const int32_t* __restri
     const unsigned a = (unsigned)off[r], o = (unsigned)new_off[i], c = (unsigned)(new_off[i + 1] - new_off[i]);
     for (unsigned j = 0; j < c; ++j)
       if (a + j < n_items_in && o + j < n_items_in) item_rows[o + j] = a + j;  // (kept items are no more than the items there are)
+  }
+}
+
+// the kept rows' item spans of an INT64 leaf back to back in `out`: [off[r], off[r + 1]) -> [new_off[i], new_off[i + 1]).  A group of 16
+// lanes (one DPP row) owns a kept row and lane l moves items l, l + 16, ...: a group's step is one 128-byte line on either side, where
+// one thread per row would walk a read's 100-250 qualities alone.  n_items_in: the items `in` holds; out_cap: the items `out` holds
+__global__ __launch_bounds__(TAKE_TPB) void k_take_item_spans(const uint64_t* __restrict__ in, unsigned n_items_in, const int32_t* __restrict__ off,
+                                                              const uint32_t* __restrict__ rows, const unsigned* __restrict__ n_p, unsigned cap, unsigned n_in,
+                                                              const int32_t* __restrict__ new_off, uint64_t* __restrict__ out, unsigned out_cap) {
+  constexpr unsigned GROUP = 16, GROUPS = TAKE_TPB / GROUP;
+  const unsigned n = min(*n_p, cap);
+  const unsigned l = threadIdx.x & (GROUP - 1);
+  for (unsigned i = blockIdx.x * GROUPS + threadIdx.x / GROUP; i < n; i += gridDim.x * GROUPS) {
+    const unsigned r = rows[i];
+    if (r >= n_in) continue;
+    const unsigned a = (unsigned)off[r], o = (unsigned)new_off[i], c = (unsigned)(new_off[i + 1] - new_off[i]);
+    if ((uint64_t)a + c > n_items_in || (uint64_t)o + c > out_cap) continue;
+    for (unsigned j = l; j < c; j += GROUP) out[o + j] = in[a + j];
   }
 }
 
@@ -286,11 +324,12 @@ size_t text_need(const ExonTextColumns& in, int i, size_t cap) {
   if (nd.kind == ExonTextNode::UTF8 && nd.offsets) need += TakeBuf::part((size_t)nd.n_values + 64);
   if (nd.kind == ExonTextNode::LIST && nd.offsets && nd.kid[0] >= 0) {
     const size_t items = (size_t)in.nodes[nd.kid[0]].length;
-    need += TakeBuf::part((items + 64) * 4) + text_need(in, nd.kid[0], items);
+    if (in.nodes[nd.kid[0]].kind == ExonTextNode::INT64) need += TakeBuf::part((items + 8) * 8);  // the kept spans of 8-byte items; no index list
+    else need += TakeBuf::part((items + 64) * 4) + text_need(in, nd.kid[0], items);
   }
   return need;
 }
-// node i of `in` (UTF8 or LIST: exon_text_take has looked) at rows[0 .. *d_n) (at most `cap` of them; the node's own length is what the rows index) -> its node in `out`
+// node i of `in` (UTF8 or LIST, an INT64 leaf is taken by its LIST: exon_text_take has looked) at rows[0 .. *d_n) (at most `cap` of them; the node's own length is what the rows index) -> its node in `out`
 int take_node(TextTake& t, int i, const uint32_t* rows, const unsigned* d_n, int n_word, unsigned cap) {
   const ExonTextNode& nd = t.in->nodes[i];
   const unsigned n_in = (unsigned)nd.length;
@@ -326,11 +365,28 @@ int take_node(TextTake& t, int i, const uint32_t* rows, const unsigned* d_n, int
       const unsigned in_bytes = (unsigned)nd.n_values;
       uint8_t* v = t.s->text.take<uint8_t>((size_t)in_bytes + 64);
       if (!v) return short_of(t);
-      hipLaunchKernelGGL(k_take_spans, dim3(grid), dim3(TAKE_TPB), 0, t.hs, static_cast<const uint8_t*>(nd.values), in_bytes, nd.offsets, rows, d_n, cap, n_in, new_off, v, in_bytes);
+      if (nd.n_values >= TAKE_WIDE_MEAN_BYTES * nd.length)
+        hipLaunchKernelGGL(k_take_spans_wide, dim3(grid_of((size_t)cap * 16)), dim3(TAKE_TPB), 0, t.hs, static_cast<const uint8_t*>(nd.values), in_bytes, nd.offsets, rows, d_n, cap, n_in,
+                           new_off, v, in_bytes);
+      else
+        hipLaunchKernelGGL(k_take_spans, dim3(grid), dim3(TAKE_TPB), 0, t.hs, static_cast<const uint8_t*>(nd.values), in_bytes, nd.offsets, rows, d_n, cap, n_in, new_off, v, in_bytes);
       o.values = v;
     }
   } else if (nd.kid[0] >= 0) {
-    if (nd.offsets) {  // the kept rows' items, by index, are the child's rows
+    if (nd.offsets && t.in->nodes[nd.kid[0]].kind == ExonTextNode::INT64) {  // List<Int64>: the kept rows' spans of 8-byte items, copied as spans
+      const ExonTextNode& leaf = t.in->nodes[nd.kid[0]];
+      const unsigned items_in = (unsigned)leaf.length;
+      uint64_t* v = t.s->text.take<uint64_t>(((size_t)items_in + 8) * 8);
+      if (!v) return short_of(t);
+      if (leaf.values)
+        hipLaunchKernelGGL(k_take_item_spans, dim3(grid_of((size_t)cap * 16)), dim3(TAKE_TPB), 0, t.hs, static_cast<const uint64_t*>(leaf.values), items_in, nd.offsets, rows, d_n, cap,
+                           n_in, new_off, v, items_in);
+      ExonTextNode ol = leaf;
+      ol.values = v;
+      ol.length = ol.n_values = 0;
+      kid = t.out->add(ol);
+      if (kid >= 0) t.len_word[kid] = t.val_word[kid] = items_word;  // (an INT64 node's n_values is its length)
+    } else if (nd.offsets) {  // the kept rows' items, by index, are the child's rows
       const unsigned items_in = (unsigned)t.in->nodes[nd.kid[0]].length;
       uint32_t* item_rows = t.s->text.take<uint32_t>(((size_t)items_in + 64) * 4);
       if (!item_rows) return short_of(t);
@@ -357,9 +413,16 @@ int exon_text_take(exon_hip_ctx* ctx, void* stream, ExonTakeScratch* s, const Ex
   *out = ExonTextColumns();
   if (!s || !s->h_res) return fail(ctx, EXON_HIP_ESTATE, "exon_text_take before exon_take_index");
   if (in.n_roots == 0) return EXON_HIP_OK;
-  for (int i = 0; i < in.n_nodes; ++i)  // the kinds VCF has none of arrive with the format that needs them
-    if (in.nodes[i].kind != ExonTextNode::UTF8 && in.nodes[i].kind != ExonTextNode::LIST)
-      return fail(ctx, EXON_HIP_EUNSUPPORTED, "take-rows of a %s column on the device", in.nodes[i].kind == ExonTextNode::STRUCT2 ? "struct (map)" : "List<Int64>");
+  for (int i = 0; i < in.n_nodes; ++i)  // STRUCT2: no format with a map has a predicate
+    if (in.nodes[i].kind == ExonTextNode::STRUCT2) return fail(ctx, EXON_HIP_EUNSUPPORTED, "take-rows of a struct (map) column on the device");
+  for (int i = 0; i < in.n_nodes; ++i) {  // an INT64 node is the item leaf of a LIST (BAM / SAM quality_score), never a column or a UTF8 node's child
+    const ExonTextNode& nd = in.nodes[i];
+    const bool int64_kid = nd.kid[0] >= 0 && nd.kid[0] < in.n_nodes && in.nodes[nd.kid[0]].kind == ExonTextNode::INT64;
+    if (int64_kid && nd.kind != ExonTextNode::LIST) return fail(ctx, EXON_HIP_EUNSUPPORTED, "take-rows of an Int64 node that is no list's items");
+    if (nd.kind == ExonTextNode::INT64 && (nd.length < 0 || nd.length > (int64_t)0x7FFFFFFF)) return fail(ctx, EXON_HIP_EINVAL, "exon_text_take: %lld list items", (long long)nd.length);
+  }
+  for (int k = 0; k < in.n_roots; ++k)
+    if (in.nodes[in.roots[k]].kind == ExonTextNode::INT64) return fail(ctx, EXON_HIP_EUNSUPPORTED, "take-rows of a bare Int64 text column on the device");
   hipStream_t hs = pick_stream(ctx, stream);
   hipSetDevice(ctx->device);
   size_t need = TakeBuf::part(TAKE_RES_WORDS * 4);

@@ -1083,6 +1083,8 @@ void exon_text_scratch_destroy(ExonTextScratch* s) { delete s; }
 //                    length / 8 + 64 bytes: fits
 //   take   a UTF8 node's bytes: spans of the kept elements, disjoint parts of the input's n_values bytes, against n_values + 64: fits
 //   take   a LIST's item-index list: the kept rows' item ranges, disjoint ranges of the child's `length` items, against length + 64: fits
+//   take   a LIST's INT64 items (BAM / SAM quality_score; no index list): the kept rows' spans, disjoint ranges of the leaf's `length` 8-byte
+//                    items, against length + 8 items: fits
 //          No take buffer is "checked": a compacted buffer is never larger than its input.  The kernels bound every index and every
 //          write all the same.
 static int scratch_for(exon_hip_ctx* ctx, ExonTextScratch** sp, int64_t max_rows, int64_t max_bytes, TextLayout lay) {

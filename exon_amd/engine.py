@@ -458,8 +458,11 @@ class Scan:
                "gff": {"attributes": 256}, "gtf": {"attributes": 256}, "bed": L.PROJECT_BED}
 
     def __init__(self, path, fmt, compression=None, batch_size=0, info_field=None, region=None, use_index=False,
-                 gpu_parse=False, project=(), where=None):
-        """where: (column, op, literal), one comparison the scan evaluates itself (exon_hip_scan_set_predicate): `column` a scan column
+                 gpu_parse=False, project=(), where=None, where_flags=None):
+        """where_flags: (mask, value[, mapq_min]), the flag / mapping-quality predicate a BAM or SAM scan evaluates itself
+        (exon_hip_scan_set_flag_predicate): rows with (flag & mask) != value, or -- for a mapq_min >= 0 -- a NULL or smaller
+        mapping_quality, are not emitted (ANDed with `region`).
+        where: (column, op, literal), one comparison the scan evaluates itself (exon_hip_scan_set_predicate): `column` a scan column
         (VCF: 2 = qual, 4 + k = typed INFO field k of info_field; Float32, or Int32 values), `op` one of ">" ">=" "<" "<=" "=" "!=";
         rows whose column is NULL or fails are not emitted (ANDed with `region`).
         project: names of the reference's columns beyond the fused kernels' operands (EXON_HIP_PROJECT_*): VCF "id", "ref", "alt",
@@ -487,6 +490,12 @@ class Scan:
             except Exception:
                 self.close()
                 raise
+        if where_flags is not None:
+            try:
+                self.set_flag_predicate(*where_flags)
+            except Exception:
+                self.close()
+                raise
 
     WHERE_OPS = {">": 0, ">=": 1, "<": 2, "<=": 3, "=": 4, "!=": 5}
 
@@ -494,6 +503,12 @@ class Scan:
         """exon_hip_scan_set_predicate: before bind_ctx / the first batch / Stream.consume; a second call replaces the first.  `op` may
         be the C ABI's integer too."""
         self._check(self.lib.exon_hip_scan_set_predicate(self.h, column, self.WHERE_OPS[op] if isinstance(op, str) else op, float(literal)))
+        return self
+
+    def set_flag_predicate(self, mask, value, mapq_min=-1):
+        """exon_hip_scan_set_flag_predicate (BAM, SAM): before bind_ctx / the first batch / Stream.consume; a second call replaces the
+        first.  mapq_min < 0: no conjunct on mapping_quality."""
+        self._check(self.lib.exon_hip_scan_set_flag_predicate(self.h, int(mask), int(value), int(mapq_min)))
         return self
 
     def export_stats(self):

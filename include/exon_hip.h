@@ -642,6 +642,25 @@ int exon_hip_scan_bind_ctx(exon_hip_scan* scan, exon_hip_ctx* ctx);
  * second conjunct.  As with a region, a FILTER dictionary built on the device may hold values that only dropped rows carried:
  * they show up as groups with zero counts. */
 int exon_hip_scan_set_predicate(exon_hip_scan* scan, int32_t column, int32_t cmp_op, double literal);
+/* (additive; the ABI stays 5)
+ * The flag / mapping-quality predicate of alignment scans, evaluated by the scan itself: a row is emitted iff
+ *   (flag & flag_mask) == flag_value  AND  (mapq_min < 0  OR  (mapping_quality valid AND mapping_quality >= mapq_min))
+ * -- the row predicate of EXON_HIP_PLAN_FLAG_MAPQ_GROUP_COUNT (K3), i.e. the flag tests of udfs/sam/samflags.rs:26-47 and
+ * CAST(mapping_quality AS INT) >= q under FilterExec, where a NULL mapping_quality (255 in BAM and SAM) never passes.  The three
+ * operands are plain int32 as K3 takes them: a flag_value with bits outside flag_mask, or a mapq_min above 255, keeps no row and is
+ * no error.  DECISION: mapq_min < 0 means "no conjunct on mapping_quality" (`WHERE flag & 4 = 0` has none); K3's own plan field
+ * keeps its meaning.
+ * EXON_HIP_FORMAT_BAM and EXON_HIP_FORMAT_SAM (plain, gzip or BGZF) only, ANDed with `region`, with or without use_index; any other
+ * format, CRAM included, is EXON_HIP_EUNSUPPORTED (BAM has no EXON_HIP_REFERENCE_QUIRKS region path to refuse).  Call order as
+ * exon_hip_scan_set_predicate: after exon_hip_scan_open and before exon_hip_scan_bind_ctx / the first exon_hip_scan_next /
+ * exon_hip_stream_consume_scan (later: EXON_HIP_ESTATE); a second call replaces the first.  exon_hip_scan_set_predicate on a BAM or
+ * SAM scan stays EXON_HIP_EUNSUPPORTED.
+ * Like `region` this is the reader's own filter: dropped rows are not built, exon_hip_scan_rows counts the rows emitted, and a SAM
+ * FLAG / MAPQ field that is no number lets the record through to the builder.  Bound to a context, every slab is masked on the
+ * device, the kept rows of every column -- name, cigar, sequence and the List<Int64> quality_score included -- are taken there and
+ * only they are copied back (exon_hip_scan_export_stats).  A fused plan over such a scan sees the kept rows only: K3 gets a second
+ * conjunct, K6 / K7 count kept rows. */
+int exon_hip_scan_set_flag_predicate(exon_hip_scan* scan, int32_t flag_mask, int32_t flag_value, int32_t mapq_min);
 /* after the scan has ended: slabs exported by the GPU pipeline, how many of them went through the device take-rows step,
  * bytes copied device -> host for batches (mask / count words included). Any pointer may be NULL. */
 int exon_hip_scan_export_stats(exon_hip_scan* scan, int64_t* slabs, int64_t* compacted_slabs, int64_t* d2h_bytes);

@@ -169,6 +169,9 @@ extern "C" {
     /// one pushed-down comparison on a Float32 / Int32 value column of a VCF scan (EXON_HIP_GT .. EXON_HIP_NE), evaluated by the scan
     /// itself and ANDed with its region; call right after exon_hip_scan_open
     pub fn exon_hip_scan_set_predicate(scan: *mut exon_hip_scan, column: i32, cmp_op: i32, literal: f64) -> c_int;
+    /// the flag / mapping-quality predicate of a BAM or SAM scan, evaluated by the scan itself and ANDed with its region: a row is emitted
+    /// iff (flag & flag_mask) == flag_value and (mapq_min < 0 or mapping_quality is valid and >= mapq_min); call right after exon_hip_scan_open
+    pub fn exon_hip_scan_set_flag_predicate(scan: *mut exon_hip_scan, flag_mask: i32, flag_value: i32, mapq_min: i32) -> c_int;
     /// after the scan has ended: slabs the GPU pipeline exported, how many went through the device take-rows step, bytes copied back
     pub fn exon_hip_scan_export_stats(scan: *mut exon_hip_scan, slabs: *mut i64, compacted_slabs: *mut i64, d2h_bytes: *mut i64) -> c_int;
     pub fn exon_hip_scan_close(scan: *mut exon_hip_scan) -> c_int;
