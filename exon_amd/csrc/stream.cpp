@@ -31,6 +31,7 @@
 #include <vector>
 
 #include "host/arrow_build.h"
+#include "host/bitmap.h"
 #include "host/raw_batch.h"
 #include "internal.h"
 
@@ -290,31 +291,8 @@ class CopyPool {
 };
 }  // namespace
 
-// ---- bit utilities (Arrow LSB-first bitmaps) -------------------------------------------------------
-static void append_bits(uint8_t* dst, int64_t dst_off, const uint8_t* src, int64_t src_off, int64_t n) {
-  if (n <= 0) return;
-  if (src == nullptr) {  // all valid
-    int64_t i = 0;
-    while (i < n && ((dst_off + i) & 7)) {
-      dst[(dst_off + i) >> 3] |= (uint8_t)(1u << ((dst_off + i) & 7));
-      ++i;
-    }
-    const int64_t full = (n - i) / 8;
-    if (full > 0) memset(dst + ((dst_off + i) >> 3), 0xFF, (size_t)full);
-    i += full * 8;
-    for (; i < n; ++i) dst[(dst_off + i) >> 3] |= (uint8_t)(1u << ((dst_off + i) & 7));
-    return;
-  }
-  if (((dst_off | src_off) & 7) == 0) {
-    const int64_t full = n / 8;
-    memcpy(dst + (dst_off >> 3), src + (src_off >> 3), (size_t)full);
-    for (int64_t i = full * 8; i < n; ++i)
-      if ((src[(src_off + i) >> 3] >> ((src_off + i) & 7)) & 1) dst[(dst_off + i) >> 3] |= (uint8_t)(1u << ((dst_off + i) & 7));
-    return;
-  }
-  for (int64_t i = 0; i < n; ++i)
-    if ((src[(src_off + i) >> 3] >> ((src_off + i) & 7)) & 1) dst[(dst_off + i) >> 3] |= (uint8_t)(1u << ((dst_off + i) & 7));
-}
+// (Arrow LSB-first bitmaps: host/bitmap.h)
+using exon::append_bits;
 
 static double now_s() {
   struct timespec ts;
@@ -708,8 +686,12 @@ static int column_child(exon_hip_stream* st, const struct ArrowArray* batch, int
     return fail(st->ctx, EXON_HIP_EUNSUPPORTED, "column %d is a nested (list) column; the plan's operands are scalar columns", idx);
   const int need = st->plan->cols[c].utf8 ? 3 : 2;
   if (ch->n_buffers < need) return fail(st->ctx, EXON_HIP_EINVAL, "column %d has %lld buffers, expected %d", idx, (long long)ch->n_buffers, need);
+  if (batch->offset < 0 || batch->length < 0 || ch->offset < 0 || ch->length < 0)
+    return fail(st->ctx, EXON_HIP_EINVAL, "column %d: negative offset or length", idx);
   *eff_off = batch->offset + ch->offset;
-  if (ch->length + ch->offset < batch->offset + batch->length)
+  // (Arrow C Data Interface: a child's `length` counts from its own `offset`, and the struct's rows are the child's LOGICAL rows
+  //  [batch->offset, batch->offset + batch->length) -- the child's offset buys it nothing here)
+  if (ch->length < batch->offset + batch->length)
     return fail(st->ctx, EXON_HIP_EINVAL, "column %d shorter than the batch", idx);
   *child = ch;
   return EXON_HIP_OK;
@@ -717,8 +699,11 @@ static int column_child(exon_hip_stream* st, const struct ArrowArray* batch, int
 
 int exon_hip_stream_push(exon_hip_stream* st, struct ArrowArray* batch) {
   if (!st || !batch) return fail(st ? st->ctx : nullptr, EXON_HIP_EINVAL, "exon_hip_stream_push: NULL argument");
-  if (st->closed) return fail(st->ctx, EXON_HIP_ESTATE, "push after finish/close");
   if (!batch->release) return fail(st->ctx, EXON_HIP_EINVAL, "batch already released");
+  if (st->closed) {
+    batch->release(batch);  // moved all the same: a refused batch is released too
+    return fail(st->ctx, EXON_HIP_ESTATE, "push after finish/close");
+  }
   exon_hip_plan* p = st->plan;
   const int64_t rows = batch->length;
   int rc = EXON_HIP_OK;

@@ -1174,6 +1174,8 @@ class Stream:
         try:
             self.ctx._check(self.ctx.lib.exon_hip_stream_push(self.h, C.byref(arr)))
         finally:
+            if arr.release:  # (the library moves the batch whatever it returns; only a call it could not even look at leaves it here)
+                C.CFUNCTYPE(None, C.POINTER(L.ArrowArray))(arr.release)(C.byref(arr))
             if sch.release:
                 C.CFUNCTYPE(None, C.POINTER(L.ArrowSchema))(sch.release)(C.byref(sch))
 

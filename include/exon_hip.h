@@ -411,7 +411,10 @@ int exon_hip_rccl_comm_count(void* rccl_comm, int32_t* world, int32_t* rank);
  * device-resident partial state and pinned staging buffers. */
 int exon_hip_stream_open(exon_hip_plan* plan, int32_t partition, exon_hip_stream** out);
 /* Host Arrow struct batch (children = columns).  The batch is MOVED (Arrow C Data Interface: on return `batch->release` is
- * NULL and the stream owns the array): the library calls the array's release callback exactly once, after its buffers have
+ * NULL and the stream owns the array), WHATEVER the call returns: a batch that is refused (a finished stream, a column that is
+ * missing, nested, short of buffers or shorter than the batch, a failed flush) is released before the call returns with its
+ * error.  Only a NULL argument or a batch that is already released (release == NULL) leaves the struct untouched.  The
+ * library calls the array's release callback exactly once, after its buffers have
  * been copied -- for a batch of up to 131072 rows of fixed-width columns that may be AFTER this call returns: such batches are
  * held and copied together, by a pool of threads, when their staging slot is flushed (the next push that fills it, sync,
  * state, finish, reset or close).  Everything the array points to must therefore stay valid until the callback runs, as the
