@@ -148,6 +148,8 @@ class GzipStats(C.Structure):
 
 FORMATS = {"vcf": 1, "bam": 2, "fastq": 3, "fasta": 4, "sam": 5, "bcf": 6, "cram": 7, "gff": 8, "gtf": 9, "bed": 10}
 COMPRESSION = {"auto": 0, None: 0, "none": 1, "gzip": 2}
+# EXON_HIP_PROJECT_VCF_FORMATS_ON_DEVICE: a modifier of the VCF `formats` bit (16), not a column
+PROJECT_VCF_FORMATS_ON_DEVICE = 32
 # EXON_HIP_PROJECT_BED_*: bit k = column k of the reference's BED schema; n_fields = k is the mask of bits 3 .. k - 1
 PROJECT_BED = {"name": 1 << 3, "score": 1 << 4, "strand": 1 << 5, "thick_start": 1 << 6, "thick_end": 1 << 7, "color": 1 << 8,
                "block_count": 1 << 9, "block_sizes": 1 << 10, "block_starts": 1 << 11}
@@ -256,6 +258,8 @@ SIGNATURES = {
     "exon_hip_vcf_parser_set_null_key": (C.c_int, [_vp, _i32]),
     "exon_hip_vcf_parser_set_key_types": (C.c_int, [_vp, C.c_char_p, C.c_char_p, _i32]),
     "exon_hip_vcf_parser_info_text": (C.c_int, [_vp, _vp, C.POINTER(VCFInfoText)]),
+    "exon_hip_vcf_parser_set_format_key_types": (C.c_int, [_vp, C.c_char_p, C.c_char_p, _i32]),
+    "exon_hip_vcf_parser_formats_text": (C.c_int, [_vp, _vp, C.POINTER(VCFInfoText)]),
     "exon_hip_vcf_parser_destroy": (C.c_int, [_vp]),
     "exon_hip_qual_pos_hist_chunks": (C.c_int, [_vp, _vp, _colp, _i32, _vp, _i32, _vp]),
     "exon_hip_qual_pos_hist_views": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp]),

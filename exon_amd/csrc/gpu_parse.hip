@@ -799,12 +799,12 @@ struct exon_hip_vcf_parser {
   int32_t h_filter_stat = 0;                   // the FILTER dictionary's overflow flag after the last slab
   // the `info` text column (exon_hip_vcf_parser_set_key_types / _info_text): the header's key types on the device, the slab of
   // the last parse call as the caller passed it (last_rows < 0: none, or one with undecided rows) and the column's buffers
-  PoolBufs key_bufs;
-  ExonVcfKeyTable key_table{};
+  PoolBufs key_bufs, format_key_bufs;
+  ExonVcfKeyTable key_table{}, format_key_table{};  // the INFO keys' types; the FORMAT keys' (exon_hip_vcf_parser_set_format_key_types / _formats_text)
   const uint8_t* last_text = nullptr;
   int64_t last_bytes = 0, last_rows = -1;
   ExonTextScratch* info_scratch = nullptr;
-  explicit exon_hip_vcf_parser(exon_hip_ctx* c) : ctx(c), bufs(c), key_bufs(c) {}
+  explicit exon_hip_vcf_parser(exon_hip_ctx* c) : ctx(c), bufs(c), key_bufs(c), format_key_bufs(c) {}
   ~exon_hip_vcf_parser() { exon_text_scratch_destroy(info_scratch); }
 };
 
@@ -986,7 +986,14 @@ int exon_hip_vcf_parser_set_key_types(exon_hip_vcf_parser* p, const char* packed
   if (!p || n < 0 || (n > 0 && (!packed_keys || !kinds))) return fail(p ? p->ctx : nullptr, EXON_HIP_EINVAL, "exon_hip_vcf_parser_set_key_types: bad argument");
   for (int32_t k = 0; k < n; ++k)
     if (!strchr("ifbcs", kinds[k]) || !kinds[k]) return fail(p->ctx, EXON_HIP_EINVAL, "exon_hip_vcf_parser_set_key_types: kind '%c' of key %d (i f b c s)", kinds[k], k);
-  return exon_vcf_key_table_build(p->ctx, &p->key_bufs, packed_keys, kinds, n, &p->key_table);
+  return exon_vcf_key_table_build(p->ctx, &p->key_bufs, packed_keys, kinds, n, ExonVcfKeySeed::Info, &p->key_table);
+}
+
+int exon_hip_vcf_parser_set_format_key_types(exon_hip_vcf_parser* p, const char* packed_keys, const char* kinds, int32_t n) {
+  if (!p || n < 0 || (n > 0 && (!packed_keys || !kinds))) return fail(p ? p->ctx : nullptr, EXON_HIP_EINVAL, "exon_hip_vcf_parser_set_format_key_types: bad argument");
+  for (int32_t k = 0; k < n; ++k)  // (a Flag is no FORMAT type)
+    if (!strchr("ifcs", kinds[k]) || !kinds[k]) return fail(p->ctx, EXON_HIP_EINVAL, "exon_hip_vcf_parser_set_format_key_types: kind '%c' of key %d (i f c s)", kinds[k], k);
+  return exon_vcf_key_table_build(p->ctx, &p->format_key_bufs, packed_keys, kinds, n, ExonVcfKeySeed::Format, &p->format_key_table);
 }
 
 int exon_hip_vcf_parser_info_text(exon_hip_vcf_parser* p, void* stream, exon_hip_vcf_info_text* out) {
@@ -996,7 +1003,7 @@ int exon_hip_vcf_parser_info_text(exon_hip_vcf_parser* p, void* stream, exon_hip
   if (p->last_rows < 0) return fail(p->ctx, EXON_HIP_ESTATE, "exon_hip_vcf_parser_info_text: no slab to build from (parse first; a slab with undecided rows has none)");
   ExonTextColumns t;
   int64_t und = 0;
-  if (int rc = exon_text_vcf(p->ctx, stream, &p->info_scratch, p->last_text, p->last_bytes, p->idx.nl, p->last_rows, EXON_HIP_PROJECT_VCF_INFO, &p->key_table, &t, &und)) return rc;
+  if (int rc = exon_text_vcf(p->ctx, stream, &p->info_scratch, p->last_text, p->last_bytes, p->idx.nl, p->last_rows, EXON_HIP_PROJECT_VCF_INFO, &p->key_table, nullptr, &t, &und)) return rc;
   HIP_TRY(p->ctx, hipStreamSynchronize(pick_stream(p->ctx, stream)));
   out->n_undecided = und;
   if (und || !t.n_roots) return EXON_HIP_OK;  // (a slab of no rows has no column)
@@ -1007,9 +1014,30 @@ int exon_hip_vcf_parser_info_text(exon_hip_vcf_parser* p, void* stream, exon_hip
   return EXON_HIP_OK;
 }
 
+int exon_hip_vcf_parser_formats_text(exon_hip_vcf_parser* p, void* stream, exon_hip_vcf_info_text* out) {
+  if (!p || !out) return fail(p ? p->ctx : nullptr, EXON_HIP_EINVAL, "exon_hip_vcf_parser_formats_text: NULL argument");
+  memset(out, 0, sizeof *out);
+  if (!p->format_key_table.hash) return fail(p->ctx, EXON_HIP_ESTATE, "exon_hip_vcf_parser_formats_text: no key types (call exon_hip_vcf_parser_set_format_key_types first)");
+  if (p->last_rows < 0) return fail(p->ctx, EXON_HIP_ESTATE, "exon_hip_vcf_parser_formats_text: no slab to build from (parse first; a slab with undecided rows has none)");
+  ExonTextColumns t;
+  int64_t und = 0;
+  if (int rc = exon_text_vcf(p->ctx, stream, &p->info_scratch, p->last_text, p->last_bytes, p->idx.nl, p->last_rows, EXON_HIP_PROJECT_VCF_FORMATS | EXON_HIP_PROJECT_VCF_FORMATS_ON_DEVICE,
+                             nullptr, &p->format_key_table, &t, &und))
+    return rc;
+  HIP_TRY(p->ctx, hipStreamSynchronize(pick_stream(p->ctx, stream)));
+  out->n_undecided = und;
+  if (und || !t.n_roots) return EXON_HIP_OK;  // (a slab of no rows has no column)
+  const ExonTextNode& formats = t.nodes[t.roots[0]];
+  out->n_bytes = formats.n_values;
+  out->offsets = formats.offsets;
+  out->values = static_cast<const uint8_t*>(formats.values);
+  return EXON_HIP_OK;
+}
+
 }  // extern "C"
 const unsigned* exon_hip_vcf_parser_newlines(exon_hip_vcf_parser* p) { return p ? p->idx.nl : nullptr; }
 const ExonVcfKeyTable* exon_hip_vcf_parser_key_table(exon_hip_vcf_parser* p) { return p ? &p->key_table : nullptr; }
+const ExonVcfKeyTable* exon_hip_vcf_parser_format_key_table(exon_hip_vcf_parser* p) { return p ? &p->format_key_table : nullptr; }
 extern "C" {
 
 // a device-built dictionary (FILTER lists, or the values of a String INFO key) in id order: names '\0'-separated into `buf`.

@@ -66,16 +66,22 @@ struct ExonVcfKeyTable {
   unsigned mask;              // slots - 1
 };
 class PoolBufs;
-int exon_vcf_key_table_build(exon_hip_ctx* ctx, PoolBufs* bufs, const char* keys, const char* kinds, int32_t n, ExonVcfKeyTable* out);
-// gpu_parse.hip: the table exon_hip_vcf_parser_set_key_types has made (hash == nullptr: none yet)
+// which reserved keys of the specification seed the table behind the header's: INFO's (VcfKeyTypes::reserved_info) or FORMAT's
+// (::reserved_format; kinds i f c s -- GT is known by its name, not by the table)
+enum class ExonVcfKeySeed { Info, Format };
+int exon_vcf_key_table_build(exon_hip_ctx* ctx, PoolBufs* bufs, const char* keys, const char* kinds, int32_t n, ExonVcfKeySeed seed, ExonVcfKeyTable* out);
+// gpu_parse.hip: the table exon_hip_vcf_parser_set_key_types has made (hash == nullptr: none yet), and _set_format_key_types'
 const ExonVcfKeyTable* exon_hip_vcf_parser_key_table(exon_hip_vcf_parser* p);
+const ExonVcfKeyTable* exon_hip_vcf_parser_format_key_table(exon_hip_vcf_parser* p);
 // n_undecided != 0 (every exon_text_* that has it): nothing was built, the slab is the host reader's -- a total beyond what the
 // scratch buffers hold (IDs of many empty items, CIGARs of long ops; see scratch_for), or what the format's own note names
 // (VCF `info`, with EXON_HIP_PROJECT_VCF_INFO and info_keys: the rows text_columns.hip lists next to k_vcf_info_measure)
 // VCF: id List<Utf8>? (validity: the ID field is not '.'), ref Utf8, alt List<Utf8>? (validity: ALT is not '.'; no offsets, no items:
-// see text_columns.hip), info Utf8 (the entries printed again; never NULL, "" for INFO '.')
+// see text_columns.hip), info Utf8 (the entries printed again; never NULL, "" for INFO '.'), formats Utf8 (FORMAT, a TAB, the samples
+// printed again; never NULL; built only with EXON_HIP_PROJECT_VCF_FORMATS | _FORMATS_ON_DEVICE and format_keys -- undecided: the rows
+// text_columns.hip lists next to k_fmt_rows)
 int exon_text_vcf(exon_hip_ctx* ctx, void* stream, ExonTextScratch** scratch, const uint8_t* d_text, int64_t n_bytes, const unsigned* d_nl, int64_t n_rows, uint64_t projection,
-                  const ExonVcfKeyTable* info_keys, ExonTextColumns* out, int64_t* n_undecided);
+                  const ExonVcfKeyTable* info_keys, const ExonVcfKeyTable* format_keys, ExonTextColumns* out, int64_t* n_undecided);
 // BAM: name Utf8?, cigar Utf8, sequence Utf8, quality_scores List<Int64> over sequence's offsets (a record's qualities are as many as its bases)
 int exon_text_bam(exon_hip_ctx* ctx, void* stream, ExonTextScratch** scratch, const uint8_t* d_data, int64_t n_bytes, const uint32_t* d_rec_of_row, int64_t n_rows, uint64_t projection,
                   ExonTextColumns* out, int64_t* n_undecided);

@@ -511,16 +511,19 @@ int exon_hip_scan_open(const char* path, const exon_hip_scan_options* o, exon_hi
       return fail(nullptr, EXON_HIP_EUNSUPPORTED, "exon_hip_scan_options.projection: the id / ref / alt (/ info / formats) and name / cigar / sequence / quality_score columns are built for VCF, BCF, BAM and SAM scans");
     switch (o->format) {
       case EXON_HIP_FORMAT_VCF:
-        if (o->projection & ~31ull) return fail(nullptr, EXON_HIP_EINVAL, "projection 0x%llx: VCF knows EXON_HIP_PROJECT_VCF_ID / _REF / _ALT / _INFO / _FORMATS", (unsigned long long)o->projection);
+        if (o->projection & ~63ull) return fail(nullptr, EXON_HIP_EINVAL, "projection 0x%llx: VCF knows EXON_HIP_PROJECT_VCF_ID / _REF / _ALT / _INFO / _FORMATS (and the modifier _FORMATS_ON_DEVICE)", (unsigned long long)o->projection);
+        if ((o->projection & EXON_HIP_PROJECT_VCF_FORMATS_ON_DEVICE) && !(o->projection & EXON_HIP_PROJECT_VCF_FORMATS))
+          return fail(nullptr, EXON_HIP_EINVAL, "projection 0x%llx: EXON_HIP_PROJECT_VCF_FORMATS_ON_DEVICE is a modifier of EXON_HIP_PROJECT_VCF_FORMATS and needs it", (unsigned long long)o->projection);
         // a pushed-down region filter rides along as a row mask (k_region_mask); with use_index the host plans the
         // tabix chunks and only their BGZF blocks are shipped (indexed scans are BGZF by definition)
         s->gpu_parse = o->gpu_parse != 0 && (!rf.use_index || (rf.active && wants_gpu_inflate(o, path)));
         // info / formats as text are the reference's re-printed entries (host/vcf_text.h: number formatting per header type).
         // info is printed on the device too (text_columns.hip: k_vcf_info_measure / k_vcf_info_fill); formats -- genotypes,
-        // per-sample walks -- is the host reader's, so a scan that asks for it decodes there
+        // per-sample walks -- is the host reader's by default, so a scan that asks for it decodes there; with the modifier
+        // EXON_HIP_PROJECT_VCF_FORMATS_ON_DEVICE it is printed on the device too (text_columns.hip: k_fmt_*, a thread a sample)
         if (o->projection & (EXON_HIP_PROJECT_VCF_INFO | EXON_HIP_PROJECT_VCF_FORMATS)) {
           s->gpu_candidate = s->gpu_parse;  // (a fused plan never reads them: exon_hip_stream_consume_scan may still decode on the device)
-          if (o->projection & EXON_HIP_PROJECT_VCF_FORMATS) s->gpu_parse = false;
+          if ((o->projection & EXON_HIP_PROJECT_VCF_FORMATS) && !(o->projection & EXON_HIP_PROJECT_VCF_FORMATS_ON_DEVICE)) s->gpu_parse = false;
         }
         if (reference_tail_quirk(rf)) s->gpu_parse = false;
         break;
@@ -2444,6 +2447,14 @@ static int create_parser(exon_hip_scan* scan, exon_hip_ctx* ctx, int64_t max_tex
         }
         rc = exon_hip_vcf_parser_set_key_types(h, packed.data(), kinds.data(), (int32_t)kinds.size());
       }
+      if (!rc && (scan->opt.projection & EXON_HIP_PROJECT_VCF_FORMATS_ON_DEVICE)) {  // the `formats` text column: the ##FORMAT lines' types
+        std::string packed, kinds;
+        for (const auto& kv : scan->vcf()->key_types.format) {
+          packed.append(kv.first.c_str(), kv.first.size() + 1);
+          kinds += kv.second == 'b' ? 's' : kv.second;  // (a FORMAT line typed Flag: print_value copies its items as a String's)
+        }
+        rc = exon_hip_vcf_parser_set_format_key_types(h, packed.data(), kinds.data(), (int32_t)kinds.size());
+      }
       break;
     }
     case EXON_HIP_FORMAT_BCF: {
@@ -2666,9 +2677,10 @@ static int build_text(exon_hip_scan* scan, exon_hip_ctx* ctx, hipStream_t hs, co
   int64_t undecided = 0;
   int r = EXON_HIP_OK;
   switch (scan->format) {
-    case EXON_HIP_FORMAT_VCF:  // undecided (here and for BAM, as for the other two): totals beyond what the scratch buffers hold; `info`: a row the host reader must print or refuse
+    case EXON_HIP_FORMAT_VCF:  // undecided (here and for BAM, as for the other two): totals beyond what the scratch buffers hold; `info` / `formats`: a row the host reader must print or refuse
       r = exon_text_vcf(ctx, hs, &scan->text_scratch, d_text, (int64_t)n, exon_hip_vcf_parser_newlines(scan->parser.as<exon_hip_vcf_parser>()), n_rows, proj,
-                        exon_hip_vcf_parser_key_table(scan->parser.as<exon_hip_vcf_parser>()), &t->cols, &undecided);
+                        exon_hip_vcf_parser_key_table(scan->parser.as<exon_hip_vcf_parser>()), exon_hip_vcf_parser_format_key_table(scan->parser.as<exon_hip_vcf_parser>()), &t->cols,
+                        &undecided);
       break;
     case EXON_HIP_FORMAT_BCF:  // undecided: an ID / allele that is not a typed string (the host reader reports what it is)
       r = exon_text_bcf(ctx, hs, &scan->text_scratch, d_text, (int64_t)n, exon_hip_bcf_parser_row_records(scan->parser.as<exon_hip_bcf_parser>()), n_rows, proj, &t->cols, &undecided);

@@ -8,6 +8,7 @@
 //                   bases into a local string and then calls `alternates.append(true)` without ever appending a value (:191-205);
 //                   reproduced as it is (results identical to the reference's), the quirk is written down in DESIGN.md
 //        info       Utf8: the parsed entries printed again, not the field's bytes ("AF=0.50" -> "AF=0.5")      :216-297
+//        formats    Utf8: FORMAT, a TAB, the samples printed again (by opt-in: EXON_HIP_PROJECT_VCF_FORMATS_ON_DEVICE)  :310-423
 //   BAM  name       Utf8, NULL for '*'                                exon-bam/src/array_builder.rs:105-113
 //        cigar      Utf8, "<len><op>..." with ops MIDNSHP=X           :144-167
 //        sequence   Utf8, 4-bit codes through "=ACMGRSVTWYHKDBN"      :178-183
@@ -15,7 +16,8 @@
 //   GFF  attributes Map<Utf8, List<Utf8>>, never NULL                 exon-gff/src/array_builder.rs:141-165 (host/gff.h: THE ATTRIBUTE RULES)
 //   GTF  attributes Map<Utf8, Utf8>, never NULL                       exon-gtf/src/array_builder.rs:82-87 (host/gtf.h: THE ATTRIBUTE RULES)
 // One thread per row measures, an exclusive scan turns lengths into offsets, one thread per row fills (rows are short; the bytes
-// of a slab are read twice, L2-resident the second time).  Nothing here is on the fused kernels' path: a scan that projects none of
+// of a slab are read twice, L2-resident the second time).  VCF `formats` alone is cut by SAMPLE, not by row (a row may hold
+// thousands): see its block.  Nothing here is on the fused kernels' path: a scan that projects none of
 // these columns launches none of this.
 #include <hip/hip_runtime.h>
 
@@ -26,6 +28,7 @@
 
 #include "host/decimal_f32.h"
 #include "host/f32_print.h"
+#include "host/vcf_sample_walk.h"
 #include "host/vcf_text.h"
 #include "internal.h"
 #include "list_kernels.h"
@@ -986,6 +989,196 @@ __global__ __launch_bounds__(TPB) void k_vcf_info_fill(const uint8_t* __restrict
   vcf_info_walk(text, fb, fb + field_len[row], kt, f);
 }
 
+// ---- VCF `formats` -----------------------------------------------------------------------------------------------------------------
+// The `formats` Utf8 column (host/vcf_text.h: vcf_formats_string, restated item by item in host/vcf_sample_walk.h, THE RULES
+// there): the FORMAT field, a TAB, the samples printed again and joined by TABs.  A row of 2 504 samples is 30 - 60 KB of text,
+// and a slab of such rows holds a few thousand of them: the unit of work is the SAMPLE, not the row.  No thread here does work
+// that grows with the samples of its row: a thread takes 64 bytes of text (the tab index), the first nine fields of a row, or
+// one sample.
+//   tab index  k_fmt_tab_count / scan / k_fmt_tab_fill: the position of every TAB of the slab's rows, ascending.  The count comes
+//              back before the buffers behind it are sized (one position per two bytes is the worst case; nothing is allocated
+//              for it up front, and no slab has more tabs than its buffer holds).
+//   rows       k_fmt_rows, a thread a row: first_tab[r] = the lower bound of the line's begin in the index; FORMAT lies between
+//              tabs 7 and 8 of the row; its keys -> a word of types, 4 bits a key (0: the row prints "\t" and no sample); the head
+//              item's length = len(FORMAT) + 1.
+//   samples    k_fmt_sample_measure, a thread a tab: tab t of row r (binary search over the line index) with ordinal
+//              t - first_tab[r] >= 8 starts sample ordinal - 8, which runs to the next tab or the line's end (its CR dropped);
+//              length = the sample walk's + 1 for the TAB in front of every sample but the first.  Other tabs: 0.
+//   places     the lengths lie at slot(head of r) = first_tab[r] + r and slot(tab t) = t + r + 1: ONE scan over rows + tabs words
+//              places every item, and the row offsets are item_off[first_tab[r] + r] (k_fmt_head_fill gathers them).
+//   fill       k_fmt_head_fill (FORMAT + TAB) and k_fmt_sample_fill write their item inside [item_off[slot], item_off[slot + 1])
+//              and below the buffer's size, nowhere else.
+// Nothing spins or looks back; the binary searches are bounded by the index sizes.
+// UNDECIDED (the row is counted, the file goes to the host reader, which prints it or raises with its own message): fewer than
+// eight fields; more than 16 FORMAT keys; a byte >= 0x80 in FORMAT or in a sample; a value that has a key and is empty or "."
+// (so also a line that has FORMAT and ends there: the host raises on its empty sample); an allele that is empty or not all
+// digits; an integer print_i32 refuses; a float dec::parse_f32 leaves open (the inf / infinity / nan spellings are printed
+// here).  A slab whose column exceeds INT32_MAX bytes, whose rows + tabs exceed INT32_MAX, or whose buffers cannot be had is
+// handed over whole.
+constexpr unsigned FMT_CHUNK = 64;  // bytes of text a thread of the tab index takes
+__device__ __forceinline__ unsigned tabs_in_word(uint32_t w) {  // the bytes of w that are 0x09, exactly
+  const uint32_t x = w ^ 0x09090909u;
+  return (unsigned)__popc(~(((x & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | x | 0x7F7F7F7Fu));
+}
+// chunk c = bytes [64 c, 64 c + 64) of the aligned text; the bytes in [skip, hi) count, hi = the last row's newline
+__global__ __launch_bounds__(TPB) void k_fmt_tab_count(const uint8_t* __restrict__ text, const unsigned* __restrict__ nl, unsigned n_rows, unsigned skip, unsigned n_total,
+                                                       unsigned n_chunks, uint32_t* __restrict__ cnt) {
+  const unsigned c = blockIdx.x * TPB + threadIdx.x;
+  if (c >= n_chunks) return;
+  const unsigned hi = min(nl[n_rows - 1], n_total);
+  unsigned n = 0;
+  for (unsigned g = 0; g < FMT_CHUNK / 16; ++g) {
+    const unsigned b = c * FMT_CHUNK + g * 16;
+    if (b >= hi) break;
+    if (b >= skip && hi - b >= 16) {
+      const uint4 v = *reinterpret_cast<const uint4*>(text + b);
+      n += tabs_in_word(v.x) + tabs_in_word(v.y) + tabs_in_word(v.z) + tabs_in_word(v.w);
+    } else {
+      for (unsigned i = max(b, skip); i < min(b + 16, hi); ++i) n += text[i] == '\t';
+    }
+  }
+  cnt[c] = n;
+}
+// cap: the positions `tabs` holds (the host sized it from the count; a position beyond it is not written)
+__global__ __launch_bounds__(TPB) void k_fmt_tab_fill(const uint8_t* __restrict__ text, const unsigned* __restrict__ nl, unsigned n_rows, unsigned skip, unsigned n_total,
+                                                      unsigned n_chunks, const int32_t* __restrict__ chunk_first, uint32_t* __restrict__ tabs, unsigned cap) {
+  const unsigned c = blockIdx.x * TPB + threadIdx.x;
+  if (c >= n_chunks) return;
+  unsigned w = (unsigned)chunk_first[c];
+  if ((unsigned)chunk_first[c + 1] == w) return;
+  const unsigned hi = min(nl[n_rows - 1], n_total);
+  const unsigned b0 = max(c * FMT_CHUNK, skip), b1 = min(c * FMT_CHUNK + FMT_CHUNK, hi);
+  for (unsigned i = b0; i < b1; ++i)
+    if (text[i] == '\t') {
+      if (w < cap) tabs[w] = i;
+      ++w;
+    }
+}
+using VcfFmtMeasure = VcfInfoMeasure;  // (byte / span / i32 / f32: what the sample walk emits)
+using VcfFmtFill = VcfInfoFill;
+// the line of row r without its CR: [*begin, *end)
+__device__ __forceinline__ void fmt_line(const uint8_t* __restrict__ text, const unsigned* __restrict__ nl, unsigned r, unsigned skip, unsigned* begin, unsigned* end) {
+  *begin = r ? nl[r - 1] + 1 : skip;
+  *end = nl[r];
+  if (*end > *begin && text[*end - 1] == '\r') --*end;
+}
+// scal: [0, 1] the slab's printed bytes as one 64-bit sum, [2] undecided items, (shared with k_fmt_sample_measure)
+__device__ __forceinline__ void fmt_tally(unsigned printed, bool bad, unsigned* __restrict__ scal) {
+  unsigned long long sum = printed;
+  for (int d = 32; d > 0; d >>= 1) sum += __shfl_down(sum, d);
+  const unsigned long long bb = __ballot(bad);
+  if ((threadIdx.x & 63) == 0) {
+    if (sum) atomicAdd(reinterpret_cast<unsigned long long*>(scal), sum);
+    if (bb) atomicAdd(scal + 2, (unsigned)__popcll(bb));
+  }
+}
+__global__ __launch_bounds__(TPB) void k_fmt_rows(const uint8_t* __restrict__ text, const unsigned* __restrict__ nl, unsigned n_rows, unsigned skip, ExonVcfKeyTable kt,
+                                                  const uint32_t* __restrict__ tabs, unsigned n_tabs, uint32_t* __restrict__ first_tab,
+                                                  unsigned long long* __restrict__ types, uint32_t* __restrict__ item_len, unsigned* __restrict__ scal) {
+  const unsigned r = blockIdx.x * TPB + threadIdx.x;
+  bool bad = false;
+  unsigned head = 0;
+  if (r < n_rows) {
+    unsigned begin, end;
+    fmt_line(text, nl, r, skip, &begin, &end);
+    unsigned lo = 0, hi = n_tabs;  // the first tab at or behind the line's begin
+    while (lo < hi) {
+      const unsigned mid = lo + (hi - lo) / 2;
+      if (tabs[mid] < begin) lo = mid + 1;
+      else hi = mid;
+    }
+    const unsigned ft = lo;
+    unsigned nt = 0;  // the row's tabs, as far as nine matter
+    while (nt < 9 && ft + nt < n_tabs && tabs[ft + nt] < end) ++nt;
+    uint64_t ty = 0;
+    if (nt < 7) {
+      bad = true;  // fewer than eight fields: no data line
+    } else if (nt >= 8) {
+      const unsigned fb = tabs[ft + 7] + 1, fe = nt >= 9 ? tabs[ft + 8] : end;
+      bad = !exon::vsw::format_keys(text, fb, fe, [&](unsigned kb, unsigned kn) { return vcf_key_type(kt, text, kb, kn); }, &ty);
+      if (!bad && ty) {
+        head = fe - fb;
+        bad = nt == 8;  // FORMAT and no sample: the host reader raises on the empty one
+      }
+    }
+    head = bad ? 0u : head + 1;
+    first_tab[r] = ft;
+    types[r] = bad ? 0ull : ty;
+    item_len[ft + r] = head;
+  }
+  fmt_tally(head, bad, scal);
+}
+__global__ __launch_bounds__(TPB) void k_fmt_sample_measure(const uint8_t* __restrict__ text, const unsigned* __restrict__ nl, unsigned n_rows, unsigned skip,
+                                                            const uint32_t* __restrict__ tabs, unsigned n_tabs, const uint32_t* __restrict__ first_tab,
+                                                            const unsigned long long* __restrict__ types, uint32_t* __restrict__ tab_row,
+                                                            uint32_t* __restrict__ item_len, unsigned* __restrict__ scal) {
+  const unsigned t = blockIdx.x * TPB + threadIdx.x;
+  bool bad = false;
+  unsigned printed = 0;
+  if (t < n_tabs) {
+    const unsigned p = tabs[t];
+    unsigned lo = 0, hi = n_rows - 1;  // the row of the tab: the first line that ends behind it (every indexed tab lies in front of the last newline)
+    while (lo < hi) {
+      const unsigned mid = lo + (hi - lo) / 2;
+      if (nl[mid] < p) lo = mid + 1;
+      else hi = mid;
+    }
+    const unsigned r = lo, ft = first_tab[r];
+    const uint64_t ty = types[r];
+    if (t >= ft + 8 && ty) {
+      unsigned begin, end;
+      fmt_line(text, nl, r, skip, &begin, &end);
+      const unsigned sb = p + 1, se = (t + 1 < n_tabs && tabs[t + 1] < end) ? tabs[t + 1] : end;
+      if (sb > se) {
+        bad = true;  // (never: a tab lies in front of its line's end)
+      } else {
+        VcfFmtMeasure m;
+        bad = exon::vsw::sample(text, sb, se, ty, m);
+        printed = bad ? 0u : m.n + (t > ft + 8 ? 1u : 0u);
+      }
+    }
+    tab_row[t] = r;
+    item_len[t + r + 1] = printed;
+  }
+  fmt_tally(printed, bad, scal);
+}
+// the head item of every row (FORMAT, TAB) and the row offsets out of the items' places; cap: the bytes `values` holds
+__global__ __launch_bounds__(TPB) void k_fmt_head_fill(const uint8_t* __restrict__ text, unsigned n_rows, const uint32_t* __restrict__ tabs, unsigned n_tabs,
+                                                       const uint32_t* __restrict__ first_tab, const int32_t* __restrict__ item_off, int32_t* __restrict__ row_off,
+                                                       uint8_t* __restrict__ values, unsigned cap, unsigned n_total) {
+  const unsigned r = blockIdx.x * TPB + threadIdx.x;
+  if (r >= n_rows) return;
+  const unsigned ft = first_tab[r], slot = ft + r;
+  const unsigned at = (unsigned)item_off[slot], n = (unsigned)(item_off[slot + 1] - item_off[slot]);
+  row_off[r] = (int32_t)at;
+  if (r == n_rows - 1) row_off[n_rows] = item_off[n_rows + n_tabs];
+  if (n == 0 || (uint64_t)at + n > cap) return;
+  if (n > 1) {  // (a head longer than its TAB: the row has a FORMAT field, so eight tabs)
+    if (ft + 7 >= n_tabs) return;
+    const unsigned fb = tabs[ft + 7] + 1;
+    if ((uint64_t)fb + (n - 1) > n_total) return;
+    copy_run(values + at, text + fb, n - 1);
+  }
+  values[at + n - 1] = '\t';
+}
+__global__ __launch_bounds__(TPB) void k_fmt_sample_fill(const uint8_t* __restrict__ text, const unsigned* __restrict__ nl, unsigned skip, const uint32_t* __restrict__ tabs,
+                                                         unsigned n_tabs, const uint32_t* __restrict__ first_tab, const unsigned long long* __restrict__ types,
+                                                         const uint32_t* __restrict__ tab_row, const int32_t* __restrict__ item_off, uint8_t* __restrict__ values,
+                                                         unsigned cap) {
+  const unsigned t = blockIdx.x * TPB + threadIdx.x;
+  if (t >= n_tabs) return;
+  const unsigned r = tab_row[t], slot = t + r + 1;
+  const unsigned at = (unsigned)item_off[slot], n = (unsigned)(item_off[slot + 1] - item_off[slot]);
+  if (n == 0 || (uint64_t)at + n > cap) return;
+  unsigned begin, end;
+  fmt_line(text, nl, r, skip, &begin, &end);
+  const unsigned sb = tabs[t] + 1, se = (t + 1 < n_tabs && tabs[t + 1] < end) ? tabs[t + 1] : end;
+  if (sb > se) return;
+  VcfFmtFill f{text, values + at, n};
+  if (t > first_tab[r] + 8) f.byte('\t');
+  exon::vsw::sample(text, sb, se, types[r], f);
+}
+
 // What a format's kernels need of the scratch.  A scratch serves the layout it was made for and no other (scratch_for).
 struct TextLayout {
   int8_t cols;         // length arrays and the offsets scanned out of them (len[k], off[k])
@@ -1009,6 +1202,21 @@ struct ExonTextScratch {
   uint8_t* info_values = nullptr;
   unsigned* info_scal = nullptr;    // device [4]: k_vcf_info_measure's scalars
   unsigned* h_info_scal = nullptr;  // pinned
+  // VCF `formats`: the buffers sized by the slab (fmt_rows rows, fmt_chunks chunks of FMT_CHUNK bytes), by its tabs (fmt_tabs) and
+  // the printed bytes (fmt_cap), each grown on demand (fmt_for)
+  PoolBufs fmt_slab_bufs, fmt_tab_bufs, fmt_value_bufs;
+  size_t fmt_rows = 0, fmt_chunks = 0, fmt_tabs = 0, fmt_cap = 0;
+  uint32_t *fmt_cnt = nullptr, *fmt_first_tab = nullptr;            // [chunks], [rows]
+  int32_t *fmt_chunk_first = nullptr, *fmt_row_off = nullptr;       // [chunks + 1], [rows + 1]
+  unsigned long long* fmt_types = nullptr;                          // [rows]
+  unsigned* fmt_chunk_sums = nullptr;                               // the block sums of the scan over the chunks
+  uint32_t *fmt_tab_pos = nullptr, *fmt_tab_row = nullptr;          // [tabs]
+  uint32_t* fmt_item_len = nullptr;                                 // [rows + tabs]
+  int32_t* fmt_item_off = nullptr;                                  // [rows + tabs + 1]
+  unsigned* fmt_item_sums = nullptr;                                // the block sums of the scan over the items
+  uint8_t* fmt_values = nullptr;
+  unsigned* fmt_scal = nullptr;    // device [8]: [0, 1] printed bytes, [2] undecided items, [3] the u32 total of the items' scan, [4] the tabs
+  unsigned* h_fmt_scal = nullptr;  // pinned
   int64_t max_rows = 0, max_bytes = 0;
   TextLayout layout{};
   uint32_t* len[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
@@ -1024,7 +1232,8 @@ struct ExonTextScratch {
   size_t qual_cap = 0;
   size_t value_cap = 0;  // bytes every values[k] holds
   size_t item_cap = 0;   // entries every item_off[k] holds
-  explicit ExonTextScratch(exon_hip_ctx* ctx) : bufs(ctx), qual_bufs(ctx), info_row_bufs(ctx), info_value_bufs(ctx) {}
+  explicit ExonTextScratch(exon_hip_ctx* ctx)
+      : bufs(ctx), qual_bufs(ctx), info_row_bufs(ctx), info_value_bufs(ctx), fmt_slab_bufs(ctx), fmt_tab_bufs(ctx), fmt_value_bufs(ctx) {}
 };
 
 void exon_text_scratch_destroy(ExonTextScratch* s) { delete s; }
@@ -1042,6 +1251,14 @@ void exon_text_scratch_destroy(ExonTextScratch* s) { delete s; }
 //                    the field).  k_vcf_info_measure yields every row's exact length and their 64-bit sum; info_for grows the buffer to
 //                    the sum before the fill; a sum beyond INT32_MAX (int32 offsets), or a buffer that cannot be had, hands the slab
 //                    over; k_vcf_info_fill writes inside [offsets[r], offsets[r + 1]) and below the buffer's size only: checked
+//   VCF    fmt_tab_pos / fmt_tab_row: a position and a row per TAB of the slab's rows; k_fmt_tab_count yields their exact number, which
+//                    comes back before fmt_for makes the buffers (a quarter more than the count, at least 64 Ki): fits; k_fmt_tab_fill
+//                    bounds its writes all the same
+//   VCF    fmt_item_len / fmt_item_off: rows + tabs items (+ 1 entry), against fmt_rows + fmt_tabs + 64 (+ 1): fits
+//   VCF    fmt_values: the printed `formats` items, NOT bounded by the slab (as info_values): the measure kernels yield every item's
+//                    exact length and their 64-bit sum; fmt_for grows the buffer to the sum before the fills; a sum beyond INT32_MAX,
+//                    rows + tabs beyond INT32_MAX, or a buffer that cannot be had, hands the slab over; the fills write inside
+//                    [item_off[slot], item_off[slot + 1]) and below the buffer's size only: checked
 //   BCF    values[0], [1], [2] (max_bytes = n_bytes): id / ref / alt, characters of typed strings inside the records: <= n_bytes each: fits
 //   BCF    item_off[BCF_ID_ITEMS]: a typed ID of k characters is up to k + 1 items behind a descriptor byte: up to n_bytes items + 1 entry: checked
 //   BCF    item_off[BCF_ALT_ITEMS]: an empty allele is its descriptor byte alone: up to n_bytes items + 1 entry: checked
@@ -1147,10 +1364,13 @@ static bool fits(const ExonTextScratch* s, std::initializer_list<unsigned> bytes
 }
 
 // lengths -> offsets (n + 1 of them); the total -> *total
-static void scan_lengths(hipStream_t hs, ExonTextScratch* s, const uint32_t* len, unsigned n, int32_t* offsets, unsigned* total) {
+static void scan_lengths_with(hipStream_t hs, unsigned* sums, const uint32_t* len, unsigned n, int32_t* offsets, unsigned* total) {
   const int nb = (int)((n + LIST_TPB - 1) / LIST_TPB);
-  launch_list_scan(hs, len, nullptr, n, nb, s->sums, total);
-  hipLaunchKernelGGL(k_write_offsets, dim3(nb), dim3(LIST_TPB), 0, hs, len, n, s->sums, offsets);
+  launch_list_scan(hs, len, nullptr, n, nb, sums, total);
+  hipLaunchKernelGGL(k_write_offsets, dim3(nb), dim3(LIST_TPB), 0, hs, len, n, sums, offsets);
+}
+static void scan_lengths(hipStream_t hs, ExonTextScratch* s, const uint32_t* len, unsigned n, int32_t* offsets, unsigned* total) {
+  scan_lengths_with(hs, s->sums, len, n, offsets, total);  // (sums: a word per 256 rows; the `formats` scans bring block sums of their own)
 }
 
 // One builder's run.  text_begin is every builder's prologue: a scratch of the format's layout for the slab, the stream, the launch
@@ -1221,21 +1441,87 @@ static bool info_for(ExonTextScratch* s, size_t rows, size_t bytes) {
   return true;
 }
 
+// room for the `formats` column, each part kept between slabs and grown on demand: for a slab of `rows` rows in `bytes` aligned
+// bytes (tabs == 0 and value_bytes == 0), for its `tabs` tabs, for its `value_bytes` printed bytes (at least 1 MiB).  false: no
+// memory (the caller hands the slab over)
+static bool fmt_for(ExonTextScratch* s, size_t rows, size_t bytes, size_t tabs, size_t value_bytes) {
+  const size_t chunks = (bytes + FMT_CHUNK - 1) / FMT_CHUNK;
+  if (rows && (s->fmt_rows < rows || s->fmt_chunks < chunks)) {
+    PoolBufs& b = s->fmt_slab_bufs;
+    const size_t r = std::max(rows, s->fmt_rows) + 64, c = std::max(chunks, s->fmt_chunks) + 64;
+    b.release();
+    s->fmt_rows = s->fmt_chunks = 0;
+    s->fmt_tab_bufs.release();  // (the items' buffers are sized for fmt_rows + fmt_tabs items: they are made again for the new rows)
+    s->fmt_tabs = 0;
+    s->fmt_cnt = b.take<uint32_t>(c * 4);
+    s->fmt_chunk_first = b.take<int32_t>((c + 1) * 4);
+    s->fmt_chunk_sums = b.take<unsigned>((c / LIST_TPB + 4) * 4);
+    s->fmt_first_tab = b.take<uint32_t>(r * 4);
+    s->fmt_row_off = b.take<int32_t>((r + 1) * 4);
+    s->fmt_types = b.take<unsigned long long>(r * 8);
+    s->fmt_scal = b.take<unsigned>(32);
+    s->h_fmt_scal = b.pinned<unsigned>(32);
+    if (b.status() != hipSuccess) {
+      (void)hipGetLastError();
+      b.release();
+      return false;
+    }
+    s->fmt_rows = r - 64;
+    s->fmt_chunks = c - 64;
+  }
+  if (tabs > s->fmt_tabs) {
+    PoolBufs& b = s->fmt_tab_bufs;
+    b.release();
+    s->fmt_tabs = 0;
+    const size_t t = std::max<size_t>(tabs + tabs / 4, (size_t)1 << 16), items = t + s->fmt_rows + 64;
+    s->fmt_tab_pos = b.take<uint32_t>((t + 64) * 4);
+    s->fmt_tab_row = b.take<uint32_t>((t + 64) * 4);
+    s->fmt_item_len = b.take<uint32_t>(items * 4);
+    s->fmt_item_off = b.take<int32_t>((items + 1) * 4);
+    s->fmt_item_sums = b.take<unsigned>((items / LIST_TPB + 4) * 4);
+    if (b.status() != hipSuccess) {
+      (void)hipGetLastError();
+      b.release();
+      return false;
+    }
+    s->fmt_tabs = t;
+  }
+  if (value_bytes > s->fmt_cap) {
+    s->fmt_value_bufs.release();
+    s->fmt_cap = 0;
+    const size_t cap = std::max<size_t>(value_bytes + value_bytes / 4, (size_t)1 << 20);
+    s->fmt_values = s->fmt_value_bufs.take<uint8_t>(cap + 64);
+    if (!s->fmt_values) {
+      (void)hipGetLastError();
+      s->fmt_value_bufs.release();
+      return false;
+    }
+    s->fmt_cap = cap;
+  }
+  return true;
+}
+
 // the key types of a VCF header, flattened for the device: open addressing over a power of two of slots, at most half of them taken.
 // keys: n names, each with its NUL, back to back; kinds: their n type characters (i f b c s).  The first line of a key wins, as
 // in the host reader; the reserved keys of the specification follow with the types noodles falls back to (VcfKeyTypes::
-// reserved_info), unless the header has typed them.
-int exon_vcf_key_table_build(exon_hip_ctx* ctx, PoolBufs* bufs, const char* keys, const char* kinds, int32_t n, ExonVcfKeyTable* out) {
-  // (the names of VcfKeyTypes::reserved_info's three lists: that function is the authority on their types)
+// reserved_info, or ::reserved_format for the table of the FORMAT keys), unless the header has typed them.  (GT is no entry of
+// the FORMAT table: the walk knows it by its name, whatever the header says.)
+int exon_vcf_key_table_build(exon_hip_ctx* ctx, PoolBufs* bufs, const char* keys, const char* kinds, int32_t n, ExonVcfKeySeed seed, ExonVcfKeyTable* out) {
+  // (the names of VcfKeyTypes::reserved_info's three lists and of ::reserved_format's two: those functions are the authority on their types)
   static const char* const reserved[] = {"AC", "AD", "ADF", "ADR", "AN", "DP", "END", "MQ0", "NS", "SB", "SVLEN", "CIPOS", "CIEND", "HOMLEN", "CILEN", "DPADJ",
                                          "CN", "CNADJ", "CICN", "CICNADJ", "AF", "BQ", "MQ", "DB", "H2", "H3", "SOMATIC", "VALIDATED", "1000G", "IMPRECISE", "NOVEL"};
+  static const char* const reserved_format[] = {"AD", "ADF", "ADR", "DP", "EC", "GQ", "HQ", "MQ", "PL", "PP", "PQ", "PS", "CN", "NQ", "HAP", "AHAP", "GL", "GP", "CNQ", "CNL", "CNP"};
+  const bool format = seed == ExonVcfKeySeed::Format;
   std::vector<std::pair<std::string, char>> entries;
   const char* p = keys;
   for (int32_t k = 0; k < n; ++k) {
     entries.emplace_back(std::string(p), kinds[k]);
     p += entries.back().first.size() + 1;
   }
-  for (const char* r : reserved) entries.emplace_back(r, exon::VcfKeyTypes::reserved_info(r));
+  if (format)
+    for (const char* r : reserved_format) entries.emplace_back(r, exon::VcfKeyTypes::reserved_format(r));
+  else
+    for (const char* r : reserved) entries.emplace_back(r, exon::VcfKeyTypes::reserved_info(r));
   size_t slots = 64;
   while (slots < 2 * entries.size()) slots *= 2;
   std::vector<uint64_t> hash(slots, 0);
@@ -1275,20 +1561,24 @@ int exon_vcf_key_table_build(exon_hip_ctx* ctx, PoolBufs* bufs, const char* keys
     (void)hipGetLastError();
     bufs->release();
     memset(out, 0, sizeof *out);
-    return fail(ctx, EXON_HIP_ENOMEM, "the INFO key types of a VCF header (%zu keys): %s", entries.size(), msg.c_str());
+    return fail(ctx, EXON_HIP_ENOMEM, "the %s key types of a VCF header (%zu keys): %s", format ? "FORMAT" : "INFO", entries.size(), msg.c_str());
   }
   *out = ExonVcfKeyTable{d_hash, d_off, d_len, d_type, d_text, (unsigned)(slots - 1)};
   return EXON_HIP_OK;
 }
 
 int exon_text_vcf(exon_hip_ctx* ctx, void* stream, ExonTextScratch** sp, const uint8_t* d_text, int64_t n_bytes, const unsigned* d_nl, int64_t n_rows, uint64_t projection,
-                  const ExonVcfKeyTable* info_keys, ExonTextColumns* out, int64_t* n_undecided) {
+                  const ExonVcfKeyTable* info_keys, const ExonVcfKeyTable* format_keys, ExonTextColumns* out, int64_t* n_undecided) {
   *out = ExonTextColumns();
   *n_undecided = 0;
   const bool path3 = (projection & (EXON_HIP_PROJECT_VCF_ID | EXON_HIP_PROJECT_VCF_REF | EXON_HIP_PROJECT_VCF_ALT)) != 0;
   const bool info = (projection & EXON_HIP_PROJECT_VCF_INFO) != 0;
-  if (n_rows == 0 || !(path3 || info)) return EXON_HIP_OK;
+  // (bit 16 without the modifier is the host reader's column: nothing is built for it here)
+  const bool formats = (projection & EXON_HIP_PROJECT_VCF_FORMATS) && (projection & EXON_HIP_PROJECT_VCF_FORMATS_ON_DEVICE);
+  if (n_rows == 0 || !(path3 || info || formats)) return EXON_HIP_OK;
   if (info && (!info_keys || !info_keys->hash)) return fail(ctx, EXON_HIP_ESTATE, "the VCF info column needs the header's key types (exon_hip_vcf_parser_set_key_types)");
+  if (formats && (!format_keys || !format_keys->hash))
+    return fail(ctx, EXON_HIP_ESTATE, "the VCF formats column needs the header's FORMAT key types (exon_hip_vcf_parser_set_format_key_types)");
   const unsigned skip = (unsigned)(reinterpret_cast<uintptr_t>(d_text) & 15);
   d_text -= skip;
   n_bytes += skip;
@@ -1296,6 +1586,34 @@ int exon_text_vcf(exon_hip_ctx* ctx, void* stream, ExonTextScratch** sp, const u
   if (int rc = text_begin(ctx, stream, sp, n_rows, n_bytes, LAYOUT_VCF, &t)) return rc;
   ExonTextScratch* s = t.s;
   VcfLens L{s->len[0], s->len[1], s->len[2], s->field, s->field + 3 * ((size_t)s->max_rows + 64)};
+  unsigned n_tabs = 0, n_items = 0;
+  if (formats) {  // the tab index first: its size comes back before the buffers behind it are made
+    const unsigned n_total = (unsigned)n_bytes, n_chunks = (unsigned)(((size_t)n_bytes + FMT_CHUNK - 1) / FMT_CHUNK);
+    const int cb = (int)((n_chunks + TPB - 1) / TPB);
+    if (!fmt_for(s, (size_t)std::max<int64_t>(n_rows, 1 << 16), (size_t)std::max<int64_t>(n_bytes, 1 << 20), 0, 0))
+      return fail(ctx, EXON_HIP_ENOMEM, "buffers for the formats column of a slab (%lld rows, %lld bytes)", (long long)n_rows, (long long)n_bytes);
+    HIP_TRY(ctx, hipMemsetAsync(s->fmt_scal, 0, 32, t.hs));
+    hipLaunchKernelGGL(k_fmt_tab_count, dim3(cb), dim3(TPB), 0, t.hs, d_text, d_nl, t.n, skip, n_total, n_chunks, s->fmt_cnt);
+    scan_lengths_with(t.hs, s->fmt_chunk_sums, s->fmt_cnt, n_chunks, s->fmt_chunk_first, s->fmt_scal + 4);
+    HIP_TRY(ctx, hipMemcpyAsync(s->h_fmt_scal, s->fmt_scal, 32, hipMemcpyDeviceToHost, t.hs));
+    HIP_TRY(ctx, hipStreamSynchronize(t.hs));
+    n_tabs = s->h_fmt_scal[4];
+    // no tab at all: no row has eight fields; rows + tabs beyond int32: the items' scan has no room; no memory: all the host reader's
+    if (n_tabs == 0 || (uint64_t)n_tabs + (uint64_t)t.n > (uint64_t)INT32_MAX || !fmt_for(s, 0, 0, n_tabs, 0)) {
+      *n_undecided = n_rows;
+      return EXON_HIP_OK;
+    }
+    n_items = n_tabs + t.n;
+    const int tb = (int)((n_tabs + TPB - 1) / TPB);
+    hipLaunchKernelGGL(k_fmt_tab_fill, dim3(cb), dim3(TPB), 0, t.hs, d_text, d_nl, t.n, skip, n_total, n_chunks, s->fmt_chunk_first, s->fmt_tab_pos,
+                       (unsigned)std::min<size_t>(s->fmt_tabs, 0xFFFFFFFFu));
+    hipLaunchKernelGGL(k_fmt_rows, dim3(t.nb), dim3(TPB), 0, t.hs, d_text, d_nl, t.n, skip, *format_keys, s->fmt_tab_pos, n_tabs, s->fmt_first_tab, s->fmt_types, s->fmt_item_len,
+                       s->fmt_scal);
+    hipLaunchKernelGGL(k_fmt_sample_measure, dim3(tb), dim3(TPB), 0, t.hs, d_text, d_nl, t.n, skip, s->fmt_tab_pos, n_tabs, s->fmt_first_tab, s->fmt_types, s->fmt_tab_row,
+                       s->fmt_item_len, s->fmt_scal);
+    scan_lengths_with(t.hs, s->fmt_item_sums, s->fmt_item_len, n_items, s->fmt_item_off, s->fmt_scal + 3);
+    HIP_TRY(ctx, hipMemcpyAsync(s->h_fmt_scal, s->fmt_scal, 32, hipMemcpyDeviceToHost, t.hs));
+  }
   if (info) {
     if (!info_for(s, (size_t)std::max<int64_t>(n_rows, 1 << 16), 0)) return fail(ctx, EXON_HIP_ENOMEM, "buffers for the info column of a slab (%lld rows)", (long long)n_rows);
     HIP_TRY(ctx, hipMemsetAsync(s->info_scal, 0, 16, t.hs));
@@ -1317,10 +1635,29 @@ int exon_text_vcf(exon_hip_ctx* ctx, void* stream, ExonTextScratch** sp, const u
       return EXON_HIP_OK;
     }
   }
+  uint64_t fmt_bytes = 0;
+  if (formats) {
+    if (s->h_fmt_scal[2]) {  // rows (or samples of rows) the host reader must print, or refuse
+      *n_undecided = s->h_fmt_scal[2];
+      return EXON_HIP_OK;
+    }
+    fmt_bytes = (uint64_t)s->h_fmt_scal[0] | (uint64_t)s->h_fmt_scal[1] << 32;
+    if (fmt_bytes > (uint64_t)INT32_MAX || !fmt_for(s, 0, 0, 0, (size_t)std::max<uint64_t>(fmt_bytes, 1))) {  // int32 offsets; no buffer of that size
+      *n_undecided = n_rows;
+      return EXON_HIP_OK;
+    }
+  }
   const unsigned id_items = path3 ? s->h_res[0] : 0u, id_bytes = path3 ? s->h_res[1] : 0u, ref_bytes = path3 ? s->h_res[2] : 0u;
   if (path3 && !fits(s, {id_bytes, ref_bytes}, {id_items})) {  // (IDs of many empty items)
     *n_undecided = n_rows;
     return EXON_HIP_OK;
+  }
+  if (formats) {
+    const unsigned cap = (unsigned)std::min<size_t>(s->fmt_cap, 0xFFFFFFFFu);
+    hipLaunchKernelGGL(k_fmt_head_fill, dim3(t.nb), dim3(TPB), 0, t.hs, d_text, t.n, s->fmt_tab_pos, n_tabs, s->fmt_first_tab, s->fmt_item_off, s->fmt_row_off, s->fmt_values, cap,
+                       (unsigned)n_bytes);
+    hipLaunchKernelGGL(k_fmt_sample_fill, dim3((n_tabs + TPB - 1) / TPB), dim3(TPB), 0, t.hs, d_text, d_nl, skip, s->fmt_tab_pos, n_tabs, s->fmt_first_tab, s->fmt_types,
+                       s->fmt_tab_row, s->fmt_item_off, s->fmt_values, cap);
   }
   if (path3) {
     hipLaunchKernelGGL(k_vcf_fill, dim3(t.nb), dim3(TPB), 0, t.hs, d_text, t.n, L, s->off[0], s->off[1], s->off[2], s->item_off[VCF_ID_ITEMS], s->values[0], s->values[2], id_items,
@@ -1335,6 +1672,7 @@ int exon_text_vcf(exon_hip_ctx* ctx, void* stream, ExonTextScratch** sp, const u
   if (projection & EXON_HIP_PROJECT_VCF_REF) out->root(out->utf8(t.n, s->off[2], nullptr, s->values[2], ref_bytes));
   if (projection & EXON_HIP_PROJECT_VCF_ALT) out->root(out->list_utf8(t.n, nullptr, s->valid[1], 0, nullptr, nullptr, 0));  // (no items: the note at the top)
   if (info) out->root(out->utf8(t.n, s->info_off, nullptr, s->info_values, (int64_t)info_bytes));
+  if (formats) out->root(out->utf8(t.n, s->fmt_row_off, nullptr, s->fmt_values, (int64_t)fmt_bytes));
   return text_done(ctx, out);
 }
 

@@ -458,15 +458,17 @@ class Scan:
                "gff": {"attributes": 256}, "gtf": {"attributes": 256}, "bed": L.PROJECT_BED}
 
     def __init__(self, path, fmt, compression=None, batch_size=0, info_field=None, region=None, use_index=False,
-                 gpu_parse=False, project=(), where=None, where_flags=None):
-        """where_flags: (mask, value[, mapq_min]), the flag / mapping-quality predicate a BAM or SAM scan evaluates itself
+                 gpu_parse=False, project=(), where=None, where_flags=None, formats_on_device=False):
+        """formats_on_device: VCF, next to "formats" in `project`: the modifier EXON_HIP_PROJECT_VCF_FORMATS_ON_DEVICE -- a gpu_parse scan
+        then prints the column on the device instead of decoding on the host (no column of its own; the open refuses it without "formats").
+        where_flags: (mask, value[, mapq_min]), the flag / mapping-quality predicate a BAM or SAM scan evaluates itself
         (exon_hip_scan_set_flag_predicate): rows with (flag & mask) != value, or -- for a mapq_min >= 0 -- a NULL or smaller
         mapping_quality, are not emitted (ANDed with `region`).
         where: (column, op, literal), one comparison the scan evaluates itself (exon_hip_scan_set_predicate): `column` a scan column
         (VCF: 2 = qual, 4 + k = typed INFO field k of info_field; Float32, or Int32 values), `op` one of ">" ">=" "<" "<=" "=" "!=";
         rows whose column is NULL or fails are not emitted (ANDed with `region`).
         project: names of the reference's columns beyond the fused kernels' operands (EXON_HIP_PROJECT_*): VCF "id", "ref", "alt",
-        "info", "formats" (the last two as the reference's unparsed Utf8 columns; info from the GPU pipeline too, formats host reader only);
+        "info", "formats" (the last two as the reference's unparsed Utf8 columns; info from the GPU pipeline too, formats only with formats_on_device);
         BAM "name", "cigar", "sequence", "quality_score" -- appended behind the default columns in that order; GFF "attributes"
         (the reference's Map<Utf8, List<Utf8>>, column 8); GTF "attributes" (the reference's Map<Utf8, Utf8>, column 8); BED "name",
         "score", "strand", "thick_start", "thick_end", "color", "block_count", "block_sizes", "block_starts" (bits 3 .. 11: the
@@ -476,6 +478,10 @@ class Scan:
         mask = 0
         for name in project:
             mask |= self.PROJECT[fmt][name]
+        if formats_on_device:  # (a modifier, not a name of PROJECT: it adds no column)
+            if fmt != "vcf":
+                raise ValueError("formats_on_device is an option of VCF scans")
+            mask |= L.PROJECT_VCF_FORMATS_ON_DEVICE
         opt = L.ScanOptions(L.FORMATS[fmt], L.COMPRESSION[compression], batch_size,
                             info_field.encode() if info_field else None, region.encode() if region else None,
                             1 if use_index else 0, 1 if gpu_parse else 0, mask)
@@ -594,9 +600,11 @@ class Scan:
 class VCFParser:
     """VCF record parsing on the GPU (exon_hip_vcf_parser_*): text slab in HBM -> device-layout columns in HBM."""
 
-    def __init__(self, ctx, contigs, info_field=None, max_slab_bytes=64 << 20, key_types=None):
+    def __init__(self, ctx, contigs, info_field=None, max_slab_bytes=64 << 20, key_types=None, format_key_types=None):
         """key_types: {INFO key: "i" | "f" | "b" | "c" | "s"} as the header's ##INFO lines type them, for the `info` text column
-        (parse_host(..., info_text=True)); {} = the reserved keys of the specification alone."""
+        (parse_host(..., info_text=True)); {} = the reserved keys of the specification alone.
+        format_key_types: {FORMAT key: "i" | "f" | "c" | "s"} as the ##FORMAT lines type them, for the `formats` text column
+        (parse_host(..., formats_text=True)); {} = the reserved FORMAT keys alone (GT is known by its name)."""
         self.ctx = ctx
         names = (C.c_char_p * max(len(contigs), 1))(*[c.encode() for c in contigs])
         h = C.c_void_p()
@@ -605,6 +613,8 @@ class VCFParser:
         self.h = h
         if key_types is not None:
             self.set_key_types(key_types)
+        if format_key_types is not None:
+            self.set_format_key_types(format_key_types)
         self.has_info = bool(info_field)
         self.cap_items = max_slab_bytes // 2 + 1  # items a list key's buffers hold (exon_hip_vcf_parser_create)
 
@@ -620,11 +630,18 @@ class VCFParser:
         kinds = "".join(key_types.values()).encode()
         self.ctx._check(self.ctx.lib.exon_hip_vcf_parser_set_key_types(self.h, packed, kinds, len(key_types)))
 
-    def parse_host(self, text, misalign=0, info_text=False):
+    def set_format_key_types(self, key_types):
+        """The value types of the header's FORMAT keys (exon_hip_vcf_parser_set_format_key_types)."""
+        packed = b"".join(k.encode() + b"\0" for k in key_types)
+        kinds = "".join(key_types.values()).encode()
+        self.ctx._check(self.ctx.lib.exon_hip_vcf_parser_set_format_key_types(self.h, packed, kinds, len(key_types)))
+
+    def parse_host(self, text, misalign=0, info_text=False, formats_text=False):
         """Test helper: copy `text` (bytes of complete lines) to HBM (`misalign` bytes past a 16-byte boundary), parse,
         bring the columns back as numpy arrays.  info_text: the `info` Utf8 column too, printed on the device
         (exon_hip_vcf_parser_info_text): res["info_text"] = {"n_bytes", "n_undecided"} + "offsets" / "values" when 0 rows are
-        undecided (nothing when the parse itself left rows undecided)."""
+        undecided (nothing when the parse itself left rows undecided).  formats_text: the same for the `formats` column
+        (exon_hip_vcf_parser_formats_text): res["formats_text"]."""
         buf = np.frombuffer(text, np.uint8)
         d = self.ctx.to_device(np.concatenate([np.full(misalign, 10, np.uint8), buf, np.zeros(64, np.uint8)]))
         cols = self.parse_device(d.ptr + misalign, len(buf))
@@ -666,6 +683,14 @@ class VCFParser:
                 it["offsets"] = get(t.offsets, np.int32, n + 1)
                 it["values"] = get(t.values, np.uint8, t.n_bytes)
             res["info_text"] = it
+        if formats_text and cols.n_undecided == 0 and n:
+            t = L.VCFInfoText()
+            self.ctx._check(self.ctx.lib.exon_hip_vcf_parser_formats_text(self.h, None, C.byref(t)))
+            ft = {"n_bytes": t.n_bytes, "n_undecided": t.n_undecided}
+            if t.n_undecided == 0:
+                ft["offsets"] = get(t.offsets, np.int32, n + 1)
+                ft["values"] = get(t.values, np.uint8, t.n_bytes)
+            res["formats_text"] = ft
         return res
 
     def filters(self):

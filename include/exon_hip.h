@@ -572,8 +572,12 @@ typedef struct exon_hip_scan_options {
                              info comes from the host reader and from the GPU pipeline (text_columns.hip: k_vcf_info_measure /
                              k_vcf_info_fill print the entries on the device; a row the device does not decide -- a missing
                              value, an integer outside i32, a float of more than 19 significant digits, a byte >= 0x80
-                             -- hands the file to the host reader).  formats is built by the host reader only: a gpu_parse scan
-                             that asks for it decodes on the host.
+                             -- hands the file to the host reader).  formats is built by the host reader: a gpu_parse scan that
+                             asks for it decodes on the host, UNLESS it also sets the modifier EXON_HIP_PROJECT_VCF_FORMATS_ON_DEVICE
+                             (32; no column of its own, valid only next to bit 16, EXON_HIP_EINVAL without it): then the column
+                             comes from the GPU pipeline too (text_columns.hip: k_fmt_*, one thread a sample), and a row the
+                             device does not decide -- a missing sample value, an allele that is no number, more than 16 FORMAT
+                             keys, a byte >= 0x80, what `info` hands over for its numbers -- hands the file to the host reader.
                              BCF: id List<Utf8>, ref Utf8, alt List<Utf8> through the reference's EAGER builder (lists with their
                              items, never NULL: eager_array_builder.rs:112-134); SAM: the BAM columns from the line's fields
                              (exon-sam/src/array_builder.rs:101-185); both from the host readers and from the GPU pipeline.
@@ -586,7 +590,8 @@ typedef struct exon_hip_scan_options {
 #define EXON_HIP_PROJECT_VCF_REF 2ull
 #define EXON_HIP_PROJECT_VCF_ALT 4ull
 #define EXON_HIP_PROJECT_VCF_INFO 8ull     /* host reader and GPU pipeline (the entries are printed again on the device) */
-#define EXON_HIP_PROJECT_VCF_FORMATS 16ull /* host reader only: a gpu_parse scan that asks for it decodes on the host */
+#define EXON_HIP_PROJECT_VCF_FORMATS 16ull /* host reader; the GPU pipeline only with the modifier below (else a gpu_parse scan decodes on the host) */
+#define EXON_HIP_PROJECT_VCF_FORMATS_ON_DEVICE 32ull /* (additive; the ABI stays 5) a modifier, not a column: with bit 16, `formats` is printed on the device */
 #define EXON_HIP_PROJECT_BAM_NAME 1ull
 #define EXON_HIP_PROJECT_BAM_CIGAR 2ull
 #define EXON_HIP_PROJECT_BAM_SEQUENCE 4ull
@@ -776,6 +781,13 @@ typedef struct exon_hip_vcf_info_text {
 } exon_hip_vcf_info_text;
 int exon_hip_vcf_parser_set_key_types(exon_hip_vcf_parser* parser, const char* packed_keys, const char* kinds, int32_t n);
 int exon_hip_vcf_parser_info_text(exon_hip_vcf_parser* parser, void* stream, exon_hip_vcf_info_text* out);
+/* (additive; the ABI stays 5) The `formats` Utf8 column, built on the device: FORMAT, a TAB, every sample printed again (see
+ * exon_hip_scan_options.projection).  set_format_key_types: the value types of the header's ##FORMAT lines, packed like
+ * set_key_types'; kinds i f c s (b is no FORMAT type: EXON_HIP_EINVAL).  GT is known by its name whatever the header says; the
+ * reserved FORMAT keys of the specification keep their types unless the header names them; n = 0: the reserved keys alone.
+ * formats_text follows info_text's contract and fills the same struct. */
+int exon_hip_vcf_parser_set_format_key_types(exon_hip_vcf_parser* parser, const char* packed_keys, const char* kinds, int32_t n);
+int exon_hip_vcf_parser_formats_text(exon_hip_vcf_parser* parser, void* stream, exon_hip_vcf_info_text* out);
 int exon_hip_vcf_parser_destroy(exon_hip_vcf_parser* parser);
 
 /* ---- BGZF inflate on the GPU (compressed blocks in HBM -> inflated bytes in HBM) ------------------------------------

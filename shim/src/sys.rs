@@ -13,6 +13,11 @@ pub struct exon_hip_plan { _p: [u8; 0] }
 pub struct exon_hip_stream { _p: [u8; 0] }
 #[repr(C)]
 pub struct exon_hip_scan { _p: [u8; 0] }
+#[repr(C)]
+pub struct exon_hip_vcf_parser { _p: [u8; 0] }
+/// exon_hip_vcf_parser_info_text's and _formats_text's result (device pointers, owned by the parser): handled by pointer only
+#[repr(C)]
+pub struct exon_hip_vcf_info_text { _p: [u8; 0] }
 
 pub const EXON_HIP_ABI_VERSION: i32 = 5;
 pub const EXON_HIP_PLAN_REGION_COUNT: i32 = 2;
@@ -53,7 +58,8 @@ pub const EXON_HIP_PROJECT_GTF_ATTRIBUTES: u64 = 256; // exon_hip_scan_options.p
 pub const EXON_HIP_PROJECT_GFF_ATTRIBUTES: u64 = 256; // exon_hip_scan_options.projection: GFF column 8, Map<Utf8, List<Utf8>>
 // exon_hip_scan_options.projection of a VCF scan: the reference's unparsed Utf8 columns (the parsed entries printed again)
 pub const EXON_HIP_PROJECT_VCF_INFO: u64 = 8; // from the host reader and, printed on the device, from the GPU pipeline
-pub const EXON_HIP_PROJECT_VCF_FORMATS: u64 = 16; // host reader only: a gpu_parse scan that asks for it decodes on the host
+pub const EXON_HIP_PROJECT_VCF_FORMATS: u64 = 16; // host reader; the GPU pipeline only with the modifier below
+pub const EXON_HIP_PROJECT_VCF_FORMATS_ON_DEVICE: u64 = 32; // a modifier, not a column: with bit 16, `formats` is printed on the device
 pub const EXON_HIP_COMPRESSION_AUTO: i32 = 0;
 pub const EXON_HIP_MAX_GROUPS: i32 = 4096;
 pub const EXON_HIP_REGION_OPEN_END: i64 = i64::MAX;
@@ -113,6 +119,9 @@ pub struct exon_hip_device_info {
 
 extern "C" {
     pub fn exon_hip_abi_version() -> c_int;
+    /// the `formats` Utf8 column printed on the device: the ##FORMAT lines' value types (kinds i f c s), then the column of the last parsed slab
+    pub fn exon_hip_vcf_parser_set_format_key_types(parser: *mut exon_hip_vcf_parser, packed_keys: *const c_char, kinds: *const c_char, n: i32) -> c_int;
+    pub fn exon_hip_vcf_parser_formats_text(parser: *mut exon_hip_vcf_parser, stream: *mut c_void, out: *mut exon_hip_vcf_info_text) -> c_int;
     pub fn exon_hip_ctx_create(device: c_int, out: *mut *mut exon_hip_ctx) -> c_int;
     pub fn exon_hip_ctx_destroy(ctx: *mut exon_hip_ctx) -> c_int;
     pub fn exon_hip_ctx_info(ctx: *mut exon_hip_ctx, out: *mut exon_hip_device_info) -> c_int;

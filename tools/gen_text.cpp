@@ -7,6 +7,8 @@
 // `gen_text gtf <rows> <out> [attrs]` an Ensembl-like GTF table with the same (seqname, start) layout; attrs: rich ninth fields.
 // `gen_text bed <rows> <out> [n=6]` a BED table of n-field lines (3, 4, 5, 6 or 12; `mix`: all five, changing from row to row),
 // sorted by (reference_sequence_name, start); 0-based starts, scores 0 .. 65535, strands + - .
+// `gen_text vcf <rows> <out> [samples=0]` with samples > 0: a FORMAT field GT:DP:GQ:PL and that many samples behind every row
+// (##FORMAT lines and sample names in the header); 0 writes the file without them, byte for byte as before.
 // build: g++ -O2 -std=c++17 tools/gen_text.cpp -o tools/bin/gen_text      run: gen_text vcf <rows> <out.vcf>
 #include <cstdint>
 #include <cstdio>
@@ -17,7 +19,7 @@ static inline uint64_t mix64(uint64_t z) { z = (z ^ (z >> 30)) * 0xBF58476D1CE4E
 static inline uint64_t rnd(uint64_t seed, uint64_t col, uint64_t i) { return mix64(seed + col * 0xD1B54A32D192ED03ULL + (i + 1) * 0x9E3779B97F4A7C15ULL); }
 static inline uint32_t pct_thr(int p) { return (uint32_t)((((uint64_t)p) << 32) / 100); }
 int main(int argc, char** argv) {
-  if (argc < 4) { fprintf(stderr, "usage: gen_text vcf|bcf|fastq|bam|sam|gff|gtf|bed <rows> <out> [read_len | attrs | n] [ragged]\n"); return 2; }
+  if (argc < 4) { fprintf(stderr, "usage: gen_text vcf|bcf|fastq|bam|sam|gff|gtf|bed <rows> <out> [read_len | attrs | n | samples] [ragged]\n"); return 2; }
   const int64_t n = (int64_t)atof(argv[2]);
   FILE* f = fopen(argv[3], "wb");
   if (!f) return 1;
@@ -396,8 +398,29 @@ int main(int argc, char** argv) {
     fclose(f);
     return 0;
   }
+  const int n_samples = argc > 4 ? atoi(argv[4]) : 0;
   fputs("##fileformat=VCFv4.3\n##contig=<ID=1>\n##INFO=<ID=AF,Number=1,Type=Float,Description=\"AF\">\n"
-        "##FILTER=<ID=q10,Description=\"q\">\n##FILTER=<ID=s50,Description=\"s\">\n#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\n", f);
+        "##FILTER=<ID=q10,Description=\"q\">\n##FILTER=<ID=s50,Description=\"s\">\n", f);
+  if (n_samples > 0) {
+    fputs("##FORMAT=<ID=GT,Number=1,Type=String,Description=\"GT\">\n##FORMAT=<ID=DP,Number=1,Type=Integer,Description=\"DP\">\n"
+          "##FORMAT=<ID=GQ,Number=1,Type=Integer,Description=\"GQ\">\n##FORMAT=<ID=PL,Number=G,Type=Integer,Description=\"PL\">\n", f);
+    fputs("#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\tFORMAT", f);
+    for (int k = 0; k < n_samples; ++k) fprintf(f, "\tS%d", k + 1);
+    fputc('\n', f);
+  } else {
+    fputs("#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\n", f);
+  }
+  // sample k of row i: a genotype of two alleles in either phasing, a depth, a quality, three likelihoods (one of them 0)
+  auto samples = [&](int64_t i) {
+    if (n_samples <= 0) return;
+    fputs("\tGT:DP:GQ:PL", f);
+    for (int k = 0; k < n_samples; ++k) {
+      const uint64_t r = rnd(9, (uint64_t)k, i);
+      const unsigned a0 = (unsigned)(r & 1), a1 = (unsigned)((r >> 1) & 1), dp = (unsigned)((r >> 8) % 60) + 1, gq = (unsigned)((r >> 16) % 100);
+      const unsigned p1 = (unsigned)((r >> 24) % 255), p2 = (unsigned)((r >> 32) % 255);
+      fprintf(f, "\t%u%c%u:%u:%u:%u,%u,%u", a0, ((r >> 2) & 1) ? '|' : '/', a1, dp, gq, a0 + a1 == 0 ? 0u : p1 + 1, a0 + a1 == 1 ? 0u : p1 + 2, a0 + a1 == 2 ? 0u : p2 + 3);
+    }
+  };
   const char* FILT[5] = {"PASS", ".", "q10", "q10;s50", "s50"};
   const uint32_t t0 = pct_thr(85), t1 = pct_thr(90), t2 = pct_thr(96), t3 = pct_thr(99);
   for (int64_t i = 0; i < n; ++i) {
@@ -412,8 +435,10 @@ int main(int argc, char** argv) {
     const int fid = (u >= t0) + (u >= t1) + (u >= t2) + (u >= t3);
     char q[16];
     if (qv) snprintf(q, sizeof q, "%u.%u", kq / 10, kq % 10); else strcpy(q, ".");
-    if (av) fprintf(f, "1\t%lld\t.\tA\tC\t%s\t%s\tAF=%.9g\n", (long long)(i + 1), q, FILT[fid], (double)a);
-    else fprintf(f, "1\t%lld\t.\tA\tC\t%s\t%s\t.\n", (long long)(i + 1), q, FILT[fid]);
+    if (av) fprintf(f, "1\t%lld\t.\tA\tC\t%s\t%s\tAF=%.9g", (long long)(i + 1), q, FILT[fid], (double)a);
+    else fprintf(f, "1\t%lld\t.\tA\tC\t%s\t%s\t.", (long long)(i + 1), q, FILT[fid]);
+    samples(i);
+    fputc('\n', f);
   }
   fclose(f);
   return 0;
