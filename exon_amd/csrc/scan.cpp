@@ -1340,8 +1340,17 @@ class GpuTextSource {
     if (more) reader_ = std::thread([this, k] { run_on(local_cpus_); fill(k ^ 1, &nxt_); });  // overlaps with everything the GPU does below
     if (!more && n_text > 0) {  // last line without a terminator (a carried tail never ends in one)
       // the slab's last byte is on the host unless the slab is a carried tail only (cur_.n and front_extra both 0)
-      const bool ends_nl = (cur_.n > 0 || cur_.front_extra > 0) && cur_.last_byte == '\n';
+      const bool fresh = cur_.n > 0 || cur_.front_extra > 0;
+      const bool ends_nl = fresh && cur_.last_byte == '\n';
       if (!ends_nl) {
+        // A CR that ends the input is a byte of the last field: the readers drop one only in front of a '\n' (host/io.h read_line).
+        // Behind an appended '\n' the parsers would drop it, so that input is the host reader's.
+        uint8_t lastb = cur_.last_byte;
+        if (!fresh) {  // (the copy of the carried tail is queued on hs_ in front of this one)
+          HIP_TRY(ctx_, hipMemcpyAsync(&lastb, d_text_[k] + front + n_text - 1, 1, hipMemcpyDeviceToHost, hs_));
+          HIP_TRY(ctx_, hipStreamSynchronize(hs_));
+        }
+        if (lastb == '\r') return 1;
         HIP_TRY(ctx_, hipMemsetAsync(d_text_[k] + front + n_text, '\n', 1, hs_));
         ++n_text;
       }
@@ -1457,6 +1466,7 @@ class GpuTextSource {
       uint8_t lastb = 0;
       HIP_TRY(ctx_, hipMemcpyAsync(&lastb, d_text_[k] + front + n_text - 1, 1, hipMemcpyDeviceToHost, hs_));
       HIP_TRY(ctx_, hipStreamSynchronize(hs_));
+      if (lastb == '\r') return 1;  // a CR without its LF is a byte of the last field (see next()): the host reader's
       if (lastb != '\n') {
         HIP_TRY(ctx_, hipMemsetAsync(d_text_[k] + front + n_text, '\n', 1, hs_));
         ++n_text;

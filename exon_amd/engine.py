@@ -654,7 +654,7 @@ class VCFParser:
                 self.ctx._check(self.ctx.lib.exon_hip_memcpy_d2h(self.ctx.h, _np_ptr(out), ptr, out.nbytes, None))
             return out
 
-        res = {"n_rows": n, "n_undecided": cols.n_undecided,
+        res = {"n_rows": n, "n_undecided": cols.n_undecided, "consumed_bytes": cols.consumed_bytes,
                "chrom_id": get(cols.chrom_id, np.int32, n), "pos": get(cols.pos, np.int64, n),
                "pos_valid": get(cols.pos_valid, np.uint8, nb), "qual": get(cols.qual, np.float32, n),
                "qual_valid": get(cols.qual_valid, np.uint8, nb), "filter_id": get(cols.filter_id, np.int32, n)}
@@ -886,6 +886,7 @@ class SAMParser:
         h = C.c_void_p()
         ctx._check(ctx.lib.exon_hip_sam_parser_create(ctx.h, names, len(references), max_slab_bytes, C.byref(h)))
         self.h = h
+        self.max_rows = max_slab_bytes // 12 + 1  # rows the column buffers hold (exon_hip_sam_parser_create)
 
     def parse_device(self, d_text, n_bytes, stream=None):
         cols = L.BAMColumns()
@@ -895,11 +896,12 @@ class SAMParser:
 
     def parse_host(self, text, misalign=0):
         """Test helper: copy `text` (complete alignment lines) to HBM (`misalign` bytes past a 16-byte boundary), parse, bring the
-        columns back as numpy arrays -- of every row, undecided ones included (their slots hold whatever was there)."""
+        columns back as numpy arrays -- of every row, undecided ones included (their slots hold whatever was there); of a slab
+        with more lines than the row buffers hold (n_rows says how many, n_undecided is not 0) the rows that fit."""
         buf = np.frombuffer(text, np.uint8)
         d = self.ctx.to_device(np.concatenate([np.full(misalign, 10, np.uint8), buf, np.zeros(64, np.uint8)]))
         cols = self.parse_device(d.ptr + misalign, len(buf))
-        n = cols.n_rows
+        n = min(cols.n_rows, self.max_rows)
         nb = (n + 7) // 8
 
         def get(ptr, dtype, count):
@@ -908,7 +910,7 @@ class SAMParser:
                 self.ctx._check(self.ctx.lib.exon_hip_memcpy_d2h(self.ctx.h, _np_ptr(out), ptr, out.nbytes, None))
             return out
 
-        return {"n_rows": n, "n_undecided": cols.n_undecided, "consumed_bytes": cols.consumed_bytes,
+        return {"n_rows": cols.n_rows, "n_undecided": cols.n_undecided, "consumed_bytes": cols.consumed_bytes,
                 "flag": get(cols.flag, np.int32, n), "mapq": get(cols.mapq, np.uint8, n),
                 "mapq_valid": get(cols.mapq_valid, np.uint8, nb), "ref_id": get(cols.ref_id, np.int32, n),
                 "ref_valid": get(cols.ref_valid, np.uint8, nb), "start": get(cols.start, np.int64, n),
@@ -1055,7 +1057,8 @@ class FASTQParser:
         shift = (d.ptr + misalign) - (v.text_base or (d.ptr + misalign))
         return {"n_reads": n, "n_undecided": v.n_undecided, "consumed_bytes": v.consumed_bytes, "views": v, "d_text": v.text_base,
                 "keepalive": d, "seq_start": get(v.seq_start) - shift, "seq_end": get(v.seq_end) - shift,
-                "qual_start": get(v.qual_start) - shift, "qual_end": get(v.qual_end) - shift}
+                "qual_start": get(v.qual_start) - shift, "qual_end": get(v.qual_end) - shift,
+                "head_start": get(v.head_start) - shift, "head_end": get(v.head_end) - shift}
 
     def close(self):
         if self.h:
