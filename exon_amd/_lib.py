@@ -162,6 +162,7 @@ PLAN_OVERLAP_COUNT = 6
 PLAN_WITHIN_COUNT = 7
 PLAN_CMP_MINMAX_BY_GROUP = 8
 PLAN_READ_STATS_HIST = 9
+PLAN_SEQ_STATS_HIST = 10
 LAUNCH_ACCUMULATE = 0
 LAUNCH_OVERWRITE = 1
 CMP = {">": 0, ">=": 1, "<": 2, "<=": 3, "=": 4, "==": 4, "!=": 5, "<>": 5}
@@ -272,6 +273,9 @@ SIGNATURES = {
     "exon_hip_fasta_parser_create": (C.c_int, [_vp, _i64, C.POINTER(_vp)]),
     "exon_hip_fasta_parser_parse": (C.c_int, [_vp, _vp, _vp, _i64, _i32, C.POINTER(FASTAViews)]),
     "exon_hip_fasta_parser_destroy": (C.c_int, [_vp]),
+    "exon_hip_seq_stats_hist": (C.c_int, [_vp, _vp, _colp, _i64, _i32, _vp]),
+    "exon_hip_seq_stats_hist_views": (C.c_int, [_vp, _vp, C.POINTER(FASTAViews), _i32, _vp]),
+    "exon_hip_seq_stats_layout": (C.c_int, [_i32, C.POINTER(_i64)]),
     "exon_hip_bam_parser_create": (C.c_int, [_vp, _i32, _i64, C.POINTER(_vp)]),
     "exon_hip_bam_parser_parse": (C.c_int, [_vp, _vp, _vp, _i64, C.POINTER(BAMColumns)]),
     "exon_hip_bam_parser_destroy": (C.c_int, [_vp]),

@@ -559,6 +559,52 @@ int exon_op_read_stats_hist(exon_hip_ctx* ctx, void* stream, const exon_hip_colu
                           (const uint8_t*)qual->values, qual->offsets, qual->offsets ? qual->offsets + 1 : nullptr, n_reads, lmax, d_state, flags);
 }
 
+// K10 (seq_stats.hip): both forms share the checks on the state
+static int seq_stats_checks(exon_hip_ctx* ctx, const char* who, int32_t lmax, const int64_t* d_state) {
+  if (!ctx || !d_state) return fail(ctx, EXON_HIP_EINVAL, "%s: NULL argument", who);
+  if (lmax < 1 || lmax > 65536) return fail(ctx, EXON_HIP_EINVAL, "lmax %d out of range", lmax);
+  if (reinterpret_cast<uintptr_t>(d_state) & 7) return fail(ctx, EXON_HIP_EINVAL, "%s: d_state must be 8-byte aligned", who);
+  return EXON_HIP_OK;
+}
+
+int exon_op_seq_stats_hist(exon_hip_ctx* ctx, void* stream, const exon_hip_column* seq, int64_t n_records, int32_t lmax, int64_t* d_state,
+                           int flags) {
+  static const char* who = "exon_hip_seq_stats_hist";
+  if (int rc = seq_stats_checks(ctx, who, lmax, d_state)) return rc;
+  if (n_records < 0) return fail(ctx, EXON_HIP_EINVAL, "n_records < 0");
+  hipStream_t s = pick_stream(ctx, stream);
+  if (n_records == 0) return empty_input(ctx, s, flags, d_state, (size_t)exon::seq_stats_words(lmax) * 8);
+  if (!seq) return fail(ctx, EXON_HIP_EINVAL, "%s: the sequence column is NULL", who);
+  if (seq->length < n_records) return fail(ctx, EXON_HIP_EINVAL, "%s: length < n_records", who);
+  if (!seq->offsets) return fail(ctx, EXON_HIP_EINVAL, "%s: offsets NULL", who);
+  // (validity is not read, as in K5 and K9; values may be NULL when every record is empty: nothing is loaded from it then)
+  Workspace ws;
+  int rc;
+  if ((rc = get_workspace(ctx, s, exon::seq_stats_partial_words(), &ws))) return fail(ctx, rc, "workspace allocation failed");
+  HIP_TRY(ctx, exon::launch_seq_stats_hist(s, cfg_for(ctx, flags), ws, (const uint8_t*)seq->values, seq->offsets, n_records, lmax, d_state));
+  return EXON_HIP_OK;
+}
+
+int exon_op_seq_stats_hist_views(exon_hip_ctx* ctx, void* stream, const exon_hip_fasta_views* v, int32_t lmax, int64_t* d_state, int flags) {
+  static const char* who = "exon_hip_seq_stats_hist_views";
+  if (int rc = seq_stats_checks(ctx, who, lmax, d_state)) return rc;
+  if (!v) return fail(ctx, EXON_HIP_EINVAL, "%s: views is NULL", who);
+  if (v->n_undecided) return fail(ctx, EXON_HIP_EINVAL, "%s: the parser left the slab undecided: decode it on the host", who);
+  if (v->n_records < 0) return fail(ctx, EXON_HIP_EINVAL, "n_records < 0");
+  hipStream_t s = pick_stream(ctx, stream);
+  if (v->n_records == 0) return empty_input(ctx, s, flags, d_state, (size_t)exon::seq_stats_words(lmax) * 8);
+  if (!v->text_base || !v->head_start || !v->seq_offsets || !v->line_end || !v->line_dst) return fail(ctx, EXON_HIP_EINVAL, "%s: a view is NULL", who);
+  if ((reinterpret_cast<uintptr_t>(v->text_base) & 15) || v->first_line_start < 0 || v->first_line_start > 15 || v->consumed_bytes < 0 ||
+      v->first_line_start + v->consumed_bytes > v->text_bytes)
+    return fail(ctx, EXON_HIP_EINVAL, "%s: text_base / first_line_start / consumed_bytes are not what exon_hip_fasta_parser_parse returns", who);
+  Workspace ws;
+  int rc;
+  if ((rc = get_workspace(ctx, s, exon::seq_stats_partial_words(), &ws))) return fail(ctx, rc, "workspace allocation failed");
+  HIP_TRY(ctx, exon::launch_seq_stats_hist_views(s, cfg_for(ctx, flags), ws, v->text_base, v->first_line_start, v->consumed_bytes, v->n_records, v->n_lines,
+                                                 v->seq_bytes, v->head_start, v->seq_offsets, v->line_end, v->line_dst, lmax, d_state));
+  return EXON_HIP_OK;
+}
+
 extern "C" {
 
 int exon_hip_region_count(exon_hip_ctx* ctx, void* stream, const exon_hip_column* chrom_id, const exon_hip_column* pos,
@@ -670,6 +716,27 @@ int exon_hip_read_stats_layout(int32_t lmax, int64_t* out /*[5]*/) {
   out[2] = out[1] + lmax + 1;
   out[3] = out[2] + 102;
   out[4] = out[3] + 257;
+  return EXON_HIP_OK;
+}
+
+int exon_hip_seq_stats_hist(exon_hip_ctx* ctx, void* stream, const exon_hip_column* sequence, int64_t n_records, int32_t lmax, int64_t* d_state) {
+  return exon_op_seq_stats_hist(ctx, stream, sequence, n_records, lmax, d_state, EXON_HIP_LAUNCH_ACCUMULATE);
+}
+
+int exon_hip_seq_stats_hist_views(exon_hip_ctx* ctx, void* stream, const exon_hip_fasta_views* views, int32_t lmax, int64_t* d_state) {
+  return exon_op_seq_stats_hist_views(ctx, stream, views, lmax, d_state, EXON_HIP_LAUNCH_ACCUMULATE);
+}
+
+// word offsets of the five sections of K10's state, and its size; host only
+int exon_hip_seq_stats_layout(int32_t lmax, int64_t* out /*[6]*/) {
+  if (!out) return fail(nullptr, EXON_HIP_EINVAL, "exon_hip_seq_stats_layout: out is NULL");
+  if (lmax < 1 || lmax > 65536) return fail(nullptr, EXON_HIP_EINVAL, "lmax %d out of range", lmax);
+  out[0] = 0;
+  out[1] = 3;
+  out[2] = out[1] + 256;
+  out[3] = out[2] + lmax + 2;
+  out[4] = out[3] + 32;
+  out[5] = out[4] + 102;
   return EXON_HIP_OK;
 }
 

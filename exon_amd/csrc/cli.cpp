@@ -20,6 +20,7 @@
 //   SELECT filter, MIN(qual), MAX(qual), COUNT(*) FROM v WHERE info."AF" > 0.01 GROUP BY filter -- K8 (also MIN / MAX(info."DP"))
 //   SELECT * FROM fastq_quality_histogram('<p>'[, 'gzip'])                                        -- K5
 //   SELECT * FROM fastq_read_stats('<p>'[, 'gzip'])                                               -- K9
+//   SELECT * FROM fasta_seq_stats('<p>'[, 'gzip'])                                                -- K10
 //   SELECT COUNT(*) FROM <bam table> WHERE bam_region_filter('<r>', reference, start, end)          -- K6 (plain table; INDEXED_BAM plans chunks on the host)
 //   DROP TABLE t;
 #include <dirent.h>
@@ -293,7 +294,7 @@ void open_scan(const Source& src, const std::string& file, const char* info_fiel
   // INDEXED_* tables / *_indexed_scan: plan BGZF chunks from <file>.tbi / <file>.bai
   // (exon-core/src/datasources/indexed_file/indexed_bgzf_file.rs:129-155)
   o.use_index = (src.indexed && !region.empty()) ? 1 : 0;
-  o.gpu_parse = (for_gpu_query && (src.format == EXON_HIP_FORMAT_VCF || src.format == EXON_HIP_FORMAT_FASTQ || src.format == EXON_HIP_FORMAT_BAM || src.format == EXON_HIP_FORMAT_BCF || src.format == EXON_HIP_FORMAT_SAM || src.format == EXON_HIP_FORMAT_GFF || src.format == EXON_HIP_FORMAT_GTF || src.format == EXON_HIP_FORMAT_BED) &&
+  o.gpu_parse = (for_gpu_query && (src.format == EXON_HIP_FORMAT_VCF || src.format == EXON_HIP_FORMAT_FASTQ || src.format == EXON_HIP_FORMAT_BAM || src.format == EXON_HIP_FORMAT_BCF || src.format == EXON_HIP_FORMAT_SAM || src.format == EXON_HIP_FORMAT_GFF || src.format == EXON_HIP_FORMAT_GTF || src.format == EXON_HIP_FORMAT_BED || src.format == EXON_HIP_FORMAT_FASTA) &&
                  region.empty() && gpu_parse_enabled()) ? 1 : 0;
   ck(nullptr, exon_hip_scan_open(file.c_str(), &o, &g->s));
 }
@@ -427,7 +428,7 @@ Source resolve_from(Session& se, Parser& ps) {
   Source src;
   const std::string name = ps.ident();
   const std::string lname = lower(name);
-  if (ps.accept_sym("(")) {  // table function: <fmt>_scan / <fmt>_indexed_scan / fastq_quality_histogram / fastq_read_stats
+  if (ps.accept_sym("(")) {  // table function: <fmt>_scan / <fmt>_indexed_scan / fastq_quality_histogram / fastq_read_stats / fasta_seq_stats
     const std::string path = ps.str();
     std::string arg2;
     if (ps.accept_sym(",")) arg2 = ps.str();
@@ -583,7 +584,7 @@ void exec_select(Session& se, Parser& ps) {
     proj.push_back(item);
   } while (ps.accept_sym(","));
   ps.expect_kw("from");
-  const bool hist = ps.is_kw("fastq_quality_histogram"), read_stats = ps.is_kw("fastq_read_stats");
+  const bool hist = ps.is_kw("fastq_quality_histogram"), read_stats = ps.is_kw("fastq_read_stats"), seq_stats = ps.is_kw("fasta_seq_stats");
   Source src = resolve_from(se, ps);
   Predicate pr;
   if (ps.accept_kw("where")) pr = parse_where(ps, src.format);
@@ -644,6 +645,34 @@ void exec_select(Session& se, Parser& ps) {
     static const char* const total_names[4] = {"reads", "bases", "gc", "quality_sum"};
     std::vector<std::vector<std::string>> rows;
     for (int st = 0; st < 4; ++st)
+      for (int64_t w = at[st]; w < at[st + 1]; ++w)
+        if (st == 0 || total[(size_t)w]) rows.push_back({stat_names[st], st == 0 ? std::string(total_names[w]) : std::to_string(w - at[st]), std::to_string(total[(size_t)w])});
+    print_table({"stat", "bin", "count"}, rows, se.quiet);
+    return;
+  }
+
+  if (seq_stats) {  // K10: the per-record FASTA tables; every word of the state adds, so the files' states do
+    exon_hip_ctx* ctx = se.gpu();
+    const int lmax = 65536;
+    int64_t at[6];
+    ck(nullptr, exon_hip_seq_stats_layout(lmax, at));
+    std::vector<int64_t> total((size_t)at[5], 0);
+    for (const auto& f : src.files) {
+      ScanGuard g; open_scan(src, f, nullptr, "", &g, true);
+      StreamGuard sg;
+      exon_hip_plan_desc d; memset(&d, 0, sizeof d);
+      d.kind = EXON_HIP_PLAN_SEQ_STATS_HIST; d.lmax = lmax; d.columns[0] = 2;
+      ck(ctx, exon_hip_plan_create(ctx, &d, &sg.p));
+      ck(ctx, exon_hip_stream_open(sg.p, 0, &sg.s));
+      ck(ctx, exon_hip_stream_consume_scan(sg.s, g.s, nullptr));
+      std::vector<int64_t> h((size_t)at[5]);
+      ck(ctx, exon_hip_stream_finish(sg.s, h.data(), nullptr));
+      for (size_t i = 0; i < h.size(); ++i) total[i] += h[i];
+    }
+    static const char* const stat_names[5] = {"total", "composition", "length", "length_log2", "gc_percent"};
+    static const char* const total_names[3] = {"records", "bases", "gc"};
+    std::vector<std::vector<std::string>> rows;  // (a composition row shows its byte as a number)
+    for (int st = 0; st < 5; ++st)
       for (int64_t w = at[st]; w < at[st + 1]; ++w)
         if (st == 0 || total[(size_t)w]) rows.push_back({stat_names[st], st == 0 ? std::string(total_names[w]) : std::to_string(w - at[st]), std::to_string(total[(size_t)w])});
     print_table({"stat", "bin", "count"}, rows, se.quiet);
@@ -995,6 +1024,7 @@ int main(int argc, char** argv) {
              "  functions: fasta_scan fastq_scan vcf_scan bam_scan gff_scan gtf_scan bed_scan ('<path>'[, 'gzip']); vcf_indexed_scan bam_indexed_scan gff_indexed_scan ('<path>', '<region>');\n"
              "             fastq_quality_histogram('<path>')\n"
              "             fastq_read_stats('<path>')\n"
+             "             fasta_seq_stats('<path>'[, 'gzip'])\n"
              "  queries:   SELECT COUNT(*) FROM <src> [WHERE chrom = 'c' AND pos >= a AND pos <= b | vcf_region_filter('r', chrom) | bam_region_filter('r', reference, start, end)\n"
              "             | gff_region_filter('r', seqname[, start])]\n"
              "             SELECT COUNT(*) FROM <bam|sam> WHERE [bam_region_filter('r', reference, start, end) AND] flag & M = V [AND CAST(mapping_quality AS INT) >= q]\n"

@@ -92,6 +92,22 @@ hipError_t launch_read_stats_hist(hipStream_t s, const LaunchCfg& cfg, const Wor
                                   const int32_t* se, const uint8_t* qbytes, const int32_t* qs, const int32_t* qe, int64_t n_reads, int lmax,
                                   int64_t* d_state);
 
+// K10 (seq_stats.hip): per-record FASTA statistics -- totals, byte composition, length, log2 length and GC percent histograms; state
+// layout in include/exon_hip.h.  Work is divided by source bytes: tiles of SS_T bytes; workspace: one u32 per tile in ws.partials
+// (seq_stats_partial_words() 8-byte words cover any int32-offset payload).  1 <= lmax <= 65536.  cfg.overwrite: state := this launch.
+constexpr int SS_T = 16384;
+constexpr int64_t SS_MAX_TILES = (((int64_t)1 << 31) + 16) / SS_T + 1;
+constexpr int64_t seq_stats_words(int lmax) { return 3 + 256 + ((int64_t)lmax + 2) + 32 + 102; }
+size_t seq_stats_partial_words();
+// Arrow form: record r = values[offsets[r], offsets[r + 1]); no byte outside [offsets[0], offsets[n_records]) is loaded
+hipError_t launch_seq_stats_hist(hipStream_t s, const LaunchCfg& cfg, const Workspace& ws, const uint8_t* values, const int32_t* offsets,
+                                 int64_t n_records, int lmax, int64_t* d_state);
+// views form: the fields of an exon_hip_fasta_views; no byte outside [first_line_start, first_line_start + consumed_bytes) of
+// text_base (16-byte aligned) is loaded
+hipError_t launch_seq_stats_hist_views(hipStream_t s, const LaunchCfg& cfg, const Workspace& ws, const uint8_t* text_base, int64_t first_line_start,
+                                       int64_t consumed_bytes, int64_t n_records, int64_t n_lines, int64_t seq_bytes, const int32_t* head_start,
+                                       const int32_t* seq_offsets, const uint32_t* line_end, const uint32_t* line_dst, int lmax, int64_t* d_state);
+
 // pushed-down region filter as a row mask: out_valid = in_valid AND (row hits the region); *n_pass += rows kept.
 // point form (VCF): id_col = chrom id, start = pos; range form (BAM): id_col = reference id, [start, end].
 hipError_t launch_region_mask(hipStream_t s, bool range_form, const int32_t* id_col, const uint8_t* id_valid, const int64_t* start,

@@ -67,8 +67,9 @@ struct exon_hip_scan {
   // (exon_hip_scan_next) come from the host reader, but a consume_scan whose plan reads none of those columns still takes the
   // GPU pipeline -- the device parser decodes and validates the list keys and does not look at the string keys at all
   bool gpu_candidate = false;
-  // FASTA opened with gpu_parse: remembered for exon_hip_scan_bind_ctx alone, which turns gpu_parse on.  Unbound, the scan is the host
-  // reader's -- exon_hip_scan_next and exon_hip_stream_consume_scan as without the option (there is no fused FASTA plan)
+  // FASTA opened with gpu_parse: remembered for exon_hip_scan_bind_ctx (batches) and for a stream of the sequence statistics plan
+  // (exon_hip_stream_consume_scan), which turn gpu_parse on.  Otherwise the scan is the host reader's -- exon_hip_scan_next and every
+  // other plan kind as without the option
   bool fasta_gpu_request = false;
   bool gpu_inflated = false;  // the last GPU-parsed consume also inflated BGZF blocks on the device
   bool gpu_decoded = false;   // the last consume decoded every record on the device (no host fallback)
@@ -223,6 +224,7 @@ int exon_hip_stream_plan_column(exon_hip_stream* st, int arg);
 int exon_hip_stream_set_value_types(exon_hip_stream* st, int x_type, int y_type);
 int exon_hip_stream_set_null_group(exon_hip_stream* st, std::function<int32_t()> id_of_null);
 int exon_hip_stream_launch_views(exon_hip_stream* st, const uint8_t* d_text, const exon_hip_fastq_views& v);
+int exon_hip_stream_launch_fasta_views(exon_hip_stream* st, const exon_hip_fasta_views& v);
 void* exon_hip_stream_hip_stream(exon_hip_stream* st);
 exon_hip_ctx* exon_hip_stream_ctx(exon_hip_stream* st);
 int exon_hip_stream_state_copy(exon_hip_stream* st, void* d_snapshot, bool restore, int64_t* rows_pushed);
@@ -2850,8 +2852,8 @@ static int consume_text_gpu(exon_hip_stream* st, exon_hip_scan* scan, int64_t* r
           ExonTextColumns ft;
           rc = scan->fasta() ? exon_text_fasta(ctx, hs, &scan->text_scratch, &p.fasta_views, &ft) : exon_text_fastq(ctx, hs, &scan->text_scratch, &p.views, (int64_t)n + 16, &ft);
           if (!rc) rc = export_text_slab(scan, ft, p.n_rows, hs);
-        } else if (scan->fasta()) {  // (never: gpu_parse is set on a FASTA scan by exon_hip_scan_bind_ctx alone)
-          rc = fail(ctx, EXON_HIP_EUNSUPPORTED, "there is no fused plan over FASTA text: a stream reads a FASTA scan through the host reader");
+        } else if (scan->fasta()) {  // the per-record sequence statistics, straight from the slab's views (asynchronous; no column is built)
+          rc = exon_hip_stream_launch_fasta_views(st, p.fasta_views);
         } else {
           rc = exon_hip_stream_launch_views(st, d_text, p.views);  // asynchronous: overlaps with preparing the next slab
         }
@@ -3131,6 +3133,14 @@ int exon_hip_stream_consume_scan(exon_hip_stream* st, exon_hip_scan* scan, int64
     const int rc0 = exon_hip_stream_set_region_id(st, id < 0 ? -1 : id);  // -1: no reference of that name, no row matches
     if (rc0) return rc0;
   }
+  if (exon_hip_stream_plan_kind(st) == EXON_HIP_PLAN_SEQ_STATS_HIST) {
+    exon_hip_ctx* ctx = exon_hip_stream_ctx(st);
+    if (scan->fastq() && scan->gpu_parse)  // before anything is read: the stream and the scan stay as they are
+      return fail(ctx, EXON_HIP_EUNSUPPORTED, "the sequence statistics plan (kind %d) has no path over GPU-parsed FASTQ text: use the per-read statistics plan (kind %d) there, or open the scan with gpu_parse=False, whose sequence column this plan takes",
+                  EXON_HIP_PLAN_SEQ_STATS_HIST, EXON_HIP_PLAN_READ_STATS_HIST);
+    if (scan->fasta() && scan->fasta_gpu_request && !scan->exporter && exon_hip_stream_plan_column(st, 0) != 2)
+      return fail(ctx, EXON_HIP_EINVAL, "the sequence statistics plan needs scan column %d; over a FASTA scan its operand is column 2 (sequence)", exon_hip_stream_plan_column(st, 0));
+  }
   // group keys travel by VALUE: the scan's dictionary ids are re-keyed into the stream's (stream.cpp)
   bool tracked = false, redirected = false;
   int rc = exon_hip_stream_begin_scan(st, &tracked, &redirected);
@@ -3178,6 +3188,17 @@ static int consume_scan_impl(exon_hip_stream* st, exon_hip_scan* scan, int64_t* 
       } catch (const std::exception& e) {
         return fail(nullptr, EXON_HIP_EINVAL, "%s", e.what());
       }
+    }
+  }
+  // a FASTA scan opened with gpu_parse under the sequence statistics plan takes the device pipeline, by exon_hip_scan_bind_ctx's rules:
+  // the text starts with a definition line (text in front of it, or an empty input, is the host reader's)
+  if (scan->fasta() && scan->fasta_gpu_request && !scan->gpu_parse && !scan->exporter && scan->rows == 0 &&
+      exon_hip_stream_plan_kind(st) == EXON_HIP_PLAN_SEQ_STATS_HIST) {
+    scan->fasta_gpu_request = false;
+    try {
+      if (scan->fasta()->first_byte() == '>') scan->gpu_parse = true;
+    } catch (const std::exception& e) {
+      return fail(nullptr, EXON_HIP_EINVAL, "%s", e.what());
     }
   }
   if (scan->gpu_parse) {

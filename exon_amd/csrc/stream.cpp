@@ -376,6 +376,8 @@ static int run_plan(const exon_hip_plan* p, void* stream, const exon_hip_column*
       return exon_op_qual_pos_hist(ctx, stream, &cols[0], n, d.lmax, counts, flags);
     case EXON_HIP_PLAN_READ_STATS_HIST:
       return exon_op_read_stats_hist(ctx, stream, &cols[0], &cols[1], n, d.lmax, counts, flags);
+    case EXON_HIP_PLAN_SEQ_STATS_HIST:
+      return exon_op_seq_stats_hist(ctx, stream, &cols[0], n, d.lmax, counts, flags);
     case EXON_HIP_PLAN_OVERLAP_COUNT:
     case EXON_HIP_PLAN_WITHIN_COUNT:
       return exon_op_overlap_count(ctx, stream, &cols[0], &cols[1], &cols[2], n, d.region_chrom_id, d.region_start,
@@ -618,6 +620,16 @@ int exon_hip_plan_create(exon_hip_ctx* ctx, const exon_hip_plan_desc* desc, exon
       }
       p->n_i64 = 4 + ((int64_t)desc->lmax + 1) + 102 + 257;  // exon_hip_read_stats_layout
       break;
+    case EXON_HIP_PLAN_SEQ_STATS_HIST:  // sequence
+      p->n_cols = 1;
+      p->cols[0].elem = 1;
+      p->cols[0].utf8 = true;
+      if (desc->lmax < 1 || desc->lmax > 65536) {
+        delete p;
+        return fail(ctx, EXON_HIP_EINVAL, "lmax %d out of range", desc->lmax);
+      }
+      p->n_i64 = 3 + 256 + ((int64_t)desc->lmax + 2) + 32 + 102;  // exon_hip_seq_stats_layout
+      break;
     default:
       delete p;
       return fail(ctx, EXON_HIP_EINVAL, "unknown plan kind %d", desc->kind);
@@ -836,6 +848,21 @@ int exon_hip_stream_set_null_group(exon_hip_stream* st, std::function<int32_t()>
   int rc = EXON_HIP_OK;
   if (!id_of_null && st->null_group && !st->closed) rc = flush_slot(st);
   st->null_group = std::move(id_of_null);
+  return rc;
+}
+// K10 over the views of a FASTA slab resident in HBM: scan column 2 = sequence
+int exon_hip_stream_launch_fasta_views(exon_hip_stream* st, const exon_hip_fasta_views& v) {
+  exon_hip_plan* p = st->plan;
+  if (st->closed) return fail(st->ctx, EXON_HIP_ESTATE, "push after finish/close");
+  if (p->d.kind != EXON_HIP_PLAN_SEQ_STATS_HIST)
+    return fail(st->ctx, EXON_HIP_EUNSUPPORTED, "GPU-side FASTA splitting serves the per-record sequence statistics plan (kind %d) only", EXON_HIP_PLAN_SEQ_STATS_HIST);
+  if (p->d.columns[0] != 2)
+    return fail(st->ctx, EXON_HIP_EINVAL, "the sequence statistics plan needs scan column %d; over a FASTA scan its operand is column 2 (sequence)", p->d.columns[0]);
+  int rc = flush_slot(st);
+  if (!rc) rc = settle_reset(st);
+  if (rc) return rc;
+  rc = exon_hip_seq_stats_hist_views(st->ctx, st->stream, &v, p->d.lmax, reinterpret_cast<int64_t*>(st->d_state));
+  if (!rc) st->rows_pushed += v.n_records;
   return rc;
 }
 // K5 / K9 over views into text resident in HBM (FASTQ slabs): scan column 2 = sequence lines, 3 = quality lines
@@ -1899,6 +1926,21 @@ int exon_hip_stream_finish_arrow(exon_hip_stream* st, struct ArrowArray* out, st
       std::vector<int32_t> stat, bin;
       std::vector<int64_t> cnt;
       for (int s = 0; s < 4; ++s)
+        for (int64_t w = at[s]; w < at[s + 1]; ++w)
+          if (s == 0 || counts[(size_t)w]) {
+            stat.push_back(s);
+            bin.push_back((int32_t)(w - at[s]));
+            cnt.push_back(counts[(size_t)w]);
+          }
+      make_struct(out, (int64_t)stat.size(), {prim(stat), prim(bin), prim(cnt)});
+      make_schema(out_schema, "+s", "", false, {field("i", "stat", false), field("i", "bin", false), field("l", "count", false)});
+      break;
+    }
+    case EXON_HIP_PLAN_SEQ_STATS_HIST: {  // stat: 0 totals (always its three rows), 1 composition, 2 length, 3 length_log2, 4 gc_percent (nonzero bins)
+      const int64_t at[6] = {0, 3, 3 + 256, 3 + 256 + (int64_t)d.lmax + 2, 3 + 256 + (int64_t)d.lmax + 2 + 32, p->n_i64};
+      std::vector<int32_t> stat, bin;
+      std::vector<int64_t> cnt;
+      for (int s = 0; s < 5; ++s)
         for (int64_t w = at[s]; w < at[s + 1]; ++w)
           if (s == 0 || counts[(size_t)w]) {
             stat.push_back(s);

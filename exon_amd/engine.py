@@ -230,6 +230,18 @@ class Context:
         self._check(self.lib.exon_hip_read_stats_hist_views(self.h, stream, ptr(d_text), ptr(seq_start), ptr(seq_end), ptr(qual_start),
                                                             ptr(qual_end), n_reads, lmax, ptr(d_state)))
 
+    def seq_stats_hist(self, seq_offsets, seq_data, n_records, lmax, d_state, stream=None):
+        """K10 over one Utf8 column (sequence): totals, byte composition and the length / log2 length / GC percent histograms
+        of the records, accumulated into `d_state` (seq_stats_layout(lmax)[5] int64 words)."""
+        c0 = _col(seq_data, None, seq_offsets, n_records)
+        self._check(self.lib.exon_hip_seq_stats_hist(self.h, stream, C.byref(c0), n_records, lmax,
+                                                     d_state.ptr if isinstance(d_state, DeviceBuffer) else d_state))
+
+    def seq_stats_hist_views(self, views, lmax, d_state, stream=None):
+        """K10 over the views of one FASTA slab in HBM (FASTAParser.parse_device): nothing is compacted or copied."""
+        self._check(self.lib.exon_hip_seq_stats_hist_views(self.h, stream, C.byref(views), lmax,
+                                                           d_state.ptr if isinstance(d_state, DeviceBuffer) else d_state))
+
     def bgzf_inflate(self, data, verify_crc=True, stream=None):
         """Test / tool helper: BGZF bytes -> inflated bytes through the GPU (exon_hip_bgzf_inflate).  Returns
         (inflated uint8 array, seconds spent in the device call)."""
@@ -330,6 +342,23 @@ class Context:
         scan.  State: read_stats_layout(lmax)[4] int64 words, all of which add."""
         d = L.PlanDesc(kind=L.PLAN_READ_STATS_HIST, lmax=lmax)
         return Plan(self, d, columns)
+
+    def plan_seq_stats_hist(self, lmax, columns=(0,)):
+        """Per-record totals, byte composition and length / log2 length / GC percent histograms over one Utf8 column (sequence):
+        column 2 of a FASTA scan and of a FASTQ scan.  State: seq_stats_layout(lmax)[5] int64 words, all of which add."""
+        d = L.PlanDesc(kind=L.PLAN_SEQ_STATS_HIST, lmax=lmax)
+        return Plan(self, d, columns)
+
+
+def seq_stats_layout(lmax):
+    """exon_hip_seq_stats_layout (host-only): word offsets of the totals / composition / length / length_log2 / gc_percent
+    sections of a per-record sequence statistics state, and its size in words."""
+    lib = L.load()
+    out = (C.c_int64 * 6)()
+    rc = lib.exon_hip_seq_stats_layout(lmax, out)
+    if rc:
+        raise ExonHipError(rc, lib.exon_hip_last_error(None).decode(errors="replace"))
+    return tuple(out)
 
 
 def read_stats_layout(lmax):

@@ -30,6 +30,8 @@
  *        (exon-core/src/udfs/sequence/quality_score_string_to_list.rs:56-117) + unnest + GROUP BY
  *   exon_hip_read_stats_hist              GCContent::invoke (exon-core/src/udfs/sequence/gc_content.rs:52-71), the read length
  *        and the per-row mean of quality_scores_to_list, each binned (integers) and counted: GROUP BY bin, COUNT(*)
+ *   exon_hip_seq_stats_hist               GCContent::invoke (exon-core/src/udfs/sequence/gc_content.rs:52-71) and length(sequence) over
+ *        FASTA (or any Utf8 sequence column), each binned (integers) and counted: GROUP BY bin, COUNT(*); plus the byte composition
  *   exon_hip_regroup_files_by_size        regroup_files_by_size
  *        (exon-core/src/datasources/exon_file_scan_config.rs:79-110) -- the multi-GPU shard rule
  */
@@ -315,6 +317,8 @@ int exon_hip_regroup_files_by_size(const int64_t* sizes, int32_t n_files, int32_
 #define EXON_HIP_PLAN_CMP_MINMAX_BY_GROUP 8
 /* K9: lmax, columns: sequence, quality_scores (both Utf8; (2, 3) of a FASTQ scan); state: exon_hip_read_stats_layout words, all add */
 #define EXON_HIP_PLAN_READ_STATS_HIST 9
+/* K10: lmax, columns: sequence (Utf8; column 2 of a FASTA scan and of a FASTQ scan); state: exon_hip_seq_stats_layout words, all add */
+#define EXON_HIP_PLAN_SEQ_STATS_HIST 10
 
 #define EXON_HIP_X_FLOAT32 0
 #define EXON_HIP_X_INT32 1
@@ -339,7 +343,7 @@ typedef struct exon_hip_plan_desc {
   /* K4: type of AVG's argument y, EXON_HIP_X_FLOAT32 / EXON_HIP_X_INT32 (DataFusion's avg casts either to Float64) */
   int32_t y_type;
   /* input column indexes into the batch's children, in operator argument order
-   * (K2: chrom_id,pos  K3: flag,mapq,ref_id  K4: x,y,group_id  K5: quality_scores  K6: ref_id,start,end  K9: sequence,quality_scores) */
+   * (K2: chrom_id,pos  K3: flag,mapq,ref_id  K4: x,y,group_id  K5: quality_scores  K6: ref_id,start,end  K9: sequence,quality_scores  K10: sequence) */
   int32_t columns[4];
 } exon_hip_plan_desc;
 
@@ -556,10 +560,12 @@ typedef struct exon_hip_scan_options {
                              them on the GPU (exon_hip_bgzf_inflate, exon_hip_vcf_parser_* / exon_hip_fastq_parser_* /
                              exon_hip_bam_parser_* ...).  exon_hip_scan_next on such a scan needs exon_hip_scan_bind_ctx first
                              (batches then come out of the same GPU pipeline); without a bound ctx it returns ESTATE.
-                             FASTA: the request is remembered for exon_hip_scan_bind_ctx alone (batches from the GPU pipeline,
-                             exon_hip_fasta_parser_*).  There is no fused FASTA plan: exon_hip_stream_consume_scan reads such a
-                             scan through the host reader, and exon_hip_scan_next without a bound ctx returns the host reader's
-                             batches (that reader defers nothing) */
+                             FASTA: the request is remembered for exon_hip_scan_bind_ctx (batches from the GPU pipeline,
+                             exon_hip_fasta_parser_*) and for exon_hip_stream_consume_scan under the one fused FASTA plan,
+                             EXON_HIP_PLAN_SEQ_STATS_HIST (exon_hip_seq_stats_hist_views over every slab's views; an input that does
+                             not start with '>', an undecided slab or a record beyond the carry limit is handed to the host reader).
+                             A stream of any other plan kind reads such a scan through the host reader, and exon_hip_scan_next
+                             without a bound ctx returns the host reader's batches (that reader defers nothing) */
   uint64_t projection;    /* (ABI 5) EXON_HIP_PROJECT_* bits: columns of the reference's schema beyond the fused kernels' operands,
                              appended BEHIND the default ones in bit order (0 = none: the hot path ships only what a plan reads).
                              VCF text: id List<Utf8>?, ref Utf8, alt List<Utf8>? (lazy_array_builder.rs:169-205; the alt list has no
@@ -883,6 +889,35 @@ int exon_hip_fasta_parser_create(exon_hip_ctx* ctx, int64_t max_slab_bytes, exon
 int exon_hip_fasta_parser_parse(exon_hip_fasta_parser* parser, void* stream, const uint8_t* d_text, int64_t n_bytes,
                                 int32_t final_slab, exon_hip_fasta_views* views);
 int exon_hip_fasta_parser_destroy(exon_hip_fasta_parser* parser);
+
+/* K10 (additive; the ABI stays 5).  Per-RECORD statistics of sequences (s = a record's sequence bytes as the reader returns them),
+ *      integers only.  d_state holds 3 + 256 + (lmax + 2) + 32 + 102 int64 words (exon_hip_seq_stats_layout), and every word adds; a
+ *      zeroed state is the empty state:
+ *        totals       [3]         n_records, sum len(s), sum gc(s)
+ *        composition  [256]       word b = number of sequence bytes equal to b, over all records
+ *        length       [lmax + 2]  bin len(s) for len(s) <= lmax; bin lmax + 1 = every longer record (not an error: contigs are long)
+ *        length_log2  [32]        bin 0 = empty sequence; bin k = 2^(k-1) <= len(s) < 2^k (int32 offsets keep k <= 31)
+ *        gc_percent   [102]       bin floor(100 gc(s) / len(s)); bin 101 = empty sequence.  gc(s) = bytes equal to 'G' or 'C', upper
+ *                                 case only (exon-core/src/udfs/sequence/gc_content.rs:52-71); the bin is the exact integer floor
+ *                                 
+ *      sum composition = sum len; composition['G'] + composition['C'] = sum gc; length, length_log2 and gc_percent each sum to
+ *      n_records.  1 <= lmax <= 65536.  Validity is not read (as K5, K9); a negative offset difference counts as length 0; nothing in
+ *      this plan is an input error.  The offsets must ascend, as Arrow requires: the kernel finds a tile's records by searching them,
+ *      so offsets that do not ascend give counts without meaning (records missed or counted twice, G/C counts of several records
+ *      in one) -- but never an access outside the payload or the state: every index is clamped.  No byte outside
+ *      [offsets[0], offsets[n_records]) of `values` is loaded.  Accumulates.
+ *      Any Utf8 column is an operand: through the host reader (pushes, a scan opened without gpu_parse) the plan counts whatever
+ *      column `columns[0]` names -- `description` (1) of a FASTA scan included --, while the device path over FASTA text exists for
+ *      column 2 alone and refuses any other index (EXON_HIP_EINVAL) instead of handing the scan to the host reader. */
+int exon_hip_seq_stats_hist(exon_hip_ctx* ctx, void* stream, const exon_hip_column* sequence /*utf8*/, int64_t n_records, int32_t lmax,
+                            int64_t* d_state);
+/* K10 over the views of one FASTA slab resident in HBM (exon_hip_fasta_parser_parse; n_undecided must be 0): the n_records emitted
+ * records, by the reader's rules (CR before LF dropped, definition lines and line ends are not sequence).  Nothing is compacted or
+ * copied; no byte outside [first_line_start, first_line_start + consumed_bytes) of text_base is loaded. */
+int exon_hip_seq_stats_hist_views(exon_hip_ctx* ctx, void* stream, const exon_hip_fasta_views* views, int32_t lmax, int64_t* d_state);
+/* Host-only: out[0..4] = word offset of K10's totals / composition / length / length_log2 / gc_percent sections, out[5] = the
+ * state's words.  EXON_HIP_EINVAL outside 1 <= lmax <= 65536.  Needs no device. */
+int exon_hip_seq_stats_layout(int32_t lmax, int64_t* out /*[6]*/);
 
 /* ---- BAM record splitting + field extraction on the GPU (inflated BAM bytes in HBM -> device-layout columns) ----
  * Column rules of BAMArrayBuilder::append (exon-bam/src/array_builder.rs:102-218) for flag, mapping_quality (NULL when

@@ -18,6 +18,9 @@ pub struct exon_hip_vcf_parser { _p: [u8; 0] }
 /// exon_hip_vcf_parser_info_text's and _formats_text's result (device pointers, owned by the parser): handled by pointer only
 #[repr(C)]
 pub struct exon_hip_vcf_info_text { _p: [u8; 0] }
+/// exon_hip_fasta_parser_parse's result (device pointers, owned by the parser): handled by pointer only
+#[repr(C)]
+pub struct exon_hip_fasta_views { _p: [u8; 0] }
 
 pub const EXON_HIP_ABI_VERSION: i32 = 5;
 pub const EXON_HIP_PLAN_REGION_COUNT: i32 = 2;
@@ -28,6 +31,7 @@ pub const EXON_HIP_PLAN_OVERLAP_COUNT: i32 = 6;
 pub const EXON_HIP_PLAN_WITHIN_COUNT: i32 = 7;
 pub const EXON_HIP_PLAN_CMP_MINMAX_BY_GROUP: i32 = 8; // K4's fields; state = 4 * n_groups int64 words (counts, then min / max words)
 pub const EXON_HIP_PLAN_READ_STATS_HIST: i32 = 9; // lmax, columns (sequence, quality_scores); state = exon_hip_read_stats_layout words, all add
+pub const EXON_HIP_PLAN_SEQ_STATS_HIST: i32 = 10; // lmax, column (sequence); state = exon_hip_seq_stats_layout words, all add
 pub const EXON_HIP_GT: i32 = 0;
 pub const EXON_HIP_GE: i32 = 1;
 pub const EXON_HIP_LT: i32 = 2;
@@ -139,6 +143,12 @@ extern "C" {
     pub fn exon_hip_read_stats_hist_views(ctx: *mut exon_hip_ctx, stream: *mut c_void, d_bytes: *const u8, seq_s: *const i32, seq_e: *const i32, qual_s: *const i32, qual_e: *const i32, n_reads: i64, lmax: i32, d_state: *mut i64) -> c_int;
     /// host-only: word offsets of K9's totals / length / gc_percent / mean_quality sections and the state's size
     pub fn exon_hip_read_stats_layout(lmax: i32, out: *mut i64) -> c_int;
+    /// K10 (bare operator): per-record totals, byte composition, length / log2 length / GC percent histograms over one Utf8 column; accumulates
+    pub fn exon_hip_seq_stats_hist(ctx: *mut exon_hip_ctx, stream: *mut c_void, sequence: *const exon_hip_column, n_records: i64, lmax: i32, d_state: *mut i64) -> c_int;
+    /// K10 over the views of one FASTA slab resident in HBM (exon_hip_fasta_parser_parse)
+    pub fn exon_hip_seq_stats_hist_views(ctx: *mut exon_hip_ctx, stream: *mut c_void, views: *const exon_hip_fasta_views, lmax: i32, d_state: *mut i64) -> c_int;
+    /// host-only: word offsets of K10's totals / composition / length / length_log2 / gc_percent sections and the state's size
+    pub fn exon_hip_seq_stats_layout(lmax: i32, out: *mut i64) -> c_int;
     /// fold of `world` packed states by the plan's own layout (add; unsigned max for K8's extreme planes)
     pub fn exon_hip_plan_fold_states(plan: *const exon_hip_plan, stream: *mut c_void, d_gathered: *const c_void, world: i32, d_out: *mut c_void) -> c_int;
     pub fn exon_hip_stream_open(plan: *mut exon_hip_plan, partition: i32, out: *mut *mut exon_hip_stream) -> c_int;
