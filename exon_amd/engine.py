@@ -76,9 +76,13 @@ class Context:
         self.device = device
 
     # -- plumbing ---------------------------------------------------------------------------
+    def _last_error(self):
+        """the calling thread's own text first (another thread of this ctx may have failed since), then the ctx's"""
+        return self.lib.exon_hip_last_error(None).decode(errors="replace") or self.lib.exon_hip_last_error(self.h).decode(errors="replace")
+
     def _check(self, rc):
         if rc < 0:
-            raise ExonHipError(rc, self.lib.exon_hip_last_error(self.h).decode(errors="replace"))
+            raise ExonHipError(rc, self._last_error())
         return rc
 
     def info(self):
@@ -1275,8 +1279,7 @@ class Stream:
         n = C.c_int64()
         rc = self.ctx.lib.exon_hip_stream_consume_scan(self.h, scan.h, C.byref(n))
         if rc < 0:
-            msg = self.ctx.lib.exon_hip_last_error(self.ctx.h).decode(errors="replace") or self.ctx.lib.exon_hip_last_error(None).decode(errors="replace")
-            raise ExonHipError(rc, msg)
+            raise ExonHipError(rc, self.ctx._last_error())
         return n.value
 
     def state(self):

@@ -129,6 +129,14 @@ int exon_hip_ctx_info(exon_hip_ctx* ctx, exon_hip_device_info* out);
 /* Text of the last error on this ctx (or, with ctx == NULL, of the calling thread).  Owned by the
  * library, valid until the next failing call on the same ctx/thread. */
 const char* exon_hip_last_error(const exon_hip_ctx* ctx);
+/* Threads.  Different streams, scans and parsers of one ctx may be driven from different threads at the same time (one thread per
+ * partition: every stream has its own hipStream_t, workspace and status word; the ctx's buffer pool, the slab buffers a scan
+ * borrows, the inflate scratch, the pinned export blocks and the staging threads are shared and locked inside the library).
+ * One HANDLE -- a stream, a scan, a parser, a plan being destroyed -- belongs to one thread at a time; a plan may be shared by the
+ * streams opened from it.  exon_hip_timer_start / _stop_ms use ONE event pair per ctx: time from one thread at a time.
+ * exon_hip_last_error(ctx) is the last failure of ANY thread on that ctx (and its pointer is only good until another thread
+ * fails there); exon_hip_last_error(NULL) is the calling thread's own last failure, which is what a caller that runs several
+ * partitions should read first.  tests/test_gpu_concurrent_partitions.py pins this contract. */
 
 /* Device-memory helpers so a host without its own HIP binding can stage columns.  `stream` is a
  * hipStream_t passed as void* (NULL = the ctx's own stream). */
