@@ -163,6 +163,10 @@ PLAN_WITHIN_COUNT = 7
 PLAN_CMP_MINMAX_BY_GROUP = 8
 PLAN_READ_STATS_HIST = 9
 PLAN_SEQ_STATS_HIST = 10
+PLAN_REGION_SET_OVERLAP = 11
+REGION_SET_MAX_REGIONS = 1 << 20
+REGION_SET_LDS_MAX = 6144  # kernels.h: sets with M + C up to this are searched and counted in LDS
+REGION_SET_TILE_SMALL, REGION_SET_TILE_BIG = 2048, 8192  # kernels.h: rows per workgroup tile of the two launch shapes
 LAUNCH_ACCUMULATE = 0
 LAUNCH_OVERWRITE = 1
 CMP = {">": 0, ">=": 1, "<": 2, "<=": 3, "=": 4, "==": 4, "!=": 5, "<>": 5}
@@ -213,6 +217,10 @@ SIGNATURES = {
     "exon_hip_fold_states": (C.c_int, [_vp, _vp, _vp, _i32, _i64, _i64, _vp]),
     "exon_hip_merge_states": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp]),
     "exon_hip_plan_fold_states": (C.c_int, [_vp, _vp, _vp, _i32, _vp]),
+    "exon_hip_plan_create_region_set": (C.c_int, [_vp, C.POINTER(_i32), C.c_char_p, C.c_size_t, _vp, _vp, _vp, _i32, C.POINTER(_vp)]),
+    "exon_hip_region_set_layout": (C.c_int, [_vp, C.POINTER(_i64)]),
+    "exon_hip_region_set_decode": (C.c_int, [_vp, _vp, _vp]),
+    "exon_hip_region_set_overlap": (C.c_int, [_vp, _vp, _colp, _colp, _colp, _i64, _vp, _vp]),
     "exon_hip_rccl_unique_id": (C.c_int, [_vp]),
     "exon_hip_rccl_comm_init": (C.c_int, [_vp, _vp, _i32, _i32, C.POINTER(_vp)]),
     "exon_hip_rccl_comm_destroy": (C.c_int, [_vp]),

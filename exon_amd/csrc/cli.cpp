@@ -22,6 +22,7 @@
 //   SELECT * FROM fastq_read_stats('<p>'[, 'gzip'])                                               -- K9
 //   SELECT * FROM fasta_seq_stats('<p>'[, 'gzip'])                                                -- K10
 //   SELECT COUNT(*) FROM <bam table> WHERE bam_region_filter('<r>', reference, start, end)          -- K6 (plain table; INDEXED_BAM plans chunks on the host)
+//   SELECT * FROM overlap_counts('<bam|sam|cram|gff|gtf file>', '<regions.bed>'[, 'gzip'])       -- K11: one row per BED line, in file order
 //   DROP TABLE t;
 #include <dirent.h>
 #include <sys/stat.h>
@@ -142,6 +143,7 @@ struct Source {  // resolved FROM clause
   std::string region;  // from *_indexed_scan
   bool indexed = false;
   int n_fields = 12;  // BED
+  std::string regions_bed;  // overlap_counts: the BED file of the region set
 };
 
 struct Session {
@@ -428,8 +430,26 @@ Source resolve_from(Session& se, Parser& ps) {
   Source src;
   const std::string name = ps.ident();
   const std::string lname = lower(name);
-  if (ps.accept_sym("(")) {  // table function: <fmt>_scan / <fmt>_indexed_scan / fastq_quality_histogram / fastq_read_stats / fasta_seq_stats
+  if (ps.accept_sym("(")) {  // table function: <fmt>_scan / <fmt>_indexed_scan / fastq_quality_histogram / fastq_read_stats / fasta_seq_stats / overlap_counts
     const std::string path = ps.str();
+    if (lname == "overlap_counts") {  // ('<file>', '<regions.bed>'[, '<compression>']): the source's format by its extension
+      ps.expect_sym(",");
+      src.regions_bed = ps.str();
+      if (ps.accept_sym(",")) src.compression = compression_of(ps.str());
+      ps.expect_sym(")");
+      std::string stem = lower(path);
+      for (const char* z : {".gz", ".bgz"})
+        if (ends_with(stem, z)) stem.resize(stem.size() - strlen(z));
+      if (ends_with(stem, ".bam")) src.format = EXON_HIP_FORMAT_BAM;
+      else if (ends_with(stem, ".sam")) src.format = EXON_HIP_FORMAT_SAM;
+      else if (ends_with(stem, ".cram")) src.format = EXON_HIP_FORMAT_CRAM;
+      else if (ends_with(stem, ".gff") || ends_with(stem, ".gff3")) src.format = EXON_HIP_FORMAT_GFF;
+      else if (ends_with(stem, ".gtf")) src.format = EXON_HIP_FORMAT_GTF;
+      else if (ends_with(stem, ".bed")) throw Err("overlap_counts: a BED source is not served (its half-open columns need the strict form); sources are BAM, SAM, CRAM, GFF and GTF files");
+      else throw Err("overlap_counts: cannot tell the format of '" + path + "' from its extension (.bam .sam .cram .gff .gff3 .gtf, optionally .gz / .bgz)");
+      list_files(path, format_exts(src.format, ""), &src.files);
+      return src;
+    }
     std::string arg2;
     if (ps.accept_sym(",")) arg2 = ps.str();
     ps.expect_sym(")");
@@ -648,6 +668,49 @@ void exec_select(Session& se, Parser& ps) {
       for (int64_t w = at[st]; w < at[st + 1]; ++w)
         if (st == 0 || total[(size_t)w]) rows.push_back({stat_names[st], st == 0 ? std::string(total_names[w]) : std::to_string(w - at[st]), std::to_string(total[(size_t)w])});
     print_table({"stat", "bin", "count"}, rows, se.quiet);
+    return;
+  }
+
+  if (!src.regions_bed.empty()) {  // K11: every region of the BED file over the source in ONE pass; the names are resolved per file
+    std::ifstream in(src.regions_bed);
+    if (!in) throw Err("no such file: " + src.regions_bed);
+    std::vector<std::string> names;
+    std::vector<int64_t> starts, ends;
+    std::string packed, line;
+    for (int64_t ln = 1; std::getline(in, line); ++ln) {
+      if (!line.empty() && line.back() == '\r') line.pop_back();
+      if (line.empty() || line[0] == '#' || line.rfind("track", 0) == 0 || line.rfind("browser", 0) == 0) continue;
+      std::istringstream ls(line);
+      std::string chrom;
+      long long s = -1, e = -1;
+      if (!(ls >> chrom >> s >> e) || s < 0 || e < s) throw Err(src.regions_bed + " line " + std::to_string(ln) + ": expected <chrom> <start> <end> with 0 <= start <= end");
+      // BED is 0-based half-open: (chrom, s, e) is the 1-based closed interval [s + 1, e], which is empty when s == e
+      if (s == e) throw Err(src.regions_bed + " line " + std::to_string(ln) + ": zero-length region " + chrom + ":" + std::to_string(s) + "-" + std::to_string(e));
+      names.push_back(chrom);
+      packed += chrom;
+      packed.push_back('\0');
+      starts.push_back(s + 1);
+      ends.push_back(e);
+    }
+    if (names.empty()) throw Err(src.regions_bed + ": no regions");
+    exon_hip_ctx* ctx = se.gpu();  // (the region file is judged first: its errors need no device)
+    const bool annotation = src.format == EXON_HIP_FORMAT_GFF || src.format == EXON_HIP_FORMAT_GTF;
+    const int32_t columns[3] = {annotation ? 0 : 2, 3, 4};
+    StreamGuard sg;
+    ck(ctx, exon_hip_plan_create_region_set(ctx, columns, packed.data(), packed.size(), nullptr, starts.data(), ends.data(), (int32_t)names.size(), &sg.p));
+    ck(ctx, exon_hip_stream_open(sg.p, 0, &sg.s));
+    for (const auto& f : src.files) {  // one stream: the state is keyed by the region set, the files add up
+      ScanGuard g; open_scan(src, f, nullptr, "", &g, true);
+      ck(ctx, exon_hip_stream_consume_scan(sg.s, g.s, nullptr));
+    }
+    int64_t n_i64 = 0, n_f64 = 0;
+    ck(ctx, exon_hip_plan_state_size(sg.p, &n_i64, &n_f64));
+    std::vector<int64_t> state((size_t)n_i64), counts(names.size());
+    ck(ctx, exon_hip_stream_finish(sg.s, state.data(), nullptr));
+    ck(ctx, exon_hip_region_set_decode(sg.p, state.data(), counts.data()));
+    std::vector<std::vector<std::string>> rows;
+    for (size_t i = 0; i < names.size(); ++i) rows.push_back({names[i], std::to_string(starts[i]), std::to_string(ends[i]), std::to_string(counts[i])});
+    print_table({"contig", "start", "end", "count"}, rows, se.quiet);
     return;
   }
 
@@ -1025,6 +1088,7 @@ int main(int argc, char** argv) {
              "             fastq_quality_histogram('<path>')\n"
              "             fastq_read_stats('<path>')\n"
              "             fasta_seq_stats('<path>'[, 'gzip'])\n"
+             "             overlap_counts('<bam|sam|cram|gff|gtf file>', '<regions.bed>'[, 'gzip'])   one row per BED line: contig, start, end (1-based closed), count\n"
              "  queries:   SELECT COUNT(*) FROM <src> [WHERE chrom = 'c' AND pos >= a AND pos <= b | vcf_region_filter('r', chrom) | bam_region_filter('r', reference, start, end)\n"
              "             | gff_region_filter('r', seqname[, start])]\n"
              "             SELECT COUNT(*) FROM <bam|sam> WHERE [bam_region_filter('r', reference, start, end) AND] flag & M = V [AND CAST(mapping_quality AS INT) >= q]\n"

@@ -240,6 +240,8 @@ int exon_op_read_stats_hist(exon_hip_ctx* ctx, void* stream, const exon_hip_colu
 int exon_op_seq_stats_hist(exon_hip_ctx* ctx, void* stream, const exon_hip_column* seq, int64_t n_records, int32_t lmax, int64_t* d_state,
                            int flags);
 int exon_op_seq_stats_hist_views(exon_hip_ctx* ctx, void* stream, const exon_hip_fasta_views* views, int32_t lmax, int64_t* d_state, int flags);
+int exon_op_region_set_overlap(exon_hip_ctx* ctx, void* stream, const exon_hip_column* ref_id, const exon_hip_column* start, const exon_hip_column* end,
+                               int64_t n, const exon::RegionSetTables& tables, int64_t* d_state, int flags);
 // chunk c is q[c * stride]
 int exon_op_qual_pos_hist_chunks(exon_hip_ctx* ctx, void* stream, const exon_hip_column* q, int stride, int32_t n_chunks,
                                  const int64_t* n_reads, int32_t lmax, int64_t* d_hist, int flags);

@@ -108,6 +108,32 @@ hipError_t launch_seq_stats_hist_views(hipStream_t s, const LaunchCfg& cfg, cons
                                        int64_t consumed_bytes, int64_t n_records, int64_t n_lines, int64_t seq_bytes, const int32_t* head_start,
                                        const int32_t* seq_offsets, const uint32_t* line_end, const uint32_t* line_dst, int lmax, int64_t* d_state);
 
+// K11 (region_set.hip): K6's overlap count for every region of a set in one pass; state [counted, null_rows, elsewhere, inverted]
+// [A: M + C] [B: M + C] (include/exon_hip.h, exon_hip_region_set_layout).  The tables live on the device: map[n_map] = contig slot of
+// a reference id or -1, off[C + 1] = regions in front of each contig, ends / starts [M] sorted within each contig.  Sets with
+// M + C <= REGION_SET_LDS_MAX keep the tables and a u32 histogram pair in LDS (24 bytes per word of the bound: 144 KiB of the CU's
+// 160 at the bound); larger ones search through L2 and add to the state with global atomics.  Rows are dealt in tiles of
+// RS_TILE_BIG (1024 threads) once every CU gets one, else RS_TILE_SMALL (256 threads).  Column bases need their element's alignment
+// only.  `ones`: 64 bytes of 0xFF on the device (Workspace::status + 8).  cfg.overwrite: state := this launch.
+constexpr int RS_J = 2;
+constexpr int RS_TILE_SMALL = 4 * 256 * RS_J, RS_TILE_BIG = 16 * 256 * RS_J;
+constexpr int REGION_SET_LDS_MAX = 6144;
+constexpr int REGION_SET_MAX_REGIONS = 1 << 20;
+constexpr int64_t REGION_SET_LAUNCH_ROWS = (int64_t)1 << 31;  // rows per kernel launch: the LDS bins are u32
+constexpr int64_t region_set_words(int64_t M, int64_t C) { return 4 + 2 * (M + C); }
+constexpr size_t region_set_lds_bytes(int M, int C) { return (size_t)M * 16 + (size_t)(M + C) * 8; }
+struct RegionSetTables {
+  const int32_t* map;
+  int32_t n_map;
+  const int32_t* off;
+  const int64_t* ends;
+  const int64_t* starts;
+  int32_t M, C;
+};
+hipError_t launch_region_set_overlap(hipStream_t s, const LaunchCfg& cfg, const uint8_t* ones, const int32_t* ref, const uint8_t* ref_valid,
+                                     const int64_t* start, const uint8_t* start_valid, const int64_t* end, const uint8_t* end_valid, int64_t n,
+                                     const RegionSetTables& t, int64_t* d_state);
+
 // pushed-down region filter as a row mask: out_valid = in_valid AND (row hits the region); *n_pass += rows kept.
 // point form (VCF): id_col = chrom id, start = pos; range form (BAM): id_col = reference id, [start, end].
 hipError_t launch_region_mask(hipStream_t s, bool range_form, const int32_t* id_col, const uint8_t* id_valid, const int64_t* start,

@@ -234,6 +234,9 @@ int exon_hip_stream_begin_scan(exon_hip_stream* st, bool* tracked, bool* redirec
 int exon_hip_stream_end_scan(exon_hip_stream* st, const std::vector<std::string>* scan_keys, bool tracked, bool redirected, bool ok);
 bool exon_hip_stream_region_contig(exon_hip_stream* st, std::string* name);
 int exon_hip_stream_set_region_id(exon_hip_stream* st, int32_t id);
+const std::vector<std::string>* exon_hip_stream_region_set_names(exon_hip_stream* st);
+int exon_hip_stream_set_region_set_map(exon_hip_stream* st, const std::vector<int32_t>& map);
+int exon_hip_stream_end_region_set_scan(exon_hip_stream* st);
 
 // BGZF inputs of GPU-parsed scans are inflated on the GPU too (EXON_HIP_GPU_INFLATE=0: host threads inflate)
 static bool gpu_inflate_enabled() {
@@ -3133,6 +3136,35 @@ int exon_hip_stream_consume_scan(exon_hip_stream* st, exon_hip_scan* scan, int64
     const int rc0 = exon_hip_stream_set_region_id(st, id < 0 ? -1 : id);  // -1: no reference of that name, no row matches
     if (rc0) return rc0;
   }
+  // a region-set plan made from names: every distinct name by the same rule; the stream gets this scan's id -> contig slot map
+  const std::vector<std::string>* set_names = exon_hip_stream_region_set_names(st);
+  struct RegionSetScanGuard {
+    exon_hip_stream* st;
+    bool on;
+    ~RegionSetScanGuard() {
+      if (on) exon_hip_stream_end_region_set_scan(st);
+    }
+  } region_set_guard{st, false};
+  if (set_names) {
+    exon::Dictionary* d = dict_of(scan, region_dict_column(scan));
+    if (!d) return fail(exon_hip_stream_ctx(st), EXON_HIP_EINVAL, "this scan has no contig / reference dictionary to resolve the region set's names in");
+    const bool fixed = scan->format == EXON_HIP_FORMAT_BAM || scan->format == EXON_HIP_FORMAT_SAM || scan->format == EXON_HIP_FORMAT_CRAM;
+    std::vector<int32_t> ids(set_names->size(), -1);
+    int32_t max_id = -1;
+    for (size_t c = 0; c < set_names->size(); ++c) {
+      const std::string& name = (*set_names)[c];
+      int32_t id = d->find(name);
+      if (id < 0 && !fixed) id = d->lookup_or_insert(name.data(), name.size());
+      ids[c] = id;  // -1: no reference of that name, no row matches
+      max_id = std::max(max_id, id);
+    }
+    std::vector<int32_t> map((size_t)(max_id + 1), -1);
+    for (size_t c = 0; c < ids.size(); ++c)
+      if (ids[c] >= 0) map[(size_t)ids[c]] = (int32_t)c;
+    const int rc0 = exon_hip_stream_set_region_set_map(st, map);
+    if (rc0) return rc0;
+    region_set_guard.on = true;
+  }
   if (exon_hip_stream_plan_kind(st) == EXON_HIP_PLAN_SEQ_STATS_HIST) {
     exon_hip_ctx* ctx = exon_hip_stream_ctx(st);
     if (scan->fastq() && scan->gpu_parse)  // before anything is read: the stream and the scan stay as they are
@@ -3151,7 +3183,12 @@ int exon_hip_stream_consume_scan(exon_hip_stream* st, exon_hip_scan* scan, int64
     if (exon::Dictionary* d = dict_of(scan, exon_hip_stream_plan_column(st, 2))) keys = &d->names;
   }
   const int rc2 = exon_hip_stream_end_scan(st, keys, tracked, redirected, rc == EXON_HIP_OK);
-  return rc ? rc : rc2;
+  int rc3 = EXON_HIP_OK;
+  if (region_set_guard.on) {  // (what the scan staged is launched under ITS map)
+    region_set_guard.on = false;
+    rc3 = exon_hip_stream_end_region_set_scan(st);
+  }
+  return rc ? rc : rc2 ? rc2 : rc3;
 }
 
 }  // extern "C"

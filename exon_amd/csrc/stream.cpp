@@ -33,6 +33,7 @@
 #include "host/arrow_build.h"
 #include "host/bitmap.h"
 #include "host/raw_batch.h"
+#include "host/region_set.h"
 #include "internal.h"
 
 namespace {
@@ -82,6 +83,24 @@ struct Slot {
   std::atomic<size_t> pending{0};
 };
 
+// plan kind 11: the region set (host/region_set.h) and its device tables, built once by exon_hip_plan_create_region_set and freed
+// with the plan.  A names-form plan has no map of its own: every consumed scan brings one (exon_hip_stream_set_region_set_map).
+struct PlanRegionSet {
+  exon::RegionSet set;
+  int32_t* d_map = nullptr;
+  int32_t n_map = 0;
+  int32_t* d_off = nullptr;
+  int64_t* d_ends = nullptr;
+  int64_t* d_starts = nullptr;
+  ~PlanRegionSet() {
+    if (d_map) hipFree(d_map);
+    if (d_off) hipFree(d_off);
+    if (d_ends) hipFree(d_ends);
+    if (d_starts) hipFree(d_starts);
+  }
+  exon::RegionSetTables tables(const int32_t* map, int32_t n) const { return exon::RegionSetTables{map, n, d_off, d_ends, d_starts, set.M, set.C}; }
+};
+
 }  // namespace
 
 struct exon_hip_plan {
@@ -91,6 +110,7 @@ struct exon_hip_plan {
   int64_t n_max = 0;  // the last n_max of the n_i64 words fold by unsigned max, not add (CMP_MINMAX_BY_GROUP: its two extreme planes)
   int n_cols;
   ColSpec cols[4];
+  std::unique_ptr<PlanRegionSet> rs;  // REGION_SET_OVERLAP only
 };
 
 struct exon_hip_stream {
@@ -127,6 +147,10 @@ struct exon_hip_stream {
   std::string region_contig;
   bool has_region_contig = false;
   int32_t region_id_override = INT32_MIN;
+  // region-set plans (kind 11) in the names form: the scan being consumed has resolved the set's names in its own dictionary;
+  // d_map / map_cap hold its id -> contig slot map (the re-keying map's buffer: such a plan is not keyed)
+  bool rs_in_scan = false;
+  int32_t rs_n_map = 0;
 };
 enum { KEYS_NONE = 0, KEYS_LOCAL = 1, KEYS_AGREED = 2 };
 constexpr size_t COLL_SCRATCH = 8192;  // device words for the collectives' votes (up to 511 ranks x 16 bytes), allocated with the state
@@ -349,7 +373,7 @@ static int alloc_slot(exon_hip_stream* st, Slot& s) {
 // launch the plan's kernel over device columns (operator argument order) into the packed state [n_i64][n_f64]
 // x_type / y_type: EXON_HIP_X_* of K4's compared column / AVG argument, or -1 = what the plan says
 static int run_plan(const exon_hip_plan* p, void* stream, const exon_hip_column* cols, int64_t n, int flags, void* d_state, int x_type = -1,
-                    int y_type = -1, int32_t region_id = INT32_MIN) {
+                    int y_type = -1, int32_t region_id = INT32_MIN, const int32_t* rs_map = nullptr, int32_t rs_n_map = 0) {
   exon_hip_plan_desc d = p->d;
   if (region_id != INT32_MIN) d.region_chrom_id = region_id;
   if (x_type < 0) x_type = d.x_type;
@@ -382,12 +406,19 @@ static int run_plan(const exon_hip_plan* p, void* stream, const exon_hip_column*
     case EXON_HIP_PLAN_WITHIN_COUNT:
       return exon_op_overlap_count(ctx, stream, &cols[0], &cols[1], &cols[2], n, d.region_chrom_id, d.region_start,
                                    d.region_end, counts, flags, d.kind == EXON_HIP_PLAN_WITHIN_COUNT);
+    case EXON_HIP_PLAN_REGION_SET_OVERLAP:
+      if (p->rs->set.by_name && !rs_map)
+        return fail(ctx, EXON_HIP_ESTATE, "a region-set plan made from contig NAMES has no ids to compare the rows' with: feed it files (exon_hip_stream_consume_scan), "
+                                          "or create the plan from reference ids");
+      return exon_op_region_set_overlap(ctx, stream, &cols[0], &cols[1], &cols[2], n, p->rs->set.by_name ? p->rs->tables(rs_map, rs_n_map) : p->rs->tables(p->rs->d_map, p->rs->n_map),
+                                        counts, flags);
   }
   return fail(ctx, EXON_HIP_EINVAL, "unknown plan kind %d", d.kind);
 }
 static int launch_plan(exon_hip_stream* st, const exon_hip_column* cols, int64_t n) {
   const int flags = st->overwrite_next ? EXON_HIP_LAUNCH_OVERWRITE : EXON_HIP_LAUNCH_ACCUMULATE;
-  int rc = run_plan(st->plan, st->stream, cols, n, flags, st->d_state, st->x_type, st->y_type, st->region_id_override);
+  int rc = run_plan(st->plan, st->stream, cols, n, flags, st->d_state, st->x_type, st->y_type, st->region_id_override, st->rs_in_scan ? st->d_map : nullptr,
+                    st->rs_n_map);
   if (!rc) st->overwrite_next = false;
   return rc;
 }
@@ -527,8 +558,10 @@ static int ensure_capacity(exon_hip_stream* st, int64_t rows, int64_t bytes) {
 extern "C" {
 
 int exon_hip_plan_create(exon_hip_ctx* ctx, const exon_hip_plan_desc* desc, exon_hip_plan** out) {
+  if (out) *out = nullptr;
+  if (desc && desc->kind == EXON_HIP_PLAN_REGION_SET_OVERLAP)
+    return fail(ctx, EXON_HIP_EINVAL, "plan kind %d takes a region set, which exon_hip_plan_desc cannot hold: use exon_hip_plan_create_region_set", desc->kind);
   if (!ctx || !desc || !out) return fail(ctx, EXON_HIP_EINVAL, "exon_hip_plan_create: NULL argument");
-  *out = nullptr;
   exon_hip_plan* p = new (std::nothrow) exon_hip_plan();
   if (!p) return fail(ctx, EXON_HIP_ENOMEM, "out of host memory");
   p->ctx = ctx;
@@ -648,6 +681,142 @@ int exon_hip_plan_destroy(exon_hip_plan* plan) {
   return EXON_HIP_OK;
 }
 
+// plan kind 11.  ctx may be NULL: a host-only plan for exon_hip_region_set_layout / _decode (no device tables, nothing to launch).
+int exon_hip_plan_create_region_set(exon_hip_ctx* ctx, const int32_t columns[3], const char* packed_contig_names, size_t packed_bytes, const int32_t* ref_ids,
+                                    const int64_t* starts, const int64_t* ends, int32_t n_regions, exon_hip_plan** out) {
+  static const char* who = "exon_hip_plan_create_region_set";
+  if (!out) return fail(ctx, EXON_HIP_EINVAL, "%s: NULL argument", who);
+  *out = nullptr;
+  if (n_regions < 1) return fail(ctx, EXON_HIP_EINVAL, "%s: n_regions %d: a region set holds at least one region", who, n_regions);
+  if (n_regions > exon::REGION_SET_MAX_REGIONS) return fail(ctx, EXON_HIP_EUNSUPPORTED, "%s: n_regions %d beyond %d", who, n_regions, exon::REGION_SET_MAX_REGIONS);
+  if (!columns || !starts || !ends || (!packed_contig_names && !ref_ids)) return fail(ctx, EXON_HIP_EINVAL, "%s: NULL argument", who);
+  for (int c = 0; c < 3; ++c)
+    if (columns[c] < 0) return fail(ctx, EXON_HIP_EINVAL, "negative column index");
+  std::unique_ptr<PlanRegionSet> rs(new (std::nothrow) PlanRegionSet());
+  exon_hip_plan* p = new (std::nothrow) exon_hip_plan();
+  if (!rs || !p) {
+    delete p;
+    return fail(ctx, EXON_HIP_ENOMEM, "out of host memory");
+  }
+  std::unique_ptr<exon_hip_plan> guard(p);
+  exon::RegionSet& set = rs->set;
+  set.M = n_regions;
+  set.by_name = packed_contig_names != nullptr;
+  set.starts.assign(starts, starts + n_regions);
+  set.ends.assign(ends, ends + n_regions);
+  set.slot.resize((size_t)n_regions);
+  for (int32_t i = 0; i < n_regions; ++i)
+    if (starts[i] < 1 || ends[i] < starts[i])
+      return fail(ctx, EXON_HIP_EINVAL, "%s: region %d: the interval must satisfy 1 <= start <= end", who, i);
+  int32_t max_id = -1;
+  if (set.by_name) {
+    std::unordered_map<std::string, int32_t> index;
+    size_t at = 0;
+    for (int32_t i = 0; i < n_regions; ++i) {
+      const void* z = at < packed_bytes ? memchr(packed_contig_names + at, 0, packed_bytes - at) : nullptr;
+      if (!z) return fail(ctx, EXON_HIP_EINVAL, "%s: packed_contig_names holds fewer than %d '\\0'-terminated names", who, n_regions);
+      std::string name(packed_contig_names + at, static_cast<const char*>(z));
+      if (name.empty()) return fail(ctx, EXON_HIP_EINVAL, "%s: region %d: empty contig name", who, i);
+      at += name.size() + 1;
+      auto it = index.find(name);
+      if (it == index.end()) {
+        it = index.emplace(name, (int32_t)set.contig_names.size()).first;
+        set.contig_names.push_back(name);
+      }
+      set.slot[(size_t)i] = it->second;
+    }
+    set.C = (int32_t)set.contig_names.size();
+  } else {
+    std::unordered_map<int32_t, int32_t> index;
+    for (int32_t i = 0; i < n_regions; ++i) {
+      if (ref_ids[i] < 0) return fail(ctx, EXON_HIP_EINVAL, "%s: region %d: negative reference id %d", who, i, ref_ids[i]);
+      if (ref_ids[i] >= EXON_HIP_MAX_REFERENCES)
+        return fail(ctx, EXON_HIP_EUNSUPPORTED, "%s: region %d: reference id %d beyond %d (the id -> contig map is a dense table)", who, i, ref_ids[i], EXON_HIP_MAX_REFERENCES - 1);
+      auto it = index.find(ref_ids[i]);
+      if (it == index.end()) {
+        it = index.emplace(ref_ids[i], (int32_t)set.contig_ids.size()).first;
+        set.contig_ids.push_back(ref_ids[i]);
+      }
+      set.slot[(size_t)i] = it->second;
+      max_id = std::max(max_id, ref_ids[i]);
+    }
+    set.C = (int32_t)set.contig_ids.size();
+  }
+  set.build();
+  p->ctx = ctx;
+  memset(&p->d, 0, sizeof p->d);
+  p->d.kind = EXON_HIP_PLAN_REGION_SET_OVERLAP;
+  for (int c = 0; c < 3; ++c) p->d.columns[c] = columns[c];
+  p->n_cols = 3;
+  p->cols[0].elem = 4;
+  p->cols[1].elem = p->cols[2].elem = 8;
+  p->n_i64 = set.words();
+  p->n_f64 = 0;
+  if (ctx) {  // the device tables
+    hipSetDevice(ctx->device);
+    const size_t M = (size_t)set.M;
+    std::vector<int32_t> map;
+    if (!set.by_name) {
+      map.assign((size_t)max_id + 1, -1);
+      for (int32_t c = 0; c < set.C; ++c) map[(size_t)set.contig_ids[(size_t)c]] = c;
+      rs->n_map = (int32_t)map.size();
+    }
+    hipError_t e;
+    if ((!set.by_name && (e = hipMalloc((void**)&rs->d_map, map.size() * 4)) != hipSuccess) || (e = hipMalloc((void**)&rs->d_off, set.off.size() * 4)) != hipSuccess ||
+        (e = hipMalloc((void**)&rs->d_ends, M * 8)) != hipSuccess || (e = hipMalloc((void**)&rs->d_starts, M * 8)) != hipSuccess)
+      return fail(ctx, EXON_HIP_ENOMEM, "%s: device tables: %s", who, hipGetErrorString(e));
+    if ((!set.by_name && (e = hipMemcpy(rs->d_map, map.data(), map.size() * 4, hipMemcpyHostToDevice)) != hipSuccess) ||
+        (e = hipMemcpy(rs->d_off, set.off.data(), set.off.size() * 4, hipMemcpyHostToDevice)) != hipSuccess ||
+        (e = hipMemcpy(rs->d_ends, set.sorted_ends.data(), M * 8, hipMemcpyHostToDevice)) != hipSuccess ||
+        (e = hipMemcpy(rs->d_starts, set.sorted_starts.data(), M * 8, hipMemcpyHostToDevice)) != hipSuccess)
+      return fail(ctx, EXON_HIP_EDEVICE, "%s: device tables: %s", who, hipGetErrorString(e));
+  }
+  p->rs = std::move(rs);
+  *out = guard.release();
+  return EXON_HIP_OK;
+}
+
+static const PlanRegionSet* region_set_of(const exon_hip_plan* plan, const char* who) {
+  if (!plan || plan->d.kind != EXON_HIP_PLAN_REGION_SET_OVERLAP || !plan->rs) {
+    fail(plan ? plan->ctx : nullptr, EXON_HIP_EINVAL, "%s: not a region-set plan (kind %d)", who, EXON_HIP_PLAN_REGION_SET_OVERLAP);
+    return nullptr;
+  }
+  return plan->rs.get();
+}
+
+// host only: word offsets of totals, A, B and the state's size
+int exon_hip_region_set_layout(const exon_hip_plan* plan, int64_t* out /*[4]*/) {
+  const PlanRegionSet* rs = region_set_of(plan, "exon_hip_region_set_layout");
+  if (!rs) return EXON_HIP_EINVAL;
+  if (!out) return fail(plan->ctx, EXON_HIP_EINVAL, "exon_hip_region_set_layout: out is NULL");
+  out[0] = 0;
+  out[1] = 4;
+  out[2] = 4 + (int64_t)rs->set.M + rs->set.C;
+  out[3] = rs->set.words();
+  return EXON_HIP_OK;
+}
+
+// host only: state words -> one count per region, in the caller's order; linear in the state
+int exon_hip_region_set_decode(const exon_hip_plan* plan, const int64_t* state, int64_t* out_counts /*[M]*/) {
+  const PlanRegionSet* rs = region_set_of(plan, "exon_hip_region_set_decode");
+  if (!rs) return EXON_HIP_EINVAL;
+  if (!state || !out_counts) return fail(plan->ctx, EXON_HIP_EINVAL, "exon_hip_region_set_decode: NULL argument");
+  rs->set.decode(state, out_counts);
+  return EXON_HIP_OK;
+}
+
+// K11, bare operator: accumulates into d_state (the plan's state words, zeroed once per query by the caller)
+int exon_hip_region_set_overlap(exon_hip_ctx* ctx, void* stream, const exon_hip_column* ref_id, const exon_hip_column* start, const exon_hip_column* end, int64_t n,
+                                const exon_hip_plan* plan, int64_t* d_state) {
+  const PlanRegionSet* rs = region_set_of(plan, "exon_hip_region_set_overlap");
+  if (!rs) return EXON_HIP_EINVAL;
+  if (!ctx || ctx != plan->ctx) return fail(ctx, EXON_HIP_EINVAL, "exon_hip_region_set_overlap: the plan's tables live on the context it was created with");
+  if (rs->set.by_name)
+    return fail(ctx, EXON_HIP_ESTATE, "a region-set plan made from contig NAMES has no ids to compare the rows' with: feed it files (exon_hip_stream_consume_scan), "
+                                      "or create the plan from reference ids");
+  return exon_op_region_set_overlap(ctx, stream, ref_id, start, end, n, rs->tables(rs->d_map, rs->n_map), d_state, EXON_HIP_LAUNCH_ACCUMULATE);
+}
+
 int exon_hip_plan_state_size(const exon_hip_plan* plan, int64_t* n_i64, int64_t* n_f64) {
   if (!plan || !n_i64 || !n_f64) return fail(nullptr, EXON_HIP_EINVAL, "exon_hip_plan_state_size: NULL argument");
   *n_i64 = plan->n_i64;
@@ -660,6 +829,7 @@ int exon_hip_stream_open(exon_hip_plan* plan, int32_t partition, exon_hip_stream
   if (!plan || !out) return fail(plan ? plan->ctx : nullptr, EXON_HIP_EINVAL, "exon_hip_stream_open: NULL argument");
   *out = nullptr;
   exon_hip_ctx* ctx = plan->ctx;
+  if (!ctx) return fail(nullptr, EXON_HIP_EINVAL, "exon_hip_stream_open: a host-only plan (created without a context) cannot be executed");
   exon_hip_stream* st = new (std::nothrow) exon_hip_stream();
   if (!st) return fail(ctx, EXON_HIP_ENOMEM, "out of host memory");
   st->plan = plan;
@@ -717,6 +887,11 @@ int exon_hip_stream_push(exon_hip_stream* st, struct ArrowArray* batch) {
     return fail(st->ctx, EXON_HIP_ESTATE, "push after finish/close");
   }
   exon_hip_plan* p = st->plan;
+  if (p->rs && p->rs->set.by_name && !st->rs_in_scan) {
+    batch->release(batch);
+    return fail(st->ctx, EXON_HIP_ESTATE, "a region-set plan made from contig NAMES has no ids to compare a pushed batch's with: feed it files "
+                                          "(exon_hip_stream_consume_scan), or create the plan from reference ids");
+  }
   const int64_t rows = batch->length;
   int rc = EXON_HIP_OK;
   const struct ArrowArray* ch[4];
@@ -965,6 +1140,9 @@ int exon_hip_stream_push_device(exon_hip_stream* st, const struct ArrowDeviceArr
   if (dbatch->device_id != st->ctx->device)
     return fail(st->ctx, EXON_HIP_EINVAL, "batch lives on device %lld, stream on %d", (long long)dbatch->device_id, st->ctx->device);
   exon_hip_plan* p = st->plan;
+  if (p->rs && p->rs->set.by_name && !st->rs_in_scan)
+    return fail(st->ctx, EXON_HIP_ESTATE, "a region-set plan made from contig NAMES has no ids to compare a pushed batch's with: feed it files "
+                                          "(exon_hip_stream_consume_scan), or create the plan from reference ids");
   const struct ArrowArray* batch = &dbatch->array;
   const int64_t rows = batch->length;
   exon_hip_column cols[4];
@@ -1137,6 +1315,36 @@ int exon_hip_stream_set_region_id(exon_hip_stream* st, int32_t id) {
   }
   st->region_id_override = id;
   return EXON_HIP_OK;
+}
+// region-set plans (kind 11) in the names form: the set's distinct contig names, in slot order (nullptr: another plan, or ids form)
+const std::vector<std::string>* exon_hip_stream_region_set_names(exon_hip_stream* st) {
+  return st->plan->rs && st->plan->rs->set.by_name ? &st->plan->rs->set.contig_names : nullptr;
+}
+// map[id of the scan's dictionary] = contig slot or -1, for the scan about to be consumed.  Rows staged by the previous file were
+// decoded under ITS ids: they are launched first.  Synchronises the stream (the map is staged from pageable memory).
+int exon_hip_stream_set_region_set_map(exon_hip_stream* st, const std::vector<int32_t>& map) {
+  int rc = flush_slot(st);
+  if (rc) return rc;
+  if (st->map_cap < map.size() || !st->d_map) {
+    HIP_TRY(st->ctx, hipStreamSynchronize(st->stream));
+    if (st->d_map) hipFree(st->d_map);
+    st->d_map = nullptr;
+    st->map_cap = 0;
+    const size_t cap = std::max<size_t>(map.size(), 64);
+    if (hipMalloc((void**)&st->d_map, cap * 4) != hipSuccess) return fail(st->ctx, EXON_HIP_ENOMEM, "region-set id map of %zu entries", cap);
+    st->map_cap = cap;
+  }
+  if (!map.empty()) HIP_TRY(st->ctx, hipMemcpyAsync(st->d_map, map.data(), map.size() * 4, hipMemcpyHostToDevice, st->stream));
+  HIP_TRY(st->ctx, hipStreamSynchronize(st->stream));
+  st->rs_n_map = (int32_t)map.size();
+  st->rs_in_scan = true;
+  return EXON_HIP_OK;
+}
+// the scan is over: what it staged is launched under its map, then the stream has no ids again
+int exon_hip_stream_end_region_set_scan(exon_hip_stream* st) {
+  const int rc = st->closed ? EXON_HIP_OK : flush_slot(st);
+  st->rs_in_scan = false;
+  return rc;
 }
 
 // ---- RCCL (loaded on first use: hosts that never merge across GPUs -- and machines without RCCL -- do not need it) ----
@@ -1949,6 +2157,25 @@ int exon_hip_stream_finish_arrow(exon_hip_stream* st, struct ArrowArray* out, st
           }
       make_struct(out, (int64_t)stat.size(), {prim(stat), prim(bin), prim(cnt)});
       make_schema(out_schema, "+s", "", false, {field("i", "stat", false), field("i", "bin", false), field("l", "count", false)});
+      break;
+    }
+    case EXON_HIP_PLAN_REGION_SET_OVERLAP: {  // one row per region, in the caller's order
+      const exon::RegionSet& set = p->rs->set;
+      std::vector<int64_t> cnt((size_t)set.M);
+      set.decode(counts.data(), cnt.data());
+      struct ArrowArray* contig;
+      if (set.by_name) {
+        std::vector<std::string> names((size_t)set.M);
+        for (int32_t i = 0; i < set.M; ++i) names[(size_t)i] = set.contig_names[(size_t)set.slot[(size_t)i]];
+        contig = exon::utf8_array(names);
+      } else {
+        std::vector<int32_t> ids((size_t)set.M);
+        for (int32_t i = 0; i < set.M; ++i) ids[(size_t)i] = set.contig_ids[(size_t)set.slot[(size_t)i]];
+        contig = prim(ids);
+      }
+      make_struct(out, (int64_t)set.M, {contig, prim(set.starts), prim(set.ends), prim(cnt)});
+      make_schema(out_schema, "+s", "", false,
+                  {field(set.by_name ? "u" : "i", "contig", false), field("l", "start", false), field("l", "end", false), field("l", "count", false)});
       break;
     }
     default:

@@ -353,6 +353,31 @@ class Context:
         d = L.PlanDesc(kind=L.PLAN_SEQ_STATS_HIST, lmax=lmax)
         return Plan(self, d, columns)
 
+    def plan_region_set_overlap(self, regions, columns=(2, 3, 4)):
+        """K6's overlap count for every region of a set in one pass over the rows (plan kind 11).  `regions`: (contig, start, end)
+        triples, 1-based inclusive, end None = open; contig an int (reference ids, the caller's or the file's own) in all of them
+        or a str (names, resolved by every consumed scan in its own header order) in all of them.  State: 4 + 2 * (M + C) int64
+        words, all of which add; RegionSetPlan.decode turns them into one count per region, finish_arrow into a table."""
+        return RegionSetPlan(self, regions, columns)
+
+    def region_set_overlap(self, ref_id, ref_valid, start, start_valid, end, end_valid, n, plan, d_state, stream=None):
+        """K11 (bare operator, ids form): accumulates the batch into `d_state` (plan.n_i64 int64 words)."""
+        c0, c1, c2 = _col(ref_id, ref_valid, None, n), _col(start, start_valid, None, n), _col(end, end_valid, None, n)
+        self._check(self.lib.exon_hip_region_set_overlap(self.h, stream, C.byref(c0), C.byref(c1), C.byref(c2), n, plan.h,
+                                                         d_state.ptr if isinstance(d_state, DeviceBuffer) else d_state))
+
+
+def region_set_layout(plan):
+    """exon_hip_region_set_layout (host-only): word offsets of the totals / A / B sections of a region-set plan's state, and its
+    size in words."""
+    return plan.layout()
+
+
+def region_set_decode(plan, state):
+    """exon_hip_region_set_decode (host-only): the state's words -> one count per region, in the order the regions were given.
+    Linear: the decoded states of partitions add up to the decoded merged state."""
+    return plan.decode(state)
+
 
 def seq_stats_layout(lmax):
     """exon_hip_seq_stats_layout (host-only): word offsets of the totals / composition / length / length_log2 / gc_percent
@@ -1215,6 +1240,62 @@ class Plan:
     def close(self):
         if self.h:
             self.ctx.lib.exon_hip_plan_destroy(self.h)
+            self.h = None
+
+
+class RegionSetPlan(Plan):
+    """Plan kind 11 (exon_hip_plan_create_region_set).  ctx None: a host-only plan that serves layout() and decode() and cannot be
+    launched."""
+
+    def __init__(self, ctx, regions, columns=(2, 3, 4)):
+        self.ctx = ctx
+        self.lib = ctx.lib if ctx is not None else L.load()
+        regions = [(c, int(s), L.REGION_OPEN_END if e is None else int(e)) for (c, s, e) in regions]
+        by_name = [isinstance(c, (str, bytes)) for c, _, _ in regions]
+        if any(by_name) and not all(by_name):
+            raise ValueError("a region set names its contigs either all by name or all by reference id")
+        self.by_name = bool(regions) and by_name[0]
+        self.regions = regions
+        self.n_cols = 3
+        m = len(regions)
+        starts = np.array([r[1] for r in regions], np.int64)
+        ends = np.array([r[2] for r in regions], np.int64)
+        cols = (C.c_int32 * 3)(*columns)
+        packed, ids = None, None
+        if self.by_name:
+            packed = b"".join((c if isinstance(c, bytes) else c.encode()) + b"\0" for c, _, _ in regions)
+        else:
+            ids = np.array([r[0] for r in regions], np.int32)
+        h = C.c_void_p()
+        self._check(self.lib.exon_hip_plan_create_region_set(ctx.h if ctx is not None else None, cols, packed, len(packed) if packed else 0,
+                                                             ids.ctypes.data if ids is not None and m else None,
+                                                             starts.ctypes.data if m else None, ends.ctypes.data if m else None, m, C.byref(h)))
+        self.h = h
+        a, b = C.c_int64(), C.c_int64()
+        self._check(self.lib.exon_hip_plan_state_size(h, C.byref(a), C.byref(b)))
+        self.n_i64, self.n_f64 = a.value, b.value
+
+    def _check(self, rc):
+        if rc < 0:
+            raise ExonHipError(rc, self.lib.exon_hip_last_error(None).decode(errors="replace"))
+        return rc
+
+    def layout(self):
+        out = (C.c_int64 * 4)()
+        self._check(self.lib.exon_hip_region_set_layout(self.h, out))
+        return tuple(out)
+
+    def decode(self, state):
+        state = np.ascontiguousarray(state, np.int64)
+        if state.size != self.n_i64:
+            raise ValueError("the state of this plan has %d words, %d given" % (self.n_i64, state.size))
+        out = np.zeros(len(self.regions), np.int64)
+        self._check(self.lib.exon_hip_region_set_decode(self.h, state.ctypes.data, out.ctypes.data))
+        return out
+
+    def close(self):
+        if self.h:
+            self.lib.exon_hip_plan_destroy(self.h)
             self.h = None
 
 

@@ -360,6 +360,53 @@ int exon_hip_plan_destroy(exon_hip_plan* plan);
 /* number of int64 / float64 words of the partial-aggregate state of this plan */
 int exon_hip_plan_state_size(const exon_hip_plan* plan, int64_t* n_i64, int64_t* n_f64);
 
+/* ---- K11: overlap counts for a whole region set in one pass (plan kind 11) -------------------------------------------------------
+ * K6's question for M regions at once -- what `bedtools multicov` / `intersect -c` answer, a join + GROUP BY in the reference: for
+ * every region i, the rows with ref_id = the region's contig AND start <= re_i AND end >= rs_i, all three valid, 1-based inclusive.
+ * Every row is visited once, whatever M is: per contig the region ends and the region starts are sorted; a row [s, e] finds
+ * p = |{ i : re_i < s }| and q = |{ i : rs_i <= e }| by two binary searches and adds 1 to A[p] and to B[q]; region i of rank a_i among
+ * the ends and b_i among the starts then has  count_i = sum(A[0 .. a_i]) - sum(B[0 .. b_i])  (DESIGN.md 3.5).
+ *
+ * The region set does not fit exon_hip_plan_desc, so the plan has a constructor of its own (exon_hip_plan_create with kind 11 is
+ * EXON_HIP_EINVAL and names it).  columns: ref_id (Int32), start (Int64), end (Int64) -- K6's order.
+ *   1 <= n_regions <= 1048576 (more: EXON_HIP_EUNSUPPORTED); every region 1 <= start <= end, end may be EXON_HIP_REGION_OPEN_END;
+ *   duplicate, nested and overlapping regions are legal, each has its own count.
+ *   ids form (packed_contig_names NULL): ref_ids[i] is the caller's or the file's own id, as K6's region_chrom_id; a negative id is
+ *     EXON_HIP_EINVAL, one of EXON_HIP_MAX_REFERENCES or more EXON_HIP_EUNSUPPORTED (the id -> contig map is a dense table).
+ *   names form: n_regions '\0'-terminated names in packed_bytes bytes.  exon_hip_stream_consume_scan resolves every distinct name in
+ *     that scan's contig / reference dictionary by exon_hip_stream_set_region_contig's rule (a name the file lacks contributes no
+ *     rows; formats without a header may intern it), so files with different header orders add up in one stream.  Such a plan has
+ *     no ids of its own: exon_hip_stream_push, exon_hip_stream_push_device, exon_hip_plan_launch and the bare operator are
+ *     EXON_HIP_ESTATE.
+ *   ctx may be NULL: a host-only plan that serves exon_hip_region_set_layout / _decode / exon_hip_plan_state_size and nothing else.
+ *
+ * State: 4 + 2 * (M + C) int64 words, n_f64 = 0; M = regions, C = distinct contigs of the set.  Every word adds, so streams, chunked
+ * launches, exon_hip_plan_fold_states, exon_hip_stream_all_reduce and the file pipelines carry it like K9's and K10's; the words are
+ * keyed by the region set, not by a file's dictionary.
+ *   totals[4]  counted, null_rows (any of the three values invalid), elsewhere (the contig is not in the set: also an id below 0 or
+ *              beyond the map), inverted (end < start); the four sum to the rows seen
+ *   A[M + C], B[M + C]  contig c (in order of first appearance in the set, m_c regions) owns m_c + 1 consecutive bins of each
+ * DECISION: a row with end < start adds to `inverted` and to NO region.  K6 would count such a row for a region that strictly
+ * contains the gap between end and start; the identity above needs s <= e, and no reader here emits such a row for a valid file.
+ *
+ * The device tables (id -> contig map, per-contig offsets, sorted ends and starts) are built once and owned by the plan.  Sets with
+ * M + C <= 6144 are searched and counted in LDS; larger ones search through L2 and count with global atomics.  The columns' values
+ * need their element's alignment only (4 / 8 / 8 bytes). */
+#define EXON_HIP_PLAN_REGION_SET_OVERLAP 11
+#define EXON_HIP_REGION_SET_MAX_REGIONS 1048576
+int exon_hip_plan_create_region_set(exon_hip_ctx* ctx, const int32_t* columns /*[3]*/,
+                                    const char* packed_contig_names /* n_regions '\0'-terminated names, or NULL */, size_t packed_bytes,
+                                    const int32_t* ref_ids /* used when names are NULL */, const int64_t* starts, const int64_t* ends,
+                                    int32_t n_regions, exon_hip_plan** out);
+/* host only: out = word offsets of totals, A, B, and the word count */
+int exon_hip_region_set_layout(const exon_hip_plan* plan, int64_t* out /*[4]*/);
+/* host only: the state's words -> one count per region, in the caller's region order.  Linear: decoded partial states add up to the
+ * decoded merged state. */
+int exon_hip_region_set_decode(const exon_hip_plan* plan, const int64_t* state, int64_t* out_counts /*[M]*/);
+/* K11, bare operator (ids form; `ctx` is the plan's): d_state (exon_hip_plan_state_size words) += this batch */
+int exon_hip_region_set_overlap(exon_hip_ctx* ctx, void* stream, const exon_hip_column* ref_id /*i32*/, const exon_hip_column* start /*i64*/,
+                                const exon_hip_column* end /*i64*/, int64_t n, const exon_hip_plan* plan, int64_t* d_state);
+
 /* Stateless form of a push: run the plan's fused kernel over HBM-resident columns (`columns[i]` = operator argument i, see
  * exon_hip_plan_desc.columns for the order; n_columns must match the plan) on the caller's hipStream_t into a caller-owned
  * packed partial state [n_i64 x int64][n_f64 x float64] (exon_hip_plan_state_size; 8-byte aligned device memory).

@@ -32,6 +32,8 @@ pub const EXON_HIP_PLAN_WITHIN_COUNT: i32 = 7;
 pub const EXON_HIP_PLAN_CMP_MINMAX_BY_GROUP: i32 = 8; // K4's fields; state = 4 * n_groups int64 words (counts, then min / max words)
 pub const EXON_HIP_PLAN_READ_STATS_HIST: i32 = 9; // lmax, columns (sequence, quality_scores); state = exon_hip_read_stats_layout words, all add
 pub const EXON_HIP_PLAN_SEQ_STATS_HIST: i32 = 10; // lmax, column (sequence); state = exon_hip_seq_stats_layout words, all add
+pub const EXON_HIP_PLAN_REGION_SET_OVERLAP: i32 = 11; // made by exon_hip_plan_create_region_set; state = 4 + 2 * (M + C) words, all add
+pub const EXON_HIP_REGION_SET_MAX_REGIONS: i32 = 1048576;
 pub const EXON_HIP_GT: i32 = 0;
 pub const EXON_HIP_GE: i32 = 1;
 pub const EXON_HIP_LT: i32 = 2;
@@ -149,6 +151,14 @@ extern "C" {
     pub fn exon_hip_seq_stats_hist_views(ctx: *mut exon_hip_ctx, stream: *mut c_void, views: *const exon_hip_fasta_views, lmax: i32, d_state: *mut i64) -> c_int;
     /// host-only: word offsets of K10's totals / composition / length / length_log2 / gc_percent sections and the state's size
     pub fn exon_hip_seq_stats_layout(lmax: i32, out: *mut i64) -> c_int;
+    /// K11: the plan of a whole region set (ids form: `packed_contig_names` null; names form: n_regions NUL-terminated names, resolved per consumed scan)
+    pub fn exon_hip_plan_create_region_set(ctx: *mut exon_hip_ctx, columns: *const i32, packed_contig_names: *const c_char, packed_bytes: usize, ref_ids: *const i32, starts: *const i64, ends: *const i64, n_regions: i32, out: *mut *mut exon_hip_plan) -> c_int;
+    /// host-only: word offsets of K11's totals / A / B sections and the state's size
+    pub fn exon_hip_region_set_layout(plan: *const exon_hip_plan, out: *mut i64) -> c_int;
+    /// host-only: K11's state words -> one count per region, in the caller's order; linear in the state
+    pub fn exon_hip_region_set_decode(plan: *const exon_hip_plan, state: *const i64, out_counts: *mut i64) -> c_int;
+    /// K11 (bare operator, ids form): overlap counts of every region of the plan's set over one batch; accumulates
+    pub fn exon_hip_region_set_overlap(ctx: *mut exon_hip_ctx, stream: *mut c_void, ref_id: *const exon_hip_column, start: *const exon_hip_column, end: *const exon_hip_column, n: i64, plan: *const exon_hip_plan, d_state: *mut i64) -> c_int;
     /// fold of `world` packed states by the plan's own layout (add; unsigned max for K8's extreme planes)
     pub fn exon_hip_plan_fold_states(plan: *const exon_hip_plan, stream: *mut c_void, d_gathered: *const c_void, world: i32, d_out: *mut c_void) -> c_int;
     pub fn exon_hip_stream_open(plan: *mut exon_hip_plan, partition: i32, out: *mut *mut exon_hip_stream) -> c_int;
