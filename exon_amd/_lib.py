@@ -167,6 +167,8 @@ PLAN_REGION_SET_OVERLAP = 11
 REGION_SET_MAX_REGIONS = 1 << 20
 REGION_SET_LDS_MAX = 6144  # kernels.h: sets with M + C up to this are searched and counted in LDS
 REGION_SET_TILE_SMALL, REGION_SET_TILE_BIG = 2048, 8192  # kernels.h: rows per workgroup tile of the two launch shapes
+PLAN_REGION_SET_BASES = 12
+REGION_BASES_LDS_MAX = 4096  # kernels.h: sets with P + C up to this are searched and summed in LDS (32 B a unit: 128 KiB)
 LAUNCH_ACCUMULATE = 0
 LAUNCH_OVERWRITE = 1
 CMP = {">": 0, ">=": 1, "<": 2, "<=": 3, "=": 4, "==": 4, "!=": 5, "<>": 5}
@@ -221,6 +223,10 @@ SIGNATURES = {
     "exon_hip_region_set_layout": (C.c_int, [_vp, C.POINTER(_i64)]),
     "exon_hip_region_set_decode": (C.c_int, [_vp, _vp, _vp]),
     "exon_hip_region_set_overlap": (C.c_int, [_vp, _vp, _colp, _colp, _colp, _i64, _vp, _vp]),
+    "exon_hip_plan_create_region_set_bases": (C.c_int, [_vp, C.POINTER(_i32), C.c_char_p, C.c_size_t, _vp, _vp, _vp, _i32, C.POINTER(_vp)]),
+    "exon_hip_region_bases_layout": (C.c_int, [_vp, C.POINTER(_i64)]),
+    "exon_hip_region_bases_decode": (C.c_int, [_vp, _vp, _vp]),
+    "exon_hip_region_set_bases": (C.c_int, [_vp, _vp, _colp, _colp, _colp, _i64, _vp, _vp]),
     "exon_hip_rccl_unique_id": (C.c_int, [_vp]),
     "exon_hip_rccl_comm_init": (C.c_int, [_vp, _vp, _i32, _i32, C.POINTER(_vp)]),
     "exon_hip_rccl_comm_destroy": (C.c_int, [_vp]),

@@ -54,7 +54,8 @@ int get_workspace(exon_hip_ctx* ctx, hipStream_t s, size_t words, Workspace* out
     // status[0] = device error word, status[1..7] = scratch flags (K5 path selection), then 64 bytes of 0xFF
     // (stand-in for absent validity bitmaps)
     if (hipMalloc(&ws.status, 8 * sizeof(int) + 64) != hipSuccess) return EXON_HIP_ENOMEM;
-    if (hipMemset(ws.status, 0, 8 * sizeof(int)) != hipSuccess || hipMemset(ws.status + 8, 0xFF, 64) != hipSuccess) {
+    // (the fills run on the NULL stream, which does not order the non-blocking streams the kernels run on: wait for them)
+    if (hipMemset(ws.status, 0, 8 * sizeof(int)) != hipSuccess || hipMemset(ws.status + 8, 0xFF, 64) != hipSuccess || hipStreamSynchronize(nullptr) != hipSuccess) {
       hipFree(ws.status);
       ws.status = nullptr;
       return EXON_HIP_EDEVICE;
@@ -628,6 +629,32 @@ int exon_op_region_set_overlap(exon_hip_ctx* ctx, void* stream, const exon_hip_c
   HIP_TRY(ctx, exon::launch_region_set_overlap(s, cfg_for(ctx, flags), reinterpret_cast<const uint8_t*>(ws.status + 8), (const int32_t*)ref_id->values,
                                                ref_id->validity, (const int64_t*)start->values, start->validity, (const int64_t*)end->values,
                                                end->validity, n, t, d_state));
+  return EXON_HIP_OK;
+}
+
+// K12 (region_bases.hip): the tables are the plan's (stream.cpp).  Column bases need their element's alignment only.
+int exon_op_region_set_bases(exon_hip_ctx* ctx, void* stream, const exon_hip_column* ref_id, const exon_hip_column* start, const exon_hip_column* end,
+                             int64_t n, const exon::RegionBasesTables& t, int64_t* d_state, int flags) {
+  static const char* who = "exon_hip_region_set_bases";
+  if (!ctx || !d_state) return fail(ctx, EXON_HIP_EINVAL, "%s: NULL argument", who);
+  if (reinterpret_cast<uintptr_t>(d_state) & 7) return fail(ctx, EXON_HIP_EINVAL, "%s: d_state must be 8-byte aligned", who);
+  if (n < 0) return fail(ctx, EXON_HIP_EINVAL, "n < 0");
+  hipStream_t s = pick_stream(ctx, stream);
+  if (n == 0) return empty_input(ctx, s, flags, d_state, (size_t)exon::region_bases_words(t.P, t.C) * 8);
+  const exon_hip_column* cols[3] = {ref_id, start, end};
+  static const char* names[3] = {"ref_id", "start", "end"};
+  for (int c = 0; c < 3; ++c) {
+    if (!cols[c] || !cols[c]->values) return fail(ctx, EXON_HIP_EINVAL, "%s: column %s is NULL", who, names[c]);
+    if (cols[c]->length < n) return fail(ctx, EXON_HIP_EINVAL, "%s: %s: length %lld < n %lld", who, names[c], (long long)cols[c]->length, (long long)n);
+    if (reinterpret_cast<uintptr_t>(cols[c]->values) & (c ? 7 : 3)) return fail(ctx, EXON_HIP_EINVAL, "%s: %s: values must be %d-byte aligned", who, names[c], c ? 8 : 4);
+  }
+  if (!t.map || !t.poff || !t.points) return fail(ctx, EXON_HIP_ESTATE, "%s: the plan has no device tables", who);
+  Workspace ws;
+  int rc;
+  if ((rc = get_workspace(ctx, s, 0, &ws))) return fail(ctx, rc, "workspace allocation failed");
+  HIP_TRY(ctx, exon::launch_region_set_bases(s, cfg_for(ctx, flags), reinterpret_cast<const uint8_t*>(ws.status + 8), (const int32_t*)ref_id->values,
+                                             ref_id->validity, (const int64_t*)start->values, start->validity, (const int64_t*)end->values,
+                                             end->validity, n, t, d_state));
   return EXON_HIP_OK;
 }
 

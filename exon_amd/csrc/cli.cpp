@@ -23,6 +23,7 @@
 //   SELECT * FROM fasta_seq_stats('<p>'[, 'gzip'])                                                -- K10
 //   SELECT COUNT(*) FROM <bam table> WHERE bam_region_filter('<r>', reference, start, end)          -- K6 (plain table; INDEXED_BAM plans chunks on the host)
 //   SELECT * FROM overlap_counts('<bam|sam|cram|gff|gtf file>', '<regions.bed>'[, 'gzip'])       -- K11: one row per BED line, in file order
+//   SELECT * FROM covered_bases('<bam|sam|cram|gff|gtf file>', '<regions.bed>'[, 'gzip'])        -- K12: the rows' bases inside each BED line
 //   DROP TABLE t;
 #include <dirent.h>
 #include <sys/stat.h>
@@ -143,7 +144,8 @@ struct Source {  // resolved FROM clause
   std::string region;  // from *_indexed_scan
   bool indexed = false;
   int n_fields = 12;  // BED
-  std::string regions_bed;  // overlap_counts: the BED file of the region set
+  std::string regions_bed;  // overlap_counts / covered_bases: the BED file of the region set
+  bool bases = false;       // covered_bases: K12's sums instead of K11's counts
 };
 
 struct Session {
@@ -430,11 +432,12 @@ Source resolve_from(Session& se, Parser& ps) {
   Source src;
   const std::string name = ps.ident();
   const std::string lname = lower(name);
-  if (ps.accept_sym("(")) {  // table function: <fmt>_scan / <fmt>_indexed_scan / fastq_quality_histogram / fastq_read_stats / fasta_seq_stats / overlap_counts
+  if (ps.accept_sym("(")) {  // table function: <fmt>_scan / <fmt>_indexed_scan / fastq_quality_histogram / fastq_read_stats / fasta_seq_stats / overlap_counts / covered_bases
     const std::string path = ps.str();
-    if (lname == "overlap_counts") {  // ('<file>', '<regions.bed>'[, '<compression>']): the source's format by its extension
+    if (lname == "overlap_counts" || lname == "covered_bases") {  // ('<file>', '<regions.bed>'[, '<compression>']): the source's format by its extension
       ps.expect_sym(",");
       src.regions_bed = ps.str();
+      src.bases = lname == "covered_bases";
       if (ps.accept_sym(",")) src.compression = compression_of(ps.str());
       ps.expect_sym(")");
       std::string stem = lower(path);
@@ -445,8 +448,8 @@ Source resolve_from(Session& se, Parser& ps) {
       else if (ends_with(stem, ".cram")) src.format = EXON_HIP_FORMAT_CRAM;
       else if (ends_with(stem, ".gff") || ends_with(stem, ".gff3")) src.format = EXON_HIP_FORMAT_GFF;
       else if (ends_with(stem, ".gtf")) src.format = EXON_HIP_FORMAT_GTF;
-      else if (ends_with(stem, ".bed")) throw Err("overlap_counts: a BED source is not served (its half-open columns need the strict form); sources are BAM, SAM, CRAM, GFF and GTF files");
-      else throw Err("overlap_counts: cannot tell the format of '" + path + "' from its extension (.bam .sam .cram .gff .gff3 .gtf, optionally .gz / .bgz)");
+      else if (ends_with(stem, ".bed")) throw Err(lname + ": a BED source is not served (its half-open columns need the strict form); sources are BAM, SAM, CRAM, GFF and GTF files");
+      else throw Err(lname + ": cannot tell the format of '" + path + "' from its extension (.bam .sam .cram .gff .gff3 .gtf, optionally .gz / .bgz)");
       list_files(path, format_exts(src.format, ""), &src.files);
       return src;
     }
@@ -671,7 +674,7 @@ void exec_select(Session& se, Parser& ps) {
     return;
   }
 
-  if (!src.regions_bed.empty()) {  // K11: every region of the BED file over the source in ONE pass; the names are resolved per file
+  if (!src.regions_bed.empty()) {  // K11 / K12: every region of the BED file over the source in ONE pass; the names are resolved per file
     std::ifstream in(src.regions_bed);
     if (!in) throw Err("no such file: " + src.regions_bed);
     std::vector<std::string> names;
@@ -697,7 +700,8 @@ void exec_select(Session& se, Parser& ps) {
     const bool annotation = src.format == EXON_HIP_FORMAT_GFF || src.format == EXON_HIP_FORMAT_GTF;
     const int32_t columns[3] = {annotation ? 0 : 2, 3, 4};
     StreamGuard sg;
-    ck(ctx, exon_hip_plan_create_region_set(ctx, columns, packed.data(), packed.size(), nullptr, starts.data(), ends.data(), (int32_t)names.size(), &sg.p));
+    ck(ctx, (src.bases ? exon_hip_plan_create_region_set_bases : exon_hip_plan_create_region_set)(ctx, columns, packed.data(), packed.size(), nullptr, starts.data(),
+                                                                                                   ends.data(), (int32_t)names.size(), &sg.p));
     ck(ctx, exon_hip_stream_open(sg.p, 0, &sg.s));
     for (const auto& f : src.files) {  // one stream: the state is keyed by the region set, the files add up
       ScanGuard g; open_scan(src, f, nullptr, "", &g, true);
@@ -707,10 +711,10 @@ void exec_select(Session& se, Parser& ps) {
     ck(ctx, exon_hip_plan_state_size(sg.p, &n_i64, &n_f64));
     std::vector<int64_t> state((size_t)n_i64), counts(names.size());
     ck(ctx, exon_hip_stream_finish(sg.s, state.data(), nullptr));
-    ck(ctx, exon_hip_region_set_decode(sg.p, state.data(), counts.data()));
+    ck(ctx, (src.bases ? exon_hip_region_bases_decode : exon_hip_region_set_decode)(sg.p, state.data(), counts.data()));
     std::vector<std::vector<std::string>> rows;
     for (size_t i = 0; i < names.size(); ++i) rows.push_back({names[i], std::to_string(starts[i]), std::to_string(ends[i]), std::to_string(counts[i])});
-    print_table({"contig", "start", "end", "count"}, rows, se.quiet);
+    print_table({"contig", "start", "end", src.bases ? "bases" : "count"}, rows, se.quiet);
     return;
   }
 
@@ -1089,6 +1093,7 @@ int main(int argc, char** argv) {
              "             fastq_read_stats('<path>')\n"
              "             fasta_seq_stats('<path>'[, 'gzip'])\n"
              "             overlap_counts('<bam|sam|cram|gff|gtf file>', '<regions.bed>'[, 'gzip'])   one row per BED line: contig, start, end (1-based closed), count\n"
+             "             covered_bases('<bam|sam|cram|gff|gtf file>', '<regions.bed>'[, 'gzip'])    one row per BED line: contig, start, end (1-based closed), bases\n"
              "  queries:   SELECT COUNT(*) FROM <src> [WHERE chrom = 'c' AND pos >= a AND pos <= b | vcf_region_filter('r', chrom) | bam_region_filter('r', reference, start, end)\n"
              "             | gff_region_filter('r', seqname[, start])]\n"
              "             SELECT COUNT(*) FROM <bam|sam> WHERE [bam_region_filter('r', reference, start, end) AND] flag & M = V [AND CAST(mapping_quality AS INT) >= q]\n"

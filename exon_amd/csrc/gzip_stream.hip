@@ -1128,7 +1128,8 @@ int exon_hip_gzip_stream_create(exon_hip_ctx* ctx, int64_t max_comp_bytes, int64
   ok = ok && hipHostMalloc((void**)&s->h_res, nc * sizeof(GzChunk)) == hipSuccess && hipHostMalloc((void**)&s->h_members, nc * MAX_MEMBER_ENDS * sizeof(GzMember)) == hipSuccess &&
        hipHostMalloc((void**)&s->h_tasks, nc * sizeof(GzTask)) == hipSuccess &&
        hipHostMalloc((void**)&s->h_acc, nc * sizeof(Accepted)) == hipSuccess && hipHostMalloc((void**)&s->h_pieces, s->max_pieces * sizeof(CrcPiece)) == hipSuccess;
-  if (ok) ok = hipMemset(s->d_win[0], 0, WIN) == hipSuccess && hipMemset(s->d_win[1], 0, WIN) == hipSuccess;
+  // (NULL-stream fills: waited for, the decoder's non-blocking streams are not ordered behind them)
+  if (ok) ok = hipMemset(s->d_win[0], 0, WIN) == hipSuccess && hipMemset(s->d_win[1], 0, WIN) == hipSuccess && hipStreamSynchronize(nullptr) == hipSuccess;
   if (!ok) {
     (void)hipGetLastError();
     gz_free(s.get());

@@ -2719,7 +2719,8 @@ unsigned* par_stats_buffer(int dev) {
   std::lock_guard<std::mutex> g(g_par_mu);
   ParDev& d = g_par_dev[dev];
   if (!d.stats) {
-    if (hipMalloc((void**)&d.stats, 64 * sizeof(unsigned)) != hipSuccess || hipMemset(d.stats, 0, 64 * sizeof(unsigned)) != hipSuccess) {
+    if (hipMalloc((void**)&d.stats, 64 * sizeof(unsigned)) != hipSuccess || hipMemset(d.stats, 0, 64 * sizeof(unsigned)) != hipSuccess ||
+        hipStreamSynchronize(nullptr) != hipSuccess) {  // (a NULL-stream fill: waited for)
       (void)hipGetLastError();
       d.stats = nullptr;
     }

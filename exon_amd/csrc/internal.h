@@ -184,7 +184,10 @@ class PoolBufs {
       return nullptr;
     }
     dev_.push_back(p);
-    if (fill >= 0 && (err_ = hipMemset(p, fill, bytes)) != hipSuccess) return nullptr;
+    // The fill runs on the NULL stream and a memset of device memory may return before it has run; the kernels that read the buffer
+    // run on non-blocking streams, which the null stream does not order.  Without the wait a recycled buffer can still hold another
+    // parser's words when the first kernel reads them (the line index: look-back words of the same generation), or be zeroed under it.
+    if (fill >= 0 && ((err_ = hipMemset(p, fill, bytes)) != hipSuccess || (err_ = hipStreamSynchronize(nullptr)) != hipSuccess)) return nullptr;
     return static_cast<T*>(p);
   }
   template <class T>
@@ -242,6 +245,8 @@ int exon_op_seq_stats_hist(exon_hip_ctx* ctx, void* stream, const exon_hip_colum
 int exon_op_seq_stats_hist_views(exon_hip_ctx* ctx, void* stream, const exon_hip_fasta_views* views, int32_t lmax, int64_t* d_state, int flags);
 int exon_op_region_set_overlap(exon_hip_ctx* ctx, void* stream, const exon_hip_column* ref_id, const exon_hip_column* start, const exon_hip_column* end,
                                int64_t n, const exon::RegionSetTables& tables, int64_t* d_state, int flags);
+int exon_op_region_set_bases(exon_hip_ctx* ctx, void* stream, const exon_hip_column* ref_id, const exon_hip_column* start, const exon_hip_column* end,
+                             int64_t n, const exon::RegionBasesTables& tables, int64_t* d_state, int flags);
 // chunk c is q[c * stride]
 int exon_op_qual_pos_hist_chunks(exon_hip_ctx* ctx, void* stream, const exon_hip_column* q, int stride, int32_t n_chunks,
                                  const int64_t* n_reads, int32_t lmax, int64_t* d_hist, int flags);

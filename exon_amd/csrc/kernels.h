@@ -134,6 +134,28 @@ hipError_t launch_region_set_overlap(hipStream_t s, const LaunchCfg& cfg, const 
                                      const int64_t* start, const uint8_t* start_valid, const int64_t* end, const uint8_t* end_valid, int64_t n,
                                      const RegionSetTables& t, int64_t* d_state);
 
+// K12 (region_bases.hip): the bases of the rows that fall inside every region of a set, in one pass; state [counted, null_rows,
+// elsewhere, inverted] [Ns: P + C] [Ss: P + C] [Ne: P + C] [Se: P + C], every word modulo 2^64 (include/exon_hip.h,
+// exon_hip_region_bases_layout).  Device tables: map[n_map] as K11's, poff[C + 1] = points in front of each contig, points[P] sorted
+// and unique within each contig.  K11's row loop, tiles (RS_TILE_SMALL / RS_TILE_BIG) and `ones`.
+// REGION_BASES_LDS_MAX bounds P + C of the LDS tier.  One unit of P + C takes at most 8 B of point table (P <= P + C) and, per bin,
+// u32 Ns + u32 Ne + u64 Ss + u64 Se = 24 B: 32 B, so 4096 units are 128 KiB of the CU's 160 KiB.  The largest power of two that
+// fits (K11 likewise stops short of the 160 KiB a workgroup may ask for, at 144); a bound of 5119 (all of it, untried) would move the
+// tier edge by a quarter only.  Larger sets search through L2 and add to the state with global 64-bit atomics.
+constexpr int REGION_BASES_LDS_MAX = 4096;
+constexpr int64_t region_bases_words(int64_t P, int64_t C) { return 4 + 4 * (P + C); }
+constexpr size_t region_bases_lds_bytes(int P, int C) { return (size_t)P * 8 + (size_t)(P + C) * 24; }
+struct RegionBasesTables {
+  const int32_t* map;
+  int32_t n_map;
+  const int32_t* poff;
+  const int64_t* points;
+  int32_t P, C;
+};
+hipError_t launch_region_set_bases(hipStream_t s, const LaunchCfg& cfg, const uint8_t* ones, const int32_t* ref, const uint8_t* ref_valid,
+                                   const int64_t* start, const uint8_t* start_valid, const int64_t* end, const uint8_t* end_valid, int64_t n,
+                                   const RegionBasesTables& t, int64_t* d_state);
+
 // pushed-down region filter as a row mask: out_valid = in_valid AND (row hits the region); *n_pass += rows kept.
 // point form (VCF): id_col = chrom id, start = pos; range form (BAM): id_col = reference id, [start, end].
 hipError_t launch_region_mask(hipStream_t s, bool range_form, const int32_t* id_col, const uint8_t* id_valid, const int64_t* start,

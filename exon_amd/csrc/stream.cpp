@@ -33,6 +33,7 @@
 #include "host/arrow_build.h"
 #include "host/bitmap.h"
 #include "host/raw_batch.h"
+#include "host/region_bases.h"
 #include "host/region_set.h"
 #include "internal.h"
 
@@ -101,6 +102,22 @@ struct PlanRegionSet {
   exon::RegionSetTables tables(const int32_t* map, int32_t n) const { return exon::RegionSetTables{map, n, d_off, d_ends, d_starts, set.M, set.C}; }
 };
 
+// plan kind 12: the set's point table (host/region_bases.h) and its device copy, built once by exon_hip_plan_create_region_set_bases.
+// The names form takes its map from the consumed scan, as kind 11's does.
+struct PlanRegionBases {
+  exon::RegionBases set;
+  int32_t* d_map = nullptr;
+  int32_t n_map = 0;
+  int32_t* d_poff = nullptr;
+  int64_t* d_points = nullptr;
+  ~PlanRegionBases() {
+    if (d_map) hipFree(d_map);
+    if (d_poff) hipFree(d_poff);
+    if (d_points) hipFree(d_points);
+  }
+  exon::RegionBasesTables tables(const int32_t* map, int32_t n) const { return exon::RegionBasesTables{map, n, d_poff, d_points, set.P, set.C}; }
+};
+
 }  // namespace
 
 struct exon_hip_plan {
@@ -111,6 +128,10 @@ struct exon_hip_plan {
   int n_cols;
   ColSpec cols[4];
   std::unique_ptr<PlanRegionSet> rs;  // REGION_SET_OVERLAP only
+  std::unique_ptr<PlanRegionBases> rb;  // REGION_SET_BASES only
+  // a region-set plan (kind 11 or 12) made from contig names: its ids come from the scan being consumed
+  bool set_by_name() const { return (rs && rs->set.by_name) || (rb && rb->set.by_name); }
+  const std::vector<std::string>* set_names() const { return rs && rs->set.by_name ? &rs->set.contig_names : rb && rb->set.by_name ? &rb->set.contig_names : nullptr; }
 };
 
 struct exon_hip_stream {
@@ -147,12 +168,63 @@ struct exon_hip_stream {
   std::string region_contig;
   bool has_region_contig = false;
   int32_t region_id_override = INT32_MIN;
-  // region-set plans (kind 11) in the names form: the scan being consumed has resolved the set's names in its own dictionary;
+  // region-set plans (kinds 11 and 12) in the names form: the scan being consumed has resolved the set's names in its own dictionary;
   // d_map / map_cap hold its id -> contig slot map (the re-keying map's buffer: such a plan is not keyed)
   bool rs_in_scan = false;
   int32_t rs_n_map = 0;
 };
 enum { KEYS_NONE = 0, KEYS_LOCAL = 1, KEYS_AGREED = 2 };
+
+// the arguments of a region-set constructor (kinds 11 and 12 take the same ones, by the same rules) -> the set's regions in caller
+// order, their contig slots in order of first appearance, and the largest reference id of the ids form
+template <typename Set>
+static int fill_region_set(exon_hip_ctx* ctx, const char* who, const char* packed_contig_names, size_t packed_bytes, const int32_t* ref_ids, const int64_t* starts,
+                           const int64_t* ends, int32_t n_regions, Set& set, int32_t* max_id) {
+  *max_id = -1;
+  set.M = n_regions;
+  set.by_name = packed_contig_names != nullptr;
+  set.starts.assign(starts, starts + n_regions);
+  set.ends.assign(ends, ends + n_regions);
+  set.slot.resize((size_t)n_regions);
+  for (int32_t i = 0; i < n_regions; ++i)
+    if (starts[i] < 1 || ends[i] < starts[i])
+      return fail(ctx, EXON_HIP_EINVAL, "%s: region %d: the interval must satisfy 1 <= start <= end", who, i);
+  if (set.by_name) {
+    std::unordered_map<std::string, int32_t> index;
+    size_t at = 0;
+    for (int32_t i = 0; i < n_regions; ++i) {
+      const void* z = at < packed_bytes ? memchr(packed_contig_names + at, 0, packed_bytes - at) : nullptr;
+      if (!z) return fail(ctx, EXON_HIP_EINVAL, "%s: packed_contig_names holds fewer than %d '\\0'-terminated names", who, n_regions);
+      std::string name(packed_contig_names + at, static_cast<const char*>(z));
+      if (name.empty()) return fail(ctx, EXON_HIP_EINVAL, "%s: region %d: empty contig name", who, i);
+      at += name.size() + 1;
+      auto it = index.find(name);
+      if (it == index.end()) {
+        it = index.emplace(name, (int32_t)set.contig_names.size()).first;
+        set.contig_names.push_back(name);
+      }
+      set.slot[(size_t)i] = it->second;
+    }
+    set.C = (int32_t)set.contig_names.size();
+  } else {
+    std::unordered_map<int32_t, int32_t> index;
+    for (int32_t i = 0; i < n_regions; ++i) {
+      if (ref_ids[i] < 0) return fail(ctx, EXON_HIP_EINVAL, "%s: region %d: negative reference id %d", who, i, ref_ids[i]);
+      if (ref_ids[i] >= EXON_HIP_MAX_REFERENCES)
+        return fail(ctx, EXON_HIP_EUNSUPPORTED, "%s: region %d: reference id %d beyond %d (the id -> contig map is a dense table)", who, i, ref_ids[i], EXON_HIP_MAX_REFERENCES - 1);
+      auto it = index.find(ref_ids[i]);
+      if (it == index.end()) {
+        it = index.emplace(ref_ids[i], (int32_t)set.contig_ids.size()).first;
+        set.contig_ids.push_back(ref_ids[i]);
+      }
+      set.slot[(size_t)i] = it->second;
+      *max_id = std::max(*max_id, ref_ids[i]);
+    }
+    set.C = (int32_t)set.contig_ids.size();
+  }
+  return EXON_HIP_OK;
+}
+
 constexpr size_t COLL_SCRATCH = 8192;  // device words for the collectives' votes (up to 511 ranks x 16 bytes), allocated with the state
 constexpr int64_t HOLD_MAX_ROWS = 1 << 17;  // batches up to this many rows are held until their slot is flushed
 
@@ -412,6 +484,12 @@ static int run_plan(const exon_hip_plan* p, void* stream, const exon_hip_column*
                                           "or create the plan from reference ids");
       return exon_op_region_set_overlap(ctx, stream, &cols[0], &cols[1], &cols[2], n, p->rs->set.by_name ? p->rs->tables(rs_map, rs_n_map) : p->rs->tables(p->rs->d_map, p->rs->n_map),
                                         counts, flags);
+    case EXON_HIP_PLAN_REGION_SET_BASES:
+      if (p->rb->set.by_name && !rs_map)
+        return fail(ctx, EXON_HIP_ESTATE, "a region-set plan made from contig NAMES has no ids to compare the rows' with: feed it files (exon_hip_stream_consume_scan), "
+                                          "or create the plan from reference ids");
+      return exon_op_region_set_bases(ctx, stream, &cols[0], &cols[1], &cols[2], n, p->rb->set.by_name ? p->rb->tables(rs_map, rs_n_map) : p->rb->tables(p->rb->d_map, p->rb->n_map),
+                                      counts, flags);
   }
   return fail(ctx, EXON_HIP_EINVAL, "unknown plan kind %d", d.kind);
 }
@@ -561,6 +639,8 @@ int exon_hip_plan_create(exon_hip_ctx* ctx, const exon_hip_plan_desc* desc, exon
   if (out) *out = nullptr;
   if (desc && desc->kind == EXON_HIP_PLAN_REGION_SET_OVERLAP)
     return fail(ctx, EXON_HIP_EINVAL, "plan kind %d takes a region set, which exon_hip_plan_desc cannot hold: use exon_hip_plan_create_region_set", desc->kind);
+  if (desc && desc->kind == EXON_HIP_PLAN_REGION_SET_BASES)
+    return fail(ctx, EXON_HIP_EINVAL, "plan kind %d takes a region set, which exon_hip_plan_desc cannot hold: use exon_hip_plan_create_region_set_bases", desc->kind);
   if (!ctx || !desc || !out) return fail(ctx, EXON_HIP_EINVAL, "exon_hip_plan_create: NULL argument");
   exon_hip_plan* p = new (std::nothrow) exon_hip_plan();
   if (!p) return fail(ctx, EXON_HIP_ENOMEM, "out of host memory");
@@ -699,49 +779,9 @@ int exon_hip_plan_create_region_set(exon_hip_ctx* ctx, const int32_t columns[3],
     return fail(ctx, EXON_HIP_ENOMEM, "out of host memory");
   }
   std::unique_ptr<exon_hip_plan> guard(p);
-  exon::RegionSet& set = rs->set;
-  set.M = n_regions;
-  set.by_name = packed_contig_names != nullptr;
-  set.starts.assign(starts, starts + n_regions);
-  set.ends.assign(ends, ends + n_regions);
-  set.slot.resize((size_t)n_regions);
-  for (int32_t i = 0; i < n_regions; ++i)
-    if (starts[i] < 1 || ends[i] < starts[i])
-      return fail(ctx, EXON_HIP_EINVAL, "%s: region %d: the interval must satisfy 1 <= start <= end", who, i);
   int32_t max_id = -1;
-  if (set.by_name) {
-    std::unordered_map<std::string, int32_t> index;
-    size_t at = 0;
-    for (int32_t i = 0; i < n_regions; ++i) {
-      const void* z = at < packed_bytes ? memchr(packed_contig_names + at, 0, packed_bytes - at) : nullptr;
-      if (!z) return fail(ctx, EXON_HIP_EINVAL, "%s: packed_contig_names holds fewer than %d '\\0'-terminated names", who, n_regions);
-      std::string name(packed_contig_names + at, static_cast<const char*>(z));
-      if (name.empty()) return fail(ctx, EXON_HIP_EINVAL, "%s: region %d: empty contig name", who, i);
-      at += name.size() + 1;
-      auto it = index.find(name);
-      if (it == index.end()) {
-        it = index.emplace(name, (int32_t)set.contig_names.size()).first;
-        set.contig_names.push_back(name);
-      }
-      set.slot[(size_t)i] = it->second;
-    }
-    set.C = (int32_t)set.contig_names.size();
-  } else {
-    std::unordered_map<int32_t, int32_t> index;
-    for (int32_t i = 0; i < n_regions; ++i) {
-      if (ref_ids[i] < 0) return fail(ctx, EXON_HIP_EINVAL, "%s: region %d: negative reference id %d", who, i, ref_ids[i]);
-      if (ref_ids[i] >= EXON_HIP_MAX_REFERENCES)
-        return fail(ctx, EXON_HIP_EUNSUPPORTED, "%s: region %d: reference id %d beyond %d (the id -> contig map is a dense table)", who, i, ref_ids[i], EXON_HIP_MAX_REFERENCES - 1);
-      auto it = index.find(ref_ids[i]);
-      if (it == index.end()) {
-        it = index.emplace(ref_ids[i], (int32_t)set.contig_ids.size()).first;
-        set.contig_ids.push_back(ref_ids[i]);
-      }
-      set.slot[(size_t)i] = it->second;
-      max_id = std::max(max_id, ref_ids[i]);
-    }
-    set.C = (int32_t)set.contig_ids.size();
-  }
+  if (const int rc = fill_region_set(ctx, who, packed_contig_names, packed_bytes, ref_ids, starts, ends, n_regions, rs->set, &max_id)) return rc;
+  exon::RegionSet& set = rs->set;
   set.build();
   p->ctx = ctx;
   memset(&p->d, 0, sizeof p->d);
@@ -817,6 +857,99 @@ int exon_hip_region_set_overlap(exon_hip_ctx* ctx, void* stream, const exon_hip_
   return exon_op_region_set_overlap(ctx, stream, ref_id, start, end, n, rs->tables(rs->d_map, rs->n_map), d_state, EXON_HIP_LAUNCH_ACCUMULATE);
 }
 
+// plan kind 12: kind 11's arguments and rules.  ctx may be NULL: a host-only plan for exon_hip_region_bases_layout / _decode.
+int exon_hip_plan_create_region_set_bases(exon_hip_ctx* ctx, const int32_t columns[3], const char* packed_contig_names, size_t packed_bytes, const int32_t* ref_ids,
+                                          const int64_t* starts, const int64_t* ends, int32_t n_regions, exon_hip_plan** out) {
+  static const char* who = "exon_hip_plan_create_region_set_bases";
+  if (!out) return fail(ctx, EXON_HIP_EINVAL, "%s: NULL argument", who);
+  *out = nullptr;
+  if (n_regions < 1) return fail(ctx, EXON_HIP_EINVAL, "%s: n_regions %d: a region set holds at least one region", who, n_regions);
+  if (n_regions > exon::REGION_SET_MAX_REGIONS) return fail(ctx, EXON_HIP_EUNSUPPORTED, "%s: n_regions %d beyond %d", who, n_regions, exon::REGION_SET_MAX_REGIONS);
+  if (!columns || !starts || !ends || (!packed_contig_names && !ref_ids)) return fail(ctx, EXON_HIP_EINVAL, "%s: NULL argument", who);
+  for (int c = 0; c < 3; ++c)
+    if (columns[c] < 0) return fail(ctx, EXON_HIP_EINVAL, "negative column index");
+  std::unique_ptr<PlanRegionBases> rb(new (std::nothrow) PlanRegionBases());
+  exon_hip_plan* p = new (std::nothrow) exon_hip_plan();
+  if (!rb || !p) {
+    delete p;
+    return fail(ctx, EXON_HIP_ENOMEM, "out of host memory");
+  }
+  std::unique_ptr<exon_hip_plan> guard(p);
+  int32_t max_id = -1;
+  if (const int rc = fill_region_set(ctx, who, packed_contig_names, packed_bytes, ref_ids, starts, ends, n_regions, rb->set, &max_id)) return rc;
+  exon::RegionBases& set = rb->set;
+  set.build();
+  p->ctx = ctx;
+  memset(&p->d, 0, sizeof p->d);
+  p->d.kind = EXON_HIP_PLAN_REGION_SET_BASES;
+  for (int c = 0; c < 3; ++c) p->d.columns[c] = columns[c];
+  p->n_cols = 3;
+  p->cols[0].elem = 4;
+  p->cols[1].elem = p->cols[2].elem = 8;
+  p->n_i64 = set.words();
+  p->n_f64 = 0;
+  if (ctx) {  // the device tables
+    hipSetDevice(ctx->device);
+    std::vector<int32_t> map;
+    if (!set.by_name) {
+      map.assign((size_t)max_id + 1, -1);
+      for (int32_t c = 0; c < set.C; ++c) map[(size_t)set.contig_ids[(size_t)c]] = c;
+      rb->n_map = (int32_t)map.size();
+    }
+    hipError_t e;
+    if ((!set.by_name && (e = hipMalloc((void**)&rb->d_map, map.size() * 4)) != hipSuccess) || (e = hipMalloc((void**)&rb->d_poff, set.poff.size() * 4)) != hipSuccess ||
+        (e = hipMalloc((void**)&rb->d_points, set.points.size() * 8)) != hipSuccess)
+      return fail(ctx, EXON_HIP_ENOMEM, "%s: device tables: %s", who, hipGetErrorString(e));
+    if ((!set.by_name && (e = hipMemcpy(rb->d_map, map.data(), map.size() * 4, hipMemcpyHostToDevice)) != hipSuccess) ||
+        (e = hipMemcpy(rb->d_poff, set.poff.data(), set.poff.size() * 4, hipMemcpyHostToDevice)) != hipSuccess ||
+        (e = hipMemcpy(rb->d_points, set.points.data(), set.points.size() * 8, hipMemcpyHostToDevice)) != hipSuccess)
+      return fail(ctx, EXON_HIP_EDEVICE, "%s: device tables: %s", who, hipGetErrorString(e));
+  }
+  p->rb = std::move(rb);
+  *out = guard.release();
+  return EXON_HIP_OK;
+}
+
+static const PlanRegionBases* region_bases_of(const exon_hip_plan* plan, const char* who) {
+  if (!plan || plan->d.kind != EXON_HIP_PLAN_REGION_SET_BASES || !plan->rb) {
+    fail(plan ? plan->ctx : nullptr, EXON_HIP_EINVAL, "%s: not a region-set bases plan (kind %d)", who, EXON_HIP_PLAN_REGION_SET_BASES);
+    return nullptr;
+  }
+  return plan->rb.get();
+}
+
+// host only: word offsets of totals, Ns, Ss, Ne, Se and the state's size
+int exon_hip_region_bases_layout(const exon_hip_plan* plan, int64_t* out /*[6]*/) {
+  const PlanRegionBases* rb = region_bases_of(plan, "exon_hip_region_bases_layout");
+  if (!rb) return EXON_HIP_EINVAL;
+  if (!out) return fail(plan->ctx, EXON_HIP_EINVAL, "exon_hip_region_bases_layout: out is NULL");
+  out[0] = 0;
+  for (int k = 0; k < 4; ++k) out[1 + k] = 4 + k * rb->set.bins();
+  out[5] = rb->set.words();
+  return EXON_HIP_OK;
+}
+
+// host only: state words -> the covered bases of every region, in the caller's order; linear in the state, modulo 2^64
+int exon_hip_region_bases_decode(const exon_hip_plan* plan, const int64_t* state, int64_t* out_bases /*[M]*/) {
+  const PlanRegionBases* rb = region_bases_of(plan, "exon_hip_region_bases_decode");
+  if (!rb) return EXON_HIP_EINVAL;
+  if (!state || !out_bases) return fail(plan->ctx, EXON_HIP_EINVAL, "exon_hip_region_bases_decode: NULL argument");
+  rb->set.decode(state, out_bases);
+  return EXON_HIP_OK;
+}
+
+// K12, bare operator: accumulates into d_state (the plan's state words, zeroed once per query by the caller)
+int exon_hip_region_set_bases(exon_hip_ctx* ctx, void* stream, const exon_hip_column* ref_id, const exon_hip_column* start, const exon_hip_column* end, int64_t n,
+                              const exon_hip_plan* plan, int64_t* d_state) {
+  const PlanRegionBases* rb = region_bases_of(plan, "exon_hip_region_set_bases");
+  if (!rb) return EXON_HIP_EINVAL;
+  if (!ctx || ctx != plan->ctx) return fail(ctx, EXON_HIP_EINVAL, "exon_hip_region_set_bases: the plan's tables live on the context it was created with");
+  if (rb->set.by_name)
+    return fail(ctx, EXON_HIP_ESTATE, "a region-set plan made from contig NAMES has no ids to compare the rows' with: feed it files (exon_hip_stream_consume_scan), "
+                                      "or create the plan from reference ids");
+  return exon_op_region_set_bases(ctx, stream, ref_id, start, end, n, rb->tables(rb->d_map, rb->n_map), d_state, EXON_HIP_LAUNCH_ACCUMULATE);
+}
+
 int exon_hip_plan_state_size(const exon_hip_plan* plan, int64_t* n_i64, int64_t* n_f64) {
   if (!plan || !n_i64 || !n_f64) return fail(nullptr, EXON_HIP_EINVAL, "exon_hip_plan_state_size: NULL argument");
   *n_i64 = plan->n_i64;
@@ -887,7 +1020,7 @@ int exon_hip_stream_push(exon_hip_stream* st, struct ArrowArray* batch) {
     return fail(st->ctx, EXON_HIP_ESTATE, "push after finish/close");
   }
   exon_hip_plan* p = st->plan;
-  if (p->rs && p->rs->set.by_name && !st->rs_in_scan) {
+  if (p->set_by_name() && !st->rs_in_scan) {
     batch->release(batch);
     return fail(st->ctx, EXON_HIP_ESTATE, "a region-set plan made from contig NAMES has no ids to compare a pushed batch's with: feed it files "
                                           "(exon_hip_stream_consume_scan), or create the plan from reference ids");
@@ -1140,7 +1273,7 @@ int exon_hip_stream_push_device(exon_hip_stream* st, const struct ArrowDeviceArr
   if (dbatch->device_id != st->ctx->device)
     return fail(st->ctx, EXON_HIP_EINVAL, "batch lives on device %lld, stream on %d", (long long)dbatch->device_id, st->ctx->device);
   exon_hip_plan* p = st->plan;
-  if (p->rs && p->rs->set.by_name && !st->rs_in_scan)
+  if (p->set_by_name() && !st->rs_in_scan)
     return fail(st->ctx, EXON_HIP_ESTATE, "a region-set plan made from contig NAMES has no ids to compare a pushed batch's with: feed it files "
                                           "(exon_hip_stream_consume_scan), or create the plan from reference ids");
   const struct ArrowArray* batch = &dbatch->array;
@@ -1316,9 +1449,9 @@ int exon_hip_stream_set_region_id(exon_hip_stream* st, int32_t id) {
   st->region_id_override = id;
   return EXON_HIP_OK;
 }
-// region-set plans (kind 11) in the names form: the set's distinct contig names, in slot order (nullptr: another plan, or ids form)
+// region-set plans (kinds 11 and 12) in the names form: the set's distinct contig names, in slot order (nullptr: another plan, or ids form)
 const std::vector<std::string>* exon_hip_stream_region_set_names(exon_hip_stream* st) {
-  return st->plan->rs && st->plan->rs->set.by_name ? &st->plan->rs->set.contig_names : nullptr;
+  return st->plan->set_names();
 }
 // map[id of the scan's dictionary] = contig slot or -1, for the scan about to be consumed.  Rows staged by the previous file were
 // decoded under ITS ids: they are launched first.  Synchronises the stream (the map is staged from pageable memory).
@@ -2176,6 +2309,25 @@ int exon_hip_stream_finish_arrow(exon_hip_stream* st, struct ArrowArray* out, st
       make_struct(out, (int64_t)set.M, {contig, prim(set.starts), prim(set.ends), prim(cnt)});
       make_schema(out_schema, "+s", "", false,
                   {field(set.by_name ? "u" : "i", "contig", false), field("l", "start", false), field("l", "end", false), field("l", "count", false)});
+      break;
+    }
+    case EXON_HIP_PLAN_REGION_SET_BASES: {  // one row per region, in the caller's order
+      const exon::RegionBases& set = p->rb->set;
+      std::vector<int64_t> bases((size_t)set.M);
+      set.decode(counts.data(), bases.data());
+      struct ArrowArray* contig;
+      if (set.by_name) {
+        std::vector<std::string> names((size_t)set.M);
+        for (int32_t i = 0; i < set.M; ++i) names[(size_t)i] = set.contig_names[(size_t)set.slot[(size_t)i]];
+        contig = exon::utf8_array(names);
+      } else {
+        std::vector<int32_t> ids((size_t)set.M);
+        for (int32_t i = 0; i < set.M; ++i) ids[(size_t)i] = set.contig_ids[(size_t)set.slot[(size_t)i]];
+        contig = prim(ids);
+      }
+      make_struct(out, (int64_t)set.M, {contig, prim(set.starts), prim(set.ends), prim(bases)});
+      make_schema(out_schema, "+s", "", false,
+                  {field(set.by_name ? "u" : "i", "contig", false), field("l", "start", false), field("l", "end", false), field("l", "bases", false)});
       break;
     }
     default:

@@ -366,6 +366,31 @@ class Context:
         self._check(self.lib.exon_hip_region_set_overlap(self.h, stream, C.byref(c0), C.byref(c1), C.byref(c2), n, plan.h,
                                                          d_state.ptr if isinstance(d_state, DeviceBuffer) else d_state))
 
+    def plan_region_set_bases(self, regions, columns=(2, 3, 4)):
+        """The bases of the rows that fall inside every region of a set, in one pass over the rows (plan kind 12): for region i the
+        sum over the counted rows [s, e] of max(0, min(e, end_i) - max(s, start_i) + 1).  `regions` as plan_region_set_overlap's.
+        State: 4 + 4 * (P + C) int64 words, all of which add modulo 2^64; RegionBasesPlan.decode turns them into one sum per region,
+        finish_arrow into a table."""
+        return RegionBasesPlan(self, regions, columns)
+
+    def region_set_bases(self, ref_id, ref_valid, start, start_valid, end, end_valid, n, plan, d_state, stream=None):
+        """K12 (bare operator, ids form): accumulates the batch into `d_state` (plan.n_i64 int64 words)."""
+        c0, c1, c2 = _col(ref_id, ref_valid, None, n), _col(start, start_valid, None, n), _col(end, end_valid, None, n)
+        self._check(self.lib.exon_hip_region_set_bases(self.h, stream, C.byref(c0), C.byref(c1), C.byref(c2), n, plan.h,
+                                                       d_state.ptr if isinstance(d_state, DeviceBuffer) else d_state))
+
+
+def region_bases_layout(plan):
+    """exon_hip_region_bases_layout (host-only): word offsets of the totals / Ns / Ss / Ne / Se sections of a kind-12 plan's state,
+    and its size in words."""
+    return plan.layout()
+
+
+def region_bases_decode(plan, state):
+    """exon_hip_region_bases_decode (host-only): the state's words -> the covered bases of every region, in the order the regions
+    were given.  Linear modulo 2^64: the decoded states of partitions add up to the decoded merged state."""
+    return plan.decode(state)
+
 
 def region_set_layout(plan):
     """exon_hip_region_set_layout (host-only): word offsets of the totals / A / B sections of a region-set plan's state, and its
@@ -1247,6 +1272,8 @@ class RegionSetPlan(Plan):
     """Plan kind 11 (exon_hip_plan_create_region_set).  ctx None: a host-only plan that serves layout() and decode() and cannot be
     launched."""
 
+    _CREATE, _LAYOUT, _LAYOUT_WORDS, _DECODE = "exon_hip_plan_create_region_set", "exon_hip_region_set_layout", 4, "exon_hip_region_set_decode"
+
     def __init__(self, ctx, regions, columns=(2, 3, 4)):
         self.ctx = ctx
         self.lib = ctx.lib if ctx is not None else L.load()
@@ -1267,9 +1294,9 @@ class RegionSetPlan(Plan):
         else:
             ids = np.array([r[0] for r in regions], np.int32)
         h = C.c_void_p()
-        self._check(self.lib.exon_hip_plan_create_region_set(ctx.h if ctx is not None else None, cols, packed, len(packed) if packed else 0,
-                                                             ids.ctypes.data if ids is not None and m else None,
-                                                             starts.ctypes.data if m else None, ends.ctypes.data if m else None, m, C.byref(h)))
+        self._check(getattr(self.lib, self._CREATE)(ctx.h if ctx is not None else None, cols, packed, len(packed) if packed else 0,
+                                                    ids.ctypes.data if ids is not None and m else None,
+                                                    starts.ctypes.data if m else None, ends.ctypes.data if m else None, m, C.byref(h)))
         self.h = h
         a, b = C.c_int64(), C.c_int64()
         self._check(self.lib.exon_hip_plan_state_size(h, C.byref(a), C.byref(b)))
@@ -1281,8 +1308,8 @@ class RegionSetPlan(Plan):
         return rc
 
     def layout(self):
-        out = (C.c_int64 * 4)()
-        self._check(self.lib.exon_hip_region_set_layout(self.h, out))
+        out = (C.c_int64 * self._LAYOUT_WORDS)()
+        self._check(getattr(self.lib, self._LAYOUT)(self.h, out))
         return tuple(out)
 
     def decode(self, state):
@@ -1290,13 +1317,20 @@ class RegionSetPlan(Plan):
         if state.size != self.n_i64:
             raise ValueError("the state of this plan has %d words, %d given" % (self.n_i64, state.size))
         out = np.zeros(len(self.regions), np.int64)
-        self._check(self.lib.exon_hip_region_set_decode(self.h, state.ctypes.data, out.ctypes.data))
+        self._check(getattr(self.lib, self._DECODE)(self.h, state.ctypes.data, out.ctypes.data))
         return out
 
     def close(self):
         if self.h:
             self.lib.exon_hip_plan_destroy(self.h)
             self.h = None
+
+
+class RegionBasesPlan(RegionSetPlan):
+    """Plan kind 12 (exon_hip_plan_create_region_set_bases): RegionSetPlan's arguments; layout() gives the word offsets of the
+    totals / Ns / Ss / Ne / Se sections and the word count, decode() the covered bases of every region."""
+
+    _CREATE, _LAYOUT, _LAYOUT_WORDS, _DECODE = "exon_hip_plan_create_region_set_bases", "exon_hip_region_bases_layout", 6, "exon_hip_region_bases_decode"
 
 
 class Stream:

@@ -407,6 +407,54 @@ int exon_hip_region_set_decode(const exon_hip_plan* plan, const int64_t* state, 
 int exon_hip_region_set_overlap(exon_hip_ctx* ctx, void* stream, const exon_hip_column* ref_id /*i32*/, const exon_hip_column* start /*i64*/,
                                 const exon_hip_column* end /*i64*/, int64_t n, const exon_hip_plan* plan, int64_t* d_state);
 
+/* ---- K12: covered bases per region of a set in one pass (plan kind 12) ------------------------------------------------------------
+ * The depth question over K11's inputs -- the sum `samtools bedcov` / `bedtools coverage` print; mean depth is that sum divided by
+ * the region's length.  Rows and regions are 1-based inclusive.  A row [s, e] with s <= e on a region's contig, all three values
+ * valid, covers  max(0, min(e, re_i) - max(s, rs_i) + 1)  bases of the region [rs_i, re_i]; bases_i is the sum over such rows.
+ * Every row is visited once, whatever M is.  Per contig the POINTS are the sorted unique values { rs_i - 1 } U { re_i }: k_c points
+ * x_0 < ... < x_{k_c - 1}.  A counted row finds p = the index of the first point >= s and q = the index of the first point >= e (the
+ * same lower bound in the same table, both in [0, k_c]) and adds 1 to Ns[p], s to Ss[p], 1 to Ne[q], e to Se[q].  With inclusive
+ * prefix sums cNs, cSs, cNe, cSe over the contig's bins
+ *     G(x_r)  = (x_r + 1) * cNs[r] - cSs[r] - x_r * cNe[r] + cSe[r]      bases of the contig's rows at positions <= x_r
+ *     bases_i = G(re_i) - G(rs_i - 1)                                    
+ * ARITHMETIC IS MODULO 2^64: the four sections and the decode use unsigned 64-bit arithmetic that wraps.  Every step is a ring
+ * operation, so bases_i is exact whenever its true value fits an int64 -- also for re_i = EXON_HIP_REGION_OPEN_END, where x + 1
+ * wraps, and for coordinate sums beyond 2^63.  A single word of Ss / Se is therefore meaningful only modulo 2^64.
+ *
+ * What it does not compute: the alignment span [start, end] counts as covered, deletions and reference skips included, as the `end`
+ * column defines it -- there is no CIGAR-aware split; there is no per-base depth, only the sum per region; a BED source is not
+ * served.
+ *
+ * exon_hip_plan_create_region_set_bases takes exon_hip_plan_create_region_set's arguments under the same rules and error classes
+ * (ids form or names form, 1 <= start <= end with an open end allowed, at most 1048576 regions, ctx may be NULL for a host-only
+ * plan; exon_hip_plan_create with kind 12 is EXON_HIP_EINVAL and names the constructor).  A names-form plan is resolved per consumed
+ * scan exactly as kind 11's and refuses pushes, device pushes, plan launches and the bare operator with EXON_HIP_ESTATE.  Duplicate,
+ * nested and overlapping regions are legal, each has its own sum.  Kind 11's helpers refuse a kind-12 plan and these refuse kind 11's.
+ *
+ * State: 4 + 4 * (P + C) int64 words, n_f64 = 0; P = sum of k_c, C = distinct contigs of the set.  Every word adds (modulo 2^64), so
+ * streams, chunked launches, exon_hip_plan_fold_states, exon_hip_stream_all_reduce and the file pipelines carry it like K11's.
+ *   totals[4]  counted, null_rows, elsewhere, inverted: exactly kind 11's
+ *   Ns[P + C], Ss[P + C], Ne[P + C], Se[P + C]  contig c (in order of first appearance in the set) owns k_c + 1 consecutive bins
+ *              of each section, starting at (points of the contigs in front of it) + c
+ * DECISION (kind 11's): a row with end < start adds to `inverted` and to NO region.
+ *
+ * Sets with P + C <= 4096 are searched and summed in LDS; larger ones search through L2 and add with global atomics.  The columns'
+ * values need their element's alignment only (4 / 8 / 8 bytes).  finish_arrow: contig, start, end, bases (Int64), one row per region
+ * in the caller's order. */
+#define EXON_HIP_PLAN_REGION_SET_BASES 12
+int exon_hip_plan_create_region_set_bases(exon_hip_ctx* ctx, const int32_t* columns /*[3]*/,
+                                          const char* packed_contig_names /* n_regions '\0'-terminated names, or NULL */, size_t packed_bytes,
+                                          const int32_t* ref_ids /* used when names are NULL */, const int64_t* starts, const int64_t* ends,
+                                          int32_t n_regions, exon_hip_plan** out);
+/* host only: out = word offsets of totals, Ns, Ss, Ne, Se, and the word count */
+int exon_hip_region_bases_layout(const exon_hip_plan* plan, int64_t* out /*[6]*/);
+/* host only: the state's words -> the covered bases of every region, in the caller's region order.  Linear modulo 2^64: decoded
+ * partial states add up to the decoded merged state. */
+int exon_hip_region_bases_decode(const exon_hip_plan* plan, const int64_t* state, int64_t* out_bases /*[M]*/);
+/* K12, bare operator (ids form; `ctx` is the plan's): d_state (exon_hip_plan_state_size words) += this batch */
+int exon_hip_region_set_bases(exon_hip_ctx* ctx, void* stream, const exon_hip_column* ref_id /*i32*/, const exon_hip_column* start /*i64*/,
+                              const exon_hip_column* end /*i64*/, int64_t n, const exon_hip_plan* plan, int64_t* d_state);
+
 /* Stateless form of a push: run the plan's fused kernel over HBM-resident columns (`columns[i]` = operator argument i, see
  * exon_hip_plan_desc.columns for the order; n_columns must match the plan) on the caller's hipStream_t into a caller-owned
  * packed partial state [n_i64 x int64][n_f64 x float64] (exon_hip_plan_state_size; 8-byte aligned device memory).

@@ -34,6 +34,7 @@ pub const EXON_HIP_PLAN_READ_STATS_HIST: i32 = 9; // lmax, columns (sequence, qu
 pub const EXON_HIP_PLAN_SEQ_STATS_HIST: i32 = 10; // lmax, column (sequence); state = exon_hip_seq_stats_layout words, all add
 pub const EXON_HIP_PLAN_REGION_SET_OVERLAP: i32 = 11; // made by exon_hip_plan_create_region_set; state = 4 + 2 * (M + C) words, all add
 pub const EXON_HIP_REGION_SET_MAX_REGIONS: i32 = 1048576;
+pub const EXON_HIP_PLAN_REGION_SET_BASES: i32 = 12; // made by exon_hip_plan_create_region_set_bases; state = 4 + 4 * (P + C) words, all add modulo 2^64
 pub const EXON_HIP_GT: i32 = 0;
 pub const EXON_HIP_GE: i32 = 1;
 pub const EXON_HIP_LT: i32 = 2;
@@ -159,6 +160,14 @@ extern "C" {
     pub fn exon_hip_region_set_decode(plan: *const exon_hip_plan, state: *const i64, out_counts: *mut i64) -> c_int;
     /// K11 (bare operator, ids form): overlap counts of every region of the plan's set over one batch; accumulates
     pub fn exon_hip_region_set_overlap(ctx: *mut exon_hip_ctx, stream: *mut c_void, ref_id: *const exon_hip_column, start: *const exon_hip_column, end: *const exon_hip_column, n: i64, plan: *const exon_hip_plan, d_state: *mut i64) -> c_int;
+    /// K12: the plan of the covered bases of every region of a set; exon_hip_plan_create_region_set's arguments and rules
+    pub fn exon_hip_plan_create_region_set_bases(ctx: *mut exon_hip_ctx, columns: *const i32, packed_contig_names: *const c_char, packed_bytes: usize, ref_ids: *const i32, starts: *const i64, ends: *const i64, n_regions: i32, out: *mut *mut exon_hip_plan) -> c_int;
+    /// host-only: word offsets of K12's totals / Ns / Ss / Ne / Se sections and the state's size (out[6])
+    pub fn exon_hip_region_bases_layout(plan: *const exon_hip_plan, out: *mut i64) -> c_int;
+    /// host-only: K12's state words -> the covered bases of every region, in the caller's order; linear in the state modulo 2^64
+    pub fn exon_hip_region_bases_decode(plan: *const exon_hip_plan, state: *const i64, out_bases: *mut i64) -> c_int;
+    /// K12 (bare operator, ids form): covered bases of every region of the plan's set over one batch; accumulates
+    pub fn exon_hip_region_set_bases(ctx: *mut exon_hip_ctx, stream: *mut c_void, ref_id: *const exon_hip_column, start: *const exon_hip_column, end: *const exon_hip_column, n: i64, plan: *const exon_hip_plan, d_state: *mut i64) -> c_int;
     /// fold of `world` packed states by the plan's own layout (add; unsigned max for K8's extreme planes)
     pub fn exon_hip_plan_fold_states(plan: *const exon_hip_plan, stream: *mut c_void, d_gathered: *const c_void, world: i32, d_out: *mut c_void) -> c_int;
     pub fn exon_hip_stream_open(plan: *mut exon_hip_plan, partition: i32, out: *mut *mut exon_hip_stream) -> c_int;

@@ -1,0 +1,377 @@
+"""GPU: the covered-bases plan (kind 12) against plain numpy (region_bases_expect.py), on all four totals, on every region's sum and on
+sum(Ns) == sum(Ne) == counted: the bare operator, plan launches in both modes, chunks, folds and streams, in both tiers and both launch
+shapes."""
+import numpy as np
+import pytest
+
+import exon_amd
+from exon_amd import _lib as L
+
+import region_bases_expect as E
+
+pytestmark = pytest.mark.gpu
+
+LDS_MAX = exon_amd.REGION_BASES_LDS_MAX
+TILE_S, TILE_B = L.REGION_SET_TILE_SMALL, L.REGION_SET_TILE_BIG
+ESTATE = -5
+
+
+def full(regions):
+    return [(c, s, E.OPEN_END if e is None else e) for c, s, e in regions]
+
+
+class Cols:
+    """three host columns (+ optional validity) on the device; `shift` = elements in front of each column's first row"""
+
+    def __init__(self, ctx, ref, start, end, rv=None, sv=None, ev=None, shift=(0, 0, 0)):
+        self.host = (np.asarray(ref, np.int32), np.asarray(start, np.int64), np.asarray(end, np.int64))
+        self.valid = (rv, sv, ev)
+        self.n = len(self.host[0])
+        self.bufs, self.ptrs = [], []
+        for a, k in zip(self.host, shift):
+            b = ctx.to_device(np.concatenate([np.zeros(k, a.dtype), a, np.zeros(8, a.dtype)]))
+            self.bufs.append(b)
+            self.ptrs.append(b.ptr + k * a.dtype.itemsize)
+        self.vbufs = [None if v is None else ctx.to_device(np.concatenate([E.pack_bits(v), np.zeros(64, np.uint8)])) for v in self.valid]
+
+    def columns(self, lo=0, hi=None):
+        """(values, validity, offsets) triples of rows [lo, hi); lo a multiple of 8"""
+        assert lo % 8 == 0
+        return [(p + lo * a.dtype.itemsize, None if v is None else v.ptr + lo // 8, None) for p, a, v in zip(self.ptrs, self.host, self.vbufs)]
+
+    def expect(self, regions, fast=False):
+        return (E.expect_fast if fast else E.expect)(full(regions), *self.host, *self.valid)
+
+
+def launch(ctx, plan, cols, overwrite=True, d_state=None, lo=0, hi=None):
+    hi = cols.n if hi is None else hi
+    d_state = d_state if d_state is not None else ctx.zeros(np.int64, plan.n_i64)
+    plan.launch(cols.columns(lo), hi - lo, d_state, overwrite=overwrite)
+    ctx.sync()
+    return d_state
+
+
+def check(plan, state, want):
+    totals, bases = want
+    assert state[:4].tolist() == totals.tolist()
+    assert plan.decode(state).tolist() == bases.tolist()
+    at = plan.layout()
+    assert state[at[1]:at[2]].sum() == totals[0] == state[at[3]:at[4]].sum()  # every counted row adds once to Ns and once to Ne
+
+
+def random_rows(rng, n, n_refs=6, span=2000, null=0.05, inverted=0.02):
+    ref = rng.integers(-1, n_refs + 1, n).astype(np.int32)
+    start = rng.integers(1, span, n)
+    end = start + rng.integers(0, 150, n)
+    inv = rng.random(n) < inverted
+    end[inv] = start[inv] - rng.integers(1, 5, int(inv.sum()))
+    return ref, start, end, rng.random(n) >= null, rng.random(n) >= null, rng.random(n) >= null
+
+
+def random_regions(rng, m, contigs, span=2000, width=300):
+    out = []
+    for _ in range(m):
+        s = int(rng.integers(1, span))
+        out.append((int(rng.choice(contigs)), s, s + int(rng.integers(0, width))))
+    return out
+
+
+SEVEN = [(0, 100, 400), (0, 100, 400), (2, 1, None), (2, 500, 500), (1, 300, 1900), (4, 1500, 1600), (0, 350, 360)]
+THREE = [(0, 10, 20), (0, 21, 21), (0, 30, None)]
+
+
+@pytest.mark.parametrize("row,want", [
+    ((5, 9), [0, 0, 0]), ((5, 10), [1, 0, 0]), ((5, 20), [11, 0, 0]), ((5, 21), [11, 1, 0]),  # ending at 9, 10, 20, 21
+    ((20, 25), [1, 1, 0]), ((21, 25), [0, 1, 0]), ((22, 29), [0, 0, 0]),                      # starting at 20, 21, 22
+    ((5, 40), [11, 1, 11]),                                                                   # spanning all three
+    ((12, 15), [4, 0, 0]), ((35, 35), [0, 0, 1]),                                             # inside one
+    ((10, 20), [11, 0, 0]), ((21, 21), [0, 1, 0]),                                            # equal to a region
+    ((2**62, 2**63 - 1), [0, 0, 2**62])])                                                     # the open end, to the last coordinate
+def test_boundaries_one_row(ctx, row, want):
+    plan = ctx.plan_region_set_bases(THREE, columns=(0, 1, 2))
+    cols = Cols(ctx, [0], [row[0]], [row[1]])
+    st = launch(ctx, plan, cols).to_host()
+    assert plan.decode(st).tolist() == want
+    check(plan, st, cols.expect(THREE))
+    assert np.array_equal(st, E.expect_state(full(THREE), *cols.host))
+
+
+def test_single_base_regions_give_the_kind_11_counts(ctx):
+    rng = np.random.default_rng(1)
+    regions = [(int(c), int(x), int(x)) for c, x in zip(rng.integers(0, 6, 300), rng.integers(1, 2100, 300))]
+    cols = Cols(ctx, *random_rows(rng, 5000))
+    bases = ctx.plan_region_set_bases(regions, columns=(0, 1, 2))
+    counts = ctx.plan_region_set_overlap(regions, columns=(0, 1, 2))
+    sb, sc = launch(ctx, bases, cols).to_host(), launch(ctx, counts, cols).to_host()
+    assert sb[:4].tolist() == sc[:4].tolist()
+    assert bases.decode(sb).tolist() == counts.decode(sc).tolist()
+    check(bases, sb, cols.expect(regions))
+    assert bases.decode(sb).max() > 0
+
+
+def test_region_shapes_and_row_classes(ctx):
+    rng = np.random.default_rng(2)
+    regions = [(1, 50, 90)] * 3                                          # identical x 3
+    regions += [(1, 10, 1000), (1, 20, 900), (1, 30, 800), (1, 40, 41)]  # nested
+    regions += [(2, 10, 500), (2, 100, 500), (2, 499, 500)]              # equal ends
+    regions += [(2, 700, 710), (2, 700, 800), (2, 700, None)]            # equal starts
+    regions += [(2, 501, 600), (2, 601, 699)]                            # abutting: [.., 500][501, 600][601, 699][700, ..
+    regions += [(40, 1, 100), (40, 1, None)]                             # a contig no row has
+    ref, start, end, rv, sv, ev = random_rows(rng, 4000, n_refs=4, span=1100)
+    ref[:50] = -1
+    ref[50:100] = 41           # beyond the map (its last id is 40)
+    ref[100:150] = 2**31 - 1
+    ref[150:200] = -2**31
+    ref[200:260] = 3           # inside the map, not in the set
+    cols = Cols(ctx, ref, start, end, rv, sv, ev)
+    plan = ctx.plan_region_set_bases(regions, columns=(0, 1, 2))
+    st = launch(ctx, plan, cols).to_host()
+    want = cols.expect(regions)
+    check(plan, st, want)
+    assert want[0].min() > 0 and want[0].sum() == cols.n  # all four classes occur
+    assert np.array_equal(st, E.expect_state(full(regions), *cols.host, *cols.valid))  # word by word
+    assert want[1].tolist() == E.expect_pileup(full(regions), *cols.host, *cols.valid)[1].tolist()  # (and by per-base depth)
+    got = plan.decode(st)
+    assert got[0] == got[1] == got[2] > 0 and got[-1] == got[-2] == 0
+    # regions 9, 13, 14 and 12 abut and tile [499, inf) of contig 2: their sums add up to one region over the same bases
+    one = ctx.plan_region_set_bases([(2, 499, None)], columns=(0, 1, 2))
+    assert got[[9, 13, 14, 12]].sum() == one.decode(launch(ctx, one, cols).to_host())[0] > 0
+
+
+@pytest.mark.parametrize("which", [0, 1, 2])
+def test_each_column_null_alone(ctx, which):
+    rng = np.random.default_rng(3 + which)
+    ref, start, end, _, _, _ = random_rows(rng, 3000, inverted=0)
+    v = [None, None, None]
+    v[which] = rng.random(3000) < 0.5
+    cols = Cols(ctx, ref, start, end, *v)
+    plan = ctx.plan_region_set_bases(SEVEN, columns=(0, 1, 2))
+    st = launch(ctx, plan, cols).to_host()
+    check(plan, st, cols.expect(SEVEN))
+    assert st[1] == (~v[which]).sum() > 0
+
+
+def test_inverted_rows_add_to_no_region(ctx):
+    regions = [(0, 1, 1000), (0, 40, 60)]
+    cols = Cols(ctx, [0, 0, 0, 0], [70, 50, 61, 30], [30, 50, 39, 70])  # [70, 30] and [61, 39] span region 1's interval backwards
+    plan = ctx.plan_region_set_bases(regions, columns=(0, 1, 2))
+    st = launch(ctx, plan, cols).to_host()
+    assert st[:4].tolist() == [2, 0, 0, 2] and plan.decode(st).tolist() == [1 + 41, 1 + 21]
+    check(plan, st, cols.expect(regions))
+
+
+def test_sums_wrap_modulo_2_64_on_the_device(ctx):
+    """3000 rows near 2^62: every Ss / Se word wraps many times over, the decoded sums are exact"""
+    rng = np.random.default_rng(23)
+    shift = 2**62
+    ref, start, end, rv, sv, ev = random_rows(rng, 3000)
+    cols = Cols(ctx, ref, start + shift, end + shift, rv, sv, ev)
+    regions = [(c, s + shift, None if e is None else e + shift) for c, s, e in SEVEN]
+    plan = ctx.plan_region_set_bases(regions, columns=(0, 1, 2))
+    st = launch(ctx, plan, cols).to_host()
+    check(plan, st, cols.expect(regions))
+    small = E.expect(full(SEVEN), ref, start, end, rv, sv, ev)
+    assert plan.decode(st).tolist() == small[1].tolist() and small[1].min() >= 0 and small[1].sum() > 0
+    assert np.array_equal(st, E.expect_state(full(regions), *cols.host, *cols.valid))
+
+
+@pytest.mark.parametrize("n", [0, 1, 63, 64, 65, TILE_S - 1, TILE_S, TILE_S + 1, 3 * TILE_S + 517])
+def test_row_counts_small_shape(ctx, n):
+    rng = np.random.default_rng(100 + n)
+    cols = Cols(ctx, *random_rows(rng, n))
+    plan = ctx.plan_region_set_bases(SEVEN, columns=(0, 1, 2))
+    d = ctx.to_device(np.full(plan.n_i64, -7, np.int64))  # overwrite: garbage in front, n = 0 included
+    check(plan, launch(ctx, plan, cols, d_state=d).to_host(), cols.expect(SEVEN))
+
+
+@pytest.mark.parametrize("extra", [TILE_B - 1, TILE_B + 1])
+@pytest.mark.parametrize("tier", ["lds", "global"])
+def test_row_counts_big_shape(ctx, extra, tier):
+    """the 1024-thread shape takes over once every CU gets a tile: that many rows and one tile -/+ 1 more"""
+    n = ctx.info()["compute_units"] * TILE_B + extra
+    rng = np.random.default_rng(extra)
+    cols = Cols(ctx, *random_rows(rng, n, null=0.01))
+    regions = SEVEN if tier == "lds" else SEVEN + [(5, 1 + i, 1 + i) for i in range(LDS_MAX)]
+    plan = ctx.plan_region_set_bases(regions, columns=(0, 1, 2))
+    assert (plan.n_i64 - 4) // 4 <= LDS_MAX if tier == "lds" else (plan.n_i64 - 4) // 4 > LDS_MAX
+    check(plan, launch(ctx, plan, cols).to_host(), cols.expect(regions, fast=True))
+
+
+@pytest.mark.parametrize("shift", [(1, 1, 1), (3, 1, 1), (2, 1, 0), (1, 0, 0), (0, 1, 0)])
+def test_unaligned_column_bases(ctx, shift):
+    """(1, 1, 1) and (3, 1, 1) line up behind a head of 3 / 1 rows; the others never do and are read row by row"""
+    rng = np.random.default_rng(sum(shift))
+    cols = Cols(ctx, *random_rows(rng, 2 * TILE_S + 77), shift=shift)
+    plan = ctx.plan_region_set_bases(SEVEN, columns=(0, 1, 2))
+    check(plan, launch(ctx, plan, cols).to_host(), cols.expect(SEVEN))
+    d = ctx.zeros(np.int64, plan.n_i64)
+    c = cols.columns()
+    ctx.region_set_bases(c[0][0], c[0][1], c[1][0], c[1][1], c[2][0], c[2][1], cols.n, plan, d)  # the bare operator takes them too
+    ctx.sync()
+    check(plan, d.to_host(), cols.expect(SEVEN))
+
+
+def edge_sets(total, many):
+    """region sets with P + C == total.  One contig: total - 1 points = total - 2 abutting regions between random boundaries.  Many:
+    total // 3 contigs of one region each (2 points + 1), and the remainder as regions abutting contig 0's (a point each)"""
+    rng = np.random.default_rng(total)
+    if not many:
+        pts = np.sort(rng.choice(np.arange(1, 60_000), total - 1, replace=False)).tolist()
+        return [(0, a + 1, b) for a, b in zip(pts[:-1], pts[1:])]
+    c = total // 3
+    regions = [(i, int(rng.integers(1, 1000)), int(rng.integers(1000, 2000))) for i in range(c)]
+    at = regions[0][2]
+    for _ in range(total - 3 * c):
+        regions.append((0, at + 1, at + 50))
+        at += 50
+    return regions
+
+
+@pytest.mark.parametrize("many", [False, True])
+@pytest.mark.parametrize("total", [LDS_MAX, LDS_MAX + 1])
+def test_tier_edge(ctx, total, many):
+    regions = edge_sets(total, many)
+    plan = ctx.plan_region_set_bases(regions, columns=(0, 1, 2))
+    assert plan.n_i64 == 4 + 4 * total
+    rng = np.random.default_rng(7)
+    n = 30_000
+    ref = rng.integers(0, total // 3 if many else 2, n).astype(np.int32)
+    start = rng.integers(1, 2200 if many else 61_000, n)
+    end = start + rng.integers(0, 300, n)
+    cols = Cols(ctx, ref, start, end, rng.random(n) < 0.97)
+    st = launch(ctx, plan, cols).to_host()
+    check(plan, st, cols.expect(regions, fast=True))
+    sub = slice(0, 400)  # and by brute force on a few rows, in the same plan
+    few = Cols(ctx, ref[sub], start[sub], end[sub])
+    check(plan, launch(ctx, plan, few).to_host(), few.expect(regions))
+
+
+def test_large_tier_100000_regions(ctx):
+    rng = np.random.default_rng(11)
+    regions = random_regions(rng, 100_000, [0, 5, 9], span=3_000_000, width=5000)
+    n = 200_000
+    ref = rng.choice([0, 5, 9, 2], n).astype(np.int32)
+    start = rng.integers(1, 3_000_000, n)
+    end = start + rng.integers(0, 400, n)
+    cols = Cols(ctx, ref, start, end, None, rng.random(n) < 0.99, None)
+    plan = ctx.plan_region_set_bases(regions, columns=(0, 1, 2))
+    check(plan, launch(ctx, plan, cols).to_host(), cols.expect(regions, fast=True))
+
+
+@pytest.mark.parametrize("tier", ["lds", "global"])
+def test_hot_bin_sorted_rows(ctx, tier):
+    """a coordinate-sorted file: a million rows inside ONE region of the set, ascending -- whole waves on one bin, whose values the
+    wave sums before it adds"""
+    m = LDS_MAX // 2 if tier == "lds" else LDS_MAX  # abutting regions: m + 1 points on one contig, P + C = m + 2
+    regions = [(0, 1 + 1000 * i, 1000 * (i + 1)) for i in range(m)]
+    n = 1_000_000
+    rng = np.random.default_rng(5)
+    start = np.sort(rng.integers(1_000_100, 1_000_800, n))  # region 1000 = [1000001, 1001000]
+    end = start + rng.integers(0, 100, n)
+    cols = Cols(ctx, np.zeros(n, np.int32), start, end)
+    plan = ctx.plan_region_set_bases(regions, columns=(0, 1, 2))
+    assert plan.n_i64 == 4 + 4 * (m + 2)
+    st = launch(ctx, plan, cols).to_host()
+    got = plan.decode(st)
+    assert got[1000] == int((end - start + 1).sum()) == got.sum()
+    check(plan, st, cols.expect(regions, fast=True))
+
+
+def test_launch_modes_and_chunks(ctx):
+    rng = np.random.default_rng(13)
+    cols = Cols(ctx, *random_rows(rng, 3 * 4096))
+    plan = ctx.plan_region_set_bases(SEVEN, columns=(0, 1, 2))
+    whole = launch(ctx, plan, cols).to_host()
+    check(plan, whole, cols.expect(SEVEN))
+    d = ctx.zeros(np.int64, plan.n_i64)
+    for k in range(3):  # accumulate over three launches = one launch of the concatenation
+        launch(ctx, plan, cols, overwrite=False, d_state=d, lo=4096 * k, hi=4096 * (k + 1))
+    assert np.array_equal(d.to_host(), whole)
+    d = ctx.to_device(rng.integers(-2**40, 2**40, plan.n_i64))  # overwrite on a state full of garbage
+    assert np.array_equal(launch(ctx, plan, cols, d_state=d).to_host(), whole)
+    d = ctx.to_device(rng.integers(-2**40, 2**40, plan.n_i64))
+    plan.launch_chunks([(cols.columns(0), 4096), (cols.columns(4096), 0), (cols.columns(4096), 8192)], d, overwrite=True)
+    ctx.sync()
+    assert np.array_equal(d.to_host(), whole)
+    plan.launch_chunks([], d, overwrite=True)  # an overwrite of nothing is the empty state
+    ctx.sync()
+    assert not d.to_host().any()
+
+
+def test_fold_states_of_two_ranks(ctx):
+    rng = np.random.default_rng(17)
+    cols = Cols(ctx, *random_rows(rng, 6000))
+    plan = ctx.plan_region_set_bases(SEVEN, columns=(0, 1, 2))
+    a = launch(ctx, plan, cols, lo=0, hi=2400).to_host()
+    b = launch(ctx, plan, cols, lo=2400).to_host()
+    out = ctx.zeros(np.int64, plan.n_i64)
+    plan.fold_states(ctx.to_device(np.concatenate([a, b])), 2, out)
+    ctx.sync()
+    whole = launch(ctx, plan, cols).to_host()
+    assert np.array_equal(out.to_host(), whole)
+    assert np.array_equal(plan.decode(a) + plan.decode(b), plan.decode(whole))
+
+
+def test_streams(ctx):
+    import pyarrow as pa
+    rng = np.random.default_rng(19)
+    plan = ctx.plan_region_set_bases(SEVEN, columns=(1, 2, 3))
+    st = plan.open()
+    ref, start, end, rv, sv, ev = random_rows(rng, 9000)
+
+    def batch(lo, hi, pad):
+        # `pad` rows in front, sliced away: the validity bitmaps start at a bit offset that is not zero
+        sl = slice(max(lo - pad, 0), hi)
+        arrs = [pa.array(ref[sl], mask=~rv[sl]), pa.array(start[sl], mask=~sv[sl]), pa.array(end[sl], mask=~ev[sl])]
+        b = pa.RecordBatch.from_arrays([pa.array(np.zeros(hi - sl.start, np.int8))] + arrs, names=["x", "ref", "start", "end"])
+        return b.slice(lo - sl.start)
+    for lo, hi, pad in [(0, 100, 0), (100, 4099, 3), (4099, 4100, 5), (4100, 9000, 13)]:
+        st.push(batch(lo, hi, pad))
+    want = E.expect(full(SEVEN), ref, start, end, rv, sv, ev)
+    counts, sums = st.finish()
+    assert sums.size == 0
+    check(plan, counts, want)
+    # a new query on the same stream: reset, device batches, the Arrow result
+    st.reset()
+    cols = Cols(ctx, ref[:5000], start[:5000], end[:5000], rv[:5000], sv[:5000], ev[:5000])
+    dummy = ctx.zeros(np.int8, 5000)
+    st.push_device([(dummy, None, None)] + [(b, v, None) for b, v in zip(cols.bufs, cols.vbufs)], 5000)
+    table = st.finish_arrow()
+    want = cols.expect(SEVEN)
+    assert [f.name for f in table.type] == ["contig", "start", "end", "bases"]
+    assert [str(f.type) for f in table.type] == ["int32", "int64", "int64", "int64"]
+    assert table.field("contig").to_pylist() == [r[0] for r in SEVEN]
+    assert table.field("start").to_pylist() == [r[1] for r in SEVEN]
+    assert table.field("end").to_pylist() == [r[2] for r in full(SEVEN)]
+    assert table.field("bases").to_pylist() == want[1].tolist()
+    # reset with nothing behind it: the empty state
+    st.reset()
+    assert not st.finish()[0].any()
+    st.close()
+
+
+def test_names_form_refuses_rows_without_a_file(ctx):
+    import pyarrow as pa
+    plan = ctx.plan_region_set_bases([("chr1", 1, 100), ("chr2", 5, None)], columns=(0, 1, 2))
+    assert plan.by_name and plan.layout() == (0, 4, 10, 16, 22, 28)
+    st = plan.open()
+    b = pa.RecordBatch.from_arrays([pa.array(np.zeros(4, np.int32)), pa.array(np.ones(4, np.int64)), pa.array(np.ones(4, np.int64))], names=["r", "s", "e"])
+    with pytest.raises(exon_amd.ExonHipError) as e:
+        st.push(b)
+    assert e.value.code == ESTATE and "NAMES" in str(e.value)
+    cols = Cols(ctx, np.zeros(4, np.int32), np.ones(4, np.int64), np.ones(4, np.int64))
+    with pytest.raises(exon_amd.ExonHipError) as e:
+        st.push_device([(x, None, None) for x in cols.bufs], 4)
+    assert e.value.code == ESTATE
+    d = ctx.zeros(np.int64, plan.n_i64)
+    with pytest.raises(exon_amd.ExonHipError) as e:
+        plan.launch(cols.columns(), 4, d)
+    assert e.value.code == ESTATE
+    with pytest.raises(exon_amd.ExonHipError) as e:
+        c = cols.columns()
+        ctx.region_set_bases(c[0][0], None, c[1][0], None, c[2][0], None, 4, plan, d)
+    assert e.value.code == ESTATE
+    table = st.finish_arrow()  # nothing was summed; the names come back
+    assert str(table.type[0].type) == "string" and table.field("contig").to_pylist() == ["chr1", "chr2"]
+    assert table.field("bases").to_pylist() == [0, 0]
+    st.close()
