@@ -606,15 +606,16 @@ int exon_op_seq_stats_hist_views(exon_hip_ctx* ctx, void* stream, const exon_hip
   return EXON_HIP_OK;
 }
 
-// K11 (region_set.hip): the tables are the plan's (stream.cpp).  Column bases need their element's alignment only.
-int exon_op_region_set_overlap(exon_hip_ctx* ctx, void* stream, const exon_hip_column* ref_id, const exon_hip_column* start, const exon_hip_column* end,
-                               int64_t n, const exon::RegionSetTables& t, int64_t* d_state, int flags) {
-  static const char* who = "exon_hip_region_set_overlap";
+// K11 / K12 (region_set.hip, region_bases.hip): the tables are the plan's (stream.cpp).  Column bases need their element's alignment
+// only.  launch(s, ws) starts the kernel over the checked columns and reports as every operator does (HIP_TRY names the call).
+template <typename Launch>
+static int region_set_op(exon_hip_ctx* ctx, void* stream, const char* who, const exon_hip_column* ref_id, const exon_hip_column* start, const exon_hip_column* end,
+                         int64_t n, size_t state_bytes, bool has_tables, int64_t* d_state, int flags, Launch launch) {
   if (!ctx || !d_state) return fail(ctx, EXON_HIP_EINVAL, "%s: NULL argument", who);
   if (reinterpret_cast<uintptr_t>(d_state) & 7) return fail(ctx, EXON_HIP_EINVAL, "%s: d_state must be 8-byte aligned", who);
   if (n < 0) return fail(ctx, EXON_HIP_EINVAL, "n < 0");
   hipStream_t s = pick_stream(ctx, stream);
-  if (n == 0) return empty_input(ctx, s, flags, d_state, (size_t)exon::region_set_words(t.M, t.C) * 8);
+  if (n == 0) return empty_input(ctx, s, flags, d_state, state_bytes);
   const exon_hip_column* cols[3] = {ref_id, start, end};
   static const char* names[3] = {"ref_id", "start", "end"};
   for (int c = 0; c < 3; ++c) {
@@ -622,40 +623,33 @@ int exon_op_region_set_overlap(exon_hip_ctx* ctx, void* stream, const exon_hip_c
     if (cols[c]->length < n) return fail(ctx, EXON_HIP_EINVAL, "%s: %s: length %lld < n %lld", who, names[c], (long long)cols[c]->length, (long long)n);
     if (reinterpret_cast<uintptr_t>(cols[c]->values) & (c ? 7 : 3)) return fail(ctx, EXON_HIP_EINVAL, "%s: %s: values must be %d-byte aligned", who, names[c], c ? 8 : 4);
   }
-  if (!t.map || !t.off || !t.ends || !t.starts) return fail(ctx, EXON_HIP_ESTATE, "%s: the plan has no device tables", who);
+  if (!has_tables) return fail(ctx, EXON_HIP_ESTATE, "%s: the plan has no device tables", who);
   Workspace ws;
   int rc;
   if ((rc = get_workspace(ctx, s, 0, &ws))) return fail(ctx, rc, "workspace allocation failed");
-  HIP_TRY(ctx, exon::launch_region_set_overlap(s, cfg_for(ctx, flags), reinterpret_cast<const uint8_t*>(ws.status + 8), (const int32_t*)ref_id->values,
-                                               ref_id->validity, (const int64_t*)start->values, start->validity, (const int64_t*)end->values,
-                                               end->validity, n, t, d_state));
-  return EXON_HIP_OK;
+  return launch(s, ws);
 }
 
-// K12 (region_bases.hip): the tables are the plan's (stream.cpp).  Column bases need their element's alignment only.
+int exon_op_region_set_overlap(exon_hip_ctx* ctx, void* stream, const exon_hip_column* ref_id, const exon_hip_column* start, const exon_hip_column* end,
+                               int64_t n, const exon::RegionSetTables& t, int64_t* d_state, int flags) {
+  return region_set_op(ctx, stream, "exon_hip_region_set_overlap", ref_id, start, end, n, (size_t)exon::region_set_words(t.M, t.C) * 8,
+                       t.map && t.off && t.ends && t.starts, d_state, flags, [&](hipStream_t s, const Workspace& ws) {
+                         HIP_TRY(ctx, exon::launch_region_set_overlap(s, cfg_for(ctx, flags), reinterpret_cast<const uint8_t*>(ws.status + 8), (const int32_t*)ref_id->values,
+                                                                      ref_id->validity, (const int64_t*)start->values, start->validity, (const int64_t*)end->values,
+                                                                      end->validity, n, t, d_state));
+                         return (int)EXON_HIP_OK;
+                       });
+}
+
 int exon_op_region_set_bases(exon_hip_ctx* ctx, void* stream, const exon_hip_column* ref_id, const exon_hip_column* start, const exon_hip_column* end,
                              int64_t n, const exon::RegionBasesTables& t, int64_t* d_state, int flags) {
-  static const char* who = "exon_hip_region_set_bases";
-  if (!ctx || !d_state) return fail(ctx, EXON_HIP_EINVAL, "%s: NULL argument", who);
-  if (reinterpret_cast<uintptr_t>(d_state) & 7) return fail(ctx, EXON_HIP_EINVAL, "%s: d_state must be 8-byte aligned", who);
-  if (n < 0) return fail(ctx, EXON_HIP_EINVAL, "n < 0");
-  hipStream_t s = pick_stream(ctx, stream);
-  if (n == 0) return empty_input(ctx, s, flags, d_state, (size_t)exon::region_bases_words(t.P, t.C) * 8);
-  const exon_hip_column* cols[3] = {ref_id, start, end};
-  static const char* names[3] = {"ref_id", "start", "end"};
-  for (int c = 0; c < 3; ++c) {
-    if (!cols[c] || !cols[c]->values) return fail(ctx, EXON_HIP_EINVAL, "%s: column %s is NULL", who, names[c]);
-    if (cols[c]->length < n) return fail(ctx, EXON_HIP_EINVAL, "%s: %s: length %lld < n %lld", who, names[c], (long long)cols[c]->length, (long long)n);
-    if (reinterpret_cast<uintptr_t>(cols[c]->values) & (c ? 7 : 3)) return fail(ctx, EXON_HIP_EINVAL, "%s: %s: values must be %d-byte aligned", who, names[c], c ? 8 : 4);
-  }
-  if (!t.map || !t.poff || !t.points) return fail(ctx, EXON_HIP_ESTATE, "%s: the plan has no device tables", who);
-  Workspace ws;
-  int rc;
-  if ((rc = get_workspace(ctx, s, 0, &ws))) return fail(ctx, rc, "workspace allocation failed");
-  HIP_TRY(ctx, exon::launch_region_set_bases(s, cfg_for(ctx, flags), reinterpret_cast<const uint8_t*>(ws.status + 8), (const int32_t*)ref_id->values,
-                                             ref_id->validity, (const int64_t*)start->values, start->validity, (const int64_t*)end->values,
-                                             end->validity, n, t, d_state));
-  return EXON_HIP_OK;
+  return region_set_op(ctx, stream, "exon_hip_region_set_bases", ref_id, start, end, n, (size_t)exon::region_bases_words(t.P, t.C) * 8,
+                       t.map && t.poff && t.points, d_state, flags, [&](hipStream_t s, const Workspace& ws) {
+                         HIP_TRY(ctx, exon::launch_region_set_bases(s, cfg_for(ctx, flags), reinterpret_cast<const uint8_t*>(ws.status + 8), (const int32_t*)ref_id->values,
+                                                                    ref_id->validity, (const int64_t*)start->values, start->validity, (const int64_t*)end->values,
+                                                                    end->validity, n, t, d_state));
+                         return (int)EXON_HIP_OK;
+                       });
 }
 
 extern "C" {

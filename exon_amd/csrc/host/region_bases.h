@@ -13,18 +13,14 @@
 #include <stdint.h>
 
 #include <algorithm>
-#include <string>
 #include <vector>
+
+#include "region_set.h"
 
 namespace exon {
 
-struct RegionBases {
-  int32_t M = 0, C = 0, P = 0;  // regions, distinct contigs, points
-  bool by_name = false;
-  std::vector<std::string> contig_names;  // [C], names form, in order of first appearance
-  std::vector<int32_t> contig_ids;        // [C], ids form
-  std::vector<int32_t> slot;              // [M] contig slot of region i
-  std::vector<int64_t> starts, ends;      // [M] caller order
+struct RegionBases : RegionSetSpec {
+  int32_t P = 0;                          // points
   std::vector<int32_t> poff;              // [C + 1] points in front of each contig
   std::vector<int64_t> points;            // [P], contig c at [poff[c], poff[c + 1]), ascending and unique
   std::vector<int32_t> idx_lo, idx_hi;    // [M] index of rs_i - 1 / re_i among its contig's points

@@ -10,20 +10,20 @@
 #include <stdint.h>
 
 #include <algorithm>
-#include <numeric>
 #include <string>
-#include <unordered_map>
 #include <vector>
 
 namespace exon {
 
-struct RegionSet {
+struct RegionSetSpec {  // what the caller gave: regions and their contigs (kinds 11 and 12 alike; stream.cpp fills it)
   int32_t M = 0, C = 0;
   bool by_name = false;
   std::vector<std::string> contig_names;  // [C], names form, in order of first appearance
   std::vector<int32_t> contig_ids;        // [C], ids form
   std::vector<int32_t> slot;              // [M] contig slot of region i
   std::vector<int64_t> starts, ends;      // [M] caller order
+};
+struct RegionSet : RegionSetSpec {
   std::vector<int32_t> off;               // [C + 1]
   std::vector<int64_t> sorted_ends, sorted_starts;  // [M], contig c at [off[c], off[c + 1])
   std::vector<int32_t> rank_a, rank_b;    // [M]

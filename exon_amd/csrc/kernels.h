@@ -112,9 +112,9 @@ hipError_t launch_seq_stats_hist_views(hipStream_t s, const LaunchCfg& cfg, cons
 // [A: M + C] [B: M + C] (include/exon_hip.h, exon_hip_region_set_layout).  The tables live on the device: map[n_map] = contig slot of
 // a reference id or -1, off[C + 1] = regions in front of each contig, ends / starts [M] sorted within each contig.  Sets with
 // M + C <= REGION_SET_LDS_MAX keep the tables and a u32 histogram pair in LDS (24 bytes per word of the bound: 144 KiB of the CU's
-// 160 at the bound); larger ones search through L2 and add to the state with global atomics.  Rows are dealt in tiles of
-// RS_TILE_BIG (1024 threads) once every CU gets one, else RS_TILE_SMALL (256 threads).  Column bases need their element's alignment
-// only.  `ones`: 64 bytes of 0xFF on the device (Workspace::status + 8).  cfg.overwrite: state := this launch.
+// 160 at the bound); larger ones search through L2 and add to the state with global atomics.  The row walk is region_rows.h's (shared
+// with K12): tiles of RS_TILE_BIG (1024 threads) once every CU gets one, else RS_TILE_SMALL (256 threads).  Column bases need their
+// element's alignment only.  `ones`: 64 bytes of 0xFF on the device (Workspace::status + 8).  cfg.overwrite: state := this launch.
 constexpr int RS_J = 2;
 constexpr int RS_TILE_SMALL = 4 * 256 * RS_J, RS_TILE_BIG = 16 * 256 * RS_J;
 constexpr int REGION_SET_LDS_MAX = 6144;
@@ -137,7 +137,7 @@ hipError_t launch_region_set_overlap(hipStream_t s, const LaunchCfg& cfg, const 
 // K12 (region_bases.hip): the bases of the rows that fall inside every region of a set, in one pass; state [counted, null_rows,
 // elsewhere, inverted] [Ns: P + C] [Ss: P + C] [Ne: P + C] [Se: P + C], every word modulo 2^64 (include/exon_hip.h,
 // exon_hip_region_bases_layout).  Device tables: map[n_map] as K11's, poff[C + 1] = points in front of each contig, points[P] sorted
-// and unique within each contig.  K11's row loop, tiles (RS_TILE_SMALL / RS_TILE_BIG) and `ones`.
+// and unique within each contig.  The row walk (region_rows.h), the tiles (RS_TILE_SMALL / RS_TILE_BIG) and `ones` are K11's.
 // REGION_BASES_LDS_MAX bounds P + C of the LDS tier.  One unit of P + C takes at most 8 B of point table (P <= P + C) and, per bin,
 // u32 Ns + u32 Ne + u64 Ss + u64 Se = 24 B: 32 B, so 4096 units are 128 KiB of the CU's 160 KiB.  The largest power of two that
 // fits (K11 likewise stops short of the 160 KiB a workgroup may ask for, at 144); a bound of 5119 (all of it, untried) would move the

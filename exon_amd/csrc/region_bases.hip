@@ -27,66 +27,14 @@
 //   ONE add of the sum of their values, which a 6-step DPP scan over the wave makes.  A coordinate-sorted file sends whole waves to
 //   one bin; left alone that is 64 serialised adds on one address, twice.  Fewer lanes add for themselves: the scan costs more.
 //
-//   ROWS.  K11's loop: per lane 4 consecutive rows = one 16-byte load of the ids and two of each coordinate, validity by nibble.
-//   Column bases need their element's alignment only: the host finds the `head` (0 .. 3 rows) behind which all three columns
-//   are 16-byte aligned; rows in front of it and behind the last whole tile are read one by one, by whole waves, and columns that
-//   never line up (head = n) are read one by one throughout.
-#include <algorithm>
-
-#include "kernels.h"
+//   ROWS.  region_rows.h walks them (shared with K11): the loads, the head rule, the map lookup, the four totals and the launches.
+//   This file holds what a row ADDS: the point table and its LDS copy, the two searches, the combined adds and the LDS flush.
+#include "region_rows.h"
 
 namespace exon {
 namespace {
 
-typedef int rb_v4i __attribute__((ext_vector_type(4)));
-template <typename T>
-__device__ __forceinline__ T rb_ld16(const void* p) {  // streaming 16-byte load
-  static_assert(sizeof(T) == 16, "16-byte vector expected");
-  const rb_v4i v = __builtin_nontemporal_load(reinterpret_cast<const rb_v4i*>(p));
-  T r;
-  __builtin_memcpy(&r, &v, 16);
-  return r;
-}
-template <typename T>
-__device__ __forceinline__ T rb_ld16_plain(const void* p) {  // the second half of a lane's 32 bytes: the line is already there
-  static_assert(sizeof(T) == 16, "16-byte vector expected");
-  const rb_v4i v = *reinterpret_cast<const rb_v4i*>(p);
-  T r;
-  __builtin_memcpy(&r, &v, 16);
-  return r;
-}
-// validity bits of rows [r, r + 4) (all below n); a NULL bitmap reads the 64 bytes of 0xFF instead: no branch in the tile loop
-__device__ __forceinline__ unsigned rb_valid4(const uint8_t* __restrict__ bm, const uint8_t* __restrict__ ones, int64_t r) {
-  const uint8_t* p0 = bm ? bm + (r >> 3) : ones;
-  const uint8_t* p1 = bm ? bm + ((r + 3) >> 3) : ones;
-  return ((unsigned(*p0) | unsigned(*p1) << 8) >> (r & 7)) & 0xFu;
-}
-__device__ __forceinline__ bool rb_valid1(const uint8_t* __restrict__ bm, int64_t r) { return bm == nullptr ? true : ((bm[r >> 3] >> (r & 7)) & 1); }
-
-struct RBArgs {
-  const int32_t* ref;
-  const uint8_t* rv;
-  const int64_t* start;
-  const uint8_t* sv;
-  const int64_t* end;
-  const uint8_t* ev;
-  const uint8_t* ones;
-  int64_t n, head, ntiles;  // rows [head, head + ntiles * TILE) are read 16 bytes at a time
-  RegionBasesTables t;
-  unsigned long long* state;
-};
-
-// |{ i < m : tab[i] < x }|: branch-free halving, ceil(log2 m) dependent loads
-__device__ __forceinline__ int rb_search(const int64_t* __restrict__ tab, int m, int64_t x) {
-  if (m <= 0) return 0;
-  int base = 0, len = m;
-  while (len > 1) {
-    const int half = len >> 1;
-    base += tab[base + half - 1] < x ? half : 0;
-    len -= half;
-  }
-  return base + (tab[base] < x ? 1 : 0);
-}
+using namespace region_rows;
 
 // the sum of `v` over the 64 lanes of a wave, modulo 2^64, in every lane.  Called by whole waves.  An inclusive scan by DPP row
 // shifts (1, 2, 4, 8 within a row of 16 lanes, lanes shifted in from outside read 0), then lane 15 of rows 0 and 2 added to rows 1
@@ -143,67 +91,26 @@ __device__ __forceinline__ void rb_add(T* cnt, unsigned long long* sum, int idx,
   }
 }
 
-template <bool LDS>
-struct RBBins;
-template <>
-struct RBBins<true> {
-  typedef unsigned word;
-};
-template <>
-struct RBBins<false> {
-  typedef unsigned long long word;
-};
-
-struct RBTotals {
-  unsigned counted = 0, null_rows = 0, elsewhere = 0, inverted = 0;
-};
-
 template <typename W>
 struct RBSections {
   W *Ns, *Ne;
   unsigned long long *Ss, *Se;
 };
 
-// one row, by a whole wave: `live` is false for lanes that have none
-template <bool LDS>
-__device__ __forceinline__ void rb_row(const RBArgs& a, const int64_t* __restrict__ points, const RBSections<typename RBBins<LDS>::word>& b, bool live,
-                                       int32_t r, int64_t s, int64_t e, bool valid, RBTotals& t, int lane) {
-  valid = live && valid;
-  int32_t slot = -1;
-  if (valid && (uint32_t)r < (uint32_t)a.t.n_map) slot = a.t.map[r];  // (an id below 0 is beyond the map as unsigned)
-  const bool on = slot >= 0 && slot < a.t.C;
-  const bool hit = on && e >= s;
-  t.null_rows += live && !valid;
-  t.elsewhere += valid && !on;
-  t.inverted += on && !hit;
-  t.counted += hit;
-  int lo = 0, m = 0;
-  if (hit) {
-    lo = a.t.poff[slot];
-    m = a.t.poff[slot + 1] - lo;
-  }
-  const int p = rb_search(points + lo, m, s);
-  const int q = rb_search(points + lo, m, e);
-  const int base = hit ? lo + slot : 0;
-  rb_add(b.Ns, b.Ss, base + p, (unsigned long long)s, hit, lane);
-  rb_add(b.Ne, b.Se, base + q, (unsigned long long)e, hit, lane);
-}
-
 template <int THREADS, bool LDS>
-__global__ __launch_bounds__(THREADS) void k_region_set_bases(const RBArgs a) {
-  constexpr int WAVES = THREADS / 64, WT = 256 * RS_J, TILE = WAVES * WT;
-  typedef typename RBBins<LDS>::word word;
+__global__ __launch_bounds__(THREADS) void k_region_set_bases(const Rows a, const RegionBasesTables t) {
+  typedef typename BinWord<LDS>::type word;
   extern __shared__ __align__(16) unsigned char rb_lds[];
   __shared__ unsigned long long tot[4];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int P = a.t.P, NB = a.t.P + a.t.C;
-  const int64_t* points = a.t.points;
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int P = t.P, NB = t.P + t.C;
+  const int64_t* points = t.points;
   RBSections<word> b;
   if (LDS) {  // [points: P x 8] [Ss: NB x 8] [Se: NB x 8] [Ns: NB x 4] [Ne: NB x 4]
     int64_t* l_points = reinterpret_cast<int64_t*>(rb_lds);
     unsigned long long* l_sums = reinterpret_cast<unsigned long long*>(l_points + P);
     unsigned* l_cnts = reinterpret_cast<unsigned*>(l_sums + 2 * NB);
-    for (int i = tid; i < P; i += THREADS) l_points[i] = a.t.points[i];
+    for (int i = tid; i < P; i += THREADS) l_points[i] = t.points[i];
     for (int i = tid; i < 2 * NB; i += THREADS) {
       l_sums[i] = 0;
       l_cnts[i] = 0;
@@ -220,60 +127,20 @@ __global__ __launch_bounds__(THREADS) void k_region_set_bases(const RBArgs a) {
   if (tid < 4) tot[tid] = 0;
   __syncthreads();
 
-  RBTotals t;
-  for (int64_t tile = blockIdx.x; tile < a.ntiles; tile += gridDim.x) {
-    const int64_t wbase = a.head + tile * TILE + (int64_t)wave * WT;
-    int4 c[RS_J];
-    longlong2 s0[RS_J], s1[RS_J], e0[RS_J], e1[RS_J];
-    unsigned rm[RS_J], sm[RS_J], em[RS_J];
-#pragma unroll
-    for (int j = 0; j < RS_J; ++j) {
-      const int64_t r = wbase + j * 256 + lane * 4;
-      c[j] = rb_ld16<int4>(a.ref + r);
-      s0[j] = rb_ld16<longlong2>(a.start + r);
-      s1[j] = rb_ld16_plain<longlong2>(a.start + r + 2);
-      e0[j] = rb_ld16<longlong2>(a.end + r);
-      e1[j] = rb_ld16_plain<longlong2>(a.end + r + 2);
-      rm[j] = rb_valid4(a.rv, a.ones, r);
-      sm[j] = rb_valid4(a.sv, a.ones, r);
-      em[j] = rb_valid4(a.ev, a.ones, r);
+  walk<THREADS>(a, tot, [&](int32_t slot, int64_t s, int64_t e) {
+    const bool hit = slot >= 0;
+    int lo = 0, m = 0;
+    if (hit) {
+      lo = t.poff[slot];
+      m = t.poff[slot + 1] - lo;
     }
-#pragma unroll
-    for (int j = 0; j < RS_J; ++j) {
-      const unsigned v = rm[j] & sm[j] & em[j];
-      rb_row<LDS>(a, points, b, true, c[j].x, s0[j].x, e0[j].x, v >> 0 & 1, t, lane);
-      rb_row<LDS>(a, points, b, true, c[j].y, s0[j].y, e0[j].y, v >> 1 & 1, t, lane);
-      rb_row<LDS>(a, points, b, true, c[j].z, s1[j].x, e1[j].x, v >> 2 & 1, t, lane);
-      rb_row<LDS>(a, points, b, true, c[j].w, s1[j].y, e1[j].y, v >> 3 & 1, t, lane);
-    }
-  }
-  // the rows in front of `head` and behind the last whole tile, one by one; they go to the LAST workgroups, which have a tile less
-  // when the tiles do not divide evenly.  Whole waves walk the loop (rb_add's ballots).
-  const int64_t vec_rows = a.ntiles * TILE, scalar_rows = a.n - vec_rows;
-  for (int64_t k0 = (int64_t)(gridDim.x - 1u - blockIdx.x) * THREADS; k0 < scalar_rows; k0 += (int64_t)gridDim.x * THREADS) {
-    const int64_t k = k0 + tid;
-    const bool live = k < scalar_rows;
-    const int64_t r = !live ? 0 : k < a.head ? k : k + vec_rows;
-    int32_t id = 0;
-    int64_t s = 0, e = 0;
-    bool valid = false;
-    if (live) {
-      id = a.ref[r], s = a.start[r], e = a.end[r];
-      valid = rb_valid1(a.rv, r) && rb_valid1(a.sv, r) && rb_valid1(a.ev, r);
-    }
-    rb_row<LDS>(a, points, b, live, id, s, e, valid, t, lane);
-  }
+    const int p = count_below<false>(points + lo, m, s);
+    const int q = count_below<false>(points + lo, m, e);
+    const int base = hit ? lo + slot : 0;
+    rb_add(b.Ns, b.Ss, base + p, (unsigned long long)s, hit, lane);
+    rb_add(b.Ne, b.Se, base + q, (unsigned long long)e, hit, lane);
+  });
 
-  // totals: lanes -> wave -> workgroup -> state
-  unsigned long long w[4] = {t.counted, t.null_rows, t.elsewhere, t.inverted};
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) w[i] += __shfl_down(w[i], o, 64);
-    if (lane == 0 && w[i]) atomicAdd(&tot[i], w[i]);
-  }
-  __syncthreads();
-  if (tid < 4 && tot[tid]) atomicAdd(&a.state[tid], tot[tid]);
   if (LDS) {  // the workgroup's non-zero bins, one global atomic each; sections in state order Ns, Ss, Ne, Se
     const unsigned long long* l_sums = reinterpret_cast<const unsigned long long*>(rb_lds + (size_t)P * 8);
     const unsigned* l_cnts = reinterpret_cast<const unsigned*>(l_sums + 2 * NB);
@@ -287,24 +154,8 @@ __global__ __launch_bounds__(THREADS) void k_region_set_bases(const RBArgs a) {
 }
 
 template <int THREADS, bool LDS>
-hipError_t rb_launch(hipStream_t s, const LaunchCfg& cfg, RBArgs a, int64_t span) {
-  constexpr int TILE = THREADS / 64 * 256 * RS_J;
-  const size_t lds = LDS ? region_bases_lds_bytes(a.t.P, a.t.C) : 0;
-  if (lds > 48 * 1024) {
-    static hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(k_region_set_bases<THREADS, LDS>),
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, REGION_BASES_LDS_MAX * 32);
-    if (attr != hipSuccess) return attr;
-  }
-  a.ntiles = span / TILE;
-  // a persistent grid: what is co-resident, at most one workgroup per tile; rows read one by one count as tiles of THREADS rows
-  int resident = 1;  // (asked per launch for the small shape only: the LDS a workgroup takes is the plan's)
-  if (THREADS < 1024 && (hipOccupancyMaxActiveBlocksPerMultiprocessor(&resident, k_region_set_bases<THREADS, LDS>, THREADS, lds) != hipSuccess || resident < 1))
-    resident = 1;
-  const int per_cu = THREADS >= 1024 ? 1 : std::min(std::max(cfg.blocks_per_cu, 1), resident);
-  const int64_t work = a.ntiles + (a.n - a.ntiles * TILE + THREADS - 1) / THREADS;
-  const int64_t grid = std::max<int64_t>(1, std::min<int64_t>((int64_t)std::max(cfg.compute_units, 1) * per_cu, work));
-  hipLaunchKernelGGL((k_region_set_bases<THREADS, LDS>), dim3((unsigned)grid), dim3(THREADS), lds, s, a);
-  return hipGetLastError();
+hipError_t rb_launch(hipStream_t s, const LaunchCfg& cfg, const Rows& a, const RegionBasesTables& t, int64_t span) {
+  return launch<THREADS, k_region_set_bases<THREADS, LDS>>(s, cfg, a, t, span, LDS ? region_bases_lds_bytes(t.P, t.C) : 0, REGION_BASES_LDS_MAX * 32);
 }
 
 }  // namespace
@@ -312,39 +163,14 @@ hipError_t rb_launch(hipStream_t s, const LaunchCfg& cfg, RBArgs a, int64_t span
 hipError_t launch_region_set_bases(hipStream_t s, const LaunchCfg& cfg, const uint8_t* ones, const int32_t* ref, const uint8_t* ref_valid,
                                    const int64_t* start, const uint8_t* start_valid, const int64_t* end, const uint8_t* end_valid, int64_t n,
                                    const RegionBasesTables& t, int64_t* d_state) {
-  hipError_t e;
-  if (cfg.overwrite && (e = hipMemsetAsync(d_state, 0, (size_t)region_bases_words(t.P, t.C) * 8, s)) != hipSuccess) return e;  // the kernel adds
-  if (n <= 0) return hipSuccess;
+  const Rows all{ref, ref_valid, start, start_valid, end, end_valid, ones, n, 0, 0, t.map, t.n_map, t.C, reinterpret_cast<unsigned long long*>(d_state)};
   // (a contig has two points or more: rs - 1 < re)
-  if (t.C < 1 || t.P < 2 * (int64_t)t.C || t.P > 2 * REGION_SET_MAX_REGIONS || t.n_map < 0) return hipErrorInvalidValue;
-  // the head behind which all three columns are 16-byte aligned (their elements are aligned: capi.cpp); none: every row one by one
-  int64_t head = n;
-  for (int h = 0; h < 4; ++h)
-    if (!((reinterpret_cast<uintptr_t>(ref + h) | reinterpret_cast<uintptr_t>(start + h) | reinterpret_cast<uintptr_t>(end + h)) & 15)) {
-      head = std::min<int64_t>(h, n);
-      break;
-    }
+  const bool ok = !(t.C < 1 || t.P < 2 * (int64_t)t.C || t.P > 2 * REGION_SET_MAX_REGIONS || t.n_map < 0);
   const bool lds = t.P + t.C <= REGION_BASES_LDS_MAX;
-  // u32 counts in LDS: a launch covers at most 2^31 rows
-  for (int64_t o = 0; o < n; o += REGION_SET_LAUNCH_ROWS) {
-    const int64_t m = std::min(n - o, REGION_SET_LAUNCH_ROWS);
-    RBArgs a;
-    a.ref = ref + o, a.start = start + o, a.end = end + o;
-    // (REGION_SET_LAUNCH_ROWS is a multiple of 8: the bitmaps move by whole bytes)
-    a.rv = ref_valid ? ref_valid + (o >> 3) : nullptr, a.sv = start_valid ? start_valid + (o >> 3) : nullptr, a.ev = end_valid ? end_valid + (o >> 3) : nullptr;
-    a.ones = ones;
-    a.n = m;
-    a.head = std::min(head, m);
-    a.ntiles = 0;
-    a.t = t;
-    a.state = reinterpret_cast<unsigned long long*>(d_state);
-    const int64_t span = m - a.head;
-    const bool big = span / RS_TILE_BIG >= std::max(cfg.compute_units, 1);
-    if (lds) e = big ? rb_launch<1024, true>(s, cfg, a, span) : rb_launch<256, true>(s, cfg, a, span);
-    else e = big ? rb_launch<1024, false>(s, cfg, a, span) : rb_launch<256, false>(s, cfg, a, span);
-    if (e != hipSuccess) return e;
-  }
-  return hipSuccess;
+  return run(s, cfg, all, region_bases_words(t.P, t.C), ok, [&](bool big, const Rows& a, int64_t span) {
+    if (lds) return big ? rb_launch<1024, true>(s, cfg, a, t, span) : rb_launch<256, true>(s, cfg, a, t, span);
+    return big ? rb_launch<1024, false>(s, cfg, a, t, span) : rb_launch<256, false>(s, cfg, a, t, span);
+  });
 }
 
 }  // namespace exon

@@ -84,38 +84,28 @@ struct Slot {
   std::atomic<size_t> pending{0};
 };
 
-// plan kind 11: the region set (host/region_set.h) and its device tables, built once by exon_hip_plan_create_region_set and freed
-// with the plan.  A names-form plan has no map of its own: every consumed scan brings one (exon_hip_stream_set_region_set_map).
-struct PlanRegionSet {
-  exon::RegionSet set;
+// plan kinds 11 and 12: the region set (host/region_set.h, host/region_bases.h; the plan's kind says which of the two is filled) and
+// its device tables, built once by the plan's constructor and freed with the plan.  A names-form plan has no map of its own: every
+// consumed scan brings one (exon_hip_stream_set_region_set_map).
+struct PlanRegions {
+  bool bases = false;  // kind 12
+  exon::RegionSet counts;
+  exon::RegionBases covered;
   int32_t* d_map = nullptr;
   int32_t n_map = 0;
-  int32_t* d_off = nullptr;
-  int64_t* d_ends = nullptr;
-  int64_t* d_starts = nullptr;
-  ~PlanRegionSet() {
+  void* d_tab[3] = {nullptr, nullptr, nullptr};  // kind 11: off, ends, starts; kind 12: poff, points
+  ~PlanRegions() {
     if (d_map) hipFree(d_map);
-    if (d_off) hipFree(d_off);
-    if (d_ends) hipFree(d_ends);
-    if (d_starts) hipFree(d_starts);
+    for (void* t : d_tab)
+      if (t) hipFree(t);
   }
-  exon::RegionSetTables tables(const int32_t* map, int32_t n) const { return exon::RegionSetTables{map, n, d_off, d_ends, d_starts, set.M, set.C}; }
-};
-
-// plan kind 12: the set's point table (host/region_bases.h) and its device copy, built once by exon_hip_plan_create_region_set_bases.
-// The names form takes its map from the consumed scan, as kind 11's does.
-struct PlanRegionBases {
-  exon::RegionBases set;
-  int32_t* d_map = nullptr;
-  int32_t n_map = 0;
-  int32_t* d_poff = nullptr;
-  int64_t* d_points = nullptr;
-  ~PlanRegionBases() {
-    if (d_map) hipFree(d_map);
-    if (d_poff) hipFree(d_poff);
-    if (d_points) hipFree(d_points);
+  const exon::RegionSetSpec& spec() const { return bases ? static_cast<const exon::RegionSetSpec&>(covered) : counts; }
+  exon::RegionSetTables count_tables(const int32_t* map, int32_t n) const {
+    return exon::RegionSetTables{map, n, (const int32_t*)d_tab[0], (const int64_t*)d_tab[1], (const int64_t*)d_tab[2], counts.M, counts.C};
   }
-  exon::RegionBasesTables tables(const int32_t* map, int32_t n) const { return exon::RegionBasesTables{map, n, d_poff, d_points, set.P, set.C}; }
+  exon::RegionBasesTables covered_tables(const int32_t* map, int32_t n) const {
+    return exon::RegionBasesTables{map, n, (const int32_t*)d_tab[0], (const int64_t*)d_tab[1], covered.P, covered.C};
+  }
 };
 
 }  // namespace
@@ -127,11 +117,10 @@ struct exon_hip_plan {
   int64_t n_max = 0;  // the last n_max of the n_i64 words fold by unsigned max, not add (CMP_MINMAX_BY_GROUP: its two extreme planes)
   int n_cols;
   ColSpec cols[4];
-  std::unique_ptr<PlanRegionSet> rs;  // REGION_SET_OVERLAP only
-  std::unique_ptr<PlanRegionBases> rb;  // REGION_SET_BASES only
+  std::unique_ptr<PlanRegions> rs;  // REGION_SET_OVERLAP and REGION_SET_BASES only
   // a region-set plan (kind 11 or 12) made from contig names: its ids come from the scan being consumed
-  bool set_by_name() const { return (rs && rs->set.by_name) || (rb && rb->set.by_name); }
-  const std::vector<std::string>* set_names() const { return rs && rs->set.by_name ? &rs->set.contig_names : rb && rb->set.by_name ? &rb->set.contig_names : nullptr; }
+  bool set_by_name() const { return rs && rs->spec().by_name; }
+  const std::vector<std::string>* set_names() const { return set_by_name() ? &rs->spec().contig_names : nullptr; }
 };
 
 struct exon_hip_stream {
@@ -177,9 +166,8 @@ enum { KEYS_NONE = 0, KEYS_LOCAL = 1, KEYS_AGREED = 2 };
 
 // the arguments of a region-set constructor (kinds 11 and 12 take the same ones, by the same rules) -> the set's regions in caller
 // order, their contig slots in order of first appearance, and the largest reference id of the ids form
-template <typename Set>
 static int fill_region_set(exon_hip_ctx* ctx, const char* who, const char* packed_contig_names, size_t packed_bytes, const int32_t* ref_ids, const int64_t* starts,
-                           const int64_t* ends, int32_t n_regions, Set& set, int32_t* max_id) {
+                           const int64_t* ends, int32_t n_regions, exon::RegionSetSpec& set, int32_t* max_id) {
   *max_id = -1;
   set.M = n_regions;
   set.by_name = packed_contig_names != nullptr;
@@ -223,6 +211,22 @@ static int fill_region_set(exon_hip_ctx* ctx, const char* who, const char* packe
     set.C = (int32_t)set.contig_ids.size();
   }
   return EXON_HIP_OK;
+}
+
+// a names-form region-set plan asked to run without a scan's map; `whose`: "the rows'" / "a pushed batch's"
+static int names_form_refusal(exon_hip_ctx* ctx, const char* whose) {
+  return fail(ctx, EXON_HIP_ESTATE, "a region-set plan made from contig NAMES has no ids to compare %s with: feed it files (exon_hip_stream_consume_scan), "
+                                    "or create the plan from reference ids", whose);
+}
+
+// K11 / K12 of a region-set plan over device columns; map: a scan's id -> contig slot map (names form), NULL: the plan's own
+static int run_region_plan(const exon_hip_plan* p, exon_hip_ctx* ctx, void* stream, const exon_hip_column* ref_id, const exon_hip_column* start,
+                           const exon_hip_column* end, int64_t n, const int32_t* map, int32_t n_map, int64_t* d_state, int flags) {
+  const PlanRegions& rs = *p->rs;
+  if (rs.spec().by_name && !map) return names_form_refusal(ctx, "the rows'");
+  if (!rs.spec().by_name) map = rs.d_map, n_map = rs.n_map;
+  return rs.bases ? exon_op_region_set_bases(ctx, stream, ref_id, start, end, n, rs.covered_tables(map, n_map), d_state, flags)
+                  : exon_op_region_set_overlap(ctx, stream, ref_id, start, end, n, rs.count_tables(map, n_map), d_state, flags);
 }
 
 constexpr size_t COLL_SCRATCH = 8192;  // device words for the collectives' votes (up to 511 ranks x 16 bytes), allocated with the state
@@ -479,17 +483,8 @@ static int run_plan(const exon_hip_plan* p, void* stream, const exon_hip_column*
       return exon_op_overlap_count(ctx, stream, &cols[0], &cols[1], &cols[2], n, d.region_chrom_id, d.region_start,
                                    d.region_end, counts, flags, d.kind == EXON_HIP_PLAN_WITHIN_COUNT);
     case EXON_HIP_PLAN_REGION_SET_OVERLAP:
-      if (p->rs->set.by_name && !rs_map)
-        return fail(ctx, EXON_HIP_ESTATE, "a region-set plan made from contig NAMES has no ids to compare the rows' with: feed it files (exon_hip_stream_consume_scan), "
-                                          "or create the plan from reference ids");
-      return exon_op_region_set_overlap(ctx, stream, &cols[0], &cols[1], &cols[2], n, p->rs->set.by_name ? p->rs->tables(rs_map, rs_n_map) : p->rs->tables(p->rs->d_map, p->rs->n_map),
-                                        counts, flags);
     case EXON_HIP_PLAN_REGION_SET_BASES:
-      if (p->rb->set.by_name && !rs_map)
-        return fail(ctx, EXON_HIP_ESTATE, "a region-set plan made from contig NAMES has no ids to compare the rows' with: feed it files (exon_hip_stream_consume_scan), "
-                                          "or create the plan from reference ids");
-      return exon_op_region_set_bases(ctx, stream, &cols[0], &cols[1], &cols[2], n, p->rb->set.by_name ? p->rb->tables(rs_map, rs_n_map) : p->rb->tables(p->rb->d_map, p->rb->n_map),
-                                      counts, flags);
+      return run_region_plan(p, ctx, stream, &cols[0], &cols[1], &cols[2], n, rs_map, rs_n_map, counts, flags);
   }
   return fail(ctx, EXON_HIP_EINVAL, "unknown plan kind %d", d.kind);
 }
@@ -761,10 +756,10 @@ int exon_hip_plan_destroy(exon_hip_plan* plan) {
   return EXON_HIP_OK;
 }
 
-// plan kind 11.  ctx may be NULL: a host-only plan for exon_hip_region_set_layout / _decode (no device tables, nothing to launch).
-int exon_hip_plan_create_region_set(exon_hip_ctx* ctx, const int32_t columns[3], const char* packed_contig_names, size_t packed_bytes, const int32_t* ref_ids,
-                                    const int64_t* starts, const int64_t* ends, int32_t n_regions, exon_hip_plan** out) {
-  static const char* who = "exon_hip_plan_create_region_set";
+// plan kinds 11 and 12 take the same arguments, by the same rules.  ctx may be NULL: a host-only plan for the kind's _layout / _decode
+// (no device tables, nothing to launch).
+static int create_region_plan(exon_hip_ctx* ctx, const char* who, int kind, const int32_t columns[3], const char* packed_contig_names, size_t packed_bytes,
+                              const int32_t* ref_ids, const int64_t* starts, const int64_t* ends, int32_t n_regions, exon_hip_plan** out) {
   if (!out) return fail(ctx, EXON_HIP_EINVAL, "%s: NULL argument", who);
   *out = nullptr;
   if (n_regions < 1) return fail(ctx, EXON_HIP_EINVAL, "%s: n_regions %d: a region set holds at least one region", who, n_regions);
@@ -772,53 +767,80 @@ int exon_hip_plan_create_region_set(exon_hip_ctx* ctx, const int32_t columns[3],
   if (!columns || !starts || !ends || (!packed_contig_names && !ref_ids)) return fail(ctx, EXON_HIP_EINVAL, "%s: NULL argument", who);
   for (int c = 0; c < 3; ++c)
     if (columns[c] < 0) return fail(ctx, EXON_HIP_EINVAL, "negative column index");
-  std::unique_ptr<PlanRegionSet> rs(new (std::nothrow) PlanRegionSet());
+  std::unique_ptr<PlanRegions> rs(new (std::nothrow) PlanRegions());
   exon_hip_plan* p = new (std::nothrow) exon_hip_plan();
   if (!rs || !p) {
     delete p;
     return fail(ctx, EXON_HIP_ENOMEM, "out of host memory");
   }
   std::unique_ptr<exon_hip_plan> guard(p);
+  rs->bases = kind == EXON_HIP_PLAN_REGION_SET_BASES;
+  exon::RegionSetSpec& set = rs->bases ? static_cast<exon::RegionSetSpec&>(rs->covered) : rs->counts;
   int32_t max_id = -1;
-  if (const int rc = fill_region_set(ctx, who, packed_contig_names, packed_bytes, ref_ids, starts, ends, n_regions, rs->set, &max_id)) return rc;
-  exon::RegionSet& set = rs->set;
-  set.build();
+  if (const int rc = fill_region_set(ctx, who, packed_contig_names, packed_bytes, ref_ids, starts, ends, n_regions, set, &max_id)) return rc;
+  struct Upload {
+    void** dst;
+    const void* src;
+    size_t bytes;
+  };
+  std::vector<int32_t> map;
+  std::vector<Upload> up;
+  if (!set.by_name) {
+    map.assign((size_t)max_id + 1, -1);
+    for (int32_t c = 0; c < set.C; ++c) map[(size_t)set.contig_ids[(size_t)c]] = c;
+    rs->n_map = (int32_t)map.size();
+    up.push_back({(void**)&rs->d_map, map.data(), map.size() * 4});
+  }
+  if (rs->bases) {
+    exon::RegionBases& b = rs->covered;
+    b.build();
+    p->n_i64 = b.words();
+    up.push_back({&rs->d_tab[0], b.poff.data(), b.poff.size() * 4});
+    up.push_back({&rs->d_tab[1], b.points.data(), b.points.size() * 8});
+  } else {
+    exon::RegionSet& a = rs->counts;
+    a.build();
+    p->n_i64 = a.words();
+    up.push_back({&rs->d_tab[0], a.off.data(), a.off.size() * 4});
+    up.push_back({&rs->d_tab[1], a.sorted_ends.data(), (size_t)a.M * 8});
+    up.push_back({&rs->d_tab[2], a.sorted_starts.data(), (size_t)a.M * 8});
+  }
   p->ctx = ctx;
   memset(&p->d, 0, sizeof p->d);
-  p->d.kind = EXON_HIP_PLAN_REGION_SET_OVERLAP;
+  p->d.kind = kind;
   for (int c = 0; c < 3; ++c) p->d.columns[c] = columns[c];
   p->n_cols = 3;
   p->cols[0].elem = 4;
   p->cols[1].elem = p->cols[2].elem = 8;
-  p->n_i64 = set.words();
   p->n_f64 = 0;
   if (ctx) {  // the device tables
     hipSetDevice(ctx->device);
-    const size_t M = (size_t)set.M;
-    std::vector<int32_t> map;
-    if (!set.by_name) {
-      map.assign((size_t)max_id + 1, -1);
-      for (int32_t c = 0; c < set.C; ++c) map[(size_t)set.contig_ids[(size_t)c]] = c;
-      rs->n_map = (int32_t)map.size();
-    }
     hipError_t e;
-    if ((!set.by_name && (e = hipMalloc((void**)&rs->d_map, map.size() * 4)) != hipSuccess) || (e = hipMalloc((void**)&rs->d_off, set.off.size() * 4)) != hipSuccess ||
-        (e = hipMalloc((void**)&rs->d_ends, M * 8)) != hipSuccess || (e = hipMalloc((void**)&rs->d_starts, M * 8)) != hipSuccess)
-      return fail(ctx, EXON_HIP_ENOMEM, "%s: device tables: %s", who, hipGetErrorString(e));
-    if ((!set.by_name && (e = hipMemcpy(rs->d_map, map.data(), map.size() * 4, hipMemcpyHostToDevice)) != hipSuccess) ||
-        (e = hipMemcpy(rs->d_off, set.off.data(), set.off.size() * 4, hipMemcpyHostToDevice)) != hipSuccess ||
-        (e = hipMemcpy(rs->d_ends, set.sorted_ends.data(), M * 8, hipMemcpyHostToDevice)) != hipSuccess ||
-        (e = hipMemcpy(rs->d_starts, set.sorted_starts.data(), M * 8, hipMemcpyHostToDevice)) != hipSuccess)
-      return fail(ctx, EXON_HIP_EDEVICE, "%s: device tables: %s", who, hipGetErrorString(e));
+    for (const Upload& u : up)
+      if ((e = hipMalloc(u.dst, u.bytes)) != hipSuccess) return fail(ctx, EXON_HIP_ENOMEM, "%s: device tables: %s", who, hipGetErrorString(e));
+    for (const Upload& u : up)
+      if ((e = hipMemcpy(*u.dst, u.src, u.bytes, hipMemcpyHostToDevice)) != hipSuccess) return fail(ctx, EXON_HIP_EDEVICE, "%s: device tables: %s", who, hipGetErrorString(e));
   }
   p->rs = std::move(rs);
   *out = guard.release();
   return EXON_HIP_OK;
 }
 
-static const PlanRegionSet* region_set_of(const exon_hip_plan* plan, const char* who) {
-  if (!plan || plan->d.kind != EXON_HIP_PLAN_REGION_SET_OVERLAP || !plan->rs) {
-    fail(plan ? plan->ctx : nullptr, EXON_HIP_EINVAL, "%s: not a region-set plan (kind %d)", who, EXON_HIP_PLAN_REGION_SET_OVERLAP);
+int exon_hip_plan_create_region_set(exon_hip_ctx* ctx, const int32_t columns[3], const char* packed_contig_names, size_t packed_bytes, const int32_t* ref_ids,
+                                    const int64_t* starts, const int64_t* ends, int32_t n_regions, exon_hip_plan** out) {
+  return create_region_plan(ctx, "exon_hip_plan_create_region_set", EXON_HIP_PLAN_REGION_SET_OVERLAP, columns, packed_contig_names, packed_bytes, ref_ids, starts, ends,
+                            n_regions, out);
+}
+int exon_hip_plan_create_region_set_bases(exon_hip_ctx* ctx, const int32_t columns[3], const char* packed_contig_names, size_t packed_bytes, const int32_t* ref_ids,
+                                          const int64_t* starts, const int64_t* ends, int32_t n_regions, exon_hip_plan** out) {
+  return create_region_plan(ctx, "exon_hip_plan_create_region_set_bases", EXON_HIP_PLAN_REGION_SET_BASES, columns, packed_contig_names, packed_bytes, ref_ids, starts,
+                            ends, n_regions, out);
+}
+
+// the region set of a plan of `kind` (11 or 12), or NULL with the error set
+static const PlanRegions* region_plan_of(const exon_hip_plan* plan, int kind, const char* who) {
+  if (!plan || plan->d.kind != kind || !plan->rs) {
+    fail(plan ? plan->ctx : nullptr, EXON_HIP_EINVAL, "%s: not a region-set%s plan (kind %d)", who, kind == EXON_HIP_PLAN_REGION_SET_BASES ? " bases" : "", kind);
     return nullptr;
   }
   return plan->rs.get();
@@ -826,128 +848,58 @@ static const PlanRegionSet* region_set_of(const exon_hip_plan* plan, const char*
 
 // host only: word offsets of totals, A, B and the state's size
 int exon_hip_region_set_layout(const exon_hip_plan* plan, int64_t* out /*[4]*/) {
-  const PlanRegionSet* rs = region_set_of(plan, "exon_hip_region_set_layout");
+  const PlanRegions* rs = region_plan_of(plan, EXON_HIP_PLAN_REGION_SET_OVERLAP, "exon_hip_region_set_layout");
   if (!rs) return EXON_HIP_EINVAL;
   if (!out) return fail(plan->ctx, EXON_HIP_EINVAL, "exon_hip_region_set_layout: out is NULL");
   out[0] = 0;
   out[1] = 4;
-  out[2] = 4 + (int64_t)rs->set.M + rs->set.C;
-  out[3] = rs->set.words();
+  out[2] = 4 + (int64_t)rs->counts.M + rs->counts.C;
+  out[3] = rs->counts.words();
   return EXON_HIP_OK;
-}
-
-// host only: state words -> one count per region, in the caller's order; linear in the state
-int exon_hip_region_set_decode(const exon_hip_plan* plan, const int64_t* state, int64_t* out_counts /*[M]*/) {
-  const PlanRegionSet* rs = region_set_of(plan, "exon_hip_region_set_decode");
-  if (!rs) return EXON_HIP_EINVAL;
-  if (!state || !out_counts) return fail(plan->ctx, EXON_HIP_EINVAL, "exon_hip_region_set_decode: NULL argument");
-  rs->set.decode(state, out_counts);
-  return EXON_HIP_OK;
-}
-
-// K11, bare operator: accumulates into d_state (the plan's state words, zeroed once per query by the caller)
-int exon_hip_region_set_overlap(exon_hip_ctx* ctx, void* stream, const exon_hip_column* ref_id, const exon_hip_column* start, const exon_hip_column* end, int64_t n,
-                                const exon_hip_plan* plan, int64_t* d_state) {
-  const PlanRegionSet* rs = region_set_of(plan, "exon_hip_region_set_overlap");
-  if (!rs) return EXON_HIP_EINVAL;
-  if (!ctx || ctx != plan->ctx) return fail(ctx, EXON_HIP_EINVAL, "exon_hip_region_set_overlap: the plan's tables live on the context it was created with");
-  if (rs->set.by_name)
-    return fail(ctx, EXON_HIP_ESTATE, "a region-set plan made from contig NAMES has no ids to compare the rows' with: feed it files (exon_hip_stream_consume_scan), "
-                                      "or create the plan from reference ids");
-  return exon_op_region_set_overlap(ctx, stream, ref_id, start, end, n, rs->tables(rs->d_map, rs->n_map), d_state, EXON_HIP_LAUNCH_ACCUMULATE);
-}
-
-// plan kind 12: kind 11's arguments and rules.  ctx may be NULL: a host-only plan for exon_hip_region_bases_layout / _decode.
-int exon_hip_plan_create_region_set_bases(exon_hip_ctx* ctx, const int32_t columns[3], const char* packed_contig_names, size_t packed_bytes, const int32_t* ref_ids,
-                                          const int64_t* starts, const int64_t* ends, int32_t n_regions, exon_hip_plan** out) {
-  static const char* who = "exon_hip_plan_create_region_set_bases";
-  if (!out) return fail(ctx, EXON_HIP_EINVAL, "%s: NULL argument", who);
-  *out = nullptr;
-  if (n_regions < 1) return fail(ctx, EXON_HIP_EINVAL, "%s: n_regions %d: a region set holds at least one region", who, n_regions);
-  if (n_regions > exon::REGION_SET_MAX_REGIONS) return fail(ctx, EXON_HIP_EUNSUPPORTED, "%s: n_regions %d beyond %d", who, n_regions, exon::REGION_SET_MAX_REGIONS);
-  if (!columns || !starts || !ends || (!packed_contig_names && !ref_ids)) return fail(ctx, EXON_HIP_EINVAL, "%s: NULL argument", who);
-  for (int c = 0; c < 3; ++c)
-    if (columns[c] < 0) return fail(ctx, EXON_HIP_EINVAL, "negative column index");
-  std::unique_ptr<PlanRegionBases> rb(new (std::nothrow) PlanRegionBases());
-  exon_hip_plan* p = new (std::nothrow) exon_hip_plan();
-  if (!rb || !p) {
-    delete p;
-    return fail(ctx, EXON_HIP_ENOMEM, "out of host memory");
-  }
-  std::unique_ptr<exon_hip_plan> guard(p);
-  int32_t max_id = -1;
-  if (const int rc = fill_region_set(ctx, who, packed_contig_names, packed_bytes, ref_ids, starts, ends, n_regions, rb->set, &max_id)) return rc;
-  exon::RegionBases& set = rb->set;
-  set.build();
-  p->ctx = ctx;
-  memset(&p->d, 0, sizeof p->d);
-  p->d.kind = EXON_HIP_PLAN_REGION_SET_BASES;
-  for (int c = 0; c < 3; ++c) p->d.columns[c] = columns[c];
-  p->n_cols = 3;
-  p->cols[0].elem = 4;
-  p->cols[1].elem = p->cols[2].elem = 8;
-  p->n_i64 = set.words();
-  p->n_f64 = 0;
-  if (ctx) {  // the device tables
-    hipSetDevice(ctx->device);
-    std::vector<int32_t> map;
-    if (!set.by_name) {
-      map.assign((size_t)max_id + 1, -1);
-      for (int32_t c = 0; c < set.C; ++c) map[(size_t)set.contig_ids[(size_t)c]] = c;
-      rb->n_map = (int32_t)map.size();
-    }
-    hipError_t e;
-    if ((!set.by_name && (e = hipMalloc((void**)&rb->d_map, map.size() * 4)) != hipSuccess) || (e = hipMalloc((void**)&rb->d_poff, set.poff.size() * 4)) != hipSuccess ||
-        (e = hipMalloc((void**)&rb->d_points, set.points.size() * 8)) != hipSuccess)
-      return fail(ctx, EXON_HIP_ENOMEM, "%s: device tables: %s", who, hipGetErrorString(e));
-    if ((!set.by_name && (e = hipMemcpy(rb->d_map, map.data(), map.size() * 4, hipMemcpyHostToDevice)) != hipSuccess) ||
-        (e = hipMemcpy(rb->d_poff, set.poff.data(), set.poff.size() * 4, hipMemcpyHostToDevice)) != hipSuccess ||
-        (e = hipMemcpy(rb->d_points, set.points.data(), set.points.size() * 8, hipMemcpyHostToDevice)) != hipSuccess)
-      return fail(ctx, EXON_HIP_EDEVICE, "%s: device tables: %s", who, hipGetErrorString(e));
-  }
-  p->rb = std::move(rb);
-  *out = guard.release();
-  return EXON_HIP_OK;
-}
-
-static const PlanRegionBases* region_bases_of(const exon_hip_plan* plan, const char* who) {
-  if (!plan || plan->d.kind != EXON_HIP_PLAN_REGION_SET_BASES || !plan->rb) {
-    fail(plan ? plan->ctx : nullptr, EXON_HIP_EINVAL, "%s: not a region-set bases plan (kind %d)", who, EXON_HIP_PLAN_REGION_SET_BASES);
-    return nullptr;
-  }
-  return plan->rb.get();
 }
 
 // host only: word offsets of totals, Ns, Ss, Ne, Se and the state's size
 int exon_hip_region_bases_layout(const exon_hip_plan* plan, int64_t* out /*[6]*/) {
-  const PlanRegionBases* rb = region_bases_of(plan, "exon_hip_region_bases_layout");
-  if (!rb) return EXON_HIP_EINVAL;
+  const PlanRegions* rs = region_plan_of(plan, EXON_HIP_PLAN_REGION_SET_BASES, "exon_hip_region_bases_layout");
+  if (!rs) return EXON_HIP_EINVAL;
   if (!out) return fail(plan->ctx, EXON_HIP_EINVAL, "exon_hip_region_bases_layout: out is NULL");
   out[0] = 0;
-  for (int k = 0; k < 4; ++k) out[1 + k] = 4 + k * rb->set.bins();
-  out[5] = rb->set.words();
+  for (int k = 0; k < 4; ++k) out[1 + k] = 4 + k * rs->covered.bins();
+  out[5] = rs->covered.words();
   return EXON_HIP_OK;
 }
 
-// host only: state words -> the covered bases of every region, in the caller's order; linear in the state, modulo 2^64
+// host only: state words -> one value per region (kind 11: its count; kind 12: its covered bases, modulo 2^64), in the caller's order;
+// linear in the state
+static int region_plan_decode(const exon_hip_plan* plan, int kind, const char* who, const int64_t* state, int64_t* out) {
+  const PlanRegions* rs = region_plan_of(plan, kind, who);
+  if (!rs) return EXON_HIP_EINVAL;
+  if (!state || !out) return fail(plan->ctx, EXON_HIP_EINVAL, "%s: NULL argument", who);
+  if (rs->bases) rs->covered.decode(state, out);
+  else rs->counts.decode(state, out);
+  return EXON_HIP_OK;
+}
+int exon_hip_region_set_decode(const exon_hip_plan* plan, const int64_t* state, int64_t* out_counts /*[M]*/) {
+  return region_plan_decode(plan, EXON_HIP_PLAN_REGION_SET_OVERLAP, "exon_hip_region_set_decode", state, out_counts);
+}
 int exon_hip_region_bases_decode(const exon_hip_plan* plan, const int64_t* state, int64_t* out_bases /*[M]*/) {
-  const PlanRegionBases* rb = region_bases_of(plan, "exon_hip_region_bases_decode");
-  if (!rb) return EXON_HIP_EINVAL;
-  if (!state || !out_bases) return fail(plan->ctx, EXON_HIP_EINVAL, "exon_hip_region_bases_decode: NULL argument");
-  rb->set.decode(state, out_bases);
-  return EXON_HIP_OK;
+  return region_plan_decode(plan, EXON_HIP_PLAN_REGION_SET_BASES, "exon_hip_region_bases_decode", state, out_bases);
 }
 
-// K12, bare operator: accumulates into d_state (the plan's state words, zeroed once per query by the caller)
+// K11 / K12, bare operators: accumulate into d_state (the plan's state words, zeroed once per query by the caller)
+static int region_plan_op(exon_hip_ctx* ctx, void* stream, int kind, const char* who, const exon_hip_column* ref_id, const exon_hip_column* start,
+                          const exon_hip_column* end, int64_t n, const exon_hip_plan* plan, int64_t* d_state) {
+  if (!region_plan_of(plan, kind, who)) return EXON_HIP_EINVAL;
+  if (!ctx || ctx != plan->ctx) return fail(ctx, EXON_HIP_EINVAL, "%s: the plan's tables live on the context it was created with", who);
+  return run_region_plan(plan, ctx, stream, ref_id, start, end, n, nullptr, 0, d_state, EXON_HIP_LAUNCH_ACCUMULATE);
+}
+int exon_hip_region_set_overlap(exon_hip_ctx* ctx, void* stream, const exon_hip_column* ref_id, const exon_hip_column* start, const exon_hip_column* end, int64_t n,
+                                const exon_hip_plan* plan, int64_t* d_state) {
+  return region_plan_op(ctx, stream, EXON_HIP_PLAN_REGION_SET_OVERLAP, "exon_hip_region_set_overlap", ref_id, start, end, n, plan, d_state);
+}
 int exon_hip_region_set_bases(exon_hip_ctx* ctx, void* stream, const exon_hip_column* ref_id, const exon_hip_column* start, const exon_hip_column* end, int64_t n,
                               const exon_hip_plan* plan, int64_t* d_state) {
-  const PlanRegionBases* rb = region_bases_of(plan, "exon_hip_region_set_bases");
-  if (!rb) return EXON_HIP_EINVAL;
-  if (!ctx || ctx != plan->ctx) return fail(ctx, EXON_HIP_EINVAL, "exon_hip_region_set_bases: the plan's tables live on the context it was created with");
-  if (rb->set.by_name)
-    return fail(ctx, EXON_HIP_ESTATE, "a region-set plan made from contig NAMES has no ids to compare the rows' with: feed it files (exon_hip_stream_consume_scan), "
-                                      "or create the plan from reference ids");
-  return exon_op_region_set_bases(ctx, stream, ref_id, start, end, n, rb->tables(rb->d_map, rb->n_map), d_state, EXON_HIP_LAUNCH_ACCUMULATE);
+  return region_plan_op(ctx, stream, EXON_HIP_PLAN_REGION_SET_BASES, "exon_hip_region_set_bases", ref_id, start, end, n, plan, d_state);
 }
 
 int exon_hip_plan_state_size(const exon_hip_plan* plan, int64_t* n_i64, int64_t* n_f64) {
@@ -1022,8 +974,7 @@ int exon_hip_stream_push(exon_hip_stream* st, struct ArrowArray* batch) {
   exon_hip_plan* p = st->plan;
   if (p->set_by_name() && !st->rs_in_scan) {
     batch->release(batch);
-    return fail(st->ctx, EXON_HIP_ESTATE, "a region-set plan made from contig NAMES has no ids to compare a pushed batch's with: feed it files "
-                                          "(exon_hip_stream_consume_scan), or create the plan from reference ids");
+    return names_form_refusal(st->ctx, "a pushed batch's");
   }
   const int64_t rows = batch->length;
   int rc = EXON_HIP_OK;
@@ -1274,8 +1225,7 @@ int exon_hip_stream_push_device(exon_hip_stream* st, const struct ArrowDeviceArr
     return fail(st->ctx, EXON_HIP_EINVAL, "batch lives on device %lld, stream on %d", (long long)dbatch->device_id, st->ctx->device);
   exon_hip_plan* p = st->plan;
   if (p->set_by_name() && !st->rs_in_scan)
-    return fail(st->ctx, EXON_HIP_ESTATE, "a region-set plan made from contig NAMES has no ids to compare a pushed batch's with: feed it files "
-                                          "(exon_hip_stream_consume_scan), or create the plan from reference ids");
+    return names_form_refusal(st->ctx, "a pushed batch's");
   const struct ArrowArray* batch = &dbatch->array;
   const int64_t rows = batch->length;
   exon_hip_column cols[4];
@@ -2292,10 +2242,12 @@ int exon_hip_stream_finish_arrow(exon_hip_stream* st, struct ArrowArray* out, st
       make_schema(out_schema, "+s", "", false, {field("i", "stat", false), field("i", "bin", false), field("l", "count", false)});
       break;
     }
-    case EXON_HIP_PLAN_REGION_SET_OVERLAP: {  // one row per region, in the caller's order
-      const exon::RegionSet& set = p->rs->set;
-      std::vector<int64_t> cnt((size_t)set.M);
-      set.decode(counts.data(), cnt.data());
+    case EXON_HIP_PLAN_REGION_SET_OVERLAP:
+    case EXON_HIP_PLAN_REGION_SET_BASES: {  // one row per region, in the caller's order: its count (kind 11) or its covered bases (kind 12)
+      const exon::RegionSetSpec& set = p->rs->spec();
+      std::vector<int64_t> val((size_t)set.M);
+      if (p->rs->bases) p->rs->covered.decode(counts.data(), val.data());
+      else p->rs->counts.decode(counts.data(), val.data());
       struct ArrowArray* contig;
       if (set.by_name) {
         std::vector<std::string> names((size_t)set.M);
@@ -2306,28 +2258,10 @@ int exon_hip_stream_finish_arrow(exon_hip_stream* st, struct ArrowArray* out, st
         for (int32_t i = 0; i < set.M; ++i) ids[(size_t)i] = set.contig_ids[(size_t)set.slot[(size_t)i]];
         contig = prim(ids);
       }
-      make_struct(out, (int64_t)set.M, {contig, prim(set.starts), prim(set.ends), prim(cnt)});
+      make_struct(out, (int64_t)set.M, {contig, prim(set.starts), prim(set.ends), prim(val)});
       make_schema(out_schema, "+s", "", false,
-                  {field(set.by_name ? "u" : "i", "contig", false), field("l", "start", false), field("l", "end", false), field("l", "count", false)});
-      break;
-    }
-    case EXON_HIP_PLAN_REGION_SET_BASES: {  // one row per region, in the caller's order
-      const exon::RegionBases& set = p->rb->set;
-      std::vector<int64_t> bases((size_t)set.M);
-      set.decode(counts.data(), bases.data());
-      struct ArrowArray* contig;
-      if (set.by_name) {
-        std::vector<std::string> names((size_t)set.M);
-        for (int32_t i = 0; i < set.M; ++i) names[(size_t)i] = set.contig_names[(size_t)set.slot[(size_t)i]];
-        contig = exon::utf8_array(names);
-      } else {
-        std::vector<int32_t> ids((size_t)set.M);
-        for (int32_t i = 0; i < set.M; ++i) ids[(size_t)i] = set.contig_ids[(size_t)set.slot[(size_t)i]];
-        contig = prim(ids);
-      }
-      make_struct(out, (int64_t)set.M, {contig, prim(set.starts), prim(set.ends), prim(bases)});
-      make_schema(out_schema, "+s", "", false,
-                  {field(set.by_name ? "u" : "i", "contig", false), field("l", "start", false), field("l", "end", false), field("l", "bases", false)});
+                  {field(set.by_name ? "u" : "i", "contig", false), field("l", "start", false), field("l", "end", false),
+                   field("l", p->rs->bases ? "bases" : "count", false)});
       break;
     }
     default:
