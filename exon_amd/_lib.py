@@ -169,6 +169,9 @@ REGION_SET_LDS_MAX = 6144  # kernels.h: sets with M + C up to this are searched 
 REGION_SET_TILE_SMALL, REGION_SET_TILE_BIG = 2048, 8192  # kernels.h: rows per workgroup tile of the two launch shapes
 PLAN_REGION_SET_BASES = 12
 REGION_BASES_LDS_MAX = 4096  # kernels.h: sets with P + C up to this are searched and summed in LDS (32 B a unit: 128 KiB)
+PLAN_WINDOW_BASES = 13
+WINDOW_BASES_LDS_MAX = 8192  # kernels.h: plans with B windows up to this add in LDS (16 B a window: 128 KiB)
+WINDOW_MAX_BINS = 1 << 25
 LAUNCH_ACCUMULATE = 0
 LAUNCH_OVERWRITE = 1
 CMP = {">": 0, ">=": 1, "<": 2, "<=": 3, "=": 4, "==": 4, "!=": 5, "<>": 5}
@@ -227,6 +230,11 @@ SIGNATURES = {
     "exon_hip_region_bases_layout": (C.c_int, [_vp, C.POINTER(_i64)]),
     "exon_hip_region_bases_decode": (C.c_int, [_vp, _vp, _vp]),
     "exon_hip_region_set_bases": (C.c_int, [_vp, _vp, _colp, _colp, _colp, _i64, _vp, _vp]),
+    "exon_hip_plan_create_window_bases": (C.c_int, [_vp, C.POINTER(_i32), C.c_char_p, C.c_size_t, _vp, _vp, _i32, _i64, C.POINTER(_vp)]),
+    "exon_hip_window_bases_layout": (C.c_int, [_vp, C.POINTER(_i64)]),
+    "exon_hip_window_bases_offsets": (C.c_int, [_vp, _vp]),
+    "exon_hip_window_bases_decode": (C.c_int, [_vp, _vp, _vp]),
+    "exon_hip_window_bases": (C.c_int, [_vp, _vp, _colp, _colp, _colp, _i64, _vp, _vp]),
     "exon_hip_rccl_unique_id": (C.c_int, [_vp]),
     "exon_hip_rccl_comm_init": (C.c_int, [_vp, _vp, _i32, _i32, C.POINTER(_vp)]),
     "exon_hip_rccl_comm_destroy": (C.c_int, [_vp]),
@@ -256,6 +264,7 @@ SIGNATURES = {
     "exon_hip_scan_dictionary_intern": (C.c_int, [_vp, _i32, C.c_char_p, C.POINTER(_i32)]),
     "exon_hip_scan_dictionary_value": (C.c_int, [_vp, _i32, _i32, C.POINTER(C.c_char_p)]),
     "exon_hip_scan_rows": (C.c_int, [_vp, C.POINTER(_i64)]),
+    "exon_hip_scan_reference_lengths": (C.c_int, [_vp, _vp, _i32, C.POINTER(_i32)]),
     "exon_hip_scan_bind_ctx": (C.c_int, [_vp, _vp]),
     "exon_hip_scan_set_predicate": (C.c_int, [_vp, _i32, _i32, C.c_double]),
     "exon_hip_scan_set_flag_predicate": (C.c_int, [_vp, _i32, _i32, _i32]),

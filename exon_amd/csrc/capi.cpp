@@ -606,7 +606,7 @@ int exon_op_seq_stats_hist_views(exon_hip_ctx* ctx, void* stream, const exon_hip
   return EXON_HIP_OK;
 }
 
-// K11 / K12 (region_set.hip, region_bases.hip): the tables are the plan's (stream.cpp).  Column bases need their element's alignment
+// K11 / K12 / K13 (region_set.hip, region_bases.hip, window_bases.hip): the tables are the plan's (stream.cpp).  Column bases need their element's alignment
 // only.  launch(s, ws) starts the kernel over the checked columns and reports as every operator does (HIP_TRY names the call).
 template <typename Launch>
 static int region_set_op(exon_hip_ctx* ctx, void* stream, const char* who, const exon_hip_column* ref_id, const exon_hip_column* start, const exon_hip_column* end,
@@ -648,6 +648,17 @@ int exon_op_region_set_bases(exon_hip_ctx* ctx, void* stream, const exon_hip_col
                          HIP_TRY(ctx, exon::launch_region_set_bases(s, cfg_for(ctx, flags), reinterpret_cast<const uint8_t*>(ws.status + 8), (const int32_t*)ref_id->values,
                                                                     ref_id->validity, (const int64_t*)start->values, start->validity, (const int64_t*)end->values,
                                                                     end->validity, n, t, d_state));
+                         return (int)EXON_HIP_OK;
+                       });
+}
+
+int exon_op_window_bases(exon_hip_ctx* ctx, void* stream, const exon_hip_column* ref_id, const exon_hip_column* start, const exon_hip_column* end, int64_t n,
+                         const exon::WindowBasesTables& t, int64_t* d_state, int flags) {
+  return region_set_op(ctx, stream, "exon_hip_window_bases", ref_id, start, end, n, (size_t)exon::window_bases_words(t.B) * 8, t.map && t.woff && t.len, d_state, flags,
+                       [&](hipStream_t s, const Workspace& ws) {
+                         HIP_TRY(ctx, exon::launch_window_bases(s, cfg_for(ctx, flags), reinterpret_cast<const uint8_t*>(ws.status + 8), (const int32_t*)ref_id->values,
+                                                                ref_id->validity, (const int64_t*)start->values, start->validity, (const int64_t*)end->values, end->validity,
+                                                                n, t, d_state));
                          return (int)EXON_HIP_OK;
                        });
 }

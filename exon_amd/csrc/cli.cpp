@@ -24,12 +24,14 @@
 //   SELECT COUNT(*) FROM <bam table> WHERE bam_region_filter('<r>', reference, start, end)          -- K6 (plain table; INDEXED_BAM plans chunks on the host)
 //   SELECT * FROM overlap_counts('<bam|sam|cram|gff|gtf file>', '<regions.bed>'[, 'gzip'])       -- K11: one row per BED line, in file order
 //   SELECT * FROM covered_bases('<bam|sam|cram|gff|gtf file>', '<regions.bed>'[, 'gzip'])        -- K12: the rows' bases inside each BED line
+//   SELECT * FROM window_depth('<bam|sam|cram file>', <W>[, '<genome file>'])                     -- K13: the rows' bases per window of width W along every contig
 //   DROP TABLE t;
 #include <dirent.h>
 #include <sys/stat.h>
 
 #include <algorithm>
 #include <cctype>
+#include <climits>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -146,6 +148,8 @@ struct Source {  // resolved FROM clause
   int n_fields = 12;  // BED
   std::string regions_bed;  // overlap_counts / covered_bases: the BED file of the region set
   bool bases = false;       // covered_bases: K12's sums instead of K11's counts
+  int64_t window = 0;       // window_depth: the window width (0: another source)
+  std::string genome_file;  // window_depth: contigs and lengths from a bedtools genome file / .fai instead of the file's header
 };
 
 struct Session {
@@ -432,13 +436,22 @@ Source resolve_from(Session& se, Parser& ps) {
   Source src;
   const std::string name = ps.ident();
   const std::string lname = lower(name);
-  if (ps.accept_sym("(")) {  // table function: <fmt>_scan / <fmt>_indexed_scan / fastq_quality_histogram / fastq_read_stats / fasta_seq_stats / overlap_counts / covered_bases
+  if (ps.accept_sym("(")) {  // table function: <fmt>_scan / <fmt>_indexed_scan / fastq_quality_histogram / fastq_read_stats / fasta_seq_stats / overlap_counts / covered_bases / window_depth
     const std::string path = ps.str();
-    if (lname == "overlap_counts" || lname == "covered_bases") {  // ('<file>', '<regions.bed>'[, '<compression>']): the source's format by its extension
+    if (lname == "overlap_counts" || lname == "covered_bases" || lname == "window_depth") {  // the source's format by its extension
       ps.expect_sym(",");
-      src.regions_bed = ps.str();
-      src.bases = lname == "covered_bases";
-      if (ps.accept_sym(",")) src.compression = compression_of(ps.str());
+      if (lname == "window_depth") {  // ('<file>', <W>[, '<genome file>'])
+        const std::string w = ps.number();
+        char* endp = nullptr;
+        src.window = strtoll(w.c_str(), &endp, 10);
+        if (*endp) throw Err("window_depth: the window width must be a whole number, got " + w);
+        if (src.window < 1) throw Err("window_depth: the window width must be at least 1, got " + w);
+        if (ps.accept_sym(",")) src.genome_file = ps.str();
+      } else {  // ('<file>', '<regions.bed>'[, '<compression>'])
+        src.regions_bed = ps.str();
+        src.bases = lname == "covered_bases";
+        if (ps.accept_sym(",")) src.compression = compression_of(ps.str());
+      }
       ps.expect_sym(")");
       std::string stem = lower(path);
       for (const char* z : {".gz", ".bgz"})
@@ -715,6 +728,74 @@ void exec_select(Session& se, Parser& ps) {
     std::vector<std::vector<std::string>> rows;
     for (size_t i = 0; i < names.size(); ++i) rows.push_back({names[i], std::to_string(starts[i]), std::to_string(ends[i]), std::to_string(counts[i])});
     print_table({"contig", "start", "end", src.bases ? "bases" : "count"}, rows, se.quiet);
+    return;
+  }
+
+  if (src.window > 0) {  // K13: the rows' bases per window along every contig; contigs and lengths from the genome file or the first file's header
+    std::vector<std::string> names;
+    std::vector<int64_t> lengths;
+    const bool annotation = src.format == EXON_HIP_FORMAT_GFF || src.format == EXON_HIP_FORMAT_GTF;
+    if (!src.genome_file.empty()) {
+      std::ifstream in(src.genome_file);
+      if (!in) throw Err("no such file: " + src.genome_file);
+      std::string line;
+      for (int64_t ln = 1; std::getline(in, line); ++ln) {
+        if (!line.empty() && line.back() == '\r') line.pop_back();
+        if (line.empty() || line[0] == '#') continue;
+        std::istringstream ls(line);
+        std::string chrom;
+        long long len = 0;
+        if (!(ls >> chrom >> len) || len < 1 || len > INT32_MAX)
+          throw Err(src.genome_file + " line " + std::to_string(ln) + ": expected <name> <length> with 1 <= length <= 2147483647");
+        names.push_back(chrom);
+        lengths.push_back(len);
+      }
+      if (names.empty()) throw Err(src.genome_file + ": no contigs");
+    } else {
+      if (annotation) throw Err("window_depth: a GFF / GTF source has no contig lengths: give a genome file, window_depth('<file>', <W>, '<genome file>')");
+      if (src.files.empty()) throw Err("window_depth: no input file");
+      ScanGuard g; open_scan(src, src.files[0], nullptr, "", &g);
+      int32_t n = 0;
+      ck(nullptr, exon_hip_scan_reference_lengths(g.s, nullptr, 0, &n));
+      std::vector<int64_t> len((size_t)n);
+      if (n) ck(nullptr, exon_hip_scan_reference_lengths(g.s, len.data(), n, &n));
+      for (int32_t i = 0; i < n; ++i) {
+        if (len[(size_t)i] < 1) continue;  // (a SAM @SQ without LN: it has no windows)
+        const char* name = nullptr;
+        ck(nullptr, exon_hip_scan_dictionary_value(g.s, 2, i, &name));
+        names.push_back(name);
+        lengths.push_back(len[(size_t)i]);
+      }
+      if (names.empty()) throw Err("window_depth: the header of " + src.files[0] + " names no contig with a length");
+    }
+    std::string packed;
+    for (const auto& nm : names) {
+      packed += nm;
+      packed.push_back('\0');
+    }
+    exon_hip_ctx* ctx = se.gpu();  // (the genome file and the header are judged first: their errors need no device)
+    const int32_t columns[3] = {annotation ? 0 : 2, 3, 4};
+    StreamGuard sg;
+    ck(ctx, exon_hip_plan_create_window_bases(ctx, columns, packed.data(), packed.size(), nullptr, lengths.data(), (int32_t)names.size(), src.window, &sg.p));
+    ck(ctx, exon_hip_stream_open(sg.p, 0, &sg.s));
+    for (const auto& f : src.files) {  // one stream: the state is keyed by the windows, the files add up
+      ScanGuard g; open_scan(src, f, nullptr, "", &g, true);
+      ck(ctx, exon_hip_stream_consume_scan(sg.s, g.s, nullptr));
+    }
+    int64_t n_i64 = 0, n_f64 = 0;
+    ck(ctx, exon_hip_plan_state_size(sg.p, &n_i64, &n_f64));
+    std::vector<int64_t> state((size_t)n_i64), woff(names.size() + 1);
+    ck(ctx, exon_hip_stream_finish(sg.s, state.data(), nullptr));
+    ck(ctx, exon_hip_window_bases_offsets(sg.p, woff.data()));
+    std::vector<int64_t> bases((size_t)woff.back());
+    ck(ctx, exon_hip_window_bases_decode(sg.p, state.data(), bases.data()));
+    std::vector<std::vector<std::string>> rows;
+    for (size_t c = 0; c < names.size(); ++c)
+      for (int64_t b = woff[c]; b < woff[c + 1]; ++b) {
+        const int64_t j = b - woff[c];
+        rows.push_back({names[c], std::to_string(j * src.window + 1), std::to_string(b + 1 == woff[c + 1] ? lengths[c] : (j + 1) * src.window), std::to_string(bases[(size_t)b])});
+      }
+    print_table({"contig", "start", "end", "bases"}, rows, se.quiet);
     return;
   }
 
@@ -1094,7 +1175,9 @@ int main(int argc, char** argv) {
              "             fasta_seq_stats('<path>'[, 'gzip'])\n"
              "             overlap_counts('<bam|sam|cram|gff|gtf file>', '<regions.bed>'[, 'gzip'])   one row per BED line: contig, start, end (1-based closed), count\n"
              "             covered_bases('<bam|sam|cram|gff|gtf file>', '<regions.bed>'[, 'gzip'])    one row per BED line: contig, start, end (1-based closed), bases\n"
-             "  queries:   SELECT COUNT(*) FROM <src> [WHERE chrom = 'c' AND pos >= a AND pos <= b | vcf_region_filter('r', chrom) | bam_region_filter('r', reference, start, end)\n"
+             "             window_depth('<bam|sam|cram file>', <W>)                                   one row per window of width W along every contig of the header: contig, start, end, bases\n"
+             "             window_depth('<bam|sam|cram|gff|gtf file>', <W>, '<genome file>')          the contigs and lengths from `name<TAB>length` lines (a bedtools genome file, a .fai)\n"
+             "  queries:  SELECT COUNT(*) FROM <src> [WHERE chrom = 'c' AND pos >= a AND pos <= b | vcf_region_filter('r', chrom) | bam_region_filter('r', reference, start, end)\n"
              "             | gff_region_filter('r', seqname[, start])]\n"
              "             SELECT COUNT(*) FROM <bam|sam> WHERE [bam_region_filter('r', reference, start, end) AND] flag & M = V [AND CAST(mapping_quality AS INT) >= q]\n"
              "             SELECT reference, COUNT(*) FROM <bam> WHERE flag & M = V AND CAST(mapping_quality AS INT) >= q GROUP BY reference\n"

@@ -156,6 +156,36 @@ hipError_t launch_region_set_bases(hipStream_t s, const LaunchCfg& cfg, const ui
                                    const int64_t* start, const uint8_t* start_valid, const int64_t* end, const uint8_t* end_valid, int64_t n,
                                    const RegionBasesTables& t, int64_t* d_state);
 
+// K13 (window_bases.hip): the bases of the rows inside every fixed-width window along each contig, in one pass; state [counted,
+// null_rows, elsewhere, inverted] [E: B] [D: B], every word modulo 2^64 (include/exon_hip.h, exon_hip_window_bases_layout).  Device
+// tables: map[n_map] as K11's, woff[C + 1] = windows in front of each contig, len[C] = contig lengths.  The window of a clipped
+// coordinate x is (x - 1) / W with x - 1 < 2^31: W (clamped to 2^31 - 1, which changes no quotient) travels with the reciprocal
+// window_bases_reciprocal() makes, so the kernel multiplies and shifts.  Plans with B <= WINDOW_BASES_LDS_MAX keep E and D in LDS as
+// u64, 16 B a bin: 128 KiB, the largest power of two under the 160 KiB a workgroup may take (K12's reasoning); D stays 64 bits wide
+// there: a launch of 2^31 rows can leave a net of +2^31 or -2^31 in one bin, which 32 bits cannot tell apart.  Larger plans add to the
+// state with global 64-bit atomics.  The row walk, the tiles and `ones` are K11's.  cfg.overwrite: state := this launch.
+constexpr int WINDOW_BASES_LDS_MAX = 8192;
+constexpr int64_t WINDOW_BASES_MAX_BINS = (int64_t)1 << 25;
+constexpr int64_t window_bases_words(int64_t B) { return 4 + 2 * B; }
+struct WindowBasesTables {
+  const int32_t* map;
+  int32_t n_map;
+  const int32_t* woff;
+  const int32_t* len;
+  uint32_t W, mul, shift;  // floor(x / W) = (uint64_t)x * mul >> shift for every x < 2^31
+  int32_t B, C;
+};
+// exact for 0 <= x < 2^31 and 1 <= W < 2^31 (Granlund & Montgomery 1994, N = 31): l = ceil(log2 W), mul = ceil(2^(31 + l) / W) < 2^32
+inline void window_bases_reciprocal(uint32_t W, uint32_t* mul, uint32_t* shift) {
+  uint32_t l = 0;
+  while (((uint64_t)1 << l) < W) ++l;
+  *shift = 31 + l;
+  *mul = (uint32_t)((((uint64_t)1 << *shift) + W - 1) / W);
+}
+hipError_t launch_window_bases(hipStream_t s, const LaunchCfg& cfg, const uint8_t* ones, const int32_t* ref, const uint8_t* ref_valid,
+                               const int64_t* start, const uint8_t* start_valid, const int64_t* end, const uint8_t* end_valid, int64_t n,
+                               const WindowBasesTables& t, int64_t* d_state);
+
 // pushed-down region filter as a row mask: out_valid = in_valid AND (row hits the region); *n_pass += rows kept.
 // point form (VCF): id_col = chrom id, start = pos; range form (BAM): id_col = reference id, [start, end].
 hipError_t launch_region_mask(hipStream_t s, bool range_form, const int32_t* id_col, const uint8_t* id_valid, const int64_t* start,

@@ -24,8 +24,9 @@
 //   counts into u32 bins (ds_add_u32) and the sums into u64 bins (ds_add_u64), then adds its non-zero bins to the state with one
 //   global atomic each.  Beyond: the searches read the table through L2 and every add is a global 64-bit atomic.  In both, the lanes
 //   of a wave that hit the bin of the wave's first live lane are combined once there are 16 of them: ONE add of their count, and
-//   ONE add of the sum of their values, which a 6-step DPP scan over the wave makes.  A coordinate-sorted file sends whole waves to
-//   one bin; left alone that is 64 serialised adds on one address, twice.  Fewer lanes add for themselves: the scan costs more.
+//   ONE add of the sum of their values, which a 6-step DPP scan over the wave makes (region_rows.h's wave_sum, shared with K13).  A
+//   coordinate-sorted file sends whole waves to one bin; left alone that is 64 serialised adds on one address, twice.  Fewer lanes
+//   add for themselves: the scan costs more.
 //
 //   ROWS.  region_rows.h walks them (shared with K11): the loads, the head rule, the map lookup, the four totals and the launches.
 //   This file holds what a row ADDS: the point table and its LDS copy, the two searches, the combined adds and the LDS flush.
@@ -36,34 +37,10 @@ namespace {
 
 using namespace region_rows;
 
-// the sum of `v` over the 64 lanes of a wave, modulo 2^64, in every lane.  Called by whole waves.  An inclusive scan by DPP row
-// shifts (1, 2, 4, 8 within a row of 16 lanes, lanes shifted in from outside read 0), then lane 15 of rows 0 and 2 added to rows 1
-// and 3 and lane 31 to rows 2 and 3: lane 63 holds the total.  VALU only -- a __shfl_xor butterfly is 12 ds_bpermute per sum, on the
-// LDS pipeline the searches and the adds need.
-__device__ __forceinline__ unsigned long long rb_wave_sum(unsigned long long v) {
-#define RB_DPP_ADD(CTRL, ROWS)                                                                                  \
-  {                                                                                                             \
-    const unsigned lo = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(unsigned)v, CTRL, ROWS, 0xf, true);         \
-    const unsigned hi = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(unsigned)(v >> 32), CTRL, ROWS, 0xf, true); \
-    v += (unsigned long long)hi << 32 | lo;                                                                     \
-  }
-  RB_DPP_ADD(0x111, 0xf)  // row_shr:1
-  RB_DPP_ADD(0x112, 0xf)  // row_shr:2
-  RB_DPP_ADD(0x114, 0xf)  // row_shr:4
-  RB_DPP_ADD(0x118, 0xf)  // row_shr:8
-  RB_DPP_ADD(0x142, 0xa)  // row_bcast:15 into rows 1 and 3 (the other rows add `old` = 0)
-  RB_DPP_ADD(0x143, 0xc)  // row_bcast:31 into rows 2 and 3
-#undef RB_DPP_ADD
-  const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)v, 63), hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(v >> 32), 63);
-  return (unsigned long long)hi << 32 | lo;
-}
-
 // cnt[idx] += 1 and sum[idx] += val (modulo 2^64) for every lane with `act`.  When RB_COMBINE_MIN lanes or more share the bin of the
-// wave's first live lane, they become one add of their count and one add of the sum of their values; every other lane adds for
-// itself.  Called by whole waves (the ballots and the scan need every lane).  The threshold: the scan is about 30 VALU instructions
-// a sum, a few lanes on one address serialise for a few cycles each; measured, combining from two lanes on cost rows in random order
-// 0.2 ms per 1e8 (profiles/region_set_bases.md), while whole waves on one bin -- a coordinate-sorted file -- need it.
-constexpr int RB_COMBINE_MIN = 16;
+// wave's first live lane, they become one add of their count and one add of the sum of their values (region_rows.h's wave_sum);
+// every other lane adds for itself.  Called by whole waves (the ballots and the scan need every lane).
+constexpr int RB_COMBINE_MIN = COMBINE_MIN;
 template <typename T>
 __device__ __forceinline__ void rb_add(T* cnt, unsigned long long* sum, int idx, unsigned long long val, bool act, int lane) {
   const unsigned long long live = __ballot(act);
@@ -77,7 +54,7 @@ __device__ __forceinline__ void rb_add(T* cnt, unsigned long long* sum, int idx,
   }
   if (__popcll(sm) >= RB_COMBINE_MIN) {
     const bool same = (sm >> lane) & 1;
-    const unsigned long long tot = rb_wave_sum(same ? val : 0ull);
+    const unsigned long long tot = wave_sum(same ? val : 0ull);
     if (lane == first) {
       atomicAdd(&cnt[idx], (T)__popcll(sm));
       atomicAdd(&sum[idx], tot);

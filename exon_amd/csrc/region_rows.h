@@ -1,4 +1,4 @@
-// region_rows.h -- the row walk that the region-set kernels share (K11 region_set.hip, K12 region_bases.hip): how a kernel gets from
+// region_rows.h -- the row walk that the region-set kernels share (K11 region_set.hip, K12 region_bases.hip, K13 window_bases.hip): how a kernel gets from
 // the three interval columns to "this row is on contig slot c with coordinates [s, e]", and how the host cuts the rows into launches.
 // What a row then ADDS is the including kernel's business: it hands walk() a functor.  Included by .hip files only.
 //
@@ -150,6 +150,33 @@ __device__ __forceinline__ int count_below(const int64_t* __restrict__ tab, int 
   const int64_t v = tab[base];
   return base + ((UPPER ? v <= x : v < x) ? 1 : 0);
 }
+
+// the sum of `v` over the 64 lanes of a wave, modulo 2^64, in every lane.  Called by whole waves.  An inclusive scan by DPP row
+// shifts (1, 2, 4, 8 within a row of 16 lanes, lanes shifted in from outside read 0), then lane 15 of rows 0 and 2 added to rows 1
+// and 3 and lane 31 to rows 2 and 3: lane 63 holds the total.  VALU only -- a __shfl_xor butterfly is 12 ds_bpermute per sum, on the
+// LDS pipeline the searches and the adds need.
+__device__ __forceinline__ unsigned long long wave_sum(unsigned long long v) {
+#define RR_DPP_ADD(CTRL, ROWS)                                                                                  \
+  {                                                                                                             \
+    const unsigned lo = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(unsigned)v, CTRL, ROWS, 0xf, true);         \
+    const unsigned hi = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(unsigned)(v >> 32), CTRL, ROWS, 0xf, true); \
+    v += (unsigned long long)hi << 32 | lo;                                                                     \
+  }
+  RR_DPP_ADD(0x111, 0xf)  // row_shr:1
+  RR_DPP_ADD(0x112, 0xf)  // row_shr:2
+  RR_DPP_ADD(0x114, 0xf)  // row_shr:4
+  RR_DPP_ADD(0x118, 0xf)  // row_shr:8
+  RR_DPP_ADD(0x142, 0xa)  // row_bcast:15 into rows 1 and 3 (the other rows add `old` = 0)
+  RR_DPP_ADD(0x143, 0xc)  // row_bcast:31 into rows 2 and 3
+#undef RR_DPP_ADD
+  const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)v, 63), hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(v >> 32), 63);
+  return (unsigned long long)hi << 32 | lo;
+}
+// The lanes of a wave that add to the bin of the wave's first live lane are combined into one add (K12's rb_add, K13's wb_add) once
+// there are this many of them.  The scan is about 30 VALU instructions a sum, a few lanes on one address serialise for a few cycles
+// each; measured on K12, combining from two lanes on cost rows in random order 0.2 ms per 1e8 (profiles/region_set_bases.md), while
+// whole waves on one bin -- a coordinate-sorted file -- need it.
+constexpr int COMBINE_MIN = 16;
 
 // the word of a count bin: u32 in a workgroup's LDS (at most REGION_SET_LAUNCH_ROWS rows a launch), the state's 64 bits in memory
 template <bool LDS>

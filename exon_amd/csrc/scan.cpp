@@ -653,6 +653,19 @@ int exon_hip_scan_rows(exon_hip_scan* s, int64_t* rows) {
   return EXON_HIP_OK;
 }
 
+// the header's reference lengths: every reader parses them with the names, whichever decoder then takes the records
+int exon_hip_scan_reference_lengths(exon_hip_scan* s, int64_t* out, int32_t cap, int32_t* n) {
+  if (!s || !n || cap < 0 || (cap > 0 && !out)) return fail(nullptr, EXON_HIP_EINVAL, "exon_hip_scan_reference_lengths: bad argument");
+  const std::vector<int32_t>* len = nullptr;
+  if (exon::BAMBatchReader* r = s->bam()) len = &r->ref_lengths;
+  else if (exon::SAMBatchReader* r = s->sam()) len = &r->ref_lengths;
+  else if (exon::CRAMBatchReader* r = s->reader_if<exon::CRAMBatchReader>(EXON_HIP_FORMAT_CRAM)) len = &r->ref_lengths;
+  if (!len) return fail(nullptr, EXON_HIP_EUNSUPPORTED, "exon_hip_scan_reference_lengths: only BAM, SAM and CRAM headers carry reference lengths (format %d)", s->format);
+  *n = (int32_t)len->size();
+  for (int32_t i = 0; i < std::min(*n, cap); ++i) out[i] = (*len)[(size_t)i];
+  return EXON_HIP_OK;
+}
+
 int exon_hip_scan_index_chunks(exon_hip_scan* s, int32_t* n) {
   if (!s || !n) return fail(nullptr, EXON_HIP_EINVAL, "NULL argument");
   *n = s->vcf() ? s->vcf()->n_chunks : s->bam() ? s->bam()->n_chunks : s->gff() ? s->gff()->n_chunks : -1;
@@ -2936,8 +2949,11 @@ static int consume_text_gpu(exon_hip_stream* st, exon_hip_scan* scan, int64_t* r
             (t_init - t_begin) * 1e3, (t_loop - t_init) * 1e3, n_sources, t_next * 1e3, t_parse * 1e3, (t_loop - t_init - t_next - t_parse) * 1e3, t_reader * 1e3);
   }
   if (rc == EXON_HIP_OK && (filtered || valued || flagged)) {  // the scan emitted the rows that hit the region and pass the predicate
+    // (read on the scan's stream: a null-stream copy does not wait for a non-blocking stream, and an indexed region without chunks
+    // runs no source, so nothing above has waited for the fill of the two words)
     unsigned long long kept = 0;
-    HIP_TRY(ctx, hipMemcpy(&kept, scan->d_region_pass, 8, hipMemcpyDeviceToHost));
+    HIP_TRY(ctx, hipMemcpyAsync(&kept, scan->d_region_pass, 8, hipMemcpyDeviceToHost, hs));
+    HIP_TRY(ctx, hipStreamSynchronize(hs));
     total = (int64_t)kept;
   }
   if (rc == EXON_HIP_OK && scan->parser.owns_names) {  // the dictionaries the device built -> scan

@@ -34,6 +34,7 @@
 #include "host/bitmap.h"
 #include "host/raw_batch.h"
 #include "host/region_bases.h"
+#include "host/window_bases.h"
 #include "host/region_set.h"
 #include "internal.h"
 
@@ -84,27 +85,34 @@ struct Slot {
   std::atomic<size_t> pending{0};
 };
 
-// plan kinds 11 and 12: the region set (host/region_set.h, host/region_bases.h; the plan's kind says which of the two is filled) and
-// its device tables, built once by the plan's constructor and freed with the plan.  A names-form plan has no map of its own: every
-// consumed scan brings one (exon_hip_stream_set_region_set_map).
+// plan kinds 11, 12 and 13: the region set or the windows (host/region_set.h, host/region_bases.h, host/window_bases.h; the plan's kind
+// says which of the three is filled) and its device tables, built once by the plan's constructor and freed with the plan.  A
+// names-form plan has no map of its own: every consumed scan brings one (exon_hip_stream_set_region_set_map).
 struct PlanRegions {
-  bool bases = false;  // kind 12
+  bool bases = false;    // kind 12
+  bool windows = false;  // kind 13
   exon::RegionSet counts;
   exon::RegionBases covered;
+  exon::WindowBases win;
   int32_t* d_map = nullptr;
   int32_t n_map = 0;
-  void* d_tab[3] = {nullptr, nullptr, nullptr};  // kind 11: off, ends, starts; kind 12: poff, points
+  void* d_tab[3] = {nullptr, nullptr, nullptr};  // kind 11: off, ends, starts; kind 12: poff, points; kind 13: woff, len
   ~PlanRegions() {
     if (d_map) hipFree(d_map);
     for (void* t : d_tab)
       if (t) hipFree(t);
   }
-  const exon::RegionSetSpec& spec() const { return bases ? static_cast<const exon::RegionSetSpec&>(covered) : counts; }
+  const exon::RegionSetSpec& spec() const { return windows ? static_cast<const exon::RegionSetSpec&>(win) : bases ? static_cast<const exon::RegionSetSpec&>(covered) : counts; }
   exon::RegionSetTables count_tables(const int32_t* map, int32_t n) const {
     return exon::RegionSetTables{map, n, (const int32_t*)d_tab[0], (const int64_t*)d_tab[1], (const int64_t*)d_tab[2], counts.M, counts.C};
   }
   exon::RegionBasesTables covered_tables(const int32_t* map, int32_t n) const {
     return exon::RegionBasesTables{map, n, (const int32_t*)d_tab[0], (const int64_t*)d_tab[1], covered.P, covered.C};
+  }
+  exon::WindowBasesTables window_tables(const int32_t* map, int32_t n) const {
+    exon::WindowBasesTables t{map, n, (const int32_t*)d_tab[0], (const int32_t*)d_tab[1], (uint32_t)std::min<int64_t>(win.W, INT32_MAX), 0, 0, (int32_t)win.B, win.C};
+    exon::window_bases_reciprocal(t.W, &t.mul, &t.shift);
+    return t;
   }
 };
 
@@ -117,8 +125,8 @@ struct exon_hip_plan {
   int64_t n_max = 0;  // the last n_max of the n_i64 words fold by unsigned max, not add (CMP_MINMAX_BY_GROUP: its two extreme planes)
   int n_cols;
   ColSpec cols[4];
-  std::unique_ptr<PlanRegions> rs;  // REGION_SET_OVERLAP and REGION_SET_BASES only
-  // a region-set plan (kind 11 or 12) made from contig names: its ids come from the scan being consumed
+  std::unique_ptr<PlanRegions> rs;  // REGION_SET_OVERLAP, REGION_SET_BASES and WINDOW_BASES only
+  // a region-set or window plan (kind 11, 12 or 13) made from contig names: its ids come from the scan being consumed
   bool set_by_name() const { return rs && rs->spec().by_name; }
   const std::vector<std::string>* set_names() const { return set_by_name() ? &rs->spec().contig_names : nullptr; }
 };
@@ -157,7 +165,7 @@ struct exon_hip_stream {
   std::string region_contig;
   bool has_region_contig = false;
   int32_t region_id_override = INT32_MIN;
-  // region-set plans (kinds 11 and 12) in the names form: the scan being consumed has resolved the set's names in its own dictionary;
+  // region-set and window plans (kinds 11, 12 and 13) in the names form: the scan being consumed has resolved the set's names in its own dictionary;
   // d_map / map_cap hold its id -> contig slot map (the re-keying map's buffer: such a plan is not keyed)
   bool rs_in_scan = false;
   int32_t rs_n_map = 0;
@@ -165,9 +173,10 @@ struct exon_hip_stream {
 enum { KEYS_NONE = 0, KEYS_LOCAL = 1, KEYS_AGREED = 2 };
 
 // the arguments of a region-set constructor (kinds 11 and 12 take the same ones, by the same rules) -> the set's regions in caller
-// order, their contig slots in order of first appearance, and the largest reference id of the ids form
+// order, their contig slots in order of first appearance, and the largest reference id of the ids form.  Kind 13 names its contigs
+// by the same rules (`what`: what an entry is called in a message)
 static int fill_region_set(exon_hip_ctx* ctx, const char* who, const char* packed_contig_names, size_t packed_bytes, const int32_t* ref_ids, const int64_t* starts,
-                           const int64_t* ends, int32_t n_regions, exon::RegionSetSpec& set, int32_t* max_id) {
+                           const int64_t* ends, int32_t n_regions, exon::RegionSetSpec& set, int32_t* max_id, const char* what = "region") {
   *max_id = -1;
   set.M = n_regions;
   set.by_name = packed_contig_names != nullptr;
@@ -184,7 +193,7 @@ static int fill_region_set(exon_hip_ctx* ctx, const char* who, const char* packe
       const void* z = at < packed_bytes ? memchr(packed_contig_names + at, 0, packed_bytes - at) : nullptr;
       if (!z) return fail(ctx, EXON_HIP_EINVAL, "%s: packed_contig_names holds fewer than %d '\\0'-terminated names", who, n_regions);
       std::string name(packed_contig_names + at, static_cast<const char*>(z));
-      if (name.empty()) return fail(ctx, EXON_HIP_EINVAL, "%s: region %d: empty contig name", who, i);
+      if (name.empty()) return fail(ctx, EXON_HIP_EINVAL, "%s: %s %d: empty contig name", who, what, i);
       at += name.size() + 1;
       auto it = index.find(name);
       if (it == index.end()) {
@@ -197,9 +206,9 @@ static int fill_region_set(exon_hip_ctx* ctx, const char* who, const char* packe
   } else {
     std::unordered_map<int32_t, int32_t> index;
     for (int32_t i = 0; i < n_regions; ++i) {
-      if (ref_ids[i] < 0) return fail(ctx, EXON_HIP_EINVAL, "%s: region %d: negative reference id %d", who, i, ref_ids[i]);
+      if (ref_ids[i] < 0) return fail(ctx, EXON_HIP_EINVAL, "%s: %s %d: negative reference id %d", who, what, i, ref_ids[i]);
       if (ref_ids[i] >= EXON_HIP_MAX_REFERENCES)
-        return fail(ctx, EXON_HIP_EUNSUPPORTED, "%s: region %d: reference id %d beyond %d (the id -> contig map is a dense table)", who, i, ref_ids[i], EXON_HIP_MAX_REFERENCES - 1);
+        return fail(ctx, EXON_HIP_EUNSUPPORTED, "%s: %s %d: reference id %d beyond %d (the id -> contig map is a dense table)", who, what, i, ref_ids[i], EXON_HIP_MAX_REFERENCES - 1);
       auto it = index.find(ref_ids[i]);
       if (it == index.end()) {
         it = index.emplace(ref_ids[i], (int32_t)set.contig_ids.size()).first;
@@ -219,12 +228,13 @@ static int names_form_refusal(exon_hip_ctx* ctx, const char* whose) {
                                     "or create the plan from reference ids", whose);
 }
 
-// K11 / K12 of a region-set plan over device columns; map: a scan's id -> contig slot map (names form), NULL: the plan's own
+// K11 / K12 / K13 of a region-set or window plan over device columns; map: a scan's id -> contig slot map (names form), NULL: the plan's own
 static int run_region_plan(const exon_hip_plan* p, exon_hip_ctx* ctx, void* stream, const exon_hip_column* ref_id, const exon_hip_column* start,
                            const exon_hip_column* end, int64_t n, const int32_t* map, int32_t n_map, int64_t* d_state, int flags) {
   const PlanRegions& rs = *p->rs;
   if (rs.spec().by_name && !map) return names_form_refusal(ctx, "the rows'");
   if (!rs.spec().by_name) map = rs.d_map, n_map = rs.n_map;
+  if (rs.windows) return exon_op_window_bases(ctx, stream, ref_id, start, end, n, rs.window_tables(map, n_map), d_state, flags);
   return rs.bases ? exon_op_region_set_bases(ctx, stream, ref_id, start, end, n, rs.covered_tables(map, n_map), d_state, flags)
                   : exon_op_region_set_overlap(ctx, stream, ref_id, start, end, n, rs.count_tables(map, n_map), d_state, flags);
 }
@@ -484,6 +494,7 @@ static int run_plan(const exon_hip_plan* p, void* stream, const exon_hip_column*
                                    d.region_end, counts, flags, d.kind == EXON_HIP_PLAN_WITHIN_COUNT);
     case EXON_HIP_PLAN_REGION_SET_OVERLAP:
     case EXON_HIP_PLAN_REGION_SET_BASES:
+    case EXON_HIP_PLAN_WINDOW_BASES:
       return run_region_plan(p, ctx, stream, &cols[0], &cols[1], &cols[2], n, rs_map, rs_n_map, counts, flags);
   }
   return fail(ctx, EXON_HIP_EINVAL, "unknown plan kind %d", d.kind);
@@ -636,6 +647,8 @@ int exon_hip_plan_create(exon_hip_ctx* ctx, const exon_hip_plan_desc* desc, exon
     return fail(ctx, EXON_HIP_EINVAL, "plan kind %d takes a region set, which exon_hip_plan_desc cannot hold: use exon_hip_plan_create_region_set", desc->kind);
   if (desc && desc->kind == EXON_HIP_PLAN_REGION_SET_BASES)
     return fail(ctx, EXON_HIP_EINVAL, "plan kind %d takes a region set, which exon_hip_plan_desc cannot hold: use exon_hip_plan_create_region_set_bases", desc->kind);
+  if (desc && desc->kind == EXON_HIP_PLAN_WINDOW_BASES)
+    return fail(ctx, EXON_HIP_EINVAL, "plan kind %d takes contig lengths and a window width, which exon_hip_plan_desc cannot hold: use exon_hip_plan_create_window_bases", desc->kind);
   if (!ctx || !desc || !out) return fail(ctx, EXON_HIP_EINVAL, "exon_hip_plan_create: NULL argument");
   exon_hip_plan* p = new (std::nothrow) exon_hip_plan();
   if (!p) return fail(ctx, EXON_HIP_ENOMEM, "out of host memory");
@@ -837,10 +850,81 @@ int exon_hip_plan_create_region_set_bases(exon_hip_ctx* ctx, const int32_t colum
                             ends, n_regions, out);
 }
 
-// the region set of a plan of `kind` (11 or 12), or NULL with the error set
+// plan kind 13: the contigs by kind 11 / 12's rules (ids form or names form, each contig once), their lengths and the window width.
+// ctx may be NULL: a host-only plan for exon_hip_window_bases_layout / _offsets / _decode.
+int exon_hip_plan_create_window_bases(exon_hip_ctx* ctx, const int32_t columns[3], const char* packed_contig_names, size_t packed_bytes, const int32_t* ref_ids,
+                                      const int64_t* lengths, int32_t n_contigs, int64_t window, exon_hip_plan** out) {
+  const char* who = "exon_hip_plan_create_window_bases";
+  if (!out) return fail(ctx, EXON_HIP_EINVAL, "%s: NULL argument", who);
+  *out = nullptr;
+  if (n_contigs < 1) return fail(ctx, EXON_HIP_EINVAL, "%s: n_contigs %d: the plan holds at least one contig", who, n_contigs);
+  if (n_contigs > EXON_HIP_WINDOW_MAX_BINS) return fail(ctx, EXON_HIP_EUNSUPPORTED, "%s: n_contigs %d beyond %d (every contig has a window)", who, n_contigs, EXON_HIP_WINDOW_MAX_BINS);
+  if (!columns || !lengths || (!packed_contig_names && !ref_ids)) return fail(ctx, EXON_HIP_EINVAL, "%s: NULL argument", who);
+  if (window < 1) return fail(ctx, EXON_HIP_EINVAL, "%s: window %lld: the width must be at least 1", who, (long long)window);
+  for (int c = 0; c < 3; ++c)
+    if (columns[c] < 0) return fail(ctx, EXON_HIP_EINVAL, "negative column index");
+  for (int32_t c = 0; c < n_contigs; ++c)
+    if (lengths[c] < 1 || lengths[c] > INT32_MAX)
+      return fail(ctx, EXON_HIP_EINVAL, "%s: contig %d: length %lld outside [1, 2^31 - 1]", who, c, (long long)lengths[c]);
+  std::unique_ptr<PlanRegions> rs(new (std::nothrow) PlanRegions());
+  std::unique_ptr<exon_hip_plan> p(new (std::nothrow) exon_hip_plan());
+  if (!rs || !p) return fail(ctx, EXON_HIP_ENOMEM, "out of host memory");
+  static_assert(exon::WindowBases::MAX_BINS == EXON_HIP_WINDOW_MAX_BINS && exon::WINDOW_BASES_MAX_BINS == EXON_HIP_WINDOW_MAX_BINS, "one bound in three headers");
+  rs->windows = true;
+  exon::WindowBases& w = rs->win;
+  int32_t max_id = -1;
+  // (a contig's [length, length] passes as an interval: the names and ids are read by kind 11 / 12's parser)
+  if (const int rc = fill_region_set(ctx, who, packed_contig_names, packed_bytes, ref_ids, lengths, lengths, n_contigs, w, &max_id, "contig")) return rc;
+  for (int32_t c = 0; c < n_contigs; ++c)
+    if (w.slot[(size_t)c] != c) {  // slots are handed out in order of first appearance: this entry fell into an earlier one
+      if (w.by_name) return fail(ctx, EXON_HIP_EINVAL, "%s: contig %d: '%s' is given twice", who, c, w.contig_names[(size_t)w.slot[(size_t)c]].c_str());
+      return fail(ctx, EXON_HIP_EINVAL, "%s: contig %d: reference id %d is given twice", who, c, w.contig_ids[(size_t)w.slot[(size_t)c]]);
+    }
+  w.M = 0;  // it has no regions
+  w.slot.clear(), w.starts.clear(), w.ends.clear();
+  w.W = window;
+  w.len.assign(lengths, lengths + n_contigs);
+  if (!w.build())
+    return fail(ctx, EXON_HIP_EUNSUPPORTED, "%s: %lld windows of width %lld beyond %lld (a state of 512 MiB)", who, (long long)w.B, (long long)window, (long long)EXON_HIP_WINDOW_MAX_BINS);
+  p->ctx = ctx;
+  memset(&p->d, 0, sizeof p->d);
+  p->d.kind = EXON_HIP_PLAN_WINDOW_BASES;
+  for (int c = 0; c < 3; ++c) p->d.columns[c] = columns[c];
+  p->n_cols = 3;
+  p->cols[0].elem = 4;
+  p->cols[1].elem = p->cols[2].elem = 8;
+  p->n_i64 = w.words();
+  p->n_f64 = 0;
+  if (ctx) {  // the device tables
+    std::vector<int32_t> map;
+    if (!w.by_name) {
+      map.assign((size_t)max_id + 1, -1);
+      for (int32_t c = 0; c < w.C; ++c) map[(size_t)w.contig_ids[(size_t)c]] = c;
+      rs->n_map = (int32_t)map.size();
+    }
+    const struct {
+      void** dst;
+      const void* src;
+      size_t bytes;
+    } up[3] = {{(void**)&rs->d_map, map.data(), map.size() * 4}, {&rs->d_tab[0], w.woff.data(), w.woff.size() * 4}, {&rs->d_tab[1], w.len.data(), w.len.size() * 4}};
+    hipSetDevice(ctx->device);
+    hipError_t e;
+    for (const auto& u : up) {
+      if (!u.bytes) continue;
+      if ((e = hipMalloc(u.dst, u.bytes)) != hipSuccess) return fail(ctx, EXON_HIP_ENOMEM, "%s: device tables: %s", who, hipGetErrorString(e));
+      if ((e = hipMemcpy(*u.dst, u.src, u.bytes, hipMemcpyHostToDevice)) != hipSuccess) return fail(ctx, EXON_HIP_EDEVICE, "%s: device tables: %s", who, hipGetErrorString(e));
+    }
+  }
+  p->rs = std::move(rs);
+  *out = p.release();
+  return EXON_HIP_OK;
+}
+
+// the region set of a plan of `kind` (11 or 12) or the windows of one of kind 13, or NULL with the error set
 static const PlanRegions* region_plan_of(const exon_hip_plan* plan, int kind, const char* who) {
   if (!plan || plan->d.kind != kind || !plan->rs) {
-    fail(plan ? plan->ctx : nullptr, EXON_HIP_EINVAL, "%s: not a region-set%s plan (kind %d)", who, kind == EXON_HIP_PLAN_REGION_SET_BASES ? " bases" : "", kind);
+    if (kind == EXON_HIP_PLAN_WINDOW_BASES) fail(plan ? plan->ctx : nullptr, EXON_HIP_EINVAL, "%s: not a window-bases plan (kind %d)", who, kind);
+    else fail(plan ? plan->ctx : nullptr, EXON_HIP_EINVAL, "%s: not a region-set%s plan (kind %d)", who, kind == EXON_HIP_PLAN_REGION_SET_BASES ? " bases" : "", kind);
     return nullptr;
   }
   return plan->rs.get();
@@ -900,6 +984,38 @@ int exon_hip_region_set_overlap(exon_hip_ctx* ctx, void* stream, const exon_hip_
 int exon_hip_region_set_bases(exon_hip_ctx* ctx, void* stream, const exon_hip_column* ref_id, const exon_hip_column* start, const exon_hip_column* end, int64_t n,
                               const exon_hip_plan* plan, int64_t* d_state) {
   return region_plan_op(ctx, stream, EXON_HIP_PLAN_REGION_SET_BASES, "exon_hip_region_set_bases", ref_id, start, end, n, plan, d_state);
+}
+
+// kind 13, host only: word offsets of totals, E, D and the state's size
+int exon_hip_window_bases_layout(const exon_hip_plan* plan, int64_t* out /*[4]*/) {
+  const PlanRegions* rs = region_plan_of(plan, EXON_HIP_PLAN_WINDOW_BASES, "exon_hip_window_bases_layout");
+  if (!rs) return EXON_HIP_EINVAL;
+  if (!out) return fail(plan->ctx, EXON_HIP_EINVAL, "exon_hip_window_bases_layout: out is NULL");
+  out[0] = 0;
+  out[1] = 4;
+  out[2] = 4 + rs->win.B;
+  out[3] = rs->win.words();
+  return EXON_HIP_OK;
+}
+// kind 13, host only: the windows in front of each contig, then B
+int exon_hip_window_bases_offsets(const exon_hip_plan* plan, int64_t* woff /*[C + 1]*/) {
+  const PlanRegions* rs = region_plan_of(plan, EXON_HIP_PLAN_WINDOW_BASES, "exon_hip_window_bases_offsets");
+  if (!rs) return EXON_HIP_EINVAL;
+  if (!woff) return fail(plan->ctx, EXON_HIP_EINVAL, "exon_hip_window_bases_offsets: woff is NULL");
+  std::copy(rs->win.woff.begin(), rs->win.woff.end(), woff);
+  return EXON_HIP_OK;
+}
+// kind 13, host only: state words -> the bases of every window (modulo 2^64), contig by contig; linear in the state
+int exon_hip_window_bases_decode(const exon_hip_plan* plan, const int64_t* state, int64_t* out_bases /*[B]*/) {
+  const PlanRegions* rs = region_plan_of(plan, EXON_HIP_PLAN_WINDOW_BASES, "exon_hip_window_bases_decode");
+  if (!rs) return EXON_HIP_EINVAL;
+  if (!state || !out_bases) return fail(plan->ctx, EXON_HIP_EINVAL, "exon_hip_window_bases_decode: NULL argument");
+  rs->win.decode(state, out_bases);
+  return EXON_HIP_OK;
+}
+int exon_hip_window_bases(exon_hip_ctx* ctx, void* stream, const exon_hip_column* ref_id, const exon_hip_column* start, const exon_hip_column* end, int64_t n,
+                          const exon_hip_plan* plan, int64_t* d_state) {
+  return region_plan_op(ctx, stream, EXON_HIP_PLAN_WINDOW_BASES, "exon_hip_window_bases", ref_id, start, end, n, plan, d_state);
 }
 
 int exon_hip_plan_state_size(const exon_hip_plan* plan, int64_t* n_i64, int64_t* n_f64) {
@@ -2262,6 +2378,27 @@ int exon_hip_stream_finish_arrow(exon_hip_stream* st, struct ArrowArray* out, st
       make_schema(out_schema, "+s", "", false,
                   {field(set.by_name ? "u" : "i", "contig", false), field("l", "start", false), field("l", "end", false),
                    field("l", p->rs->bases ? "bases" : "count", false)});
+      break;
+    }
+    case EXON_HIP_PLAN_WINDOW_BASES: {  // one row per window, contig by contig in the caller's order, windows ascending
+      const exon::WindowBases& w = p->rs->win;
+      std::vector<int64_t> val((size_t)w.B), ws((size_t)w.B), we((size_t)w.B);
+      w.decode(counts.data(), val.data());
+      std::vector<int32_t> ids;
+      std::vector<std::string> names;
+      if (w.by_name) names.resize((size_t)w.B);
+      else ids.resize((size_t)w.B);
+      for (int32_t c = 0; c < w.C; ++c)
+        for (int64_t b = w.woff[(size_t)c]; b < w.woff[(size_t)c + 1]; ++b) {
+          const int64_t j = b - w.woff[(size_t)c];
+          ws[(size_t)b] = w.window_start(j);
+          we[(size_t)b] = w.window_end(c, j);
+          if (w.by_name) names[(size_t)b] = w.contig_names[(size_t)c];
+          else ids[(size_t)b] = w.contig_ids[(size_t)c];
+        }
+      make_struct(out, w.B, {w.by_name ? exon::utf8_array(names) : prim(ids), prim(ws), prim(we), prim(val)});
+      make_schema(out_schema, "+s", "", false,
+                  {field(w.by_name ? "u" : "i", "contig", false), field("l", "start", false), field("l", "end", false), field("l", "bases", false)});
       break;
     }
     default:

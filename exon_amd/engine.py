@@ -379,6 +379,20 @@ class Context:
         self._check(self.lib.exon_hip_region_set_bases(self.h, stream, C.byref(c0), C.byref(c1), C.byref(c2), n, plan.h,
                                                        d_state.ptr if isinstance(d_state, DeviceBuffer) else d_state))
 
+    def plan_window_bases(self, contigs, window, columns=(2, 3, 4)):
+        """The bases of the rows inside every window of width `window` along each contig, in one pass over the rows (plan kind 13).
+        `contigs`: (contig, length) pairs, contig an int (reference ids) in all of them or a str (names, resolved by every consumed
+        scan in its own header order) in all of them.  Window j of a contig is [j * window + 1, min((j + 1) * window, length)]; rows
+        are clipped to [1, length].  State: 4 + 2 * B int64 words, all of which add modulo 2^64; WindowBasesPlan.decode turns them
+        into one sum per window, finish_arrow into a table."""
+        return WindowBasesPlan(self, contigs, window, columns)
+
+    def window_bases(self, ref_id, ref_valid, start, start_valid, end, end_valid, n, plan, d_state, stream=None):
+        """K13 (bare operator, ids form): accumulates the batch into `d_state` (plan.n_i64 int64 words)."""
+        c0, c1, c2 = _col(ref_id, ref_valid, None, n), _col(start, start_valid, None, n), _col(end, end_valid, None, n)
+        self._check(self.lib.exon_hip_window_bases(self.h, stream, C.byref(c0), C.byref(c1), C.byref(c2), n, plan.h,
+                                                   d_state.ptr if isinstance(d_state, DeviceBuffer) else d_state))
+
 
 def region_bases_layout(plan):
     """exon_hip_region_bases_layout (host-only): word offsets of the totals / Ns / Ss / Ne / Se sections of a kind-12 plan's state,
@@ -668,6 +682,15 @@ class Scan:
         n = C.c_int64()
         self._check(self.lib.exon_hip_scan_rows(self.h, C.byref(n)))
         return n.value
+
+    def reference_lengths(self):
+        """The header's reference lengths in dictionary-id order (BAM, SAM, CRAM; a SAM @SQ without LN gives 0), as dictionary(2)
+        gives the names (exon_hip_scan_reference_lengths)."""
+        n = C.c_int32()
+        self._check(self.lib.exon_hip_scan_reference_lengths(self.h, None, 0, C.byref(n)))
+        out = np.zeros(max(n.value, 1), np.int64)
+        self._check(self.lib.exon_hip_scan_reference_lengths(self.h, out.ctypes.data, n.value, C.byref(n)))
+        return [int(x) for x in out[:n.value]]
 
     def index_chunks(self):
         n = C.c_int32()
@@ -1331,6 +1354,53 @@ class RegionBasesPlan(RegionSetPlan):
     totals / Ns / Ss / Ne / Se sections and the word count, decode() the covered bases of every region."""
 
     _CREATE, _LAYOUT, _LAYOUT_WORDS, _DECODE = "exon_hip_plan_create_region_set_bases", "exon_hip_region_bases_layout", 6, "exon_hip_region_bases_decode"
+
+
+class WindowBasesPlan(RegionSetPlan):
+    """Plan kind 13 (exon_hip_plan_create_window_bases).  ctx None: a host-only plan that serves layout(), offsets() and decode() and
+    cannot be launched.  layout() gives the word offsets of the totals / E / D sections and the word count, offsets() the windows in
+    front of each contig and their total B, decode() the bases of every window, contig by contig."""
+
+    _LAYOUT, _LAYOUT_WORDS, _DECODE = "exon_hip_window_bases_layout", 4, "exon_hip_window_bases_decode"
+
+    def __init__(self, ctx, contigs, window, columns=(2, 3, 4)):
+        self.ctx = ctx
+        self.lib = ctx.lib if ctx is not None else L.load()
+        contigs = [(c, int(n)) for (c, n) in contigs]
+        by_name = [isinstance(c, (str, bytes)) for c, _ in contigs]
+        if any(by_name) and not all(by_name):
+            raise ValueError("a window plan names its contigs either all by name or all by reference id")
+        self.by_name = bool(contigs) and by_name[0]
+        self.contigs, self.window = contigs, int(window)
+        self.n_cols = 3
+        m = len(contigs)
+        lengths = np.array([n for _, n in contigs], np.int64)
+        packed, ids = None, None
+        if self.by_name:
+            packed = b"".join((c if isinstance(c, bytes) else c.encode()) + b"\0" for c, _ in contigs)
+        else:
+            ids = np.array([c for c, _ in contigs], np.int32)
+        h = C.c_void_p()
+        self._check(self.lib.exon_hip_plan_create_window_bases(ctx.h if ctx is not None else None, (C.c_int32 * 3)(*columns), packed, len(packed) if packed else 0,
+                                                               ids.ctypes.data if ids is not None and m else None, lengths.ctypes.data if m else None, m,
+                                                               self.window, C.byref(h)))
+        self.h = h
+        a, b = C.c_int64(), C.c_int64()
+        self._check(self.lib.exon_hip_plan_state_size(h, C.byref(a), C.byref(b)))
+        self.n_i64, self.n_f64 = a.value, b.value
+
+    def offsets(self):
+        out = np.zeros(len(self.contigs) + 1, np.int64)
+        self._check(self.lib.exon_hip_window_bases_offsets(self.h, out.ctypes.data))
+        return out
+
+    def decode(self, state):
+        state = np.ascontiguousarray(state, np.int64)
+        if state.size != self.n_i64:
+            raise ValueError("the state of this plan has %d words, %d given" % (self.n_i64, state.size))
+        out = np.zeros((self.n_i64 - 4) // 2, np.int64)
+        self._check(self.lib.exon_hip_window_bases_decode(self.h, state.ctypes.data, out.ctypes.data))
+        return out
 
 
 class Stream:

@@ -455,6 +455,59 @@ int exon_hip_region_bases_decode(const exon_hip_plan* plan, const int64_t* state
 int exon_hip_region_set_bases(exon_hip_ctx* ctx, void* stream, const exon_hip_column* ref_id /*i32*/, const exon_hip_column* start /*i64*/,
                               const exon_hip_column* end /*i64*/, int64_t n, const exon_hip_plan* plan, int64_t* d_state);
 
+/* ---- K13: bases per fixed-width window along each contig in one pass (plan kind 13) -------------------------------------------------
+ * The depth question without a BED file -- what `mosdepth --by W`, `bedtools makewindows | bedtools coverage` and every coverage
+ * track compute; mean depth is bases / window length.  Inputs are K6 / K11 / K12's three columns, 1-based inclusive.  The plan holds
+ * a window width W >= 1 and C >= 1 contigs of lengths 1 <= L_c <= 2^31 - 1 (BAM's own limit).  Contig c has K_c = ceil(L_c / W)
+ * windows, window j = [j * W + 1, min((j + 1) * W, L_c)]; B = sum of K_c, woff[c] = windows in front of contig c.  B may be at most
+ * EXON_HIP_WINDOW_MAX_BINS (a state of 512 MiB); more is EXON_HIP_EUNSUPPORTED.  bases_j is the sum over the counted rows [s, e] of
+ * the bases of the row inside window j.  The row classes and the four totals are exactly kind 11's.
+ * DECISIONS: a counted row is CLIPPED to [1, L_c]; a counted row with s > L_c or e < 1 stays `counted` and adds to no window.
+ *
+ * Every row is visited once and the window of a coordinate is a division, not a search.  With js = (s - 1) / W and je = (e - 1) / W
+ * of the clipped row:
+ *     js == je:      E[js] += e - s + 1
+ *     otherwise:     E[js] += (js + 1) * W - s + 1,   E[je] += e - je * W
+ *     je > js + 1:   D[js + 1] += 1,   D[je] -= 1
+ * and per contig  bases_j = E[j] + W * (D[0] + ... + D[j])  (DESIGN.md 3.7): a window strictly between two others is never a contig's
+ * short last window.  ARITHMETIC IS MODULO 2^64, as kind 12's; the -1 is an add of 2^64 - 1.
+ *
+ * What it does not compute: the alignment span [start, end] counts as covered, deletions and reference skips included -- there is no
+ * CIGAR-aware split; there is no per-base track, only the sum per window (W = 1 gives one, at 16 bytes a base); a BED source is not
+ * served.
+ *
+ * exon_hip_plan_create_window_bases names its contigs by kind 11 / 12's rules and error classes: ids form (packed_contig_names NULL;
+ * a negative id is EXON_HIP_EINVAL, one of EXON_HIP_MAX_REFERENCES or more EXON_HIP_EUNSUPPORTED) or names form (n_contigs
+ * '\0'-terminated names; an empty name or too few names is EXON_HIP_EINVAL; resolved per consumed scan; exon_hip_stream_push,
+ * exon_hip_stream_push_device, exon_hip_plan_launch and the bare operator are EXON_HIP_ESTATE).  A contig given twice, window < 1,
+ * n_contigs < 1 and a length outside [1, 2^31 - 1] are EXON_HIP_EINVAL.  ctx may be NULL: a host-only plan for the three helpers
+ * below and exon_hip_plan_state_size.  exon_hip_plan_create with kind 13 is EXON_HIP_EINVAL and names this constructor.  Kind 11 /
+ * 12's helpers refuse a kind-13 plan and these refuse kinds 11 / 12.
+ *
+ * State: 4 + 2 * B int64 words, n_f64 = 0: totals[4] (counted, null_rows, elsewhere, inverted), E[B], D[B]; contig c (in the caller's
+ * order) owns bins [woff[c], woff[c + 1]) of E and of D.  Every word adds (modulo 2^64), so streams, chunked launches,
+ * exon_hip_plan_fold_states, exon_hip_stream_all_reduce and the file pipelines carry it like kind 11's and 12's.
+ *
+ * Plans with B <= 8192 add in LDS; larger ones add to the state with global atomics.  The columns' values need their element's
+ * alignment only (4 / 8 / 8 bytes).  finish_arrow: contig (Int32, or Utf8 in the names form), start, end (Int64, 1-based closed),
+ * bases (Int64), one row per window in contig order, then window order. */
+#define EXON_HIP_PLAN_WINDOW_BASES 13
+#define EXON_HIP_WINDOW_MAX_BINS 33554432
+int exon_hip_plan_create_window_bases(exon_hip_ctx* ctx, const int32_t* columns /*[3]*/,
+                                      const char* packed_contig_names /* n_contigs '\0'-terminated names, or NULL */, size_t packed_bytes,
+                                      const int32_t* ref_ids /* used when names are NULL */, const int64_t* lengths, int32_t n_contigs,
+                                      int64_t window, exon_hip_plan** out);
+/* host only: out = word offsets of totals, E, D, and the word count */
+int exon_hip_window_bases_layout(const exon_hip_plan* plan, int64_t* out /*[4]*/);
+/* host only: woff[c] = windows in front of contig c; woff[C] = B */
+int exon_hip_window_bases_offsets(const exon_hip_plan* plan, int64_t* woff /*[C + 1]*/);
+/* host only: the state's words -> the bases of every window, contig by contig.  Linear modulo 2^64: decoded partial states add up to
+ * the decoded merged state. */
+int exon_hip_window_bases_decode(const exon_hip_plan* plan, const int64_t* state, int64_t* out_bases /*[B]*/);
+/* K13, bare operator (ids form; `ctx` is the plan's): d_state (exon_hip_plan_state_size words) += this batch */
+int exon_hip_window_bases(exon_hip_ctx* ctx, void* stream, const exon_hip_column* ref_id /*i32*/, const exon_hip_column* start /*i64*/,
+                          const exon_hip_column* end /*i64*/, int64_t n, const exon_hip_plan* plan, int64_t* d_state);
+
 /* Stateless form of a push: run the plan's fused kernel over HBM-resident columns (`columns[i]` = operator argument i, see
  * exon_hip_plan_desc.columns for the order; n_columns must match the plan) on the caller's hipStream_t into a caller-owned
  * packed partial state [n_i64 x int64][n_f64 x float64] (exon_hip_plan_state_size; 8-byte aligned device memory).
@@ -727,6 +780,10 @@ int exon_hip_scan_dictionary_size(exon_hip_scan* scan, int32_t column, int32_t* 
 int exon_hip_scan_dictionary_intern(exon_hip_scan* scan, int32_t column, const char* name, int32_t* id);
 int exon_hip_scan_dictionary_value(exon_hip_scan* scan, int32_t column, int32_t id, const char** name);
 int exon_hip_scan_rows(exon_hip_scan* scan, int64_t* rows_emitted);
+/* the reference lengths of a BAM, SAM or CRAM header in dictionary-id order (the order of exon_hip_scan_dictionary_value on the
+ * reference column), with the host and with the GPU decoders alike: *n = their number, and the first min(*n, cap) go to out (out may
+ * be NULL when cap is 0).  A SAM @SQ line without LN reports 0.  Any other format: EXON_HIP_EUNSUPPORTED. */
+int exon_hip_scan_reference_lengths(exon_hip_scan* scan, int64_t* out, int32_t cap, int32_t* n);
 /* (round 5, additive) Batches of a scan opened with gpu_parse = 1 come out of the GPU decode pipeline on `ctx`: after this
  * call exon_hip_scan_next drives the same slab pipeline exon_hip_stream_consume_scan drives (file bytes to HBM, BGZF inflate,
  * record parse, pushed-down region mask on the device), copies every slab's columns back and returns them as batch_size-row

@@ -35,6 +35,8 @@ pub const EXON_HIP_PLAN_SEQ_STATS_HIST: i32 = 10; // lmax, column (sequence); st
 pub const EXON_HIP_PLAN_REGION_SET_OVERLAP: i32 = 11; // made by exon_hip_plan_create_region_set; state = 4 + 2 * (M + C) words, all add
 pub const EXON_HIP_REGION_SET_MAX_REGIONS: i32 = 1048576;
 pub const EXON_HIP_PLAN_REGION_SET_BASES: i32 = 12; // made by exon_hip_plan_create_region_set_bases; state = 4 + 4 * (P + C) words, all add modulo 2^64
+pub const EXON_HIP_PLAN_WINDOW_BASES: i32 = 13; // made by exon_hip_plan_create_window_bases; state = 4 + 2 * B words, all add modulo 2^64
+pub const EXON_HIP_WINDOW_MAX_BINS: i32 = 33554432;
 pub const EXON_HIP_GT: i32 = 0;
 pub const EXON_HIP_GE: i32 = 1;
 pub const EXON_HIP_LT: i32 = 2;
@@ -168,6 +170,18 @@ extern "C" {
     pub fn exon_hip_region_bases_decode(plan: *const exon_hip_plan, state: *const i64, out_bases: *mut i64) -> c_int;
     /// K12 (bare operator, ids form): covered bases of every region of the plan's set over one batch; accumulates
     pub fn exon_hip_region_set_bases(ctx: *mut exon_hip_ctx, stream: *mut c_void, ref_id: *const exon_hip_column, start: *const exon_hip_column, end: *const exon_hip_column, n: i64, plan: *const exon_hip_plan, d_state: *mut i64) -> c_int;
+    /// K13: the plan of the bases per window of width `window` along each contig; contigs by id or by name as kind 11's, each once
+    pub fn exon_hip_plan_create_window_bases(ctx: *mut exon_hip_ctx, columns: *const i32, packed_contig_names: *const c_char, packed_bytes: usize, ref_ids: *const i32, lengths: *const i64, n_contigs: i32, window: i64, out: *mut *mut exon_hip_plan) -> c_int;
+    /// host-only: word offsets of K13's totals / E / D sections and the state's size (out[4])
+    pub fn exon_hip_window_bases_layout(plan: *const exon_hip_plan, out: *mut i64) -> c_int;
+    /// host-only: the windows in front of each contig, then their total B (woff[C + 1])
+    pub fn exon_hip_window_bases_offsets(plan: *const exon_hip_plan, woff: *mut i64) -> c_int;
+    /// host-only: K13's state words -> the bases of every window, contig by contig; linear in the state modulo 2^64
+    pub fn exon_hip_window_bases_decode(plan: *const exon_hip_plan, state: *const i64, out_bases: *mut i64) -> c_int;
+    /// K13 (bare operator, ids form): bases per window over one batch; accumulates
+    pub fn exon_hip_window_bases(ctx: *mut exon_hip_ctx, stream: *mut c_void, ref_id: *const exon_hip_column, start: *const exon_hip_column, end: *const exon_hip_column, n: i64, plan: *const exon_hip_plan, d_state: *mut i64) -> c_int;
+    /// the reference lengths of a BAM / SAM / CRAM header in dictionary-id order: *n of them, the first min(*n, cap) into out
+    pub fn exon_hip_scan_reference_lengths(scan: *mut exon_hip_scan, out: *mut i64, cap: i32, n: *mut i32) -> c_int;
     /// fold of `world` packed states by the plan's own layout (add; unsigned max for K8's extreme planes)
     pub fn exon_hip_plan_fold_states(plan: *const exon_hip_plan, stream: *mut c_void, d_gathered: *const c_void, world: i32, d_out: *mut c_void) -> c_int;
     pub fn exon_hip_stream_open(plan: *mut exon_hip_plan, partition: i32, out: *mut *mut exon_hip_stream) -> c_int;
