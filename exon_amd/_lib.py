@@ -172,6 +172,11 @@ REGION_BASES_LDS_MAX = 4096  # kernels.h: sets with P + C up to this are searche
 PLAN_WINDOW_BASES = 13
 WINDOW_BASES_LDS_MAX = 8192  # kernels.h: plans with B windows up to this add in LDS (16 B a window: 128 KiB)
 WINDOW_MAX_BINS = 1 << 25
+PLAN_REGION_SET_DEPTH = 14
+REGION_DEPTH_LDS_MAX = 8192  # kernels.h: plans with T + C bins up to this add in LDS (8 B a bin, the interval table beside them if both fit 128 KiB)
+REGION_DEPTH_REDUCE_TILE = 256  # kernels.h: bins per tile of the reduce's running sum (one wave, 4 bins a lane)
+REGION_DEPTH_MAX_BINS = 1 << 26
+REGION_DEPTH_MAX_THRESHOLDS = 8
 LAUNCH_ACCUMULATE = 0
 LAUNCH_OVERWRITE = 1
 CMP = {">": 0, ">=": 1, "<": 2, "<=": 3, "=": 4, "==": 4, "!=": 5, "<>": 5}
@@ -235,6 +240,13 @@ SIGNATURES = {
     "exon_hip_window_bases_offsets": (C.c_int, [_vp, _vp]),
     "exon_hip_window_bases_decode": (C.c_int, [_vp, _vp, _vp]),
     "exon_hip_window_bases": (C.c_int, [_vp, _vp, _colp, _colp, _colp, _i64, _vp, _vp]),
+    "exon_hip_plan_create_region_set_depth": (C.c_int, [_vp, C.POINTER(_i32), C.c_char_p, C.c_size_t, _vp, _vp, _vp, _i32, _vp, _i32, C.POINTER(_vp)]),
+    "exon_hip_region_depth_layout": (C.c_int, [_vp, C.POINTER(_i64)]),
+    "exon_hip_region_depth_intervals": (C.c_int, [_vp, C.POINTER(_i32), _vp, _vp, _vp, _vp]),
+    "exon_hip_region_depth_per_base": (C.c_int, [_vp, _vp, _vp]),
+    "exon_hip_region_depth_decode": (C.c_int, [_vp, _vp, _vp]),
+    "exon_hip_region_depth_reduce": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
+    "exon_hip_region_set_depth": (C.c_int, [_vp, _vp, _colp, _colp, _colp, _i64, _vp, _vp]),
     "exon_hip_rccl_unique_id": (C.c_int, [_vp]),
     "exon_hip_rccl_comm_init": (C.c_int, [_vp, _vp, _i32, _i32, C.POINTER(_vp)]),
     "exon_hip_rccl_comm_destroy": (C.c_int, [_vp]),

@@ -606,7 +606,7 @@ int exon_op_seq_stats_hist_views(exon_hip_ctx* ctx, void* stream, const exon_hip
   return EXON_HIP_OK;
 }
 
-// K11 / K12 / K13 (region_set.hip, region_bases.hip, window_bases.hip): the tables are the plan's (stream.cpp).  Column bases need their element's alignment
+// K11 - K14 (region_set.hip, region_bases.hip, window_bases.hip, region_depth.hip): the tables are the plan's (stream.cpp).  Column bases need their element's alignment
 // only.  launch(s, ws) starts the kernel over the checked columns and reports as every operator does (HIP_TRY names the call).
 template <typename Launch>
 static int region_set_op(exon_hip_ctx* ctx, void* stream, const char* who, const exon_hip_column* ref_id, const exon_hip_column* start, const exon_hip_column* end,
@@ -661,6 +661,31 @@ int exon_op_window_bases(exon_hip_ctx* ctx, void* stream, const exon_hip_column*
                                                                 n, t, d_state));
                          return (int)EXON_HIP_OK;
                        });
+}
+
+int exon_op_region_set_depth(exon_hip_ctx* ctx, void* stream, const exon_hip_column* ref_id, const exon_hip_column* start, const exon_hip_column* end, int64_t n,
+                             const exon::RegionDepthTables& t, int64_t* d_state, int flags) {
+  return region_set_op(ctx, stream, "exon_hip_region_set_depth", ref_id, start, end, n, (size_t)exon::region_depth_words(t.NB) * 8,
+                       t.map && t.ioff && t.doff && t.ms && t.cl, d_state, flags, [&](hipStream_t s, const Workspace& ws) {
+                         HIP_TRY(ctx, exon::launch_region_set_depth(s, cfg_for(ctx, flags), reinterpret_cast<const uint8_t*>(ws.status + 8), (const int32_t*)ref_id->values,
+                                                                    ref_id->validity, (const int64_t*)start->values, start->validity, (const int64_t*)end->values,
+                                                                    end->validity, n, t, d_state));
+                         return (int)EXON_HIP_OK;
+                       });
+}
+
+// K14's reduce (region_depth.hip): the tile sums and offsets live in the stream's workspace
+int exon_op_region_depth_reduce(exon_hip_ctx* ctx, void* stream, const exon::RegionDepthReduce& r, const int64_t* d_state, int64_t* d_out) {
+  const char* who = "exon_hip_region_depth_reduce";
+  if (!ctx || !d_state || !d_out) return fail(ctx, EXON_HIP_EINVAL, "%s: NULL argument", who);
+  if ((reinterpret_cast<uintptr_t>(d_state) | reinterpret_cast<uintptr_t>(d_out)) & 7) return fail(ctx, EXON_HIP_EINVAL, "%s: d_state and d_out must be 8-byte aligned", who);
+  if (!r.pfx || !r.lo || !r.hi) return fail(ctx, EXON_HIP_ESTATE, "%s: the plan has no device tables", who);
+  hipStream_t s = pick_stream(ctx, stream);
+  Workspace ws;
+  int rc;
+  if ((rc = get_workspace(ctx, s, 2 * (size_t)exon::region_depth_reduce_tiles(r.NB), &ws))) return fail(ctx, rc, "workspace allocation failed");
+  HIP_TRY(ctx, exon::launch_region_depth_reduce(s, cfg_for(ctx, 0), r, d_state, ws.partials, d_out));
+  return EXON_HIP_OK;
 }
 
 extern "C" {

@@ -24,6 +24,7 @@
 //   SELECT COUNT(*) FROM <bam table> WHERE bam_region_filter('<r>', reference, start, end)          -- K6 (plain table; INDEXED_BAM plans chunks on the host)
 //   SELECT * FROM overlap_counts('<bam|sam|cram|gff|gtf file>', '<regions.bed>'[, 'gzip'])       -- K11: one row per BED line, in file order
 //   SELECT * FROM covered_bases('<bam|sam|cram|gff|gtf file>', '<regions.bed>'[, 'gzip'])        -- K12: the rows' bases inside each BED line
+//   SELECT * FROM depth_thresholds('<bam|sam|cram|gff|gtf file>', '<regions.bed>', '<T1,T2,...>'[, 'gzip'])  -- K14: per BED line its bases and how many are covered >= T times
 //   SELECT * FROM window_depth('<bam|sam|cram file>', <W>[, '<genome file>'])                     -- K13: the rows' bases per window of width W along every contig
 //   DROP TABLE t;
 #include <dirent.h>
@@ -31,6 +32,7 @@
 
 #include <algorithm>
 #include <cctype>
+#include <cerrno>
 #include <climits>
 #include <cmath>
 #include <cstdio>
@@ -148,6 +150,8 @@ struct Source {  // resolved FROM clause
   int n_fields = 12;  // BED
   std::string regions_bed;  // overlap_counts / covered_bases: the BED file of the region set
   bool bases = false;       // covered_bases: K12's sums instead of K11's counts
+  bool depth = false;       // depth_thresholds: K14's bases and threshold counts
+  std::vector<int64_t> thresholds;  // depth_thresholds: strictly increasing, each >= 1, at most 8
   int64_t window = 0;       // window_depth: the window width (0: another source)
   std::string genome_file;  // window_depth: contigs and lengths from a bedtools genome file / .fai instead of the file's header
 };
@@ -436,9 +440,9 @@ Source resolve_from(Session& se, Parser& ps) {
   Source src;
   const std::string name = ps.ident();
   const std::string lname = lower(name);
-  if (ps.accept_sym("(")) {  // table function: <fmt>_scan / <fmt>_indexed_scan / fastq_quality_histogram / fastq_read_stats / fasta_seq_stats / overlap_counts / covered_bases / window_depth
+  if (ps.accept_sym("(")) {  // table function: <fmt>_scan / <fmt>_indexed_scan / fastq_quality_histogram / fastq_read_stats / fasta_seq_stats / overlap_counts / covered_bases / depth_thresholds / window_depth
     const std::string path = ps.str();
-    if (lname == "overlap_counts" || lname == "covered_bases" || lname == "window_depth") {  // the source's format by its extension
+    if (lname == "overlap_counts" || lname == "covered_bases" || lname == "depth_thresholds" || lname == "window_depth") {  // the source's format by its extension
       ps.expect_sym(",");
       if (lname == "window_depth") {  // ('<file>', <W>[, '<genome file>'])
         const std::string w = ps.number();
@@ -450,6 +454,23 @@ Source resolve_from(Session& se, Parser& ps) {
       } else {  // ('<file>', '<regions.bed>'[, '<compression>'])
         src.regions_bed = ps.str();
         src.bases = lname == "covered_bases";
+        src.depth = lname == "depth_thresholds";
+        if (src.depth) {  // ('<file>', '<regions.bed>', '<T1,T2,...>'[, '<compression>'])
+          ps.expect_sym(",");
+          const std::string list = ps.str();
+          const Err bad("depth_thresholds: the thresholds are whole numbers >= 1 in strictly increasing order, at most " +
+                        std::to_string(EXON_HIP_REGION_DEPTH_MAX_THRESHOLDS) + " of them, separated by commas; got '" + list + "'");
+          std::istringstream ts(list);
+          for (std::string item; std::getline(ts, item, ',');) {
+            char* endp = nullptr;
+            errno = 0;
+            const long long t = strtoll(item.c_str(), &endp, 10);
+            while (*endp == ' ') ++endp;
+            if (item.empty() || endp == item.c_str() || *endp || errno || t < 1 || (!src.thresholds.empty() && t <= src.thresholds.back())) throw bad;
+            src.thresholds.push_back(t);
+          }
+          if (src.thresholds.empty() || src.thresholds.size() > EXON_HIP_REGION_DEPTH_MAX_THRESHOLDS || (!list.empty() && list.back() == ',')) throw bad;
+        }
         if (ps.accept_sym(",")) src.compression = compression_of(ps.str());
       }
       ps.expect_sym(")");
@@ -687,7 +708,7 @@ void exec_select(Session& se, Parser& ps) {
     return;
   }
 
-  if (!src.regions_bed.empty()) {  // K11 / K12: every region of the BED file over the source in ONE pass; the names are resolved per file
+  if (!src.regions_bed.empty()) {  // K11 / K12 / K14: every region of the BED file over the source in ONE pass; the names are resolved per file
     std::ifstream in(src.regions_bed);
     if (!in) throw Err("no such file: " + src.regions_bed);
     std::vector<std::string> names;
@@ -713,8 +734,12 @@ void exec_select(Session& se, Parser& ps) {
     const bool annotation = src.format == EXON_HIP_FORMAT_GFF || src.format == EXON_HIP_FORMAT_GTF;
     const int32_t columns[3] = {annotation ? 0 : 2, 3, 4};
     StreamGuard sg;
-    ck(ctx, (src.bases ? exon_hip_plan_create_region_set_bases : exon_hip_plan_create_region_set)(ctx, columns, packed.data(), packed.size(), nullptr, starts.data(),
-                                                                                                   ends.data(), (int32_t)names.size(), &sg.p));
+    if (src.depth)
+      ck(ctx, exon_hip_plan_create_region_set_depth(ctx, columns, packed.data(), packed.size(), nullptr, starts.data(), ends.data(), (int32_t)names.size(),
+                                                    src.thresholds.data(), (int32_t)src.thresholds.size(), &sg.p));
+    else
+      ck(ctx, (src.bases ? exon_hip_plan_create_region_set_bases : exon_hip_plan_create_region_set)(ctx, columns, packed.data(), packed.size(), nullptr, starts.data(),
+                                                                                                     ends.data(), (int32_t)names.size(), &sg.p));
     ck(ctx, exon_hip_stream_open(sg.p, 0, &sg.s));
     for (const auto& f : src.files) {  // one stream: the state is keyed by the region set, the files add up
       ScanGuard g; open_scan(src, f, nullptr, "", &g, true);
@@ -724,6 +749,20 @@ void exec_select(Session& se, Parser& ps) {
     ck(ctx, exon_hip_plan_state_size(sg.p, &n_i64, &n_f64));
     std::vector<int64_t> state((size_t)n_i64), counts(names.size());
     ck(ctx, exon_hip_stream_finish(sg.s, state.data(), nullptr));
+    if (src.depth) {  // one row per BED line: bases, then the bases covered at least T times for every threshold
+      const size_t w = 1 + src.thresholds.size();
+      std::vector<int64_t> tab(names.size() * w);
+      ck(ctx, exon_hip_region_depth_decode(sg.p, state.data(), tab.data()));
+      std::vector<std::string> head = {"contig", "start", "end", "bases"};
+      for (int64_t t : src.thresholds) head.push_back("ge_" + std::to_string(t));
+      std::vector<std::vector<std::string>> rows;
+      for (size_t i = 0; i < names.size(); ++i) {
+        rows.push_back({names[i], std::to_string(starts[i]), std::to_string(ends[i])});
+        for (size_t c = 0; c < w; ++c) rows.back().push_back(std::to_string(tab[i * w + c]));
+      }
+      print_table(head, rows, se.quiet);
+      return;
+    }
     ck(ctx, (src.bases ? exon_hip_region_bases_decode : exon_hip_region_set_decode)(sg.p, state.data(), counts.data()));
     std::vector<std::vector<std::string>> rows;
     for (size_t i = 0; i < names.size(); ++i) rows.push_back({names[i], std::to_string(starts[i]), std::to_string(ends[i]), std::to_string(counts[i])});
@@ -1175,6 +1214,7 @@ int main(int argc, char** argv) {
              "             fasta_seq_stats('<path>'[, 'gzip'])\n"
              "             overlap_counts('<bam|sam|cram|gff|gtf file>', '<regions.bed>'[, 'gzip'])   one row per BED line: contig, start, end (1-based closed), count\n"
              "             covered_bases('<bam|sam|cram|gff|gtf file>', '<regions.bed>'[, 'gzip'])    one row per BED line: contig, start, end (1-based closed), bases\n"
+             "             depth_thresholds('<bam|sam|cram|gff|gtf file>', '<regions.bed>', '<T1,T2,...>'[, 'gzip'])  one row per BED line: contig, start, end, bases, ge_<T> = its bases covered at least T times\n"
              "             window_depth('<bam|sam|cram file>', <W>)                                   one row per window of width W along every contig of the header: contig, start, end, bases\n"
              "             window_depth('<bam|sam|cram|gff|gtf file>', <W>, '<genome file>')          the contigs and lengths from `name<TAB>length` lines (a bedtools genome file, a .fai)\n"
              "  queries:  SELECT COUNT(*) FROM <src> [WHERE chrom = 'c' AND pos >= a AND pos <= b | vcf_region_filter('r', chrom) | bam_region_filter('r', reference, start, end)\n"

@@ -249,6 +249,9 @@ int exon_op_region_set_bases(exon_hip_ctx* ctx, void* stream, const exon_hip_col
                              int64_t n, const exon::RegionBasesTables& tables, int64_t* d_state, int flags);
 int exon_op_window_bases(exon_hip_ctx* ctx, void* stream, const exon_hip_column* ref_id, const exon_hip_column* start, const exon_hip_column* end, int64_t n,
                          const exon::WindowBasesTables& tables, int64_t* d_state, int flags);
+int exon_op_region_set_depth(exon_hip_ctx* ctx, void* stream, const exon_hip_column* ref_id, const exon_hip_column* start, const exon_hip_column* end, int64_t n,
+                             const exon::RegionDepthTables& tables, int64_t* d_state, int flags);
+int exon_op_region_depth_reduce(exon_hip_ctx* ctx, void* stream, const exon::RegionDepthReduce& r, const int64_t* d_state, int64_t* d_out);
 // chunk c is q[c * stride]
 int exon_op_qual_pos_hist_chunks(exon_hip_ctx* ctx, void* stream, const exon_hip_column* q, int stride, int32_t n_chunks,
                                  const int64_t* n_reads, int32_t lmax, int64_t* d_hist, int flags);

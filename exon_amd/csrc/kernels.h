@@ -186,6 +186,53 @@ hipError_t launch_window_bases(hipStream_t s, const LaunchCfg& cfg, const uint8_
                                const int64_t* start, const uint8_t* start_valid, const int64_t* end, const uint8_t* end_valid, int64_t n,
                                const WindowBasesTables& t, int64_t* d_state);
 
+// K14 (region_depth.hip): the per-base depth over the bases a region set covers, in one pass; state [counted, null_rows, elsewhere,
+// inverted] [D: T + C], every word modulo 2^64 (include/exon_hip.h, exon_hip_region_depth_layout).  Device tables: map[n_map] as K11's,
+// ioff[C + 1] = merged intervals in front of each contig, doff[C] = first bin of each contig, ms[I] = interval starts ascending within
+// a contig, cl[I] = { target bases of the contig in front of the interval, the interval's own }.  A counted row takes one
+// count_below<true> per endpoint and adds +1 / -1 to two bins of D.  Plans with NB = T + C <= REGION_DEPTH_LDS_MAX keep the bins in
+// LDS as u64 (64 KiB at the bound; 64 bits for K13's reason), and the interval table (16 B an interval) beside them when both fit
+// REGION_DEPTH_LDS_MAX * 16 bytes = 128 KiB, K12's and K13's figure -- sets of one- and two-base targets have nearly an interval a
+// bin and read the table through L2 instead.  Larger plans search through L2 and add to the state with global 64-bit atomics.  The
+// row walk, the tiles and `ones` are K11's.  cfg.overwrite: state := this launch.
+constexpr int REGION_DEPTH_LDS_MAX = 8192;
+constexpr int64_t REGION_DEPTH_MAX_BINS = (int64_t)1 << 26;
+constexpr int REGION_DEPTH_MAX_THRESHOLDS = 8;
+constexpr int64_t region_depth_words(int64_t NB) { return 4 + NB; }
+// 0: global atomics; 1: bins in LDS, table through L2; 2: bins and table in LDS
+constexpr int region_depth_tier(int64_t NB, int64_t I) {
+  return NB > REGION_DEPTH_LDS_MAX ? 0 : NB * 8 + I * 16 > (int64_t)REGION_DEPTH_LDS_MAX * 16 ? 1 : 2;
+}
+struct RegionDepthTables {
+  const int32_t* map;
+  int32_t n_map;
+  const int32_t* ioff;
+  const int32_t* doff;
+  const int64_t* ms;
+  const int2* cl;
+  int32_t I, C, NB;
+};
+hipError_t launch_region_set_depth(hipStream_t s, const LaunchCfg& cfg, const uint8_t* ones, const int32_t* ref, const uint8_t* ref_valid,
+                                   const int64_t* start, const uint8_t* start_valid, const int64_t* end, const uint8_t* end_valid, int64_t n,
+                                   const RegionDepthTables& t, int64_t* d_state);
+// K14's reduce: d_out[M][1 + k] = { bases_i, ge_t ... } from a state, word for word what host/region_depth.h's decode gives.  The
+// running sum of D is taken over the whole section as one array, in tiles of REGION_DEPTH_REDUCE_TILE bins (a wave, 4 bins a lane):
+// per-tile sums, one workgroup scans them, then one wave per piece (region x tile) rebuilds the tile's running sum from its offset and
+// adds what the region's bins give to d_out.  pfx[M + 1] = pieces in front of each region (the plan's), lo / hi [M] = a region's bins.
+// scratch: 2 * region_depth_reduce_tiles(NB) words.  d_state is only read.
+constexpr int REGION_DEPTH_REDUCE_TILE = 256;
+constexpr int64_t region_depth_reduce_tiles(int64_t NB) { return (NB + REGION_DEPTH_REDUCE_TILE - 1) / REGION_DEPTH_REDUCE_TILE; }
+struct RegionDepthReduce {
+  const int64_t* pfx;
+  const int32_t* lo;
+  const int32_t* hi;
+  int64_t n_pieces;
+  int32_t M, NB, k;
+  int64_t thr[REGION_DEPTH_MAX_THRESHOLDS];
+};
+hipError_t launch_region_depth_reduce(hipStream_t s, const LaunchCfg& cfg, const RegionDepthReduce& r, const int64_t* d_state, unsigned long long* scratch,
+                                      int64_t* d_out);
+
 // pushed-down region filter as a row mask: out_valid = in_valid AND (row hits the region); *n_pass += rows kept.
 // point form (VCF): id_col = chrom id, start = pos; range form (BAM): id_col = reference id, [start, end].
 hipError_t launch_region_mask(hipStream_t s, bool range_form, const int32_t* id_col, const uint8_t* id_valid, const int64_t* start,

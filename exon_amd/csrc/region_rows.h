@@ -1,4 +1,4 @@
-// region_rows.h -- the row walk that the region-set kernels share (K11 region_set.hip, K12 region_bases.hip, K13 window_bases.hip): how a kernel gets from
+// region_rows.h -- the row walk that the region-set kernels share (K11 region_set.hip, K12 region_bases.hip, K13 window_bases.hip, K14 region_depth.hip): how a kernel gets from
 // the three interval columns to "this row is on contig slot c with coordinates [s, e]", and how the host cuts the rows into launches.
 // What a row then ADDS is the including kernel's business: it hands walk() a functor.  Included by .hip files only.
 //

@@ -34,6 +34,7 @@
 #include "host/bitmap.h"
 #include "host/raw_batch.h"
 #include "host/region_bases.h"
+#include "host/region_depth.h"
 #include "host/window_bases.h"
 #include "host/region_set.h"
 #include "internal.h"
@@ -85,24 +86,30 @@ struct Slot {
   std::atomic<size_t> pending{0};
 };
 
-// plan kinds 11, 12 and 13: the region set or the windows (host/region_set.h, host/region_bases.h, host/window_bases.h; the plan's kind
-// says which of the three is filled) and its device tables, built once by the plan's constructor and freed with the plan.  A
+// plan kinds 11 to 14: the region set or the windows (host/region_set.h, host/region_bases.h, host/window_bases.h, host/region_depth.h;
+// the plan's kind says which of the four is filled) and its device tables, built once by the plan's constructor and freed with the plan.  A
 // names-form plan has no map of its own: every consumed scan brings one (exon_hip_stream_set_region_set_map).
 struct PlanRegions {
   bool bases = false;    // kind 12
   bool windows = false;  // kind 13
+  bool depth = false;    // kind 14
   exon::RegionSet counts;
   exon::RegionBases covered;
   exon::WindowBases win;
+  exon::RegionDepth dep;
+  int64_t n_pieces = 0;  // kind 14: the reduce's work items, (region x reduce tile) pairs
   int32_t* d_map = nullptr;
   int32_t n_map = 0;
-  void* d_tab[3] = {nullptr, nullptr, nullptr};  // kind 11: off, ends, starts; kind 12: poff, points; kind 13: woff, len
+  // kind 11: off, ends, starts; kind 12: poff, points; kind 13: woff, len; kind 14: ioff, doff, ms, cl, and the reduce's pfx, lo, hi
+  void* d_tab[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
   ~PlanRegions() {
     if (d_map) hipFree(d_map);
     for (void* t : d_tab)
       if (t) hipFree(t);
   }
-  const exon::RegionSetSpec& spec() const { return windows ? static_cast<const exon::RegionSetSpec&>(win) : bases ? static_cast<const exon::RegionSetSpec&>(covered) : counts; }
+  const exon::RegionSetSpec& spec() const {
+    return depth ? static_cast<const exon::RegionSetSpec&>(dep) : windows ? static_cast<const exon::RegionSetSpec&>(win) : bases ? static_cast<const exon::RegionSetSpec&>(covered) : counts;
+  }
   exon::RegionSetTables count_tables(const int32_t* map, int32_t n) const {
     return exon::RegionSetTables{map, n, (const int32_t*)d_tab[0], (const int64_t*)d_tab[1], (const int64_t*)d_tab[2], counts.M, counts.C};
   }
@@ -113,6 +120,14 @@ struct PlanRegions {
     exon::WindowBasesTables t{map, n, (const int32_t*)d_tab[0], (const int32_t*)d_tab[1], (uint32_t)std::min<int64_t>(win.W, INT32_MAX), 0, 0, (int32_t)win.B, win.C};
     exon::window_bases_reciprocal(t.W, &t.mul, &t.shift);
     return t;
+  }
+  exon::RegionDepthTables depth_tables(const int32_t* map, int32_t n) const {
+    return exon::RegionDepthTables{map, n, (const int32_t*)d_tab[0], (const int32_t*)d_tab[1], (const int64_t*)d_tab[2], (const int2*)d_tab[3], dep.I, dep.C, (int32_t)dep.bins()};
+  }
+  exon::RegionDepthReduce depth_reduce() const {
+    exon::RegionDepthReduce r{(const int64_t*)d_tab[4], (const int32_t*)d_tab[5], (const int32_t*)d_tab[6], n_pieces, dep.M, (int32_t)dep.bins(), dep.k(), {0, 0, 0, 0, 0, 0, 0, 0}};
+    std::copy(dep.thresholds.begin(), dep.thresholds.end(), r.thr);
+    return r;
   }
 };
 
@@ -125,8 +140,8 @@ struct exon_hip_plan {
   int64_t n_max = 0;  // the last n_max of the n_i64 words fold by unsigned max, not add (CMP_MINMAX_BY_GROUP: its two extreme planes)
   int n_cols;
   ColSpec cols[4];
-  std::unique_ptr<PlanRegions> rs;  // REGION_SET_OVERLAP, REGION_SET_BASES and WINDOW_BASES only
-  // a region-set or window plan (kind 11, 12 or 13) made from contig names: its ids come from the scan being consumed
+  std::unique_ptr<PlanRegions> rs;  // REGION_SET_OVERLAP, REGION_SET_BASES, WINDOW_BASES and REGION_SET_DEPTH only
+  // a region-set or window plan (kinds 11 to 14) made from contig names: its ids come from the scan being consumed
   bool set_by_name() const { return rs && rs->spec().by_name; }
   const std::vector<std::string>* set_names() const { return set_by_name() ? &rs->spec().contig_names : nullptr; }
 };
@@ -235,6 +250,7 @@ static int run_region_plan(const exon_hip_plan* p, exon_hip_ctx* ctx, void* stre
   if (rs.spec().by_name && !map) return names_form_refusal(ctx, "the rows'");
   if (!rs.spec().by_name) map = rs.d_map, n_map = rs.n_map;
   if (rs.windows) return exon_op_window_bases(ctx, stream, ref_id, start, end, n, rs.window_tables(map, n_map), d_state, flags);
+  if (rs.depth) return exon_op_region_set_depth(ctx, stream, ref_id, start, end, n, rs.depth_tables(map, n_map), d_state, flags);
   return rs.bases ? exon_op_region_set_bases(ctx, stream, ref_id, start, end, n, rs.covered_tables(map, n_map), d_state, flags)
                   : exon_op_region_set_overlap(ctx, stream, ref_id, start, end, n, rs.count_tables(map, n_map), d_state, flags);
 }
@@ -495,6 +511,7 @@ static int run_plan(const exon_hip_plan* p, void* stream, const exon_hip_column*
     case EXON_HIP_PLAN_REGION_SET_OVERLAP:
     case EXON_HIP_PLAN_REGION_SET_BASES:
     case EXON_HIP_PLAN_WINDOW_BASES:
+    case EXON_HIP_PLAN_REGION_SET_DEPTH:
       return run_region_plan(p, ctx, stream, &cols[0], &cols[1], &cols[2], n, rs_map, rs_n_map, counts, flags);
   }
   return fail(ctx, EXON_HIP_EINVAL, "unknown plan kind %d", d.kind);
@@ -649,6 +666,8 @@ int exon_hip_plan_create(exon_hip_ctx* ctx, const exon_hip_plan_desc* desc, exon
     return fail(ctx, EXON_HIP_EINVAL, "plan kind %d takes a region set, which exon_hip_plan_desc cannot hold: use exon_hip_plan_create_region_set_bases", desc->kind);
   if (desc && desc->kind == EXON_HIP_PLAN_WINDOW_BASES)
     return fail(ctx, EXON_HIP_EINVAL, "plan kind %d takes contig lengths and a window width, which exon_hip_plan_desc cannot hold: use exon_hip_plan_create_window_bases", desc->kind);
+  if (desc && desc->kind == EXON_HIP_PLAN_REGION_SET_DEPTH)
+    return fail(ctx, EXON_HIP_EINVAL, "plan kind %d takes a region set and thresholds, which exon_hip_plan_desc cannot hold: use exon_hip_plan_create_region_set_depth", desc->kind);
   if (!ctx || !desc || !out) return fail(ctx, EXON_HIP_EINVAL, "exon_hip_plan_create: NULL argument");
   exon_hip_plan* p = new (std::nothrow) exon_hip_plan();
   if (!p) return fail(ctx, EXON_HIP_ENOMEM, "out of host memory");
@@ -769,10 +788,11 @@ int exon_hip_plan_destroy(exon_hip_plan* plan) {
   return EXON_HIP_OK;
 }
 
-// plan kinds 11 and 12 take the same arguments, by the same rules.  ctx may be NULL: a host-only plan for the kind's _layout / _decode
-// (no device tables, nothing to launch).
+// plan kinds 11, 12 and 14 take the same region arguments, by the same rules; kind 14 adds its thresholds and needs finite ends.  ctx
+// may be NULL: a host-only plan for the kind's _layout / _decode (no device tables, nothing to launch).
 static int create_region_plan(exon_hip_ctx* ctx, const char* who, int kind, const int32_t columns[3], const char* packed_contig_names, size_t packed_bytes,
-                              const int32_t* ref_ids, const int64_t* starts, const int64_t* ends, int32_t n_regions, exon_hip_plan** out) {
+                              const int32_t* ref_ids, const int64_t* starts, const int64_t* ends, int32_t n_regions, exon_hip_plan** out,
+                              const int64_t* thresholds = nullptr, int32_t n_thresholds = 0) {
   if (!out) return fail(ctx, EXON_HIP_EINVAL, "%s: NULL argument", who);
   *out = nullptr;
   if (n_regions < 1) return fail(ctx, EXON_HIP_EINVAL, "%s: n_regions %d: a region set holds at least one region", who, n_regions);
@@ -788,9 +808,33 @@ static int create_region_plan(exon_hip_ctx* ctx, const char* who, int kind, cons
   }
   std::unique_ptr<exon_hip_plan> guard(p);
   rs->bases = kind == EXON_HIP_PLAN_REGION_SET_BASES;
-  exon::RegionSetSpec& set = rs->bases ? static_cast<exon::RegionSetSpec&>(rs->covered) : rs->counts;
+  rs->depth = kind == EXON_HIP_PLAN_REGION_SET_DEPTH;
+  exon::RegionSetSpec& set = rs->depth ? static_cast<exon::RegionSetSpec&>(rs->dep) : rs->bases ? static_cast<exon::RegionSetSpec&>(rs->covered) : rs->counts;
   int32_t max_id = -1;
   if (const int rc = fill_region_set(ctx, who, packed_contig_names, packed_bytes, ref_ids, starts, ends, n_regions, set, &max_id)) return rc;
+  std::vector<int64_t> pfx;  // kind 14: pieces in front of each region
+  if (rs->depth) {
+    static_assert(exon::RegionDepth::MAX_BINS == EXON_HIP_REGION_DEPTH_MAX_BINS && exon::REGION_DEPTH_MAX_BINS == EXON_HIP_REGION_DEPTH_MAX_BINS, "one bound in three headers");
+    static_assert(exon::RegionDepth::MAX_THRESHOLDS == EXON_HIP_REGION_DEPTH_MAX_THRESHOLDS && exon::REGION_DEPTH_MAX_THRESHOLDS == EXON_HIP_REGION_DEPTH_MAX_THRESHOLDS, "one bound in three headers");
+    if (n_thresholds < 0 || n_thresholds > EXON_HIP_REGION_DEPTH_MAX_THRESHOLDS)
+      return fail(ctx, EXON_HIP_EINVAL, "%s: n_thresholds %d outside [0, %d]", who, n_thresholds, EXON_HIP_REGION_DEPTH_MAX_THRESHOLDS);
+    if (n_thresholds > 0 && !thresholds) return fail(ctx, EXON_HIP_EINVAL, "%s: NULL argument", who);
+    for (int32_t t = 0; t < n_thresholds; ++t)
+      if (thresholds[t] < 1 || (t > 0 && thresholds[t] <= thresholds[t - 1]))
+        return fail(ctx, EXON_HIP_EINVAL, "%s: threshold %d: the thresholds are at least 1 and strictly increasing", who, t);
+    for (int32_t i = 0; i < n_regions; ++i)
+      if (ends[i] == EXON_HIP_REGION_OPEN_END)
+        return fail(ctx, EXON_HIP_EUNSUPPORTED, "%s: region %d: an open end has no per-base state; give the contig's length as the end", who, i);
+    exon::RegionDepth& dd = rs->dep;
+    dd.thresholds.assign(thresholds, thresholds + n_thresholds);
+    if (!dd.build())
+      return fail(ctx, EXON_HIP_EUNSUPPORTED, "%s: %lld target bases on %d contigs beyond %lld bins (a state of 512 MiB); kind 13 serves whole genomes", who, (long long)dd.T,
+                  dd.C, (long long)EXON_HIP_REGION_DEPTH_MAX_BINS);
+    pfx.assign((size_t)dd.M + 1, 0);
+    for (int32_t i = 0; i < dd.M; ++i)
+      pfx[(size_t)i + 1] = pfx[(size_t)i] + ((dd.hi[(size_t)i] - 1) / exon::REGION_DEPTH_REDUCE_TILE - dd.lo[(size_t)i] / exon::REGION_DEPTH_REDUCE_TILE + 1);
+    rs->n_pieces = pfx.back();
+  }
   struct Upload {
     void** dst;
     const void* src;
@@ -804,7 +848,20 @@ static int create_region_plan(exon_hip_ctx* ctx, const char* who, int kind, cons
     rs->n_map = (int32_t)map.size();
     up.push_back({(void**)&rs->d_map, map.data(), map.size() * 4});
   }
-  if (rs->bases) {
+  std::vector<int2> cl;
+  if (rs->depth) {
+    exon::RegionDepth& dd = rs->dep;
+    p->n_i64 = dd.words();
+    cl.resize((size_t)dd.I);
+    for (int32_t j = 0; j < dd.I; ++j) cl[(size_t)j] = make_int2(dd.cum[(size_t)j], dd.len[(size_t)j]);
+    up.push_back({&rs->d_tab[0], dd.ioff.data(), dd.ioff.size() * 4});
+    up.push_back({&rs->d_tab[1], dd.doff.data(), dd.doff.size() * 4});
+    up.push_back({&rs->d_tab[2], dd.ms.data(), dd.ms.size() * 8});
+    up.push_back({&rs->d_tab[3], cl.data(), cl.size() * 8});
+    up.push_back({&rs->d_tab[4], pfx.data(), pfx.size() * 8});
+    up.push_back({&rs->d_tab[5], dd.lo.data(), dd.lo.size() * 4});
+    up.push_back({&rs->d_tab[6], dd.hi.data(), dd.hi.size() * 4});
+  } else if (rs->bases) {
     exon::RegionBases& b = rs->covered;
     b.build();
     p->n_i64 = b.words();
@@ -848,6 +905,12 @@ int exon_hip_plan_create_region_set_bases(exon_hip_ctx* ctx, const int32_t colum
                                           const int64_t* starts, const int64_t* ends, int32_t n_regions, exon_hip_plan** out) {
   return create_region_plan(ctx, "exon_hip_plan_create_region_set_bases", EXON_HIP_PLAN_REGION_SET_BASES, columns, packed_contig_names, packed_bytes, ref_ids, starts,
                             ends, n_regions, out);
+}
+
+int exon_hip_plan_create_region_set_depth(exon_hip_ctx* ctx, const int32_t columns[3], const char* packed_contig_names, size_t packed_bytes, const int32_t* ref_ids,
+                                          const int64_t* starts, const int64_t* ends, int32_t n_regions, const int64_t* thresholds, int32_t n_thresholds, exon_hip_plan** out) {
+  return create_region_plan(ctx, "exon_hip_plan_create_region_set_depth", EXON_HIP_PLAN_REGION_SET_DEPTH, columns, packed_contig_names, packed_bytes, ref_ids, starts,
+                            ends, n_regions, out, thresholds, n_thresholds);
 }
 
 // plan kind 13: the contigs by kind 11 / 12's rules (ids form or names form, each contig once), their lengths and the window width.
@@ -924,6 +987,7 @@ int exon_hip_plan_create_window_bases(exon_hip_ctx* ctx, const int32_t columns[3
 static const PlanRegions* region_plan_of(const exon_hip_plan* plan, int kind, const char* who) {
   if (!plan || plan->d.kind != kind || !plan->rs) {
     if (kind == EXON_HIP_PLAN_WINDOW_BASES) fail(plan ? plan->ctx : nullptr, EXON_HIP_EINVAL, "%s: not a window-bases plan (kind %d)", who, kind);
+    else if (kind == EXON_HIP_PLAN_REGION_SET_DEPTH) fail(plan ? plan->ctx : nullptr, EXON_HIP_EINVAL, "%s: not a region-set depth plan (kind %d)", who, kind);
     else fail(plan ? plan->ctx : nullptr, EXON_HIP_EINVAL, "%s: not a region-set%s plan (kind %d)", who, kind == EXON_HIP_PLAN_REGION_SET_BASES ? " bases" : "", kind);
     return nullptr;
   }
@@ -1016,6 +1080,60 @@ int exon_hip_window_bases_decode(const exon_hip_plan* plan, const int64_t* state
 int exon_hip_window_bases(exon_hip_ctx* ctx, void* stream, const exon_hip_column* ref_id, const exon_hip_column* start, const exon_hip_column* end, int64_t n,
                           const exon_hip_plan* plan, int64_t* d_state) {
   return region_plan_op(ctx, stream, EXON_HIP_PLAN_WINDOW_BASES, "exon_hip_window_bases", ref_id, start, end, n, plan, d_state);
+}
+
+// kind 14, host only: word offsets of totals and D, and the state's size
+int exon_hip_region_depth_layout(const exon_hip_plan* plan, int64_t* out /*[3]*/) {
+  const PlanRegions* rs = region_plan_of(plan, EXON_HIP_PLAN_REGION_SET_DEPTH, "exon_hip_region_depth_layout");
+  if (!rs) return EXON_HIP_EINVAL;
+  if (!out) return fail(plan->ctx, EXON_HIP_EINVAL, "exon_hip_region_depth_layout: out is NULL");
+  out[0] = 0;
+  out[1] = 4;
+  out[2] = rs->dep.words();
+  return EXON_HIP_OK;
+}
+// kind 14, host only: the merged intervals in bin order (*n of them; the arrays may be NULL to ask for *n alone)
+int exon_hip_region_depth_intervals(const exon_hip_plan* plan, int32_t* n, int32_t* slot, int64_t* start, int64_t* end, int64_t* bin) {
+  const PlanRegions* rs = region_plan_of(plan, EXON_HIP_PLAN_REGION_SET_DEPTH, "exon_hip_region_depth_intervals");
+  if (!rs) return EXON_HIP_EINVAL;
+  if (!n) return fail(plan->ctx, EXON_HIP_EINVAL, "exon_hip_region_depth_intervals: n is NULL");
+  const exon::RegionDepth& d = rs->dep;
+  *n = d.I;
+  for (int32_t c = 0; c < d.C; ++c)
+    for (int32_t j = d.ioff[(size_t)c]; j < d.ioff[(size_t)c + 1]; ++j) {
+      if (slot) slot[j] = c;
+      if (start) start[j] = d.ms[(size_t)j];
+      if (end) end[j] = d.me[(size_t)j];
+      if (bin) bin[j] = d.interval_bin(c, j);
+    }
+  return EXON_HIP_OK;
+}
+// kind 14, host only: state words -> the depth of every target base in bin order (NOT linear in the state beyond this point)
+int exon_hip_region_depth_per_base(const exon_hip_plan* plan, const int64_t* state, int64_t* out_depth /*[T]*/) {
+  const PlanRegions* rs = region_plan_of(plan, EXON_HIP_PLAN_REGION_SET_DEPTH, "exon_hip_region_depth_per_base");
+  if (!rs) return EXON_HIP_EINVAL;
+  if (!state || !out_depth) return fail(plan->ctx, EXON_HIP_EINVAL, "exon_hip_region_depth_per_base: NULL argument");
+  rs->dep.per_base(state, out_depth);
+  return EXON_HIP_OK;
+}
+// kind 14, host only: state words -> [M][1 + k] = bases and threshold counts per region, in the caller's order
+int exon_hip_region_depth_decode(const exon_hip_plan* plan, const int64_t* state, int64_t* out /*[M * (1 + k)]*/) {
+  const PlanRegions* rs = region_plan_of(plan, EXON_HIP_PLAN_REGION_SET_DEPTH, "exon_hip_region_depth_decode");
+  if (!rs) return EXON_HIP_EINVAL;
+  if (!state || !out) return fail(plan->ctx, EXON_HIP_EINVAL, "exon_hip_region_depth_decode: NULL argument");
+  rs->dep.decode(state, out);
+  return EXON_HIP_OK;
+}
+// kind 14: the same table on the device, on the caller's stream; d_state is only read
+int exon_hip_region_depth_reduce(exon_hip_ctx* ctx, void* stream, const exon_hip_plan* plan, const int64_t* d_state, int64_t* d_out /*[M * (1 + k)]*/) {
+  const PlanRegions* rs = region_plan_of(plan, EXON_HIP_PLAN_REGION_SET_DEPTH, "exon_hip_region_depth_reduce");
+  if (!rs) return EXON_HIP_EINVAL;
+  if (!ctx || ctx != plan->ctx) return fail(ctx, EXON_HIP_EINVAL, "exon_hip_region_depth_reduce: the plan's tables live on the context it was created with");
+  return exon_op_region_depth_reduce(ctx, stream, rs->depth_reduce(), d_state, d_out);
+}
+int exon_hip_region_set_depth(exon_hip_ctx* ctx, void* stream, const exon_hip_column* ref_id, const exon_hip_column* start, const exon_hip_column* end, int64_t n,
+                              const exon_hip_plan* plan, int64_t* d_state) {
+  return region_plan_op(ctx, stream, EXON_HIP_PLAN_REGION_SET_DEPTH, "exon_hip_region_set_depth", ref_id, start, end, n, plan, d_state);
 }
 
 int exon_hip_plan_state_size(const exon_hip_plan* plan, int64_t* n_i64, int64_t* n_f64) {
@@ -2234,16 +2352,61 @@ struct ArrowArray* prim(const std::vector<T>& v, const std::vector<uint8_t>* val
 struct ArrowSchema* field(const char* fmt, const char* name, bool nullable) { return exon::new_field(fmt, name, nullable); }
 }  // namespace
 
+// kind 14: the state stays on the device (it may be 512 MiB); the reduce makes the table there and M * (1 + k) words come back.  One row
+// per region in the caller's order: contig, start, end, bases, ge_<T> for every threshold.
+static int finish_arrow_region_depth(exon_hip_stream* st, struct ArrowArray* out, struct ArrowSchema* out_schema) {
+  const exon_hip_plan* p = st->plan;
+  const exon::RegionDepth& dd = p->rs->dep;
+  int rc = exon_hip_stream_sync(st);
+  if (rc) return rc;
+  st->closed = true;
+  const int32_t k = dd.k();
+  const size_t words = (size_t)dd.M * (size_t)(1 + k);
+  std::vector<int64_t> table(words);
+  int64_t* d_table = nullptr;
+  HIP_TRY(st->ctx, hipMalloc((void**)&d_table, words * 8));
+  rc = exon_hip_region_depth_reduce(st->ctx, st->stream, p, reinterpret_cast<const int64_t*>(st->d_state), d_table);
+  hipError_t e = hipSuccess;
+  if (!rc && (e = hipMemcpyAsync(table.data(), d_table, words * 8, hipMemcpyDeviceToHost, st->stream)) == hipSuccess) e = hipStreamSynchronize(st->stream);
+  hipFree(d_table);
+  if (rc) return rc;
+  HIP_TRY(st->ctx, e);
+  std::vector<struct ArrowArray*> cols;
+  std::vector<struct ArrowSchema*> fields;
+  if (dd.by_name) {
+    std::vector<std::string> names((size_t)dd.M);
+    for (int32_t i = 0; i < dd.M; ++i) names[(size_t)i] = dd.contig_names[(size_t)dd.slot[(size_t)i]];
+    cols.push_back(exon::utf8_array(names));
+  } else {
+    std::vector<int32_t> ids((size_t)dd.M);
+    for (int32_t i = 0; i < dd.M; ++i) ids[(size_t)i] = dd.contig_ids[(size_t)dd.slot[(size_t)i]];
+    cols.push_back(prim(ids));
+  }
+  fields.push_back(field(dd.by_name ? "u" : "i", "contig", false));
+  cols.push_back(prim(dd.starts)), fields.push_back(field("l", "start", false));
+  cols.push_back(prim(dd.ends)), fields.push_back(field("l", "end", false));
+  std::vector<int64_t> col((size_t)dd.M);
+  for (int32_t c = 0; c <= k; ++c) {
+    for (int32_t i = 0; i < dd.M; ++i) col[(size_t)i] = table[(size_t)i * (size_t)(1 + k) + (size_t)c];
+    cols.push_back(prim(col));
+    fields.push_back(field("l", c == 0 ? "bases" : ("ge_" + std::to_string(dd.thresholds[(size_t)c - 1])).c_str(), false));
+  }
+  make_struct(out, (int64_t)dd.M, cols);
+  make_schema(out_schema, "+s", "", false, fields);
+  return EXON_HIP_OK;
+}
+
 extern "C" {
 
 int exon_hip_stream_finish_arrow(exon_hip_stream* st, struct ArrowArray* out, struct ArrowSchema* out_schema) {
   if (!st || !out || !out_schema) return fail(st ? st->ctx : nullptr, EXON_HIP_EINVAL, "exon_hip_stream_finish_arrow: NULL argument");
   const exon_hip_plan* p = st->plan;
+  const exon_hip_plan_desc& d = p->d;
+  if (d.kind == EXON_HIP_PLAN_REGION_SET_DEPTH) return finish_arrow_region_depth(st, out, out_schema);
   std::vector<int64_t> counts((size_t)p->n_i64);
   std::vector<double> sums((size_t)p->n_f64);
   int rc = exon_hip_stream_finish(st, counts.data(), sums.data());
   if (rc) return rc;
-  const exon_hip_plan_desc& d = p->d;
   switch (d.kind) {
     case EXON_HIP_PLAN_OVERLAP_COUNT:
     case EXON_HIP_PLAN_WITHIN_COUNT:

@@ -387,6 +387,19 @@ class Context:
         into one sum per window, finish_arrow into a table."""
         return WindowBasesPlan(self, contigs, window, columns)
 
+    def plan_region_set_depth(self, regions, thresholds, columns=(2, 3, 4)):
+        """The per-base depth over the bases a region set covers, in one pass over the rows (plan kind 14), and per region its bases
+        and how many of them are covered at least thresholds[t] times.  `regions` as plan_region_set_overlap's, with finite ends;
+        `thresholds`: up to 8 strictly increasing depths >= 1.  State: 4 + T + C int64 words, all of which add modulo 2^64; the decode
+        is not linear: add partial states first.  RegionDepthPlan.decode / .reduce make the table, finish_arrow serves it."""
+        return RegionDepthPlan(self, regions, thresholds, columns)
+
+    def region_set_depth(self, ref_id, ref_valid, start, start_valid, end, end_valid, n, plan, d_state, stream=None):
+        """K14 (bare operator, ids form): accumulates the batch into `d_state` (plan.n_i64 int64 words)."""
+        c0, c1, c2 = _col(ref_id, ref_valid, None, n), _col(start, start_valid, None, n), _col(end, end_valid, None, n)
+        self._check(self.lib.exon_hip_region_set_depth(self.h, stream, C.byref(c0), C.byref(c1), C.byref(c2), n, plan.h,
+                                                       d_state.ptr if isinstance(d_state, DeviceBuffer) else d_state))
+
     def window_bases(self, ref_id, ref_valid, start, start_valid, end, end_valid, n, plan, d_state, stream=None):
         """K13 (bare operator, ids form): accumulates the batch into `d_state` (plan.n_i64 int64 words)."""
         c0, c1, c2 = _col(ref_id, ref_valid, None, n), _col(start, start_valid, None, n), _col(end, end_valid, None, n)
@@ -1319,11 +1332,15 @@ class RegionSetPlan(Plan):
         h = C.c_void_p()
         self._check(getattr(self.lib, self._CREATE)(ctx.h if ctx is not None else None, cols, packed, len(packed) if packed else 0,
                                                     ids.ctypes.data if ids is not None and m else None,
-                                                    starts.ctypes.data if m else None, ends.ctypes.data if m else None, m, C.byref(h)))
+                                                    starts.ctypes.data if m else None, ends.ctypes.data if m else None, m, *self._create_extra(), C.byref(h)))
         self.h = h
         a, b = C.c_int64(), C.c_int64()
         self._check(self.lib.exon_hip_plan_state_size(h, C.byref(a), C.byref(b)))
         self.n_i64, self.n_f64 = a.value, b.value
+
+    def _create_extra(self):
+        """What the kind's constructor takes between n_regions and the plan."""
+        return ()
 
     def _check(self, rc):
         if rc < 0:
@@ -1400,6 +1417,58 @@ class WindowBasesPlan(RegionSetPlan):
             raise ValueError("the state of this plan has %d words, %d given" % (self.n_i64, state.size))
         out = np.zeros((self.n_i64 - 4) // 2, np.int64)
         self._check(self.lib.exon_hip_window_bases_decode(self.h, state.ctypes.data, out.ctypes.data))
+        return out
+
+
+class RegionDepthPlan(RegionSetPlan):
+    """Plan kind 14 (exon_hip_plan_create_region_set_depth): RegionSetPlan's regions (finite ends) and up to 8 strictly increasing
+    depth thresholds.  ctx None: a host-only plan that serves layout(), intervals(), per_base() and decode() and cannot be launched.
+    layout(): the word offsets of the totals and of D and the word count; intervals(): the merged intervals in bin order as (slot,
+    start, end, bin) arrays; per_base(state): the depth of every target base in bin order; decode(state): (bases[M], ge[M, k]) per
+    region in the caller's order; reduce(d_state): the same table, [M, 1 + k] int64 words, made on the device."""
+
+    _CREATE, _LAYOUT, _LAYOUT_WORDS = "exon_hip_plan_create_region_set_depth", "exon_hip_region_depth_layout", 3
+
+    def __init__(self, ctx, regions, thresholds, columns=(2, 3, 4)):
+        self.thresholds = [int(t) for t in thresholds]
+        self._thr = np.array(self.thresholds, np.int64)
+        super().__init__(ctx, regions, columns)
+
+    def _create_extra(self):
+        return (self._thr.ctypes.data if self._thr.size else None, int(self._thr.size))
+
+    def _state(self, state):
+        state = np.ascontiguousarray(state, np.int64)
+        if state.size != self.n_i64:
+            raise ValueError("the state of this plan has %d words, %d given" % (self.n_i64, state.size))
+        return state
+
+    def intervals(self):
+        n = C.c_int32()
+        self._check(self.lib.exon_hip_region_depth_intervals(self.h, C.byref(n), None, None, None, None))
+        slot = np.zeros(n.value, np.int32)
+        start, end, bins = (np.zeros(n.value, np.int64) for _ in range(3))
+        self._check(self.lib.exon_hip_region_depth_intervals(self.h, C.byref(n), slot.ctypes.data, start.ctypes.data, end.ctypes.data, bins.ctypes.data))
+        return slot, start, end, bins
+
+    def per_base(self, state):
+        state = self._state(state)
+        n_contigs = len(set(c for c, _, _ in self.regions))
+        out = np.zeros(self.n_i64 - 4 - n_contigs, np.int64)
+        self._check(self.lib.exon_hip_region_depth_per_base(self.h, state.ctypes.data, out.ctypes.data))
+        return out
+
+    def decode(self, state):
+        state = self._state(state)
+        k = len(self.thresholds)
+        out = np.zeros((len(self.regions), 1 + k), np.int64)
+        self._check(self.lib.exon_hip_region_depth_decode(self.h, state.ctypes.data, out.ctypes.data))
+        return out[:, 0].copy(), out[:, 1:].copy()
+
+    def reduce(self, d_state, stream=None):
+        """exon_hip_region_depth_reduce: a DeviceBuffer of [M, 1 + k] int64 words (bases, ge_t ...); `d_state` is only read."""
+        out = self.ctx.empty(np.int64, len(self.regions) * (1 + len(self.thresholds)))
+        self._check(self.lib.exon_hip_region_depth_reduce(self.ctx.h, stream, self.h, d_state.ptr if isinstance(d_state, DeviceBuffer) else d_state, out.ptr))
         return out
 
 

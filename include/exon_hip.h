@@ -508,6 +508,71 @@ int exon_hip_window_bases_decode(const exon_hip_plan* plan, const int64_t* state
 int exon_hip_window_bases(exon_hip_ctx* ctx, void* stream, const exon_hip_column* ref_id /*i32*/, const exon_hip_column* start /*i64*/,
                           const exon_hip_column* end /*i64*/, int64_t n, const exon_hip_plan* plan, int64_t* d_state);
 
+/* ---- K14: per-base depth over a region set, threshold counts per region, in one pass (plan kind 14) ----------------------------------
+ * The QC question on a target list -- how much of each target is covered at least 1x, 10x, 20x, 30x: `mosdepth --thresholds`, Picard's
+ * PCT_TARGET_BASES_20X; `samtools depth -b targets.bed` lists the per-base values.  None of it follows from kind 12's or 13's sums.
+ * Inputs are K6 / K11 - K13's three columns, 1-based inclusive; the row classes and the four totals are exactly kind 11's.
+ *
+ * TARGET SPACE.  Contigs in order of first appearance in the set.  Per contig the regions are sorted and merged into disjoint
+ * intervals [ms_j, me_j]: two merge when the next start <= the current end + 1, so overlapping and abutting regions both merge.
+ * cum_j = the bases of the contig's intervals in front of interval j, T_c = the contig's target bases, T = sum of T_c.  Contig c owns
+ * T_c + 1 consecutive bins from doff_c = (T of the contigs in front) + c: a bin per target base, then a terminator.  T + C may be at
+ * most EXON_HIP_REGION_DEPTH_MAX_BINS (a state of 512 MiB, kind 13's bound; more is EXON_HIP_EUNSUPPORTED): panels, exomes and the
+ * smaller chromosomes whole; kind 13 stays the answer for whole genomes.
+ * COMPRESSED COORDINATE.  below_c(x) = the contig's target bases at positions <= x: with j = the intervals with ms <= x, 0 if j = 0,
+ * else cum_{j-1} + min(x - ms_{j-1} + 1, len_{j-1}), computed without overflow for every int64 x.  A region [rs, re] is the bins
+ * [below(rs - 1), below(re)) of its contig, re - rs + 1 of them.
+ *
+ * State: 4 + T + C int64 words, n_f64 = 0: totals[4] (counted, null_rows, elsewhere, inverted), D[T + C].  A counted row [s, e] takes
+ * lo = below(s - 1) (0 when s <= 1) and hi = below(e); if hi > lo it adds 1 to D[doff_c + lo] and 2^64 - 1 to D[doff_c + hi], else
+ * nothing: a read across the gap between two targets is still one pair of adds, a read inside a gap none.  Every word adds MODULO
+ * 2^64, so streams, chunked launches, exon_hip_plan_fold_states, exon_hip_stream_all_reduce and the file pipelines carry the state
+ * like kinds 11 - 13's.  Each contig's bins sum to 0 in every state that adds can produce, so THE DEPTH OF BIN b IS DEFINED AS THE
+ * RUNNING SUM OF THE WHOLE SECTION D[0] + ... + D[b], one array, on the host and on the device: the two agree word for word on any
+ * input.  DECISION (kind 11's): a row with end < start adds to `inverted` and to no bin.
+ * THE DECODE IS NOT LINEAR: bases_i adds over partial states, the threshold counts do not.  Add the states, then decode or reduce.
+ *
+ * What it does not compute: the alignment span [start, end] counts as covered, deletions and reference skips included -- there is no
+ * CIGAR-aware split; a BED source is not served; there are no open-ended regions.
+ *
+ * exon_hip_plan_create_region_set_depth takes exon_hip_plan_create_region_set's region arguments under the same rules and error
+ * classes (ids form or names form, 1 <= start <= end, at most 1048576 regions, duplicate, nested and overlapping regions legal and
+ * each with its own result, ctx may be NULL for a host-only plan; exon_hip_plan_create with kind 14 is EXON_HIP_EINVAL and names the
+ * constructor; a names-form plan refuses pushes, device pushes, plan launches and the bare operator with EXON_HIP_ESTATE).  Its own:
+ * end == EXON_HIP_REGION_OPEN_END is EXON_HIP_EUNSUPPORTED (a per-base state needs a finite end); 0 <= n_thresholds <=
+ * EXON_HIP_REGION_DEPTH_MAX_THRESHOLDS, every threshold >= 1, the list strictly increasing, anything else EXON_HIP_EINVAL.  Kind 11 /
+ * 12 / 13's helpers refuse a kind-14 plan and these refuse the other kinds.
+ *
+ * Plans with T + C <= 8192 add in LDS (the interval table beside the bins when both fit 128 KiB); larger ones search through L2 and
+ * add with global atomics.  The columns' values need their element's alignment only (4 / 8 / 8 bytes).  finish_arrow runs the reduce
+ * on the device and copies M * (1 + k) words: contig (Int32, or Utf8 in the names form), start, end, bases, then ge_<T> for each
+ * threshold T, all Int64, one row per region in the caller's order. */
+#define EXON_HIP_PLAN_REGION_SET_DEPTH 14
+#define EXON_HIP_REGION_DEPTH_MAX_BINS 67108864
+#define EXON_HIP_REGION_DEPTH_MAX_THRESHOLDS 8
+int exon_hip_plan_create_region_set_depth(exon_hip_ctx* ctx, const int32_t* columns /*[3]*/,
+                                          const char* packed_contig_names /* n_regions '\0'-terminated names, or NULL */, size_t packed_bytes,
+                                          const int32_t* ref_ids /* used when names are NULL */, const int64_t* starts, const int64_t* ends,
+                                          int32_t n_regions, const int64_t* thresholds, int32_t n_thresholds, exon_hip_plan** out);
+/* host only: out = word offsets of totals and D, and the word count */
+int exon_hip_region_depth_layout(const exon_hip_plan* plan, int64_t* out /*[3]*/);
+/* host only: the merged intervals in bin order: *n of them, each with its contig slot, its 1-based closed [start, end] and the bin of
+ * its first base.  Any of the four arrays may be NULL; all NULL asks for *n alone. */
+int exon_hip_region_depth_intervals(const exon_hip_plan* plan, int32_t* n, int32_t* slot, int64_t* start, int64_t* end, int64_t* bin);
+/* host only: the state's words -> the depth of every target base in bin order, the C terminator bins left out (what `samtools depth
+ * -b` lists) */
+int exon_hip_region_depth_per_base(const exon_hip_plan* plan, const int64_t* state, int64_t* out_depth /*[T]*/);
+/* host only: the state's words -> row-major [M][1 + k], per region in the caller's order: bases = the sum of the depths over the
+ * region's bins (kind 12's bases_i for the same rows and regions), then ge_t = the region's bases whose depth, read as int64, is
+ * >= thresholds[t] */
+int exon_hip_region_depth_decode(const exon_hip_plan* plan, const int64_t* state, int64_t* out /*[M * (1 + k)]*/);
+/* the same table made on the device, on the caller's stream (`ctx` is the plan's), equal to _decode word for word.  d_state is only
+ * read; nothing proportional to T crosses to or from the host.  The running sum is taken in tiles of 256 bins. */
+int exon_hip_region_depth_reduce(exon_hip_ctx* ctx, void* stream, const exon_hip_plan* plan, const int64_t* d_state, int64_t* d_out /*[M * (1 + k)]*/);
+/* K14, bare operator (ids form; `ctx` is the plan's): d_state (exon_hip_plan_state_size words) += this batch */
+int exon_hip_region_set_depth(exon_hip_ctx* ctx, void* stream, const exon_hip_column* ref_id /*i32*/, const exon_hip_column* start /*i64*/,
+                              const exon_hip_column* end /*i64*/, int64_t n, const exon_hip_plan* plan, int64_t* d_state);
+
 /* Stateless form of a push: run the plan's fused kernel over HBM-resident columns (`columns[i]` = operator argument i, see
  * exon_hip_plan_desc.columns for the order; n_columns must match the plan) on the caller's hipStream_t into a caller-owned
  * packed partial state [n_i64 x int64][n_f64 x float64] (exon_hip_plan_state_size; 8-byte aligned device memory).

@@ -37,6 +37,9 @@ pub const EXON_HIP_REGION_SET_MAX_REGIONS: i32 = 1048576;
 pub const EXON_HIP_PLAN_REGION_SET_BASES: i32 = 12; // made by exon_hip_plan_create_region_set_bases; state = 4 + 4 * (P + C) words, all add modulo 2^64
 pub const EXON_HIP_PLAN_WINDOW_BASES: i32 = 13; // made by exon_hip_plan_create_window_bases; state = 4 + 2 * B words, all add modulo 2^64
 pub const EXON_HIP_WINDOW_MAX_BINS: i32 = 33554432;
+pub const EXON_HIP_PLAN_REGION_SET_DEPTH: i32 = 14; // made by exon_hip_plan_create_region_set_depth; state = 4 + T + C words, all add modulo 2^64
+pub const EXON_HIP_REGION_DEPTH_MAX_BINS: i32 = 67108864;
+pub const EXON_HIP_REGION_DEPTH_MAX_THRESHOLDS: i32 = 8;
 pub const EXON_HIP_GT: i32 = 0;
 pub const EXON_HIP_GE: i32 = 1;
 pub const EXON_HIP_LT: i32 = 2;
@@ -180,6 +183,20 @@ extern "C" {
     pub fn exon_hip_window_bases_decode(plan: *const exon_hip_plan, state: *const i64, out_bases: *mut i64) -> c_int;
     /// K13 (bare operator, ids form): bases per window over one batch; accumulates
     pub fn exon_hip_window_bases(ctx: *mut exon_hip_ctx, stream: *mut c_void, ref_id: *const exon_hip_column, start: *const exon_hip_column, end: *const exon_hip_column, n: i64, plan: *const exon_hip_plan, d_state: *mut i64) -> c_int;
+    /// K14: the plan of the per-base depth over a region set; regions as kind 11's with finite ends, up to 8 strictly increasing thresholds
+    pub fn exon_hip_plan_create_region_set_depth(ctx: *mut exon_hip_ctx, columns: *const i32, packed_contig_names: *const c_char, packed_bytes: usize, ref_ids: *const i32, starts: *const i64, ends: *const i64, n_regions: i32, thresholds: *const i64, n_thresholds: i32, out: *mut *mut exon_hip_plan) -> c_int;
+    /// host-only: word offsets of K14's totals and D and the state's size (out[3])
+    pub fn exon_hip_region_depth_layout(plan: *const exon_hip_plan, out: *mut i64) -> c_int;
+    /// host-only: the merged intervals in bin order (*n of them; any array may be NULL)
+    pub fn exon_hip_region_depth_intervals(plan: *const exon_hip_plan, n: *mut i32, slot: *mut i32, start: *mut i64, end: *mut i64, bin: *mut i64) -> c_int;
+    /// host-only: K14's state words -> the depth of every target base in bin order (out_depth[T])
+    pub fn exon_hip_region_depth_per_base(plan: *const exon_hip_plan, state: *const i64, out_depth: *mut i64) -> c_int;
+    /// host-only: K14's state words -> [M][1 + k] bases and threshold counts per region; not linear in the state
+    pub fn exon_hip_region_depth_decode(plan: *const exon_hip_plan, state: *const i64, out: *mut i64) -> c_int;
+    /// the same table made on the device on the caller's stream; d_state is only read
+    pub fn exon_hip_region_depth_reduce(ctx: *mut exon_hip_ctx, stream: *mut c_void, plan: *const exon_hip_plan, d_state: *const i64, d_out: *mut i64) -> c_int;
+    /// K14 (bare operator, ids form): per-base depth over the set's bases for one batch; accumulates
+    pub fn exon_hip_region_set_depth(ctx: *mut exon_hip_ctx, stream: *mut c_void, ref_id: *const exon_hip_column, start: *const exon_hip_column, end: *const exon_hip_column, n: i64, plan: *const exon_hip_plan, d_state: *mut i64) -> c_int;
     /// the reference lengths of a BAM / SAM / CRAM header in dictionary-id order: *n of them, the first min(*n, cap) into out
     pub fn exon_hip_scan_reference_lengths(scan: *mut exon_hip_scan, out: *mut i64, cap: i32, n: *mut i32) -> c_int;
     /// fold of `world` packed states by the plan's own layout (add; unsigned max for K8's extreme planes)
