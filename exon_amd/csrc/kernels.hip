@@ -19,6 +19,7 @@
 // Reference semantics restated by each kernel are cited at the kernel.
 #include "kernels.h"
 #include "host/cmp_key.h"
+#include "host/k4_route.h"
 
 #include <algorithm>
 #include <cstdlib>
@@ -946,16 +947,8 @@ __device__ __forceinline__ unsigned cmp_key_passes(float xf, unsigned xv, int32_
   const unsigned inr = unsigned(kx >= klo) & unsigned(kx <= khi);
   return xv & (inr ^ (unsigned)negate);
 }
-constexpr int K4_TAIL_MAX_RANGES = 2048;  // (2^24 - 4100) / 8192 ids
-constexpr int K4_TAIL_MAX_GRID = 2048;    // workgroups of the main kernel the partitioned tier 3 has histogram rows for
-constexpr int K4_TAIL_RANGE = 8192;  // ids per range of the partitioned tier 3 = entries of k4_tail_aggregate's LDS table (128 KiB)
-// The main kernel counts its tier-3 records per id range in LDS.  With few ranges the 64 lanes of a wave instruction land on
-// a handful of counters and same-address LDS atomics serialise, so every range gets 2^k counters picked by lane (summed when
-// the workgroup stores its row of the histogram); k shrinks as the ranges grow: at most 3072 counters = 12 KiB behind the
-// tier-2 table, which keeps two workgroups on a CU.
-__host__ __device__ static inline int k4_hist_copies_log2(int n_ranges) {
-  return n_ranges <= 192 ? 4 : n_ranges <= 384 ? 3 : n_ranges <= 768 ? 2 : n_ranges <= 1536 ? 1 : 0;
-}
+// (K4's tiers, ranges, chunks and the per-range histogram copies -- K4_TAIL_RANGE, K4_CHUNK, k4_hist_copies_log2 ... -- are
+// host/k4_route.h's: the host's choice of a tier-3 form and the device code below read the same constants)
 // Direct partition (round 6): the main kernel writes a tier-3 record straight into a CHUNK of its id range -- no compaction,
 // no scatter pass.  A workgroup owns `cpw` chunks of K4_CHUNK records (its rows / K4_CHUNK + one per stream: what it can
 // fill + one partly filled chunk per stream); a STREAM = (id range, copy) has an LDS cursor word  chunk << 13 | position:
@@ -964,13 +957,7 @@ __host__ __device__ static inline int k4_hist_copies_log2(int n_ranges) {
 // position behind it wait for that.  Few ranges get 2-4 copies each (picked by lane) so that the 64 lanes of an add do not
 // queue on a dozen addresses.  Behind the tile loop the workgroup appends its chunks to the per-range chunk lists
 // (one global atomic per range and workgroup); k4_tail_aggregate_chunks walks the lists.
-constexpr int K4_CHUNK = 2048;        // records per chunk (16 KiB): two per thread of k4_tail_aggregate_chunks
-constexpr int K4_POS_BITS = 13;       // position field of a cursor: K4_CHUNK + 1024 lanes' failed draws < 8192
 constexpr unsigned K4_POS_MASK = (1u << K4_POS_BITS) - 1u;
-constexpr int K4_DIRECT_MAX_RANGES = 128;
-static inline int k4_stream_copies_log2(int n_ranges) {
-  return n_ranges == 1 ? 2 : 0;  // measured (profiles/r6_groupby_direct.md): the main kernel slows down with the streams a wave store spreads over
-}
 struct K4Tail {                 // tier 3 (unused when NG == NL)
   unsigned long long* counts;   // the caller's [cnn[NG]] [crow[NG]]
   double* sums;                 // the caller's [sum[NG]]
@@ -1004,7 +991,6 @@ struct K4Entry {  // tier-2 table entry
 // -- and with them the shuffle tree, the record and the fold -- are the bits the register form gives.
 // Tile loop of <5, .>: 30.0 vector instructions + 1 LDS add per row against 45.9 with register groups; 5 and more groups take
 // the slots (and J = 2 with them, see k4_one_launch), 1 .. 4 groups keep the registers: there the slot form is not faster.
-constexpr int K4_SLOTS_MIN_G = 5;
 template <int G, typename S, bool OVF, bool YI = false>
 __global__ __launch_bounds__(S::THREADS) void k4_cmp_avg_by_group_main(
     const float* __restrict__ x, const uint8_t* __restrict__ xvalid, const float* __restrict__ y,
@@ -1441,10 +1427,6 @@ __global__ __launch_bounds__(S::THREADS) void k4_cmp_avg_by_group_main(
   if (fa.ticket) fold_if_last<THREADS>(fa, partials);
 }
 
-constexpr int K4_OVF_REGS = 4;                   // register groups of the > 8-group variant
-constexpr int K4_LDS_GROUPS = K4_OVF_REGS + 4096;  // ids handled by registers + the LDS table
-static int k4_nl(int n_groups) { return n_groups < K4_LDS_GROUPS ? n_groups : K4_LDS_GROUPS; }
-
 size_t k4_partial_words(const LaunchCfg& cfg, int n_groups) { return (size_t)max_grid(cfg) * 3 * (size_t)k4_nl(n_groups); }
 
 template <int G, typename S, bool OVF, bool YI = false>
@@ -1860,14 +1842,9 @@ __global__ __launch_bounds__(1024) void k4_tail_aggregate_chunks(const uint2* __
   }
 }
 
-// rows per launch of the partitioned tier 3: its scratch is 2 x 8 bytes per row of a launch, so a longer table is cut
-// into launches of this many rows (a multiple of every tile size and of 8: column and bitmap pointers stay aligned)
-constexpr int64_t K4_TAIL_CHUNK_ROWS = int64_t(1) << 28;
-constexpr int64_t K4_TAIL_SLACK = 2048 * 2048;  // grid x tile of the largest launch shape: rounding of the per-workgroup regions
-size_t k4_tail_records(int64_t n, int n_groups) {
-  if (n_groups <= K4_LDS_GROUPS) return 0;
-  return (size_t)(std::min<int64_t>(n, K4_TAIL_CHUNK_ROWS) + K4_TAIL_SLACK);
-}
+size_t k4_tail_records(int64_t n, int n_groups) { return k4_tail_records_for(n, n_groups); }
+static_assert(ShapeOf<ShapeBig>::TILE == K4_TILE_BIG_J4 && ShapeOf<ShapeBigJ2>::TILE == K4_TILE_BIG && ShapeOf<ShapeSmall>::TILE == K4_TILE_SMALL,
+              "host/k4_route.h states the launch shapes' tiles");
 
 template <int G>
 using K4Big = typename std::conditional<(G >= K4_SLOTS_MIN_G), ShapeBigJ2, ShapeBig>::type;  // the 1024-thread shape of G register groups
@@ -1875,35 +1852,18 @@ using K4Big = typename std::conditional<(G >= K4_SLOTS_MIN_G), ShapeBigJ2, Shape
 static hipError_t k4_one_launch(hipStream_t s, const LaunchCfg& cfg, const Workspace& ws, const float* x, const uint8_t* x_valid,
                                 const float* y, const uint8_t* y_valid, const int32_t* gid, int64_t n, int32_t klo, int32_t khi,
                                 int32_t negate, int32_t keymask, int32_t yint, int n_groups, int64_t* d_counts, double* d_sums) {
-  const int nl = k4_nl(n_groups);
-  const bool has_tail = n_groups > nl;
-  // With register groups (1 .. 4 groups) K4 keeps the 16384-row tile whenever every CU gets one: measured on MI355X at 1e7 rows
-  // J = 4 27.8 us, J = 2 31.5 us (its per-tile bookkeeping -- counter spills, 15-value reductions -- outweighs the better tile
-  // balance that pays for K2).  With the sums in lane-private LDS slots (5 .. 8 groups) the choice was run again and J = 2 wins:
-  // 5 groups, 1e9 rows 1.86 - 1.91 ms against 1.92 - 1.96 at J = 4, 125e6 rows 0.238 - 0.252 against 0.257, 1e7 rows
-  // 29.5 - 30.5 us against 31.1 (profiles/k4_lane_slots.md); the threshold -- a 16384-row tile per CU -- stays.
-  const bool big = n / ShapeOf<ShapeBig>::TILE >= (int64_t)cfg.compute_units && use_big_shape(cfg, n);
+  // launch shape, tiers and the form of tier 3: host/k4_route.h (the measurements behind the choices are cited there)
+  const K4Route rt = k4_route(K4RouteIn{cfg.compute_units, cfg.blocks_per_cu, n, n_groups, ws.tail_rec_a && ws.tail_rec_b ? ws.tail_capacity : 0,
+                                        ws.tail_rec_a && ws.tail_rec_b == ws.tail_rec_a + ws.tail_capacity, ws.tail_u32 != nullptr});
+  const int nl = rt.nl, n_ranges = rt.n_ranges;
+  const bool has_tail = rt.has_tail, big = rt.big;
+  const bool direct = rt.form == K4_FORM_DIRECT, partition = direct || rt.form == K4_FORM_SCATTER;
+  const size_t pool_chunks = rt.pool_chunks;
   int grid = 1;
   hipError_t e;
   const FoldArgs fa = has_tail ? FoldArgs{nullptr, nullptr, nullptr, 0, 0, 0}
                                : fold_args(cfg, ws, 3 * n_groups, 2 * n_groups, d_counts, d_sums);
   K4Tail tail{reinterpret_cast<unsigned long long*>(d_counts), d_sums, nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr, 0};
-  const int n_ranges = has_tail ? (n_groups - nl + K4_TAIL_RANGE - 1) / K4_TAIL_RANGE : 0;
-  // partitioned tier 3 when its scratch is there (capi.cpp sizes it with k4_tail_records) and the launch has whole tiles
-  const bool partition = has_tail && ws.tail_rec_a && ws.tail_rec_b && ws.tail_u32 &&
-                         ws.tail_capacity >= (size_t)(n + K4_TAIL_SLACK) && n_ranges <= K4_TAIL_MAX_RANGES &&
-                         max_grid(cfg) <= K4_TAIL_MAX_GRID;
-  // the direct partition (round 6) when the chunk pool + the chunk lists fit the two record buffers (one allocation)
-  const int64_t tile_rows = big ? ShapeOf<ShapeBigJ2>::TILE : ShapeOf<ShapeSmall>::TILE;
-  const size_t n_streams = (size_t)n_ranges << k4_stream_copies_log2(n_ranges);
-  // chunks of all workgroups, at most: their rows (rounded up to tiles per workgroup) + one per stream and workgroup
-  const int64_t grid_ub = big ? cfg.compute_units : std::min<int64_t>(max_grid(cfg), n / tile_rows + 1);  // grid_for's bounds
-  const size_t pool_chunks = (size_t)(n + grid_ub * tile_rows) / K4_CHUNK + (size_t)grid_ub * n_streams;
-  const int64_t tiles_all = n / tile_rows, grid_min = std::max<int64_t>(1, std::min<int64_t>(tiles_all, cfg.compute_units));
-  const size_t cpw_max = (size_t)((tiles_all + grid_min - 1) / grid_min) * tile_rows / K4_CHUNK + n_streams;
-  const bool direct = partition && n_ranges <= K4_DIRECT_MAX_RANGES && ws.tail_rec_b == ws.tail_rec_a + ws.tail_capacity &&
-                      pool_chunks * K4_CHUNK + (size_t)n_ranges * pool_chunks <= 2 * ws.tail_capacity &&
-                      cpw_max < 65536;  // chunk numbers inside a workgroup are 16-bit
   unsigned *wg_count = nullptr, *totals = nullptr, *offsets = nullptr, *slice_start = nullptr, *wg_hist = nullptr;
   if (partition) {  // every word the kernels below read is written by the launch before it: nothing to clear
     wg_count = ws.tail_u32;                       // [K4_TAIL_MAX_GRID]
@@ -1919,7 +1879,7 @@ static hipError_t k4_one_launch(hipStream_t s, const LaunchCfg& cfg, const Works
       tail.list_stride = (unsigned)pool_chunks;
       tail.n_list = wg_count;
       tail.totals = totals;
-      tail.copies_log2 = k4_stream_copies_log2(n_ranges);
+      tail.copies_log2 = rt.copies_log2;
       hipError_t ez = hipMemsetAsync(wg_count, 0, (size_t)(K4_TAIL_MAX_GRID + K4_TAIL_MAX_RANGES) * 4, s);  // list lengths + range totals
       if (ez != hipSuccess) return ez;
     }
@@ -1959,8 +1919,7 @@ static hipError_t k4_one_launch(hipStream_t s, const LaunchCfg& cfg, const Works
       hipLaunchKernelGGL(k4_tail_aggregate_chunks, dim3(target + n_ranges), dim3(1024), 0, s, ws.tail_rec_a, tail.lists, tail.list_stride, tail.n_list,
                          slice_start, n_ranges, nl, n_groups, yint, reinterpret_cast<unsigned long long*>(d_counts), d_sums);
     } else if (partition) {
-      const int64_t tile = big ? ShapeOf<ShapeBigJ2>::TILE : ShapeOf<ShapeSmall>::TILE;
-      const unsigned cap_wg = (unsigned)(((n / tile + grid - 1) / grid) * tile);  // the main kernel's formula
+      const unsigned cap_wg = (unsigned)(((n / rt.tile_rows + grid - 1) / grid) * rt.tile_rows);  // the main kernel's formula
       hipLaunchKernelGGL(k4_tail_wg_scan, dim3(n_ranges), dim3(1024), 0, s, wg_hist, grid, n_ranges, totals);
       // k4_tail_aggregate holds one workgroup per CU (128 KiB table): one workgroup per CU in all, shared out over the ranges
       // by their records.  One round measured best (1e5 zipf keys: 3.90 / 4.07 / 4.32 / 4.54 ms per 1e9 rows for 1 / 2 / 3 / 4
