@@ -181,6 +181,7 @@ LAUNCH_ACCUMULATE = 0
 LAUNCH_OVERWRITE = 1
 CMP = {">": 0, ">=": 1, "<": 2, "<=": 3, "=": 4, "==": 4, "!=": 5, "<>": 5}
 REGION_OPEN_END = 2**63 - 1
+COVER_ALIGNED, COVER_ALIGNED_DEL, COVER_OPS_LEGAL = 0x181, 0x185, 0x18D  # exon_hip_cigar_blocks: M = X; + D; every op that consumes the reference
 
 _vp, _i32, _i64, _u64, _dbl = C.c_void_p, C.c_int32, C.c_int64, C.c_uint64, C.c_double
 _colp = C.POINTER(Column)
@@ -247,6 +248,8 @@ SIGNATURES = {
     "exon_hip_region_depth_decode": (C.c_int, [_vp, _vp, _vp]),
     "exon_hip_region_depth_reduce": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
     "exon_hip_region_set_depth": (C.c_int, [_vp, _vp, _colp, _colp, _colp, _i64, _vp, _vp]),
+    "exon_hip_cigar_blocks": (C.c_int, [_vp, _vp, _colp, _colp, _vp, _vp, _i64, C.c_uint32, _vp, _vp, _vp, _vp, _i64, C.POINTER(_i64)]),
+    "exon_hip_cigar_blocks_host": (C.c_int, [_vp, _i32, _i64, C.c_uint32, _vp, _vp, _i32, C.POINTER(_i32)]),
     "exon_hip_rccl_unique_id": (C.c_int, [_vp]),
     "exon_hip_rccl_comm_init": (C.c_int, [_vp, _vp, _i32, _i32, C.POINTER(_vp)]),
     "exon_hip_rccl_comm_destroy": (C.c_int, [_vp]),
@@ -280,6 +283,7 @@ SIGNATURES = {
     "exon_hip_scan_bind_ctx": (C.c_int, [_vp, _vp]),
     "exon_hip_scan_set_predicate": (C.c_int, [_vp, _i32, _i32, C.c_double]),
     "exon_hip_scan_set_flag_predicate": (C.c_int, [_vp, _i32, _i32, _i32]),
+    "exon_hip_scan_set_cover_ops": (C.c_int, [_vp, C.c_uint32]),
     "exon_hip_scan_export_stats": (C.c_int, [_vp, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64)]),
     "exon_hip_scan_decoded_on_gpu": (C.c_int, [_vp, C.POINTER(_i32), C.POINTER(_i32)]),
     "exon_hip_scan_close": (C.c_int, [_vp]),
@@ -313,6 +317,7 @@ SIGNATURES = {
     "exon_hip_seq_stats_layout": (C.c_int, [_i32, C.POINTER(_i64)]),
     "exon_hip_bam_parser_create": (C.c_int, [_vp, _i32, _i64, C.POINTER(_vp)]),
     "exon_hip_bam_parser_parse": (C.c_int, [_vp, _vp, _vp, _i64, C.POINTER(BAMColumns)]),
+    "exon_hip_bam_parser_cigar_blocks": (C.c_int, [_vp, _vp, _vp, _i64, C.POINTER(BAMColumns), _vp, C.c_uint32, _colp, C.POINTER(_i64), C.POINTER(_i64)]),
     "exon_hip_bam_parser_destroy": (C.c_int, [_vp]),
     "exon_hip_sam_parser_create": (C.c_int, [_vp, C.POINTER(C.c_char_p), _i32, _i64, C.POINTER(_vp)]),
     "exon_hip_sam_parser_parse": (C.c_int, [_vp, _vp, _vp, _i64, C.POINTER(BAMColumns)]),

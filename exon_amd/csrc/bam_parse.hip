@@ -123,7 +123,9 @@ struct exon_hip_bam_parser {
   int64_t max_bytes = 0;
   chain::ChainState chain;
   BamOut out{};
+  ExonBlockBufs* blocks = nullptr;  // exon_hip_bam_parser_cigar_blocks: the block rows of the last slab (cigar_blocks.hip)
   explicit exon_hip_bam_parser(exon_hip_ctx* c) : ctx(c), bufs(c) {}
+  ~exon_hip_bam_parser() { exon_cigar_blocks_free(blocks); }
 };
 
 extern "C" {
@@ -195,6 +197,35 @@ int exon_hip_bam_parser_parse(exon_hip_bam_parser* p, void* stream, const uint8_
   cols->end = p->out.end;
   cols->pos_valid = (uint8_t*)p->out.pos_valid;
   return EXON_HIP_OK;
+}
+
+// The stage a blocks-mode scan runs per slab (scan.cpp, launch_blocks), for a caller that drives the parser itself
+int exon_hip_bam_parser_cigar_blocks(exon_hip_bam_parser* p, void* stream, const uint8_t* d_data, int64_t n_bytes, const exon_hip_bam_columns* cols,
+                                     const uint8_t* d_row_mask, uint32_t cover_ops, exon_hip_column* out, int64_t* n_blocks, int64_t* n_undecided) {
+  static const char* who = "exon_hip_bam_parser_cigar_blocks";
+  if (!p || !cols || !out || !n_blocks || !n_undecided || !d_data) return fail(p ? p->ctx : nullptr, EXON_HIP_EINVAL, "%s: NULL argument", who);
+  exon_hip_ctx* ctx = p->ctx;
+  *n_blocks = *n_undecided = 0;
+  if (cols->n_undecided != 0) return fail(ctx, EXON_HIP_ESTATE, "%s: the parser left the slab undecided: decode it on the host", who);
+  if (cols->ref_id != p->out.ref_id || cols->start != p->out.start || n_bytes <= 0 || n_bytes > p->max_bytes)
+    return fail(ctx, EXON_HIP_EINVAL, "%s: cols / n_bytes are not what the last exon_hip_bam_parser_parse call of this parser returned", who);
+  if (cover_ops == 0 || (cover_ops & ~0x18Du)) return fail(ctx, EXON_HIP_EINVAL, "%s: cover_ops 0x%X is not a non-empty subset of 0x18D (M D N = X, the ops that consume the reference)", who, cover_ops);
+  if (cols->n_rows == 0) return EXON_HIP_OK;
+  ExonBlockSlab in{};
+  in.data = d_data;
+  in.n_bytes = n_bytes;
+  in.rec_of_row = p->out.rec_of_row;
+  in.ref = cols->ref_id;
+  in.ref_valid = cols->ref_valid;
+  in.start = cols->start;
+  in.pos_valid = cols->pos_valid;
+  in.row_mask = d_row_mask;
+  in.n_rows = cols->n_rows;
+  in.cover_ops = cover_ops;
+  int undecided = 0;
+  const int rc = exon_cigar_blocks_slab(ctx, pick_stream(ctx, stream), &p->blocks, in, out, n_blocks, &undecided);
+  *n_undecided = undecided;
+  return rc;
 }
 
 }  // extern "C"

@@ -154,6 +154,7 @@ struct Source {  // resolved FROM clause
   std::vector<int64_t> thresholds;  // depth_thresholds: strictly increasing, each >= 1, at most 8
   int64_t window = 0;       // window_depth: the window width (0: another source)
   std::string genome_file;  // window_depth: contigs and lengths from a bedtools genome file / .fai instead of the file's header
+  uint32_t cover_ops = 0;   // covered_bases / depth_thresholds / window_depth: 'cover=aligned' / 'cover=aligned+del' (exon_hip_scan_set_cover_ops); 0: the span
 };
 
 struct Session {
@@ -309,6 +310,7 @@ void open_scan(const Source& src, const std::string& file, const char* info_fiel
   o.gpu_parse = (for_gpu_query && (src.format == EXON_HIP_FORMAT_VCF || src.format == EXON_HIP_FORMAT_FASTQ || src.format == EXON_HIP_FORMAT_BAM || src.format == EXON_HIP_FORMAT_BCF || src.format == EXON_HIP_FORMAT_SAM || src.format == EXON_HIP_FORMAT_GFF || src.format == EXON_HIP_FORMAT_GTF || src.format == EXON_HIP_FORMAT_BED || src.format == EXON_HIP_FORMAT_FASTA) &&
                  region.empty() && gpu_parse_enabled()) ? 1 : 0;
   ck(nullptr, exon_hip_scan_open(file.c_str(), &o, &g->s));
+  if (src.cover_ops) ck(nullptr, exon_hip_scan_set_cover_ops(g->s, src.cover_ops));  // (a source without a CIGAR: the scan's own refusal)
 }
 
 // CPU plumbing: decode and count rows (optionally with a pushed-down region filter)
@@ -346,6 +348,20 @@ struct Predicate {  // what the WHERE clause turned into
 // the WHERE clause's flag / mapping_quality conjuncts into the scan itself (BAM, SAM; any other source: the scan's own refusal)
 void push_flags(exon_hip_scan* s, const Predicate* pr) {
   if (pr && pr->flags) ck(nullptr, exon_hip_scan_set_flag_predicate(s, pr->flag_mask, pr->flag_value, pr->scan_mapq_min()));
+}
+
+// The last optional argument of covered_bases / depth_thresholds / window_depth: 'cover=span' (the default: a read's whole span),
+// 'cover=aligned' (M = X: samtools depth, bedcov -j) or 'cover=aligned+del' (+ D: samtools depth -J).  false: `arg` is something else.
+bool cover_arg(const std::string& fn, const std::string& arg, Source* src) {
+  if (arg.rfind("cover=", 0) != 0) return false;
+  if (fn == "overlap_counts")
+    throw Err("overlap_counts: 'cover=' belongs to covered_bases, depth_thresholds and window_depth, which add per base; overlap_counts counts records, and a record would count once per aligned block");
+  const std::string v = arg.substr(6);
+  if (v == "span") src->cover_ops = 0;
+  else if (v == "aligned") src->cover_ops = EXON_HIP_COVER_ALIGNED;
+  else if (v == "aligned+del") src->cover_ops = EXON_HIP_COVER_ALIGNED_DEL;
+  else throw Err(fn + ": cover= takes span, aligned or aligned+del, got '" + v + "'");
+  return true;
 }
 
 int cmp_code(const std::string& s) {
@@ -450,7 +466,13 @@ Source resolve_from(Session& se, Parser& ps) {
         src.window = strtoll(w.c_str(), &endp, 10);
         if (*endp) throw Err("window_depth: the window width must be a whole number, got " + w);
         if (src.window < 1) throw Err("window_depth: the window width must be at least 1, got " + w);
-        if (ps.accept_sym(",")) src.genome_file = ps.str();
+        if (ps.accept_sym(",")) {
+          const std::string a = ps.str();
+          if (!cover_arg(lname, a, &src)) {
+            src.genome_file = a;
+            if (ps.accept_sym(",") && !cover_arg(lname, ps.str(), &src)) throw Err(lname + ": the argument behind the genome file is 'cover=span', 'cover=aligned' or 'cover=aligned+del'");
+          }
+        }
       } else {  // ('<file>', '<regions.bed>'[, '<compression>'])
         src.regions_bed = ps.str();
         src.bases = lname == "covered_bases";
@@ -471,7 +493,13 @@ Source resolve_from(Session& se, Parser& ps) {
           }
           if (src.thresholds.empty() || src.thresholds.size() > EXON_HIP_REGION_DEPTH_MAX_THRESHOLDS || (!list.empty() && list.back() == ',')) throw bad;
         }
-        if (ps.accept_sym(",")) src.compression = compression_of(ps.str());
+        if (ps.accept_sym(",")) {
+          const std::string a = ps.str();
+          if (!cover_arg(lname, a, &src)) {
+            src.compression = compression_of(a);
+            if (ps.accept_sym(",") && !cover_arg(lname, ps.str(), &src)) throw Err(lname + ": the argument behind the compression is 'cover=span', 'cover=aligned' or 'cover=aligned+del'");
+          }
+        }
       }
       ps.expect_sym(")");
       std::string stem = lower(path);
@@ -1217,6 +1245,8 @@ int main(int argc, char** argv) {
              "             depth_thresholds('<bam|sam|cram|gff|gtf file>', '<regions.bed>', '<T1,T2,...>'[, 'gzip'])  one row per BED line: contig, start, end, bases, ge_<T> = its bases covered at least T times\n"
              "             window_depth('<bam|sam|cram file>', <W>)                                   one row per window of width W along every contig of the header: contig, start, end, bases\n"
              "             window_depth('<bam|sam|cram|gff|gtf file>', <W>, '<genome file>')          the contigs and lengths from `name<TAB>length` lines (a bedtools genome file, a .fai)\n"
+             "             covered_bases, depth_thresholds and window_depth take one more last argument over a BAM or SAM file: 'cover=span' (the default: a read's whole\n"
+             "             span), 'cover=aligned' (its aligned blocks, M = X: samtools depth, bedcov -j) or 'cover=aligned+del' (+ D: samtools depth -J)\n"
              "  queries:  SELECT COUNT(*) FROM <src> [WHERE chrom = 'c' AND pos >= a AND pos <= b | vcf_region_filter('r', chrom) | bam_region_filter('r', reference, start, end)\n"
              "             | gff_region_filter('r', seqname[, start])]\n"
              "             SELECT COUNT(*) FROM <bam|sam> WHERE [bam_region_filter('r', reference, start, end) AND] flag & M = V [AND CAST(mapping_quality AS INT) >= q]\n"

@@ -22,6 +22,7 @@
 
 #include "arrow_build.h"
 #include "bgzf_index.h"
+#include "cigar_blocks.h"
 #include "cmp_key.h"
 #include "decimal_f32.h"
 #include "io.h"
@@ -946,6 +947,10 @@ struct BAMConfig {
   RegionFilter filter;  // bam_region_filter: SemiLazyRecord::intersects
   FlagPredicate flags;  // ANDed with `filter`; like it the READER'S filter: dropped rows are not built
   uint64_t projection = 0;  // EXON_HIP_PROJECT_BAM_*: name / cigar / sequence / quality_scores behind the default columns
+  // exon_hip_scan_set_cover_ops (BAM, SAM; 0: off).  BLOCKS MODE: a kept record whose reference and position are not NULL becomes
+  // one row per aligned block (cigar_blocks.h: the rule), [start, start - 1] when it has none; any other record stays one row.  The
+  // filters above select RECORDS, by span.  Only the five default columns are built (the scan refuses a projection).
+  uint32_t cover_ops = 0;
 };
 
 // device-layout BAM batch: flag i32, mapq u8? (255 -> NULL), reference dict? (-1 -> NULL), start i64?, end i64?
@@ -1044,6 +1049,22 @@ class BAMArrayBuilder : public ExonArrayBuilder {
       end_.append_value(pos0 + 1 + ref_len - 1);  // alignment_end = start + reference length - 1
     }
     ++rows_;
+  }
+  // blocks mode: one aligned block [s, e] of a record whose reference and position are not NULL
+  void append_block(int32_t flag, int32_t ref_id, int mapq, int64_t s, int64_t e) {
+    flag_.append_value(flag);
+    if (mapq == 255) mapq_.append_null(255);
+    else mapq_.append_value((uint8_t)mapq);
+    ref_.append_value(ref_id);
+    start_.append_value(s);
+    end_.append_value(e);
+    ++rows_;
+  }
+  // the blocks of such a record, [start, start - 1] when it has none
+  template <typename Ops>
+  void append_blocks(Ops ops, uint32_t cover_ops, int32_t flag, int32_t ref_id, int mapq, int64_t start) {
+    const uint32_t k = cigar::walk_blocks(ops, start, cover_ops, [&](uint32_t, int64_t s, int64_t e) { append_block(flag, ref_id, mapq, s, e); });
+    if (!k) append_block(flag, ref_id, mapq, start, start - 1);
   }
   size_t len() const override { return rows_; }
   std::vector<struct ArrowArray*> finish() override {
@@ -1147,6 +1168,16 @@ class BAMBatchReader : public BatchReader {
         if (!(ref_id == region_ref_id_ && s <= rg.end && rg.start <= e)) continue;
       }
       if (cfg_.flags.active && !bam_flag_hit(rec.data(), cfg_.flags)) continue;
+      ++records;
+      if (cfg_.cover_ops && ref_id >= 0 && pos >= 0) {
+        const cigar::ByteOps ops{rec.data() + co, n_cigar};
+        uint32_t l_seq;
+        memcpy(&l_seq, &rec[16], 4);
+        if (cigar::is_cg_placeholder(ops, l_seq))
+          throw std::runtime_error("BAM record's CIGAR is the placeholder of a CG tag (" + std::to_string(l_seq) + "S then N): the real ops are in the CG tag, which is not read; aligned blocks cannot be made for this file");
+        b.append_blocks(ops, cfg_.cover_ops, (int32_t)flag, ref_id, mapq, (int64_t)pos + 1);
+        continue;
+      }
       b.append((int32_t)flag, ref_id, pos, mapq, ref_len);
       b.append_text(rec.data(), rec.size());
     }
@@ -1169,6 +1200,7 @@ class BAMBatchReader : public BatchReader {
   std::string header_text;
   std::vector<std::string> ref_names;
   std::vector<int32_t> ref_lengths;
+  int64_t records = 0;  // records built so far (in blocks mode a batch has more rows than records)
   int n_chunks = -1;
   std::vector<Chunk> planned_chunks;  // the chunks of an indexed scan (the GPU decode path ships exactly these blocks)
   int32_t region_ref_id() const { return region_ref_id_; }  // header index of the pushed-down region's reference (-2: unknown)
@@ -1285,6 +1317,14 @@ class SAMBatchReader : public BatchReader {
         if (!(ref_id == region_ref_id_ && pos1 <= rg.end && rg.start <= e)) continue;
       }
       if (cfg_.flags.active && !sam_flag_hit(f[1], fl[1], f[4], fl[4], cfg_.flags)) continue;
+      ++records;
+      if (cfg_.cover_ops && ref_id >= 0 && pos1 >= 1) {
+        const uint8_t* cg = reinterpret_cast<const uint8_t*>(f[5]);
+        if (!cigar::text_ops_ok(cg, cg + fl[5])) throw std::runtime_error("invalid CIGAR '" + std::string(f[5], fl[5]) + "'");
+        const bool none = fl[5] == 1 && f[5][0] == '*';
+        b.append_blocks(cigar::TextOps{cg, cg + (none ? 0 : fl[5])}, cfg_.cover_ops, flag, ref_id, mapq, pos1);
+        continue;
+      }
       if (cfg_.projection) {
         if (nf < 11) throw std::runtime_error("SAM record has fewer than 11 fields");
         b.append_sam_text(f[0], fl[0], f[5], fl[5], f[9], fl[9], f[10], fl[10]);
@@ -1308,6 +1348,7 @@ class SAMBatchReader : public BatchReader {
   std::string header_text;
   std::vector<std::string> ref_names;
   std::vector<int32_t> ref_lengths;
+  int64_t records = 0;  // records built so far (in blocks mode a batch has more rows than records)
 
  private:
   BufReader r_;

@@ -162,6 +162,26 @@ const unsigned* exon_hip_sam_parser_newlines(exon_hip_sam_parser* p);      // gp
 const uint32_t* exon_hip_bam_parser_row_records(exon_hip_bam_parser* p);
 const uint32_t* exon_hip_bcf_parser_row_records(exon_hip_bcf_parser* p);   // bcf_parse.hip: the same for BCF records   // bam_parse.hip: byte offset of every row's record
 
+// cigar_blocks.hip: one slab's alignment rows -> their aligned blocks as rows (ref_id, start, end) with ONE validity bitmap, in buffers
+// that belong to the scan (exon_hip_scan_set_cover_ops).  rec_of_row set: a BAM slab (`data` = the records); else a SAM slab (`data` =
+// the text as the parser was given it, `newlines` = its line index).  *undecided: the host reader takes the file.
+struct ExonBlockBufs;
+struct ExonBlockSlab {
+  const uint8_t* data;
+  int64_t n_bytes;
+  const uint32_t* rec_of_row;
+  const unsigned* newlines;
+  const int32_t* ref;
+  const uint8_t* ref_valid;
+  const int64_t* start;
+  const uint8_t* pos_valid;
+  const uint8_t* row_mask;  // NULL: every row is kept
+  int64_t n_rows;
+  uint32_t cover_ops;
+};
+int exon_cigar_blocks_slab(exon_hip_ctx* ctx, void* stream, ExonBlockBufs** bufs, const ExonBlockSlab& in, exon_hip_column* cols /*[3]*/, int64_t* n_blocks, int* undecided);
+void exon_cigar_blocks_free(ExonBlockBufs* b);
+
 // capi.cpp: size-keyed recycling of device buffers (released by exon_hip_ctx_destroy)
 void* exon_pool_alloc(exon_hip_ctx* ctx, size_t bytes);
 void exon_pool_free(exon_hip_ctx* ctx, void* p);

@@ -93,6 +93,10 @@ struct exon_hip_scan {
   // pushed-down flag / mapping-quality predicate (exon_hip_scan_set_flag_predicate; BAM, SAM): the host reader's filter
   // (BAMConfig::flags) and, on the GPU decode path, k_flag_mapq_mask in k_value_mask's place
   exon::FlagPredicate flags;
+  // blocks mode (exon_hip_scan_set_cover_ops; BAM, SAM; 0: off): every kept record reaches the plan as its aligned blocks -- the host
+  // readers emit them (BAMConfig::cover_ops), the GPU decode path expands each slab's rows (cigar_blocks.hip) into these buffers
+  uint32_t cover_ops = 0;
+  ExonBlockBufs* block_bufs = nullptr;
   // exon_hip_scan_export_stats: written by the exporter's producer thread, read when the scan has ended
   std::atomic<int64_t> stat_slabs{0}, stat_compacted{0}, stat_d2h{0};
 
@@ -409,6 +413,7 @@ static std::unique_ptr<exon::BatchReader> open_reader(const exon_hip_scan& s, De
   // (set after the scan was opened: exon_hip_scan_set_flag_predicate re-opens the reader)
   auto flagged = [&](exon::BAMConfig cfg) {
     cfg.flags = s.flags;
+    cfg.cover_ops = s.cover_ops;  // (exon_hip_scan_set_cover_ops, the same way)
     return cfg;
   };
   switch (s.format) {
@@ -602,21 +607,32 @@ int exon_hip_scan_schema(exon_hip_scan* s, struct ArrowSchema* out) {
   }
 }
 
-int exon_hip_scan_next(exon_hip_scan* s, struct ArrowArray* out) {
-  if (!s || !out) return fail(nullptr, EXON_HIP_EINVAL, "exon_hip_scan_next: NULL argument");
-  if (s->gpu_parse && s->exporter) return gpu_next(s, out);
-  if (s->gpu_parse)
-    return fail(nullptr, EXON_HIP_ESTATE, "this scan was opened with gpu_parse: use exon_hip_stream_consume_scan, or exon_hip_scan_bind_ctx for batches from the GPU pipeline");
+// the host reader's next batch.  s->rows counts RECORDS: in blocks mode a batch has a row per aligned block
+static int host_next(exon_hip_scan* s, struct ArrowArray* out, int64_t* records) {
   try {
     memset(out, 0, sizeof *out);
+    const int64_t before = s->bam() ? s->bam()->records : s->sam() ? s->sam()->records : 0;
     if (!s->reader->read_batch(out)) return 1;
-    s->rows += out->length;
+    *records = s->cover_ops ? (s->bam() ? s->bam()->records : s->sam()->records) - before : out->length;
+    s->rows += *records;
     return EXON_HIP_OK;
   } catch (const exon::UnsupportedError& e) {
     return fail(nullptr, EXON_HIP_EUNSUPPORTED, "%s", e.what());
   } catch (const std::exception& e) {
     return fail(nullptr, EXON_HIP_EINVAL, "%s", e.what());
   }
+}
+static const char* const BLOCKS_MODE_BATCHES =
+    "a scan in blocks mode (exon_hip_scan_set_cover_ops) serves fused plans of kinds 12, 13 and 14 only: batches keep the reference's schema of one row per record";
+
+int exon_hip_scan_next(exon_hip_scan* s, struct ArrowArray* out) {
+  if (!s || !out) return fail(nullptr, EXON_HIP_EINVAL, "exon_hip_scan_next: NULL argument");
+  if (s->cover_ops) return fail(nullptr, EXON_HIP_EUNSUPPORTED, "exon_hip_scan_next: %s", BLOCKS_MODE_BATCHES);
+  if (s->gpu_parse && s->exporter) return gpu_next(s, out);
+  if (s->gpu_parse)
+    return fail(nullptr, EXON_HIP_ESTATE, "this scan was opened with gpu_parse: use exon_hip_stream_consume_scan, or exon_hip_scan_bind_ctx for batches from the GPU pipeline");
+  int64_t records = 0;
+  return host_next(s, out, &records);
 }
 
 int exon_hip_scan_dictionary_size(exon_hip_scan* s, int32_t column, int32_t* size) {
@@ -698,6 +714,7 @@ int exon_hip_index_query(const char* index_path, int32_t is_bai, const char* ref
 int exon_hip_scan_bind_ctx(exon_hip_scan* s, exon_hip_ctx* ctx) {
   if (!s || !ctx) return fail(ctx, EXON_HIP_EINVAL, "exon_hip_scan_bind_ctx: NULL argument");
   if (s->exporter) return fail(ctx, EXON_HIP_ESTATE, "the scan is bound to a context already");
+  if (s->cover_ops) return fail(ctx, EXON_HIP_EUNSUPPORTED, "exon_hip_scan_bind_ctx: %s", BLOCKS_MODE_BATCHES);
   if (s->format == EXON_HIP_FORMAT_CRAM)
     return fail(ctx, EXON_HIP_EUNSUPPORTED, "batches from the GPU pipeline: VCF, BCF, BAM, SAM, FASTQ, FASTA, GFF, GTF and BED scans (CRAM batches come from the host reader)");
   if (!s->gpu_parse && !s->fasta_gpu_request)  // not opened with gpu_parse, or String / list-valued INFO keys were named: the host reader builds those columns
@@ -773,6 +790,30 @@ int exon_hip_scan_set_flag_predicate(exon_hip_scan* s, int32_t flag_mask, int32_
   return EXON_HIP_OK;
 }
 
+int exon_hip_scan_set_cover_ops(exon_hip_scan* s, uint32_t cover_ops) {
+  static const char* who = "exon_hip_scan_set_cover_ops";
+  if (!s) return fail(nullptr, EXON_HIP_EINVAL, "%s: NULL argument", who);
+  if (s->format == EXON_HIP_FORMAT_CRAM)
+    return fail(nullptr, EXON_HIP_EUNSUPPORTED, "%s: the CRAM decoder reconstructs an alignment's span only, not its CIGAR; aligned blocks come from BAM and SAM scans", who);
+  if (s->format != EXON_HIP_FORMAT_BAM && s->format != EXON_HIP_FORMAT_SAM)
+    return fail(nullptr, EXON_HIP_EUNSUPPORTED, "%s: this format's records have no CIGAR; aligned blocks come from BAM and SAM scans", who);
+  if (s->exporter || s->rows != 0)
+    return fail(nullptr, EXON_HIP_ESTATE, "%s: the scan %s already; set the mask right after exon_hip_scan_open", who, s->exporter ? "is bound to a context" : "has been read from");
+  if (cover_ops != 0 && !exon::cigar::cover_ops_ok(cover_ops))
+    return fail(nullptr, EXON_HIP_EINVAL, "%s: cover_ops 0x%X is not a subset of 0x18D (M D N = X, the ops that consume the reference)", who, cover_ops);
+  if (cover_ops != 0 && s->opt.projection)
+    return fail(nullptr, EXON_HIP_EUNSUPPORTED, "%s: a blocks-mode scan serves fused plans only and builds none of the projected columns; open the scan without a projection", who);
+  const uint32_t before = s->cover_ops;
+  s->cover_ops = cover_ops;
+  try {  // the reader starts over with the mask in its config (nothing has been read: the header again, that is all)
+    s->reader = open_reader(*s, s->gpu_parse ? Decode::Device : Decode::Host);
+  } catch (const std::exception& e) {
+    s->cover_ops = before;
+    return fail(nullptr, EXON_HIP_EINVAL, "%s", e.what());
+  }
+  return EXON_HIP_OK;
+}
+
 int exon_hip_scan_export_stats(exon_hip_scan* s, int64_t* slabs, int64_t* compacted_slabs, int64_t* d2h_bytes) {
   if (!s) return fail(nullptr, EXON_HIP_EINVAL, "exon_hip_scan_export_stats: NULL argument");
   if (slabs) *slabs = s->stat_slabs.load();
@@ -788,6 +829,7 @@ int exon_hip_scan_close(exon_hip_scan* s) {
   if (s && s->take_scratch) exon_take_scratch_destroy(s->take_scratch);
   if (s && s->d_region_mask) hipFree(s->d_region_mask);
   if (s && s->d_region_pass) hipFree(s->d_region_pass);
+  if (s) exon_cigar_blocks_free(s->block_bufs);
   delete s;
   return EXON_HIP_OK;
 }
@@ -2749,6 +2791,33 @@ static int build_text(exon_hip_scan* scan, exon_hip_ctx* ctx, hipStream_t hs, co
   return r;
 }
 
+// Blocks mode (exon_hip_scan_set_cover_ops): the slab's rows -> the aligned blocks of its kept records (cigar_blocks.hip) -> the plan
+// over THEM: reference, start and end come from the block rows and share their one validity bitmap, in which the row mask has
+// already been spent.  The region and flag predicates have selected RECORDS, by span, before this.  1: the host reader takes over.
+static int launch_blocks(exon_hip_scan* scan, exon_hip_ctx* ctx, exon_hip_stream* st, hipStream_t hs, const uint8_t* d_text, size_t n, const SlabParse& p,
+                         const uint8_t* row_mask) {
+  ExonBlockSlab in{};
+  in.data = d_text;
+  in.n_bytes = (int64_t)n;
+  if (scan->bam()) in.rec_of_row = exon_hip_bam_parser_row_records(scan->parser.as<exon_hip_bam_parser>());
+  else in.newlines = exon_hip_sam_parser_newlines(scan->parser.as<exon_hip_sam_parser>());
+  if (!in.rec_of_row && !in.newlines) return fail(ctx, EXON_HIP_ESTATE, "aligned blocks: the device parser kept no record index");
+  in.ref = static_cast<const int32_t*>(p.sc[2].values);
+  in.ref_valid = p.sc[2].validity;
+  in.start = static_cast<const int64_t*>(p.sc[3].values);
+  in.pos_valid = p.sc[3].validity;
+  in.row_mask = row_mask;
+  in.n_rows = p.n_rows;
+  in.cover_ops = scan->cover_ops;
+  exon_hip_column sc[4 + EXON_HIP_MAX_INFO_FIELDS];
+  std::copy(std::begin(p.sc), std::end(p.sc), sc);
+  int64_t n_blocks = 0;
+  int undecided = 0;
+  if (const int rc = exon_cigar_blocks_slab(ctx, hs, &scan->block_bufs, in, &sc[2], &n_blocks, &undecided)) return rc;
+  if (undecided) return 1;
+  return exon_hip_stream_launch_scan_columns(st, sc, 4 + EXON_HIP_MAX_INFO_FIELDS, n_blocks, nullptr);
+}
+
 // file -> text slabs in HBM (GpuTextSource) -> GPU parser -> fused kernel (or, bound to an exporter, batches).  Returns 1 when the
 // device could not decide something: the caller restores the state and re-decodes the file on the host.
 static int consume_text_gpu(exon_hip_stream* st, exon_hip_scan* scan, int64_t* rows_out) {
@@ -2914,6 +2983,8 @@ static int consume_text_gpu(exon_hip_stream* st, exon_hip_scan* scan, int64_t* r
           SlabText text;
           text.build = [&] { return build_text(scan, ctx, hs, d_text, n, n_rows, &text); };
           rc = export_slab(scan, p.sc, n_rows, row_mask, hs, &text);
+        } else if (scan->cover_ops && !scan->exporter) {
+          rc = launch_blocks(scan, ctx, st, hs, d_text, n, p, row_mask);
         } else {
           rc = scan->exporter ? export_slab(scan, p.sc, n_rows, row_mask, hs, nullptr)
                               : exon_hip_stream_launch_scan_columns(st, p.sc, 4 + EXON_HIP_MAX_INFO_FIELDS, n_rows, row_mask);
@@ -3141,6 +3212,13 @@ extern "C" {
 
 int exon_hip_stream_consume_scan(exon_hip_stream* st, exon_hip_scan* scan, int64_t* rows) {
   if (!st || !scan) return fail(nullptr, EXON_HIP_EINVAL, "exon_hip_stream_consume_scan: NULL argument");
+  if (scan->cover_ops) {  // before anything is read: the stream and the scan stay as they are
+    const int kind = exon_hip_stream_plan_kind(st);
+    if (kind != EXON_HIP_PLAN_REGION_SET_BASES && kind != EXON_HIP_PLAN_WINDOW_BASES && kind != EXON_HIP_PLAN_REGION_SET_DEPTH)
+      return fail(exon_hip_stream_ctx(st), EXON_HIP_EUNSUPPORTED,
+                  "a scan in blocks mode (exon_hip_scan_set_cover_ops) serves plans of kinds 12, 13 and 14, which add per base; a plan of kind %d counts records, and a record would count once per aligned block",
+                  kind);
+  }
   // a region plan fed by files names its contig; every file numbers its contigs in its own header order
   std::string contig;
   if (exon_hip_stream_region_contig(st, &contig)) {
@@ -3320,10 +3398,11 @@ static int consume_scan_impl(exon_hip_stream* st, exon_hip_scan* scan, int64_t* 
   }
   for (;;) {
     struct ArrowArray batch;
-    int rc = exon_hip_scan_next(scan, &batch);
+    int64_t records = -1;  // (blocks mode: the host reader's batches carry a row per aligned block; `rows` stays records)
+    int rc = scan->cover_ops ? host_next(scan, &batch, &records) : exon_hip_scan_next(scan, &batch);
     if (rc == 1) break;
     if (rc < 0) return rc;
-    n += batch.length;
+    n += records >= 0 ? records : batch.length;
     rc = exon_hip_stream_push(st, &batch);  // moves the batch
     if (rc < 0) return rc;
   }

@@ -406,6 +406,49 @@ class Context:
         self._check(self.lib.exon_hip_window_bases(self.h, stream, C.byref(c0), C.byref(c1), C.byref(c2), n, plan.h,
                                                    d_state.ptr if isinstance(d_state, DeviceBuffer) else d_state))
 
+    def cigar_blocks(self, ref_id, ref_valid, start, start_valid, cigar_offsets, cigar_ops, n, cover_ops, out_ref, out_start, out_end, out_valid,
+                     cap, stream=None):
+        """exon_hip_cigar_blocks: n alignment rows and their CIGAR ops (an Arrow List<UInt32> on the device, `len << 4 | code`) -> the
+        aligned block rows kinds 12 - 14 take in place of the spans.  Returns the rows emitted.  Synchronous.  A `cap` too small
+        raises ExonHipError(ECAPACITY) with the need in its `.need`; nothing has been written then."""
+        def p(x):
+            return None if x is None else x.ptr if isinstance(x, DeviceBuffer) else int(x)
+        c0, c1 = _col(ref_id, ref_valid, None, n), _col(start, start_valid, None, n)
+        need = C.c_int64()
+        rc = self.lib.exon_hip_cigar_blocks(self.h, stream, C.byref(c0), C.byref(c1), p(cigar_offsets), p(cigar_ops), n, cover_ops_mask(cover_ops),
+                                            p(out_ref), p(out_start), p(out_end), p(out_valid), int(cap), C.byref(need))
+        if rc < 0:
+            e = ExonHipError(rc, self._last_error())
+            e.need = need.value
+            raise e
+        return need.value
+
+
+def cover_ops_mask(cover_ops):
+    """'aligned' (M = X: `samtools depth`, `bedcov -j`), 'aligned+del' (+ D: `samtools depth -J`) or the mask itself"""
+    if isinstance(cover_ops, str):
+        try:
+            return {"aligned": L.COVER_ALIGNED, "aligned+del": L.COVER_ALIGNED_DEL}[cover_ops]
+        except KeyError:
+            raise ValueError(f"cover_ops {cover_ops!r}: 'aligned', 'aligned+del' or a mask of BAM op codes") from None
+    return int(cover_ops)
+
+
+def cigar_blocks_host(ops, start, cover_ops, cap=None):
+    """exon_hip_cigar_blocks_host (host-only): the aligned blocks [(first, last)] of one record whose ops are `len << 4 | code`.
+    `cap`: room for that many blocks (default: all of them); fewer than the record has raises ExonHipError(ECAPACITY), `.need` = k."""
+    lib = L.load()
+    ops = np.ascontiguousarray(ops, dtype=np.uint32)
+    cap = len(ops) if cap is None else int(cap)
+    s, e = np.empty(max(cap, 1), np.int64), np.empty(max(cap, 1), np.int64)
+    k = C.c_int32()
+    rc = lib.exon_hip_cigar_blocks_host(ops.ctypes.data if len(ops) else None, len(ops), int(start), cover_ops_mask(cover_ops), s.ctypes.data, e.ctypes.data, cap, C.byref(k))
+    if rc < 0:
+        err = ExonHipError(rc, lib.exon_hip_last_error(None).decode(errors="replace"))
+        err.need = k.value
+        raise err
+    return list(zip(s[:k.value].tolist(), e[:k.value].tolist()))
+
 
 def region_bases_layout(plan):
     """exon_hip_region_bases_layout (host-only): word offsets of the totals / Ns / Ss / Ne / Se sections of a kind-12 plan's state,
@@ -568,8 +611,11 @@ class Scan:
                "gff": {"attributes": 256}, "gtf": {"attributes": 256}, "bed": L.PROJECT_BED}
 
     def __init__(self, path, fmt, compression=None, batch_size=0, info_field=None, region=None, use_index=False,
-                 gpu_parse=False, project=(), where=None, where_flags=None, formats_on_device=False):
-        """formats_on_device: VCF, next to "formats" in `project`: the modifier EXON_HIP_PROJECT_VCF_FORMATS_ON_DEVICE -- a gpu_parse scan
+                 gpu_parse=False, project=(), where=None, where_flags=None, formats_on_device=False, cover_ops=None):
+        """cover_ops: "aligned" (M = X: `samtools depth`, `bedcov -j`), "aligned+del" (+ D: `samtools depth -J`) or a mask of BAM op
+        codes inside 0x18D (exon_hip_scan_set_cover_ops; BAM, SAM): BLOCKS MODE -- plans of kinds 12, 13 and 14 get every kept record
+        as its aligned blocks instead of its span; nothing else may read the scan.
+        formats_on_device: VCF, next to "formats" in `project`: the modifier EXON_HIP_PROJECT_VCF_FORMATS_ON_DEVICE -- a gpu_parse scan
         then prints the column on the device instead of decoding on the host (no column of its own; the open refuses it without "formats").
         where_flags: (mask, value[, mapq_min]), the flag / mapping-quality predicate a BAM or SAM scan evaluates itself
         (exon_hip_scan_set_flag_predicate): rows with (flag & mask) != value, or -- for a mapq_min >= 0 -- a NULL or smaller
@@ -612,6 +658,12 @@ class Scan:
             except Exception:
                 self.close()
                 raise
+        if cover_ops is not None and cover_ops != 0:  # (0 is "off", like None: no call, so no refusal on a format without a CIGAR)
+            try:
+                self.set_cover_ops(cover_ops)
+            except Exception:
+                self.close()
+                raise
 
     WHERE_OPS = {">": 0, ">=": 1, "<": 2, "<=": 3, "=": 4, "!=": 5}
 
@@ -625,6 +677,12 @@ class Scan:
         """exon_hip_scan_set_flag_predicate (BAM, SAM): before bind_ctx / the first batch / Stream.consume; a second call replaces the
         first.  mapq_min < 0: no conjunct on mapping_quality."""
         self._check(self.lib.exon_hip_scan_set_flag_predicate(self.h, int(mask), int(value), int(mapq_min)))
+        return self
+
+    def set_cover_ops(self, cover_ops):
+        """exon_hip_scan_set_cover_ops (BAM, SAM): before the first Stream.consume; a second call replaces the first, 0 turns blocks mode
+        off.  `cover_ops`: "aligned", "aligned+del" or the mask."""
+        self._check(self.lib.exon_hip_scan_set_cover_ops(self.h, cover_ops_mask(cover_ops)))
         return self
 
     def export_stats(self):
@@ -1071,6 +1129,22 @@ class BAMParser:
                 "mapq_valid": get(cols.mapq_valid, np.uint8, nb), "ref_id": get(cols.ref_id, np.int32, n),
                 "ref_valid": get(cols.ref_valid, np.uint8, nb), "start": get(cols.start, np.int64, n),
                 "end": get(cols.end, np.int64, n), "pos_valid": get(cols.pos_valid, np.uint8, nb)}
+
+    def parse(self, d_data, n_bytes, stream=None):
+        """exon_hip_bam_parser_parse over record bytes resident in HBM: the columns struct (device pointers into the parser's buffers)"""
+        cols = L.BAMColumns()
+        self.ctx._check(self.ctx.lib.exon_hip_bam_parser_parse(self.h, stream, d_data.ptr if isinstance(d_data, DeviceBuffer) else d_data, int(n_bytes), C.byref(cols)))
+        return cols
+
+    def cigar_blocks(self, d_data, n_bytes, cols, cover_ops, row_mask=None, stream=None):
+        """exon_hip_bam_parser_cigar_blocks: the aligned blocks of the slab `parse` has just split -> (n_blocks, n_undecided, [ref, start,
+        end] as L.Column: device pointers into the parser's buffers, one validity bitmap).  What a blocks-mode scan runs per slab."""
+        out = (L.Column * 3)()
+        n, u = C.c_int64(), C.c_int64()
+        p = lambda x: None if x is None else x.ptr if isinstance(x, DeviceBuffer) else int(x)
+        self.ctx._check(self.ctx.lib.exon_hip_bam_parser_cigar_blocks(self.h, stream, p(d_data), int(n_bytes), C.byref(cols), p(row_mask), cover_ops_mask(cover_ops), out,
+                                                                    C.byref(n), C.byref(u)))
+        return n.value, u.value, out
 
     def close(self):
         if self.h:

@@ -422,8 +422,8 @@ int exon_hip_region_set_overlap(exon_hip_ctx* ctx, void* stream, const exon_hip_
  * wraps, and for coordinate sums beyond 2^63.  A single word of Ss / Se is therefore meaningful only modulo 2^64.
  *
  * What it does not compute: the alignment span [start, end] counts as covered, deletions and reference skips included, as the `end`
- * column defines it -- there is no CIGAR-aware split; there is no per-base depth, only the sum per region; a BED source is not
- * served.
+ * column defines it (the CIGAR-aware rows are exon_hip_cigar_blocks'); there is no per-base depth, only the sum per region; a BED
+ * source is not served.
  *
  * exon_hip_plan_create_region_set_bases takes exon_hip_plan_create_region_set's arguments under the same rules and error classes
  * (ids form or names form, 1 <= start <= end with an open end allowed, at most 1048576 regions, ctx may be NULL for a host-only
@@ -472,9 +472,9 @@ int exon_hip_region_set_bases(exon_hip_ctx* ctx, void* stream, const exon_hip_co
  * and per contig  bases_j = E[j] + W * (D[0] + ... + D[j])  (DESIGN.md 3.7): a window strictly between two others is never a contig's
  * short last window.  ARITHMETIC IS MODULO 2^64, as kind 12's; the -1 is an add of 2^64 - 1.
  *
- * What it does not compute: the alignment span [start, end] counts as covered, deletions and reference skips included -- there is no
- * CIGAR-aware split; there is no per-base track, only the sum per window (W = 1 gives one, at 16 bytes a base); a BED source is not
- * served.
+ * What it does not compute: the alignment span [start, end] counts as covered, deletions and reference skips included (the
+ * CIGAR-aware rows are exon_hip_cigar_blocks'); there is no per-base track, only the sum per window (W = 1 gives one, at 16 bytes a
+ * base); a BED source is not served.
  *
  * exon_hip_plan_create_window_bases names its contigs by kind 11 / 12's rules and error classes: ids form (packed_contig_names NULL;
  * a negative id is EXON_HIP_EINVAL, one of EXON_HIP_MAX_REFERENCES or more EXON_HIP_EUNSUPPORTED) or names form (n_contigs
@@ -532,8 +532,8 @@ int exon_hip_window_bases(exon_hip_ctx* ctx, void* stream, const exon_hip_column
  * input.  DECISION (kind 11's): a row with end < start adds to `inverted` and to no bin.
  * THE DECODE IS NOT LINEAR: bases_i adds over partial states, the threshold counts do not.  Add the states, then decode or reduce.
  *
- * What it does not compute: the alignment span [start, end] counts as covered, deletions and reference skips included -- there is no
- * CIGAR-aware split; a BED source is not served; there are no open-ended regions.
+ * What it does not compute: the alignment span [start, end] counts as covered, deletions and reference skips included (the
+ * CIGAR-aware rows are exon_hip_cigar_blocks'); a BED source is not served; there are no open-ended regions.
  *
  * exon_hip_plan_create_region_set_depth takes exon_hip_plan_create_region_set's region arguments under the same rules and error
  * classes (ids form or names form, 1 <= start <= end, at most 1048576 regions, duplicate, nested and overlapping regions legal and
@@ -572,6 +572,46 @@ int exon_hip_region_depth_reduce(exon_hip_ctx* ctx, void* stream, const exon_hip
 /* K14, bare operator (ids form; `ctx` is the plan's): d_state (exon_hip_plan_state_size words) += this batch */
 int exon_hip_region_set_depth(exon_hip_ctx* ctx, void* stream, const exon_hip_column* ref_id /*i32*/, const exon_hip_column* start /*i64*/,
                               const exon_hip_column* end /*i64*/, int64_t n, const exon_hip_plan* plan, int64_t* d_state);
+
+/* ---- aligned blocks: alignment rows -> the CIGAR-aware interval rows of kinds 12 - 14 (additive; the ABI stays 5) -------------------
+ * Kinds 12 - 14 count a row's whole span [start, end].  For alignments that is `bedtools`' / `samtools bedcov`'s default and the wrong
+ * answer for `samtools depth` and `bedcov -j`: the intron of a spliced read (50M10000N50M) and every deletion count as covered.  All
+ * three plans add per base, so a read may be replaced by its disjoint aligned blocks with no change to any plan: this operator makes
+ * the block rows, the plans' operators (or exon_hip_stream_push_device) take them as they take any interval rows.
+ *
+ * cover_ops: bit i = "the reference positions under a CIGAR op of BAM code i are covered" (codes: M 0, I 1, D 2, N 3, S 4, H 5, P 6,
+ * = 7, X 8).  Legal bits are the ops that consume the reference, M D N = X: a non-empty subset of 0x18D, anything else is
+ * EXON_HIP_EINVAL.  EXON_HIP_COVER_ALIGNED (M = X) is `samtools depth` and `bedcov -j`, EXON_HIP_COVER_ALIGNED_DEL (+ D) is `samtools
+ * depth -J`, 0x18D gives the span back.
+ * THE RULE (exon_amd/csrc/host/cigar_blocks.h, one function for the host and both device passes).  Walk the ops from `start`: an op
+ * whose code is in 0x18D advances the position by its length, counted or not; every other op (codes 9 - 15 included) advances
+ * nothing.  The covered positions are the union of the counted ops' intervals, and a BLOCK is a maximal run of consecutive covered
+ * positions, 1-based inclusive like its row: 10M5I10M is one block, 5M0N5M is one, 5M3D5M without D is two, a zero-length counted op
+ * makes none.  A record has k >= 0 blocks.  Ops are u32 in BAM's encoding, len << 4 | code.
+ *
+ * exon_hip_cigar_blocks: n rows of ref_id (i32) and start (i64), each with an optional validity bitmap, and an Arrow List<UInt32> of
+ * ops on the device: d_cigar_offsets[n + 1] (int32, the first may be non-zero, in order) and d_cigar_ops.  Row r emits max(1, k)
+ * rows of (d_out_ref, d_out_start, d_out_end) and one bit each of d_out_valid, ONE bitmap for the three columns: a row whose ref_id or
+ * start is NULL emits one invalid row (values 0); a valid row of k = 0 emits the valid row [start, start - 1], which the plans count
+ * as `inverted`, as they count such a record in span mode; a valid row of k >= 1 emits its blocks in order.  So the plans' four
+ * totals count BLOCK ROWS, not records.  cap = the rows the three value buffers hold; d_out_valid holds 4 * ceil(cap / 32) bytes and
+ * is 4-byte aligned (bits behind the last row of its last word are 1).  *n_blocks = the rows emitted.  When cap is too small the call
+ * is EXON_HIP_ECAPACITY, *n_blocks is the need and NOTHING has been written (cap = 0 with NULL buffers asks for the need alone).
+ * Offsets out of order are EXON_HIP_EINVAL; no op is loaded from outside [offsets[0], offsets[n]).  n = 0 is OK and launches nothing;
+ * n >= 2^31 is EXON_HIP_EUNSUPPORTED.  SYNCHRONOUS on `stream` (the total comes back in one small copy between the two passes).  Values
+ * need their element's alignment only.  A BAM record whose CIGAR is the two-op placeholder of a CG tag cannot be told from its ops
+ * alone: a caller that decodes BAM itself must expand or refuse it before this call.
+ * exon_hip_cigar_blocks_host: the rule for ONE record on the host, no ctx and no device: the first min(k, cap) blocks into out_start /
+ * out_end, *n_blocks = k; k > cap is EXON_HIP_ECAPACITY, n_ops = 0 gives k = 0.
+ * BAM and SAM scans make the same rows themselves: exon_hip_scan_set_cover_ops.  Not here: CRAM, the CG tag, mate-overlap
+ * correction. */
+#define EXON_HIP_COVER_ALIGNED 0x181u     /* M = X */
+#define EXON_HIP_COVER_ALIGNED_DEL 0x185u /* M D = X */
+int exon_hip_cigar_blocks(exon_hip_ctx* ctx, void* stream, const exon_hip_column* ref_id /*i32*/, const exon_hip_column* start /*i64*/,
+                          const int32_t* d_cigar_offsets /*[n + 1]*/, const uint32_t* d_cigar_ops, int64_t n, uint32_t cover_ops,
+                          int32_t* d_out_ref, int64_t* d_out_start, int64_t* d_out_end, uint8_t* d_out_valid, int64_t cap, int64_t* n_blocks);
+int exon_hip_cigar_blocks_host(const uint32_t* ops, int32_t n_ops, int64_t start, uint32_t cover_ops, int64_t* out_start, int64_t* out_end,
+                               int32_t cap, int32_t* n_blocks);
 
 /* Stateless form of a push: run the plan's fused kernel over HBM-resident columns (`columns[i]` = operator argument i, see
  * exon_hip_plan_desc.columns for the order; n_columns must match the plan) on the caller's hipStream_t into a caller-owned
@@ -900,6 +940,24 @@ int exon_hip_scan_set_predicate(exon_hip_scan* scan, int32_t column, int32_t cmp
  * only they are copied back (exon_hip_scan_export_stats).  A fused plan over such a scan sees the kept rows only: K3 gets a second
  * conjunct, K6 / K7 count kept rows. */
 int exon_hip_scan_set_flag_predicate(exon_hip_scan* scan, int32_t flag_mask, int32_t flag_value, int32_t mapq_min);
+/* (additive; the ABI stays 5)
+ * BLOCKS MODE: the scan hands a plan every kept record as its ALIGNED BLOCKS instead of its span (exon_hip_cigar_blocks above states
+ * the rule, cover_ops and the rows a record emits).  cover_ops = 0 turns it off; any bit outside 0x18D is EXON_HIP_EINVAL.
+ * EXON_HIP_FORMAT_BAM and EXON_HIP_FORMAT_SAM only (plain, gzip, BGZF; with or without `region`, use_index or a flag predicate); any
+ * other format is EXON_HIP_EUNSUPPORTED with the reason (CRAM: the decoder reconstructs the span only; GFF, GTF, BED and the rest
+ * have no CIGAR), and so is a scan opened with a projection.  Call order and EXON_HIP_ESTATE as exon_hip_scan_set_flag_predicate; a
+ * second call replaces the first.
+ * The region and the flag predicate keep selecting RECORDS, by span as without the mode; every block of a kept record is emitted.
+ * A blocks-mode scan serves FUSED PLANS OF KINDS 12, 13 AND 14 ONLY: exon_hip_stream_consume_scan under any other kind is
+ * EXON_HIP_EUNSUPPORTED before anything is read (kind 11, K3 and K6 count records: a record would count once per block), and so are
+ * exon_hip_scan_next and exon_hip_scan_bind_ctx (batches keep the reference's schema of one row per record).
+ * THE PLANS' FOUR TOTALS COUNT BLOCK ROWS; `rows` of exon_hip_stream_consume_scan and exon_hip_scan_rows keep counting RECORDS, on
+ * both decode paths.  The host readers emit the same block rows as the device stage (cigar_blocks.hip: a count pass, the offsets
+ * scan, a fill pass per slab, the slab's total in one small copy), so gpu_parse = 0, EXON_HIP_GPU_PARSE=0 and every hand-over give
+ * the same state word for word.  DECISIONS: a BAM record whose CIGAR is the two-op placeholder of a CG tag (<l_seq>S<n>N) is an
+ * error that names the tag -- the device leaves it undecided, the host reader reports it -- never zero coverage; a SAM op longer
+ * than 2^28 - 1, an op without a count and a letter outside MIDNSHP=X are `invalid CIGAR '...'` the same way. */
+int exon_hip_scan_set_cover_ops(exon_hip_scan* scan, uint32_t cover_ops);
 /* after the scan has ended: slabs exported by the GPU pipeline, how many of them went through the device take-rows step,
  * bytes copied device -> host for batches (mask / count words included). Any pointer may be NULL. */
 int exon_hip_scan_export_stats(exon_hip_scan* scan, int64_t* slabs, int64_t* compacted_slabs, int64_t* d2h_bytes);
@@ -1168,6 +1226,15 @@ int exon_hip_bam_parser_create(exon_hip_ctx* ctx, int32_t n_references, int64_t 
 /* Synchronises `stream`. */
 int exon_hip_bam_parser_parse(exon_hip_bam_parser* parser, void* stream, const uint8_t* d_data, int64_t n_bytes,
                               exon_hip_bam_columns* cols);
+/* (additive; the ABI stays 5) The aligned blocks of the slab of the LAST exon_hip_bam_parser_parse call of this parser -- d_data,
+ * n_bytes and cols as that call had them -- for a caller that drives the parser itself: what a blocks-mode scan
+ * (exon_hip_scan_set_cover_ops) runs per slab.  Rows, rule, cover_ops and the one shared validity bitmap are exon_hip_cigar_blocks';
+ * d_row_mask (optional, one bit a row, LSB first): a row whose bit is 0 emits one invalid row.  out[0 .. 3) = ref_id (i32), start,
+ * end (i64) of *n_blocks rows, in buffers that belong to the parser (16-byte aligned; overwritten by the next call, freed with the
+ * parser).  Every load is checked against n_bytes again.  *n_undecided != 0: a record beyond the slab, or the CG-tag placeholder;
+ * nothing was produced, decode on the host, whose reader reports what is wrong.  Synchronises `stream`. */
+int exon_hip_bam_parser_cigar_blocks(exon_hip_bam_parser* parser, void* stream, const uint8_t* d_data, int64_t n_bytes, const exon_hip_bam_columns* cols,
+                                     const uint8_t* d_row_mask, uint32_t cover_ops, exon_hip_column* out /*[3]*/, int64_t* n_blocks, int64_t* n_undecided);
 int exon_hip_bam_parser_destroy(exon_hip_bam_parser* parser);
 
 /* ---- SAM text parsing on the GPU (alignment lines in HBM -> the BAM device layout; `cols` is the BAM column struct) ----

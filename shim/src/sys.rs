@@ -40,6 +40,9 @@ pub const EXON_HIP_WINDOW_MAX_BINS: i32 = 33554432;
 pub const EXON_HIP_PLAN_REGION_SET_DEPTH: i32 = 14; // made by exon_hip_plan_create_region_set_depth; state = 4 + T + C words, all add modulo 2^64
 pub const EXON_HIP_REGION_DEPTH_MAX_BINS: i32 = 67108864;
 pub const EXON_HIP_REGION_DEPTH_MAX_THRESHOLDS: i32 = 8;
+/// exon_hip_cigar_blocks' cover_ops: bit i = BAM op code i is covered (M = X; + D)
+pub const EXON_HIP_COVER_ALIGNED: u32 = 0x181;
+pub const EXON_HIP_COVER_ALIGNED_DEL: u32 = 0x185;
 pub const EXON_HIP_GT: i32 = 0;
 pub const EXON_HIP_GE: i32 = 1;
 pub const EXON_HIP_LT: i32 = 2;
@@ -197,6 +200,10 @@ extern "C" {
     pub fn exon_hip_region_depth_reduce(ctx: *mut exon_hip_ctx, stream: *mut c_void, plan: *const exon_hip_plan, d_state: *const i64, d_out: *mut i64) -> c_int;
     /// K14 (bare operator, ids form): per-base depth over the set's bases for one batch; accumulates
     pub fn exon_hip_region_set_depth(ctx: *mut exon_hip_ctx, stream: *mut c_void, ref_id: *const exon_hip_column, start: *const exon_hip_column, end: *const exon_hip_column, n: i64, plan: *const exon_hip_plan, d_state: *mut i64) -> c_int;
+    /// alignment rows + a List<UInt32> of CIGAR ops on the device -> their aligned blocks as interval rows for kinds 12 - 14; synchronous
+    pub fn exon_hip_cigar_blocks(ctx: *mut exon_hip_ctx, stream: *mut c_void, ref_id: *const exon_hip_column, start: *const exon_hip_column, d_cigar_offsets: *const i32, d_cigar_ops: *const u32, n: i64, cover_ops: u32, d_out_ref: *mut i32, d_out_start: *mut i64, d_out_end: *mut i64, d_out_valid: *mut u8, cap: i64, n_blocks: *mut i64) -> c_int;
+    /// host-only: the aligned blocks of one record's ops (len << 4 | code)
+    pub fn exon_hip_cigar_blocks_host(ops: *const u32, n_ops: i32, start: i64, cover_ops: u32, out_start: *mut i64, out_end: *mut i64, cap: i32, n_blocks: *mut i32) -> c_int;
     /// the reference lengths of a BAM / SAM / CRAM header in dictionary-id order: *n of them, the first min(*n, cap) into out
     pub fn exon_hip_scan_reference_lengths(scan: *mut exon_hip_scan, out: *mut i64, cap: i32, n: *mut i32) -> c_int;
     /// fold of `world` packed states by the plan's own layout (add; unsigned max for K8's extreme planes)
@@ -241,6 +248,8 @@ extern "C" {
     /// the flag / mapping-quality predicate of a BAM or SAM scan, evaluated by the scan itself and ANDed with its region: a row is emitted
     /// iff (flag & flag_mask) == flag_value and (mapq_min < 0 or mapping_quality is valid and >= mapq_min); call right after exon_hip_scan_open
     pub fn exon_hip_scan_set_flag_predicate(scan: *mut exon_hip_scan, flag_mask: i32, flag_value: i32, mapq_min: i32) -> c_int;
+    /// blocks mode of a BAM / SAM scan: kinds 12 - 14 get every kept record as its aligned blocks (0 turns it off); call right after exon_hip_scan_open
+    pub fn exon_hip_scan_set_cover_ops(scan: *mut exon_hip_scan, cover_ops: u32) -> c_int;
     /// after the scan has ended: slabs the GPU pipeline exported, how many went through the device take-rows step, bytes copied back
     pub fn exon_hip_scan_export_stats(scan: *mut exon_hip_scan, slabs: *mut i64, compacted_slabs: *mut i64, d2h_bytes: *mut i64) -> c_int;
     pub fn exon_hip_scan_close(scan: *mut exon_hip_scan) -> c_int;
